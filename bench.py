@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the MI355X batched Vorbis (aoTuV) encode path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload = BASELINE.json configs[2]: "1 GPU: full pipe incl. residue VQ on device, 16384 streams, q5 coupled
@@ -18,8 +18,13 @@ the audio seconds of the blocks that came out if that is less (streams falling b
 count as served); the ratio of the two is reported.  Before the W warm-up steps the streams are started up (PRIME
 writes, the first ten with four rounds each, part of the set-up like loading a model: every stream begins with short
 blocks, which would otherwise leave a backlog of rounds for the timed region to drain, and one burst period has to pass
-before as many streams are catching up after a burst as in the steady state).  The per-block path alone (pre-cut long blocks, no front end: the
-§8(a) measurement) is timed in the same run and reported as `per_block_path`.
+before as many streams are catching up after a burst as in the steady state).
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the result line.  --full adds the
+rest: the per-block path alone (pre-cut long blocks, no front end: the §8(a) measurement, reported as
+`per_block_path`), every stage alone (leg `solo`: `roofline`, `stage_solo_ms`), the stage times of the from-PCM leg,
+the MDCT kernel alone, the CPU baseline and the drop-in path (`compat_path`).  --dump-outputs DIR writes the packets of
+the last timed step to DIR/*.npy (inputs are seeded: the same arguments give the same inputs in every run).
 
 Streams shard across ranks with no data-path collective: weak scaling, every rank encodes its own
 16384 streams.  The control path (barrier, max-over-ranks time, work sum) is vorbis_aotuv_lancer_amd/shard.py over
@@ -54,6 +59,7 @@ MIN_ROUNDS = int(os.environ.get("VBM_BENCH_MIN_ROUNDS", "1"))   # from PCM: bloc
                                                                  # buffers decide (more while one is past half full)
 DISTINCT_STEPS = 8              # per-block leg: PCM for this many consecutive blocks per stream is kept in HBM
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_CAP_BYTES = 60 << 20       # --dump-outputs writes at most this much (+ the .npy headers)
 
 # algorithmic HBM bytes per long channel-block and stage
 n = N_LONG // 2
@@ -217,17 +223,50 @@ def load_traffic(ncb):
     return tj.get("hbm_bytes_per_launch", {}), src
 
 
+def dump_packets(out_dir, stream, packetno, nbytes, packets, n_streams, per_row, whole=None):
+    """--dump-outputs: the packets of one step as .npy files (float64; the packet bytes float32).  Rows are sorted by
+    (stream, packet number): which lane of the batch a block ran in is not part of the result.  `packet_bytes` is the
+    valid bytes of every row (nbytes of them) one row after the other.  Should that exceed DUMP_CAP_BYTES, the rows of
+    the streams that fit are written, the streams taken in a fixed, seeded order.  per_row: {name: array with one entry
+    per row}; whole: written as they are."""
+    whole = whole or {}
+    valid = np.clip(nbytes, 0, None).astype(np.int64)
+    row_bytes = 4 * valid + 8 * sum(np.asarray(a).size // max(len(valid), 1) for a in per_row.values())
+    budget = DUMP_CAP_BYTES - 8 * sum(np.asarray(a).size for a in whole.values())
+    order = np.lexsort((packetno, stream))
+    if row_bytes.sum() > budget:
+        seq = np.random.default_rng(0x5EED).permutation(n_streams)
+        fits = np.cumsum(np.bincount(stream, weights=row_bytes, minlength=n_streams)[seq]) <= budget
+        pick = np.zeros(n_streams, bool)
+        pick[seq[fits]] = True
+        order = order[pick[stream[order]]]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in per_row.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a)[order].astype(np.float64))
+    for name, a in whole.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a).astype(np.float64))
+    width = np.arange(packets.shape[1])
+    np.save(os.path.join(out_dir, "packet_bytes.npy"),
+            packets[order][width[None, :] < valid[order][:, None]].astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=48)
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other legs (per-block path, every stage alone -> roofline), the "
+                         "stage times of the from-PCM leg, the MDCT kernel alone, the CPU baseline, the drop-in path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the packets of the headline leg's last timed step to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
     ap.add_argument("--from-pcm", action="store_true", help="(default) value = whole encoder from raw PCM")
     ap.add_argument("--per-block", action="store_true",
                     help="value = the per-block path alone on pre-cut long blocks (the §8(a) measurement; no front "
                          "end, no block switching) — for A/B work on the kernels")
-    ap.add_argument("--only", choices=["pcm", "block", "solo"], default=None, help="run one leg only")
+    ap.add_argument("--only", choices=["pcm", "block", "solo"], default=None,
+                    help="run this leg only (with --full: and its extra timings)")
     ap.add_argument("--bitrate", type=int, default=0,
                     help="managed-bitrate setup of this nominal rate (vorbis_encode_init, SURVEY 8f N2: all 15 "
                          "packetblobs per block) instead of the q5 VBR setup of the headline metric")
@@ -289,7 +328,21 @@ def main():
     traffic, traffic_src = load_traffic(ncb)
     # (the per-block leg first: the front end adds HIP streams; the solo leg last: its encoder's internal streams would
     # change which hardware queues the streams of the timed legs land on — measured: per-block step 3.7 ms instead of 2.8)
-    legs = [args.only] if args.only else ["block", "pcm", "solo"]
+    if args.only:
+        legs = [args.only]
+    elif args.full:
+        legs = ["block", "pcm", "solo"]
+    else:
+        legs = ["block" if args.per_block else "pcm"]
+    dump_leg = "block" if (args.per_block or "pcm" not in legs) else "pcm"     # the headline's leg
+    # HIP streams share the hardware queues (GPU_MAX_HW_QUEUES) in the order they are first used.  The per-block leg's
+    # side stream, the first of torch's stream pool, is made and used here, before any leg, as when that leg ran first
+    # in every run: taken after the front end's streams, the from-PCM step takes 5.4 ms instead of 4.6 (MI355X, 4 queues).
+    side_q = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(side_q):
+        torch.zeros(1, device=dev).add_(1)
+    torch.cuda.synchronize()
+    dump = args.dump_outputs if rank == 0 else None
 
     def barrier():
         shard.barrier()
@@ -393,7 +446,7 @@ def main():
         fe.join()
         torch.cuda.synchronize()
         # warmup is not counted; the timed region starts with a join so that nothing of it is left pending
-        PROF_STEPS = 8
+        PROF_STEPS = 8 if args.full else 0
         nsteps_total = args.warmup + args.steps + PROF_STEPS
         chunks[:] = [synth_pcm(torch, dev, params, gen, (PRIME + k) * HOP, HOP) for k in range(nsteps_total)]   # resident in HBM
         for k in range(args.warmup):
@@ -410,8 +463,24 @@ def main():
         stat["host_enqueue_ms_per_step"] = 1e3 * t_enq / max(args.steps, 1)
         end_stats = fe.device_stats() if DEVICE_ROUNDS else None
         counting[0] = False
-        # stage times: a few more steps with HIP events between the stage kernels (outside the timed region: the
-        # device-built rounds run as HIP graphs, which have no room for events; with timing on they are launched
+        if dump and dump_leg == "pcm":
+            if DEVICE_ROUNDS:
+                info_t, pk_, nb_, counts = kept[-1]
+                live = torch.nonzero(nb_ != -2).flatten()          # -2: a lane no block went to
+                rec = info_t[live].cpu().numpy().view(np.dtype(v.PacketInfo)).reshape(-1)
+                whole = {"round_counts": counts.cpu().numpy()}
+            else:
+                rec, pk_, nb_ = kept[-1]
+                live = torch.arange(len(nb_), device=dev)
+                whole = {}
+            nb = nb_[live].cpu().numpy()
+            pk = pk_[live, :max(int(nb.max()) if len(nb) else 0, 0)].cpu().numpy()
+            stream = rec["stream"].astype(np.int64) + lo
+            info = np.stack([rec[f] for f in rec.dtype.names], axis=1).astype(np.float64)
+            info[:, 0] = stream
+            dump_packets(dump, stream, rec["packetno"], nb, pk, hi, {"packet_info": info, "packet_nbytes": nb}, whole)
+        # stage times (--full): a few more steps with HIP events between the stage kernels (outside the timed region:
+        # the device-built rounds run as HIP graphs, which have no room for events; with timing on they are launched
         # kernel by kernel)
         if os.environ.get("VBM_BENCH_NO_STAGE_PASS"):      # kernel traces of the timed region alone (tools/gpu_pcm_trace.sh)
             PROF_STEPS = 0
@@ -455,7 +524,7 @@ def main():
         del x
         ids = np.arange(S, dtype=np.int32)
         wflags = np.full(S, 3, dtype=np.uint8)   # lW = nW = long
-        back_q = torch.cuda.Stream(device=dev)
+        back_q = side_q
         outs = [(torch.empty((S, enc.max_packet_bytes), dtype=torch.uint8, device=dev),
                  torch.empty((S,), dtype=torch.int32, device=dev)) for _ in range(2)]
         last = [None]
@@ -467,19 +536,25 @@ def main():
                 last[0] = enc.analysis_batch(3, ids, wflags, blocks[k % DISTINCT_STEPS])
 
         dt_local, stage_ms, calls, blocks_prof = timed(step_block)
-        # The MDCT kernel on its own (same launch shape as in the pipeline: one long block of every channel), timed
-        # with HIP events inside the library on this stream: the kernel's own HBM rate.
-        import ctypes as C
-        lk = v.MdctLookup(N_LONG, short_n=N_SHORT)
-        xb = blocks[0].reshape(ncb, N_LONG)
-        y = torch.empty((ncb, N_LONG // 2), device=dev)
-        ms = C.c_float()
-        st_ = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        v.check(v.lib.vbm_window_mdct_time(lk._h, xb.data_ptr(), y.data_ptr(), None, ncb, 3, st_, C.byref(ms)))
-        v.check(v.lib.vbm_window_mdct_time(lk._h, xb.data_ptr(), y.data_ptr(), None, ncb, 20, st_, C.byref(ms)))
+        if dump and dump_leg == "block":
+            nb = last[0][1].cpu().numpy()
+            pk = last[0][0][:, :max(int(nb.max()), 0)].cpu().numpy()
+            stream = ids.astype(np.int64) + lo
+            dump_packets(dump, stream, np.zeros(S), nb, pk, hi, {"packet_stream": stream, "packet_nbytes": nb})
         results["block"] = dict(dt_local=dt_local, stage_ms=stage_ms, calls=calls, blocks_prof=blocks_prof,
-                                audio_local=S * HOP / RATE * args.steps, mdct_alone_ms=ms.value / 20,
-                                mean_bytes=float(last[0][1].float().mean().item()))
+                                audio_local=S * HOP / RATE * args.steps, mean_bytes=float(last[0][1].float().mean().item()))
+        if args.full:
+            # The MDCT kernel on its own (same launch shape as in the pipeline: one long block of every channel), timed
+            # with HIP events inside the library on this stream: the kernel's own HBM rate.
+            import ctypes as C
+            lk = v.MdctLookup(N_LONG, short_n=N_SHORT)
+            xb = blocks[0].reshape(ncb, N_LONG)
+            y = torch.empty((ncb, N_LONG // 2), device=dev)
+            ms = C.c_float()
+            st_ = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            v.check(v.lib.vbm_window_mdct_time(lk._h, xb.data_ptr(), y.data_ptr(), None, ncb, 3, st_, C.byref(ms)))
+            v.check(v.lib.vbm_window_mdct_time(lk._h, xb.data_ptr(), y.data_ptr(), None, ncb, 20, st_, C.byref(ms)))
+            results["block"]["mdct_alone_ms"] = ms.value / 20
 
     # ---- leg "solo": every stage of the per-block path ALONE (one HIP stream, the two mask branches one after the other:
     #      no kernel runs beside another), HIP events between the stages on that stream.  What `roofline` is made of;
@@ -599,7 +674,7 @@ def main():
             "stage_ms_per_step": per_step,
             "stage_ms_per_launch": per_launch,
         }
-        if traffic_src and traffic_src.get("valu_instructions_per_write_from_pcm") and headline == "pcm":
+        if args.full and traffic_src and traffic_src.get("valu_instructions_per_write_from_pcm") and headline == "pcm":
             # What bounds the step is instruction issue, not HBM: vector instructions issued per write (PMC,
             # committed measurement) against what 1024 SIMDs issue per second at one instruction per four cycles
             n_valu = traffic_src["valu_instructions_per_write_from_pcm"]
@@ -646,6 +721,7 @@ def main():
                 "stage_ms_per_step": bstep, "dominant": roof_of(bdom, blaunch[bdom], bcb, traffic),
                 "mean_packet_bytes": B["mean_bytes"],
             }
+        if "block" in results and "mdct_alone_ms" in results["block"]:      # (--full)
             r_mdct = roof_of("window_mdct", blaunch["window_mdct"], bcb, traffic)
             r_mdct["in_pipeline_ms"] = r_mdct["kernel_ms"]
             r_mdct["in_pipeline_frac"] = r_mdct["frac"]
@@ -654,9 +730,9 @@ def main():
             r_mdct["frac"] = r_mdct["achieved"] / HBM_PEAK_GBPS
             r_mdct["note"] = "kernel alone, 20 launches of the step's blocks; in_pipeline_* = beside the previous step's back half"
             line["mdct_roofline"] = r_mdct
-        if not args.no_cpu_baseline and world == 1:   # host baseline: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # host baseline: rank 0 at N = 1 only
             line["cpu_baseline"] = cpu_baseline()
-        if world == 1 and not args.only and not args.bitrate and not os.environ.get("VBM_BENCH_NO_COMPAT"):
+        if args.full and world == 1 and not args.only and not args.bitrate and not os.environ.get("VBM_BENCH_NO_COMPAT"):
             # (outside the headline: what a user of the reference's own API gets; the bench's device objects are gone by now)
             enc.close()
             torch.cuda.synchronize()

@@ -2,7 +2,7 @@
 # A/B of environment knobs on the whole bench: usage: gpu_ab.sh "ENV1=a ENV2=b" "ENV1=c" ...
 cd $GRAFT_REPO_ROOT
 for cfg in "$@"; do
-  env $cfg python3 bench.py --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | python3 -c "
+  env $cfg python3 bench.py --full --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 pb=d.get('per_block_path',{})
