@@ -387,6 +387,64 @@ int vbm_window_mdct_time(const vbm_mdct_plan *plan, const float *d_pcm, float *d
                          const uint8_t *d_wflags, long nblocks, int iters, void *stream,
                          float *ms_total);
 
+/* ---- decode: Vorbis packets -> PCM for many streams -------------------------------------------------------
+ * The decode half of the reference, batched like the encode path.  One call takes one audio packet for each of up to
+ * max_batch streams that share one set of headers and returns, per row, the PCM that became final with that packet:
+ * vorbis_synthesis + vorbis_synthesis_blockin + vorbis_synthesis_pcmout + vorbis_synthesis_read
+ * (reference lib/synthesis.c:25-91, lib/block.c:897-1190; examples/decoder_example.c).
+ * Not supported (VBM_EIMPL at setup): floor type 0, block sizes outside 256..4096, more than 8 channels.  No half-rate
+ * decoding, seeking or chained streams.  The reference's own vorbis_synthesis* names are not exported. */
+#define VBM_ENOTVORBIS (-132) /* OV_ENOTVORBIS, include/vorbis/codec.h:229-233 */
+#define VBM_EBADHEADER (-133) /* OV_EBADHEADER */
+#define VBM_EVERSION   (-134) /* OV_EVERSION   */
+#define VBM_ENOTAUDIO  (-135) /* OV_ENOTAUDIO  */
+#define VBM_EBADPACKET (-136) /* OV_EBADPACKET */
+
+typedef struct vbm_decode_setup vbm_decode_setup;
+typedef struct vbm_decoder vbm_decoder;
+
+/* Host only, no device needed: the three header packets, back to back in `headers` with lengths lens[3] ->
+ * decode setup (vorbis_synthesis_headerin x3, lib/info.c:237-498, and vorbis_book_init_decode).  Returns 0,
+ * VBM_ENOTVORBIS, VBM_EBADHEADER, VBM_EVERSION or VBM_EIMPL. */
+int  vbm_decode_setup_create(vbm_decode_setup **ds, const uint8_t *headers, const long *lens);
+void vbm_decode_setup_destroy(vbm_decode_setup *ds);
+int  vbm_decode_setup_info(const vbm_decode_setup *ds, int *channels, long *rate, int *blocksizes /*[2]*/, int *modes);
+/* counts[4] = books, floors, residues, mappings of the setup header */
+int  vbm_decode_setup_counts(const vbm_decode_setup *ds, int *counts);
+/* Host instance of the device's packet unpack (the same source, csrc/decode.h), for parity tests.  Returns the row
+ * status (0, VBM_ENOTAUDIO, VBM_EBADPACKET).  Outputs, all optional except info:
+ *   info[4]       mode, W, lW, nW
+ *   floor_index   [channels][blocksizes[1]/2] floor line as indices into FLOOR1_fromdB_LOOKUP; 0 on channels whose
+ *                 floor is not coded and beyond blocksizes[W]/2
+ *   residue       [channels][blocksizes[1]/2] decoded residue before inverse coupling, 0 beyond blocksizes[W]/2
+ *   floor_used    [channels] nonzero flag after its propagation over the coupling pairs (mapping0_inverse) */
+int  vbm_host_unpack_packet(const vbm_decode_setup *ds, const uint8_t *packet, long bytes, int *info,
+                            int *floor_index, float *residue, int *floor_used);
+
+/* Device.  nstreams streams of state (previous block size, overlap tail [channels][blocksizes[1]/2], granulepos, sample
+ * count) live on the device.  Without a HIP device: VBM_ENODEV. */
+int  vbm_decoder_create(vbm_decoder **dec, const vbm_decode_setup *ds, int nstreams, int max_batch);
+void vbm_decoder_destroy(vbm_decoder *dec);
+/* every stream back to its initial state (device idle afterwards) */
+int  vbm_decoder_reset(vbm_decoder *dec);
+/* vorbis_synthesis_restart (lib/block.c:814) for n streams, enqueued on `stream` */
+int  vbm_decoder_restart_streams(vbm_decoder *dec, int n, const int *stream_ids /*host*/, void *stream);
+/* One packet for each of nsb streams (ids distinct: duplicates are VBM_EINVAL), enqueued on `stream` (no host
+ * synchronisation).  Row k: d_packets + k*packet_stride, d_packet_bytes[k] bytes, granulepos d_granulepos[k] (NULL:
+ * all -1), end of stream d_eos[k] (NULL: none).  Outputs: d_pcm [nsb][channels][blocksizes[1]/2] floats, d_samples[k]
+ * samples per channel, d_status[k] = 0, VBM_ENOTAUDIO or VBM_EBADPACKET.  A row with an error returns 0 samples and
+ * leaves its stream untouched; the first packet of a stream (or after a restart) returns 0 samples; with granulepos /
+ * eos the output is trimmed as lib/block.c:1084-1161 trims it. */
+int  vbm_synthesis_batch(vbm_decoder *dec, int nsb, const int *stream_ids /*host*/,
+                         const uint8_t *d_packets, long packet_stride, const int *d_packet_bytes,
+                         const long long *d_granulepos, const uint8_t *d_eos,
+                         float *d_pcm, int *d_samples, int *d_status, void *stream);
+/* Intermediates of the LAST call, per row, padded to blocksizes[1]/2 per channel (as vbm_encoder_fetch):
+ *   "info" int [nsb][4]; "floor_index" int, "residue" float, "spectrum" float [nsb][channels][blocksizes[1]/2]
+ *   (spectrum: after inverse coupling and the floor multiply, before the IMDCT); "floor_used" int [nsb][channels].
+ * d_out NULL: only *rows (values per channel row, 4 for "info") and *kind ('i' / 'f') are returned. */
+int  vbm_decoder_fetch(vbm_decoder *dec, const char *name, void *d_out, long *rows, char *kind, void *stream);
+
 /* ---- test instrumentation --------------------------------------------------------------------------------
  * The path is spread over several internal HIP streams; events order them.  These calls make a missing edge show
  * deterministically (tests/test_ordering_gpu.py); they change timing and scratch contents only, never results.

@@ -111,6 +111,21 @@ SIGNATURES = {
     "vbm_debug_poison_frontend": (C.c_int, [C.c_void_p, C.c_int]),
     "vbm_window_mdct_time": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int,
                                        C.c_void_p, C.POINTER(C.c_float)]),
+    "vbm_decode_setup_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_long)]),
+    "vbm_decode_setup_destroy": (None, [C.c_void_p]),
+    "vbm_decode_setup_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int)]),
+    "vbm_decode_setup_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "vbm_host_unpack_packet": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "vbm_decoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int]),
+    "vbm_decoder_destroy": (None, [C.c_void_p]),
+    "vbm_decoder_reset": (C.c_int, [C.c_void_p]),
+    "vbm_decoder_restart_streams": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vbm_synthesis_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vbm_decoder_fetch": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_char),
+                                    C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

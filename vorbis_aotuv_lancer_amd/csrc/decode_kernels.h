@@ -1,0 +1,29 @@
+// internal: launchers of the decode kernels (decode_kernels.hip), used by capi_decoder.cpp
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "decode.h"
+
+// device buffers of one decoder, as the kernels see them (rows: the current call's nsb)
+struct vbmd_launch {
+    const vbmd_setup *s;             // device copy of the setup, the book blob follows it
+    const uint8_t *blob;
+    int nsb, ch;
+    long half, n1;                   // blocksizes[1]/2, blocksizes[1]
+    int *info, *fit, *flags, *status, *lists, *counts;
+    float *res, *spec, *imdct;
+    uint8_t *cls;
+    const float *fromdB, *win0, *win1;
+    float *tail;                     // [streams][ch][half]
+    int *prevW;                      // [streams] -1: no block yet (pcm_returned == -1)
+    long long *gp, *sc;              // [streams] granulepos, sample_count
+};
+
+int vbmd_launch_unpack(const vbmd_launch &L, const uint8_t *packets, long stride, const int *nbytes, int *status_out,
+                       hipStream_t q);
+int vbmd_launch_spectrum(const vbmd_launch &L, float *spec, int *findex, hipStream_t q);
+int vbmd_launch_imdct(const vbmd_launch &L, int W, int N, const float *trig, hipStream_t q);
+int vbmd_launch_overlap(const vbmd_launch &L, const int *ids, const long long *granulepos, const uint8_t *eos,
+                        float *pcm, int *samples, hipStream_t q);
+int vbmd_launch_restart(const int *ids, int n, int *prevW, long long *gp, long long *sc, hipStream_t q);
+int vbmd_launch_used(const int *flags, int *out, long n, hipStream_t q);

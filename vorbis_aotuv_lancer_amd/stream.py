@@ -66,3 +66,80 @@ def write_ogg(setup, packets, infos, serialno=1, comments=()):
     out += os_.pages(flush=True)
     os_.close()
     return b"".join(out)
+
+
+def _crc_table():
+    t = []
+    for i in range(256):
+        r = i << 24
+        for _ in range(8):
+            r = ((r << 1) ^ 0x04C11DB7) & 0xFFFFFFFF if r & 0x80000000 else (r << 1) & 0xFFFFFFFF
+        t.append(r)
+    return t
+
+
+_CRC = _crc_table()
+
+
+def _page_crc(page):
+    crc = 0
+    for b in page:
+        crc = ((crc << 8) & 0xFFFFFFFF) ^ _CRC[((crc >> 24) & 0xFF) ^ b]
+    return crc
+
+
+def read_ogg(data):
+    """.ogg bytes of ONE logical Vorbis stream -> (headers [3 packets], packets, granulepos, eos), the inverse of
+    write_ogg (host only).  Pages are checked for the capture pattern, version and CRC (doc/framing.html); packets
+    are reassembled from the lacing values across pages.  As libogg's ogg_stream_packetout reports them, a packet
+    carries its page's granule position only if it is the last packet that ends on that page (-1 otherwise), and
+    the end-of-stream flag only if it is the last packet of the stream's last page."""
+    import struct
+    data = bytes(data)
+    pos, serial = 0, None
+    out, gps, eoss = [], [], []
+    partial = b""
+    expect_seq = 0
+    while pos < len(data):
+        if data[pos:pos + 4] != b"OggS":
+            raise ValueError(f"no Ogg capture pattern at byte {pos}")
+        if len(data) < pos + 27:
+            raise ValueError("truncated page header")
+        version, flags, granule, sno, seq, crc, nseg = struct.unpack_from("<BBqIIIB", data, pos + 4)
+        if version != 0:
+            raise ValueError(f"unsupported Ogg version {version}")
+        lacing = data[pos + 27:pos + 27 + nseg]
+        body_len = sum(lacing)
+        end = pos + 27 + nseg + body_len
+        if len(lacing) != nseg or end > len(data):
+            raise ValueError("truncated page")
+        page = bytearray(data[pos:end])
+        page[22:26] = b"\0\0\0\0"
+        if _page_crc(page) != crc:
+            raise ValueError(f"CRC mismatch in page {seq}")
+        if serial is None:
+            serial = sno
+        elif sno != serial:
+            raise ValueError("more than one logical stream (chained or multiplexed streams are not supported)")
+        if seq != expect_seq:
+            raise ValueError(f"page {seq} out of sequence (expected {expect_seq})")
+        expect_seq += 1
+        if not (flags & 1) and partial:
+            raise ValueError("a packet continues into a page that is not marked as a continuation")
+        body = data[pos + 27 + nseg:end]
+        bpos, ended = 0, []
+        for lv in lacing:
+            partial += body[bpos:bpos + lv]
+            bpos += lv
+            if lv < 255:
+                ended.append(partial)
+                partial = b""
+        for i, p in enumerate(ended):
+            last = i == len(ended) - 1
+            out.append(p)
+            gps.append(granule if last else -1)
+            eoss.append(bool(flags & 4) and last)
+        pos = end
+    if len(out) < 3:
+        raise ValueError("fewer than three header packets")
+    return out[:3], out[3:], gps[3:], eoss[3:]
