@@ -351,6 +351,19 @@ int vbm_header_packets(const vbm_setup_handle *setup, const char *vendor, const 
                        int ncomments, uint8_t *buf, long cap, long *lens);
 /* The comment header alone (reference vorbis_commentheader_out, lib/info.c:600-617); buf == NULL: size query. */
 int vbm_comment_packet(const char *vendor, const char *const *comments, int ncomments, uint8_t *buf, long cap, long *len);
+/* The inverse, host only: .ogg bytes of ONE logical Vorbis stream -> its packets (libogg's ogg_sync_pageout +
+ * ogg_stream_pagein + ogg_stream_packetout, as the Python read_ogg).  Pages are checked for the capture pattern, version,
+ * CRC, truncation, one serial number, page sequence and the continuation flag: any violation returns VBM_EOGG (message
+ * in vbm_last_error) and nothing past data[n) is read.  sizes[5] = the three header packet lengths, the number of audio
+ * packets, their total bytes.  Size query with headers == NULL; then call again with sizes as returned and
+ *   headers     sizes[0]+sizes[1]+sizes[2] bytes, the header packets back to back
+ *   packets     sizes[4] bytes, the audio packets back to back; offsets [sizes[3]+1] (CSR, offsets[0] = 0)
+ *   granulepos  [sizes[3]] the page's granule position on the last packet that ends on a page, else -1
+ *   eos         [sizes[3]] 1 on the last packet of the end-of-stream page
+ * An unterminated packet at the end of the data is dropped.  Fewer than three packets: VBM_EOGG. */
+#define VBM_EOGG (-1002)
+int vbm_ogg_demux(const uint8_t *data, long n, long *sizes, uint8_t *headers, uint8_t *packets, long long *offsets,
+                  long long *granulepos, uint8_t *eos);
 typedef struct vbm_ogg_stream vbm_ogg_stream;
 int vbm_ogg_stream_create(vbm_ogg_stream **os, int serialno);
 void vbm_ogg_stream_destroy(vbm_ogg_stream *os);
@@ -439,6 +452,23 @@ int  vbm_synthesis_batch(vbm_decoder *dec, int nsb, const int *stream_ids /*host
                          const uint8_t *d_packets, long packet_stride, const int *d_packet_bytes,
                          const long long *d_granulepos, const uint8_t *d_eos,
                          float *d_pcm, int *d_samples, int *d_status, void *stream);
+/* Many packets per stream per call: run r is run_packets[r] (>= 0) consecutive packets of stream stream_ids[r] (ids
+ * distinct), in stream order.  Rows are the runs concatenated, P = sum(run_packets) <= max_batch.  Packets are CSR:
+ * packet k is d_data[d_offsets[k] .. d_offsets[k+1]), clamped to [0, data_bytes) (nothing outside is read);
+ * d_granulepos / d_eos [P] as above.  Outputs: d_pcm [nruns][channels][pcm_stride], run r's PCM contiguous from sample
+ * 0, d_run_samples[r] samples per channel; per packet, d_samples[k] and d_status[k] exactly as vbm_synthesis_batch
+ * reports them.  For any split of a stream's packets into runs and vbm_synthesis_batch calls, the concatenated PCM,
+ * samples and status are bit-for-bit those of one packet per call: the per-stream state (tail, previous block size,
+ * granulepos, sample count) is shared, and vbm_decoder_restart_streams applies between calls of either kind.
+ * Enqueued on `stream`; no host synchronisation (the run table goes through a pinned staging slot, as the ids of
+ * vbm_synthesis_batch).  VBM_EINVAL: a stream id twice or out of range, P > max_batch, a negative count,
+ * pcm_stride < max(run_packets) * blocksizes[1]/2. */
+int  vbm_synthesis_runs(vbm_decoder *dec, int nruns, const int *stream_ids /*host, distinct*/,
+                        const int *run_packets /*host, >= 0*/,
+                        const uint8_t *d_data, const long long *d_offsets /*[P+1]*/, long long data_bytes,
+                        const long long *d_granulepos /*[P] or NULL*/, const uint8_t *d_eos /*[P] or NULL*/,
+                        float *d_pcm, long pcm_stride, int *d_run_samples /*[nruns]*/,
+                        int *d_samples /*[P]*/, int *d_status /*[P]*/, void *stream);
 /* Intermediates of the LAST call, per row, padded to blocksizes[1]/2 per channel (as vbm_encoder_fetch):
  *   "info" int [nsb][4]; "floor_index" int, "residue" float, "spectrum" float [nsb][channels][blocksizes[1]/2]
  *   (spectrum: after inverse coupling and the floor multiply, before the IMDCT); "floor_used" int [nsb][channels].

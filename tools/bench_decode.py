@@ -7,6 +7,10 @@ step inputs are built on the device first; then `--warmup` steps run, and `--ste
 stream each, never synchronised with the host in between) are timed with device events.  Prints one JSON line:
 ms per step, and the streams decoded at 1x realtime (decoded audio seconds / wall seconds).
 
+With --packets-per-call P > 1 the same workload goes through vbm_synthesis_runs instead: each call takes P
+consecutive packets of every stream (P * (warmup + steps) packets per stream are needed: raise --seconds), and the
+result reports ms per call and per packet-step (ms per call / P).  P = 1 (the default) is the one-packet path above.
+
 Per-kernel times: run this under `rocprofv3 --kernel-trace --stats`."""
 import argparse
 import json
@@ -30,7 +34,12 @@ def main():
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--packets-per-call", type=int, default=1,
+                    help="P > 1: P consecutive packets per stream per call through synthesis_runs")
     a = ap.parse_args()
+    P = a.packets_per_call
+    if P < 1:
+        raise SystemExit("--packets-per-call must be at least 1")
 
     import vorbis_aotuv_lancer_amd as v
     from tests.signals import synth_signal
@@ -65,6 +74,8 @@ def main():
     for x in lead:
         x.sort()
     nsteps = a.warmup + a.steps
+    if P > 1:
+        return runs(a, v, dev, setup, lead)
     if min(len(x) for x in lead) < nsteps:
         raise SystemExit(f"need {nsteps} packets per stream, have {min(len(x) for x in lead)}: raise --seconds")
     stride = max(len(p[1]) for x in lead for p in x[:nsteps])
@@ -108,6 +119,65 @@ def main():
         "steps": a.steps, "ms_per_step": ms / a.steps, "realtime_streams": audio_s / (ms / 1e3),
         "packet_bytes_per_step": sum(nbytes_step[a.warmup:]) / a.steps, "status_errors": int(bad),
         "blocksizes": list(ds.blocksizes),
+    }
+    print(json.dumps(res))
+    dec.close()
+    ds.close()
+
+
+def runs(a, v, dev, setup, lead):
+    """the same workload, P packets per stream per call (vbm_synthesis_runs)"""
+    S, K, ch, rate, P = a.streams, a.signals, a.channels, a.rate, a.packets_per_call
+    ncalls = a.warmup + a.steps
+    if S % K:
+        raise SystemExit("--streams must be a multiple of --signals with --packets-per-call > 1")
+    if min(len(x) for x in lead) < P * ncalls:
+        raise SystemExit(f"need {P * ncalls} packets per stream, have {min(len(x) for x in lead)}: raise --seconds")
+    inputs, nbytes_call = [], []
+    for c in range(ncalls):                               # stream s reads lead s % K: the K leads tiled S // K times
+        data, offs, gps, base = [], [np.zeros(1, np.int64)], [], 0
+        for k in range(K):
+            seg = lead[k][c * P:(c + 1) * P]
+            b = b"".join(p[1] for p in seg)
+            data.append(np.frombuffer(b, np.uint8))
+            offs.append(np.cumsum([len(p[1]) for p in seg]).astype(np.int64) + base)
+            gps.append(np.array([p[2] for p in seg], np.int64))
+            base += len(b)
+        one = np.concatenate(data)
+        o1 = np.concatenate(offs)
+        reps = S // K
+        offsets = np.concatenate([np.zeros(1, np.int64)] + [o1[1:] + r * base for r in range(reps)])
+        inputs.append((torch.from_numpy(np.tile(one, reps)).to(dev), torch.from_numpy(offsets).to(dev),
+                       torch.from_numpy(np.tile(np.concatenate(gps), reps)).to(dev)))
+        nbytes_call.append(float(base * reps))
+    ds = v.DecodeSetup(v.header_packets(setup))
+    dec = v.Decoder(ds, S, S * P)
+    half = ds.blocksizes[1] // 2
+    ids = np.arange(S, dtype=np.int32)
+    counts = np.full(S, P, np.int32)
+    pcm = [torch.empty((S, ch, P * half), dtype=torch.float32, device=dev) for _ in range(2)]
+    outs = [(pcm[c % 2], torch.empty(S, dtype=torch.int32, device=dev), torch.empty(S * P, dtype=torch.int32, device=dev),
+             torch.empty(S * P, dtype=torch.int32, device=dev)) for c in range(ncalls)]
+    for c in range(a.warmup):
+        data, offs, gp = inputs[c]
+        dec.synthesis_runs(ids, counts, data, offs, granulepos=gp, out=outs[c])
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for c in range(a.warmup, ncalls):                     # nothing but the decode calls between the events
+        data, offs, gp = inputs[c]
+        dec.synthesis_runs(ids, counts, data, offs, granulepos=gp, out=outs[c])
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1)
+    samples_sum = sum(int(outs[c][1].sum()) for c in range(a.warmup, ncalls))
+    bad = sum(int((outs[c][3] != 0).sum()) for c in range(ncalls))
+    audio_s = samples_sum / rate
+    res = {
+        "metric": "decode_runs_ms", "streams": S, "signals": K, "channels": ch, "rate": rate, "quality": a.quality,
+        "packets_per_call": P, "calls": a.steps, "ms_per_call": ms / a.steps, "ms_per_packet_step": ms / a.steps / P,
+        "realtime_streams": audio_s / (ms / 1e3), "packet_bytes_per_call": sum(nbytes_call[a.warmup:]) / a.steps,
+        "status_errors": int(bad), "blocksizes": list(ds.blocksizes),
     }
     print(json.dumps(res))
     dec.close()

@@ -124,6 +124,11 @@ SIGNATURES = {
     "vbm_decoder_restart_streams": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vbm_synthesis_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vbm_synthesis_runs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "vbm_ogg_demux": (C.c_int, [C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
     "vbm_decoder_fetch": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_char),
                                     C.c_void_p]),
 }

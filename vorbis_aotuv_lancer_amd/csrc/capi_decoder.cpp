@@ -4,6 +4,10 @@
 // k_unpack (entropy decode, row lists by block size), k_spectrum, one k_imdct launch per block size (each reads its row
 // count from the device: rows of mixed block size are never sorted on the host) and k_overlap.  Nothing waits on
 // the device, except a staging slot that is still in flight from four calls back.
+//
+// vbm_synthesis_runs enqueues the same unpack (from CSR offsets), spectrum and IMDCT launches over rows that are runs of
+// consecutive packets of one stream, then k_run_plan, k_overlap_runs and k_run_commit in place of k_overlap.  The run
+// table (stream ids and run starts) goes up through the same staging ring.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -29,15 +33,17 @@ struct vbm_decoder {
     const float *fromdB = nullptr, *win[2] = {}, *trig[2] = {};
     int *d_ids = nullptr, *d_info = nullptr, *d_fit = nullptr, *d_flags = nullptr, *d_status = nullptr;
     int *d_lists = nullptr, *d_counts = nullptr;
+    int *d_runtab = nullptr, *d_plan = nullptr, *d_run_last = nullptr;   // runs: [2S+1], [cap][6], [S]
     float *d_res = nullptr, *d_spec = nullptr, *d_imdct = nullptr;
     uint8_t *d_cls = nullptr;
     float *d_tail = nullptr;
     int *d_prevW = nullptr;
     long long *d_gp = nullptr, *d_sc = nullptr;
-    int *h_stage[kStage] = {};
+    int *h_stage[kStage] = {};       // max(cap, 2S+1) ints each
     hipEvent_t ev_stage[kStage] = {};
     int stage_turn = 0;
     std::vector<uint8_t> seen;
+    std::vector<int> run_start;
     int last_nsb = 0;
 
     vbmd_launch launch(int nsb) const
@@ -76,7 +82,8 @@ void free_decoder(vbm_decoder *d)
 {
     if (!d) return;
     void *bufs[] = {d->d_setup, d->d_tables, d->d_ids, d->d_info, d->d_fit, d->d_flags, d->d_status, d->d_lists,
-                    d->d_counts, d->d_res, d->d_spec, d->d_imdct, d->d_cls, d->d_tail, d->d_prevW, d->d_gp, d->d_sc};
+                    d->d_counts, d->d_res, d->d_spec, d->d_imdct, d->d_cls, d->d_tail, d->d_prevW, d->d_gp, d->d_sc,
+                    d->d_runtab, d->d_plan, d->d_run_last};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     for (int i = 0; i < kStage; i++) {
@@ -86,20 +93,26 @@ void free_decoder(vbm_decoder *d)
     delete d;
 }
 
-// host ids -> d_ids through the next pinned staging slot
-int stage_ids(vbm_decoder *d, const int *ids, int n, hipStream_t q)
+// host ints -> dst (d_ids or d_runtab) through the next pinned staging slot
+int stage_ints(vbm_decoder *d, int *dst, const int *const *parts, const int *lens, int nparts, hipStream_t q)
 {
     const int t = d->stage_turn;
     d->stage_turn = (t + 1) % kStage;
     hipError_t e = hipEventSynchronize(d->ev_stage[t]);      // the copy from kStage calls ago has been done
     if (e != hipSuccess) return vbm_set_hip_error(e, "hipEventSynchronize(stage)");
-    memcpy(d->h_stage[t], ids, (size_t)n * sizeof(int));
-    e = hipMemcpyAsync(d->d_ids, d->h_stage[t], (size_t)n * sizeof(int), hipMemcpyHostToDevice, q);
+    size_t n = 0;
+    for (int i = 0; i < nparts; i++) {
+        memcpy(d->h_stage[t] + n, parts[i], (size_t)lens[i] * sizeof(int));
+        n += (size_t)lens[i];
+    }
+    e = hipMemcpyAsync(dst, d->h_stage[t], n * sizeof(int), hipMemcpyHostToDevice, q);
     if (e != hipSuccess) return vbm_set_hip_error(e, "hipMemcpyAsync(ids)");
     e = hipEventRecord(d->ev_stage[t], q);
     if (e != hipSuccess) return vbm_set_hip_error(e, "hipEventRecord(stage)");
     return VBM_OK;
 }
+
+int stage_ids(vbm_decoder *d, const int *ids, int n, hipStream_t q) { return stage_ints(d, d->d_ids, &ids, &n, 1, q); }
 
 int check_ids(vbm_decoder *d, int n, const int *ids)
 {
@@ -174,8 +187,12 @@ extern "C" int vbm_decoder_create(vbm_decoder **out, const vbm_decode_setup *ds,
     CK(hipMalloc((void **)&d->d_prevW, (size_t)nstreams * sizeof(int)));
     CK(hipMalloc((void **)&d->d_gp, (size_t)nstreams * sizeof(long long)));
     CK(hipMalloc((void **)&d->d_sc, (size_t)nstreams * sizeof(long long)));
+    const size_t runtab = 2 * (size_t)nstreams + 1, stage = cap > runtab ? cap : runtab;
+    CK(hipMalloc((void **)&d->d_runtab, runtab * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_plan, cap * 6 * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_run_last, (size_t)nstreams * sizeof(int)));
     for (int i = 0; i < kStage; i++) {
-        CK(hipHostMalloc((void **)&d->h_stage[i], cap * sizeof(int), hipHostMallocDefault));
+        CK(hipHostMalloc((void **)&d->h_stage[i], stage * sizeof(int), hipHostMallocDefault));
         CK(hipEventCreateWithFlags(&d->ev_stage[i], hipEventDisableTiming));
     }
 #undef CK
@@ -238,6 +255,51 @@ extern "C" int vbm_synthesis_batch(vbm_decoder *d, int nsb, const int *stream_id
         if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W], d->trig[W], q)) return VBM_EHIP;
     if (vbmd_launch_overlap(L, d->d_ids, d_granulepos, d_eos, d_pcm, d_samples, q)) return VBM_EHIP;
     d->last_nsb = nsb;
+    return VBM_OK;
+}
+
+extern "C" int vbm_synthesis_runs(vbm_decoder *d, int nruns, const int *stream_ids, const int *run_packets,
+                                  const uint8_t *d_data, const long long *d_offsets, long long data_bytes,
+                                  const long long *d_granulepos, const uint8_t *d_eos, float *d_pcm, long pcm_stride,
+                                  int *d_run_samples, int *d_samples, int *d_status, void *stream)
+{
+    if (!d || nruns < 0 || (nruns > 0 && (!stream_ids || !run_packets)) || data_bytes < 0 ||
+        (data_bytes > 0 && !d_data) || !d_offsets || !d_run_samples)
+        return VBM_EINVAL;
+    if (nruns == 0) return VBM_OK;
+    if (nruns > d->S) { g_vbm_err = "more runs than streams"; return VBM_EINVAL; }
+    int rc = check_ids(d, nruns, stream_ids);
+    if (rc) return rc;
+    d->run_start.resize((size_t)nruns + 1);
+    long long P = 0;
+    int most = 0;
+    for (int r = 0; r < nruns; r++) {
+        if (run_packets[r] < 0) { g_vbm_err = "negative packet count"; return VBM_EINVAL; }
+        d->run_start[r] = (int)P;
+        P += run_packets[r];
+        if (P > d->cap) { g_vbm_err = "more packets than max_batch in one call"; return VBM_EINVAL; }
+        if (run_packets[r] > most) most = run_packets[r];
+    }
+    d->run_start[nruns] = (int)P;
+    if (P > 0 && (!d_pcm || !d_samples || !d_status)) return VBM_EINVAL;
+    if (pcm_stride < (long)most * d->half) { g_vbm_err = "pcm_stride below max(run_packets) * blocksizes[1]/2"; return VBM_EINVAL; }
+    hipStream_t q = (hipStream_t)stream;
+    const int *parts[2] = {stream_ids, d->run_start.data()};
+    const int lens[2] = {nruns, nruns + 1};
+    if ((rc = stage_ints(d, d->d_runtab, parts, lens, 2, q))) return rc;
+    const int nsb = (int)P;
+    hipError_t e = hipMemsetAsync(d->d_counts, 0, 2 * sizeof(int), q);
+    if (e == hipSuccess) e = hipMemsetAsync(d->d_res, 0, (size_t)nsb * d->ch * d->half * sizeof(float), q);
+    if (e != hipSuccess) return vbm_set_hip_error(e, "hipMemsetAsync(decode runs)");
+    const vbmd_launch L = d->launch(nsb);
+    if (vbmd_launch_unpack_csr(L, d_data, d_offsets, data_bytes, d_status, q)) return VBM_EHIP;
+    if (vbmd_launch_spectrum(L, d->d_spec, nullptr, q)) return VBM_EHIP;
+    for (int W = 0; W < 2; W++)
+        if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W], d->trig[W], q)) return VBM_EHIP;
+    if (vbmd_launch_runs(L, nruns, d->d_runtab, d_granulepos, d_eos, d->d_plan, d->d_run_last, d_pcm, pcm_stride,
+                         d_run_samples, d_samples, q))
+        return VBM_EHIP;
+    if (nsb > 0) d->last_nsb = nsb;
     return VBM_OK;
 }
 

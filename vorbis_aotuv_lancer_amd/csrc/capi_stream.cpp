@@ -14,7 +14,10 @@
 //                        1.3's: the first page holds the first packet alone, later pages close once they carry
 //                        more than 4096 body bytes and at least four packets, at 255 segments, on flush, or at
 //                        the end of the stream.
+//   vbm_ogg_demux        the inverse for one logical stream (read_ogg in stream.py, restated): pages checked, packets
+//                        reassembled from the lacing values, CSR output for vbm_synthesis_runs.
 #include <limits.h>
+#include <new>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -384,6 +387,34 @@ extern "C" int vbm_comment_packet(const char *vendor, const char *const *comment
 }
 
 // ---- Ogg pages (doc/framing.html) -----------------------------------------------------------------
+namespace {
+
+// CRC-32 of a page, polynomial 0x04c11db7, initial value and final XOR 0 (doc/framing.html:363-366)
+struct OggCrc {
+    uint32_t table[256];
+    OggCrc()
+    {
+        for (uint32_t i = 0; i < 256; i++) {
+            uint32_t r = i << 24;
+            for (int k = 0; k < 8; k++) r = (r & 0x80000000u) ? (r << 1) ^ 0x04c11db7u : (r << 1);
+            table[i] = r;
+        }
+    }
+    uint32_t update(uint32_t crc, const uint8_t *p, size_t n) const
+    {
+        for (size_t i = 0; i < n; i++) crc = (crc << 8) ^ table[((crc >> 24) & 0xff) ^ p[i]];
+        return crc;
+    }
+};
+
+const OggCrc &ogg_crc()
+{
+    static const OggCrc c;
+    return c;
+}
+
+}  // namespace
+
 struct vbm_ogg_stream {
     int serialno;
     long pageno = 0;
@@ -394,7 +425,6 @@ struct vbm_ogg_stream {
     std::vector<uint8_t> lacing;      // one value per queued segment
     std::vector<long long> granule;   // granulepos of the packet that ENDS at this segment (else -1)
     std::vector<uint8_t> page;        // last page handed out
-    uint32_t crc_table[256];
 };
 
 extern "C" int vbm_ogg_stream_create(vbm_ogg_stream **out, int serialno)
@@ -402,11 +432,6 @@ extern "C" int vbm_ogg_stream_create(vbm_ogg_stream **out, int serialno)
     if (!out) return VBM_EINVAL;
     vbm_ogg_stream *os = new vbm_ogg_stream();
     os->serialno = serialno;
-    for (uint32_t i = 0; i < 256; i++) {
-        uint32_t r = i << 24;
-        for (int k = 0; k < 8; k++) r = (r & 0x80000000u) ? (r << 1) ^ 0x04c11db7u : (r << 1);
-        os->crc_table[i] = r;
-    }
     *out = os;
     return VBM_OK;
 }
@@ -477,8 +502,7 @@ extern "C" int vbm_ogg_stream_pageout(vbm_ogg_stream *os, int flush, const uint8
     pg[26] = (uint8_t)vals;
     for (int i = 0; i < vals; i++) pg[27 + i] = os->lacing[i];
     memcpy(pg.data() + 27 + vals, os->body.data(), body_bytes);
-    uint32_t crc = 0;
-    for (size_t i = 0; i < pg.size(); i++) crc = (crc << 8) ^ os->crc_table[((crc >> 24) & 0xff) ^ pg[i]];
+    const uint32_t crc = ogg_crc().update(0, pg.data(), pg.size());
     for (int i = 0; i < 4; i++) pg[22 + i] = (uint8_t)((crc >> (8 * i)) & 0xff);
 
     os->body.erase(os->body.begin(), os->body.begin() + body_bytes);
@@ -490,4 +514,122 @@ extern "C" int vbm_ogg_stream_pageout(vbm_ogg_stream *os, int flush, const uint8
     *page = pg.data();
     *bytes = (long)pg.size();
     return 1;
+}
+
+// ---- Ogg demux (the inverse of the page writer, as stream.py's read_ogg) ----------------------------------
+namespace {
+
+struct Demuxed {
+    std::vector<uint8_t> bytes;          // every packet back to back
+    std::vector<long long> off{0}, gp;   // CSR offsets, granulepos
+    std::vector<uint8_t> eos;
+};
+
+inline uint32_t rd32(const uint8_t *p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
+
+int demux_fail(const std::string &msg)
+{
+    g_vbm_err = msg;
+    return VBM_EOGG;
+}
+
+int demux(const uint8_t *data, long n, Demuxed &out)
+{
+    const OggCrc &crc = ogg_crc();
+    static const uint8_t zero4[4] = {0, 0, 0, 0};
+    long pos = 0;
+    bool have_serial = false, partial = false;
+    uint32_t serial = 0, expect_seq = 0;
+    long long packet_begin = 0;           // start of the packet being assembled in out.bytes
+    while (pos < n) {
+        if (n - pos < 4 || memcmp(data + pos, "OggS", 4))
+            return demux_fail("no Ogg capture pattern at byte " + std::to_string(pos));
+        if (n - pos < 27) return demux_fail("truncated page header");
+        const uint8_t *h = data + pos;
+        const int version = h[4], flags = h[5], nseg = h[26];
+        unsigned long long ug = 0;
+        for (int i = 0; i < 8; i++) ug |= (unsigned long long)h[6 + i] << (8 * i);
+        const long long granule = (long long)ug;
+        const uint32_t sno = rd32(h + 14), seq = rd32(h + 18), want = rd32(h + 22);
+        if (version != 0) return demux_fail("unsupported Ogg version " + std::to_string(version));
+        if (n - pos - 27 < nseg) return demux_fail("truncated page");
+        const uint8_t *lacing = h + 27;
+        long body_len = 0;
+        for (int i = 0; i < nseg; i++) body_len += lacing[i];
+        if (n - pos - 27 - nseg < body_len) return demux_fail("truncated page");
+        const long page_len = 27 + nseg + body_len;
+        uint32_t c = crc.update(0, h, 22);
+        c = crc.update(c, zero4, 4);
+        c = crc.update(c, h + 26, (size_t)(page_len - 26));
+        if (c != want) return demux_fail("CRC mismatch in page " + std::to_string(seq));
+        if (!have_serial) {
+            serial = sno;
+            have_serial = true;
+        } else if (sno != serial) {
+            return demux_fail("more than one logical stream (chained or multiplexed streams are not supported)");
+        }
+        if (seq != expect_seq)
+            return demux_fail("page " + std::to_string(seq) + " out of sequence (expected " + std::to_string(expect_seq) + ")");
+        expect_seq++;
+        if (!(flags & 1) && partial) return demux_fail("a packet continues into a page that is not marked as a continuation");
+        const uint8_t *body = h + 27 + nseg;
+        long bpos = 0;
+        int last_end = -1;                // the last packet that ends on this page carries its granule / eos
+        for (int i = 0; i < nseg; i++)
+            if (lacing[i] < 255) last_end = i;
+        for (int i = 0; i < nseg; i++) {
+            const int lv = lacing[i];
+            out.bytes.insert(out.bytes.end(), body + bpos, body + bpos + lv);
+            bpos += lv;
+            partial = true;
+            if (lv < 255) {
+                const bool last = i == last_end;
+                out.off.push_back((long long)out.bytes.size());
+                out.gp.push_back(last ? granule : -1);
+                out.eos.push_back((flags & 4) && last ? 1 : 0);
+                packet_begin = (long long)out.bytes.size();
+                partial = false;
+            }
+        }
+        pos += page_len;
+    }
+    out.bytes.resize((size_t)packet_begin);   // an unterminated packet at the end is dropped
+    if (out.gp.size() < 3) return demux_fail("fewer than three header packets");
+    return VBM_OK;
+}
+
+}  // namespace
+
+extern "C" int vbm_ogg_demux(const uint8_t *data, long n, long *sizes, uint8_t *headers, uint8_t *packets,
+                             long long *offsets, long long *granulepos, uint8_t *eos)
+{
+    if (!sizes || n < 0 || (n > 0 && !data)) return VBM_EINVAL;
+    Demuxed d;
+    try {
+        const int rc = demux(data, n, d);
+        if (rc) return rc;
+    } catch (const std::bad_alloc &) {
+        g_vbm_err = "out of host memory";
+        return VBM_EFAULT;
+    }
+    const long long hbytes = d.off[3], np = (long long)d.gp.size() - 3, pbytes = (long long)d.bytes.size() - hbytes;
+    if (!headers) {
+        for (int i = 0; i < 3; i++) sizes[i] = (long)(d.off[i + 1] - d.off[i]);
+        sizes[3] = (long)np;
+        sizes[4] = (long)pbytes;
+        return VBM_OK;
+    }
+    if (sizes[0] + sizes[1] + sizes[2] < hbytes || sizes[3] < np || sizes[4] < pbytes ||
+        (np > 0 && (!offsets || !granulepos || !eos)) || (pbytes > 0 && !packets) || !offsets) {
+        g_vbm_err = "vbm_ogg_demux: buffers smaller than the size query returned";
+        return VBM_EINVAL;
+    }
+    memcpy(headers, d.bytes.data(), (size_t)hbytes);
+    if (pbytes) memcpy(packets, d.bytes.data() + hbytes, (size_t)pbytes);
+    for (long long k = 0; k <= np; k++) offsets[k] = d.off[3 + k] - hbytes;
+    for (long long k = 0; k < np; k++) {
+        granulepos[k] = d.gp[3 + k];
+        eos[k] = d.eos[3 + k];
+    }
+    return VBM_OK;
 }

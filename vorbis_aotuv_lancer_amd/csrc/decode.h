@@ -308,6 +308,9 @@ VBMD_HD void vbmd_residue_inverse(const vbmd_setup &s, const uint8_t *blob, cons
 //   flags        [channels] bit 0: the channel's floor is coded, bit 1: nonzero after the coupling propagation
 //   res          [channels][stride] residue before inverse coupling; must be zero on entry (bins < blocksize/2 used)
 //   cls          partition-class scratch, s.max_classes bytes
+// Copy: one instantiation per kernel that calls it (k_unpack the default, k_unpack_csr 1), so that each has a single
+// call site and is inlined as it was with one caller, instead of becoming a shared out-of-line function.
+template <int Copy = 0>
 VBMD_HD int vbmd_unpack(const vbmd_setup &s, const uint8_t *blob, const uint8_t *pkt, long bytes, int *info, int *fit,
                         int *flags, float *res, long stride, uint8_t *cls)
 {

@@ -25,5 +25,12 @@ int vbmd_launch_spectrum(const vbmd_launch &L, float *spec, int *findex, hipStre
 int vbmd_launch_imdct(const vbmd_launch &L, int W, int N, const float *trig, hipStream_t q);
 int vbmd_launch_overlap(const vbmd_launch &L, const int *ids, const long long *granulepos, const uint8_t *eos,
                         float *pcm, int *samples, hipStream_t q);
+// runs (vbm_synthesis_runs): CSR unpack; then plan, overlap-add into the runs' PCM and the tail commit.  runtab:
+// stream ids [nruns] and run starts [nruns + 1]; plan: 6 ints per row; run_last: [nruns]
+int vbmd_launch_unpack_csr(const vbmd_launch &L, const uint8_t *data, const long long *offsets, long long data_bytes,
+                           int *status_out, hipStream_t q);
+int vbmd_launch_runs(const vbmd_launch &L, int nruns, const int *runtab, const long long *granulepos,
+                     const uint8_t *eos, int *plan, int *run_last, float *pcm, long pcm_stride, int *run_samples,
+                     int *samples, hipStream_t q);
 int vbmd_launch_restart(const int *ids, int n, int *prevW, long long *gp, long long *sc, hipStream_t q);
 int vbmd_launch_used(const int *flags, int *out, long n, hipStream_t q);

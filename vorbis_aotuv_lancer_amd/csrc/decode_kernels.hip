@@ -9,6 +9,16 @@
 //                 forward kernels (mdct_butterflies.h), one wavefront per 512-complex group
 //   k_overlap     one workgroup per row: vorbis_synthesis_blockin's overlap-add and copy (lib/block.c:897-1166, scalar
 //                 branches), granulepos trimming, vorbis_synthesis_pcmout + _read of everything that became final
+//
+// Runs (vbm_synthesis_runs): rows are runs of consecutive packets of one stream.  k_unpack_csr addresses the packets
+// through CSR offsets; k_spectrum and k_imdct* are the same launches; the serial part of blockin moves into a planning
+// pass and the overlap-add reads the previous packet's IMDCT row instead of the stream's tail:
+//   k_run_plan       one lane per run: walks its rows in order -> per row lW, previous valid row (or the carried
+//                    tail), begin/end (k_overlap's granulepos bookkeeping) and the output offset; the run's final
+//                    prevW / granulepos / sample count and its total samples
+//   k_overlap_runs   one workgroup per row: k_overlap's overlap-add expression into the run's PCM at the planned offset
+//   k_run_commit     one workgroup per run: the last valid row's second half -> the stream's tail (a separate launch:
+//                    the first row of a run reads the tail that this writes)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -37,6 +47,31 @@ void k_unpack(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob
     if (nb < 0) nb = 0;
     const int st = vbmd_unpack(*s, blob, packets + (long)k * stride, nb, info + 4 * k, fit + (long)k * ch * VBMD_POSTS,
                                flags + (long)k * ch, res + (long)k * ch * half, half, cls + (long)k * s->max_classes);
+    status[k] = st;
+    status_out[k] = st;
+    if (st == 0) {
+        const int W = info[4 * k + 1];
+        const int pos = atomicAdd(&counts[W], 1);
+        lists[(long)W * nsb + pos] = k;
+    }
+}
+
+// k_unpack over CSR rows: packet k is data[offsets[k] .. offsets[k+1]), clamped to [0, data_bytes)
+__global__ __launch_bounds__(64)
+void k_unpack_csr(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob, int nsb,
+                  const uint8_t *__restrict__ data, const long long *__restrict__ offsets, long long data_bytes,
+                  int *__restrict__ info, int *__restrict__ fit, int *__restrict__ flags, float *__restrict__ res,
+                  long half, uint8_t *__restrict__ cls, int *__restrict__ status, int *__restrict__ status_out,
+                  int *__restrict__ lists, int *__restrict__ counts)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nsb) return;
+    const int ch = s->channels;
+    long long b = offsets[k], e = offsets[k + 1];
+    b = b < 0 ? 0 : b > data_bytes ? data_bytes : b;
+    e = e < b ? b : e > data_bytes ? data_bytes : e;
+    const int st = vbmd_unpack<1>(*s, blob, data + b, (long)(e - b), info + 4 * k, fit + (long)k * ch * VBMD_POSTS,
+                                  flags + (long)k * ch, res + (long)k * ch * half, half, cls + (long)k * s->max_classes);
     status[k] = st;
     status_out[k] = st;
     if (st == 0) {
@@ -398,6 +433,145 @@ void k_overlap(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict_
     }
 }
 
+// One lane per run.  runtab: ids[nruns], then the run starts [nruns + 1] (rows are the runs concatenated).  Per row:
+// plan[k] = {run, previous valid row of the run (-1: the stream's tail), lW, begin, end, output offset}, and samples[k].
+// The run's final prevW / granulepos / sample count go straight to the stream state: no kernel of this call reads
+// them after this one.  run_last[r]: the run's last valid row (-1: none), for k_run_commit.
+__global__ __launch_bounds__(64)
+void k_run_plan(const vbmd_setup *__restrict__ s, int nruns, const int *__restrict__ runtab,
+                const int *__restrict__ status, const int *__restrict__ info,
+                const long long *__restrict__ granulepos, const uint8_t *__restrict__ eos, int *__restrict__ prevW,
+                long long *__restrict__ st_gp, long long *__restrict__ st_sc, int *__restrict__ plan,
+                int *__restrict__ samples, int *__restrict__ run_samples, int *__restrict__ run_last)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nruns) return;
+    const int sid = runtab[r], k0 = runtab[nruns + r], k1 = runtab[nruns + r + 1];
+    int lW = prevW[sid], prev = -1, off = 0;
+    long long sc = st_sc[sid], gp = st_gp[sid];
+    for (int k = k0; k < k1; k++) {
+        int *pl = plan + 6 * (long)k;
+        if (status[k] != 0) {
+            samples[k] = 0;
+            continue;
+        }
+        const int W = info[4 * k + 1];
+        // k_overlap's bookkeeping, statement for statement
+        long begin = 0, end = 0;
+        if (lW >= 0) end = (s->blocksizes[lW] >> 2) + (s->blocksizes[W] >> 2);
+        const long long vgp = granulepos ? granulepos[k] : -1;
+        const int eof = eos ? eos[k] : 0;
+        const long long step = (lW >= 0 ? (s->blocksizes[lW] >> 2) : 0) + (s->blocksizes[W] >> 2);
+        sc = (sc == -1) ? 0 : sc + step;
+        if (gp == -1) {
+            if (vgp != -1) {
+                gp = vgp;
+                if (sc > gp) {
+                    long long extra = sc - vgp;
+                    if (extra < 0) extra = 0;
+                    if (eof) {
+                        if (extra > end - begin) extra = end - begin;
+                        end -= extra;
+                    } else {
+                        begin += extra;
+                        if (begin > end) begin = end;
+                    }
+                }
+            }
+        } else {
+            gp += step;
+            if (vgp != -1 && gp != vgp) {
+                if (gp > vgp) {
+                    long long extra = gp - vgp;
+                    if (extra && eof) {
+                        if (extra > end - begin) extra = end - begin;
+                        if (extra < 0) extra = 0;
+                        end -= extra;
+                    }
+                }
+                gp = vgp;
+            }
+        }
+        pl[0] = r;
+        pl[1] = prev;
+        pl[2] = lW;
+        pl[3] = (int)begin;
+        pl[4] = (int)end;
+        pl[5] = off;
+        samples[k] = (int)(end - begin);
+        off += (int)(end - begin);
+        prev = k;
+        lW = W;
+    }
+    prevW[sid] = lW;
+    st_gp[sid] = gp;
+    st_sc[sid] = sc;
+    run_samples[r] = off;
+    run_last[r] = prev;
+}
+
+// One workgroup per row: k_overlap's overlap-add, term for term, with the tail read from the previous valid row's
+// IMDCT output (its second half, which is what k_overlap's tail copy would hold) or, for a run's first valid row,
+// from the stream's tail.  Output: the run's PCM [nruns][ch][pcm_stride] at the planned offset.
+__global__ __launch_bounds__(256)
+void k_overlap_runs(const vbmd_setup *__restrict__ s, const int *__restrict__ runtab, const int *__restrict__ status,
+                    const int *__restrict__ info, const int *__restrict__ plan, const float *__restrict__ imdct, long n1,
+                    const float *__restrict__ win0, const float *__restrict__ win1, const float *__restrict__ tail,
+                    float *__restrict__ pcm, long pcm_stride, long half)
+{
+    const int row = blockIdx.x, tid = threadIdx.x;
+    if (status[row] != 0) return;
+    const int *pl = plan + 6 * (long)row;
+    const int run = pl[0], prev = pl[1], lW = pl[2];
+    const long begin = pl[3], end = pl[4], off = pl[5];
+    if (end <= begin) return;                   // lW < 0 (end = 0) included
+    const int ch = s->channels, sid = runtab[run];
+    const int W = info[4 * row + 1];
+    const int bs0 = s->blocksizes[0], bs1 = s->blocksizes[1];
+    const int n0 = bs0 >> 1, nh1 = bs1 >> 1;
+    for (int c = 0; c < ch; c++) {
+        const float *p = imdct + ((long)row * ch + c) * n1;
+        const float *t = prev >= 0 ? imdct + ((long)prev * ch + c) * n1 + (s->blocksizes[lW] >> 1)
+                                   : tail + ((long)sid * ch + c) * half;
+        float *o = pcm + ((long)run * ch + c) * pcm_stride + off;
+        for (long i = begin + tid; i < end; i += blockDim.x) {
+            float v;
+            if (lW == 1 && W == 1) {
+                v = t[i] * win1[nh1 - i - 1] + p[i] * win1[i];
+            } else if (lW == 1) {
+                const long o2 = nh1 / 2 - n0 / 2;
+                if (i < o2) v = t[i];
+                else { const long k = i - o2; v = t[i] * win0[n0 - k - 1] + p[k] * win0[k]; }
+            } else if (W == 1) {
+                const long o2 = nh1 / 2 - n0 / 2;
+                if (i < n0) v = t[i] * win0[n0 - i - 1] + p[o2 + i] * win0[i];
+                else v = p[o2 + i];
+            } else {
+                v = t[i] * win0[n0 - i - 1] + p[i] * win0[i];
+            }
+            o[i - begin] = v;
+        }
+    }
+}
+
+// One workgroup per run: the second half of the run's last valid row -> the stream's tail (k_overlap's tail copy)
+__global__ __launch_bounds__(256)
+void k_run_commit(const vbmd_setup *__restrict__ s, int nruns, const int *__restrict__ runtab,
+                  const int *__restrict__ run_last, const int *__restrict__ info, const float *__restrict__ imdct,
+                  long n1, float *__restrict__ tail, long half)
+{
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int last = run_last[r];
+    if (last < 0) return;
+    const int ch = s->channels, sid = runtab[r];
+    const int n = s->blocksizes[info[4 * last + 1]] >> 1;
+    for (int c = 0; c < ch; c++) {
+        const float *p = imdct + ((long)last * ch + c) * n1;
+        float *t = tail + ((long)sid * ch + c) * half;
+        for (int i = tid; i < n; i += blockDim.x) t[i] = p[n + i];
+    }
+}
+
 __global__ void k_restart(const int *__restrict__ ids, int n, int *__restrict__ prevW, long long *__restrict__ gp,
                           long long *__restrict__ sc)
 {
@@ -481,5 +655,33 @@ int vbmd_launch_used(const int *flags, int *out, long n, hipStream_t q)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(k_used, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, flags, out, n);
+    return last_err();
+}
+
+int vbmd_launch_unpack_csr(const vbmd_launch &L, const uint8_t *data, const long long *offsets, long long data_bytes,
+                           int *status_out, hipStream_t q)
+{
+    if (L.nsb <= 0) return 0;
+    hipLaunchKernelGGL(k_unpack_csr, dim3((L.nsb + 63) / 64), dim3(64), 0, q, L.s, L.blob, L.nsb, data, offsets,
+                       data_bytes, L.info, L.fit, L.flags, L.res, L.half, L.cls, L.status, status_out, L.lists,
+                       L.counts);
+    return last_err();
+}
+
+int vbmd_launch_runs(const vbmd_launch &L, int nruns, const int *runtab, const long long *granulepos,
+                     const uint8_t *eos, int *plan, int *run_last, float *pcm, long pcm_stride, int *run_samples,
+                     int *samples, hipStream_t q)
+{
+    if (nruns <= 0) return 0;
+    hipLaunchKernelGGL(k_run_plan, dim3((nruns + 63) / 64), dim3(64), 0, q, L.s, nruns, runtab, L.status, L.info,
+                       granulepos, eos, L.prevW, L.gp, L.sc, plan, samples, run_samples, run_last);
+    if (last_err()) return -2;
+    if (L.nsb > 0) {
+        hipLaunchKernelGGL(k_overlap_runs, dim3(L.nsb), dim3(256), 0, q, L.s, runtab, L.status, L.info, plan, L.imdct,
+                           L.n1, L.win0, L.win1, L.tail, pcm, pcm_stride, L.half);
+        if (last_err()) return -2;
+        hipLaunchKernelGGL(k_run_commit, dim3(nruns), dim3(256), 0, q, L.s, nruns, runtab, run_last, L.info, L.imdct,
+                           L.n1, L.tail, L.half);
+    }
     return last_err();
 }

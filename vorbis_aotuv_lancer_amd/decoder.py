@@ -4,11 +4,12 @@ the reference's application loop does per packet: vorbis_synthesis + vorbis_synt
 vorbis_synthesis_pcmout + vorbis_synthesis_read (reference examples/decoder_example.c).  Every step from the packet
 bytes to the PCM runs in gfx950 kernels; there is no CPU fallback."""
 import ctypes as C
+import os
 
 import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import lib, check, VbmError
 
 ENOTVORBIS, EBADHEADER, EVERSION, ENOTAUDIO, EBADPACKET = -132, -133, -134, -135, -136
 
@@ -114,6 +115,46 @@ class Decoder:
         self._last = (nsb, dev, packets, nbytes, gp, eo)     # inputs stay alive until the work has run
         return pcm, samples, status
 
+    def synthesis_runs(self, stream_ids, counts, data, offsets, granulepos=None, eos=None, pcm_stride=None, out=None):
+        """Many packets per stream: run r is counts[r] consecutive packets of stream stream_ids[r] (host ints; ids
+        distinct), rows are the runs concatenated (P = sum(counts) <= max_batch).  data: uint8 [bytes] and offsets:
+        int64 [P+1] on the device (CSR: packet k is data[offsets[k]:offsets[k+1]]); granulepos int64 [P] / eos uint8
+        [P] or None.  pcm_stride defaults to max(counts) * blocksizes[1]//2.
+        -> (pcm float32 [nruns, channels, pcm_stride], run_samples int32 [nruns], samples int32 [P],
+        status int32 [P]), device tensors; run r's PCM is pcm[r, :, :run_samples[r]].  Bit-identical to one packet per
+        call through synthesis_batch.  Only enqueues work on the current stream."""
+        ids = np.ascontiguousarray(np.asarray(stream_ids, dtype=np.int32))
+        cnt = np.ascontiguousarray(np.asarray(counts, dtype=np.int32))
+        if ids.shape != cnt.shape or ids.ndim != 1:
+            raise ValueError("stream_ids and counts must be 1-D and of the same length")
+        nruns, P = len(ids), int(cnt.sum())
+        dev = offsets.device
+        assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
+        offsets = offsets.to(torch.int64).contiguous()
+        if offsets.numel() != P + 1:
+            raise ValueError(f"offsets must have sum(counts) + 1 = {P + 1} entries, has {offsets.numel()}")
+        half = self.blocksizes[1] // 2
+        if pcm_stride is None:
+            pcm_stride = max(1, int(cnt.max(initial=0)) * half)
+        if out is None:
+            pcm = torch.empty((nruns, self.channels, pcm_stride), dtype=torch.float32, device=dev)
+            run_samples = torch.empty(nruns, dtype=torch.int32, device=dev)
+            samples = torch.empty(P, dtype=torch.int32, device=dev)
+            status = torch.empty(P, dtype=torch.int32, device=dev)
+        else:
+            pcm, run_samples, samples, status = out
+            pcm_stride = pcm.stride(1)
+        gp = granulepos.to(torch.int64).contiguous() if granulepos is not None else None
+        eo = eos.to(torch.uint8).contiguous() if eos is not None else None
+        check(lib.vbm_synthesis_runs(self._h, nruns, ids.ctypes.data, cnt.ctypes.data, data.data_ptr(),
+                                     offsets.data_ptr(), data.numel(), gp.data_ptr() if gp is not None else None,
+                                     eo.data_ptr() if eo is not None else None, pcm.data_ptr(), pcm_stride,
+                                     run_samples.data_ptr(), samples.data_ptr(), status.data_ptr(), self._stream()),
+              "vbm_synthesis_runs")
+        if P:
+            self._last = (P, dev, data, offsets, gp, eo)      # inputs stay alive until the work has run
+        return pcm, run_samples, samples, status
+
     def fetch(self, name):
         """Intermediate of the last call: "info" [nsb, 4], "floor_used" [nsb, ch], "floor_index" / "residue" /
         "spectrum" [nsb, ch, blocksizes[1]//2]."""
@@ -152,3 +193,85 @@ class Decoder:
             self.close()
         except Exception:
             pass
+
+
+def decode_ogg(files, max_packets=4096):
+    """.ogg files (bytes or paths), one logical stream each -> [(pcm float32 [channels, n] contiguous on the current
+    device, rate)], one per file.  Files whose identification and setup headers are byte-equal share one DecodeSetup
+    and Decoder, one stream per file; their packets go through synthesis_runs in calls of at most max_packets rows.
+    Packets that fail to decode are skipped (as the reference's decoder_example.c skips them).  Waits for the device
+    once, at the end, to place the outputs."""
+    from .stream import demux_ogg
+    if max_packets <= 0:
+        raise ValueError("max_packets must be positive")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    names, demuxed, groups = [], [], {}
+    for i, f in enumerate(files):
+        names.append(os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}")
+        if isinstance(f, (str, os.PathLike)):
+            with open(f, "rb") as fh:
+                f = fh.read()
+        try:
+            d = demux_ogg(f)
+        except VbmError as e:
+            raise VbmError(f"{names[i]}: {e}") from None
+        demuxed.append(d)
+        groups.setdefault((d[0][0], d[0][2]), []).append(i)
+    for members in groups.values():                       # every setup is checked before any work is enqueued
+        rc = DecodeSetup.status(demuxed[members[0]][0])
+        if rc:
+            raise VbmError(f"{names[members[0]]}: unsupported or invalid Vorbis headers (code {rc}): "
+                           f"{lib.vbm_last_error().decode()}")
+    pieces = [[] for _ in files]                          # per file: (pcm [channels, stride] view, index into lens)
+    lens, keep, rates, nlens = [], [], [0] * len(files), 0
+    for members in groups.values():
+        ds = DecodeSetup(demuxed[members[0]][0])
+        dec = Decoder(ds, len(members), max_packets)
+        keep.append((ds, dec))
+        half = ds.blocksizes[1] // 2
+        src = [(torch.from_numpy(demuxed[j][1]).to(dev), demuxed[j][2], torch.from_numpy(demuxed[j][3]).to(dev),
+                torch.from_numpy(demuxed[j][4]).to(dev)) for j in members]
+        pos = [0] * len(members)
+        while True:
+            live = [s for s in range(len(members)) if pos[s] < len(src[s][1]) - 1]
+            if not live:
+                break
+            share, budget = max(1, max_packets // len(live)), max_packets
+            ids, counts = [], []
+            for s in live:                                # the row budget in equal shares over the unfinished streams
+                c = min(len(src[s][1]) - 1 - pos[s], share, budget)
+                if c <= 0:
+                    break
+                ids.append(s)
+                counts.append(c)
+                budget -= c
+            datas, offs, gps, eoss, base = [], [np.zeros(1, np.int64)], [], [], 0
+            for s, c in zip(ids, counts):
+                data, o, gp, eo = src[s]
+                a, b = int(o[pos[s]]), int(o[pos[s] + c])
+                datas.append(data[a:b])
+                offs.append(o[pos[s] + 1:pos[s] + c + 1] - a + base)
+                gps.append(gp[pos[s]:pos[s] + c])
+                eoss.append(eo[pos[s]:pos[s] + c])
+                base += b - a
+                pos[s] += c
+            pcm, run_samples, _, _ = dec.synthesis_runs(
+                ids, counts, torch.cat(datas), torch.from_numpy(np.concatenate(offs)).to(dev),
+                granulepos=torch.cat(gps), eos=torch.cat(eoss), pcm_stride=max(counts) * half)
+            for r, s in enumerate(ids):
+                pieces[members[s]].append((pcm[r], nlens + r))
+            lens.append(run_samples)
+            nlens += len(ids)
+        for j in members:
+            rates[j] = ds.rate
+            if not pieces[j]:
+                pieces[j].append((torch.zeros((ds.channels, 0), dtype=torch.float32, device=dev), None))
+    n = torch.cat(lens).cpu().tolist() if lens else []   # the one wait for the device
+    out = []
+    for j in range(len(files)):
+        parts = [p if k is None else p[:, :n[k]] for p, k in pieces[j]]
+        out.append((torch.cat(parts, dim=1).contiguous(), rates[j]))
+    for ds, dec in keep:
+        dec.close()
+        ds.close()
+    return out

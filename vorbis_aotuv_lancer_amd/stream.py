@@ -3,6 +3,8 @@ vorbis_analysis_headerout (reference lib/info.c:636-717) and libogg's ogg_stream
 (page format: reference doc/framing.html) over the C ABI of include/vorbis_mi355x.h."""
 import ctypes as C
 
+import numpy as np
+
 from ._lib import lib, check
 
 
@@ -143,3 +145,24 @@ def read_ogg(data):
     if len(out) < 3:
         raise ValueError("fewer than three header packets")
     return out[:3], out[3:], gps[3:], eoss[3:]
+
+
+def demux_ogg(data):
+    """read_ogg in C (vbm_ogg_demux), with the packets in CSR form for Decoder.synthesis_runs: .ogg bytes of ONE
+    logical Vorbis stream -> (headers [3 packets], data uint8 [bytes], offsets int64 [P+1], granulepos int64 [P],
+    eos uint8 [P]) as numpy arrays; audio packet k is data[offsets[k]:offsets[k+1]].  The same pages are rejected
+    (VbmError instead of ValueError)."""
+    raw = bytes(data)
+    buf = (C.c_ubyte * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
+    sizes = (C.c_long * 5)()
+    check(lib.vbm_ogg_demux(buf, len(raw), sizes, None, None, None, None, None), "vbm_ogg_demux")
+    hdr = np.zeros(max(1, sizes[0] + sizes[1] + sizes[2]), np.uint8)
+    body = np.zeros(sizes[4], np.uint8)
+    offsets = np.zeros(sizes[3] + 1, np.int64)
+    gp = np.zeros(sizes[3], np.int64)
+    eos = np.zeros(sizes[3], np.uint8)
+    check(lib.vbm_ogg_demux(buf, len(raw), sizes, hdr.ctypes.data, body.ctypes.data if len(body) else None,
+                            offsets.ctypes.data, gp.ctypes.data, eos.ctypes.data), "vbm_ogg_demux")
+    h = hdr.tobytes()
+    headers = [h[:sizes[0]], h[sizes[0]:sizes[0] + sizes[1]], h[sizes[0] + sizes[1]:sizes[0] + sizes[1] + sizes[2]]]
+    return headers, body, offsets, gp, eos
