@@ -105,14 +105,6 @@ struct vbm_batch {
     int blob_pw_rows, blob_m6_rows, blob_len_rows;
     uint64_t *vqcodeT_blob;         // blob k at + k * vq_blob_words
     size_t vq_blob_words;
-    // Fused packet assembly (k_pack_fused, pack_kernels.hip): one wavefront per stream-block, codewords in LDS.  Setups with
-    // one residue submap whose channels form ONE coded vector (stereo coupled res2, mono) on the lane-per-bin couple kernel.
-    int noise_ring;                 // k_noisemask keeps its running sums in a 512-row ring (host-checked window reaches, configure())
-    int pack_fused;                 // the batch takes that path (host decision, configure())
-    int *res_bm;                    // [nsb][n * ch] quantised residue as the residue coder reads it: bin-interleaved channels
-                                    //   (work[x] = in[x % ch][x / ch], lib/res0.c:781-787), written by k_couple_fast
-                                    //   instead of the tiled iworkT rows when pack_fused
-                                    // packetT then holds ROWS: [sb][max_packet_bytes], only the packet's own bytes written
     int pack_submaps;               // residue submaps of this block type and their partition counts (host copy)
     int pack_partvals[16];
     int pack_spp[16];               // samples per partition (residue grouping) of each submap

@@ -310,7 +310,6 @@ extern "C" int vbm_encoder_create(vbm_encoder **out, vbm_setup_handle *setup, in
     A(b.mdct_bm, float, L * nmax);
     A(b.logfft_bm, float, L * nmax);
     A(b.qf_bm, uint16_t, L * nmax);
-    A(b.res_bm, int, L * nmax);
     A(b.local_ampmax, float, L);
     A(b.wflags_cb, uint8_t, L);
     // tiled slabs (batch.h): every per-bin array of a 64-lane tile sits in one contiguous slab
@@ -522,15 +521,7 @@ static void configure(vbm_encoder *e, vbm_batch &b, int block_mode, int nsb, con
         const int posts = s->floor[mp.floorsubmap[mp.chmuxlist[c]]].posts;
         if (posts > b.fit_max_posts) b.fit_max_posts = posts;
     }
-    b.mix_makes_qf = getenv("VBM_SEPARATE_FLOOR_PREP") ? 0 : vbm_mix_can_make_qf(&b);
-    {
-        // opt-in (VBM_NOISE_RING=1): measured slower than the plain form — alone 0.93 ms against 0.73, from PCM 5.10 ms per
-        // step against 4.51 (profiles/r03/README.md): a barrier per 64-bin chunk puts the scan's chunk on every iteration's
-        // critical path, and seven workgroups of five wavefronts per CU do not make up for it
-        const char *rv = getenv("VBM_NOISE_RING");      // (read per call: the tests switch it inside one process)
-        const int ring = rv ? atoi(rv) : 0;
-        b.noise_ring = ring && s->psy[block_mode].hy_ring;
-    }
+    b.mix_makes_qf = vbm_mix_can_make_qf(&b);
     {
         // partition slicing of couple/quantise (quant_kernels.hip): allowed when no channel takes part
         // in two coupling steps; lowpass rounding as lib/mapping0.c:778-781
@@ -552,25 +543,9 @@ static void configure(vbm_encoder *e, vbm_batch &b, int block_mode, int nsb, con
         if (b.couple_parts > b.n / 8 + 1) b.couple_parallel = 0;   // table rows were sized for partitions >= 8 bins
         // lane-per-bin kernel (quant_kernels.hip, k_couple_fast): 32-bin partitions only
         b.couple_fast = 0;
-        if (partition == 32 && p.normal_partition == 32 && (b.n % 32) == 0 && !getenv("VBM_COUPLE_GENERAL")) {
+        if (partition == 32 && p.normal_partition == 32 && (b.n % 32) == 0) {
             if (m.coupling_steps == 0) b.couple_fast = 1;
             else if (m.coupling_steps == 1 && e->ch == 2 && b.couple_parallel) b.couple_fast = 2;
-        }
-        // fused packet assembly: one submap, its channels one coded vector, couple kernel = the lane-per-bin one (it writes
-        // the residue in the coder's own order).  Opt-in (VBM_PACK_FUSED=1): it moves 0.2 GB per step instead of 0.9, issues
-        // the same vector instructions as the three-kernel path (136 M against 150 M per step: the cascaded VQ is ~100
-        // instructions per vector either way) and holds 21 KB of LDS per stream-block while it does — a wavefront of the
-        // lane-per-block kernels holds 8 KB for 64 of them — which keeps the other half of the pipeline off the CUs:
-        // pack alone 0.80 ms against 0.64, from PCM 4.81 ms per step against 4.67.
-        {
-            const char *pf = getenv("VBM_PACK_FUSED");      // (read per call: the tests switch it inside one process)
-            const int want = pf ? atoi(pf) : 0;
-            const vbm_residue &r0 = s->residue[m.residuesubmap[0]];
-            const int nbch = e->ch;
-            b.pack_fused = want && !s->managed && m.submaps == 1 && b.couple_fast &&
-                           ((r0.type == 2 && (r0.grouping % nbch) == 0 && (r0.begin % nbch) == 0) || e->ch == 1) &&
-                           r0.end <= b.n * nbch && r0.phrase_dim >= 1 && r0.phrase_dim <= 8 &&
-                           (r0.end - r0.begin) / r0.grouping <= 64;     // a lane per partition
         }
         b.pack_submaps = m.submaps;
         for (int i = 0; i < m.submaps && i < 16; i++) {
@@ -592,7 +567,7 @@ static vbm_batch slice_of(const vbm_batch &f, int sb0, int nsb, uint8_t *d_packe
     v.nsb = nsb;
     v.ncb = nsb * f.ch;
     v.stream_id += sb0; v.wflags += sb0;
-    v.pcm += cb0 * f.N; v.mdct_bm += cb0 * f.n; v.logfft_bm += cb0 * f.n; v.qf_bm += cb0 * f.n; v.res_bm += cb0 * f.n;
+    v.pcm += cb0 * f.N; v.mdct_bm += cb0 * f.n; v.logfft_bm += cb0 * f.n; v.qf_bm += cb0 * f.n;
     v.local_ampmax += cb0; v.wflags_cb += cb0; v.poste += cb0; v.post_valid += cb0; v.nonzero += cb0;
     v.post_valid_blob += cb0; v.nonzero_blob += cb0;
     v.global_ampmax += sb0; v.packet_bytes += sb0; v.packet_bits += sb0; v.packet_bits_blob += sb0;
@@ -632,34 +607,23 @@ static int managed_front(const vbm_batch &v, hipStream_t q)
 // touches state carried from block to block: bm_avg_reservoir / bm_minmax_reservoir / bm_avgfloat of the streams)
 static int managed_back(const vbm_batch &v, uint8_t *d_packets, hipStream_t q, const std::function<int()> &before_choose = nullptr)
 {
-    const char *wv = getenv("VBM_MANAGED_WIDE");        // (read per call: the tests switch it inside one process)
-    const int wide = wv ? atoi(wv) : 1;
-    if (wide) {
-        // all fifteen packetblobs per launch (blob = blockIdx.z); the blobs' coupling passes form a chain through the npeak
-        // rows (lib/mapping0.c:1249-1260, lib/psy.c:5100-5108): the lane-per-bin kernel walks them in a loop of its own, the
-        // general kernel is launched once per blob
-        vbm_batch f = v;
-        f.nblobs = VBM_PACKETBLOBS;
-        vbm_blob_select(f, 0);
-        if (vbm_launch_floor_encode(&f, q)) return -2;
-        if (f.couple_fast) {
-            if (vbm_launch_couple_quantize(&f, q)) return -2;
-        } else {
-            for (int k = 0; k < VBM_PACKETBLOBS; k++) {
-                vbm_batch g = v;
-                vbm_blob_select(g, k);
-                if (vbm_launch_couple_quantize(&g, q)) return -2;
-            }
+    // all fifteen packetblobs per launch (blob = blockIdx.z); the blobs' coupling passes form a chain through the npeak
+    // rows (lib/mapping0.c:1249-1260, lib/psy.c:5100-5108): the lane-per-bin kernel walks them in a loop of its own, the
+    // general kernel is launched once per blob
+    vbm_batch f = v;
+    f.nblobs = VBM_PACKETBLOBS;
+    vbm_blob_select(f, 0);
+    if (vbm_launch_floor_encode(&f, q)) return -2;
+    if (f.couple_fast) {
+        if (vbm_launch_couple_quantize(&f, q)) return -2;
+    } else {
+        for (int k = 0; k < VBM_PACKETBLOBS; k++) {
+            vbm_batch g = v;
+            vbm_blob_select(g, k);
+            if (vbm_launch_couple_quantize(&g, q)) return -2;
         }
-        if (vbm_launch_pack(&f, q)) return -2;
-        if (before_choose && before_choose()) return -2;
-        return vbm_launch_bitrate_choose(&v, d_packets, q);
     }
-    for (int k = 0; k < VBM_PACKETBLOBS; k++) {
-        vbm_batch f = v;
-        vbm_blob_select(f, k);
-        if (vbm_launch_floor_encode(&f, q) || vbm_launch_couple_quantize(&f, q) || vbm_launch_pack(&f, q)) return -2;
-    }
+    if (vbm_launch_pack(&f, q)) return -2;
     if (before_choose && before_choose()) return -2;
     return vbm_launch_bitrate_choose(&v, d_packets, q);
 }
@@ -810,10 +774,6 @@ extern "C" int vbm_analysis_batch2(vbm_encoder *e, int block_mode, int nsb, cons
             STAGE(10, q, RUN(vbm_launch_pack(&v, q)));
         }
         STAGE(11, q, {
-            if (v.pack_fused) {
-                RUN(vbm_launch_packets_out(&v, d_packets ? d_packets + (size_t)sb0 * e->max_packet_bytes : nullptr,
-                                           d_packet_bytes ? d_packet_bytes + sb0 : nullptr, q));
-            } else {
             if (d_packets && !s->managed)   // word-major tiles -> [nsb][max_packet_bytes] bytes (little-endian words)
                 RUN(vbm_launch_untranspose_i32((const int *)v.packetT,
                                                (int *)(d_packets + (size_t)sb0 * e->max_packet_bytes),
@@ -822,7 +782,6 @@ extern "C" int vbm_analysis_batch2(vbm_encoder *e, int block_mode, int nsb, cons
             if (d_packet_bytes) {
                 if ((err = hipMemcpyAsync(d_packet_bytes + sb0, v.packet_bytes, v.nsb * sizeof(int), hipMemcpyDeviceToDevice, q)) != hipSuccess)
                     return vbm_set_hip_error(err, "hipMemcpyAsync(packet_bytes)");
-            }
             }
         });
         return 0;
@@ -936,22 +895,11 @@ static int enqueue_job(vbm_encoder *e, const type_job &j)
                 return vbm_set_hip_error(err, "hipStreamWaitEvent");
     if (!j.grouped) vbm_debug_delay_point(VBM_DP_JOB_STATE, q);
     { TIMED(3, q); RUN(vbm_launch_prologue(&v, q)); }
-    // the long-block batch of a round: tone mask (log spectrum + the prologue's maxima) beside the noise mask (MDCT) on a
-    // second stream, as in the two-stream form (vbm_analysis_batch2); under a stream capture the fork and the join become
-    // edges of the graph.  One such batch is enqueued at a time (rounds are built one after the other): aux[0] is its own.
-    static const int round_branches = getenv("VBM_ROUND_BRANCHES") ? atoi(getenv("VBM_ROUND_BRANCHES")) : 0;   // measured: from PCM 5.04 ms per step with, 4.58 without (the two LDS-heavy kernels side by side crowd out the back half of the round before) — off
-    if (round_branches && e->overlap_branches && !e->aux.empty() && m == 3 && !j.few && (j.big || (j.grouped && j.part == 1))) {
-        hipStream_t qa = e->aux[0];
-        if ((err = hipEventRecord(e->ev_aux_fork[0], q)) != hipSuccess || (err = hipStreamWaitEvent(qa, e->ev_aux_fork[0], 0)) != hipSuccess)
-            return vbm_set_hip_error(err, "tone-mask branch fork");
-        { TIMED(5, qa); RUN(vbm_launch_tonemask(&v, s->psy[v.block_mode].total_octave_lines, qa)); }
-        if ((err = hipEventRecord(e->ev_aux_join[0], qa)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-        { TIMED(4, q); RUN(vbm_launch_noisemask(&v, q)); }
-        if ((err = hipStreamWaitEvent(q, e->ev_aux_join[0], 0)) != hipSuccess) return vbm_set_hip_error(err, "tone-mask branch join");
-    } else {
+    // noise mask, then tone mask, on one stream.  With the tone mask of the long-block batch on a second stream beside the
+    // noise mask (as in vbm_analysis_batch2) the step from PCM measured 5.04 ms against 4.58: the two LDS-heavy kernels side
+    // by side crowd out the back half of the round before (profiles/r03/README.md).
     { TIMED(4, q); RUN(vbm_launch_noisemask(&v, q)); }
     { TIMED(5, q); RUN(vbm_launch_tonemask(&v, s->psy[v.block_mode].total_octave_lines, q)); }
-    }
     { TIMED(6, q);
       if (s->managed) RUN(managed_front(v, q));
       else { RUN(vbm_launch_mix(&v, q)); RUN(vbm_launch_block_state(&v, q)); } }
@@ -986,13 +934,7 @@ static int enqueue_job(vbm_encoder *e, const type_job &j)
     }
     if (j.grouped) return VBM_OK;     // the group's caller copies the outputs and records the events
     vbm_debug_delay_point(VBM_DP_JOB_OUT, q);
-    { TIMED(11, q);
-      if (v.pack_fused) RUN(vbm_launch_packets_out(&v, j.d_packets, j.d_packet_bytes, q));
-      else {
-      if (j.d_packets && !s->managed)
-          RUN(vbm_launch_untranspose_counted((const int *)v.packetT, (int *)j.d_packets, e->max_packet_bytes / 4,
-                                             (size_t)(e->max_packet_bytes / 4) * 64, v.nsb, v.d_nsb, q));
-      if (j.d_packet_bytes) RUN(vbm_launch_copy_counted(j.d_packet_bytes, v.packet_bytes, v.nsb, v.d_nsb, q)); } }
+    { TIMED(11, q); RUN(vbm_launch_packets_out(&v, s->managed ? nullptr : j.d_packets, j.d_packet_bytes, q)); }
 #undef TIMED
     if ((err = hipEventRecord(e->ev_done[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
     return VBM_OK;
@@ -1007,11 +949,7 @@ static int copy_outputs(vbm_encoder *e, const type_job &j, hipStream_t q)
     vbm_batch v = slice_of(full, j.lane0, j.bound);
     v.d_nsb = j.d_nsb;
     if (e->hs->managed) return VBM_OK;   // (managed_back delivers the chosen packets itself)
-    if (v.pack_fused) { RUN(vbm_launch_packets_out(&v, j.d_packets, j.d_packet_bytes, q)); return VBM_OK; }
-    if (j.d_packets)
-        RUN(vbm_launch_untranspose_counted((const int *)v.packetT, (int *)j.d_packets, e->max_packet_bytes / 4,
-                                           (size_t)(e->max_packet_bytes / 4) * 64, v.nsb, v.d_nsb, q));
-    if (j.d_packet_bytes) RUN(vbm_launch_copy_counted(j.d_packet_bytes, v.packet_bytes, v.nsb, v.d_nsb, q));
+    RUN(vbm_launch_packets_out(&v, j.d_packets, j.d_packet_bytes, q));
     return VBM_OK;
 }
 #undef RUN
@@ -1272,16 +1210,14 @@ int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, 
 // A group of a round as a graph: `jobs` (grouped type_jobs) forked from and joined to `origin`; several jobs run side
 // by side on sub[job.m].  First use: plain launches (the launchers' one-time set-up runs then); second use: the
 // same calls under a stream capture, instantiated; from then on one hipGraphLaunch.
-static int run_group(vbm_encoder *e, vbm_encoder::round_graph &g, hipStream_t origin, type_job *jobs, int njobs, int kind = 0)
+static int run_group(vbm_encoder *e, vbm_encoder::round_graph &g, hipStream_t origin, type_job *jobs, int njobs)
 {
     hipError_t err;
-    static int mask = -1;
-    if (mask < 0) mask = getenv("VBM_GRAPH_MASK") ? atoi(getenv("VBM_GRAPH_MASK")) : 7;   // debugging: bit 0 small groups, 1 big front, 2 big back
     if (g.exec) {
         if ((err = hipGraphLaunch(g.exec, origin)) != hipSuccess) return vbm_set_hip_error(err, "hipGraphLaunch");
         return VBM_OK;
     }
-    const bool capture = e->use_graphs == 1 && g.uses >= 1 && ((mask >> kind) & 1);   // (use_graphs 2: the groups as plain launches, for A/B)
+    const bool capture = e->use_graphs == 1 && g.uses >= 1;   // (use_graphs 2: the groups as plain launches, for A/B)
     g.uses++;
     if (capture && (err = hipStreamBeginCapture(origin, hipStreamCaptureModeThreadLocal)) != hipSuccess)
         return vbm_set_hip_error(err, "hipStreamBeginCapture");
@@ -1368,13 +1304,13 @@ static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, cons
         type_job jf = job_of(3, 1), jb = job_of(3, 2);
         vbm_debug_stamp(qF, 10);
         vbm_debug_delay_point(VBM_DP_DEV_BIG_FRONT, qF);
-        if ((rc = run_group(e, e->gJ[w][4][1], qF, &jf, 1, 1))) return rc;
+        if ((rc = run_group(e, e->gJ[w][4][1], qF, &jf, 1))) return rc;
         vbm_debug_stamp(qF, 11);
         if ((err = hipEventRecord(e->ev_state_big[w], qF)) != hipSuccess ||
             (err = hipStreamWaitEvent(qB, e->ev_state_big[w], 0)) != hipSuccess) return vbm_set_hip_error(err, "big batch hand-over");
         vbm_debug_stamp(qB, 12);
         vbm_debug_delay_point(VBM_DP_DEV_BIG_BACK, qB);
-        if ((rc = run_group(e, e->gJ[w][4][2], qB, &jb, 1, 2))) return rc;
+        if ((rc = run_group(e, e->gJ[w][4][2], qB, &jb, 1))) return rc;
         vbm_debug_delay_point(VBM_DP_DEV_OUT, qB);
         if ((rc = copy_outputs(e, jb, qB))) return rc;
         vbm_debug_stamp(qB, 13);
@@ -1396,10 +1332,10 @@ static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, cons
         j.few = j2.few = 1;
         vbm_debug_stamp(q, 20 + m);
         vbm_debug_delay_point(VBM_DP_DEV_SMALL_FRONT, q);
-        if ((rc = run_group(e, e->gJ[w][m][1], q, &j, 1, 0))) return rc;
+        if ((rc = run_group(e, e->gJ[w][m][1], q, &j, 1))) return rc;
         if ((err = hipEventRecord(e->ev_state[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
         vbm_debug_delay_point(VBM_DP_DEV_SMALL_BACK, q);
-        if ((rc = run_group(e, e->gJ[w][m][2], q, &j2, 1, 0))) return rc;
+        if ((rc = run_group(e, e->gJ[w][m][2], q, &j2, 1))) return rc;
         vbm_debug_delay_point(VBM_DP_DEV_OUT, q);
         if ((rc = copy_outputs(e, j2, q))) return rc;
         vbm_debug_stamp(q, 30 + m);
@@ -1675,12 +1611,6 @@ extern "C" int vbm_encoder_fetch(vbm_encoder *e, const char *name, void *d_out, 
         {"floor_out", b.floor_outT, VBM_VIF_POSIT + 2, 'i', b.ncb},
         {"residue", b.iworkT, b.n, 'i', b.ncb},
     };
-    if (b.pack_fused && !strcmp(name, "residue")) {   // the couple kernel wrote the coder's interleaved order (res_bm), not the tiles
-        if (rows_out) *rows_out = b.n;
-        if (kind) *kind = 'i';
-        if (!d_out) return VBM_OK;
-        return vbm_launch_res_bm_rows(&b, (int *)d_out, st) ? VBM_EHIP : VBM_OK;
-    }
     for (const Ent &t : table) {
         if (strcmp(t.name, name)) continue;
         if (rows_out) *rows_out = t.rows < 0 ? b.n : t.rows;

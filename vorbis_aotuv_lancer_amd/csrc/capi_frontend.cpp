@@ -95,9 +95,6 @@ extern "C" void vbm_frontend_destroy(vbm_frontend *fe)
 static int fe_enter(vbm_frontend *fe, void *stream)
 {
     hipError_t err;
-    static int skip = -1;
-    if (skip < 0) skip = getenv("VBM_DEBUG_NO_ENTER") ? 1 : 0;   // timing experiments only
-    if (skip) return VBM_OK;
     if ((err = hipEventRecord(fe->ev_in, (hipStream_t)stream)) != hipSuccess ||
         (err = hipStreamWaitEvent(fe->q, fe->ev_in, 0)) != hipSuccess) return vbm_set_hip_error(err, "front end stream hand-over");
     return VBM_OK;

@@ -15,12 +15,11 @@
 // them as one 16-bit word (quantised level | test << 15) in BLOCK-major rows qf_bm[channel-block][n]
 // (tile transpose through LDS).  The fit walks data-dependent bin ranges (inspect_error), so each
 // lane reads its own row: consecutive bins of a lane share cache lines, which the bin-major tiles
-// cannot offer.  k_floor_fit runs `lpw` lanes per wavefront (launch parameter) to put more
-// wavefronts in flight than ncb/64.
+// cannot offer.  k_floor_fit runs `lpw` lanes per wavefront (launch parameter; vbm_launch_floor_fit
+// passes 64).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include <type_traits>
 #include "batch.h"
 #include "kernels.h"
 
@@ -77,24 +76,16 @@ __device__ __forceinline__ int dBquant(float x)
     return i;
 }
 
-// accumulate_fit's ten sums per post segment (fields: xa ya x2a xya an xb yb x2b xyb bn), either in the lane's
-// private memory or in LDS ([segment * 10 + field][lane]: conflict-free).  The greedy loop re-reads them in
-// every fit_line (two per split), a chain of dependent loads: from LDS they come back in tens of cycles
-// instead of a scratch round trip.
+// accumulate_fit's ten sums per post segment (fields: xa ya x2a xya an xb yb x2b xyb bn), in the lane's private
+// memory.  (A form with the sums in LDS was measured and removed: DESIGN.md 4.)
 struct fits_private {
     int v[(VBM_VIF_POSIT + 1) * 10];
     __device__ __forceinline__ int get(int seg, int f) const { return v[seg * 10 + f]; }
     __device__ __forceinline__ void set(int seg, int f, int x) { v[seg * 10 + f] = x; }
 };
-struct fits_lds {
-    int *p;   // base + lane
-    __device__ __forceinline__ int get(int seg, int f) const { return p[(seg * 10 + f) * 64]; }
-    __device__ __forceinline__ void set(int seg, int f, int x) { p[(seg * 10 + f) * 64] = x; }
-};
 
 // fit_line over segments [seg0, seg0 + fits) (lib/floor1.c:477-535); x0 / x1 are the outer posts of the range
-template <typename Store>
-__device__ __forceinline__ int fit_line(const Store &S, const int *__restrict__ sorted_index, int seg0, int fits, int *y0, int *y1,
+__device__ __forceinline__ int fit_line(const fits_private &S, const int *__restrict__ sorted_index, int seg0, int fits, int *y0, int *y1,
                                         const float twofitweight)
 {
     double xb = 0, yb = 0, x2b = 0, xyb = 0, bn = 0;
@@ -196,10 +187,8 @@ __global__ void k_floor_prep(vbm_batch b)
     }
 }
 
-template <bool LDS>
 __global__ void k_floor_fit(vbm_batch b, int lpw)
 {
-    extern __shared__ int fit_lds[];   // LDS: [(posts - 1) * 10][64]
     const int lane = blockIdx.x * lpw + threadIdx.x;
     if ((int)threadIdx.x >= lpw || lane >= vbm_ncb(b)) return;
     const size_t tb = (size_t)(lane >> 6) * b.slab_words + (lane & 63);
@@ -222,8 +211,7 @@ __global__ void k_floor_fit(vbm_batch b, int lpw)
     int i, j;
     int nonzero = 0;
 
-    typename std::conditional<LDS, fits_lds, fits_private>::type fits;
-    if constexpr (LDS) fits.p = fit_lds + threadIdx.x;
+    fits_private fits;
     int fit_valueA[VBM_VIF_POSIT + 2];
     int fit_valueB[VBM_VIF_POSIT + 2];
     int loneighbor[VBM_VIF_POSIT + 2];
@@ -568,7 +556,7 @@ __device__ __forceinline__ void fit_line2(const fitgrp &G, const short *__restri
     yb0 = __shfl(o0, gbase + 8); yb1 = __shfl(o1, gbase + 8); retb = __shfl(ret, gbase + 8);
 }
 
-__global__ __launch_bounds__(64) void k_floor_fit_coop(vbm_batch b, const int pmax, const int phases)   // phases: timing experiments (31 = all)
+__global__ __launch_bounds__(64) void k_floor_fit_coop(vbm_batch b, const int pmax)
 {
     extern __shared__ int fitc_lds[];
     const int lane64 = (int)threadIdx.x, g = lane64 >> 4, l = lane64 & 15, gbase = g << 4;
@@ -613,7 +601,6 @@ __global__ __launch_bounds__(64) void k_floor_fit_coop(vbm_batch b, const int pm
         const int lastp = sorted_index[posts - 1];
         const int top = (lastp < n - 1) ? lastp : n - 1;          // last bin any segment holds
         int sp = -1;                                              // posts strictly below the lane's current piece, less one
-        if (phases & 1)
         for (int c8 = l; (c8 << 3) <= top; c8 += FG) {
             const int i0 = c8 << 3;
             const uint4 v = *reinterpret_cast<const uint4 *>(row + i0);
@@ -698,7 +685,6 @@ __global__ __launch_bounds__(64) void k_floor_fit_coop(vbm_batch b, const int pm
     if (l == 0) { G.A[0] = (short)y0; G.B[0] = (short)y0; G.B[1] = (short)y1; G.A[1] = (short)y1; }
     fit_lds_sync();
 
-    if (phases & 2)
     for (int i = 2; i < posts; i++) {
         const int sortpos = reverse_index[i];
         const int ln = G.lo[sortpos], hn = G.hi[sortpos];
@@ -727,7 +713,7 @@ __global__ __launch_bounds__(64) void k_floor_fit_coop(vbm_batch b, const int pm
                 }
             }
             const int xlo = lx + 1, xhi = hx - 1;
-            if (xlo <= xhi && (phases & 4)) {
+            if (xlo <= xhi) {
                 const int blast = xhi >> 3;
                 for (int c8 = (xlo >> 3) + l; c8 <= blast; c8 += FG) {
                     const uint4 v = *reinterpret_cast<const uint4 *>(row + (c8 << 3));
@@ -765,7 +751,7 @@ __global__ __launch_bounds__(64) void k_floor_fit_coop(vbm_batch b, const int pm
             else split = 0;
         }
 
-        if (split && (phases & 8)) {
+        if (split) {
             int ly0 = -200, ly1 = -200, hy0 = -200, hy1 = -200, ret0 = 0, ret1 = 0;
             fit_line2(G, sorted_index, l, gbase, lsortpos, sortpos - lsortpos, sortpos, hsortpos - sortpos, ly0, ly1, hy0, hy1,
                       ret0, ret1, twofitweight);
@@ -810,7 +796,6 @@ __global__ __launch_bounds__(64) void k_floor_fit_coop(vbm_batch b, const int pm
     fit_lds_sync();
     for (int k = l; k < posts; k += FG) out[k] = (k < 2) ? (short)post_Y(G.A, G.B, k) : (short)0;
     fit_lds_sync();
-    if (phases & 16)
     for (int pass = 0; pass < posts; pass++) {
         int nv[(VBM_VIF_POSIT + 2 + FG - 1) / FG];
         int changed = 0;
@@ -1043,33 +1028,17 @@ extern "C" int vbm_launch_floor_fit(const vbm_batch *b, hipStream_t st)
     // a fit keeps 5 of 16 lanes busy).  The step is bound by instruction issue, not by any one kernel's latency
     // (DESIGN.md 4), so the full-size batch is faster with the lean kernel (per-block step 2.80 ms against 3.00,
     // from PCM 4.80 against 4.94), and the cooperative one serves the small batches, whose chain of kernels is what a
-    // stream inside a run of short blocks waits for.  VBM_FLOORFIT_COOP: 0 never, 1 small batches (default), 2 always.
-    static const int coop = getenv("VBM_FLOORFIT_COOP") ? atoi(getenv("VBM_FLOORFIT_COOP")) : 1;
-    // "Small": up to 8192 channel-blocks (VBM_FLOORFIT_COOP_MAX) — the rounds of a 4096-stream pool of the drop-in shim are
-    // that size: 27.3-27.9 k streams at 1x through the reference's entry points against 25.2-25.7 k with the limit at 4096;
-    // the from-PCM step of the batched boundary does not notice (its small batches carry the `few` flag anyway).
-    static const int coop_max = getenv("VBM_FLOORFIT_COOP_MAX") ? atoi(getenv("VBM_FLOORFIT_COOP_MAX")) : 128 * 64;
-    if (coop == 2 || (coop == 1 && (b->few || b->ncb <= coop_max))) {
+    // stream inside a run of short blocks waits for.
+    // "Small": up to 8192 channel-blocks — the rounds of a 4096-stream pool of the drop-in shim are that size: 27.3-27.9 k
+    // streams at 1x through the reference's entry points against 25.2-25.7 k with the limit at 4096; the from-PCM step of
+    // the batched boundary does not notice (its small batches carry the `few` flag anyway).
+    if (b->few || b->ncb <= 128 * 64) {
         const int pmax = b->fit_max_posts;
         const size_t lds = (size_t)4 * (((pmax - 1) * 10 + ((10 * pmax + 1) >> 1) + 1) & ~1) * sizeof(int);
-        static const int phases = getenv("VBM_FLOORFIT_PHASES") ? atoi(getenv("VBM_FLOORFIT_PHASES")) : 31;   // timing experiments
-        hipLaunchKernelGGL(k_floor_fit_coop, dim3((unsigned)((b->ncb + 3) / 4)), dim3(64), lds, st, *b, pmax, phases);
+        hipLaunchKernelGGL(k_floor_fit_coop, dim3((unsigned)((b->ncb + 3) / 4)), dim3(64), lds, st, *b, pmax);
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
-    static const int lpw = [] {
-        const char *e = getenv("VBM_FLOORFIT_LPW");   // tuning knob: lanes per wavefront of the greedy fit
-        const int v = e ? atoi(e) : 64;
-        return (v < 1 || v > 64) ? 64 : v;
-    }();
-    size_t lds = (size_t)(b->fit_max_posts - 1) * 10 * 64 * sizeof(int);
-    static const int force = getenv("VBM_FLOORFIT_LDS") ? 1 : 0;
-    static const bool allowed = hipFuncSetAttribute(reinterpret_cast<const void *>(k_floor_fit<true>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
-    (void)allowed;
-    if (lds <= 80 * 1024 && lpw == 64 && (force || (coop == 0 && (b->few || b->ncb <= 64 * 64))) && !getenv("VBM_FLOORFIT_PRIVATE"))
-        hipLaunchKernelGGL(k_floor_fit<true>, dim3((unsigned)((b->ncb + 63) / 64)), dim3(64), lds, st, *b, 64);
-    else
-        hipLaunchKernelGGL(k_floor_fit<false>, dim3((unsigned)((b->ncb + lpw - 1) / lpw)), dim3(64), 0, st, *b, lpw);
+    hipLaunchKernelGGL(k_floor_fit, dim3((unsigned)((b->ncb + 63) / 64)), dim3(64), 0, st, *b, 64);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 extern "C" int vbm_launch_floor_interp(const vbm_batch *b, hipStream_t st)

@@ -785,12 +785,7 @@ static inline dim3 grid_for(int lanes) { return dim3((unsigned)((lanes + 63) / 6
 // slices of the bin range for the kernels whose bins are independent (long blocks: 64 bins each)
 static inline int bin_chunks(const vbm_batch *b)
 {
-    static const int big = [] {
-        const char *e = getenv("VBM_BIN_CHUNKS");   // tuning knob: slices of the long-block bin range
-        const int v = e ? atoi(e) : 16;
-        return (v < 1 || v > 64) ? 16 : v;
-    }();
-    const int chunks = b->n >= 1024 ? big : b->n >= 512 ? 8 : b->n >= 256 ? 4 : 2;
+    const int chunks = b->n >= 1024 ? 16 : b->n >= 512 ? 8 : b->n >= 256 ? 4 : 2;
     // A small batch (the short rounds of the front end: a few wavefronts on an empty chip) is bound by the
     // latency of each wavefront's walk over its bins, not by throughput: slices of 8-16 bins instead of 64.
     if (b->few || b->ncb <= 1024) {

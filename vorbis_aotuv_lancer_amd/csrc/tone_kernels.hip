@@ -99,7 +99,7 @@ __device__ __forceinline__ void chase_run(const unsigned short *__restrict__ gl,
 
 // TM_NB channel-blocks per workgroup, 32 threads per block
 template <int TM_NB>
-__global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int phases, const int runin)   // phases: timing experiments (31 = all)
+__global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int runin)
 {
     constexpr int TM_THREADS = TM_NB * 32;
     extern __shared__ __align__(16) int tm_lds[];
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int 
     __syncthreads();
 
     // ---- stamp ------------------------------------------------------------------------------------------
-    if (phases & 1) {
+    {
         const int ngroups = p->ngroups;
         const int4 *__restrict__ group_tab = (const int4 *)p->group_tab;
         const float *__restrict__ tonecurves = p->tonecurves;
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int 
     // 8 x 13 comparisons; a line at a time it was 8 reads and the index arithmetic per line: 44 M of the kernel's 209 M
     // vector instructions per launch, rocprofv3 SQ_INSTS_VALU with the phase switched off), the eight results go out as
     // one 16-byte store (the rows are 8-line aligned: glp is a multiple of 8, the row's base a multiple of 32 bytes).
-    if (phases & 2) {
+    {
         const int ngrp = (tn + 7) >> 3;
         int cblk = 0, cg = tid;
         for (int item = tid; item < nblk * ngrp; item += TM_THREADS, cg += TM_THREADS) {
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int 
     __syncthreads();
 
     // ---- chase: 16 lanes per block, 64 lines each --------------------------------------------------------------
-    if (phases & 4) {
+    {
         const int blk = tid / TM_CHUNKS, c = tid % TM_CHUNKS;      // threads [0, 16 NB): the first half of the workgroup
         const int own = c * 64;
         const bool active = blk < nblk && own < tn;
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int 
     __syncthreads();
 
     // ---- fill: wavefront w takes blocks w, w + 4, ...; lane = line within a 64-line chunk ------------------------
-    if (phases & 8) {
+    {
         const int wave = tid >> 6, lane = tid & 63;
         for (int blk = wave; blk < nblk; blk += TM_THREADS / 64) {
             float *sd = seedF + blk * tnp;
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int 
     __syncthreads();
 
     // ---- apply: tone[i] = max(ath[i] + att, min over the bin's seed segment) -----------------------------------
-    if (phases & 16) {
+    {
         const int blk = tid % TM_NB, r0 = tid / TM_NB;
         if (blk < nblk) {
             const int cb = cb0 + blk;
@@ -346,15 +346,11 @@ __global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int 
 }
 
 template <int NB>
-int launch(const vbm_batch *b, int tn, size_t lds, int phases, hipStream_t st)
+int launch(const vbm_batch *b, int tn, size_t lds, hipStream_t st)
 {
-    // (launchers are called from several host threads at once — one per block type of a round: one-time set-up goes
-    // through initialisers of function-local statics, which C++ runs once, and the LDS limit only ever grows)
-    static const int runin = [] {
-        int r = getenv("VBM_TONE_RUNIN") ? atoi(getenv("VBM_TONE_RUNIN")) : 16;
-        r = (r + 3) & ~3;
-        return (r < 8 || r > 64) ? 16 : r;
-    }();
+    // (launchers are called from several host threads at once — one per block type of a round: the LDS limit only
+    // ever grows, under a lock)
+    const int runin = 16;
     {
         static std::mutex mu;
         static size_t allowed = 0;
@@ -365,7 +361,7 @@ int launch(const vbm_batch *b, int tn, size_t lds, int phases, hipStream_t st)
             allowed = lds;
         }
     }
-    hipLaunchKernelGGL(k_tonemask<NB>, dim3((unsigned)((b->ncb + NB - 1) / NB)), dim3(NB * 32), lds, st, *b, phases, runin);
+    hipLaunchKernelGGL(k_tonemask<NB>, dim3((unsigned)((b->ncb + NB - 1) / NB)), dim3(NB * 32), lds, st, *b, runin);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -377,12 +373,9 @@ size_t lds_bytes(int nb, int tn) { return (size_t)(nb * (tn | 1)) * 4 + (size_t)
 extern "C" int vbm_launch_tonemask(const vbm_batch *b, int tn, hipStream_t st)
 {
     if (tn > TM_CHUNKS * 64 || tn < 2) return -2;
-    static const int phases = getenv("VBM_TONE_PHASES") ? atoi(getenv("VBM_TONE_PHASES")) : 31;
     // 8 blocks per workgroup (256 threads, ~38 KB of LDS).  Measured on MI355X, 16384 stereo streams: alone the kernel
     // takes the same 0.7 ms with 8, 16 or 32 blocks per workgroup, but beside the noise-mask branch and the previous
     // step's back half (MDCT, couple and residue-VQ workgroups want LDS too) the step takes 3.07 / 3.19 / 3.22 ms
     // (round 3, four blocks per workgroup: per-block step 2.93 against 2.91, from PCM 4.83-5.02 against 4.67-4.71).
-    static const int force = getenv("VBM_TONE_NB") ? atoi(getenv("VBM_TONE_NB")) : 8;
-    if (force == 16) return launch<16>(b, tn, lds_bytes(16, tn), phases, st);
-    return launch<8>(b, tn, lds_bytes(8, tn), phases, st);
+    return launch<8>(b, tn, lds_bytes(8, tn), st);
 }
