@@ -6,7 +6,6 @@
 // (reference lib/analysis.c:29-63, lib/bitrate.c:88-96, :229-252, VBR) for `nsb` blocks of the same
 // block type, one per stream.  Kernel order = mapping0_forward (lib/mapping0.c:738-1322).
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <functional>
@@ -107,10 +106,9 @@ struct vbm_encoder {
     round_graph gJ[kMaxWS][5][3];
     hipEvent_t ev_state_big[kMaxWS] = {};  // front half of the big batch run in the workspace
     int queue_last_w[4] = {-1, -1, -1, -1};   // workspace of the newest job on sub[0..3]
-    bool small_streams_set = false, small_share = false;
+    bool small_streams_set = false;
     hipEvent_t ev_cap_fork = nullptr, ev_cap_join[4] = {};
     int *d_counts_ws = nullptr;            // [kMaxWS][4] block counts of the round in each workspace
-    int use_graphs = -1;
     int device_mode = 0;                   // how the last device-built round ran: 1 graphs, 2 plain launches
     bool device_rounds = false;            // ... have run: the per-stream bookkeeping below knows nothing of them
     // the tone-mask branch of a slice runs on its own stream beside the noise-mask branch
@@ -148,6 +146,8 @@ struct stage_scope {
         }
     }
 };
+// a launcher's nonzero return: the launch failed
+#define RUN(x) do { if (x) { g_vbm_err = std::string("launch failed: ") + #x; return VBM_EHIP; } } while (0)
 static const int kBigBatch = 1024;   // stream-blocks from which a round's batch counts as big (own stream; front end holds its streams)
 
 template <typename T>
@@ -179,7 +179,6 @@ extern "C" void vbm_encoder_destroy(vbm_encoder *e)
         if (e->ev_cap_join[i]) (void)hipEventDestroy(e->ev_cap_join[i]);
     for (hipEvent_t ev : e->events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ev_join) (void)hipEventDestroy(ev);
-    if (e->small_share && e->sub.size() >= 4) { e->sub[1] = nullptr; e->sub[3] = nullptr; }   // (aliases of sub[0] / sub[2])
     for (hipStream_t q : e->sub)
         if (q) (void)hipStreamDestroy(q);
     for (hipStream_t q : e->aux) (void)hipStreamDestroy(q);
@@ -558,9 +557,8 @@ static void configure(vbm_encoder *e, vbm_batch &b, int block_mode, int nsb, con
 
 // slice [sb0, sb0+nsb) of a configured batch; sb0 is a multiple of 64, so every tiled array starts on
 // a tile boundary (channel-block tiles as well: 64*ch channel-blocks)
-static vbm_batch slice_of(const vbm_batch &f, int sb0, int nsb, uint8_t *d_packets_unused = nullptr)
+static vbm_batch slice_of(const vbm_batch &f, int sb0, int nsb)
 {
-    (void)d_packets_unused;
     vbm_batch v = f;
     const size_t cb0 = (size_t)sb0 * f.ch;
     const size_t ct = cb0 >> 6, stl = (size_t)sb0 >> 6;
@@ -626,6 +624,90 @@ static int managed_back(const vbm_batch &v, uint8_t *d_packets, hipStream_t q, c
     if (vbm_launch_pack(&f, q)) return -2;
     if (before_choose && before_choose()) return -2;
     return vbm_launch_bitrate_choose(&v, d_packets, q);
+}
+
+// ---- the stages of one batch (kStageNames), for vbm_analysis_batch2 and the rounds (enqueue_job) ----------------------
+// Each stage goes to the stream it is given, bracketed by a stage_scope when `timed`; the caller picks the streams and
+// places the forks, joins and waits around the groups.
+
+// spread flags, then loop A: window + MDCT (stage 0) and window + FFT + log spectrum (stage 1), a wave per block.  They
+// read the blocks' PCM only.  (Stage 2, "transpose", is gone: k_noisemask writes the tiled MDCT rows itself.)
+static int launch_transforms(vbm_encoder *e, const vbm_batch &v, hipStream_t q, bool timed)
+{
+    const vbm_setup *d = vbm_setup_device_ptrs(e->H);
+    const int W = v.W, short_n = e->hs->blocksizes[0];
+    const uint8_t *wf = W ? v.wflags_cb : nullptr;
+    RUN(vbm_launch_spread_flags(&v, q));
+    {
+        stage_scope t(e, timed, 0, q);
+        RUN(vbm_launch_window_mdct(v.pcm, v.mdct_bm, wf, d->mdct_trig[W], d->window[W], d->window[0], v.N, short_n, 1, v.ncb,
+                                   0, v.d_nsb, e->ch, q));
+    }
+    stage_scope t(e, timed, 1, q);
+    RUN(vbm_launch_window_fft_log(v.pcm, v.logfft_bm, v.local_ampmax, wf, d->fft_wa[W], d->window[W], d->window[0], v.N,
+                                  short_n, v.ncb, v.d_nsb, e->ch, q));
+    return VBM_OK;
+}
+
+// loop B up to the hand-over: prologue (3), noise mask (4), tone mask (5), offset_and_mix + block state (6; managed
+// bitrate: managed_front).  The tone mask reads only the log spectrum and the prologue's maxima, the noise mask only the
+// MDCT: with `side` >= 0 the tone mask runs on aux[side] beside the noise mask, forked after the prologue and joined
+// before stage 6.
+static int launch_psy(vbm_encoder *e, const vbm_batch &v, hipStream_t q, bool timed, int side = -1)
+{
+    const int lines = e->hs->psy[v.block_mode].total_octave_lines;
+    hipError_t err;
+    { stage_scope t(e, timed, 3, q); RUN(vbm_launch_prologue(&v, q)); }
+    if (side >= 0) {
+        hipStream_t qa = e->aux[side];
+        if ((err = hipEventRecord(e->ev_aux_fork[side], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
+        if ((err = hipStreamWaitEvent(qa, e->ev_aux_fork[side], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
+        { stage_scope t(e, timed, 5, qa); RUN(vbm_launch_tonemask(&v, lines, qa)); }
+        if ((err = hipEventRecord(e->ev_aux_join[side], qa)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
+        { stage_scope t(e, timed, 4, q); RUN(vbm_launch_noisemask(&v, q)); }
+        if ((err = hipStreamWaitEvent(q, e->ev_aux_join[side], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
+    } else {
+        { stage_scope t(e, timed, 4, q); RUN(vbm_launch_noisemask(&v, q)); }
+        { stage_scope t(e, timed, 5, q); RUN(vbm_launch_tonemask(&v, lines, q)); }
+    }
+    stage_scope t(e, timed, 6, q);
+    if (e->hs->managed) RUN(managed_front(v, q));
+    else { RUN(vbm_launch_mix(&v, q)); RUN(vbm_launch_block_state(&v, q)); }
+    return VBM_OK;
+}
+
+// floor fit (7), then loop C: floor encode (8), couple/quantise (9), residue + packet assembly (10).  Managed bitrate:
+// managed_back as stage 10, which writes the chosen packets to `d_packets` itself.
+static int launch_back(vbm_encoder *e, const vbm_batch &v, hipStream_t q, bool timed, uint8_t *d_packets,
+                       const std::function<int()> &before_choose = nullptr)
+{
+    if (e->hs->managed) {
+        stage_scope t(e, timed, 10, q);
+        RUN(managed_back(v, d_packets, q, before_choose));
+        return VBM_OK;
+    }
+    { stage_scope t(e, timed, 7, q); RUN(vbm_launch_floor_fit(&v, q)); }
+    { stage_scope t(e, timed, 8, q); RUN(vbm_launch_floor_encode(&v, q)); }
+    { stage_scope t(e, timed, 9, q); RUN(vbm_launch_couple_quantize(&v, q)); }
+    stage_scope t(e, timed, 10, q);
+    RUN(vbm_launch_pack(&v, q));
+    return VBM_OK;
+}
+
+// stage 11 of vbm_analysis_batch2 for stream-blocks [sb0, sb0 + v.nsb): word-major packet tiles -> [nsb][max_packet_bytes]
+// bytes (little-endian words; managed bitrate: managed_back has written them), and the lengths
+static int copy_packets(vbm_encoder *e, const vbm_batch &v, uint8_t *d_packets, int *d_packet_bytes, int sb0, hipStream_t q,
+                        bool timed)
+{
+    stage_scope t(e, timed, 11, q);
+    if (d_packets && !e->hs->managed)
+        RUN(vbm_launch_untranspose_i32((const int *)v.packetT, (int *)(d_packets + (size_t)sb0 * e->max_packet_bytes),
+                                       e->max_packet_bytes / 4, (size_t)(e->max_packet_bytes / 4) * 64, v.nsb, q));
+    if (d_packet_bytes) {
+        hipError_t err = hipMemcpyAsync(d_packet_bytes + sb0, v.packet_bytes, v.nsb * sizeof(int), hipMemcpyDeviceToDevice, q);
+        if (err != hipSuccess) return vbm_set_hip_error(err, "hipMemcpyAsync(packet_bytes)");
+    }
+    return VBM_OK;
 }
 
 extern "C" int vbm_analysis_batch(vbm_encoder *e, int block_mode, int nsb, const int *stream_ids,
@@ -712,87 +794,16 @@ extern "C" int vbm_analysis_batch2(vbm_encoder *e, int block_mode, int nsb, cons
     const int nback = nsplit;             // two-stream form: the sub-batches apply to the back half only
     if (two) nsplit = 1;
 
-    int W = b.W;
-    int rc = 0;
+    int rc;
     const size_t ev_need = (size_t)2 * (kFront + (size_t)(nsplit > nback ? nsplit : nback) * kBack);
     const bool prof = e->profiling && e->prof_calls < e->prof_max_calls && e->events_used + ev_need <= e->events.size();
-    // STAGE(k, q, launch): run `launch` on stream q, bracketed by a (begin, end) event pair when profiling
-#define RUN(x) do { rc = (x); if (rc) { g_vbm_err = std::string("launch failed: ") + #x; return VBM_EHIP; } } while (0)
-#define STAGE(k, q, launch)                                                                    \
-    do {                                                                                       \
-        size_t eb_ = 0;                                                                        \
-        if (prof) { eb_ = e->events_used++; (void)hipEventRecord(e->events[eb_], (q)); }       \
-        launch;                                                                                \
-        if (prof) {                                                                            \
-            size_t ee_ = e->events_used++;                                                     \
-            (void)hipEventRecord(e->events[ee_], (q));                                         \
-            e->spans.push_back({(k), eb_, ee_});                                               \
-        }                                                                                      \
-    } while (0)
     vbm_debug_delay_point(VBM_DP_BATCH_FRONT, st);
-    RUN(vbm_launch_spread_flags(&b, st));
-    // loop A: window + MDCT, window + FFT + log spectrum (wave per block), whole batch
-    STAGE(0, st, RUN(vbm_launch_window_mdct(b.pcm, b.mdct_bm, W ? b.wflags_cb : nullptr,
-                                            vbm_setup_device_ptrs(e->H)->mdct_trig[W], vbm_setup_device_ptrs(e->H)->window[W],
-                                            vbm_setup_device_ptrs(e->H)->window[0], b.N, s->blocksizes[0], 1, b.ncb, 0, nullptr, 0, st)));
-    STAGE(1, st, RUN(vbm_launch_window_fft_log(b.pcm, b.logfft_bm, b.local_ampmax, W ? b.wflags_cb : nullptr,
-                                               vbm_setup_device_ptrs(e->H)->fft_wa[W], vbm_setup_device_ptrs(e->H)->window[W],
-                                               vbm_setup_device_ptrs(e->H)->window[0], b.N, s->blocksizes[0], b.ncb, nullptr, 0, st)));
-    // (stage 2, "transpose": gone — k_noisemask writes the tiled MDCT rows itself)
-
-    // the stages between the transforms and the hand-over: psychoacoustics, offset_and_mix, block state
-    auto front_stages = [&](vbm_batch &v, hipStream_t q, int part) -> int {
-        // loop B: psychoacoustics + floor fit (lane per channel-block).  The tone-mask branch reads only
-        // the log spectrum and the prologue's maxima, the noise-mask branch only the MDCT: they run side
-        // by side on two streams and meet at _vp_offset_and_mix.
-        STAGE(3, q, RUN(vbm_launch_prologue(&v, q)));
-        if (e->overlap_branches) {
-            hipStream_t qa = e->aux[part];
-            if ((err = hipEventRecord(e->ev_aux_fork[part], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-            if ((err = hipStreamWaitEvent(qa, e->ev_aux_fork[part], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-            STAGE(5, qa, RUN(vbm_launch_tonemask(&v, s->psy[v.block_mode].total_octave_lines, qa)));
-            if ((err = hipEventRecord(e->ev_aux_join[part], qa)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-            STAGE(4, q, RUN(vbm_launch_noisemask(&v, q)));
-            if ((err = hipStreamWaitEvent(q, e->ev_aux_join[part], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-        } else {
-            STAGE(4, q, RUN(vbm_launch_noisemask(&v, q)));
-            STAGE(5, q, RUN(vbm_launch_tonemask(&v, s->psy[v.block_mode].total_octave_lines, q)));
-        }
-        if (s->managed) STAGE(6, q, RUN(managed_front(v, q)));
-        else STAGE(6, q, { RUN(vbm_launch_mix(&v, q)); RUN(vbm_launch_block_state(&v, q)); });
-        return 0;
-    };
-    // floor fit .. packets of stream-blocks [sb0, sb0 + v.nsb)
-    auto back_stages = [&](vbm_batch &v, hipStream_t q, int sb0) -> int {
-        if (s->managed) {
-            STAGE(10, q, RUN(managed_back(v, d_packets ? d_packets + (size_t)sb0 * e->max_packet_bytes : nullptr, q)));
-        } else {
-            STAGE(7, q, RUN(vbm_launch_floor_fit(&v, q)));
-            // loop C: floor encode, couple/quantise, residue + packet assembly
-            STAGE(8, q, RUN(vbm_launch_floor_encode(&v, q)));
-            STAGE(9, q, RUN(vbm_launch_couple_quantize(&v, q)));
-            STAGE(10, q, RUN(vbm_launch_pack(&v, q)));
-        }
-        STAGE(11, q, {
-            if (d_packets && !s->managed)   // word-major tiles -> [nsb][max_packet_bytes] bytes (little-endian words)
-                RUN(vbm_launch_untranspose_i32((const int *)v.packetT,
-                                               (int *)(d_packets + (size_t)sb0 * e->max_packet_bytes),
-                                               e->max_packet_bytes / 4, (size_t)(e->max_packet_bytes / 4) * 64,
-                                               v.nsb, q));
-            if (d_packet_bytes) {
-                if ((err = hipMemcpyAsync(d_packet_bytes + sb0, v.packet_bytes, v.nsb * sizeof(int), hipMemcpyDeviceToDevice, q)) != hipSuccess)
-                    return vbm_set_hip_error(err, "hipMemcpyAsync(packet_bytes)");
-            }
-        });
-        return 0;
-    };
-
+    if ((rc = launch_transforms(e, b, st, prof))) return rc;
     if (two) {
         // front half of the whole batch on the caller's front stream; the back half as `nback` tile-aligned
         // slices, the first on the caller's back stream and the others on internal streams beside it (their
         // few-wavefront serial kernels then overlap each other's wide ones), joined back before ev_back
-        vbm_batch v = b;
-        if ((rc = front_stages(v, st, 0))) return rc;
+        if ((rc = launch_psy(e, b, st, prof, e->overlap_branches ? 0 : -1))) return rc;
         if ((err = hipEventRecord(e->ev_front[w], st)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
         for (int part = 0; part < nback; part++) {
             const int t0 = (int)((long)tiles * part / nback), t1 = (int)((long)tiles * (part + 1) / nback);
@@ -802,7 +813,9 @@ extern "C" int vbm_analysis_batch2(vbm_encoder *e, int block_mode, int nsb, cons
             if ((err = hipStreamWaitEvent(qb, e->ev_front[w], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
             vbm_debug_delay_point(VBM_DP_BATCH_BACK, qb);
             vbm_batch vs = nback > 1 ? slice_of(b, sb0, sb1 - sb0) : b;
-            if ((rc = back_stages(vs, qb, sb0))) return rc;
+            if ((rc = launch_back(e, vs, qb, prof, d_packets ? d_packets + (size_t)sb0 * e->max_packet_bytes : nullptr)) ||
+                (rc = copy_packets(e, vs, d_packets, d_packet_bytes, sb0, qb, prof)))
+                return rc;
             if (part) {
                 if ((err = hipEventRecord(e->ev_join[part], qb)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
                 if ((err = hipStreamWaitEvent(sback, e->ev_join[part], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
@@ -823,8 +836,10 @@ extern "C" int vbm_analysis_batch2(vbm_encoder *e, int block_mode, int nsb, cons
                 v = slice_of(b, sb0, sb1 - sb0);
                 if ((err = hipStreamWaitEvent(q, e->ev_fork, 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
             }
-            if ((rc = front_stages(v, q, part))) return rc;
-            if ((rc = back_stages(v, q, sb0))) return rc;
+            if ((rc = launch_psy(e, v, q, prof, e->overlap_branches ? part : -1)) ||
+                (rc = launch_back(e, v, q, prof, d_packets ? d_packets + (size_t)sb0 * e->max_packet_bytes : nullptr)) ||
+                (rc = copy_packets(e, v, d_packets, d_packet_bytes, sb0, q, prof)))
+                return rc;
             if (nsplit > 1) {
                 if ((err = hipEventRecord(e->ev_join[part], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
                 if ((err = hipStreamWaitEvent(st, e->ev_join[part], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
@@ -832,8 +847,6 @@ extern "C" int vbm_analysis_batch2(vbm_encoder *e, int block_mode, int nsb, cons
         }
     }
     if (prof) { e->prof_calls++; e->prof_blocks += nsb; }
-#undef STAGE
-#undef RUN
     return VBM_OK;
 }
 
@@ -855,104 +868,116 @@ struct type_job {
     hipStream_t q_on = nullptr;  // grouped: the stream to enqueue on
 };
 
+// the job's region of its workspace as a batch
+static vbm_batch job_batch(vbm_encoder *e, const type_job &j)
+{
+    vbm_batch full;
+    configure(e, full, j.m, j.bound, j.pcm, j.w);
+    vbm_batch v = slice_of(full, j.lane0, j.bound);
+    v.pcm = j.pcm;
+    v.d_nsb = j.d_nsb;
+    v.few = j.few;
+    return v;
+}
+
+// stage 11 of a round's batch: packets and lengths to the caller's buffers (managed bitrate: the lengths only,
+// managed_back has written the packets)
+static int round_outputs(vbm_encoder *e, const vbm_batch &v, const type_job &j, hipStream_t q, bool timed)
+{
+    stage_scope t(e, timed, 11, q);
+    RUN(vbm_launch_packets_out(&v, e->hs->managed ? nullptr : j.d_packets, j.d_packet_bytes, q));
+    return VBM_OK;
+}
+
 static int enqueue_job(vbm_encoder *e, const type_job &j)
 {
-    const vbm_setup *s = e->hs;
     hipError_t err;
-    int rc = 0;
+    int rc;
     const int m = j.m, w = j.w;
     hipStream_t q = j.grouped ? j.q_on : (j.big ? e->sub[4] : e->sub[m]);
     const int qid = j.big ? 4 : m;
     if (!j.grouped && (err = hipStreamWaitEvent(q, e->ev_fork, 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
     if (!j.grouped && j.part != 2) vbm_debug_delay_point(j.big ? VBM_DP_JOB_BIG : VBM_DP_JOB_SMALL, q);
-    vbm_batch full;
-    configure(e, full, m, j.bound, j.pcm, w);
-    vbm_batch v = slice_of(full, j.lane0, j.bound);
-    v.pcm = j.pcm;
-    v.d_nsb = j.d_nsb;
-    v.few = j.few;
-    const int W = v.W;
-    const bool pr = j.timed;
-#define RUN(x) do { rc = (x); if (rc) { g_vbm_err = std::string("launch failed: ") + #x; return VBM_EHIP; } } while (0)
-#define TIMED(k, qq) stage_scope scope_##k(e, pr, k, qq)
+    const vbm_batch v = job_batch(e, j);
     if (j.part != 2) {
-    RUN(vbm_launch_spread_flags(&v, q));
-    { TIMED(0, q);
-      RUN(vbm_launch_window_mdct(v.pcm, v.mdct_bm, W ? v.wflags_cb : nullptr, vbm_setup_device_ptrs(e->H)->mdct_trig[W],
-                                 vbm_setup_device_ptrs(e->H)->window[W], vbm_setup_device_ptrs(e->H)->window[0], v.N,
-                                 s->blocksizes[0], 1, v.ncb, 0, v.d_nsb, e->ch, q)); }
-    { TIMED(1, q);
-      RUN(vbm_launch_window_fft_log(v.pcm, v.logfft_bm, v.local_ampmax, W ? v.wflags_cb : nullptr,
-                                    vbm_setup_device_ptrs(e->H)->fft_wa[W], vbm_setup_device_ptrs(e->H)->window[W],
-                                    vbm_setup_device_ptrs(e->H)->window[0], v.N, s->blocksizes[0], v.ncb, v.d_nsb, e->ch, q)); }
-    // the transforms above read the block's PCM only; from here on the carried stream state is involved: the
-    // batches this batch's streams were last part of come first (those on this very HIP stream already do)
-    if (!j.grouped)
-    for (int ww = 0; ww < e->nws; ww++)
-        for (int t = 0; t < 4; t++)
-            if (((j.depmask >> (ww * 4 + t)) & 1u) && e->slot_queue[ww][t] != qid &&
-                (err = hipStreamWaitEvent(q, e->ev_state[ww][t], 0)) != hipSuccess)
-                return vbm_set_hip_error(err, "hipStreamWaitEvent");
-    if (!j.grouped) vbm_debug_delay_point(VBM_DP_JOB_STATE, q);
-    { TIMED(3, q); RUN(vbm_launch_prologue(&v, q)); }
-    // noise mask, then tone mask, on one stream.  With the tone mask of the long-block batch on a second stream beside the
-    // noise mask (as in vbm_analysis_batch2) the step from PCM measured 5.04 ms against 4.58: the two LDS-heavy kernels side
-    // by side crowd out the back half of the round before (profiles/r03/README.md).
-    { TIMED(4, q); RUN(vbm_launch_noisemask(&v, q)); }
-    { TIMED(5, q); RUN(vbm_launch_tonemask(&v, s->psy[v.block_mode].total_octave_lines, q)); }
-    { TIMED(6, q);
-      if (s->managed) RUN(managed_front(v, q));
-      else { RUN(vbm_launch_mix(&v, q)); RUN(vbm_launch_block_state(&v, q)); } }
-    }   // part != 2
-    if (j.part == 1) return VBM_OK;
-    if (!j.grouped) {
-    if ((err = hipEventRecord(e->ev_state[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-    if (j.big) {   // hand over to the back-half stream of big batches
-        if ((err = hipStreamWaitEvent(e->sub[5], e->ev_state[w][m], 0)) != hipSuccess)
-            return vbm_set_hip_error(err, "big batch hand-over");
-        q = e->sub[5];
-    }
-    vbm_debug_delay_point(VBM_DP_JOB_BACK, q);
-    }
-    if (s->managed) {
-        TIMED(10, q);
-        // a managed stream's reservoirs move in the bitrate manager's choice at the end of the back half: that step (not
-        // the front half, not the blobs' passes) waits for the DONE events of the batches this one's streams were in
-        hipStream_t qb = q;
-        RUN(managed_back(v, j.d_packets, q, [&]() -> int {
-            if (j.grouped) return 0;
+        if ((rc = launch_transforms(e, v, q, j.timed))) return rc;
+        // the transforms read the block's PCM only; from here on the carried stream state is involved: the batches
+        // this batch's streams were last part of come first (those on this very HIP stream already do)
+        if (!j.grouped) {
             for (int ww = 0; ww < e->nws; ww++)
                 for (int t = 0; t < 4; t++)
-                    if (((j.depmask >> (ww * 4 + t)) & 1u) && hipStreamWaitEvent(qb, e->ev_done[ww][t], 0) != hipSuccess) return -2;
-            return 0;
-        }));
-    } else {
-        { TIMED(7, q); RUN(vbm_launch_floor_fit(&v, q)); }
-        { TIMED(8, q); RUN(vbm_launch_floor_encode(&v, q)); }
-        { TIMED(9, q); RUN(vbm_launch_couple_quantize(&v, q)); }
-        { TIMED(10, q); RUN(vbm_launch_pack(&v, q)); }
+                    if (((j.depmask >> (ww * 4 + t)) & 1u) && e->slot_queue[ww][t] != qid &&
+                        (err = hipStreamWaitEvent(q, e->ev_state[ww][t], 0)) != hipSuccess)
+                        return vbm_set_hip_error(err, "hipStreamWaitEvent");
+            vbm_debug_delay_point(VBM_DP_JOB_STATE, q);
+        }
+        // noise mask, then tone mask, on one stream.  With the tone mask of the long-block batch on a second stream beside
+        // the noise mask (as in vbm_analysis_batch2) the step from PCM measured 5.04 ms against 4.58: the two LDS-heavy
+        // kernels side by side crowd out the back half of the round before (profiles/r03/README.md).
+        if ((rc = launch_psy(e, v, q, j.timed))) return rc;
     }
+    if (j.part == 1) return VBM_OK;
+    if (!j.grouped) {
+        if ((err = hipEventRecord(e->ev_state[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
+        if (j.big) {   // hand over to the back-half stream of big batches
+            if ((err = hipStreamWaitEvent(e->sub[5], e->ev_state[w][m], 0)) != hipSuccess)
+                return vbm_set_hip_error(err, "big batch hand-over");
+            q = e->sub[5];
+        }
+        vbm_debug_delay_point(VBM_DP_JOB_BACK, q);
+    }
+    // a managed stream's reservoirs move in the bitrate manager's choice at the end of the back half: that step (not
+    // the front half, not the blobs' passes) waits for the DONE events of the batches this one's streams were in
+    auto wait_done = [&]() -> int {
+        if (j.grouped) return 0;
+        for (int ww = 0; ww < e->nws; ww++)
+            for (int t = 0; t < 4; t++)
+                if (((j.depmask >> (ww * 4 + t)) & 1u) && hipStreamWaitEvent(q, e->ev_done[ww][t], 0) != hipSuccess) return -2;
+        return 0;
+    };
+    if ((rc = launch_back(e, v, q, j.timed, j.d_packets, wait_done))) return rc;
     if (j.grouped) return VBM_OK;     // the group's caller copies the outputs and records the events
     vbm_debug_delay_point(VBM_DP_JOB_OUT, q);
-    { TIMED(11, q); RUN(vbm_launch_packets_out(&v, s->managed ? nullptr : j.d_packets, j.d_packet_bytes, q)); }
-#undef TIMED
+    if ((rc = round_outputs(e, v, j, q, j.timed))) return rc;
     if ((err = hipEventRecord(e->ev_done[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
     return VBM_OK;
 }
 
-// outputs of one block type of workspace w to the caller's buffers (the tail of enqueue_job, for grouped jobs)
-static int copy_outputs(vbm_encoder *e, const type_job &j, hipStream_t q)
+// workspace slot (w, m) takes a batch whose front half runs on sub[queue]
+static void take_slot(vbm_encoder *e, int w, int m, int queue)
 {
-    int rc = 0;
-    vbm_batch full;
-    configure(e, full, j.m, j.bound, j.pcm, j.w);
-    vbm_batch v = slice_of(full, j.lane0, j.bound);
-    v.d_nsb = j.d_nsb;
-    if (e->hs->managed) return VBM_OK;   // (managed_back delivers the chosen packets itself)
-    RUN(vbm_launch_packets_out(&v, j.d_packets, j.d_packet_bytes, q));
+    e->done_pending[w][m] = true;
+    e->reuse_pending[w][m] = true;
+    e->slot_queue[w][m] = (signed char)queue;
+    e->epoch[w][m]++;
+}
+
+// The batches of a round, jobs[0..n) in this order, each after taking its slot: every one enqueued by a host thread of
+// its own, except jobs[n - 1] when `last_here`, which the calling thread enqueues.  The ~40 launches of a block type's
+// pipeline cost the host more than the kernels of a small batch cost the device, and the batches are independent.
+static int run_jobs(vbm_encoder *e, const type_job *jobs, int n, bool last_here)
+{
+    int dev_id = 0;
+    (void)hipGetDevice(&dev_id);
+    int rcs[4] = {0, 0, 0, 0};
+    std::string msgs[4];
+    std::thread workers[4];
+    for (int k = 0; k < n; k++) {
+        const type_job &j = jobs[k];
+        take_slot(e, j.w, j.m, j.big ? 4 : j.m);
+        auto run = [e, &j, &rcs, &msgs]() {
+            rcs[j.m] = enqueue_job(e, j);
+            if (rcs[j.m]) msgs[j.m] = g_vbm_err;
+        };
+        if (last_here && k == n - 1) run();
+        else workers[k] = std::thread([run, dev_id]() { (void)hipSetDevice(dev_id); run(); });
+    }
+    for (std::thread &t : workers)
+        if (t.joinable()) t.join();
+    for (int m = 0; m < 4; m++)
+        if (rcs[m]) { g_vbm_err = msgs[m]; return rcs[m]; }
     return VBM_OK;
 }
-#undef RUN
 
 // One round of blocks of all four block types: counts[m] blocks of type m, described by stream_ids /
 // wflags grouped by type (type 0 first); d_pcm: the blocks of type m start at float offset
@@ -1022,9 +1047,6 @@ static int analysis_round_impl(vbm_encoder *e, const int *counts, const int *str
             const vbm_encoder::last_batch &lb = e->last[stream_ids[off[m] + i]];
             if (lb.w >= 0 && e->epoch[(int)lb.w][(int)lb.m] == lb.epoch) dep[m] |= 1u << (lb.w * 4 + lb.m);
         }
-    if (getenv("VBM_ROUND_DEBUG"))
-        fprintf(stderr, "round w=%d defer=%d counts=[%d %d %d %d] dep masks: %04x %04x %04x %04x\n", w, (int)defer, counts[0], counts[1],
-                counts[2], counts[3], dep[0], dep[1], dep[2], dep[3]);
     // ids / flags in the padded lane layout, through the pinned staging (always uploaded: the layout changes
     // from round to round)
     {
@@ -1046,7 +1068,6 @@ static int analysis_round_impl(vbm_encoder *e, const int *counts, const int *str
     }
     if ((err = hipEventRecord(e->ev_fork, st)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
     e->last_nsb = 0;
-#define RUN(x) do { rc = (x); if (rc) { g_vbm_err = std::string("launch failed: ") + #x; return VBM_EHIP; } } while (0)
     // Every block type gets its own internal stream; the largest batch is enqueued first so that its
     // launches are in flight while the host issues the ~35 launches of each small batch.  Measured
     // alternatives on MI355X: big batch on the caller's stream + one side stream, and two
@@ -1065,14 +1086,15 @@ static int analysis_round_impl(vbm_encoder *e, const int *counts, const int *str
     for (int a = 0; a < 4; a++)
         for (int c = a + 1; c < 4; c++)
             if (counts[order[c]] > counts[order[a]]) { int t_ = order[a]; order[a] = order[c]; order[c] = t_; }
-    // The ~40 launches of a block type's pipeline cost the host more than the kernels of a small batch cost the
-    // device, and the four types are independent: every type is enqueued by its own host thread (the largest
-    // batch on the calling thread), each on its own HIP stream.
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
+    // every type on its own HIP stream, enqueued by its own host thread, the smallest first: their threads start while
+    // the largest batch is enqueued on the calling thread
     const bool prof = e->profiling && e->prof_calls < e->prof_max_calls && e->events_used + 2 * (size_t)kNumStages <= e->events.size();
-    auto enqueue_type = [&](const int m) -> int {
-        type_job j;
+    type_job jobs[4];
+    int njobs = 0;
+    for (int rank = 3; rank >= 0; rank--) {
+        const int m = order[rank];
+        if (!counts[m]) continue;
+        type_job &j = jobs[njobs++];
         j.m = m; j.w = w; j.lane0 = pad[m]; j.bound = counts[m]; j.d_nsb = nullptr;
         j.pcm = d_pcm + (size_t)off[m] * e->ch * s->blocksizes[1];
         j.d_packets = d_packets ? d_packets + (size_t)off[m] * e->max_packet_bytes : nullptr;
@@ -1080,44 +1102,18 @@ static int analysis_round_impl(vbm_encoder *e, const int *counts, const int *str
         j.big = counts[m] >= kBigBatch;          // a big batch gets streams of its own (front / back half)
         j.timed = prof && m == order[0];         // stage timing covers the round's largest batch (calling thread)
         j.depmask = dep[m];
-        return enqueue_job(e, j);
-    };
-    int rcs[4] = {0, 0, 0, 0};
-    std::string msgs[4];
-    std::thread workers[4];
-    const bool threaded = !getenv("VBM_ROUND_SINGLE_THREAD");
-    for (int rank = 3; rank >= 0; rank--) {      // smallest first: their threads start while the big one is enqueued here
-        const int m = order[rank];
-        if (!counts[m]) continue;
-        e->done_pending[w][m] = true;
-        e->reuse_pending[w][m] = true;
-        e->slot_queue[w][m] = (signed char)(counts[m] >= kBigBatch ? 4 : m);
-        if (rank == 0 || !threaded) {
-            rcs[m] = enqueue_type(m);
-            if (rcs[m]) msgs[m] = g_vbm_err;
-        } else {
-            workers[m] = std::thread([&, m]() {
-                (void)hipSetDevice(dev_id);
-                rcs[m] = enqueue_type(m);
-                if (rcs[m]) msgs[m] = g_vbm_err;
-            });
-        }
     }
-    for (int m = 0; m < 4; m++)
-        if (workers[m].joinable()) workers[m].join();
-    for (int m = 0; m < 4; m++)
-        if (rcs[m]) { g_vbm_err = msgs[m]; return rcs[m]; }
+    if ((rc = run_jobs(e, jobs, njobs, true))) return rc;
     if (prof) {
         e->prof_calls++;
         e->prof_blocks += counts[order[0]];
     }
-#undef RUN
     for (int m = 0; m < 4; m++)
         if (counts[m] >= kBigBatch) { e->lazy_w = w; e->lazy_m = m; }
     // remember which batch every stream of this round belongs to
     for (int m = 0; m < 4; m++) {
         if (!counts[m]) continue;
-        const unsigned ep = ++e->epoch[w][m];
+        const unsigned ep = e->epoch[w][m];
         for (int i = 0; i < counts[m]; i++) e->last[stream_ids[off[m] + i]] = {(signed char)w, (signed char)m, ep};
     }
     e->round_w = w;
@@ -1137,24 +1133,20 @@ int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, 
     if (!e->small_streams_set) {
         // Streams of the device-built rounds.  sub[0..3]: the small batches, chains of ~40 short kernels; beside the
         // big batch every one of them queues behind its wide launches, so they get high priority (their workgroups
-        // are few and go first: the chain's latency is what the short-block runs of a stream wait for;
-        // VBM_SMALL_PRIORITY=0: plain streams).  sub[4], sub[5]: front and back half of the big batch.  The runtime
-        // hands out a limited number of hardware queues per priority (GPU_MAX_HW_QUEUES) in the order the streams
-        // are made and lets later streams share: the two big-batch streams are made before the others, so that
-        // they do not end up on one queue (the back half of a call has to run beside the front half of the next).
+        // are few and go first: the chain's latency is what the short-block runs of a stream wait for).  sub[4],
+        // sub[5]: front and back half of the big batch.  The runtime hands out a limited number of hardware queues
+        // per priority (GPU_MAX_HW_QUEUES) in the order the streams are made and lets later streams share: the two
+        // big-batch streams are made before the others, so that they do not end up on one queue (the back half of a
+        // call has to run beside the front half of the next).
         e->small_streams_set = true;
-        const char *env = getenv("VBM_SMALL_PRIORITY");
         int lo = 0, hi = 0;
-        const bool prio = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi < lo && (!env || atoi(env));
+        const bool prio = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi < lo;
         while ((int)e->sub.size() < 6) {
             e->sub.push_back(nullptr);
             hipEvent_t ev;
             if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return VBM_EHIP;
             e->ev_join.push_back(ev);
         }
-        // VBM_SMALL_STREAMS=2: types 0 / 1 share one stream, types 2 / 3 another (fewer hardware queues in play)
-        const char *ss = getenv("VBM_SMALL_STREAMS");
-        e->small_share = ss && atoi(ss) == 2;
         static const int order[6] = {4, 5, 0, 1, 2, 3};
         for (int k = 0; k < 6; k++) {
             const int m = order[k];
@@ -1169,12 +1161,6 @@ int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, 
                 (void)hipStreamDestroy(e->sub[m]);
             }
             e->sub[m] = q;
-        }
-        if (e->small_share) {
-            (void)hipStreamDestroy(e->sub[1]);
-            (void)hipStreamDestroy(e->sub[3]);
-            e->sub[1] = e->sub[0];
-            e->sub[3] = e->sub[2];
         }
     }
     const int w = e->next;
@@ -1217,7 +1203,7 @@ static int run_group(vbm_encoder *e, vbm_encoder::round_graph &g, hipStream_t or
         if ((err = hipGraphLaunch(g.exec, origin)) != hipSuccess) return vbm_set_hip_error(err, "hipGraphLaunch");
         return VBM_OK;
     }
-    const bool capture = e->use_graphs == 1 && g.uses >= 1;   // (use_graphs 2: the groups as plain launches, for A/B)
+    const bool capture = g.uses >= 1;
     g.uses++;
     if (capture && (err = hipStreamBeginCapture(origin, hipStreamCaptureModeThreadLocal)) != hipSuccess)
         return vbm_set_hip_error(err, "hipStreamBeginCapture");
@@ -1312,13 +1298,10 @@ static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, cons
         vbm_debug_delay_point(VBM_DP_DEV_BIG_BACK, qB);
         if ((rc = run_group(e, e->gJ[w][4][2], qB, &jb, 1))) return rc;
         vbm_debug_delay_point(VBM_DP_DEV_OUT, qB);
-        if ((rc = copy_outputs(e, jb, qB))) return rc;
+        if ((rc = round_outputs(e, job_batch(e, jb), jb, qB, false))) return rc;
         vbm_debug_stamp(qB, 13);
         if ((err = hipEventRecord(e->ev_done[w][3], qB)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-        e->done_pending[w][3] = true;
-        e->reuse_pending[w][3] = true;
-        e->slot_queue[w][3] = 4;
-        e->epoch[w][3]++;
+        take_slot(e, w, 3, 4);
     }
     for (int m = 0; m < 4; m++) {
         if (!cap[m] || (m == 3 && has_big)) continue;
@@ -1337,13 +1320,10 @@ static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, cons
         vbm_debug_delay_point(VBM_DP_DEV_SMALL_BACK, q);
         if ((rc = run_group(e, e->gJ[w][m][2], q, &j2, 1))) return rc;
         vbm_debug_delay_point(VBM_DP_DEV_OUT, q);
-        if ((rc = copy_outputs(e, j2, q))) return rc;
+        if ((rc = round_outputs(e, job_batch(e, j2), j2, q, false))) return rc;
         vbm_debug_stamp(q, 30 + m);
         if ((err = hipEventRecord(e->ev_done[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-        e->done_pending[w][m] = true;
-        e->reuse_pending[w][m] = true;
-        e->slot_queue[w][m] = (signed char)m;
-        e->epoch[w][m]++;
+        take_slot(e, w, m, m);
         e->queue_last_w[m] = w;
     }
     if (has_big) { e->call_big_w = w; e->lazy_w = w; e->lazy_m = 3; }
@@ -1361,13 +1341,9 @@ int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const 
     for (int m = 0; m < 4; m++)
         if (cap[m] < 0 || (lane0[m] & 63) || lane0[m] + cap[m] > e->Ls || (cap[m] && s->modes < 2 && (m >> 1))) return VBM_EINVAL;
     if (d_count != e->d_counts_ws + 4 * w) return VBM_EINVAL;
-    if (e->use_graphs < 0) {
-        const char *env = getenv("VBM_DEVICE_GRAPHS");     // 0: plain launches, 1 (default): HIP graphs, 2: groups without capture
-        e->use_graphs = env ? atoi(env) : 1;
-    }
     // Stage timing needs the plain launches (events between the kernels); a managed-bitrate back half writes the
     // chosen packets straight to the caller's buffers, which change from call to call: plain launches as well.
-    const int mode = (e->use_graphs && !e->profiling && !s->managed) ? 1 : 2;
+    const int mode = (!e->profiling && !s->managed) ? 1 : 2;
     if (e->device_mode && e->device_mode != mode) {
         // the two ways use different internal streams: everything in flight is waited for at the switch
         for (int ww = 0; ww < e->nws; ww++)
@@ -1385,54 +1361,23 @@ int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const 
         for (int t = 0; t < 4; t++)
             if (ww != w && e->reuse_pending[ww][t]) depmask |= 1u << (ww * 4 + t);
     const bool prof = e->profiling && e->prof_calls < e->prof_max_calls && e->events_used + 2 * (size_t)kNumStages <= e->events.size();
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
-    int rcs[4] = {0, 0, 0, 0};
-    std::string msgs[4];
-    std::thread workers[4];
-    const bool threaded = !getenv("VBM_ROUND_SINGLE_THREAD");
-    const int bigm = first_round ? 3 : -1;
-    auto job_of = [&](int m) {
-        type_job j;
+    // types 0-2 on host threads of their own, the long blocks on the calling thread
+    type_job jobs[4];
+    int njobs = 0;
+    for (int m = 0; m < 4; m++) {
+        if (!cap[m]) continue;
+        type_job &j = jobs[njobs++];
         j.m = m; j.w = w; j.lane0 = lane0[m]; j.bound = cap[m]; j.d_nsb = d_count + m;
         j.pcm = d_blocks + (size_t)lane0[m] * e->ch * s->blocksizes[1];
         j.d_packets = d_packets ? d_packets + (size_t)lane0[m] * e->max_packet_bytes : nullptr;
         j.d_packet_bytes = d_packet_bytes ? d_packet_bytes + lane0[m] : nullptr;
-        j.big = m == bigm;
+        j.big = m == 3 && first_round;
         j.timed = prof && m == 3 && first_round;
         // (short blocks never follow a type-3 block directly: no wait for the newest big batch)
         j.depmask = (m < 2 && e->call_big_w >= 0) ? depmask & ~(1u << (e->call_big_w * 4 + 3)) : depmask;
-        return j;
-    };
-    for (int m = 0; m < 4; m++) {
-        if (!cap[m] || m == 3) continue;
-        e->done_pending[w][m] = true;
-        e->reuse_pending[w][m] = true;
-        e->slot_queue[w][m] = (signed char)m;
-        e->epoch[w][m]++;
-        if (!threaded) {
-            rcs[m] = enqueue_job(e, job_of(m));
-            if (rcs[m]) msgs[m] = g_vbm_err;
-        } else {
-            workers[m] = std::thread([&, m]() {
-                (void)hipSetDevice(dev_id);
-                rcs[m] = enqueue_job(e, job_of(m));
-                if (rcs[m]) msgs[m] = g_vbm_err;
-            });
-        }
     }
-    if (cap[3]) {      // the long blocks on the calling thread
-        e->done_pending[w][3] = true;
-        e->reuse_pending[w][3] = true;
-        e->slot_queue[w][3] = (signed char)(bigm == 3 ? 4 : 3);
-        e->epoch[w][3]++;
-        rcs[3] = enqueue_job(e, job_of(3));
-        if (rcs[3]) msgs[3] = g_vbm_err;
-    }
-    for (int m = 0; m < 4; m++)
-        if (workers[m].joinable()) workers[m].join();
-    for (int m = 0; m < 4; m++)
-        if (rcs[m]) { g_vbm_err = msgs[m]; return rcs[m]; }
+    int rc = run_jobs(e, jobs, njobs, cap[3] > 0);
+    if (rc) return rc;
     if (prof && first_round) e->prof_calls++;
     if (first_round) { e->call_big_w = w; e->lazy_w = w; e->lazy_m = 3; }
     e->round_w = w;
