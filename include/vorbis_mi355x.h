@@ -406,7 +406,8 @@ int vbm_window_mdct_time(const vbm_mdct_plan *plan, const float *d_pcm, float *d
  * vorbis_synthesis + vorbis_synthesis_blockin + vorbis_synthesis_pcmout + vorbis_synthesis_read
  * (reference lib/synthesis.c:25-91, lib/block.c:897-1190; examples/decoder_example.c).
  * Not supported (VBM_EIMPL at setup): floor type 0, block sizes outside 256..4096, more than 8 channels.  No half-rate
- * decoding, seeking or chained streams.  The reference's own vorbis_synthesis* names are not exported. */
+ * decoding or chained streams; seeking is by sample windows of a range store (vbm_synthesis_ranges), not of a live
+ * stream.  The reference's own vorbis_synthesis* names are not exported. */
 #define VBM_ENOTVORBIS (-132) /* OV_ENOTVORBIS, include/vorbis/codec.h:229-233 */
 #define VBM_EBADHEADER (-133) /* OV_EBADHEADER */
 #define VBM_EVERSION   (-134) /* OV_EVERSION   */
@@ -469,6 +470,41 @@ int  vbm_synthesis_runs(vbm_decoder *dec, int nruns, const int *stream_ids /*hos
                         const long long *d_granulepos /*[P] or NULL*/, const uint8_t *d_eos /*[P] or NULL*/,
                         float *d_pcm, long pcm_stride, int *d_run_samples /*[nruns]*/,
                         int *d_samples /*[P]*/, int *d_status /*[P]*/, void *stream);
+/* ---- seekable range decoding ----
+ * A stream's linear decode is the PCM of all its packets decoded in order from a fresh stream, one packet per call
+ * (what vbm_synthesis_runs returns for the whole stream); output position t is its sample t.
+ *
+ * Host only, no device needed: the index of one stream's npackets demuxed packets (CSR as for vbm_synthesis_runs,
+ * clamped to [0, data_bytes); granulepos / eos NULL: all -1 / 0), from a fresh stream state.  Per packet: status[k]
+ * (0, VBM_ENOTAUDIO, VBM_EBADPACKET: the header bits decide it, as in the device unpack), samples[k] (what the linear
+ * decode returns for it) and out_start[k] (the exclusive prefix sum of samples); *total = the stream's length
+ * (ov_pcm_total).  Reads only each packet's header bits, its granulepos and its eos flag. */
+int  vbm_decode_index(const vbm_decode_setup *ds, long long npackets, const uint8_t *data, const long long *offsets,
+                      long long data_bytes, const long long *granulepos, const uint8_t *eos, int *status,
+                      int *samples, long long *out_start, long long *total);
+/* A range store: the packets of nstreams streams decoded by `dec` (one set of headers), kept in device memory with
+ * their index.  Host inputs, the demuxed streams back to back: stream i is packets stream_packets[i] ..
+ * stream_packets[i+1] (stream_packets[0] = 0, non-decreasing), packet k is data[offsets[k] .. offsets[k+1]) clamped to
+ * [0, data_bytes), granulepos / eos [stream_packets[nstreams]] or NULL.  The store belongs to `dec`; destroy it
+ * before the decoder.  vbm_range_store_totals: totals[nstreams], each stream's linear decode length. */
+typedef struct vbm_range_store vbm_range_store;
+int  vbm_range_store_create(vbm_range_store **st, vbm_decoder *dec, int nstreams, const long long *stream_packets,
+                            const uint8_t *data, const long long *offsets, long long data_bytes,
+                            const long long *granulepos, const uint8_t *eos);
+void vbm_range_store_destroy(vbm_range_store *st);
+int  vbm_range_store_totals(const vbm_range_store *st, long long *totals);
+/* Sample windows of the store's streams.  Range r is stream stream_ids[r], start starts[r] >= 0, length lengths[r]
+ * >= 0 (host arrays; ranges may repeat and overlap).  got[r] (host) = clamp(total - start, 0, length), and
+ *   d_pcm[r][c][0 .. got[r]) == linear decode of the stream [c][start .. start + got[r])   bit for bit;
+ * nothing else of d_pcm [nranges][channels][pcm_stride] is written.  Reads and writes no stream state of the decoder:
+ * range calls and vbm_synthesis_batch / _runs calls may be interleaved.  Each range decodes the packets that cover it
+ * plus one pre-roll packet; a range of more than max_batch packets is cut into pieces, and pieces are packed into
+ * sub-calls of at most max_batch rows, all enqueued on `stream` (the piece table of each goes through the staging
+ * ring).  VBM_EINVAL, with nothing enqueued: a store of another decoder, a stream id out of range, a negative start
+ * or length, pcm_stride < max(lengths), max_batch < 2. */
+int  vbm_synthesis_ranges(vbm_decoder *dec, const vbm_range_store *st, int nranges, const int *stream_ids,
+                          const long long *starts, const int *lengths, float *d_pcm, long pcm_stride, int *got,
+                          void *stream);
 /* Intermediates of the LAST call, per row, padded to blocksizes[1]/2 per channel (as vbm_encoder_fetch):
  *   "info" int [nsb][4]; "floor_index" int, "residue" float, "spectrum" float [nsb][channels][blocksizes[1]/2]
  *   (spectrum: after inverse coupling and the floor multiply, before the IMDCT); "floor_used" int [nsb][channels].

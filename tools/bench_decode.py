@@ -11,6 +11,11 @@ With --packets-per-call P > 1 the same workload goes through vbm_synthesis_runs 
 consecutive packets of every stream (P * (warmup + steps) packets per stream are needed: raise --seconds), and the
 result reports ms per call and per packet-step (ms per call / P).  P = 1 (the default) is the one-packet path above.
 
+With --ranges N the store of seekable range decoding is measured instead (vbm_synthesis_ranges): the `--streams`
+streams (the encoded signals dealt round robin) go into one range store, and every call decodes N seeded random
+(stream, start) windows of --range-seconds each.  The result reports ms per call, ranges/s, audio seconds decoded per
+wall second, rows per call and the pre-roll share of those rows (from the host index).
+
 Per-kernel times: run this under `rocprofv3 --kernel-trace --stats`."""
 import argparse
 import json
@@ -36,6 +41,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--packets-per-call", type=int, default=1,
                     help="P > 1: P consecutive packets per stream per call through synthesis_runs")
+    ap.add_argument("--ranges", type=int, default=0, help="N > 0: N random windows per call through synthesis_ranges")
+    ap.add_argument("--range-seconds", type=float, default=1.0, help="length of each window (--ranges)")
+    ap.add_argument("--max-batch", type=int, default=65536, help="rows per sub-call of a range call (--ranges)")
     a = ap.parse_args()
     P = a.packets_per_call
     if P < 1:
@@ -74,6 +82,8 @@ def main():
     for x in lead:
         x.sort()
     nsteps = a.warmup + a.steps
+    if a.ranges > 0:
+        return ranges(a, v, dev, setup, lead)
     if P > 1:
         return runs(a, v, dev, setup, lead)
     if min(len(x) for x in lead) < nsteps:
@@ -180,6 +190,67 @@ def runs(a, v, dev, setup, lead):
         "status_errors": int(bad), "blocksizes": list(ds.blocksizes),
     }
     print(json.dumps(res))
+    dec.close()
+    ds.close()
+
+
+def ranges(a, v, dev, setup, lead):
+    """random sample windows of a range store of --streams streams (vbm_synthesis_ranges)"""
+    S, K, ch, rate, N = a.streams, a.signals, a.channels, a.rate, a.ranges
+    L = int(a.range_seconds * rate)
+    streams = []
+    for k in range(K):
+        b = b"".join(p[1] for p in lead[k])
+        streams.append((np.frombuffer(b, np.uint8), np.cumsum([0] + [len(p[1]) for p in lead[k]]).astype(np.int64),
+                        np.array([p[2] for p in lead[k]], np.int64), np.array([p[3] for p in lead[k]], np.uint8)))
+    ds = v.DecodeSetup(v.header_packets(setup))
+    index = [v.decode_index(ds, *s) for s in streams]
+    dec = v.Decoder(ds, 1, a.max_batch)
+    store = v.RangeStore(dec, [streams[s % K] for s in range(S)])
+    rng = np.random.default_rng(1234)
+    ncalls = a.warmup + a.steps
+    calls, rows, preroll = [], 0, 0
+    for c in range(ncalls):
+        ids = rng.integers(0, S, N).astype(np.int32)
+        starts = (rng.random(N) * np.maximum(store.totals[ids] - L, 1)).astype(np.int64)
+        calls.append((ids, starts))
+        if c >= a.warmup:                                  # rows of the plan, from the host index
+            for i, s in zip(ids, starts):
+                status, samples, out_start, total = index[i % K]
+                n = min(L, total - s)
+                if n <= 0:
+                    continue
+                out_end = out_start + samples
+                k = int(np.searchsorted(out_end, s, side="right"))
+                m = int(np.searchsorted(out_end, s + n - 1, side="right"))
+                p = k - 1
+                while status[p] != 0:
+                    p -= 1
+                rows += m - p + 1
+                preroll += 1
+    pcm = [torch.empty((N, ch, L), dtype=torch.float32, device=dev) for _ in range(2)]
+    lengths = np.full(N, L, np.int32)
+    for c in range(a.warmup):
+        dec.synthesis_ranges(store, calls[c][0], calls[c][1], lengths, out=pcm[c % 2])
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    got_sum = 0
+    for c in range(a.warmup, ncalls):                     # the range calls only (the host plans each call)
+        _, got = dec.synthesis_ranges(store, calls[c][0], calls[c][1], lengths, out=pcm[c % 2])
+        got_sum += int(got.sum())
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1)
+    res = {
+        "metric": "decode_ranges_ms", "streams": S, "signals": K, "channels": ch, "rate": rate, "quality": a.quality,
+        "ranges_per_call": N, "range_seconds": a.range_seconds, "max_batch": a.max_batch, "calls": a.steps,
+        "ms_per_call": ms / a.steps, "ranges_per_s": N * a.steps / (ms / 1e3),
+        "audio_s_per_wall_s": got_sum / rate / (ms / 1e3), "rows_per_call": rows / a.steps,
+        "preroll_share": preroll / max(rows, 1), "blocksizes": list(ds.blocksizes),
+    }
+    print(json.dumps(res))
+    store.close()
     dec.close()
     ds.close()
 

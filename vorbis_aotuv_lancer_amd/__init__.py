@@ -1,5 +1,6 @@
 """vorbis_aotuv_lancer_amd — MI355X-native batched Vorbis (aoTuV) encode path, plus a batched
-device decoder (DecodeSetup, Decoder: Vorbis packets -> PCM; decode_ogg: .ogg files -> PCM).
+device decoder (DecodeSetup, Decoder: Vorbis packets -> PCM; decode_ogg: .ogg files -> PCM; OggIndex: random sample
+windows of many .ogg files).
 
 Host-side mirror (Python) of the reference's per-block encode interface over the C ABI in
 include/vorbis_mi355x.h.  PyTorch is used only as plumbing (device memory, streams,
@@ -13,7 +14,7 @@ from .mdct import MdctLookup, mdct_forward, window_mdct, window_fft_log  # noqa:
 
 from .encoder import Setup, Encoder, FrontEnd, PacketInfo  # noqa: F401,E402
 from .stream import header_packets, OggStream, write_ogg, read_ogg, demux_ogg  # noqa: F401,E402
-from .decoder import DecodeSetup, Decoder, decode_ogg  # noqa: F401,E402
+from .decoder import DecodeSetup, Decoder, decode_ogg, decode_index, RangeStore, OggIndex  # noqa: F401,E402
 
-__all__ = ["Setup", "Encoder", "FrontEnd", "PacketInfo", "header_packets", "OggStream", "write_ogg", "read_ogg", "demux_ogg", "DecodeSetup", "Decoder", "decode_ogg", "lib", "LIB_PATH", "COMPAT_LIB_PATH", "VbmError", "check", "window_table",
+__all__ = ["Setup", "Encoder", "FrontEnd", "PacketInfo", "header_packets", "OggStream", "write_ogg", "read_ogg", "demux_ogg", "DecodeSetup", "Decoder", "decode_ogg", "decode_index", "RangeStore", "OggIndex", "lib", "LIB_PATH", "COMPAT_LIB_PATH", "VbmError", "check", "window_table",
            "MdctLookup", "mdct_forward", "window_mdct", "window_fft_log"]

@@ -131,6 +131,14 @@ SIGNATURES = {
                                 C.c_void_p, C.c_void_p]),
     "vbm_decoder_fetch": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_char),
                                     C.c_void_p]),
+    "vbm_decode_index": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]),
+    "vbm_range_store_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "vbm_range_store_destroy": (None, [C.c_void_p]),
+    "vbm_range_store_totals": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vbm_synthesis_ranges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

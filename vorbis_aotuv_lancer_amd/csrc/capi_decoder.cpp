@@ -8,6 +8,13 @@
 // vbm_synthesis_runs enqueues the same unpack (from CSR offsets), spectrum and IMDCT launches over rows that are runs of
 // consecutive packets of one stream, then k_run_plan, k_overlap_runs and k_run_commit in place of k_overlap.  The run
 // table (stream ids and run starts) goes up through the same staging ring.
+//
+// vbm_synthesis_ranges decodes sample windows of the streams of a range store (packets and index in device memory).
+// The host plans pieces (a pre-roll packet and the packets after it) from the store's host index; per sub-call the
+// piece table goes up through the staging ring, then k_range_rows, k_unpack_rows, the same spectrum and IMDCT
+// launches, k_range_plan and k_overlap_runs.  No stream state is read or written.
+#include <algorithm>
+#include <climits>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -34,12 +41,13 @@ struct vbm_decoder {
     int *d_ids = nullptr, *d_info = nullptr, *d_fit = nullptr, *d_flags = nullptr, *d_status = nullptr;
     int *d_lists = nullptr, *d_counts = nullptr;
     int *d_runtab = nullptr, *d_plan = nullptr, *d_run_last = nullptr;   // runs: [2S+1], [cap][6], [S]
+    int *d_rtab = nullptr, *d_rows = nullptr, *d_zero = nullptr;         // ranges: [4 cap + 1], [cap], [cap] zeros
     float *d_res = nullptr, *d_spec = nullptr, *d_imdct = nullptr;
     uint8_t *d_cls = nullptr;
     float *d_tail = nullptr;
     int *d_prevW = nullptr;
     long long *d_gp = nullptr, *d_sc = nullptr;
-    int *h_stage[kStage] = {};       // max(cap, 2S+1) ints each
+    int *h_stage[kStage] = {};       // max(2S+1, 4 cap + 1) ints each
     hipEvent_t ev_stage[kStage] = {};
     int stage_turn = 0;
     std::vector<uint8_t> seen;
@@ -83,7 +91,7 @@ void free_decoder(vbm_decoder *d)
     if (!d) return;
     void *bufs[] = {d->d_setup, d->d_tables, d->d_ids, d->d_info, d->d_fit, d->d_flags, d->d_status, d->d_lists,
                     d->d_counts, d->d_res, d->d_spec, d->d_imdct, d->d_cls, d->d_tail, d->d_prevW, d->d_gp, d->d_sc,
-                    d->d_runtab, d->d_plan, d->d_run_last};
+                    d->d_runtab, d->d_plan, d->d_run_last, d->d_rtab, d->d_rows, d->d_zero};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     for (int i = 0; i < kStage; i++) {
@@ -187,10 +195,15 @@ extern "C" int vbm_decoder_create(vbm_decoder **out, const vbm_decode_setup *ds,
     CK(hipMalloc((void **)&d->d_prevW, (size_t)nstreams * sizeof(int)));
     CK(hipMalloc((void **)&d->d_gp, (size_t)nstreams * sizeof(long long)));
     CK(hipMalloc((void **)&d->d_sc, (size_t)nstreams * sizeof(long long)));
-    const size_t runtab = 2 * (size_t)nstreams + 1, stage = cap > runtab ? cap : runtab;
+    // range piece tables: at most cap / 2 pieces (each has two rows or more) of 7 ints, and the row starts
+    const size_t runtab = 2 * (size_t)nstreams + 1, rtab = 4 * cap + 1, stage = rtab > runtab ? rtab : runtab;
     CK(hipMalloc((void **)&d->d_runtab, runtab * sizeof(int)));
     CK(hipMalloc((void **)&d->d_plan, cap * 6 * sizeof(int)));
     CK(hipMalloc((void **)&d->d_run_last, (size_t)nstreams * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_rtab, rtab * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_rows, cap * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_zero, cap * sizeof(int)));
+    CK(hipMemset(d->d_zero, 0, cap * sizeof(int)));
     for (int i = 0; i < kStage; i++) {
         CK(hipHostMalloc((void **)&d->h_stage[i], stage * sizeof(int), hipHostMallocDefault));
         CK(hipEventCreateWithFlags(&d->ev_stage[i], hipEventDisableTiming));
@@ -327,4 +340,185 @@ extern "C" int vbm_decoder_fetch(vbm_decoder *d, const char *name, void *d_out, 
     else if (!strcmp(name, "floor_used")) return vbmd_launch_used(d->d_flags, (int *)d_out, (long)nsb * d->ch, q) ? VBM_EHIP : VBM_OK;
     else return vbmd_launch_spectrum(L, nullptr, (int *)d_out, q) ? VBM_EHIP : VBM_OK;   // floor line from the posts
     return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "hipMemcpyAsync(decoder fetch)");
+}
+
+// ---- range stores and range calls ----------------------------------------------------------------------------------
+struct vbm_range_store {
+    vbm_decoder *dec = nullptr;
+    int S = 0;
+    std::vector<long long> first;        // [S + 1] first packet of each stream
+    std::vector<int> status;             // [P] host index
+    std::vector<long long> out_end;      // [P] out_start + samples
+    std::vector<long long> totals;       // [S]
+    long long data_bytes = 0;
+    uint8_t *d_data = nullptr;
+    long long *d_offsets = nullptr, *d_out_start = nullptr;   // [P + 1], [P]
+    int *d_begin = nullptr, *d_end = nullptr;                 // [P]
+};
+
+namespace {
+
+void free_store(vbm_range_store *st)
+{
+    if (!st) return;
+    void *bufs[] = {st->d_data, st->d_offsets, st->d_out_start, st->d_begin, st->d_end};
+    for (void *p : bufs)
+        if (p) (void)hipFree(p);
+    delete st;
+}
+
+struct range_piece {
+    int r, pre, first, count;            // output row, pre-roll packet, first packet after it, packets after it
+};
+
+}  // namespace
+
+extern "C" int vbm_range_store_create(vbm_range_store **out, vbm_decoder *d, int nstreams,
+                                      const long long *stream_packets, const uint8_t *data, const long long *offsets,
+                                      long long data_bytes, const long long *granulepos, const uint8_t *eos)
+{
+    if (!out || !d || nstreams <= 0 || !stream_packets || data_bytes < 0 || (data_bytes > 0 && !data) || !offsets)
+        return VBM_EINVAL;
+    *out = nullptr;
+    if (stream_packets[0] != 0) { g_vbm_err = "stream_packets[0] must be 0"; return VBM_EINVAL; }
+    for (int i = 0; i < nstreams; i++)
+        if (stream_packets[i + 1] < stream_packets[i]) { g_vbm_err = "stream_packets must not decrease"; return VBM_EINVAL; }
+    const long long P = stream_packets[nstreams];
+    if (P >= INT_MAX) { g_vbm_err = "more than 2^31 - 2 packets in one store"; return VBM_EINVAL; }
+    vbm_range_store *st = new vbm_range_store();
+    st->dec = d;
+    st->S = nstreams;
+    st->first.assign(stream_packets, stream_packets + nstreams + 1);
+    st->status.resize((size_t)P);
+    st->out_end.resize((size_t)P);
+    st->totals.resize((size_t)nstreams);
+    st->data_bytes = data_bytes;
+    std::vector<int> begin((size_t)P), end((size_t)P);
+    std::vector<long long> out_start((size_t)P);
+    for (int i = 0; i < nstreams; i++) {
+        const long long a = stream_packets[i];
+        vbmd_index_stream(d->hs, stream_packets[i + 1] - a, data, offsets + a, data_bytes,
+                          granulepos ? granulepos + a : nullptr, eos ? eos + a : nullptr, st->status.data() + a,
+                          begin.data() + a, end.data() + a, out_start.data() + a, &st->totals[i]);
+    }
+    for (long long k = 0; k < P; k++) st->out_end[k] = out_start[k] + (end[k] - begin[k]);
+    hipError_t e = hipSuccess;
+#define CK(x) do { e = (x); if (e != hipSuccess) { int rc = vbm_set_hip_error(e, #x); free_store(st); return rc; } } while (0)
+    const size_t np = (size_t)P;
+    CK(hipMalloc((void **)&st->d_data, data_bytes > 0 ? (size_t)data_bytes : 1));
+    CK(hipMalloc((void **)&st->d_offsets, (np + 1) * sizeof(long long)));
+    CK(hipMalloc((void **)&st->d_out_start, (np ? np : 1) * sizeof(long long)));
+    CK(hipMalloc((void **)&st->d_begin, (np ? np : 1) * sizeof(int)));
+    CK(hipMalloc((void **)&st->d_end, (np ? np : 1) * sizeof(int)));
+    if (data_bytes > 0) CK(hipMemcpy(st->d_data, data, (size_t)data_bytes, hipMemcpyHostToDevice));
+    CK(hipMemcpy(st->d_offsets, offsets, (np + 1) * sizeof(long long), hipMemcpyHostToDevice));
+    if (np) {
+        CK(hipMemcpy(st->d_out_start, out_start.data(), np * sizeof(long long), hipMemcpyHostToDevice));
+        CK(hipMemcpy(st->d_begin, begin.data(), np * sizeof(int), hipMemcpyHostToDevice));
+        CK(hipMemcpy(st->d_end, end.data(), np * sizeof(int), hipMemcpyHostToDevice));
+    }
+#undef CK
+    *out = st;
+    return VBM_OK;
+}
+
+extern "C" void vbm_range_store_destroy(vbm_range_store *st)
+{
+    if (!st) return;
+    (void)hipDeviceSynchronize();
+    free_store(st);
+}
+
+extern "C" int vbm_range_store_totals(const vbm_range_store *st, long long *totals)
+{
+    if (!st || !totals) return VBM_EINVAL;
+    std::copy(st->totals.begin(), st->totals.end(), totals);
+    return VBM_OK;
+}
+
+extern "C" int vbm_synthesis_ranges(vbm_decoder *d, const vbm_range_store *st, int nranges, const int *stream_ids,
+                                    const long long *starts, const int *lengths, float *d_pcm, long pcm_stride,
+                                    int *got, void *stream)
+{
+    if (!d || !st || nranges < 0 || (nranges > 0 && (!stream_ids || !starts || !lengths || !got)))
+        return VBM_EINVAL;
+    if (st->dec != d) { g_vbm_err = "the range store belongs to another decoder"; return VBM_EINVAL; }
+    if (d->cap < 2) { g_vbm_err = "range calls need max_batch >= 2"; return VBM_EINVAL; }
+    long most = 0;
+    bool any = false;
+    for (int r = 0; r < nranges; r++) {
+        if (stream_ids[r] < 0 || stream_ids[r] >= st->S) { g_vbm_err = "stream id out of range"; return VBM_EINVAL; }
+        if (starts[r] < 0 || lengths[r] < 0) { g_vbm_err = "negative start or length"; return VBM_EINVAL; }
+        if (lengths[r] > most) most = lengths[r];
+        any |= lengths[r] > 0 && starts[r] < st->totals[stream_ids[r]];
+    }
+    if (pcm_stride < most) { g_vbm_err = "pcm_stride below max(lengths)"; return VBM_EINVAL; }
+    if (any && !d_pcm) return VBM_EINVAL;
+    // plan: per range the packets k (first with output past s) .. m (holds s + got - 1) after the pre-roll p (the
+    // last valid packet before k), cut into pieces of at most max_batch rows; pieces packed into sub-calls
+    const int cap = d->cap;
+    std::vector<range_piece> pieces;
+    std::vector<int> call_first{0}, call_r0;             // per sub-call: first piece, first output row
+    int rows = 0;
+    for (int r = 0; r < nranges; r++) {
+        const int i = stream_ids[r];
+        const long long total = st->totals[i], s = starts[r];
+        got[r] = (int)std::max(0LL, std::min(total - s, (long long)lengths[r]));
+        if (got[r] == 0) continue;
+        const long long *oe = st->out_end.data();
+        const long long a = st->first[i], b = st->first[i + 1];
+        const int k = (int)(std::upper_bound(oe + a, oe + b, s) - oe);
+        const int m = (int)(std::upper_bound(oe + a, oe + b, s + got[r] - 1) - oe);
+        int pre = k - 1;
+        while (pre >= a && st->status[pre] != 0) pre--;
+        if (pre < a) { g_vbm_err = "range store index: no pre-roll packet"; return VBM_EINVAL; }   // lW >= 0 at k
+        for (int f = pre + 1; f <= m;) {
+            const int count = std::min(m - f + 1, cap - 1);
+            if (rows + count + 1 > cap || (!call_r0.empty() && r - call_r0.back() >= cap)) {
+                call_first.push_back((int)pieces.size());
+                rows = 0;
+            }
+            if (call_r0.size() < call_first.size()) call_r0.push_back(r);
+            pieces.push_back({r - call_r0.back(), pre, f, count});
+            rows += count + 1;
+            f += count;
+            for (int j = f - 1; j > pre; j--)            // the next piece's pre-roll: this one's last valid packet
+                if (st->status[j] == 0) { pre = j; break; }
+        }
+    }
+    call_first.push_back((int)pieces.size());
+    hipStream_t q = (hipStream_t)stream;
+    std::vector<int> tab;
+    for (size_t c = 0; c + 1 < call_first.size(); c++) {
+        const int p0 = call_first[c], np = call_first[c + 1] - p0;
+        if (np <= 0) continue;
+        tab.assign(1, 0);
+        for (int p = p0; p < p0 + np; p++) tab.push_back(tab.back() + pieces[p].count + 1);
+        const int nsb = tab.back();
+        const int r0 = call_r0[c];
+        for (int p = p0; p < p0 + np; p++) {
+            const range_piece &pc = pieces[p];
+            const unsigned long long s = (unsigned long long)starts[r0 + pc.r];
+            tab.insert(tab.end(), {pc.r, pc.pre, pc.first, (int)(unsigned)(s & 0xffffffffu), (int)(unsigned)(s >> 32),
+                                   got[r0 + pc.r]});
+        }
+        const int *parts[1] = {tab.data()};
+        const int lens[1] = {(int)tab.size()};
+        int rc = stage_ints(d, d->d_rtab, parts, lens, 1, q);
+        if (rc) return rc;
+        hipError_t e = hipMemsetAsync(d->d_counts, 0, 2 * sizeof(int), q);
+        if (e == hipSuccess) e = hipMemsetAsync(d->d_res, 0, (size_t)nsb * d->ch * d->half * sizeof(float), q);
+        if (e != hipSuccess) return vbm_set_hip_error(e, "hipMemsetAsync(decode ranges)");
+        const vbmd_launch L = d->launch(nsb);
+        if (vbmd_launch_unpack_rows(L, np, d->d_rtab, d->d_rows, st->d_data, st->d_offsets, st->data_bytes, q))
+            return VBM_EHIP;
+        if (vbmd_launch_spectrum(L, d->d_spec, nullptr, q)) return VBM_EHIP;
+        for (int W = 0; W < 2; W++)
+            if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W], d->trig[W], q)) return VBM_EHIP;
+        if (vbmd_launch_ranges(L, np, d->d_rtab, d->d_rows, st->d_begin, st->d_end, st->d_out_start, d->d_zero,
+                               d->d_plan, d_pcm + (size_t)r0 * d->ch * pcm_stride, pcm_stride, q))
+            return VBM_EHIP;
+        d->last_nsb = nsb;
+    }
+    return VBM_OK;
 }

@@ -302,14 +302,77 @@ VBMD_HD void vbmd_residue_inverse(const vbmd_setup &s, const uint8_t *blob, cons
 }
 
 // ---- one packet ----------------------------------------------------------------------------------------------------
-// Returns 0, VBM_ENOTAUDIO (-135) or VBM_EBADPACKET (-136), as vorbis_synthesis does.
+// The packet's header bits (vorbis_synthesis, lib/synthesis.c:25-91): packet type, mode, W, lW, nW.  Returns 0,
+// VBM_ENOTAUDIO (-135) or VBM_EBADPACKET (-136).  Nothing after them can make a packet fail, so this decides the
+// status of vbmd_unpack, and the host index (vbmd_index_stream) reads only this.
+VBMD_HD int vbmd_head(const vbmd_setup &s, vbmd_bits &b, int &mode, int &W, int &lW, int &nW)
+{
+    if (vbmd_read(b, 1) != 0) return -135;
+    mode = (int)vbmd_read(b, s.modebits);
+    if (mode < 0 || mode >= s.modes) return -136;
+    W = s.mode_blockflag[mode];
+    lW = 0;
+    nW = 0;
+    if (W) {
+        lW = (int)vbmd_read(b, 1);
+        nW = (int)vbmd_read(b, 1);
+        if (nW == -1) return -136;
+    }
+    return 0;
+}
+
+// vorbis_synthesis_blockin's bookkeeping (lib/block.c:1050-1161) for a valid packet of block size W after one of
+// block size lW (-1: the stream's first): the part of the packet's output that becomes final, [begin, end), and the
+// stream's sample count sc and granulepos gp (-1: none yet), advanced by the packet's granulepos vgp (-1: none) and
+// its end-of-stream flag.  One definition for k_overlap, k_run_plan and the host index (vbmd_index_stream).
+VBMD_HD void vbmd_blockin(const int *blocksizes, int lW, int W, long long vgp, int eof, long long &sc, long long &gp,
+                          long &begin, long &end)
+{
+    begin = 0;
+    end = 0;
+    if (lW >= 0) end = (blocksizes[lW] >> 2) + (blocksizes[W] >> 2);
+    const long long step = (lW >= 0 ? (blocksizes[lW] >> 2) : 0) + (blocksizes[W] >> 2);
+    sc = (sc == -1) ? 0 : sc + step;
+    if (gp == -1) {
+        if (vgp != -1) {
+            gp = vgp;
+            if (sc > gp) {
+                long long extra = sc - vgp;
+                if (extra < 0) extra = 0;
+                if (eof) {
+                    if (extra > end - begin) extra = end - begin;
+                    end -= extra;
+                } else {
+                    begin += extra;
+                    if (begin > end) begin = end;
+                }
+            }
+        }
+    } else {
+        gp += step;
+        if (vgp != -1 && gp != vgp) {
+            if (gp > vgp) {
+                long long extra = gp - vgp;
+                if (extra && eof) {
+                    if (extra > end - begin) extra = end - begin;
+                    if (extra < 0) extra = 0;
+                    end -= extra;
+                }
+            }
+            gp = vgp;
+        }
+    }
+}
+
+// Returns vbmd_head's status.
 //   info[4]      mode, W, lW, nW
 //   fit          [channels][VBMD_POSTS] floor Y values (valid where bit 0 of flags is set)
 //   flags        [channels] bit 0: the channel's floor is coded, bit 1: nonzero after the coupling propagation
 //   res          [channels][stride] residue before inverse coupling; must be zero on entry (bins < blocksize/2 used)
 //   cls          partition-class scratch, s.max_classes bytes
-// Copy: one instantiation per kernel that calls it (k_unpack the default, k_unpack_csr 1), so that each has a single
-// call site and is inlined as it was with one caller, instead of becoming a shared out-of-line function.
+// Copy: one instantiation per kernel that calls it (k_unpack the default, k_unpack_csr 1, k_unpack_rows 2), so that
+// each has a single call site and is inlined as it was with one caller, instead of becoming a shared out-of-line
+// function.
 template <int Copy = 0>
 VBMD_HD int vbmd_unpack(const vbmd_setup &s, const uint8_t *blob, const uint8_t *pkt, long bytes, int *info, int *fit,
                         int *flags, float *res, long stride, uint8_t *cls)
@@ -317,16 +380,9 @@ VBMD_HD int vbmd_unpack(const vbmd_setup &s, const uint8_t *blob, const uint8_t 
     vbmd_bits b = {pkt, bytes < 0 ? 0 : bytes, 0};
     info[0] = info[1] = info[2] = info[3] = 0;
     for (int c = 0; c < s.channels; c++) flags[c] = 0;
-    if (vbmd_read(b, 1) != 0) return -135;
-    const int mode = (int)vbmd_read(b, s.modebits);
-    if (mode < 0 || mode >= s.modes) return -136;
-    const int W = s.mode_blockflag[mode];
-    int lW = 0, nW = 0;
-    if (W) {
-        lW = (int)vbmd_read(b, 1);
-        nW = (int)vbmd_read(b, 1);
-        if (nW == -1) return -136;
-    }
+    int mode, W, lW, nW;
+    const int head = vbmd_head(s, b, mode, W, lW, nW);
+    if (head) return head;
     info[0] = mode;
     info[1] = W;
     info[2] = lW;

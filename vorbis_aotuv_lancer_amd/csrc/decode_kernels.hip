@@ -19,6 +19,11 @@
 //   k_overlap_runs   one workgroup per row: k_overlap's overlap-add expression into the run's PCM at the planned offset
 //   k_run_commit     one workgroup per run: the last valid row's second half -> the stream's tail (a separate launch:
 //                    the first row of a run reads the tail that this writes)
+//
+// Ranges (vbm_synthesis_ranges): rows are pieces of a range store's streams, each a pre-roll packet and the packets
+// after it.  k_range_rows maps rows to store packets, k_unpack_rows unpacks them from the store, k_spectrum and
+// k_imdct* are the same launches, k_range_plan writes k_run_plan's entries from the store's index and k_overlap_runs
+// runs unchanged.  No stream state is read or written.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -363,43 +368,12 @@ void k_overlap(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict_
     const int W = info[4 * row + 1], lW = prevW[sid];
     const int bs0 = s->blocksizes[0], bs1 = s->blocksizes[1];
     const int n = s->blocksizes[W] >> 1, n0 = bs0 >> 1, nh1 = bs1 >> 1;
-    // vorbis_synthesis_blockin: what becomes final, and the granulepos bookkeeping (lib/block.c:1050-1161)
-    long begin = 0, end = 0;
-    if (lW >= 0) end = (s->blocksizes[lW] >> 2) + (s->blocksizes[W] >> 2);
+    // vorbis_synthesis_blockin: what becomes final, and the granulepos bookkeeping
     long long sc = st_sc[sid], gp = st_gp[sid];
     const long long vgp = granulepos ? granulepos[row] : -1;
     const int eof = eos ? eos[row] : 0;
-    const long long step = (lW >= 0 ? (s->blocksizes[lW] >> 2) : 0) + (s->blocksizes[W] >> 2);
-    sc = (sc == -1) ? 0 : sc + step;
-    if (gp == -1) {
-        if (vgp != -1) {
-            gp = vgp;
-            if (sc > gp) {
-                long long extra = sc - vgp;
-                if (extra < 0) extra = 0;
-                if (eof) {
-                    if (extra > end - begin) extra = end - begin;
-                    end -= extra;
-                } else {
-                    begin += extra;
-                    if (begin > end) begin = end;
-                }
-            }
-        }
-    } else {
-        gp += step;
-        if (vgp != -1 && gp != vgp) {
-            if (gp > vgp) {
-                long long extra = gp - vgp;
-                if (extra && eof) {
-                    if (extra > end - begin) extra = end - begin;
-                    if (extra < 0) extra = 0;
-                    end -= extra;
-                }
-            }
-            gp = vgp;
-        }
-    }
+    long begin, end;
+    vbmd_blockin(s->blocksizes, lW, W, vgp, eof, sc, gp, begin, end);
     for (int c = 0; c < ch; c++) {
         const float *p = imdct + ((long)row * ch + c) * n1;
         float *t = tail + ((long)sid * ch + c) * half;
@@ -456,42 +430,10 @@ void k_run_plan(const vbmd_setup *__restrict__ s, int nruns, const int *__restri
             continue;
         }
         const int W = info[4 * k + 1];
-        // k_overlap's bookkeeping, statement for statement
-        long begin = 0, end = 0;
-        if (lW >= 0) end = (s->blocksizes[lW] >> 2) + (s->blocksizes[W] >> 2);
         const long long vgp = granulepos ? granulepos[k] : -1;
         const int eof = eos ? eos[k] : 0;
-        const long long step = (lW >= 0 ? (s->blocksizes[lW] >> 2) : 0) + (s->blocksizes[W] >> 2);
-        sc = (sc == -1) ? 0 : sc + step;
-        if (gp == -1) {
-            if (vgp != -1) {
-                gp = vgp;
-                if (sc > gp) {
-                    long long extra = sc - vgp;
-                    if (extra < 0) extra = 0;
-                    if (eof) {
-                        if (extra > end - begin) extra = end - begin;
-                        end -= extra;
-                    } else {
-                        begin += extra;
-                        if (begin > end) begin = end;
-                    }
-                }
-            }
-        } else {
-            gp += step;
-            if (vgp != -1 && gp != vgp) {
-                if (gp > vgp) {
-                    long long extra = gp - vgp;
-                    if (extra && eof) {
-                        if (extra > end - begin) extra = end - begin;
-                        if (extra < 0) extra = 0;
-                        end -= extra;
-                    }
-                }
-                gp = vgp;
-            }
-        }
+        long begin, end;
+        vbmd_blockin(s->blocksizes, lW, W, vgp, eof, sc, gp, begin, end);   // k_overlap's bookkeeping
         pl[0] = r;
         pl[1] = prev;
         pl[2] = lW;
@@ -569,6 +511,85 @@ void k_run_commit(const vbmd_setup *__restrict__ s, int nruns, const int *__rest
         const float *p = imdct + ((long)last * ch + c) * n1;
         float *t = tail + ((long)sid * ch + c) * half;
         for (int i = tid; i < n; i += blockDim.x) t[i] = p[n + i];
+    }
+}
+
+// Ranges (vbm_synthesis_ranges).  A piece is a pre-roll packet of the store followed by `count` consecutive packets;
+// its rows are contiguous in the call.  rtab: row starts [npieces + 1], then per piece {output row, pre-roll packet,
+// first packet, window start (low, high 32 bits), window length}.  One lane per piece: row -> store packet.
+__global__ __launch_bounds__(64)
+void k_range_rows(int npieces, const int *__restrict__ rtab, int *__restrict__ rows)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npieces) return;
+    const int k0 = rtab[p], k1 = rtab[p + 1];
+    const int *pc = rtab + npieces + 1 + 6 * (long)p;
+    rows[k0] = pc[1];
+    for (int k = k0 + 1; k < k1; k++) rows[k] = pc[2] + (k - k0 - 1);
+}
+
+// k_unpack_csr with the bytes of row k taken from the store's packet rows[k]
+__global__ __launch_bounds__(64)
+void k_unpack_rows(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob, int nsb,
+                   const int *__restrict__ rows, const uint8_t *__restrict__ data,
+                   const long long *__restrict__ offsets, long long data_bytes, int *__restrict__ info,
+                   int *__restrict__ fit, int *__restrict__ flags, float *__restrict__ res, long half,
+                   uint8_t *__restrict__ cls, int *__restrict__ status, int *__restrict__ lists,
+                   int *__restrict__ counts)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nsb) return;
+    const int ch = s->channels;
+    const long j = rows[k];
+    long long b = offsets[j], e = offsets[j + 1];
+    b = b < 0 ? 0 : b > data_bytes ? data_bytes : b;
+    e = e < b ? b : e > data_bytes ? data_bytes : e;
+    const int st = vbmd_unpack<2>(*s, blob, data + b, (long)(e - b), info + 4 * k, fit + (long)k * ch * VBMD_POSTS,
+                                  flags + (long)k * ch, res + (long)k * ch * half, half, cls + (long)k * s->max_classes);
+    status[k] = st;
+    if (st == 0) {
+        const int W = info[4 * k + 1];
+        const int pos = atomicAdd(&counts[W], 1);
+        lists[(long)W * nsb + pos] = k;
+    }
+}
+
+// One lane per piece: k_run_plan's plan entries, with begin / end / out_start from the store's index instead of the
+// carried granulepos state.  The pre-roll row writes nothing (end = 0); every later valid row writes the part of
+// [out_start, out_start + end - begin) that lies in the piece's window, at its offset in the range's output row.
+// Its previous valid row is always inside the piece, so k_overlap_runs never reads a stream's tail.
+__global__ __launch_bounds__(64)
+void k_range_plan(int npieces, const int *__restrict__ rtab, const int *__restrict__ rows,
+                  const int *__restrict__ status, const int *__restrict__ info, const int *__restrict__ pk_begin,
+                  const int *__restrict__ pk_end, const long long *__restrict__ out_start, int *__restrict__ plan)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npieces) return;
+    const int k0 = rtab[p], k1 = rtab[p + 1];
+    const int *pc = rtab + npieces + 1 + 6 * (long)p;
+    const int r = pc[0];
+    const long long ws = (long long)(((unsigned long long)(unsigned)pc[4] << 32) | (unsigned)pc[3]);
+    const long long we = ws + pc[5];
+    int *pl = plan + 6 * (long)k0;
+    pl[0] = r;
+    pl[1] = -1;
+    pl[2] = -1;
+    pl[3] = pl[4] = pl[5] = 0;
+    int prev = k0, lW = info[4 * k0 + 1];
+    for (int k = k0 + 1; k < k1; k++) {
+        if (status[k] != 0) continue;
+        const int j = rows[k];
+        const long long o = out_start[j], b = pk_begin[j], n = pk_end[j] - b;
+        const long long lo = o > ws ? o : ws, hi = o + n < we ? o + n : we;
+        pl = plan + 6 * (long)k;
+        pl[0] = r;
+        pl[1] = prev;
+        pl[2] = lW;
+        pl[3] = hi > lo ? (int)(b + lo - o) : 0;
+        pl[4] = hi > lo ? (int)(b + hi - o) : 0;
+        pl[5] = hi > lo ? (int)(lo - ws) : 0;
+        prev = k;
+        lW = info[4 * k + 1];
     }
 }
 
@@ -683,5 +704,29 @@ int vbmd_launch_runs(const vbmd_launch &L, int nruns, const int *runtab, const l
         hipLaunchKernelGGL(k_run_commit, dim3(nruns), dim3(256), 0, q, L.s, nruns, runtab, run_last, L.info, L.imdct,
                            L.n1, L.tail, L.half);
     }
+    return last_err();
+}
+
+int vbmd_launch_unpack_rows(const vbmd_launch &L, int npieces, const int *rtab, int *rows, const uint8_t *data,
+                            const long long *offsets, long long data_bytes, hipStream_t q)
+{
+    if (L.nsb <= 0) return 0;
+    hipLaunchKernelGGL(k_range_rows, dim3((npieces + 63) / 64), dim3(64), 0, q, npieces, rtab, rows);
+    if (last_err()) return -2;
+    hipLaunchKernelGGL(k_unpack_rows, dim3((L.nsb + 63) / 64), dim3(64), 0, q, L.s, L.blob, L.nsb, rows, data, offsets,
+                       data_bytes, L.info, L.fit, L.flags, L.res, L.half, L.cls, L.status, L.lists, L.counts);
+    return last_err();
+}
+
+int vbmd_launch_ranges(const vbmd_launch &L, int npieces, const int *rtab, const int *rows, const int *pk_begin,
+                       const int *pk_end, const long long *out_start, const int *runtab, int *plan, float *pcm,
+                       long pcm_stride, hipStream_t q)
+{
+    if (L.nsb <= 0) return 0;
+    hipLaunchKernelGGL(k_range_plan, dim3((npieces + 63) / 64), dim3(64), 0, q, npieces, rtab, rows, L.status, L.info,
+                       pk_begin, pk_end, out_start, plan);
+    if (last_err()) return -2;
+    hipLaunchKernelGGL(k_overlap_runs, dim3(L.nsb), dim3(256), 0, q, L.s, runtab, L.status, L.info, plan, L.imdct,
+                       L.n1, L.win0, L.win1, L.tail, pcm, pcm_stride, L.half);
     return last_err();
 }

@@ -602,6 +602,46 @@ extern "C" int vbm_decode_setup_counts(const vbm_decode_setup *ds, int *counts)
     return VBM_OK;
 }
 
+void vbmd_index_stream(const vbmd_setup &s, long long n, const uint8_t *data, const long long *offsets,
+                       long long data_bytes, const long long *granulepos, const uint8_t *eos, int *status, int *begin,
+                       int *end, long long *out_start, long long *total)
+{
+    int lW = -1;
+    long long sc = -1, gp = -1, at = 0;
+    for (long long k = 0; k < n; k++) {
+        long long b = offsets[k], e = offsets[k + 1];
+        b = b < 0 ? 0 : b > data_bytes ? data_bytes : b;
+        e = e < b ? b : e > data_bytes ? data_bytes : e;
+        vbmd_bits bits = {data + b, (long)(e - b), 0};
+        int mode, W, plW, nW;
+        status[k] = vbmd_head(s, bits, mode, W, plW, nW);
+        long pb = 0, pe = 0;
+        if (status[k] == 0) {
+            vbmd_blockin(s.blocksizes, lW, W, granulepos ? granulepos[k] : -1, eos ? eos[k] : 0, sc, gp, pb, pe);
+            lW = W;
+        }
+        if (begin) begin[k] = (int)pb;
+        if (end) end[k] = (int)pe;
+        out_start[k] = at;
+        at += pe - pb;
+    }
+    *total = at;
+}
+
+extern "C" int vbm_decode_index(const vbm_decode_setup *ds, long long npackets, const uint8_t *data,
+                                const long long *offsets, long long data_bytes, const long long *granulepos,
+                                const uint8_t *eos, int *status, int *samples, long long *out_start, long long *total)
+{
+    if (!ds || npackets < 0 || data_bytes < 0 || (data_bytes > 0 && !data) || !offsets || !total ||
+        (npackets > 0 && (!status || !samples || !out_start)))
+        return VBM_EINVAL;
+    std::vector<int> b((size_t)npackets), e((size_t)npackets);
+    vbmd_index_stream(ds->s, npackets, data, offsets, data_bytes, granulepos, eos, status, b.data(), e.data(),
+                      out_start, total);
+    for (long long k = 0; k < npackets; k++) samples[k] = e[k] - b[k];
+    return VBM_OK;
+}
+
 extern "C" int vbm_host_unpack_packet(const vbm_decode_setup *ds, const uint8_t *packet, long bytes, int *info,
                                       int *floor_index, float *residue, int *floor_used)
 {

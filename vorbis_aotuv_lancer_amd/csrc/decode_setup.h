@@ -11,4 +11,11 @@ struct vbm_decode_setup {
     std::vector<float> win[2];        // rising half-windows of blocksizes[0] and [1] (_vorbis_window_get)
 };
 
+// The host index of one stream's n packets (CSR as vbm_synthesis_runs takes them, clamped to [0, data_bytes)), from a
+// fresh stream state: per packet the status (vbmd_head) and, for valid packets, vbmd_blockin's [begin, end) (0, 0 for
+// failed ones) and out_start, the exclusive prefix sum of end - begin; *total = the sum.  begin / end may be NULL.
+void vbmd_index_stream(const vbmd_setup &s, long long n, const uint8_t *data, const long long *offsets,
+                       long long data_bytes, const long long *granulepos, const uint8_t *eos, int *status, int *begin,
+                       int *end, long long *out_start, long long *total);
+
 void vbmd_host_floor_index(const vbmd_setup &s, const vbmd_floor &f, const int *fit, int n, int *out);

@@ -155,6 +155,32 @@ class Decoder:
             self._last = (P, dev, data, offsets, gp, eo)      # inputs stay alive until the work has run
         return pcm, run_samples, samples, status
 
+    def synthesis_ranges(self, store, stream_ids, starts, lengths, pcm_stride=None, out=None):
+        """Sample windows of a RangeStore's streams: range r is lengths[r] samples of stream stream_ids[r] from sample
+        starts[r] of its linear decode (host ints).  pcm_stride defaults to max(lengths).
+        -> (pcm float32 [n, channels, pcm_stride] on the device, got int32 [n] numpy), pcm[r, :, :got[r]] bit for bit
+        the linear decode's samples; nothing else of pcm is written.  Reads and writes no stream state; only
+        enqueues work on the current stream."""
+        ids = np.ascontiguousarray(np.asarray(stream_ids, dtype=np.int32))
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.int64))
+        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32))
+        if not (ids.ndim == st.ndim == ln.ndim == 1 and len(ids) == len(st) == len(ln)):
+            raise ValueError("stream_ids, starts and lengths must be 1-D and of the same length")
+        n = len(ids)
+        if pcm_stride is None:
+            pcm_stride = max(1, int(ln.max(initial=0)))
+        if out is None:
+            pcm = torch.empty((n, self.channels, pcm_stride), dtype=torch.float32,
+                              device=torch.device("cuda", torch.cuda.current_device()))
+        else:
+            pcm = out
+            pcm_stride = pcm.stride(1)
+        got = np.zeros(n, np.int32)
+        check(lib.vbm_synthesis_ranges(self._h, store._h, n, ids.ctypes.data, st.ctypes.data, ln.ctypes.data,
+                                       pcm.data_ptr(), pcm_stride, got.ctypes.data, self._stream()),
+              "vbm_synthesis_ranges")
+        return pcm, got
+
     def fetch(self, name):
         """Intermediate of the last call: "info" [nsb, 4], "floor_used" [nsb, ch], "floor_index" / "residue" /
         "spectrum" [nsb, ch, blocksizes[1]//2]."""
@@ -193,6 +219,122 @@ class Decoder:
             self.close()
         except Exception:
             pass
+
+
+def decode_index(dsetup, data, offsets, granulepos=None, eos=None):
+    """Host index of one stream's demuxed packets (vbm_decode_index; no device needed): data uint8 [bytes], offsets
+    int64 [P+1], granulepos int64 [P], eos uint8 [P] (numpy, as demux_ogg returns them).
+    -> (status int32 [P], samples int32 [P], out_start int64 [P], total)"""
+    data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8))
+    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    P = len(offsets) - 1
+    if P < 0:
+        raise ValueError("offsets needs at least one entry")
+    gp = None if granulepos is None else np.ascontiguousarray(np.asarray(granulepos, dtype=np.int64))
+    eo = None if eos is None else np.ascontiguousarray(np.asarray(eos, dtype=np.uint8))
+    if (gp is not None and len(gp) != P) or (eo is not None and len(eo) != P):
+        raise ValueError("granulepos and eos need one entry per packet")
+    status, samples = np.zeros(P, np.int32), np.zeros(P, np.int32)
+    out_start = np.zeros(P, np.int64)
+    total = C.c_longlong()
+    check(lib.vbm_decode_index(dsetup._h, P, data.ctypes.data if len(data) else None, offsets.ctypes.data, len(data),
+                               None if gp is None else gp.ctypes.data, None if eo is None else eo.ctypes.data,
+                               status.ctypes.data, samples.ctypes.data, out_start.ctypes.data, C.byref(total)),
+          "vbm_decode_index")
+    return status, samples, out_start, total.value
+
+
+class RangeStore:
+    """The packets of many streams of one Decoder's headers in device memory, with their index, for
+    Decoder.synthesis_ranges.  streams: (data, offsets, granulepos, eos) tuples as demux_ogg returns them (granulepos
+    / eos may be None).  .totals: int64 [nstreams], each stream's linear decode length (ov_pcm_total)."""
+
+    def __init__(self, decoder, streams):
+        streams = list(streams)
+        if not streams:
+            raise ValueError("a range store needs at least one stream")
+        datas, offs, gps, eoss, first, base = [], [np.zeros(1, np.int64)], [], [], [0], 0
+        for data, o, gp, eo in streams:
+            data = np.asarray(data, dtype=np.uint8).ravel()
+            o = np.asarray(o, dtype=np.int64)
+            P = len(o) - 1
+            datas.append(data)
+            offs.append(o[1:] + base)
+            gps.append(np.full(P, -1, np.int64) if gp is None else np.asarray(gp, dtype=np.int64))
+            eoss.append(np.zeros(P, np.uint8) if eo is None else np.asarray(eo, dtype=np.uint8))
+            first.append(first[-1] + P)
+            base += len(data)
+        data = np.ascontiguousarray(np.concatenate(datas)) if datas else np.zeros(0, np.uint8)
+        offsets = np.ascontiguousarray(np.concatenate(offs))
+        gp = np.ascontiguousarray(np.concatenate(gps))
+        eo = np.ascontiguousarray(np.concatenate(eoss))
+        first = np.ascontiguousarray(np.asarray(first, np.int64))
+        self.decoder, self.nstreams = decoder, len(streams)
+        self.packets = first
+        self._h = C.c_void_p()
+        check(lib.vbm_range_store_create(C.byref(self._h), decoder._h, len(streams), first.ctypes.data,
+                                         data.ctypes.data if len(data) else None, offsets.ctypes.data, len(data),
+                                         gp.ctypes.data, eo.ctypes.data), "vbm_range_store_create")
+        self.totals = np.zeros(len(streams), np.int64)
+        check(lib.vbm_range_store_totals(self._h, self.totals.ctypes.data), "vbm_range_store_totals")
+
+    def close(self):
+        if self._h:
+            lib.vbm_range_store_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OggIndex:
+    """Random sample windows of many .ogg files (bytes or paths, one logical stream each, one set of headers: files
+    whose identification or setup headers differ are a ValueError).  The files' packets and index stay in device
+    memory (about the compressed size + 24 B per packet); no PCM is kept.  .total_samples: int64 [files].
+    decode_ranges(file_ids, starts, lengths) -> (pcm float32 [n, channels, max(lengths)] CUDA tensor, zeros past got;
+    got int32 [n]), pcm[r, :, :got[r]] bit for bit decode_ogg's output of that file from starts[r]."""
+
+    def __init__(self, files, max_batch=4096):
+        from .stream import demux_ogg
+        if max_batch < 2:
+            raise ValueError("max_batch must be at least 2")
+        demuxed = []
+        for i, f in enumerate(files):
+            name = os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}"
+            if isinstance(f, (str, os.PathLike)):
+                with open(f, "rb") as fh:
+                    f = fh.read()
+            try:
+                demuxed.append(demux_ogg(f))
+            except VbmError as e:
+                raise VbmError(f"{name}: {e}") from None
+        if not demuxed:
+            raise ValueError("OggIndex needs at least one file")
+        h0 = demuxed[0][0]
+        for i, d in enumerate(demuxed):
+            if d[0][0] != h0[0] or d[0][2] != h0[2]:
+                raise ValueError(f"file {i} has other identification or setup headers than file 0: one OggIndex "
+                                 "takes one header class")
+        self.setup = DecodeSetup(h0)
+        self.channels, self.rate = self.setup.channels, self.setup.rate
+        self.decoder = Decoder(self.setup, 1, max_batch)
+        self.store = RangeStore(self.decoder, [d[1:] for d in demuxed])
+        self.total_samples = self.store.totals
+
+    def decode_ranges(self, file_ids, starts, lengths):
+        ln = np.asarray(lengths, dtype=np.int64)
+        L = max(1, int(ln.max(initial=0)))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        pcm = torch.zeros((len(ln), self.channels, L), dtype=torch.float32, device=dev)
+        return self.decoder.synthesis_ranges(self.store, file_ids, starts, lengths, out=pcm)
+
+    def close(self):
+        self.store.close()
+        self.decoder.close()
+        self.setup.close()
 
 
 def decode_ogg(files, max_packets=4096):
