@@ -12,7 +12,7 @@
 //   k_res_vq        res*_class (_01class lib/res0.c:406-468, _2class :473-526) and the res2
 //                   interleave (:781-787) of its partition slice, then
 //                   the cascade of _01forward (:528-640): _encodepart :384-404 ->
-//                   local_book_besterror :316-378.  A partition's stages only touch that
+//                   local_book_besterror :316-378 (both in vq_search.h).  A partition's stages only touch that
 //                   partition's samples, so partitions are sliced over blockIdx.y; every codeword
 //                   goes to a scratch slot (code | length << 32) and the partition's bit count per
 //                   stage to lenT.
@@ -30,6 +30,7 @@
 #include <stdint.h>
 #include "batch.h"
 #include "kernels.h"
+#include "vq_search.h"
 
 namespace {
 
@@ -85,123 +86,18 @@ __device__ __forceinline__ int book_encode(const vbm_book *bk, int a, BitW &w)
     return bk->lengthlist[a];
 }
 
-// the fields of a book the VQ search reads per vector, fetched once per (partition, stage): the book
-// is addressed per lane, and the compiler cannot hoist its loads over the stores of the search loop
-struct book_regs {
-    int dim, minval, delta, quantvals, used, entries;
-    const signed char *lengthlist;
-    const uint32_t *codelist;
-    const int *used_point, *used_index;
-    const short *used_pack;
-    const int *used_norm;
-};
-__device__ __forceinline__ book_regs load_book(const vbm_book *book)
-{
-    book_regs r;
-    r.dim = book->dim; r.minval = book->minval; r.delta = book->delta; r.quantvals = book->quantvals;
-    r.used = book->used; r.entries = book->entries;
-    r.lengthlist = book->lengthlist; r.codelist = book->codelist;
-    r.used_point = book->used_point; r.used_index = book->used_index;
-    r.used_pack = book->used_pack; r.used_norm = book->used_norm;
-    return r;
-}
-
-// num / den as C computes it (truncation toward zero) for den > 0.  Below 2^23 the correctly rounded float
-// quotient cannot reach the next integer (it is at least 1/den away, the rounding error is below
-// |num| / den * 2^-24), so its truncation is the integer quotient: ~10 instructions instead of ~40.
-__device__ __forceinline__ int div_trunc(int num, int den)
-{
-    if (abs(num) < (1 << 23)) return (int)((float)num / (float)den);
-    return num / den;
-}
-
-// local_book_besterror (lib/res0.c:316-378); a[] is the vector (dim <= 8) in registers
-__device__ __forceinline__ int besterror(const book_regs *book, int *a)
-{
-    const int dim = book->dim;
-    int i, j, o;
-    const int minval = book->minval, del = book->delta, qv = book->quantvals;
-    const int ze = (qv >> 1);
-    int index = 0;
-    int p[VBM_MAX_BOOK_DIM] = {0, 0, 0, 0, 0, 0, 0, 0};
-
-    if (del != 1) {
-        for (i = 0, o = dim; i < dim; i++) {
-            int v = div_trunc(a[--o] - minval + (del >> 1), del);
-            int m = (v < ze ? ((ze - v) << 1) - 1 : ((v - ze) << 1));
-            index = index * qv + (m < 0 ? 0 : (m >= qv ? qv - 1 : m));
-            p[o] = v * del + minval;
-        }
-    } else {
-        for (i = 0, o = dim; i < dim; i++) {
-            int v = a[--o] - minval;
-            int m = (v < ze ? ((ze - v) << 1) - 1 : ((v - ze) << 1));
-            index = index * qv + (m < 0 ? 0 : (m >= qv ? qv - 1 : m));
-            p[o] = v * del + minval;
-        }
-    }
-
-    if (book->lengthlist[index] <= 0) {
-        // exhaustive search over the entries that have a codeword, first minimum wins (lib/res0.c:343-370).
-        // |pt - a|^2 = |pt|^2 - 2 pt.a + |a|^2: the last term is common, so entries are compared by
-        // |pt|^2 - 2 pt.a (same order, same ties); pt.a as packed 16-bit dot products, one 16-byte
-        // load per entry.  Only the winner's index is tracked; its point is fetched afterwards.
-        const int used = book->used;
-        int bi = 0;
-        bool small = book->used_pack != nullptr;
-        for (j = 0; j < dim; j++) small = small && (a[j] >= -32768 && a[j] <= 32767);
-        if (small) {
-            typedef short short2v __attribute__((ext_vector_type(2)));
-            uint32_t pa[4] = {0u, 0u, 0u, 0u};
-            for (j = 0; j < dim; j++) pa[j >> 1] |= ((uint32_t)a[j] & 0xffffu) << ((j & 1) * 16);
-            const uint4 *pk = reinterpret_cast<const uint4 *>(book->used_pack);
-            const int *__restrict__ nrm = book->used_norm;
-            const int words = (dim + 1) >> 1;
-            int best = 0;
-            for (i = 0; i < used; i++) {
-                const uint4 v = pk[i];
-                int dot = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, v.x), __builtin_bit_cast(short2v, pa[0]), 0, false);
-                if (words > 1) dot = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, v.y), __builtin_bit_cast(short2v, pa[1]), dot, false);
-                if (words > 2) {
-                    dot = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, v.z), __builtin_bit_cast(short2v, pa[2]), dot, false);
-                    dot = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, v.w), __builtin_bit_cast(short2v, pa[3]), dot, false);
-                }
-                const int score = nrm[i] - 2 * dot;
-                if (i == 0 || score < best) { best = score; bi = i; }
-            }
-        } else {
-            int best = -1;
-            const int *pt = book->used_point;
-            for (i = 0; i < used; i++, pt += dim) {
-                int dist = 0;
-                for (j = 0; j < dim; j++) {
-                    int val = pt[j] - a[j];
-                    dist += val * val;
-                }
-                if (best == -1 || dist < best) { best = dist; bi = i; }
-            }
-        }
-        if (used > 0) {
-            const int *pt = book->used_point + (size_t)bi * dim;
-            for (j = 0; j < dim; j++) p[j] = pt[j];
-            index = book->used_index[bi];
-        }
-    }
-
-    if (index > -1)
-        for (i = 0; i < dim; i++) a[i] -= p[i];
-    return index;
-}
-
-// which channels of submap `sm` take part, and the residue's vector shape
+// which channels of submap `sm` take part, and the residue's vector shape.  The channel lists are eight 4-bit
+// numbers in one register each (VBM_MAXCH = 8): arrays indexed at run time would live in private memory.
 struct res_view {
     const vbm_residue *r;
     int nb;                       // channels in the submap
-    int chlist[VBM_MAXCH];
+    uint32_t chlist;              // nibble k: k-th channel of the submap
     int used;                     // vectors that are coded (res2: 0 or 1; res0/1: nonzero channels)
-    int vch[VBM_MAXCH];           // res0/1: channel of vector j
+    uint32_t vch;                 // res0/1: nibble j: channel of vector j
     int partvals, spp;
 };
+static_assert(VBM_MAXCH <= 8, "res_view packs a channel list into eight nibbles");
+#define NIB(w, k) ((int)(((w) >> (4 * (k))) & 15u))
 
 __device__ __forceinline__ res_view residue_view(const vbm_batch &b, const vbm_map *info, int sm, size_t col0)
 {
@@ -209,13 +105,15 @@ __device__ __forceinline__ res_view residue_view(const vbm_batch &b, const vbm_m
     v.r = &b.setup->residue[info->residuesubmap[sm]];
     v.nb = 0;
     v.used = 0;
+    v.chlist = 0;
+    v.vch = 0;
     int any = 0;
     for (int j = 0; j < b.ch; j++)
         if (info->chmuxlist[j] == sm) {
             const int nz = b.nonzero[col0 + j] ? 1 : 0;
-            v.chlist[v.nb++] = j;
+            v.chlist |= (uint32_t)j << (4 * v.nb++);
             any |= nz;
-            if (nz && v.r->type != 2) v.vch[v.used++] = j;
+            if (nz && v.r->type != 2) v.vch |= (uint32_t)j << (4 * v.used++);
         }
     if (v.r->type == 2) v.used = any ? 1 : 0;
     v.spp = v.r->grouping;
@@ -555,10 +453,10 @@ __device__ __forceinline__ void res_classify(const vbm_batch &b, const res_view 
             int magmax = 0, angmax = 0;
             int l = rbegin / nb + i * lsteps;
             for (j = 0; j < v.spp; j += nb, l++) {
-                int v0 = abs(IWC(v.chlist[0], l));
+                int v0 = abs(IWC(NIB(v.chlist, 0), l));
                 if (v0 > magmax) magmax = v0;
                 for (k = 1; k < nb; k++) {
-                    int vk = abs(IWC(v.chlist[k], l));
+                    int vk = abs(IWC(NIB(v.chlist, k), l));
                     if (vk > angmax) angmax = vk;
                 }
             }
@@ -574,7 +472,7 @@ __device__ __forceinline__ void res_classify(const vbm_batch &b, const res_view 
             for (j = 0; j < v.used; j++) {
                 int mx = 0, ent = 0;
                 for (k = 0; k < v.spp; k++) {
-                    int a = abs(IWC(v.vch[j], offset + k));
+                    int a = abs(IWC(NIB(v.vch, j), offset + k));
                     if (a > mx) mx = a;
                     ent += a;
                 }
@@ -622,11 +520,11 @@ __global__ void k_res_vq(vbm_batch b, int sm, int nchunks)
             if (r->type == 2) {
                 int l = offset / nb, k = offset - l * nb;      // work[x] = in[x % nb][x / nb]
                 for (int e = 0; e < spp; e++) {
-                    stage[e * 64] = IWC(v.chlist[k], l);
+                    stage[e * 64] = IWC(NIB(v.chlist, k), l);
                     if (++k == nb) { k = 0; l++; }
                 }
             } else {
-                for (int e = 0; e < spp; e++) stage[e * 64] = IWC(v.vch[j], offset + e);
+                for (int e = 0; e < spp; e++) stage[e * 64] = IWC(NIB(v.vch, j), offset + e);
             }
             const int cls = PW(j, i);
             for (int st = 0; st < r->stages; st++) {
@@ -634,24 +532,7 @@ __global__ void k_res_vq(vbm_batch b, int sm, int nchunks)
                 const int bi = (r->secondstages[cls] & (1 << st)) ? r->partbook[cls][st] : -1;
                 if (bi >= 0) {
                     const book_regs bk = load_book(&s->book[bi]);
-                    const book_regs *book = &bk;
-                    const int dim = book->dim;
-                    const int step = spp / dim;
-                    uint64_t *sl = slot + (st * stage_slots + (size_t)j * veclen + offset) * 64;
-                    for (int t = 0; t < step; t++) {
-                        int a[VBM_MAX_BOOK_DIM];
-                        int *src = stage + t * dim * 64;
-                        for (int d = 0; d < dim; d++) a[d] = src[d * 64];
-                        const int entry = besterror(book, a);
-                        for (int d = 0; d < dim; d++) src[d * 64] = a[d];
-                        uint64_t cw = 0;
-                        if (entry >= 0 && entry < book->entries) {
-                            const int len = book->lengthlist[entry];
-                            cw = (uint64_t)book->codelist[entry] | ((uint64_t)(uint32_t)len << 32);
-                            bits += len;
-                        }
-                        sl[(size_t)t * 64] = cw;
-                    }
+                    bits = vq_encode_partition(&bk, stage, spp, slot + (st * stage_slots + (size_t)j * veclen + offset) * 64);
                 }
                 LEN(st, j, i) = bits;
             }

@@ -786,16 +786,15 @@ __global__ __launch_bounds__(FP * FPC) void k_couple_fast(vbm_batch b_in)
                     const unsigned mc = (unsigned)(__ballot(cond && j < jn) >> base);
                     const unsigned mp = (unsigned)(__ballot(cond && phase && j < jn) >> base);
                     const int rp = __popc(mp), pp = __popc(mc & ~mp);
-                    const double term = fabs((double)fabsf(resM) - (double)fabsf(resA));
-                    float residue_def = 0;
-                    for (int t = 0; t < FP; t++) {
-                        const double tt = __shfl(term, base + t);
-                        if ((mc >> t) & 1u) residue_def = (float)((double)residue_def + tt);
-                    }
                     const int ap = rp + pp;
                     if (ap != 0) {
-                        const float temp_def = residue_def = residue_def / ap;
+                        // temp_def = (sum over the bins with `cond`, in bin order, of | |resM| - |resA| |) / ap is formed
+                        // in ONE place, k_couple_m6stats, which ran just before over the same mdctT / iworkT / nonzero
+                        // and left it in m6defT[pi] (ap != 0 and a nonzero channel here are its conditions for a value
+                        // other than -1; couple_m6parts covers every partition with tonefix_end > i below the lowpass)
                         const float *m6 = b.m6defT + (size_t)(col >> 6) * b.sb_slab_words + (col & 63);
+                        const float temp_def = m6[(size_t)pi * 64];
+                        float residue_def = temp_def;
                         const float side = (pi > 0) ? m6[(size_t)(pi - 1) * 64] : -1.f;
                         if (side > 0) residue_def = (float)((double)temp_def * 0.5 + (double)side * 0.5);
                         if (residue_def > 1.f) {
