@@ -370,6 +370,60 @@ void vbm_ogg_stream_destroy(vbm_ogg_stream *os);
 int vbm_ogg_stream_packetin(vbm_ogg_stream *os, const uint8_t *packet, long bytes, int e_o_s, long long granulepos);
 int vbm_ogg_stream_pageout(vbm_ogg_stream *os, int flush, const uint8_t **page, long *bytes);
 
+/* ---- stream wrapper, device form: paging for every stream of an encoder at once ---------------------------------
+ * The same pages as vbm_ogg_stream_* makes, byte for byte, for `nstreams` streams per call and without a host in the
+ * loop: the call consumes what vbm_frontend_encode_rounds_device (or _encode_round / _encode_rounds) leaves in device
+ * memory and leaves one compact byte run per stream, ready to append to that stream's file or socket.  One D2H copy
+ * per write then carries finished Ogg pages.  Rule, state sizes and the output bound: csrc/ogg_mux.h.
+ *   vbm_ogg_mux_create       state for `nstreams` streams on the current device.  max_packet_bytes: the largest packet a
+ *                            row may carry (vbm_encoder_max_packet_bytes).  max_rows_per_stream: the most rows one
+ *                            stream may have in one call (0 = 16, at most 64; a device-built call yields at most its
+ *                            `nrounds`).  queue_bytes: body bytes a stream may keep queued between calls, 0 = the most
+ *                            the paging rule can leave, min(254 * 255, max(4 * max_packet_bytes, 4096 + max_packet_bytes)).
+ *   vbm_host_ogg_mux_create  the same with the state in host memory, for vbm_host_ogg_mux_packets: touches no device.
+ *   vbm_ogg_mux_start_streams  host code: a new stream starts in each listed slot (at most once per call) with its serial
+ *                            number.  Returns the header pages of the listed streams (the three header packets of the
+ *                            setup, then a flush: examples/encoder_example.c:139-157) back to back in host_buf, those
+ *                            of stream_ids[k] at host_offsets[k] .. host_offsets[k+1]; host_buf == NULL only fills
+ *                            host_offsets [n+1] (size query) and resets nothing.  Otherwise the slots' state becomes
+ *                            "header pages written, queue empty" (device mux: on `stream`, complete on return).
+ *   vbm_ogg_mux_packets      rows k < nrows: packet at d_packets + k * packet_stride, d_packet_bytes[k] bytes (negative: no
+ *                            packet), d_info[k] (stream < 0: none), in no stream order; inside a stream the order is
+ *                            info.packetno.  flush != 0 acts as ogg_stream_flush for every stream after its packets.
+ *                            Outputs: the pages of stream s at d_out + d_offsets[s] .. d_offsets[s+1], d_offsets[nstreams]
+ *                            = bytes written; d_status[s] = VBM_MUX_* of stream s, d_status[nstreams] = rows whose
+ *                            stream index was >= nstreams (ignored).  out_capacity must be at least
+ *                            vbm_ogg_mux_out_bound(mux, nrows), the most a call with nrows rows can emit (VBM_EINVAL
+ *                            otherwise, before anything is enqueued).  The call synchronises nothing, allocates
+ *                            nothing and runs on `stream`.
+ *   vbm_host_ogg_mux_packets the same on the CPU with host pointers and a host mux (no device needed).
+ * A stream with a status other than VBM_MUX_OK takes no packet from the failing one on: VBM_MUX_ESTATE for a row of a
+ * stream that has not been started or is past its e_o_s (vbm_ogg_stream_packetin's VBM_EINVAL; the state is unchanged);
+ * VBM_MUX_EROWS (more rows than max_rows_per_stream: none is taken), VBM_MUX_EQUEUE (queue_bytes exceeded) and
+ * VBM_MUX_EPACKET (a packet above max_packet_bytes) lose data and stay set until the slot is started again.  Other
+ * streams are not affected. */
+#define VBM_MUX_OK      0
+#define VBM_MUX_EROWS   1
+#define VBM_MUX_EQUEUE  2
+#define VBM_MUX_ESTATE  3
+#define VBM_MUX_EPACKET 4
+typedef struct vbm_ogg_mux vbm_ogg_mux;
+int vbm_ogg_mux_create(vbm_ogg_mux **mux, const vbm_setup_handle *setup, int nstreams, int max_packet_bytes,
+                       int max_rows_per_stream, int queue_bytes);
+int vbm_host_ogg_mux_create(vbm_ogg_mux **mux, const vbm_setup_handle *setup, int nstreams, int max_packet_bytes,
+                            int max_rows_per_stream, int queue_bytes);
+void vbm_ogg_mux_destroy(vbm_ogg_mux *mux);
+int vbm_ogg_mux_start_streams(vbm_ogg_mux *mux, const int *stream_ids, int n, const int *serialnos, const char *vendor,
+                              const char *const *comments, int ncomments, uint8_t *host_buf, long long cap,
+                              long long *host_offsets, void *stream);
+long long vbm_ogg_mux_out_bound(const vbm_ogg_mux *mux, int nrows);
+int vbm_ogg_mux_packets(vbm_ogg_mux *mux, const uint8_t *d_packets, long long packet_stride, const int *d_packet_bytes,
+                        const vbm_packet_info *d_info, int nrows, int flush, uint8_t *d_out, long long out_capacity,
+                        long long *d_offsets, int *d_status, void *stream);
+int vbm_host_ogg_mux_packets(vbm_ogg_mux *mux, const uint8_t *packets, long long packet_stride, const int *packet_bytes,
+                             const vbm_packet_info *info, int nrows, int flush, uint8_t *out, long long out_capacity,
+                             long long *offsets, int *status);
+
 /* Per-stage timing of vbm_analysis_batch: HIP events are recorded between the pipeline's kernels,
  * on the stream each kernel is launched on, for the next `max_calls` calls; profile_end waits for
  * the device and returns the summed milliseconds per stage over all launches

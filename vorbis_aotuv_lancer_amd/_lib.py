@@ -101,6 +101,16 @@ SIGNATURES = {
     "vbm_ogg_stream_destroy": (None, [C.c_void_p]),
     "vbm_ogg_stream_packetin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_longlong]),
     "vbm_ogg_stream_pageout": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
+    "vbm_ogg_mux_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vbm_host_ogg_mux_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vbm_ogg_mux_destroy": (None, [C.c_void_p]),
+    "vbm_ogg_mux_start_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "vbm_ogg_mux_out_bound": (C.c_longlong, [C.c_void_p, C.c_int]),
+    "vbm_ogg_mux_packets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vbm_host_ogg_mux_packets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "vbm_encoder_stage_count": (C.c_int, []),
     "vbm_encoder_stage_name": (C.c_char_p, [C.c_int]),
     "vbm_host_mdct_trig": (C.c_int, [C.c_int, C.c_void_p]),

@@ -1,11 +1,12 @@
-"""Stream wrapper (host only): the three Vorbis header packets of a Setup and Ogg page framing —
+"""Stream wrapper: the three Vorbis header packets of a Setup and Ogg page framing —
 vorbis_analysis_headerout (reference lib/info.c:636-717) and libogg's ogg_stream_packetin/_pageout
-(page format: reference doc/framing.html) over the C ABI of include/vorbis_mi355x.h."""
+(page format: reference doc/framing.html) over the C ABI of include/vorbis_mi355x.h.  OggStream / write_ogg page one
+stream on the host; OggMux pages every stream of an encoder at once on the device (vbm_ogg_mux_*)."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check
+from ._lib import lib, check, VbmError
 
 
 def header_packets(setup, comments=(), vendor=None):
@@ -68,6 +69,136 @@ def write_ogg(setup, packets, infos, serialno=1, comments=()):
     out += os_.pages(flush=True)
     os_.close()
     return b"".join(out)
+
+
+class OggMux:
+    """Ogg paging for `nstreams` streams at once (vbm_ogg_mux_*): the pages write_ogg makes, byte for byte, from the rows
+    an encode call leaves on the device.  serialnos: one per stream (default: the stream index).
+
+        mux = OggMux(setup, S, enc.max_packet_bytes)
+        headers = mux.start()                                 # list[bytes]: the header pages of every stream
+        out, offsets, status = mux.mux(*fe.encode_rounds_device(2)[:3])
+        # stream s of this call: out[offsets[s]:offsets[s + 1]]; status[s] != 0: see VBM_MUX_* in the C header
+
+    mux() needs a GPU; mux_host() is its CPU twin over numpy arrays, with a state of its own.  start() resets both."""
+
+    OK, EROWS, EQUEUE, ESTATE, EPACKET = 0, 1, 2, 3, 4
+
+    def __init__(self, setup, nstreams, max_packet_bytes, serialnos=None, comments=(), max_rows_per_stream=16,
+                 queue_bytes=0, device=None):
+        import torch
+        self.setup, self.nstreams, self.max_packet_bytes = setup, nstreams, max_packet_bytes
+        self.serialnos = np.arange(nstreams, dtype=np.int32) if serialnos is None else \
+            np.ascontiguousarray(serialnos).astype(np.uint32).astype(np.int32)
+        if len(self.serialnos) != nstreams:
+            raise ValueError("one serial number per stream")
+        self.comments = [c.encode() if isinstance(c, str) else c for c in comments]
+        self._hh, self._h = C.c_void_p(), C.c_void_p()
+        check(lib.vbm_host_ogg_mux_create(C.byref(self._hh), setup._h, nstreams, max_packet_bytes, max_rows_per_stream,
+                                          queue_bytes), "vbm_host_ogg_mux_create")
+        self.device = None
+        if device is not None or torch.cuda.is_available():
+            self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+            with torch.cuda.device(self.device):
+                check(lib.vbm_ogg_mux_create(C.byref(self._h), setup._h, nstreams, max_packet_bytes, max_rows_per_stream,
+                                             queue_bytes), "vbm_ogg_mux_create")
+        self._ring, self._ring_rows, self._ring_at = None, -1, 0
+
+    def out_bound(self, nrows):
+        """most bytes one call with nrows rows can emit (vbm_ogg_mux_out_bound)"""
+        return int(lib.vbm_ogg_mux_out_bound(self._hh, int(nrows)))
+
+    def start(self, stream_ids=None, serialnos=None):
+        """A new stream starts in each listed slot (default: all), optionally with new serial numbers -> the header
+        pages of each as bytes, in the order listed."""
+        ids = np.arange(self.nstreams, dtype=np.int32) if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.int32)
+        if serialnos is not None:
+            self.serialnos[ids] = np.ascontiguousarray(serialnos).astype(np.uint32).astype(np.int32)
+        sn = np.ascontiguousarray(self.serialnos[ids])
+        n = len(ids)
+        arr = (C.c_char_p * max(len(self.comments), 1))(*self.comments)
+        off = np.zeros(n + 1, np.int64)
+        buf = None
+        for h, st in ((self._hh, None),) + (((self._h, C.c_void_p(self._stream())),) if self._h else ()):
+            check(lib.vbm_ogg_mux_start_streams(h, ids.ctypes.data, n, sn.ctypes.data, None, arr, len(self.comments), None, 0,
+                                                off.ctypes.data, st), "vbm_ogg_mux_start_streams")
+            buf = np.zeros(max(int(off[n]), 1), np.uint8)
+            check(lib.vbm_ogg_mux_start_streams(h, ids.ctypes.data, n, sn.ctypes.data, None, arr, len(self.comments),
+                                                buf.ctypes.data, len(buf), off.ctypes.data, st), "vbm_ogg_mux_start_streams")
+        raw = buf.tobytes()
+        return [raw[off[k]:off[k + 1]] for k in range(n)]
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def mux(self, info, packets, nbytes, flush=False):
+        """Rows of one encode call -> (out uint8 [capacity] on the device, offsets int64 [nstreams + 1], status int32
+        [nstreams + 1]), all device tensors complete on the current stream: stream s got out[offsets[s]:offsets[s+1]],
+        offsets[nstreams] bytes in all.  info: the device tensor of FrontEnd.encode_rounds_device, or the host records
+        of encode_round / encode_rounds, which are uploaded on the current stream.  packets uint8 [n, stride >=
+        max_packet_bytes], nbytes int32 [n] on the device.  The outputs live in a ring of three sets sized by
+        vbm_ogg_mux_out_bound: a result stays valid until the third call after it."""
+        import torch
+        if not self._h:
+            raise VbmError("OggMux.mux needs a GPU (mux_host is the CPU twin)")
+        n = int(nbytes.shape[0])
+        if isinstance(info, torch.Tensor):
+            dinfo = info
+        else:
+            rec = np.ascontiguousarray(info)
+            dinfo = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(self.device)
+        if dinfo.numel() < n * 40 or int(packets.shape[0]) < n:
+            raise ValueError("info and packets need one entry per row of nbytes")
+        if n and not (packets.is_cuda and packets.dtype == torch.uint8 and packets.stride(-1) == 1 and nbytes.is_cuda
+                      and nbytes.dtype == torch.int32 and nbytes.is_contiguous() and dinfo.is_contiguous()):
+            raise ValueError("packets: CUDA uint8 rows, nbytes: contiguous CUDA int32")
+        if self._ring is None or self._ring_rows < n:
+            if self._ring is not None:
+                torch.cuda.synchronize(self.device)
+            cap = self.out_bound(n)
+            self._ring = [(torch.empty((cap,), dtype=torch.uint8, device=self.device),
+                           torch.zeros((self.nstreams + 1,), dtype=torch.int64, device=self.device),
+                           torch.zeros((self.nstreams + 1,), dtype=torch.int32, device=self.device)) for _ in range(3)]
+            self._ring_rows, self._ring_at = n, 0
+        out, offsets, status = self._ring[self._ring_at]
+        self._ring_at = (self._ring_at + 1) % 3
+        stride = int(packets.stride(0)) if n and packets.dim() == 2 else self.max_packet_bytes
+        check(lib.vbm_ogg_mux_packets(self._h, packets.data_ptr() if n else None, stride, nbytes.data_ptr() if n else None,
+                                      dinfo.data_ptr() if n else None, n, 1 if flush else 0, out.data_ptr(), out.numel(),
+                                      offsets.data_ptr(), status.data_ptr(), C.c_void_p(self._stream())),
+              "vbm_ogg_mux_packets")
+        self._keep = (dinfo, packets, nbytes)
+        return out, offsets, status
+
+    def mux_host(self, info, packets, nbytes, flush=False):
+        """The CPU twin (vbm_host_ogg_mux_packets) over numpy arrays: info records (PacketInfo fields), packets uint8
+        [n, stride], nbytes int32 [n] -> (out uint8 [bytes], offsets int64 [nstreams + 1], status int32 [nstreams + 1])."""
+        nb = np.ascontiguousarray(nbytes, dtype=np.int32)
+        n = len(nb)
+        rec = np.ascontiguousarray(info)
+        pk = np.ascontiguousarray(packets, dtype=np.uint8)
+        if rec.nbytes < n * 40 or (n and (pk.ndim != 2 or pk.shape[0] < n)):
+            raise ValueError("info and packets need one entry per row of nbytes")
+        out = np.empty(self.out_bound(n), np.uint8)
+        offsets = np.zeros(self.nstreams + 1, np.int64)
+        status = np.zeros(self.nstreams + 1, np.int32)
+        check(lib.vbm_host_ogg_mux_packets(self._hh, pk.ctypes.data if n else None, pk.shape[1] if n else self.max_packet_bytes,
+                                           nb.ctypes.data if n else None, rec.ctypes.data if n else None, n,
+                                           1 if flush else 0, out.ctypes.data, len(out), offsets.ctypes.data,
+                                           status.ctypes.data), "vbm_host_ogg_mux_packets")
+        return out[:offsets[-1]], offsets, status
+
+    def close(self):
+        if self._h:
+            import torch
+            torch.cuda.synchronize(self.device)
+            self._ring = None
+            lib.vbm_ogg_mux_destroy(self._h)
+            self._h = C.c_void_p()
+        if self._hh:
+            lib.vbm_ogg_mux_destroy(self._hh)
+            self._hh = C.c_void_p()
 
 
 def _crc_table():
