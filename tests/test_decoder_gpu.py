@@ -163,11 +163,14 @@ def overlap64(tail, lW, p, W, bs, win):
     return out, p[n:2 * n].copy()
 
 
-def check_pcm_bound(ds, streams_pk, pcm_steps, spec_steps, info_steps, samples_steps):
-    """per stream: the device PCM of every step against float64 IMDCT + window + OLA of the fetched spectrum"""
+def check_pcm_bound(ds, streams_pk, pcm_steps, spec_steps, info_steps, samples_steps, win=None, peaks=None):
+    """per stream: the device PCM of every step against float64 IMDCT + window + OLA of the fetched spectrum.
+    win: the two windows' rising halves (default: the product's own table); peaks: a list that receives every step's
+    float64 peak"""
     import vorbis_aotuv_lancer_amd as v
     bs = ds.blocksizes
-    win = [v.window_table(bs[0]), v.window_table(bs[1])]
+    if win is None:
+        win = [v.window_table(bs[0]), v.window_table(bs[1])]
     worst = 0.0
     for s in range(len(streams_pk)):
         tail, lW = None, -1
@@ -189,6 +192,8 @@ def check_pcm_bound(ds, streams_pk, pcm_steps, spec_steps, info_steps, samples_s
             want = want[:, :ns]
             got = pcm_steps[t][s][:, :ns].astype(np.float64)
             if ns:
+                if peaks is not None:
+                    peaks.append(float(np.abs(want).max()))
                 peak = max(np.abs(want).max(), 1e-3)
                 err = np.abs(got - want).max()
                 worst = max(worst, err / peak)

@@ -1,0 +1,197 @@
+"""The device decoder on streams this project's encoder never writes: unpack and spectrum bit for bit against the
+independent model (tests/vorbis_model.py) on the generated corpus, PCM of every block-size pair within the project's
+bound of a float64 IMDCT + float64 Vorbis window + overlap-add, the runs and ranges paths against the stepwise one on
+synthetic setups, and batches whose row x channel counts do not fill the IMDCT kernels' groups."""
+import numpy as np
+import pytest
+import torch
+
+from tests import vorbis_model as vm
+from tests.test_decode_ranges_gpu import as_stream, check, ranges
+from tests.test_decode_runs_gpu import runs_call, stepwise
+from tests.test_decoder_gpu import check_pcm_bound, rows_tensor
+from tests.test_decoder_model_cpu import NAMES, family, fromdB
+
+PAIR_IDS = [f"{a}_{b}" for a, b in vm.PAIRS]
+
+
+def against_model(dec, results, status, samples, what):
+    """the intermediates of the last call against the model's results, row by row"""
+    got = {n: dec.fetch(n).cpu().numpy() for n in ("info", "floor_used", "floor_index", "residue", "spectrum")}
+    for k, r in enumerate(results):
+        assert status[k] == r["status"], f"{what} row {k}: status"
+        if r["status"]:
+            assert samples[k] == 0 and not got["spectrum"][k].any(), f"{what} row {k}: a failed row gives nothing"
+            continue
+        assert list(got["info"][k]) == r["info"], f"{what} row {k}: info"
+        assert np.array_equal(got["floor_used"][k], r["used"]), f"{what} row {k}: floor used"
+        assert np.array_equal(got["floor_index"][k], r["floor_index"]), f"{what} row {k}: floor index"
+        assert got["residue"][k].tobytes() == r["residue"].tobytes(), f"{what} row {k}: residue"
+        assert got["spectrum"][k].tobytes() == r["spectrum"].tobytes(), f"{what} row {k}: spectrum"
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", range(len(vm.CORPUS)), ids=NAMES)
+def test_device_unpack_and_spectrum_equal_the_model(cuda, k):
+    """every corpus packet of the family as a row of a fresh stream, in one call"""
+    import vorbis_aotuv_lancer_amd as v
+    _, _, h, _, rows, _, bad = family(k)
+    assert not bad, bad[:3]                                     # host unpack = model (the CPU test's statement)
+    ds = v.DecodeSetup(h)
+    dec = v.Decoder(ds, len(rows), len(rows))
+    pk, nb = rows_tensor([p for _, p, _ in rows], cuda)
+    pcm, samples, status = dec.synthesis_batch(list(range(len(rows))), pk, nb)
+    samples, status = samples.cpu().numpy(), status.cpu().numpy()
+    assert not samples.any()                                    # the first packet of a stream returns nothing
+    against_model(dec, [r for _, _, r in rows], status, samples, NAMES[k])
+    dec.close()
+    ds.close()
+
+
+def decode_steps(v, ds, model, streams, cuda, what):
+    """streams of equal length, one packet per stream per call -> the step lists check_pcm_bound takes; every step's
+    intermediates are compared with the model on the way"""
+    S, T = len(streams), len(streams[0])
+    dec = v.Decoder(ds, S, S)
+    pcm_steps, spec_steps, info_steps, samples_steps = [], [], [], []
+    for t in range(T):
+        pk, nb = rows_tensor([streams[s][t][0] for s in range(S)], cuda)
+        gp = torch.tensor([streams[s][t][1] for s in range(S)], dtype=torch.int64, device=cuda)
+        eo = torch.tensor([streams[s][t][2] for s in range(S)], dtype=torch.uint8, device=cuda)
+        pcm, samples, status = dec.synthesis_batch(list(range(S)), pk, nb, granulepos=gp, eos=eo)
+        samples, status = samples.cpu().numpy(), status.cpu().numpy()
+        got = against_model(dec, [model.decode(streams[s][t][0]) for s in range(S)], status, samples, f"{what} step {t}")
+        assert not status.any()
+        pcm_steps.append(pcm.cpu().numpy())
+        spec_steps.append(got["spectrum"])
+        info_steps.append(got["info"])
+        samples_steps.append(samples)
+    dec.close()
+    return pcm_steps, spec_steps, info_steps, samples_steps
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", range(15), ids=PAIR_IDS)
+def test_pcm_of_every_block_size_pair_is_within_the_bound(cuda, k):
+    """Streams whose block-size sequence has every transition; stream 1's lW / nW bits contradict its neighbours (the
+    decoder must go by the real previous block); the last packet is trimmed by its granule position.  The reference
+    overlap-add uses the Vorbis window in float64, not the product's table.  Bound: the project's 1e-5 of the step's
+    float64 peak; every peak is >= 1e-3, so the bound's floor never applies."""
+    import vorbis_aotuv_lancer_amd as v
+    setup, coding = vm.pcm_setup(k)
+    h = vm.pack_headers(setup, coding)
+    ds = v.DecodeSetup(h)
+    assert tuple(ds.blocksizes) == vm.PAIRS[k]
+    model = vm.Model(setup, fromdB())
+    streams = vm.pcm_streams(model, 7000 + k)
+    steps = decode_steps(v, ds, model, streams, cuda, PAIR_IDS[k])
+    # the block-size sequence really has the four transitions, whatever the packets' own lW / nW bits say
+    for s, seq in enumerate(vm.SEQUENCES):
+        W = [int(steps[2][t][s][1]) for t in range(len(seq))]
+        if len({md[0] for md in setup["modes"]}) == 2:
+            assert W == [int(c == "L") for c in seq]
+            assert {(a, b) for a, b in zip(W, W[1:])} == {(0, 0), (0, 1), (1, 0), (1, 1)}
+    total = [sum(int(steps[3][t][s]) for t in range(len(streams[s]))) for s in range(len(streams))]
+    assert total == [pk[-1][1] for pk in streams]              # the granule position of the last packet
+    win = [vm.vorbis_window64(ds.blocksizes[0] // 2), vm.vorbis_window64(ds.blocksizes[1] // 2)]
+    peaks = []
+    worst = check_pcm_bound(ds, streams, *steps, win=win, peaks=peaks)
+    assert min(peaks) >= 1e-3, min(peaks)
+    print(f"\nblock sizes {PAIR_IDS[k]}, {ds.channels} ch: max |pcm - float64 reference| / peak = {worst:.3g} "
+          f"(peaks {min(peaks):.3g} .. {max(peaks):.3g})")
+    ds.close()
+
+
+def with_failed_packets(streams, headers, modes, modebits):
+    """the streams with packets that fail inside them: a header packet, the empty packet, a mode past the last"""
+    out = []
+    for s, pk in enumerate(streams):
+        pk = list(pk)
+        pk.insert(3, (headers[2], -1, 0))
+        pk.insert(6, (b"", -1, 0))
+        if modes < (1 << modebits):
+            w = vm.BitWriter()
+            w.write(0, 1)
+            w.write(modes, modebits)
+            w.write(0xABCDE, 20)
+            pk.insert(2 + s, (w.tobytes(), -1, 0))
+        out.append(pk)
+    return out
+
+
+# one setup per residue type (the 256/256 one has bs0 = bs1), and a pair of equal large blocks
+RUNS = [("pair_256_256_grouping1", 0), ("res0", 2), ("res2", 1), ("res1_3modes", 3), ("pair_1024_1024", 9)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,k", RUNS, ids=[n for n, _ in RUNS])
+def test_runs_and_ranges_equal_the_stepwise_decode(cuda, name, k):
+    import vorbis_aotuv_lancer_amd as v
+    setup, coding = vm.pcm_setup(k)
+    want_type = {"res0": 0, "res2": 2, "res1_3modes": 1}.get(name)
+    if want_type is not None:
+        assert want_type in {r["type"] for r in setup["residues"]}
+    if name.startswith("pair"):
+        assert setup["blocksizes"][0] == setup["blocksizes"][1]
+    h = vm.pack_headers(setup, coding)
+    ds = v.DecodeSetup(h)
+    model = vm.Model(setup, fromdB())
+    streams = with_failed_packets(vm.pcm_streams(model, 8000 + k), h, len(setup["modes"]), model.modebits)
+    want = stepwise(v, ds, streams, cuda)
+    assert all(any(st) for _, _, st in want)                   # the failed packets are inside
+    for pk, (pcm, samples, status) in zip(streams, want):
+        st, sm, out_start, total = v.decode_index(ds, *as_stream(pk))
+        assert list(st) == status and list(sm) == samples and total == pcm.shape[1] > 0
+        assert list(out_start) == [int(x) for x in np.cumsum([0] + samples[:-1])]
+    # synthesis_runs: every stream whole, in one call
+    P = sum(len(pk) for pk in streams)
+    dec = v.Decoder(ds, len(streams), P)
+    ids = list(range(len(streams)))[::-1]
+    pcm, rs, sm, st = runs_call(dec, ids, [streams[i] for i in ids], cuda)
+    pcm, rs, sm, st = pcm.cpu().numpy(), rs.cpu().numpy(), sm.cpu().tolist(), st.cpu().tolist()
+    at = 0
+    for r, i in enumerate(ids):
+        c = len(streams[i])
+        assert np.array_equal(pcm[r, :, :rs[r]], want[i][0]), f"{name}: run of stream {i}"
+        assert sm[at:at + c] == want[i][1] and st[at:at + c] == want[i][2]
+        at += c
+    # synthesis_ranges: whole streams, and windows inside them
+    store = v.RangeStore(dec, [as_stream(pk) for pk in streams])
+    lin = [w[0] for w in want]
+    assert list(store.totals) == [x.shape[1] for x in lin]
+    rids = list(range(len(streams)))
+    got = ranges(dec, store, rids, [0] * len(rids), [x.shape[1] for x in lin])
+    check(lin, rids, [0] * len(rids), [x.shape[1] for x in lin], *got, what=f"{name} whole")
+    rng = np.random.default_rng(9)
+    rids = [int(i) for i in rng.integers(0, len(streams), 24)]
+    starts = [int(rng.integers(0, lin[i].shape[1])) for i in rids]
+    lengths = [int(rng.integers(1, 3000)) for _ in rids]
+    got = ranges(dec, store, rids, starts, lengths)
+    check(lin, rids, starts, lengths, *got, what=f"{name} windows")
+    store.close()
+    dec.close()
+    ds.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bs,nshort,nlong", [((256, 1024), 3, 5), ((512, 2048), 5, 3), ((256, 512), 5, 3),
+                                             ((1024, 1024), 3, 0)])
+def test_batches_that_do_not_fill_the_imdct_groups(cuda, bs, nshort, nlong):
+    """7 channels: 3 or 5 rows of a block size are 21 or 35 blocks, no multiple of the 8 / 4 / 2 blocks a wavefront
+    takes at 256 / 512 / 1024; both block sizes in one call"""
+    import vorbis_aotuv_lancer_amd as v
+    setup, coding = vm.gen_setup(3000 + bs[0] + bs[1], ch=7, bs=bs, res_types=(1, 2), coupling="pairs", min_exp=0,
+                                 res_kw=dict(bad_classwords=False, masks=[1, 3, 7]))
+    h = vm.pack_headers(setup, coding)
+    ds = v.DecodeSetup(h)
+    model = vm.Model(setup, fromdB())
+    seqs = ["SSSS"] * nshort + ["LLLL"] * nlong
+    streams = vm.pcm_streams(model, 31, sequences=seqs)
+    steps = decode_steps(v, ds, model, streams, cuda, f"{bs}")
+    win = [vm.vorbis_window64(bs[0] // 2), vm.vorbis_window64(bs[1] // 2)]
+    peaks = []
+    worst = check_pcm_bound(ds, streams, *steps, win=win, peaks=peaks)
+    assert min(peaks) >= 1e-3
+    print(f"\n7 ch {bs}, {nshort} short + {nlong} long rows: max |pcm - float64 reference| / peak = {worst:.3g}")
+    ds.close()

@@ -155,6 +155,11 @@ VBMD_HD int vbmd_floor1_inverse1(const vbmd_setup &s, const uint8_t *blob, const
     if (vbmd_read(b, 1) != 1) return 0;
     fit[0] = (int)vbmd_read(b, f.qbits);
     fit[1] = (int)vbmd_read(b, f.qbits);
+    // The reference does not test these two reads (lib/floor1.c:988-989); a later book read catches the end of the
+    // packet for it, unless the floor has no book to read (no partitions, or classes without books), where it
+    // goes on with Y = -1.  The specification (7.2.3) marks the channel unused, and so does this.  The PCM is the
+    // same either way: at the end of the packet no residue is left to decode.
+    if (fit[1] < 0) return 0;
     for (int i = 0, j = 2; i < f.partitions; i++) {
         const int cls = f.partclass[i];
         const int cdim = f.class_dim[cls], csubbits = f.class_subs[cls], csub = 1 << csubbits;
