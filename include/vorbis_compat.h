@@ -198,7 +198,10 @@ int vorbis_analysis_headerout(vorbis_dsp_state *v, vorbis_comment *vc, ogg_packe
 /* host buffers of `vals` floats per channel, valid until the next call on v (lib/block.c:411-436) */
 float **vorbis_analysis_buffer(vorbis_dsp_state *v, int vals);
 /* vals > 0: the first `vals` samples of the buffers are the stream's next samples; vals <= 0: end of stream
- * (lib/block.c:482-553).  OV_EINVAL when more was written than asked for (:540-541) or after the end. */
+ * (lib/block.c:482-553).  OV_EINVAL when more was written than asked for (:540-541), after the end, or when
+ * vals is more than a stream's device buffer takes in one write (11 1/2 long blocks less 448 samples with the default
+ * buffer: 23104 samples for 256/2048 setups); nothing is queued then and the stream goes on as if the call had not been
+ * made.  The reference grows its buffer instead (:411-436). */
 int vorbis_analysis_wrote(vorbis_dsp_state *v, int vals);
 /* 1: vb describes the stream's next block; 0: more PCM needed (or stream over) — lib/block.c:557-812 */
 int vorbis_analysis_blockout(vorbis_dsp_state *v, vorbis_block *vb);

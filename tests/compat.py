@@ -124,6 +124,15 @@ class Stream:
             C.memmove(buf[c], pcm[c].ctypes.data, n * 4)
         return self.dll.vorbis_analysis_wrote(self.vd, n)
 
+    def write_as(self, pcm, buffer_vals, wrote_vals=None):
+        """vorbis_analysis_buffer(buffer_vals), then vorbis_analysis_wrote(wrote_vals) (default: all of pcm)"""
+        pcm = np.ascontiguousarray(pcm, np.float32)
+        n = pcm.shape[1] if wrote_vals is None else wrote_vals
+        buf = self.dll.vorbis_analysis_buffer(self.vd, buffer_vals)
+        for c in range(self.ch):
+            C.memmove(buf[c], pcm[c].ctypes.data, min(n, pcm.shape[1], buffer_vals) * 4)
+        return self.dll.vorbis_analysis_wrote(self.vd, n)
+
     def finish(self):
         return self.dll.vorbis_analysis_wrote(self.vd, 0)
 

@@ -62,6 +62,7 @@ struct cstream {                     // vd->backend_state
     bool over = false;               // the e_o_s block has been carved
     bool dirty = false;              // something arrived since a round last had no block for this stream
     int given_since_write = 0;       // blocks handed out since the stream's last vorbis_analysis_wrote (VORBIS_MI355X_DEFER_BLOCKS)
+    bool held_back = false;          // ... and its last vorbis_analysis_blockout was answered "more data needed" with blocks still to carve
     long writes_seen = 0;
     std::deque<cblock> ready;        // carved, not yet handed out by vorbis_analysis_blockout
     cblock cur;                      // the block vorbis_analysis_blockout handed out last
@@ -335,7 +336,8 @@ int pool_round(cpool *p, cstream *only, bool restrict_to_only, bool *got_only)
 }
 
 // queued writes -> device.  `only` != nullptr: that stream's writes alone.  Writes of equal length go up together
-// (vbm_frontend_write_streams); a write that would overrun a stream's device buffer waits for rounds to drain it.
+// (vbm_frontend_write_streams); a write that would overrun a stream's device buffer waits for rounds to drain it
+// (vorbis_analysis_wrote lets none through that a drained buffer could not take: stream_max_write).
 int pool_upload(cpool *p, cstream *only)
 {
     const int ch = p->cls->ch;
@@ -347,7 +349,6 @@ int pool_upload(cpool *p, cstream *only)
             if (!s || s->writes.empty() || (only && s != only)) continue;
             any = true;
             const int vals = s->writes.front().vals;
-            if (vals > p->capacity) return OV_EINVAL;                 // can never fit (lib/block.c:540-541)
             if (p->buffered[s->slot] + vals > p->capacity) { blocked = true; continue; }
             groups[vals].push_back(s);
         }
@@ -355,13 +356,17 @@ int pool_upload(cpool *p, cstream *only)
         if (groups.empty() && blocked) {
             // every pending write waits for room: carve blocks (they go to the queues) and try again
             bool got = false;
+            long held = 0;
+            for (cstream *s : p->slots)
+                if (s && !s->writes.empty() && (!only || s == only)) held += p->buffered[s->slot];
             int rc = pool_round(p, only, only != nullptr, &got);
             if (rc) return rc;
-            bool still = true;
+            // (a round moves a stream by one block, a large write may need several: go on while a waiting stream's
+            // buffer went down, give up — not spin — when the round freed nothing)
+            long left = 0;
             for (cstream *s : p->slots)
-                if (s && !s->writes.empty() && (!only || s == only) &&
-                    p->buffered[s->slot] + s->writes.front().vals <= p->capacity) still = false;
-            if (still) return OV_EINVAL;                              // the round freed nothing: give up, not spin
+                if (s && !s->writes.empty() && (!only || s == only)) left += p->buffered[s->slot];
+            if (left >= held) return OV_EINVAL;
             continue;
         }
         for (auto &g : groups) {
@@ -427,6 +432,28 @@ int stream_send_eof(cpool *p, cstream *s)
     s->eof_sent = true;
     s->dirty = true;
     return 0;
+}
+
+// the most samples one vorbis_analysis_wrote may bring
+int stream_max_write(const cpool *p) { return p->capacity - (3 * p->cls->bs[1] / 2 + 448); }
+
+// VORBIS_MI355X_DEFER_BLOCKS told the application to wait for blocks the reference would have handed out: before the end
+// is declared they are carved (to the stream's queue), so that the end-of-stream extrapolation is fitted to the buffer the
+// reference's would hold — a stream that ends inside a run of short blocks holds less than one long block when drained,
+// and the fit takes all of it (lib/block.c:522-524)
+int stream_carve_held_back(cpool *p, cstream *s)
+{
+    int carve;
+    { std::lock_guard<std::mutex> lk(g_mu); carve = g_carve_ahead; }
+    for (;;) {
+        int rc = pool_upload(p, carve ? nullptr : s);
+        if (rc) return rc;
+        bool got = false;
+        rc = pool_round(p, s, !carve, &got);
+        if (rc) return rc;
+        const bool put_off = p->lanes > 0 && carve && p->h_types[s->slot] >= 0;   // (device-built round: its type's lanes were full)
+        if (!got && !put_off) return 0;
+    }
 }
 
 cstream *stream_of(vorbis_dsp_state *v) { return v ? (cstream *)v->backend_state : nullptr; }
@@ -881,10 +908,17 @@ extern "C" int vorbis_analysis_wrote(vorbis_dsp_state *v, int vals)
         v->eofflag = v->pcm_current;
         // the end is declared on the device now: what the buffer holds at THIS moment decides the extrapolation
         // (lib/block.c:497-537)
-        int rc = stream_send_eof(p, s);
+        int rc = s->held_back ? stream_carve_held_back(p, s) : 0;
+        s->held_back = false;
+        if (!rc) rc = stream_send_eof(p, s);
         return rc ? OV_EINVAL : 0;
     }
     if (vals > (s->buf_in_arena ? p->arena_vals : s->buf_vals)) return OV_EINVAL;    // more than vorbis_analysis_buffer handed out (lib/block.c:540-541)
+    // A write that may never find room in the stream's device buffer is refused here, where the application sees it —
+    // queued, it would stay at the head of the queue for good, and every upload of its pool would fail with it.  A drained
+    // stream still holds up to 3/2 long blocks and 448 samples (centerW, the block bound of lib/block.c:595-601, the
+    // search's look-ahead of lib/envelope.c:577, :616-626); what the buffer takes beside that is the limit.
+    if (vals > stream_max_write(p)) return OV_EINVAL;
     span_timer tm(0);
     cwrite w;
     w.vals = vals;
@@ -898,6 +932,7 @@ extern "C" int vorbis_analysis_wrote(vorbis_dsp_state *v, int vals)
     s->writes.push_back(std::move(w));
     s->dirty = true;
     s->given_since_write = 0;
+    s->held_back = false;
     s->writes_seen++;
     v->pcm_current += vals;
     v->preextrapolate = 1;
@@ -924,8 +959,10 @@ extern "C" int vorbis_analysis_blockout(vorbis_dsp_state *v, vorbis_block *vb)
     // make the whole pool run up to eight more rounds per write, each for a handful of blocks.  The blocks come later
     // (latest when the stream's buffer is half full, or at end of stream): same packets, later delivery.
     if (defer && !s->eof_sent && !s->eof_asked && s->ready.empty() &&
-        s->given_since_write >= 1 + (s->writes_seen % 3 == 0) && p->buffered[s->slot] <= p->capacity / 2)
+        s->given_since_write >= 1 + (s->writes_seen % 3 == 0) && p->buffered[s->slot] <= p->capacity / 2) {
+        s->held_back = true;
         return 0;
+    }
     if (s->ready.empty() && s->dirty && !(s->over)) {
         if (pool_upload(p, carve ? nullptr : s)) return 0;
         if (s->ready.empty()) {
