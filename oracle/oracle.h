@@ -302,7 +302,9 @@ typedef struct orc_block {
     int cap_post_valid[ORC_MAXCH];
     int cap_nonzero[ORC_MAXCH];
     float cap_local_ampmax[ORC_MAXCH], cap_global_ampmax;
+    float cap_poste[ORC_MAXCH];          /* what orc_postnoise_detection returned for the channel */
     int cap_block_mode;
+    int cap_partition;                   /* bins per npeak entry: cap_npeak holds n/2/cap_partition values */
 } orc_block;
 
 typedef struct orc_stream {

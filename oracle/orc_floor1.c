@@ -155,14 +155,15 @@ static int fit_line(lsfit_acc *a, int fits, int *y0, int *y1, const orc_floor *i
             *y0 = rint(aa + bb * x0);
             *y1 = rint(aa + bb * x1);
 
-            if (*y0 > 1023) *y0 = 1023;
+            if (*y0 > 1023)
+                *y0 = 1023; /* REACH: fitline_y0_above_1023 */
             if (*y1 > 1023) *y1 = 1023;
             if (*y0 < 0) *y0 = 0;
             if (*y1 < 0) *y1 = 0;
 
             return 0;
         } else {
-            *y0 = 0;
+            *y0 = 0; /* REACH: fitline_denom_le0 */
             *y1 = 0;
             return 1;
         }
@@ -232,7 +233,8 @@ int orc_floor1_interpolate_fit(const orc_floor *look, const int *A, const int *B
 {
     long i;
     long posts = look->posts;
-    if (!A || !B) return 0;
+    if (!A || !B)
+        return 0; /* REACH: interpolate_fit_missing_neighbour */
     for (i = 0; i < posts; i++) {
         output[i] = ((65536 - del) * (A[i] & 0x7fff) + del * (B[i] & 0x7fff) + 32768) >> 16;
         if (A[i] & 0x8000 && B[i] & 0x8000) output[i] |= 0x8000;
@@ -310,16 +312,16 @@ int orc_floor1_fit(const orc_floor *look, const float *logmdct, const float *log
                         int ret1 = fit_line(fits + sortpos, hsortpos - sortpos, &hy0, &hy1, info);
 
                         if (ret0) {
-                            ly0 = ly;
+                            ly0 = ly; /* REACH: floor_fit_ret0 */
                             ly1 = hy0;
                         }
                         if (ret1) {
-                            hy0 = ly1;
+                            hy0 = ly1; /* REACH: floor_fit_ret1 */
                             hy1 = hy;
                         }
 
                         if (ret0 && ret1) {
-                            fit_valueA[i] = -200;
+                            fit_valueA[i] = -200; /* REACH: floor_fit_both_degenerate */
                             fit_valueB[i] = -200;
                         } else {
                             fit_valueB[ln] = ly0;

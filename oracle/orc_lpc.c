@@ -29,7 +29,7 @@ float orc_lpc_from_data(float *data, float *lpci, int n, int m)
         double r = -aut[i + 1];
 
         if (error < epsilon) {
-            memset(lpc + i, 0, (m - i) * sizeof(*lpc));
+            memset(lpc + i, 0, (m - i) * sizeof(*lpc)); /* REACH: lpc_error_below_epsilon */
             goto done;
         }
 

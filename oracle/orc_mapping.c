@@ -71,6 +71,7 @@ int orc_mapping0_forward(orc_stream *v, orc_block *vb)
     block_mode = blocktype;
     block_mode |= (modenumber << 1);
     vb->cap_block_mode = block_mode;
+    vb->cap_partition = partition;
 
     if (modenumber) lowpass_residue = s->block_lowpassr[1];
     else lowpass_residue = s->block_lowpassr[0];
@@ -96,6 +97,7 @@ int orc_mapping0_forward(orc_stream *v, orc_block *vb)
         npeak[i] = (float *)malloc((n / 2 / partition + 1) * sizeof(float));
 
         poste[i] = orc_postnoise_detection(pcm, n, block_mode, v->lW_block_mode);
+        vb->cap_poste[i] = poste[i];
 
         orc_apply_window(pcm, n, win_l, ln, win_r, rn);
         if (v->capture) memcpy(vb->cap_windowed[i], pcm, n * sizeof(float));

@@ -48,8 +48,9 @@ float orc_postnoise_detection(const float *pcm, int nn, int mode, int lw_mode)
     unt *= 15;
 
     if (upt > unt) {
-        ret = upt - unt;
-        if (ret < 0.1) ret = -1.0;
+        ret = upt - unt; /* REACH: poste_positive */
+        if (ret < 0.1)
+            ret = -1.0; /* REACH: poste_below_tenth */
     }
     return ret;
 }
@@ -376,7 +377,7 @@ static void ntfix(const orc_psy *p, const float *spectral, float *noise, int blo
         float strength = .6f;
         if (n == 256) tolerance = 15.f;
         if (nxplus > n) {
-            nx = n;
+            nx = n; /* REACH: ntfix_nxplus_over_n */
             nxplus = n - freq_unc;
         }
 
@@ -408,7 +409,8 @@ static void ntfix(const orc_psy *p, const float *spectral, float *noise, int blo
                         }
                         for (j = ps; j <= pe; j++) {
                             temp[j] = ORC_MAX(ss, temp[j]);
-                            if (temp[j] < 0) temp[j] = 0;
+                            if (temp[j] < 0)
+                                temp[j] = 0; /* REACH: ntfix_temp_below0 */
                         }
                     }
                 }
@@ -483,7 +485,8 @@ void orc_noisemask(const orc_setup *s, const orc_psy *p, float noise_compand_lev
         for (; i < thter; i++) {
             int dB = logmask[i] + .5;
             if (dB >= ORC_NOISE_COMPAND_LEVELS) dB = ORC_NOISE_COMPAND_LEVELS - 1;
-            if (dB < 0) dB = 0;
+            if (dB < 0)
+                dB = 0; /* REACH: compand_low_db_below0 */
             epeak[i] = work[i] + stn_compand[dB];
             logmask[i] = work[i] + p->noisecompand[dB] -
                          ((p->noisecompand[dB] - p->noisecompand_high[dB]) * noise_compand_level);
@@ -492,7 +495,8 @@ void orc_noisemask(const orc_setup *s, const orc_psy *p, float noise_compand_lev
     for (; i < n; i++) {
         int dB = logmask[i] + .5;
         if (dB >= ORC_NOISE_COMPAND_LEVELS) dB = ORC_NOISE_COMPAND_LEVELS - 1;
-        if (dB < 0) dB = 0;
+        if (dB < 0)
+            dB = 0; /* REACH: compand_db_below0 */
         epeak[i] = work[i] + stn_compand[dB];
         logmask[i] = work[i] + p->noisecompand[dB];
     }
@@ -503,8 +507,9 @@ void orc_noisemask(const orc_setup *s, const orc_psy *p, float noise_compand_lev
     if (poste > 0) {
         for (i = 0, k = 0; i < p->min_nn_lp; i += partition, k++) {
             float temp = ORC_MIN(ORC_MIN(poste, 30.f), p->noiseoffset[1][i] + 30.f);
-            if (temp <= 0) continue;
-            npeak[k] = -1.f;
+            if (temp <= 0)
+                continue; /* REACH: postecho_offset_nonpositive */
+            npeak[k] = -1.f; /* REACH: postecho_npeak_minus1 */
             for (j = 0; j < partition; j++) logmask[i + j] -= temp;
         }
     }
@@ -517,7 +522,8 @@ void orc_noisemask(const orc_setup *s, const orc_psy *p, float noise_compand_lev
         float avge = 0;
 
         if (o <= 0) continue;
-        if (npeak[k] < -0.5) continue;
+        if (npeak[k] < -0.5)
+            continue; /* REACH: m8_skip_postecho */
 
         for (j = 0; j < partition; j++) {
             float temp = logmdct[i + j] - logmask[i + j];
@@ -627,7 +633,8 @@ static void set_m3p(const orc_setup *s, local_mod3_psy *mp, const int lW_no, con
         }
         mp->noise_rate_low = 0;
         mp->sw = 1;
-        if (impadnum) mp->noise_rate *= (impadnum * 0.125);
+        if (impadnum)
+            mp->noise_rate *= (impadnum * 0.125); /* REACH: m3p128_impadnum */
         for (i = 0; i < n; i++) {
             cell = 75 / (float)freq_bfn128[i];
             for (j = 1; j < freq_bfn128[i]; j++) {
@@ -642,11 +649,11 @@ static void set_m3p(const orc_setup *s, local_mod3_psy *mp, const int lW_no, con
         if (!lW_block_mode) {
             count = 6;
             if (lW_no < 4) {
-                mp->noise_rate = 0.4 - (float)(lW_no - 1) / 11;
+                mp->noise_rate = 0.4 - (float)(lW_no - 1) / 11; /* REACH: m3p256_lwno_lt4 */
                 mp->noise_center = (float)(lW_no * count + 12);
                 mp->tone_rate = 8 - lW_no * 2;
             } else {
-                mp->noise_rate = 0.2;
+                mp->noise_rate = 0.2; /* REACH: m3p256_lwno_ge4 */
                 mp->noise_center = 30;
                 mp->tone_rate = 0;
             }
@@ -654,7 +661,7 @@ static void set_m3p(const orc_setup *s, local_mod3_psy *mp, const int lW_no, con
                 for (i = 0; i < n; i++) tempmdct[i] -= 10;
             }
         } else {
-            mp->noise_rate = 0.6;
+            mp->noise_rate = 0.6; /* REACH: m3p256_after_padding */
             mp->noise_center = 12;
             mp->tone_rate = 8.;
             if (mp->mdctbuf_flag == 1) {
@@ -663,7 +670,8 @@ static void set_m3p(const orc_setup *s, local_mod3_psy *mp, const int lW_no, con
         }
         mp->noise_rate_low = 0;
         mp->sw = 1;
-        if (impadnum) mp->noise_rate *= (impadnum * 0.0625);
+        if (impadnum)
+            mp->noise_rate *= (impadnum * 0.0625); /* REACH: m3p256_impadnum */
         for (i = 0; i < n; i++) {
             cell = 75 / (float)freq_bfn256[i];
             for (j = 1; j < freq_bfn256[i]; j++) {
@@ -705,7 +713,8 @@ void orc_offset_and_mix(const orc_setup *s, const orc_psy *p, const float *noise
     mp4.end_block = end_block;
 
     if (low_compand < 0 || toneatt < 25.) low_compand = 0;
-    else low_compand *= (toneatt - 25.);
+    else
+        low_compand *= (toneatt - 25.); /* REACH: low_compand_toneatt25 */
 
     set_m3p(s, &mp3, lW_no, impadnum, n, hsrate, toneatt, logmdct, lastmdct, tempmdct, block_mode, lW_block_mode,
             bit_managed, offset_select);
@@ -1222,15 +1231,15 @@ void orc_couple_quantize_normalize(const orc_setup *s, int blobno, const orc_psy
                             float hpH;
                             if (vi->coupling_steps == 1 || step == 3) {
                                 hpL = .18f;
-                                hpH = .12f;
+                                hpH = .12f; /* REACH: point_coupling_single_step */
                             } else {
                                 hpL = .18f;
-                                hpH = .04f;
+                                hpH = .04f; /* REACH: point_coupling_multi_step */
                             }
                             if (j < limit - i) {
                                 reM[j] = min_indemnity_dipole_hypot(reM[j], reA[j], hpL);
                             } else {
-                                reM[j] = min_indemnity_dipole_hypot(reM[j], reA[j], hpH);
+                                reM[j] = min_indemnity_dipole_hypot(reM[j], reA[j], hpH); /* REACH: point_coupling_above_limit */
                             }
 
                             qeM[j] = fabs(reM[j]);
@@ -1240,7 +1249,7 @@ void orc_couple_quantize_normalize(const orc_setup *s, int blobno, const orc_psy
                             resA[j] = 0;
 
                             if ((nepeak[Mi][pi] < -0.5) || (nepeak[Ai][pi] < -0.5)) {
-                                nepeak[Mi][pi] = -1;
+                                nepeak[Mi][pi] = -1; /* REACH: couple_npeak_minus1 */
                             } else {
                                 nepeak[Mi][pi] = ORC_MIN(nepeak[Mi][pi], nepeak[Ai][pi]);
                             }

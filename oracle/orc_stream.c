@@ -353,7 +353,7 @@ static void bitrate_addblock(orc_stream *v, orc_block *vb)
         long maxsize = (max_target_bits + (s->bi_reservoir_bits - v->bm_minmax_reservoir)) / 8;
         vb->choice = choice = 0;
         if (orc_bits_bytes(&vb->blob[choice]) > maxsize) {
-            orc_bits_writetrunc(&vb->blob[choice], maxsize * 8);
+            orc_bits_writetrunc(&vb->blob[choice], maxsize * 8); /* REACH: bitrate_truncates_packet */
             this_bits = orc_bits_bytes(&vb->blob[choice]) * 8;
         }
     } else {
@@ -555,5 +555,7 @@ const void *orc_block_cap(const orc_block *vb, const char *name, int ch)
     if (!strcmp(name, "nonzero")) return &vb->cap_nonzero[ch];
     if (!strcmp(name, "local_ampmax")) return &vb->cap_local_ampmax[ch];
     if (!strcmp(name, "global_ampmax")) return &vb->cap_global_ampmax;
+    if (!strcmp(name, "poste")) return &vb->cap_poste[ch];
+    if (!strcmp(name, "partition")) return &vb->cap_partition;
     return 0;
 }

@@ -210,6 +210,11 @@ class Stream:
             d["nonzero"] = np.array([self._arr("nonzero", c, 1, np.int32)[0] for c in range(self.ch)])
             d["local_ampmax"] = np.array([self._arr("local_ampmax", c, 1, np.float32)[0] for c in range(self.ch)])
             d["global_ampmax"] = self._arr("global_ampmax", 0, 1, np.float32)[0]
+            # what orc_postnoise_detection returned per channel, and npeak as couple/quantise left it:
+            # one value per `partition` bins
+            d["poste"] = np.array([self._arr("poste", c, 1, np.float32)[0] for c in range(self.ch)])
+            d["partition"] = int(self._arr("partition", 0, 1, np.int32)[0])
+            d["npeak"] = np.stack([self._arr("npeak", c, n // d["partition"], np.float32) for c in range(self.ch)])
             yield d
 
     def close(self):

@@ -40,3 +40,14 @@ def burst_signal(ch, rate, nsamples, seed=0, period=6000, burst=200, level=1.0):
         x += np.where(on, 0.6 * rng.uniform(-1, 1, nsamples), 0.0)
         out[c] = (level * x).astype(np.float32)
     return out
+
+
+def gen_windowed_sine(n=2048, maximum=0.95):
+    """test/util.c:29-45, evaluated in double and stored as float like the C code"""
+    data = np.zeros(n, np.float32)
+    half = n // 2
+    k = np.arange(half, dtype=np.float64)
+    x = np.sin(2.0 * k * np.pi * 1.0 / 32.0 + 0.4).astype(np.float32)          # data[k] = sin(...)  (float store)
+    w = maximum * (0.5 - 0.5 * np.cos(2.0 * np.pi * k / (half - 1)))             # double
+    data[:half] = (x.astype(np.float64) * w).astype(np.float32)                 # data[k] *= ...      (float store)
+    return data

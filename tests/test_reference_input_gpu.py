@@ -15,20 +15,10 @@ import pytest
 import torch
 
 from tests import compat, orc
+from tests.signals import gen_windowed_sine
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def gen_windowed_sine(n=2048, maximum=0.95):
-    """test/util.c:29-45, evaluated in double and stored as float like the C code"""
-    data = np.zeros(n, np.float32)
-    half = n // 2
-    k = np.arange(half, dtype=np.float64)
-    x = np.sin(2.0 * k * np.pi * 1.0 / 32.0 + 0.4).astype(np.float32)          # data[k] = sin(...)  (float store)
-    w = maximum * (0.5 - 0.5 * np.cos(2.0 * np.pi * k / (half - 1)))             # double
-    data[:half] = (x.astype(np.float64) * w).astype(np.float32)                 # data[k] *= ...      (float store)
-    return data
 
 
 def classes():

@@ -29,8 +29,10 @@
 // the workgroups.
 //
 // Exactness: every float / double expression is the scalar source's, evaluated in the source's order
-// (-ffp-contract=off); tests compare logmdct, noise, epeak and npeak bit for bit with the oracle for every block
-// type (tests/test_pipeline_gpu.py) and the packets behind them (all packet-level tests).
+// (-ffp-contract=off); tests compare logmdct and noise bit for bit with the oracle for every block type
+// (tests/test_pipeline_gpu.py), epeak, npeak (as couple/quantise leaves it) and the post-echo value the prologue hands
+// in as well, on signals that take the post-echo arm below (tests/test_reach_gpu.py), and the packets behind them (all
+// packet-level tests).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
