@@ -459,9 +459,10 @@ int vbm_window_mdct_time(const vbm_mdct_plan *plan, const float *d_pcm, float *d
  * max_batch streams that share one set of headers and returns, per row, the PCM that became final with that packet:
  * vorbis_synthesis + vorbis_synthesis_blockin + vorbis_synthesis_pcmout + vorbis_synthesis_read
  * (reference lib/synthesis.c:25-91, lib/block.c:897-1190; examples/decoder_example.c).
- * Not supported (VBM_EIMPL at setup): floor type 0, block sizes outside 256..4096, more than 8 channels.  No half-rate
- * decoding or chained streams; seeking is by sample windows of a range store (vbm_synthesis_ranges), not of a live
- * stream.  The reference's own vorbis_synthesis* names are not exported. */
+ * Not supported (VBM_EIMPL at setup): floor type 0, block sizes outside 256..4096, more than 8 channels.  No chained
+ * streams; seeking is by sample windows of a range store (vbm_synthesis_ranges), not of a live stream.  Half-rate
+ * decoding (vorbis_synthesis_halfrate) is a property of the decoder: vbm_decoder_create_halfrate below.  The
+ * reference's own vorbis_synthesis* names are not exported. */
 #define VBM_ENOTVORBIS (-132) /* OV_ENOTVORBIS, include/vorbis/codec.h:229-233 */
 #define VBM_EBADHEADER (-133) /* OV_EBADHEADER */
 #define VBM_EVERSION   (-134) /* OV_EVERSION   */
@@ -492,6 +493,26 @@ int  vbm_host_unpack_packet(const vbm_decode_setup *ds, const uint8_t *packet, l
 /* Device.  nstreams streams of state (previous block size, overlap tail [channels][blocksizes[1]/2], granulepos, sample
  * count) live on the device.  Without a HIP device: VBM_ENODEV. */
 int  vbm_decoder_create(vbm_decoder **dec, const vbm_decode_setup *ds, int nstreams, int max_batch);
+/* Half-rate decoding (the reference's vorbis_synthesis_halfrate, lib/synthesis.c:166-179, and
+ * ov_halfrate): halfrate 1 makes a decoder whose PCM comes out at rate / 2.  Packets are unpacked at their full block
+ * size; the inverse MDCT of a block has half its size and reads the lower half of its spectrum, the windows are those
+ * of the halved sizes, and every length below that is blocksizes[1]/2 for a full-rate decoder is blocksizes[1]/4:
+ *   vbm_synthesis_batch      d_pcm [nsb][channels][blocksizes[1]/4]; a packet of block size W after one of lW
+ *                            returns (blocksizes[lW]/4 + blocksizes[W]/4) / 2 samples
+ *   vbm_synthesis_runs       pcm_stride >= max(run_packets) * blocksizes[1]/4
+ *   vbm_range_store_create   indexes the streams at the decoder's rate; totals, and the starts / lengths / got of
+ *                            vbm_synthesis_ranges, are output samples of the half-rate linear decode
+ * Granule positions stay in full-rate samples, as in the reference: a packet whose granulepos asks for `extra`
+ * full-rate samples less loses extra / 2 (rounded down) output samples (lib/block.c:1112-1118, 1140-1150).  The
+ * invariants stated below hold unchanged: any split of a stream into runs and single-packet calls gives the same
+ * bits, and a range is bit for bit the slice of the linear decode.  vbm_decoder_fetch returns the full-rate
+ * intermediates ("spectrum" is computed on all blocksizes[W]/2 bins; the transform reads the first blocksizes[W]/4).
+ * halfrate 0 is vbm_decoder_create; any other value is VBM_EINVAL (checked before the device is looked for).  Every
+ * setup the decoder accepts can be decoded at half rate (the reference refuses block sizes <= 64).
+ * vbm_decoder_halfrate: the flag the decoder was created with. */
+int  vbm_decoder_create_halfrate(vbm_decoder **dec, const vbm_decode_setup *ds, int nstreams, int max_batch,
+                                 int halfrate);
+int  vbm_decoder_halfrate(const vbm_decoder *dec);
 void vbm_decoder_destroy(vbm_decoder *dec);
 /* every stream back to its initial state (device idle afterwards) */
 int  vbm_decoder_reset(vbm_decoder *dec);
@@ -536,6 +557,11 @@ int  vbm_synthesis_runs(vbm_decoder *dec, int nruns, const int *stream_ids /*hos
 int  vbm_decode_index(const vbm_decode_setup *ds, long long npackets, const uint8_t *data, const long long *offsets,
                       long long data_bytes, const long long *granulepos, const uint8_t *eos, int *status,
                       int *samples, long long *out_start, long long *total);
+/* The index of a decoder created with the same `halfrate` (0 or 1, otherwise VBM_EINVAL): samples, out_start and
+ * *total in its output samples.  With halfrate 0 this is vbm_decode_index. */
+int  vbm_decode_index_halfrate(const vbm_decode_setup *ds, int halfrate, long long npackets, const uint8_t *data,
+                               const long long *offsets, long long data_bytes, const long long *granulepos,
+                               const uint8_t *eos, int *status, int *samples, long long *out_start, long long *total);
 /* A range store: the packets of nstreams streams decoded by `dec` (one set of headers), kept in device memory with
  * their index.  Host inputs, the demuxed streams back to back: stream i is packets stream_packets[i] ..
  * stream_packets[i+1] (stream_packets[0] = 0, non-decreasing), packet k is data[offsets[k] .. offsets[k+1]) clamped to

@@ -16,6 +16,9 @@ streams (the encoded signals dealt round robin) go into one range store, and eve
 (stream, start) windows of --range-seconds each.  The result reports ms per call, ranges/s, audio seconds decoded per
 wall second, rows per call and the pre-roll share of those rows (from the host index).
 
+With --halfrate the decoder is a half-rate one (Decoder(..., halfrate=True)) in any of the three modes:
+the same packets, half as many output samples at rate / 2; range windows are --range-seconds of output.
+
 Per-kernel times: run this under `rocprofv3 --kernel-trace --stats`."""
 import argparse
 import json
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--ranges", type=int, default=0, help="N > 0: N random windows per call through synthesis_ranges")
     ap.add_argument("--range-seconds", type=float, default=1.0, help="length of each window (--ranges)")
     ap.add_argument("--max-batch", type=int, default=65536, help="rows per sub-call of a range call (--ranges)")
+    ap.add_argument("--halfrate", action="store_true", help="decode at half the sample rate (with any of the modes)")
     a = ap.parse_args()
     P = a.packets_per_call
     if P < 1:
@@ -104,8 +108,8 @@ def main():
     nbytes_step = [float(lnb[li, t].sum()) for t in range(nsteps)]
 
     ds = v.DecodeSetup(v.header_packets(setup))
-    dec = v.Decoder(ds, S, S)
-    half = ds.blocksizes[1] // 2
+    dec = v.Decoder(ds, S, S, halfrate=a.halfrate)
+    half = dec.row
     pcm = [torch.empty((S, ch, half), dtype=torch.float32, device=dev) for _ in range(2)]
     outs = [(pcm[t % 2], torch.empty(S, dtype=torch.int32, device=dev), torch.empty(S, dtype=torch.int32, device=dev))
             for t in range(nsteps)]
@@ -123,9 +127,9 @@ def main():
     ms = e0.elapsed_time(e1)
     samples_sum = sum(int(outs[t][1].sum()) for t in range(a.warmup, nsteps))
     bad = sum(int((outs[t][2] != 0).sum()) for t in range(nsteps))
-    audio_s = samples_sum / rate                          # per-channel samples summed over all streams
+    audio_s = samples_sum / dec.rate                      # per-channel samples summed over all streams
     res = {
-        "metric": "decode_step_ms", "streams": S, "signals": K, "channels": ch, "rate": rate, "quality": a.quality,
+        "metric": "decode_step_ms", "halfrate": bool(a.halfrate), "streams": S, "signals": K, "channels": ch, "rate": rate, "quality": a.quality,
         "steps": a.steps, "ms_per_step": ms / a.steps, "realtime_streams": audio_s / (ms / 1e3),
         "packet_bytes_per_step": sum(nbytes_step[a.warmup:]) / a.steps, "status_errors": int(bad),
         "blocksizes": list(ds.blocksizes),
@@ -161,8 +165,8 @@ def runs(a, v, dev, setup, lead):
                        torch.from_numpy(np.tile(np.concatenate(gps), reps)).to(dev)))
         nbytes_call.append(float(base * reps))
     ds = v.DecodeSetup(v.header_packets(setup))
-    dec = v.Decoder(ds, S, S * P)
-    half = ds.blocksizes[1] // 2
+    dec = v.Decoder(ds, S, S * P, halfrate=a.halfrate)
+    half = dec.row
     ids = np.arange(S, dtype=np.int32)
     counts = np.full(S, P, np.int32)
     pcm = [torch.empty((S, ch, P * half), dtype=torch.float32, device=dev) for _ in range(2)]
@@ -182,9 +186,9 @@ def runs(a, v, dev, setup, lead):
     ms = e0.elapsed_time(e1)
     samples_sum = sum(int(outs[c][1].sum()) for c in range(a.warmup, ncalls))
     bad = sum(int((outs[c][3] != 0).sum()) for c in range(ncalls))
-    audio_s = samples_sum / rate
+    audio_s = samples_sum / dec.rate
     res = {
-        "metric": "decode_runs_ms", "streams": S, "signals": K, "channels": ch, "rate": rate, "quality": a.quality,
+        "metric": "decode_runs_ms", "halfrate": bool(a.halfrate), "streams": S, "signals": K, "channels": ch, "rate": rate, "quality": a.quality,
         "packets_per_call": P, "calls": a.steps, "ms_per_call": ms / a.steps, "ms_per_packet_step": ms / a.steps / P,
         "realtime_streams": audio_s / (ms / 1e3), "packet_bytes_per_call": sum(nbytes_call[a.warmup:]) / a.steps,
         "status_errors": int(bad), "blocksizes": list(ds.blocksizes),
@@ -197,15 +201,15 @@ def runs(a, v, dev, setup, lead):
 def ranges(a, v, dev, setup, lead):
     """random sample windows of a range store of --streams streams (vbm_synthesis_ranges)"""
     S, K, ch, rate, N = a.streams, a.signals, a.channels, a.rate, a.ranges
-    L = int(a.range_seconds * rate)
+    L = int(a.range_seconds * rate) // (2 if a.halfrate else 1)       # samples at the output rate
     streams = []
     for k in range(K):
         b = b"".join(p[1] for p in lead[k])
         streams.append((np.frombuffer(b, np.uint8), np.cumsum([0] + [len(p[1]) for p in lead[k]]).astype(np.int64),
                         np.array([p[2] for p in lead[k]], np.int64), np.array([p[3] for p in lead[k]], np.uint8)))
     ds = v.DecodeSetup(v.header_packets(setup))
-    index = [v.decode_index(ds, *s) for s in streams]
-    dec = v.Decoder(ds, 1, a.max_batch)
+    index = [v.decode_index(ds, *s, halfrate=a.halfrate) for s in streams]
+    dec = v.Decoder(ds, 1, a.max_batch, halfrate=a.halfrate)
     store = v.RangeStore(dec, [streams[s % K] for s in range(S)])
     rng = np.random.default_rng(1234)
     ncalls = a.warmup + a.steps
@@ -243,10 +247,10 @@ def ranges(a, v, dev, setup, lead):
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
     res = {
-        "metric": "decode_ranges_ms", "streams": S, "signals": K, "channels": ch, "rate": rate, "quality": a.quality,
+        "metric": "decode_ranges_ms", "halfrate": bool(a.halfrate), "streams": S, "signals": K, "channels": ch, "rate": rate, "quality": a.quality,
         "ranges_per_call": N, "range_seconds": a.range_seconds, "max_batch": a.max_batch, "calls": a.steps,
         "ms_per_call": ms / a.steps, "ranges_per_s": N * a.steps / (ms / 1e3),
-        "audio_s_per_wall_s": got_sum / rate / (ms / 1e3), "rows_per_call": rows / a.steps,
+        "audio_s_per_wall_s": got_sum / dec.rate / (ms / 1e3), "rows_per_call": rows / a.steps,
         "preroll_share": preroll / max(rows, 1), "blocksizes": list(ds.blocksizes),
     }
     print(json.dumps(res))

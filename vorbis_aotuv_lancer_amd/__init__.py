@@ -1,6 +1,6 @@
 """vorbis_aotuv_lancer_amd — MI355X-native batched Vorbis (aoTuV) encode path, plus a batched
 device decoder (DecodeSetup, Decoder: Vorbis packets -> PCM; decode_ogg: .ogg files -> PCM; OggIndex: random sample
-windows of many .ogg files).
+windows of many .ogg files; halfrate=True on any of them decodes at half the sample rate).
 
 Host-side mirror (Python) of the reference's per-block encode interface over the C ABI in
 include/vorbis_mi355x.h.  PyTorch is used only as plumbing (device memory, streams,

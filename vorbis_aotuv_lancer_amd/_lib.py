@@ -129,6 +129,8 @@ SIGNATURES = {
     "vbm_host_unpack_packet": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "vbm_decoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int]),
+    "vbm_decoder_create_halfrate": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "vbm_decoder_halfrate": (C.c_int, [C.c_void_p]),
     "vbm_decoder_destroy": (None, [C.c_void_p]),
     "vbm_decoder_reset": (C.c_int, [C.c_void_p]),
     "vbm_decoder_restart_streams": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -143,6 +145,9 @@ SIGNATURES = {
                                     C.c_void_p]),
     "vbm_decode_index": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]),
+    "vbm_decode_index_halfrate": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_longlong)]),
     "vbm_range_store_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "vbm_range_store_destroy": (None, [C.c_void_p]),

@@ -13,6 +13,10 @@
 // The host plans pieces (a pre-roll packet and the packets after it) from the store's host index; per sub-call the
 // piece table goes up through the staging ring, then k_range_rows, k_unpack_rows, the same spectrum and IMDCT
 // launches, k_range_plan and k_overlap_runs.  No stream state is read or written.
+//
+// A half-rate decoder (vbm_decoder_create_halfrate) enqueues the same chains with the IMDCT of half each block size and
+// the half-rate instantiations of the overlap kernels; its windows and trig tables are those of the halved sizes, its
+// IMDCT rows, tails and PCM rows half as long.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -33,10 +37,11 @@ constexpr int kStage = 4;
 struct vbm_decoder {
     vbmd_setup hs;                   // host copy (block sizes, channels)
     int S = 0, cap = 0, ch = 0;
-    long half = 0, n1 = 0;
+    int halfrate = 0;                // 1: vorbis_synthesis_halfrate
+    long half = 0, n1 = 0, ohalf = 0;   // blocksizes[1]/2, blocksizes[1] >> halfrate, blocksizes[1]/2 >> halfrate
     int max_classes = 0;
     uint8_t *d_setup = nullptr;      // vbmd_setup + blob
-    float *d_tables = nullptr;       // fromdB[256], win0, win1, trig0, trig1
+    float *d_tables = nullptr;       // fromdB[256], win0, win1, trig0, trig1 (of blocksizes[w] >> halfrate)
     const float *fromdB = nullptr, *win[2] = {}, *trig[2] = {};
     int *d_ids = nullptr, *d_info = nullptr, *d_fit = nullptr, *d_flags = nullptr, *d_status = nullptr;
     int *d_lists = nullptr, *d_counts = nullptr;
@@ -61,8 +66,10 @@ struct vbm_decoder {
         L.blob = d_setup + sizeof(vbmd_setup);
         L.nsb = nsb;
         L.ch = ch;
+        L.hs = halfrate;
         L.half = half;
         L.n1 = n1;
+        L.ohalf = ohalf;
         L.info = d_info;
         L.fit = d_fit;
         L.flags = d_flags;
@@ -137,7 +144,16 @@ int check_ids(vbm_decoder *d, int n, const int *ids)
 
 extern "C" int vbm_decoder_create(vbm_decoder **out, const vbm_decode_setup *ds, int nstreams, int max_batch)
 {
+    return vbm_decoder_create_halfrate(out, ds, nstreams, max_batch, 0);
+}
+
+extern "C" int vbm_decoder_halfrate(const vbm_decoder *d) { return d ? d->halfrate : VBM_EINVAL; }
+
+extern "C" int vbm_decoder_create_halfrate(vbm_decoder **out, const vbm_decode_setup *ds, int nstreams, int max_batch,
+                                           int halfrate)
+{
     if (!out || !ds || nstreams <= 0 || max_batch <= 0) return VBM_EINVAL;
+    if (halfrate != 0 && halfrate != 1) { g_vbm_err = "halfrate must be 0 or 1"; return VBM_EINVAL; }
     *out = nullptr;
     const int ndev = vbm_device_count();
     if (ndev < 0) return ndev;
@@ -150,8 +166,10 @@ extern "C" int vbm_decoder_create(vbm_decoder **out, const vbm_decode_setup *ds,
     d->S = nstreams;
     d->cap = max_batch;
     d->ch = ds->s.channels;
-    d->n1 = ds->s.blocksizes[1];
-    d->half = d->n1 / 2;
+    d->halfrate = halfrate;
+    d->half = ds->s.blocksizes[1] / 2;
+    d->n1 = ds->s.blocksizes[1] >> halfrate;
+    d->ohalf = d->half >> halfrate;
     d->max_classes = ds->s.max_classes;
     const size_t cap = (size_t)max_batch, ch = (size_t)d->ch;
     hipError_t e = hipSuccess;
@@ -161,12 +179,17 @@ extern "C" int vbm_decoder_create(vbm_decoder **out, const vbm_decode_setup *ds,
     CK(hipMemcpy(d->d_setup, &ds->s, sizeof(vbmd_setup), hipMemcpyHostToDevice));
     if (!ds->blob.empty())
         CK(hipMemcpy(d->d_setup + sizeof(vbmd_setup), ds->blob.data(), ds->blob.size(), hipMemcpyHostToDevice));
-    // tables: FLOOR1_fromdB_LOOKUP, the two windows, the two MDCT trig tables (lib/mdct.c:67-76)
+    // tables: FLOOR1_fromdB_LOOKUP, the two windows, the two MDCT trig tables (lib/mdct.c:67-76); at half rate the
+    // windows and transforms of half each block size (lib/block.c:208-209, _vorbis_window_get(b->window[W] - hs))
     std::vector<float> tab(ds->fromdB);
     size_t off_win[2], off_trig[2];
-    for (int w = 0; w < 2; w++) { off_win[w] = tab.size(); tab.insert(tab.end(), ds->win[w].begin(), ds->win[w].end()); }
     for (int w = 0; w < 2; w++) {
-        const int n = ds->s.blocksizes[w];
+        const std::vector<float> &win = halfrate ? ds->hwin[w] : ds->win[w];
+        off_win[w] = tab.size();
+        tab.insert(tab.end(), win.begin(), win.end());
+    }
+    for (int w = 0; w < 2; w++) {
+        const int n = ds->s.blocksizes[w] >> halfrate;
         std::vector<float> t((size_t)n + n / 4);
         vbm_host_mdct_trig(n, t.data());
         while (tab.size() % 4) tab.push_back(0.f);
@@ -191,7 +214,7 @@ extern "C" int vbm_decoder_create(vbm_decoder **out, const vbm_decode_setup *ds,
     CK(hipMalloc((void **)&d->d_spec, cap * ch * d->half * sizeof(float)));
     CK(hipMalloc((void **)&d->d_imdct, cap * ch * d->n1 * sizeof(float)));
     CK(hipMalloc((void **)&d->d_cls, cap * (size_t)d->max_classes));
-    CK(hipMalloc((void **)&d->d_tail, (size_t)nstreams * ch * d->half * sizeof(float)));
+    CK(hipMalloc((void **)&d->d_tail, (size_t)nstreams * ch * d->ohalf * sizeof(float)));
     CK(hipMalloc((void **)&d->d_prevW, (size_t)nstreams * sizeof(int)));
     CK(hipMalloc((void **)&d->d_gp, (size_t)nstreams * sizeof(long long)));
     CK(hipMalloc((void **)&d->d_sc, (size_t)nstreams * sizeof(long long)));
@@ -229,7 +252,7 @@ extern "C" int vbm_decoder_reset(vbm_decoder *d)
     if (e == hipSuccess) e = hipMemset(d->d_prevW, 0xff, (size_t)d->S * sizeof(int));      // -1: no block yet
     if (e == hipSuccess) e = hipMemset(d->d_gp, 0xff, (size_t)d->S * sizeof(long long));
     if (e == hipSuccess) e = hipMemset(d->d_sc, 0xff, (size_t)d->S * sizeof(long long));
-    if (e == hipSuccess) e = hipMemset(d->d_tail, 0, (size_t)d->S * d->ch * d->half * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(d->d_tail, 0, (size_t)d->S * d->ch * d->ohalf * sizeof(float));
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_decoder_reset");
     d->last_nsb = 0;
@@ -265,7 +288,7 @@ extern "C" int vbm_synthesis_batch(vbm_decoder *d, int nsb, const int *stream_id
     if (vbmd_launch_unpack(L, d_packets, packet_stride, d_packet_bytes, d_status, q)) return VBM_EHIP;
     if (vbmd_launch_spectrum(L, d->d_spec, nullptr, q)) return VBM_EHIP;
     for (int W = 0; W < 2; W++)
-        if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W], d->trig[W], q)) return VBM_EHIP;
+        if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W] >> d->halfrate, d->trig[W], q)) return VBM_EHIP;
     if (vbmd_launch_overlap(L, d->d_ids, d_granulepos, d_eos, d_pcm, d_samples, q)) return VBM_EHIP;
     d->last_nsb = nsb;
     return VBM_OK;
@@ -295,7 +318,11 @@ extern "C" int vbm_synthesis_runs(vbm_decoder *d, int nruns, const int *stream_i
     }
     d->run_start[nruns] = (int)P;
     if (P > 0 && (!d_pcm || !d_samples || !d_status)) return VBM_EINVAL;
-    if (pcm_stride < (long)most * d->half) { g_vbm_err = "pcm_stride below max(run_packets) * blocksizes[1]/2"; return VBM_EINVAL; }
+    if (pcm_stride < (long)most * d->ohalf) {
+        g_vbm_err = d->halfrate ? "pcm_stride below max(run_packets) * blocksizes[1]/4"
+                                : "pcm_stride below max(run_packets) * blocksizes[1]/2";
+        return VBM_EINVAL;
+    }
     hipStream_t q = (hipStream_t)stream;
     const int *parts[2] = {stream_ids, d->run_start.data()};
     const int lens[2] = {nruns, nruns + 1};
@@ -308,7 +335,7 @@ extern "C" int vbm_synthesis_runs(vbm_decoder *d, int nruns, const int *stream_i
     if (vbmd_launch_unpack_csr(L, d_data, d_offsets, data_bytes, d_status, q)) return VBM_EHIP;
     if (vbmd_launch_spectrum(L, d->d_spec, nullptr, q)) return VBM_EHIP;
     for (int W = 0; W < 2; W++)
-        if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W], d->trig[W], q)) return VBM_EHIP;
+        if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W] >> d->halfrate, d->trig[W], q)) return VBM_EHIP;
     if (vbmd_launch_runs(L, nruns, d->d_runtab, d_granulepos, d_eos, d->d_plan, d->d_run_last, d_pcm, pcm_stride,
                          d_run_samples, d_samples, q))
         return VBM_EHIP;
@@ -397,7 +424,7 @@ extern "C" int vbm_range_store_create(vbm_range_store **out, vbm_decoder *d, int
     std::vector<long long> out_start((size_t)P);
     for (int i = 0; i < nstreams; i++) {
         const long long a = stream_packets[i];
-        vbmd_index_stream(d->hs, stream_packets[i + 1] - a, data, offsets + a, data_bytes,
+        vbmd_index_stream(d->hs, d->halfrate, stream_packets[i + 1] - a, data, offsets + a, data_bytes,
                           granulepos ? granulepos + a : nullptr, eos ? eos + a : nullptr, st->status.data() + a,
                           begin.data() + a, end.data() + a, out_start.data() + a, &st->totals[i]);
     }
@@ -514,7 +541,7 @@ extern "C" int vbm_synthesis_ranges(vbm_decoder *d, const vbm_range_store *st, i
             return VBM_EHIP;
         if (vbmd_launch_spectrum(L, d->d_spec, nullptr, q)) return VBM_EHIP;
         for (int W = 0; W < 2; W++)
-            if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W], d->trig[W], q)) return VBM_EHIP;
+            if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W] >> d->halfrate, d->trig[W], q)) return VBM_EHIP;
         if (vbmd_launch_ranges(L, np, d->d_rtab, d->d_rows, st->d_begin, st->d_end, st->d_out_start, d->d_zero,
                                d->d_plan, d_pcm + (size_t)r0 * d->ch * pcm_stride, pcm_stride, q))
             return VBM_EHIP;

@@ -330,12 +330,16 @@ VBMD_HD int vbmd_head(const vbmd_setup &s, vbmd_bits &b, int &mode, int &W, int 
 // block size lW (-1: the stream's first): the part of the packet's output that becomes final, [begin, end), and the
 // stream's sample count sc and granulepos gp (-1: none yet), advanced by the packet's granulepos vgp (-1: none) and
 // its end-of-stream flag.  One definition for k_overlap, k_run_plan and the host index (vbmd_index_stream).
+// HS: the reference's halfrate_flag.  begin / end are output samples (half as many at HS = 1); sc, gp and vgp stay
+// full-rate, so a trim of `extra` full-rate samples, clamped to twice what the packet returns, takes extra >> 1
+// output samples.  At HS = 0 every shift is by zero.
+template <int HS = 0>
 VBMD_HD void vbmd_blockin(const int *blocksizes, int lW, int W, long long vgp, int eof, long long &sc, long long &gp,
                           long &begin, long &end)
 {
     begin = 0;
     end = 0;
-    if (lW >= 0) end = (blocksizes[lW] >> 2) + (blocksizes[W] >> 2);
+    if (lW >= 0) end = ((blocksizes[lW] >> 2) + (blocksizes[W] >> 2)) >> HS;
     const long long step = (lW >= 0 ? (blocksizes[lW] >> 2) : 0) + (blocksizes[W] >> 2);
     sc = (sc == -1) ? 0 : sc + step;
     if (gp == -1) {
@@ -345,10 +349,10 @@ VBMD_HD void vbmd_blockin(const int *blocksizes, int lW, int W, long long vgp, i
                 long long extra = sc - vgp;
                 if (extra < 0) extra = 0;
                 if (eof) {
-                    if (extra > end - begin) extra = end - begin;
-                    end -= extra;
+                    if (extra > (long long)(end - begin) << HS) extra = (long long)(end - begin) << HS;
+                    end -= extra >> HS;
                 } else {
-                    begin += extra;
+                    begin += extra >> HS;
                     if (begin > end) begin = end;
                 }
             }
@@ -359,9 +363,9 @@ VBMD_HD void vbmd_blockin(const int *blocksizes, int lW, int W, long long vgp, i
             if (gp > vgp) {
                 long long extra = gp - vgp;
                 if (extra && eof) {
-                    if (extra > end - begin) extra = end - begin;
+                    if (extra > (long long)(end - begin) << HS) extra = (long long)(end - begin) << HS;
                     if (extra < 0) extra = 0;
-                    end -= extra;
+                    end -= extra >> HS;
                 }
             }
             gp = vgp;

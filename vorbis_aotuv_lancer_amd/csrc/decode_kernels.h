@@ -9,12 +9,14 @@ struct vbmd_launch {
     const vbmd_setup *s;             // device copy of the setup, the book blob follows it
     const uint8_t *blob;
     int nsb, ch;
-    long half, n1;                   // blocksizes[1]/2, blocksizes[1]
+    int hs;                          // 1: half-rate decoder (IMDCT, windows, overlap-add and PCM at half the sizes)
+    long half, n1;                   // blocksizes[1]/2 (residue / spectrum rows), blocksizes[1] >> hs (IMDCT rows)
+    long ohalf;                      // blocksizes[1]/2 >> hs (tail and PCM rows)
     int *info, *fit, *flags, *status, *lists, *counts;
     float *res, *spec, *imdct;
     uint8_t *cls;
     const float *fromdB, *win0, *win1;
-    float *tail;                     // [streams][ch][half]
+    float *tail;                     // [streams][ch][ohalf]
     int *prevW;                      // [streams] -1: no block yet (pcm_returned == -1)
     long long *gp, *sc;              // [streams] granulepos, sample_count
 };
@@ -22,6 +24,7 @@ struct vbmd_launch {
 int vbmd_launch_unpack(const vbmd_launch &L, const uint8_t *packets, long stride, const int *nbytes, int *status_out,
                        hipStream_t q);
 int vbmd_launch_spectrum(const vbmd_launch &L, float *spec, int *findex, hipStream_t q);
+// N: the transform size, blocksizes[W] >> hs (128 .. 4096), trig its table
 int vbmd_launch_imdct(const vbmd_launch &L, int W, int N, const float *trig, hipStream_t q);
 int vbmd_launch_overlap(const vbmd_launch &L, const int *ids, const long long *granulepos, const uint8_t *eos,
                         float *pcm, int *samples, hipStream_t q);

@@ -24,6 +24,11 @@
 // after it.  k_range_rows maps rows to store packets, k_unpack_rows unpacks them from the store, k_spectrum and
 // k_imdct* are the same launches, k_range_plan writes k_run_plan's entries from the store's index and k_overlap_runs
 // runs unchanged.  No stream state is read or written.
+//
+// Half rate (vbm_decoder_create_halfrate; the reference's vorbis_synthesis_halfrate, lib/synthesis.c:166-179): unpack and
+// spectrum are the same launches at the full block size; k_imdct<blocksizes[W] / 2> transforms the lower half of each
+// spectrum (128 .. 2048 points) and k_overlap<1>, k_run_plan<1>, k_overlap_runs<1> and k_run_commit<1> are the overlap
+// kernels with every size halved.  A full-rate decoder launches the <0> instantiations, in which every shift is by zero.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -219,14 +224,16 @@ __device__ __forceinline__ void store_rev4(float *o, const float *v)   // o[0..3
     *reinterpret_cast<float4 *>(o) = make_float4(v[3], v[2], v[1], v[0]);
 }
 
-// one wavefront per 512-complex group (BPG blocks of N = 256 .. 2048); blocks b of the row list of this block size
+// one wavefront per 512-complex group (BPG blocks of N = 128 .. 2048; 128 only in a half-rate decoder, whose transform
+// of a 256-sample block it is); blocks b of the row list of this block size.  Reads in[0, N/2) of each block's `half`
+// bins and writes N floats of its n1-float output row.
 template <int N>
 __global__ __launch_bounds__(64 * IM_WAVES)
 void k_imdct(const float *__restrict__ spec, float *__restrict__ out, const int *__restrict__ list,
              const int *__restrict__ count, int ch, long half, long n1, const float *__restrict__ trig_g)
 {
     constexpr int C = N / 4, BPG = 512 / C, NTRIG = N + N / 4;
-    constexpr int LOG2C = (N == 2048) ? 9 : (N == 1024) ? 8 : (N == 512) ? 7 : 6;
+    constexpr int LOG2C = (N == 2048) ? 9 : (N == 1024) ? 8 : (N == 512) ? 7 : (N == 256) ? 6 : 5;
     __shared__ __attribute__((aligned(16))) float s_trig[NTRIG];
     __shared__ __attribute__((aligned(16))) float2 s_x[IM_WAVES][SLOTS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -351,6 +358,10 @@ void k_imdct_4096(const float *__restrict__ spec, float *__restrict__ out, const
 #undef SLOT
 }
 
+// HS: 0, or 1 in a half-rate decoder (lib/block.c:897-1166 with hs = 1): every size is that of the halved block, n1 the
+// IMDCT row of blocksizes[1] >> HS floats, `half` the tail and PCM row of blocksizes[1] >> (1 + HS), win0 / win1 the
+// windows of the halved sizes.
+template <int HS>
 __global__ __launch_bounds__(256)
 void k_overlap(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict__ ids, const int *__restrict__ status,
                const int *__restrict__ info, const float *__restrict__ imdct, long n1,
@@ -367,13 +378,13 @@ void k_overlap(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict_
     const int ch = s->channels, sid = ids[row];
     const int W = info[4 * row + 1], lW = prevW[sid];
     const int bs0 = s->blocksizes[0], bs1 = s->blocksizes[1];
-    const int n = s->blocksizes[W] >> 1, n0 = bs0 >> 1, nh1 = bs1 >> 1;
+    const int n = s->blocksizes[W] >> (1 + HS), n0 = bs0 >> (1 + HS), nh1 = bs1 >> (1 + HS);
     // vorbis_synthesis_blockin: what becomes final, and the granulepos bookkeeping
     long long sc = st_sc[sid], gp = st_gp[sid];
     const long long vgp = granulepos ? granulepos[row] : -1;
     const int eof = eos ? eos[row] : 0;
     long begin, end;
-    vbmd_blockin(s->blocksizes, lW, W, vgp, eof, sc, gp, begin, end);
+    vbmd_blockin<HS>(s->blocksizes, lW, W, vgp, eof, sc, gp, begin, end);
     for (int c = 0; c < ch; c++) {
         const float *p = imdct + ((long)row * ch + c) * n1;
         float *t = tail + ((long)sid * ch + c) * half;
@@ -411,6 +422,7 @@ void k_overlap(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict_
 // plan[k] = {run, previous valid row of the run (-1: the stream's tail), lW, begin, end, output offset}, and samples[k].
 // The run's final prevW / granulepos / sample count go straight to the stream state: no kernel of this call reads
 // them after this one.  run_last[r]: the run's last valid row (-1: none), for k_run_commit.
+template <int HS>
 __global__ __launch_bounds__(64)
 void k_run_plan(const vbmd_setup *__restrict__ s, int nruns, const int *__restrict__ runtab,
                 const int *__restrict__ status, const int *__restrict__ info,
@@ -433,7 +445,7 @@ void k_run_plan(const vbmd_setup *__restrict__ s, int nruns, const int *__restri
         const long long vgp = granulepos ? granulepos[k] : -1;
         const int eof = eos ? eos[k] : 0;
         long begin, end;
-        vbmd_blockin(s->blocksizes, lW, W, vgp, eof, sc, gp, begin, end);   // k_overlap's bookkeeping
+        vbmd_blockin<HS>(s->blocksizes, lW, W, vgp, eof, sc, gp, begin, end);   // k_overlap's bookkeeping
         pl[0] = r;
         pl[1] = prev;
         pl[2] = lW;
@@ -455,6 +467,7 @@ void k_run_plan(const vbmd_setup *__restrict__ s, int nruns, const int *__restri
 // One workgroup per row: k_overlap's overlap-add, term for term, with the tail read from the previous valid row's
 // IMDCT output (its second half, which is what k_overlap's tail copy would hold) or, for a run's first valid row,
 // from the stream's tail.  Output: the run's PCM [nruns][ch][pcm_stride] at the planned offset.
+template <int HS>
 __global__ __launch_bounds__(256)
 void k_overlap_runs(const vbmd_setup *__restrict__ s, const int *__restrict__ runtab, const int *__restrict__ status,
                     const int *__restrict__ info, const int *__restrict__ plan, const float *__restrict__ imdct, long n1,
@@ -470,10 +483,10 @@ void k_overlap_runs(const vbmd_setup *__restrict__ s, const int *__restrict__ ru
     const int ch = s->channels, sid = runtab[run];
     const int W = info[4 * row + 1];
     const int bs0 = s->blocksizes[0], bs1 = s->blocksizes[1];
-    const int n0 = bs0 >> 1, nh1 = bs1 >> 1;
+    const int n0 = bs0 >> (1 + HS), nh1 = bs1 >> (1 + HS);
     for (int c = 0; c < ch; c++) {
         const float *p = imdct + ((long)row * ch + c) * n1;
-        const float *t = prev >= 0 ? imdct + ((long)prev * ch + c) * n1 + (s->blocksizes[lW] >> 1)
+        const float *t = prev >= 0 ? imdct + ((long)prev * ch + c) * n1 + (s->blocksizes[lW] >> (1 + HS))
                                    : tail + ((long)sid * ch + c) * half;
         float *o = pcm + ((long)run * ch + c) * pcm_stride + off;
         for (long i = begin + tid; i < end; i += blockDim.x) {
@@ -497,6 +510,7 @@ void k_overlap_runs(const vbmd_setup *__restrict__ s, const int *__restrict__ ru
 }
 
 // One workgroup per run: the second half of the run's last valid row -> the stream's tail (k_overlap's tail copy)
+template <int HS>
 __global__ __launch_bounds__(256)
 void k_run_commit(const vbmd_setup *__restrict__ s, int nruns, const int *__restrict__ runtab,
                   const int *__restrict__ run_last, const int *__restrict__ info, const float *__restrict__ imdct,
@@ -506,7 +520,7 @@ void k_run_commit(const vbmd_setup *__restrict__ s, int nruns, const int *__rest
     const int last = run_last[r];
     if (last < 0) return;
     const int ch = s->channels, sid = runtab[r];
-    const int n = s->blocksizes[info[4 * last + 1]] >> 1;
+    const int n = s->blocksizes[info[4 * last + 1]] >> (1 + HS);
     for (int c = 0; c < ch; c++) {
         const float *p = imdct + ((long)last * ch + c) * n1;
         float *t = tail + ((long)sid * ch + c) * half;
@@ -651,6 +665,7 @@ int vbmd_launch_imdct(const vbmd_launch &L, int W, int N, const float *trig, hip
     else if (N == 1024) LAUNCH(1024);
     else if (N == 512) LAUNCH(512);
     else if (N == 256) LAUNCH(256);
+    else if (N == 128) LAUNCH(128);
     else return -1;
 #undef LAUNCH
     return last_err();
@@ -660,8 +675,8 @@ int vbmd_launch_overlap(const vbmd_launch &L, const int *ids, const long long *g
                         float *pcm, int *samples, hipStream_t q)
 {
     if (L.nsb <= 0) return 0;
-    hipLaunchKernelGGL(k_overlap, dim3(L.nsb), dim3(256), 0, q, L.s, L.nsb, ids, L.status, L.info, L.imdct, L.n1,
-                       L.win0, L.win1, granulepos, eos, L.tail, L.prevW, L.gp, L.sc, pcm, samples, L.half);
+    hipLaunchKernelGGL(L.hs ? k_overlap<1> : k_overlap<0>, dim3(L.nsb), dim3(256), 0, q, L.s, L.nsb, ids, L.status, L.info,
+                       L.imdct, L.n1, L.win0, L.win1, granulepos, eos, L.tail, L.prevW, L.gp, L.sc, pcm, samples, L.ohalf);
     return last_err();
 }
 
@@ -694,15 +709,15 @@ int vbmd_launch_runs(const vbmd_launch &L, int nruns, const int *runtab, const l
                      int *samples, hipStream_t q)
 {
     if (nruns <= 0) return 0;
-    hipLaunchKernelGGL(k_run_plan, dim3((nruns + 63) / 64), dim3(64), 0, q, L.s, nruns, runtab, L.status, L.info,
+    hipLaunchKernelGGL(L.hs ? k_run_plan<1> : k_run_plan<0>, dim3((nruns + 63) / 64), dim3(64), 0, q, L.s, nruns, runtab, L.status, L.info,
                        granulepos, eos, L.prevW, L.gp, L.sc, plan, samples, run_samples, run_last);
     if (last_err()) return -2;
     if (L.nsb > 0) {
-        hipLaunchKernelGGL(k_overlap_runs, dim3(L.nsb), dim3(256), 0, q, L.s, runtab, L.status, L.info, plan, L.imdct,
-                           L.n1, L.win0, L.win1, L.tail, pcm, pcm_stride, L.half);
+        hipLaunchKernelGGL(L.hs ? k_overlap_runs<1> : k_overlap_runs<0>, dim3(L.nsb), dim3(256), 0, q, L.s, runtab, L.status,
+                           L.info, plan, L.imdct, L.n1, L.win0, L.win1, L.tail, pcm, pcm_stride, L.ohalf);
         if (last_err()) return -2;
-        hipLaunchKernelGGL(k_run_commit, dim3(nruns), dim3(256), 0, q, L.s, nruns, runtab, run_last, L.info, L.imdct,
-                           L.n1, L.tail, L.half);
+        hipLaunchKernelGGL(L.hs ? k_run_commit<1> : k_run_commit<0>, dim3(nruns), dim3(256), 0, q, L.s, nruns, runtab, run_last,
+                           L.info, L.imdct, L.n1, L.tail, L.ohalf);
     }
     return last_err();
 }
@@ -726,7 +741,7 @@ int vbmd_launch_ranges(const vbmd_launch &L, int npieces, const int *rtab, const
     hipLaunchKernelGGL(k_range_plan, dim3((npieces + 63) / 64), dim3(64), 0, q, npieces, rtab, rows, L.status, L.info,
                        pk_begin, pk_end, out_start, plan);
     if (last_err()) return -2;
-    hipLaunchKernelGGL(k_overlap_runs, dim3(L.nsb), dim3(256), 0, q, L.s, runtab, L.status, L.info, plan, L.imdct,
-                       L.n1, L.win0, L.win1, L.tail, pcm, pcm_stride, L.half);
+    hipLaunchKernelGGL(L.hs ? k_overlap_runs<1> : k_overlap_runs<0>, dim3(L.nsb), dim3(256), 0, q, L.s, runtab, L.status,
+                       L.info, plan, L.imdct, L.n1, L.win0, L.win1, L.tail, pcm, pcm_stride, L.ohalf);
     return last_err();
 }

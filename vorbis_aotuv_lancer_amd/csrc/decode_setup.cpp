@@ -550,7 +550,7 @@ int vbmd_setup_parse(vbm_decode_setup *ds, const uint8_t *headers, const long *l
         if (len > 0) maxc = std::max(maxc, (len / r.grouping) * (r.type == 2 ? 1 : s.channels));
     }
     s.max_classes = (int)((maxc + 15) & ~15L);
-    // the tables the device path needs: windows of both block sizes and FLOOR1_fromdB_LOOKUP (common.vpk)
+    // the tables the device path needs: windows of both block sizes and of half each, FLOOR1_fromdB_LOOKUP (common.vpk)
     const std::string path = lib_data_dir() + "/common.vpk";
     vpk_file f;
     if (vpk_open(&f, path.c_str())) { g_vbm_err = "cannot open " + path; return VBM_EFAULT; }
@@ -563,6 +563,11 @@ int vbmd_setup_parse(vbm_decode_setup *ds, const uint8_t *headers, const long *l
         const float *win = (const float *)vpk_get(&f, name.c_str(), VPK_F32, &cnt);
         ok = win && (int)cnt == s.blocksizes[w] / 2;
         if (ok) ds->win[w].assign(win, win + cnt);
+        if (!ok) break;
+        const std::string hname = "window/" + std::to_string(s.blocksizes[w] / 2);
+        win = (const float *)vpk_get(&f, hname.c_str(), VPK_F32, &cnt);
+        ok = win && (int)cnt == s.blocksizes[w] / 4;
+        if (ok) ds->hwin[w].assign(win, win + cnt);
     }
     vpk_close(&f);
     if (!ok) { g_vbm_err = "common.vpk lacks a decode table"; return VBM_EFAULT; }
@@ -602,7 +607,7 @@ extern "C" int vbm_decode_setup_counts(const vbm_decode_setup *ds, int *counts)
     return VBM_OK;
 }
 
-void vbmd_index_stream(const vbmd_setup &s, long long n, const uint8_t *data, const long long *offsets,
+void vbmd_index_stream(const vbmd_setup &s, int halfrate, long long n, const uint8_t *data, const long long *offsets,
                        long long data_bytes, const long long *granulepos, const uint8_t *eos, int *status, int *begin,
                        int *end, long long *out_start, long long *total)
 {
@@ -617,7 +622,10 @@ void vbmd_index_stream(const vbmd_setup &s, long long n, const uint8_t *data, co
         status[k] = vbmd_head(s, bits, mode, W, plW, nW);
         long pb = 0, pe = 0;
         if (status[k] == 0) {
-            vbmd_blockin(s.blocksizes, lW, W, granulepos ? granulepos[k] : -1, eos ? eos[k] : 0, sc, gp, pb, pe);
+            const long long vgp = granulepos ? granulepos[k] : -1;
+            const int eof = eos ? eos[k] : 0;
+            if (halfrate) vbmd_blockin<1>(s.blocksizes, lW, W, vgp, eof, sc, gp, pb, pe);
+            else vbmd_blockin<0>(s.blocksizes, lW, W, vgp, eof, sc, gp, pb, pe);
             lW = W;
         }
         if (begin) begin[k] = (int)pb;
@@ -632,11 +640,21 @@ extern "C" int vbm_decode_index(const vbm_decode_setup *ds, long long npackets, 
                                 const long long *offsets, long long data_bytes, const long long *granulepos,
                                 const uint8_t *eos, int *status, int *samples, long long *out_start, long long *total)
 {
+    return vbm_decode_index_halfrate(ds, 0, npackets, data, offsets, data_bytes, granulepos, eos, status, samples,
+                                     out_start, total);
+}
+
+extern "C" int vbm_decode_index_halfrate(const vbm_decode_setup *ds, int halfrate, long long npackets,
+                                         const uint8_t *data, const long long *offsets, long long data_bytes,
+                                         const long long *granulepos, const uint8_t *eos, int *status, int *samples,
+                                         long long *out_start, long long *total)
+{
+    if (halfrate != 0 && halfrate != 1) { g_vbm_err = "halfrate must be 0 or 1"; return VBM_EINVAL; }
     if (!ds || npackets < 0 || data_bytes < 0 || (data_bytes > 0 && !data) || !offsets || !total ||
         (npackets > 0 && (!status || !samples || !out_start)))
         return VBM_EINVAL;
     std::vector<int> b((size_t)npackets), e((size_t)npackets);
-    vbmd_index_stream(ds->s, npackets, data, offsets, data_bytes, granulepos, eos, status, b.data(), e.data(),
+    vbmd_index_stream(ds->s, halfrate, npackets, data, offsets, data_bytes, granulepos, eos, status, b.data(), e.data(),
                       out_start, total);
     for (long long k = 0; k < npackets; k++) samples[k] = e[k] - b[k];
     return VBM_OK;

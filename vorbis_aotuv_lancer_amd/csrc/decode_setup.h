@@ -9,12 +9,14 @@ struct vbm_decode_setup {
     std::vector<uint8_t> blob;        // codebook tables (vbmd_book offsets)
     std::vector<float> fromdB;        // FLOOR1_fromdB_LOOKUP [256]
     std::vector<float> win[2];        // rising half-windows of blocksizes[0] and [1] (_vorbis_window_get)
+    std::vector<float> hwin[2];       // ... of blocksizes[0] / 2 and [1] / 2, for half-rate decoders
 };
 
 // The host index of one stream's n packets (CSR as vbm_synthesis_runs takes them, clamped to [0, data_bytes)), from a
 // fresh stream state: per packet the status (vbmd_head) and, for valid packets, vbmd_blockin's [begin, end) (0, 0 for
 // failed ones) and out_start, the exclusive prefix sum of end - begin; *total = the sum.  begin / end may be NULL.
-void vbmd_index_stream(const vbmd_setup &s, long long n, const uint8_t *data, const long long *offsets,
+// halfrate 1: the index of a half-rate decoder, in its output samples (vbmd_blockin<1>).
+void vbmd_index_stream(const vbmd_setup &s, int halfrate, long long n, const uint8_t *data, const long long *offsets,
                        long long data_bytes, const long long *granulepos, const uint8_t *eos, int *status, int *begin,
                        int *end, long long *out_start, long long *total);
 

@@ -76,14 +76,21 @@ class DecodeSetup:
 
 
 class Decoder:
-    """nstreams decode streams on the current CUDA device; up to max_batch packets per call."""
+    """nstreams decode streams on the current CUDA device; up to max_batch packets per call.
+    halfrate=True (the reference's vorbis_synthesis_halfrate): the PCM comes out at dsetup.rate / 2, from inverse
+    MDCTs of half each block size; every PCM row is blocksizes[1]//4 long instead of blocksizes[1]//2, and sample
+    counts, range starts and lengths are output samples.  .rate is the output rate (an int when it is whole)."""
 
-    def __init__(self, dsetup, nstreams, max_batch):
+    def __init__(self, dsetup, nstreams, max_batch, halfrate=False):
         self.dsetup = dsetup
         self.channels, self.blocksizes = dsetup.channels, dsetup.blocksizes
         self.nstreams, self.max_batch = nstreams, max_batch
+        self.halfrate = bool(halfrate)
+        self.rate = output_rate(dsetup.rate, self.halfrate)
+        self.row = dsetup.blocksizes[1] // (4 if self.halfrate else 2)      # most samples one packet returns
         self._h = C.c_void_p()
-        check(lib.vbm_decoder_create(C.byref(self._h), dsetup._h, nstreams, max_batch), "vbm_decoder_create")
+        check(lib.vbm_decoder_create_halfrate(C.byref(self._h), dsetup._h, nstreams, max_batch, int(self.halfrate)),
+              "vbm_decoder_create_halfrate")
         self._last = None
 
     @staticmethod
@@ -93,15 +100,15 @@ class Decoder:
     def synthesis_batch(self, stream_ids, packets, nbytes, granulepos=None, eos=None, out=None):
         """stream_ids: host ints (distinct); packets: uint8 [nsb, stride] and nbytes: int32 [nsb] on the device;
         granulepos: int64 [nsb] (-1: none) or None; eos: uint8 [nsb] or None.
-        -> (pcm float32 [nsb, channels, blocksizes[1]//2], samples int32 [nsb], status int32 [nsb]), device tensors.
-        Only enqueues work on the current stream."""
+        -> (pcm float32 [nsb, channels, blocksizes[1]//2], samples int32 [nsb], status int32 [nsb]), device tensors
+        (blocksizes[1]//4 on a half-rate decoder).  Only enqueues work on the current stream."""
         ids = np.ascontiguousarray(np.asarray(stream_ids, dtype=np.int32))
         nsb = len(ids)
         dev = packets.device
         assert packets.dtype == torch.uint8 and packets.dim() == 2 and packets.is_contiguous()
         nbytes = nbytes.to(torch.int32).contiguous()
         if out is None:
-            pcm = torch.empty((nsb, self.channels, self.blocksizes[1] // 2), dtype=torch.float32, device=dev)
+            pcm = torch.empty((nsb, self.channels, self.row), dtype=torch.float32, device=dev)
             samples = torch.empty(nsb, dtype=torch.int32, device=dev)
             status = torch.empty(nsb, dtype=torch.int32, device=dev)
         else:
@@ -119,7 +126,7 @@ class Decoder:
         """Many packets per stream: run r is counts[r] consecutive packets of stream stream_ids[r] (host ints; ids
         distinct), rows are the runs concatenated (P = sum(counts) <= max_batch).  data: uint8 [bytes] and offsets:
         int64 [P+1] on the device (CSR: packet k is data[offsets[k]:offsets[k+1]]); granulepos int64 [P] / eos uint8
-        [P] or None.  pcm_stride defaults to max(counts) * blocksizes[1]//2.
+        [P] or None.  pcm_stride defaults to max(counts) * blocksizes[1]//2 (//4 on a half-rate decoder).
         -> (pcm float32 [nruns, channels, pcm_stride], run_samples int32 [nruns], samples int32 [P],
         status int32 [P]), device tensors; run r's PCM is pcm[r, :, :run_samples[r]].  Bit-identical to one packet per
         call through synthesis_batch.  Only enqueues work on the current stream."""
@@ -133,9 +140,8 @@ class Decoder:
         offsets = offsets.to(torch.int64).contiguous()
         if offsets.numel() != P + 1:
             raise ValueError(f"offsets must have sum(counts) + 1 = {P + 1} entries, has {offsets.numel()}")
-        half = self.blocksizes[1] // 2
         if pcm_stride is None:
-            pcm_stride = max(1, int(cnt.max(initial=0)) * half)
+            pcm_stride = max(1, int(cnt.max(initial=0)) * self.row)
         if out is None:
             pcm = torch.empty((nruns, self.channels, pcm_stride), dtype=torch.float32, device=dev)
             run_samples = torch.empty(nruns, dtype=torch.int32, device=dev)
@@ -183,7 +189,7 @@ class Decoder:
 
     def fetch(self, name):
         """Intermediate of the last call: "info" [nsb, 4], "floor_used" [nsb, ch], "floor_index" / "residue" /
-        "spectrum" [nsb, ch, blocksizes[1]//2]."""
+        "spectrum" [nsb, ch, blocksizes[1]//2] (the full-rate intermediates on a half-rate decoder too)."""
         nsb, dev = self._last[0], self._last[1]
         rows, kind = C.c_long(), C.c_char()
         st = self._stream()
@@ -221,9 +227,17 @@ class Decoder:
             pass
 
 
-def decode_index(dsetup, data, offsets, granulepos=None, eos=None):
-    """Host index of one stream's demuxed packets (vbm_decode_index; no device needed): data uint8 [bytes], offsets
-    int64 [P+1], granulepos int64 [P], eos uint8 [P] (numpy, as demux_ogg returns them).
+def output_rate(rate, halfrate):
+    """the rate of a decoder's PCM: rate, or rate / 2 at half rate (a float only when rate is odd)"""
+    if not halfrate:
+        return rate
+    return rate // 2 if rate % 2 == 0 else rate / 2
+
+
+def decode_index(dsetup, data, offsets, granulepos=None, eos=None, halfrate=False):
+    """Host index of one stream's demuxed packets (vbm_decode_index_halfrate; no device needed): data uint8 [bytes],
+    offsets int64 [P+1], granulepos int64 [P], eos uint8 [P] (numpy, as demux_ogg returns them).  halfrate: the index
+    of a Decoder(..., halfrate=True), in its output samples.
     -> (status int32 [P], samples int32 [P], out_start int64 [P], total)"""
     data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8))
     offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
@@ -237,17 +251,19 @@ def decode_index(dsetup, data, offsets, granulepos=None, eos=None):
     status, samples = np.zeros(P, np.int32), np.zeros(P, np.int32)
     out_start = np.zeros(P, np.int64)
     total = C.c_longlong()
-    check(lib.vbm_decode_index(dsetup._h, P, data.ctypes.data if len(data) else None, offsets.ctypes.data, len(data),
-                               None if gp is None else gp.ctypes.data, None if eo is None else eo.ctypes.data,
-                               status.ctypes.data, samples.ctypes.data, out_start.ctypes.data, C.byref(total)),
-          "vbm_decode_index")
+    check(lib.vbm_decode_index_halfrate(dsetup._h, int(bool(halfrate)), P, data.ctypes.data if len(data) else None,
+                                        offsets.ctypes.data, len(data), None if gp is None else gp.ctypes.data,
+                                        None if eo is None else eo.ctypes.data, status.ctypes.data,
+                                        samples.ctypes.data, out_start.ctypes.data, C.byref(total)),
+          "vbm_decode_index_halfrate")
     return status, samples, out_start, total.value
 
 
 class RangeStore:
     """The packets of many streams of one Decoder's headers in device memory, with their index, for
     Decoder.synthesis_ranges.  streams: (data, offsets, granulepos, eos) tuples as demux_ogg returns them (granulepos
-    / eos may be None).  .totals: int64 [nstreams], each stream's linear decode length (ov_pcm_total)."""
+    / eos may be None).  .totals: int64 [nstreams], each stream's linear decode length (ov_pcm_total), at the
+    decoder's rate: .halfrate is the decoder's."""
 
     def __init__(self, decoder, streams):
         streams = list(streams)
@@ -269,7 +285,7 @@ class RangeStore:
         gp = np.ascontiguousarray(np.concatenate(gps))
         eo = np.ascontiguousarray(np.concatenate(eoss))
         first = np.ascontiguousarray(np.asarray(first, np.int64))
-        self.decoder, self.nstreams = decoder, len(streams)
+        self.decoder, self.nstreams, self.halfrate = decoder, len(streams), decoder.halfrate
         self.packets = first
         self._h = C.c_void_p()
         check(lib.vbm_range_store_create(C.byref(self._h), decoder._h, len(streams), first.ctypes.data,
@@ -295,9 +311,11 @@ class OggIndex:
     whose identification or setup headers differ are a ValueError).  The files' packets and index stay in device
     memory (about the compressed size + 24 B per packet); no PCM is kept.  .total_samples: int64 [files].
     decode_ranges(file_ids, starts, lengths) -> (pcm float32 [n, channels, max(lengths)] CUDA tensor, zeros past got;
-    got int32 [n]), pcm[r, :, :got[r]] bit for bit decode_ogg's output of that file from starts[r]."""
+    got int32 [n]), pcm[r, :, :got[r]] bit for bit decode_ogg's output of that file from starts[r].
+    halfrate=True: .rate is half the files' rate, and total_samples, starts and lengths are samples at that rate
+    (decode_ogg(files, halfrate=True)'s)."""
 
-    def __init__(self, files, max_batch=4096):
+    def __init__(self, files, max_batch=4096, halfrate=False):
         from .stream import demux_ogg
         if max_batch < 2:
             raise ValueError("max_batch must be at least 2")
@@ -319,8 +337,8 @@ class OggIndex:
                 raise ValueError(f"file {i} has other identification or setup headers than file 0: one OggIndex "
                                  "takes one header class")
         self.setup = DecodeSetup(h0)
-        self.channels, self.rate = self.setup.channels, self.setup.rate
-        self.decoder = Decoder(self.setup, 1, max_batch)
+        self.decoder = Decoder(self.setup, 1, max_batch, halfrate=halfrate)
+        self.channels, self.rate, self.halfrate = self.setup.channels, self.decoder.rate, self.decoder.halfrate
         self.store = RangeStore(self.decoder, [d[1:] for d in demuxed])
         self.total_samples = self.store.totals
 
@@ -337,12 +355,13 @@ class OggIndex:
         self.setup.close()
 
 
-def decode_ogg(files, max_packets=4096):
+def decode_ogg(files, max_packets=4096, halfrate=False):
     """.ogg files (bytes or paths), one logical stream each -> [(pcm float32 [channels, n] contiguous on the current
     device, rate)], one per file.  Files whose identification and setup headers are byte-equal share one DecodeSetup
     and Decoder, one stream per file; their packets go through synthesis_runs in calls of at most max_packets rows.
-    Packets that fail to decode are skipped (as the reference's decoder_example.c skips them).  Waits for the device
-    once, at the end, to place the outputs."""
+    Packets that fail to decode are skipped (as the reference's decoder_example.c skips them).  halfrate=True: half as
+    many samples per file, and the rate returned is the output rate, half the file's (ov_halfrate).  Waits for the
+    device once, at the end, to place the outputs."""
     from .stream import demux_ogg
     if max_packets <= 0:
         raise ValueError("max_packets must be positive")
@@ -368,9 +387,9 @@ def decode_ogg(files, max_packets=4096):
     lens, keep, rates, nlens = [], [], [0] * len(files), 0
     for members in groups.values():
         ds = DecodeSetup(demuxed[members[0]][0])
-        dec = Decoder(ds, len(members), max_packets)
+        dec = Decoder(ds, len(members), max_packets, halfrate=halfrate)
         keep.append((ds, dec))
-        half = ds.blocksizes[1] // 2
+        half = dec.row
         src = [(torch.from_numpy(demuxed[j][1]).to(dev), demuxed[j][2], torch.from_numpy(demuxed[j][3]).to(dev),
                 torch.from_numpy(demuxed[j][4]).to(dev)) for j in members]
         pos = [0] * len(members)
@@ -405,7 +424,7 @@ def decode_ogg(files, max_packets=4096):
             lens.append(run_samples)
             nlens += len(ids)
         for j in members:
-            rates[j] = ds.rate
+            rates[j] = dec.rate
             if not pieces[j]:
                 pieces[j].append((torch.zeros((ds.channels, 0), dtype=torch.float32, device=dev), None))
     n = torch.cat(lens).cpu().tolist() if lens else []   # the one wait for the device
