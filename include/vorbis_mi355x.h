@@ -257,6 +257,18 @@ int vbm_frontend_write_streams(vbm_frontend *fe, const int *stream_ids, int n, c
  * vorbis_analysis_buffer hands out, reference lib/block.c:405-436).  Returns when the samples have been taken. */
 int vbm_frontend_write_streams_strided(vbm_frontend *fe, const int *stream_ids, int n, const float *pcm, int vals,
                                        long stream_stride, long ch_stride, int by_slot, void *stream);
+/* A size per stream (whole files in batches: lengths differ, last writes are ragged, slots turn over): channel c of
+ * stream_ids[k] is the vals[k] floats at pcm + src_offsets[k] + c * ch_strides[k]; stream_ids, src_offsets, vals and
+ * ch_strides are host arrays of n entries, pcm as above (typically one device-resident store of whole files).  It is
+ * vorbis_analysis_buffer + vorbis_analysis_wrote(vals[k]) for each listed stream, with the rules of the call above per
+ * stream: a stream at most once per call, vals[k] > 0, ch_strides[k] >= vals[k], src_offsets[k] >= 0; VBM_EINVAL after
+ * vbm_frontend_finish and if any listed stream's buffer would overrun.  Every check runs before anything is enqueued:
+ * a refused call changes no stream.  One upload of n job records and one append launch, whatever the sizes.  Work put
+ * on `stream` after the call sees the samples taken (as for vbm_frontend_write); a host that wants to rewrite the
+ * source itself synchronises `stream` first. */
+int vbm_frontend_write_ragged(vbm_frontend *fe, const int *stream_ids, int n, const float *pcm,
+                              const long long *src_offsets, const int *vals, const long long *ch_strides,
+                              void *stream);
 int vbm_frontend_restart_streams(vbm_frontend *fe, const int *stream_ids, int n, void *stream);
 /* Buffer occupancy, for callers that do not drain completely after every write (a stream inside a
  * run of short blocks yields up to 8 blocks per 1024 samples, each in its own round): the most

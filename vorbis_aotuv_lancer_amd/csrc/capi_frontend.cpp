@@ -41,6 +41,7 @@ struct vbm_frontend {
     int *d_ids = nullptr, *d_begin = nullptr;             // [S] per-round lists, grouped by block type
     int *h_ids = nullptr, *h_begin = nullptr;             // pinned
     uint8_t *h_flags = nullptr;
+    vbm_fe_job *d_jobs = nullptr, *h_jobs = nullptr;      // [S] job records of a ragged write (device / pinned), made by the first one
     uint8_t *d_hold = nullptr, *h_hold = nullptr;         // [S] streams left alone in the later rounds of a multi-round call
     bool hold_active = false;
     float *d_blocks = nullptr;            // [2][S][ch][blocksizes[1]] block-major batches of one round (two rounds in flight)
@@ -87,6 +88,7 @@ extern "C" void vbm_frontend_destroy(vbm_frontend *fe)
     if (fe->h_ids) (void)hipHostFree(fe->h_ids);
     if (fe->h_begin) (void)hipHostFree(fe->h_begin);
     if (fe->h_flags) (void)hipHostFree(fe->h_flags);
+    if (fe->h_jobs) (void)hipHostFree(fe->h_jobs);
     if (fe->h_hold) (void)hipHostFree(fe->h_hold);
     delete fe;
 }
@@ -353,6 +355,67 @@ extern "C" int vbm_frontend_write_streams_strided(vbm_frontend *fe, const int *s
     (void)hipStreamSynchronize(st);   // d_ids / h_ids are free again
     fe->dirty = true;
     fe->pending_steps += vals / 64 + 1;
+    if (cross) fe->pending_steps += (bs1 / 2 + bs1) / 64;
+    return VBM_OK;
+}
+
+// vorbis_analysis_buffer + vorbis_analysis_wrote(vals[k]) for each listed stream, every stream with a size of its own:
+// channel c of stream_ids[k] is the vals[k] floats at pcm + src_offsets[k] + c * ch_strides[k] (pcm as for
+// vbm_frontend_write_streams_strided; the three arrays are host arrays).  One upload of the job records, one append
+// launch over all listed streams.  Every check runs before anything is enqueued: a refused call changes no stream.
+extern "C" int vbm_frontend_write_ragged(vbm_frontend *fe, const int *stream_ids, int n, const float *pcm,
+                                         const long long *src_offsets, const int *vals, const long long *ch_strides,
+                                         void *stream)
+{
+    if (!fe || n < 0 || (n && (!stream_ids || !pcm || !src_offsets || !vals || !ch_strides))) return VBM_EINVAL;
+    if (n == 0) return VBM_OK;
+    const vbm_setup *s = fe->hs;
+    const int bs1 = s->blocksizes[1];
+    std::vector<char> seen(fe->S, 0);
+    int max_vals = 0;
+    for (int k = 0; k < n; k++) {
+        const int i = stream_ids[k];
+        if (i < 0 || i >= fe->S || seen[i]) return VBM_EINVAL;   // a stream once per call
+        seen[i] = 1;
+        if (vals[k] <= 0 || ch_strides[k] < vals[k] || src_offsets[k] < 0) return VBM_EINVAL;
+        if (fe->ended[i]) { g_vbm_err = "vbm_frontend_write_ragged after vbm_frontend_finish"; return VBM_EINVAL; }
+        if (!fe->mirrors_stale && fe->pcm_current[i] + (long)vals[k] > fe->f.cap - 3 * bs1 - fe->f.base_max) {
+            g_vbm_err = "PCM buffer full: drain blocks with vbm_frontend_encode_round before writing more";
+            return VBM_EINVAL;
+        }
+        if (vals[k] > max_vals) max_vals = vals[k];
+    }
+    hipStream_t st = fe->q;
+    int rc;
+    if (!fe->h_jobs) {                // the staging area: made by the first ragged write, so that front ends that never
+        hipError_t e;                 // see one are laid out in memory as they always were
+        if (!fe->d_jobs && (rc = fe_alloc(fe, &fe->d_jobs, (size_t)fe->S))) return rc;
+        if ((e = hipHostMalloc((void **)&fe->h_jobs, fe->S * sizeof(vbm_fe_job), hipHostMallocDefault)) != hipSuccess)
+            return vbm_set_hip_error(e, "hipHostMalloc(ragged jobs)");
+        if ((e = hipDeviceSynchronize()) != hipSuccess) return vbm_set_hip_error(e, "hipDeviceSynchronize");   // the zero fill
+    }
+    rc = fe_enter(fe, stream);
+    if (rc) return rc;
+    (void)hipStreamSynchronize(st);   // h_jobs may still be on its way from the call before
+    for (int k = 0; k < n; k++) {
+        vbm_fe_job &j = fe->h_jobs[k];
+        j.src = src_offsets[k]; j.ch_stride = ch_strides[k]; j.stream = stream_ids[k]; j.vals = vals[k];
+    }
+    hipError_t err = hipMemcpyAsync(fe->d_jobs, fe->h_jobs, n * sizeof(vbm_fe_job), hipMemcpyHostToDevice, st);
+    if (err != hipSuccess) return vbm_set_hip_error(err, "hipMemcpyAsync(ragged jobs)");
+    if (vbm_fe_launch_append_ragged(&fe->f, fe->d_jobs, n, max_vals, pcm, s->pre_amplitude, st)) return VBM_EHIP;
+    bool cross = false;
+    for (int k = 0; k < n; k++) {
+        const int i = stream_ids[k];
+        fe->pcm_current[i] += vals[k];
+        fe->written[i] += vals[k];
+        if (!fe->started[i] && fe->written[i] > bs1) { fe->started[i] = 1; cross = true; }   // lib/block.c:547-550
+    }
+    if (cross && vbm_fe_launch_extrapolate(&fe->f, nullptr, 0, 0, bs1, st)) return VBM_EHIP;
+    rc = fe_leave(fe, stream);        // the caller's stream sees the samples taken; nothing here waits for the device
+    if (rc) return rc;
+    fe->dirty = true;
+    fe->pending_steps += max_vals / 64 + 1;
     if (cross) fe->pending_steps += (bs1 / 2 + bs1) / 64;
     return VBM_OK;
 }

@@ -40,6 +40,14 @@ struct vbm_fe_state {
     float *ve_spec;              // [S*ch][VBM_FE_CHUNK][64] spectra of the 128-point search MDCTs
 };
 
+// one per listed stream of a ragged write (k_fe_append_ragged / k_fe_commit_ragged): channel c of `stream` gets the
+// `vals` floats at source + src + c * ch_stride
+struct vbm_fe_job {
+    long long src;               // floats from the call's source pointer to channel 0
+    long long ch_stride;         // floats between the channels (>= vals)
+    int stream, vals;
+};
+
 // one per stream and round (host readable)
 struct vbm_fe_decision {
     int ready;                   // vorbis_analysis_blockout returned 1

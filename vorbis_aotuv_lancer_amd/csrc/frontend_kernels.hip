@@ -3,6 +3,7 @@
 //
 //   k_fe_append / k_fe_commit       vorbis_analysis_buffer + vorbis_analysis_wrote(vals > 0)
 //                                   (reference lib/block.c:405-436, :511-553): pre_amplitude, append
+//   k_fe_append_ids / _ragged       the same for listed streams: one size for all / a size per stream
 //   k_fe_extrapolate                _preextrapolate_helper (lib/block.c:438-484) and the end-of-stream
 //                                   padding of vorbis_analysis_wrote(0) (:520-552), with
 //                                   vorbis_lpc_from_data / vorbis_lpc_predict (lib/lpc.c:60-159).
@@ -95,6 +96,44 @@ __global__ void k_fe_commit_ids(vbm_fe_state f, const int *__restrict__ ids, int
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const int s = ids[k];
+    if (f.base[s] + f.pcm_current[s] + vals > f.cap) { atomicAdd(f.overflow, 1); return; }
+    f.pcm_current[s] += vals;
+}
+
+// the same with a size of its own for every listed stream (vbm_frontend_write_ragged): jobs[k] names the stream, its
+// `vals` and where its channels lie in src.  The grid's y covers the largest vals of the call: a block whose slice
+// starts past its own stream's vals has nothing to do.  16 bytes per thread and step where this stream's source,
+// destination and vals allow it (a whole block takes one path: the test is per (stream, channel)).
+__global__ void k_fe_append_ragged(vbm_fe_state f, const vbm_fe_job *__restrict__ jobs, const float *__restrict__ src,
+                                   float pre_amplitude)
+{
+    const int kc = blockIdx.x;                      // listed stream k, channel c
+    const int k = kc / f.ch, c = kc % f.ch;
+    const vbm_fe_job j = jobs[k];
+    const int s = j.stream, vals = j.vals;
+    if (f.base[s] + f.pcm_current[s] + vals > f.cap) return;   // full (k_fe_commit_ragged counts it): never write past the buffer
+    float *dst = f.pcm + (long)f.parity[s] * f.plane + ((long)s * f.ch + c) * f.cap + f.base[s] + f.pcm_current[s];
+    const float *in = src + j.src + (long long)c * j.ch_stride;
+    const int t0 = blockIdx.y * blockDim.x + threadIdx.x, step = gridDim.y * blockDim.x;
+    if ((((uintptr_t)dst | (uintptr_t)in) & 15) == 0 && (vals & 3) == 0) {
+        const float4 *in4 = reinterpret_cast<const float4 *>(in);
+        float4 *dst4 = reinterpret_cast<float4 *>(dst);
+        for (int i = t0; i < vals / 4; i += step) {
+            float4 v = in4[i];
+            v.x *= pre_amplitude; v.y *= pre_amplitude; v.z *= pre_amplitude; v.w *= pre_amplitude;   // lib/block.c:514-518
+            dst4[i] = v;
+        }
+        return;
+    }
+    for (int i = t0; i < vals; i += step)
+        dst[i] = in[i] * pre_amplitude;
+}
+
+__global__ void k_fe_commit_ragged(vbm_fe_state f, const vbm_fe_job *__restrict__ jobs, int n)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int s = jobs[k].stream, vals = jobs[k].vals;
     if (f.base[s] + f.pcm_current[s] + vals > f.cap) { atomicAdd(f.overflow, 1); return; }
     f.pcm_current[s] += vals;
 }
@@ -844,6 +883,17 @@ extern "C" int vbm_fe_launch_append_ids(const vbm_fe_state *f, const int *d_ids,
     hipLaunchKernelGGL(k_fe_append_ids, dim3((unsigned)(n * f->ch), gy ? gy : 1), dim3(256), 0, st, *f, d_ids, d_src, vals,
                        pre_amplitude, stream_stride, ch_stride, by_slot);
     hipLaunchKernelGGL(k_fe_commit_ids, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *f, d_ids, n, vals);
+    return CHECK_LAUNCH();
+}
+
+extern "C" int vbm_fe_launch_append_ragged(const vbm_fe_state *f, const vbm_fe_job *d_jobs, int n, int max_vals,
+                                           const float *d_src, float pre_amplitude, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    const unsigned gy = (unsigned)((max_vals + 1023) / 1024);   // a thread moves 16 bytes per step
+    hipLaunchKernelGGL(k_fe_append_ragged, dim3((unsigned)(n * f->ch), gy ? gy : 1), dim3(256), 0, st, *f, d_jobs, d_src,
+                       pre_amplitude);
+    hipLaunchKernelGGL(k_fe_commit_ragged, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *f, d_jobs, n);
     return CHECK_LAUNCH();
 }
 

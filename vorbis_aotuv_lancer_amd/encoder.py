@@ -200,6 +200,27 @@ class FrontEnd:
                                                      int(stream_stride), int(ch_stride), int(bool(by_slot)), st),
               "vbm_frontend_write_streams_strided")
 
+    def write_ragged(self, stream_ids, pcm, offsets, vals, ch_strides=None):
+        """vbm_frontend_write_ragged: channel c of stream_ids[k] is the vals[k] floats at pcm + offsets[k] + c *
+        ch_strides[k] (default: vals[k]); pcm: a contiguous CUDA float32 tensor, typically one store of whole files.
+        One call for any mix of sizes.  The source must stay unchanged until the current stream has passed the call."""
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        nv = np.ascontiguousarray(vals, dtype=np.int32)
+        cs = nv.astype(np.int64) if ch_strides is None else np.ascontiguousarray(ch_strides, dtype=np.int64)
+        n = len(ids)
+        if not (off.shape == nv.shape == cs.shape == ids.shape == (n,)):
+            raise ValueError("stream_ids, offsets, vals and ch_strides need one entry per listed stream")
+        if not (pcm.dtype == torch.float32 and pcm.is_contiguous()):
+            raise ValueError("pcm must be a contiguous float32 tensor")
+        ch = self.enc.setup.channels
+        # the C call checks everything about the streams; only the caller of it knows where the source ends
+        if n and ((off < 0).any() or (off + (ch - 1) * np.maximum(cs, 0) + nv > pcm.numel()).any()):
+            raise ValueError("a listed stream's samples lie outside pcm")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(lib.vbm_frontend_write_ragged(self._h, ids.ctypes.data, n, pcm.data_ptr(), off.ctypes.data, nv.ctypes.data,
+                                            cs.ctypes.data, st), "vbm_frontend_write_ragged")
+
     def restart_streams(self, stream_ids):
         """a new stream starts in each listed slot"""
         ids = np.ascontiguousarray(stream_ids, dtype=np.int32)
