@@ -71,6 +71,70 @@ def test_frontend_write_errors(cuda):
     assert lib.vbm_frontend_finish(fe._h, np.array([0], np.int32).ctypes.data, 1, None) == VBM_EINVAL   # finished twice
 
 
+def test_device_guard_refuses_oversized_writes(oracle, cuda):
+    """The kernels' own guard (f.overflow = device_stats()[5] = FrontEnd.refused_writes), on all three intake paths.
+    After a device-built round the host mirrors are stale and the host check steps aside, so a write of twice the
+    front end's capacity (more than a channel's whole buffer, whatever its fill) reaches the device: every listed
+    stream is counted as refused, no sample is taken, and the streams go on to the oracle's packets for the signal
+    without the refused samples."""
+    import vorbis_aotuv_lancer_amd as v
+    from tests.signals import synth_signal
+    from tests.test_frontend_gpu import collect_device
+    S, ch, n, before = 3, 2, 14 * 1024, 4
+    sigs = [synth_signal(ch, 44100, n, seed=880 + s) for s in range(S)]
+    osetup = orc.Setup(oracle, ch, 44100, 0.5)
+    want = []
+    for sig in sigs:
+        st = orc.Stream(osetup)
+        oracle.lib.orc_stream_set_capture(st.v, 0)
+        seq = []
+        for at in range(0, n, 1024):
+            st.write(sig[:, at:at + 1024])
+            seq.extend(st.blocks())
+        st.finish()
+        seq.extend(st.blocks())
+        st.close()
+        want.append([((b["lW"], b["W"], b["nW"], b["block_mode"], b["eos"], b["granulepos"], b["sequence"]), b["packet"])
+                     for b in seq])
+    setup = v.Setup(ch, 44100, 0.5)
+    enc = v.Encoder(setup, S, max_batch=v.lib.vbm_device_round_lanes(setup._h, S))
+    fe = v.FrontEnd(enc)
+    got = [[] for _ in range(S)]
+    allp = torch.from_numpy(np.stack(sigs)).to(cuda)
+    for at in range(0, before * 1024, 1024):
+        fe.write(allp[:, :, at:at + 1024].contiguous())
+    collect_device(got, fe, fe.encode_rounds_device(nrounds=2))     # the host mirrors are stale from here on
+    fe.device_stats()
+    assert fe.refused_writes == 0
+
+    big = 2 * fe.capacity
+    zeros = torch.zeros((S, ch, big), device=cuda)
+    rose = []
+    for write in (lambda: fe.write(zeros), lambda: fe.write_streams([0], zeros[:1]),
+                  lambda: fe.write_ragged([0], zeros[:1], [0], [big])):
+        at0 = fe.refused_writes
+        write()
+        fe.device_stats()
+        rose.append(fe.refused_writes - at0)
+    assert rose == [S, 1, 1]
+    # what every stream holds: the half long block it starts with and the samples written, less what its blocks so far
+    # moved its window on by (a quarter of the block's own size and a quarter of the next one's, lib/block.c:742-759)
+    bs = setup.blocksizes
+    held = [bs[1] // 2 + before * 1024 - sum(bs[m[1]] // 4 + bs[m[2]] // 4 for m, _ in got[s]) for s in range(S)]
+    assert fe.max_buffered == max(held)
+
+    drain(fe, got)
+    for at in range(before * 1024, n, 1024):
+        fe.write(allp[:, :, at:at + 1024].contiguous())
+        drain(fe, got)
+    fe.finish()
+    drain(fe, got)
+    for s in range(S):
+        assert got[s] == want[s], f"stream {s} differs from the oracle"
+    fe.device_stats()
+    assert fe.refused_writes == S + 2
+
+
 @pytest.mark.parametrize("ch,rate,q", [(2, 44100, 0.5), (6, 48000, 0.8)])
 def test_digital_silence_and_near_silence(oracle, cuda, ch, rate, q):
     """stream 0: exact zeros; stream 1: 1e-6 noise; stream 2: silence, then a click, then silence"""

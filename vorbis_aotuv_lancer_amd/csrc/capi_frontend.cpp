@@ -259,42 +259,74 @@ extern "C" int vbm_frontend_capacity(const vbm_frontend *fe)
     return fe ? (int)(fe->f.cap - 3 * fe->hs->blocksizes[1] - fe->f.base_max) : VBM_EINVAL;
 }
 
-extern "C" int vbm_frontend_write(vbm_frontend *fe, const float *d_pcm, int vals, void *stream)
+// ---- PCM intake: one set of rules, three ways to hand the samples over ---------------------------------------------
+// What a write is refused for, before anything is enqueued (a refused call changes no stream).  ids: the listed
+// streams, each at most once (nullptr: all n = S streams); vals_of(k): the samples for the k-th of them, 0 if its
+// arguments are wrong; who: the entry point's name for the message.  Returns the largest vals_of(k), or the error.
+template <typename ValsOf>
+static int fe_check_write(vbm_frontend *fe, const int *ids, int n, ValsOf vals_of, const char *who)
 {
-    if (!fe || !d_pcm || vals <= 0) return VBM_EINVAL;
-    const vbm_setup *s = fe->hs;
-    const int bs1 = s->blocksizes[1];
-    for (int i = 0; i < fe->S; i++) {
-        if (fe->ended[i]) { g_vbm_err = "vbm_frontend_write after vbm_frontend_finish"; return VBM_EINVAL; }
-        if (!fe->mirrors_stale && fe->pcm_current[i] + vals > fe->f.cap - 3 * bs1 - fe->f.base_max) {   // OV_EINVAL of lib/block.c:540-541
+    const long long room = vbm_frontend_capacity(fe);
+    std::vector<char> seen(ids ? fe->S : 0, 0);
+    int max_vals = 0;
+    for (int k = 0; k < n; k++) {
+        const int i = ids ? ids[k] : k;
+        if (ids) {
+            if (i < 0 || i >= fe->S || seen[i]) return VBM_EINVAL;   // a stream once per call
+            seen[i] = 1;
+        }
+        const int v = vals_of(k);
+        if (v <= 0) return VBM_EINVAL;
+        if (fe->ended[i]) { g_vbm_err = std::string(who) + " after vbm_frontend_finish"; return VBM_EINVAL; }
+        // OV_EINVAL of lib/block.c:540-541.  (Once rounds built on the device have left the mirrors behind, the
+        // kernels' own guard refuses instead: fe_full in frontend_kernels.hip, counted in f.overflow.)
+        if (!fe->mirrors_stale && fe->pcm_current[i] + (long long)v > room) {
             g_vbm_err = "PCM buffer full: drain blocks with vbm_frontend_encode_round before writing more";
             return VBM_EINVAL;
         }
+        if (v > max_vals) max_vals = v;
     }
-    hipStream_t st = fe->q;
-    {
-        int rc = fe_enter(fe, stream);
-        if (rc) return rc;
-    }
-    vbm_debug_stamp(st, 0);
-    vbm_debug_delay_point(VBM_DP_FE_WRITE, st);
-    if (vbm_fe_launch_append(&fe->f, d_pcm, vals, s->pre_amplitude, st)) return VBM_EHIP;
-    {   // the caller's buffer is free again once the append has run
-        int rc = fe_leave(fe, stream);
-        if (rc) return rc;
-    }
+    return max_vals;
+}
+
+// The host's record of a write that has been enqueued.  Returns whether a stream crossed the start-of-stream
+// threshold with it: the caller then launches the pre-extrapolation (vbm_fe_launch_extrapolate, mode 0).
+template <typename ValsOf>
+static bool fe_note_written(vbm_frontend *fe, const int *ids, int n, ValsOf vals_of, int max_vals)
+{
+    const int bs1 = fe->hs->blocksizes[1];
     bool cross = false;
-    for (int i = 0; i < fe->S; i++) {
-        fe->pcm_current[i] += vals;
-        fe->written[i] += vals;
+    for (int k = 0; k < n; k++) {
+        const int i = ids ? ids[k] : k, v = vals_of(k);
+        fe->pcm_current[i] += v;
+        fe->written[i] += v;
         // vorbis_analysis_wrote: first time more than one long block follows centerW (lib/block.c:547-550); before a
         // stream starts nothing has left its buffer, so the samples written so far decide
         if (!fe->started[i] && fe->written[i] > bs1) { fe->started[i] = 1; cross = true; }
     }
-    if (cross && vbm_fe_launch_extrapolate(&fe->f, nullptr, 0, 0, bs1, st)) return VBM_EHIP;
     fe->dirty = true;
-    fe->pending_steps += vals / 64 + 1;
+    fe->pending_steps += max_vals / 64 + 1;
     if (cross) fe->pending_steps += (bs1 / 2 + bs1) / 64;   // the first search starts at step 0
+    return cross;
+}
+
+// vorbis_analysis_buffer + vorbis_analysis_wrote for every stream: d_pcm [S][ch][vals].  Nothing waits for the device:
+// the caller's stream is tied in by events.
+extern "C" int vbm_frontend_write(vbm_frontend *fe, const float *d_pcm, int vals, void *stream)
+{
+    if (!fe || !d_pcm || vals <= 0) return VBM_EINVAL;
+    const auto vals_of = [vals](int) { return vals; };
+    int rc = fe_check_write(fe, nullptr, fe->S, vals_of, "vbm_frontend_write");
+    if (rc < 0) return rc;
+    const int bs1 = fe->hs->blocksizes[1];
+    hipStream_t st = fe->q;
+    if ((rc = fe_enter(fe, stream))) return rc;
+    vbm_debug_stamp(st, 0);
+    vbm_debug_delay_point(VBM_DP_FE_WRITE, st);
+    if (vbm_fe_launch_append(&fe->f, d_pcm, vals, fe->hs->pre_amplitude, st)) return VBM_EHIP;
+    if ((rc = fe_leave(fe, stream))) return rc;   // the caller's buffer is free again once the append has run
+    if (fe_note_written(fe, nullptr, fe->S, vals_of, vals) && vbm_fe_launch_extrapolate(&fe->f, nullptr, 0, 0, bs1, st))
+        return VBM_EHIP;
     return VBM_OK;
 }
 
@@ -325,66 +357,35 @@ extern "C" int vbm_frontend_write_streams_strided(vbm_frontend *fe, const int *s
 {
     if (!fe || n < 0 || (n && (!stream_ids || !d_pcm)) || vals <= 0 || ch_stride < vals || stream_stride < 0) return VBM_EINVAL;
     if (n == 0) return VBM_OK;
-    const vbm_setup *s = fe->hs;
-    const int bs1 = s->blocksizes[1];
-    std::vector<char> seen(fe->S, 0);
-    for (int k = 0; k < n; k++) {
-        const int i = stream_ids[k];
-        if (i < 0 || i >= fe->S || seen[i]) return VBM_EINVAL;   // a stream once per call
-        seen[i] = 1;
-        if (fe->ended[i]) { g_vbm_err = "vbm_frontend_write_streams after vbm_frontend_finish"; return VBM_EINVAL; }
-        if (!fe->mirrors_stale && fe->pcm_current[i] + vals > fe->f.cap - 3 * bs1 - fe->f.base_max) {
-            g_vbm_err = "PCM buffer full: drain blocks with vbm_frontend_encode_round before writing more";
-            return VBM_EINVAL;
-        }
-    }
+    const auto vals_of = [vals](int) { return vals; };
+    int rc = fe_check_write(fe, stream_ids, n, vals_of, "vbm_frontend_write_streams");
+    if (rc < 0) return rc;
+    const int bs1 = fe->hs->blocksizes[1];
     hipStream_t st = fe->q;
-    int rc = fe_enter(fe, stream);
-    if (rc) return rc;
-    rc = upload_ids(fe, stream_ids, n, st);
-    if (rc) return rc;
-    if (vbm_fe_launch_append_ids(&fe->f, fe->d_ids, n, d_pcm, vals, s->pre_amplitude, stream_stride, ch_stride, by_slot, st)) return VBM_EHIP;
-    bool cross = false;
-    for (int k = 0; k < n; k++) {
-        const int i = stream_ids[k];
-        fe->pcm_current[i] += vals;
-        fe->written[i] += vals;
-        if (!fe->started[i] && fe->written[i] > bs1) { fe->started[i] = 1; cross = true; }
-    }
-    if (cross && vbm_fe_launch_extrapolate(&fe->f, nullptr, 0, 0, bs1, st)) return VBM_EHIP;
+    if ((rc = fe_enter(fe, stream))) return rc;
+    if ((rc = upload_ids(fe, stream_ids, n, st))) return rc;
+    if (vbm_fe_launch_append_ids(&fe->f, fe->d_ids, n, d_pcm, vals, fe->hs->pre_amplitude, stream_stride, ch_stride, by_slot, st))
+        return VBM_EHIP;
+    if (fe_note_written(fe, stream_ids, n, vals_of, vals) && vbm_fe_launch_extrapolate(&fe->f, nullptr, 0, 0, bs1, st))
+        return VBM_EHIP;
     (void)hipStreamSynchronize(st);   // d_ids / h_ids are free again
-    fe->dirty = true;
-    fe->pending_steps += vals / 64 + 1;
-    if (cross) fe->pending_steps += (bs1 / 2 + bs1) / 64;
     return VBM_OK;
 }
 
 // vorbis_analysis_buffer + vorbis_analysis_wrote(vals[k]) for each listed stream, every stream with a size of its own:
 // channel c of stream_ids[k] is the vals[k] floats at pcm + src_offsets[k] + c * ch_strides[k] (pcm as for
 // vbm_frontend_write_streams_strided; the three arrays are host arrays).  One upload of the job records, one append
-// launch over all listed streams.  Every check runs before anything is enqueued: a refused call changes no stream.
+// launch over all listed streams.
 extern "C" int vbm_frontend_write_ragged(vbm_frontend *fe, const int *stream_ids, int n, const float *pcm,
                                          const long long *src_offsets, const int *vals, const long long *ch_strides,
                                          void *stream)
 {
     if (!fe || n < 0 || (n && (!stream_ids || !pcm || !src_offsets || !vals || !ch_strides))) return VBM_EINVAL;
     if (n == 0) return VBM_OK;
-    const vbm_setup *s = fe->hs;
-    const int bs1 = s->blocksizes[1];
-    std::vector<char> seen(fe->S, 0);
-    int max_vals = 0;
-    for (int k = 0; k < n; k++) {
-        const int i = stream_ids[k];
-        if (i < 0 || i >= fe->S || seen[i]) return VBM_EINVAL;   // a stream once per call
-        seen[i] = 1;
-        if (vals[k] <= 0 || ch_strides[k] < vals[k] || src_offsets[k] < 0) return VBM_EINVAL;
-        if (fe->ended[i]) { g_vbm_err = "vbm_frontend_write_ragged after vbm_frontend_finish"; return VBM_EINVAL; }
-        if (!fe->mirrors_stale && fe->pcm_current[i] + (long)vals[k] > fe->f.cap - 3 * bs1 - fe->f.base_max) {
-            g_vbm_err = "PCM buffer full: drain blocks with vbm_frontend_encode_round before writing more";
-            return VBM_EINVAL;
-        }
-        if (vals[k] > max_vals) max_vals = vals[k];
-    }
+    const auto vals_of = [=](int k) { return ch_strides[k] < vals[k] || src_offsets[k] < 0 ? 0 : vals[k]; };
+    const int max_vals = fe_check_write(fe, stream_ids, n, vals_of, "vbm_frontend_write_ragged");
+    if (max_vals < 0) return max_vals;
+    const int bs1 = fe->hs->blocksizes[1];
     hipStream_t st = fe->q;
     int rc;
     if (!fe->h_jobs) {                // the staging area: made by the first ragged write, so that front ends that never
@@ -394,8 +395,7 @@ extern "C" int vbm_frontend_write_ragged(vbm_frontend *fe, const int *stream_ids
             return vbm_set_hip_error(e, "hipHostMalloc(ragged jobs)");
         if ((e = hipDeviceSynchronize()) != hipSuccess) return vbm_set_hip_error(e, "hipDeviceSynchronize");   // the zero fill
     }
-    rc = fe_enter(fe, stream);
-    if (rc) return rc;
+    if ((rc = fe_enter(fe, stream))) return rc;
     (void)hipStreamSynchronize(st);   // h_jobs may still be on its way from the call before
     for (int k = 0; k < n; k++) {
         vbm_fe_job &j = fe->h_jobs[k];
@@ -403,21 +403,10 @@ extern "C" int vbm_frontend_write_ragged(vbm_frontend *fe, const int *stream_ids
     }
     hipError_t err = hipMemcpyAsync(fe->d_jobs, fe->h_jobs, n * sizeof(vbm_fe_job), hipMemcpyHostToDevice, st);
     if (err != hipSuccess) return vbm_set_hip_error(err, "hipMemcpyAsync(ragged jobs)");
-    if (vbm_fe_launch_append_ragged(&fe->f, fe->d_jobs, n, max_vals, pcm, s->pre_amplitude, st)) return VBM_EHIP;
-    bool cross = false;
-    for (int k = 0; k < n; k++) {
-        const int i = stream_ids[k];
-        fe->pcm_current[i] += vals[k];
-        fe->written[i] += vals[k];
-        if (!fe->started[i] && fe->written[i] > bs1) { fe->started[i] = 1; cross = true; }   // lib/block.c:547-550
-    }
-    if (cross && vbm_fe_launch_extrapolate(&fe->f, nullptr, 0, 0, bs1, st)) return VBM_EHIP;
-    rc = fe_leave(fe, stream);        // the caller's stream sees the samples taken; nothing here waits for the device
-    if (rc) return rc;
-    fe->dirty = true;
-    fe->pending_steps += max_vals / 64 + 1;
-    if (cross) fe->pending_steps += (bs1 / 2 + bs1) / 64;
-    return VBM_OK;
+    if (vbm_fe_launch_append_ragged(&fe->f, fe->d_jobs, n, max_vals, pcm, fe->hs->pre_amplitude, st)) return VBM_EHIP;
+    if (fe_note_written(fe, stream_ids, n, vals_of, max_vals) && vbm_fe_launch_extrapolate(&fe->f, nullptr, 0, 0, bs1, st))
+        return VBM_EHIP;
+    return fe_leave(fe, stream);      // the caller's stream sees the samples taken; nothing here waits for the device
 }
 
 // a new stream starts in each of the listed slots (vorbis_analysis_init state for front end and encoder)
@@ -456,14 +445,9 @@ extern "C" int vbm_frontend_finish(vbm_frontend *fe, const int *stream_ids, int 
         if (s < 0 || s >= fe->S || fe->ended[s]) return VBM_EINVAL;
     }
     hipStream_t st = fe->q;
-    {
-        int rc = fe_enter(fe, stream);
-        if (rc) return rc;
-    }
-    (void)hipStreamSynchronize(st);   // h_ids is reused by the rounds
-    memcpy(fe->h_ids, stream_ids, n * sizeof(int));
-    hipError_t err = hipMemcpyAsync(fe->d_ids, fe->h_ids, n * sizeof(int), hipMemcpyHostToDevice, st);
-    if (err != hipSuccess) return vbm_set_hip_error(err, "hipMemcpyAsync(finish ids)");
+    int rc = fe_enter(fe, stream);
+    if (rc) return rc;
+    if ((rc = upload_ids(fe, stream_ids, n, st))) return rc;
     if (vbm_fe_launch_extrapolate(&fe->f, fe->d_ids, n, 1, bs1, st)) return VBM_EHIP;
     (void)hipStreamSynchronize(st);
     for (int i = 0; i < n; i++) {
@@ -498,6 +482,28 @@ static int refresh_mirrors(vbm_frontend *fe)
     return VBM_OK;
 }
 
+// evaluate the envelope over everything written since the last round (_ve_envelope_search, first part)
+static int fe_evaluate_envelope(vbm_frontend *fe, hipStream_t st)
+{
+    if (!fe->dirty) return VBM_OK;
+    if (vbm_fe_launch_ve_range(&fe->f, st)) return VBM_EHIP;
+    const vbm_setup *ds = vbm_setup_device(fe->H);
+    vbm_ve_gather g;
+    g.pcm = fe->f.pcm;
+    g.first = fe->f.ve_first; g.last = fe->f.ve_last; g.parity = fe->f.parity; g.base = fe->f.base;
+    g.ch = fe->ch; g.steps = VBM_FE_CHUNK; g.cap = fe->f.cap; g.plane = fe->f.plane;
+    for (int t0 = 0; t0 < fe->pending_steps; t0 += VBM_FE_CHUNK) {
+        g.t0 = t0;
+        if (vbm_launch_ve_mdct(&g, fe->f.ve_spec, vbm_setup_device_ptrs(fe->H)->ve.mdct_trig,
+                               vbm_setup_device_ptrs(fe->H)->ve.mdct_win, (long)fe->S * fe->ch * VBM_FE_CHUNK, st))
+            return VBM_EHIP;
+        if (vbm_fe_launch_ve_filter(&fe->f, ds, t0, st)) return VBM_EHIP;
+    }
+    fe->dirty = false;
+    fe->pending_steps = 0;
+    return VBM_OK;
+}
+
 static int round_impl(vbm_frontend *fe, uint8_t *d_packets, int *d_packet_bytes, vbm_packet_info *info, int *nblocks,
                       void *stream, bool defer)
 {
@@ -526,23 +532,7 @@ static int round_impl(vbm_frontend *fe, uint8_t *d_packets, int *d_packet_bytes,
     }
     if (!maybe) return VBM_OK;
 
-    // evaluate the envelope over everything written since the last round (_ve_envelope_search, first part)
-    if (fe->dirty) {
-        if (vbm_fe_launch_ve_range(&fe->f, st)) return VBM_EHIP;
-        vbm_ve_gather g;
-        g.pcm = fe->f.pcm;
-        g.first = fe->f.ve_first; g.last = fe->f.ve_last; g.parity = fe->f.parity; g.base = fe->f.base;
-        g.ch = ch; g.steps = VBM_FE_CHUNK; g.cap = fe->f.cap; g.plane = fe->f.plane;
-        for (int t0 = 0; t0 < fe->pending_steps; t0 += VBM_FE_CHUNK) {
-            g.t0 = t0;
-            if (vbm_launch_ve_mdct(&g, fe->f.ve_spec, vbm_setup_device_ptrs(fe->H)->ve.mdct_trig,
-                                   vbm_setup_device_ptrs(fe->H)->ve.mdct_win, (long)S * ch * VBM_FE_CHUNK, st))
-                return VBM_EHIP;
-            if (vbm_fe_launch_ve_filter(&fe->f, ds, t0, st)) return VBM_EHIP;
-        }
-        fe->dirty = false;
-        fe->pending_steps = 0;
-    }
+    if (fe_evaluate_envelope(fe, st)) return VBM_EHIP;
 
     if (vbm_fe_launch_decide(&fe->f, ds, fe->d_dec, fe->hold_active ? fe->d_hold : nullptr, st)) return VBM_EHIP;
     if ((err = hipMemcpyAsync(fe->h_dec, fe->d_dec, S * sizeof(vbm_fe_decision), hipMemcpyDeviceToHost, st)) != hipSuccess)
@@ -785,23 +775,7 @@ extern "C" int vbm_frontend_encode_rounds_device(vbm_frontend *fe, int nrounds, 
         // them (the first round's gather writing blocks that the fill then wipes): wait here, once
         if ((err = hipDeviceSynchronize()) != hipSuccess) return vbm_set_hip_error(err, "hipDeviceSynchronize");
     }
-    // evaluate the envelope over everything written since the last round (_ve_envelope_search, first part)
-    if (fe->dirty) {
-        if (vbm_fe_launch_ve_range(&fe->f, q)) return VBM_EHIP;
-        vbm_ve_gather g;
-        g.pcm = fe->f.pcm;
-        g.first = fe->f.ve_first; g.last = fe->f.ve_last; g.parity = fe->f.parity; g.base = fe->f.base;
-        g.ch = ch; g.steps = VBM_FE_CHUNK; g.cap = fe->f.cap; g.plane = fe->f.plane;
-        for (int t0 = 0; t0 < fe->pending_steps; t0 += VBM_FE_CHUNK) {
-            g.t0 = t0;
-            if (vbm_launch_ve_mdct(&g, fe->f.ve_spec, vbm_setup_device_ptrs(fe->H)->ve.mdct_trig,
-                                   vbm_setup_device_ptrs(fe->H)->ve.mdct_win, (long)S * ch * VBM_FE_CHUNK, q))
-                return VBM_EHIP;
-            if (vbm_fe_launch_ve_filter(&fe->f, ds, t0, q)) return VBM_EHIP;
-        }
-        fe->dirty = false;
-        fe->pending_steps = 0;
-    }
+    if (fe_evaluate_envelope(fe, q)) return VBM_EHIP;
     for (int r = 0; r < nrounds; r++) {
         int w, ws_lanes;
         int *d_sid, *counts_ws;

@@ -59,7 +59,7 @@ struct vbm_fe_decision {
     long long granulepos, sequence;
 };
 
-// One round built on the device (k_fe_classify / k_fe_plan / k_fe_commit): block type m owns the lane region
+// One round built on the device (k_fe_classify / k_fe_plan / k_fe_round_commit): block type m owns the lane region
 // [lane0[m], lane0[m] + cap[m]) of the round's lists and of the encoder workspace behind them.
 struct vbm_fe_round {
     int lane0[4], cap[4];

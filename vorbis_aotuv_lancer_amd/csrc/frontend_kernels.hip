@@ -1,9 +1,12 @@
 // Stream front end kernels for gfx950 (frontend.h): PCM intake, LPC extrapolation of stream start
 // and end, the envelope detector and the block carve-out decision, for S streams per launch.
 //
-//   k_fe_append / k_fe_commit       vorbis_analysis_buffer + vorbis_analysis_wrote(vals > 0)
-//                                   (reference lib/block.c:405-436, :511-553): pre_amplitude, append
-//   k_fe_append_ids / _ragged       the same for listed streams: one size for all / a size per stream
+//   fe_append_one / fe_commit_one   vorbis_analysis_buffer + vorbis_analysis_wrote(vals > 0)
+//                                   (reference lib/block.c:405-436, :511-553): pre_amplitude, append.  One body,
+//                                   three ways to name the source:
+//   k_fe_append / k_fe_commit                    every stream, one size
+//   k_fe_append_ids / k_fe_commit_ids            listed streams, one size
+//   k_fe_append_ragged / k_fe_commit_ragged      listed streams, a size and a source offset per stream
 //   k_fe_extrapolate                _preextrapolate_helper (lib/block.c:438-484) and the end-of-stream
 //                                   padding of vorbis_analysis_wrote(0) (:520-552), with
 //                                   vorbis_lpc_from_data / vorbis_lpc_predict (lib/lpc.c:60-159).
@@ -17,6 +20,8 @@
 //   k_fe_decide                     the cursor walk of _ve_envelope_search (:631-678), _ve_envelope_mark
 //                                   (:683-707), vorbis_analysis_blockout (lib/block.c:557-812) without
 //                                   its copies, _ve_envelope_shift (:709-728)
+//   k_fe_classify / k_fe_plan / k_fe_round_commit / k_fe_blank
+//                                   the same decision for rounds built on the device: look, assign lanes, commit
 //   k_fe_gather                     the block copy of vorbis_analysis_blockout (lib/block.c:653-698)
 //                                   into block-major batches for vbm_analysis_batch
 //   k_fe_shift                      the memmove of lib/block.c:757-759 as a copy into the other buffer
@@ -34,108 +39,93 @@ __device__ __forceinline__ float *chan_buf(const vbm_fe_state &f, int s, int c)
 }
 
 // ---------------------------------------------------------------------------------------------
-__global__ void k_fe_append(vbm_fe_state f, const float *__restrict__ src, int vals, float pre_amplitude)
+// PCM intake: one body, three ways to name the source.  A write that would pass the end of a stream's buffer is
+// refused whole: no channel of it is copied (fe_append_one) and the stream's pcm_current stays (fe_commit_one, which
+// counts it in f.overflow) — never write past the buffer, never lose a part of a write silently.
+__device__ __forceinline__ bool fe_full(const vbm_fe_state &f, int s, int vals)
 {
-    const int c = blockIdx.x;                       // channel index over S*ch
-    const int s = c / f.ch;
-    if (f.base[s] + f.pcm_current[s] + vals > f.cap) return;   // full (k_fe_commit counts it): never write past the buffer
-    float *dst = f.pcm + (long)f.parity[s] * f.plane + (long)c * f.cap + f.base[s] + f.pcm_current[s];
-    const float *in = src + (long)c * vals;
+    return f.base[s] + f.pcm_current[s] + vals > f.cap;
+}
+
+// channel c of stream s takes the `vals` floats at `in`, times pre_amplitude (lib/block.c:514-518).  The grid's y
+// slices the samples; 16 bytes per thread and step where source, destination and vals allow it (a whole block takes
+// one path: the test is per (stream, channel)).
+__device__ __forceinline__ void fe_append_one(const vbm_fe_state &f, int s, int c, const float *in, int vals,
+                                              float pre_amplitude)
+{
+    if (fe_full(f, s, vals)) return;
+    // (s * ch + c in int — it is a grid dimension — so that k_fe_append folds it back into its block index)
+    float *dst = f.pcm + (long)f.parity[s] * f.plane + (long)(s * f.ch + c) * f.cap + f.base[s] + f.pcm_current[s];
     const int t0 = blockIdx.y * blockDim.x + threadIdx.x, step = gridDim.y * blockDim.x;
-    if ((((uintptr_t)dst | (uintptr_t)in) & 15) == 0 && (vals & 3) == 0) {      // 16 bytes per thread and step
+    if ((((uintptr_t)dst | (uintptr_t)in) & 15) == 0 && (vals & 3) == 0) {
         const float4 *in4 = reinterpret_cast<const float4 *>(in);
         float4 *dst4 = reinterpret_cast<float4 *>(dst);
         for (int i = t0; i < vals / 4; i += step) {
             float4 v = in4[i];
-            v.x *= pre_amplitude; v.y *= pre_amplitude; v.z *= pre_amplitude; v.w *= pre_amplitude;   // lib/block.c:514-518
+            v.x *= pre_amplitude; v.y *= pre_amplitude; v.z *= pre_amplitude; v.w *= pre_amplitude;
             dst4[i] = v;
         }
         return;
     }
     for (int i = t0; i < vals; i += step)
-        dst[i] = in[i] * pre_amplitude;             // lib/block.c:514-518
+        dst[i] = in[i] * pre_amplitude;
+}
+
+// vorbis_analysis_wrote(vals > 0) for stream s, after every channel has been appended
+__device__ __forceinline__ void fe_commit_one(const vbm_fe_state &f, int s, int vals)
+{
+    if (fe_full(f, s, vals)) { atomicAdd(f.overflow, 1); return; }
+    f.pcm_current[s] += vals;
+}
+
+// every stream, `vals` each: src [S][ch][vals]
+__global__ void k_fe_append(vbm_fe_state f, const float *__restrict__ src, int vals, float pre_amplitude)
+{
+    const int sc = blockIdx.x;                      // stream s, channel c
+    const int s = sc / f.ch, c = sc - s * f.ch;
+    fe_append_one(f, s, c, src + (long)sc * vals, vals, pre_amplitude);
 }
 
 __global__ void k_fe_commit(vbm_fe_state f, int vals)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= f.S) return;
-    if (f.base[s] + f.pcm_current[s] + vals > f.cap) { atomicAdd(f.overflow, 1); return; }
-    f.pcm_current[s] += vals;
+    if (s < f.S) fe_commit_one(f, s, vals);
 }
 
-// the same for a subset of the streams: channel c of stream ids[k] comes from src + (by_slot ? ids[k] : k) * stream_stride
+// the listed streams, `vals` each: channel c of stream ids[k] comes from src + (by_slot ? ids[k] : k) * stream_stride
 // + c * ch_stride (plain [k][ch][vals]: strides ch * vals and vals).  src may be pinned host memory (the drop-in shim's
-// staging arena, read over the bus by this kernel: 16 bytes per thread and step when everything is aligned)
+// staging arena, read over the bus by this kernel)
 __global__ void k_fe_append_ids(vbm_fe_state f, const int *__restrict__ ids, const float *__restrict__ src, int vals,
                                 float pre_amplitude, long stream_stride, long ch_stride, int by_slot)
 {
     const int kc = blockIdx.x;                      // listed stream k, channel c
     const int k = kc / f.ch, c = kc % f.ch;
     const int s = ids[k];
-    if (f.base[s] + f.pcm_current[s] + vals > f.cap) return;
-    float *dst = f.pcm + (long)f.parity[s] * f.plane + ((long)s * f.ch + c) * f.cap + f.base[s] + f.pcm_current[s];
-    const float *in = src + (long)(by_slot ? s : k) * stream_stride + (long)c * ch_stride;
-    const int t0 = blockIdx.y * blockDim.x + threadIdx.x, step = gridDim.y * blockDim.x;
-    if ((((uintptr_t)dst | (uintptr_t)in) & 15) == 0 && (vals & 3) == 0) {
-        const float4 *in4 = reinterpret_cast<const float4 *>(in);
-        float4 *dst4 = reinterpret_cast<float4 *>(dst);
-        for (int i = t0; i < vals / 4; i += step) {
-            float4 v = in4[i];
-            v.x *= pre_amplitude; v.y *= pre_amplitude; v.z *= pre_amplitude; v.w *= pre_amplitude;   // lib/block.c:514-518
-            dst4[i] = v;
-        }
-        return;
-    }
-    for (int i = t0; i < vals; i += step)
-        dst[i] = in[i] * pre_amplitude;
+    fe_append_one(f, s, c, src + (long)(by_slot ? s : k) * stream_stride + (long)c * ch_stride, vals, pre_amplitude);
 }
 
 __global__ void k_fe_commit_ids(vbm_fe_state f, const int *__restrict__ ids, int n, int vals)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const int s = ids[k];
-    if (f.base[s] + f.pcm_current[s] + vals > f.cap) { atomicAdd(f.overflow, 1); return; }
-    f.pcm_current[s] += vals;
+    if (k < n) fe_commit_one(f, ids[k], vals);
 }
 
-// the same with a size of its own for every listed stream (vbm_frontend_write_ragged): jobs[k] names the stream, its
-// `vals` and where its channels lie in src.  The grid's y covers the largest vals of the call: a block whose slice
-// starts past its own stream's vals has nothing to do.  16 bytes per thread and step where this stream's source,
-// destination and vals allow it (a whole block takes one path: the test is per (stream, channel)).
+// the listed streams, each with a size of its own (vbm_frontend_write_ragged): jobs[k] names the stream, its `vals`
+// and where its channels lie in src.  The grid's y covers the largest vals of the call: a block whose slice starts
+// past its own stream's vals has nothing to do.
 __global__ void k_fe_append_ragged(vbm_fe_state f, const vbm_fe_job *__restrict__ jobs, const float *__restrict__ src,
                                    float pre_amplitude)
 {
     const int kc = blockIdx.x;                      // listed stream k, channel c
     const int k = kc / f.ch, c = kc % f.ch;
     const vbm_fe_job j = jobs[k];
-    const int s = j.stream, vals = j.vals;
-    if (f.base[s] + f.pcm_current[s] + vals > f.cap) return;   // full (k_fe_commit_ragged counts it): never write past the buffer
-    float *dst = f.pcm + (long)f.parity[s] * f.plane + ((long)s * f.ch + c) * f.cap + f.base[s] + f.pcm_current[s];
-    const float *in = src + j.src + (long long)c * j.ch_stride;
-    const int t0 = blockIdx.y * blockDim.x + threadIdx.x, step = gridDim.y * blockDim.x;
-    if ((((uintptr_t)dst | (uintptr_t)in) & 15) == 0 && (vals & 3) == 0) {
-        const float4 *in4 = reinterpret_cast<const float4 *>(in);
-        float4 *dst4 = reinterpret_cast<float4 *>(dst);
-        for (int i = t0; i < vals / 4; i += step) {
-            float4 v = in4[i];
-            v.x *= pre_amplitude; v.y *= pre_amplitude; v.z *= pre_amplitude; v.w *= pre_amplitude;   // lib/block.c:514-518
-            dst4[i] = v;
-        }
-        return;
-    }
-    for (int i = t0; i < vals; i += step)
-        dst[i] = in[i] * pre_amplitude;
+    fe_append_one(f, j.stream, c, src + j.src + (long long)c * j.ch_stride, j.vals, pre_amplitude);
 }
 
 __global__ void k_fe_commit_ragged(vbm_fe_state f, const vbm_fe_job *__restrict__ jobs, int n)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const int s = jobs[k].stream, vals = jobs[k].vals;
-    if (f.base[s] + f.pcm_current[s] + vals > f.cap) { atomicAdd(f.overflow, 1); return; }
-    f.pcm_current[s] += vals;
+    if (k < n) fe_commit_one(f, jobs[k].stream, jobs[k].vals);
 }
 
 // vorbis_analysis_init state for the listed streams (a new stream starts in a used slot): lib/block.c:306-344,
@@ -549,10 +539,19 @@ __global__ __launch_bounds__(64) void k_fe_ve_filter(vbm_fe_state f, const vbm_s
 }
 
 // ---------------------------------------------------------------------------------------------
+// "no block": what a round records for a stream that delivers nothing and stays as it is
+__device__ __forceinline__ vbm_fe_decision fe_no_decision()
+{
+    vbm_fe_decision d;
+    d.ready = 0; d.lW = d.W = d.nW = 0; d.block_mode = 0; d.eos = 0; d.beginW = 0; d.movement = 0;
+    d.granulepos = 0; d.sequence = 0;
+    return d;
+}
+
 // vorbis_analysis_blockout for stream s (lib/block.c:557-812, _ve_envelope_search's cursor walk lib/envelope.c:627-680,
 // _ve_envelope_mark :683-707, _ve_envelope_shift :709-728) without its copies.  COMMIT = false evaluates the same
 // decision without touching the stream (what WOULD come out): the device-built rounds first look, then assign
-// lanes, then commit (k_fe_classify / k_fe_plan / k_fe_commit).
+// lanes, then commit (k_fe_classify / k_fe_plan / k_fe_round_commit).
 template <bool COMMIT>
 __device__ __forceinline__ void fe_decide_one(const vbm_fe_state &f, const vbm_setup *__restrict__ setup, const int s,
                                               vbm_fe_decision &d)
@@ -560,8 +559,7 @@ __device__ __forceinline__ void fe_decide_one(const vbm_fe_state &f, const vbm_s
     const int S = f.S;
     const int searchstep = 64;
     const int bs0 = setup->blocksizes[0], bs1 = setup->blocksizes[1];
-    d.ready = 0; d.lW = d.W = d.nW = 0; d.block_mode = 0; d.eos = 0; d.beginW = 0; d.movement = 0;
-    d.granulepos = 0; d.sequence = 0;
+    d = fe_no_decision();
 
     int W = f.W[s], lW = f.lW[s], nW = f.nW[s];
     int centerW = f.centerW[s], pcm_current = f.pcm_current[s], eofflag = f.eofflag[s];
@@ -696,12 +694,8 @@ __global__ void k_fe_decide(vbm_fe_state f, const vbm_setup *__restrict__ setup,
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= f.S) return;
     vbm_fe_decision d;
-    if (hold && hold[s]) {
-        d.ready = 0; d.lW = d.W = d.nW = 0; d.block_mode = 0; d.eos = 0; d.beginW = 0; d.movement = 0;
-        d.granulepos = 0; d.sequence = 0;
-    } else {
-        fe_decide_one<true>(f, setup, s, d);
-    }
+    if (hold && hold[s]) d = fe_no_decision();
+    else fe_decide_one<true>(f, setup, s, d);
     out[s] = d;
 }
 
@@ -772,16 +766,14 @@ __global__ __launch_bounds__(1024) void k_fe_plan(vbm_fe_round r, const signed c
     }
 }
 
-// k_fe_commit: the streams that got a lane deliver their block (state changes as in k_fe_decide) and describe it in
+// k_fe_round_commit: the streams that got a lane deliver their block (state changes as in k_fe_decide) and describe it in
 // the lane's entries of the round's lists; every other stream is left alone.
-__global__ void k_fe_commit(vbm_fe_state f, const vbm_setup *__restrict__ setup, vbm_fe_round r,
-                            vbm_fe_decision *__restrict__ dec)
+__global__ void k_fe_round_commit(vbm_fe_state f, const vbm_setup *__restrict__ setup, vbm_fe_round r,
+                                  vbm_fe_decision *__restrict__ dec)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= f.S) return;
-    vbm_fe_decision d;
-    d.ready = 0; d.lW = d.W = d.nW = 0; d.block_mode = 0; d.eos = 0; d.beginW = 0; d.movement = 0;
-    d.granulepos = 0; d.sequence = 0;
+    vbm_fe_decision d = fe_no_decision();
     const int slot = r.slot[s];
     if (slot >= 0) {
         fe_decide_one<true>(f, setup, s, d);
@@ -951,7 +943,7 @@ extern "C" int vbm_fe_launch_round_plan(const vbm_fe_state *f, const vbm_setup *
     const dim3 g((unsigned)((f->S + 63) / 64));
     hipLaunchKernelGGL(k_fe_classify, g, dim3(64), 0, st, *f, d_setup, d_type);
     hipLaunchKernelGGL(k_fe_plan, dim3(1), dim3(1024), 0, st, *r, d_type, f->S);
-    hipLaunchKernelGGL(k_fe_commit, g, dim3(64), 0, st, *f, d_setup, *r, d_dec);
+    hipLaunchKernelGGL(k_fe_round_commit, g, dim3(64), 0, st, *f, d_setup, *r, d_dec);
     hipLaunchKernelGGL(k_fe_blank, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, *r, d_packet_bytes, lanes);
     return CHECK_LAUNCH();
 }
