@@ -199,13 +199,9 @@ BLOB_CASES = [
 ]
 
 
-@pytest.mark.parametrize("bitrate,makers,min_poste", BLOB_CASES, ids=["b128000_hits", "b256000_faint", "b128000_minmax_overdriven"])
-def test_managed_blobs_block_by_block(oracle, cuda, bitrate, makers, min_poste):
-    """2ch 44100 managed: all fifteen packetblobs, the bitrate manager's choice and the packets of every block.
-    Decaying hits at b128000: the blobs' coupling passes hand the npeak rows on to one another, and here rows of -1 from
-    the post-echo arm enter that chain.  Faint noise at b256000: blocks with a floor at the middle rate and none at a
-    neighbouring one, so interpolated fits come out empty.  Overdriven noise under a maximum rate: the manager runs out
-    of smaller blobs and cuts the packet."""
+def managed_blobs(oracle, cuda, bitrate, makers):
+    """2ch 44100 managed, the streams of `makers` in one encoder: all fifteen packetblobs, the bitrate manager's choice
+    and the delivered packet of every block -> (blocks compared, blocks with poste > 0, packets cut)"""
     import vorbis_aotuv_lancer_amd as v
     ch, rate = 2, 44100
     streams = [blocks_of(oracle, (name, ch, rate, bitrate), make, ch, rate, bitrate=bitrate) for name, make in makers]
@@ -241,5 +237,16 @@ def test_managed_blobs_block_by_block(oracle, cuda, bitrate, makers, min_poste):
     enc.close()
     setup.close()
     print(f"2ch 44100 b{bitrate}: {nblocks} blocks compared with all blobs, {nposte} with poste > 0, {ncut} packets cut")
+    return nblocks, nposte, ncut
+
+
+@pytest.mark.parametrize("bitrate,makers,min_poste", BLOB_CASES, ids=["b128000_hits", "b256000_faint", "b128000_minmax_overdriven"])
+def test_managed_blobs_block_by_block(oracle, cuda, bitrate, makers, min_poste):
+    """2ch 44100 managed: all fifteen packetblobs, the bitrate manager's choice and the packets of every block.
+    Decaying hits at b128000: the blobs' coupling passes hand the npeak rows on to one another, and here rows of -1 from
+    the post-echo arm enter that chain.  Faint noise at b256000: blocks with a floor at the middle rate and none at a
+    neighbouring one, so interpolated fits come out empty.  Overdriven noise under a maximum rate: the manager runs out
+    of smaller blobs and cuts the packet."""
+    nblocks, nposte, ncut = managed_blobs(oracle, cuda, bitrate, makers)
     assert nposte >= min_poste
     assert (ncut > 0) == isinstance(bitrate, tuple)

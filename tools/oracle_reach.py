@@ -134,6 +134,20 @@ def suite_corpus():
         out.append(_e(f"ordering_burst_{k}", lambda k=k: burst_signal(2, 44100, 40 * 1024, seed=70 + k, period=5000 + 1000 * k,
                                                                      level=1.0 if k % 3 else 0.05), 2, 44100, 0.5))
 
+    # tests/test_images_gpu.py: the correlated-channel corpus, and the synth_signal streams it puts beside the images
+    from tests import image_signals as im
+    for e in im.IMAGES:
+        out.append(_e("images_" + e["name"], lambda e=e: e["make"](e["ch"], e["rate"]), e["ch"], e["rate"], e["q"], e["bitrate"]))
+    for ch, rate, q, bitrate in im.classes():
+        n = whole(im.seconds_of(ch, rate, q, bitrate), rate)
+        seeds = list(range(850, 850 + max(2, 6 - len(im.images_of(ch, rate, q, bitrate)))))
+        if (ch, rate, q) in [(2, 44100, 0.5), (2, 44100, -0.1), (2, 44100, 1.0), (2, 22050, 0.5), (6, 48000, 0.3)]:
+            seeds += [840, 841]
+        if ch == 2 and bitrate is not None:
+            seeds += [860]
+        tail = f"q{q:g}" if bitrate is None else "b" + "_".join(str(x) for x in (bitrate if isinstance(bitrate, tuple) else (bitrate,)))
+        synth(f"images_beside_{ch}ch_{rate}_{tail}", ch, rate, q, seeds, n, lambda s: 1.0, bitrate=bitrate)
+
     # tests/test_reference_input_gpu.py, widened to every shipped pack: the windowed sine in one write, then the end
     for path in sorted(glob.glob(os.path.join(ROOT, "vorbis_aotuv_lancer_amd", "data", "mode_*.vpk"))):
         m = re.match(r"mode_(\d+)ch_(\d+)_(q|b)(-?[\d.]+?)(?:_max(\d+))?(?:_min(\d+))?\.vpk", os.path.basename(path))
