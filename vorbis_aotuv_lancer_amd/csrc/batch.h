@@ -27,6 +27,23 @@ struct vbm_stream_state {           // per-encoder, S streams (reference lib/cod
     double *bm_avgfloat;                                 // [S]
 };
 
+// What the lane-per-bin couple kernel (quant_kernels.hip, k_couple_fast) takes from the setup, formed once on the host
+// (capi_encoder.cpp, configure()) from its view of the same tables: the kernel reads them as kernel arguments instead
+// of rebuilding them in each of its n/32 x columns/8 workgroups through chains of dependent loads (s->psy[], s->map[],
+// coupling_prepointamp[blob] -> stereo_threshholds[..]) and an integer division (the lowpass rounding).
+struct vbm_couple_blob {            // per packetblob (lib/psy.c:4893-4911)
+    int limit, sliding_lowpass;
+    float prepoint, postpoint, prepoint_x, postpoint_x;
+};
+struct vbm_couple_consts {
+    int n, tonefix_end, lowpassr;   // lowpassr: rounded up to the normal partition (lib/mapping0.c:778-781)
+    int normal_p, normal_start;
+    int mag, ang;                   // channels of coupling step 0
+    float prae;
+    double normal_thresh;
+    vbm_couple_blob blob[VBM_PACKETBLOBS];
+};
+
 struct vbm_batch {
     const vbm_setup *setup;         // device copy
     vbm_stream_state st;
@@ -75,6 +92,7 @@ struct vbm_batch {
     int couple_parallel;            // coupling steps use disjoint channels: partitions may run sliced
     int couple_parts, couple_m6parts;  // partitions below the lowpass / those in the M6 range
     int couple_fast;                // 0 general kernel; 1 lane-per-bin kernel, no coupling; 2 lane-per-bin, stereo one step
+    vbm_couple_consts cc;           // the lane-per-bin kernel's constants of this block type (set with couple_fast)
     int *vqlenT, *vqoffT;           // [stages][ch][max partvals][Ls]  bits / bit offset of every residue run
     uint64_t *vqcodeT;              // [stages][ch*n][64] per tile of `vq_slab_words` 8-byte words: code | len << 32
     size_t vq_slab_words;

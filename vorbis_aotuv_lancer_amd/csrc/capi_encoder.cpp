@@ -546,6 +546,28 @@ static void configure(vbm_encoder *e, vbm_batch &b, int block_mode, int nsb, con
             if (m.coupling_steps == 0) b.couple_fast = 1;
             else if (m.coupling_steps == 1 && e->ch == 2 && b.couple_parallel) b.couple_fast = 2;
         }
+        // the lane-per-bin kernel's constants (batch.h): the expressions of lib/psy.c:4893-4911, evaluated here once
+        // per batch instead of once per workgroup
+        {
+            vbm_couple_consts &c = b.cc;
+            c.n = p.n;
+            c.tonefix_end = p.tonefix_end;
+            c.lowpassr = lowpassr;
+            c.normal_p = p.normal_p; c.normal_start = p.normal_start; c.normal_thresh = p.normal_thresh;
+            c.mag = m.coupling_mag[0]; c.ang = m.coupling_ang[0];
+            c.prae = (m.coupling_steps == 1) ? (float)0.34 : (float)0.825;
+            for (int k = 0; k < VBM_PACKETBLOBS; k++) {
+                vbm_couple_blob &cb = c.blob[k];
+                cb.limit = s->coupling_pointlimit[p.blockflag][k];
+                cb.prepoint = (float)s->stereo_threshholds[s->coupling_prepointamp[k]];
+                cb.postpoint = (float)s->stereo_threshholds[s->coupling_postpointamp[k]];
+                cb.prepoint_x = (float)s->stereo_threshholds_X[s->coupling_prepointamp[k]];
+                cb.postpoint_x = (float)s->stereo_threshholds_X[s->coupling_postpointamp[k]];
+                if (cb.prepoint_x < cb.prepoint) cb.prepoint_x = cb.prepoint;
+                if (cb.postpoint_x < cb.prepoint) cb.postpoint_x = cb.prepoint;
+                cb.sliding_lowpass = s->sliding_lowpass[b.W][k];
+            }
+        }
         b.pack_submaps = m.submaps;
         for (int i = 0; i < m.submaps && i < 16; i++) {
             const vbm_residue &r = s->residue[m.residuesubmap[i]];

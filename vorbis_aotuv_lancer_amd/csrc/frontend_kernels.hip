@@ -430,20 +430,27 @@ __global__ __launch_bounds__(64) void k_fe_ve_filter(vbm_fe_state f, const vbm_s
         decay = __shfl(decay, threadIdx.x & 48);   // from lane 0 of this 16-lane group
 
         // spreading, limiting, spectrum smoothing (:151-159): value k uses decay after k subtractions of 8
-        // (subtracted one at a time, as the source rounds after each)
+        // (subtracted one at a time, as the source rounds after each).  A lane owns values jb and jb + 16: their
+        // energies do not depend on k, and of the chain it only needs dk after jb and after jb + 16 subtractions.
         {
-            float dk = decay;
-            for (int k = 0; k < 32; k++) {
-                if (k == jb || k == jb + 16) {
-                    const float x = (k == jb) ? a : a2, y = (k == jb) ? bq : bq2;
-                    float val = x * x + y * y;
-                    val = fe_todB(val) * .5f;
-                    if (val < dk) val = dk;
-                    if (val < minV) val = minV;
-                    s_vec[grp][k] = val;
-                }
+            float v0 = fe_todB(a * a + bq * bq) * .5f, v1 = fe_todB(a2 * a2 + bq2 * bq2) * .5f;
+            float dk = decay, d0 = decay, d1 = decay;
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                if (k == jb) d0 = dk;
                 dk = dk - 8.f;      // (the source's decay -= 8. in double, rounded back to float: one exact difference, one rounding = the float subtraction)
             }
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                if (k == jb) d1 = dk;
+                dk = dk - 8.f;
+            }
+            if (v0 < d0) v0 = d0;
+            if (v0 < minV) v0 = minV;
+            if (v1 < d1) v1 = d1;
+            if (v1 < minV) v1 = minV;
+            s_vec[grp][jb] = v0;
+            s_vec[grp][jb + 16] = v1;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -492,11 +499,12 @@ __global__ __launch_bounds__(64) void k_fe_ve_filter(vbm_fe_state f, const vbm_s
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
         if (ci == ch - 1) {
-            // OR over the 16 lanes of the group
-            ret |= __shfl_xor(ret, 1);
-            ret |= __shfl_xor(ret, 2);
-            ret |= __shfl_xor(ret, 4);
-            ret |= __shfl_xor(ret, 8);
+            // OR over the 16 lanes of the group = one DPP row (a group is active or returned as a whole): pairs, quads,
+            // then the mirrored half-row and row (every lane of a quad / half-row holds the same value by then)
+            ret |= __builtin_amdgcn_update_dpp(0, ret, 0xB1, 0xf, 0xf, true);    // quad_perm [1,0,3,2]
+            ret |= __builtin_amdgcn_update_dpp(0, ret, 0x4E, 0xf, 0xf, true);    // quad_perm [2,3,0,1]
+            ret |= __builtin_amdgcn_update_dpp(0, ret, 0x141, 0xf, 0xf, true);   // row_half_mirror
+            ret |= __builtin_amdgcn_update_dpp(0, ret, 0x140, 0xf, 0xf, true);   // row_mirror
 
             // mark bookkeeping of _ve_envelope_search (lib/envelope.c:611-624)
             if (jb == 0) {

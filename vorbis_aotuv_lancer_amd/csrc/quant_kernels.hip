@@ -682,22 +682,16 @@ __global__ __launch_bounds__(FP * FPC) void k_couple_fast(vbm_batch b_in)
     vbm_batch b = b_in;
     __shared__ fast_lds L;
     if ((int)(blockIdx.x * FPC) >= ((MODE == 1) ? vbm_nsb(b) : vbm_ncb(b))) return;   // (launch bound > device-resident count)
-    const vbm_setup *s = b.setup;
-    const vbm_psy *p = &s->psy[b.block_mode];
-    const vbm_map *vi = &s->map[b.W];
     const size_t SW = b.slab_words;
     const int NCH = (MODE == 1) ? 2 : 1;
+    // the setup's part of the constants comes ready from the host (b_in.cc: kernel arguments, read where they are used)
     fast_consts c;
-    c.n = p->n;
-    c.tonefix_end = p->tonefix_end;
-    c.prae = (vi->coupling_steps == 1) ? (float)0.34 : (float)0.825;
-    c.nn.normal_p = p->normal_p; c.nn.normal_start = p->normal_start; c.nn.normal_thresh = p->normal_thresh;
-    {
-        int lowpassr = s->block_lowpassr[b.W ? 1 : 0];
-        if (lowpassr % p->normal_partition) lowpassr = (lowpassr / p->normal_partition + 1) * p->normal_partition;
-        c.lowpassr = lowpassr;
-    }
-    const float *__restrict__ fromdB = s->fromdB;
+    c.n = b_in.cc.n;
+    c.tonefix_end = b_in.cc.tonefix_end;
+    c.prae = b_in.cc.prae;
+    c.nn.normal_p = b_in.cc.normal_p; c.nn.normal_start = b_in.cc.normal_start; c.nn.normal_thresh = b_in.cc.normal_thresh;
+    c.lowpassr = b_in.cc.lowpassr;
+    const float *__restrict__ fromdB = b.setup->fromdB;
     const int ncols = (MODE == 1) ? vbm_nsb(b) : vbm_ncb(b);
     const int pi = blockIdx.y, i = pi * FP;
     const int tid = threadIdx.x;
@@ -739,14 +733,13 @@ __global__ __launch_bounds__(FP * FPC) void k_couple_fast(vbm_batch b_in)
         vbm_blob_select(b, kb);
     }
     const int blobno = b.blobno;
-    c.limit = s->coupling_pointlimit[p->blockflag][blobno];
-    c.prepoint = (float)s->stereo_threshholds[s->coupling_prepointamp[blobno]];
-    c.postpoint = (float)s->stereo_threshholds[s->coupling_postpointamp[blobno]];
-    c.prepoint_x = (float)s->stereo_threshholds_X[s->coupling_prepointamp[blobno]];
-    c.postpoint_x = (float)s->stereo_threshholds_X[s->coupling_postpointamp[blobno]];
-    if (c.prepoint_x < c.prepoint) c.prepoint_x = c.prepoint;
-    if (c.postpoint_x < c.prepoint) c.postpoint_x = c.prepoint;
-    c.sliding_lowpass = s->sliding_lowpass[b.W][blobno];
+    {
+        const vbm_couple_blob &cbk = b_in.cc.blob[blobno];      // (b_in: the argument block itself, never written to)
+        c.limit = cbk.limit;
+        c.prepoint = cbk.prepoint; c.postpoint = cbk.postpoint;
+        c.prepoint_x = cbk.prepoint_x; c.postpoint_x = cbk.postpoint_x;
+        c.sliding_lowpass = cbk.sliding_lowpass;
+    }
     if (!past && colL < ncols && i + lr < c.n) {
 #pragma unroll
         for (int k = 0; k < NCH; k++) {
@@ -771,7 +764,7 @@ __global__ __launch_bounds__(FP * FPC) void k_couple_fast(vbm_batch b_in)
         }
 
         if (MODE == 1) {
-            const int Mi = vi->coupling_mag[0], Ai = vi->coupling_ang[0];
+            const int Mi = b_in.cc.mag, Ai = b_in.cc.ang;
             // registers of the magnitude / angle channel
             float reM = raw[Mi & 1], reA = raw[Ai & 1], qeM = quant[Mi & 1], qeA = quant[Ai & 1];
             float floorM = floor[Mi & 1], floorA = floor[Ai & 1], resM = res[Mi & 1], resA = res[Ai & 1];

@@ -13,13 +13,20 @@
 //   chase    seed_chase's stack walk (lib/psy.c:851-881) on those bytes.  An entry further than 7 lines back can
 //            never be popped again, so the walk's whole state is a 7-bit mask "line i-k is still on the stack"
 //            (the stack itself is the set of surviving lines; an entry's amplitude is its seed).  One lane walks
-//            64 lines + 16 lines of run-in with the state "nothing poppable" assumed at the start; a lane's state
-//            at its first own line is then checked against what its left neighbour arrived at, and a lane that
-//            guessed wrong re-runs from the true state until all agree (lane 0 starts from the true empty stack,
-//            so the fixed point is the serial walk's result; re-runs are rare).  Integer operations on registers only.
+//            16 lines of run-in with the state "nothing poppable" assumed at the start (state updates only), then
+//            its 64 own lines; a lane's state at its first own line is then checked against what its left
+//            neighbour arrived at, and a lane that guessed wrong re-runs from the true state until all agree
+//            (lane 0 starts from the true empty stack, so the fixed point is the serial walk's result; re-runs are
+//            rare).  A line's fate is final when it leaves the 7-line window: for the last seven lines of a chunk
+//            that happens in the right neighbour's first seven steps, which hands the seven bits left with one
+//            shuffle (no lane walks past its chunk).  Integer operations on registers only.
 //   fill     the tail of seed_chase (lib/psy.c:1012-1026): one wavefront per block, one lane per line: a surviving
 //            line's reach ends where the next survivor starts if that one is louder, else 9 lines on; where it
 //            starts is the exclusive prefix maximum of the ends before it.  All reads before the first write-back.
+//            Form kept: the scan, by DPP (row shifts, row_bcast:15 / :31, wave_shr:1) instead of ds_bpermute.  The
+//            other form, a lane per line that reads the alive bits of lines x-8 .. x+8 and walks the survivors in
+//            [x-8, x] (no scan, no scatter loop), gave the same step: 4.016 ms against 4.014 over four alternating
+//            runs of the from-PCM bench (profiles/tone_env_couple_trim).
 //   apply    max_seeds (lib/psy.c:936-1085): per bin the minimum of its seed-line segment (host-built seg_p0/p1)
 //            raises the ATH floor.
 //
@@ -47,11 +54,37 @@ __device__ __forceinline__ int seed_key(float f)
 }
 __device__ __forceinline__ float seed_val(int k) { return __int_as_float(k ^ ((k >> 31) & 0x7fffffff)); }
 
-// One chase lane: lines [i, iend] of a block, starting with window mask m (bit b: line i-1-b is on the stack).
-// gl[j] = GE | LE << 8 of line j.  own: the lane's 64 lines start at line `own`; alive gets their final fate,
-// m_own / m_next the mask at the start of lines own and own + 64.
-__device__ __forceinline__ void chase_run(const unsigned short *__restrict__ gl, int i, const int iend, unsigned m,
-                                          const int own, unsigned long long &alive, unsigned &m_own, unsigned &m_next)
+// One line of seed_chase's walk (lib/psy.c:851-881) on the mask machine: pop while the new seed is not below the top
+// (ge) and the top is not above the entry below it (le, from H: byte b = LE of line i-1-b), both within reach (inside
+// the 7-bit window).  Returns the mask before the line itself is pushed: its bit 6 is the final fate of line i-7.
+__device__ __forceinline__ unsigned chase_pop(unsigned m, const unsigned long long H, const unsigned ge)
+{
+    for (;;) {
+        const unsigned m2 = m & (m - 1);
+        if (!m2) break;
+        const int k0 = __ffs((int)m) - 1, k1 = __ffs((int)m2) - 1;
+        const unsigned c1 = (ge >> k0) & 1u;
+        const unsigned c2 = (unsigned)(H >> (8 * k0 + (k1 - k0 - 1))) & 1u;
+        if (!(c1 & c2)) break;
+        m = m2;
+    }
+    return m;
+}
+
+// One chase lane: run-in lines [i, own), then its own lines [own, oend], starting with window mask m (bit b: line
+// i-1-b is on the stack).  gl[j] = GE | LE << 8 of line j.  i and own are multiples of 4 (four lines per LDS read).
+//   m_own / m_next  the mask at the start of lines own and oend + 1
+//   alive           final fate of the own lines the walk itself sees leave the window: own .. oend - 7, and for the
+//                   last chunk of a row (`last`) also the lines it ended on top of
+//   left7           bit t: final fate of line own - 7 + t, the left neighbour's last seven lines.  They sit in this
+//                   walk's mask at its first line and leave the window in its first seven steps, so once m_own has been
+//                   checked against the neighbour's m_next they are the truth and the neighbour need not walk on
+//                   past its chunk to learn them.
+// The run-in loop only carries the state; the own loop collects bit 6 of every step into F (bit t: line own + t - 7),
+// a nibble per LDS read: alive = F >> 7, left7 = F & 0x7f.
+__device__ __forceinline__ void chase_run(const unsigned short *__restrict__ gl, int i, unsigned m, const int own, const int oend,
+                                          const bool last, unsigned long long &alive, unsigned &left7, unsigned &m_own,
+                                          unsigned &m_next)
 {
     unsigned long long H = 0;               // byte b: LE of line i-1-b
 #pragma unroll
@@ -59,41 +92,57 @@ __device__ __forceinline__ void chase_run(const unsigned short *__restrict__ gl,
         const int q = i - 1 - b;
         if (q >= 0) H |= (unsigned long long)(gl[q] >> 8) << (8 * b);
     }
-    alive = 0;
-    // four lines per LDS read (i is a multiple of 4 here: run-ins start 16 lines before a multiple of 64)
-    for (; i <= iend; i += 4) {
+    for (; i < own; i += 4) {
         const unsigned long long g4 = *(const unsigned long long *)(gl + i);
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const int ii = i + u;
-            if (ii <= iend) {
-                if (ii == own) m_own = m;
-                if (ii == own + 64) m_next = m;
+            const unsigned g = (unsigned)(g4 >> (16 * u)) & 0xffffu;
+            m = chase_pop(m, H, g & 0xffu);
+            m = ((m << 1) | 1u) & 0x7fu;
+            H = (H << 8) | (g >> 8);
+        }
+    }
+    m_own = m;
+    unsigned long long F = 0;
+    for (; i + 3 <= oend; i += 4) {
+        const unsigned long long g4 = *(const unsigned long long *)(gl + i);
+        unsigned nb = 0;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const unsigned g = (unsigned)(g4 >> (16 * u)) & 0xffffu;
+            m = chase_pop(m, H, g & 0xffu);
+            nb |= ((m >> 6) & 1u) << u;
+            m = ((m << 1) | 1u) & 0x7fu;
+            H = (H << 8) | (g >> 8);
+        }
+        F |= (unsigned long long)nb << (i - own);
+    }
+    if (i <= oend) {                        // the last chunk's one to three lines past a multiple of four
+        const unsigned long long g4 = *(const unsigned long long *)(gl + i);
+        unsigned nb = 0;
+#pragma unroll
+        for (int u = 0; u < 3; u++) {
+            if (i + u <= oend) {
                 const unsigned g = (unsigned)(g4 >> (16 * u)) & 0xffffu;
-                const unsigned ge = g & 0xffu;
-                // lib/psy.c:851-881: pop while the new seed is not below the top (ge) and the top is not above the
-                // entry below it (le), both within reach (inside the 7-bit window)
-                for (;;) {
-                    const unsigned m2 = m & (m - 1);
-                    if (!m2) break;
-                    const int k0 = __ffs((int)m) - 1, k1 = __ffs((int)m2) - 1;
-                    const unsigned c1 = (ge >> k0) & 1u;
-                    const unsigned c2 = (unsigned)(H >> (8 * k0 + (k1 - k0 - 1))) & 1u;
-                    if (!(c1 & c2)) break;
-                    m = m2;
-                }
-                const int q = ii - 7 - own;     // line ii-7 leaves the window: its fate is final
-                if (q >= 0 && q < 64) alive |= (unsigned long long)((m >> 6) & 1u) << q;
+                m = chase_pop(m, H, g & 0xffu);
+                nb |= ((m >> 6) & 1u) << u;
                 m = ((m << 1) | 1u) & 0x7fu;
                 H = (H << 8) | (g >> 8);
             }
         }
+        F |= (unsigned long long)nb << (i - own);
     }
-    if (iend + 1 == own + 64) m_next = m;
+    m_next = m;
+    alive = F >> 7;
+    left7 = (unsigned)F & 0x7fu;
+    if (last) {
 #pragma unroll
-    for (int b = 0; b < 7; b++) {           // lines the walk ended on top of
-        const int q = iend - b - own;
-        if (q >= 0 && q < 64 && iend - b + 7 > iend) alive |= (unsigned long long)((m >> b) & 1u) << q;
+        for (int b = 0; b < 7; b++) {       // lines the walk ended on top of (a chunk of fewer than seven lines: the
+            const int q = oend - b - own;   // left neighbour's too)
+            const unsigned bit = (m >> b) & 1u;
+            if (q >= 0) alive |= (unsigned long long)bit << q;
+            else left7 |= bit << (q + 7);
+        }
     }
 }
 
@@ -228,12 +277,12 @@ __global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int 
         const bool active = blk < nblk && own < tn;
         const unsigned short *gl = glS + blk * glp;
         unsigned long long alive = 0;
-        unsigned m_own = 0, m_next = 0, used = 0;
-        int iend = own + 70;
-        if (iend > tn - 1) iend = tn - 1;
+        unsigned m_own = 0, m_next = 0, used = 0, left7 = 0;
+        const int oend = own + 63 < tn - 1 ? own + 63 : tn - 1;
+        const bool last = own + 64 >= tn;                      // the last chunk of the row: no right neighbour
         if (active) {
             const int i0 = own >= runin ? own - runin : 0;     // runin: multiple of 4
-            chase_run(gl, i0, iend, 0u, own, alive, m_own, m_next);
+            chase_run(gl, i0, 0u, own, oend, last, alive, left7, m_own, m_next);
             used = m_own;
         }
         // a lane whose assumed state differs from what its left neighbour arrived at runs again from the true one
@@ -242,9 +291,15 @@ __global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int 
             const bool redo = active && c > 0 && truth != used;
             if (!__any(redo)) break;
             if (redo) {
-                chase_run(gl, own, iend, truth, own, alive, m_own, m_next);
+                chase_run(gl, own, truth, own, oend, last, alive, left7, m_own, m_next);
                 used = truth;
             }
+        }
+        // lines own + 57 .. own + 63 left the window in the right neighbour's first seven steps (all 16 lanes of a block
+        // lie in one wavefront; a lane that is not `last` has an active right neighbour)
+        {
+            const unsigned from_right = __shfl_down(left7, 1);
+            if (active && !last) alive |= (unsigned long long)from_right << 57;
         }
         if (blk < nblk) s_alive[blk][c] = active ? alive : 0ull;   // (blk >= TM_NB >= nblk for the second half)
     }
@@ -278,25 +333,29 @@ __global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int 
                         else endpos = q + linesper + 1;
                         if (endpos > tn) endpos = tn;
                     }
+                    // inclusive prefix maximum of the ends over the wavefront (ends are >= 0: a lane with no source takes
+                    // 0): four row shifts inside the rows of 16, then lane 15 of rows 0 and 2 to the row above, then lane
+                    // 31 to rows 2 and 3 (the whole wavefront is active here; each DPP read is made once, outside any branch)
                     int incl = endpos;
-#pragma unroll
-                    for (int d = 1; d < 64; d <<= 1) {
-                        const int t = __shfl_up(incl, d);
-                        if (lane >= d && t > incl) incl = t;
-                    }
-                    int excl = __shfl_up(incl, 1);
-                    if (lane == 0) excl = 0;
+                    { const int t = __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, true); incl = t > incl ? t : incl; }    // row_shr:1
+                    { const int t = __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, true); incl = t > incl ? t : incl; }    // row_shr:2
+                    { const int t = __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, true); incl = t > incl ? t : incl; }    // row_shr:4
+                    { const int t = __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, true); incl = t > incl ? t : incl; }    // row_shr:8
+                    { const int t = __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xa, 0xf, false); incl = t > incl ? t : incl; }   // row_bcast:15
+                    { const int t = __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xc, 0xf, false); incl = t > incl ? t : incl; }   // row_bcast:31
+                    int excl = __builtin_amdgcn_update_dpp(0, incl, 0x138, 0xf, 0xf, true);            // wave_shr:1
                     if (carry > excl) excl = carry;
                     st[c] = excl;
                     en[c] = endpos;
-                    const int tot = __shfl(incl, 63);
+                    const int tot = __builtin_amdgcn_readlane(incl, 63);
                     if (tot > carry) carry = tot;
                 }
             }
             // every survivor is in registers: now the lines may be overwritten (LDS operations of a wavefront stay in order)
 #pragma unroll
             for (int c = 0; c < TM_CHUNKS; c++)
-                for (int x = st[c]; x < en[c]; x++) sd[x] = am[c];
+                if (c * 64 < tn)
+                    for (int x = st[c]; x < en[c]; x++) sd[x] = am[c];
         }
     }
     __syncthreads();
