@@ -610,8 +610,19 @@ int  vbm_decoder_fetch(vbm_decoder *dec, const char *name, void *d_out, long *ro
  *                            every point of the host code whose bit is set in `mask` (points: csrc/vbm_internal.h,
  *                            enum vbm_delay_point); process-wide; usec = 0 switches it off
  *   vbm_debug_poison_workspace  fills the scratch arrays of encoder workspace w (-1: all) with `byte`, device idle
- *   vbm_debug_poison_frontend   the same for the front end's block buffers, search spectra and round lists */
+ *   vbm_debug_poison_frontend   the same for the front end's block buffers, search spectra and round lists
+ * Some launchers take another kernel, or another slicing of the same kernel, once a batch is large (csrc/batch.h,
+ * "kernel variants chosen by batch size").  vbm_debug_batch_variants says which forms a batch of `nsb` stream-blocks of
+ * `ch` channels takes, from the launchers' own predicates; block_mode 0..3, n = blocksize / 2, few: the batch is a
+ * device-built round's (small whatever its launch bound).  Pure host arithmetic: no device, no handle.  Bits:
+ *   0  floor fit by the lane-per-channel-block kernel (else the cooperative one)
+ *   1  coarse slices of the bin range in offset-and-mix (never for block_mode 0, which is not sliced)
+ *   2  coarse slices of the floor render
+ *   3  coarse slices of the residue partitions (at most 32 per submap, else at most 256)
+ *   4  offset-and-mix leaves the floor fit's input words itself (no separate pass); decided when a batch is
+ *      configured, so for a slice of a batch or a round's batch the size to ask about is the whole batch's, few = 0 */
 int vbm_debug_set_delay(unsigned mask, int usec);
+unsigned vbm_debug_batch_variants(int block_mode, int n, int ch, int nsb, int few);
 int vbm_debug_poison_workspace(vbm_encoder *enc, int w, int byte);
 int vbm_debug_poison_frontend(vbm_frontend *fe, int byte);
 

@@ -13,10 +13,10 @@ from ._lib import lib, LIB_PATH, COMPAT_LIB_PATH, VbmError, check  # noqa: F401
 from .tables import window_table  # noqa: F401
 from .mdct import MdctLookup, mdct_forward, window_mdct, window_fft_log  # noqa: F401
 
-from .encoder import Setup, Encoder, FrontEnd, PacketInfo  # noqa: F401,E402
+from .encoder import Setup, Encoder, FrontEnd, PacketInfo, batch_variants  # noqa: F401,E402
 from .stream import header_packets, OggStream, OggMux, write_ogg, read_ogg, demux_ogg  # noqa: F401,E402
 from .decoder import DecodeSetup, Decoder, decode_ogg, decode_index, RangeStore, OggIndex  # noqa: F401,E402
 from .files import encode_ogg, plan_files  # noqa: F401,E402
 
-__all__ = ["Setup", "Encoder", "FrontEnd", "PacketInfo", "header_packets", "OggStream", "OggMux", "write_ogg", "read_ogg", "demux_ogg", "DecodeSetup", "Decoder", "decode_ogg", "encode_ogg", "plan_files", "decode_index", "RangeStore", "OggIndex", "lib", "LIB_PATH", "COMPAT_LIB_PATH", "VbmError", "check", "window_table",
+__all__ = ["Setup", "Encoder", "FrontEnd", "PacketInfo", "batch_variants", "header_packets", "OggStream", "OggMux", "write_ogg", "read_ogg", "demux_ogg", "DecodeSetup", "Decoder", "decode_ogg", "encode_ogg", "plan_files", "decode_index", "RangeStore", "OggIndex", "lib", "LIB_PATH", "COMPAT_LIB_PATH", "VbmError", "check", "window_table",
            "MdctLookup", "mdct_forward", "window_mdct", "window_fft_log"]

@@ -151,8 +151,51 @@ void vbm_blob_select(vbm_batch &b, int k)
     b.vqcodeT = b.vqcodeT_blob + (size_t)k * b.vq_blob_words;
 }
 
+// ---- kernel variants chosen by batch size ----------------------------------------------------------------------------
+// Several launchers take a latency-bound form for a small batch and a throughput form for a large one.  The limits are
+// defined here, once: the launchers (floor_kernels.hip, psy_kernels.hip, pack_kernels.hip) call these, and so does
+// vbm_debug_batch_variants (debug_hooks.hip), which is where the tests read them.  `few`: vbm_batch::few.  A slice of a
+// batch (slice_of, capi_encoder.cpp) is judged by its own size.
+
+// floor fit: the lane-per-channel-block kernel (k_floor_fit) instead of the cooperative one (k_floor_fit_coop)
+static inline bool vbm_floor_fit_lean(int ncb, int few) { return !(few || ncb <= 128 * 64); }
+// slices of the bin range of k_mix: coarse ones (2-16 per block) instead of slices of 8-64 bins
+static inline bool vbm_bin_slices_coarse(int ncb, int few) { return !(few || ncb <= 1024); }
+// k_floor_render: 2-8 slices per block instead of n/16
+static inline bool vbm_floor_render_coarse(int ncb, int few) { return !(few || ncb <= 1024); }
+// k_res_vq / k_res_emit: at most 32 slices of a submap's partitions instead of at most 256
+static inline bool vbm_residue_slices_coarse(int nsb, int few) { return !(few || nsb <= 1024); }
+
+// slices of the bin range for the kernels whose bins are independent (long blocks: 64 bins each)
+static inline int vbm_bin_chunks(int n, int ncb, int few)
+{
+    const int chunks = n >= 1024 ? 16 : n >= 512 ? 8 : n >= 256 ? 4 : 2;
+    // A small batch (the short rounds of the front end: a few wavefronts on an empty chip) is bound by the
+    // latency of each wavefront's walk over its bins, not by throughput: slices of 8-16 bins instead of 64.
+    if (!vbm_bin_slices_coarse(ncb, few)) {
+        int fine = n / (n >= 1024 ? 16 : 8);
+        if (fine > 64) fine = 64;
+        if (fine > chunks) return fine;
+    }
+    return chunks;
+}
+// slices of at most 64 bins fit the 64 x 64 tile k_mix writes the floor-fit words through (vbm_batch::mix_makes_qf)
+static inline bool vbm_mix_slices_fit_qf(int block_mode, int n, int ncb, int few)
+{
+    const int chunks = vbm_bin_chunks(n, ncb, few);
+    return block_mode != 0 && (n + chunks - 1) / chunks <= 64;
+}
+static inline int vbm_floor_render_chunks(int n, int ncb, int few)
+{
+    int nchunks = n >= 1024 ? 8 : n >= 256 ? 4 : 2;
+    if (!vbm_floor_render_coarse(ncb, few) && n / 16 > nchunks) nchunks = n / 16;   // small batch: latency-bound, finer slices
+    return nchunks;
+}
+// (a small batch is bound by the length of a slice's walk: one partition per slice there)
+static inline int vbm_residue_most_slices(int nsb, int few) { return vbm_residue_slices_coarse(nsb, few) ? 32 : 256; }
+
 #ifdef __HIPCC__
-// First statement of a back-half kernel.  The kernels are templates on BLOBS: the managed instantiation takes the blob from
+// First statement of a back-half kernel. The kernels are templates on BLOBS: the managed instantiation takes the blob from
 // blockIdx.z; the other one leaves its argument alone (a kernel argument that is written to moves, with the arrays that
 // are indexed at run time, from the constant kernarg segment into registers and scratch: measured on k_res_vq and the
 // couple kernel, + 17 % on the from-PCM step).

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include "vbm_internal.h"
+#include "batch.h"
 
 namespace {
 
@@ -44,4 +45,18 @@ extern "C" int vbm_debug_set_delay(unsigned mask, int usec)
     g_delay_usec.store(usec, std::memory_order_relaxed);
     g_delay_mask.store(usec ? mask : 0u, std::memory_order_relaxed);
     return 0;
+}
+
+// Which size-selected kernel variants (batch.h) a batch of `nsb` stream-blocks of `ch` channels, block type
+// `block_mode`, n = blocksize / 2, takes.  Pure host arithmetic on the launchers' own predicates.
+extern "C" unsigned vbm_debug_batch_variants(int block_mode, int n, int ch, int nsb, int few)
+{
+    const int ncb = nsb * ch;
+    unsigned m = 0;
+    if (vbm_floor_fit_lean(ncb, few)) m |= 1u;
+    if (block_mode != 0 && vbm_bin_slices_coarse(ncb, few)) m |= 2u;      // (k_mix does not slice impulse blocks)
+    if (vbm_floor_render_coarse(ncb, few)) m |= 4u;
+    if (vbm_residue_slices_coarse(nsb, few)) m |= 8u;
+    if (vbm_mix_slices_fit_qf(block_mode, n, ncb, few)) m |= 16u;
+    return m;
 }

@@ -1032,7 +1032,7 @@ extern "C" int vbm_launch_floor_fit(const vbm_batch *b, hipStream_t st)
     // "Small": up to 8192 channel-blocks — the rounds of a 4096-stream pool of the drop-in shim are that size: 27.3-27.9 k
     // streams at 1x through the reference's entry points against 25.2-25.7 k with the limit at 4096; the from-PCM step of
     // the batched boundary does not notice (its small batches carry the `few` flag anyway).
-    if (b->few || b->ncb <= 128 * 64) {
+    if (!vbm_floor_fit_lean(b->ncb, b->few)) {
         const int pmax = b->fit_max_posts;
         const size_t lds = (size_t)4 * (((pmax - 1) * 10 + ((10 * pmax + 1) >> 1) + 1) & ~1) * sizeof(int);
         hipLaunchKernelGGL(k_floor_fit_coop, dim3((unsigned)((b->ncb + 3) / 4)), dim3(64), lds, st, *b, pmax);
@@ -1051,8 +1051,7 @@ extern "C" int vbm_launch_floor_encode(const vbm_batch *b, hipStream_t st)
     const unsigned nbl = (unsigned)(b->nblobs > 1 ? b->nblobs : 1);      // managed bitrate: a packetblob per blockIdx.z
     if (nbl > 1) hipLaunchKernelGGL(k_floor_encode<true>, dim3((unsigned)((b->ncb + 63) / 64), 1, nbl), dim3(64), 0, st, *b);
     else hipLaunchKernelGGL(k_floor_encode<false>, dim3((unsigned)((b->ncb + 63) / 64)), dim3(64), 0, st, *b);
-    int nchunks = b->n >= 1024 ? 8 : b->n >= 256 ? 4 : 2;
-    if ((b->few || b->ncb <= 1024) && b->n / 16 > nchunks) nchunks = b->n / 16;   // small batch: latency-bound, finer slices
+    const int nchunks = vbm_floor_render_chunks(b->n, b->ncb, b->few);   // fine or coarse by the batch's size (batch.h)
     if (nbl > 1)
         hipLaunchKernelGGL(k_floor_render<true>, dim3((unsigned)((b->ncb + 63) / 64), (unsigned)nchunks, nbl), dim3(64), 0, st, *b, nchunks);
     else

@@ -747,8 +747,7 @@ extern "C" int vbm_launch_pack_residue(const vbm_batch *b, hipStream_t st)
     if (nbl > 1) hipLaunchKernelGGL(k_nonzero_propagate<true>, dim3(tiles, 1, nbl), dim3(64), 0, st, *b);
     else hipLaunchKernelGGL(k_nonzero_propagate<false>, dim3(tiles), dim3(64), 0, st, *b);
     for (int sm = 0; sm < b->pack_submaps; sm++) {
-        // (a small batch is bound by the length of a slice's walk: one partition per slice there)
-        const int most = (b->few || b->nsb <= 1024) ? 256 : 32;
+        const int most = vbm_residue_most_slices(b->nsb, b->few);   // by the batch's size (batch.h)
         int nchunks = b->pack_partvals[sm] < most ? b->pack_partvals[sm] : most;
         if (nchunks < 1) nchunks = 1;
         const size_t lds = (size_t)b->pack_spp[sm] * 64 * sizeof(int);

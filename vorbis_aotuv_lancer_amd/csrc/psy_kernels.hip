@@ -782,19 +782,8 @@ __global__ __launch_bounds__(64) void k_mix_impulse(vbm_batch b)
 }  // namespace
 
 static inline dim3 grid_for(int lanes) { return dim3((unsigned)((lanes + 63) / 64)); }
-// slices of the bin range for the kernels whose bins are independent (long blocks: 64 bins each)
-static inline int bin_chunks(const vbm_batch *b)
-{
-    const int chunks = b->n >= 1024 ? 16 : b->n >= 512 ? 8 : b->n >= 256 ? 4 : 2;
-    // A small batch (the short rounds of the front end: a few wavefronts on an empty chip) is bound by the
-    // latency of each wavefront's walk over its bins, not by throughput: slices of 8-16 bins instead of 64.
-    if (b->few || b->ncb <= 1024) {
-        int fine = b->n / (b->n >= 1024 ? 16 : 8);
-        if (fine > 64) fine = 64;
-        if (fine > chunks) return fine;
-    }
-    return chunks;
-}
+// slices of the bin range for the kernels whose bins are independent: fine or coarse by the batch's size (batch.h)
+static inline int bin_chunks(const vbm_batch *b) { return vbm_bin_chunks(b->n, b->ncb, b->few); }
 
 extern "C" int vbm_launch_prologue(const vbm_batch *b, hipStream_t st)
 {
@@ -837,10 +826,9 @@ extern "C" int vbm_launch_mix(const vbm_batch *b, hipStream_t st)
     else hipLaunchKernelGGL((k_mix<1, false, false, false>), grid, dim3(64), 0, st, *b, nchunks);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
-// slices of at most 64 bins fit the 64 x 64 tile k_mix writes the floor-fit words through
 extern "C" int vbm_mix_can_make_qf(const vbm_batch *b)
 {
-    return b->block_mode != 0 && (b->n + bin_chunks(b) - 1) / bin_chunks(b) <= 64;
+    return vbm_mix_slices_fit_qf(b->block_mode, b->n, b->ncb, b->few);
 }
 // managed bitrate: offset_select 1 (first fit), 2 (higher rate), 0 (lower rate), lib/mapping0.c:1044-1160
 extern "C" int vbm_launch_mix_managed(const vbm_batch *b, int offset_select, hipStream_t st)

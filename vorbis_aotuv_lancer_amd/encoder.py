@@ -21,6 +21,17 @@ def mode_pack_path(channels, rate, quality=None, bitrate=None):
     return os.path.join(_DATA, name + ".vpk")
 
 
+# bits of batch_variants()
+LEAN_FLOOR_FIT, COARSE_BIN_SLICES, COARSE_FLOOR_RENDER, COARSE_RESIDUE_SLICES, MIX_MAKES_FIT_WORDS = 1, 2, 4, 8, 16
+LARGE_BATCH_BITS = LEAN_FLOOR_FIT | COARSE_BIN_SLICES | COARSE_FLOOR_RENDER | COARSE_RESIDUE_SLICES
+
+
+def batch_variants(block_mode, n, channels, nsb, few=False):
+    """test instrumentation: the size-selected kernel variants a batch of `nsb` stream-blocks of block type
+    `block_mode` (n = blocksize / 2) takes, as a mask of the bits above (vbm_debug_batch_variants; needs no device)"""
+    return int(lib.vbm_debug_batch_variants(block_mode, n, channels, nsb, 1 if few else 0))
+
+
 class Setup:
     """codec_setup_info + looks for one (channels, rate, quality) class (vorbis_encode_init_vbr +
     vorbis_analysis_init in the reference) or, with bitrate=, one managed-bitrate class
