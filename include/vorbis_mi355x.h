@@ -376,6 +376,71 @@ int vbm_comment_packet(const char *vendor, const char *const *comments, int ncom
 #define VBM_EOGG (-1002)
 int vbm_ogg_demux(const uint8_t *data, long n, long *sizes, uint8_t *headers, uint8_t *packets, long long *offsets,
                   long long *granulepos, uint8_t *eos);
+
+/* ---- Ogg demux, batch form: many whole files per call, on the device ----------------------------------------------
+ * vbm_ogg_demux for `nfiles` files that lie in one device buffer, file f in d_data[file_offsets[f], file_offsets[f+1])
+ * (bytes between files may be left out by the offsets; nothing outside a file's range is read for it).  Every file
+ * holds ONE logical stream and is judged by the rules of vbm_ogg_demux, on its own bytes alone: it comes out with status
+ * 0 and the header packets, audio packet bytes, offsets, granulepos and eos vbm_ogg_demux gives for it, or with
+ * VBM_EOGG exactly when vbm_ogg_demux returns VBM_EOGG, and then adds no packet and no byte.  (One exception that no
+ * Vorbis file meets: header packets of 2^31 bytes or more in all are VBM_EOGG, as header_bytes could not hold them.)
+ * The protocol is vbm_ogg_demux's size query / fill, per batch:
+ *   vbm_ogg_demuxer_create   workspace on the current device for calls of up to max_files files that span up to
+ *                            max_bytes bytes (file_offsets[nfiles] - file_offsets[0]): about 1.2 * max_bytes + 120 *
+ *                            max_files bytes (csrc/ogg_demux.h).  vbm_host_ogg_demuxer_create: the same in host memory
+ *                            for the vbm_host_* calls, touches no device.
+ *   vbm_ogg_demux_scan       validates every file, CRCs included: d_info[f].status is final.  d_info[f] also has the
+ *                            file's page count, serial number, the three header packet lengths, its audio packets and
+ *                            their bytes (all 0 for a failed file), and packet_base / payload_base / header_base, the
+ *                            sums of packets / payload_bytes / header bytes over the files in front of it.
+ *                            d_totals[3]: audio packets, payload bytes and header bytes of the batch.  d_info and
+ *                            d_totals are device memory; file_offsets [nfiles + 1] is host memory and is free on return.
+ *   vbm_ogg_demux_fill       writes the outputs of the last scan on this demuxer (d_data must still hold the files).  The
+ *                            audio packets of all good files form ONE CSR over a dense payload: packet k of file f is
+ *                            d_payload[d_offsets[packet_base + k], d_offsets[packet_base + k + 1]), d_offsets[0] = 0 and
+ *                            d_offsets[packet_base + packets] = payload_base + payload_bytes is where the next file
+ *                            starts; d_granulepos / d_eos as vbm_ogg_demux, at packet_base + k.  The three header
+ *                            packets of file f lie back to back at d_headers + header_base.  This is the input of
+ *                            vbm_synthesis_runs with no copy in between: run_packets = packets, d_data = d_payload,
+ *                            d_offsets + packet_base of the first file of the call, and so on.
+ *                            Capacities: d_headers holds header_cap bytes, d_payload payload_cap bytes, d_offsets
+ *                            packet_cap + 1 entries, d_granulepos and d_eos packet_cap.  Nothing is written past any of
+ *                            them: when one is below the batch's total, NOTHING is written at all and the demuxer's
+ *                            status word becomes VBM_OGG_DEMUX_ECAP (0 after a fill that wrote its outputs).
+ *   vbm_ogg_demux_status     the status word of the last fill -> *status (host memory).  The one call here that waits:
+ *                            for `stream`, on which that fill must have been enqueued.
+ * scan and fill allocate nothing and only enqueue on `stream`; the one wait in scan is for the pinned slot that carried
+ * the file offsets two scans earlier.  VBM_EINVAL, with nothing enqueued: nfiles negative or above max_files, a
+ * negative or decreasing offset, a span above max_bytes, a null pointer (d_data may be null when the span is 0, d_info
+ * when nfiles is 0, an output of fill when its capacity is 0; d_offsets never), a negative capacity, fill without a scan,
+ * a host demuxer in a device call or the other way round.
+ *   vbm_host_ogg_demux_scan / _fill   the same source on the CPU with host pointers and a host demuxer. */
+#define VBM_OGG_DEMUX_ECAP 1
+typedef struct {
+    int status;                 /* 0 or VBM_EOGG */
+    int pages;
+    unsigned serialno;
+    int header_bytes[3];
+    long long packets;          /* audio packets (after the three headers) */
+    long long payload_bytes;    /* their bytes */
+    long long packet_base, payload_base, header_base;   /* exclusive sums over the files before it */
+} vbm_ogg_file_info;
+typedef struct vbm_ogg_demuxer vbm_ogg_demuxer;
+int vbm_ogg_demuxer_create(vbm_ogg_demuxer **dm, int max_files, long long max_bytes);
+int vbm_host_ogg_demuxer_create(vbm_ogg_demuxer **dm, int max_files, long long max_bytes);
+void vbm_ogg_demuxer_destroy(vbm_ogg_demuxer *dm);
+int vbm_ogg_demux_scan(vbm_ogg_demuxer *dm, int nfiles, const uint8_t *d_data, const long long *file_offsets,
+                       vbm_ogg_file_info *d_info, long long *d_totals, void *stream);
+int vbm_ogg_demux_fill(vbm_ogg_demuxer *dm, uint8_t *d_headers, long long header_cap, uint8_t *d_payload,
+                       long long payload_cap, long long *d_offsets, long long *d_granulepos, uint8_t *d_eos,
+                       long long packet_cap, void *stream);
+int vbm_ogg_demux_status(vbm_ogg_demuxer *dm, int *status, void *stream);
+int vbm_host_ogg_demux_scan(vbm_ogg_demuxer *dm, int nfiles, const uint8_t *data, const long long *file_offsets,
+                            vbm_ogg_file_info *info, long long *totals);
+int vbm_host_ogg_demux_fill(vbm_ogg_demuxer *dm, uint8_t *headers, long long header_cap, uint8_t *payload,
+                            long long payload_cap, long long *offsets, long long *granulepos, uint8_t *eos,
+                            long long packet_cap);
+
 typedef struct vbm_ogg_stream vbm_ogg_stream;
 int vbm_ogg_stream_create(vbm_ogg_stream **os, int serialno);
 void vbm_ogg_stream_destroy(vbm_ogg_stream *os);

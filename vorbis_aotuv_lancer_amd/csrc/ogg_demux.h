@@ -1,0 +1,236 @@
+// Ogg demux for many whole files at once: the acceptance rules of demux() in capi_stream.cpp (vbm_ogg_demux), written
+// once for the host twin (vbm_host_ogg_demux_*) and the device kernels (ogg_demux.hip).  Page format: the reference's
+// doc/framing.html.
+//
+// What makes the rule parallel: demux() appends the body of every page to one byte run per file and cuts it where a
+// lacing value below 255 ends a packet.  So a body byte's place in the output is the number of body bytes in front of
+// it in its file, and a packet's end is the body byte count through the segment that ends it.  With H = the end of
+// the third packet and E = the end of the last completed packet, bytes [0, H) are the header packets, [H, E) the audio
+// payload, and anything from E on is the unterminated packet that is dropped.  A page needs to know only the body bytes
+// and completed packets in front of it (OggDmxPage); the walk that finds them is the serial part, one lane per file.
+//
+// Workspace, sized at create from max_files / max_bytes: a page is at least 27 bytes, so file f (bytes
+// [off[f], off[f+1]) of the call's data) has at most (off[f+1] - off[f]) / 27 pages, and its records start at slot
+// (off[f] - off[0]) / 27: sums of floors stay below the floor of the sum, so files never share a slot and no scan is
+// needed before the walk.  That is max_bytes / 27 + 1 records of 32 B, about 1.2 bytes per input byte.  The pages that
+// were found are then numbered densely through an exclusive scan of the files' page counts (page_base), and the
+// page-parallel kernels map a dense number back to file and slot by a binary search in it.
+#pragma once
+#include <stdint.h>
+
+#include "ogg_mux.h"
+
+struct OggDmxPage {          // one page the walk accepted
+    long long at;            // first byte of the page in the call's data
+    long long body_before;   // body bytes of the file's pages in front of it
+    long long pkt_before;    // packets completed in front of it
+    int len;                 // 27 + nseg + body bytes
+    int pad;
+};
+
+struct OggDmxWalk {          // one file while its pages are walked
+    long long pos, end;      // next byte to read, end of the file
+    long long body, packets; // body bytes seen, packets completed
+    long long last_end;      // body bytes through the last completed packet
+    long long h0, h1, h2;    // ... through each of the first three packets
+    uint32_t serial, seq;    // the stream's serial number (once a page has been seen), the next page number
+    int partial;             // a packet is open at the end of the last page
+};
+
+VBMX_HD uint32_t oggdmx_rd32(const uint8_t *p)
+{
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+VBMX_HD long long oggdmx_rd64(const uint8_t *p)
+{
+    return (long long)((unsigned long long)oggdmx_rd32(p) | ((unsigned long long)oggdmx_rd32(p + 4) << 32));
+}
+
+VBMX_HD void oggdmx_walk_begin(OggDmxWalk &w, long long begin, long long end)
+{
+    w.pos = begin, w.end = end;
+    w.body = w.packets = w.last_end = 0;
+    w.h0 = w.h1 = w.h2 = 0;
+    w.serial = w.seq = 0;
+    w.partial = 0;
+}
+
+// The next page of the file: 1 and its record, 0 at the end of the file, -1 where demux() fails (CRC apart, which
+// the page-parallel pass checks).  No byte is read before it is known to lie in front of w.end, and every page taken
+// moves w.pos on by at least 27 bytes.
+VBMX_HD int oggdmx_walk_step(const uint8_t *data, OggDmxWalk &w, OggDmxPage &pg)
+{
+    if (w.pos >= w.end) return 0;
+    const long long left = w.end - w.pos;
+    if (left < 27) return -1;                                      // no capture pattern / truncated page header
+    const uint8_t *h = data + w.pos;
+    if (h[0] != 'O' || h[1] != 'g' || h[2] != 'g' || h[3] != 'S') return -1;
+    if (h[4] != 0) return -1;                                      // stream structure version
+    const int flags = h[5], nseg = h[26];
+    if (left - 27 < nseg) return -1;                               // truncated page
+    if (!(flags & 1) && w.partial) return -1;                      // a packet continues into a page that is not a continuation
+    const uint32_t sno = oggdmx_rd32(h + 14), seq = oggdmx_rd32(h + 18);
+    if (w.seq != 0 && sno != w.serial) return -1;                  // chained or multiplexed streams
+    if (seq != w.seq) return -1;                                   // page sequence counts from 0
+    long long body = w.body, packets = w.packets, last_end = w.last_end;
+    int partial = w.partial;
+    for (int i = 0; i < nseg; i++) {
+        const int lv = h[27 + i];
+        body += lv;
+        partial = lv == 255;
+        if (lv < 255) {
+            if (packets == 0) w.h0 = body;
+            if (packets == 1) w.h1 = body;
+            if (packets == 2) w.h2 = body;
+            packets++;
+            last_end = body;
+        }
+    }
+    const long long body_len = body - w.body;
+    if (left - 27 - nseg < body_len) return -1;                    // truncated page
+    pg.at = w.pos;
+    pg.body_before = w.body;
+    pg.pkt_before = w.packets;
+    pg.len = 27 + nseg + (int)body_len;
+    pg.pad = 0;
+    w.serial = sno;
+    w.seq = seq + 1;                                               // 2^32 pages would need a file of 108 GB
+    w.body = body, w.packets = packets, w.last_end = last_end;
+    w.partial = partial;
+    w.pos += pg.len;
+    return 1;
+}
+
+// what the walk leaves in a file's info: counts of a good file, VBM_EOGG and zeros otherwise (bases: the scan)
+VBMX_HD void oggdmx_walk_end(const OggDmxWalk &w, bool ok, int npages, vbm_ogg_file_info &fi)
+{
+    ok = ok && w.packets >= 3;                                     // fewer than three header packets
+    ok = ok && w.h2 < (1ll << 31);                                 // header_bytes are ints: no Vorbis header comes near
+    fi.status = ok ? 0 : VBM_EOGG;
+    fi.pages = ok ? npages : 0;
+    fi.serialno = ok ? w.serial : 0u;
+    fi.header_bytes[0] = ok ? (int)w.h0 : 0;
+    fi.header_bytes[1] = ok ? (int)(w.h1 - w.h0) : 0;
+    fi.header_bytes[2] = ok ? (int)(w.h2 - w.h1) : 0;
+    fi.packets = ok ? w.packets - 3 : 0;
+    fi.payload_bytes = ok ? w.last_end - w.h2 : 0;
+    fi.packet_base = fi.payload_base = fi.header_base = 0;
+}
+
+VBMX_HD void oggdmx_fail_file(vbm_ogg_file_info &fi)
+{
+    fi.status = VBM_EOGG;
+    fi.pages = 0;
+    fi.serialno = 0;
+    fi.header_bytes[0] = fi.header_bytes[1] = fi.header_bytes[2] = 0;
+    fi.packets = fi.payload_bytes = 0;
+}
+
+// ---- CRC of a page: the code of ogg_mux.h over any byte run, combined by its linearity ------------------------------
+// T: the 256 entries of oggmux_crc_entry
+VBMX_HD uint32_t oggdmx_crc_run(const uint32_t *T, uint32_t crc, const uint8_t *p, int n)
+{
+    int i = 0;
+    for (; i < n && ((uintptr_t)(p + i) & 3); i++) crc = (crc << 8) ^ T[((crc >> 24) ^ p[i]) & 0xff];
+    for (; i + 4 <= n; i += 4) {
+        const uint32_t w = *(const uint32_t *)(p + i);
+        crc = (crc << 8) ^ T[((crc >> 24) ^ w) & 0xff];
+        crc = (crc << 8) ^ T[((crc >> 24) ^ (w >> 8)) & 0xff];
+        crc = (crc << 8) ^ T[((crc >> 24) ^ (w >> 16)) & 0xff];
+        crc = (crc << 8) ^ T[((crc >> 24) ^ (w >> 24)) & 0xff];
+    }
+    for (; i < n; i++) crc = (crc << 8) ^ T[((crc >> 24) ^ p[i]) & 0xff];
+    return crc;
+}
+
+// The CRC field counts as zero while the page is summed.  The code is linear, so the sum over the page as it stands
+// differs from that by the code of the four field bytes alone, moved to their place: len - 26 bytes follow them.
+// whole = the code of all len bytes of the page at h; true when the field holds the page's checksum.
+VBMX_HD bool oggdmx_crc_matches(const uint32_t *T, const OggMuxPow &pw, const uint8_t *h, int len, uint32_t whole)
+{
+    uint32_t field = 0;
+    for (int i = 22; i < 26; i++) field = (field << 8) ^ T[((field >> 24) ^ h[i]) & 0xff];
+    return (whole ^ oggmux_crc_shift(pw, field, (uint32_t)(len - 26))) == oggdmx_rd32(h + 22);
+}
+
+// ---- fill: where a page's segments and body bytes go ---------------------------------------------------------------
+struct OggDmxOut {           // the buffers of a fill call
+    uint8_t *headers, *payload;
+    long long *offsets, *granulepos;
+    uint8_t *eos;
+};
+
+struct OggDmxPageCtx {       // a page of a good file, as fill sees it
+    const uint8_t *h;        // the page
+    int nseg, flags, body_len;
+    long long granule, body_before, pkt_before;
+    long long H, E;          // end of the header packets, end of the last completed packet (body bytes of the file)
+    long long packet_base, payload_base, header_base;
+};
+
+VBMX_HD void oggdmx_page_ctx(const uint8_t *data, const OggDmxPage &pg, const vbm_ogg_file_info &fi, OggDmxPageCtx &c)
+{
+    c.h = data + pg.at;
+    c.nseg = c.h[26];
+    c.flags = c.h[5];
+    c.body_len = pg.len - 27 - c.nseg;
+    c.granule = oggdmx_rd64(c.h + 6);
+    c.body_before = pg.body_before;
+    c.pkt_before = pg.pkt_before;
+    c.H = (long long)fi.header_bytes[0] + fi.header_bytes[1] + fi.header_bytes[2];
+    c.E = c.H + fi.payload_bytes;
+    c.packet_base = fi.packet_base, c.payload_base = fi.payload_base, c.header_base = fi.header_base;
+}
+
+// A segment that ends a packet (lacing value below 255): `ends_before` packets end on the page in front of it,
+// `bytes_through` body bytes of the page lie up to its end, `last` when no later segment of the page ends a packet.
+// Packet q of the file ends here.  Audio packet k = q - 3 gets its end offset, granule position and eos; the end of
+// the third header packet is the start of audio packet 0, offsets[packet_base] = payload_base.
+VBMX_HD void oggdmx_packet_end(const OggDmxPageCtx &c, const OggDmxOut &o, int ends_before, int bytes_through, bool last)
+{
+    const long long q = c.pkt_before + ends_before;
+    if (q < 2) return;
+    o.offsets[c.packet_base + (q - 2)] = c.payload_base + (c.body_before + bytes_through - c.H);
+    if (q < 3) return;
+    o.granulepos[c.packet_base + (q - 3)] = last ? c.granule : -1;
+    o.eos[c.packet_base + (q - 3)] = ((c.flags & 4) && last) ? 1 : 0;
+}
+
+// The page's body is bytes [body_before, body_before + body_len) of the file's run: the part below H goes to the
+// headers, the part in [H, E) to the payload.  Either may be empty, and the cut may fall anywhere in the body.
+struct OggDmxSplit {
+    const uint8_t *src_h, *src_p;
+    uint8_t *dst_h, *dst_p;
+    long long n_h, n_p;
+};
+
+VBMX_HD OggDmxSplit oggdmx_body_split(const OggDmxPageCtx &c, const OggDmxOut &o)
+{
+    const uint8_t *body = c.h + 27 + c.nseg;
+    const long long a = c.body_before, b = c.body_before + c.body_len;
+    const long long he = b < c.H ? b : c.H;                        // [a, he) headers
+    const long long pa = a > c.H ? a : c.H, pe = b < c.E ? b : c.E;   // [pa, pe) payload
+    OggDmxSplit s;
+    s.n_h = he > a ? he - a : 0;
+    s.src_h = body;
+    s.dst_h = o.headers + c.header_base + a;
+    s.n_p = pe > pa ? pe - pa : 0;
+    s.src_p = body + (pa - a);
+    s.dst_p = o.payload + c.payload_base + (pa - c.H);
+    return s;
+}
+
+// dense page number -> file: the last f with page_base[f] <= p (page_base[nfiles] = pages in all, p below it)
+VBMX_HD int oggdmx_file_of_page(const long long *page_base, int nfiles, long long p)
+{
+    int lo = 0, hi = nfiles - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (page_base[mid] <= p) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+VBMX_HD long long oggdmx_first_slot(const long long *off, int f) { return (off[f] - off[0]) / 27; }

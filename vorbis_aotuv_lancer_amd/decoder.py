@@ -355,28 +355,43 @@ class OggIndex:
         self.setup.close()
 
 
-def decode_ogg(files, max_packets=4096, halfrate=False):
+def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False):
     """.ogg files (bytes or paths), one logical stream each -> [(pcm float32 [channels, n] contiguous on the current
     device, rate)], one per file.  Files whose identification and setup headers are byte-equal share one DecodeSetup
     and Decoder, one stream per file; their packets go through synthesis_runs in calls of at most max_packets rows.
     Packets that fail to decode are skipped (as the reference's decoder_example.c skips them).  halfrate=True: half as
     many samples per file, and the rate returned is the output rate, half the file's (ov_halfrate).  Waits for the
-    device once, at the end, to place the outputs."""
-    from .stream import demux_ogg
+    device once, at the end, to place the outputs.  device_demux=True: the files are demuxed together on the device
+    (stream.DeviceDemuxer) instead of one by one on the host; the packet bytes then never leave the device, the offsets,
+    granule positions and eos flags are read back once to plan the calls, and the PCM is the same bit for bit."""
+    from .stream import demux_ogg, demux_ogg_device
     if max_packets <= 0:
         raise ValueError("max_packets must be positive")
     dev = torch.device("cuda", torch.cuda.current_device())
     names, demuxed, groups = [], [], {}
-    for i, f in enumerate(files):
-        names.append(os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}")
-        if isinstance(f, (str, os.PathLike)):
-            with open(f, "rb") as fh:
-                f = fh.read()
-        try:
-            d = demux_ogg(f)
-        except VbmError as e:
-            raise VbmError(f"{names[i]}: {e}") from None
-        demuxed.append(d)
+    if device_demux:
+        b = demux_ogg_device(files)
+        names = b.names
+        offsets = b.offsets.cpu().numpy()
+        for i in range(len(b)):
+            if b.status[i]:
+                raise VbmError(f"{names[i]}: vbm_ogg_demux_scan failed with code {b.status[i]}: not one valid logical "
+                               "Ogg stream (vbm_ogg_demux on the file alone names the page)")
+            a, n, at = int(b.packet_base[i]), int(b.packets[i]), int(b.payload_base[i])
+            # (headers, data, offsets, granulepos, eos) as demux_ogg's, data / granulepos / eos left on the device
+            demuxed.append((b.headers[i], b.payload[at:at + int(b.payload_bytes[i])], offsets[a:a + n + 1] - at,
+                            b.granulepos[a:a + n], b.eos[a:a + n]))
+    else:
+        for i, f in enumerate(files):
+            names.append(os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}")
+            if isinstance(f, (str, os.PathLike)):
+                with open(f, "rb") as fh:
+                    f = fh.read()
+            try:
+                demuxed.append(demux_ogg(f))
+            except VbmError as e:
+                raise VbmError(f"{names[i]}: {e}") from None
+    for i, d in enumerate(demuxed):
         groups.setdefault((d[0][0], d[0][2]), []).append(i)
     for members in groups.values():                       # every setup is checked before any work is enqueued
         rc = DecodeSetup.status(demuxed[members[0]][0])
@@ -390,8 +405,8 @@ def decode_ogg(files, max_packets=4096, halfrate=False):
         dec = Decoder(ds, len(members), max_packets, halfrate=halfrate)
         keep.append((ds, dec))
         half = dec.row
-        src = [(torch.from_numpy(demuxed[j][1]).to(dev), demuxed[j][2], torch.from_numpy(demuxed[j][3]).to(dev),
-                torch.from_numpy(demuxed[j][4]).to(dev)) for j in members]
+        up = (lambda x: x) if device_demux else (lambda x: torch.from_numpy(x).to(dev))
+        src = [(up(demuxed[j][1]), demuxed[j][2], up(demuxed[j][3]), up(demuxed[j][4])) for j in members]
         pos = [0] * len(members)
         while True:
             live = [s for s in range(len(members)) if pos[s] < len(src[s][1]) - 1]

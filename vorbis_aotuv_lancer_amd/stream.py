@@ -297,3 +297,152 @@ def demux_ogg(data):
     h = hdr.tobytes()
     headers = [h[:sizes[0]], h[sizes[0]:sizes[0] + sizes[1]], h[sizes[0] + sizes[1]:sizes[0] + sizes[1] + sizes[2]]]
     return headers, body, offsets, gp, eos
+
+
+FILE_INFO = np.dtype([("status", "<i4"), ("pages", "<i4"), ("serialno", "<u4"), ("header_bytes", "<i4", (3,)),
+                      ("packets", "<i8"), ("payload_bytes", "<i8"), ("packet_base", "<i8"), ("payload_base", "<i8"),
+                      ("header_base", "<i8")])       # vbm_ogg_file_info
+
+
+def _read_files(files):
+    """bytes or paths -> (names, [bytes])"""
+    import os
+    names, blobs = [], []
+    for i, f in enumerate(files):
+        names.append(os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}")
+        if isinstance(f, (str, os.PathLike)):
+            with open(f, "rb") as fh:
+                f = fh.read()
+        blobs.append(bytes(f))
+    return names, blobs
+
+
+class DemuxBatch:
+    """What DeviceDemuxer.demux returns.  Per file f: status[f] (0 or VBM_EOGG), headers[f] ([3 packets] as bytes, None
+    for a failed file), names[f], and info[f] (FILE_INFO: vbm_ogg_file_info).  For the batch: payload uint8 [bytes],
+    offsets int64 [P + 1], granulepos int64 [P], eos uint8 [P] — torch tensors on the device (numpy arrays with
+    host=True) holding ONE CSR over the audio packets of all good files: packet k of file f is
+    payload[offsets[packet_base[f] + k]:offsets[packet_base[f] + k + 1]], with packets[f] of them.  runs(f) is that
+    file's slice in the form Decoder.synthesis_runs takes."""
+
+    def __init__(self, names, info, headers, payload, offsets, granulepos, eos):
+        self.names, self.info, self.headers = names, info, headers
+        self.payload, self.offsets, self.granulepos, self.eos = payload, offsets, granulepos, eos
+        self.status = info["status"].tolist()
+        self.packets, self.packet_base = info["packets"], info["packet_base"]
+        self.payload_bytes, self.payload_base = info["payload_bytes"], info["payload_base"]
+
+    def __len__(self):
+        return len(self.status)
+
+    def runs(self, f):
+        """-> (offsets [packets[f] + 1] as they stand (they index the whole payload), granulepos, eos) of file f"""
+        a, n = int(self.packet_base[f]), int(self.packets[f])
+        return self.offsets[a:a + n + 1], self.granulepos[a:a + n], self.eos[a:a + n]
+
+
+class DeviceDemuxer:
+    """vbm_ogg_demux for many whole .ogg files per call, on the device (vbm_ogg_demux_scan / _fill): up to max_files
+    files of up to max_bytes bytes together per demux() call.
+
+        dm = DeviceDemuxer(len(files), sum(map(len, files)))
+        b = dm.demux(files)                       # one H2D of the files, scan, a small D2H, fill, one D2H of the headers
+        pcm, n, _, _ = dec.synthesis_runs([0], [b.packets[0]], b.payload, *b.runs(0))
+
+    host=True runs the CPU twin on numpy arrays (no GPU needed).  A failed file (status VBM_EOGG) adds nothing to the
+    batch and raises nothing here."""
+
+    EOGG = -1002
+
+    def __init__(self, max_files, max_bytes, host=False, device=None):
+        self.max_files, self.max_bytes, self.host = int(max_files), int(max_bytes), bool(host)
+        self._h = C.c_void_p()
+        self.device = None
+        if host:
+            check(lib.vbm_host_ogg_demuxer_create(C.byref(self._h), self.max_files, self.max_bytes),
+                  "vbm_host_ogg_demuxer_create")
+        else:
+            import torch
+            self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+            with torch.cuda.device(self.device):
+                check(lib.vbm_ogg_demuxer_create(C.byref(self._h), self.max_files, self.max_bytes),
+                      "vbm_ogg_demuxer_create")
+
+    def demux(self, files):
+        names, blobs = _read_files(files)
+        n = len(blobs)
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum([len(b) for b in blobs], out=off[1:])
+        raw = np.frombuffer(b"".join(blobs), np.uint8)
+        info = np.zeros(n, FILE_INFO)
+        totals = np.zeros(3, np.int64)
+        if self.host:
+            check(lib.vbm_host_ogg_demux_scan(self._h, n, raw.ctypes.data if len(raw) else None, off.ctypes.data,
+                                              info.ctypes.data if n else None, totals.ctypes.data),
+                  "vbm_host_ogg_demux_scan")
+            P, B, H = (int(x) for x in totals)
+            hdr, payload = np.zeros(H, np.uint8), np.zeros(B, np.uint8)
+            offsets, gp, eos = np.zeros(P + 1, np.int64), np.zeros(P, np.int64), np.zeros(P, np.uint8)
+            check(lib.vbm_host_ogg_demux_fill(self._h, hdr.ctypes.data if H else None, H, payload.ctypes.data if B else None,
+                                              B, offsets.ctypes.data, gp.ctypes.data if P else None,
+                                              eos.ctypes.data if P else None, P), "vbm_host_ogg_demux_fill")
+            st = C.c_int(-1)
+            check(lib.vbm_ogg_demux_status(self._h, C.byref(st), None), "vbm_ogg_demux_status")
+            h = hdr.tobytes()
+        else:
+            import torch
+            dev = self.device
+            q = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            d_raw = torch.from_numpy(raw.copy()).to(dev) if len(raw) else torch.empty(0, dtype=torch.uint8, device=dev)
+            # info and totals in one buffer: one small D2H
+            d_meta = torch.empty(n * FILE_INFO.itemsize + 24, dtype=torch.uint8, device=dev)
+            check(lib.vbm_ogg_demux_scan(self._h, n, d_raw.data_ptr() if len(raw) else None, off.ctypes.data,
+                                         d_meta.data_ptr() + 24 if n else None, d_meta.data_ptr(), q), "vbm_ogg_demux_scan")
+            meta = d_meta.cpu().numpy()
+            totals, info = meta[:24].view(np.int64), meta[24:].view(FILE_INFO)
+            P, B, H = (int(x) for x in totals)
+            d_hdr = torch.empty(H, dtype=torch.uint8, device=dev)
+            payload = torch.empty(B, dtype=torch.uint8, device=dev)
+            offsets = torch.empty(P + 1, dtype=torch.int64, device=dev)
+            gp = torch.empty(P, dtype=torch.int64, device=dev)
+            eos = torch.empty(P, dtype=torch.uint8, device=dev)
+            check(lib.vbm_ogg_demux_fill(self._h, d_hdr.data_ptr() if H else None, H, payload.data_ptr() if B else None, B,
+                                         offsets.data_ptr(), gp.data_ptr() if P else None, eos.data_ptr() if P else None, P,
+                                         q), "vbm_ogg_demux_fill")
+            h = d_hdr.cpu().numpy().tobytes()              # waits for the fill: d_raw is free after it
+            st = C.c_int(-1)
+            check(lib.vbm_ogg_demux_status(self._h, C.byref(st), q), "vbm_ogg_demux_status")
+        if st.value:
+            raise VbmError(f"vbm_ogg_demux_fill: status {st.value} with buffers of the sizes the scan returned")
+        headers = []
+        for f in range(n):
+            if info["status"][f]:
+                headers.append(None)
+                continue
+            a, hb = int(info["header_base"][f]), info["header_bytes"][f]
+            headers.append([h[a:a + hb[0]], h[a + hb[0]:a + hb[0] + hb[1]], h[a + hb[0] + hb[1]:a + hb[0] + hb[1] + hb[2]]])
+        return DemuxBatch(names, info, headers, payload, offsets, gp, eos)
+
+    def close(self):
+        if self._h:
+            if not self.host:
+                import torch
+                torch.cuda.synchronize(self.device)
+            lib.vbm_ogg_demuxer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def demux_ogg_device(files, host=False):
+    """.ogg files (bytes or paths) -> DemuxBatch, through a DeviceDemuxer made for them (host=True: its CPU twin)."""
+    names, blobs = _read_files(files)
+    dm = DeviceDemuxer(max(1, len(blobs)), sum(len(b) for b in blobs), host=host)
+    try:
+        return dm.demux(blobs)
+    finally:
+        dm.close()
