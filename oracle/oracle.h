@@ -69,6 +69,7 @@ typedef struct {
 void orc_mdct_init(orc_mdct *m, int n);
 void orc_mdct_clear(orc_mdct *m);
 void orc_mdct_forward(const orc_mdct *m, const float *in, float *out);
+void orc_mdct_backward(const orc_mdct *m, const float *in, float *out);   /* n/2 bins -> n floats */
 void orc_mdct_butterflies(const orc_mdct *m, float *x, int points);
 void orc_mdct_bitreverse(const orc_mdct *m, float *w);
 

@@ -5,6 +5,8 @@
  *   forward          lib/mdct.c:1799-1869               (mdct_forward, !__SSE__ branch)
  *   butterflies      lib/mdct.c:1105-1135, 854-894, 1032-1079, 602-658, 495-528, 432-452
  *   bit reverse      lib/mdct.c:1228-1272
+ * and of its scalar inverse (test yardstick for the device decoder's PCM):
+ *   backward         lib/mdct.c:1537-1626               (mdct_backward, !__SSE__ branch)
  *
  * Every float expression keeps the reference's shape (two rounded products,
  * one rounded sum; no FMA — compile with -ffp-contract=off).  The structure is
@@ -254,6 +256,53 @@ void orc_mdct_forward(const orc_mdct *m, const float *in, float *out)
         for (i = 0; i < n4; i++) {
             out[i]          = (w[2 * i] * T[2 * i] + w[2 * i + 1] * T[2 * i + 1]) * m->scale;
             out[n2 - 1 - i] = (w[2 * i] * T[2 * i + 1] - w[2 * i + 1] * T[2 * i]) * m->scale;
+        }
+    }
+    free(w);
+}
+
+/* n/2 bins in, n floats out.  The reference works in place in `out`; here the butterflies run
+ * in a buffer of their own, which changes no float operation. */
+void orc_mdct_backward(const orc_mdct *m, const float *in, float *out)
+{
+    int n = m->n, n2 = n >> 1, n4 = n >> 2, n8 = n >> 3;
+    float *w = (float *)malloc(sizeof(float) * n);
+    float *w2 = w + n2;
+    int q, u;
+
+    /* first rotation, lib/mdct.c:1540-1552: odd bins from the top down, trig upwards from n/4;
+     * step q fills complex element n/8-1-q of the butterflies' input */
+    for (q = 0; q < n8; q++) {
+        const float *x = in + n2 - 1 - 4 * q;
+        const float *T = m->trig + n4 + 2 * q;
+        float *o = w2 + 2 * (n8 - 1 - q);
+        o[0] = -x[0] * T[1] - x[-2] * T[0];
+        o[1] = x[-2] * T[1] - x[0] * T[0];
+    }
+    /* lib/mdct.c:1554-1566: even bins from the top down, trig downwards from n/4;
+     * step q fills complex element n/8+q */
+    for (q = 0; q < n8; q++) {
+        const float *x = in + n2 - 4 - 4 * q;
+        const float *T = m->trig + n4 - 2 - 2 * q;
+        float *o = w2 + 2 * (n8 + q);
+        o[0] = x[0] * T[1] + x[2] * T[0];
+        o[1] = x[0] * T[0] - x[2] * T[1];
+    }
+
+    orc_mdct_butterflies(m, w2, n2);
+    orc_mdct_bitreverse(m, w);
+
+    /* second rotation, lib/mdct.c:1573-1597, and the unfold, lib/mdct.c:1599-1625: pair u
+     * gives one value mirrored with a sign change about n/4 and one mirrored about 3n/4 */
+    {
+        const float *T = m->trig + n2;
+        for (u = 0; u < n4; u++) {
+            float a = w[2 * u] * T[2 * u + 1] - w[2 * u + 1] * T[2 * u];
+            float b = -(w[2 * u] * T[2 * u] + w[2 * u + 1] * T[2 * u + 1]);
+            out[n4 - 1 - u] = a;
+            out[n4 + u] = -a;
+            out[n2 + n4 - 1 - u] = b;
+            out[n2 + n4 + u] = b;
         }
     }
     free(w);

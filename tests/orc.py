@@ -41,6 +41,17 @@ class Oracle:
             self.lib.orc_mdct_forward(C.byref(m), _p(flat[i]), _p(out[i]))
         return out.reshape(x.shape[:-1] + (n // 2,))
 
+    def mdct_backward(self, x):
+        """x: (..., n/2) float32 -> (..., n)"""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = 2 * x.shape[-1]
+        m = self.mdct_lookup(n)
+        flat = x.reshape(-1, n // 2)
+        out = np.empty((flat.shape[0], n), np.float32)
+        for i in range(flat.shape[0]):
+            self.lib.orc_mdct_backward(C.byref(m), _p(flat[i]), _p(out[i]))
+        return out.reshape(x.shape[:-1] + (n,))
+
     def apply_window(self, x, win_l, win_r):
         """in-place copy: x (..., n); win_l / win_r rising half windows (their length*2 = ln/rn)"""
         x = np.array(x, dtype=np.float32, copy=True)

@@ -1,6 +1,7 @@
 """Half-rate decoding on the MI355X (Decoder(..., halfrate=True); the reference's vorbis_synthesis_halfrate): PCM of
 every block-size pair and of a real stream within the project's bound of a float64 reference — IMDCT of half the block
-size over the lower half of the float32 spectrum, the Vorbis window of half the size in float64, overlap-add — batches
+size over the lower half of the float32 spectrum, the Vorbis window of half the size in float64, overlap-add — and bit
+for bit against the oracle's scalar inverse MDCT of that size + float32 overlap-add (check_pcm_exact), batches
 that do not fill the 128-point transform's groups, runs and ranges bit for bit against the stepwise half-rate decode,
 and a full-rate and a half-rate decoder side by side."""
 import functools
@@ -13,7 +14,7 @@ import torch
 from tests import vorbis_model as vm
 from tests.test_decode_ranges_gpu import as_stream, check, ranges
 from tests.test_decode_runs_gpu import runs_call
-from tests.test_decoder_gpu import rows_tensor, split_dump
+from tests.test_decoder_gpu import check_pcm_exact, rows_tensor, split_dump
 from tests.test_decoder_model_cpu import fromdB
 from tests.test_decoder_synthetic_gpu import RUNS, with_failed_packets
 
@@ -112,6 +113,12 @@ def model_steps(v, ds, model, streams, cuda):
     return spec_steps, W_steps, pcm_steps, samples_steps
 
 
+def exact_halfrate(oracle, ds, streams, spec_steps, W_steps, pcm_steps, samples_steps):
+    """check_pcm_exact at half rate on the step lists of this file -> steps x streams compared"""
+    info_steps = [[(0, int(W)) for W in row] for row in W_steps]
+    return check_pcm_exact(oracle, ds, streams, pcm_steps, spec_steps, info_steps, samples_steps, halfrate=True)
+
+
 def assert_samples_equal_the_index(v, ds, streams, samples_steps):
     totals = []
     for s, pk in enumerate(streams):
@@ -124,7 +131,7 @@ def assert_samples_equal_the_index(v, ds, streams, samples_steps):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("k", range(15), ids=PAIR_IDS)
-def test_halfrate_pcm_of_every_block_size_pair_is_within_the_bound(cuda, k):
+def test_halfrate_pcm_of_every_block_size_pair_is_within_the_bound(oracle, cuda, k):
     """Transforms of 128 .. 2048 points, every block-size transition at each; the last packet is trimmed by its
     granule position (37 full-rate samples: 18 output samples).
     Measured on MI355X, max |pcm - float64 reference| / peak over the 15 pairs: see DESIGN.md §9c."""
@@ -147,13 +154,15 @@ def test_halfrate_pcm_of_every_block_size_pair_is_within_the_bound(cuda, k):
     assert min(peaks) >= 1e-3, min(peaks)
     print(f"\nhalf rate, block sizes {PAIR_IDS[k]}, {ds.channels} ch: max |pcm - float64 reference| / peak = "
           f"{worst:.3g} (peaks {min(peaks):.3g} .. {max(peaks):.3g})")
+    exact = exact_halfrate(oracle, ds, streams, spec_steps, W_steps, pcm_steps, samples_steps)
+    print(f"half rate, block sizes {PAIR_IDS[k]}: {exact} steps x streams equal the scalar inverse MDCT bit for bit")
     ds.close()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("bs,nshort,nlong", [((256, 2048), 3, 5), ((256, 2048), 5, 3), ((256, 256), 3, 0),
                                              ((256, 256), 5, 0)])
-def test_halfrate_batches_that_do_not_fill_the_imdct_groups(cuda, bs, nshort, nlong):
+def test_halfrate_batches_that_do_not_fill_the_imdct_groups(oracle, cuda, bs, nshort, nlong):
     """7 channels: 3 or 5 rows of a block size are 21 or 35 blocks, no multiple of the 16 blocks a wavefront takes at
     128 points (or of the 2 at 1024); both block sizes in one call"""
     import vorbis_aotuv_lancer_amd as v
@@ -173,6 +182,8 @@ def test_halfrate_batches_that_do_not_fill_the_imdct_groups(cuda, bs, nshort, nl
     assert min(peaks) >= 1e-3
     print(f"\nhalf rate, 7 ch {bs}, {nshort} short + {nlong} long rows: max |pcm - float64 reference| / peak = "
           f"{worst:.3g}")
+    exact = exact_halfrate(oracle, ds, streams, spec_steps, W_steps, pcm_steps, samples_steps)
+    print(f"half rate, 7 ch {bs}: {exact} steps x streams equal the scalar inverse MDCT bit for bit")
     ds.close()
 
 
@@ -295,7 +306,7 @@ def test_halfrate_runs_and_ranges_equal_the_stepwise_decode(cuda, name, k):
 
 
 @pytest.mark.gpu
-def test_halfrate_of_a_real_stream(cuda):
+def test_halfrate_of_a_real_stream(oracle, cuda):
     """the first 200 packets of the reference encoder's 44.1 kHz stereo q5 dump as four streams of 50; the float64
     reference is built from the spectrum a full-rate decoder fetches for the same packets"""
     import vorbis_aotuv_lancer_amd as v
@@ -306,11 +317,12 @@ def test_halfrate_of_a_real_stream(cuda):
     full = v.Decoder(ds, S, S)
     half = v.Decoder(ds, S, S, halfrate=True)
     assert (full.rate, half.rate) == (44100, 22050) and isinstance(half.rate, int)
-    spec_steps, W_steps, pcm_steps, samples_steps, full_samples = [], [], [], [], []
+    spec_steps, W_steps, pcm_steps, samples_steps, full_samples, full_pcm = [], [], [], [], [], []
     for t in range(T):
         pk, nb = rows_tensor([streams[s][t][0] for s in range(S)], cuda)
-        _, fs, st = full.synthesis_batch(list(range(S)), pk, nb)
+        fp, fs, st = full.synthesis_batch(list(range(S)), pk, nb)
         assert not st.cpu().numpy().any()
+        full_pcm.append(fp.cpu().numpy())
         spec_steps.append(full.fetch("spectrum").cpu().numpy())
         W_steps.append(full.fetch("info").cpu().numpy()[:, 1])
         full_samples.append(fs.cpu().numpy())
@@ -325,6 +337,12 @@ def test_halfrate_of_a_real_stream(cuda):
     worst = check_halfrate_bound(ds.blocksizes, 2, [T] * S, spec_steps, W_steps, pcm_steps, samples_steps, peaks)
     print(f"\nhalf rate, 2ch 44100 q0.5 reference stream: max |pcm - float64 reference| / peak = {worst:.3g} "
           f"(peaks {min(peaks):.3g} .. {max(peaks):.3g})")
+    exact = exact_halfrate(oracle, ds, streams, spec_steps, W_steps, pcm_steps, samples_steps)
+    # the full-rate decoder beside it, on the same packets and spectra
+    info_steps = [[(0, int(W)) for W in row] for row in W_steps]
+    exact_full = check_pcm_exact(oracle, ds, streams, full_pcm, spec_steps, info_steps, full_samples)
+    print(f"reference stream: {exact} steps x streams at half rate and {exact_full} at full rate equal the scalar inverse "
+          f"MDCT bit for bit")
     full.close()
     half.close()
     ds.close()

@@ -1,6 +1,7 @@
 """Decoder on the MI355X: device unpack = host unpack bit for bit, spectrum exact against a float32 restatement of the
-oracle's captures, PCM within a bound of a float64 IMDCT + window + overlap-add, the reference's own round-trip test
-(test/test.c), a full-size batch, and the API edges."""
+oracle's captures, PCM within a bound of a float64 IMDCT + window + overlap-add and bit for bit against the oracle's
+scalar inverse MDCT + float32 window + overlap-add, the reference's own round-trip test (test/test.c), a full-size
+batch, and the API edges."""
 import functools
 import glob
 import os
@@ -103,12 +104,31 @@ def test_device_unpack_equals_host_unpack(oracle, cuda, pack):
     (2, 44100, 0.5, "ref_scalar_2ch_44100_q05_20s.pkt"),
     (6, 48000, 0.8, "ref_scalar_6ch_48000_q08_10s.pkt"),
 ])
-def test_device_unpack_of_the_reference_dumps(cuda, ch, rate, q, golden):
+def test_device_unpack_of_the_reference_dumps(oracle, cuda, ch, rate, q, golden):
     import vorbis_aotuv_lancer_amd as v
     ds = v.DecodeSetup(v.header_packets(v.Setup(ch, rate, q)))
     packets = split_dump(open(os.path.join(G, golden), "rb").read())
     dec = v.Decoder(ds, len(packets), len(packets))
     device_vs_host(ds, dec, packets, cuda)
+    dec.close()
+    # the first 200 packets as four streams of 50 consecutive ones, decoded stepwise: PCM bounded and exact
+    S, T = 4, 50
+    dec = v.Decoder(ds, S, S)
+    pcm_steps, spec_steps, info_steps, samples_steps = [], [], [], []
+    for t in range(T):
+        pk, nb = rows_tensor([packets[s * T + t] for s in range(S)], cuda)
+        pcm, samples, status = dec.synthesis_batch(list(range(S)), pk, nb)
+        assert not status.cpu().numpy().any()
+        pcm_steps.append(pcm.cpu().numpy())
+        spec_steps.append(dec.fetch("spectrum").cpu().numpy())
+        info_steps.append(dec.fetch("info").cpu().numpy())
+        samples_steps.append(samples.cpu().numpy())
+    assert {int(i[1]) for step in info_steps for i in step} == {0, 1}      # both block sizes
+    streams = [list(range(T))] * S
+    worst = check_pcm_bound(ds, streams, pcm_steps, spec_steps, info_steps, samples_steps)
+    exact = check_pcm_exact(oracle, ds, streams, pcm_steps, spec_steps, info_steps, samples_steps)
+    print(f"\n{golden}: max |pcm - float64 reference| / peak = {worst:.3g}; {exact} steps x streams equal the scalar "
+          f"inverse MDCT bit for bit")
     dec.close()
     ds.close()
 
@@ -201,6 +221,79 @@ def check_pcm_bound(ds, streams_pk, pcm_steps, spec_steps, info_steps, samples_s
     return worst
 
 
+def overlap32(tail, lW, p, W, n0, n1, w0, w1):
+    """overlap64 in float32: numpy rounds each product and the sum separately, as vorbis_synthesis_blockin's scalar
+    pcm[i]*w[n-i-1] + p[i]*w[i] does with contraction off.  n0 / n1: half the two block sizes (a quarter at half
+    rate), w0 / w1 the rising half windows of those lengths"""
+    n = n1 if W else n0
+    if lW < 0:
+        return np.zeros(0, np.float32), p[n:2 * n].copy()
+    if lW == 1 and W == 1:
+        out = tail[:n1] * w1[::-1] + p[:n1] * w1
+    elif lW == 1:
+        off = n1 // 2 - n0 // 2
+        out = np.concatenate([tail[:off], tail[off:off + n0] * w0[::-1] + p[:n0] * w0])
+    elif W == 1:
+        off = n1 // 2 - n0 // 2
+        out = np.concatenate([tail[:n0] * w0[::-1] + p[off:off + n0] * w0, p[off + n0:off + n0 + off]])
+    else:
+        out = tail[:n0] * w0[::-1] + p[:n0] * w0
+    assert out.dtype == np.float32
+    return out, p[n:2 * n].copy()
+
+
+def ulps_apart(a, b):
+    """distance of two float32 values in representable values (-0.0 and 0.0 are 0 apart)"""
+    def key(x):
+        i = int(np.array(x, np.float32).view(np.int32))
+        return i if i >= 0 else -(i & 0x7fffffff)
+    return abs(key(a) - key(b))
+
+
+def check_pcm_exact(oracle, ds, streams_pk, pcm_steps, spec_steps, info_steps, samples_steps, halfrate=False):
+    """check_pcm_bound's walk with a float32 yardstick and no tolerance: the device PCM of every step, stream and
+    channel equals (np.array_equal) the oracle's scalar inverse MDCT (oracle/orc_mdct.c: orc_mdct_backward, itself
+    checked against the float64 definition in tests/test_oracle_mdct.py) of the float32 spectrum, overlap-added in
+    float32 with the product's own window tables, the tail carried in float32.  At half rate the transform has half the
+    block's points over the lower half of the bins, and the windows are those of half the size.
+    -> the number of (step, stream) pairs compared"""
+    import vorbis_aotuv_lancer_amd as v
+    bs = ds.blocksizes
+    hs = 1 if halfrate else 0
+    n0, n1 = bs[0] >> (1 + hs), bs[1] >> (1 + hs)
+    w0, w1 = v.window_table(bs[0] >> hs), v.window_table(bs[1] >> hs)
+    assert w0.dtype == np.float32 and w1.dtype == np.float32 and (len(w0), len(w1)) == (n0, n1)
+    compared = 0
+    for s in range(len(streams_pk)):
+        tail, lW = None, -1
+        for t in range(len(streams_pk[s])):
+            W = int(info_steps[t][s][1])
+            N = bs[W] >> hs                                            # points of the transform
+            spec = np.stack([np.asarray(spec_steps[t][s][c][:N // 2], np.float32) for c in range(ds.channels)])
+            p = oracle.mdct_backward(spec)
+            outs, tails = [], []
+            for c in range(ds.channels):
+                o, tl = overlap32(tail[c] if tail is not None else None, lW, p[c], W, n0, n1, w0, w1)
+                outs.append(o)
+                tails.append(tl)
+            tail, lW = tails, W
+            want = np.stack(outs)
+            ns = int(samples_steps[t][s])
+            last = t == len(streams_pk[s]) - 1
+            assert ns == want.shape[1] or (last and ns < want.shape[1]), (s, t, ns, want.shape[1])
+            want = want[:, :ns]
+            got = pcm_steps[t][s][:, :ns]
+            assert got.dtype == np.float32 and want.dtype == np.float32
+            if not np.array_equal(got, want):
+                c, i = (int(x[0]) for x in np.nonzero(got != want))
+                raise AssertionError(
+                    f"stream {s} step {t} channel {c} sample {i} (block of {bs[W]}, after {'none' if lW < 0 else bs[lW]}"
+                    f"{', half rate' if hs else ''}): device {float(got[c, i]):.9g}, scalar inverse MDCT {float(want[c, i]):.9g}, "
+                    f"{ulps_apart(got[c, i], want[c, i])} ulps apart; {int((got != want).sum())} of {got.size} differ")
+            compared += 1 if ns else 0
+    return compared
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("ch,rate,q", PARITY)
 def test_spectrum_exact_and_pcm_bounded(oracle, cuda, ch, rate, q):
@@ -234,6 +327,8 @@ def test_spectrum_exact_and_pcm_bounded(oracle, cuda, ch, rate, q):
         samples_steps.append(samples.cpu().numpy())
     worst = check_pcm_bound(ds, [list(range(steps))] * S, pcm_steps, spec_steps, info_steps, samples_steps)
     print(f"\n{ch}ch {rate} q{q}: max |pcm - float64 reference| / peak = {worst:.3g}")
+    exact = check_pcm_exact(oracle, ds, [list(range(steps))] * S, pcm_steps, spec_steps, info_steps, samples_steps)
+    print(f"{ch}ch {rate} q{q}: {exact} steps x streams equal the scalar inverse MDCT bit for bit")
     dec.close()
     ds.close()
 
@@ -401,6 +496,8 @@ def test_full_size_twins_unsynchronised_steps(oracle, cuda):
     assert (total == nchunks * 1024).all(), total
     worst = check_pcm_bound(ds, [lead[k] for k in range(K)], pcm_steps, spec_steps, info_steps, samples_steps)
     print(f"\nfull size: max |pcm - float64 reference| / peak = {worst:.3g}")
+    exact = check_pcm_exact(oracle, ds, [lead[k] for k in range(K)], pcm_steps, spec_steps, info_steps, samples_steps)
+    print(f"full size: {exact} steps x streams equal the scalar inverse MDCT bit for bit")
     dec.close()
     ds.close()
 

@@ -1,7 +1,9 @@
 """The device decoder on streams this project's encoder never writes: unpack and spectrum bit for bit against the
 independent model (tests/vorbis_model.py) on the generated corpus, PCM of every block-size pair within the project's
 bound of a float64 IMDCT + float64 Vorbis window + overlap-add, the runs and ranges paths against the stepwise one on
-synthetic setups, and batches whose row x channel counts do not fill the IMDCT kernels' groups."""
+synthetic setups, and batches whose row x channel counts do not fill the IMDCT kernels' groups.  The PCM of the
+block-size pairs, of those batches and of one mono stream alone is also compared bit for bit with the oracle's scalar
+inverse MDCT (tests/test_decoder_gpu.py: check_pcm_exact)."""
 import numpy as np
 import pytest
 import torch
@@ -9,7 +11,7 @@ import torch
 from tests import vorbis_model as vm
 from tests.test_decode_ranges_gpu import as_stream, check, ranges
 from tests.test_decode_runs_gpu import runs_call, stepwise
-from tests.test_decoder_gpu import check_pcm_bound, rows_tensor
+from tests.test_decoder_gpu import check_pcm_bound, check_pcm_exact, rows_tensor
 from tests.test_decoder_model_cpu import NAMES, family, fromdB
 
 PAIR_IDS = [f"{a}_{b}" for a, b in vm.PAIRS]
@@ -73,11 +75,12 @@ def decode_steps(v, ds, model, streams, cuda, what):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("k", range(15), ids=PAIR_IDS)
-def test_pcm_of_every_block_size_pair_is_within_the_bound(cuda, k):
+def test_pcm_of_every_block_size_pair_is_within_the_bound(oracle, cuda, k):
     """Streams whose block-size sequence has every transition; stream 1's lW / nW bits contradict its neighbours (the
     decoder must go by the real previous block); the last packet is trimmed by its granule position.  The reference
     overlap-add uses the Vorbis window in float64, not the product's table.  Bound: the project's 1e-5 of the step's
-    float64 peak; every peak is >= 1e-3, so the bound's floor never applies."""
+    float64 peak; every peak is >= 1e-3, so the bound's floor never applies.  The same steps equal the oracle's scalar
+    inverse MDCT + float32 overlap-add with the product's window tables bit for bit (check_pcm_exact)."""
     import vorbis_aotuv_lancer_amd as v
     setup, coding = vm.pcm_setup(k)
     h = vm.pack_headers(setup, coding)
@@ -100,6 +103,8 @@ def test_pcm_of_every_block_size_pair_is_within_the_bound(cuda, k):
     assert min(peaks) >= 1e-3, min(peaks)
     print(f"\nblock sizes {PAIR_IDS[k]}, {ds.channels} ch: max |pcm - float64 reference| / peak = {worst:.3g} "
           f"(peaks {min(peaks):.3g} .. {max(peaks):.3g})")
+    exact = check_pcm_exact(oracle, ds, streams, *steps)
+    print(f"block sizes {PAIR_IDS[k]}: {exact} steps x streams equal the scalar inverse MDCT bit for bit")
     ds.close()
 
 
@@ -177,7 +182,7 @@ def test_runs_and_ranges_equal_the_stepwise_decode(cuda, name, k):
 @pytest.mark.gpu
 @pytest.mark.parametrize("bs,nshort,nlong", [((256, 1024), 3, 5), ((512, 2048), 5, 3), ((256, 512), 5, 3),
                                              ((1024, 1024), 3, 0)])
-def test_batches_that_do_not_fill_the_imdct_groups(cuda, bs, nshort, nlong):
+def test_batches_that_do_not_fill_the_imdct_groups(oracle, cuda, bs, nshort, nlong):
     """7 channels: 3 or 5 rows of a block size are 21 or 35 blocks, no multiple of the 8 / 4 / 2 blocks a wavefront
     takes at 256 / 512 / 1024; both block sizes in one call"""
     import vorbis_aotuv_lancer_amd as v
@@ -194,4 +199,48 @@ def test_batches_that_do_not_fill_the_imdct_groups(cuda, bs, nshort, nlong):
     worst = check_pcm_bound(ds, streams, *steps, win=win, peaks=peaks)
     assert min(peaks) >= 1e-3
     print(f"\n7 ch {bs}, {nshort} short + {nlong} long rows: max |pcm - float64 reference| / peak = {worst:.3g}")
+    exact = check_pcm_exact(oracle, ds, streams, *steps)
+    print(f"7 ch {bs}: {exact} steps x streams equal the scalar inverse MDCT bit for bit")
+    ds.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("halfrate", [False, True], ids=["full", "half"])
+@pytest.mark.parametrize("bs", [(256, 2048), (512, 4096)], ids=["256_2048", "512_4096"])
+def test_one_mono_stream_alone_equals_the_scalar_inverse_mdct(oracle, cuda, bs, halfrate):
+    """the smallest launch: one mono stream, so one block per call.  The wavefront group of k_imdct holds 1 of its
+    16 / 8 / 4 / 2 / 1 blocks and every other slot takes the zero path.  A sequence with all four transitions, decoded
+    stepwise, bit for bit against the scalar inverse MDCT + float32 overlap-add"""
+    import vorbis_aotuv_lancer_amd as v
+    setup, coding = vm.gen_setup(4000 + bs[0] + bs[1], ch=1, bs=bs, res_types=(1, 2), min_exp=0,
+                                 res_kw=dict(bad_classwords=False, masks=[1, 3, 7]))
+    ds = v.DecodeSetup(vm.pack_headers(setup, coding))
+    assert tuple(ds.blocksizes) == bs and ds.channels == 1
+    model = vm.Model(setup, fromdB())
+    streams = vm.pcm_streams(model, 41, sequences=[vm.SEQUENCES[0]])
+    assert len(streams) == 1
+    S, T = 1, len(streams[0])
+    dec = v.Decoder(ds, S, S, halfrate=halfrate)
+    pcm_steps, spec_steps, info_steps, samples_steps = [], [], [], []
+    for t in range(T):
+        p, gp, eo = streams[0][t]
+        pk, nb = rows_tensor([p], cuda)
+        pcm, samples, status = dec.synthesis_batch([0], pk, nb,
+                                                   granulepos=torch.tensor([gp], dtype=torch.int64, device=cuda),
+                                                   eos=torch.tensor([eo], dtype=torch.uint8, device=cuda))
+        assert not status.cpu().numpy().any()
+        r = model.decode(p)
+        spec = dec.fetch("spectrum").cpu().numpy()
+        assert r["status"] == 0 and spec[0].tobytes() == r["spectrum"].tobytes(), t
+        pcm_steps.append(pcm.cpu().numpy())
+        spec_steps.append(spec)
+        info_steps.append(dec.fetch("info").cpu().numpy())
+        samples_steps.append(samples.cpu().numpy())
+    dec.close()
+    W = [int(i[0][1]) for i in info_steps]
+    assert {(a, b) for a, b in zip(W, W[1:])} == {(0, 0), (0, 1), (1, 0), (1, 1)}
+    peak = max(float(np.abs(p[0, :, :int(n[0])]).max()) for p, n in zip(pcm_steps, samples_steps) if n[0])
+    assert peak >= 1e-3                       # loud packets: the comparison is not one of zeros
+    exact = check_pcm_exact(oracle, ds, streams, pcm_steps, spec_steps, info_steps, samples_steps, halfrate=halfrate)
+    assert exact >= T - 2                     # every step but the first (and a last one trimmed to nothing) returns PCM
     ds.close()
