@@ -578,7 +578,8 @@ int  vbm_decoder_create(vbm_decoder **dec, const vbm_decode_setup *ds, int nstre
  *                            returns (blocksizes[lW]/4 + blocksizes[W]/4) / 2 samples
  *   vbm_synthesis_runs       pcm_stride >= max(run_packets) * blocksizes[1]/4
  *   vbm_range_store_create   indexes the streams at the decoder's rate; totals, and the starts / lengths / got of
- *                            vbm_synthesis_ranges, are output samples of the half-rate linear decode
+ *                            vbm_synthesis_ranges, are output samples of the half-rate linear decode (and so do
+ *                            vbm_range_store_create_device and vbm_decode_index_device)
  * Granule positions stay in full-rate samples, as in the reference: a packet whose granulepos asks for `extra`
  * full-rate samples less loses extra / 2 (rounded down) output samples (lib/block.c:1112-1118, 1140-1150).  The
  * invariants stated below hold unchanged: any split of a stream into runs and single-packet calls gives the same
@@ -650,6 +651,39 @@ int  vbm_range_store_create(vbm_range_store **st, vbm_decoder *dec, int nstreams
                             const long long *granulepos, const uint8_t *eos);
 void vbm_range_store_destroy(vbm_range_store *st);
 int  vbm_range_store_totals(const vbm_range_store *st, long long *totals);
+/* The same from a CSR that is already in device memory (what vbm_ogg_demux_fill writes): no packet byte crosses to the
+ * host.  The index is built by gfx950 kernels, one lane per packet for the header bits and one wavefront per stream
+ * for the running sample counts (64 packets per step; a stream with a granulepos below -1 on a valid packet is walked
+ * by one lane instead), bit for bit what vbm_decode_index_halfrate gives for each stream alone.
+ *
+ * vbm_decode_index_device: the index alone, at the decoder's halfrate, into the caller's device arrays: d_status,
+ * d_begin, d_end [P] (a valid packet's part [begin, end) of its block is what the linear decode returns for it:
+ * samples = end - begin; 0, 0 for a failed packet), d_out_start [P], d_totals [nstreams].  stream_packets is a host
+ * array, read before the call returns.  Only enqueues on `stream`: no allocation, and no wait but for a staging slot
+ * that is still in flight from four uploads back (the streams' first packets go up through the decoder's staging
+ * ring, at most 4 * max_batch or 2 * nstreams of the decoder per launch).  d_begin is also the kernels' workspace: it holds W between the two.  VBM_EINVAL, with nothing enqueued,
+ * on the conditions of vbm_range_store_create, or a NULL output.
+ *
+ * vbm_host_decode_index_scan: the CPU twin on host arrays (no device needed): the same 64-packet steps, the lanes as
+ * a loop.
+ *
+ * vbm_range_store_create_device: the store of vbm_range_store_create.  It owns copies of the bytes and offsets, made
+ * device to device on `stream`; status, out_start + samples and the totals are read back in one copy (12 B per
+ * packet) for the host planner of vbm_synthesis_ranges, and that is the call's one wait: when it returns, the
+ * caller's arrays are free. */
+int  vbm_decode_index_device(vbm_decoder *dec, int nstreams, const long long *stream_packets /*host [nstreams+1]*/,
+                             const uint8_t *d_data, const long long *d_offsets /*[P+1]*/, long long data_bytes,
+                             const long long *d_granulepos /*[P] or NULL*/, const uint8_t *d_eos /*[P] or NULL*/,
+                             int *d_status, int *d_begin, int *d_end, long long *d_out_start, long long *d_totals,
+                             void *stream);
+int  vbm_host_decode_index_scan(const vbm_decode_setup *ds, int halfrate, int nstreams,
+                                const long long *stream_packets, const uint8_t *data, const long long *offsets,
+                                long long data_bytes, const long long *granulepos, const uint8_t *eos, int *status,
+                                int *begin, int *end, long long *out_start, long long *totals);
+int  vbm_range_store_create_device(vbm_range_store **st, vbm_decoder *dec, int nstreams,
+                                   const long long *stream_packets /*host*/, const uint8_t *d_data,
+                                   const long long *d_offsets, long long data_bytes, const long long *d_granulepos,
+                                   const uint8_t *d_eos, void *stream);
 /* Sample windows of the store's streams.  Range r is stream stream_ids[r], start starts[r] >= 0, length lengths[r]
  * >= 0 (host arrays; ranges may repeat and overlap).  got[r] (host) = clamp(total - start, 0, length), and
  *   d_pcm[r][c][0 .. got[r]) == linear decode of the stream [c][start .. start + got[r])   bit for bit;

@@ -163,6 +163,14 @@ SIGNATURES = {
                                             C.POINTER(C.c_longlong)]),
     "vbm_range_store_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "vbm_decode_index_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "vbm_host_decode_index_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "vbm_range_store_create_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vbm_range_store_destroy": (None, [C.c_void_p]),
     "vbm_range_store_totals": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vbm_synthesis_ranges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -14,6 +14,10 @@
 // piece table goes up through the staging ring, then k_range_rows, k_unpack_rows, the same spectrum and IMDCT
 // launches, k_range_plan and k_overlap_runs.  No stream state is read or written.
 //
+// vbm_range_store_create_device makes the same store from a CSR that is already in device memory, and
+// vbm_decode_index_device the index alone: k_index_head and k_index_scan (decode_index.hip) in place of the host walk;
+// the first packets of the streams go up through the staging ring.
+//
 // A half-rate decoder (vbm_decoder_create_halfrate) enqueues the same chains with the IMDCT of half each block size and
 // the half-rate instantiations of the overlap kernels; its windows and trig tables are those of the halved sizes, its
 // IMDCT rows, tails and PCM rows half as long.
@@ -23,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "decode_index.h"
 #include "decode_kernels.h"
 #include "decode_setup.h"
 #include "vbm_internal.h"
@@ -47,6 +52,8 @@ struct vbm_decoder {
     int *d_lists = nullptr, *d_counts = nullptr;
     int *d_runtab = nullptr, *d_plan = nullptr, *d_run_last = nullptr;   // runs: [2S+1], [cap][6], [S]
     int *d_rtab = nullptr, *d_rows = nullptr, *d_zero = nullptr;         // ranges: [4 cap + 1], [cap], [cap] zeros
+    int *d_itab = nullptr;           // device index: [stage_ints] first packets of the streams of one scan launch
+    size_t stage_ints = 0;           // ints in a staging slot
     float *d_res = nullptr, *d_spec = nullptr, *d_imdct = nullptr;
     uint8_t *d_cls = nullptr;
     float *d_tail = nullptr;
@@ -98,7 +105,7 @@ void free_decoder(vbm_decoder *d)
     if (!d) return;
     void *bufs[] = {d->d_setup, d->d_tables, d->d_ids, d->d_info, d->d_fit, d->d_flags, d->d_status, d->d_lists,
                     d->d_counts, d->d_res, d->d_spec, d->d_imdct, d->d_cls, d->d_tail, d->d_prevW, d->d_gp, d->d_sc,
-                    d->d_runtab, d->d_plan, d->d_run_last, d->d_rtab, d->d_rows, d->d_zero};
+                    d->d_runtab, d->d_plan, d->d_run_last, d->d_rtab, d->d_rows, d->d_zero, d->d_itab};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     for (int i = 0; i < kStage; i++) {
@@ -227,6 +234,8 @@ extern "C" int vbm_decoder_create_halfrate(vbm_decoder **out, const vbm_decode_s
     CK(hipMalloc((void **)&d->d_rows, cap * sizeof(int)));
     CK(hipMalloc((void **)&d->d_zero, cap * sizeof(int)));
     CK(hipMemset(d->d_zero, 0, cap * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_itab, stage * sizeof(int)));
+    d->stage_ints = stage;
     for (int i = 0; i < kStage; i++) {
         CK(hipHostMalloc((void **)&d->h_stage[i], stage * sizeof(int), hipHostMallocDefault));
         CK(hipEventCreateWithFlags(&d->ev_stage[i], hipEventDisableTiming));
@@ -548,4 +557,120 @@ extern "C" int vbm_synthesis_ranges(vbm_decoder *d, const vbm_range_store *st, i
         d->last_nsb = nsb;
     }
     return VBM_OK;
+}
+
+// ---- the index and the range store from a CSR in device memory (decode_index.hip) ------------------------------------
+namespace {
+
+// the argument rules of vbm_range_store_create, for device arrays
+int check_device_csr(const vbm_decoder *d, int nstreams, const long long *stream_packets, const uint8_t *d_data,
+                     const long long *d_offsets, long long data_bytes)
+{
+    if (!d || nstreams <= 0 || !stream_packets || data_bytes < 0 || (data_bytes > 0 && !d_data) || !d_offsets)
+        return VBM_EINVAL;
+    if (stream_packets[0] != 0) { g_vbm_err = "stream_packets[0] must be 0"; return VBM_EINVAL; }
+    for (int i = 0; i < nstreams; i++)
+        if (stream_packets[i + 1] < stream_packets[i]) { g_vbm_err = "stream_packets must not decrease"; return VBM_EINVAL; }
+    if (stream_packets[nstreams] >= INT_MAX) { g_vbm_err = "more than 2^31 - 2 packets in one store"; return VBM_EINVAL; }
+    return VBM_OK;
+}
+
+// k_index_head over all packets, then k_index_scan over the streams, as many per launch as one staging slot holds
+// first packets for (they go up through the ring into d_itab; launches on one stream follow each other)
+int enqueue_index(vbm_decoder *d, int nstreams, const long long *stream_packets, const uint8_t *d_data,
+                  const long long *d_offsets, long long data_bytes, const long long *d_granulepos, const uint8_t *d_eos,
+                  int *d_status, int *d_begin, int *d_end, long long *d_out_start, long long *d_out_end,
+                  long long *d_totals, hipStream_t q)
+{
+    const vbmd_setup *s = (const vbmd_setup *)d->d_setup;
+    if (vbmd_launch_index_head(s, stream_packets[nstreams], d_data, d_offsets, data_bytes, d_status, d_begin, q))
+        return VBM_EHIP;
+    const int room = (int)std::min<size_t>(d->stage_ints - 1, (size_t)INT_MAX - 1);
+    for (int s0 = 0; s0 < nstreams; s0 += room) {
+        const int n = std::min(room, nstreams - s0);
+        const int t = d->stage_turn;
+        d->stage_turn = (t + 1) % kStage;
+        hipError_t e = hipEventSynchronize(d->ev_stage[t]);
+        if (e != hipSuccess) return vbm_set_hip_error(e, "hipEventSynchronize(stage)");
+        for (int i = 0; i <= n; i++) d->h_stage[t][i] = (int)stream_packets[s0 + i];
+        e = hipMemcpyAsync(d->d_itab, d->h_stage[t], ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, q);
+        if (e == hipSuccess) e = hipEventRecord(d->ev_stage[t], q);
+        if (e != hipSuccess) return vbm_set_hip_error(e, "upload of the streams' first packets");
+        if (vbmd_launch_index_scan(s, d->halfrate, n, d->d_itab, d_status, d_granulepos, d_eos, d_begin, d_end,
+                                   d_out_start, d_out_end, d_totals + s0, q))
+            return VBM_EHIP;
+    }
+    return VBM_OK;
+}
+
+}  // namespace
+
+extern "C" int vbm_decode_index_device(vbm_decoder *d, int nstreams, const long long *stream_packets,
+                                       const uint8_t *d_data, const long long *d_offsets, long long data_bytes,
+                                       const long long *d_granulepos, const uint8_t *d_eos, int *d_status, int *d_begin,
+                                       int *d_end, long long *d_out_start, long long *d_totals, void *stream)
+{
+    const int rc = check_device_csr(d, nstreams, stream_packets, d_data, d_offsets, data_bytes);
+    if (rc) return rc;
+    if (!d_totals || (stream_packets[nstreams] > 0 && (!d_status || !d_begin || !d_end || !d_out_start)))
+        return VBM_EINVAL;
+    return enqueue_index(d, nstreams, stream_packets, d_data, d_offsets, data_bytes, d_granulepos, d_eos, d_status,
+                         d_begin, d_end, d_out_start, nullptr, d_totals, (hipStream_t)stream);
+}
+
+extern "C" int vbm_range_store_create_device(vbm_range_store **out, vbm_decoder *d, int nstreams,
+                                             const long long *stream_packets, const uint8_t *d_data,
+                                             const long long *d_offsets, long long data_bytes,
+                                             const long long *d_granulepos, const uint8_t *d_eos, void *stream)
+{
+    if (!out) return VBM_EINVAL;
+    *out = nullptr;
+    int rc = check_device_csr(d, nstreams, stream_packets, d_data, d_offsets, data_bytes);
+    if (rc) return rc;
+    const long long P = stream_packets[nstreams];
+    const size_t np = (size_t)P, ns = (size_t)nstreams;
+    vbm_range_store *st = new vbm_range_store();
+    st->dec = d;
+    st->S = nstreams;
+    st->first.assign(stream_packets, stream_packets + nstreams + 1);
+    st->status.resize(np);
+    st->out_end.resize(np);
+    st->totals.resize(ns);
+    st->data_bytes = data_bytes;
+    // what the host planner reads, in one block so that it comes back in one copy: out_end [P], totals [S], status [P]
+    const size_t back_bytes = (np + ns) * sizeof(long long) + np * sizeof(int);
+    uint8_t *d_back = nullptr;
+    hipStream_t q = (hipStream_t)stream;
+    hipError_t e = hipSuccess;
+#define CK(x) do { e = (x); if (e != hipSuccess) { rc = vbm_set_hip_error(e, #x); goto fail; } } while (0)
+    {
+        CK(hipMalloc((void **)&st->d_data, data_bytes > 0 ? (size_t)data_bytes : 1));
+        CK(hipMalloc((void **)&st->d_offsets, (np + 1) * sizeof(long long)));
+        CK(hipMalloc((void **)&st->d_out_start, (np ? np : 1) * sizeof(long long)));
+        CK(hipMalloc((void **)&st->d_begin, (np ? np : 1) * sizeof(int)));
+        CK(hipMalloc((void **)&st->d_end, (np ? np : 1) * sizeof(int)));
+        CK(hipMalloc((void **)&d_back, back_bytes));
+        if (data_bytes > 0) CK(hipMemcpyAsync(st->d_data, d_data, (size_t)data_bytes, hipMemcpyDeviceToDevice, q));
+        CK(hipMemcpyAsync(st->d_offsets, d_offsets, (np + 1) * sizeof(long long), hipMemcpyDeviceToDevice, q));
+        long long *d_out_end = (long long *)d_back, *d_totals = d_out_end + np;
+        int *d_status = (int *)(d_totals + ns);
+        rc = enqueue_index(d, nstreams, stream_packets, st->d_data, st->d_offsets, data_bytes, d_granulepos, d_eos,
+                           d_status, st->d_begin, st->d_end, st->d_out_start, d_out_end, d_totals, q);
+        if (rc) goto fail;
+        std::vector<uint8_t> back(back_bytes);
+        CK(hipMemcpyAsync(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost, q));
+        CK(hipStreamSynchronize(q));                       // the one wait: the caller's arrays are free after it
+        if (np) memcpy(st->out_end.data(), back.data(), np * sizeof(long long));
+        memcpy(st->totals.data(), back.data() + np * sizeof(long long), ns * sizeof(long long));
+        if (np) memcpy(st->status.data(), back.data() + (np + ns) * sizeof(long long), np * sizeof(int));
+    }
+#undef CK
+    (void)hipFree(d_back);
+    *out = st;
+    return VBM_OK;
+fail:
+    (void)hipStreamSynchronize(q);                         // nothing enqueued may still write into the store
+    if (d_back) (void)hipFree(d_back);
+    free_store(st);
+    return rc;
 }

@@ -259,6 +259,69 @@ def decode_index(dsetup, data, offsets, granulepos=None, eos=None, halfrate=Fals
     return status, samples, out_start, total.value
 
 
+def _stream_packets(stream_packets, P):
+    """None: one stream of P packets -> int64 [S + 1], contiguous"""
+    first = np.asarray([0, P] if stream_packets is None else stream_packets, dtype=np.int64)
+    if first.ndim != 1 or len(first) < 2 or int(first[-1]) != P:
+        raise ValueError(f"stream_packets must run from 0 to the packet count {P} (one entry per stream, and one)")
+    return np.ascontiguousarray(first)
+
+
+def decode_index_device(decoder, data, offsets, granulepos=None, eos=None, stream_packets=None):
+    """The index of demuxed streams, built on the device (vbm_decode_index_device) at the decoder's rate: data uint8
+    [bytes], offsets int64 [P+1], granulepos int64 [P] / eos uint8 [P] or None, CUDA tensors holding one CSR over the
+    packets of all streams (a DemuxBatch's payload, offsets, granulepos and eos); stream_packets: host ints [S+1], the
+    first packet of every stream and P (None: one stream).
+    -> (status int32 [P], begin int32 [P], end int32 [P], out_start int64 [P], totals int64 [S]), device tensors;
+    end - begin, out_start and totals are decode_index's samples, out_start and total of each stream alone.  Only
+    enqueues work on the current stream."""
+    assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
+    offsets = offsets.to(torch.int64).contiguous()
+    P = offsets.numel() - 1
+    if P < 0:
+        raise ValueError("offsets needs at least one entry")
+    first = _stream_packets(stream_packets, P)
+    gp = granulepos.to(torch.int64).contiguous() if granulepos is not None else None
+    eo = eos.to(torch.uint8).contiguous() if eos is not None else None
+    if (gp is not None and gp.numel() != P) or (eo is not None and eo.numel() != P):
+        raise ValueError("granulepos and eos need one entry per packet")
+    dev = offsets.device
+    status, begin, end = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+    out_start = torch.empty(P, dtype=torch.int64, device=dev)
+    totals = torch.empty(len(first) - 1, dtype=torch.int64, device=dev)
+    check(lib.vbm_decode_index_device(decoder._h, len(first) - 1, first.ctypes.data,
+                                      data.data_ptr() if data.numel() else None, offsets.data_ptr(), data.numel(),
+                                      gp.data_ptr() if gp is not None and P else None,
+                                      eo.data_ptr() if eo is not None and P else None, status.data_ptr(),
+                                      begin.data_ptr(), end.data_ptr(), out_start.data_ptr(), totals.data_ptr(),
+                                      decoder._stream()), "vbm_decode_index_device")
+    decoder._last_index = (data, offsets, gp, eo)          # inputs stay alive until the work has run
+    return status, begin, end, out_start, totals
+
+
+def decode_index_scan_host(dsetup, data, offsets, granulepos=None, eos=None, stream_packets=None, halfrate=False):
+    """The CPU twin of decode_index_device (vbm_host_decode_index_scan; no device needed), on numpy arrays.
+    -> (status int32 [P], begin int32 [P], end int32 [P], out_start int64 [P], totals int64 [S])"""
+    data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8))
+    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    P = len(offsets) - 1
+    if P < 0:
+        raise ValueError("offsets needs at least one entry")
+    first = _stream_packets(stream_packets, P)
+    gp = None if granulepos is None else np.ascontiguousarray(np.asarray(granulepos, dtype=np.int64))
+    eo = None if eos is None else np.ascontiguousarray(np.asarray(eos, dtype=np.uint8))
+    if (gp is not None and len(gp) != P) or (eo is not None and len(eo) != P):
+        raise ValueError("granulepos and eos need one entry per packet")
+    status, begin, end = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
+    out_start, totals = np.zeros(P, np.int64), np.zeros(len(first) - 1, np.int64)
+    check(lib.vbm_host_decode_index_scan(dsetup._h, int(bool(halfrate)), len(first) - 1, first.ctypes.data,
+                                         data.ctypes.data if len(data) else None, offsets.ctypes.data, len(data),
+                                         None if gp is None else gp.ctypes.data, None if eo is None else eo.ctypes.data,
+                                         status.ctypes.data, begin.ctypes.data, end.ctypes.data, out_start.ctypes.data,
+                                         totals.ctypes.data), "vbm_host_decode_index_scan")
+    return status, begin, end, out_start, totals
+
+
 class RangeStore:
     """The packets of many streams of one Decoder's headers in device memory, with their index, for
     Decoder.synthesis_ranges.  streams: (data, offsets, granulepos, eos) tuples as demux_ogg returns them (granulepos
@@ -294,6 +357,41 @@ class RangeStore:
         self.totals = np.zeros(len(streams), np.int64)
         check(lib.vbm_range_store_totals(self._h, self.totals.ctypes.data), "vbm_range_store_totals")
 
+    @classmethod
+    def from_device(cls, decoder, payload, offsets=None, granulepos=None, eos=None, stream_packets=None):
+        """The same store from a CSR that is already on the device (vbm_range_store_create_device): payload uint8
+        [bytes], offsets int64 [P+1], granulepos int64 [P] / eos uint8 [P] or None as CUDA tensors, stream_packets host
+        ints [S+1] (the first packet of every stream, and P).  A stream.DemuxBatch may be given in place of payload,
+        alone: every file of it is a stream (a failed file an empty one).  The index is built by device kernels and
+        no packet byte crosses to the host; the store keeps its own copies, so the tensors are free when this
+        returns.  Waits for the device once."""
+        if offsets is None:
+            b = payload
+            payload, offsets, granulepos, eos = b.payload, b.offsets, b.granulepos, b.eos
+            stream_packets = np.append(np.asarray(b.packet_base, dtype=np.int64), offsets.numel() - 1)
+        assert payload.dtype == torch.uint8 and payload.dim() == 1 and payload.is_contiguous()
+        offsets = offsets.to(torch.int64).contiguous()
+        P = offsets.numel() - 1
+        if P < 0 or stream_packets is None:
+            raise ValueError("offsets needs at least one entry, and stream_packets must be given")
+        first = _stream_packets(stream_packets, P)
+        gp = granulepos.to(torch.int64).contiguous() if granulepos is not None else None
+        eo = eos.to(torch.uint8).contiguous() if eos is not None else None
+        if (gp is not None and gp.numel() != P) or (eo is not None and eo.numel() != P):
+            raise ValueError("granulepos and eos need one entry per packet")
+        self = cls.__new__(cls)
+        self.decoder, self.nstreams, self.halfrate = decoder, len(first) - 1, decoder.halfrate
+        self.packets = first
+        self._h = C.c_void_p()
+        check(lib.vbm_range_store_create_device(C.byref(self._h), decoder._h, self.nstreams, first.ctypes.data,
+                                                payload.data_ptr() if payload.numel() else None, offsets.data_ptr(),
+                                                payload.numel(), gp.data_ptr() if gp is not None and P else None,
+                                                eo.data_ptr() if eo is not None and P else None, decoder._stream()),
+              "vbm_range_store_create_device")
+        self.totals = np.zeros(self.nstreams, np.int64)
+        check(lib.vbm_range_store_totals(self._h, self.totals.ctypes.data), "vbm_range_store_totals")
+        return self
+
     def close(self):
         if self._h:
             lib.vbm_range_store_destroy(self._h)
@@ -313,12 +411,29 @@ class OggIndex:
     decode_ranges(file_ids, starts, lengths) -> (pcm float32 [n, channels, max(lengths)] CUDA tensor, zeros past got;
     got int32 [n]), pcm[r, :, :got[r]] bit for bit decode_ogg's output of that file from starts[r].
     halfrate=True: .rate is half the files' rate, and total_samples, starts and lengths are samples at that rate
-    (decode_ogg(files, halfrate=True)'s)."""
+    (decode_ogg(files, halfrate=True)'s).  device_demux=True: the files are demuxed together on the device
+    (stream.demux_ogg_device) and the store and its index are built there from the demuxed batch
+    (RangeStore.from_device) instead of file by file on the host; the index and every range are the same bit for
+    bit."""
 
-    def __init__(self, files, max_batch=4096, halfrate=False):
-        from .stream import demux_ogg
+    def __init__(self, files, max_batch=4096, halfrate=False, device_demux=False):
+        from .stream import demux_ogg, demux_ogg_device
         if max_batch < 2:
             raise ValueError("max_batch must be at least 2")
+        if device_demux:
+            files = list(files)
+            if not files:
+                raise ValueError("OggIndex needs at least one file")
+            b = demux_ogg_device(files)
+            for i, f in enumerate(files):
+                if b.status[i]:
+                    name = os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}"
+                    raise VbmError(f"{name}: vbm_ogg_demux_scan failed with code {b.status[i]}: not one valid "
+                                   "logical Ogg stream (vbm_ogg_demux on the file alone names the page)")
+            self._open(b.headers, max_batch, halfrate)
+            self.store = RangeStore.from_device(self.decoder, b)
+            self.total_samples = self.store.totals
+            return
         demuxed = []
         for i, f in enumerate(files):
             name = os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}"
@@ -331,16 +446,20 @@ class OggIndex:
                 raise VbmError(f"{name}: {e}") from None
         if not demuxed:
             raise ValueError("OggIndex needs at least one file")
-        h0 = demuxed[0][0]
-        for i, d in enumerate(demuxed):
-            if d[0][0] != h0[0] or d[0][2] != h0[2]:
+        self._open([d[0] for d in demuxed], max_batch, halfrate)
+        self.store = RangeStore(self.decoder, [d[1:] for d in demuxed])
+        self.total_samples = self.store.totals
+
+    def _open(self, headers, max_batch, halfrate):
+        """one header class -> .setup, .decoder"""
+        h0 = headers[0]
+        for i, h in enumerate(headers):
+            if h[0] != h0[0] or h[2] != h0[2]:
                 raise ValueError(f"file {i} has other identification or setup headers than file 0: one OggIndex "
                                  "takes one header class")
         self.setup = DecodeSetup(h0)
         self.decoder = Decoder(self.setup, 1, max_batch, halfrate=halfrate)
         self.channels, self.rate, self.halfrate = self.setup.channels, self.decoder.rate, self.decoder.halfrate
-        self.store = RangeStore(self.decoder, [d[1:] for d in demuxed])
-        self.total_samples = self.store.totals
 
     def decode_ranges(self, file_ids, starts, lengths):
         ln = np.asarray(lengths, dtype=np.int64)
