@@ -441,6 +441,90 @@ int vbm_host_ogg_demux_fill(vbm_ogg_demuxer *dm, uint8_t *headers, long long hea
                             long long payload_cap, long long *offsets, long long *granulepos, uint8_t *eos,
                             long long packet_cap);
 
+/* ---- Ogg demux, incremental form: the next bytes of many live streams per call, on the device -----------------------
+ * A feed holds max_streams stream slots.  Every call takes, for each slot of a list, a chunk of bytes of any length (0
+ * included) cut anywhere, and returns the audio packets those bytes completed, as ONE CSR grouped by stream in list
+ * order: the input of vbm_synthesis_runs with no copy in between.  The three header packets of a stream are kept in its
+ * slot for vbm_ogg_feed_headers.  The rules are those of vbm_ogg_demux, applied as the bytes arrive:
+ *   - a stream's run is what it carried over from earlier calls followed by the call's chunk; pages are taken from it in
+ *     order.  A page header is judged once its 27 bytes are present (capture pattern, version 0, one serial number, page
+ *     sequence from 0, continuation flag against an open packet), the CRC once the page is whole.
+ *   - a page that is not yet whole is no error: its bytes are carried.  A packet that is open at the end of the last
+ *     whole page is carried too and comes out, carried bytes first, in the call that completes it.
+ *   - granulepos / eos as vbm_ogg_demux: the last packet that ends on a page gets the page's, the others -1 and 0.
+ *   - a violation: packets completed on the pages in front of the offending page, in the same call included, are
+ *     delivered, nothing of that page is; the slot's status becomes VBM_EOGG and stays so until the slot is reset.
+ *     Bytes for a slot with a status, or after its `end`, are ignored.
+ *   - end[i] != 0 says no more bytes will come: VBM_EOGG if a partial page is left or fewer than three packets were
+ *     completed; a packet still open is dropped.
+ *   - three capacities per slot, fixed at create: max_page_carry, the bytes of an incomplete trailing page (1..65307);
+ *     max_packet_bytes, the bytes of an open audio packet at the end of a page; header_cap, the three header packets
+ *     together (an open header packet included).  A page that would exceed the second or third is not taken, a tail
+ *     above the first is not carried, and the slot gets the sticky status VBM_OGG_FEED_EBIG.  The two stores are judged
+ *     page by page, so their outcome does not depend on where the calls cut the stream.  Other slots are not touched.
+ *   - slots that a call does not list keep their state.  vbm_ogg_feed_reset_streams frees slots for new streams.
+ * The protocol is size query, then fill, per call:
+ *   vbm_ogg_feed_create      state and workspace on the current device: per slot 72 + max_page_carry + max_packet_bytes
+ *                            + header_cap bytes; per feed about 2.2 * max_call_bytes + (max_page_carry + 260) *
+ *                            max_streams (csrc/ogg_feed.h).  vbm_host_ogg_feed_create: the same in host memory for the
+ *                            vbm_host_* calls, touches no device.
+ *   vbm_ogg_feed_scan        ids [n] (host): the slots, each at most once; chunk i is d_data[chunk_offsets[i],
+ *                            chunk_offsets[i+1]) (device bytes, host offsets [n + 1]); end [n] (host) or NULL for all 0.
+ *                            Writes d_info[i] (device) for list entry i: the slot's status after the call, headers_ready
+ *                            and header_bytes (0 until ready), serialno, the audio packets / payload bytes this call
+ *                            completes and their exclusive sums over the list, pending (bytes of the incomplete page it
+ *                            carries on) and consumed (bytes of the whole pages taken, carried bytes included).
+ *                            d_totals[2] (device): packets and payload bytes of the call.  The chunks are copied: d_data is
+ *                            free once the scan has run.  It changes no stream state.
+ *   vbm_ogg_feed_fill        writes the CSR of the last scan: d_payload, d_offsets [packets + 1] (d_offsets[0] = 0, entry
+ *                            i's packets from packet_base on), d_granulepos, d_eos; then commits every listed slot's new
+ *                            carry and state.  d_payload holds payload_cap bytes, d_offsets packet_cap + 1 entries,
+ *                            d_granulepos and d_eos packet_cap.  When one is below the call's total NOTHING is written,
+ *                            the status word becomes VBM_OGG_DEMUX_ECAP and every slot stays as it was: the same scan
+ *                            can be filled again with larger buffers.  A fill that wrote leaves 0; a further fill of a
+ *                            scan that is already committed writes nothing and leaves VBM_EINVAL in the status word.
+ *   vbm_ogg_feed_status      the status word of the last fill -> *status (host).  Waits for `stream`.
+ *   vbm_ogg_feed_headers     sizes[3] and, unless headers is NULL, the three header packets of a slot back to back
+ *                            (cap bytes of host memory).  Waits for `stream`.  VBM_EINVAL while the slot has not completed
+ *                            three packets, or when cap is too small.
+ *   vbm_ogg_feed_reset_streams   ids [n] (host): those slots are fresh again (any serial number, sequence from 0).
+ * scan and fill allocate nothing and only enqueue on `stream`; the one wait in scan (and reset) is for the pinned slot
+ * that carried the arguments two calls earlier.  VBM_EINVAL, with nothing enqueued: n negative or above max_streams, an
+ * id out of range or listed twice, a negative or decreasing offset, more than max_call_bytes bytes, a null pointer
+ * (d_data may be null when there are no bytes, d_info when n is 0, d_payload / d_granulepos / d_eos when their capacity
+ * is 0), a negative capacity, fill without a scan, a host feed in a device call or the other way round.
+ *   vbm_host_ogg_feed_scan / _fill   the same source on the CPU with host pointers and a host feed; _status, _headers,
+ *                            _reset_streams and _destroy take both kinds. */
+#define VBM_OGG_FEED_EBIG (-1003)
+typedef struct {
+    int status;                 /* 0, VBM_EOGG or VBM_OGG_FEED_EBIG */
+    int headers_ready;
+    int header_bytes[3];
+    unsigned serialno;
+    long long packets;          /* audio packets this call completes */
+    long long payload_bytes;    /* their bytes */
+    long long packet_base, payload_base;   /* exclusive sums over the list entries before it */
+    long long pending;          /* bytes of the incomplete trailing page */
+    long long consumed;         /* bytes of the whole pages this call takes */
+} vbm_ogg_feed_info;
+typedef struct vbm_ogg_feed vbm_ogg_feed;
+int vbm_ogg_feed_create(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
+                        int max_packet_bytes, int header_cap);
+int vbm_host_ogg_feed_create(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
+                             int max_packet_bytes, int header_cap);
+void vbm_ogg_feed_destroy(vbm_ogg_feed *fd);
+int vbm_ogg_feed_scan(vbm_ogg_feed *fd, int n, const int *ids, const uint8_t *d_data, const long long *chunk_offsets,
+                      const uint8_t *end, vbm_ogg_feed_info *d_info, long long *d_totals, void *stream);
+int vbm_ogg_feed_fill(vbm_ogg_feed *fd, uint8_t *d_payload, long long payload_cap, long long *d_offsets,
+                      long long *d_granulepos, uint8_t *d_eos, long long packet_cap, void *stream);
+int vbm_ogg_feed_status(vbm_ogg_feed *fd, int *status, void *stream);
+int vbm_ogg_feed_headers(vbm_ogg_feed *fd, int id, uint8_t *headers, long long cap, int *sizes, void *stream);
+int vbm_ogg_feed_reset_streams(vbm_ogg_feed *fd, int n, const int *ids, void *stream);
+int vbm_host_ogg_feed_scan(vbm_ogg_feed *fd, int n, const int *ids, const uint8_t *data, const long long *chunk_offsets,
+                           const uint8_t *end, vbm_ogg_feed_info *info, long long *totals);
+int vbm_host_ogg_feed_fill(vbm_ogg_feed *fd, uint8_t *payload, long long payload_cap, long long *offsets,
+                           long long *granulepos, uint8_t *eos, long long packet_cap);
+
 typedef struct vbm_ogg_stream vbm_ogg_stream;
 int vbm_ogg_stream_create(vbm_ogg_stream **os, int serialno);
 void vbm_ogg_stream_destroy(vbm_ogg_stream *os);

@@ -154,6 +154,20 @@ SIGNATURES = {
     "vbm_host_ogg_demux_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vbm_host_ogg_demux_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_longlong]),
+    "vbm_ogg_feed_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "vbm_host_ogg_feed_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "vbm_ogg_feed_destroy": (None, [C.c_void_p]),
+    "vbm_ogg_feed_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "vbm_ogg_feed_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_longlong, C.c_void_p]),
+    "vbm_ogg_feed_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    "vbm_ogg_feed_headers": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(C.c_int), C.c_void_p]),
+    "vbm_ogg_feed_reset_streams": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vbm_host_ogg_feed_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "vbm_host_ogg_feed_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_longlong]),
     "vbm_decoder_fetch": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_char),
                                     C.c_void_p]),
     "vbm_decode_index": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,

@@ -234,3 +234,78 @@ VBMX_HD int oggdmx_file_of_page(const long long *page_base, int nfiles, long lon
 }
 
 VBMX_HD long long oggdmx_first_slot(const long long *off, int f) { return (off[f] - off[0]) / 27; }
+
+#ifdef __HIPCC__
+// ---- device helpers of the page-parallel kernels (ogg_demux.hip, ogg_feed.hip) ---------------------------------------
+// exclusive prefix of v over the block's 256 threads on top of `carry`, which moves on by the block's sum
+__device__ __forceinline__ long long block_exclusive(long long v, long long &carry, long long *wave_sum)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long x = v;
+    for (int dist = 1; dist < 64; dist <<= 1) {
+        const long long y = __shfl_up(x, dist, 64);
+        if (lane >= dist) x += y;
+    }
+    if (lane == 63) wave_sum[wave] = x;
+    __syncthreads();
+    long long at = carry + x - v, total = 0;
+    for (int k = 0; k < 4; k++) {
+        if (k < wave) at += wave_sum[k];
+        total += wave_sum[k];
+    }
+    carry += total;
+    __syncthreads();                                // wave_sum is rewritten by the next scan
+    return at;
+}
+
+// n bytes src -> dst by the 64 lanes of a wavefront.  Dword stores to the aligned middle of dst; a misaligned source is
+// read as aligned dwords that may begin up to three bytes in front of src (the page's lacing table lies there) and never
+// reach past src + n: the file may end with this body.
+__device__ __forceinline__ void dmx_wave_copy(uint8_t *dst, const uint8_t *src, int n, int lane)
+{
+    const int lead = min(n, (int)((4 - ((uintptr_t)dst & 3)) & 3));
+    if (lane < lead) dst[lane] = src[lane];
+    int nd = (n - lead) >> 2;
+    const uint8_t *s0 = src + lead;
+    const int sh = (int)((uintptr_t)s0 & 3) * 8;
+    const uint32_t *sa = (const uint32_t *)(s0 - ((uintptr_t)s0 & 3));
+    uint32_t *da = (uint32_t *)(dst + lead);
+    if (sh == 0) {
+        for (int i = lane; i < nd; i += 64) da[i] = sa[i];
+    } else {
+        // dword i needs sa[i] and sa[i + 1]: both must end at or before src + n
+        const int whole = (int)((src + n - (const uint8_t *)sa) >> 2);
+        nd = max(0, min(nd, whole - 1));
+        for (int i = lane; i < nd; i += 64) da[i] = (sa[i] >> sh) | (sa[i + 1] << (32 - sh));
+    }
+    for (int i = lead + nd * 4 + lane; i < n; i += 64) dst[i] = src[i];
+}
+
+// The packet ends of a page by the 64 lanes of a wavefront: four lacing values per lane, a wave prefix sum gives every
+// packet end its CSR slot.
+__device__ __forceinline__ void dmx_wave_packet_ends(const OggDmxPageCtx &c, const OggDmxOut &out, int lane)
+{
+    // segments 4 * lane .. 4 * lane + 3; bytes (<= 65025) and packet ends (<= 255) of a page share one word
+    int lv[4], mine = 0, last_end = -1;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int i = lane * 4 + j;
+        lv[j] = i < c.nseg ? c.h[27 + i] : -1;
+        if (lv[j] >= 0) mine += lv[j] + (lv[j] < 255 ? 1 << 20 : 0);
+        if (lv[j] >= 0 && lv[j] < 255) last_end = i;
+    }
+    int x = mine;
+    for (int dist = 1; dist < 64; dist <<= 1) {
+        const int y = __shfl_up(x, dist, 64);
+        if (lane >= dist) x += y;
+    }
+    for (int m = 32; m >= 1; m >>= 1) last_end = max(last_end, __shfl_xor(last_end, m, 64));
+    int bytes = (x - mine) & 0xfffff, ends = (x - mine) >> 20;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (lv[j] < 0) continue;
+        bytes += lv[j];
+        if (lv[j] < 255) oggdmx_packet_end(c, out, ends++, bytes, lane * 4 + j == last_end);
+    }
+}
+#endif

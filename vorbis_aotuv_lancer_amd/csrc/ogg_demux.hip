@@ -50,27 +50,6 @@ __global__ void __launch_bounds__(64) k_dmx_walk(int nfiles, const uint8_t *data
     crc_bad[f] = 0;
 }
 
-// exclusive prefix of v over the block's 256 threads on top of `carry`, which moves on by the block's sum
-__device__ __forceinline__ long long block_exclusive(long long v, long long &carry, long long *wave_sum)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long x = v;
-    for (int dist = 1; dist < 64; dist <<= 1) {
-        const long long y = __shfl_up(x, dist, 64);
-        if (lane >= dist) x += y;
-    }
-    if (lane == 63) wave_sum[wave] = x;
-    __syncthreads();
-    long long at = carry + x - v, total = 0;
-    for (int k = 0; k < 4; k++) {
-        if (k < wave) at += wave_sum[k];
-        total += wave_sum[k];
-    }
-    carry += total;
-    __syncthreads();                                // wave_sum is rewritten by the next scan
-    return at;
-}
-
 __global__ void __launch_bounds__(256) k_dmx_scan_pages(int nfiles, const long long *npages, long long *page_base)
 {
     __shared__ long long wave_sum[4];
@@ -133,29 +112,6 @@ __global__ void __launch_bounds__(256) k_dmx_scan_info(int nfiles, vbm_ogg_file_
     }
 }
 
-// n bytes src -> dst by the 64 lanes of a wavefront.  Dword stores to the aligned middle of dst; a misaligned source is
-// read as aligned dwords that may begin up to three bytes in front of src (the page's lacing table lies there) and never
-// reach past src + n: the file may end with this body.
-__device__ __forceinline__ void dmx_wave_copy(uint8_t *dst, const uint8_t *src, int n, int lane)
-{
-    const int lead = min(n, (int)((4 - ((uintptr_t)dst & 3)) & 3));
-    if (lane < lead) dst[lane] = src[lane];
-    int nd = (n - lead) >> 2;
-    const uint8_t *s0 = src + lead;
-    const int sh = (int)((uintptr_t)s0 & 3) * 8;
-    const uint32_t *sa = (const uint32_t *)(s0 - ((uintptr_t)s0 & 3));
-    uint32_t *da = (uint32_t *)(dst + lead);
-    if (sh == 0) {
-        for (int i = lane; i < nd; i += 64) da[i] = sa[i];
-    } else {
-        // dword i needs sa[i] and sa[i + 1]: both must end at or before src + n
-        const int whole = (int)((src + n - (const uint8_t *)sa) >> 2);
-        nd = max(0, min(nd, whole - 1));
-        for (int i = lane; i < nd; i += 64) da[i] = (sa[i] >> sh) | (sa[i + 1] << (32 - sh));
-    }
-    for (int i = lead + nd * 4 + lane; i < n; i += 64) dst[i] = src[i];
-}
-
 __global__ void __launch_bounds__(256) k_dmx_fill(int nfiles, const uint8_t *data, const long long *off,
                                                   const OggDmxPage *pages, const long long *page_base,
                                                   const vbm_ogg_file_info *info, const long long *totals,
@@ -179,28 +135,7 @@ __global__ void __launch_bounds__(256) k_dmx_fill(int nfiles, const uint8_t *dat
         if (fi.status) continue;                    // its CRC failed after the walk had counted its pages
         OggDmxPageCtx c;
         oggdmx_page_ctx(data, pages[oggdmx_first_slot(off, f) + (p - page_base[f])], fi, c);
-        // segments 4 * lane .. 4 * lane + 3; bytes (<= 65025) and packet ends (<= 255) of a page share one word
-        int lv[4], mine = 0, last_end = -1;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int i = lane * 4 + j;
-            lv[j] = i < c.nseg ? c.h[27 + i] : -1;
-            if (lv[j] >= 0) mine += lv[j] + (lv[j] < 255 ? 1 << 20 : 0);
-            if (lv[j] >= 0 && lv[j] < 255) last_end = i;
-        }
-        int x = mine;
-        for (int dist = 1; dist < 64; dist <<= 1) {
-            const int y = __shfl_up(x, dist, 64);
-            if (lane >= dist) x += y;
-        }
-        for (int m = 32; m >= 1; m >>= 1) last_end = max(last_end, __shfl_xor(last_end, m, 64));
-        int bytes = (x - mine) & 0xfffff, ends = (x - mine) >> 20;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (lv[j] < 0) continue;
-            bytes += lv[j];
-            if (lv[j] < 255) oggdmx_packet_end(c, out, ends++, bytes, lane * 4 + j == last_end);
-        }
+        dmx_wave_packet_ends(c, out, lane);
         const OggDmxSplit s = oggdmx_body_split(c, out);
         if (s.n_h) dmx_wave_copy(s.dst_h, s.src_h, (int)s.n_h, lane);
         if (s.n_p) dmx_wave_copy(s.dst_p, s.src_p, (int)s.n_p, lane);

@@ -1,0 +1,722 @@
+// Incremental Ogg demux on the device for many live streams (rules, state and workspace: ogg_feed.h), its host twin, and
+// the C ABI over both (include/vorbis_mi355x.h, "Ogg demux, incremental form").
+//
+//   scan:  k_feed_gather      one wavefront per listed stream: carried page tail, then the chunk -> the stream's run in
+//                             the work buffer
+//          k_feed_walk        one lane per listed stream: resumes from the slot's state, takes whole pages, stops at the
+//                             first that is not whole; every read is bounded by the run's end
+//          k_feed_scan_pages  one block: exclusive scan of the page counts -> dense page numbers
+//          k_feed_crc         one wavefront per page, as k_dmx_crc; records the first bad page of a stream
+//          k_feed_settle      one lane per listed stream: a stream with a bad page is walked again up to it
+//          k_feed_scan_counts one block: exclusive scans of packets and payload bytes; the totals
+//          k_feed_info        one lane per listed stream: the bases into its call record, its info struct
+//   fill:  k_feed_fill        one wavefront per page: packet ends and the payload part of the body, as k_dmx_fill; then
+//                             one wavefront per stream: the carried part of its open packet to the front of its payload
+//          k_feed_commit      one wavefront per page: header bytes and the open packet's bytes to the slot's stores; then
+//                             one wavefront per stream: the unconsumed tail and the new state
+//          k_feed_mark        the scan is committed
+// Nothing of a slot changes before k_feed_commit, which runs only after a fill that wrote its outputs.
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <string.h>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "ogg_feed.h"
+#include "vbm_internal.h"
+
+namespace {
+
+constexpr int kStage = 2;          // pinned staging slots for the call's host arguments
+constexpr int kWaveBlocks = 2048;  // most blocks (of four wavefronts) a wave-parallel kernel is launched with
+constexpr int kPiece = 1 << 30;    // dmx_wave_copy takes an int
+
+struct FeedArgs {                  // the call's arguments in device (or host) memory
+    const long long *off;          // [n + 1]
+    const int *ids, *end;          // [n]
+};
+
+struct FeedMem {                   // the feed's state and workspace
+    OggFeedState *state;
+    uint8_t *tail, *open, *hdr, *work;
+    OggDmxPage *pages;
+    OggFeedCall *call;
+    long long *npages, *page_base, *totals;
+    long long *count, *base;       // [2 * max_streams]: packets and payload bytes of the call per listed stream, their sums
+    int *bad, *status, *committed;
+};
+
+VBMX_HD long long feed_at(const long long *off, int i, const OggFeedCaps &caps)
+{
+    return off[i] - off[0] + (long long)i * caps.max_page_carry;
+}
+
+VBMX_HD long long feed_first_rec(const long long *off, int i) { return (off[i] - off[0]) / 27 + i; }
+
+// stream i of the list, walked from its slot's state over its run in the work buffer
+VBMX_HD void feed_walk_one(const FeedArgs &a, const FeedMem &m, const OggFeedCaps &caps, int i, int limit, bool bad_at_limit,
+                           OggFeedCall &c)
+{
+    const int slot = a.ids[i];
+    const OggFeedState st = m.state[slot];
+    const long long at = feed_at(a.off, i, caps), rec = feed_first_rec(a.off, i);
+    const long long run_end = at + oggfeed_tail_in(st, caps) + (a.off[i + 1] - a.off[i]);
+    oggfeed_walk(m.work, at, run_end, st, caps, a.end[i], limit, bad_at_limit, m.pages + rec,
+                 feed_first_rec(a.off, i + 1) - rec, slot, c);
+}
+
+// ---- kernels ---------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ void feed_wave_copy(uint8_t *dst, const uint8_t *src, long long n, int lane)
+{
+    for (; n > 0; n -= kPiece, dst += kPiece, src += kPiece) dmx_wave_copy(dst, src, (int)(n < kPiece ? n : kPiece), lane);
+}
+
+__global__ void __launch_bounds__(256) k_feed_gather(int n, FeedArgs a, FeedMem m, OggFeedCaps caps, const uint8_t *data)
+{
+    const int lane = threadIdx.x & 63, nwaves = gridDim.x * 4;
+    for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += nwaves) {
+        const int slot = a.ids[i];
+        const OggFeedState st = m.state[slot];
+        if (st.status || st.done) continue;
+        const int tail = oggfeed_tail_in(st, caps);                // at most max_page_carry: never past the slot's store
+        uint8_t *run = m.work + feed_at(a.off, i, caps);
+        dmx_wave_copy(run, m.tail + (long long)slot * caps.max_page_carry, tail, lane);
+        feed_wave_copy(run + tail, data + a.off[i], a.off[i + 1] - a.off[i], lane);
+    }
+}
+
+__global__ void __launch_bounds__(64) k_feed_walk(int n, FeedArgs a, FeedMem m, OggFeedCaps caps)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    OggFeedCall c;
+    feed_walk_one(a, m, caps, i, INT_MAX, false, c);
+    m.call[i] = c;
+    m.npages[i] = c.npages;
+    m.count[2 * i] = c.packets, m.count[2 * i + 1] = c.payload_bytes;
+    m.bad[i] = INT_MAX;
+}
+
+// exclusive prefix over v[0, n) by one block of 256 threads, four consecutive entries per thread and step -> out, *total
+template <int STRIDE>
+__device__ __forceinline__ void block_scan_array(int n, const long long *v, long long *out, long long *total, long long *wave_sum)
+{
+    long long carry = 0;
+    for (int first = 0; first < n; first += 1024) {
+        const int i0 = first + threadIdx.x * 4;
+        long long x[4], sum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            x[j] = i0 + j < n ? v[(long long)(i0 + j) * STRIDE] : 0;
+            sum += x[j];
+        }
+        long long at = block_exclusive(sum, carry, wave_sum);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (i0 + j < n) out[(long long)(i0 + j) * STRIDE] = at;
+            at += x[j];
+        }
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+__global__ void __launch_bounds__(256) k_feed_scan_pages(int n, const long long *npages, long long *page_base)
+{
+    __shared__ long long wave_sum[4];
+    block_scan_array<1>(n, npages, page_base, page_base + n, wave_sum);
+}
+
+__global__ void __launch_bounds__(256) k_feed_crc(int n, OggMuxPow pw, FeedArgs a, FeedMem m)
+{
+    __shared__ uint32_t T[256];
+    T[threadIdx.x] = oggmux_crc_entry(threadIdx.x);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const long long total = m.page_base[n], nwaves = (long long)gridDim.x * 4;
+    for (long long p = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); p < total; p += nwaves) {
+        const int i = oggdmx_file_of_page(m.page_base, n, p);
+        const long long k = p - m.page_base[i];
+        const OggDmxPage pg = m.pages[feed_first_rec(a.off, i) + k];
+        const uint8_t *h = m.work + pg.at;
+        const int L = pg.len, chunk = (L + 63) >> 6, b0 = lane * chunk, b1 = min(L, b0 + chunk);
+        uint32_t crc = 0;
+        if (b0 < b1) crc = oggmux_crc_shift(pw, oggdmx_crc_run(T, 0, h + b0, b1 - b0), (uint32_t)(L - b1));
+        for (int s = 32; s >= 1; s >>= 1) crc ^= __shfl_xor(crc, s, 64);
+        if (lane == 0 && !oggdmx_crc_matches(T, pw, h, L, crc)) atomicMin(&m.bad[i], (int)k);
+    }
+}
+
+__global__ void __launch_bounds__(64) k_feed_settle(int n, FeedArgs a, FeedMem m, OggFeedCaps caps)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int bad = m.bad[i];
+    if (bad >= m.npages[i]) return;
+    OggFeedCall c;                                  // pages from the bad one on are not taken
+    feed_walk_one(a, m, caps, i, bad, true, c);
+    m.call[i] = c;
+    m.count[2 * i] = c.packets, m.count[2 * i + 1] = c.payload_bytes;
+}
+
+__global__ void __launch_bounds__(256) k_feed_scan_counts(int n, FeedMem m, long long *out_totals)
+{
+    __shared__ long long wave_sum[4];
+    block_scan_array<2>(n, m.count, m.base, m.totals, wave_sum);
+    block_scan_array<2>(n, m.count + 1, m.base + 1, m.totals + 1, wave_sum);
+    if (threadIdx.x == 0) {
+        out_totals[0] = m.totals[0];
+        out_totals[1] = m.totals[1];
+        *m.committed = 0;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_feed_info(int n, FeedMem m, vbm_ogg_feed_info *out_info)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    m.call[i].packet_base = m.base[2 * i];
+    m.call[i].payload_base = m.base[2 * i + 1];
+    vbm_ogg_feed_info fi;
+    oggfeed_info(m.call[i], fi);
+    out_info[i] = fi;
+}
+
+__global__ void __launch_bounds__(256) k_feed_fill(int n, FeedArgs a, FeedMem m, OggFeedCaps caps, long long packet_cap,
+                                                   long long payload_cap, OggDmxOut out)
+{
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    if (*m.committed) {                             // a fill has already written and committed this scan
+        if (first) *m.status = VBM_EINVAL;
+        return;
+    }
+    if (m.totals[0] > packet_cap || m.totals[1] > payload_cap) {
+        if (first) *m.status = VBM_OGG_DEMUX_ECAP;  // the call does not fit: nothing is written, nothing committed
+        return;
+    }
+    if (first) {
+        *m.status = 0;
+        out.offsets[0] = 0;
+    }
+    const int lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long total = m.page_base[n], nwaves = (long long)gridDim.x * 4;
+    for (long long p = wave; p < total; p += nwaves) {
+        const int i = oggdmx_file_of_page(m.page_base, n, p);
+        const long long k = p - m.page_base[i];
+        const OggFeedCall &c = m.call[i];
+        if (k >= c.npages) continue;                // behind a page whose CRC failed
+        OggDmxPageCtx x;
+        oggfeed_ctx_payload(m.work, m.pages[feed_first_rec(a.off, i) + k], c, x);
+        dmx_wave_packet_ends(x, out, lane);
+        const OggDmxSplit s = oggdmx_body_split(x, out);
+        if (s.n_p) dmx_wave_copy(s.dst_p, s.src_p, (int)s.n_p, lane);
+    }
+    for (long long i = wave; i < n; i += nwaves) {
+        const OggFeedCall &c = m.call[i];
+        const int open_in = min(c.open_in, caps.max_packet_bytes);   // never past the slot's store
+        if (open_in > 0)
+            dmx_wave_copy(out.payload + c.payload_base, m.open + (long long)c.slot * caps.max_packet_bytes, open_in, lane);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_feed_commit(int n, FeedArgs a, FeedMem m, OggFeedCaps caps)
+{
+    if (*m.status != 0) return;                     // the fill wrote nothing
+    const OggDmxOut keep = {m.hdr, m.open, nullptr, nullptr, nullptr};
+    const int lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long total = m.page_base[n], nwaves = (long long)gridDim.x * 4;
+    for (long long p = wave; p < total; p += nwaves) {
+        const int i = oggdmx_file_of_page(m.page_base, n, p);
+        const long long k = p - m.page_base[i];
+        const OggFeedCall &c = m.call[i];
+        if (k >= c.npages) continue;
+        OggDmxPageCtx xh, xo;
+        oggfeed_ctx_keep(m.work, m.pages[feed_first_rec(a.off, i) + k], c, caps, xh, xo);
+        const OggDmxSplit sh = oggdmx_body_split(xh, keep), so = oggdmx_body_split(xo, keep);
+        if (sh.n_h) dmx_wave_copy(sh.dst_h, sh.src_h, (int)sh.n_h, lane);
+        if (so.n_p) dmx_wave_copy(so.dst_p, so.src_p, (int)so.n_p, lane);
+    }
+    for (long long i = wave; i < n; i += nwaves) {
+        const OggFeedCall &c = m.call[i];
+        const int tail = c.next.tail;
+        if (tail > 0 && tail <= caps.max_page_carry)
+            dmx_wave_copy(m.tail + (long long)c.slot * caps.max_page_carry, m.work + c.pos_end, tail, lane);
+        if (lane == 0) m.state[c.slot] = c.next;
+    }
+}
+
+__global__ void k_feed_mark(FeedMem m)
+{
+    if (*m.status == 0) *m.committed = 1;
+}
+
+__global__ void __launch_bounds__(256) k_feed_reset(int n, const int *ids, OggFeedState *state)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) state[ids[i]] = OggFeedState{};
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------
+
+struct CrcTable {
+    uint32_t t[256];
+    CrcTable() { for (uint32_t i = 0; i < 256; i++) t[i] = oggmux_crc_entry(i); }
+};
+
+const CrcTable &crc_table()
+{
+    static const CrcTable c;
+    return c;
+}
+
+int fail(int code, const std::string &msg)
+{
+    g_vbm_err = msg;
+    return code;
+}
+
+}  // namespace
+
+struct vbm_ogg_feed {
+    bool host = false;
+    int max_streams = 0;
+    long long max_call_bytes = 0;
+    OggFeedCaps caps = {};
+    OggMuxPow pow;
+    FeedMem m = {};                      // device memory, or host memory (calloc) for the twin
+    uint8_t *args = nullptr;             // the call's arguments: off [n + 1], ids [n], end [n]; room for n = max_streams
+    uint8_t *h_stage[kStage] = {};       // device feed: pinned, the size of args
+    hipEvent_t ev_stage[kStage] = {};
+    int stage_turn = 0;
+    std::vector<int> seen;               // [max_streams] the call that last listed a slot
+    int call_no = 0;
+    // the last scan
+    bool scanned = false, host_committed = false;
+    int n = 0;
+    long long span = 0;
+};
+
+namespace {
+
+size_t args_bytes(int n) { return ((size_t)n + 1) * sizeof(long long) + 2 * (size_t)n * sizeof(int); }
+
+FeedArgs args_view(uint8_t *base, int n)
+{
+    FeedArgs a;
+    a.off = (const long long *)base;
+    a.ids = (const int *)(base + ((size_t)n + 1) * sizeof(long long));
+    a.end = a.ids + n;
+    return a;
+}
+
+template <class T> int alloc(vbm_ogg_feed *f, T *&p, size_t n)
+{
+    if (f->host) {
+        p = (T *)calloc(n ? n : 1, sizeof(T));
+        return p ? VBM_OK : fail(VBM_EFAULT, "vbm_ogg_feed: out of host memory");
+    }
+    hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
+    if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_ogg_feed: hipMalloc");
+    e = hipMemset(p, 0, (n ? n : 1) * sizeof(T));
+    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed: hipMemset");
+}
+
+template <class T> void release(vbm_ogg_feed *f, T *&p)
+{
+    if (!p) return;
+    if (f->host) free(p);
+    else (void)hipFree(p);
+    p = nullptr;
+}
+
+int create(vbm_ogg_feed **out, int max_streams, long long max_call_bytes, int max_page_carry, int max_packet_bytes,
+           int header_cap, bool host)
+{
+    if (!out || max_streams < 1 || max_call_bytes < 0 || max_page_carry < 1 || max_page_carry > 65307 ||
+        max_packet_bytes < 1 || header_cap < 1)
+        return fail(VBM_EINVAL, "vbm_ogg_feed_create: bad argument (max_streams >= 1, max_call_bytes >= 0, max_page_carry "
+                                "in 1..65307, max_packet_bytes >= 1, header_cap >= 1)");
+    if (!host) {
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(VBM_ENODEV, "vbm_ogg_feed_create: no HIP device");
+    }
+    vbm_ogg_feed *f = new (std::nothrow) vbm_ogg_feed();
+    if (!f) return fail(VBM_EFAULT, "vbm_ogg_feed_create: out of memory");
+    f->host = host;
+    f->max_streams = max_streams;
+    f->max_call_bytes = max_call_bytes;
+    f->caps = {max_page_carry, max_packet_bytes, header_cap};
+    f->pow = oggmux_pow_table();
+    const size_t S = (size_t)max_streams;
+    int rc = VBM_OK;
+    try {
+        f->seen.assign(S, 0);
+    } catch (const std::bad_alloc &) {
+        rc = fail(VBM_EFAULT, "vbm_ogg_feed_create: out of memory");
+    }
+    if (!rc) rc = alloc(f, f->m.state, S);
+    if (!rc) rc = alloc(f, f->m.tail, S * (size_t)max_page_carry);
+    if (!rc) rc = alloc(f, f->m.open, S * (size_t)max_packet_bytes);
+    if (!rc) rc = alloc(f, f->m.hdr, S * (size_t)header_cap);
+    if (!rc) rc = alloc(f, f->m.work, (size_t)max_call_bytes + S * (size_t)max_page_carry + 4);
+    if (!rc) rc = alloc(f, f->m.pages, (size_t)(max_call_bytes / 27) + S + 1);
+    if (!rc) rc = alloc(f, f->m.call, S);
+    if (!rc) rc = alloc(f, f->m.npages, S);
+    if (!rc) rc = alloc(f, f->m.page_base, S + 1);
+    if (!rc) rc = alloc(f, f->m.totals, 2);
+    if (!rc) rc = alloc(f, f->m.count, 2 * S);
+    if (!rc) rc = alloc(f, f->m.base, 2 * S);
+    if (!rc) rc = alloc(f, f->m.bad, S);
+    if (!rc) rc = alloc(f, f->m.status, 1);
+    if (!rc) rc = alloc(f, f->m.committed, 1);
+    if (!rc) rc = alloc(f, f->args, args_bytes(max_streams));
+    for (int i = 0; i < kStage && !rc && !host; i++) {
+        hipError_t e = hipHostMalloc((void **)&f->h_stage[i], args_bytes(max_streams), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_stage[i], hipEventDisableTiming);
+        if (e != hipSuccess) rc = vbm_set_hip_error(e, "vbm_ogg_feed_create: staging");
+    }
+    if (rc) {
+        vbm_ogg_feed_destroy(f);
+        return rc;
+    }
+    *out = f;
+    return VBM_OK;
+}
+
+int check_kind(const vbm_ogg_feed *f, bool host, const char *who)
+{
+    if (!f || f->host != host)
+        return fail(VBM_EINVAL, std::string(who) + (host ? ": needs a feed made by vbm_host_ogg_feed_create"
+                                                         : ": needs a feed made by vbm_ogg_feed_create"));
+    return VBM_OK;
+}
+
+// ids: each in range, none twice (f->seen is marked: call once per call, after every other check)
+int check_ids(vbm_ogg_feed *f, int n, const int *ids, const char *who)
+{
+    if (n < 0 || n > f->max_streams) return fail(VBM_EINVAL, std::string(who) + ": n is negative or above max_streams");
+    if (n && !ids) return fail(VBM_EINVAL, std::string(who) + ": null pointer");
+    for (int i = 0; i < n; i++)
+        if (ids[i] < 0 || ids[i] >= f->max_streams)
+            return fail(VBM_EINVAL, std::string(who) + ": stream id " + std::to_string(ids[i]) + " is out of range");
+    if (++f->call_no == INT_MAX) {
+        f->seen.assign(f->seen.size(), 0);
+        f->call_no = 1;
+    }
+    for (int i = 0; i < n; i++) {
+        if (f->seen[ids[i]] == f->call_no)
+            return fail(VBM_EINVAL, std::string(who) + ": stream id " + std::to_string(ids[i]) + " is listed twice");
+        f->seen[ids[i]] = f->call_no;
+    }
+    return VBM_OK;
+}
+
+int check_scan(vbm_ogg_feed *f, bool host, int n, const int *ids, const uint8_t *data, const long long *off,
+               const vbm_ogg_feed_info *info, const long long *totals, const char *who)
+{
+    int rc = check_kind(f, host, who);
+    if (rc) return rc;
+    if (n < 0 || n > f->max_streams) return fail(VBM_EINVAL, std::string(who) + ": n is negative or above max_streams");
+    if (!off || !totals || (n && (!info || !ids))) return fail(VBM_EINVAL, std::string(who) + ": null pointer");
+    if (off[0] < 0) return fail(VBM_EINVAL, std::string(who) + ": negative chunk offset");
+    for (int i = 0; i < n; i++)
+        if (off[i + 1] < off[i]) return fail(VBM_EINVAL, std::string(who) + ": chunk offsets decrease");
+    if (off[n] - off[0] > f->max_call_bytes)
+        return fail(VBM_EINVAL, std::string(who) + ": the chunks span " + std::to_string(off[n] - off[0]) +
+                                    " bytes, above max_call_bytes = " + std::to_string(f->max_call_bytes));
+    if (off[n] > off[0] && !data) return fail(VBM_EINVAL, std::string(who) + ": null data");
+    return check_ids(f, n, ids, who);
+}
+
+int check_fill(const vbm_ogg_feed *f, bool host, const uint8_t *payload, long long payload_cap, const long long *offsets,
+               const long long *granulepos, const uint8_t *eos, long long packet_cap, const char *who)
+{
+    int rc = check_kind(f, host, who);
+    if (rc) return rc;
+    if (!f->scanned) return fail(VBM_EINVAL, std::string(who) + ": no scan has been made on this feed");
+    if (payload_cap < 0 || packet_cap < 0) return fail(VBM_EINVAL, std::string(who) + ": negative capacity");
+    if (!offsets || (payload_cap && !payload) || (packet_cap && (!granulepos || !eos)))
+        return fail(VBM_EINVAL, std::string(who) + ": null pointer");
+    return VBM_OK;
+}
+
+// off [n + 1], ids [n] and end [n] (NULL: zeros) in the layout of args_view
+void pack_args(uint8_t *dst, int n, const int *ids, const long long *off, const uint8_t *end)
+{
+    const FeedArgs a = args_view(dst, n);
+    if (off) memcpy((void *)a.off, off, ((size_t)n + 1) * sizeof(long long));
+    if (n) memcpy((void *)a.ids, ids, (size_t)n * sizeof(int));
+    int *e = (int *)a.end;
+    for (int i = 0; i < n; i++) e[i] = end ? (end[i] != 0) : 0;
+}
+
+// the call's arguments go up through a pinned slot; the only wait is for the copy out of it two calls ago
+int upload_args(vbm_ogg_feed *f, int n, const int *ids, const long long *off, const uint8_t *end, hipStream_t q,
+                const char *who)
+{
+    const int t = f->stage_turn;
+    f->stage_turn = (t + 1) % kStage;
+    hipError_t e = hipEventSynchronize(f->ev_stage[t]);
+    if (e != hipSuccess) return vbm_set_hip_error(e, who);
+    pack_args(f->h_stage[t], n, ids, off, end);
+    // one copy: the three arrays lie in one block, in the same layout on both sides
+    e = hipMemcpyAsync(f->args, f->h_stage[t], args_bytes(n), hipMemcpyHostToDevice, q);
+    if (e == hipSuccess) e = hipEventRecord(f->ev_stage[t], q);
+    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, who);
+}
+
+dim3 wave_grid(long long waves)
+{
+    const long long blocks = (waves + 3) / 4;
+    return dim3((unsigned)(blocks < 1 ? 1 : (blocks < kWaveBlocks ? blocks : kWaveBlocks)));
+}
+
+// pages of a call: every stream's first page and then one per 27 bytes at the very most; far fewer in practice, and the
+// kernels stride over what the grid does not cover
+dim3 page_grid(const vbm_ogg_feed *f) { return wave_grid(f->n + f->span / 1024); }
+
+}  // namespace
+
+extern "C" int vbm_ogg_feed_create(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
+                                   int max_packet_bytes, int header_cap)
+{
+    return create(fd, max_streams, max_call_bytes, max_page_carry, max_packet_bytes, header_cap, false);
+}
+
+extern "C" int vbm_host_ogg_feed_create(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
+                                        int max_packet_bytes, int header_cap)
+{
+    return create(fd, max_streams, max_call_bytes, max_page_carry, max_packet_bytes, header_cap, true);
+}
+
+extern "C" void vbm_ogg_feed_destroy(vbm_ogg_feed *f)
+{
+    if (!f) return;
+    release(f, f->m.state);
+    release(f, f->m.tail);
+    release(f, f->m.open);
+    release(f, f->m.hdr);
+    release(f, f->m.work);
+    release(f, f->m.pages);
+    release(f, f->m.call);
+    release(f, f->m.npages);
+    release(f, f->m.page_base);
+    release(f, f->m.totals);
+    release(f, f->m.count);
+    release(f, f->m.base);
+    release(f, f->m.bad);
+    release(f, f->m.status);
+    release(f, f->m.committed);
+    release(f, f->args);
+    for (int i = 0; i < kStage; i++) {
+        if (f->h_stage[i]) (void)hipHostFree(f->h_stage[i]);
+        if (f->ev_stage[i]) (void)hipEventDestroy(f->ev_stage[i]);
+    }
+    delete f;
+}
+
+extern "C" int vbm_ogg_feed_scan(vbm_ogg_feed *f, int n, const int *ids, const uint8_t *d_data,
+                                 const long long *chunk_offsets, const uint8_t *end, vbm_ogg_feed_info *d_info,
+                                 long long *d_totals, void *stream)
+{
+    int rc = check_scan(f, false, n, ids, d_data, chunk_offsets, d_info, d_totals, "vbm_ogg_feed_scan");
+    if (rc) return rc;
+    hipStream_t q = (hipStream_t)stream;
+    rc = upload_args(f, n, ids, chunk_offsets, end, q, "vbm_ogg_feed_scan: upload of the arguments");
+    if (rc) return rc;
+    f->scanned = true;
+    f->n = n;
+    f->span = chunk_offsets[n] - chunk_offsets[0];
+    const FeedArgs a = args_view(f->args, n);
+    if (n > 0) {
+        hipLaunchKernelGGL(k_feed_gather, wave_grid(n), dim3(256), 0, q, n, a, f->m, f->caps, d_data);
+        hipLaunchKernelGGL(k_feed_walk, dim3((n + 63) / 64), dim3(64), 0, q, n, a, f->m, f->caps);
+    }
+    hipLaunchKernelGGL(k_feed_scan_pages, dim3(1), dim3(256), 0, q, n, f->m.npages, f->m.page_base);
+    if (n > 0) hipLaunchKernelGGL(k_feed_crc, page_grid(f), dim3(256), 0, q, n, f->pow, a, f->m);
+    if (n > 0) hipLaunchKernelGGL(k_feed_settle, dim3((n + 63) / 64), dim3(64), 0, q, n, a, f->m, f->caps);
+    hipLaunchKernelGGL(k_feed_scan_counts, dim3(1), dim3(256), 0, q, n, f->m, d_totals);
+    if (n > 0) hipLaunchKernelGGL(k_feed_info, dim3((n + 255) / 256), dim3(256), 0, q, n, f->m, d_info);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_scan: launch");
+}
+
+extern "C" int vbm_ogg_feed_fill(vbm_ogg_feed *f, uint8_t *d_payload, long long payload_cap, long long *d_offsets,
+                                 long long *d_granulepos, uint8_t *d_eos, long long packet_cap, void *stream)
+{
+    int rc = check_fill(f, false, d_payload, payload_cap, d_offsets, d_granulepos, d_eos, packet_cap, "vbm_ogg_feed_fill");
+    if (rc) return rc;
+    hipStream_t q = (hipStream_t)stream;
+    const FeedArgs a = args_view(f->args, f->n);
+    // bases that are never written through (no header part here; no payload bytes when d_payload is null) stay non-null
+    const OggDmxOut out = {f->m.hdr, d_payload ? d_payload : f->m.work, d_offsets, d_granulepos, d_eos};
+    hipLaunchKernelGGL(k_feed_fill, page_grid(f), dim3(256), 0, q, f->n, a, f->m, f->caps, packet_cap, payload_cap, out);
+    hipLaunchKernelGGL(k_feed_commit, page_grid(f), dim3(256), 0, q, f->n, a, f->m, f->caps);
+    hipLaunchKernelGGL(k_feed_mark, dim3(1), dim3(1), 0, q, f->m);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_fill: launch");
+}
+
+extern "C" int vbm_ogg_feed_status(vbm_ogg_feed *f, int *status, void *stream)
+{
+    if (!f || !status) return fail(VBM_EINVAL, "vbm_ogg_feed_status: null pointer");
+    if (f->host) {
+        *status = *f->m.status;
+        return VBM_OK;
+    }
+    hipError_t e = hipMemcpyAsync(status, f->m.status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_status");
+}
+
+extern "C" int vbm_ogg_feed_headers(vbm_ogg_feed *f, int id, uint8_t *headers, long long cap, int *sizes, void *stream)
+{
+    if (!f || !sizes) return fail(VBM_EINVAL, "vbm_ogg_feed_headers: null pointer");
+    if (id < 0 || id >= f->max_streams) return fail(VBM_EINVAL, "vbm_ogg_feed_headers: stream id out of range");
+    hipStream_t q = (hipStream_t)stream;
+    OggFeedState st;
+    if (f->host) {
+        st = f->m.state[id];
+    } else {
+        hipError_t e = hipMemcpyAsync(&st, f->m.state + id, sizeof(st), hipMemcpyDeviceToHost, q);
+        if (e == hipSuccess) e = hipStreamSynchronize(q);
+        if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_ogg_feed_headers: state");
+    }
+    if (st.packets < 3 || st.h2 < 0 || st.h2 > f->caps.header_cap)
+        return fail(VBM_EINVAL, "vbm_ogg_feed_headers: the stream has not completed its three header packets");
+    sizes[0] = (int)st.h0, sizes[1] = (int)(st.h1 - st.h0), sizes[2] = (int)(st.h2 - st.h1);
+    if (!headers) return VBM_OK;
+    if (cap < st.h2) return fail(VBM_EINVAL, "vbm_ogg_feed_headers: cap is below the header packets' size");
+    const uint8_t *src = f->m.hdr + (size_t)id * (size_t)f->caps.header_cap;
+    if (f->host) {
+        memcpy(headers, src, (size_t)st.h2);
+        return VBM_OK;
+    }
+    hipError_t e = hipMemcpyAsync(headers, src, (size_t)st.h2, hipMemcpyDeviceToHost, q);
+    if (e == hipSuccess) e = hipStreamSynchronize(q);
+    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_headers: copy");
+}
+
+extern "C" int vbm_ogg_feed_reset_streams(vbm_ogg_feed *f, int n, const int *ids, void *stream)
+{
+    if (!f) return fail(VBM_EINVAL, "vbm_ogg_feed_reset_streams: null pointer");
+    int rc = check_ids(f, n, ids, "vbm_ogg_feed_reset_streams");
+    if (rc) return rc;
+    f->scanned = false;                             // a scan made before the reset is not filled after it
+    if (f->host) {
+        for (int i = 0; i < n; i++) f->m.state[ids[i]] = OggFeedState{};
+        return VBM_OK;
+    }
+    if (n == 0) return VBM_OK;
+    hipStream_t q = (hipStream_t)stream;
+    rc = upload_args(f, n, ids, nullptr, nullptr, q, "vbm_ogg_feed_reset_streams: upload of the ids");
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_feed_reset, dim3((n + 255) / 256), dim3(256), 0, q, n, args_view(f->args, n).ids,
+                       f->m.state);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_reset_streams: launch");
+}
+
+// ---- the same on the CPU: the functions of ogg_feed.h and ogg_demux.h, stream after stream and page after page ------
+extern "C" int vbm_host_ogg_feed_scan(vbm_ogg_feed *f, int n, const int *ids, const uint8_t *data,
+                                      const long long *chunk_offsets, const uint8_t *end, vbm_ogg_feed_info *info,
+                                      long long *totals)
+{
+    int rc = check_scan(f, true, n, ids, data, chunk_offsets, info, totals, "vbm_host_ogg_feed_scan");
+    if (rc) return rc;
+    const uint32_t *T = crc_table().t;
+    pack_args(f->args, n, ids, chunk_offsets, end);
+    f->scanned = true;
+    f->host_committed = false;
+    f->n = n;
+    f->span = chunk_offsets[n] - chunk_offsets[0];
+    const FeedArgs a = args_view(f->args, n);
+    const FeedMem &m = f->m;
+    long long npages = 0, packets = 0, payload = 0;
+    for (int i = 0; i < n; i++) {
+        const OggFeedState &st = m.state[ids[i]];
+        if (!st.status && !st.done) {                              // gather
+            const int tail = oggfeed_tail_in(st, f->caps);
+            uint8_t *run = m.work + feed_at(a.off, i, f->caps);
+            if (tail) memcpy(run, m.tail + (size_t)ids[i] * (size_t)f->caps.max_page_carry, (size_t)tail);
+            if (a.off[i + 1] > a.off[i]) memcpy(run + tail, data + a.off[i], (size_t)(a.off[i + 1] - a.off[i]));
+        }
+        OggFeedCall c;
+        feed_walk_one(a, m, f->caps, i, INT_MAX, false, c);
+        const OggDmxPage *pages = m.pages + feed_first_rec(a.off, i);
+        for (int k = 0; k < c.npages; k++) {
+            const uint8_t *h = m.work + pages[k].at;
+            if (oggdmx_crc_matches(T, f->pow, h, pages[k].len, oggdmx_crc_run(T, 0, h, pages[k].len))) continue;
+            feed_walk_one(a, m, f->caps, i, k, true, c);           // pages from the bad one on are not taken
+            break;
+        }
+        c.packet_base = packets, c.payload_base = payload;
+        packets += c.packets;
+        payload += c.payload_bytes;
+        m.page_base[i] = npages;
+        npages += c.npages;
+        m.call[i] = c;
+        oggfeed_info(c, info[i]);
+    }
+    m.page_base[n] = npages;
+    m.totals[0] = totals[0] = packets;
+    m.totals[1] = totals[1] = payload;
+    return VBM_OK;
+}
+
+extern "C" int vbm_host_ogg_feed_fill(vbm_ogg_feed *f, uint8_t *payload, long long payload_cap, long long *offsets,
+                                      long long *granulepos, uint8_t *eos, long long packet_cap)
+{
+    int rc = check_fill(f, true, payload, payload_cap, offsets, granulepos, eos, packet_cap, "vbm_host_ogg_feed_fill");
+    if (rc) return rc;
+    const FeedMem &m = f->m;
+    if (f->host_committed) {
+        *m.status = VBM_EINVAL;
+        return VBM_OK;
+    }
+    if (m.totals[0] > packet_cap || m.totals[1] > payload_cap) {
+        *m.status = VBM_OGG_DEMUX_ECAP;
+        return VBM_OK;
+    }
+    *m.status = 0;
+    const FeedArgs a = args_view(f->args, f->n);
+    // bases that are never written through (no header part here; no payload bytes when payload is null) stay non-null
+    const OggDmxOut out = {m.hdr, payload ? payload : m.work, offsets, granulepos, eos};
+    const OggDmxOut keep = {m.hdr, m.open, nullptr, nullptr, nullptr};
+    offsets[0] = 0;
+    for (int i = 0; i < f->n; i++) {
+        const OggFeedCall &c = m.call[i];
+        const OggDmxPage *pages = m.pages + feed_first_rec(a.off, i);
+        const int open_in = c.open_in < f->caps.max_packet_bytes ? c.open_in : f->caps.max_packet_bytes;
+        if (open_in > 0)
+            memcpy(out.payload + c.payload_base, m.open + (size_t)c.slot * (size_t)f->caps.max_packet_bytes, (size_t)open_in);
+        for (int k = 0; k < c.npages; k++) {
+            OggDmxPageCtx x;
+            oggfeed_ctx_payload(m.work, pages[k], c, x);
+            int last_end = -1, bytes = 0, ends = 0;
+            for (int s = 0; s < x.nseg; s++)
+                if (x.h[27 + s] < 255) last_end = s;
+            for (int s = 0; s < x.nseg; s++) {
+                bytes += x.h[27 + s];
+                if (x.h[27 + s] < 255) oggdmx_packet_end(x, out, ends++, bytes, s == last_end);
+            }
+            const OggDmxSplit sp = oggdmx_body_split(x, out);
+            if (sp.n_p) memcpy(sp.dst_p, sp.src_p, (size_t)sp.n_p);
+        }
+        // commit: after the stream's payload has been read out of its open store
+        for (int k = 0; k < c.npages; k++) {
+            OggDmxPageCtx xh, xo;
+            oggfeed_ctx_keep(m.work, pages[k], c, f->caps, xh, xo);
+            const OggDmxSplit sh = oggdmx_body_split(xh, keep), so = oggdmx_body_split(xo, keep);
+            if (sh.n_h) memcpy(sh.dst_h, sh.src_h, (size_t)sh.n_h);
+            if (so.n_p) memcpy(so.dst_p, so.src_p, (size_t)so.n_p);
+        }
+        const int tail = c.next.tail;
+        if (tail > 0 && tail <= f->caps.max_page_carry)
+            memcpy(m.tail + (size_t)c.slot * (size_t)f->caps.max_page_carry, m.work + c.pos_end, (size_t)tail);
+        m.state[c.slot] = c.next;
+    }
+    f->host_committed = true;
+    return VBM_OK;
+}

@@ -446,3 +446,144 @@ def demux_ogg_device(files, host=False):
         return dm.demux(blobs)
     finally:
         dm.close()
+
+
+FEED_INFO = np.dtype([("status", "<i4"), ("headers_ready", "<i4"), ("header_bytes", "<i4", (3,)), ("serialno", "<u4"),
+                      ("packets", "<i8"), ("payload_bytes", "<i8"), ("packet_base", "<i8"), ("payload_base", "<i8"),
+                      ("pending", "<i8"), ("consumed", "<i8")])       # vbm_ogg_feed_info
+
+
+class FeedResult:
+    """What OggFeed.push returns.  Per list entry i, on the host: ids[i], counts[i] (audio packets the call completed
+    for that slot), status[i] (0, VBM_EOGG or VBM_OGG_FEED_EBIG: sticky) and info[i] (FEED_INFO: vbm_ogg_feed_info).
+    For the call: payload uint8 [bytes], offsets int64 [P + 1], granulepos int64 [P], eos uint8 [P] — torch tensors on
+    the device (numpy arrays with host=True) holding ONE CSR over the packets of all entries in list order."""
+
+    def __init__(self, ids, info, payload, offsets, granulepos, eos):
+        self.ids, self.info = ids, info
+        self.payload, self.offsets, self.granulepos, self.eos = payload, offsets, granulepos, eos
+        self.counts = info["packets"].astype(np.int64)
+        self.status = info["status"].tolist()
+
+    def __len__(self):
+        return len(self.ids)
+
+
+class OggFeed:
+    """The Ogg demux for live streams (vbm_ogg_feed_scan / _fill): max_streams slots, each fed the next bytes of its
+    stream, cut anywhere, up to max_call_bytes bytes per push() over all slots.
+
+        feed = OggFeed(nstreams, nstreams * 8192)
+        r = feed.push(ids, chunks)                # one H2D of the chunks, scan, a small D2H, fill
+        live = [i for i, c in enumerate(r.counts) if c]
+        pcm, n, _, _ = dec.synthesis_runs(r.ids[live], r.counts[live], r.payload, r.offsets,
+                                          granulepos=r.granulepos, eos=r.eos)
+
+    (with every listed slot live, r.ids and r.counts go in as they are).  feed.headers(id) returns the stream's three
+    header packets once info["headers_ready"] is set.  host=True runs the CPU twin on numpy arrays (no GPU needed)."""
+
+    EOGG, EBIG = -1002, -1003
+
+    def __init__(self, max_streams, max_call_bytes, max_page_carry=65307, max_packet_bytes=65536, header_cap=16384,
+                 host=False, device=None):
+        self.max_streams, self.max_call_bytes, self.host = int(max_streams), int(max_call_bytes), bool(host)
+        self._h = C.c_void_p()
+        self.device = None
+        args = (self.max_streams, self.max_call_bytes, int(max_page_carry), int(max_packet_bytes), int(header_cap))
+        if host:
+            check(lib.vbm_host_ogg_feed_create(C.byref(self._h), *args), "vbm_host_ogg_feed_create")
+        else:
+            import torch
+            self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+            with torch.cuda.device(self.device):
+                check(lib.vbm_ogg_feed_create(C.byref(self._h), *args), "vbm_ogg_feed_create")
+
+    def _q(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def push(self, ids, chunks, end=False, offsets=None):
+        """ids: the slots, each at most once.  chunks: one bytes-like per slot (uploaded in one copy), or ONE uint8
+        tensor on the device (a numpy array with host=True) with offsets int64 [n + 1] on the host, chunk i being
+        chunks[offsets[i]:offsets[i + 1]].  end: True / False for all, or one flag per slot.  -> FeedResult"""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
+        n = len(ids)
+        if offsets is None:
+            blobs = [bytes(c) for c in chunks]
+            if len(blobs) != n:
+                raise ValueError("one chunk per id")
+            off = np.zeros(n + 1, np.int64)
+            np.cumsum([len(b) for b in blobs], out=off[1:])
+            raw = np.frombuffer(b"".join(blobs), np.uint8)
+            if not self.host:
+                import torch
+                raw = (torch.from_numpy(raw.copy()).to(self.device) if len(raw)
+                       else torch.empty(0, dtype=torch.uint8, device=self.device))
+        else:
+            raw, off = chunks, np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+            if len(off) != n + 1:
+                raise ValueError("offsets must have len(ids) + 1 entries")
+        flags = np.ascontiguousarray(np.broadcast_to(np.asarray(end, dtype=np.uint8), (n,)))
+        if self.host:
+            info, totals = np.zeros(n, FEED_INFO), np.zeros(2, np.int64)
+            check(lib.vbm_host_ogg_feed_scan(self._h, n, ids.ctypes.data, raw.ctypes.data if len(raw) else None,
+                                             off.ctypes.data, flags.ctypes.data, info.ctypes.data if n else None,
+                                             totals.ctypes.data), "vbm_host_ogg_feed_scan")
+            P, B = int(totals[0]), int(totals[1])
+            payload, offs = np.zeros(B, np.uint8), np.zeros(P + 1, np.int64)
+            gp, eos = np.zeros(P, np.int64), np.zeros(P, np.uint8)
+            check(lib.vbm_host_ogg_feed_fill(self._h, payload.ctypes.data if B else None, B, offs.ctypes.data,
+                                             gp.ctypes.data if P else None, eos.ctypes.data if P else None, P),
+                  "vbm_host_ogg_feed_fill")
+            return FeedResult(ids, info, payload, offs, gp, eos)
+        import torch
+        dev, q = self.device, self._q()
+        with torch.cuda.device(dev):
+            # totals and infos in one buffer: one small D2H
+            d_meta = torch.empty(16 + n * FEED_INFO.itemsize, dtype=torch.uint8, device=dev)
+            check(lib.vbm_ogg_feed_scan(self._h, n, ids.ctypes.data, raw.data_ptr() if raw.numel() else None, off.ctypes.data,
+                                        flags.ctypes.data, d_meta.data_ptr() + 16 if n else None, d_meta.data_ptr(), q),
+                  "vbm_ogg_feed_scan")
+            meta = d_meta.cpu().numpy()
+            totals, info = meta[:16].view(np.int64), meta[16:].view(FEED_INFO)
+            P, B = int(totals[0]), int(totals[1])
+            payload = torch.empty(B, dtype=torch.uint8, device=dev)
+            offs = torch.empty(P + 1, dtype=torch.int64, device=dev)
+            gp = torch.empty(P, dtype=torch.int64, device=dev)
+            eos = torch.empty(P, dtype=torch.uint8, device=dev)
+            # the buffers have the sizes the scan returned: this fill cannot fall short, so its status word is not waited for
+            check(lib.vbm_ogg_feed_fill(self._h, payload.data_ptr() if B else None, B, offs.data_ptr(),
+                                        gp.data_ptr() if P else None, eos.data_ptr() if P else None, P, q),
+                  "vbm_ogg_feed_fill")
+        return FeedResult(ids, info.copy(), payload, offs, gp, eos)
+
+    def headers(self, id):
+        """-> the three header packets of slot `id` as bytes (for DecodeSetup); VbmError until they are complete"""
+        sizes = (C.c_int * 3)()
+        q = None if self.host else self._q()
+        check(lib.vbm_ogg_feed_headers(self._h, int(id), None, 0, sizes, q), "vbm_ogg_feed_headers")
+        a, b, c = sizes[0], sizes[1], sizes[2]
+        buf = np.zeros(max(1, a + b + c), np.uint8)
+        check(lib.vbm_ogg_feed_headers(self._h, int(id), buf.ctypes.data, a + b + c, sizes, q), "vbm_ogg_feed_headers")
+        h = buf.tobytes()
+        return [h[:a], h[a:a + b], h[a + b:a + b + c]]
+
+    def reset(self, ids):
+        """those slots are free for new streams"""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
+        check(lib.vbm_ogg_feed_reset_streams(self._h, len(ids), ids.ctypes.data, None if self.host else self._q()),
+              "vbm_ogg_feed_reset_streams")
+
+    def close(self):
+        if self._h:
+            if not self.host:
+                import torch
+                torch.cuda.synchronize(self.device)
+            lib.vbm_ogg_feed_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
