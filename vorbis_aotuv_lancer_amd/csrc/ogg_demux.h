@@ -1,6 +1,7 @@
 // Ogg demux for many whole files at once: the acceptance rules of demux() in capi_stream.cpp (vbm_ogg_demux), written
 // once for the host twin (vbm_host_ogg_demux_*) and the device kernels (ogg_demux.hip).  Page format: the reference's
-// doc/framing.html.
+// doc/framing.html.  The incremental form (ogg_feed.h, ogg_feed.hip) uses the same statements: the page walk and the
+// counts it carries, the CRC, a page's fields, the packet-end rule, the body split, and the device helpers at the end.
 //
 // What makes the rule parallel: demux() appends the body of every page to one byte run per file and cuts it where a
 // lacing value below 255 ends a packet.  So a body byte's place in the output is the number of body bytes in front of
@@ -28,12 +29,16 @@ struct OggDmxPage {          // one page the walk accepted
     int pad;
 };
 
-struct OggDmxWalk {          // one file while its pages are walked
-    long long pos, end;      // next byte to read, end of the file
+struct OggDmxCounts {       // what a walk carries from page to page, and the feed from call to call; all zero = no page yet
     long long body, packets; // body bytes seen, packets completed
     long long last_end;      // body bytes through the last completed packet
     long long h0, h1, h2;    // ... through each of the first three packets
     uint32_t serial, seq;    // the stream's serial number (once a page has been seen), the next page number
+};
+
+struct OggDmxWalk {          // one file while its pages are walked
+    long long pos, end;      // next byte to read, end of the file
+    OggDmxCounts cnt;
     int partial;             // a packet is open at the end of the last page
 };
 
@@ -50,53 +55,56 @@ VBMX_HD long long oggdmx_rd64(const uint8_t *p)
 VBMX_HD void oggdmx_walk_begin(OggDmxWalk &w, long long begin, long long end)
 {
     w.pos = begin, w.end = end;
-    w.body = w.packets = w.last_end = 0;
-    w.h0 = w.h1 = w.h2 = 0;
-    w.serial = w.seq = 0;
+    w.cnt = OggDmxCounts{};
     w.partial = 0;
 }
 
-// The next page of the file: 1 and its record, 0 at the end of the file, -1 where demux() fails (CRC apart, which
-// the page-parallel pass checks).  No byte is read before it is known to lie in front of w.end, and every page taken
-// moves w.pos on by at least 27 bytes.
+// The next page of the file, and the only reader of a page header:
+//    1  the page is taken: its record is in pg, and w has moved past it (by at least 27 bytes)
+//    0  w.pos has reached w.end
+//   -1  the header breaks a rule of demux() (CRC apart, which the page-parallel pass checks)
+//   -2  the header, the lacing table or the body is not all in front of w.end
+// A header that is all there is judged before the rest of the page is looked for, so a caller that may see more bytes
+// later (the feed) treats -2 as "not yet"; for a whole file both are failures.  No byte is read before it is known to
+// lie in front of w.end, and w is untouched unless the result is 1.
 VBMX_HD int oggdmx_walk_step(const uint8_t *data, OggDmxWalk &w, OggDmxPage &pg)
 {
     if (w.pos >= w.end) return 0;
     const long long left = w.end - w.pos;
-    if (left < 27) return -1;                                      // no capture pattern / truncated page header
+    if (left < 27) return -2;                                      // truncated page header
     const uint8_t *h = data + w.pos;
     if (h[0] != 'O' || h[1] != 'g' || h[2] != 'g' || h[3] != 'S') return -1;
     if (h[4] != 0) return -1;                                      // stream structure version
     const int flags = h[5], nseg = h[26];
-    if (left - 27 < nseg) return -1;                               // truncated page
     if (!(flags & 1) && w.partial) return -1;                      // a packet continues into a page that is not a continuation
     const uint32_t sno = oggdmx_rd32(h + 14), seq = oggdmx_rd32(h + 18);
-    if (w.seq != 0 && sno != w.serial) return -1;                  // chained or multiplexed streams
-    if (seq != w.seq) return -1;                                   // page sequence counts from 0
-    long long body = w.body, packets = w.packets, last_end = w.last_end;
+    if (w.cnt.seq != 0 && sno != w.cnt.serial) return -1;          // chained or multiplexed streams
+    if (seq != w.cnt.seq) return -1;                               // page sequence counts from 0
+    if (left - 27 < nseg) return -2;                               // truncated lacing table
+    OggDmxCounts c = w.cnt;
     int partial = w.partial;
     for (int i = 0; i < nseg; i++) {
         const int lv = h[27 + i];
-        body += lv;
+        c.body += lv;
         partial = lv == 255;
         if (lv < 255) {
-            if (packets == 0) w.h0 = body;
-            if (packets == 1) w.h1 = body;
-            if (packets == 2) w.h2 = body;
-            packets++;
-            last_end = body;
+            if (c.packets == 0) c.h0 = c.body;
+            if (c.packets == 1) c.h1 = c.body;
+            if (c.packets == 2) c.h2 = c.body;
+            c.packets++;
+            c.last_end = c.body;
         }
     }
-    const long long body_len = body - w.body;
-    if (left - 27 - nseg < body_len) return -1;                    // truncated page
+    const long long body_len = c.body - w.cnt.body;
+    if (left - 27 - nseg < body_len) return -2;                    // truncated body
     pg.at = w.pos;
-    pg.body_before = w.body;
-    pg.pkt_before = w.packets;
+    pg.body_before = w.cnt.body;
+    pg.pkt_before = w.cnt.packets;
     pg.len = 27 + nseg + (int)body_len;
     pg.pad = 0;
-    w.serial = sno;
-    w.seq = seq + 1;                                               // 2^32 pages would need a file of 108 GB
-    w.body = body, w.packets = packets, w.last_end = last_end;
+    c.serial = sno;
+    c.seq = seq + 1;                                               // 2^32 pages would need a file of 108 GB
+    w.cnt = c;
     w.partial = partial;
     w.pos += pg.len;
     return 1;
@@ -105,16 +113,17 @@ VBMX_HD int oggdmx_walk_step(const uint8_t *data, OggDmxWalk &w, OggDmxPage &pg)
 // what the walk leaves in a file's info: counts of a good file, VBM_EOGG and zeros otherwise (bases: the scan)
 VBMX_HD void oggdmx_walk_end(const OggDmxWalk &w, bool ok, int npages, vbm_ogg_file_info &fi)
 {
-    ok = ok && w.packets >= 3;                                     // fewer than three header packets
-    ok = ok && w.h2 < (1ll << 31);                                 // header_bytes are ints: no Vorbis header comes near
+    const OggDmxCounts &c = w.cnt;
+    ok = ok && c.packets >= 3;                                     // fewer than three header packets
+    ok = ok && c.h2 < (1ll << 31);                                 // header_bytes are ints: no Vorbis header comes near
     fi.status = ok ? 0 : VBM_EOGG;
     fi.pages = ok ? npages : 0;
-    fi.serialno = ok ? w.serial : 0u;
-    fi.header_bytes[0] = ok ? (int)w.h0 : 0;
-    fi.header_bytes[1] = ok ? (int)(w.h1 - w.h0) : 0;
-    fi.header_bytes[2] = ok ? (int)(w.h2 - w.h1) : 0;
-    fi.packets = ok ? w.packets - 3 : 0;
-    fi.payload_bytes = ok ? w.last_end - w.h2 : 0;
+    fi.serialno = ok ? c.serial : 0u;
+    fi.header_bytes[0] = ok ? (int)c.h0 : 0;
+    fi.header_bytes[1] = ok ? (int)(c.h1 - c.h0) : 0;
+    fi.header_bytes[2] = ok ? (int)(c.h2 - c.h1) : 0;
+    fi.packets = ok ? c.packets - 3 : 0;
+    fi.payload_bytes = ok ? c.last_end - c.h2 : 0;
     fi.packet_base = fi.payload_base = fi.header_base = 0;
 }
 
@@ -154,6 +163,12 @@ VBMX_HD bool oggdmx_crc_matches(const uint32_t *T, const OggMuxPow &pw, const ui
     return (whole ^ oggmux_crc_shift(pw, field, (uint32_t)(len - 26))) == oggdmx_rd32(h + 22);
 }
 
+// the serial form: the page at h, len bytes, carries its own checksum
+VBMX_HD bool oggdmx_page_crc_ok(const uint32_t *T, const OggMuxPow &pw, const uint8_t *h, int len)
+{
+    return oggdmx_crc_matches(T, pw, h, len, oggdmx_crc_run(T, 0, h, len));
+}
+
 // ---- fill: where a page's segments and body bytes go ---------------------------------------------------------------
 struct OggDmxOut {           // the buffers of a fill call
     uint8_t *headers, *payload;
@@ -169,7 +184,8 @@ struct OggDmxPageCtx {       // a page of a good file, as fill sees it
     long long packet_base, payload_base, header_base;
 };
 
-VBMX_HD void oggdmx_page_ctx(const uint8_t *data, const OggDmxPage &pg, const vbm_ogg_file_info &fi, OggDmxPageCtx &c)
+// what a page record and the page's own header say of it; pkt_before, H, E and the bases are the caller's
+VBMX_HD void oggdmx_page_fields(const uint8_t *data, const OggDmxPage &pg, OggDmxPageCtx &c)
 {
     c.h = data + pg.at;
     c.nseg = c.h[26];
@@ -177,6 +193,11 @@ VBMX_HD void oggdmx_page_ctx(const uint8_t *data, const OggDmxPage &pg, const vb
     c.body_len = pg.len - 27 - c.nseg;
     c.granule = oggdmx_rd64(c.h + 6);
     c.body_before = pg.body_before;
+}
+
+VBMX_HD void oggdmx_page_ctx(const uint8_t *data, const OggDmxPage &pg, const vbm_ogg_file_info &fi, OggDmxPageCtx &c)
+{
+    oggdmx_page_fields(data, pg, c);
     c.pkt_before = pg.pkt_before;
     c.H = (long long)fi.header_bytes[0] + fi.header_bytes[1] + fi.header_bytes[2];
     c.E = c.H + fi.payload_bytes;
@@ -195,6 +216,18 @@ VBMX_HD void oggdmx_packet_end(const OggDmxPageCtx &c, const OggDmxOut &o, int e
     if (q < 3) return;
     o.granulepos[c.packet_base + (q - 3)] = last ? c.granule : -1;
     o.eos[c.packet_base + (q - 3)] = ((c.flags & 4) && last) ? 1 : 0;
+}
+
+// every packet end of a page, segment after segment (the host fills; the kernels: dmx_wave_packet_ends)
+VBMX_HD void oggdmx_page_packet_ends(const OggDmxPageCtx &c, const OggDmxOut &o)
+{
+    int last_end = -1, bytes = 0, ends = 0;
+    for (int i = 0; i < c.nseg; i++)
+        if (c.h[27 + i] < 255) last_end = i;
+    for (int i = 0; i < c.nseg; i++) {
+        bytes += c.h[27 + i];
+        if (c.h[27 + i] < 255) oggdmx_packet_end(c, o, ends++, bytes, i == last_end);
+    }
 }
 
 // The page's body is bytes [body_before, body_before + body_len) of the file's run: the part below H goes to the
@@ -233,10 +266,18 @@ VBMX_HD int oggdmx_file_of_page(const long long *page_base, int nfiles, long lon
     return lo;
 }
 
+// ... and its number among that file's (list entry's) pages
+VBMX_HD int oggdmx_entry_of_page(const long long *page_base, int n, long long p, long long &k)
+{
+    const int i = oggdmx_file_of_page(page_base, n, p);
+    k = p - page_base[i];
+    return i;
+}
+
 VBMX_HD long long oggdmx_first_slot(const long long *off, int f) { return (off[f] - off[0]) / 27; }
 
 #ifdef __HIPCC__
-// ---- device helpers of the page-parallel kernels (ogg_demux.hip, ogg_feed.hip) ---------------------------------------
+// ---- device helpers of the single-block scans and the page-parallel kernels (ogg_demux.hip, ogg_feed.hip) -------------
 // exclusive prefix of v over the block's 256 threads on top of `carry`, which moves on by the block's sum
 __device__ __forceinline__ long long block_exclusive(long long v, long long &carry, long long *wave_sum)
 {
@@ -256,6 +297,41 @@ __device__ __forceinline__ long long block_exclusive(long long v, long long &car
     carry += total;
     __syncthreads();                                // wave_sum is rewritten by the next scan
     return at;
+}
+
+// exclusive prefix over v[0, n) by one block of 256 threads, four consecutive entries per thread and step -> out, *total
+template <int STRIDE>
+__device__ __forceinline__ void block_scan_array(int n, const long long *v, long long *out, long long *total, long long *wave_sum)
+{
+    long long carry = 0;
+    for (int first = 0; first < n; first += 1024) {
+        const int i0 = first + threadIdx.x * 4;
+        long long x[4], sum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            x[j] = i0 + j < n ? v[(long long)(i0 + j) * STRIDE] : 0;
+            sum += x[j];
+        }
+        long long at = block_exclusive(sum, carry, wave_sum);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (i0 + j < n) out[(long long)(i0 + j) * STRIDE] = at;
+            at += x[j];
+        }
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+// The CRC of the page at h, len bytes, by the 64 lanes of a wavefront: lane l takes bytes [l * chunk, (l + 1) * chunk),
+// multiplies by x^(8 * bytes after it), and the xor over the lanes is the code of the page as it stands.  True (in every
+// lane) when the field holds the page's checksum.
+__device__ __forceinline__ bool dmx_wave_page_crc(const uint32_t *T, const OggMuxPow &pw, const uint8_t *h, int len, int lane)
+{
+    const int chunk = (len + 63) >> 6, a = lane * chunk, b = min(len, a + chunk);
+    uint32_t crc = 0;
+    if (a < b) crc = oggmux_crc_shift(pw, oggdmx_crc_run(T, 0, h + a, b - a), (uint32_t)(len - b));
+    for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
+    return oggdmx_crc_matches(T, pw, h, len, crc);
 }
 
 // n bytes src -> dst by the 64 lanes of a wavefront.  Dword stores to the aligned middle of dst; a misaligned source is

@@ -1,26 +1,25 @@
-// Ogg demux on the device for many whole files per call (rules and workspace: ogg_demux.h), its host twin, and the
-// C ABI over both (include/vorbis_mi355x.h, "Ogg demux, batch form").
+// Ogg demux on the device for many whole files per call (rules, workspace and device helpers: ogg_demux.h), its host
+// twin, and the C ABI over both (include/vorbis_mi355x.h, "Ogg demux, batch form"; host scaffold: twin_host.h).
 //
 //   scan:  k_dmx_walk        one lane per file: page after page, every header checked against the file's end before it
 //                            is read; records each page's start and the body bytes / packets in front of it
-//          k_dmx_scan_pages  one block: exclusive scan of the files' page counts -> dense page numbers
+//          k_dmx_scan_pages  one block, four files per thread: exclusive scan of the page counts -> dense page numbers
 //          k_dmx_crc         one wavefront per page: 64 contiguous chunks, combined by the linearity of the code
+//                            (dmx_wave_page_crc); a bad page marks its file
 //          k_dmx_scan_info   one block: final status per file, exclusive scans of packets / payload / header bytes
 //   fill:  k_dmx_fill        one wavefront per page: four lacing values per lane, a wave prefix sum gives every packet
 //                            end its CSR slot; then the body goes to the headers and the payload (dword stores;
 //                            misaligned sources through two aligned loads and a funnel shift)
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include <string.h>
 #include <new>
 #include <string>
 
 #include "ogg_demux.h"
-#include "vbm_internal.h"
+#include "twin_host.h"
 
 namespace {
 
-constexpr int kStage = 2;          // pinned staging slots for the file offsets
 constexpr int kPageBlocks = 2048;  // most blocks (of four wavefronts) a page-parallel kernel is launched with
 
 // ---- kernels ---------------------------------------------------------------------------------------------------
@@ -53,13 +52,7 @@ __global__ void __launch_bounds__(64) k_dmx_walk(int nfiles, const uint8_t *data
 __global__ void __launch_bounds__(256) k_dmx_scan_pages(int nfiles, const long long *npages, long long *page_base)
 {
     __shared__ long long wave_sum[4];
-    long long carry = 0;
-    for (int base = 0; base < nfiles; base += 256) {
-        const int f = base + threadIdx.x;
-        const long long at = block_exclusive(f < nfiles ? npages[f] : 0, carry, wave_sum);
-        if (f < nfiles) page_base[f] = at;
-    }
-    if (threadIdx.x == 0) page_base[nfiles] = carry;
+    block_scan_array<1>(nfiles, npages, page_base, page_base + nfiles, wave_sum);
 }
 
 __global__ void __launch_bounds__(256) k_dmx_crc(int nfiles, OggMuxPow pw, const uint8_t *data, const long long *off,
@@ -71,15 +64,11 @@ __global__ void __launch_bounds__(256) k_dmx_crc(int nfiles, OggMuxPow pw, const
     const int lane = threadIdx.x & 63;
     const long long total = page_base[nfiles], nwaves = (long long)gridDim.x * 4;
     for (long long p = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); p < total; p += nwaves) {
-        const int f = oggdmx_file_of_page(page_base, nfiles, p);
-        const OggDmxPage pg = pages[oggdmx_first_slot(off, f) + (p - page_base[f])];
-        const uint8_t *h = data + pg.at;
-        // lane l takes bytes [l * chunk, (l + 1) * chunk) of the page, then multiplies by x^(8 * bytes after it)
-        const int L = pg.len, chunk = (L + 63) >> 6, a = lane * chunk, b = min(L, a + chunk);
-        uint32_t crc = 0;
-        if (a < b) crc = oggmux_crc_shift(pw, oggdmx_crc_run(T, 0, h + a, b - a), (uint32_t)(L - b));
-        for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
-        if (lane == 0 && !oggdmx_crc_matches(T, pw, h, L, crc)) crc_bad[f] = 1;
+        long long k;
+        const int f = oggdmx_entry_of_page(page_base, nfiles, p, k);
+        const OggDmxPage pg = pages[oggdmx_first_slot(off, f) + k];
+        const bool ok = dmx_wave_page_crc(T, pw, data + pg.at, pg.len, lane);
+        if (lane == 0 && !ok) crc_bad[f] = 1;
     }
 }
 
@@ -130,11 +119,12 @@ __global__ void __launch_bounds__(256) k_dmx_fill(int nfiles, const uint8_t *dat
     const int lane = threadIdx.x & 63;
     const long long total = page_base[nfiles], nwaves = (long long)gridDim.x * 4;
     for (long long p = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); p < total; p += nwaves) {
-        const int f = oggdmx_file_of_page(page_base, nfiles, p);
+        long long k;
+        const int f = oggdmx_entry_of_page(page_base, nfiles, p, k);
         const vbm_ogg_file_info fi = info[f];
         if (fi.status) continue;                    // its CRC failed after the walk had counted its pages
         OggDmxPageCtx c;
-        oggdmx_page_ctx(data, pages[oggdmx_first_slot(off, f) + (p - page_base[f])], fi, c);
+        oggdmx_page_ctx(data, pages[oggdmx_first_slot(off, f) + k], fi, c);
         dmx_wave_packet_ends(c, out, lane);
         const OggDmxSplit s = oggdmx_body_split(c, out);
         if (s.n_h) dmx_wave_copy(s.dst_h, s.src_h, (int)s.n_h, lane);
@@ -142,33 +132,16 @@ __global__ void __launch_bounds__(256) k_dmx_fill(int nfiles, const uint8_t *dat
     }
 }
 
-// ---- host side -------------------------------------------------------------------------------------------------
-
-struct CrcTable {
-    uint32_t t[256];
-    CrcTable() { for (uint32_t i = 0; i < 256; i++) t[i] = oggmux_crc_entry(i); }
-};
-
-const CrcTable &crc_table()
-{
-    static const CrcTable c;
-    return c;
-}
-
-int fail(int code, const std::string &msg)
-{
-    g_vbm_err = msg;
-    return code;
-}
-
 }  // namespace
+
+// ---- host side (scaffold: twin_host.h) --------------------------------------------------------------------------
 
 struct vbm_ogg_demuxer {
     bool host = false;
     int max_files = 0;
     long long max_bytes = 0, max_slots = 0;
     OggMuxPow pow;
-    // workspace: device memory, or host memory (calloc) for the twin
+    TwinMem mem;                         // owns the workspace
     long long *off = nullptr;            // [max_files + 1] the call's file offsets
     OggDmxPage *pages = nullptr;         // [max_slots]
     long long *npages = nullptr, *page_base = nullptr;   // [max_files], [max_files + 1]
@@ -176,9 +149,7 @@ struct vbm_ogg_demuxer {
     int *crc_bad = nullptr;              // [max_files]
     long long *totals = nullptr;         // [3]
     int *status = nullptr;               // the status word of the last fill
-    long long *h_stage[kStage] = {};     // device demuxer: pinned, [max_files + 1] each
-    hipEvent_t ev_stage[kStage] = {};
-    int stage_turn = 0;
+    ArgStage stage;                      // device demuxer: the file offsets go up through it, [max_files + 1]
     // the last scan
     bool scanned = false;
     int nfiles = 0;
@@ -187,26 +158,6 @@ struct vbm_ogg_demuxer {
 };
 
 namespace {
-
-template <class T> int alloc(vbm_ogg_demuxer *m, T *&p, size_t n)
-{
-    if (m->host) {
-        p = (T *)calloc(n ? n : 1, sizeof(T));
-        return p ? VBM_OK : fail(VBM_EFAULT, "vbm_ogg_demuxer: out of host memory");
-    }
-    hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
-    if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_ogg_demuxer: hipMalloc");
-    e = hipMemset(p, 0, (n ? n : 1) * sizeof(T));
-    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_demuxer: hipMemset");
-}
-
-template <class T> void release(vbm_ogg_demuxer *m, T *&p)
-{
-    if (!p) return;
-    if (m->host) free(p);
-    else (void)hipFree(p);
-    p = nullptr;
-}
 
 int create(vbm_ogg_demuxer **out, int max_files, long long max_bytes, bool host)
 {
@@ -218,25 +169,22 @@ int create(vbm_ogg_demuxer **out, int max_files, long long max_bytes, bool host)
     }
     vbm_ogg_demuxer *m = new (std::nothrow) vbm_ogg_demuxer();
     if (!m) return fail(VBM_EFAULT, "vbm_ogg_demuxer_create: out of memory");
-    m->host = host;
+    m->host = m->mem.host = host;
     m->max_files = max_files;
     m->max_bytes = max_bytes;
     m->max_slots = max_bytes / 27 + 1;
     m->pow = oggmux_pow_table();
     const size_t F = (size_t)max_files;
-    int rc = alloc(m, m->off, F + 1);
-    if (!rc) rc = alloc(m, m->pages, (size_t)m->max_slots);
-    if (!rc) rc = alloc(m, m->npages, F);
-    if (!rc) rc = alloc(m, m->page_base, F + 1);
-    if (!rc) rc = alloc(m, m->info, F);
-    if (!rc) rc = alloc(m, m->crc_bad, F);
-    if (!rc) rc = alloc(m, m->totals, 3);
-    if (!rc) rc = alloc(m, m->status, 1);
-    for (int i = 0; i < kStage && !rc && !host; i++) {
-        hipError_t e = hipHostMalloc((void **)&m->h_stage[i], (F + 1) * sizeof(long long), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->ev_stage[i], hipEventDisableTiming);
-        if (e != hipSuccess) rc = vbm_set_hip_error(e, "vbm_ogg_demuxer_create: staging");
-    }
+    const char *who = "vbm_ogg_demuxer";
+    int rc = m->mem.get(m->off, F + 1, who);
+    if (!rc) rc = m->mem.get(m->pages, (size_t)m->max_slots, who);
+    if (!rc) rc = m->mem.get(m->npages, F, who);
+    if (!rc) rc = m->mem.get(m->page_base, F + 1, who);
+    if (!rc) rc = m->mem.get(m->info, F, who);
+    if (!rc) rc = m->mem.get(m->crc_bad, F, who);
+    if (!rc) rc = m->mem.get(m->totals, 3, who);
+    if (!rc) rc = m->mem.get(m->status, 1, who);
+    if (!rc && !host) rc = m->stage.create((F + 1) * sizeof(long long), "vbm_ogg_demuxer_create: staging");
     if (rc) {
         vbm_ogg_demuxer_destroy(m);
         return rc;
@@ -248,9 +196,7 @@ int create(vbm_ogg_demuxer **out, int max_files, long long max_bytes, bool host)
 int check_scan(const vbm_ogg_demuxer *m, bool host, int nfiles, const uint8_t *data, const long long *off,
                const vbm_ogg_file_info *info, const long long *totals, const char *who)
 {
-    if (!m || m->host != host)
-        return fail(VBM_EINVAL, std::string(who) + (host ? ": needs a demuxer made by vbm_host_ogg_demuxer_create"
-                                                         : ": needs a demuxer made by vbm_ogg_demuxer_create"));
+    if (int rc = check_kind(m, host, who, "demuxer")) return rc;
     if (nfiles < 0 || nfiles > m->max_files)
         return fail(VBM_EINVAL, std::string(who) + ": nfiles is negative or above max_files");
     if (!off || !totals || (nfiles && !info)) return fail(VBM_EINVAL, std::string(who) + ": null pointer");
@@ -268,9 +214,7 @@ int check_fill(const vbm_ogg_demuxer *m, bool host, const uint8_t *headers, long
                long long payload_cap, const long long *offsets, const long long *granulepos, const uint8_t *eos,
                long long packet_cap, const char *who)
 {
-    if (!m || m->host != host)
-        return fail(VBM_EINVAL, std::string(who) + (host ? ": needs a demuxer made by vbm_host_ogg_demuxer_create"
-                                                         : ": needs a demuxer made by vbm_ogg_demuxer_create"));
+    if (int rc = check_kind(m, host, who, "demuxer")) return rc;
     if (!m->scanned) return fail(VBM_EINVAL, std::string(who) + ": no scan has been made on this demuxer");
     if (header_cap < 0 || payload_cap < 0 || packet_cap < 0) return fail(VBM_EINVAL, std::string(who) + ": negative capacity");
     if (!offsets || (header_cap && !headers) || (payload_cap && !payload) || (packet_cap && (!granulepos || !eos)))
@@ -307,18 +251,8 @@ extern "C" int vbm_host_ogg_demuxer_create(vbm_ogg_demuxer **dm, int max_files, 
 extern "C" void vbm_ogg_demuxer_destroy(vbm_ogg_demuxer *m)
 {
     if (!m) return;
-    release(m, m->off);
-    release(m, m->pages);
-    release(m, m->npages);
-    release(m, m->page_base);
-    release(m, m->info);
-    release(m, m->crc_bad);
-    release(m, m->totals);
-    release(m, m->status);
-    for (int i = 0; i < kStage; i++) {
-        if (m->h_stage[i]) (void)hipHostFree(m->h_stage[i]);
-        if (m->ev_stage[i]) (void)hipEventDestroy(m->ev_stage[i]);
-    }
+    m->mem.free_all();
+    m->stage.destroy();
     delete m;
 }
 
@@ -328,15 +262,13 @@ extern "C" int vbm_ogg_demux_scan(vbm_ogg_demuxer *m, int nfiles, const uint8_t 
     int rc = check_scan(m, false, nfiles, d_data, file_offsets, d_info, d_totals, "vbm_ogg_demux_scan");
     if (rc) return rc;
     hipStream_t q = (hipStream_t)stream;
-    // the offsets go up through a pinned slot; the only wait is for the copy out of it two scans ago
-    const int t = m->stage_turn;
-    m->stage_turn = (t + 1) % kStage;
-    hipError_t e = hipEventSynchronize(m->ev_stage[t]);
-    if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_ogg_demux_scan: hipEventSynchronize(stage)");
-    memcpy(m->h_stage[t], file_offsets, ((size_t)nfiles + 1) * sizeof(long long));
-    e = hipMemcpyAsync(m->off, m->h_stage[t], ((size_t)nfiles + 1) * sizeof(long long), hipMemcpyHostToDevice, q);
-    if (e == hipSuccess) e = hipEventRecord(m->ev_stage[t], q);
-    if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_ogg_demux_scan: upload of the file offsets");
+    const size_t off_bytes = ((size_t)nfiles + 1) * sizeof(long long);
+    void *h_off;
+    rc = m->stage.next(h_off, "vbm_ogg_demux_scan: hipEventSynchronize(stage)");
+    if (rc) return rc;
+    memcpy(h_off, file_offsets, off_bytes);
+    rc = m->stage.send(m->off, off_bytes, q, "vbm_ogg_demux_scan: upload of the file offsets");
+    if (rc) return rc;
     remember(m, nfiles, d_data, file_offsets);
     if (nfiles > 0)
         hipLaunchKernelGGL(k_dmx_walk, dim3((nfiles + 63) / 64), dim3(64), 0, q, nfiles, d_data, m->off, m->pages, m->info,
@@ -347,7 +279,7 @@ extern "C" int vbm_ogg_demux_scan(vbm_ogg_demuxer *m, int nfiles, const uint8_t 
                            m->page_base, m->crc_bad);
     hipLaunchKernelGGL(k_dmx_scan_info, dim3(1), dim3(256), 0, q, nfiles, m->info, m->crc_bad, d_info, m->totals,
                        d_totals);
-    e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_demux_scan: launch");
 }
 
@@ -368,13 +300,7 @@ extern "C" int vbm_ogg_demux_fill(vbm_ogg_demuxer *m, uint8_t *d_headers, long l
 extern "C" int vbm_ogg_demux_status(vbm_ogg_demuxer *m, int *status, void *stream)
 {
     if (!m || !status) return fail(VBM_EINVAL, "vbm_ogg_demux_status: null pointer");
-    if (m->host) {
-        *status = *m->status;
-        return VBM_OK;
-    }
-    hipError_t e = hipMemcpyAsync(status, m->status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_demux_status");
+    return read_status(m->host, m->status, status, stream, "vbm_ogg_demux_status");
 }
 
 // ---- the same on the CPU: the functions of ogg_demux.h, file after file and page after page ---------------------------
@@ -394,8 +320,7 @@ extern "C" int vbm_host_ogg_demux_scan(vbm_ogg_demuxer *m, int nfiles, const uin
         int n = 0, r;
         bool crc_ok = true;
         while ((r = oggdmx_walk_step(data, w, pages[n])) == 1) {
-            const uint8_t *h = data + pages[n].at;
-            crc_ok = crc_ok && oggdmx_crc_matches(T, m->pow, h, pages[n].len, oggdmx_crc_run(T, 0, h, pages[n].len));
+            crc_ok = crc_ok && oggdmx_page_crc_ok(T, m->pow, data + pages[n].at, pages[n].len);
             n++;
         }
         vbm_ogg_file_info fi;
@@ -435,13 +360,7 @@ extern "C" int vbm_host_ogg_demux_fill(vbm_ogg_demuxer *m, uint8_t *headers, lon
         for (int p = 0; p < fi.pages; p++) {
             OggDmxPageCtx c;
             oggdmx_page_ctx(m->data, pages[p], fi, c);
-            int last_end = -1, bytes = 0, ends = 0;
-            for (int i = 0; i < c.nseg; i++)
-                if (c.h[27 + i] < 255) last_end = i;
-            for (int i = 0; i < c.nseg; i++) {
-                bytes += c.h[27 + i];
-                if (c.h[27 + i] < 255) oggdmx_packet_end(c, out, ends++, bytes, i == last_end);
-            }
+            oggdmx_page_packet_ends(c, out);
             const OggDmxSplit s = oggdmx_body_split(c, out);
             if (s.n_h) memcpy(s.dst_h, s.src_h, (size_t)s.n_h);
             if (s.n_p) memcpy(s.dst_p, s.src_p, (size_t)s.n_p);

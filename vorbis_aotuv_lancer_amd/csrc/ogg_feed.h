@@ -1,6 +1,7 @@
 // Incremental Ogg demux for many live streams: the rules of demux() in capi_stream.cpp applied as the bytes arrive, written
 // once for the host twin (vbm_host_ogg_feed_*) and the device kernels (ogg_feed.hip) over a fixed-size state per stream
-// slot.  The page walk, the CRC, the packet-end rule and the body split are those of ogg_demux.h.
+// slot.  The page walk (oggdmx_walk_step, whose "not all here yet" is what a feed carries), the carried counts, the CRC,
+// the packet-end rule and the body split are those of ogg_demux.h.
 //
 // A stream's body bytes are numbered over its whole life, as ogg_demux.h numbers them over a file: body byte b of the
 // stream, packet q of the stream.  A call sees the run "carried page tail + chunk", takes the whole pages from it and
@@ -26,10 +27,7 @@ struct OggFeedCaps {
 };
 
 struct OggFeedState {            // one stream slot between calls; all zero = a fresh slot
-    long long body, packets;     // body bytes and packets completed on the pages taken so far
-    long long last_end;          // body bytes through the last completed packet
-    long long h0, h1, h2;        // ... through each of the first three packets
-    uint32_t serial, seq;        // the stream's serial number, the next page number
+    OggDmxCounts cnt;            // over the pages taken so far
     int partial;                 // a packet is open at the end of the last page taken
     int status;                  // sticky: 0, VBM_EOGG, VBM_OGG_FEED_EBIG
     int tail;                    // bytes of the incomplete trailing page in the slot's tail store
@@ -55,28 +53,6 @@ VBMX_HD int oggfeed_tail_in(const OggFeedState &st, const OggFeedCaps &caps)
     return st.tail < 0 ? 0 : (st.tail > caps.max_page_carry ? caps.max_page_carry : st.tail);
 }
 
-// the header checks of demux(): all 27 bytes of the header at h are present
-VBMX_HD bool oggfeed_header_ok(const uint8_t *h, const OggDmxWalk &w)
-{
-    if (h[0] != 'O' || h[1] != 'g' || h[2] != 'g' || h[3] != 'S') return false;
-    if (h[4] != 0) return false;                                   // stream structure version
-    if (!(h[5] & 1) && w.partial) return false;                    // a packet continues into a page that is not a continuation
-    const uint32_t sno = oggdmx_rd32(h + 14), seq = oggdmx_rd32(h + 18);
-    if (w.seq != 0 && sno != w.serial) return false;               // chained or multiplexed streams
-    return seq == w.seq;                                           // page sequence counts from 0
-}
-
-// `left` >= 27 bytes are present from h on: true when they hold the whole page.  Reads the lacing table only when it is
-// present.
-VBMX_HD bool oggfeed_page_whole(const uint8_t *h, long long left)
-{
-    const int nseg = h[26];
-    if (left - 27 < nseg) return false;
-    long long body = 0;
-    for (int i = 0; i < nseg; i++) body += h[27 + i];
-    return left - 27 - nseg >= body;
-}
-
 // One stream, one call.  The run is work[at, run_end): whole pages are taken from it in order, at most `limit` of them,
 // and recorded in pages[0, room).  bad_at_limit: the page after the first `limit` failed its CRC (the second walk of a
 // stream, after the page-parallel CRC pass).  No byte is read before it is known to lie in front of run_end, and every
@@ -89,37 +65,30 @@ VBMX_HD void oggfeed_walk(const uint8_t *work, long long at, long long run_end, 
     c.at = c.pos_end = at;
     c.S = c.E = 0;
     c.packets = c.payload_bytes = c.packet_base = c.payload_base = 0;
-    c.pkt_shift = (st.packets > 3 ? st.packets : 3) - 3;
+    c.pkt_shift = (st.cnt.packets > 3 ? st.cnt.packets : 3) - 3;
     c.npages = c.open_in = 0;
     c.slot = slot, c.pad = 0;
     if (st.status || st.done) return;                              // bytes for a failed or ended stream are ignored
     OggDmxWalk w;
     w.pos = at, w.end = run_end;
-    w.body = st.body, w.packets = st.packets, w.last_end = st.last_end;
-    w.h0 = st.h0, w.h1 = st.h1, w.h2 = st.h2;
-    w.serial = st.serial, w.seq = st.seq;
-    w.partial = st.partial;
+    w.cnt = st.cnt, w.partial = st.partial;
     int status = 0, n = 0;
     while (n < limit) {
-        const long long left = w.end - w.pos;
-        if (left < 27) break;                                      // the header is judged once it is whole
-        const uint8_t *h = work + w.pos;
-        if (!oggfeed_header_ok(h, w)) { status = VBM_EOGG; break; }
-        if (!oggfeed_page_whole(h, left)) break;                   // a partial page is carried
         const OggDmxWalk before = w;
         OggDmxPage pg;
-        if (oggdmx_walk_step(work, w, pg) != 1 || n >= room) {     // cannot happen: the page is whole and passed the checks
-            w = before;
-            status = VBM_EOGG;
+        const int r = oggdmx_walk_step(work, w, pg);
+        if (r != 1) {                                              // the run is used up, or its rest is carried (-2)
+            if (r == -1) status = VBM_EOGG;
             break;
         }
         // the stores the page's body would go to.  Judged page by page, so that the outcome does not depend on where
         // the calls cut the stream.
-        const long long hdr = before.packets >= 3 ? 0 : (w.packets >= 3 ? w.h2 : w.body);
-        const long long open = w.packets >= 3 ? w.body - w.last_end : 0;
-        if (hdr > caps.header_cap || open > caps.max_packet_bytes) {
+        const long long hdr = before.cnt.packets >= 3 ? 0 : (w.cnt.packets >= 3 ? w.cnt.h2 : w.cnt.body);
+        const long long open = w.cnt.packets >= 3 ? w.cnt.body - w.cnt.last_end : 0;
+        const bool big = hdr > caps.header_cap || open > caps.max_packet_bytes;
+        if (n >= room || big) {                                    // no room: cannot happen (a page is 27 bytes or more)
             w = before;
-            status = VBM_OGG_FEED_EBIG;
+            status = n >= room ? VBM_EOGG : VBM_OGG_FEED_EBIG;
             break;
         }
         pages[n++] = pg;
@@ -128,7 +97,7 @@ VBMX_HD void oggfeed_walk(const uint8_t *work, long long at, long long run_end, 
     long long tail = status ? 0 : run_end - w.pos;
     int done = 0;
     if (!status && end_flag) {
-        if (tail > 0 || w.packets < 3) status = VBM_EOGG;          // a truncated page, fewer than three header packets
+        if (tail > 0 || w.cnt.packets < 3) status = VBM_EOGG;      // a truncated page, fewer than three header packets
         tail = 0;
         done = 1;
     } else if (!status && tail > caps.max_page_carry) {
@@ -137,17 +106,14 @@ VBMX_HD void oggfeed_walk(const uint8_t *work, long long at, long long run_end, 
     }
     c.npages = n;
     c.pos_end = w.pos;
-    if (w.packets >= 3) {
-        c.S = st.packets >= 3 ? st.last_end : w.h2;
-        c.E = w.last_end;
-        c.packets = w.packets - 3 - c.pkt_shift;
+    if (w.cnt.packets >= 3) {
+        c.S = st.cnt.packets >= 3 ? st.cnt.last_end : w.cnt.h2;
+        c.E = w.cnt.last_end;
+        c.packets = w.cnt.packets - 3 - c.pkt_shift;
         c.payload_bytes = c.E - c.S;
-        if (st.packets >= 3 && c.packets > 0) c.open_in = (int)(st.body - st.last_end);
+        if (st.cnt.packets >= 3 && c.packets > 0) c.open_in = (int)(st.cnt.body - st.cnt.last_end);
     }
-    c.next.body = w.body, c.next.packets = w.packets, c.next.last_end = w.last_end;
-    c.next.h0 = w.h0, c.next.h1 = w.h1, c.next.h2 = w.h2;
-    c.next.serial = w.serial, c.next.seq = w.seq;
-    c.next.partial = w.partial;
+    c.next.cnt = w.cnt, c.next.partial = w.partial;
     c.next.status = status;
     c.next.tail = (int)tail;
     c.next.done = done;
@@ -155,9 +121,9 @@ VBMX_HD void oggfeed_walk(const uint8_t *work, long long at, long long run_end, 
 
 VBMX_HD void oggfeed_info(const OggFeedCall &c, vbm_ogg_feed_info &fi)
 {
-    const OggFeedState &s = c.next;
+    const OggDmxCounts &s = c.next.cnt;
     const bool ready = s.packets >= 3;
-    fi.status = s.status;
+    fi.status = c.next.status;
     fi.headers_ready = ready ? 1 : 0;
     fi.header_bytes[0] = ready ? (int)s.h0 : 0;
     fi.header_bytes[1] = ready ? (int)(s.h1 - s.h0) : 0;
@@ -167,7 +133,7 @@ VBMX_HD void oggfeed_info(const OggFeedCall &c, vbm_ogg_feed_info &fi)
     fi.payload_bytes = c.payload_bytes;
     fi.packet_base = c.packet_base;
     fi.payload_base = c.payload_base;
-    fi.pending = s.tail;
+    fi.pending = c.next.tail;
     fi.consumed = c.pos_end - c.at;
 }
 
@@ -177,14 +143,9 @@ VBMX_HD void oggfeed_info(const OggFeedCall &c, vbm_ogg_feed_info &fi)
 //            from E on -> the slot's open store, at their distance from E (as the "payload" of a file that starts at E)
 VBMX_HD void oggfeed_ctx_payload(const uint8_t *work, const OggDmxPage &pg, const OggFeedCall &c, OggDmxPageCtx &x)
 {
-    x.h = work + pg.at;
-    x.nseg = x.h[26];
-    x.flags = x.h[5];
-    x.body_len = pg.len - 27 - x.nseg;
-    x.granule = oggdmx_rd64(x.h + 6);
-    x.body_before = pg.body_before;
+    oggdmx_page_fields(work, pg, x);
     x.pkt_before = pg.pkt_before - c.pkt_shift;
-    const bool audio = c.next.packets >= 3;
+    const bool audio = c.next.cnt.packets >= 3;
     const long long b = pg.body_before + x.body_len;               // while the headers are open, all of the body is theirs
     x.H = audio ? c.S : b;
     x.E = audio ? c.E : b;
@@ -195,12 +156,12 @@ VBMX_HD void oggfeed_ctx_keep(const uint8_t *work, const OggDmxPage &pg, const O
                               OggDmxPageCtx &hdr, OggDmxPageCtx &open)
 {
     oggfeed_ctx_payload(work, pg, c, hdr);
-    const bool audio = c.next.packets >= 3;
+    const bool audio = c.next.cnt.packets >= 3;
     const long long b = pg.body_before + hdr.body_len;
-    hdr.H = hdr.E = audio ? c.next.h2 : b;                         // [.., H) -> header store; no payload part
+    hdr.H = hdr.E = audio ? c.next.cnt.h2 : b;                     // [.., H) -> header store; no payload part
     hdr.header_base = (long long)c.slot * caps.header_cap;
     open = hdr;
-    open.H = audio ? c.next.last_end : b;                          // [H, ..) -> open store
+    open.H = audio ? c.next.cnt.last_end : b;                      // [H, ..) -> open store
     open.E = b;
     open.payload_base = (long long)c.slot * caps.max_packet_bytes;
 }

@@ -1,11 +1,13 @@
-// Incremental Ogg demux on the device for many live streams (rules, state and workspace: ogg_feed.h), its host twin, and
-// the C ABI over both (include/vorbis_mi355x.h, "Ogg demux, incremental form").
+// Incremental Ogg demux on the device for many live streams (rules, state and workspace: ogg_feed.h; page rules and
+// device helpers: ogg_demux.h), its host twin, and the C ABI over both (include/vorbis_mi355x.h, "Ogg demux, incremental
+// form"; host scaffold: twin_host.h).
 //
 //   scan:  k_feed_gather      one wavefront per listed stream: carried page tail, then the chunk -> the stream's run in
 //                             the work buffer
-//          k_feed_walk        one lane per listed stream: resumes from the slot's state, takes whole pages, stops at the
-//                             first that is not whole; every read is bounded by the run's end
-//          k_feed_scan_pages  one block: exclusive scan of the page counts -> dense page numbers
+//          k_feed_walk        one lane per listed stream: resumes from the slot's state, takes whole pages
+//                             (oggdmx_walk_step), stops at the first that is not whole; every read is bounded by the
+//                             run's end
+//          k_feed_scan_pages  one block, four entries per thread: exclusive scan of the page counts -> dense page numbers
 //          k_feed_crc         one wavefront per page, as k_dmx_crc; records the first bad page of a stream
 //          k_feed_settle      one lane per listed stream: a stream with a bad page is walked again up to it
 //          k_feed_scan_counts one block: exclusive scans of packets and payload bytes; the totals
@@ -15,20 +17,19 @@
 //          k_feed_commit      one wavefront per page: header bytes and the open packet's bytes to the slot's stores; then
 //                             one wavefront per stream: the unconsumed tail and the new state
 //          k_feed_mark        the scan is committed
+//   reset: k_feed_reset       one lane per listed stream: the slot's state back to all zero
 // Nothing of a slot changes before k_feed_commit, which runs only after a fill that wrote its outputs.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include <string.h>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "ogg_feed.h"
-#include "vbm_internal.h"
+#include "twin_host.h"
 
 namespace {
 
-constexpr int kStage = 2;          // pinned staging slots for the call's host arguments
 constexpr int kWaveBlocks = 2048;  // most blocks (of four wavefronts) a wave-parallel kernel is launched with
 constexpr int kPiece = 1 << 30;    // dmx_wave_copy takes an int
 
@@ -99,29 +100,6 @@ __global__ void __launch_bounds__(64) k_feed_walk(int n, FeedArgs a, FeedMem m, 
     m.bad[i] = INT_MAX;
 }
 
-// exclusive prefix over v[0, n) by one block of 256 threads, four consecutive entries per thread and step -> out, *total
-template <int STRIDE>
-__device__ __forceinline__ void block_scan_array(int n, const long long *v, long long *out, long long *total, long long *wave_sum)
-{
-    long long carry = 0;
-    for (int first = 0; first < n; first += 1024) {
-        const int i0 = first + threadIdx.x * 4;
-        long long x[4], sum = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            x[j] = i0 + j < n ? v[(long long)(i0 + j) * STRIDE] : 0;
-            sum += x[j];
-        }
-        long long at = block_exclusive(sum, carry, wave_sum);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (i0 + j < n) out[(long long)(i0 + j) * STRIDE] = at;
-            at += x[j];
-        }
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
 __global__ void __launch_bounds__(256) k_feed_scan_pages(int n, const long long *npages, long long *page_base)
 {
     __shared__ long long wave_sum[4];
@@ -136,15 +114,11 @@ __global__ void __launch_bounds__(256) k_feed_crc(int n, OggMuxPow pw, FeedArgs 
     const int lane = threadIdx.x & 63;
     const long long total = m.page_base[n], nwaves = (long long)gridDim.x * 4;
     for (long long p = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); p < total; p += nwaves) {
-        const int i = oggdmx_file_of_page(m.page_base, n, p);
-        const long long k = p - m.page_base[i];
+        long long k;
+        const int i = oggdmx_entry_of_page(m.page_base, n, p, k);
         const OggDmxPage pg = m.pages[feed_first_rec(a.off, i) + k];
-        const uint8_t *h = m.work + pg.at;
-        const int L = pg.len, chunk = (L + 63) >> 6, b0 = lane * chunk, b1 = min(L, b0 + chunk);
-        uint32_t crc = 0;
-        if (b0 < b1) crc = oggmux_crc_shift(pw, oggdmx_crc_run(T, 0, h + b0, b1 - b0), (uint32_t)(L - b1));
-        for (int s = 32; s >= 1; s >>= 1) crc ^= __shfl_xor(crc, s, 64);
-        if (lane == 0 && !oggdmx_crc_matches(T, pw, h, L, crc)) atomicMin(&m.bad[i], (int)k);
+        const bool ok = dmx_wave_page_crc(T, pw, m.work + pg.at, pg.len, lane);
+        if (lane == 0 && !ok) atomicMin(&m.bad[i], (int)k);
     }
 }
 
@@ -202,8 +176,8 @@ __global__ void __launch_bounds__(256) k_feed_fill(int n, FeedArgs a, FeedMem m,
     const int lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6);
     const long long total = m.page_base[n], nwaves = (long long)gridDim.x * 4;
     for (long long p = wave; p < total; p += nwaves) {
-        const int i = oggdmx_file_of_page(m.page_base, n, p);
-        const long long k = p - m.page_base[i];
+        long long k;
+        const int i = oggdmx_entry_of_page(m.page_base, n, p, k);
         const OggFeedCall &c = m.call[i];
         if (k >= c.npages) continue;                // behind a page whose CRC failed
         OggDmxPageCtx x;
@@ -227,8 +201,8 @@ __global__ void __launch_bounds__(256) k_feed_commit(int n, FeedArgs a, FeedMem 
     const int lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6);
     const long long total = m.page_base[n], nwaves = (long long)gridDim.x * 4;
     for (long long p = wave; p < total; p += nwaves) {
-        const int i = oggdmx_file_of_page(m.page_base, n, p);
-        const long long k = p - m.page_base[i];
+        long long k;
+        const int i = oggdmx_entry_of_page(m.page_base, n, p, k);
         const OggFeedCall &c = m.call[i];
         if (k >= c.npages) continue;
         OggDmxPageCtx xh, xo;
@@ -257,26 +231,9 @@ __global__ void __launch_bounds__(256) k_feed_reset(int n, const int *ids, OggFe
     if (i < n) state[ids[i]] = OggFeedState{};
 }
 
-// ---- host side -------------------------------------------------------------------------------------------------
-
-struct CrcTable {
-    uint32_t t[256];
-    CrcTable() { for (uint32_t i = 0; i < 256; i++) t[i] = oggmux_crc_entry(i); }
-};
-
-const CrcTable &crc_table()
-{
-    static const CrcTable c;
-    return c;
-}
-
-int fail(int code, const std::string &msg)
-{
-    g_vbm_err = msg;
-    return code;
-}
-
 }  // namespace
+
+// ---- host side (scaffold: twin_host.h) --------------------------------------------------------------------------
 
 struct vbm_ogg_feed {
     bool host = false;
@@ -284,11 +241,10 @@ struct vbm_ogg_feed {
     long long max_call_bytes = 0;
     OggFeedCaps caps = {};
     OggMuxPow pow;
-    FeedMem m = {};                      // device memory, or host memory (calloc) for the twin
+    TwinMem mem;                         // owns what m and args point to
+    FeedMem m = {};
     uint8_t *args = nullptr;             // the call's arguments: off [n + 1], ids [n], end [n]; room for n = max_streams
-    uint8_t *h_stage[kStage] = {};       // device feed: pinned, the size of args
-    hipEvent_t ev_stage[kStage] = {};
-    int stage_turn = 0;
+    ArgStage stage;                      // device feed: they go up through it; the size of args
     std::vector<int> seen;               // [max_streams] the call that last listed a slot
     int call_no = 0;
     // the last scan
@@ -310,26 +266,6 @@ FeedArgs args_view(uint8_t *base, int n)
     return a;
 }
 
-template <class T> int alloc(vbm_ogg_feed *f, T *&p, size_t n)
-{
-    if (f->host) {
-        p = (T *)calloc(n ? n : 1, sizeof(T));
-        return p ? VBM_OK : fail(VBM_EFAULT, "vbm_ogg_feed: out of host memory");
-    }
-    hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
-    if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_ogg_feed: hipMalloc");
-    e = hipMemset(p, 0, (n ? n : 1) * sizeof(T));
-    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed: hipMemset");
-}
-
-template <class T> void release(vbm_ogg_feed *f, T *&p)
-{
-    if (!p) return;
-    if (f->host) free(p);
-    else (void)hipFree(p);
-    p = nullptr;
-}
-
 int create(vbm_ogg_feed **out, int max_streams, long long max_call_bytes, int max_page_carry, int max_packet_bytes,
            int header_cap, bool host)
 {
@@ -343,52 +279,41 @@ int create(vbm_ogg_feed **out, int max_streams, long long max_call_bytes, int ma
     }
     vbm_ogg_feed *f = new (std::nothrow) vbm_ogg_feed();
     if (!f) return fail(VBM_EFAULT, "vbm_ogg_feed_create: out of memory");
-    f->host = host;
+    f->host = f->mem.host = host;
     f->max_streams = max_streams;
     f->max_call_bytes = max_call_bytes;
     f->caps = {max_page_carry, max_packet_bytes, header_cap};
     f->pow = oggmux_pow_table();
     const size_t S = (size_t)max_streams;
+    const char *who = "vbm_ogg_feed";
     int rc = VBM_OK;
     try {
         f->seen.assign(S, 0);
     } catch (const std::bad_alloc &) {
         rc = fail(VBM_EFAULT, "vbm_ogg_feed_create: out of memory");
     }
-    if (!rc) rc = alloc(f, f->m.state, S);
-    if (!rc) rc = alloc(f, f->m.tail, S * (size_t)max_page_carry);
-    if (!rc) rc = alloc(f, f->m.open, S * (size_t)max_packet_bytes);
-    if (!rc) rc = alloc(f, f->m.hdr, S * (size_t)header_cap);
-    if (!rc) rc = alloc(f, f->m.work, (size_t)max_call_bytes + S * (size_t)max_page_carry + 4);
-    if (!rc) rc = alloc(f, f->m.pages, (size_t)(max_call_bytes / 27) + S + 1);
-    if (!rc) rc = alloc(f, f->m.call, S);
-    if (!rc) rc = alloc(f, f->m.npages, S);
-    if (!rc) rc = alloc(f, f->m.page_base, S + 1);
-    if (!rc) rc = alloc(f, f->m.totals, 2);
-    if (!rc) rc = alloc(f, f->m.count, 2 * S);
-    if (!rc) rc = alloc(f, f->m.base, 2 * S);
-    if (!rc) rc = alloc(f, f->m.bad, S);
-    if (!rc) rc = alloc(f, f->m.status, 1);
-    if (!rc) rc = alloc(f, f->m.committed, 1);
-    if (!rc) rc = alloc(f, f->args, args_bytes(max_streams));
-    for (int i = 0; i < kStage && !rc && !host; i++) {
-        hipError_t e = hipHostMalloc((void **)&f->h_stage[i], args_bytes(max_streams), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_stage[i], hipEventDisableTiming);
-        if (e != hipSuccess) rc = vbm_set_hip_error(e, "vbm_ogg_feed_create: staging");
-    }
+    if (!rc) rc = f->mem.get(f->m.state, S, who);
+    if (!rc) rc = f->mem.get(f->m.tail, S * (size_t)max_page_carry, who);
+    if (!rc) rc = f->mem.get(f->m.open, S * (size_t)max_packet_bytes, who);
+    if (!rc) rc = f->mem.get(f->m.hdr, S * (size_t)header_cap, who);
+    if (!rc) rc = f->mem.get(f->m.work, (size_t)max_call_bytes + S * (size_t)max_page_carry + 4, who);
+    if (!rc) rc = f->mem.get(f->m.pages, (size_t)(max_call_bytes / 27) + S + 1, who);
+    if (!rc) rc = f->mem.get(f->m.call, S, who);
+    if (!rc) rc = f->mem.get(f->m.npages, S, who);
+    if (!rc) rc = f->mem.get(f->m.page_base, S + 1, who);
+    if (!rc) rc = f->mem.get(f->m.totals, 2, who);
+    if (!rc) rc = f->mem.get(f->m.count, 2 * S, who);
+    if (!rc) rc = f->mem.get(f->m.base, 2 * S, who);
+    if (!rc) rc = f->mem.get(f->m.bad, S, who);
+    if (!rc) rc = f->mem.get(f->m.status, 1, who);
+    if (!rc) rc = f->mem.get(f->m.committed, 1, who);
+    if (!rc) rc = f->mem.get(f->args, args_bytes(max_streams), who);
+    if (!rc && !host) rc = f->stage.create(args_bytes(max_streams), "vbm_ogg_feed_create: staging");
     if (rc) {
         vbm_ogg_feed_destroy(f);
         return rc;
     }
     *out = f;
-    return VBM_OK;
-}
-
-int check_kind(const vbm_ogg_feed *f, bool host, const char *who)
-{
-    if (!f || f->host != host)
-        return fail(VBM_EINVAL, std::string(who) + (host ? ": needs a feed made by vbm_host_ogg_feed_create"
-                                                         : ": needs a feed made by vbm_ogg_feed_create"));
     return VBM_OK;
 }
 
@@ -415,7 +340,7 @@ int check_ids(vbm_ogg_feed *f, int n, const int *ids, const char *who)
 int check_scan(vbm_ogg_feed *f, bool host, int n, const int *ids, const uint8_t *data, const long long *off,
                const vbm_ogg_feed_info *info, const long long *totals, const char *who)
 {
-    int rc = check_kind(f, host, who);
+    int rc = check_kind(f, host, who, "feed");
     if (rc) return rc;
     if (n < 0 || n > f->max_streams) return fail(VBM_EINVAL, std::string(who) + ": n is negative or above max_streams");
     if (!off || !totals || (n && (!info || !ids))) return fail(VBM_EINVAL, std::string(who) + ": null pointer");
@@ -432,7 +357,7 @@ int check_scan(vbm_ogg_feed *f, bool host, int n, const int *ids, const uint8_t 
 int check_fill(const vbm_ogg_feed *f, bool host, const uint8_t *payload, long long payload_cap, const long long *offsets,
                const long long *granulepos, const uint8_t *eos, long long packet_cap, const char *who)
 {
-    int rc = check_kind(f, host, who);
+    int rc = check_kind(f, host, who, "feed");
     if (rc) return rc;
     if (!f->scanned) return fail(VBM_EINVAL, std::string(who) + ": no scan has been made on this feed");
     if (payload_cap < 0 || packet_cap < 0) return fail(VBM_EINVAL, std::string(who) + ": negative capacity");
@@ -455,15 +380,12 @@ void pack_args(uint8_t *dst, int n, const int *ids, const long long *off, const 
 int upload_args(vbm_ogg_feed *f, int n, const int *ids, const long long *off, const uint8_t *end, hipStream_t q,
                 const char *who)
 {
-    const int t = f->stage_turn;
-    f->stage_turn = (t + 1) % kStage;
-    hipError_t e = hipEventSynchronize(f->ev_stage[t]);
-    if (e != hipSuccess) return vbm_set_hip_error(e, who);
-    pack_args(f->h_stage[t], n, ids, off, end);
+    void *h_args;
+    const int rc = f->stage.next(h_args, who);
+    if (rc) return rc;
+    pack_args((uint8_t *)h_args, n, ids, off, end);
     // one copy: the three arrays lie in one block, in the same layout on both sides
-    e = hipMemcpyAsync(f->args, f->h_stage[t], args_bytes(n), hipMemcpyHostToDevice, q);
-    if (e == hipSuccess) e = hipEventRecord(f->ev_stage[t], q);
-    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, who);
+    return f->stage.send(f->args, args_bytes(n), q, who);
 }
 
 dim3 wave_grid(long long waves)
@@ -493,26 +415,8 @@ extern "C" int vbm_host_ogg_feed_create(vbm_ogg_feed **fd, int max_streams, long
 extern "C" void vbm_ogg_feed_destroy(vbm_ogg_feed *f)
 {
     if (!f) return;
-    release(f, f->m.state);
-    release(f, f->m.tail);
-    release(f, f->m.open);
-    release(f, f->m.hdr);
-    release(f, f->m.work);
-    release(f, f->m.pages);
-    release(f, f->m.call);
-    release(f, f->m.npages);
-    release(f, f->m.page_base);
-    release(f, f->m.totals);
-    release(f, f->m.count);
-    release(f, f->m.base);
-    release(f, f->m.bad);
-    release(f, f->m.status);
-    release(f, f->m.committed);
-    release(f, f->args);
-    for (int i = 0; i < kStage; i++) {
-        if (f->h_stage[i]) (void)hipHostFree(f->h_stage[i]);
-        if (f->ev_stage[i]) (void)hipEventDestroy(f->ev_stage[i]);
-    }
+    f->mem.free_all();
+    f->stage.destroy();
     delete f;
 }
 
@@ -561,13 +465,7 @@ extern "C" int vbm_ogg_feed_fill(vbm_ogg_feed *f, uint8_t *d_payload, long long 
 extern "C" int vbm_ogg_feed_status(vbm_ogg_feed *f, int *status, void *stream)
 {
     if (!f || !status) return fail(VBM_EINVAL, "vbm_ogg_feed_status: null pointer");
-    if (f->host) {
-        *status = *f->m.status;
-        return VBM_OK;
-    }
-    hipError_t e = hipMemcpyAsync(status, f->m.status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_status");
+    return read_status(f->host, f->m.status, status, stream, "vbm_ogg_feed_status");
 }
 
 extern "C" int vbm_ogg_feed_headers(vbm_ogg_feed *f, int id, uint8_t *headers, long long cap, int *sizes, void *stream)
@@ -583,17 +481,18 @@ extern "C" int vbm_ogg_feed_headers(vbm_ogg_feed *f, int id, uint8_t *headers, l
         if (e == hipSuccess) e = hipStreamSynchronize(q);
         if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_ogg_feed_headers: state");
     }
-    if (st.packets < 3 || st.h2 < 0 || st.h2 > f->caps.header_cap)
+    const OggDmxCounts &c = st.cnt;
+    if (c.packets < 3 || c.h2 < 0 || c.h2 > f->caps.header_cap)
         return fail(VBM_EINVAL, "vbm_ogg_feed_headers: the stream has not completed its three header packets");
-    sizes[0] = (int)st.h0, sizes[1] = (int)(st.h1 - st.h0), sizes[2] = (int)(st.h2 - st.h1);
+    sizes[0] = (int)c.h0, sizes[1] = (int)(c.h1 - c.h0), sizes[2] = (int)(c.h2 - c.h1);
     if (!headers) return VBM_OK;
-    if (cap < st.h2) return fail(VBM_EINVAL, "vbm_ogg_feed_headers: cap is below the header packets' size");
+    if (cap < c.h2) return fail(VBM_EINVAL, "vbm_ogg_feed_headers: cap is below the header packets' size");
     const uint8_t *src = f->m.hdr + (size_t)id * (size_t)f->caps.header_cap;
     if (f->host) {
-        memcpy(headers, src, (size_t)st.h2);
+        memcpy(headers, src, (size_t)c.h2);
         return VBM_OK;
     }
-    hipError_t e = hipMemcpyAsync(headers, src, (size_t)st.h2, hipMemcpyDeviceToHost, q);
+    hipError_t e = hipMemcpyAsync(headers, src, (size_t)c.h2, hipMemcpyDeviceToHost, q);
     if (e == hipSuccess) e = hipStreamSynchronize(q);
     return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_headers: copy");
 }
@@ -646,8 +545,7 @@ extern "C" int vbm_host_ogg_feed_scan(vbm_ogg_feed *f, int n, const int *ids, co
         feed_walk_one(a, m, f->caps, i, INT_MAX, false, c);
         const OggDmxPage *pages = m.pages + feed_first_rec(a.off, i);
         for (int k = 0; k < c.npages; k++) {
-            const uint8_t *h = m.work + pages[k].at;
-            if (oggdmx_crc_matches(T, f->pow, h, pages[k].len, oggdmx_crc_run(T, 0, h, pages[k].len))) continue;
+            if (oggdmx_page_crc_ok(T, f->pow, m.work + pages[k].at, pages[k].len)) continue;
             feed_walk_one(a, m, f->caps, i, k, true, c);           // pages from the bad one on are not taken
             break;
         }
@@ -694,13 +592,7 @@ extern "C" int vbm_host_ogg_feed_fill(vbm_ogg_feed *f, uint8_t *payload, long lo
         for (int k = 0; k < c.npages; k++) {
             OggDmxPageCtx x;
             oggfeed_ctx_payload(m.work, pages[k], c, x);
-            int last_end = -1, bytes = 0, ends = 0;
-            for (int s = 0; s < x.nseg; s++)
-                if (x.h[27 + s] < 255) last_end = s;
-            for (int s = 0; s < x.nseg; s++) {
-                bytes += x.h[27 + s];
-                if (x.h[27 + s] < 255) oggdmx_packet_end(x, out, ends++, bytes, s == last_end);
-            }
+            oggdmx_page_packet_ends(x, out);
             const OggDmxSplit sp = oggdmx_body_split(x, out);
             if (sp.n_p) memcpy(sp.dst_p, sp.src_p, (size_t)sp.n_p);
         }

@@ -1,5 +1,5 @@
 // Ogg paging on the device for every stream of a call at once (rule and sizes: ogg_mux.h), its host twin, and the
-// C ABI over both (include/vorbis_mi355x.h, "stream wrapper, device form").
+// C ABI over both (include/vorbis_mi355x.h, "stream wrapper, device form"; host scaffold: twin_host.h).
 //
 //   k_mux_index   one lane per row: the row joins its stream's list (order of the appends is free: plan sorts)
 //   k_mux_plan    one lane per stream: sort by packetno, queue the lacing values, run the rule, record the pages
@@ -9,7 +9,6 @@
 //                 shift), CRC in 64 contiguous chunks combined by the linearity of the code, then the commit: what
 //                 the pages did not take becomes the queue of the next call
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include <algorithm>
 #include <string.h>
 #include <new>
@@ -17,7 +16,7 @@
 #include <vector>
 
 #include "ogg_mux.h"
-#include "vbm_internal.h"
+#include "twin_host.h"
 
 #define OGGMUX_MAX_ROWS 64   // rows per stream per call the emit kernel's piece table holds
 
@@ -283,26 +282,9 @@ __global__ void __launch_bounds__(256) k_mux_reset(int n, const int *start, OggM
     count[s] = 0;
 }
 
-// ---- host side -------------------------------------------------------------------------------------------------
-
-struct CrcTable {
-    uint32_t t[256];
-    CrcTable() { for (uint32_t i = 0; i < 256; i++) t[i] = oggmux_crc_entry(i); }
-};
-
-const CrcTable &crc_table()
-{
-    static const CrcTable c;
-    return c;
-}
-
-int fail(int code, const std::string &msg)
-{
-    g_vbm_err = msg;
-    return code;
-}
-
 }  // namespace
+
+// ---- host side (scaffold: twin_host.h) --------------------------------------------------------------------------
 
 struct vbm_ogg_mux {
     OggMuxDims d;
@@ -310,7 +292,7 @@ struct vbm_ogg_mux {
     const vbm_setup_handle *setup = nullptr;
     OggMuxPow pow;
     int qstride = 0;
-    // per-stream state and call scratch: device memory, or host memory (calloc) for the twin
+    TwinMem mem;                        // owns the per-stream state and the call scratch
     OggMuxHead *head = nullptr;
     uint8_t *lacing = nullptr;
     long long *gran = nullptr;
@@ -325,26 +307,6 @@ struct vbm_ogg_mux {
 
 namespace {
 
-template <class T> int alloc(vbm_ogg_mux *m, T *&p, size_t n)
-{
-    if (m->host) {
-        p = (T *)calloc(n ? n : 1, sizeof(T));
-        return p ? VBM_OK : fail(VBM_EFAULT, "vbm_ogg_mux: out of host memory");
-    }
-    hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
-    if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_ogg_mux: hipMalloc");
-    e = hipMemset(p, 0, (n ? n : 1) * sizeof(T));
-    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_mux: hipMemset");
-}
-
-template <class T> void release(vbm_ogg_mux *m, T *&p)
-{
-    if (!p) return;
-    if (m->host) free(p);
-    else (void)hipFree(p);
-    p = nullptr;
-}
-
 int create(vbm_ogg_mux **out, const vbm_setup_handle *setup, int nstreams, int max_packet_bytes, int max_rows,
            int queue_bytes, bool host)
 {
@@ -358,22 +320,23 @@ int create(vbm_ogg_mux **out, const vbm_setup_handle *setup, int nstreams, int m
     }
     vbm_ogg_mux *m = new (std::nothrow) vbm_ogg_mux();
     if (!m) return fail(VBM_EFAULT, "vbm_ogg_mux_create: out of memory");
-    m->host = host;
+    m->host = m->mem.host = host;
     m->setup = setup;
     m->d = oggmux_dims(nstreams, max_packet_bytes, max_rows ? max_rows : 16, queue_bytes);
     m->pow = oggmux_pow_table();
     m->qstride = (m->d.queue_bytes + 15) & ~15;
     const size_t S = (size_t)nstreams;
-    int rc = alloc(m, m->head, S);
-    if (!rc) rc = alloc(m, m->lacing, S * m->d.lace_cap);
-    if (!rc) rc = alloc(m, m->gran, S * m->d.lace_cap);
-    if (!rc) rc = alloc(m, m->body, S * m->qstride);
-    if (!rc) rc = alloc(m, m->rows, S * m->d.max_rows);
-    if (!rc) rc = alloc(m, m->count, S);
-    if (!rc) rc = alloc(m, m->pages, S * m->d.max_pages);
-    if (!rc) rc = alloc(m, m->call, S);
-    if (!rc && !host) rc = alloc(m, m->sizes, S);
-    if (!rc && !host) rc = alloc(m, m->d_start, S * 3);
+    const char *who = "vbm_ogg_mux";
+    int rc = m->mem.get(m->head, S, who);
+    if (!rc) rc = m->mem.get(m->lacing, S * m->d.lace_cap, who);
+    if (!rc) rc = m->mem.get(m->gran, S * m->d.lace_cap, who);
+    if (!rc) rc = m->mem.get(m->body, S * m->qstride, who);
+    if (!rc) rc = m->mem.get(m->rows, S * m->d.max_rows, who);
+    if (!rc) rc = m->mem.get(m->count, S, who);
+    if (!rc) rc = m->mem.get(m->pages, S * m->d.max_pages, who);
+    if (!rc) rc = m->mem.get(m->call, S, who);
+    if (!rc && !host) rc = m->mem.get(m->sizes, S, who);
+    if (!rc && !host) rc = m->mem.get(m->d_start, S * 3, who);
     if (rc) {
         vbm_ogg_mux_destroy(m);
         return rc;
@@ -386,8 +349,7 @@ int check_call(const vbm_ogg_mux *m, bool host, const uint8_t *packets, long lon
                const vbm_packet_info *info, int nrows, uint8_t *out, long long out_capacity, long long *offsets,
                int *status, const char *who)
 {
-    if (!m || m->host != host)
-        return fail(VBM_EINVAL, std::string(who) + (host ? ": needs a mux made by vbm_host_ogg_mux_create" : ": needs a mux made by vbm_ogg_mux_create"));
+    if (int rc = check_kind(m, host, who, "mux")) return rc;
     if (nrows < 0 || (nrows && (!packets || !packet_bytes || !info)) || !out || !offsets || !status)
         return fail(VBM_EINVAL, std::string(who) + ": null pointer or negative row count");
     if (nrows > 0 && packet_stride < m->d.max_packet_bytes)
@@ -415,16 +377,7 @@ extern "C" int vbm_host_ogg_mux_create(vbm_ogg_mux **mux, const vbm_setup_handle
 extern "C" void vbm_ogg_mux_destroy(vbm_ogg_mux *m)
 {
     if (!m) return;
-    release(m, m->head);
-    release(m, m->lacing);
-    release(m, m->gran);
-    release(m, m->body);
-    release(m, m->rows);
-    release(m, m->count);
-    release(m, m->pages);
-    release(m, m->call);
-    release(m, m->sizes);
-    release(m, m->d_start);
+    m->mem.free_all();
     delete m;
 }
 

@@ -278,6 +278,72 @@ def read_ogg(data):
     return out[:3], out[3:], gps[3:], eoss[3:]
 
 
+def _split3(h, sizes, at=0):
+    """-> the three header packets, of those sizes, that lie in the bytes h from h[at] on"""
+    a, b, c = (int(x) for x in sizes[:3])
+    return [h[at:at + a], h[at + a:at + a + b], h[at + a + b:at + a + b + c]]
+
+
+def _join(blobs, device=None):
+    """[bytes] -> (raw uint8 [all of them end to end], offsets int64 [n + 1]); raw goes to `device` in one copy if one is
+    given, and is a numpy array otherwise"""
+    off = np.zeros(len(blobs) + 1, np.int64)
+    np.cumsum([len(b) for b in blobs], out=off[1:])
+    raw = np.frombuffer(b"".join(blobs), np.uint8)
+    if device is not None:
+        import torch
+        raw = torch.from_numpy(raw.copy()).to(device) if len(raw) else torch.empty(0, dtype=torch.uint8, device=device)
+    return raw, off
+
+
+def _csr_buffers(P, B, device=None):
+    """-> (payload uint8 [B], offsets int64 [P + 1], granulepos int64 [P], eos uint8 [P]) for a fill: torch tensors on
+    `device`, or numpy arrays without one"""
+    if device is None:
+        return np.zeros(B, np.uint8), np.zeros(P + 1, np.int64), np.zeros(P, np.int64), np.zeros(P, np.uint8)
+    import torch
+    return (torch.empty(B, dtype=torch.uint8, device=device), torch.empty(P + 1, dtype=torch.int64, device=device),
+            torch.empty(P, dtype=torch.int64, device=device), torch.empty(P, dtype=torch.uint8, device=device))
+
+
+class _TwinHandle:
+    """The handle of a C object that comes as a device form (made under its device, destroyed after a synchronize) and a
+    host twin: vbm_[host_]ogg_<kind>_create(&h, *args) and vbm_ogg_<kind>_destroy(h)."""
+
+    def __init__(self, kind, host, device, *args):
+        self.host, self.device, self._h = bool(host), None, C.c_void_p()
+        self._destroy = getattr(lib, f"vbm_ogg_{kind}_destroy")
+        name = f"vbm_host_ogg_{kind}_create" if host else f"vbm_ogg_{kind}_create"
+        if host:
+            check(getattr(lib, name)(C.byref(self._h), *args), name)
+        else:
+            import torch
+            self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+            with torch.cuda.device(self.device):
+                check(getattr(lib, name)(C.byref(self._h), *args), name)
+
+    def _q(self):
+        """the current stream of the device; None for the host twin"""
+        if self.host:
+            return None
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if self._h:
+            if not self.host:
+                import torch
+                torch.cuda.synchronize(self.device)
+            self._destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def demux_ogg(data):
     """read_ogg in C (vbm_ogg_demux), with the packets in CSR form for Decoder.synthesis_runs: .ogg bytes of ONE
     logical Vorbis stream -> (headers [3 packets], data uint8 [bytes], offsets int64 [P+1], granulepos int64 [P],
@@ -288,15 +354,10 @@ def demux_ogg(data):
     sizes = (C.c_long * 5)()
     check(lib.vbm_ogg_demux(buf, len(raw), sizes, None, None, None, None, None), "vbm_ogg_demux")
     hdr = np.zeros(max(1, sizes[0] + sizes[1] + sizes[2]), np.uint8)
-    body = np.zeros(sizes[4], np.uint8)
-    offsets = np.zeros(sizes[3] + 1, np.int64)
-    gp = np.zeros(sizes[3], np.int64)
-    eos = np.zeros(sizes[3], np.uint8)
+    body, offsets, gp, eos = _csr_buffers(sizes[3], sizes[4])
     check(lib.vbm_ogg_demux(buf, len(raw), sizes, hdr.ctypes.data, body.ctypes.data if len(body) else None,
                             offsets.ctypes.data, gp.ctypes.data, eos.ctypes.data), "vbm_ogg_demux")
-    h = hdr.tobytes()
-    headers = [h[:sizes[0]], h[sizes[0]:sizes[0] + sizes[1]], h[sizes[0] + sizes[1]:sizes[0] + sizes[1] + sizes[2]]]
-    return headers, body, offsets, gp, eos
+    return _split3(hdr.tobytes(), sizes), body, offsets, gp, eos
 
 
 FILE_INFO = np.dtype([("status", "<i4"), ("pages", "<i4"), ("serialno", "<u4"), ("header_bytes", "<i4", (3,)),
@@ -341,7 +402,7 @@ class DemuxBatch:
         return self.offsets[a:a + n + 1], self.granulepos[a:a + n], self.eos[a:a + n]
 
 
-class DeviceDemuxer:
+class DeviceDemuxer(_TwinHandle):
     """vbm_ogg_demux for many whole .ogg files per call, on the device (vbm_ogg_demux_scan / _fill): up to max_files
     files of up to max_bytes bytes together per demux() call.
 
@@ -355,34 +416,21 @@ class DeviceDemuxer:
     EOGG = -1002
 
     def __init__(self, max_files, max_bytes, host=False, device=None):
-        self.max_files, self.max_bytes, self.host = int(max_files), int(max_bytes), bool(host)
-        self._h = C.c_void_p()
-        self.device = None
-        if host:
-            check(lib.vbm_host_ogg_demuxer_create(C.byref(self._h), self.max_files, self.max_bytes),
-                  "vbm_host_ogg_demuxer_create")
-        else:
-            import torch
-            self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-            with torch.cuda.device(self.device):
-                check(lib.vbm_ogg_demuxer_create(C.byref(self._h), self.max_files, self.max_bytes),
-                      "vbm_ogg_demuxer_create")
+        self.max_files, self.max_bytes = int(max_files), int(max_bytes)
+        super().__init__("demuxer", host, device, self.max_files, self.max_bytes)
 
     def demux(self, files):
         names, blobs = _read_files(files)
         n = len(blobs)
-        off = np.zeros(n + 1, np.int64)
-        np.cumsum([len(b) for b in blobs], out=off[1:])
-        raw = np.frombuffer(b"".join(blobs), np.uint8)
-        info = np.zeros(n, FILE_INFO)
-        totals = np.zeros(3, np.int64)
+        raw, off = _join(blobs, self.device)
         if self.host:
+            info, totals = np.zeros(n, FILE_INFO), np.zeros(3, np.int64)
             check(lib.vbm_host_ogg_demux_scan(self._h, n, raw.ctypes.data if len(raw) else None, off.ctypes.data,
                                               info.ctypes.data if n else None, totals.ctypes.data),
                   "vbm_host_ogg_demux_scan")
             P, B, H = (int(x) for x in totals)
-            hdr, payload = np.zeros(H, np.uint8), np.zeros(B, np.uint8)
-            offsets, gp, eos = np.zeros(P + 1, np.int64), np.zeros(P, np.int64), np.zeros(P, np.uint8)
+            hdr = np.zeros(H, np.uint8)
+            payload, offsets, gp, eos = _csr_buffers(P, B)
             check(lib.vbm_host_ogg_demux_fill(self._h, hdr.ctypes.data if H else None, H, payload.ctypes.data if B else None,
                                               B, offsets.ctypes.data, gp.ctypes.data if P else None,
                                               eos.ctypes.data if P else None, P), "vbm_host_ogg_demux_fill")
@@ -391,51 +439,26 @@ class DeviceDemuxer:
             h = hdr.tobytes()
         else:
             import torch
-            dev = self.device
-            q = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            d_raw = torch.from_numpy(raw.copy()).to(dev) if len(raw) else torch.empty(0, dtype=torch.uint8, device=dev)
+            dev, q = self.device, self._q()
             # info and totals in one buffer: one small D2H
             d_meta = torch.empty(n * FILE_INFO.itemsize + 24, dtype=torch.uint8, device=dev)
-            check(lib.vbm_ogg_demux_scan(self._h, n, d_raw.data_ptr() if len(raw) else None, off.ctypes.data,
+            check(lib.vbm_ogg_demux_scan(self._h, n, raw.data_ptr() if len(raw) else None, off.ctypes.data,
                                          d_meta.data_ptr() + 24 if n else None, d_meta.data_ptr(), q), "vbm_ogg_demux_scan")
             meta = d_meta.cpu().numpy()
             totals, info = meta[:24].view(np.int64), meta[24:].view(FILE_INFO)
             P, B, H = (int(x) for x in totals)
             d_hdr = torch.empty(H, dtype=torch.uint8, device=dev)
-            payload = torch.empty(B, dtype=torch.uint8, device=dev)
-            offsets = torch.empty(P + 1, dtype=torch.int64, device=dev)
-            gp = torch.empty(P, dtype=torch.int64, device=dev)
-            eos = torch.empty(P, dtype=torch.uint8, device=dev)
+            payload, offsets, gp, eos = _csr_buffers(P, B, dev)
             check(lib.vbm_ogg_demux_fill(self._h, d_hdr.data_ptr() if H else None, H, payload.data_ptr() if B else None, B,
                                          offsets.data_ptr(), gp.data_ptr() if P else None, eos.data_ptr() if P else None, P,
                                          q), "vbm_ogg_demux_fill")
-            h = d_hdr.cpu().numpy().tobytes()              # waits for the fill: d_raw is free after it
+            h = d_hdr.cpu().numpy().tobytes()              # waits for the fill: raw is free after it
             st = C.c_int(-1)
             check(lib.vbm_ogg_demux_status(self._h, C.byref(st), q), "vbm_ogg_demux_status")
         if st.value:
             raise VbmError(f"vbm_ogg_demux_fill: status {st.value} with buffers of the sizes the scan returned")
-        headers = []
-        for f in range(n):
-            if info["status"][f]:
-                headers.append(None)
-                continue
-            a, hb = int(info["header_base"][f]), info["header_bytes"][f]
-            headers.append([h[a:a + hb[0]], h[a + hb[0]:a + hb[0] + hb[1]], h[a + hb[0] + hb[1]:a + hb[0] + hb[1] + hb[2]]])
+        headers = [None if fi["status"] else _split3(h, fi["header_bytes"], int(fi["header_base"])) for fi in info]
         return DemuxBatch(names, info, headers, payload, offsets, gp, eos)
-
-    def close(self):
-        if self._h:
-            if not self.host:
-                import torch
-                torch.cuda.synchronize(self.device)
-            lib.vbm_ogg_demuxer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def demux_ogg_device(files, host=False):
@@ -469,7 +492,7 @@ class FeedResult:
         return len(self.ids)
 
 
-class OggFeed:
+class OggFeed(_TwinHandle):
     """The Ogg demux for live streams (vbm_ogg_feed_scan / _fill): max_streams slots, each fed the next bytes of its
     stream, cut anywhere, up to max_call_bytes bytes per push() over all slots.
 
@@ -486,21 +509,9 @@ class OggFeed:
 
     def __init__(self, max_streams, max_call_bytes, max_page_carry=65307, max_packet_bytes=65536, header_cap=16384,
                  host=False, device=None):
-        self.max_streams, self.max_call_bytes, self.host = int(max_streams), int(max_call_bytes), bool(host)
-        self._h = C.c_void_p()
-        self.device = None
-        args = (self.max_streams, self.max_call_bytes, int(max_page_carry), int(max_packet_bytes), int(header_cap))
-        if host:
-            check(lib.vbm_host_ogg_feed_create(C.byref(self._h), *args), "vbm_host_ogg_feed_create")
-        else:
-            import torch
-            self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-            with torch.cuda.device(self.device):
-                check(lib.vbm_ogg_feed_create(C.byref(self._h), *args), "vbm_ogg_feed_create")
-
-    def _q(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self.max_streams, self.max_call_bytes = int(max_streams), int(max_call_bytes)
+        super().__init__("feed", host, device, self.max_streams, self.max_call_bytes, int(max_page_carry),
+                         int(max_packet_bytes), int(header_cap))
 
     def push(self, ids, chunks, end=False, offsets=None):
         """ids: the slots, each at most once.  chunks: one bytes-like per slot (uploaded in one copy), or ONE uint8
@@ -512,13 +523,7 @@ class OggFeed:
             blobs = [bytes(c) for c in chunks]
             if len(blobs) != n:
                 raise ValueError("one chunk per id")
-            off = np.zeros(n + 1, np.int64)
-            np.cumsum([len(b) for b in blobs], out=off[1:])
-            raw = np.frombuffer(b"".join(blobs), np.uint8)
-            if not self.host:
-                import torch
-                raw = (torch.from_numpy(raw.copy()).to(self.device) if len(raw)
-                       else torch.empty(0, dtype=torch.uint8, device=self.device))
+            raw, off = _join(blobs, self.device)
         else:
             raw, off = chunks, np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
             if len(off) != n + 1:
@@ -530,8 +535,7 @@ class OggFeed:
                                              off.ctypes.data, flags.ctypes.data, info.ctypes.data if n else None,
                                              totals.ctypes.data), "vbm_host_ogg_feed_scan")
             P, B = int(totals[0]), int(totals[1])
-            payload, offs = np.zeros(B, np.uint8), np.zeros(P + 1, np.int64)
-            gp, eos = np.zeros(P, np.int64), np.zeros(P, np.uint8)
+            payload, offs, gp, eos = _csr_buffers(P, B)
             check(lib.vbm_host_ogg_feed_fill(self._h, payload.ctypes.data if B else None, B, offs.ctypes.data,
                                              gp.ctypes.data if P else None, eos.ctypes.data if P else None, P),
                   "vbm_host_ogg_feed_fill")
@@ -547,10 +551,7 @@ class OggFeed:
             meta = d_meta.cpu().numpy()
             totals, info = meta[:16].view(np.int64), meta[16:].view(FEED_INFO)
             P, B = int(totals[0]), int(totals[1])
-            payload = torch.empty(B, dtype=torch.uint8, device=dev)
-            offs = torch.empty(P + 1, dtype=torch.int64, device=dev)
-            gp = torch.empty(P, dtype=torch.int64, device=dev)
-            eos = torch.empty(P, dtype=torch.uint8, device=dev)
+            payload, offs, gp, eos = _csr_buffers(P, B, dev)
             # the buffers have the sizes the scan returned: this fill cannot fall short, so its status word is not waited for
             check(lib.vbm_ogg_feed_fill(self._h, payload.data_ptr() if B else None, B, offs.data_ptr(),
                                         gp.data_ptr() if P else None, eos.data_ptr() if P else None, P, q),
@@ -560,30 +561,14 @@ class OggFeed:
     def headers(self, id):
         """-> the three header packets of slot `id` as bytes (for DecodeSetup); VbmError until they are complete"""
         sizes = (C.c_int * 3)()
-        q = None if self.host else self._q()
+        q = self._q()
         check(lib.vbm_ogg_feed_headers(self._h, int(id), None, 0, sizes, q), "vbm_ogg_feed_headers")
-        a, b, c = sizes[0], sizes[1], sizes[2]
-        buf = np.zeros(max(1, a + b + c), np.uint8)
-        check(lib.vbm_ogg_feed_headers(self._h, int(id), buf.ctypes.data, a + b + c, sizes, q), "vbm_ogg_feed_headers")
-        h = buf.tobytes()
-        return [h[:a], h[a:a + b], h[a + b:a + b + c]]
+        buf = np.zeros(max(1, sum(sizes)), np.uint8)
+        check(lib.vbm_ogg_feed_headers(self._h, int(id), buf.ctypes.data, sum(sizes), sizes, q), "vbm_ogg_feed_headers")
+        return _split3(buf.tobytes(), sizes)
 
     def reset(self, ids):
         """those slots are free for new streams"""
         ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
-        check(lib.vbm_ogg_feed_reset_streams(self._h, len(ids), ids.ctypes.data, None if self.host else self._q()),
+        check(lib.vbm_ogg_feed_reset_streams(self._h, len(ids), ids.ctypes.data, self._q()),
               "vbm_ogg_feed_reset_streams")
-
-    def close(self):
-        if self._h:
-            if not self.host:
-                import torch
-                torch.cuda.synchronize(self.device)
-            lib.vbm_ogg_feed_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
