@@ -441,6 +441,46 @@ int vbm_host_ogg_demux_fill(vbm_ogg_demuxer *dm, uint8_t *headers, long long hea
                             long long payload_cap, long long *offsets, long long *granulepos, uint8_t *eos,
                             long long packet_cap);
 
+/* ---- Ogg chains: where the links of chained files start, for many files per call, on the device ----------------------
+ * A chained file is whole logical streams ("links") back to back, and the calls above take one stream per file.  A split
+ * finds where the links of `nfiles` files start, file f in d_data[file_offsets[f], file_offsets[f+1]) as above, so that
+ * the links can be demuxed as files.  The rule (csrc/ogg_chain.h): link 0 starts at the file's first byte, in every
+ * file, an empty one included; then page after page from there, a page that carries the beginning-of-stream flag
+ * (header byte 5, bit 0x02) and is not the file's first starts a link.  The walk stops where fewer than 27 bytes are
+ * left, the capture pattern is not "OggS", the version is not 0, or the lacing table or the body is not all in front of
+ * the file's end, and the rest of the file then belongs to the last link found.  There is no resync.  The split never
+ * fails and never judges: CRC, serial number, page sequence and continuation flag stay with the demux of each link,
+ * which rejects a link exactly as it would reject those bytes as a file.  A file with no second beginning-of-stream
+ * page is one link, the file.  Nothing outside a file's range is read for it.
+ *   vbm_ogg_chain_create   workspace on the current device for calls of up to max_files files that span up to max_bytes
+ *                          bytes: about 0.3 * max_bytes + 16 * max_files bytes.  vbm_host_ogg_chain_create: the same in
+ *                          host memory for vbm_host_ogg_chain_split, touches no device.
+ *   vbm_ogg_chain_split    d_file_links [nfiles + 1]: the exclusive sums of the files' link counts, so file f has links
+ *                          d_file_links[f] .. d_file_links[f+1] - 1 of the batch and d_file_links[nfiles] = total.
+ *                          ALWAYS written.  d_link_offsets, of capacity link_cap + 1 entries: link j of the batch is
+ *                          d_data[d_link_offsets[j], d_link_offsets[j+1]), and d_link_offsets[total] =
+ *                          file_offsets[nfiles].  When total > link_cap NOTHING is written to d_link_offsets and the
+ *                          status word becomes VBM_OGG_DEMUX_ECAP (0 after a split that wrote them).  Both outputs are
+ *                          device memory; file_offsets is host memory and is free on return.  d_link_offsets, copied to
+ *                          the host, is a valid file_offsets of vbm_ogg_demux_scan with nfiles = total over the same
+ *                          d_data.
+ *   vbm_ogg_chain_status   the status word of the last split -> *status (host memory); waits for `stream`, on which
+ *                          that split must have been enqueued.
+ * split allocates nothing and only enqueues on `stream`; its one wait is for the pinned slot that carried the file
+ * offsets two splits earlier.  VBM_EINVAL, with nothing enqueued: nfiles negative or above max_files, a negative or
+ * decreasing offset, a span above max_bytes, a null pointer (d_data may be null when the span is 0), a negative
+ * link_cap, a host object in a device call or the other way round.
+ *   vbm_host_ogg_chain_split   the same source on the CPU with host pointers and a host object. */
+typedef struct vbm_ogg_chain vbm_ogg_chain;
+int vbm_ogg_chain_create(vbm_ogg_chain **ch, int max_files, long long max_bytes);
+int vbm_host_ogg_chain_create(vbm_ogg_chain **ch, int max_files, long long max_bytes);
+void vbm_ogg_chain_destroy(vbm_ogg_chain *ch);
+int vbm_ogg_chain_split(vbm_ogg_chain *ch, int nfiles, const uint8_t *d_data, const long long *file_offsets,
+                        long long *d_file_links, long long *d_link_offsets, long long link_cap, void *stream);
+int vbm_ogg_chain_status(vbm_ogg_chain *ch, int *status, void *stream);
+int vbm_host_ogg_chain_split(vbm_ogg_chain *ch, int nfiles, const uint8_t *data, const long long *file_offsets,
+                             long long *file_links, long long *link_offsets, long long link_cap);
+
 /* ---- Ogg demux, incremental form: the next bytes of many live streams per call, on the device -----------------------
  * A feed holds max_streams stream slots.  Every call takes, for each slot of a list, a chunk of bytes of any length (0
  * included) cut anywhere, and returns the audio packets those bytes completed, as ONE CSR grouped by stream in list

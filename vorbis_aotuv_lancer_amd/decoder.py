@@ -474,7 +474,7 @@ class OggIndex:
         self.setup.close()
 
 
-def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False):
+def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chained=False):
     """.ogg files (bytes or paths), one logical stream each -> [(pcm float32 [channels, n] contiguous on the current
     device, rate)], one per file.  Files whose identification and setup headers are byte-equal share one DecodeSetup
     and Decoder, one stream per file; their packets go through synthesis_runs in calls of at most max_packets rows.
@@ -482,15 +482,21 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False):
     many samples per file, and the rate returned is the output rate, half the file's (ov_halfrate).  Waits for the
     device once, at the end, to place the outputs.  device_demux=True: the files are demuxed together on the device
     (stream.DeviceDemuxer) instead of one by one on the host; the packet bytes then never leave the device, the offsets,
-    granule positions and eos flags are read back once to plan the calls, and the PCM is the same bit for bit."""
-    from .stream import demux_ogg, demux_ogg_device
+    granule positions and eos flags are read back once to plan the calls, and the PCM is the same bit for bit.
+    chained=True: the files may be chained (stream.split_ogg_chain, csrc/ogg_chain.h), and the result is one list per
+    file of (pcm, rate), one per link in file order.  Every link decodes as the file it would be alone: its own
+    headers, fresh overlap state, its own granule positions; links and files with byte-equal identification and setup
+    headers share a decoder.  A link that is not one valid logical stream raises VbmError naming file and link."""
+    from .stream import demux_ogg, demux_ogg_device, split_ogg_chain
     if max_packets <= 0:
         raise ValueError("max_packets must be positive")
     dev = torch.device("cuda", torch.cuda.current_device())
     names, demuxed, groups = [], [], {}
+    file_links = None
     if device_demux:
-        b = demux_ogg_device(files)
+        b = demux_ogg_device(files, chained=chained)
         names = b.names
+        file_links = b.file_links if chained else None
         offsets = b.offsets.cpu().numpy()
         for i in range(len(b)):
             if b.status[i]:
@@ -501,15 +507,20 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False):
             demuxed.append((b.headers[i], b.payload[at:at + int(b.payload_bytes[i])], offsets[a:a + n + 1] - at,
                             b.granulepos[a:a + n], b.eos[a:a + n]))
     else:
+        file_links = [0]
         for i, f in enumerate(files):
-            names.append(os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}")
+            name = os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}"
             if isinstance(f, (str, os.PathLike)):
                 with open(f, "rb") as fh:
                     f = fh.read()
-            try:
-                demuxed.append(demux_ogg(f))
-            except VbmError as e:
-                raise VbmError(f"{names[i]}: {e}") from None
+            entries = [(f"{name} link {k}", link) for k, link in enumerate(split_ogg_chain(f))] if chained else [(name, f)]
+            for entry, blob in entries:
+                names.append(entry)
+                try:
+                    demuxed.append(demux_ogg(blob))
+                except VbmError as e:
+                    raise VbmError(f"{entry}: {e}") from None
+            file_links.append(len(demuxed))
     for i, d in enumerate(demuxed):
         groups.setdefault((d[0][0], d[0][2]), []).append(i)
     for members in groups.values():                       # every setup is checked before any work is enqueued
@@ -517,8 +528,8 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False):
         if rc:
             raise VbmError(f"{names[members[0]]}: unsupported or invalid Vorbis headers (code {rc}): "
                            f"{lib.vbm_last_error().decode()}")
-    pieces = [[] for _ in files]                          # per file: (pcm [channels, stride] view, index into lens)
-    lens, keep, rates, nlens = [], [], [0] * len(files), 0
+    pieces = [[] for _ in demuxed]                        # per entry: (pcm [channels, stride] view, index into lens)
+    lens, keep, rates, nlens = [], [], [0] * len(demuxed), 0
     for members in groups.values():
         ds = DecodeSetup(demuxed[members[0]][0])
         dec = Decoder(ds, len(members), max_packets, halfrate=halfrate)
@@ -563,10 +574,12 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False):
                 pieces[j].append((torch.zeros((ds.channels, 0), dtype=torch.float32, device=dev), None))
     n = torch.cat(lens).cpu().tolist() if lens else []   # the one wait for the device
     out = []
-    for j in range(len(files)):
+    for j in range(len(demuxed)):
         parts = [p if k is None else p[:, :n[k]] for p, k in pieces[j]]
         out.append((torch.cat(parts, dim=1).contiguous(), rates[j]))
     for ds, dec in keep:
         dec.close()
         ds.close()
+    if chained:
+        return [out[int(file_links[f]):int(file_links[f + 1])] for f in range(len(file_links) - 1)]
     return out

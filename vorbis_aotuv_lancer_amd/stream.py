@@ -384,10 +384,13 @@ class DemuxBatch:
     offsets int64 [P + 1], granulepos int64 [P], eos uint8 [P] — torch tensors on the device (numpy arrays with
     host=True) holding ONE CSR over the audio packets of all good files: packet k of file f is
     payload[offsets[packet_base[f] + k]:offsets[packet_base[f] + k + 1]], with packets[f] of them.  runs(f) is that
-    file's slice in the form Decoder.synthesis_runs takes."""
+    file's slice in the form Decoder.synthesis_runs takes.  From demux_ogg_device(chained=True) the entries ("files"
+    above) are the links of the files given, named "<file> link k": file_links int64 [given files + 1] counts them, and
+    links(f) is the range of entries of given file f.  Otherwise every file is its own one entry."""
 
-    def __init__(self, names, info, headers, payload, offsets, granulepos, eos):
+    def __init__(self, names, info, headers, payload, offsets, granulepos, eos, file_links=None):
         self.names, self.info, self.headers = names, info, headers
+        self.file_links = np.arange(len(names) + 1, dtype=np.int64) if file_links is None else file_links
         self.payload, self.offsets, self.granulepos, self.eos = payload, offsets, granulepos, eos
         self.status = info["status"].tolist()
         self.packets, self.packet_base = info["packets"], info["packet_base"]
@@ -400,6 +403,10 @@ class DemuxBatch:
         """-> (offsets [packets[f] + 1] as they stand (they index the whole payload), granulepos, eos) of file f"""
         a, n = int(self.packet_base[f]), int(self.packets[f])
         return self.offsets[a:a + n + 1], self.granulepos[a:a + n], self.eos[a:a + n]
+
+    def links(self, f):
+        """-> the entries that are the links of given file f"""
+        return range(int(self.file_links[f]), int(self.file_links[f + 1]))
 
 
 class DeviceDemuxer(_TwinHandle):
@@ -421,8 +428,13 @@ class DeviceDemuxer(_TwinHandle):
 
     def demux(self, files):
         names, blobs = _read_files(files)
-        n = len(blobs)
-        raw, off = _join(blobs, self.device)
+        return self.demux_joined(names, *_join(blobs, self.device))
+
+    def demux_joined(self, names, raw, off):
+        """demux() of files that already lie in one buffer: raw uint8 (a tensor on the device; a numpy array with
+        host=True), entry i in raw[off[i]:off[i + 1]], off int64 numpy [n + 1]"""
+        off = np.ascontiguousarray(off, np.int64)
+        n = len(off) - 1
         if self.host:
             info, totals = np.zeros(n, FILE_INFO), np.zeros(3, np.int64)
             check(lib.vbm_host_ogg_demux_scan(self._h, n, raw.ctypes.data if len(raw) else None, off.ctypes.data,
@@ -461,14 +473,93 @@ class DeviceDemuxer(_TwinHandle):
         return DemuxBatch(names, info, headers, payload, offsets, gp, eos)
 
 
-def demux_ogg_device(files, host=False):
-    """.ogg files (bytes or paths) -> DemuxBatch, through a DeviceDemuxer made for them (host=True: its CPU twin)."""
-    names, blobs = _read_files(files)
-    dm = DeviceDemuxer(max(1, len(blobs)), sum(len(b) for b in blobs), host=host)
+class ChainSplitter(_TwinHandle):
+    """Where the links of chained .ogg files start, for up to max_files files of up to max_bytes bytes together per
+    split() call, on the device (vbm_ogg_chain_split; the rule: csrc/ogg_chain.h).  host=True runs the CPU twin on numpy
+    arrays (no GPU needed).  The split never fails: what does not parse stays with the last link found, for the demux
+    to reject."""
+
+    ECAP = 1
+
+    def __init__(self, max_files, max_bytes, host=False, device=None):
+        self.max_files, self.max_bytes = int(max_files), int(max_bytes)
+        super().__init__("chain", host, device, self.max_files, self.max_bytes)
+
+    def split(self, raw, off, link_cap=None):
+        """raw uint8 (a tensor on the device; a numpy array with host=True), file f in raw[off[f]:off[f + 1]], off int64
+        numpy [n + 1] -> (file_links int64 [n + 1], link_offsets int64 [total + 1]) on the host: file f has links
+        file_links[f] .. file_links[f + 1] - 1, and link j is raw[link_offsets[j]:link_offsets[j + 1]].  link_cap: the
+        links the first try has room for (default 2 n + 62); a batch with more takes a second try with the exact total.
+        One small D2H per try."""
+        off = np.ascontiguousarray(off, np.int64)
+        n = len(off) - 1
+        cap = 2 * n + 62 if link_cap is None else int(link_cap)
+        for attempt in range(2):
+            st = C.c_int(-1)
+            if self.host:
+                out = np.zeros(n + cap + 2, np.int64)
+                check(lib.vbm_host_ogg_chain_split(self._h, n, raw.ctypes.data if len(raw) else None, off.ctypes.data,
+                                                   out.ctypes.data, out.ctypes.data + 8 * (n + 1), cap),
+                      "vbm_host_ogg_chain_split")
+                check(lib.vbm_ogg_chain_status(self._h, C.byref(st), None), "vbm_ogg_chain_status")
+            else:
+                import torch
+                q = self._q()
+                # file_links and link_offsets in one buffer: one small D2H
+                d_out = torch.empty(n + cap + 2, dtype=torch.int64, device=self.device)
+                check(lib.vbm_ogg_chain_split(self._h, n, raw.data_ptr() if len(raw) else None, off.ctypes.data,
+                                              d_out.data_ptr(), d_out.data_ptr() + 8 * (n + 1), cap, q), "vbm_ogg_chain_split")
+                out = d_out.cpu().numpy()
+                check(lib.vbm_ogg_chain_status(self._h, C.byref(st), q), "vbm_ogg_chain_status")
+            total = int(out[n])
+            if st.value == 0:
+                return out[:n + 1].copy(), out[n + 1:n + total + 2].copy()
+            if st.value != self.ECAP or attempt:
+                break
+            cap = total
+        raise VbmError(f"vbm_ogg_chain_split: status {st.value} with room for the {total} links it counted")
+
+
+def split_ogg_chain(data):
+    """.ogg bytes of one file -> [bytes], its links (csrc/ogg_chain.h): a page with the beginning-of-stream flag that is
+    not the file's first starts a link, and a file without one is its own one link.  On the host; needs no GPU.  The
+    split never fails: each link is judged when it is demuxed (demux_ogg)."""
+    raw = bytes(data)
+    sp = ChainSplitter(1, len(raw), host=True)
     try:
-        return dm.demux(blobs)
+        _, lo = sp.split(np.frombuffer(raw, np.uint8), np.array([0, len(raw)], np.int64))
+    finally:
+        sp.close()
+    return [raw[int(a):int(b)] for a, b in zip(lo[:-1], lo[1:])]
+
+
+def demux_ogg_device(files, host=False, chained=False):
+    """.ogg files (bytes or paths) -> DemuxBatch, through a DeviceDemuxer made for them (host=True: its CPU twin).
+    chained=True: the files may be chained.  After the one upload a ChainSplitter finds their links, one small D2H brings
+    the link offsets back, and the demuxer runs over the same buffer with the links as its files: the batch's entries
+    are the links, b.links(f) those of file f, each judged alone (a bad link fails alone)."""
+    names, blobs = _read_files(files)
+    nbytes = sum(len(b) for b in blobs)
+    if not chained:
+        dm = DeviceDemuxer(max(1, len(blobs)), nbytes, host=host)
+        try:
+            return dm.demux(blobs)
+        finally:
+            dm.close()
+    sp = ChainSplitter(max(1, len(blobs)), nbytes, host=host)
+    try:
+        raw, off = _join(blobs, sp.device)
+        file_links, link_off = sp.split(raw, off)
+    finally:
+        sp.close()
+    link_names = [f"{names[f]} link {k}" for f in range(len(blobs)) for k in range(int(file_links[f + 1] - file_links[f]))]
+    dm = DeviceDemuxer(max(1, len(link_names)), nbytes, host=host, device=sp.device)
+    try:
+        b = dm.demux_joined(link_names, raw, link_off)
     finally:
         dm.close()
+    b.file_links = file_links
+    return b
 
 
 FEED_INFO = np.dtype([("status", "<i4"), ("headers_ready", "<i4"), ("header_bytes", "<i4", (3,)), ("serialno", "<u4"),
