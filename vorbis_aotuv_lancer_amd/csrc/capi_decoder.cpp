@@ -1,22 +1,21 @@
 // C ABI of the batched device decoder (include/vorbis_mi355x.h, "decode" section).
 //
-// One vbm_synthesis_batch call enqueues, on the caller's stream: the upload of the row -> stream map (pinned staging),
-// k_unpack (entropy decode, row lists by block size), k_spectrum, one k_imdct launch per block size (each reads its row
-// count from the device: rows of mixed block size are never sorted on the host) and k_overlap.  Nothing waits on
-// the device, except a staging slot that is still in flight from four calls back.
+// Every decode call enqueues, on the caller's stream: one table through the pinned staging ring (stage), then the front
+// chain (enqueue_front): the clears, its own unpack kernel (entropy decode, row lists by block size), k_spectrum and
+// one k_imdct launch per block size (each reads its row count from the device: rows of mixed block size are never
+// sorted on the host); then its own overlap kernels.  Nothing waits on the device, except a staging slot that is still
+// in flight from four turns back.
+//   vbm_synthesis_batch: the row -> stream map, k_unpack, k_overlap.
+//   vbm_synthesis_runs, whose rows are runs of consecutive packets of one stream: the run table (stream ids and run
+//     starts), k_unpack_csr (from CSR offsets), k_run_plan, k_overlap_runs and k_run_commit.
+//   vbm_synthesis_ranges, sample windows of the streams of a range store (packets and index in device memory): the host
+//     plans pieces (a pre-roll packet and the packets after it) from the store's host index (range_plan.h, pure host
+//     code); per sub-call the piece table, k_range_rows, k_unpack_rows, k_range_plan and k_overlap_runs.  No stream
+//     state is read or written.
 //
-// vbm_synthesis_runs enqueues the same unpack (from CSR offsets), spectrum and IMDCT launches over rows that are runs of
-// consecutive packets of one stream, then k_run_plan, k_overlap_runs and k_run_commit in place of k_overlap.  The run
-// table (stream ids and run starts) goes up through the same staging ring.
-//
-// vbm_synthesis_ranges decodes sample windows of the streams of a range store (packets and index in device memory).
-// The host plans pieces (a pre-roll packet and the packets after it) from the store's host index; per sub-call the
-// piece table goes up through the staging ring, then k_range_rows, k_unpack_rows, the same spectrum and IMDCT
-// launches, k_range_plan and k_overlap_runs.  No stream state is read or written.
-//
-// vbm_range_store_create_device makes the same store from a CSR that is already in device memory, and
-// vbm_decode_index_device the index alone: k_index_head and k_index_scan (decode_index.hip) in place of the host walk;
-// the first packets of the streams go up through the staging ring.
+// vbm_range_store_create_device makes the store of vbm_range_store_create (check_csr and new_store serve both) from a
+// CSR that is already in device memory, and vbm_decode_index_device the index alone: k_index_head and k_index_scan
+// (decode_index.hip) in place of the host walk; the first packets of the streams go up through the staging ring.
 //
 // A half-rate decoder (vbm_decoder_create_halfrate) enqueues the same chains with the IMDCT of half each block size and
 // the half-rate instantiations of the overlap kernels; its windows and trig tables are those of the halved sizes, its
@@ -30,6 +29,7 @@
 #include "decode_index.h"
 #include "decode_kernels.h"
 #include "decode_setup.h"
+#include "range_plan.h"
 #include "vbm_internal.h"
 #include "vorbis_mi355x.h"
 
@@ -38,6 +38,9 @@ extern "C" int vbm_host_mdct_trig(int n, float *out);
 namespace {
 constexpr int kStage = 4;
 }
+
+// set-up code: a HIP call that fails is recorded, and the function's own fail(rc) frees what it has made so far
+#define CK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return fail(vbm_set_hip_error(e_, #x)); } while (0)
 
 struct vbm_decoder {
     vbmd_setup hs;                   // host copy (block sizes, channels)
@@ -115,18 +118,15 @@ void free_decoder(vbm_decoder *d)
     delete d;
 }
 
-// host ints -> dst (d_ids or d_runtab) through the next pinned staging slot
-int stage_ints(vbm_decoder *d, int *dst, const int *const *parts, const int *lens, int nparts, hipStream_t q)
+// One turn of the staging ring: fill(slot) writes n host ints into the next pinned slot, and they go up to dst
+template <class Fill>
+int stage(vbm_decoder *d, int *dst, size_t n, hipStream_t q, Fill fill)
 {
     const int t = d->stage_turn;
     d->stage_turn = (t + 1) % kStage;
-    hipError_t e = hipEventSynchronize(d->ev_stage[t]);      // the copy from kStage calls ago has been done
+    hipError_t e = hipEventSynchronize(d->ev_stage[t]);      // the copy from kStage turns ago has been done
     if (e != hipSuccess) return vbm_set_hip_error(e, "hipEventSynchronize(stage)");
-    size_t n = 0;
-    for (int i = 0; i < nparts; i++) {
-        memcpy(d->h_stage[t] + n, parts[i], (size_t)lens[i] * sizeof(int));
-        n += (size_t)lens[i];
-    }
+    fill(d->h_stage[t]);
     e = hipMemcpyAsync(dst, d->h_stage[t], n * sizeof(int), hipMemcpyHostToDevice, q);
     if (e != hipSuccess) return vbm_set_hip_error(e, "hipMemcpyAsync(ids)");
     e = hipEventRecord(d->ev_stage[t], q);
@@ -134,7 +134,11 @@ int stage_ints(vbm_decoder *d, int *dst, const int *const *parts, const int *len
     return VBM_OK;
 }
 
-int stage_ids(vbm_decoder *d, const int *ids, int n, hipStream_t q) { return stage_ints(d, d->d_ids, &ids, &n, 1, q); }
+// n host ints -> dst (d_ids or d_rtab)
+int stage_ints(vbm_decoder *d, int *dst, const int *src, size_t n, hipStream_t q)
+{
+    return stage(d, dst, n, q, [=](int *slot) { memcpy(slot, src, n * sizeof(int)); });
+}
 
 int check_ids(vbm_decoder *d, int n, const int *ids)
 {
@@ -144,6 +148,21 @@ int check_ids(vbm_decoder *d, int n, const int *ids)
         if (d->seen[ids[i]]) { g_vbm_err = "stream id appears twice in one call"; return VBM_EINVAL; }
         d->seen[ids[i]] = 1;
     }
+    return VBM_OK;
+}
+
+// The front of every decode call, over the L.nsb rows of L = d->launch(nsb): the two clears, unpack() (the entry
+// point's unpack launch), spectrum and one IMDCT launch per block size.  what: the error text of a failed clear.
+template <class Unpack>
+int enqueue_front(const vbm_decoder *d, const vbmd_launch &L, hipStream_t q, const char *what, Unpack unpack)
+{
+    hipError_t e = hipMemsetAsync(d->d_counts, 0, 2 * sizeof(int), q);
+    if (e == hipSuccess) e = hipMemsetAsync(d->d_res, 0, (size_t)L.nsb * d->ch * d->half * sizeof(float), q);
+    if (e != hipSuccess) return vbm_set_hip_error(e, what);
+    if (unpack()) return VBM_EHIP;
+    if (vbmd_launch_spectrum(L, d->d_spec, nullptr, q)) return VBM_EHIP;
+    for (int W = 0; W < 2; W++)
+        if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W] >> d->halfrate, d->trig[W], q)) return VBM_EHIP;
     return VBM_OK;
 }
 
@@ -179,8 +198,7 @@ extern "C" int vbm_decoder_create_halfrate(vbm_decoder **out, const vbm_decode_s
     d->ohalf = d->half >> halfrate;
     d->max_classes = ds->s.max_classes;
     const size_t cap = (size_t)max_batch, ch = (size_t)d->ch;
-    hipError_t e = hipSuccess;
-#define CK(x) do { e = (x); if (e != hipSuccess) { int rc = vbm_set_hip_error(e, #x); free_decoder(d); return rc; } } while (0)
+    auto fail = [d](int rc) { free_decoder(d); return rc; };
     const size_t setup_bytes = sizeof(vbmd_setup) + ds->blob.size();
     CK(hipMalloc((void **)&d->d_setup, setup_bytes));
     CK(hipMemcpy(d->d_setup, &ds->s, sizeof(vbmd_setup), hipMemcpyHostToDevice));
@@ -240,9 +258,8 @@ extern "C" int vbm_decoder_create_halfrate(vbm_decoder **out, const vbm_decode_s
         CK(hipHostMalloc((void **)&d->h_stage[i], stage * sizeof(int), hipHostMallocDefault));
         CK(hipEventCreateWithFlags(&d->ev_stage[i], hipEventDisableTiming));
     }
-#undef CK
     const int rc = vbm_decoder_reset(d);
-    if (rc) { free_decoder(d); return rc; }
+    if (rc) return fail(rc);
     *out = d;
     return VBM_OK;
 }
@@ -275,7 +292,7 @@ extern "C" int vbm_decoder_restart_streams(vbm_decoder *d, int n, const int *str
     int rc = check_ids(d, n, stream_ids);
     if (rc) return rc;
     hipStream_t q = (hipStream_t)stream;
-    if ((rc = stage_ids(d, stream_ids, n, q))) return rc;
+    if ((rc = stage_ints(d, d->d_ids, stream_ids, (size_t)n, q))) return rc;
     return vbmd_launch_restart(d->d_ids, n, d->d_prevW, d->d_gp, d->d_sc, q) ? VBM_EHIP : VBM_OK;
 }
 
@@ -289,15 +306,11 @@ extern "C" int vbm_synthesis_batch(vbm_decoder *d, int nsb, const int *stream_id
     int rc = check_ids(d, nsb, stream_ids);
     if (rc) return rc;
     hipStream_t q = (hipStream_t)stream;
-    if ((rc = stage_ids(d, stream_ids, nsb, q))) return rc;
-    hipError_t e = hipMemsetAsync(d->d_counts, 0, 2 * sizeof(int), q);
-    if (e == hipSuccess) e = hipMemsetAsync(d->d_res, 0, (size_t)nsb * d->ch * d->half * sizeof(float), q);
-    if (e != hipSuccess) return vbm_set_hip_error(e, "hipMemsetAsync(decode)");
+    if ((rc = stage_ints(d, d->d_ids, stream_ids, (size_t)nsb, q))) return rc;
     const vbmd_launch L = d->launch(nsb);
-    if (vbmd_launch_unpack(L, d_packets, packet_stride, d_packet_bytes, d_status, q)) return VBM_EHIP;
-    if (vbmd_launch_spectrum(L, d->d_spec, nullptr, q)) return VBM_EHIP;
-    for (int W = 0; W < 2; W++)
-        if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W] >> d->halfrate, d->trig[W], q)) return VBM_EHIP;
+    rc = enqueue_front(d, L, q, "hipMemsetAsync(decode)",
+                       [&] { return vbmd_launch_unpack(L, d_packets, packet_stride, d_packet_bytes, d_status, q); });
+    if (rc) return rc;
     if (vbmd_launch_overlap(L, d->d_ids, d_granulepos, d_eos, d_pcm, d_samples, q)) return VBM_EHIP;
     d->last_nsb = nsb;
     return VBM_OK;
@@ -333,18 +346,16 @@ extern "C" int vbm_synthesis_runs(vbm_decoder *d, int nruns, const int *stream_i
         return VBM_EINVAL;
     }
     hipStream_t q = (hipStream_t)stream;
-    const int *parts[2] = {stream_ids, d->run_start.data()};
-    const int lens[2] = {nruns, nruns + 1};
-    if ((rc = stage_ints(d, d->d_runtab, parts, lens, 2, q))) return rc;
+    rc = stage(d, d->d_runtab, 2 * (size_t)nruns + 1, q, [&](int *slot) {      // the run table: ids, then run starts
+        memcpy(slot, stream_ids, (size_t)nruns * sizeof(int));
+        memcpy(slot + nruns, d->run_start.data(), ((size_t)nruns + 1) * sizeof(int));
+    });
+    if (rc) return rc;
     const int nsb = (int)P;
-    hipError_t e = hipMemsetAsync(d->d_counts, 0, 2 * sizeof(int), q);
-    if (e == hipSuccess) e = hipMemsetAsync(d->d_res, 0, (size_t)nsb * d->ch * d->half * sizeof(float), q);
-    if (e != hipSuccess) return vbm_set_hip_error(e, "hipMemsetAsync(decode runs)");
     const vbmd_launch L = d->launch(nsb);
-    if (vbmd_launch_unpack_csr(L, d_data, d_offsets, data_bytes, d_status, q)) return VBM_EHIP;
-    if (vbmd_launch_spectrum(L, d->d_spec, nullptr, q)) return VBM_EHIP;
-    for (int W = 0; W < 2; W++)
-        if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W] >> d->halfrate, d->trig[W], q)) return VBM_EHIP;
+    rc = enqueue_front(d, L, q, "hipMemsetAsync(decode runs)",
+                       [&] { return vbmd_launch_unpack_csr(L, d_data, d_offsets, data_bytes, d_status, q); });
+    if (rc) return rc;
     if (vbmd_launch_runs(L, nruns, d->d_runtab, d_granulepos, d_eos, d->d_plan, d->d_run_last, d_pcm, pcm_stride,
                          d_run_samples, d_samples, q))
         return VBM_EHIP;
@@ -358,24 +369,24 @@ extern "C" int vbm_decoder_fetch(vbm_decoder *d, const char *name, void *d_out, 
     hipStream_t q = (hipStream_t)stream;
     const int nsb = d->last_nsb;
     const size_t plane = (size_t)nsb * d->ch * d->half;
-    const vbmd_launch L = d->launch(nsb);
-    long r;
-    char k;
-    if (!strcmp(name, "info")) { r = 4; k = 'i'; }
-    else if (!strcmp(name, "floor_used")) { r = 1; k = 'i'; }
-    else if (!strcmp(name, "floor_index")) { r = d->half; k = 'i'; }
-    else if (!strcmp(name, "residue") || !strcmp(name, "spectrum")) { r = d->half; k = 'f'; }
-    else { g_vbm_err = std::string("unknown intermediate: ") + name; return VBM_EINVAL; }
-    if (rows) *rows = r;
-    if (kind) *kind = k;
+    enum source { COPY, USED, FLOOR };                     // a buffer as it is; from the flags; the floor line from the posts
+    const struct { const char *name; long rows; char kind; source from; const void *buf; size_t bytes; } tab[] = {
+        {"info", 4, 'i', COPY, d->d_info, (size_t)nsb * 4 * sizeof(int)},
+        {"floor_used", 1, 'i', USED, nullptr, 0},
+        {"floor_index", d->half, 'i', FLOOR, nullptr, 0},
+        {"residue", d->half, 'f', COPY, d->d_res, plane * sizeof(float)},
+        {"spectrum", d->half, 'f', COPY, d->d_spec, plane * sizeof(float)}};
+    const auto *t = std::find_if(std::begin(tab), std::end(tab), [name](const auto &x) { return !strcmp(name, x.name); });
+    if (t == std::end(tab)) { g_vbm_err = std::string("unknown intermediate: ") + name; return VBM_EINVAL; }
+    if (rows) *rows = t->rows;
+    if (kind) *kind = t->kind;
     if (!d_out) return VBM_OK;
-    hipError_t e = hipSuccess;
-    if (!strcmp(name, "info")) e = hipMemcpyAsync(d_out, d->d_info, (size_t)nsb * 4 * sizeof(int), hipMemcpyDeviceToDevice, q);
-    else if (!strcmp(name, "residue")) e = hipMemcpyAsync(d_out, d->d_res, plane * sizeof(float), hipMemcpyDeviceToDevice, q);
-    else if (!strcmp(name, "spectrum")) e = hipMemcpyAsync(d_out, d->d_spec, plane * sizeof(float), hipMemcpyDeviceToDevice, q);
-    else if (!strcmp(name, "floor_used")) return vbmd_launch_used(d->d_flags, (int *)d_out, (long)nsb * d->ch, q) ? VBM_EHIP : VBM_OK;
-    else return vbmd_launch_spectrum(L, nullptr, (int *)d_out, q) ? VBM_EHIP : VBM_OK;   // floor line from the posts
-    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "hipMemcpyAsync(decoder fetch)");
+    if (t->from == COPY) {
+        const hipError_t e = hipMemcpyAsync(d_out, t->buf, t->bytes, hipMemcpyDeviceToDevice, q);
+        return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "hipMemcpyAsync(decoder fetch)");
+    }
+    if (t->from == USED) return vbmd_launch_used(d->d_flags, (int *)d_out, (long)nsb * d->ch, q) ? VBM_EHIP : VBM_OK;
+    return vbmd_launch_spectrum(d->launch(nsb), nullptr, (int *)d_out, q) ? VBM_EHIP : VBM_OK;
 }
 
 // ---- range stores and range calls ----------------------------------------------------------------------------------
@@ -403,9 +414,69 @@ void free_store(vbm_range_store *st)
     delete st;
 }
 
-struct range_piece {
-    int r, pre, first, count;            // output row, pre-roll packet, first packet after it, packets after it
-};
+// The argument rules of a range store's CSR, for host arrays (vbm_range_store_create) and device arrays alike
+int check_csr(const vbm_decoder *d, int nstreams, const long long *stream_packets, const uint8_t *data,
+              const long long *offsets, long long data_bytes)
+{
+    if (!d || nstreams <= 0 || !stream_packets || data_bytes < 0 || (data_bytes > 0 && !data) || !offsets)
+        return VBM_EINVAL;
+    if (stream_packets[0] != 0) { g_vbm_err = "stream_packets[0] must be 0"; return VBM_EINVAL; }
+    for (int i = 0; i < nstreams; i++)
+        if (stream_packets[i + 1] < stream_packets[i]) { g_vbm_err = "stream_packets must not decrease"; return VBM_EINVAL; }
+    if (stream_packets[nstreams] >= INT_MAX) { g_vbm_err = "more than 2^31 - 2 packets in one store"; return VBM_EINVAL; }
+    return VBM_OK;
+}
+
+// *out: a store of d for a CSR that check_csr passes, the host index sized, the device arrays allocated, none filled
+int new_store(vbm_range_store **out, vbm_decoder *d, int nstreams, const long long *stream_packets, const uint8_t *data,
+              const long long *offsets, long long data_bytes)
+{
+    if (!out) return VBM_EINVAL;
+    *out = nullptr;
+    const int bad = check_csr(d, nstreams, stream_packets, data, offsets, data_bytes);
+    if (bad) return bad;
+    const size_t np = (size_t)stream_packets[nstreams];
+    vbm_range_store *st = new vbm_range_store();
+    auto fail = [st](int rc) { free_store(st); return rc; };
+    st->dec = d;
+    st->S = nstreams;
+    st->first.assign(stream_packets, stream_packets + nstreams + 1);
+    st->status.resize(np);
+    st->out_end.resize(np);
+    st->totals.resize((size_t)nstreams);
+    st->data_bytes = data_bytes;
+    CK(hipMalloc((void **)&st->d_data, data_bytes > 0 ? (size_t)data_bytes : 1));
+    CK(hipMalloc((void **)&st->d_offsets, (np + 1) * sizeof(long long)));
+    CK(hipMalloc((void **)&st->d_out_start, (np ? np : 1) * sizeof(long long)));
+    CK(hipMalloc((void **)&st->d_begin, (np ? np : 1) * sizeof(int)));
+    CK(hipMalloc((void **)&st->d_end, (np ? np : 1) * sizeof(int)));
+    *out = st;
+    return VBM_OK;
+}
+
+// k_index_head over all packets, then k_index_scan over the streams, as many per launch as one staging slot holds
+// first packets for (they go up through the ring into d_itab; launches on one stream follow each other)
+int enqueue_index(vbm_decoder *d, int nstreams, const long long *stream_packets, const uint8_t *d_data,
+                  const long long *d_offsets, long long data_bytes, const long long *d_granulepos, const uint8_t *d_eos,
+                  int *d_status, int *d_begin, int *d_end, long long *d_out_start, long long *d_out_end,
+                  long long *d_totals, hipStream_t q)
+{
+    const vbmd_setup *s = (const vbmd_setup *)d->d_setup;
+    if (vbmd_launch_index_head(s, stream_packets[nstreams], d_data, d_offsets, data_bytes, d_status, d_begin, q))
+        return VBM_EHIP;
+    const int room = (int)std::min<size_t>(d->stage_ints - 1, (size_t)INT_MAX - 1);
+    for (int s0 = 0; s0 < nstreams; s0 += room) {
+        const int n = std::min(room, nstreams - s0);
+        const int rc = stage(d, d->d_itab, (size_t)n + 1, q, [&](int *slot) {
+            for (int i = 0; i <= n; i++) slot[i] = (int)stream_packets[s0 + i];
+        });
+        if (rc) return rc;
+        if (vbmd_launch_index_scan(s, d->halfrate, n, d->d_itab, d_status, d_granulepos, d_eos, d_begin, d_end,
+                                   d_out_start, d_out_end, d_totals + s0, q))
+            return VBM_EHIP;
+    }
+    return VBM_OK;
+}
 
 }  // namespace
 
@@ -413,39 +484,20 @@ extern "C" int vbm_range_store_create(vbm_range_store **out, vbm_decoder *d, int
                                       const long long *stream_packets, const uint8_t *data, const long long *offsets,
                                       long long data_bytes, const long long *granulepos, const uint8_t *eos)
 {
-    if (!out || !d || nstreams <= 0 || !stream_packets || data_bytes < 0 || (data_bytes > 0 && !data) || !offsets)
-        return VBM_EINVAL;
-    *out = nullptr;
-    if (stream_packets[0] != 0) { g_vbm_err = "stream_packets[0] must be 0"; return VBM_EINVAL; }
-    for (int i = 0; i < nstreams; i++)
-        if (stream_packets[i + 1] < stream_packets[i]) { g_vbm_err = "stream_packets must not decrease"; return VBM_EINVAL; }
-    const long long P = stream_packets[nstreams];
-    if (P >= INT_MAX) { g_vbm_err = "more than 2^31 - 2 packets in one store"; return VBM_EINVAL; }
-    vbm_range_store *st = new vbm_range_store();
-    st->dec = d;
-    st->S = nstreams;
-    st->first.assign(stream_packets, stream_packets + nstreams + 1);
-    st->status.resize((size_t)P);
-    st->out_end.resize((size_t)P);
-    st->totals.resize((size_t)nstreams);
-    st->data_bytes = data_bytes;
-    std::vector<int> begin((size_t)P), end((size_t)P);
-    std::vector<long long> out_start((size_t)P);
+    const int bad = new_store(out, d, nstreams, stream_packets, data, offsets, data_bytes);
+    if (bad) return bad;
+    vbm_range_store *st = *out;
+    auto fail = [=](int rc) { free_store(st); *out = nullptr; return rc; };
+    const size_t np = (size_t)stream_packets[nstreams];
+    std::vector<int> begin(np), end(np);
+    std::vector<long long> out_start(np);
     for (int i = 0; i < nstreams; i++) {
         const long long a = stream_packets[i];
         vbmd_index_stream(d->hs, d->halfrate, stream_packets[i + 1] - a, data, offsets + a, data_bytes,
                           granulepos ? granulepos + a : nullptr, eos ? eos + a : nullptr, st->status.data() + a,
                           begin.data() + a, end.data() + a, out_start.data() + a, &st->totals[i]);
     }
-    for (long long k = 0; k < P; k++) st->out_end[k] = out_start[k] + (end[k] - begin[k]);
-    hipError_t e = hipSuccess;
-#define CK(x) do { e = (x); if (e != hipSuccess) { int rc = vbm_set_hip_error(e, #x); free_store(st); return rc; } } while (0)
-    const size_t np = (size_t)P;
-    CK(hipMalloc((void **)&st->d_data, data_bytes > 0 ? (size_t)data_bytes : 1));
-    CK(hipMalloc((void **)&st->d_offsets, (np + 1) * sizeof(long long)));
-    CK(hipMalloc((void **)&st->d_out_start, (np ? np : 1) * sizeof(long long)));
-    CK(hipMalloc((void **)&st->d_begin, (np ? np : 1) * sizeof(int)));
-    CK(hipMalloc((void **)&st->d_end, (np ? np : 1) * sizeof(int)));
+    for (size_t k = 0; k < np; k++) st->out_end[k] = out_start[k] + (end[k] - begin[k]);
     if (data_bytes > 0) CK(hipMemcpy(st->d_data, data, (size_t)data_bytes, hipMemcpyHostToDevice));
     CK(hipMemcpy(st->d_offsets, offsets, (np + 1) * sizeof(long long), hipMemcpyHostToDevice));
     if (np) {
@@ -453,8 +505,6 @@ extern "C" int vbm_range_store_create(vbm_range_store **out, vbm_decoder *d, int
         CK(hipMemcpy(st->d_begin, begin.data(), np * sizeof(int), hipMemcpyHostToDevice));
         CK(hipMemcpy(st->d_end, end.data(), np * sizeof(int), hipMemcpyHostToDevice));
     }
-#undef CK
-    *out = st;
     return VBM_OK;
 }
 
@@ -490,67 +540,32 @@ extern "C" int vbm_synthesis_ranges(vbm_decoder *d, const vbm_range_store *st, i
     }
     if (pcm_stride < most) { g_vbm_err = "pcm_stride below max(lengths)"; return VBM_EINVAL; }
     if (any && !d_pcm) return VBM_EINVAL;
-    // plan: per range the packets k (first with output past s) .. m (holds s + got - 1) after the pre-roll p (the
-    // last valid packet before k), cut into pieces of at most max_batch rows; pieces packed into sub-calls
-    const int cap = d->cap;
-    std::vector<range_piece> pieces;
-    std::vector<int> call_first{0}, call_r0;             // per sub-call: first piece, first output row
-    int rows = 0;
-    for (int r = 0; r < nranges; r++) {
-        const int i = stream_ids[r];
-        const long long total = st->totals[i], s = starts[r];
-        got[r] = (int)std::max(0LL, std::min(total - s, (long long)lengths[r]));
-        if (got[r] == 0) continue;
-        const long long *oe = st->out_end.data();
-        const long long a = st->first[i], b = st->first[i + 1];
-        const int k = (int)(std::upper_bound(oe + a, oe + b, s) - oe);
-        const int m = (int)(std::upper_bound(oe + a, oe + b, s + got[r] - 1) - oe);
-        int pre = k - 1;
-        while (pre >= a && st->status[pre] != 0) pre--;
-        if (pre < a) { g_vbm_err = "range store index: no pre-roll packet"; return VBM_EINVAL; }   // lW >= 0 at k
-        for (int f = pre + 1; f <= m;) {
-            const int count = std::min(m - f + 1, cap - 1);
-            if (rows + count + 1 > cap || (!call_r0.empty() && r - call_r0.back() >= cap)) {
-                call_first.push_back((int)pieces.size());
-                rows = 0;
-            }
-            if (call_r0.size() < call_first.size()) call_r0.push_back(r);
-            pieces.push_back({r - call_r0.back(), pre, f, count});
-            rows += count + 1;
-            f += count;
-            for (int j = f - 1; j > pre; j--)            // the next piece's pre-roll: this one's last valid packet
-                if (st->status[j] == 0) { pre = j; break; }
-        }
-    }
-    call_first.push_back((int)pieces.size());
+    vbm_range_plan plan;
+    const char *err = vbm_plan_ranges(st->first.data(), st->status.data(), st->out_end.data(), st->totals.data(), d->cap,
+                                      nranges, stream_ids, starts, lengths, got, &plan);
+    if (err) { g_vbm_err = err; return VBM_EINVAL; }
     hipStream_t q = (hipStream_t)stream;
     std::vector<int> tab;
-    for (size_t c = 0; c + 1 < call_first.size(); c++) {
-        const int p0 = call_first[c], np = call_first[c + 1] - p0;
+    for (size_t c = 0; c + 1 < plan.call_first.size(); c++) {
+        const int p0 = plan.call_first[c], np = plan.call_first[c + 1] - p0;
         if (np <= 0) continue;
         tab.assign(1, 0);
-        for (int p = p0; p < p0 + np; p++) tab.push_back(tab.back() + pieces[p].count + 1);
+        for (int p = p0; p < p0 + np; p++) tab.push_back(tab.back() + plan.pieces[p].count + 1);
         const int nsb = tab.back();
-        const int r0 = call_r0[c];
+        const int r0 = plan.call_r0[c];
         for (int p = p0; p < p0 + np; p++) {
-            const range_piece &pc = pieces[p];
+            const vbm_range_piece &pc = plan.pieces[p];
             const unsigned long long s = (unsigned long long)starts[r0 + pc.r];
             tab.insert(tab.end(), {pc.r, pc.pre, pc.first, (int)(unsigned)(s & 0xffffffffu), (int)(unsigned)(s >> 32),
                                    got[r0 + pc.r]});
         }
-        const int *parts[1] = {tab.data()};
-        const int lens[1] = {(int)tab.size()};
-        int rc = stage_ints(d, d->d_rtab, parts, lens, 1, q);
+        int rc = stage_ints(d, d->d_rtab, tab.data(), tab.size(), q);
         if (rc) return rc;
-        hipError_t e = hipMemsetAsync(d->d_counts, 0, 2 * sizeof(int), q);
-        if (e == hipSuccess) e = hipMemsetAsync(d->d_res, 0, (size_t)nsb * d->ch * d->half * sizeof(float), q);
-        if (e != hipSuccess) return vbm_set_hip_error(e, "hipMemsetAsync(decode ranges)");
         const vbmd_launch L = d->launch(nsb);
-        if (vbmd_launch_unpack_rows(L, np, d->d_rtab, d->d_rows, st->d_data, st->d_offsets, st->data_bytes, q))
-            return VBM_EHIP;
-        if (vbmd_launch_spectrum(L, d->d_spec, nullptr, q)) return VBM_EHIP;
-        for (int W = 0; W < 2; W++)
-            if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W] >> d->halfrate, d->trig[W], q)) return VBM_EHIP;
+        rc = enqueue_front(d, L, q, "hipMemsetAsync(decode ranges)", [&] {
+            return vbmd_launch_unpack_rows(L, np, d->d_rtab, d->d_rows, st->d_data, st->d_offsets, st->data_bytes, q);
+        });
+        if (rc) return rc;
         if (vbmd_launch_ranges(L, np, d->d_rtab, d->d_rows, st->d_begin, st->d_end, st->d_out_start, d->d_zero,
                                d->d_plan, d_pcm + (size_t)r0 * d->ch * pcm_stride, pcm_stride, q))
             return VBM_EHIP;
@@ -560,57 +575,12 @@ extern "C" int vbm_synthesis_ranges(vbm_decoder *d, const vbm_range_store *st, i
 }
 
 // ---- the index and the range store from a CSR in device memory (decode_index.hip) ------------------------------------
-namespace {
-
-// the argument rules of vbm_range_store_create, for device arrays
-int check_device_csr(const vbm_decoder *d, int nstreams, const long long *stream_packets, const uint8_t *d_data,
-                     const long long *d_offsets, long long data_bytes)
-{
-    if (!d || nstreams <= 0 || !stream_packets || data_bytes < 0 || (data_bytes > 0 && !d_data) || !d_offsets)
-        return VBM_EINVAL;
-    if (stream_packets[0] != 0) { g_vbm_err = "stream_packets[0] must be 0"; return VBM_EINVAL; }
-    for (int i = 0; i < nstreams; i++)
-        if (stream_packets[i + 1] < stream_packets[i]) { g_vbm_err = "stream_packets must not decrease"; return VBM_EINVAL; }
-    if (stream_packets[nstreams] >= INT_MAX) { g_vbm_err = "more than 2^31 - 2 packets in one store"; return VBM_EINVAL; }
-    return VBM_OK;
-}
-
-// k_index_head over all packets, then k_index_scan over the streams, as many per launch as one staging slot holds
-// first packets for (they go up through the ring into d_itab; launches on one stream follow each other)
-int enqueue_index(vbm_decoder *d, int nstreams, const long long *stream_packets, const uint8_t *d_data,
-                  const long long *d_offsets, long long data_bytes, const long long *d_granulepos, const uint8_t *d_eos,
-                  int *d_status, int *d_begin, int *d_end, long long *d_out_start, long long *d_out_end,
-                  long long *d_totals, hipStream_t q)
-{
-    const vbmd_setup *s = (const vbmd_setup *)d->d_setup;
-    if (vbmd_launch_index_head(s, stream_packets[nstreams], d_data, d_offsets, data_bytes, d_status, d_begin, q))
-        return VBM_EHIP;
-    const int room = (int)std::min<size_t>(d->stage_ints - 1, (size_t)INT_MAX - 1);
-    for (int s0 = 0; s0 < nstreams; s0 += room) {
-        const int n = std::min(room, nstreams - s0);
-        const int t = d->stage_turn;
-        d->stage_turn = (t + 1) % kStage;
-        hipError_t e = hipEventSynchronize(d->ev_stage[t]);
-        if (e != hipSuccess) return vbm_set_hip_error(e, "hipEventSynchronize(stage)");
-        for (int i = 0; i <= n; i++) d->h_stage[t][i] = (int)stream_packets[s0 + i];
-        e = hipMemcpyAsync(d->d_itab, d->h_stage[t], ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, q);
-        if (e == hipSuccess) e = hipEventRecord(d->ev_stage[t], q);
-        if (e != hipSuccess) return vbm_set_hip_error(e, "upload of the streams' first packets");
-        if (vbmd_launch_index_scan(s, d->halfrate, n, d->d_itab, d_status, d_granulepos, d_eos, d_begin, d_end,
-                                   d_out_start, d_out_end, d_totals + s0, q))
-            return VBM_EHIP;
-    }
-    return VBM_OK;
-}
-
-}  // namespace
-
 extern "C" int vbm_decode_index_device(vbm_decoder *d, int nstreams, const long long *stream_packets,
                                        const uint8_t *d_data, const long long *d_offsets, long long data_bytes,
                                        const long long *d_granulepos, const uint8_t *d_eos, int *d_status, int *d_begin,
                                        int *d_end, long long *d_out_start, long long *d_totals, void *stream)
 {
-    const int rc = check_device_csr(d, nstreams, stream_packets, d_data, d_offsets, data_bytes);
+    const int rc = check_csr(d, nstreams, stream_packets, d_data, d_offsets, data_bytes);
     if (rc) return rc;
     if (!d_totals || (stream_packets[nstreams] > 0 && (!d_status || !d_begin || !d_end || !d_out_start)))
         return VBM_EINVAL;
@@ -623,54 +593,35 @@ extern "C" int vbm_range_store_create_device(vbm_range_store **out, vbm_decoder 
                                              const long long *d_offsets, long long data_bytes,
                                              const long long *d_granulepos, const uint8_t *d_eos, void *stream)
 {
-    if (!out) return VBM_EINVAL;
-    *out = nullptr;
-    int rc = check_device_csr(d, nstreams, stream_packets, d_data, d_offsets, data_bytes);
+    int rc = new_store(out, d, nstreams, stream_packets, d_data, d_offsets, data_bytes);
     if (rc) return rc;
-    const long long P = stream_packets[nstreams];
-    const size_t np = (size_t)P, ns = (size_t)nstreams;
-    vbm_range_store *st = new vbm_range_store();
-    st->dec = d;
-    st->S = nstreams;
-    st->first.assign(stream_packets, stream_packets + nstreams + 1);
-    st->status.resize(np);
-    st->out_end.resize(np);
-    st->totals.resize(ns);
-    st->data_bytes = data_bytes;
+    vbm_range_store *st = *out;
+    const size_t np = (size_t)stream_packets[nstreams], ns = (size_t)nstreams;
     // what the host planner reads, in one block so that it comes back in one copy: out_end [P], totals [S], status [P]
     const size_t back_bytes = (np + ns) * sizeof(long long) + np * sizeof(int);
     uint8_t *d_back = nullptr;
     hipStream_t q = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-#define CK(x) do { e = (x); if (e != hipSuccess) { rc = vbm_set_hip_error(e, #x); goto fail; } } while (0)
-    {
-        CK(hipMalloc((void **)&st->d_data, data_bytes > 0 ? (size_t)data_bytes : 1));
-        CK(hipMalloc((void **)&st->d_offsets, (np + 1) * sizeof(long long)));
-        CK(hipMalloc((void **)&st->d_out_start, (np ? np : 1) * sizeof(long long)));
-        CK(hipMalloc((void **)&st->d_begin, (np ? np : 1) * sizeof(int)));
-        CK(hipMalloc((void **)&st->d_end, (np ? np : 1) * sizeof(int)));
-        CK(hipMalloc((void **)&d_back, back_bytes));
-        if (data_bytes > 0) CK(hipMemcpyAsync(st->d_data, d_data, (size_t)data_bytes, hipMemcpyDeviceToDevice, q));
-        CK(hipMemcpyAsync(st->d_offsets, d_offsets, (np + 1) * sizeof(long long), hipMemcpyDeviceToDevice, q));
-        long long *d_out_end = (long long *)d_back, *d_totals = d_out_end + np;
-        int *d_status = (int *)(d_totals + ns);
-        rc = enqueue_index(d, nstreams, stream_packets, st->d_data, st->d_offsets, data_bytes, d_granulepos, d_eos,
-                           d_status, st->d_begin, st->d_end, st->d_out_start, d_out_end, d_totals, q);
-        if (rc) goto fail;
-        std::vector<uint8_t> back(back_bytes);
-        CK(hipMemcpyAsync(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost, q));
-        CK(hipStreamSynchronize(q));                       // the one wait: the caller's arrays are free after it
-        if (np) memcpy(st->out_end.data(), back.data(), np * sizeof(long long));
-        memcpy(st->totals.data(), back.data() + np * sizeof(long long), ns * sizeof(long long));
-        if (np) memcpy(st->status.data(), back.data() + (np + ns) * sizeof(long long), np * sizeof(int));
-    }
-#undef CK
+    auto fail = [&](int rc) {
+        (void)hipStreamSynchronize(q);                     // nothing enqueued may still write into the store
+        if (d_back) (void)hipFree(d_back);
+        free_store(st);
+        *out = nullptr;
+        return rc;
+    };
+    CK(hipMalloc((void **)&d_back, back_bytes));
+    if (data_bytes > 0) CK(hipMemcpyAsync(st->d_data, d_data, (size_t)data_bytes, hipMemcpyDeviceToDevice, q));
+    CK(hipMemcpyAsync(st->d_offsets, d_offsets, (np + 1) * sizeof(long long), hipMemcpyDeviceToDevice, q));
+    long long *d_out_end = (long long *)d_back, *d_totals = d_out_end + np;
+    int *d_status = (int *)(d_totals + ns);
+    rc = enqueue_index(d, nstreams, stream_packets, st->d_data, st->d_offsets, data_bytes, d_granulepos, d_eos,
+                       d_status, st->d_begin, st->d_end, st->d_out_start, d_out_end, d_totals, q);
+    if (rc) return fail(rc);
+    std::vector<uint8_t> back(back_bytes);
+    CK(hipMemcpyAsync(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost, q));
+    CK(hipStreamSynchronize(q));                           // the one wait: the caller's arrays are free after it
+    if (np) memcpy(st->out_end.data(), back.data(), np * sizeof(long long));
+    memcpy(st->totals.data(), back.data() + np * sizeof(long long), ns * sizeof(long long));
+    if (np) memcpy(st->status.data(), back.data() + (np + ns) * sizeof(long long), np * sizeof(int));
     (void)hipFree(d_back);
-    *out = st;
     return VBM_OK;
-fail:
-    (void)hipStreamSynchronize(q);                         // nothing enqueued may still write into the store
-    if (d_back) (void)hipFree(d_back);
-    free_store(st);
-    return rc;
 }

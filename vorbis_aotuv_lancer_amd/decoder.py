@@ -4,7 +4,6 @@ the reference's application loop does per packet: vorbis_synthesis + vorbis_synt
 vorbis_synthesis_pcmout + vorbis_synthesis_read (reference examples/decoder_example.c).  Every step from the packet
 bytes to the PCM runs in gfx950 kernels; there is no CPU fallback."""
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -14,8 +13,70 @@ from ._lib import lib, check, VbmError
 ENOTVORBIS, EBADHEADER, EVERSION, ENOTAUDIO, EBADPACKET = -132, -133, -134, -135, -136
 
 
-class DecodeSetup:
+def _i32(ints):
+    """host ints (stream ids, counts, lengths) -> int32 [n], contiguous"""
+    return np.ascontiguousarray(np.asarray(ints, dtype=np.int32))
+
+
+def _per_packet(granulepos, eos, P=None):
+    """The optional per-packet CUDA tensors -> (int64 or None, uint8 or None), contiguous; of P entries when P is given"""
+    gp = granulepos.to(torch.int64).contiguous() if granulepos is not None else None
+    eo = eos.to(torch.uint8).contiguous() if eos is not None else None
+    if P is not None and ((gp is not None and gp.numel() != P) or (eo is not None and eo.numel() != P)):
+        raise ValueError("granulepos and eos need one entry per packet")
+    return gp, eo
+
+
+def _csr_np(data, offsets, granulepos, eos):
+    """A host CSR -> (data uint8, offsets int64, P, granulepos int64 [P] or None, eos uint8 [P] or None), contiguous"""
+    data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8))
+    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    P = len(offsets) - 1
+    if P < 0:
+        raise ValueError("offsets needs at least one entry")
+    gp = None if granulepos is None else np.ascontiguousarray(np.asarray(granulepos, dtype=np.int64))
+    eo = None if eos is None else np.ascontiguousarray(np.asarray(eos, dtype=np.uint8))
+    if (gp is not None and len(gp) != P) or (eo is not None and len(eo) != P):
+        raise ValueError("granulepos and eos need one entry per packet")
+    return data, offsets, P, gp, eo
+
+
+def _csr_t(data, offsets, granulepos, eos, stream_packets):
+    """A CSR in CUDA tensors -> (offsets int64, P, first int64 [S + 1] numpy, granulepos, eos as _per_packet's)"""
+    assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
+    offsets = offsets.to(torch.int64).contiguous()
+    P = offsets.numel() - 1
+    if P < 0:
+        raise ValueError("offsets needs at least one entry")
+    return (offsets, P, _stream_packets(stream_packets, P)) + _per_packet(granulepos, eos, P)
+
+
+def _ptr(a, when=True):
+    """The address of an optional tensor or numpy array for a C call: None for None, and when `when` is false"""
+    if a is None or not when:
+        return None
+    return a.data_ptr() if torch.is_tensor(a) else a.ctypes.data
+
+
+class _Handle:
+    """Owner of the C object ._h: close() destroys it, once, and so does collection"""
+    _destroy = None                  # the name of the entry point that destroys it
+
+    def close(self):
+        if self._h:
+            getattr(lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DecodeSetup(_Handle):
     """The three header packets (vorbis_synthesis_headerin x3).  Host only: no device needed."""
+    _destroy = "vbm_decode_setup_destroy"
 
     def __init__(self, headers):
         headers = [bytes(h) for h in headers]
@@ -63,23 +124,13 @@ class DecodeSetup:
                                         used.ctypes.data)
         return rc, list(info), findex, res, used
 
-    def close(self):
-        if self._h:
-            lib.vbm_decode_setup_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Decoder:
+class Decoder(_Handle):
     """nstreams decode streams on the current CUDA device; up to max_batch packets per call.
     halfrate=True (the reference's vorbis_synthesis_halfrate): the PCM comes out at dsetup.rate / 2, from inverse
     MDCTs of half each block size; every PCM row is blocksizes[1]//4 long instead of blocksizes[1]//2, and sample
     counts, range starts and lengths are output samples.  .rate is the output rate (an int when it is whole)."""
+    _destroy = "vbm_decoder_destroy"
 
     def __init__(self, dsetup, nstreams, max_batch, halfrate=False):
         self.dsetup = dsetup
@@ -102,7 +153,7 @@ class Decoder:
         granulepos: int64 [nsb] (-1: none) or None; eos: uint8 [nsb] or None.
         -> (pcm float32 [nsb, channels, blocksizes[1]//2], samples int32 [nsb], status int32 [nsb]), device tensors
         (blocksizes[1]//4 on a half-rate decoder).  Only enqueues work on the current stream."""
-        ids = np.ascontiguousarray(np.asarray(stream_ids, dtype=np.int32))
+        ids = _i32(stream_ids)
         nsb = len(ids)
         dev = packets.device
         assert packets.dtype == torch.uint8 and packets.dim() == 2 and packets.is_contiguous()
@@ -113,11 +164,9 @@ class Decoder:
             status = torch.empty(nsb, dtype=torch.int32, device=dev)
         else:
             pcm, samples, status = out
-        gp = granulepos.to(torch.int64).contiguous() if granulepos is not None else None
-        eo = eos.to(torch.uint8).contiguous() if eos is not None else None
+        gp, eo = _per_packet(granulepos, eos)
         check(lib.vbm_synthesis_batch(self._h, nsb, ids.ctypes.data, packets.data_ptr(), packets.stride(0),
-                                      nbytes.data_ptr(), gp.data_ptr() if gp is not None else None,
-                                      eo.data_ptr() if eo is not None else None, pcm.data_ptr(), samples.data_ptr(),
+                                      nbytes.data_ptr(), _ptr(gp), _ptr(eo), pcm.data_ptr(), samples.data_ptr(),
                                       status.data_ptr(), self._stream()), "vbm_synthesis_batch")
         self._last = (nsb, dev, packets, nbytes, gp, eo)     # inputs stay alive until the work has run
         return pcm, samples, status
@@ -130,8 +179,7 @@ class Decoder:
         -> (pcm float32 [nruns, channels, pcm_stride], run_samples int32 [nruns], samples int32 [P],
         status int32 [P]), device tensors; run r's PCM is pcm[r, :, :run_samples[r]].  Bit-identical to one packet per
         call through synthesis_batch.  Only enqueues work on the current stream."""
-        ids = np.ascontiguousarray(np.asarray(stream_ids, dtype=np.int32))
-        cnt = np.ascontiguousarray(np.asarray(counts, dtype=np.int32))
+        ids, cnt = _i32(stream_ids), _i32(counts)
         if ids.shape != cnt.shape or ids.ndim != 1:
             raise ValueError("stream_ids and counts must be 1-D and of the same length")
         nruns, P = len(ids), int(cnt.sum())
@@ -150,11 +198,9 @@ class Decoder:
         else:
             pcm, run_samples, samples, status = out
             pcm_stride = pcm.stride(1)
-        gp = granulepos.to(torch.int64).contiguous() if granulepos is not None else None
-        eo = eos.to(torch.uint8).contiguous() if eos is not None else None
+        gp, eo = _per_packet(granulepos, eos)
         check(lib.vbm_synthesis_runs(self._h, nruns, ids.ctypes.data, cnt.ctypes.data, data.data_ptr(),
-                                     offsets.data_ptr(), data.numel(), gp.data_ptr() if gp is not None else None,
-                                     eo.data_ptr() if eo is not None else None, pcm.data_ptr(), pcm_stride,
+                                     offsets.data_ptr(), data.numel(), _ptr(gp), _ptr(eo), pcm.data_ptr(), pcm_stride,
                                      run_samples.data_ptr(), samples.data_ptr(), status.data_ptr(), self._stream()),
               "vbm_synthesis_runs")
         if P:
@@ -167,9 +213,8 @@ class Decoder:
         -> (pcm float32 [n, channels, pcm_stride] on the device, got int32 [n] numpy), pcm[r, :, :got[r]] bit for bit
         the linear decode's samples; nothing else of pcm is written.  Reads and writes no stream state; only
         enqueues work on the current stream."""
-        ids = np.ascontiguousarray(np.asarray(stream_ids, dtype=np.int32))
+        ids, ln = _i32(stream_ids), _i32(lengths)
         st = np.ascontiguousarray(np.asarray(starts, dtype=np.int64))
-        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32))
         if not (ids.ndim == st.ndim == ln.ndim == 1 and len(ids) == len(st) == len(ln)):
             raise ValueError("stream_ids, starts and lengths must be 1-D and of the same length")
         n = len(ids)
@@ -208,23 +253,16 @@ class Decoder:
 
     def restart_streams(self, stream_ids):
         """vorbis_synthesis_restart for these streams (enqueued on the current stream)"""
-        ids = np.ascontiguousarray(np.asarray(stream_ids, dtype=np.int32))
+        ids = _i32(stream_ids)
         check(lib.vbm_decoder_restart_streams(self._h, len(ids), ids.ctypes.data, self._stream()),
               "vbm_decoder_restart_streams")
 
     def reset(self):
         check(lib.vbm_decoder_reset(self._h), "vbm_decoder_reset")
 
-    def close(self):
-        if self._h:
-            lib.vbm_decoder_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _hold_index_inputs(self, *tensors):
+        """decode_index_device's inputs stay alive until the work has run (apart from ._last, which fetch reads)"""
+        self._last_index = tensors
 
 
 def output_rate(rate, halfrate):
@@ -239,23 +277,13 @@ def decode_index(dsetup, data, offsets, granulepos=None, eos=None, halfrate=Fals
     offsets int64 [P+1], granulepos int64 [P], eos uint8 [P] (numpy, as demux_ogg returns them).  halfrate: the index
     of a Decoder(..., halfrate=True), in its output samples.
     -> (status int32 [P], samples int32 [P], out_start int64 [P], total)"""
-    data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8))
-    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    P = len(offsets) - 1
-    if P < 0:
-        raise ValueError("offsets needs at least one entry")
-    gp = None if granulepos is None else np.ascontiguousarray(np.asarray(granulepos, dtype=np.int64))
-    eo = None if eos is None else np.ascontiguousarray(np.asarray(eos, dtype=np.uint8))
-    if (gp is not None and len(gp) != P) or (eo is not None and len(eo) != P):
-        raise ValueError("granulepos and eos need one entry per packet")
+    data, offsets, P, gp, eo = _csr_np(data, offsets, granulepos, eos)
     status, samples = np.zeros(P, np.int32), np.zeros(P, np.int32)
     out_start = np.zeros(P, np.int64)
     total = C.c_longlong()
-    check(lib.vbm_decode_index_halfrate(dsetup._h, int(bool(halfrate)), P, data.ctypes.data if len(data) else None,
-                                        offsets.ctypes.data, len(data), None if gp is None else gp.ctypes.data,
-                                        None if eo is None else eo.ctypes.data, status.ctypes.data,
-                                        samples.ctypes.data, out_start.ctypes.data, C.byref(total)),
-          "vbm_decode_index_halfrate")
+    check(lib.vbm_decode_index_halfrate(dsetup._h, int(bool(halfrate)), P, _ptr(data, len(data)), offsets.ctypes.data,
+                                        len(data), _ptr(gp), _ptr(eo), status.ctypes.data, samples.ctypes.data,
+                                        out_start.ctypes.data, C.byref(total)), "vbm_decode_index_halfrate")
     return status, samples, out_start, total.value
 
 
@@ -275,58 +303,39 @@ def decode_index_device(decoder, data, offsets, granulepos=None, eos=None, strea
     -> (status int32 [P], begin int32 [P], end int32 [P], out_start int64 [P], totals int64 [S]), device tensors;
     end - begin, out_start and totals are decode_index's samples, out_start and total of each stream alone.  Only
     enqueues work on the current stream."""
-    assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
-    offsets = offsets.to(torch.int64).contiguous()
-    P = offsets.numel() - 1
-    if P < 0:
-        raise ValueError("offsets needs at least one entry")
-    first = _stream_packets(stream_packets, P)
-    gp = granulepos.to(torch.int64).contiguous() if granulepos is not None else None
-    eo = eos.to(torch.uint8).contiguous() if eos is not None else None
-    if (gp is not None and gp.numel() != P) or (eo is not None and eo.numel() != P):
-        raise ValueError("granulepos and eos need one entry per packet")
+    offsets, P, first, gp, eo = _csr_t(data, offsets, granulepos, eos, stream_packets)
     dev = offsets.device
     status, begin, end = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
     out_start = torch.empty(P, dtype=torch.int64, device=dev)
     totals = torch.empty(len(first) - 1, dtype=torch.int64, device=dev)
-    check(lib.vbm_decode_index_device(decoder._h, len(first) - 1, first.ctypes.data,
-                                      data.data_ptr() if data.numel() else None, offsets.data_ptr(), data.numel(),
-                                      gp.data_ptr() if gp is not None and P else None,
-                                      eo.data_ptr() if eo is not None and P else None, status.data_ptr(),
+    check(lib.vbm_decode_index_device(decoder._h, len(first) - 1, first.ctypes.data, _ptr(data, data.numel()),
+                                      offsets.data_ptr(), data.numel(), _ptr(gp, P), _ptr(eo, P), status.data_ptr(),
                                       begin.data_ptr(), end.data_ptr(), out_start.data_ptr(), totals.data_ptr(),
                                       decoder._stream()), "vbm_decode_index_device")
-    decoder._last_index = (data, offsets, gp, eo)          # inputs stay alive until the work has run
+    decoder._hold_index_inputs(data, offsets, gp, eo)
     return status, begin, end, out_start, totals
 
 
 def decode_index_scan_host(dsetup, data, offsets, granulepos=None, eos=None, stream_packets=None, halfrate=False):
     """The CPU twin of decode_index_device (vbm_host_decode_index_scan; no device needed), on numpy arrays.
     -> (status int32 [P], begin int32 [P], end int32 [P], out_start int64 [P], totals int64 [S])"""
-    data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8))
-    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    P = len(offsets) - 1
-    if P < 0:
-        raise ValueError("offsets needs at least one entry")
+    data, offsets, P, gp, eo = _csr_np(data, offsets, granulepos, eos)
     first = _stream_packets(stream_packets, P)
-    gp = None if granulepos is None else np.ascontiguousarray(np.asarray(granulepos, dtype=np.int64))
-    eo = None if eos is None else np.ascontiguousarray(np.asarray(eos, dtype=np.uint8))
-    if (gp is not None and len(gp) != P) or (eo is not None and len(eo) != P):
-        raise ValueError("granulepos and eos need one entry per packet")
     status, begin, end = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
     out_start, totals = np.zeros(P, np.int64), np.zeros(len(first) - 1, np.int64)
     check(lib.vbm_host_decode_index_scan(dsetup._h, int(bool(halfrate)), len(first) - 1, first.ctypes.data,
-                                         data.ctypes.data if len(data) else None, offsets.ctypes.data, len(data),
-                                         None if gp is None else gp.ctypes.data, None if eo is None else eo.ctypes.data,
+                                         _ptr(data, len(data)), offsets.ctypes.data, len(data), _ptr(gp), _ptr(eo),
                                          status.ctypes.data, begin.ctypes.data, end.ctypes.data, out_start.ctypes.data,
                                          totals.ctypes.data), "vbm_host_decode_index_scan")
     return status, begin, end, out_start, totals
 
 
-class RangeStore:
+class RangeStore(_Handle):
     """The packets of many streams of one Decoder's headers in device memory, with their index, for
     Decoder.synthesis_ranges.  streams: (data, offsets, granulepos, eos) tuples as demux_ogg returns them (granulepos
     / eos may be None).  .totals: int64 [nstreams], each stream's linear decode length (ov_pcm_total), at the
     decoder's rate: .halfrate is the decoder's."""
+    _destroy = "vbm_range_store_destroy"
 
     def __init__(self, decoder, streams):
         streams = list(streams)
@@ -347,14 +356,16 @@ class RangeStore:
         offsets = np.ascontiguousarray(np.concatenate(offs))
         gp = np.ascontiguousarray(np.concatenate(gps))
         eo = np.ascontiguousarray(np.concatenate(eoss))
-        first = np.ascontiguousarray(np.asarray(first, np.int64))
-        self.decoder, self.nstreams, self.halfrate = decoder, len(streams), decoder.halfrate
+        self._create(decoder, np.ascontiguousarray(np.asarray(first, np.int64)), "vbm_range_store_create",
+                     _ptr(data, len(data)), offsets.ctypes.data, len(data), gp.ctypes.data, eo.ctypes.data)
+
+    def _create(self, decoder, first, create, *csr):
+        """the tail of both constructors: the fields, the C store from create(..., stream_packets, *csr), its totals"""
+        self.decoder, self.nstreams, self.halfrate = decoder, len(first) - 1, decoder.halfrate
         self.packets = first
         self._h = C.c_void_p()
-        check(lib.vbm_range_store_create(C.byref(self._h), decoder._h, len(streams), first.ctypes.data,
-                                         data.ctypes.data if len(data) else None, offsets.ctypes.data, len(data),
-                                         gp.ctypes.data, eo.ctypes.data), "vbm_range_store_create")
-        self.totals = np.zeros(len(streams), np.int64)
+        check(getattr(lib, create)(C.byref(self._h), decoder._h, self.nstreams, first.ctypes.data, *csr), create)
+        self.totals = np.zeros(self.nstreams, np.int64)
         check(lib.vbm_range_store_totals(self._h, self.totals.ctypes.data), "vbm_range_store_totals")
 
     @classmethod
@@ -369,39 +380,30 @@ class RangeStore:
             b = payload
             payload, offsets, granulepos, eos = b.payload, b.offsets, b.granulepos, b.eos
             stream_packets = np.append(np.asarray(b.packet_base, dtype=np.int64), offsets.numel() - 1)
-        assert payload.dtype == torch.uint8 and payload.dim() == 1 and payload.is_contiguous()
-        offsets = offsets.to(torch.int64).contiguous()
-        P = offsets.numel() - 1
-        if P < 0 or stream_packets is None:
+        if offsets.numel() < 1 or stream_packets is None:
             raise ValueError("offsets needs at least one entry, and stream_packets must be given")
-        first = _stream_packets(stream_packets, P)
-        gp = granulepos.to(torch.int64).contiguous() if granulepos is not None else None
-        eo = eos.to(torch.uint8).contiguous() if eos is not None else None
-        if (gp is not None and gp.numel() != P) or (eo is not None and eo.numel() != P):
-            raise ValueError("granulepos and eos need one entry per packet")
+        offsets, P, first, gp, eo = _csr_t(payload, offsets, granulepos, eos, stream_packets)
         self = cls.__new__(cls)
-        self.decoder, self.nstreams, self.halfrate = decoder, len(first) - 1, decoder.halfrate
-        self.packets = first
-        self._h = C.c_void_p()
-        check(lib.vbm_range_store_create_device(C.byref(self._h), decoder._h, self.nstreams, first.ctypes.data,
-                                                payload.data_ptr() if payload.numel() else None, offsets.data_ptr(),
-                                                payload.numel(), gp.data_ptr() if gp is not None and P else None,
-                                                eo.data_ptr() if eo is not None and P else None, decoder._stream()),
-              "vbm_range_store_create_device")
-        self.totals = np.zeros(self.nstreams, np.int64)
-        check(lib.vbm_range_store_totals(self._h, self.totals.ctypes.data), "vbm_range_store_totals")
+        self._create(decoder, first, "vbm_range_store_create_device", _ptr(payload, payload.numel()),
+                     offsets.data_ptr(), payload.numel(), _ptr(gp, P), _ptr(eo, P), decoder._stream())
         return self
 
-    def close(self):
-        if self._h:
-            lib.vbm_range_store_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _demux_host(name, blob):
+    """demux_ogg of one file or link, its errors under the entry's name"""
+    from .stream import demux_ogg
+    try:
+        return demux_ogg(blob)
+    except VbmError as e:
+        raise VbmError(f"{name}: {e}") from None
+
+
+def _raise_failed(batch, names):
+    """VbmError for the first failed entry of a device-demuxed batch"""
+    for name, code in zip(names, batch.status):
+        if code:
+            raise VbmError(f"{name}: vbm_ogg_demux_scan failed with code {code}: not one valid logical Ogg stream "
+                           "(vbm_ogg_demux on the file alone names the page)")
 
 
 class OggIndex:
@@ -417,37 +419,20 @@ class OggIndex:
     bit."""
 
     def __init__(self, files, max_batch=4096, halfrate=False, device_demux=False):
-        from .stream import demux_ogg, demux_ogg_device
+        from .stream import _read_files, demux_ogg_device
         if max_batch < 2:
             raise ValueError("max_batch must be at least 2")
-        if device_demux:
-            files = list(files)
-            if not files:
-                raise ValueError("OggIndex needs at least one file")
-            b = demux_ogg_device(files)
-            for i, f in enumerate(files):
-                if b.status[i]:
-                    name = os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}"
-                    raise VbmError(f"{name}: vbm_ogg_demux_scan failed with code {b.status[i]}: not one valid "
-                                   "logical Ogg stream (vbm_ogg_demux on the file alone names the page)")
-            self._open(b.headers, max_batch, halfrate)
-            self.store = RangeStore.from_device(self.decoder, b)
-            self.total_samples = self.store.totals
-            return
-        demuxed = []
-        for i, f in enumerate(files):
-            name = os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}"
-            if isinstance(f, (str, os.PathLike)):
-                with open(f, "rb") as fh:
-                    f = fh.read()
-            try:
-                demuxed.append(demux_ogg(f))
-            except VbmError as e:
-                raise VbmError(f"{name}: {e}") from None
-        if not demuxed:
+        names, blobs = _read_files(files)
+        if not blobs:
             raise ValueError("OggIndex needs at least one file")
-        self._open([d[0] for d in demuxed], max_batch, halfrate)
-        self.store = RangeStore(self.decoder, [d[1:] for d in demuxed])
+        if device_demux:
+            b = demux_ogg_device(blobs)
+            _raise_failed(b, names)
+        else:
+            demuxed = [_demux_host(name, blob) for name, blob in zip(names, blobs)]
+        self._open(b.headers if device_demux else [d[0] for d in demuxed], max_batch, halfrate)
+        self.store = (RangeStore.from_device(self.decoder, b) if device_demux
+                      else RangeStore(self.decoder, [d[1:] for d in demuxed]))
         self.total_samples = self.store.totals
 
     def _open(self, headers, max_batch, halfrate):
@@ -474,6 +459,60 @@ class OggIndex:
         self.setup.close()
 
 
+def _demux_files(files, device_demux, chained):
+    """decode_ogg's demux -> (names, entries, file_links): entry i, a file or with chained a link, is (headers, data,
+    offsets, granulepos, eos) as demux_ogg's, offsets a numpy array and the rest where the demux left them (CUDA tensors
+    or numpy arrays); file f is entries file_links[f] .. file_links[f + 1] - 1"""
+    from .stream import _read_files, demux_ogg_device, split_ogg_chain
+    if device_demux:
+        b = demux_ogg_device(files, chained=chained)
+        _raise_failed(b, b.names)
+        offsets, entries = b.offsets.cpu().numpy(), []
+        for i in range(len(b)):
+            a, n, at = int(b.packet_base[i]), int(b.packets[i]), int(b.payload_base[i])
+            entries.append((b.headers[i], b.payload[at:at + int(b.payload_bytes[i])], offsets[a:a + n + 1] - at,
+                            b.granulepos[a:a + n], b.eos[a:a + n]))
+        return b.names, entries, b.file_links
+    names, entries, file_links = [], [], [0]
+    for name, blob in zip(*_read_files(files)):
+        links = [(f"{name} link {k}", link) for k, link in enumerate(split_ogg_chain(blob))] if chained else [(name, blob)]
+        for entry, link in links:
+            names.append(entry)
+            entries.append(_demux_host(entry, link))
+        file_links.append(len(entries))
+    return names, entries, file_links
+
+
+def _calls(src, max_packets):
+    """The synthesis_runs calls over one group's streams src[s] = (data, offsets, granulepos, eos), each yielded as
+    (ids, counts, data, offsets, granulepos, eos): its runs and their CSR"""
+    pos = [0] * len(src)
+    while True:
+        live = [s for s in range(len(src)) if pos[s] < len(src[s][1]) - 1]
+        if not live:
+            return
+        share, budget = max(1, max_packets // len(live)), max_packets
+        ids, counts = [], []
+        for s in live:                                    # the row budget in equal shares over the unfinished streams
+            c = min(len(src[s][1]) - 1 - pos[s], share, budget)
+            if c <= 0:
+                break
+            ids.append(s)
+            counts.append(c)
+            budget -= c
+        datas, offs, gps, eoss, base = [], [np.zeros(1, np.int64)], [], [], 0
+        for s, c in zip(ids, counts):
+            data, o, gp, eo = src[s]
+            a, b = int(o[pos[s]]), int(o[pos[s] + c])
+            datas.append(data[a:b])
+            offs.append(o[pos[s] + 1:pos[s] + c + 1] - a + base)
+            gps.append(gp[pos[s]:pos[s] + c])
+            eoss.append(eo[pos[s]:pos[s] + c])
+            base += b - a
+            pos[s] += c
+        yield ids, counts, torch.cat(datas), np.concatenate(offs), torch.cat(gps), torch.cat(eoss)
+
+
 def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chained=False):
     """.ogg files (bytes or paths), one logical stream each -> [(pcm float32 [channels, n] contiguous on the current
     device, rate)], one per file.  Files whose identification and setup headers are byte-equal share one DecodeSetup
@@ -487,40 +526,11 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
     file of (pcm, rate), one per link in file order.  Every link decodes as the file it would be alone: its own
     headers, fresh overlap state, its own granule positions; links and files with byte-equal identification and setup
     headers share a decoder.  A link that is not one valid logical stream raises VbmError naming file and link."""
-    from .stream import demux_ogg, demux_ogg_device, split_ogg_chain
     if max_packets <= 0:
         raise ValueError("max_packets must be positive")
     dev = torch.device("cuda", torch.cuda.current_device())
-    names, demuxed, groups = [], [], {}
-    file_links = None
-    if device_demux:
-        b = demux_ogg_device(files, chained=chained)
-        names = b.names
-        file_links = b.file_links if chained else None
-        offsets = b.offsets.cpu().numpy()
-        for i in range(len(b)):
-            if b.status[i]:
-                raise VbmError(f"{names[i]}: vbm_ogg_demux_scan failed with code {b.status[i]}: not one valid logical "
-                               "Ogg stream (vbm_ogg_demux on the file alone names the page)")
-            a, n, at = int(b.packet_base[i]), int(b.packets[i]), int(b.payload_base[i])
-            # (headers, data, offsets, granulepos, eos) as demux_ogg's, data / granulepos / eos left on the device
-            demuxed.append((b.headers[i], b.payload[at:at + int(b.payload_bytes[i])], offsets[a:a + n + 1] - at,
-                            b.granulepos[a:a + n], b.eos[a:a + n]))
-    else:
-        file_links = [0]
-        for i, f in enumerate(files):
-            name = os.fspath(f) if isinstance(f, (str, os.PathLike)) else f"file {i}"
-            if isinstance(f, (str, os.PathLike)):
-                with open(f, "rb") as fh:
-                    f = fh.read()
-            entries = [(f"{name} link {k}", link) for k, link in enumerate(split_ogg_chain(f))] if chained else [(name, f)]
-            for entry, blob in entries:
-                names.append(entry)
-                try:
-                    demuxed.append(demux_ogg(blob))
-                except VbmError as e:
-                    raise VbmError(f"{entry}: {e}") from None
-            file_links.append(len(demuxed))
+    names, demuxed, file_links = _demux_files(files, device_demux, chained)
+    groups = {}
     for i, d in enumerate(demuxed):
         groups.setdefault((d[0][0], d[0][2]), []).append(i)
     for members in groups.values():                       # every setup is checked before any work is enqueued
@@ -534,36 +544,11 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
         ds = DecodeSetup(demuxed[members[0]][0])
         dec = Decoder(ds, len(members), max_packets, halfrate=halfrate)
         keep.append((ds, dec))
-        half = dec.row
-        up = (lambda x: x) if device_demux else (lambda x: torch.from_numpy(x).to(dev))
+        up = lambda x: torch.as_tensor(x, device=dev)     # host-demuxed arrays go up here; demuxed on the device: as is
         src = [(up(demuxed[j][1]), demuxed[j][2], up(demuxed[j][3]), up(demuxed[j][4])) for j in members]
-        pos = [0] * len(members)
-        while True:
-            live = [s for s in range(len(members)) if pos[s] < len(src[s][1]) - 1]
-            if not live:
-                break
-            share, budget = max(1, max_packets // len(live)), max_packets
-            ids, counts = [], []
-            for s in live:                                # the row budget in equal shares over the unfinished streams
-                c = min(len(src[s][1]) - 1 - pos[s], share, budget)
-                if c <= 0:
-                    break
-                ids.append(s)
-                counts.append(c)
-                budget -= c
-            datas, offs, gps, eoss, base = [], [np.zeros(1, np.int64)], [], [], 0
-            for s, c in zip(ids, counts):
-                data, o, gp, eo = src[s]
-                a, b = int(o[pos[s]]), int(o[pos[s] + c])
-                datas.append(data[a:b])
-                offs.append(o[pos[s] + 1:pos[s] + c + 1] - a + base)
-                gps.append(gp[pos[s]:pos[s] + c])
-                eoss.append(eo[pos[s]:pos[s] + c])
-                base += b - a
-                pos[s] += c
-            pcm, run_samples, _, _ = dec.synthesis_runs(
-                ids, counts, torch.cat(datas), torch.from_numpy(np.concatenate(offs)).to(dev),
-                granulepos=torch.cat(gps), eos=torch.cat(eoss), pcm_stride=max(counts) * half)
+        for ids, counts, data, offsets, gp, eo in _calls(src, max_packets):
+            pcm, run_samples, _, _ = dec.synthesis_runs(ids, counts, data, torch.from_numpy(offsets).to(dev),
+                                                        granulepos=gp, eos=eo, pcm_stride=max(counts) * dec.row)
             for r, s in enumerate(ids):
                 pieces[members[s]].append((pcm[r], nlens + r))
             lens.append(run_samples)
