@@ -102,9 +102,10 @@ struct vbm_encoder {
     // batch for one workspace, captured the second time it is needed and replayed from then on.
     struct round_graph { hipGraphExec_t exec = nullptr; int uses = 0; };
     // [workspace][block type; 4 = the big batch (type 3, first round): its launches differ from a small type-3 batch's
-    // (throughput variants of the kernels, own streams)][0 whole pipeline, 1 front half, 2 back half]
+    // (throughput variants of the kernels, own streams)][type_job::part - 1: transforms, psychoacoustics, back half]
     round_graph gJ[kMaxWS][5][3];
     hipEvent_t ev_state_big[kMaxWS] = {};  // front half of the big batch run in the workspace
+    hipEvent_t ev_tf_big[kMaxWS] = {};     // transforms of the big batch run in the workspace (they run on another stream)
     int queue_last_w[4] = {-1, -1, -1, -1};   // workspace of the newest job on sub[0..3]
     bool small_streams_set = false;
     hipEvent_t ev_cap_fork = nullptr, ev_cap_join[4] = {};
@@ -173,6 +174,7 @@ extern "C" void vbm_encoder_destroy(vbm_encoder *e)
             for (int k = 0; k < 3; k++)
                 if (e->gJ[i][m][k].exec) (void)hipGraphExecDestroy(e->gJ[i][m][k].exec);
         if (e->ev_state_big[i]) (void)hipEventDestroy(e->ev_state_big[i]);
+        if (e->ev_tf_big[i]) (void)hipEventDestroy(e->ev_tf_big[i]);
     }
     if (e->ev_cap_fork) (void)hipEventDestroy(e->ev_cap_fork);
     for (int i = 0; i < 4; i++)
@@ -404,7 +406,8 @@ extern "C" int vbm_encoder_create(vbm_encoder **out, vbm_setup_handle *setup, in
         for (int m = 0; m < 4; m++)
             if (hipEventCreateWithFlags(&e->ev_done[i][m], hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&e->ev_state[i][m], hipEventDisableTiming) != hipSuccess ||
-                (m == 0 && hipEventCreateWithFlags(&e->ev_state_big[i], hipEventDisableTiming) != hipSuccess)) {
+                (m == 0 && (hipEventCreateWithFlags(&e->ev_state_big[i], hipEventDisableTiming) != hipSuccess ||
+                            hipEventCreateWithFlags(&e->ev_tf_big[i], hipEventDisableTiming) != hipSuccess))) {
                 vbm_encoder_destroy(e);
                 return VBM_EHIP;
             }
@@ -885,7 +888,8 @@ struct type_job {
     // rounds run as graphs (device_round_run_graphs): the job is one piece of a group that is forked from / joined
     // to its origin stream by the caller, in or outside a stream capture
     int few = 0;                 // small batch behind a large launch bound (device-built rounds): latency-bound kernel variants
-    int part = 0;                // 0 whole pipeline, 1 front half only (up to the block-state update), 2 back half only
+    int part = 0;                // 0 whole pipeline; one piece of it: 1 transforms, 2 psychoacoustics (prologue up to the
+                                 // block-state update), 3 back half
     bool grouped = false;        // no ev_fork wait, no dependency waits, no state / done events, no output copy
     hipStream_t q_on = nullptr;  // grouped: the stream to enqueue on
 };
@@ -919,10 +923,11 @@ static int enqueue_job(vbm_encoder *e, const type_job &j)
     hipStream_t q = j.grouped ? j.q_on : (j.big ? e->sub[4] : e->sub[m]);
     const int qid = j.big ? 4 : m;
     if (!j.grouped && (err = hipStreamWaitEvent(q, e->ev_fork, 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-    if (!j.grouped && j.part != 2) vbm_debug_delay_point(j.big ? VBM_DP_JOB_BIG : VBM_DP_JOB_SMALL, q);
+    if (!j.grouped) vbm_debug_delay_point(j.big ? VBM_DP_JOB_BIG : VBM_DP_JOB_SMALL, q);
     const vbm_batch v = job_batch(e, j);
-    if (j.part != 2) {
-        if ((rc = launch_transforms(e, v, q, j.timed))) return rc;
+    if (j.part <= 1 && (rc = launch_transforms(e, v, q, j.timed))) return rc;
+    if (j.part == 1) return VBM_OK;
+    if (j.part != 3) {
         // the transforms read the block's PCM only; from here on the carried stream state is involved: the batches
         // this batch's streams were last part of come first (those on this very HIP stream already do)
         if (!j.grouped) {
@@ -938,7 +943,7 @@ static int enqueue_job(vbm_encoder *e, const type_job &j)
         // kernels side by side crowd out the back half of the round before (profiles/r03/README.md).
         if ((rc = launch_psy(e, v, q, j.timed))) return rc;
     }
-    if (j.part == 1) return VBM_OK;
+    if (j.part == 2) return VBM_OK;
     if (!j.grouped) {
         if ((err = hipEventRecord(e->ev_state[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
         if (j.big) {   // hand over to the back-half stream of big batches
@@ -1268,6 +1273,17 @@ static int run_group(vbm_encoder *e, vbm_encoder::round_graph &g, hipStream_t or
 // through the transition batches.  A job waits for the newest state event of every type it may follow, as they stood
 // before the round's own jobs went in; for the long types that includes the front half of the newest big batch (the
 // call's own in its later rounds: a stream that has fallen behind delivers a long block in every round).
+//
+// A batch is three graphs, each a linear capture of one stream: transforms (spread flags, window + MDCT, window + FFT +
+// log spectrum), psychoacoustics (prologue .. block state), back half.  The transforms run AHEAD of the state waits,
+// as in the host-built rounds (enqueue_job): a small batch's on its own stream right after the fork, the big batch's on
+// `fork` itself with ev_tf_big behind them, which sub[4] waits for beside its predecessors.  Why that is safe: they
+// read the round's gathered block PCM (the front end's block buffer of workspace w), the round's window flags
+// (d_wflags[w]) and the round's counts (d_counts_ws + 4 * w), all complete at ev_fork, and tables of the setup; they
+// write mdct_bm, logfft_bm, local_ampmax and wflags_cb of the job's own lane region, which configure() / slice_of()
+// take from bw[w]: every one an allocation of workspace w alone, none of the carried stream state (vbm_batch::st).
+// Workspace w is free by then: vbm_encoder_device_round_open has made `fork` wait for the done events of every batch
+// that ran in it, before the round was planned, and ev_fork comes after that on the same stream.
 extern "C" void vbm_debug_stamp(hipStream_t st, int tag);   // util_kernels.hip (timing experiments)
 static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, const int *cap, const float *d_blocks,
                                    uint8_t *d_packets, int *d_packet_bytes, bool first_round, hipStream_t fork)
@@ -1306,10 +1322,17 @@ static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, cons
     };
     int rc;
     if (has_big) {      // the long pole first
-        hipStream_t qF = e->sub[4], qB = e->sub[5];
-        if ((err = hipStreamWaitEvent(qF, e->ev_fork, 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
+        // The transforms go to the front end's own stream, right behind the fork: nothing the front end queues next
+        // (its buffer shift, the next round's plan) is needed sooner than they are, and sub[4] still runs the front
+        // half of the batch before.  (On sub[3], which carries no job in a first round, they measured no gain:
+        // profiles/transforms_ahead.)
+        hipStream_t qT = fork, qF = e->sub[4], qB = e->sub[5];
+        type_job jt = job_of(3, 1), jf = job_of(3, 2), jb = job_of(3, 3);
+        vbm_debug_delay_point(VBM_DP_DEV_BIG_TRANSFORMS, qT);
+        if ((rc = run_group(e, e->gJ[w][4][0], qT, &jt, 1))) return rc;
+        if ((err = hipEventRecord(e->ev_tf_big[w], qT)) != hipSuccess ||
+            (err = hipStreamWaitEvent(qF, e->ev_tf_big[w], 0)) != hipSuccess) return vbm_set_hip_error(err, "big batch transforms");
         if ((rc = wait_preds(qF, 3, 4))) return rc;
-        type_job jf = job_of(3, 1), jb = job_of(3, 2);
         vbm_debug_stamp(qF, 10);
         vbm_debug_delay_point(VBM_DP_DEV_BIG_FRONT, qF);
         if ((rc = run_group(e, e->gJ[w][4][1], qF, &jf, 1))) return rc;
@@ -1329,12 +1352,14 @@ static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, cons
         if (!cap[m] || (m == 3 && has_big)) continue;
         hipStream_t q = e->sub[m];
         if ((err = hipStreamWaitEvent(q, e->ev_fork, 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
+        // three graphs: the transforms ahead of the state waits, and the state event between the psychoacoustics and
+        // the back half: what follows this batch on another stream waits for its front half only (the chain short
+        // blocks -> transition -> long blocks of the next call is what the big batch of the next call waits for)
+        type_job jt = job_of(m, 1), j = job_of(m, 2), j2 = job_of(m, 3);
+        jt.few = j.few = j2.few = 1;
+        vbm_debug_delay_point(VBM_DP_DEV_SMALL_TRANSFORMS, q);
+        if ((rc = run_group(e, e->gJ[w][m][0], q, &jt, 1))) return rc;
         if ((rc = wait_preds(q, m, m))) return rc;
-        // two graphs, the state event between them: what follows this batch on another stream waits for its front
-        // half only (the chain short blocks -> transition -> long blocks of the next call is what the big batch of
-        // the next call waits for)
-        type_job j = job_of(m, 1), j2 = job_of(m, 2);
-        j.few = j2.few = 1;
         vbm_debug_stamp(q, 20 + m);
         vbm_debug_delay_point(VBM_DP_DEV_SMALL_FRONT, q);
         if ((rc = run_group(e, e->gJ[w][m][1], q, &j, 1))) return rc;

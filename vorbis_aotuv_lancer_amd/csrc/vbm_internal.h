@@ -15,7 +15,7 @@ enum vbm_delay_point {
     VBM_DP_JOB_OUT = 4,        // before a batch's outputs are copied to the caller's buffers
     VBM_DP_FE_FORK = 5,        // front end: between the gathers of a round and the round's fork
     VBM_DP_FE_SHIFT = 6,       // front end: before the buffer shift of a round
-    VBM_DP_DEV_BIG_FRONT = 7,  // device-built round: before the big batch's front-half graph
+    VBM_DP_DEV_BIG_FRONT = 7,  // device-built round: before the big batch's psychoacoustics graph, behind its state waits
     VBM_DP_DEV_BIG_BACK = 8,   // ... back-half graph
     VBM_DP_DEV_SMALL_FRONT = 9,
     VBM_DP_DEV_SMALL_BACK = 10,
@@ -24,5 +24,7 @@ enum vbm_delay_point {
     VBM_DP_BATCH_BACK = 13,    // ... the back half
     VBM_DP_FE_WRITE = 14,      // front end: before the append of a write
     VBM_DP_DEV_OUT = 15,       // device-built round: before a batch's output copy
+    VBM_DP_DEV_BIG_TRANSFORMS = 16,    // device-built round: before the big batch's transforms graph (ahead of its state waits)
+    VBM_DP_DEV_SMALL_TRANSFORMS = 17,  // ... a small batch's
 };
 void vbm_debug_delay_point(int point, hipStream_t q);
