@@ -534,8 +534,51 @@ int vbm_host_ogg_chain_split(vbm_ogg_chain *ch, int nfiles, const uint8_t *data,
  * (d_data may be null when there are no bytes, d_info when n is 0, d_payload / d_granulepos / d_eos when their capacity
  * is 0), a negative capacity, fill without a scan, a host feed in a device call or the other way round.
  *   vbm_host_ogg_feed_scan / _fill   the same source on the CPU with host pointers and a host feed; _status, _headers,
- *                            _reset_streams and _destroy take both kinds. */
+ *                            _reset_streams and _destroy take both kinds.
+ *
+ * Resync mode (vbm_ogg_feed_create2 with VBM_OGG_FEED_RESYNC; flags = 0 is vbm_ogg_feed_create) is the tolerant form for a
+ * live mount: it follows a chain of logical streams (links), joins a stream mid-way and goes on after lost or damaged
+ * pages, as libogg's ogg_sync_pageseek / ogg_stream_pagein do.  scan and fill are used as before; the rules differ
+ * (stated once in csrc/ogg_feed.h, oggfeed_rs_walk):
+ *   1 finding a page: at the walk's position a page header is "OggS" and version 0.  Without one the walk moves to the
+ *     next "OggS" of the run and counts the bytes passed as skipped; with none in the run its last 3 bytes are carried
+ *     (they may begin one).  A candidate whose header, lacing table or body is not all present is carried, within
+ *     max_page_carry (above it: VBM_OGG_FEED_EBIG, as in strict mode; only 65307 is immune to a false header that claims
+ *     a long page).  A whole candidate has its CRC checked at once; with a bad CRC the walk resumes one byte on and the
+ *     candidate counts as skipped bytes.
+ *   2 whose page: a page with a good CRC and the beginning-of-stream flag is a link start.  Any other page is ignored
+ *     (and counted) when its serial number is not the current link's, when no link is open, when the link is bad (see 3)
+ *     or has delivered its end-of-stream page.
+ *   3 a page of the link whose sequence number is not the expected one, or whose continuation flag does not match
+ *     whether a packet is open, is a discontinuity page: the open packet is dropped; if the flag says continued, the
+ *     leading segments through the first lacing value below 255 belong to no packet; the expected sequence becomes the
+ *     page's plus 1; the next packet completed carries a gap mark.  While the link's headers are open (fewer than three
+ *     packets) the link becomes bad instead: nothing more of it is delivered, headers_ready stays 0 and the slot waits
+ *     for the next link start.  That is no status.
+ *   4 a link start closes the current link, drops an open packet, zeroes the counts and takes the page's serial and
+ *     sequence number.  The header store is refilled: headers_ready is 0 until the new link's third packet completes,
+ *     then vbm_ogg_feed_headers returns the new link's headers.  The first audio packet of every link after the slot's
+ *     first carries a gap mark: the caller switches or restarts its decoder there.
+ *   5 a link start or a discontinuity page is taken only as the first page a call takes for the slot.  Met later it ends
+ *     the slot's walk in front of it: unvisited bytes of the carried tail stay the tail, unvisited bytes of the chunk are
+ *     reported as `left`, and the caller pushes chunk[len - left:] again (that push takes the stopping page first).  So
+ *     one call delivers, per slot, packets of one link with nothing lost between them: at most the first carries a mark.
+ *     A call takes at most chunk / 27 + 1 pages for a slot (its page records): the carried tail can hold whole pages,
+ *     behind a candidate that claimed more bytes than it had, and the page after the last record ends the walk the same
+ *     way.
+ *   6 `end` is honoured only when left == 0 and the walk did not end at a stop: a partial page or an open packet is
+ *     dropped and the slot is done.  After a stop with `end` given, push again (with no bytes if left == 0) while
+ *     pending > 0.  The only statuses are VBM_OGG_FEED_EBIG and VBM_EINVAL; VBM_EOGG does not occur.
+ *   vbm_ogg_feed_create2     vbm_ogg_feed_create with flags: 0, or VBM_OGG_FEED_RESYNC (16 bytes more per slot); any other
+ *                            bit is VBM_EINVAL.
+ *   vbm_ogg_feed_scan_events  between scan and fill: d_events[i] (device) for list entry i of the last scan.  VBM_EINVAL
+ *                            without a scan, and on a strict feed.
+ *   vbm_ogg_feed_fill_gaps   vbm_ogg_feed_fill plus d_gap [packet_cap] (uint8, device; NULL: no marks are written):
+ *                            1 when something was lost between the slot's previous delivered packet and this one.
+ *                            vbm_ogg_feed_fill on a resync feed drops the marks; on a strict feed fill_gaps writes zeros.
+ *   vbm_host_ogg_feed_create2 / _scan_events / _fill_gaps   the host twin. */
 #define VBM_OGG_FEED_EBIG (-1003)
+#define VBM_OGG_FEED_RESYNC 1u
 typedef struct {
     int status;                 /* 0, VBM_EOGG or VBM_OGG_FEED_EBIG */
     int headers_ready;
@@ -547,6 +590,15 @@ typedef struct {
     long long pending;          /* bytes of the incomplete trailing page */
     long long consumed;         /* bytes of the whole pages this call takes */
 } vbm_ogg_feed_info;
+typedef struct {                /* resync mode: what a scan met for one list entry */
+    int link;                   /* the link the call's packets belong to, from 0 over the slot's life (0 too before the first starts) */
+    int link_started;           /* the first page this call took began a link */
+    int link_bad;               /* the link lost a page while its headers were open */
+    int gaps;                   /* packets of this call that carry a gap mark */
+    long long skipped_bytes;    /* bytes the call passed that belong to no page with a good CRC */
+    long long ignored_pages;    /* pages with a good CRC that were ignored */
+    long long left;             /* bytes at the end of the chunk that the call did not look at */
+} vbm_ogg_feed_events;
 typedef struct vbm_ogg_feed vbm_ogg_feed;
 int vbm_ogg_feed_create(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
                         int max_packet_bytes, int header_cap);
@@ -564,6 +616,17 @@ int vbm_host_ogg_feed_scan(vbm_ogg_feed *fd, int n, const int *ids, const uint8_
                            const uint8_t *end, vbm_ogg_feed_info *info, long long *totals);
 int vbm_host_ogg_feed_fill(vbm_ogg_feed *fd, uint8_t *payload, long long payload_cap, long long *offsets,
                            long long *granulepos, uint8_t *eos, long long packet_cap);
+
+int vbm_ogg_feed_create2(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
+                         int max_packet_bytes, int header_cap, unsigned flags);
+int vbm_host_ogg_feed_create2(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
+                              int max_packet_bytes, int header_cap, unsigned flags);
+int vbm_ogg_feed_scan_events(vbm_ogg_feed *fd, vbm_ogg_feed_events *d_events, void *stream);
+int vbm_host_ogg_feed_scan_events(vbm_ogg_feed *fd, vbm_ogg_feed_events *events);
+int vbm_ogg_feed_fill_gaps(vbm_ogg_feed *fd, uint8_t *d_payload, long long payload_cap, long long *d_offsets,
+                           long long *d_granulepos, uint8_t *d_eos, uint8_t *d_gap, long long packet_cap, void *stream);
+int vbm_host_ogg_feed_fill_gaps(vbm_ogg_feed *fd, uint8_t *payload, long long payload_cap, long long *offsets,
+                                long long *granulepos, uint8_t *eos, uint8_t *gap, long long packet_cap);
 
 typedef struct vbm_ogg_stream vbm_ogg_stream;
 int vbm_ogg_stream_create(vbm_ogg_stream **os, int serialno);
@@ -747,6 +810,18 @@ int  vbm_synthesis_runs(vbm_decoder *dec, int nruns, const int *stream_ids /*hos
                         const long long *d_granulepos /*[P] or NULL*/, const uint8_t *d_eos /*[P] or NULL*/,
                         float *d_pcm, long pcm_stride, int *d_run_samples /*[nruns]*/,
                         int *d_samples /*[P]*/, int *d_status /*[P]*/, void *stream);
+/* vbm_synthesis_runs with a gap mark per packet (vbm_ogg_feed_fill_gaps writes them): d_gap[k] != 0 says packets were
+ * lost in front of packet k, and before it is laid in the stream's granule position and sample count become -1, as
+ * vorbis_synthesis_blockin does at v->sequence + 1 != vb->sequence (lib/block.c:911-915).  The overlap tail and the
+ * previous block size are kept, as the reference keeps them.  A mark on a row with an error goes to the stream's next
+ * valid packet, in this call or a later one: that packet follows a lost one too.  d_gap NULL is vbm_synthesis_runs. */
+int  vbm_synthesis_runs_gaps(vbm_decoder *dec, int nruns, const int *stream_ids /*host, distinct*/,
+                             const int *run_packets /*host, >= 0*/,
+                             const uint8_t *d_data, const long long *d_offsets /*[P+1]*/, long long data_bytes,
+                             const long long *d_granulepos /*[P] or NULL*/, const uint8_t *d_eos /*[P] or NULL*/,
+                             const uint8_t *d_gap /*[P] or NULL*/,
+                             float *d_pcm, long pcm_stride, int *d_run_samples /*[nruns]*/,
+                             int *d_samples /*[P]*/, int *d_status /*[P]*/, void *stream);
 /* ---- seekable range decoding ----
  * A stream's linear decode is the PCM of all its packets decoded in order from a fresh stream, one packet per call
  * (what vbm_synthesis_runs returns for the whole stream); output position t is its sample t.

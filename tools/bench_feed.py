@@ -12,6 +12,13 @@ Reported: the medians over the passes of the mean scan and fill time per call, G
 on the same bytes demux_ogg on one core (median of 3) and the batch demux (vbm_ogg_demux_scan / _fill) given the same
 streams whole.  Prints one JSON line.
 
+`--resync` runs the same calls through a resync feed (vbm_ogg_feed_create2 with VBM_OGG_FEED_RESYNC; scan, scan_events,
+fill_gaps).  Before anything is timed every call's outputs are compared with the strict feed's; then the same passes are
+timed, and once more on streams that have lost pages (four copies of every signal, every audio page of a copy lost
+with probability 1/100, seeded; `--lose` sets the rate), where the first pass counts the gap marks and the bytes calls
+gave back.  The whole-file
+comparisons are left out.
+
 Per-kernel times: run this under `rocprofv3 --kernel-trace --stats`."""
 import argparse
 import ctypes as C
@@ -60,6 +67,119 @@ def make_streams(v, K, writes, quality):
     return [bytes(r) for r in runs]
 
 
+def cut_calls(runs, S, T):
+    """call t gives slot s piece t of runs[s % K] -> [(data on the device, offsets, end)]"""
+    K = len(runs)
+    piece = [-(-len(r) // T) for r in runs]
+    calls = []
+    for t in range(T):
+        parts = [runs[k][t * piece[k]:(t + 1) * piece[k]] for k in range(K)]
+        off = np.zeros(S + 1, np.int64)
+        np.cumsum([len(parts[s % K]) for s in range(S)], out=off[1:])
+        data = torch.from_numpy(np.frombuffer(b"".join(parts[s % K] for s in range(S)), np.uint8).copy()).cuda()
+        calls.append((data, off, np.full(S, t == T - 1, np.uint8)))
+    return calls
+
+
+def _ends(pages):
+    """packets that end on these pages"""
+    return sum(1 for p in pages for lv in p[27:27 + p[26]] if lv < 255)
+
+
+def lose_pages(runs, rate, seed=1):
+    """every page behind those of the three header packets goes with probability `rate` -> (runs, pages lost)"""
+    rng, out, lost = np.random.default_rng(seed), [], 0
+    for r in runs:
+        pages, at = [], 0
+        while at < len(r):
+            n = 27 + r[at + 26] + sum(r[at + 27:at + 27 + r[at + 26]])
+            pages.append(r[at:at + n])
+            at += n
+        headers = next(k + 1 for k in range(len(pages)) if _ends(pages[:k + 1]) >= 3)
+        keep = [p for k, p in enumerate(pages) if k < headers or rng.random() >= rate]
+        lost += len(pages) - len(keep)
+        out.append(b"".join(keep))
+    return out, lost
+
+
+def timed_passes(lib, check, feed, ids, calls, caps, reps, resync):
+    """the calls reps + 1 times from fresh slots (the first pass warms up), device events around every scan and every
+    fill -> the medians over the passes of the mean scan and fill time per call, in ms"""
+    from vorbis_aotuv_lancer_amd.stream import FEED_EVENTS, FEED_INFO
+    S = len(ids)
+    q = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    meta = torch.zeros(16 + S * (FEED_INFO.itemsize + FEED_EVENTS.itemsize), dtype=torch.uint8, device="cuda")
+    P, B = max(c[0] for c in caps), max(c[1] for c in caps)
+    payload = torch.zeros(max(B, 1), dtype=torch.uint8, device="cuda")
+    offsets = torch.zeros(P + 1, dtype=torch.int64, device="cuda")
+    gp = torch.zeros(max(P, 1), dtype=torch.int64, device="cuda")
+    eos = torch.zeros(max(P, 1), dtype=torch.uint8, device="cuda")
+    gap = torch.zeros(max(P, 1), dtype=torch.uint8, device="cuda")
+    scan_ms, fill_ms = [], []
+    for rep in range(reps + 1):
+        feed.reset(ids)
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in calls]
+        for (data, off, end), e, (cp, cb) in zip(calls, ev, caps):
+            e[0].record()
+            check(lib.vbm_ogg_feed_scan(feed._h, S, ids.ctypes.data, data.data_ptr(), off.ctypes.data, end.ctypes.data,
+                                        meta.data_ptr() + 16, meta.data_ptr(), q), "vbm_ogg_feed_scan")
+            if resync:
+                check(lib.vbm_ogg_feed_scan_events(feed._h, meta.data_ptr() + 16 + S * FEED_INFO.itemsize, q),
+                      "vbm_ogg_feed_scan_events")
+            e[1].record()
+            if resync:
+                check(lib.vbm_ogg_feed_fill_gaps(feed._h, payload.data_ptr(), cb, offsets.data_ptr(), gp.data_ptr(),
+                                                 eos.data_ptr(), gap.data_ptr(), cp, q), "vbm_ogg_feed_fill_gaps")
+            else:
+                check(lib.vbm_ogg_feed_fill(feed._h, payload.data_ptr(), cb, offsets.data_ptr(), gp.data_ptr(), eos.data_ptr(),
+                                            cp, q), "vbm_ogg_feed_fill")
+            e[2].record()
+        torch.cuda.synchronize()
+        st = C.c_int(-1)
+        check(lib.vbm_ogg_feed_status(feed._h, C.byref(st), q), "vbm_ogg_feed_status")
+        assert st.value == 0, st.value
+        if rep:
+            scan_ms.append(statistics.mean(e[0].elapsed_time(e[1]) for e in ev))
+            fill_ms.append(statistics.mean(e[1].elapsed_time(e[2]) for e in ev))
+    return statistics.median(scan_ms), statistics.median(fill_ms)
+
+
+def resync_run(v, lib, check, a, runs, ids, calls, strict_feed):
+    """--resync: the outputs against the strict feed's call by call, then the timed passes on the same bytes and on
+    bytes with lost pages -> the JSON fields"""
+    S, T = a.streams, a.writes
+    kw = dict(max_page_carry=a.max_page_carry, max_packet_bytes=a.max_packet_bytes, header_cap=a.header_cap)
+    feed = v.OggFeed(S, max(int(c[1][-1]) for c in calls), resync=True, **kw)
+    caps = []
+    strict_feed.reset(ids)
+    for data, off, end in calls:
+        r, w = feed.push(ids, data, end=end, offsets=off), strict_feed.push(ids, data, end=end, offsets=off)
+        assert r.info.tobytes() == w.info.tobytes() and not r.left.any() and not r.gap.any().item()
+        assert all(torch.equal(x, y) for x, y in ((r.payload, w.payload), (r.offsets, w.offsets),
+                                                  (r.granulepos, w.granulepos), (r.eos, w.eos)))
+        assert not r.events["skipped_bytes"].any() and not r.events["ignored_pages"].any() and not r.events["link"].any()
+        caps.append((int(r.offsets.numel()) - 1, int(r.payload.numel())))
+    scan, fill = timed_passes(lib, check, feed, ids, calls, caps, a.reps, True)
+    feed.close()
+    # the same streams with lost pages
+    damaged, lost = lose_pages(runs * 4, a.lose)                   # four differently damaged copies of every signal
+    dcalls = cut_calls(damaged, S, T)
+    feed = v.OggFeed(S, max(int(c[1][-1]) for c in dcalls), resync=True, **kw)
+    dcaps, gaps, left, packets = [], 0, 0, 0
+    for data, off, end in dcalls:
+        r = feed.push(ids, data, end=end, offsets=off)
+        assert not r.info["status"].any()
+        gaps, left, packets = gaps + int(r.events["gaps"].sum()), left + int(r.left.sum()), packets + int(r.counts.sum())
+        dcaps.append((int(r.offsets.numel()) - 1, int(r.payload.numel())))
+    dscan, dfill = timed_passes(lib, check, feed, ids, dcalls, dcaps, a.reps, True)
+    feed.close()
+    per_call = sum(int(c[1][-1]) for c in dcalls) / T
+    return {"equal_to_strict": True, "scan_ms": scan, "fill_ms": fill,
+            "lost_pages": {"rate": a.lose, "pages_lost_of_the_damaged_copies": lost, "damaged_copies": len(damaged), "gap_marks": gaps, "bytes_given_back": left,
+                           "packets": packets, "ogg_bytes_per_call": per_call, "scan_ms": dscan, "fill_ms": dfill,
+                           "GB_per_s": per_call / ((dscan + dfill) / 1e3) / 1e9}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=16384)
@@ -70,27 +190,20 @@ def main():
     ap.add_argument("--max-page-carry", type=int, default=8192)
     ap.add_argument("--max-packet-bytes", type=int, default=8192)
     ap.add_argument("--header-cap", type=int, default=8192)
+    ap.add_argument("--resync", action="store_true", help="measure a resync feed against the strict feed of the same run")
+    ap.add_argument("--lose", type=float, default=0.01, help="--resync: the share of pages the second figure loses")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_feed.py needs a GPU: there is nothing to measure without one")
 
     import vorbis_aotuv_lancer_amd as v
     from vorbis_aotuv_lancer_amd._lib import lib, check
-    from vorbis_aotuv_lancer_amd.stream import FEED_INFO
     from bench_demux import device_demux
 
     S, K, T = a.streams, a.signals, a.writes
     runs = make_streams(v, K, T, a.quality)
-    piece = [-(-len(r) // T) for r in runs]
     ids = np.arange(S, dtype=np.int32)
-    calls = []
-    for t in range(T):
-        parts = [runs[k][t * piece[k]:(t + 1) * piece[k]] for k in range(K)]
-        off = np.zeros(S + 1, np.int64)
-        np.cumsum([len(parts[s % K]) for s in range(S)], out=off[1:])
-        data = torch.from_numpy(np.frombuffer(b"".join(parts[s % K] for s in range(S)), np.uint8).copy()).cuda()
-        end = np.full(S, t == T - 1, np.uint8)
-        calls.append((data, off, end))
+    calls = cut_calls(runs, S, T)
     call_bytes = [int(c[1][-1]) for c in calls]
     total_bytes = sum(call_bytes)
 
@@ -121,34 +234,19 @@ def main():
     same = same and sum(packets_per_call) == sum(len(want[s % K][3]) for s in range(S))
 
     # the timed passes: raw calls, outputs of the sizes the first pass found, device events around every scan and fill
-    q = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    meta = torch.zeros(16 + S * FEED_INFO.itemsize, dtype=torch.uint8, device="cuda")
-    P, B = max(c[0] for c in caps), max(c[1] for c in caps)
-    payload = torch.zeros(max(B, 1), dtype=torch.uint8, device="cuda")
-    offsets = torch.zeros(P + 1, dtype=torch.int64, device="cuda")
-    gp = torch.zeros(max(P, 1), dtype=torch.int64, device="cuda")
-    eos = torch.zeros(max(P, 1), dtype=torch.uint8, device="cuda")
-    scan_ms, fill_ms = [], []
-    for rep in range(a.reps + 1):
-        feed.reset(ids)
-        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in calls]
-        for (data, off, end), e, (cp, cb) in zip(calls, ev, caps):
-            e[0].record()
-            check(lib.vbm_ogg_feed_scan(feed._h, S, ids.ctypes.data, data.data_ptr(), off.ctypes.data, end.ctypes.data,
-                                        meta.data_ptr() + 16, meta.data_ptr(), q), "vbm_ogg_feed_scan")
-            e[1].record()
-            check(lib.vbm_ogg_feed_fill(feed._h, payload.data_ptr(), cb, offsets.data_ptr(), gp.data_ptr(), eos.data_ptr(), cp,
-                                        q), "vbm_ogg_feed_fill")
-            e[2].record()
-        torch.cuda.synchronize()
-        st = C.c_int(-1)
-        check(lib.vbm_ogg_feed_status(feed._h, C.byref(st), q), "vbm_ogg_feed_status")
-        assert st.value == 0, st.value
-        if rep:
-            scan_ms.append(statistics.mean(e[0].elapsed_time(e[1]) for e in ev))
-            fill_ms.append(statistics.mean(e[1].elapsed_time(e[2]) for e in ev))
+    ms_scan, ms_fill = timed_passes(lib, check, feed, ids, calls, caps, a.reps, False)
+    per_call = total_bytes / T
+    if a.resync:
+        res = resync_run(v, lib, check, a, runs, ids, calls, feed)
+        feed.close()
+        res["GB_per_s"] = per_call / ((res["scan_ms"] + res["fill_ms"]) / 1e3) / 1e9
+        print(json.dumps({
+            "metric": "ogg_feed_resync", "streams": S, "signals": K, "quality": a.quality, "calls": T, "reps": a.reps,
+            "ogg_bytes_per_call": per_call, "packets_per_call": statistics.mean(packets_per_call), "same_outputs": bool(same),
+            "strict": {"scan_ms": ms_scan, "fill_ms": ms_fill, "GB_per_s": per_call / ((ms_scan + ms_fill) / 1e3) / 1e9},
+            "resync": res, "scan_ratio": res["scan_ms"] / ms_scan}), flush=True)
+        return
     feed.close()
-    ms_scan, ms_fill = statistics.median(scan_ms), statistics.median(fill_ms)
 
     # the same bytes as whole files: demux_ogg on one core, and the batch demux on the device
     files = [runs[s % K] for s in range(S)]
@@ -161,7 +259,6 @@ def main():
     host_s = statistics.median(host)
     b_scan, b_fill, _ = device_demux(v, files, a.reps)
 
-    per_call = total_bytes / T
     state = 72 + a.max_page_carry + a.max_packet_bytes + a.header_cap
     print(json.dumps({
         "metric": "ogg_feed", "streams": S, "signals": K, "quality": a.quality, "calls": T, "reps": a.reps,

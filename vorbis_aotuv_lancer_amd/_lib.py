@@ -176,6 +176,18 @@ SIGNATURES = {
                                          C.c_void_p]),
     "vbm_host_ogg_feed_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_longlong]),
+    "vbm_ogg_feed_create2": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_uint]),
+    "vbm_host_ogg_feed_create2": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                            C.c_uint]),
+    "vbm_ogg_feed_scan_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vbm_host_ogg_feed_scan_events": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vbm_ogg_feed_fill_gaps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_longlong, C.c_void_p]),
+    "vbm_host_ogg_feed_fill_gaps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_longlong]),
+    "vbm_synthesis_runs_gaps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vbm_decoder_fetch": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_char),
                                     C.c_void_p]),
     "vbm_decode_index": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,

@@ -321,6 +321,16 @@ extern "C" int vbm_synthesis_runs(vbm_decoder *d, int nruns, const int *stream_i
                                   const long long *d_granulepos, const uint8_t *d_eos, float *d_pcm, long pcm_stride,
                                   int *d_run_samples, int *d_samples, int *d_status, void *stream)
 {
+    return vbm_synthesis_runs_gaps(d, nruns, stream_ids, run_packets, d_data, d_offsets, data_bytes, d_granulepos, d_eos,
+                                   nullptr, d_pcm, pcm_stride, d_run_samples, d_samples, d_status, stream);
+}
+
+extern "C" int vbm_synthesis_runs_gaps(vbm_decoder *d, int nruns, const int *stream_ids, const int *run_packets,
+                                       const uint8_t *d_data, const long long *d_offsets, long long data_bytes,
+                                       const long long *d_granulepos, const uint8_t *d_eos, const uint8_t *d_gap,
+                                       float *d_pcm, long pcm_stride, int *d_run_samples, int *d_samples, int *d_status,
+                                       void *stream)
+{
     if (!d || nruns < 0 || (nruns > 0 && (!stream_ids || !run_packets)) || data_bytes < 0 ||
         (data_bytes > 0 && !d_data) || !d_offsets || !d_run_samples)
         return VBM_EINVAL;
@@ -356,7 +366,7 @@ extern "C" int vbm_synthesis_runs(vbm_decoder *d, int nruns, const int *stream_i
     rc = enqueue_front(d, L, q, "hipMemsetAsync(decode runs)",
                        [&] { return vbmd_launch_unpack_csr(L, d_data, d_offsets, data_bytes, d_status, q); });
     if (rc) return rc;
-    if (vbmd_launch_runs(L, nruns, d->d_runtab, d_granulepos, d_eos, d->d_plan, d->d_run_last, d_pcm, pcm_stride,
+    if (vbmd_launch_runs(L, nruns, d->d_runtab, d_granulepos, d_eos, d_gap, d->d_plan, d->d_run_last, d_pcm, pcm_stride,
                          d_run_samples, d_samples, q))
         return VBM_EHIP;
     if (nsb > 0) d->last_nsb = nsb;

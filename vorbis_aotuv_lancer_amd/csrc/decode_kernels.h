@@ -29,12 +29,12 @@ int vbmd_launch_imdct(const vbmd_launch &L, int W, int N, const float *trig, hip
 int vbmd_launch_overlap(const vbmd_launch &L, const int *ids, const long long *granulepos, const uint8_t *eos,
                         float *pcm, int *samples, hipStream_t q);
 // runs (vbm_synthesis_runs): CSR unpack; then plan, overlap-add into the runs' PCM and the tail commit.  runtab:
-// stream ids [nruns] and run starts [nruns + 1]; plan: 6 ints per row; run_last: [nruns]
+// stream ids [nruns] and run starts [nruns + 1]; plan: 6 ints per row; run_last: [nruns]; gap: null, or a mark per row
 int vbmd_launch_unpack_csr(const vbmd_launch &L, const uint8_t *data, const long long *offsets, long long data_bytes,
                            int *status_out, hipStream_t q);
 int vbmd_launch_runs(const vbmd_launch &L, int nruns, const int *runtab, const long long *granulepos,
-                     const uint8_t *eos, int *plan, int *run_last, float *pcm, long pcm_stride, int *run_samples,
-                     int *samples, hipStream_t q);
+                     const uint8_t *eos, const uint8_t *gap, int *plan, int *run_last, float *pcm, long pcm_stride,
+                     int *run_samples, int *samples, hipStream_t q);
 // ranges (vbm_synthesis_ranges): rtab is the piece table (k_range_rows in decode_kernels.hip); rows: [nsb] store
 // packet of each row; pk_begin / pk_end / out_start: the store's index; runtab: one readable int per output row
 int vbmd_launch_unpack_rows(const vbmd_launch &L, int npieces, const int *rtab, int *rows, const uint8_t *data,

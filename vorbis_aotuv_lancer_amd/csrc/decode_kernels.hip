@@ -426,7 +426,8 @@ template <int HS>
 __global__ __launch_bounds__(64)
 void k_run_plan(const vbmd_setup *__restrict__ s, int nruns, const int *__restrict__ runtab,
                 const int *__restrict__ status, const int *__restrict__ info,
-                const long long *__restrict__ granulepos, const uint8_t *__restrict__ eos, int *__restrict__ prevW,
+                const long long *__restrict__ granulepos, const uint8_t *__restrict__ eos,
+                const uint8_t *__restrict__ gap, int *__restrict__ prevW,
                 long long *__restrict__ st_gp, long long *__restrict__ st_sc, int *__restrict__ plan,
                 int *__restrict__ samples, int *__restrict__ run_samples, int *__restrict__ run_last)
 {
@@ -437,6 +438,7 @@ void k_run_plan(const vbmd_setup *__restrict__ s, int nruns, const int *__restri
     long long sc = st_sc[sid], gp = st_gp[sid];
     for (int k = k0; k < k1; k++) {
         int *pl = plan + 6 * (long)k;
+        if (gap && gap[k]) sc = gp = -1;            // packets were lost: lib/block.c:911-915; an error row hands it on
         if (status[k] != 0) {
             samples[k] = 0;
             continue;
@@ -705,12 +707,12 @@ int vbmd_launch_unpack_csr(const vbmd_launch &L, const uint8_t *data, const long
 }
 
 int vbmd_launch_runs(const vbmd_launch &L, int nruns, const int *runtab, const long long *granulepos,
-                     const uint8_t *eos, int *plan, int *run_last, float *pcm, long pcm_stride, int *run_samples,
-                     int *samples, hipStream_t q)
+                     const uint8_t *eos, const uint8_t *gap, int *plan, int *run_last, float *pcm, long pcm_stride,
+                     int *run_samples, int *samples, hipStream_t q)
 {
     if (nruns <= 0) return 0;
     hipLaunchKernelGGL(L.hs ? k_run_plan<1> : k_run_plan<0>, dim3((nruns + 63) / 64), dim3(64), 0, q, L.s, nruns, runtab, L.status, L.info,
-                       granulepos, eos, L.prevW, L.gp, L.sc, plan, samples, run_samples, run_last);
+                       granulepos, eos, gap, L.prevW, L.gp, L.sc, plan, samples, run_samples, run_last);
     if (last_err()) return -2;
     if (L.nsb > 0) {
         hipLaunchKernelGGL(L.hs ? k_overlap_runs<1> : k_overlap_runs<0>, dim3(L.nsb), dim3(256), 0, q, L.s, runtab, L.status,

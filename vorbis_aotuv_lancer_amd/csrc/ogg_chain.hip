@@ -21,20 +21,6 @@ constexpr int kEmitBlocks = 2048;  // most blocks k_chain_emit is launched with
 
 // ---- kernels ---------------------------------------------------------------------------------------------------
 
-// up to four bytes at p, the first `avail` of which lie in front of the file's end (avail may be negative) -> one
-// word, the first byte lowest; what is not there reads as 0
-__device__ __forceinline__ uint32_t chain_load4(const uint8_t *p, long long avail)
-{
-    uint32_t w = 0;
-    if (avail >= 4) {
-        __builtin_memcpy(&w, p, 4);
-    } else {
-        for (int j = 0; j < 3; j++)
-            if (j < avail) w |= (uint32_t)p[j] << (8 * j);
-    }
-    return w;
-}
-
 __global__ void __launch_bounds__(64) k_chain_walk(const uint8_t *data, const long long *off, long long *starts,
                                                    long long *nlinks)
 {
@@ -49,7 +35,7 @@ __global__ void __launch_bounds__(64) k_chain_walk(const uint8_t *data, const lo
         // the round trip: header byte `lane`, and lacing values 4 * lane .. 4 * lane + 3 if the file goes on that far
         // (past nseg they are body bytes of this file, and are masked below)
         const int hb = lane < 27 ? h[lane] : 0;
-        const uint32_t lw = chain_load4(h + 27 + 4 * lane, left - 27 - 4 * lane);
+        const uint32_t lw = dmx_load4(h + 27 + 4 * lane, left - 27 - 4 * lane);
         const uint32_t capture = (uint32_t)__builtin_amdgcn_readlane(hb, 0) | ((uint32_t)__builtin_amdgcn_readlane(hb, 1) << 8) |
                                  ((uint32_t)__builtin_amdgcn_readlane(hb, 2) << 16) |
                                  ((uint32_t)__builtin_amdgcn_readlane(hb, 3) << 24);

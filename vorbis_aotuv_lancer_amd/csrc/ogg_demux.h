@@ -59,6 +59,23 @@ VBMX_HD void oggdmx_walk_begin(OggDmxWalk &w, long long begin, long long end)
     w.partial = 0;
 }
 
+// Segments [from, nseg) of the page at h laid onto the counts: a lacing value below 255 ends a packet.
+VBMX_HD void oggdmx_lacing(const uint8_t *h, int from, int nseg, OggDmxCounts &c, int &partial)
+{
+    for (int i = from; i < nseg; i++) {
+        const int lv = h[27 + i];
+        c.body += lv;
+        partial = lv == 255;
+        if (lv < 255) {
+            if (c.packets == 0) c.h0 = c.body;
+            if (c.packets == 1) c.h1 = c.body;
+            if (c.packets == 2) c.h2 = c.body;
+            c.packets++;
+            c.last_end = c.body;
+        }
+    }
+}
+
 // The next page of the file, and the only reader of a page header:
 //    1  the page is taken: its record is in pg, and w has moved past it (by at least 27 bytes)
 //    0  w.pos has reached w.end
@@ -83,18 +100,7 @@ VBMX_HD int oggdmx_walk_step(const uint8_t *data, OggDmxWalk &w, OggDmxPage &pg)
     if (left - 27 < nseg) return -2;                               // truncated lacing table
     OggDmxCounts c = w.cnt;
     int partial = w.partial;
-    for (int i = 0; i < nseg; i++) {
-        const int lv = h[27 + i];
-        c.body += lv;
-        partial = lv == 255;
-        if (lv < 255) {
-            if (c.packets == 0) c.h0 = c.body;
-            if (c.packets == 1) c.h1 = c.body;
-            if (c.packets == 2) c.h2 = c.body;
-            c.packets++;
-            c.last_end = c.body;
-        }
-    }
+    oggdmx_lacing(h, 0, nseg, c, partial);
     const long long body_len = c.body - w.cnt.body;
     if (left - 27 - nseg < body_len) return -2;                    // truncated body
     pg.at = w.pos;
@@ -320,6 +326,20 @@ __device__ __forceinline__ void block_scan_array(int n, const long long *v, long
         }
     }
     if (threadIdx.x == 0) *total = carry;
+}
+
+// up to four bytes at p, the first `avail` of which lie in front of the run's end (avail may be negative) -> one
+// word, the first byte lowest; what is not there reads as 0
+__device__ __forceinline__ uint32_t dmx_load4(const uint8_t *p, long long avail)
+{
+    uint32_t w = 0;
+    if (avail >= 4) {
+        __builtin_memcpy(&w, p, 4);
+    } else {
+        for (int j = 0; j < 3; j++)
+            if (j < avail) w |= (uint32_t)p[j] << (8 * j);
+    }
+    return w;
 }
 
 // The CRC of the page at h, len bytes, by the 64 lanes of a wavefront: lane l takes bytes [l * chunk, (l + 1) * chunk),

@@ -17,6 +17,16 @@
 // list starts at chunk_offset[i] - chunk_offset[0] + i * max_page_carry), and the page records.  A run whose tail is
 // an incomplete page holds at most chunk / 27 + 1 pages, so stream i's records start at slot
 // (chunk_offset[i] - chunk_offset[0]) / 27 + i and there are max_call_bytes / 27 + max_streams + 1 of them.
+//
+// Resync mode (oggfeed_rs_walk; the rules: include/vorbis_mi355x.h, "Resync mode") keeps the same numbering and the same
+// page records, so gather, fill and commit are those of the strict mode.  A link start numbers the new link's body bytes
+// and packets from 0 again.  A discontinuity page rewinds the numbering to last_end, which empties the open store (an
+// open packet's bytes lie at their distance from last_end), and a continued discontinuity page folds its front skip
+// into its record: with `skip` leading body bytes that belong to no packet, body_before is `skip` below the rewound
+// count, so the skipped bytes get numbers below S (no payload), the first kept byte gets number S, and the lacing value
+// that ends the skipped part counts as the end of the packet in front of the call's first (pkt_before one less), which
+// rewrites that packet's end offset, the call's first CSR entry, with the value it has.  Such a record is marked
+// (OggDmxPage::pad), because its numbers below S are not header bytes.  Per slot 16 B more (OggFeedLink).
 #pragma once
 #include <limits.h>
 
@@ -47,10 +57,39 @@ struct OggFeedCall {             // one listed stream of a scan, for fill and co
     int slot, pad;
 };
 
+struct OggFeedLink {             // resync mode: a slot's link between calls; all zero = no link yet
+    int links;                   // link starts seen: the current link is links - 1 (reported as 0 before the first)
+    int bad;                     // the link lost a page while its headers were open
+    int eos;                     // the link has delivered its end-of-stream page
+    int gap;                     // the next packet completed carries a gap mark
+};
+
+struct OggFeedRsCall {           // one listed stream of a resync scan, beside its OggFeedCall
+    OggFeedLink next;            // the slot's link once the call is committed
+    vbm_ogg_feed_events ev;
+};
+
+struct OggFeedHead {             // a whole page candidate
+    int flags, nseg, body;       // header type, segments, body bytes (the sum of the lacing values)
+    uint32_t serial, seq;
+};
+
 VBMX_HD int oggfeed_tail_in(const OggFeedState &st, const OggFeedCaps &caps)
 {
     if (st.status || st.done) return 0;
     return st.tail < 0 ? 0 : (st.tail > caps.max_page_carry ? caps.max_page_carry : st.tail);
+}
+
+// a call that takes nothing
+VBMX_HD void oggfeed_call_begin(const OggFeedState &st, long long at, int slot, OggFeedCall &c)
+{
+    c.next = st;
+    c.at = c.pos_end = at;
+    c.S = c.E = 0;
+    c.packets = c.payload_bytes = c.packet_base = c.payload_base = 0;
+    c.pkt_shift = (st.cnt.packets > 3 ? st.cnt.packets : 3) - 3;
+    c.npages = c.open_in = 0;
+    c.slot = slot, c.pad = 0;
 }
 
 // One stream, one call.  The run is work[at, run_end): whole pages are taken from it in order, at most `limit` of them,
@@ -61,13 +100,7 @@ VBMX_HD void oggfeed_walk(const uint8_t *work, long long at, long long run_end, 
                           const OggFeedCaps &caps, int end_flag, int limit, bool bad_at_limit, OggDmxPage *pages,
                           long long room, int slot, OggFeedCall &c)
 {
-    c.next = st;
-    c.at = c.pos_end = at;
-    c.S = c.E = 0;
-    c.packets = c.payload_bytes = c.packet_base = c.payload_base = 0;
-    c.pkt_shift = (st.cnt.packets > 3 ? st.cnt.packets : 3) - 3;
-    c.npages = c.open_in = 0;
-    c.slot = slot, c.pad = 0;
+    oggfeed_call_begin(st, at, slot, c);
     if (st.status || st.done) return;                              // bytes for a failed or ended stream are ignored
     OggDmxWalk w;
     w.pos = at, w.end = run_end;
@@ -159,9 +192,211 @@ VBMX_HD void oggfeed_ctx_keep(const uint8_t *work, const OggDmxPage &pg, const O
     const bool audio = c.next.cnt.packets >= 3;
     const long long b = pg.body_before + hdr.body_len;
     hdr.H = hdr.E = audio ? c.next.cnt.h2 : b;                     // [.., H) -> header store; no payload part
+    if (pg.pad) hdr.H = hdr.E = pg.body_before;                    // a front skip: its numbers are no header bytes
     hdr.header_base = (long long)c.slot * caps.header_cap;
     open = hdr;
     open.H = audio ? c.next.cnt.last_end : b;                      // [H, ..) -> open store
     open.E = b;
     open.payload_base = (long long)c.slot * caps.max_packet_bytes;
+}
+
+// ---- resync mode ---------------------------------------------------------------------------------------------------
+VBMX_HD bool oggfeed_rs_capture(uint32_t w) { return w == 0x5367674fu; }   // "OggS", the first byte lowest
+
+// One stream, one call, by the six rules of the resync mode.  The run is work[at, run_end), its first tail_in bytes the
+// carried tail.  What looks at many bytes comes from `ops`, serial on the host and by the lanes of a wavefront on the
+// device (there every argument and result is uniform over the wavefront, and so is every exit of the loop):
+//   find(work, pos, end)   the first p in [pos, end - 4] with the capture pattern at work[p, p + 4), or -1
+//   head(h, left, hd)      the candidate at h with `left` bytes in front of the run's end: 1 whole (hd filled), 0 no
+//                          header (version), -2 the header, the lacing table or the body is not all here
+//   crc(h, len)            the page carries its own checksum
+// No byte is read before it is known to lie in front of run_end; every turn of the loop moves pos on by one byte at least
+// or leaves it.  Fills `c` but for its bases, and `r`.
+template <class Ops>
+VBMX_HD void oggfeed_rs_walk(const Ops &ops, const uint8_t *work, long long at, long long run_end, int tail_in,
+                             const OggFeedState &st, const OggFeedLink &lk0, const OggFeedCaps &caps, int end_flag,
+                             OggDmxPage *pages, long long room, int slot, OggFeedCall &c, OggFeedRsCall &r)
+{
+    oggfeed_call_begin(st, at, slot, c);
+    r.next = lk0;
+    r.ev.link = lk0.links > 0 ? lk0.links - 1 : 0;
+    r.ev.link_started = r.ev.gaps = 0;
+    r.ev.link_bad = lk0.bad;
+    r.ev.skipped_bytes = r.ev.ignored_pages = r.ev.left = 0;
+    if (st.status || st.done) return;                              // bytes for a failed or ended stream are ignored
+    OggDmxCounts cnt = st.cnt, base = st.cnt;                      // base: the counts the call's payload starts from
+    OggFeedLink lk = lk0;
+    int partial = st.partial, n = 0, status = 0;
+    bool took = false, stopped = false, started = false;
+    long long pos = at, skipped = 0, ignored = 0;
+    // The page records of a call are sized for its chunk (chunk / 27 + 1 per slot).  The carried tail may hold whole
+    // pages too: behind a candidate that claimed more bytes than it had (a truncated page, a damaged lacing table)
+    // everything is carried until the claim is filled, and when its CRC then fails the walk meets them all at once.  So
+    // a call takes chunk / 27 + 1 pages at most, one at least, and the next ends the walk as any stop of rule 5 does.
+    const long long fit = (run_end - at - tail_in) / 27 + 1, most = fit < room ? fit : room;
+    while (run_end - pos >= 4) {
+        // 1 finding a page
+        const long long p = ops.find(work, pos, run_end);
+        if (p < 0) {                                               // the last three bytes may begin a capture pattern
+            skipped += run_end - 3 - pos;
+            pos = run_end - 3;
+            break;
+        }
+        skipped += p - pos;
+        pos = p;
+        const uint8_t *h = work + pos;
+        OggFeedHead hd = {};
+        const int whole = ops.head(h, run_end - pos, hd);
+        if (whole == -2) break;                                    // carried
+        const int len = 27 + hd.nseg + hd.body;                    // (of a whole candidate)
+        if (whole == 0 || !ops.crc(h, len)) {
+            skipped++;
+            pos++;
+            continue;
+        }
+        // 2 whose page
+        const bool start = (hd.flags & 2) != 0, cont = (hd.flags & 1) != 0;
+        if (!start && (lk.links == 0 || lk.bad || lk.eos || hd.serial != cnt.serial)) {
+            ignored++;
+            pos += len;
+            continue;
+        }
+        const bool disc = start ? cont : (hd.seq != cnt.seq || cont != (partial != 0));
+        if (((start || disc) && took) || n >= most) {              // 5 only as the first page the call takes; records
+            stopped = true;
+            break;
+        }
+        OggDmxCounts pre = cnt;
+        OggFeedLink nl = lk;
+        int np = partial, from = 0, skip = 0, skip_end = 0;
+        if (start) {                                               // 4 link start
+            pre = OggDmxCounts{};
+            nl.links++;
+            nl.bad = nl.eos = 0;
+            nl.gap = nl.links > 1;
+            np = 0;
+        }
+        if (disc) {                                                // 3 discontinuity
+            if (pre.packets < 3) {                                 // headers open: the link is bad, the page is used up
+                nl.bad = 1;
+                cnt = pre, lk = nl, partial = 0;
+                started = started || start;
+                if (start) base = pre;
+                took = true;
+                pos += len;
+                continue;
+            }
+            pre.body = pre.last_end;                               // the open packet is dropped
+            np = 0;
+            nl.gap = 1;
+            if (cont)
+                while (from < hd.nseg && !skip_end) {
+                    const int lv = h[27 + from++];
+                    skip += lv;
+                    skip_end = lv < 255;
+                }
+        }
+        OggDmxCounts nc = pre;
+        oggdmx_lacing(h, from, hd.nseg, nc, np);
+        // the stores the page's body would go to, judged page by page as in the strict mode
+        const long long hdr = pre.packets >= 3 ? 0 : (nc.packets >= 3 ? nc.h2 : nc.body);
+        const long long open = nc.packets >= 3 ? nc.body - nc.last_end : 0;
+        if (hdr > caps.header_cap || open > caps.max_packet_bytes) {
+            status = VBM_OGG_FEED_EBIG;
+            break;
+        }
+        OggDmxPage pg;
+        pg.at = pos;
+        pg.body_before = pre.body - skip;
+        pg.pkt_before = pre.packets - skip_end;
+        pg.len = len;
+        pg.pad = skip > 0 || skip_end;
+        pages[n++] = pg;
+        if (start || disc) base = pre;
+        started = started || start;
+        cnt = nc;
+        cnt.serial = hd.serial;
+        cnt.seq = hd.seq + 1;
+        partial = np;
+        lk = nl;
+        if (hd.flags & 4) lk.eos = 1;
+        took = true;
+        pos += len;
+    }
+    // 5 stops: what the walk did not visit stays the tail (carried bytes) or is reported as left (bytes of the chunk)
+    const long long chunk_at = at + tail_in;
+    long long tail = run_end - pos, left = 0;
+    if (stopped) {
+        tail = pos < chunk_at ? chunk_at - pos : 0;
+        left = run_end - (pos < chunk_at ? chunk_at : pos);
+    }
+    if (status) tail = left = 0;
+    int done = 0;
+    if (!status && end_flag && !stopped) {                         // 6 a partial page is dropped; not at a stop: left > 0,
+                                                                   // or whole pages of the tail are still unvisited
+        skipped += tail;
+        tail = 0;
+        done = 1;
+    } else if (!status && tail > caps.max_page_carry) {
+        status = VBM_OGG_FEED_EBIG;
+        tail = 0;
+    }
+    c.npages = n;
+    c.pos_end = pos;
+    c.pkt_shift = (base.packets > 3 ? base.packets : 3) - 3;
+    if (cnt.packets >= 3) {
+        c.S = base.packets >= 3 ? base.last_end : cnt.h2;
+        c.E = cnt.last_end;
+        c.packets = cnt.packets - 3 - c.pkt_shift;
+        c.payload_bytes = c.E - c.S;
+        if (base.packets >= 3 && c.packets > 0) c.open_in = (int)(base.body - base.last_end);
+    }
+    if (c.packets > 0 && lk.gap) {                                 // the call's first packet carries the mark
+        r.ev.gaps = 1;
+        lk.gap = 0;
+    }
+    c.next.cnt = cnt, c.next.partial = partial;
+    c.next.status = status;
+    c.next.tail = (int)tail;
+    c.next.done = done;
+    r.next = lk;
+    r.ev.link = lk.links > 0 ? lk.links - 1 : 0;
+    r.ev.link_started = started;
+    r.ev.link_bad = lk.bad;
+    r.ev.skipped_bytes = skipped;
+    r.ev.ignored_pages = ignored;
+    r.ev.left = left;
+}
+
+// the host's three: byte after byte
+struct OggFeedSerialOps {
+    const uint32_t *T;
+    const OggMuxPow *pw;
+
+    long long find(const uint8_t *work, long long pos, long long end) const
+    {
+        for (long long p = pos; p + 4 <= end; p++)
+            if (oggfeed_rs_capture(oggdmx_rd32(work + p))) return p;
+        return -1;
+    }
+
+    int head(const uint8_t *h, long long left, OggFeedHead &hd) const
+    {
+        if (left >= 5 && h[4] != 0) return 0;
+        if (left < 27) return -2;
+        hd.flags = h[5], hd.nseg = h[26];
+        hd.serial = oggdmx_rd32(h + 14), hd.seq = oggdmx_rd32(h + 18);
+        if (left - 27 < hd.nseg) return -2;
+        hd.body = 0;
+        for (int i = 0; i < hd.nseg; i++) hd.body += h[27 + i];
+        return left - 27 - hd.nseg < hd.body ? -2 : 1;
+    }
+
+    bool crc(const uint8_t *h, int len) const { return oggdmx_page_crc_ok(T, *pw, h, len); }
+};
+
+VBMX_HD void oggfeed_rs_info(const OggFeedCall &c, const OggFeedRsCall &r, vbm_ogg_feed_info &fi)
+{
+    oggfeed_info(c, fi);
+    fi.serialno = r.next.links ? c.next.cnt.serial : 0u;           // a sequence number may be any value here
 }

@@ -18,6 +18,13 @@
 //                             one wavefront per stream: the unconsumed tail and the new state
 //          k_feed_mark        the scan is committed
 //   reset: k_feed_reset       one lane per listed stream: the slot's state back to all zero
+// A resync feed (vbm_ogg_feed_create2 with VBM_OGG_FEED_RESYNC) runs one kernel in the place of walk, crc and settle:
+//          k_feed_resync_walk one wavefront per listed stream (oggfeed_rs_walk with FeedWaveOps): the capture search
+//                             tests one 4-byte window per lane over 64 positions and a ballot finds the first hit; per
+//                             candidate every lane loads one header byte and four lacing bytes, a wave reduction gives
+//                             the body length, and the CRC is dmx_wave_page_crc at once, because it decides where the
+//                             walk goes next
+//          k_feed_events      one lane per listed stream: its event struct
 // Nothing of a slot changes before k_feed_commit, which runs only after a fill that wrote its outputs.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -46,6 +53,8 @@ struct FeedMem {                   // the feed's state and workspace
     long long *npages, *page_base, *totals;
     long long *count, *base;       // [2 * max_streams]: packets and payload bytes of the call per listed stream, their sums
     int *bad, *status, *committed;
+    OggFeedLink *link;             // resync feeds only (else null): [max_streams] the slots' links,
+    OggFeedRsCall *rs;             // [max_streams] the listed streams of the scan beside `call`
 };
 
 VBMX_HD long long feed_at(const long long *off, int i, const OggFeedCaps &caps)
@@ -98,6 +107,95 @@ __global__ void __launch_bounds__(64) k_feed_walk(int n, FeedArgs a, FeedMem m, 
     m.npages[i] = c.npages;
     m.count[2 * i] = c.packets, m.count[2 * i + 1] = c.payload_bytes;
     m.bad[i] = INT_MAX;
+}
+
+// oggfeed_rs_walk's three by the 64 lanes of a wavefront; every result is the same in every lane
+struct FeedWaveOps {
+    const uint32_t *T;             // the CRC table in LDS
+    const OggMuxPow *pw;
+    int lane;
+
+    __device__ long long find(const uint8_t *work, long long pos, long long end) const
+    {
+        for (; pos + 4 <= end; pos += 64) {
+            const long long p = pos + lane;
+            const bool hit = p + 4 <= end && oggfeed_rs_capture(dmx_load4(work + p, 4));
+            const unsigned long long hits = __ballot(hit);
+            if (hits) return pos + __builtin_ctzll(hits);
+        }
+        return -1;
+    }
+
+    __device__ int head(const uint8_t *h, long long left, OggFeedHead &hd) const
+    {
+        // the round trip: header byte `lane`, and lacing values 4 * lane .. 4 * lane + 3 if the run goes on that far
+        // (past nseg they are body bytes of this run, and are masked below)
+        const int hb = lane < 27 && lane < left ? h[lane] : 0;
+        const uint32_t lw = dmx_load4(h + 27 + 4 * lane, left - 27 - 4 * lane);
+        if (left >= 5 && __builtin_amdgcn_readlane(hb, 4) != 0) return 0;
+        if (left < 27) return -2;
+        hd.flags = __builtin_amdgcn_readlane(hb, 5), hd.nseg = __builtin_amdgcn_readlane(hb, 26);
+        hd.serial = field(hb, 14), hd.seq = field(hb, 18);
+        if (left - 27 < hd.nseg) return -2;
+        const int mine = min(4, max(0, hd.nseg - 4 * lane));       // how many of my four are lacing values
+        const uint32_t v = mine == 4 ? lw : lw & ((1u << (8 * mine)) - 1u);
+        int body = (int)((v & 0xff) + ((v >> 8) & 0xff) + ((v >> 16) & 0xff) + (v >> 24));
+        for (int m = 32; m >= 1; m >>= 1) body += __shfl_xor(body, m, 64);
+        hd.body = __builtin_amdgcn_readfirstlane(body);
+        return left - 27 - hd.nseg < hd.body ? -2 : 1;
+    }
+
+    __device__ bool crc(const uint8_t *h, int len) const
+    {
+        return __builtin_amdgcn_readfirstlane((int)dmx_wave_page_crc(T, *pw, h, len, lane)) != 0;
+    }
+
+    // header bytes at .. at + 3, each in its lane, as one word
+    static __device__ uint32_t field(int hb, int at)
+    {
+        return (uint32_t)__builtin_amdgcn_readlane(hb, at) | ((uint32_t)__builtin_amdgcn_readlane(hb, at + 1) << 8) |
+               ((uint32_t)__builtin_amdgcn_readlane(hb, at + 2) << 16) | ((uint32_t)__builtin_amdgcn_readlane(hb, at + 3) << 24);
+    }
+};
+
+// stream i of the list by the rules of the resync mode
+template <class Ops>
+VBMX_HD void feed_rs_walk_one(const Ops &ops, const FeedArgs &a, const FeedMem &m, const OggFeedCaps &caps, int i,
+                              OggFeedCall &c, OggFeedRsCall &r)
+{
+    const int slot = a.ids[i];
+    const OggFeedState st = m.state[slot];
+    const long long at = feed_at(a.off, i, caps), rec = feed_first_rec(a.off, i);
+    const int tail_in = oggfeed_tail_in(st, caps);
+    oggfeed_rs_walk(ops, m.work, at, at + tail_in + (a.off[i + 1] - a.off[i]), tail_in, st, m.link[slot], caps, a.end[i],
+                    m.pages + rec, feed_first_rec(a.off, i + 1) - rec, slot, c, r);
+}
+
+__global__ void __launch_bounds__(256) k_feed_resync_walk(int n, OggMuxPow pw, FeedArgs a, FeedMem m, OggFeedCaps caps)
+{
+    __shared__ uint32_t T[256];
+    T[threadIdx.x] = oggmux_crc_entry(threadIdx.x);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, nwaves = gridDim.x * 4;
+    const FeedWaveOps ops = {T, &pw, lane};
+    // the wavefront's number, as a scalar: the slot's state and every count of the walk stay in scalar registers
+    for (int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < n; i += nwaves) {
+        OggFeedCall c;
+        OggFeedRsCall r;
+        feed_rs_walk_one(ops, a, m, caps, i, c, r);
+        if (lane == 0) {
+            m.call[i] = c;
+            m.rs[i] = r;
+            m.npages[i] = c.npages;
+            m.count[2 * i] = c.packets, m.count[2 * i + 1] = c.payload_bytes;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_feed_events(int n, const OggFeedRsCall *rs, vbm_ogg_feed_events *out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = rs[i].ev;
 }
 
 __global__ void __launch_bounds__(256) k_feed_scan_pages(int n, const long long *npages, long long *page_base)
@@ -153,12 +251,14 @@ __global__ void __launch_bounds__(256) k_feed_info(int n, FeedMem m, vbm_ogg_fee
     m.call[i].packet_base = m.base[2 * i];
     m.call[i].payload_base = m.base[2 * i + 1];
     vbm_ogg_feed_info fi;
-    oggfeed_info(m.call[i], fi);
+    if (m.rs) oggfeed_rs_info(m.call[i], m.rs[i], fi);
+    else oggfeed_info(m.call[i], fi);
     out_info[i] = fi;
 }
 
+// gap: null, or one mark per packet: the first packet of an entry whose scan met a gap gets 1, every other 0
 __global__ void __launch_bounds__(256) k_feed_fill(int n, FeedArgs a, FeedMem m, OggFeedCaps caps, long long packet_cap,
-                                                   long long payload_cap, OggDmxOut out)
+                                                   long long payload_cap, OggDmxOut out, uint8_t *gap)
 {
     const bool first = blockIdx.x == 0 && threadIdx.x == 0;
     if (*m.committed) {                             // a fill has already written and committed this scan
@@ -191,6 +291,10 @@ __global__ void __launch_bounds__(256) k_feed_fill(int n, FeedArgs a, FeedMem m,
         const int open_in = min(c.open_in, caps.max_packet_bytes);   // never past the slot's store
         if (open_in > 0)
             dmx_wave_copy(out.payload + c.payload_base, m.open + (long long)c.slot * caps.max_packet_bytes, open_in, lane);
+        if (gap) {
+            const int mark = m.rs ? m.rs[i].ev.gaps : 0;
+            for (long long k = lane; k < c.packets; k += 64) gap[c.packet_base + k] = k == 0 && mark;
+        }
     }
 }
 
@@ -217,6 +321,7 @@ __global__ void __launch_bounds__(256) k_feed_commit(int n, FeedArgs a, FeedMem 
         if (tail > 0 && tail <= caps.max_page_carry)
             dmx_wave_copy(m.tail + (long long)c.slot * caps.max_page_carry, m.work + c.pos_end, tail, lane);
         if (lane == 0) m.state[c.slot] = c.next;
+        if (lane == 0 && m.rs) m.link[c.slot] = m.rs[i].next;
     }
 }
 
@@ -225,10 +330,12 @@ __global__ void k_feed_mark(FeedMem m)
     if (*m.status == 0) *m.committed = 1;
 }
 
-__global__ void __launch_bounds__(256) k_feed_reset(int n, const int *ids, OggFeedState *state)
+__global__ void __launch_bounds__(256) k_feed_reset(int n, const int *ids, OggFeedState *state, OggFeedLink *link)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) state[ids[i]] = OggFeedState{};
+    if (i >= n) return;
+    state[ids[i]] = OggFeedState{};
+    if (link) link[ids[i]] = OggFeedLink{};
 }
 
 }  // namespace
@@ -236,7 +343,7 @@ __global__ void __launch_bounds__(256) k_feed_reset(int n, const int *ids, OggFe
 // ---- host side (scaffold: twin_host.h) --------------------------------------------------------------------------
 
 struct vbm_ogg_feed {
-    bool host = false;
+    bool host = false, resync = false;
     int max_streams = 0;
     long long max_call_bytes = 0;
     OggFeedCaps caps = {};
@@ -267,12 +374,13 @@ FeedArgs args_view(uint8_t *base, int n)
 }
 
 int create(vbm_ogg_feed **out, int max_streams, long long max_call_bytes, int max_page_carry, int max_packet_bytes,
-           int header_cap, bool host)
+           int header_cap, unsigned flags, bool host, const char *name)
 {
     if (!out || max_streams < 1 || max_call_bytes < 0 || max_page_carry < 1 || max_page_carry > 65307 ||
-        max_packet_bytes < 1 || header_cap < 1)
-        return fail(VBM_EINVAL, "vbm_ogg_feed_create: bad argument (max_streams >= 1, max_call_bytes >= 0, max_page_carry "
-                                "in 1..65307, max_packet_bytes >= 1, header_cap >= 1)");
+        max_packet_bytes < 1 || header_cap < 1 || (flags & ~VBM_OGG_FEED_RESYNC))
+        return fail(VBM_EINVAL, std::string(name) + ": bad argument (max_streams >= 1, max_call_bytes >= 0, max_page_carry "
+                                                    "in 1..65307, max_packet_bytes >= 1, header_cap >= 1, flags 0 or "
+                                                    "VBM_OGG_FEED_RESYNC)");
     if (!host) {
         int n = 0;
         if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(VBM_ENODEV, "vbm_ogg_feed_create: no HIP device");
@@ -280,6 +388,7 @@ int create(vbm_ogg_feed **out, int max_streams, long long max_call_bytes, int ma
     vbm_ogg_feed *f = new (std::nothrow) vbm_ogg_feed();
     if (!f) return fail(VBM_EFAULT, "vbm_ogg_feed_create: out of memory");
     f->host = f->mem.host = host;
+    f->resync = (flags & VBM_OGG_FEED_RESYNC) != 0;
     f->max_streams = max_streams;
     f->max_call_bytes = max_call_bytes;
     f->caps = {max_page_carry, max_packet_bytes, header_cap};
@@ -308,6 +417,8 @@ int create(vbm_ogg_feed **out, int max_streams, long long max_call_bytes, int ma
     if (!rc) rc = f->mem.get(f->m.status, 1, who);
     if (!rc) rc = f->mem.get(f->m.committed, 1, who);
     if (!rc) rc = f->mem.get(f->args, args_bytes(max_streams), who);
+    if (!rc && f->resync) rc = f->mem.get(f->m.link, S, who);
+    if (!rc && f->resync) rc = f->mem.get(f->m.rs, S, who);
     if (!rc && !host) rc = f->stage.create(args_bytes(max_streams), "vbm_ogg_feed_create: staging");
     if (rc) {
         vbm_ogg_feed_destroy(f);
@@ -352,6 +463,16 @@ int check_scan(vbm_ogg_feed *f, bool host, int n, const int *ids, const uint8_t 
                                     " bytes, above max_call_bytes = " + std::to_string(f->max_call_bytes));
     if (off[n] > off[0] && !data) return fail(VBM_EINVAL, std::string(who) + ": null data");
     return check_ids(f, n, ids, who);
+}
+
+int check_events(const vbm_ogg_feed *f, bool host, const vbm_ogg_feed_events *events, const char *who)
+{
+    int rc = check_kind(f, host, who, "feed");
+    if (rc) return rc;
+    if (!f->resync) return fail(VBM_EINVAL, std::string(who) + ": needs a feed made with VBM_OGG_FEED_RESYNC");
+    if (!f->scanned) return fail(VBM_EINVAL, std::string(who) + ": no scan has been made on this feed");
+    if (f->n && !events) return fail(VBM_EINVAL, std::string(who) + ": null pointer");
+    return VBM_OK;
 }
 
 int check_fill(const vbm_ogg_feed *f, bool host, const uint8_t *payload, long long payload_cap, const long long *offsets,
@@ -403,13 +524,25 @@ dim3 page_grid(const vbm_ogg_feed *f) { return wave_grid(f->n + f->span / 1024);
 extern "C" int vbm_ogg_feed_create(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
                                    int max_packet_bytes, int header_cap)
 {
-    return create(fd, max_streams, max_call_bytes, max_page_carry, max_packet_bytes, header_cap, false);
+    return create(fd, max_streams, max_call_bytes, max_page_carry, max_packet_bytes, header_cap, 0, false, "vbm_ogg_feed_create");
 }
 
 extern "C" int vbm_host_ogg_feed_create(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
                                         int max_packet_bytes, int header_cap)
 {
-    return create(fd, max_streams, max_call_bytes, max_page_carry, max_packet_bytes, header_cap, true);
+    return create(fd, max_streams, max_call_bytes, max_page_carry, max_packet_bytes, header_cap, 0, true, "vbm_host_ogg_feed_create");
+}
+
+extern "C" int vbm_ogg_feed_create2(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
+                                    int max_packet_bytes, int header_cap, unsigned flags)
+{
+    return create(fd, max_streams, max_call_bytes, max_page_carry, max_packet_bytes, header_cap, flags, false, "vbm_ogg_feed_create2");
+}
+
+extern "C" int vbm_host_ogg_feed_create2(vbm_ogg_feed **fd, int max_streams, long long max_call_bytes, int max_page_carry,
+                                         int max_packet_bytes, int header_cap, unsigned flags)
+{
+    return create(fd, max_streams, max_call_bytes, max_page_carry, max_packet_bytes, header_cap, flags, true, "vbm_host_ogg_feed_create2");
 }
 
 extern "C" void vbm_ogg_feed_destroy(vbm_ogg_feed *f)
@@ -435,31 +568,61 @@ extern "C" int vbm_ogg_feed_scan(vbm_ogg_feed *f, int n, const int *ids, const u
     const FeedArgs a = args_view(f->args, n);
     if (n > 0) {
         hipLaunchKernelGGL(k_feed_gather, wave_grid(n), dim3(256), 0, q, n, a, f->m, f->caps, d_data);
-        hipLaunchKernelGGL(k_feed_walk, dim3((n + 63) / 64), dim3(64), 0, q, n, a, f->m, f->caps);
+        if (f->resync) hipLaunchKernelGGL(k_feed_resync_walk, wave_grid(n), dim3(256), 0, q, n, f->pow, a, f->m, f->caps);
+        else hipLaunchKernelGGL(k_feed_walk, dim3((n + 63) / 64), dim3(64), 0, q, n, a, f->m, f->caps);
     }
     hipLaunchKernelGGL(k_feed_scan_pages, dim3(1), dim3(256), 0, q, n, f->m.npages, f->m.page_base);
-    if (n > 0) hipLaunchKernelGGL(k_feed_crc, page_grid(f), dim3(256), 0, q, n, f->pow, a, f->m);
-    if (n > 0) hipLaunchKernelGGL(k_feed_settle, dim3((n + 63) / 64), dim3(64), 0, q, n, a, f->m, f->caps);
+    if (n > 0 && !f->resync) {                      // a resync walk has judged every CRC itself
+        hipLaunchKernelGGL(k_feed_crc, page_grid(f), dim3(256), 0, q, n, f->pow, a, f->m);
+        hipLaunchKernelGGL(k_feed_settle, dim3((n + 63) / 64), dim3(64), 0, q, n, a, f->m, f->caps);
+    }
     hipLaunchKernelGGL(k_feed_scan_counts, dim3(1), dim3(256), 0, q, n, f->m, d_totals);
     if (n > 0) hipLaunchKernelGGL(k_feed_info, dim3((n + 255) / 256), dim3(256), 0, q, n, f->m, d_info);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_scan: launch");
 }
 
-extern "C" int vbm_ogg_feed_fill(vbm_ogg_feed *f, uint8_t *d_payload, long long payload_cap, long long *d_offsets,
-                                 long long *d_granulepos, uint8_t *d_eos, long long packet_cap, void *stream)
+extern "C" int vbm_ogg_feed_scan_events(vbm_ogg_feed *f, vbm_ogg_feed_events *d_events, void *stream)
 {
-    int rc = check_fill(f, false, d_payload, payload_cap, d_offsets, d_granulepos, d_eos, packet_cap, "vbm_ogg_feed_fill");
+    int rc = check_events(f, false, d_events, "vbm_ogg_feed_scan_events");
+    if (rc || f->n == 0) return rc;
+    hipLaunchKernelGGL(k_feed_events, dim3((f->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, f->n, f->m.rs, d_events);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_scan_events: launch");
+}
+
+// vbm_ogg_feed_fill (d_gap null) and vbm_ogg_feed_fill_gaps
+static int fill_device(vbm_ogg_feed *f, uint8_t *d_payload, long long payload_cap, long long *d_offsets,
+                       long long *d_granulepos, uint8_t *d_eos, uint8_t *d_gap, long long packet_cap, void *stream,
+                       const char *who)
+{
+    int rc = check_fill(f, false, d_payload, payload_cap, d_offsets, d_granulepos, d_eos, packet_cap, who);
     if (rc) return rc;
     hipStream_t q = (hipStream_t)stream;
     const FeedArgs a = args_view(f->args, f->n);
     // bases that are never written through (no header part here; no payload bytes when d_payload is null) stay non-null
     const OggDmxOut out = {f->m.hdr, d_payload ? d_payload : f->m.work, d_offsets, d_granulepos, d_eos};
-    hipLaunchKernelGGL(k_feed_fill, page_grid(f), dim3(256), 0, q, f->n, a, f->m, f->caps, packet_cap, payload_cap, out);
+    hipLaunchKernelGGL(k_feed_fill, page_grid(f), dim3(256), 0, q, f->n, a, f->m, f->caps, packet_cap, payload_cap, out,
+                       d_gap);
     hipLaunchKernelGGL(k_feed_commit, page_grid(f), dim3(256), 0, q, f->n, a, f->m, f->caps);
     hipLaunchKernelGGL(k_feed_mark, dim3(1), dim3(1), 0, q, f->m);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_fill: launch");
+    return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, (std::string(who) + ": launch").c_str());
+}
+
+extern "C" int vbm_ogg_feed_fill(vbm_ogg_feed *f, uint8_t *d_payload, long long payload_cap, long long *d_offsets,
+                                 long long *d_granulepos, uint8_t *d_eos, long long packet_cap, void *stream)
+{
+    return fill_device(f, d_payload, payload_cap, d_offsets, d_granulepos, d_eos, nullptr, packet_cap, stream,
+                       "vbm_ogg_feed_fill");
+}
+
+extern "C" int vbm_ogg_feed_fill_gaps(vbm_ogg_feed *f, uint8_t *d_payload, long long payload_cap, long long *d_offsets,
+                                      long long *d_granulepos, uint8_t *d_eos, uint8_t *d_gap, long long packet_cap,
+                                      void *stream)
+{
+    return fill_device(f, d_payload, payload_cap, d_offsets, d_granulepos, d_eos, d_gap, packet_cap, stream,
+                       "vbm_ogg_feed_fill_gaps");
 }
 
 extern "C" int vbm_ogg_feed_status(vbm_ogg_feed *f, int *status, void *stream)
@@ -504,7 +667,10 @@ extern "C" int vbm_ogg_feed_reset_streams(vbm_ogg_feed *f, int n, const int *ids
     if (rc) return rc;
     f->scanned = false;                             // a scan made before the reset is not filled after it
     if (f->host) {
-        for (int i = 0; i < n; i++) f->m.state[ids[i]] = OggFeedState{};
+        for (int i = 0; i < n; i++) {
+            f->m.state[ids[i]] = OggFeedState{};
+            if (f->resync) f->m.link[ids[i]] = OggFeedLink{};
+        }
         return VBM_OK;
     }
     if (n == 0) return VBM_OK;
@@ -512,7 +678,7 @@ extern "C" int vbm_ogg_feed_reset_streams(vbm_ogg_feed *f, int n, const int *ids
     rc = upload_args(f, n, ids, nullptr, nullptr, q, "vbm_ogg_feed_reset_streams: upload of the ids");
     if (rc) return rc;
     hipLaunchKernelGGL(k_feed_reset, dim3((n + 255) / 256), dim3(256), 0, q, n, args_view(f->args, n).ids,
-                       f->m.state);
+                       f->m.state, f->m.link);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_reset_streams: launch");
 }
@@ -542,12 +708,16 @@ extern "C" int vbm_host_ogg_feed_scan(vbm_ogg_feed *f, int n, const int *ids, co
             if (a.off[i + 1] > a.off[i]) memcpy(run + tail, data + a.off[i], (size_t)(a.off[i + 1] - a.off[i]));
         }
         OggFeedCall c;
-        feed_walk_one(a, m, f->caps, i, INT_MAX, false, c);
-        const OggDmxPage *pages = m.pages + feed_first_rec(a.off, i);
-        for (int k = 0; k < c.npages; k++) {
-            if (oggdmx_page_crc_ok(T, f->pow, m.work + pages[k].at, pages[k].len)) continue;
-            feed_walk_one(a, m, f->caps, i, k, true, c);           // pages from the bad one on are not taken
-            break;
+        if (f->resync) {
+            feed_rs_walk_one(OggFeedSerialOps{T, &f->pow}, a, m, f->caps, i, c, m.rs[i]);
+        } else {
+            feed_walk_one(a, m, f->caps, i, INT_MAX, false, c);
+            const OggDmxPage *pages = m.pages + feed_first_rec(a.off, i);
+            for (int k = 0; k < c.npages; k++) {
+                if (oggdmx_page_crc_ok(T, f->pow, m.work + pages[k].at, pages[k].len)) continue;
+                feed_walk_one(a, m, f->caps, i, k, true, c);       // pages from the bad one on are not taken
+                break;
+            }
         }
         c.packet_base = packets, c.payload_base = payload;
         packets += c.packets;
@@ -555,7 +725,8 @@ extern "C" int vbm_host_ogg_feed_scan(vbm_ogg_feed *f, int n, const int *ids, co
         m.page_base[i] = npages;
         npages += c.npages;
         m.call[i] = c;
-        oggfeed_info(c, info[i]);
+        if (f->resync) oggfeed_rs_info(c, m.rs[i], info[i]);
+        else oggfeed_info(c, info[i]);
     }
     m.page_base[n] = npages;
     m.totals[0] = totals[0] = packets;
@@ -563,10 +734,19 @@ extern "C" int vbm_host_ogg_feed_scan(vbm_ogg_feed *f, int n, const int *ids, co
     return VBM_OK;
 }
 
-extern "C" int vbm_host_ogg_feed_fill(vbm_ogg_feed *f, uint8_t *payload, long long payload_cap, long long *offsets,
-                                      long long *granulepos, uint8_t *eos, long long packet_cap)
+extern "C" int vbm_host_ogg_feed_scan_events(vbm_ogg_feed *f, vbm_ogg_feed_events *events)
 {
-    int rc = check_fill(f, true, payload, payload_cap, offsets, granulepos, eos, packet_cap, "vbm_host_ogg_feed_fill");
+    const int rc = check_events(f, true, events, "vbm_host_ogg_feed_scan_events");
+    if (rc) return rc;
+    for (int i = 0; i < f->n; i++) events[i] = f->m.rs[i].ev;
+    return VBM_OK;
+}
+
+// vbm_host_ogg_feed_fill (gap null) and vbm_host_ogg_feed_fill_gaps
+static int fill_host(vbm_ogg_feed *f, uint8_t *payload, long long payload_cap, long long *offsets, long long *granulepos,
+                     uint8_t *eos, uint8_t *gap, long long packet_cap, const char *who)
+{
+    int rc = check_fill(f, true, payload, payload_cap, offsets, granulepos, eos, packet_cap, who);
     if (rc) return rc;
     const FeedMem &m = f->m;
     if (f->host_committed) {
@@ -589,6 +769,8 @@ extern "C" int vbm_host_ogg_feed_fill(vbm_ogg_feed *f, uint8_t *payload, long lo
         const int open_in = c.open_in < f->caps.max_packet_bytes ? c.open_in : f->caps.max_packet_bytes;
         if (open_in > 0)
             memcpy(out.payload + c.payload_base, m.open + (size_t)c.slot * (size_t)f->caps.max_packet_bytes, (size_t)open_in);
+        if (gap)
+            for (long long k = 0; k < c.packets; k++) gap[c.packet_base + k] = k == 0 && f->resync && m.rs[i].ev.gaps;
         for (int k = 0; k < c.npages; k++) {
             OggDmxPageCtx x;
             oggfeed_ctx_payload(m.work, pages[k], c, x);
@@ -608,7 +790,20 @@ extern "C" int vbm_host_ogg_feed_fill(vbm_ogg_feed *f, uint8_t *payload, long lo
         if (tail > 0 && tail <= f->caps.max_page_carry)
             memcpy(m.tail + (size_t)c.slot * (size_t)f->caps.max_page_carry, m.work + c.pos_end, (size_t)tail);
         m.state[c.slot] = c.next;
+        if (f->resync) m.link[c.slot] = m.rs[i].next;
     }
     f->host_committed = true;
     return VBM_OK;
+}
+
+extern "C" int vbm_host_ogg_feed_fill(vbm_ogg_feed *f, uint8_t *payload, long long payload_cap, long long *offsets,
+                                      long long *granulepos, uint8_t *eos, long long packet_cap)
+{
+    return fill_host(f, payload, payload_cap, offsets, granulepos, eos, nullptr, packet_cap, "vbm_host_ogg_feed_fill");
+}
+
+extern "C" int vbm_host_ogg_feed_fill_gaps(vbm_ogg_feed *f, uint8_t *payload, long long payload_cap, long long *offsets,
+                                           long long *granulepos, uint8_t *eos, uint8_t *gap, long long packet_cap)
+{
+    return fill_host(f, payload, payload_cap, offsets, granulepos, eos, gap, packet_cap, "vbm_host_ogg_feed_fill_gaps");
 }

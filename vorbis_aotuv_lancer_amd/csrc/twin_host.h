@@ -41,13 +41,13 @@ template <class M> int check_kind(const M *m, bool host, const char *who, const 
 struct TwinMem {
     bool host = false;
     int n = 0;
-    void *held[16] = {};
+    void *held[20] = {};
 
     // p = count zeroed elements (one at least); who: the object's name in the error text
     template <class T> int get(T *&p, size_t count, const char *who)
     {
         const size_t bytes = (count ? count : 1) * sizeof(T);
-        if (n == 16) return fail(VBM_EFAULT, std::string(who) + ": too many buffers");
+        if (n == 20) return fail(VBM_EFAULT, std::string(who) + ": too many buffers");
         void *v = nullptr;
         if (host) {
             v = calloc(bytes, 1);

@@ -171,11 +171,14 @@ class Decoder(_Handle):
         self._last = (nsb, dev, packets, nbytes, gp, eo)     # inputs stay alive until the work has run
         return pcm, samples, status
 
-    def synthesis_runs(self, stream_ids, counts, data, offsets, granulepos=None, eos=None, pcm_stride=None, out=None):
+    def synthesis_runs(self, stream_ids, counts, data, offsets, granulepos=None, eos=None, pcm_stride=None, out=None,
+                       gap=None):
         """Many packets per stream: run r is counts[r] consecutive packets of stream stream_ids[r] (host ints; ids
         distinct), rows are the runs concatenated (P = sum(counts) <= max_batch).  data: uint8 [bytes] and offsets:
         int64 [P+1] on the device (CSR: packet k is data[offsets[k]:offsets[k+1]]); granulepos int64 [P] / eos uint8
-        [P] or None.  pcm_stride defaults to max(counts) * blocksizes[1]//2 (//4 on a half-rate decoder).
+        [P] or None.  gap: uint8 [P] on the device or None (FeedResult.gap of a resync OggFeed): a non-zero mark says
+        packets were lost in front of that packet, and the stream's granule position and sample count start over there
+        (the overlap-add goes on).  pcm_stride defaults to max(counts) * blocksizes[1]//2 (//4 on a half-rate decoder).
         -> (pcm float32 [nruns, channels, pcm_stride], run_samples int32 [nruns], samples int32 [P],
         status int32 [P]), device tensors; run r's PCM is pcm[r, :, :run_samples[r]].  Bit-identical to one packet per
         call through synthesis_batch.  Only enqueues work on the current stream."""
@@ -199,12 +202,16 @@ class Decoder(_Handle):
             pcm, run_samples, samples, status = out
             pcm_stride = pcm.stride(1)
         gp, eo = _per_packet(granulepos, eos)
-        check(lib.vbm_synthesis_runs(self._h, nruns, ids.ctypes.data, cnt.ctypes.data, data.data_ptr(),
-                                     offsets.data_ptr(), data.numel(), _ptr(gp), _ptr(eo), pcm.data_ptr(), pcm_stride,
-                                     run_samples.data_ptr(), samples.data_ptr(), status.data_ptr(), self._stream()),
-              "vbm_synthesis_runs")
+        if gap is not None:
+            gap = gap.to(torch.uint8).contiguous()
+            if gap.numel() != P:
+                raise ValueError(f"gap must have sum(counts) = {P} entries, has {gap.numel()}")
+        check(lib.vbm_synthesis_runs_gaps(self._h, nruns, ids.ctypes.data, cnt.ctypes.data, data.data_ptr(),
+                                          offsets.data_ptr(), data.numel(), _ptr(gp), _ptr(eo), _ptr(gap), pcm.data_ptr(),
+                                          pcm_stride, run_samples.data_ptr(), samples.data_ptr(), status.data_ptr(),
+                                          self._stream()), "vbm_synthesis_runs_gaps")
         if P:
-            self._last = (P, dev, data, offsets, gp, eo)      # inputs stay alive until the work has run
+            self._last = (P, dev, data, offsets, gp, eo, gap)  # inputs stay alive until the work has run
         return pcm, run_samples, samples, status
 
     def synthesis_ranges(self, store, stream_ids, starts, lengths, pcm_stride=None, out=None):

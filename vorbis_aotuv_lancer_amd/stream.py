@@ -310,10 +310,10 @@ class _TwinHandle:
     """The handle of a C object that comes as a device form (made under its device, destroyed after a synchronize) and a
     host twin: vbm_[host_]ogg_<kind>_create(&h, *args) and vbm_ogg_<kind>_destroy(h)."""
 
-    def __init__(self, kind, host, device, *args):
+    def __init__(self, kind, host, device, *args, create="create"):
         self.host, self.device, self._h = bool(host), None, C.c_void_p()
         self._destroy = getattr(lib, f"vbm_ogg_{kind}_destroy")
-        name = f"vbm_host_ogg_{kind}_create" if host else f"vbm_ogg_{kind}_create"
+        name = f"vbm_host_ogg_{kind}_{create}" if host else f"vbm_ogg_{kind}_{create}"
         if host:
             check(getattr(lib, name)(C.byref(self._h), *args), name)
         else:
@@ -567,17 +567,29 @@ FEED_INFO = np.dtype([("status", "<i4"), ("headers_ready", "<i4"), ("header_byte
                       ("pending", "<i8"), ("consumed", "<i8")])       # vbm_ogg_feed_info
 
 
+FEED_EVENTS = np.dtype([("link", "<i4"), ("link_started", "<i4"), ("link_bad", "<i4"), ("gaps", "<i4"),
+                        ("skipped_bytes", "<i8"), ("ignored_pages", "<i8"), ("left", "<i8")])    # vbm_ogg_feed_events
+
+
 class FeedResult:
     """What OggFeed.push returns.  Per list entry i, on the host: ids[i], counts[i] (audio packets the call completed
     for that slot), status[i] (0, VBM_EOGG or VBM_OGG_FEED_EBIG: sticky) and info[i] (FEED_INFO: vbm_ogg_feed_info).
     For the call: payload uint8 [bytes], offsets int64 [P + 1], granulepos int64 [P], eos uint8 [P] — torch tensors on
-    the device (numpy arrays with host=True) holding ONE CSR over the packets of all entries in list order."""
+    the device (numpy arrays with host=True) holding ONE CSR over the packets of all entries in list order.
+    From a resync feed also: gap uint8 [P] beside eos (1: something was lost in front of that packet), and per list entry
+    on the host events[i] (FEED_EVENTS: vbm_ogg_feed_events) with its fields left, link and link_started as arrays;
+    None from a strict feed."""
 
-    def __init__(self, ids, info, payload, offsets, granulepos, eos):
+    def __init__(self, ids, info, payload, offsets, granulepos, eos, gap=None, events=None):
         self.ids, self.info = ids, info
         self.payload, self.offsets, self.granulepos, self.eos = payload, offsets, granulepos, eos
         self.counts = info["packets"].astype(np.int64)
         self.status = info["status"].tolist()
+        self.gap, self.events = gap, events
+        self.left = self.link = self.link_started = None
+        if events is not None:
+            self.left = events["left"].astype(np.int64)
+            self.link, self.link_started = events["link"].copy(), events["link_started"].astype(bool)
 
     def __len__(self):
         return len(self.ids)
@@ -594,15 +606,32 @@ class OggFeed(_TwinHandle):
                                           granulepos=r.granulepos, eos=r.eos)
 
     (with every listed slot live, r.ids and r.counts go in as they are).  feed.headers(id) returns the stream's three
-    header packets once info["headers_ready"] is set.  host=True runs the CPU twin on numpy arrays (no GPU needed)."""
+    header packets once info["headers_ready"] is set.  host=True runs the CPU twin on numpy arrays (no GPU needed).
+
+    resync=True makes the tolerant feed of a live mount (include/vorbis_mi355x.h, "Resync mode"): it follows chained
+    links, joins mid-stream and goes on after lost or damaged pages.  A slot delivers packets of one link per call, so
+    a chunk may come back in part (r.left); push_all pushes those parts again:
+
+        feed = OggFeed(nstreams, nstreams * 8192, resync=True)
+        for r in feed.push_all(ids, chunks):
+            for i in np.flatnonzero((r.info["headers_ready"] != 0) & (r.link != link_of[r.ids])):
+                ...                               # a new link: DecodeSetup(feed.headers(r.ids[i])), dec.restart_streams
+                link_of[r.ids[i]] = r.link[i]     # (r.link_started marks the call its first page came in)
+            live = np.flatnonzero(r.counts)
+            dec.synthesis_runs(r.ids[live], r.counts[live], r.payload, r.offsets, granulepos=r.granulepos, eos=r.eos,
+                               gap=r.gap)"""
 
     EOGG, EBIG = -1002, -1003
+    RESYNC = 1
 
     def __init__(self, max_streams, max_call_bytes, max_page_carry=65307, max_packet_bytes=65536, header_cap=16384,
-                 host=False, device=None):
-        self.max_streams, self.max_call_bytes = int(max_streams), int(max_call_bytes)
-        super().__init__("feed", host, device, self.max_streams, self.max_call_bytes, int(max_page_carry),
-                         int(max_packet_bytes), int(header_cap))
+                 host=False, device=None, resync=False):
+        self.max_streams, self.max_call_bytes, self.resync = int(max_streams), int(max_call_bytes), bool(resync)
+        args = (self.max_streams, self.max_call_bytes, int(max_page_carry), int(max_packet_bytes), int(header_cap))
+        if resync:
+            super().__init__("feed", host, device, *args, self.RESYNC, create="create2")
+        else:
+            super().__init__("feed", host, device, *args)
 
     def push(self, ids, chunks, end=False, offsets=None):
         """ids: the slots, each at most once.  chunks: one bytes-like per slot (uploaded in one copy), or ONE uint8
@@ -627,27 +656,89 @@ class OggFeed(_TwinHandle):
                                              totals.ctypes.data), "vbm_host_ogg_feed_scan")
             P, B = int(totals[0]), int(totals[1])
             payload, offs, gp, eos = _csr_buffers(P, B)
-            check(lib.vbm_host_ogg_feed_fill(self._h, payload.ctypes.data if B else None, B, offs.ctypes.data,
-                                             gp.ctypes.data if P else None, eos.ctypes.data if P else None, P),
-                  "vbm_host_ogg_feed_fill")
-            return FeedResult(ids, info, payload, offs, gp, eos)
+            if not self.resync:
+                check(lib.vbm_host_ogg_feed_fill(self._h, payload.ctypes.data if B else None, B, offs.ctypes.data,
+                                                 gp.ctypes.data if P else None, eos.ctypes.data if P else None, P),
+                      "vbm_host_ogg_feed_fill")
+                return FeedResult(ids, info, payload, offs, gp, eos)
+            events, gap = np.zeros(n, FEED_EVENTS), np.zeros(P, np.uint8)
+            check(lib.vbm_host_ogg_feed_scan_events(self._h, events.ctypes.data if n else None),
+                  "vbm_host_ogg_feed_scan_events")
+            check(lib.vbm_host_ogg_feed_fill_gaps(self._h, payload.ctypes.data if B else None, B, offs.ctypes.data,
+                                                  gp.ctypes.data if P else None, eos.ctypes.data if P else None,
+                                                  gap.ctypes.data if P else None, P), "vbm_host_ogg_feed_fill_gaps")
+            return FeedResult(ids, info, payload, offs, gp, eos, gap, events)
         import torch
         dev, q = self.device, self._q()
         with torch.cuda.device(dev):
-            # totals and infos in one buffer: one small D2H
-            d_meta = torch.empty(16 + n * FEED_INFO.itemsize, dtype=torch.uint8, device=dev)
+            # totals, infos and (resync) events in one buffer: one small D2H
+            ni, ne = n * FEED_INFO.itemsize, n * FEED_EVENTS.itemsize if self.resync else 0
+            d_meta = torch.empty(16 + ni + ne, dtype=torch.uint8, device=dev)
             check(lib.vbm_ogg_feed_scan(self._h, n, ids.ctypes.data, raw.data_ptr() if raw.numel() else None, off.ctypes.data,
                                         flags.ctypes.data, d_meta.data_ptr() + 16 if n else None, d_meta.data_ptr(), q),
                   "vbm_ogg_feed_scan")
+            if self.resync:
+                check(lib.vbm_ogg_feed_scan_events(self._h, d_meta.data_ptr() + 16 + ni if n else None, q),
+                      "vbm_ogg_feed_scan_events")
             meta = d_meta.cpu().numpy()
-            totals, info = meta[:16].view(np.int64), meta[16:].view(FEED_INFO)
+            totals, info = meta[:16].view(np.int64), meta[16:16 + ni].view(FEED_INFO)
             P, B = int(totals[0]), int(totals[1])
             payload, offs, gp, eos = _csr_buffers(P, B, dev)
             # the buffers have the sizes the scan returned: this fill cannot fall short, so its status word is not waited for
-            check(lib.vbm_ogg_feed_fill(self._h, payload.data_ptr() if B else None, B, offs.data_ptr(),
-                                        gp.data_ptr() if P else None, eos.data_ptr() if P else None, P, q),
-                  "vbm_ogg_feed_fill")
-        return FeedResult(ids, info.copy(), payload, offs, gp, eos)
+            if not self.resync:
+                check(lib.vbm_ogg_feed_fill(self._h, payload.data_ptr() if B else None, B, offs.data_ptr(),
+                                            gp.data_ptr() if P else None, eos.data_ptr() if P else None, P, q),
+                      "vbm_ogg_feed_fill")
+                return FeedResult(ids, info.copy(), payload, offs, gp, eos)
+            gap = torch.empty(P, dtype=torch.uint8, device=dev)
+            check(lib.vbm_ogg_feed_fill_gaps(self._h, payload.data_ptr() if B else None, B, offs.data_ptr(),
+                                             gp.data_ptr() if P else None, eos.data_ptr() if P else None,
+                                             gap.data_ptr() if P else None, P, q), "vbm_ogg_feed_fill_gaps")
+        return FeedResult(ids, info.copy(), payload, offs, gp, eos, gap, meta[16 + ni:].view(FEED_EVENTS).copy())
+
+    @staticmethod
+    def _again(r, flags):
+        """the entries to push again: bytes came back, or the end was given at a stop and carried bytes are still there"""
+        if r.left is None:
+            return []
+        return np.flatnonzero((r.left > 0) | ((flags != 0) & (r.info["pending"] > 0)))
+
+    def push_all(self, ids, chunks, end=False, offsets=None):
+        """push() for a resync feed, again and again with the parts of the chunks that came back (r.left) until none is
+        left; yields each FeedResult, whose ids are the slots that call listed.  `end` is passed on with every push (a
+        slot honours it in the call that does not end at a stop; until then an entry is pushed again, with no bytes if
+        none came back).  Chunks on the device are gathered with torch indexing."""
+        ids = np.asarray(ids, dtype=np.int32)
+        flags = np.broadcast_to(np.asarray(end, dtype=np.uint8), (len(ids),))
+        if offsets is None:
+            parts = [bytes(c) for c in chunks]
+            if len(parts) != len(ids):
+                raise ValueError("one chunk per id")
+            while True:
+                r = self.push(ids, parts, flags)
+                yield r
+                keep = self._again(r, flags)
+                if len(keep) == 0:
+                    return
+                parts = [parts[i][len(parts[i]) - int(r.left[i]):] for i in keep]
+                ids, flags = ids[keep], flags[keep]
+        off = np.asarray(offsets, dtype=np.int64)
+        while True:
+            r = self.push(ids, chunks, flags, off)
+            yield r
+            keep = self._again(r, flags)
+            if len(keep) == 0:
+                return
+            # the left parts, back to back
+            a, b = off[1:][keep] - r.left[keep], off[1:][keep]
+            noff = np.concatenate([[0], np.cumsum(b - a)]).astype(np.int64)
+            idx = np.concatenate([np.arange(x, y) for x, y in zip(a, b)])
+            if self.host:
+                chunks = np.ascontiguousarray(chunks[idx])
+            else:
+                import torch
+                chunks = chunks[torch.from_numpy(idx).to(chunks.device)]
+            ids, flags, off = ids[keep], flags[keep], noff
 
     def headers(self, id):
         """-> the three header packets of slot `id` as bytes (for DecodeSetup); VbmError until they are complete"""
