@@ -20,7 +20,7 @@ STAGE_OF = [("k_window_mdct", "window_mdct"), ("k_window_fft_log", "window_fft_l
             ("k_nonzero_propagate", "pack"), ("k_bitrate_choose", "pack"), ("k_blob_gather", "packet_out"),
             ("k_couple_", "couple_quantize"), ("k_pack_head", "pack"), ("k_pack_fused", "pack"), ("k_rows_out", "packet_out"),
             ("k_res_", "pack"), ("k_from_tiled", "packet_out"), ("k_fe_", "front_end"), ("k_spread_flags", "prologue"),
-            ("k_copy_counted", "packet_out")]
+            ("k_copy_counted", "packet_out"), ("k_packets_out", "packet_out")]
 
 def short(name):
     name = re.sub(r"\(.*\)", "", name)

@@ -77,7 +77,8 @@ print(f"{'write':>5s} {'kernels':>7s} {'chain us':>9s}  head")
 for k in range(len(cf) - N, len(cf)):
     c = cf[k]
     ff = [r for r in back if "k_floor_fit" in r[6] and r[0] < c[0]][-1]
-    last = [r for r in back if "k_copy_counted" in r[6] and r[0] > c[0]][0]
+    # the batch's last kernel: k_packets_out (before the packet-words change: k_copy_counted)
+    last = [r for r in back if ("k_packets_out" in r[6] or "k_copy_counted" in r[6]) and r[0] > c[0]][0]
     chain = [r for r in back if ff[0] <= r[0] <= last[0]]
     h = [r for r in chain if "k_pack_head" in r[6]][0]
     where = f"k_pack_head {h[1]:.0f} us alone, starts {h[0] - (c[0] + c[1]):+.1f} us from the end of k_couple_fast ({c[1]:.0f} us)"

@@ -725,13 +725,8 @@ static int copy_packets(vbm_encoder *e, const vbm_batch &v, uint8_t *d_packets, 
                         bool timed)
 {
     stage_scope t(e, timed, 11, q);
-    if (d_packets && !e->hs->managed)
-        RUN(vbm_launch_untranspose_i32((const int *)v.packetT, (int *)(d_packets + (size_t)sb0 * e->max_packet_bytes),
-                                       e->max_packet_bytes / 4, (size_t)(e->max_packet_bytes / 4) * 64, v.nsb, q));
-    if (d_packet_bytes) {
-        hipError_t err = hipMemcpyAsync(d_packet_bytes + sb0, v.packet_bytes, v.nsb * sizeof(int), hipMemcpyDeviceToDevice, q);
-        if (err != hipSuccess) return vbm_set_hip_error(err, "hipMemcpyAsync(packet_bytes)");
-    }
+    RUN(vbm_launch_packets_out(&v, (d_packets && !e->hs->managed) ? d_packets + (size_t)sb0 * e->max_packet_bytes : nullptr,
+                               d_packet_bytes ? d_packet_bytes + sb0 : nullptr, q));
     return VBM_OK;
 }
 

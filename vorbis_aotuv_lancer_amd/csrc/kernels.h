@@ -20,8 +20,9 @@ int vbm_launch_floor_fit(const vbm_batch *b, hipStream_t st);
 int vbm_launch_floor_encode(const vbm_batch *b, hipStream_t st);
 int vbm_launch_couple_quantize(const vbm_batch *b, hipStream_t st);
 int vbm_launch_pack(const vbm_batch *b, hipStream_t st);          // = pack_head, then pack_residue
-// packets of the batch to the caller's buffers: dst [nsb][max_packet_bytes] (bytes past a packet's length zero), lengths to dst_bytes;
-// either may be NULL; d_nsb as in vbm_batch (device-resident count or NULL).  The untranspose, then the length copy.
+// VBR packets of the batch to the caller's buffers: dst [nsb][max_packet_bytes] (bytes past a packet's length zero), lengths to
+// dst_bytes; either may be NULL; d_nsb as in vbm_batch (device-resident count or NULL).  One kernel: a packet's own words
+// come from the tiles, the rest of its row is written as zeros without being read.
 int vbm_launch_packets_out(const vbm_batch *b, uint8_t *dst, int *dst_bytes, hipStream_t st);
 int vbm_launch_pack_head(const vbm_batch *b, hipStream_t st);     // header + floor bits: may run beside couple/quantise
 int vbm_launch_pack_residue(const vbm_batch *b, hipStream_t st);  // after both: nonzero propagation, residue class + VQ + bits
@@ -30,8 +31,5 @@ int vbm_launch_untranspose_f32(const float *srcT, float *dst_bm, int rows, size_
 int vbm_launch_untranspose_i32(const int *srcT, int *dst_bm, int rows, size_t slab, int ncols, hipStream_t st);
 // packet rows -> one byte run per packet at 4-byte aligned offsets (off[n+1], exclusive scan of the padded lengths)
 int vbm_launch_compact(const uint8_t *rows, const int *len, int n, int maxb, long long *off, uint8_t *out, hipStream_t q);
-// the same with a device-resident column count (NULL: ncols), and a plain int copy of the first *d_count (or n) entries
-int vbm_launch_untranspose_counted(const int *srcT, int *dst_bm, int rows, size_t slab, int ncols, const int *d_ncols, hipStream_t st);
-int vbm_launch_copy_counted(int *dst, const int *src, int n, const int *d_count, hipStream_t st);
 int vbm_launch_untranspose_u8(const uint8_t *srcT, uint8_t *dst_bm, int rows, size_t slab, int ncols, hipStream_t st);
 }

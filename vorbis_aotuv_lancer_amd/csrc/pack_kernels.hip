@@ -20,6 +20,7 @@
 //                   partition, vector) over the bit counts: integer prefix sum -> bit offset of
 //                   every (stage, partition, vector) run; emits the phrase codewords.  Serial, short.
 //   k_res_emit      ORs every run into the packet at its offset (sliced over partitions).
+//   k_packets_out   the packets' words to the caller's rows [block][bytes], zeros past each packet's end, and the lengths.
 // Bits are appended LSb first (libogg oggpack semantics).  Packet buffers are 32-bit-word-major
 // tiles packetT[word][64 lanes], zeroed before k_pack_head; runs written by different wavefronts
 // meet inside words, hence atomicOr.  packet_bytes[sb] = oggpack_bytes(), or -1 on overflow.
@@ -770,11 +771,45 @@ extern "C" int vbm_launch_pack(const vbm_batch *b, hipStream_t st)
     return rc ? rc : vbm_launch_pack_residue(b, st);
 }
 
+// VBR packet tiles -> dst[c][rows] and the lengths -> dst_bytes (either may be NULL): the untranspose and the length copy
+// in one launch.  The tiles are zero past a packet's end (k_zero_u128), so those words need not be read: a word is
+// taken from the tile only inside the packet (an overflowed packet, -1: every row), every other word of the row is
+// written as zero, and a row tile above the longest packet of its 64 lanes goes out without a load or a barrier.
+static __global__ void k_packets_out(const uint32_t *__restrict__ src, const int *__restrict__ bytes, uint32_t *__restrict__ dst,
+                              int *__restrict__ dst_bytes, int ncols, int rows, const int *__restrict__ d_ncols)
+{
+    if (d_ncols) ncols = *d_ncols;                 // device-resident count: `ncols` was the launch bound
+    const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
+    if (c0 >= ncols) return;
+    __shared__ uint32_t tile[64][65];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    int nw = 0;                                    // words of lane c0 + tx that come from the tile
+    if (c0 + tx < ncols) {
+        const int nb = bytes[c0 + tx];
+        nw = nb < 0 ? rows : (nb + 3) >> 2;
+        if (blockIdx.y == 0 && ty == 0 && dst_bytes) dst_bytes[c0 + tx] = nb;
+    }
+    if (!dst) return;
+    const bool any = __any(nw > r0);               // every wavefront holds all 64 lanes: uniform over the workgroup
+    if (any) {
+        const uint32_t *s = src + (size_t)blockIdx.x * rows * 64 + tx;
+        for (int rr = ty; rr < 64; rr += 4) {
+            const int r = r0 + rr;
+            tile[rr][tx] = (r < rows && r < nw) ? s[(size_t)r * 64] : 0u;
+        }
+        __syncthreads();
+    }
+    for (int cc = ty; cc < 64; cc += 4) {
+        const int c = c0 + cc, r = r0 + tx;
+        if (c < ncols && r < rows) dst[(size_t)c * rows + r] = any ? tile[tx][cc] : 0u;
+    }
+}
+
 extern "C" int vbm_launch_packets_out(const vbm_batch *b, uint8_t *dst, int *dst_bytes, hipStream_t st)
 {
-    int rc = 0;
-    if (dst) rc = vbm_launch_untranspose_counted((const int *)b->packetT, (int *)dst, b->max_packet_bytes / 4,
-                                                 (size_t)(b->max_packet_bytes / 4) * 64, b->nsb, b->d_nsb, st);
-    if (!rc && dst_bytes) rc = vbm_launch_copy_counted(dst_bytes, b->packet_bytes, b->nsb, b->d_nsb, st);
-    return rc;
+    if (b->nsb <= 0 || (!dst && !dst_bytes)) return 0;
+    const int rows = b->max_packet_bytes / 4;
+    hipLaunchKernelGGL(k_packets_out, dim3((unsigned)((b->nsb + 63) / 64), dst ? (unsigned)((rows + 63) / 64) : 1u), dim3(256), 0, st,
+                       (const uint32_t *)b->packetT, b->packet_bytes, (uint32_t *)dst, dst_bytes, b->nsb, rows, b->d_nsb);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
 }
