@@ -289,7 +289,11 @@ int vbm_frontend_encode_round_streams(vbm_frontend *fe, const int *stream_ids, i
  * as one byte run in d_out, packet k at d_offsets[k] (4-byte aligned, exclusive prefix sum of the padded
  * lengths), d_offsets[n] = bytes of d_out used; negative lengths count as 0.  d_out needs n * max_packet_bytes
  * bytes in the worst case, d_offsets n + 1 entries.  One D2H copy of d_offsets[n] bytes then replaces n row
- * copies (what vorbis_bitrate_flushpacket's ogg_packet needs on the host, reference lib/bitrate.c:229-252). */
+ * copies (what vorbis_bitrate_flushpacket's ogg_packet needs on the host, reference lib/bitrate.c:229-252).
+ * A packet's run is its length rounded up to 4 bytes; the pad bytes are the row's own.  Nothing of d_out beyond
+ * d_offsets[n] is written.  Lengths are at most max_packet_bytes (not checked); max_packet_bytes is a multiple of 4, d_packets
+ * and d_out are 4-byte aligned, n >= 0 (VBM_EINVAL otherwise, and for a NULL d_offsets, or with n > 0 any NULL
+ * pointer).  n == 0: d_offsets[0] = 0 is written on `stream`, the other pointers are not looked at. */
 int vbm_packets_compact(const uint8_t *d_packets, const int *d_packet_bytes, int n, int max_packet_bytes,
                         uint8_t *d_out, long long *d_offsets, void *stream);
 /* Up to max_rounds rounds in one call (deferred joins: vbm_analysis_round_begin), results complete on `stream`
@@ -329,6 +333,12 @@ int vbm_frontend_join(vbm_frontend *fe, void *stream);
  *   the next call or vbm_frontend_join, as vbm_frontend_encode_rounds_lazy; lazy = 2: nothing is tied to `stream` by
  *   the call — a consumer calls vbm_frontend_join(fe, its_stream) before it reads, so the stream that feeds PCM never
  *   waits for packets).  The buffers belong to the call until then.
+ *   With lazy = 2 nothing on the device ties a consumer's reads of a call's buffers to a later call that is given
+ *   the same buffers: the caller does.  Either it keeps every read of a buffer set ahead of the call that reuses it,
+ *   or it records an event on the consumer's stream behind those reads and makes `stream` wait for that event before
+ *   the reusing call (every kernel and copy that writes the four outputs runs on a stream forked from the front end's
+ *   own stream after the call has made that stream wait for `stream`, the transforms that run ahead of the state
+ *   waits included).  The Python front end's ring of three sets does the second through FrontEnd.release().
  *   The encoder must have been created with max_batch >= vbm_device_round_lanes(setup, nstreams).
  * Mixing with the host-built rounds above is allowed (e.g. to drain completely before vbm_frontend_finish): the first
  * such call waits for the front end's stream and fetches the buffer fills it needs.  While only device-built rounds

@@ -133,3 +133,69 @@ class TwinLedger:
     def lead_packets(self, k):
         """packets of reference stream k in packet-number order"""
         return [self.first[k][pn] for pn in sorted(self.first[k])]
+
+
+class DeviceLog:
+    """The outputs of every encode_rounds_device call of a window, kept on the device with no host involvement, and fed to
+    a TwinLedger only after the window (TwinLedger.add* reads back on every call: it cannot run while calls are in flight).
+
+    One slot per call is allocated up front, in the shapes encode_rounds_device returns for that call's round count.
+    take() is four copy_ on the current stream.  take_compact() copies the packets out the way a host consumer does,
+    with vbm_packets_compact on the current stream: the slot keeps the compacted run, its offsets, the lengths and the
+    records, and replay() rebuilds the zero-padded rows from them on the host.  Neither waits for the device."""
+
+    def __init__(self, fe, rounds_per_call, device, compact=False):
+        lanes, maxb = fe.device_lanes, fe.enc.max_packet_bytes
+        self.maxb, self.dev, self.compact = maxb, device, compact
+        need = sum(nr * lanes * (maxb + 40 + 4 + (8 if compact else 0)) + 64 for nr in rounds_per_call)
+        free, _ = torch.cuda.mem_get_info(device)
+        assert need < 0.8 * free, f"the log of {len(rounds_per_call)} calls needs {need >> 20} MB, the device has {free >> 20} MB free"
+        self.slots = []
+        for nr in rounds_per_call:
+            n = nr * lanes
+            info = torch.empty((n, 40), dtype=torch.uint8, device=device)
+            nbytes = torch.empty((n,), dtype=torch.int32, device=device)
+            counts = torch.empty((nr, 4), dtype=torch.int32, device=device)
+            if compact:
+                self.slots.append((info, torch.empty((n * maxb,), dtype=torch.uint8, device=device), nbytes, counts,
+                                   torch.empty((n + 1,), dtype=torch.int64, device=device)))
+            else:
+                self.slots.append((info, torch.empty((n, maxb), dtype=torch.uint8, device=device), nbytes, counts))
+        self.taken = 0
+
+    def take(self, c, info, packets, nbytes, counts):
+        s = self.slots[c]
+        s[0].copy_(info)
+        s[1].copy_(packets)
+        s[2].copy_(nbytes)
+        s[3].copy_(counts)
+        self.taken += 1
+
+    def take_compact(self, c, info, packets, nbytes, counts):
+        import vorbis_aotuv_lancer_amd as v
+        s = self.slots[c]
+        st = torch.cuda.current_stream().cuda_stream
+        v.check(v.lib.vbm_packets_compact(packets.data_ptr(), nbytes.data_ptr(), int(nbytes.shape[0]), self.maxb,
+                                          s[1].data_ptr(), s[4].data_ptr(), st), "vbm_packets_compact")
+        s[0].copy_(info)
+        s[2].copy_(nbytes)
+        s[3].copy_(counts)
+        self.taken += 1
+
+    def replay(self, ledger):
+        """after the window (the device is idle): every slot to ledger.add_device_rounds, in call order"""
+        assert self.taken == len(self.slots)
+        for c, s in enumerate(self.slots):
+            if not self.compact:
+                ledger.add_device_rounds(s[0], s[1], s[2], f"write {c}")
+                continue
+            nb, off = s[2].cpu().numpy(), s[4].cpu().numpy()
+            n = len(nb)
+            pad = (np.maximum(nb, 0).astype(np.int64) + 3) & ~3          # (-2: an empty lane, no bytes)
+            assert off[n] == pad.sum(), f"write {c}: offsets[n] = {off[n]}, the padded lengths add up to {pad.sum()}"
+            assert np.array_equal(off[:n], np.cumsum(pad) - pad), f"write {c}: offsets are not the prefix sum of the padded lengths"
+            run = s[1][:int(off[n])].cpu().numpy()
+            rows = np.zeros((n, self.maxb), np.uint8)
+            for k in np.flatnonzero(nb > 0):
+                rows[k, :nb[k]] = run[off[k]:off[k] + nb[k]]
+            ledger.add_device_rounds(s[0], torch.from_numpy(rows).to(self.dev), s[2], f"write {c} (compacted)")

@@ -707,8 +707,12 @@ extern "C" int vbm_packets_compact(const uint8_t *d_packets, const int *d_packet
                                    uint8_t *d_out, long long *d_offsets, void *stream)
 {
     if (n < 0 || max_packet_bytes <= 0 || (max_packet_bytes & 3)) return VBM_EINVAL;
-    if (n == 0) return VBM_OK;
-    if (!d_packets || !d_packet_bytes || !d_out || !d_offsets) return VBM_EINVAL;
+    if (!d_offsets) return VBM_EINVAL;
+    if (n == 0) {       // d_offsets[n] = bytes of d_out used: 0 (nothing else is read or written)
+        hipError_t err = hipMemsetAsync(d_offsets, 0, sizeof(long long), (hipStream_t)stream);
+        return err == hipSuccess ? VBM_OK : vbm_set_hip_error(err, "hipMemsetAsync(offsets)");
+    }
+    if (!d_packets || !d_packet_bytes || !d_out) return VBM_EINVAL;
     if (((uintptr_t)d_packets & 3) || ((uintptr_t)d_out & 3)) return VBM_EINVAL;
     return vbm_launch_compact(d_packets, d_packet_bytes, n, max_packet_bytes, d_offsets, d_out, (hipStream_t)stream)
                ? VBM_EHIP : VBM_OK;

@@ -319,13 +319,23 @@ class FrontEnd:
         [nrounds * lanes, max_bytes], nbytes int32 [nrounds * lanes] with -2 = empty lane, counts int32 [nrounds, 4]),
         complete on the current stream when the call's work has run (lazy: the call's long-block batch one call
         later; lazy=2: not tied to the current stream at all — a consumer calls join(stream) before it reads).  They
-        live in a ring of three sets per round count owned by this object."""
+        live in a ring of three sets per round count owned by this object.
+
+        Lifetime of a set.  Without release(): until the third call with the same `nrounds` after it; nothing on the
+        device enforces that, the caller keeps its reads inside that span.  With release(): a consumer that has enqueued
+        its reads of everything joined so far calls release(its_stream); the call that hands a released set out again
+        makes the current stream wait (on the device, event.wait(); the host never blocks) for that point of the
+        consumer's stream before anything of the call is enqueued.  Every kernel and copy that writes the four
+        outputs runs on a stream forked from the front end's stream after the call's entry, which itself waits for
+        the current stream, so the wait covers all of them.  A consumer that lags then slows the producer down instead
+        of reading packets that a later call has overwritten."""
         dev = device or torch.device("cuda", torch.cuda.current_device())
         lanes = self.device_lanes
         rings = getattr(self, "_drings", None)
         if rings is None:
             rings = self._drings = {}
             self._dring_dev = dev
+            self._dhanded, self._dreleased = set(), {}   # sets handed out since the last release(); set -> release event
         if (nrounds, dev) not in rings:      # one ring of three sets per round count (callers may vary it from call to call)
             n = nrounds * lanes
             rings[(nrounds, dev)] = [[(torch.zeros((n, C.sizeof(PacketInfo)), dtype=torch.uint8, device=dev),
@@ -336,11 +346,29 @@ class FrontEnd:
         at = ring[1]
         ring[1] = (at + 1) % 3
         info, packets, nbytes, counts = ring[0][at]
+        released = self._dreleased.pop((nrounds, dev, at), None)
+        if released is not None:
+            released.wait()          # the current stream, and through the call's entry everything that writes the set
+        self._dhanded.add((nrounds, dev, at))
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         check(lib.vbm_frontend_encode_rounds_device(self._h, nrounds, packets.data_ptr(), nbytes.data_ptr(), info.data_ptr(),
                                                     counts.data_ptr(), int(lazy), st),
               "vbm_frontend_encode_rounds_device")
         return info, packets, nbytes, counts
+
+    def release(self, stream=None):
+        """The consumer's half of the ring's reuse guard: `stream` (default: the current one) has been given every read
+        of the sets that encode_rounds_device handed out since the previous release().  One event is recorded on it
+        for those sets; the call that hands one of them out again waits for it on the device.  A caller that never
+        calls release() keeps the unguarded lifetime (three calls per round count)."""
+        handed = getattr(self, "_dhanded", None)
+        if not handed:
+            return
+        ev = torch.cuda.Event()
+        ev.record(stream if stream is not None else torch.cuda.current_stream())
+        for key in handed:
+            self._dreleased[key] = ev
+        handed.clear()
 
     def debug_poison(self, byte=0xFF):
         """test instrumentation: fill the front end's scratch (block buffers, search spectra, round lists) with `byte`"""
@@ -359,6 +387,8 @@ class FrontEnd:
                 self.join()
                 torch.cuda.synchronize(self._dring_dev)
                 self._drings = None
+                self._dhanded.clear()
+                self._dreleased.clear()
             if getattr(self, "_ring", None) is not None:      # nothing may still be writing the ring
                 self.join()
                 torch.cuda.synchronize(self._ring_dev)
