@@ -10,7 +10,6 @@
 #include <string.h>
 #include <functional>
 #include <string>
-#include <algorithm>
 #include <thread>
 #include <vector>
 
@@ -20,9 +19,6 @@
 #include "kernels.h"
 #include "mdct_kernel.h"
 #include "vbm_internal.h"
-
-extern "C" int vbm_launch_spread_flags(const vbm_batch *b, hipStream_t st);
-vbm_setup_host *vbm_setup_handle_host(vbm_setup_handle *h);
 
 static const int kMaxWS = 8;     // (dependency masks hold 4 bits per workspace in 32)
 
@@ -35,6 +31,7 @@ struct vbm_encoder {
     int max_oct, max_partvals;
     std::vector<void *> allocs;
     std::vector<size_t> alloc_bytes;          // size of every entry of `allocs`
+    std::vector<hipEvent_t> owned_events;     // every event made by new_event()
     size_t ws_alloc[kMaxWS + 1] = {};         // allocs [ws_alloc[w], ws_alloc[w + 1]) are the scratch of workspace w (vbm_debug_poison_workspace)
     // Two complete batch workspaces (device pointers; the stream state is shared).  Consecutive calls
     // alternate between them, so that vbm_analysis_batch2 can run the second half of call k (floor fit,
@@ -102,13 +99,12 @@ struct vbm_encoder {
     // batch for one workspace, captured the second time it is needed and replayed from then on.
     struct round_graph { hipGraphExec_t exec = nullptr; int uses = 0; };
     // [workspace][block type; 4 = the big batch (type 3, first round): its launches differ from a small type-3 batch's
-    // (throughput variants of the kernels, own streams)][type_job::part - 1: transforms, psychoacoustics, back half]
+    // (throughput variants of the kernels, own streams)][job_piece: transforms, psychoacoustics, back half]
     round_graph gJ[kMaxWS][5][3];
     hipEvent_t ev_state_big[kMaxWS] = {};  // front half of the big batch run in the workspace
     hipEvent_t ev_tf_big[kMaxWS] = {};     // transforms of the big batch run in the workspace (they run on another stream)
     int queue_last_w[4] = {-1, -1, -1, -1};   // workspace of the newest job on sub[0..3]
     bool small_streams_set = false;
-    hipEvent_t ev_cap_fork = nullptr, ev_cap_join[4] = {};
     int *d_counts_ws = nullptr;            // [kMaxWS][4] block counts of the round in each workspace
     int device_mode = 0;                   // how the last device-built round ran: 1 graphs, 2 plain launches
     bool device_rounds = false;            // ... have run: the per-stream bookkeeping below knows nothing of them
@@ -165,50 +161,66 @@ static int dalloc(vbm_encoder *e, T **p, size_t count, bool zero = true)
     return 0;
 }
 
+// Every event of the encoder is made here and destroyed in vbm_encoder_destroy (hipEventDefault: the timed events of the
+// profiling pool).  NULL: the error is set.
+static hipEvent_t new_event(vbm_encoder *e, unsigned flags = hipEventDisableTiming)
+{
+    hipEvent_t ev = nullptr;
+    hipError_t err = flags == hipEventDefault ? hipEventCreate(&ev) : hipEventCreateWithFlags(&ev, flags);
+    if (err != hipSuccess) { vbm_set_hip_error(err, "hipEventCreate"); return nullptr; }
+    e->owned_events.push_back(ev);
+    return ev;
+}
+
+// sub[] grows to n internal streams, each with its join event; `make` false: the new entries stay empty
+// (vbm_encoder_device_round_open makes its streams in an order of its own)
+static int grow_sub(vbm_encoder *e, int n, bool make = true)
+{
+    while ((int)e->sub.size() < n) {
+        hipStream_t q = nullptr;
+        hipError_t err = make ? hipStreamCreateWithFlags(&q, hipStreamNonBlocking) : hipSuccess;
+        if (err != hipSuccess) return vbm_set_hip_error(err, "hipStreamCreateWithFlags");
+        e->sub.push_back(q);
+        hipEvent_t ev = new_event(e);
+        if (!ev) return VBM_EHIP;
+        e->ev_join.push_back(ev);
+    }
+    return VBM_OK;
+}
+
 extern "C" void vbm_encoder_destroy(vbm_encoder *e)
 {
     if (!e) return;
-    for (void *p : e->allocs) (void)hipFree(p);
-    for (int i = 0; i < kMaxWS; i++) {
-        for (int m = 0; m < 5; m++)
-            for (int k = 0; k < 3; k++)
-                if (e->gJ[i][m][k].exec) (void)hipGraphExecDestroy(e->gJ[i][m][k].exec);
-        if (e->ev_state_big[i]) (void)hipEventDestroy(e->ev_state_big[i]);
-        if (e->ev_tf_big[i]) (void)hipEventDestroy(e->ev_tf_big[i]);
-    }
-    if (e->ev_cap_fork) (void)hipEventDestroy(e->ev_cap_fork);
-    for (int i = 0; i < 4; i++)
-        if (e->ev_cap_join[i]) (void)hipEventDestroy(e->ev_cap_join[i]);
-    for (hipEvent_t ev : e->events) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->ev_join) (void)hipEventDestroy(ev);
-    for (hipStream_t q : e->sub)
-        if (q) (void)hipStreamDestroy(q);
-    for (hipStream_t q : e->aux) (void)hipStreamDestroy(q);
-    for (hipEvent_t ev : e->ev_aux_fork) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->ev_aux_join) (void)hipEventDestroy(ev);
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    for (int i = 0; i < kMaxWS; i++)
-        for (int m = 0; m < 4; m++)
-            { if (e->ev_done[i][m]) (void)hipEventDestroy(e->ev_done[i][m]);
-              if (e->ev_state[i][m]) (void)hipEventDestroy(e->ev_state[i][m]); }
-    for (int i = 0; i < kMaxWS; i++) {
-        if (e->ev_front[i]) (void)hipEventDestroy(e->ev_front[i]);
-        if (e->ev_back[i]) (void)hipEventDestroy(e->ev_back[i]);
-    }
+    for (auto &ws : e->gJ)
+        for (auto &type : ws)
+            for (vbm_encoder::round_graph &g : type)
+                if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    for (hipEvent_t ev : e->owned_events) (void)hipEventDestroy(ev);
+    for (const std::vector<hipStream_t> *qs : {&e->sub, &e->aux})
+        for (hipStream_t q : *qs)
+            if (q) (void)hipStreamDestroy(q);
     for (int i = 0; i < 2; i++) {
         if (e->h_ids[i]) (void)hipHostFree(e->h_ids[i]);
         if (e->h_flags[i]) (void)hipHostFree(e->h_flags[i]);
-        if (e->ev_stage[i]) (void)hipEventDestroy(e->ev_stage[i]);
     }
+    for (void *p : e->allocs) (void)hipFree(p);
     delete e;
 }
 
-// vorbis_bitrate_init (reference lib/bitrate.c:28-56): reservoirs at the desired fill, floater in the middle
-static int bitrate_state_init(vbm_encoder *e, vbm_stream_state &st)
+// vorbis_bitrate_init (reference lib/bitrate.c:28-56): the reservoirs' desired fill
+static long long reservoir_fill(const vbm_setup *s)
 {
-    const vbm_setup *s = e->hs;
-    const long long fill = s->managed ? (long long)((double)s->bi_reservoir_bits * s->bi_reservoir_bias) : 0;
-    std::vector<long long> r(e->S, fill);
+    return s->managed ? (long long)((double)s->bi_reservoir_bits * s->bi_reservoir_bias) : 0;
+}
+
+// Start values of the carried stream state that are not zero (vbm_encoder_create, vbm_encoder_reset): -9999 amplitude
+// maxima as vorbis_block_init / _vp_global_look set them; reservoirs at the desired fill, floater in the middle
+static int stream_state_init(vbm_encoder *e, vbm_stream_state &st)
+{
+    std::vector<float> init(e->S, -9999.f);
+    (void)hipMemcpy(st.g_ampmax, init.data(), e->S * sizeof(float), hipMemcpyHostToDevice);
+    (void)hipMemcpy(st.vbi_ampmax, init.data(), e->S * sizeof(float), hipMemcpyHostToDevice);
+    std::vector<long long> r(e->S, reservoir_fill(e->hs));
     std::vector<double> f(e->S, (double)(VBM_PACKETBLOBS / 2));
     if (hipMemcpy(st.bm_avg_reservoir, r.data(), e->S * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(st.bm_minmax_reservoir, r.data(), e->S * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess ||
@@ -264,7 +276,7 @@ extern "C" int vbm_encoder_create(vbm_encoder **out, vbm_setup_handle *setup, in
     b.ch = e->ch;
     b.max_packet_bytes = e->max_packet_bytes;
 #define A(field, type, count) do { type *p_; rc = dalloc<type>(e, &p_, (count)); if (rc) { vbm_encoder_destroy(e); return rc; } field = p_; } while (0)
-    // stream state (lib/codec_internal.h:85-92); -9999 ampmax as vorbis_block_init / _vp_global_look set it
+    // stream state (lib/codec_internal.h:85-92)
     b.st.S = nstreams;
     b.st.ch = e->ch;
     b.st.Lc = round64(nstreams * e->ch);
@@ -280,13 +292,8 @@ extern "C" int vbm_encoder_create(vbm_encoder **out, vbm_setup_handle *setup, in
     A(b.st.bm_avg_reservoir, long long, (size_t)nstreams);
     A(b.st.bm_minmax_reservoir, long long, (size_t)nstreams);
     A(b.st.bm_avgfloat, double, (size_t)nstreams);
-    rc = bitrate_state_init(e, b.st);
+    rc = stream_state_init(e, b.st);
     if (rc) { vbm_encoder_destroy(e); return rc; }
-    {
-        std::vector<float> init(nstreams, -9999.f);
-        (void)hipMemcpy(b.st.g_ampmax, init.data(), nstreams * sizeof(float), hipMemcpyHostToDevice);
-        (void)hipMemcpy(b.st.vbi_ampmax, init.data(), nstreams * sizeof(float), hipMemcpyHostToDevice);
-    }
   }
   {
       const char *env = getenv("VBM_WORKSPACES");
@@ -383,34 +390,22 @@ extern "C" int vbm_encoder_create(vbm_encoder **out, vbm_setup_handle *setup, in
     e->ws_alloc[w + 1] = e->allocs.size();
   }
 #undef A
+    bool ok = true;
     for (int i = 0; i < kMaxWS; i++)
-        if (hipEventCreateWithFlags(&e->ev_front[i], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_back[i], hipEventDisableTiming) != hipSuccess) {
-            vbm_encoder_destroy(e);
-            return VBM_EHIP;
-        }
-    for (int i = 0; i < 2; i++) {
-        if (hipHostMalloc((void **)&e->h_ids[i], Ls * sizeof(int), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void **)&e->h_flags[i], Ls, hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_stage[i], hipEventDisableTiming) != hipSuccess) {
-            vbm_encoder_destroy(e);
-            g_vbm_err = "hipHostMalloc / hipEventCreate (staging) failed";
-            return VBM_EHIP;
-        }
-    }
-    if (hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess) {
-        vbm_encoder_destroy(e);
-        return VBM_EHIP;
-    }
+        ok = ok && (e->ev_front[i] = new_event(e)) && (e->ev_back[i] = new_event(e));
+    for (int i = 0; i < 2; i++)
+        ok = ok && hipHostMalloc((void **)&e->h_ids[i], Ls * sizeof(int), hipHostMallocDefault) == hipSuccess &&
+             hipHostMalloc((void **)&e->h_flags[i], Ls, hipHostMallocDefault) == hipSuccess && (e->ev_stage[i] = new_event(e));
+    ok = ok && (e->ev_fork = new_event(e));
     for (int i = 0; i < kMaxWS; i++)
         for (int m = 0; m < 4; m++)
-            if (hipEventCreateWithFlags(&e->ev_done[i][m], hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&e->ev_state[i][m], hipEventDisableTiming) != hipSuccess ||
-                (m == 0 && (hipEventCreateWithFlags(&e->ev_state_big[i], hipEventDisableTiming) != hipSuccess ||
-                            hipEventCreateWithFlags(&e->ev_tf_big[i], hipEventDisableTiming) != hipSuccess))) {
-                vbm_encoder_destroy(e);
-                return VBM_EHIP;
-            }
+            ok = ok && (e->ev_done[i][m] = new_event(e)) && (e->ev_state[i][m] = new_event(e)) &&
+                 (m || ((e->ev_state_big[i] = new_event(e)) && (e->ev_tf_big[i] = new_event(e))));
+    if (!ok) {
+        vbm_encoder_destroy(e);
+        g_vbm_err = "hipHostMalloc / hipEventCreate (encoder) failed";
+        return VBM_EHIP;
+    }
     e->last.assign(nstreams, {-1, -1, 0u});
     {
         const char *env = getenv("VBM_SUB_BATCHES");
@@ -428,25 +423,15 @@ extern "C" int vbm_encoder_create(vbm_encoder **out, vbm_setup_handle *setup, in
 extern "C" int vbm_encoder_set_sub_batches(vbm_encoder *e, int n)
 {
     if (!e || n < 1 || n > 64) return VBM_EINVAL;
-    while ((int)e->sub.size() < n) {
-        hipStream_t q;
-        hipEvent_t ev;
-        hipError_t err = hipStreamCreateWithFlags(&q, hipStreamNonBlocking);
-        if (err != hipSuccess) return vbm_set_hip_error(err, "hipStreamCreateWithFlags");
-        e->sub.push_back(q);
-        err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (err != hipSuccess) return vbm_set_hip_error(err, "hipEventCreateWithFlags");
-        e->ev_join.push_back(ev);
-    }
+    int rc = grow_sub(e, n);
+    if (rc) return rc;
     while ((int)e->aux.size() < n) {
         hipStream_t q;
-        hipEvent_t e1, e2;
         hipError_t err = hipStreamCreateWithFlags(&q, hipStreamNonBlocking);
         if (err != hipSuccess) return vbm_set_hip_error(err, "hipStreamCreateWithFlags");
         e->aux.push_back(q);
-        if ((err = hipEventCreateWithFlags(&e1, hipEventDisableTiming)) != hipSuccess ||
-            (err = hipEventCreateWithFlags(&e2, hipEventDisableTiming)) != hipSuccess)
-            return vbm_set_hip_error(err, "hipEventCreateWithFlags");
+        hipEvent_t e1 = new_event(e), e2 = new_event(e);
+        if (!e1 || !e2) return VBM_EHIP;
         e->ev_aux_fork.push_back(e1);
         e->ev_aux_join.push_back(e2);
     }
@@ -482,25 +467,76 @@ extern "C" int vbm_encoder_reset(vbm_encoder *e)
     (void)hipMemset(st.lW_block_mode, 0, e->S * sizeof(int));
     (void)hipMemset(st.lW_no, 0, e->S * sizeof(int));
     (void)hipMemset(st.impadnum, 0, e->S * sizeof(int));
-    std::vector<float> init(e->S, -9999.f);
-    (void)hipMemcpy(st.g_ampmax, init.data(), e->S * sizeof(float), hipMemcpyHostToDevice);
-    (void)hipMemcpy(st.vbi_ampmax, init.data(), e->S * sizeof(float), hipMemcpyHostToDevice);
-    return bitrate_state_init(e, st);
+    return stream_state_init(e, st);
+}
+
+// ---- workspace slots and their events ("Workspace slots and their events") -----------------------------------
+
+// `q` waits for ev_done of every slot (w, m) whose flag in `flags` (done_pending or reuse_pending) is set and that
+// pred(w, m) accepts; `clear`: the flag is cleared, the slot counts as waited for
+template <typename Pred>
+static int wait_slots(vbm_encoder *e, hipStream_t q, bool (*flags)[4], Pred pred, bool clear)
+{
+    for (int w = 0; w < e->nws; w++)
+        for (int m = 0; m < 4; m++)
+            if (flags[w][m] && pred(w, m)) {
+                hipError_t err = hipStreamWaitEvent(q, e->ev_done[w][m], 0);
+                if (err != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
+                if (clear) flags[w][m] = false;
+            }
+    return VBM_OK;
+}
+static bool any_slot(int, int) { return true; }
+struct slots_of { int w; bool operator()(int ww, int) const { return ww == w; } };   // the slots of workspace w
+
+// The next workspace in rotation, free for `q` and everything forked from it: q waits for the back half of the
+// vbm_analysis_batch2 call that last read it and for the rounds' batches that last ran in it.  < 0: VBM_E*
+static int take_workspace(vbm_encoder *e, hipStream_t q)
+{
+    const int w = e->next;
+    e->next = (e->next + 1) % e->nws;
+    e->cur = w;
+    if (e->back_pending[w]) {
+        hipError_t err = hipStreamWaitEvent(q, e->ev_back[w], 0);
+        if (err != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
+        e->back_pending[w] = false;
+    }
+    const int rc = wait_slots(e, q, e->reuse_pending, slots_of{w}, true);
+    return rc ? rc : w;
+}
+
+// Stream ids / window flags reach the device through pinned staging, so the copy never stalls the host.  stage_begin:
+// the turn whose buffers (h_ids[t], h_flags[t]) the caller may fill, once the copy that last used them has run;
+// stage_commit: their first n entries go to workspace w on `q`.
+static int stage_begin(vbm_encoder *e)
+{
+    const int t = e->stage_turn;
+    e->stage_turn ^= 1;
+    (void)hipEventSynchronize(e->ev_stage[t]);
+    return t;
+}
+static int stage_commit(vbm_encoder *e, int t, int w, int n, hipStream_t q)
+{
+    hipError_t err;
+    if ((err = hipMemcpyAsync(e->d_stream_id[w], e->h_ids[t], n * sizeof(int), hipMemcpyHostToDevice, q)) != hipSuccess ||
+        (err = hipMemcpyAsync(e->d_wflags[w], e->h_flags[t], n, hipMemcpyHostToDevice, q)) != hipSuccess)
+        return vbm_set_hip_error(err, "hipMemcpyAsync(stream ids / window flags)");
+    (void)hipEventRecord(e->ev_stage[t], q);
+    return VBM_OK;
+}
+
+// stage timing covers this call: profiling is on, calls are left and the pool has `need` events
+static bool prof_gate(const vbm_encoder *e, size_t need)
+{
+    return e->profiling && e->prof_calls < e->prof_max_calls && e->events_used + need <= e->events.size();
 }
 
 // the listed streams start over (a new stream in a used slot); d_ids: device copy of the ids
 int vbm_encoder_reset_streams_dev(vbm_encoder *e, const int *d_ids, int n, hipStream_t q)
 {
-    const vbm_setup *s = e->hs;
-    const long long fill = s->managed ? (long long)((double)s->bi_reservoir_bits * s->bi_reservoir_bias) : 0;
-    if (vbm_analysis_round_join(e, q)) return VBM_EHIP;
-    for (int w = 0; w < e->nws; w++)      // ... including batches a join to another stream has already released
-        for (int m = 0; m < 4; m++)
-            if (e->reuse_pending[w][m]) {
-                if (hipStreamWaitEvent(q, e->ev_done[w][m], 0) != hipSuccess) return VBM_EHIP;
-                e->reuse_pending[w][m] = false;
-            }
-    return vbm_launch_reset_streams(&e->bw[0].st, d_ids, n, fill, q) ? VBM_EHIP : VBM_OK;
+    // every batch in flight comes first, including those a join to another stream has already released
+    if (vbm_analysis_round_join(e, q) || wait_slots(e, q, e->reuse_pending, any_slot, true)) return VBM_EHIP;
+    return vbm_launch_reset_streams(&e->bw[0].st, d_ids, n, reservoir_fill(e->hs), q) ? VBM_EHIP : VBM_OK;
 }
 
 static void configure(vbm_encoder *e, vbm_batch &b, int block_mode, int nsb, const float *d_pcm, int w)
@@ -758,28 +794,15 @@ extern "C" int vbm_analysis_batch2(vbm_encoder *e, int block_mode, int nsb, cons
     hipStream_t sback = (hipStream_t)stream_back;
     const bool two = (sback != st);
     hipError_t err;
-    {   // rounds begun with a deferred join are completed first: their streams may be in this batch
-        int rcj = vbm_analysis_round_join(e, stream);
-        if (rcj) return rcj;
-        for (int ww = 0; ww < e->nws; ww++)
-            for (int m = 0; m < 4; m++)
-                if (e->reuse_pending[ww][m]) {
-                    if ((err = hipStreamWaitEvent((hipStream_t)stream, e->ev_done[ww][m], 0)) != hipSuccess)
-                        return vbm_set_hip_error(err, "hipStreamWaitEvent");
-                    e->reuse_pending[ww][m] = false;
-                }
-        e->round_w = -1;
-    }
-    const int w = e->next;
-    e->next = (e->next + 1) % e->nws;
-    e->cur = w;
-    // this workspace was last read by the back half of the call before the previous one
-    if (e->back_pending[w]) {
-        if ((err = hipStreamWaitEvent(st, e->ev_back[w], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-        e->back_pending[w] = false;
-    }
-    // stream ids / window flags: through pinned staging so the copy never stalls the host, and not
-    // at all when the caller repeats the previous lists (the steady state of a streaming encode)
+    int rc;
+    // rounds begun with a deferred join are completed first: their streams may be in this batch
+    if ((rc = vbm_analysis_round_join(e, stream)) || (rc = wait_slots(e, st, e->reuse_pending, any_slot, true))) return rc;
+    e->round_w = -1;
+    // (the workspace was last read by the back half of the call before the previous one)
+    const int w = take_workspace(e, st);
+    if (w < 0) return w;
+    // stream ids / window flags: not uploaded at all when the caller repeats the previous lists (the steady state of
+    // a streaming encode)
     if ((int)e->last_ids[w].size() != nsb || memcmp(e->last_ids[w].data(), stream_ids, nsb * sizeof(int)) ||
         memcmp(e->last_flags[w].data(), wflags, nsb)) {
         // a stream once per batch: two blocks of one stream would race on its carried state
@@ -788,16 +811,10 @@ extern "C" int vbm_analysis_batch2(vbm_encoder *e, int block_mode, int nsb, cons
             if (e->seen[stream_ids[i]]) { g_vbm_err = "a stream id appears twice in one batch"; return VBM_EINVAL; }
             e->seen[stream_ids[i]] = 1;
         }
-        const int t = e->stage_turn;
-        e->stage_turn ^= 1;
-        (void)hipEventSynchronize(e->ev_stage[t]);   // the copy that last used this buffer has run
+        const int t = stage_begin(e);
         memcpy(e->h_ids[t], stream_ids, nsb * sizeof(int));
         memcpy(e->h_flags[t], wflags, nsb);
-        if ((err = hipMemcpyAsync(e->d_stream_id[w], e->h_ids[t], nsb * sizeof(int), hipMemcpyHostToDevice, st)) != hipSuccess)
-            return vbm_set_hip_error(err, "hipMemcpyAsync(stream_ids)");
-        if ((err = hipMemcpyAsync(e->d_wflags[w], e->h_flags[t], nsb, hipMemcpyHostToDevice, st)) != hipSuccess)
-            return vbm_set_hip_error(err, "hipMemcpyAsync(wflags)");
-        (void)hipEventRecord(e->ev_stage[t], st);
+        if ((rc = stage_commit(e, t, w, nsb, st))) return rc;
         e->last_ids[w].assign(stream_ids, stream_ids + nsb);
         e->last_flags[w].assign(wflags, wflags + nsb);
     }
@@ -807,70 +824,48 @@ extern "C" int vbm_analysis_batch2(vbm_encoder *e, int block_mode, int nsb, cons
     e->last_nsb = nsb;
     e->last_mode = block_mode;
 
-    // slices: multiples of 64 stream-blocks
+    // Parts: the stages behind the transforms run as tile-aligned slices (multiples of 64 stream-blocks), forked from
+    // an event and joined to the `home` stream.  One-stream form: psychoacoustics and back half of a part on sub[part],
+    // forked from ev_fork behind the transforms, joined to the caller's stream (a single part stays on it).  Two-stream
+    // form: the front half of the whole batch on the caller's front stream; only the back half in parts, forked from
+    // ev_front[w], the first on the caller's back stream and the others on internal streams beside it (their
+    // few-wavefront serial kernels then overlap each other's wide ones), joined back before ev_back.
     const int tiles = (nsb + 63) / 64;
-    int nsplit = e->nsplit < tiles ? e->nsplit : tiles;
-    if (nsplit < 1) nsplit = 1;
-    const int nback = nsplit;             // two-stream form: the sub-batches apply to the back half only
-    if (two) nsplit = 1;
-
-    int rc;
-    const size_t ev_need = (size_t)2 * (kFront + (size_t)(nsplit > nback ? nsplit : nback) * kBack);
-    const bool prof = e->profiling && e->prof_calls < e->prof_max_calls && e->events_used + ev_need <= e->events.size();
+    const int nparts = e->nsplit < tiles ? e->nsplit : tiles;
+    const bool prof = prof_gate(e, (size_t)2 * (kFront + (size_t)nparts * kBack));
+    const bool forked = two || nparts > 1;
+    hipStream_t home = two ? sback : st;
+    hipEvent_t ev_parts = two ? e->ev_front[w] : e->ev_fork;
     vbm_debug_delay_point(VBM_DP_BATCH_FRONT, st);
     if ((rc = launch_transforms(e, b, st, prof))) return rc;
-    if (two) {
-        // front half of the whole batch on the caller's front stream; the back half as `nback` tile-aligned
-        // slices, the first on the caller's back stream and the others on internal streams beside it (their
-        // few-wavefront serial kernels then overlap each other's wide ones), joined back before ev_back
-        if ((rc = launch_psy(e, b, st, prof, e->overlap_branches ? 0 : -1))) return rc;
-        if ((err = hipEventRecord(e->ev_front[w], st)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-        for (int part = 0; part < nback; part++) {
-            const int t0 = (int)((long)tiles * part / nback), t1 = (int)((long)tiles * (part + 1) / nback);
-            const int sb0 = t0 * 64, sb1 = (t1 * 64 < nsb) ? t1 * 64 : nsb;
-            if (sb1 <= sb0) continue;
-            hipStream_t qb = part ? e->sub[part] : sback;
-            if ((err = hipStreamWaitEvent(qb, e->ev_front[w], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-            vbm_debug_delay_point(VBM_DP_BATCH_BACK, qb);
-            vbm_batch vs = nback > 1 ? slice_of(b, sb0, sb1 - sb0) : b;
-            if ((rc = launch_back(e, vs, qb, prof, d_packets ? d_packets + (size_t)sb0 * e->max_packet_bytes : nullptr)) ||
-                (rc = copy_packets(e, vs, d_packets, d_packet_bytes, sb0, qb, prof)))
-                return rc;
-            if (part) {
-                if ((err = hipEventRecord(e->ev_join[part], qb)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-                if ((err = hipStreamWaitEvent(sback, e->ev_join[part], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-            }
+    if (two && (rc = launch_psy(e, b, st, prof, e->overlap_branches ? 0 : -1))) return rc;
+    if (forked && (err = hipEventRecord(ev_parts, st)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
+    for (int part = 0; part < nparts; part++) {
+        const int t0 = (int)((long)tiles * part / nparts), t1 = (int)((long)tiles * (part + 1) / nparts);
+        const int sb0 = t0 * 64, sb1 = (t1 * 64 < nsb) ? t1 * 64 : nsb;
+        if (sb1 <= sb0) continue;
+        hipStream_t q = (two ? part > 0 : nparts > 1) ? e->sub[part] : home;
+        if (forked && (err = hipStreamWaitEvent(q, ev_parts, 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
+        if (two) vbm_debug_delay_point(VBM_DP_BATCH_BACK, q);
+        const vbm_batch v = nparts > 1 ? slice_of(b, sb0, sb1 - sb0) : b;
+        if ((!two && (rc = launch_psy(e, v, q, prof, e->overlap_branches ? part : -1))) ||
+            (rc = launch_back(e, v, q, prof, d_packets ? d_packets + (size_t)sb0 * e->max_packet_bytes : nullptr)) ||
+            (rc = copy_packets(e, v, d_packets, d_packet_bytes, sb0, q, prof)))
+            return rc;
+        if (q != home) {
+            if ((err = hipEventRecord(e->ev_join[part], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
+            if ((err = hipStreamWaitEvent(home, e->ev_join[part], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
         }
+    }
+    if (two) {
         if ((err = hipEventRecord(e->ev_back[w], sback)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
         e->back_pending[w] = true;
-    } else {
-        if (nsplit > 1 && (err = hipEventRecord(e->ev_fork, st)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-        for (int part = 0; part < nsplit; part++) {
-            const int t0 = (int)((long)tiles * part / nsplit), t1 = (int)((long)tiles * (part + 1) / nsplit);
-            const int sb0 = t0 * 64, sb1 = (t1 * 64 < nsb) ? t1 * 64 : nsb;
-            if (sb1 <= sb0) continue;
-            hipStream_t q = st;
-            vbm_batch v = b;
-            if (nsplit > 1) {
-                q = e->sub[part];
-                v = slice_of(b, sb0, sb1 - sb0);
-                if ((err = hipStreamWaitEvent(q, e->ev_fork, 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-            }
-            if ((rc = launch_psy(e, v, q, prof, e->overlap_branches ? part : -1)) ||
-                (rc = launch_back(e, v, q, prof, d_packets ? d_packets + (size_t)sb0 * e->max_packet_bytes : nullptr)) ||
-                (rc = copy_packets(e, v, d_packets, d_packet_bytes, sb0, q, prof)))
-                return rc;
-            if (nsplit > 1) {
-                if ((err = hipEventRecord(e->ev_join[part], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-                if ((err = hipStreamWaitEvent(st, e->ev_join[part], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-            }
-        }
     }
     if (prof) { e->prof_calls++; e->prof_blocks += nsb; }
     return VBM_OK;
 }
 
-// One block type of a round: its whole pipeline on its internal HIP stream(s), forked from ev_fork.
+// One block type of a round: the batch in its lane region of a workspace.
 struct type_job {
     int m, w;                    // block type, workspace
     int lane0, bound;            // first stream-block lane of the type's region; blocks in it (d_nsb set: the most it may hold)
@@ -878,16 +873,24 @@ struct type_job {
     const float *pcm;            // the region's block PCM [bound][ch][N]
     uint8_t *d_packets;          // outputs of this type, already offset (may be NULL)
     int *d_packet_bytes;
-    bool big, timed;
-    unsigned depmask;            // bit (ww * 4 + t): slot (ww, t) holds a batch this one's streams may come from
-    // rounds run as graphs (device_round_run_graphs): the job is one piece of a group that is forked from / joined
-    // to its origin stream by the caller, in or outside a stream capture
+    bool big = false, timed = false;
+    unsigned depmask = 0;        // bit (ww * 4 + t): slot (ww, t) holds a batch this one's streams may come from
     int few = 0;                 // small batch behind a large launch bound (device-built rounds): latency-bound kernel variants
-    int part = 0;                // 0 whole pipeline; one piece of it: 1 transforms, 2 psychoacoustics (prologue up to the
-                                 // block-state update), 3 back half
-    bool grouped = false;        // no ev_fork wait, no dependency waits, no state / done events, no output copy
-    hipStream_t q_on = nullptr;  // grouped: the stream to enqueue on
 };
+
+// Block type m in lanes [lane0, lane0 + bound) of workspace w.  Its PCM and outputs start `data_off` blocks into the
+// caller's buffers: compact (blocks of lower types) in the host-built rounds, lane0 in the device-built ones.  The
+// caller sets big, timed, few and depmask.
+static type_job make_job(vbm_encoder *e, int w, int m, int lane0, int data_off, int bound, const int *d_nsb,
+                         const float *pcm_base, uint8_t *d_packets, int *d_packet_bytes)
+{
+    type_job j;
+    j.m = m; j.w = w; j.lane0 = lane0; j.bound = bound; j.d_nsb = d_nsb;
+    j.pcm = pcm_base + (size_t)data_off * e->ch * e->hs->blocksizes[1];
+    j.d_packets = d_packets ? d_packets + (size_t)data_off * e->max_packet_bytes : nullptr;
+    j.d_packet_bytes = d_packet_bytes ? d_packet_bytes + data_off : nullptr;
+    return j;
+}
 
 // the job's region of its workspace as a batch
 static vbm_batch job_batch(vbm_encoder *e, const type_job &j)
@@ -910,55 +913,46 @@ static int round_outputs(vbm_encoder *e, const vbm_batch &v, const type_job &j, 
     return VBM_OK;
 }
 
+// The whole pipeline of a job on its internal HIP stream (sub[m]; a big batch: front half on sub[4], back half on
+// sub[5]), forked from ev_fork, up to its outputs and ev_done.
 static int enqueue_job(vbm_encoder *e, const type_job &j)
 {
     hipError_t err;
     int rc;
-    const int m = j.m, w = j.w;
-    hipStream_t q = j.grouped ? j.q_on : (j.big ? e->sub[4] : e->sub[m]);
-    const int qid = j.big ? 4 : m;
-    if (!j.grouped && (err = hipStreamWaitEvent(q, e->ev_fork, 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-    if (!j.grouped) vbm_debug_delay_point(j.big ? VBM_DP_JOB_BIG : VBM_DP_JOB_SMALL, q);
+    const int m = j.m, w = j.w, qid = j.big ? 4 : m;
+    hipStream_t q = e->sub[qid];
+    if ((err = hipStreamWaitEvent(q, e->ev_fork, 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
+    vbm_debug_delay_point(j.big ? VBM_DP_JOB_BIG : VBM_DP_JOB_SMALL, q);
     const vbm_batch v = job_batch(e, j);
-    if (j.part <= 1 && (rc = launch_transforms(e, v, q, j.timed))) return rc;
-    if (j.part == 1) return VBM_OK;
-    if (j.part != 3) {
-        // the transforms read the block's PCM only; from here on the carried stream state is involved: the batches
-        // this batch's streams were last part of come first (those on this very HIP stream already do)
-        if (!j.grouped) {
-            for (int ww = 0; ww < e->nws; ww++)
-                for (int t = 0; t < 4; t++)
-                    if (((j.depmask >> (ww * 4 + t)) & 1u) && e->slot_queue[ww][t] != qid &&
-                        (err = hipStreamWaitEvent(q, e->ev_state[ww][t], 0)) != hipSuccess)
-                        return vbm_set_hip_error(err, "hipStreamWaitEvent");
-            vbm_debug_delay_point(VBM_DP_JOB_STATE, q);
-        }
-        // noise mask, then tone mask, on one stream.  With the tone mask of the long-block batch on a second stream beside
-        // the noise mask (as in vbm_analysis_batch2) the step from PCM measured 5.04 ms against 4.58: the two LDS-heavy
-        // kernels side by side crowd out the back half of the round before (profiles/r03/README.md).
-        if ((rc = launch_psy(e, v, q, j.timed))) return rc;
+    if ((rc = launch_transforms(e, v, q, j.timed))) return rc;
+    // the transforms read the block's PCM only; from here on the carried stream state is involved: the batches
+    // this batch's streams were last part of come first (those on this very HIP stream already do)
+    for (int ww = 0; ww < e->nws; ww++)
+        for (int t = 0; t < 4; t++)
+            if (((j.depmask >> (ww * 4 + t)) & 1u) && e->slot_queue[ww][t] != qid &&
+                (err = hipStreamWaitEvent(q, e->ev_state[ww][t], 0)) != hipSuccess)
+                return vbm_set_hip_error(err, "hipStreamWaitEvent");
+    vbm_debug_delay_point(VBM_DP_JOB_STATE, q);
+    // noise mask, then tone mask, on one stream.  With the tone mask of the long-block batch on a second stream beside
+    // the noise mask (as in vbm_analysis_batch2) the step from PCM measured 5.04 ms against 4.58: the two LDS-heavy
+    // kernels side by side crowd out the back half of the round before (profiles/r03/README.md).
+    if ((rc = launch_psy(e, v, q, j.timed))) return rc;
+    if ((err = hipEventRecord(e->ev_state[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
+    if (j.big) {   // hand over to the back-half stream of big batches
+        if ((err = hipStreamWaitEvent(e->sub[5], e->ev_state[w][m], 0)) != hipSuccess)
+            return vbm_set_hip_error(err, "big batch hand-over");
+        q = e->sub[5];
     }
-    if (j.part == 2) return VBM_OK;
-    if (!j.grouped) {
-        if ((err = hipEventRecord(e->ev_state[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
-        if (j.big) {   // hand over to the back-half stream of big batches
-            if ((err = hipStreamWaitEvent(e->sub[5], e->ev_state[w][m], 0)) != hipSuccess)
-                return vbm_set_hip_error(err, "big batch hand-over");
-            q = e->sub[5];
-        }
-        vbm_debug_delay_point(VBM_DP_JOB_BACK, q);
-    }
+    vbm_debug_delay_point(VBM_DP_JOB_BACK, q);
     // a managed stream's reservoirs move in the bitrate manager's choice at the end of the back half: that step (not
     // the front half, not the blobs' passes) waits for the DONE events of the batches this one's streams were in
     auto wait_done = [&]() -> int {
-        if (j.grouped) return 0;
         for (int ww = 0; ww < e->nws; ww++)
             for (int t = 0; t < 4; t++)
                 if (((j.depmask >> (ww * 4 + t)) & 1u) && hipStreamWaitEvent(q, e->ev_done[ww][t], 0) != hipSuccess) return -2;
         return 0;
     };
     if ((rc = launch_back(e, v, q, j.timed, j.d_packets, wait_done))) return rc;
-    if (j.grouped) return VBM_OK;     // the group's caller copies the outputs and records the events
     vbm_debug_delay_point(VBM_DP_JOB_OUT, q);
     if ((rc = round_outputs(e, v, j, q, j.timed))) return rc;
     if ((err = hipEventRecord(e->ev_done[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
@@ -1007,8 +1001,6 @@ static int run_jobs(vbm_encoder *e, const type_job *jobs, int n, bool last_here)
 // The four batches are independent (different streams), so each runs on its own internal HIP stream
 // on a tile-aligned slice of the workspace; a handful of short blocks then costs the round no more
 // than the big long-block batch it runs beside.  Outputs are compact: packet k of the grouped order.
-extern "C" int vbm_analysis_round_join(vbm_encoder *e, void *stream);
-
 // `defer`: the batches are not joined back to `stream`; vbm_analysis_round_join does that.  A deferred round only
 // waits for the batches of the previous round that its own streams were part of (a stream's blocks stay in
 // order), so the few short blocks of one round can run beside the long-block batch of the round before.
@@ -1039,26 +1031,11 @@ static int analysis_round_impl(vbm_encoder *e, const int *counts, const int *str
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipError_t err;
-    const int w = e->next;
-    e->next = (e->next + 1) % e->nws;
-    e->cur = w;
-    if (e->back_pending[w]) {
-        if ((err = hipStreamWaitEvent(st, e->ev_back[w], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-        e->back_pending[w] = false;
-    }
     // the round that last used this workspace has to be done before `st` (and everything forked from it) goes on
-    for (int m = 0; m < 4; m++)
-        if (e->reuse_pending[w][m]) {
-            if ((err = hipStreamWaitEvent(st, e->ev_done[w][m], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-            e->reuse_pending[w][m] = false;
-        }
+    const int w = take_workspace(e, st);
+    if (w < 0) return w;
     if (e->device_rounds) {   // rounds built on the device ran in between: their streams are unknown here
-        for (int ww = 0; ww < e->nws; ww++)
-            for (int t = 0; t < 4; t++)
-                if (e->reuse_pending[ww][t]) {
-                    if ((err = hipStreamWaitEvent(st, e->ev_done[ww][t], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-                    e->reuse_pending[ww][t] = false;
-                }
+        if ((rc = wait_slots(e, st, e->reuse_pending, any_slot, true))) return rc;
         e->device_rounds = false;
     }
     // Which earlier batches do the streams of each batch of this round come from?  bit (ww * 4 + t) of dep[m]:
@@ -1072,19 +1049,14 @@ static int analysis_round_impl(vbm_encoder *e, const int *counts, const int *str
     // ids / flags in the padded lane layout, through the pinned staging (always uploaded: the layout changes
     // from round to round)
     {
-        const int t = e->stage_turn;
-        e->stage_turn ^= 1;
-        (void)hipEventSynchronize(e->ev_stage[t]);
+        const int t = stage_begin(e);
         memset(e->h_ids[t], 0, lanes * sizeof(int));
         memset(e->h_flags[t], 0, lanes);
         for (int m = 0; m < 4; m++) {
             memcpy(e->h_ids[t] + pad[m], stream_ids + off[m], counts[m] * sizeof(int));
             memcpy(e->h_flags[t] + pad[m], wflags + off[m], counts[m]);
         }
-        if ((err = hipMemcpyAsync(e->d_stream_id[w], e->h_ids[t], lanes * sizeof(int), hipMemcpyHostToDevice, st)) != hipSuccess ||
-            (err = hipMemcpyAsync(e->d_wflags[w], e->h_flags[t], lanes, hipMemcpyHostToDevice, st)) != hipSuccess)
-            return vbm_set_hip_error(err, "hipMemcpyAsync(round ids)");
-        (void)hipEventRecord(e->ev_stage[t], st);
+        if ((rc = stage_commit(e, t, w, lanes, st))) return rc;
         e->last_ids[w].clear();
         e->last_flags[w].clear();
     }
@@ -1096,31 +1068,20 @@ static int analysis_round_impl(vbm_encoder *e, const int *counts, const int *str
     // streams with disjoint CU masks (hipExtStreamCreateWithCUMask) — both slower: the single-wavefront
     // kernels of the small batches run several times slower beside the wide kernels of the big batch, so
     // their chains are better run next to each other than one after another.
-    while ((int)e->sub.size() < 6) {      // one per block type + two for a big batch (front / back half)
-        hipStream_t q;
-        hipEvent_t ev;
-        if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return VBM_EHIP;
-        e->sub.push_back(q);
-        e->ev_join.push_back(ev);
-    }
+    if ((rc = grow_sub(e, 6))) return rc;      // one per block type + two for a big batch (front / back half)
     int order[4] = {0, 1, 2, 3};
     for (int a = 0; a < 4; a++)
         for (int c = a + 1; c < 4; c++)
             if (counts[order[c]] > counts[order[a]]) { int t_ = order[a]; order[a] = order[c]; order[c] = t_; }
     // every type on its own HIP stream, enqueued by its own host thread, the smallest first: their threads start while
     // the largest batch is enqueued on the calling thread
-    const bool prof = e->profiling && e->prof_calls < e->prof_max_calls && e->events_used + 2 * (size_t)kNumStages <= e->events.size();
+    const bool prof = prof_gate(e, 2 * (size_t)kNumStages);
     type_job jobs[4];
     int njobs = 0;
     for (int rank = 3; rank >= 0; rank--) {
         const int m = order[rank];
         if (!counts[m]) continue;
-        type_job &j = jobs[njobs++];
-        j.m = m; j.w = w; j.lane0 = pad[m]; j.bound = counts[m]; j.d_nsb = nullptr;
-        j.pcm = d_pcm + (size_t)off[m] * e->ch * s->blocksizes[1];
-        j.d_packets = d_packets ? d_packets + (size_t)off[m] * e->max_packet_bytes : nullptr;
-        j.d_packet_bytes = d_packet_bytes ? d_packet_bytes + off[m] : nullptr;
+        type_job &j = jobs[njobs++] = make_job(e, w, m, pad[m], off[m], counts[m], nullptr, d_pcm, d_packets, d_packet_bytes);
         j.big = counts[m] >= kBigBatch;          // a big batch gets streams of its own (front / back half)
         j.timed = prof && m == order[0];         // stage timing covers the round's largest batch (calling thread)
         j.depmask = dep[m];
@@ -1163,12 +1124,7 @@ int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, 
         e->small_streams_set = true;
         int lo = 0, hi = 0;
         const bool prio = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi < lo;
-        while ((int)e->sub.size() < 6) {
-            e->sub.push_back(nullptr);
-            hipEvent_t ev;
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return VBM_EHIP;
-            e->ev_join.push_back(ev);
-        }
+        if ((rc = grow_sub(e, 6, false))) return rc;
         static const int order[6] = {4, 5, 0, 1, 2, 3};
         for (int k = 0; k < 6; k++) {
             const int m = order[k];
@@ -1185,19 +1141,8 @@ int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, 
             e->sub[m] = q;
         }
     }
-    const int w = e->next;
-    e->next = (e->next + 1) % e->nws;
-    e->cur = w;
-    hipError_t err;
-    if (e->back_pending[w]) {
-        if ((err = hipStreamWaitEvent(fork, e->ev_back[w], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-        e->back_pending[w] = false;
-    }
-    for (int m = 0; m < 4; m++)
-        if (e->reuse_pending[w][m]) {
-            if ((err = hipStreamWaitEvent(fork, e->ev_done[w][m], 0)) != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-            e->reuse_pending[w][m] = false;
-        }
+    const int w = take_workspace(e, fork);
+    if (w < 0) return w;
     e->last_ids[w].clear();
     e->last_flags[w].clear();
     if (!e->d_counts_ws) {
@@ -1215,46 +1160,34 @@ int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, 
     return VBM_OK;
 }
 
-// A group of a round as a graph: `jobs` (grouped type_jobs) forked from and joined to `origin`; several jobs run side
-// by side on sub[job.m].  First use: plain launches (the launchers' one-time set-up runs then); second use: the
-// same calls under a stream capture, instantiated; from then on one hipGraphLaunch.
-static int run_group(vbm_encoder *e, vbm_encoder::round_graph &g, hipStream_t origin, type_job *jobs, int njobs)
+// One piece of a job as a graph on `q`, a linear capture of that stream.  First use: plain launches (the launchers'
+// one-time set-up runs then); second use: the same calls under a stream capture, instantiated; from then on one
+// hipGraphLaunch, with nothing built from the job.
+enum job_piece { kTransforms = 0, kPsy = 1, kBackHalf = 2 };
+static int run_piece(vbm_encoder *e, vbm_encoder::round_graph &g, hipStream_t q, const type_job &j, job_piece piece)
 {
     hipError_t err;
     if (g.exec) {
-        if ((err = hipGraphLaunch(g.exec, origin)) != hipSuccess) return vbm_set_hip_error(err, "hipGraphLaunch");
+        if ((err = hipGraphLaunch(g.exec, q)) != hipSuccess) return vbm_set_hip_error(err, "hipGraphLaunch");
         return VBM_OK;
     }
     const bool capture = g.uses >= 1;
     g.uses++;
-    if (capture && (err = hipStreamBeginCapture(origin, hipStreamCaptureModeThreadLocal)) != hipSuccess)
+    if (capture && (err = hipStreamBeginCapture(q, hipStreamCaptureModeThreadLocal)) != hipSuccess)
         return vbm_set_hip_error(err, "hipStreamBeginCapture");
-    int rc = VBM_OK;
-    if (njobs == 1) {
-        jobs[0].q_on = origin;
-        rc = enqueue_job(e, jobs[0]);
-    } else {
-        if ((err = hipEventRecord(e->ev_cap_fork, origin)) != hipSuccess) rc = vbm_set_hip_error(err, "hipEventRecord");
-        for (int k = 0; k < njobs && !rc; k++) {
-            hipStream_t q = e->sub[jobs[k].m];
-            jobs[k].q_on = q;
-            if ((err = hipStreamWaitEvent(q, e->ev_cap_fork, 0)) != hipSuccess) { rc = vbm_set_hip_error(err, "hipStreamWaitEvent"); break; }
-            rc = enqueue_job(e, jobs[k]);
-            if (rc) break;
-            if ((err = hipEventRecord(e->ev_cap_join[jobs[k].m], q)) != hipSuccess ||
-                (err = hipStreamWaitEvent(origin, e->ev_cap_join[jobs[k].m], 0)) != hipSuccess)
-                rc = vbm_set_hip_error(err, "group join");
-        }
-    }
+    const vbm_batch v = job_batch(e, j);
+    const int rc = piece == kTransforms ? launch_transforms(e, v, q, false)
+                   : piece == kPsy      ? launch_psy(e, v, q, false)
+                                        : launch_back(e, v, q, false, j.d_packets);
     if (capture) {
         hipGraph_t graph = nullptr;
-        err = hipStreamEndCapture(origin, &graph);
+        err = hipStreamEndCapture(q, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (err != hipSuccess) return vbm_set_hip_error(err, "hipStreamEndCapture");
         err = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (err != hipSuccess) { g.exec = nullptr; return vbm_set_hip_error(err, "hipGraphInstantiate"); }
-        if ((err = hipGraphLaunch(g.exec, origin)) != hipSuccess) return vbm_set_hip_error(err, "hipGraphLaunch");
+        if ((err = hipGraphLaunch(g.exec, q)) != hipSuccess) return vbm_set_hip_error(err, "hipGraphLaunch");
     }
     return rc;
 }
@@ -1279,26 +1212,15 @@ static int run_group(vbm_encoder *e, vbm_encoder::round_graph &g, hipStream_t or
 // take from bw[w]: every one an allocation of workspace w alone, none of the carried stream state (vbm_batch::st).
 // Workspace w is free by then: vbm_encoder_device_round_open has made `fork` wait for the done events of every batch
 // that ran in it, before the round was planned, and ev_fork comes after that on the same stream.
-extern "C" void vbm_debug_stamp(hipStream_t st, int tag);   // util_kernels.hip (timing experiments)
 static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, const int *cap, const float *d_blocks,
                                    uint8_t *d_packets, int *d_packet_bytes, bool first_round, hipStream_t fork)
 {
-    const vbm_setup *s = e->hs;
     hipError_t err;
     const int *d_count = e->d_counts_ws + 4 * w;
     if ((err = hipEventRecord(e->ev_fork, fork)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
     e->last_nsb = 0;
     const bool has_big = first_round && cap[3] > 0;
-    auto job_of = [&](int m, int part) {
-        type_job j;
-        j.m = m; j.w = w; j.lane0 = lane0[m]; j.bound = cap[m]; j.d_nsb = d_count + m;
-        j.pcm = d_blocks + (size_t)lane0[m] * e->ch * s->blocksizes[1];
-        j.d_packets = d_packets ? d_packets + (size_t)lane0[m] * e->max_packet_bytes : nullptr;
-        j.d_packet_bytes = d_packet_bytes ? d_packet_bytes + lane0[m] : nullptr;
-        j.big = false; j.timed = false; j.depmask = 0;
-        j.part = part; j.grouped = true;
-        return j;
-    };
+    auto job_of = [&](int m) { return make_job(e, w, m, lane0[m], lane0[m], cap[m], d_count + m, d_blocks, d_packets, d_packet_bytes); };
     // newest state event of every queue before this round: (workspace, type) of the last job on sub[0..3] and of
     // the newest big batch (first round: the previous call's; later rounds: this call's)
     int last_w[4];
@@ -1322,23 +1244,23 @@ static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, cons
         // half of the batch before.  (On sub[3], which carries no job in a first round, they measured no gain:
         // profiles/transforms_ahead.)
         hipStream_t qT = fork, qF = e->sub[4], qB = e->sub[5];
-        type_job jt = job_of(3, 1), jf = job_of(3, 2), jb = job_of(3, 3);
+        const type_job j = job_of(3);
         vbm_debug_delay_point(VBM_DP_DEV_BIG_TRANSFORMS, qT);
-        if ((rc = run_group(e, e->gJ[w][4][0], qT, &jt, 1))) return rc;
+        if ((rc = run_piece(e, e->gJ[w][4][kTransforms], qT, j, kTransforms))) return rc;
         if ((err = hipEventRecord(e->ev_tf_big[w], qT)) != hipSuccess ||
             (err = hipStreamWaitEvent(qF, e->ev_tf_big[w], 0)) != hipSuccess) return vbm_set_hip_error(err, "big batch transforms");
         if ((rc = wait_preds(qF, 3, 4))) return rc;
         vbm_debug_stamp(qF, 10);
         vbm_debug_delay_point(VBM_DP_DEV_BIG_FRONT, qF);
-        if ((rc = run_group(e, e->gJ[w][4][1], qF, &jf, 1))) return rc;
+        if ((rc = run_piece(e, e->gJ[w][4][kPsy], qF, j, kPsy))) return rc;
         vbm_debug_stamp(qF, 11);
         if ((err = hipEventRecord(e->ev_state_big[w], qF)) != hipSuccess ||
             (err = hipStreamWaitEvent(qB, e->ev_state_big[w], 0)) != hipSuccess) return vbm_set_hip_error(err, "big batch hand-over");
         vbm_debug_stamp(qB, 12);
         vbm_debug_delay_point(VBM_DP_DEV_BIG_BACK, qB);
-        if ((rc = run_group(e, e->gJ[w][4][2], qB, &jb, 1))) return rc;
+        if ((rc = run_piece(e, e->gJ[w][4][kBackHalf], qB, j, kBackHalf))) return rc;
         vbm_debug_delay_point(VBM_DP_DEV_OUT, qB);
-        if ((rc = round_outputs(e, job_batch(e, jb), jb, qB, false))) return rc;
+        if ((rc = round_outputs(e, job_batch(e, j), j, qB, false))) return rc;
         vbm_debug_stamp(qB, 13);
         if ((err = hipEventRecord(e->ev_done[w][3], qB)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
         take_slot(e, w, 3, 4);
@@ -1350,19 +1272,19 @@ static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, cons
         // three graphs: the transforms ahead of the state waits, and the state event between the psychoacoustics and
         // the back half: what follows this batch on another stream waits for its front half only (the chain short
         // blocks -> transition -> long blocks of the next call is what the big batch of the next call waits for)
-        type_job jt = job_of(m, 1), j = job_of(m, 2), j2 = job_of(m, 3);
-        jt.few = j.few = j2.few = 1;
+        type_job j = job_of(m);
+        j.few = 1;
         vbm_debug_delay_point(VBM_DP_DEV_SMALL_TRANSFORMS, q);
-        if ((rc = run_group(e, e->gJ[w][m][0], q, &jt, 1))) return rc;
+        if ((rc = run_piece(e, e->gJ[w][m][kTransforms], q, j, kTransforms))) return rc;
         if ((rc = wait_preds(q, m, m))) return rc;
         vbm_debug_stamp(q, 20 + m);
         vbm_debug_delay_point(VBM_DP_DEV_SMALL_FRONT, q);
-        if ((rc = run_group(e, e->gJ[w][m][1], q, &j, 1))) return rc;
+        if ((rc = run_piece(e, e->gJ[w][m][kPsy], q, j, kPsy))) return rc;
         if ((err = hipEventRecord(e->ev_state[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
         vbm_debug_delay_point(VBM_DP_DEV_SMALL_BACK, q);
-        if ((rc = run_group(e, e->gJ[w][m][2], q, &j2, 1))) return rc;
+        if ((rc = run_piece(e, e->gJ[w][m][kBackHalf], q, j, kBackHalf))) return rc;
         vbm_debug_delay_point(VBM_DP_DEV_OUT, q);
-        if ((rc = round_outputs(e, job_batch(e, j2), j2, q, false))) return rc;
+        if ((rc = round_outputs(e, job_batch(e, j), j, q, false))) return rc;
         vbm_debug_stamp(q, 30 + m);
         if ((err = hipEventRecord(e->ev_done[w][m], q)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
         take_slot(e, w, m, m);
@@ -1380,6 +1302,7 @@ int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const 
 {
     const vbm_setup *s = e->hs;
     hipError_t err;
+    int rc;
     for (int m = 0; m < 4; m++)
         if (cap[m] < 0 || (lane0[m] & 63) || lane0[m] + cap[m] > e->Ls || (cap[m] && s->modes < 2 && (m >> 1))) return VBM_EINVAL;
     if (d_count != e->d_counts_ws + 4 * w) return VBM_EINVAL;
@@ -1387,11 +1310,10 @@ int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const 
     // chosen packets straight to the caller's buffers, which change from call to call: plain launches as well.
     const int mode = (!e->profiling && !s->managed) ? 1 : 2;
     if (e->device_mode && e->device_mode != mode) {
-        // the two ways use different internal streams: everything in flight is waited for at the switch
-        for (int ww = 0; ww < e->nws; ww++)
-            for (int t = 0; t < 4; t++)
-                if (e->reuse_pending[ww][t] && (err = hipStreamWaitEvent(fork, e->ev_done[ww][t], 0)) != hipSuccess)
-                    return vbm_set_hip_error(err, "hipStreamWaitEvent");
+        // The two ways use different internal streams: everything in flight is waited for at the switch.  The flags
+        // stay: a set flag only costs a later wait for an event that has fired by then, and the plain form's depmask
+        // below is built from them (its jobs keep the state waits they would have had without the switch).
+        if ((rc = wait_slots(e, fork, e->reuse_pending, any_slot, false))) return rc;
     }
     e->device_mode = mode;
     if (mode == 1) return device_round_run_graphs(e, w, lane0, cap, d_blocks, d_packets, d_packet_bytes, first_round, fork);
@@ -1402,24 +1324,19 @@ int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const 
     for (int ww = 0; ww < e->nws; ww++)
         for (int t = 0; t < 4; t++)
             if (ww != w && e->reuse_pending[ww][t]) depmask |= 1u << (ww * 4 + t);
-    const bool prof = e->profiling && e->prof_calls < e->prof_max_calls && e->events_used + 2 * (size_t)kNumStages <= e->events.size();
+    const bool prof = prof_gate(e, 2 * (size_t)kNumStages);
     // types 0-2 on host threads of their own, the long blocks on the calling thread
     type_job jobs[4];
     int njobs = 0;
     for (int m = 0; m < 4; m++) {
         if (!cap[m]) continue;
-        type_job &j = jobs[njobs++];
-        j.m = m; j.w = w; j.lane0 = lane0[m]; j.bound = cap[m]; j.d_nsb = d_count + m;
-        j.pcm = d_blocks + (size_t)lane0[m] * e->ch * s->blocksizes[1];
-        j.d_packets = d_packets ? d_packets + (size_t)lane0[m] * e->max_packet_bytes : nullptr;
-        j.d_packet_bytes = d_packet_bytes ? d_packet_bytes + lane0[m] : nullptr;
+        type_job &j = jobs[njobs++] = make_job(e, w, m, lane0[m], lane0[m], cap[m], d_count + m, d_blocks, d_packets, d_packet_bytes);
         j.big = m == 3 && first_round;
         j.timed = prof && m == 3 && first_round;
         // (short blocks never follow a type-3 block directly: no wait for the newest big batch)
         j.depmask = (m < 2 && e->call_big_w >= 0) ? depmask & ~(1u << (e->call_big_w * 4 + 3)) : depmask;
     }
-    int rc = run_jobs(e, jobs, njobs, cap[3] > 0);
-    if (rc) return rc;
+    if ((rc = run_jobs(e, jobs, njobs, cap[3] > 0))) return rc;
     if (prof && first_round) e->prof_calls++;
     if (first_round) { e->call_big_w = w; e->lazy_w = w; e->lazy_m = 3; }
     e->round_w = w;
@@ -1444,15 +1361,7 @@ extern "C" int vbm_analysis_round_begin(vbm_encoder *e, const int *counts, const
 // `stream` waits for every batch of the rounds begun so far
 extern "C" int vbm_analysis_round_join(vbm_encoder *e, void *stream)
 {
-    if (!e) return VBM_EINVAL;
-    for (int w = 0; w < e->nws; w++)
-        for (int m = 0; m < 4; m++)
-            if (e->done_pending[w][m]) {
-                hipError_t err = hipStreamWaitEvent((hipStream_t)stream, e->ev_done[w][m], 0);
-                if (err != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-                e->done_pending[w][m] = false;
-            }
-    return VBM_OK;
+    return e ? wait_slots(e, (hipStream_t)stream, e->done_pending, any_slot, true) : VBM_EINVAL;
 }
 
 // like vbm_analysis_round_join, but the newest big batch and the batches of the newest round stay pending: a later
@@ -1462,29 +1371,15 @@ extern "C" int vbm_analysis_round_join(vbm_encoder *e, void *stream)
 extern "C" int vbm_analysis_round_join_lazy(vbm_encoder *e, void *stream)
 {
     if (!e) return VBM_EINVAL;
-    for (int w = 0; w < e->nws; w++)
-        for (int m = 0; m < 4; m++)
-            if (e->done_pending[w][m] && !(w == e->lazy_w && m == e->lazy_m) && w != e->round_w) {
-                hipError_t err = hipStreamWaitEvent((hipStream_t)stream, e->ev_done[w][m], 0);
-                if (err != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-                e->done_pending[w][m] = false;
-            }
-    return VBM_OK;
+    auto joined_now = [e](int w, int m) { return !(w == e->lazy_w && m == e->lazy_m) && w != e->round_w; };
+    return wait_slots(e, (hipStream_t)stream, e->done_pending, joined_now, true);
 }
 
 // `stream` waits until the workspace the next round will use is free (buffers handed to that round may then
 // be rewritten on `stream`)
 extern "C" int vbm_analysis_round_wait_workspace(vbm_encoder *e, void *stream)
 {
-    if (!e) return VBM_EINVAL;
-    const int w = e->next;
-    for (int m = 0; m < 4; m++)
-        if (e->reuse_pending[w][m]) {
-            hipError_t err = hipStreamWaitEvent((hipStream_t)stream, e->ev_done[w][m], 0);
-            if (err != hipSuccess) return vbm_set_hip_error(err, "hipStreamWaitEvent");
-            e->reuse_pending[w][m] = false;
-        }
-    return VBM_OK;
+    return e ? wait_slots(e, (hipStream_t)stream, e->reuse_pending, slots_of{e->next}, true) : VBM_EINVAL;
 }
 
 // Test instrumentation: every scratch array of workspace w (-1: all) is filled with `byte` while the device is idle.
@@ -1510,9 +1405,8 @@ extern "C" int vbm_encoder_profile_begin(vbm_encoder *e, int max_calls)
     if (!e || max_calls <= 0) return VBM_EINVAL;
     size_t need = (size_t)max_calls * 2 * (kFront + (size_t)e->nsplit * kBack);
     while (e->events.size() < need) {
-        hipEvent_t ev;
-        hipError_t err = hipEventCreate(&ev);
-        if (err != hipSuccess) return vbm_set_hip_error(err, "hipEventCreate");
+        hipEvent_t ev = new_event(e, hipEventDefault);
+        if (!ev) return VBM_EHIP;
         e->events.push_back(ev);
     }
     e->events_used = 0;

@@ -14,21 +14,9 @@
 #include "setup_host.h"
 #include "frontend.h"
 #include "frontend_kernels.h"
-extern "C" void vbm_debug_stamp(hipStream_t st, int tag);   // util_kernels.hip (timing experiments)
 #include "mdct_kernel.h"
 #include "kernels.h"
 #include "vbm_internal.h"
-
-vbm_setup_host *vbm_encoder_setup_host(vbm_encoder *e);
-vbm_setup_host *vbm_setup_handle_host(vbm_setup_handle *h);
-int vbm_encoder_streams(const vbm_encoder *e);
-int vbm_encoder_workspaces(const vbm_encoder *e);
-int vbm_encoder_reset_streams_dev(vbm_encoder *e, const int *d_ids, int n, hipStream_t q);
-int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, int **d_stream_id, uint8_t **d_wflags, int *lanes,
-                                  int **d_counts);
-int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const int *cap, const int *d_count,
-                                 const float *d_blocks, uint8_t *d_packets, int *d_packet_bytes, bool first_round,
-                                 hipStream_t fork);
 
 struct vbm_frontend {
     vbm_encoder *enc;

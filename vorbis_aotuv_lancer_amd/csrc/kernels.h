@@ -4,6 +4,7 @@
 #include "batch.h"
 
 extern "C" {
+int vbm_launch_spread_flags(const vbm_batch *b, hipStream_t st);   // util_kernels.hip: wflags -> wflags_cb
 int vbm_launch_transpose_in(const vbm_batch *b, hipStream_t st);   // mdct_bm -> mdctT
 int vbm_launch_prologue(const vbm_batch *b, hipStream_t st);
 int vbm_launch_noisemask(const vbm_batch *b, hipStream_t st);

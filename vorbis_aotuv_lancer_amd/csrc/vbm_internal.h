@@ -6,6 +6,22 @@
 extern thread_local std::string g_vbm_err;
 int vbm_set_hip_error(hipError_t e, const char *where);
 
+// what the translation units use of each other's objects
+struct vbm_setup_handle;
+struct vbm_setup_host;
+struct vbm_encoder;
+vbm_setup_host *vbm_setup_handle_host(vbm_setup_handle *h);        // capi_setup.cpp
+vbm_setup_host *vbm_encoder_setup_host(vbm_encoder *e);            // capi_encoder.cpp, for the stream front end
+int vbm_encoder_streams(const vbm_encoder *e);
+int vbm_encoder_workspaces(const vbm_encoder *e);
+int vbm_encoder_reset_streams_dev(vbm_encoder *e, const int *d_ids, int n, hipStream_t q);
+int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, int **d_stream_id, uint8_t **d_wflags, int *lanes,
+                                  int **d_counts);
+int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const int *cap, const int *d_count,
+                                 const float *d_blocks, uint8_t *d_packets, int *d_packet_bytes, bool first_round,
+                                 hipStream_t fork);
+extern "C" void vbm_debug_stamp(hipStream_t st, int tag);          // util_kernels.hip (timing experiments, VBM_DEBUG_STAMPS)
+
 // test instrumentation (debug_hooks.hip): a spin kernel on `q` when `point` is in the mask of vbm_debug_set_delay
 enum vbm_delay_point {
     VBM_DP_JOB_BIG = 0,        // host-built round: before the first kernel of a big batch (its own front stream)
