@@ -491,6 +491,62 @@ int vbm_ogg_chain_status(vbm_ogg_chain *ch, int *status, void *stream);
 int vbm_host_ogg_chain_split(vbm_ogg_chain *ch, int nfiles, const uint8_t *data, const long long *file_offsets,
                              long long *file_links, long long *link_offsets, long long link_cap);
 
+/* ---- Ogg stream selection: the Vorbis stream of multiplexed files, for many files per call, on the device -------------
+ * A multiplexed file carries the pages of several logical streams interleaved (.ogv: Theora beside Vorbis; Skeleton,
+ * Kate or CMML tracks beside the audio), and the calls above take one stream per file.  A selection copies, for each of
+ * `nfiles` files, file f in d_data[file_offsets[f], file_offsets[f+1]) as above, the pages of its Vorbis stream to
+ * d_out and drops the rest, so that what comes out is a plain Vorbis file, or a plain chained one for
+ * vbm_ogg_chain_split.  Pages are copied whole: CRCs, page numbers and granule positions stay as they are.  The rule
+ * (csrc/ogg_select.h), page after page with the parse test and the stops of the chain split: a page is a head page if it
+ * carries the beginning-of-stream flag or is the file's first; a head page behind a page that is none starts a new group
+ * (a chain boundary), in which nothing is chosen yet; the first head page of a group whose body begins with the 7 bytes
+ * 01 "vorbis" chooses its serial number for the group; a page is kept if and only if a stream is chosen and the page
+ * carries its serial number.  At a stop the rest of the file is kept if a stream is chosen there.  So the first Vorbis
+ * stream of a group wins (as in the reference's vorbisfile.c), a group without one keeps nothing, and a plain Vorbis
+ * file or chain comes out byte for byte as it went in.  The selection never fails and never judges: CRC, page sequence,
+ * continuation flags and header packets stay with the demux.  There is no resync, and nothing outside a file's range is
+ * read for it.
+ *   vbm_ogg_select_create   workspace on the current device for calls of up to max_files files that span up to max_bytes
+ *                           bytes: about 0.9 * max_bytes + 24 * max_files bytes.  vbm_host_ogg_select_create: the same
+ *                           in host memory for vbm_host_ogg_select, touches no device.
+ *   vbm_ogg_select          d_out_offsets [nfiles + 1]: the exclusive sums of the files' kept bytes from 0 on, so the
+ *                           output of file f is d_out[d_out_offsets[f], d_out_offsets[f+1]) and d_out_offsets[nfiles] =
+ *                           total; with d_out as d_data it is a valid file_offsets of vbm_ogg_chain_split and
+ *                           vbm_ogg_demux_scan.  d_info [nfiles]: one record per file.  Both are ALWAYS written.  d_out,
+ *                           of capacity out_cap bytes: the size of the input, file_offsets[nfiles] - file_offsets[0],
+ *                           always suffices.  It must not overlap the files: the selection is not done in place.  When
+ *                           total > out_cap NOTHING is written to d_out and the status word becomes
+ *                           VBM_OGG_DEMUX_ECAP (0 after a selection that wrote it).  The outputs are device memory;
+ *                           file_offsets is host memory and is free on return.
+ *   vbm_ogg_select_status   the status word of the last selection -> *status (host memory); waits for `stream`, on
+ *                           which that selection must have been enqueued.
+ * select allocates nothing, reads nothing back and only enqueues on `stream`; its one wait is for the pinned slot that
+ * carried the file offsets two calls earlier.  VBM_EINVAL, with nothing enqueued: nfiles negative or above max_files, a
+ * negative or decreasing offset, a span above max_bytes, a null pointer (d_data may be null when the span is 0, d_out
+ * when out_cap is 0, d_info when nfiles is 0), a negative out_cap, an output that overlaps the files, a host object in
+ * a device call or the other way round.
+ *   vbm_host_ogg_select     the same source on the CPU with host pointers and a host object.
+ * VBM_OGG_SELECT_CHUNK: the bytes of d_out that one block of the copy kernel writes (its grid is sized from the input). */
+#define VBM_OGG_SELECT_CHUNK 16384
+typedef struct {
+    long long kept_bytes;       /* bytes of the file that are kept: pages, and the tail behind a stop */
+    long long kept_pages;       /* pages kept */
+    long long foreign_pages;    /* pages dropped */
+    int streams;                /* groups in which a Vorbis stream was chosen; 0: the file has none and keeps nothing */
+    int foreign_streams;        /* head pages that were dropped */
+    uint32_t first_serial;      /* serial number of the first chosen stream (0 without one) */
+    int reserved;               /* 0 */
+} vbm_ogg_select_info;
+typedef struct vbm_ogg_selector vbm_ogg_selector;
+int vbm_ogg_select_create(vbm_ogg_selector **sel, int max_files, long long max_bytes);
+int vbm_host_ogg_select_create(vbm_ogg_selector **sel, int max_files, long long max_bytes);
+void vbm_ogg_select_destroy(vbm_ogg_selector *sel);
+int vbm_ogg_select(vbm_ogg_selector *sel, int nfiles, const uint8_t *d_data, const long long *file_offsets, uint8_t *d_out,
+                   long long out_cap, long long *d_out_offsets, vbm_ogg_select_info *d_info, void *stream);
+int vbm_ogg_select_status(vbm_ogg_selector *sel, int *status, void *stream);
+int vbm_host_ogg_select(vbm_ogg_selector *sel, int nfiles, const uint8_t *data, const long long *file_offsets, uint8_t *out,
+                        long long out_cap, long long *out_offsets, vbm_ogg_select_info *info);
+
 /* ---- Ogg demux, incremental form: the next bytes of many live streams per call, on the device -----------------------
  * A feed holds max_streams stream slots.  Every call takes, for each slot of a list, a chunk of bytes of any length (0
  * included) cut anywhere, and returns the audio packets those bytes completed, as ONE CSR grouped by stream in list

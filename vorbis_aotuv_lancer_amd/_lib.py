@@ -160,6 +160,14 @@ SIGNATURES = {
     "vbm_ogg_chain_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "vbm_host_ogg_chain_split": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_longlong]),
+    "vbm_ogg_select_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_longlong]),
+    "vbm_host_ogg_select_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_longlong]),
+    "vbm_ogg_select_destroy": (None, [C.c_void_p]),
+    "vbm_ogg_select": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+    "vbm_ogg_select_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    "vbm_host_ogg_select": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                      C.c_void_p]),
     "vbm_host_ogg_demux_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_longlong]),
     "vbm_ogg_feed_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int]),

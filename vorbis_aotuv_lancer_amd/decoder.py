@@ -405,10 +405,26 @@ def _demux_host(name, blob):
         raise VbmError(f"{name}: {e}") from None
 
 
+NO_VORBIS = "no Vorbis stream was found among its pages"
+
+
+def _select_host(name, blob):
+    """select_vorbis_stream of one file, the Vorbis stream's pages alone; VbmError under the file's name without one"""
+    from .stream import select_vorbis_stream
+    out = select_vorbis_stream(blob)
+    if not out:                                           # the chosen page is kept: nothing kept, nothing chosen
+        raise VbmError(f"{name}: {NO_VORBIS}")
+    return out
+
+
 def _raise_failed(batch, names):
     """VbmError for the first failed entry of a device-demuxed batch"""
-    for name, code in zip(names, batch.status):
+    for i, (name, code) in enumerate(zip(names, batch.status)):
         if code:
+            if batch.select_info is not None:
+                f = int(np.searchsorted(batch.file_links, i, side="right")) - 1    # the given file of entry i
+                if batch.select_info["streams"][f] == 0:
+                    raise VbmError(f"{name}: {NO_VORBIS} (vbm_ogg_demux_scan failed with code {code} on the empty entry)")
             raise VbmError(f"{name}: vbm_ogg_demux_scan failed with code {code}: not one valid logical Ogg stream "
                            "(vbm_ogg_demux on the file alone names the page)")
 
@@ -423,9 +439,11 @@ class OggIndex:
     (decode_ogg(files, halfrate=True)'s).  device_demux=True: the files are demuxed together on the device
     (stream.demux_ogg_device) and the store and its index are built there from the demuxed batch
     (RangeStore.from_device) instead of file by file on the host; the index and every range are the same bit for
-    bit."""
+    bit.  multiplexed=True: the files may carry other streams beside the Vorbis one (stream.StreamSelector on the
+    device with device_demux, stream.select_vorbis_stream on the host without); a file without a Vorbis stream is a
+    VbmError that says so."""
 
-    def __init__(self, files, max_batch=4096, halfrate=False, device_demux=False):
+    def __init__(self, files, max_batch=4096, halfrate=False, device_demux=False, multiplexed=False):
         from .stream import _read_files, demux_ogg_device
         if max_batch < 2:
             raise ValueError("max_batch must be at least 2")
@@ -433,10 +451,11 @@ class OggIndex:
         if not blobs:
             raise ValueError("OggIndex needs at least one file")
         if device_demux:
-            b = demux_ogg_device(blobs)
+            b = demux_ogg_device(blobs, multiplexed=multiplexed)
             _raise_failed(b, names)
         else:
-            demuxed = [_demux_host(name, blob) for name, blob in zip(names, blobs)]
+            demuxed = [_demux_host(name, _select_host(name, blob) if multiplexed else blob)
+                       for name, blob in zip(names, blobs)]
         self._open(b.headers if device_demux else [d[0] for d in demuxed], max_batch, halfrate)
         self.store = (RangeStore.from_device(self.decoder, b) if device_demux
                       else RangeStore(self.decoder, [d[1:] for d in demuxed]))
@@ -466,13 +485,13 @@ class OggIndex:
         self.setup.close()
 
 
-def _demux_files(files, device_demux, chained):
+def _demux_files(files, device_demux, chained, multiplexed=False):
     """decode_ogg's demux -> (names, entries, file_links): entry i, a file or with chained a link, is (headers, data,
     offsets, granulepos, eos) as demux_ogg's, offsets a numpy array and the rest where the demux left them (CUDA tensors
     or numpy arrays); file f is entries file_links[f] .. file_links[f + 1] - 1"""
     from .stream import _read_files, demux_ogg_device, split_ogg_chain
     if device_demux:
-        b = demux_ogg_device(files, chained=chained)
+        b = demux_ogg_device(files, chained=chained, multiplexed=multiplexed)
         _raise_failed(b, b.names)
         offsets, entries = b.offsets.cpu().numpy(), []
         for i in range(len(b)):
@@ -482,6 +501,8 @@ def _demux_files(files, device_demux, chained):
         return b.names, entries, b.file_links
     names, entries, file_links = [], [], [0]
     for name, blob in zip(*_read_files(files)):
+        if multiplexed:
+            blob = _select_host(name, blob)
         links = [(f"{name} link {k}", link) for k, link in enumerate(split_ogg_chain(blob))] if chained else [(name, blob)]
         for entry, link in links:
             names.append(entry)
@@ -520,7 +541,7 @@ def _calls(src, max_packets):
         yield ids, counts, torch.cat(datas), np.concatenate(offs), torch.cat(gps), torch.cat(eoss)
 
 
-def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chained=False):
+def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chained=False, multiplexed=False):
     """.ogg files (bytes or paths), one logical stream each -> [(pcm float32 [channels, n] contiguous on the current
     device, rate)], one per file.  Files whose identification and setup headers are byte-equal share one DecodeSetup
     and Decoder, one stream per file; their packets go through synthesis_runs in calls of at most max_packets rows.
@@ -532,11 +553,15 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
     chained=True: the files may be chained (stream.split_ogg_chain, csrc/ogg_chain.h), and the result is one list per
     file of (pcm, rate), one per link in file order.  Every link decodes as the file it would be alone: its own
     headers, fresh overlap state, its own granule positions; links and files with byte-equal identification and setup
-    headers share a decoder.  A link that is not one valid logical stream raises VbmError naming file and link."""
+    headers share a decoder.  A link that is not one valid logical stream raises VbmError naming file and link.
+    multiplexed=True: the files may carry other streams beside the Vorbis one (Theora, Skeleton, Kate ...); the first
+    Vorbis stream of a file, or with chained of each of its links, is decoded and the rest is ignored, as the
+    reference's vorbisfile.c does (csrc/ogg_select.h; on the device with device_demux, stream.select_vorbis_stream on the
+    host without).  A file without a Vorbis stream raises VbmError saying so."""
     if max_packets <= 0:
         raise ValueError("max_packets must be positive")
     dev = torch.device("cuda", torch.cuda.current_device())
-    names, demuxed, file_links = _demux_files(files, device_demux, chained)
+    names, demuxed, file_links = _demux_files(files, device_demux, chained, multiplexed)
     groups = {}
     for i, d in enumerate(demuxed):
         groups.setdefault((d[0][0], d[0][2]), []).append(i)

@@ -386,10 +386,13 @@ class DemuxBatch:
     payload[offsets[packet_base[f] + k]:offsets[packet_base[f] + k + 1]], with packets[f] of them.  runs(f) is that
     file's slice in the form Decoder.synthesis_runs takes.  From demux_ogg_device(chained=True) the entries ("files"
     above) are the links of the files given, named "<file> link k": file_links int64 [given files + 1] counts them, and
-    links(f) is the range of entries of given file f.  Otherwise every file is its own one entry."""
+    links(f) is the range of entries of given file f.  Otherwise every file is its own one entry.  From
+    demux_ogg_device(multiplexed=True) select_info holds one SELECT_INFO record per given file (vbm_ogg_select_info);
+    None otherwise."""
 
     def __init__(self, names, info, headers, payload, offsets, granulepos, eos, file_links=None):
         self.names, self.info, self.headers = names, info, headers
+        self.select_info = None
         self.file_links = np.arange(len(names) + 1, dtype=np.int64) if file_links is None else file_links
         self.payload, self.offsets, self.granulepos, self.eos = payload, offsets, granulepos, eos
         self.status = info["status"].tolist()
@@ -533,32 +536,109 @@ def split_ogg_chain(data):
     return [raw[int(a):int(b)] for a, b in zip(lo[:-1], lo[1:])]
 
 
-def demux_ogg_device(files, host=False, chained=False):
+SELECT_INFO = np.dtype([("kept_bytes", "<i8"), ("kept_pages", "<i8"), ("foreign_pages", "<i8"), ("streams", "<i4"),
+                        ("foreign_streams", "<i4"), ("first_serial", "<u4"), ("reserved", "<i4")])   # vbm_ogg_select_info
+
+
+class StreamSelector(_TwinHandle):
+    """The Vorbis stream of multiplexed .ogg files (Theora, Skeleton, Kate ... pages between the audio's), for up to
+    max_files files of up to max_bytes bytes together per select() call, on the device (vbm_ogg_select; the rule:
+    csrc/ogg_select.h): the pages of the first Vorbis stream of every group are copied, whole and in order, to a second
+    buffer and the rest is dropped, so that what comes out is a plain Vorbis file (or a plain chain) for DeviceDemuxer
+    and ChainSplitter.  host=True runs the CPU twin on numpy arrays (no GPU needed).  The selection never fails: a file
+    without a Vorbis stream comes out empty (info["streams"] == 0), for the demux to reject."""
+
+    CHUNK = 16384       # VBM_OGG_SELECT_CHUNK: the output bytes one block of the copy kernel writes
+
+    def __init__(self, max_files, max_bytes, host=False, device=None):
+        self.max_files, self.max_bytes = int(max_files), int(max_bytes)
+        super().__init__("select", host, device, self.max_files, self.max_bytes)
+
+    def select(self, raw, off):
+        """raw uint8 (a tensor on the device; a numpy array with host=True), file f in raw[off[f]:off[f + 1]], off int64
+        numpy [n + 1] -> (out_raw, out_off, info): out_raw uint8 where raw is, the kept bytes of file f in
+        out_raw[out_off[f]:out_off[f + 1]]; out_off int64 [n + 1] and info (SELECT_INFO [n]) on the host, brought back
+        in one small D2H.  raw is free once the work enqueued here is done (the device form only enqueues it)."""
+        off = np.ascontiguousarray(off, np.int64)
+        n = len(off) - 1
+        cap = int(off[n] - off[0])                       # the input's size always suffices: the status stays 0
+        nb = 8 * (n + 1)
+        if self.host:
+            out, meta = np.zeros(cap, np.uint8), np.zeros(nb + n * SELECT_INFO.itemsize, np.uint8)
+            check(lib.vbm_host_ogg_select(self._h, n, raw.ctypes.data if len(raw) else None, off.ctypes.data,
+                                          out.ctypes.data if cap else None, cap, meta.ctypes.data,
+                                          meta.ctypes.data + nb if n else None), "vbm_host_ogg_select")
+        else:
+            import torch
+            out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+            d_meta = torch.empty(nb + n * SELECT_INFO.itemsize, dtype=torch.uint8, device=self.device)
+            check(lib.vbm_ogg_select(self._h, n, raw.data_ptr() if len(raw) else None, off.ctypes.data,
+                                     out.data_ptr() if cap else None, cap, d_meta.data_ptr(),
+                                     d_meta.data_ptr() + nb if n else None, self._q()), "vbm_ogg_select")
+            meta = d_meta.cpu().numpy()
+        out_off, info = meta[:nb].view(np.int64).copy(), meta[nb:].view(SELECT_INFO).copy()
+        return out[:int(out_off[n])], out_off, info
+
+
+def select_vorbis_stream(data):
+    """.ogg bytes of one file -> bytes: the pages of its Vorbis stream alone (csrc/ogg_select.h), the first one of every
+    group of a chained file; a plain Vorbis file comes back as it is, and a file without a Vorbis stream as b"".  On the
+    host; needs no GPU.  The selection never fails: what it returns is judged when it is demuxed (demux_ogg)."""
+    raw = bytes(data)
+    sel = StreamSelector(1, len(raw), host=True)
+    try:
+        out, _, _ = sel.select(np.frombuffer(raw, np.uint8), np.array([0, len(raw)], np.int64))
+    finally:
+        sel.close()
+    return out.tobytes()
+
+
+def demux_ogg_device(files, host=False, chained=False, multiplexed=False):
     """.ogg files (bytes or paths) -> DemuxBatch, through a DeviceDemuxer made for them (host=True: its CPU twin).
     chained=True: the files may be chained.  After the one upload a ChainSplitter finds their links, one small D2H brings
     the link offsets back, and the demuxer runs over the same buffer with the links as its files: the batch's entries
-    are the links, b.links(f) those of file f, each judged alone (a bad link fails alone)."""
+    are the links, b.links(f) those of file f, each judged alone (a bad link fails alone).
+    multiplexed=True: the files may carry other streams beside the Vorbis one.  After the upload a StreamSelector copies
+    the Vorbis pages of every file to a second device buffer, one small D2H brings the new file offsets and the records
+    b.select_info (SELECT_INFO, one per given file) back, and the split and the demux run over that buffer.  A file
+    without a Vorbis stream is an empty entry, which fails as one (VBM_EOGG)."""
     names, blobs = _read_files(files)
     nbytes = sum(len(b) for b in blobs)
-    if not chained:
+    if not chained and not multiplexed:
         dm = DeviceDemuxer(max(1, len(blobs)), nbytes, host=host)
         try:
             return dm.demux(blobs)
         finally:
             dm.close()
-    sp = ChainSplitter(max(1, len(blobs)), nbytes, host=host)
+    device, select_info, file_links = None, None, None
+    raw = None
+    if multiplexed:
+        sel = StreamSelector(max(1, len(blobs)), nbytes, host=host)
+        try:
+            device = sel.device
+            raw, off = _join(blobs, device)
+            raw, off, select_info = sel.select(raw, off)     # the D2H waits for the copy: the upload is free after it
+        finally:
+            sel.close()
+    entry_names, entry_off = names, None if raw is None else off
+    if chained:
+        sp = ChainSplitter(max(1, len(blobs)), nbytes, host=host, device=device)
+        try:
+            device = sp.device
+            if raw is None:
+                raw, off = _join(blobs, device)
+            file_links, entry_off = sp.split(raw, off)
+        finally:
+            sp.close()
+        entry_names = [f"{names[f]} link {k}" for f in range(len(blobs)) for k in range(int(file_links[f + 1] - file_links[f]))]
+    dm = DeviceDemuxer(max(1, len(entry_names)), nbytes, host=host, device=device)
     try:
-        raw, off = _join(blobs, sp.device)
-        file_links, link_off = sp.split(raw, off)
-    finally:
-        sp.close()
-    link_names = [f"{names[f]} link {k}" for f in range(len(blobs)) for k in range(int(file_links[f + 1] - file_links[f]))]
-    dm = DeviceDemuxer(max(1, len(link_names)), nbytes, host=host, device=sp.device)
-    try:
-        b = dm.demux_joined(link_names, raw, link_off)
+        b = dm.demux_joined(entry_names, raw, entry_off)
     finally:
         dm.close()
-    b.file_links = file_links
+    if chained:
+        b.file_links = file_links
+    b.select_info = select_info
     return b
 
 
