@@ -967,6 +967,67 @@ int  vbm_synthesis_ranges(vbm_decoder *dec, const vbm_range_store *st, int nrang
  * d_out NULL: only *rows (values per channel row, 4 for "info") and *kind ('i' / 'f') are returned. */
 int  vbm_decoder_fetch(vbm_decoder *dec, const char *name, void *d_out, long *rows, char *kind, void *stream);
 
+/* ---- Ogg cut: sample windows of a range store's streams as new Ogg Vorbis files, no packet decoded or re-encoded -------
+ * Range r is stream stream_ids[r] of the store, start starts[r] >= 0, length lengths[r] >= 0 in the store's output
+ * samples (host arrays; ranges may repeat and overlap).  Output r is a whole Ogg Vorbis file whose decode is the window:
+ * the range's header pages as given, then the store's packets pre .. m unchanged (the packets vbm_synthesis_ranges would
+ * decode for the window, pre-roll included), paged and given granule positions so that a Vorbis decoder drops the samples
+ * in front of the start and stops at the end (csrc/ogg_cut.h has the rule; reference lib/block.c:1084-1157 is what the
+ * decoder does with it).  Both ends are exact, except for a window inside ONE packet: its start moves back to that
+ * packet's first sample.  got_starts[r], got_lengths[r] (host): the window the file holds, got_lengths[r] =
+ * clamp(total - start, 0, length) (+ the move); 0 gives an empty output, status 0.
+ *   vbm_ogg_cut_create      workspace on the current device for calls of up to max_ranges ranges, max_out_bytes output
+ *                           bytes and max_header_bytes of header page sets: about 0.17 * max_out_bytes + 250 * max_ranges +
+ *                           3 * max_header_bytes bytes (two thirds of the last pinned host memory).
+ *                           vbm_host_ogg_cut_create: the same in host memory for vbm_host_ogg_cut_ranges, no device.
+ *   vbm_ogg_cut_ranges      header_pages[header_offsets[e], header_offsets[e + 1]), e < nheaders (host,
+ *                           header_offsets[0] = 0): sets of whole Ogg pages as the host writer makes them of a stream's
+ *                           three header packets (vbm_ogg_stream_*: the identification packet alone on the first page,
+ *                           a flush behind the third packet), under any serial number.  Output r opens with set
+ *                           header_ids[r] (NULL: r), so the cuts of one source file share one set; serialnos[r] (NULL:
+ *                           r) is written into its pages and each page's CRC corrected, which gives the pages the
+ *                           writer makes under that serial number.  The audio pages carry the same serial number and
+ *                           page numbers that run on from the header pages.  A set that no non-empty output uses is
+ *                           only checked for whole pages.
+ *                           d_out_offsets [nranges + 1]: exclusive sums of the output sizes, output r is
+ *                           d_out[d_out_offsets[r], d_out_offsets[r + 1]).  d_status [nranges + 1]: per range 0 or
+ *                           VBM_OGG_CUT_ESHAPE (refused: the output is empty, and its length counts as 0 whatever
+ *                           got_lengths[r] says: the refusal is found on the device); d_status[nranges] is the call's
+ *                           status word.  Both are ALWAYS written.  When the total exceeds out_cap (0 is allowed, and
+ *                           asks for the sizes) NOTHING is written to d_out and the status word is VBM_OGG_CUT_ECAP.
+ *                           Refused: packets pre .. k that do not fit one page, a packet behind k (or k itself when the
+ *                           window lies inside it) whose start the source trimmed, offsets that are no CSR inside the
+ *                           store's data (csrc/ogg_cut.h (a) - (d)).  A store with e_o_s in front of a stream's last
+ *                           packet is not covered.
+ * cut_ranges allocates no device or pinned memory, reads nothing back and only enqueues on `stream`; its one wait is for the pinned slot that
+ * carried the arguments two calls earlier.  VBM_EINVAL, with nothing enqueued: a stream id out of range, a negative
+ * start or length, nranges negative or above max_ranges, out_cap negative or above max_out_bytes, header pages above
+ * max_header_bytes or not whole pages, decreasing header_offsets, a header id out of range, a null pointer, an output that overlaps the store's
+ * data, a half-rate store (its positions are not packet granule positions), a host object in a device call or the other
+ * way round.
+ *   vbm_host_ogg_cut_ranges the same source on the CPU.  The index comes as plain host arrays (first [nstreams + 1]; status,
+ *                           begin, out_end [P]; totals [nstreams]; data, offsets [P + 1]): neither a device nor a packet
+ *                           that decodes is needed.  It knows the refusals and writes got_lengths[r] = 0 for them. */
+#define VBM_OGG_CUT_ECAP   VBM_OGG_DEMUX_ECAP
+#define VBM_OGG_CUT_ESHAPE 2
+typedef struct vbm_ogg_cutter vbm_ogg_cutter;
+int  vbm_ogg_cut_create(vbm_ogg_cutter **cut, int max_ranges, long long max_out_bytes, long long max_header_bytes);
+int  vbm_host_ogg_cut_create(vbm_ogg_cutter **cut, int max_ranges, long long max_out_bytes, long long max_header_bytes);
+void vbm_ogg_cut_destroy(vbm_ogg_cutter *cut);
+int  vbm_ogg_cut_ranges(vbm_ogg_cutter *cut, const vbm_range_store *st, int nranges, const int *stream_ids,
+                        const long long *starts, const long long *lengths, const int *serialnos, int nheaders,
+                        const uint8_t *header_pages, const long long *header_offsets, const int *header_ids,
+                        uint8_t *d_out, long long out_cap,
+                        long long *d_out_offsets, int *d_status, long long *got_starts, long long *got_lengths,
+                        void *stream);
+int  vbm_host_ogg_cut_ranges(vbm_ogg_cutter *cut, int nstreams, const long long *first, const int *status, const int *begin,
+                             const long long *out_end, const long long *totals, const uint8_t *data,
+                             const long long *offsets, long long data_bytes, int nranges, const int *stream_ids,
+                             const long long *starts, const long long *lengths, const int *serialnos, int nheaders,
+                             const uint8_t *header_pages, const long long *header_offsets, const int *header_ids,
+                             uint8_t *out, long long out_cap,
+                             long long *out_offsets, int *out_status, long long *got_starts, long long *got_lengths);
+
 /* ---- test instrumentation --------------------------------------------------------------------------------
  * The path is spread over several internal HIP streams; events order them.  These calls make a missing edge show
  * deterministically (tests/test_ordering_gpu.py); they change timing and scratch contents only, never results.

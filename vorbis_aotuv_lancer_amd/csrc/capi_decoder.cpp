@@ -525,6 +525,12 @@ extern "C" void vbm_range_store_destroy(vbm_range_store *st)
     free_store(st);
 }
 
+void vbm_range_store_get_view(const vbm_range_store *st, vbm_range_store_view *v)
+{
+    *v = {st->S, st->dec->halfrate, (long long)st->status.size(), st->data_bytes, st->first.data(), st->out_end.data(),
+          st->totals.data(), st->status.data(), st->d_data, st->d_offsets, st->d_out_start, st->d_begin, st->d_end};
+}
+
 extern "C" int vbm_range_store_totals(const vbm_range_store *st, long long *totals)
 {
     if (!st || !totals) return VBM_EINVAL;

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "ogg_emit.h"
 #include "ogg_mux.h"
 #include "twin_host.h"
 
@@ -96,33 +97,6 @@ __global__ void __launch_bounds__(1024) k_mux_scan(int nstreams, const long long
     if (t == 0) offsets[nstreams] = carry;
 }
 
-// n bytes src -> dst by the 64 lanes of a wavefront, src and dst not overlapping; stores at or beyond `room` bytes
-// from dst are dropped (second line of defence: the host has checked the capacity against the bound)
-__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *src, int n, long long room, int lane)
-{
-    if (n > room) n = room > 0 ? (int)room : 0;
-    const int lead = min(n, (int)((4 - ((uintptr_t)dst & 3)) & 3));
-    if (lane < lead) dst[lane] = src[lane];
-    const int nd = (n - lead) >> 2;
-    const uint8_t *s0 = src + lead;
-    const int sh = (int)((uintptr_t)s0 & 3) * 8;
-    const uint32_t *sa = (const uint32_t *)(s0 - ((uintptr_t)s0 & 3));
-    uint32_t *da = (uint32_t *)(dst + lead);
-    if (sh == 0) {
-        for (int i = lane; i < nd; i += 64) da[i] = sa[i];
-    } else {
-        // the dword after the last one read still holds a byte of the source: it lies inside the source's allocation
-        for (int i = lane; i < nd; i += 64) da[i] = (sa[i] >> sh) | (sa[i + 1] << (32 - sh));
-    }
-    const int done = lead + nd * 4;
-    if (lane < n - done) dst[done + lane] = src[done + lane];
-}
-
-__device__ __forceinline__ uint32_t crc_byte(const uint32_t *T, uint32_t crc, uint32_t b)
-{
-    return (crc << 8) ^ T[((crc >> 24) ^ b) & 0xff];
-}
-
 __global__ void __launch_bounds__(64) k_mux_emit(OggMuxDims d, OggMuxPow pw, int qstride, OggMuxHead *head,
                                                  uint8_t *lacing, long long *gran, uint8_t *body, const int *rows,
                                                  const OggMuxPage *pages, const OggMuxCall *call,
@@ -183,23 +157,13 @@ __global__ void __launch_bounds__(64) k_mux_emit(OggMuxDims d, OggMuxPow pw, int
                     const int pe = min(vend, piece_off[k + 1]);
                     const uint8_t *src = piece_ptr[k] + (v - piece_off[k]);
                     const int n = pe - v;
-                    int i = 0;
-                    for (; i < n && ((uintptr_t)(src + i) & 3); i++) crc = crc_byte(T, crc, src[i]);
-                    for (; i + 4 <= n; i += 4) {
-                        const uint32_t w = *(const uint32_t *)(src + i);
-                        crc = crc_byte(T, crc, w & 0xff);
-                        crc = crc_byte(T, crc, (w >> 8) & 0xff);
-                        crc = crc_byte(T, crc, (w >> 16) & 0xff);
-                        crc = crc_byte(T, crc, w >> 24);
-                    }
-                    for (; i < n; i++) crc = crc_byte(T, crc, src[i]);
+                    crc = crc_run(T, crc, src, n);
                     v = pe;
                     k++;
                 }
             }
-            crc = oggmux_crc_shift(pw, crc, (uint32_t)(L - b));
         }
-        for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
+        crc = crc_wave_combine(pw, crc, a < b, (uint32_t)(L - b));
         if (lane < 4) hdr[22 + lane] = (uint8_t)((crc >> (8 * lane)) & 0xff);
         __syncthreads();
 

@@ -19,6 +19,7 @@
 #include <new>
 #include <string>
 
+#include "ogg_emit.h"
 #include "ogg_select.h"
 #include "twin_host.h"
 
@@ -110,55 +111,6 @@ __global__ void __launch_bounds__(256) k_sel_scan(int nfiles, const long long *k
     if (threadIdx.x == 0) *status = out_offsets[nfiles] > out_cap ? VBM_OGG_DEMUX_ECAP : 0;   // its own store
 }
 
-// 16 bytes from byte 16 * i + 4 * q + r of the aligned words at sa (q, r in 0..3, not both 0): words i and i + 1
-__device__ __forceinline__ uint4 sel_fetch(const uint4 *sa, int i, int q, int r)
-{
-    const uint4 a = sa[i], b = sa[i + 1];
-    const uint32_t x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    uint32_t s[5];
-#pragma unroll
-    for (int j = 0; j < 5; j++) s[j] = q == 0 ? x[j] : q == 1 ? x[j + 1] : q == 2 ? x[j + 2] : x[j + 3];
-    uint32_t o[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) o[j] = (uint32_t)((((unsigned long long)s[j + 1] << 32) | s[j]) >> (8 * r));
-    return make_uint4(o[0], o[1], o[2], o[3]);
-}
-
-// n bytes src -> dst by the 256 threads of a block.  16-byte stores to the aligned middle of dst.  A source that is not
-// aligned with it is read as aligned 16-byte words: the first may begin up to 15 bytes in front of src (still inside the
-// buffer's allocation, whose base is aligned), and none reaches past src + n: the buffer may end with this run.
-__device__ __forceinline__ void sel_block_copy(uint8_t *dst, const uint8_t *src, int n)
-{
-    const int t = threadIdx.x;
-    const int lead = min(n, (int)((16 - ((uintptr_t)dst & 15)) & 15));
-    if (t < lead) dst[t] = src[t];
-    int nd = (n - lead) >> 4;
-    const uint8_t *s0 = src + lead;
-    const int sh = (int)((uintptr_t)s0 & 15);
-    const uint4 *sa = (const uint4 *)(s0 - sh);
-    uint4 *da = (uint4 *)(dst + lead);
-    if (sh) {
-        // word i needs sa[i] and sa[i + 1]: both must end at or before src + n
-        const int whole = (int)((src + n - (const uint8_t *)sa) >> 4);
-        nd = max(0, min(nd, whole - 1));
-    }
-    const int q = sh >> 2, r = sh & 3;
-    for (int i0 = t; i0 < nd; i0 += 4 * 256) {      // four loads in flight per thread, then their stores
-        uint4 v[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int i = i0 + j * 256;
-            if (i < nd) v[j] = sh ? sel_fetch(sa, i, q, r) : sa[i];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int i = i0 + j * 256;
-            if (i < nd) da[i] = v[j];
-        }
-    }
-    for (int i = lead + nd * 16 + t; i < n; i += 256) dst[i] = src[i];
-}
-
 __global__ void __launch_bounds__(256) k_sel_copy(int nfiles, const uint8_t *data, const long long *off, const OggSelRun *runs,
                                                   const long long *nruns, const long long *out_offsets, uint8_t *out,
                                                   long long out_cap)
@@ -176,7 +128,7 @@ __global__ void __launch_bounds__(256) k_sel_copy(int nfiles, const uint8_t *dat
         const OggSelRun R = fr[r];
         const long long within = d - fbase - R.dst;
         const long long n = min(R.len - within, d1 - d);
-        sel_block_copy(out + d, data + R.src + within, (int)n);
+        vec_copy<256>(out + d, data + R.src + within, (int)n, threadIdx.x);
         d += n;
         if (within + n < R.len) break;              // the chunk ends inside this run
         r++;

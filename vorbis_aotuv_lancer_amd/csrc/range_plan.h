@@ -14,6 +14,19 @@ struct vbm_range_plan {
     std::vector<int> call_first, call_r0;   // per sub-call: first piece (and the end of the last), first output row
 };
 
+// The packets of `got` > 0 samples from s of a stream whose packets are [a, b): k, the first with output past s; m, which
+// holds sample s + got - 1; pre, the last valid packet (status 0) before k, the pre-roll.  False: there is none.
+// (vbm_plan_ranges below, and the Ogg cut of ogg_cut.hip, which copies the packets pre .. m.)
+inline bool vbm_range_find(long long a, long long b, const int *status, const long long *out_end, long long s,
+                           long long got, int &k, int &m, int &pre)
+{
+    k = (int)(std::upper_bound(out_end + a, out_end + b, s) - out_end);
+    m = (int)(std::upper_bound(out_end + a, out_end + b, s + got - 1) - out_end);
+    pre = k - 1;
+    while (pre >= a && status[pre] != 0) pre--;
+    return pre >= a;
+}
+
 // The index: stream i has packets first[i] .. first[i + 1] - 1 and totals[i] samples; packet j has status[j] (0: it
 // decodes) and out_end[j], its stream's samples up to and with it.  Range r: lengths[r] samples of stream stream_ids[r]
 // from starts[r], all checked by the caller; got[r] becomes the samples of it that exist.  Per range the packets k (first
@@ -33,12 +46,8 @@ inline const char *vbm_plan_ranges(const long long *first, const int *status, co
         const long long total = totals[i], s = starts[r];
         got[r] = (int)std::max(0LL, std::min(total - s, (long long)lengths[r]));
         if (got[r] == 0) continue;
-        const long long a = first[i], b = first[i + 1];
-        const int k = (int)(std::upper_bound(out_end + a, out_end + b, s) - out_end);
-        const int m = (int)(std::upper_bound(out_end + a, out_end + b, s + got[r] - 1) - out_end);
-        int pre = k - 1;
-        while (pre >= a && status[pre] != 0) pre--;
-        if (pre < a) {                                   // lW >= 0 at k
+        int k, m, pre;
+        if (!vbm_range_find(first[i], first[i + 1], status, out_end, s, got[r], k, m, pre)) {   // lW >= 0 at k
             *plan = {};
             return "range store index: no pre-roll packet";
         }

@@ -1,5 +1,5 @@
 // Host-side scaffold of the container objects that come as a device form and a host twin (ogg_mux.hip, ogg_demux.hip,
-// ogg_feed.hip, ogg_chain.hip): the host CRC table, the error setter, the kind check, the owner of the object's memory, the pinned
+// ogg_feed.hip, ogg_chain.hip, ogg_select.hip, ogg_cut.hip): the host CRC table, the error setter, the kind check, the owner of the object's memory, the pinned
 // stage a call's host arguments go up through, and the read-back of a status word.  Everything here has internal
 // linkage: each of those files gets its own copy and none exports a name.
 #pragma once
@@ -29,7 +29,7 @@ int fail(int code, const std::string &msg)
     return code;
 }
 
-// a host call needs the twin, a device call the device form; kind: "mux", "demuxer", "feed", "chain"
+// a host call needs the twin, a device call the device form; kind: "mux", "demuxer", "feed", "chain", "select", "cut"
 template <class M> int check_kind(const M *m, bool host, const char *who, const char *kind)
 {
     if (m && m->host == host) return VBM_OK;

@@ -20,6 +20,17 @@ int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, 
 int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const int *cap, const int *d_count,
                                  const float *d_blocks, uint8_t *d_packets, int *d_packet_bytes, bool first_round,
                                  hipStream_t fork);
+struct vbm_range_store;
+struct vbm_range_store_view {          // a range store's index and device arrays, for ogg_cut.hip
+    int S, halfrate;
+    long long packets, data_bytes;
+    const long long *first, *out_end, *totals;   // host: [S + 1], [P], [S]
+    const int *status;                           // host: [P]
+    const uint8_t *d_data;
+    const long long *d_offsets, *d_out_start;    // device: [P + 1], [P]
+    const int *d_begin, *d_end;                  // device: [P]
+};
+void vbm_range_store_get_view(const vbm_range_store *st, vbm_range_store_view *v);   // capi_decoder.cpp
 extern "C" void vbm_debug_stamp(hipStream_t st, int tag);          // util_kernels.hip (timing experiments, VBM_DEBUG_STAMPS)
 
 // test instrumentation (debug_hooks.hip): a spin kernel on `q` when `point` is in the mask of vbm_debug_set_delay

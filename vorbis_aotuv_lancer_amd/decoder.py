@@ -435,6 +435,7 @@ class OggIndex:
     memory (about the compressed size + 24 B per packet); no PCM is kept.  .total_samples: int64 [files].
     decode_ranges(file_ids, starts, lengths) -> (pcm float32 [n, channels, max(lengths)] CUDA tensor, zeros past got;
     got int32 [n]), pcm[r, :, :got[r]] bit for bit decode_ogg's output of that file from starts[r].
+    cut_ranges(file_ids, starts, lengths) -> the same windows as new .ogg files, the packets copied unchanged.
     halfrate=True: .rate is half the files' rate, and total_samples, starts and lengths are samples at that rate
     (decode_ogg(files, halfrate=True)'s).  device_demux=True: the files are demuxed together on the device
     (stream.demux_ogg_device) and the store and its index are built there from the demuxed batch
@@ -471,6 +472,8 @@ class OggIndex:
         self.setup = DecodeSetup(h0)
         self.decoder = Decoder(self.setup, 1, max_batch, halfrate=halfrate)
         self.channels, self.rate, self.halfrate = self.setup.channels, self.decoder.rate, self.decoder.halfrate
+        self.headers = [[bytes(p) for p in h] for h in headers]     # per file; the comment packets are the files' own
+        self._hdr_pages, self._cutter = {}, None
 
     def decode_ranges(self, file_ids, starts, lengths):
         ln = np.asarray(lengths, dtype=np.int64)
@@ -479,7 +482,77 @@ class OggIndex:
         pcm = torch.zeros((len(ln), self.channels, L), dtype=torch.float32, device=dev)
         return self.decoder.synthesis_ranges(self.store, file_ids, starts, lengths, out=pcm)
 
+    def _header_pages(self, f):
+        """the pages that open a cut of file f (the cutter writes the cut's serial number into them): the class's
+        identification and setup packets, the file's own comment packet"""
+        from .stream import header_pages
+        f = int(f)
+        if f not in self._hdr_pages:
+            self._hdr_pages[f] = header_pages(self.headers[f], 0)
+        return self._hdr_pages[f]
+
+    def _cutter_for(self, n, out_bytes, hdr_bytes):
+        """the index's own cutter, grown (never shrunk) to hold such a call"""
+        from .stream import OggCutter
+        c = self._cutter
+        if c is None or c.max_ranges < n or c.max_out_bytes < out_bytes or c.max_header_bytes < hdr_bytes:
+            caps = (n, out_bytes, hdr_bytes) if c is None else (max(n, c.max_ranges), max(out_bytes, c.max_out_bytes),
+                                                                max(hdr_bytes, c.max_header_bytes))
+            if c is not None:
+                c.close()
+            self._cutter = c = OggCutter(max(1, caps[0]), caps[1], caps[2])
+        return c
+
+    def cut_ranges(self, file_ids, starts, lengths, serialnos=None, out=None, cutter=None):
+        """Sample windows of the files as new .ogg files, the packets copied as they are (stream.OggCutter, rule:
+        csrc/ogg_cut.h): file r decodes to decode_ranges' samples of (file_ids[r], starts[r], lengths[r]) with the
+        source file's comments, under serial number serialnos[r] (None: r).  A window inside one packet starts at that
+        packet's first sample; the starts and lengths returned say what every file holds.  A window past the file's
+        end is an empty output, status 0; a window the packets cannot give is refused: empty, length 0, status
+        stream.CUT_ESHAPE.
+        -> ([bytes], starts int64 [n], lengths int64 [n], status int32 [n]): one call for the sizes, one that writes,
+        and the outputs brought back in one copy.
+        out=uint8 CUDA tensor: the single-call form, which only enqueues: -> (out_offsets int64 [n + 1], starts,
+        lengths, status int32 [n + 1]) as device tensors, file r in out[out_offsets[r]:out_offsets[r + 1]], status[n]
+        stream.CUT_ECAP when out is too small (nothing is written then).  cutter: an OggCutter of the caller's for the
+        out= form, e.g. one per CUDA stream; without one the index keeps its own and regrows it as calls need."""
+        from .stream import CUT_ECAP, CUT_ESHAPE
+        if self.halfrate:
+            raise ValueError("cut_ranges needs a full-rate index: half-rate positions are not packet granule positions")
+        ids = np.asarray(file_ids, dtype=np.int64)
+        n = len(ids)
+        if ((ids < 0) | (ids >= len(self.headers))).any():
+            raise ValueError("file id out of range")
+        sn = np.arange(n, dtype=np.int64) if serialnos is None else np.asarray(serialnos, dtype=np.int64)
+        if len(sn) != n:
+            raise ValueError("serialnos needs one entry per range")
+        pages = [self._header_pages(f) for f in ids]
+        hb = sum(len(self._hdr_pages[f]) for f in set(ids.tolist()))
+        if out is not None:
+            c = cutter if cutter is not None else self._cutter_for(n, out.numel(), hb)
+            off, stat, got_s, got_l = c.cut(self.store, ids, starts, lengths, pages, sn, out=out)
+            dev = out.device
+            got_l = torch.as_tensor(got_l, device=dev)
+            got_l = torch.where(stat[:n] == CUT_ESHAPE, torch.zeros_like(got_l), got_l)
+            return off, torch.as_tensor(got_s, device=dev), got_l, stat
+        c = self._cutter_for(n, 0, hb)
+        off, stat, got_s, got_l = c.cut(self.store, ids, starts, lengths, pages, sn)
+        total = int(off[n].item())                            # the sizes: one small D2H
+        c = self._cutter_for(n, total, hb)
+        buf = torch.empty(max(total, 1), dtype=torch.uint8, device=c.device)
+        off, stat, got_s, got_l = c.cut(self.store, ids, starts, lengths, pages, sn, out=buf[:total] if total else None)
+        meta = torch.cat([off.view(torch.uint8), stat.view(torch.uint8), buf[:total]]).cpu().numpy()
+        off, stat = meta[:8 * (n + 1)].view(np.int64), meta[8 * (n + 1):12 * (n + 1)].view(np.int32)
+        if stat[n] not in (0, CUT_ECAP) or (stat[n] and total):
+            raise VbmError(f"vbm_ogg_cut_ranges: status word {stat[n]}")
+        raw = meta[12 * (n + 1):].tobytes()
+        got_l[stat[:n] == CUT_ESHAPE] = 0
+        return [raw[int(a):int(b)] for a, b in zip(off[:-1], off[1:])], got_s, got_l, stat[:n].copy()
+
     def close(self):
+        if self._cutter is not None:
+            self._cutter.close()
+            self._cutter = None
         self.store.close()
         self.decoder.close()
         self.setup.close()

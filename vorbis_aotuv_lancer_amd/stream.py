@@ -834,3 +834,75 @@ class OggFeed(_TwinHandle):
         ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
         check(lib.vbm_ogg_feed_reset_streams(self._h, len(ids), ids.ctypes.data, self._q()),
               "vbm_ogg_feed_reset_streams")
+
+
+CUT_ECAP, CUT_ESHAPE = 1, 2      # VBM_OGG_CUT_ECAP (the call's status word), VBM_OGG_CUT_ESHAPE (a refused range)
+
+
+def header_pages(headers, serialno):
+    """The pages that open a stream with these three header packets under `serialno`, as write_ogg makes them -> bytes"""
+    os_ = OggStream(serialno)
+    try:
+        for h in headers:
+            os_.packetin(bytes(h), 0)
+        return b"".join(os_.pages(flush=True))
+    finally:
+        os_.close()
+
+
+class OggCutter(_TwinHandle):
+    """Sample windows of indexed streams as new Ogg Vorbis files with the packets left as they are (vbm_ogg_cut_*; the
+    rule and the refusals: csrc/ogg_cut.h), for up to max_ranges windows, max_out_bytes output bytes and
+    max_header_bytes of header pages per cut() call.  The device form cuts from a decoder.RangeStore and only enqueues
+    on the current stream; one cutter serves one stream at a time (its workspace is the call's).  host=True runs the
+    CPU twin over an index in numpy arrays (no GPU needed)."""
+
+    def __init__(self, max_ranges, max_out_bytes, max_header_bytes, host=False, device=None):
+        self.max_ranges, self.max_out_bytes = int(max_ranges), int(max_out_bytes)
+        self.max_header_bytes = int(max_header_bytes)
+        super().__init__("cut", host, device, self.max_ranges, self.max_out_bytes, self.max_header_bytes)
+
+    def cut(self, src, stream_ids, starts, lengths, header_pages, serialnos=None, out=None):
+        """src: a RangeStore (device form), or with host=True the index as a tuple of numpy arrays (first int64 [S + 1],
+        status int32 [P], begin int32 [P], out_end int64 [P], totals int64 [S], data uint8, offsets int64 [P + 1]).
+        header_pages: one bytes object per range, the pages that open its file (stream.header_pages, under any serial
+        number: serialnos[r], or r without serialnos, is written into them); ranges that give the same bytes share
+        one uploaded copy.  out: uint8 [cap], a tensor on the device (a numpy array with host=True), or None to ask for the
+        sizes alone (the status word is then CUT_ECAP unless every output is empty).
+        -> (out_offsets int64 [n + 1], status int32 [n + 1], got_starts int64 [n], got_lengths int64 [n]): the first
+        two where out lives (device tensors that the enqueued work fills; numpy with host=True), the last two numpy.
+        status[n] is the call's status word, status[r] 0 or CUT_ESHAPE; a refused range's length counts as 0."""
+        ids = np.ascontiguousarray(stream_ids, np.int32)
+        st, ln = np.ascontiguousarray(starts, np.int64), np.ascontiguousarray(lengths, np.int64)
+        n = len(ids)
+        if len(st) != n or len(ln) != n or len(header_pages) != n or (serialnos is not None and len(serialnos) != n):
+            raise ValueError("stream_ids, starts, lengths, header_pages and serialnos need one entry per range")
+        sn = None if serialnos is None else np.ascontiguousarray(np.asarray(serialnos, np.int64).astype(np.int32))
+        sets, hid = {}, np.zeros(n, np.int32)
+        for r, p in enumerate(header_pages):              # the distinct sets, in the order they first appear
+            hid[r] = sets.setdefault(p, len(sets))
+        hdr, hoff = _join(list(sets))
+        got_s, got_l = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        cap = 0 if out is None else int(out.numel() if not self.host else out.size)
+        tail = (n, ids.ctypes.data, st.ctypes.data, ln.ctypes.data, None if sn is None else sn.ctypes.data, len(sets),
+                hdr.ctypes.data if len(hdr) else None, hoff.ctypes.data, hid.ctypes.data)
+        if self.host:
+            first, status, begin, out_end, totals, data, offsets = src
+            first, out_end, totals, offsets = (np.ascontiguousarray(a, np.int64) for a in (first, out_end, totals, offsets))
+            status, begin = np.ascontiguousarray(status, np.int32), np.ascontiguousarray(begin, np.int32)
+            data = np.ascontiguousarray(data, np.uint8)
+            off, stat = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int32)
+            check(lib.vbm_host_ogg_cut_ranges(self._h, len(first) - 1, first.ctypes.data, status.ctypes.data,
+                                              begin.ctypes.data, out_end.ctypes.data, totals.ctypes.data,
+                                              data.ctypes.data if len(data) else None, offsets.ctypes.data, len(data),
+                                              *tail, out.ctypes.data if cap else None, cap, off.ctypes.data,
+                                              stat.ctypes.data, got_s.ctypes.data, got_l.ctypes.data),
+                  "vbm_host_ogg_cut_ranges")
+        else:
+            import torch
+            off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            stat = torch.empty(n + 1, dtype=torch.int32, device=self.device)
+            check(lib.vbm_ogg_cut_ranges(self._h, src._h, *tail, out.data_ptr() if cap else None, cap, off.data_ptr(),
+                                         stat.data_ptr(), got_s.ctypes.data, got_l.ctypes.data, self._q()),
+                  "vbm_ogg_cut_ranges")
+        return off, stat, got_s, got_l
