@@ -5,10 +5,10 @@
 // A workgroup of 256 threads owns NB consecutive channel-blocks (lanes of one 64-lane tile, batch.h).  The five
 // running sums N, X, XX, Y, XY of a block live in LDS (five arrays of n floats: 20 KB for a long block, so several
 // workgroups share a CU); logmdct, work and noise of bin i live in the registers of thread i mod 256, for all NB
-// blocks.  HBM traffic is the algorithmic one: the block's MDCT row in (block-major, straight from k_window_mdct),
-// MDCT (the layout change for k_mix and the couple kernels rides along) / logmdct / logmask / epeak rows and the
-// npeak entries out (tiled bin-major: the lane-per-block kernels behind this one read them), the carried lastmdct row
-// in for M9.
+// blocks (rows of 128 bins: thread i mod 128 of either half of the workgroup, for NB / 2 blocks each).  HBM traffic is
+// the algorithmic one: the block's MDCT row in (block-major, straight from k_window_mdct), MDCT (the layout change for
+// k_mix and the couple kernels rides along) / logmdct / logmask / epeak rows and the npeak entries out (tiled bin-major:
+// the lane-per-block kernels behind this one read them), the carried lastmdct row in for M9.
 //
 //   terms    every bin's five addends w, w*x, w*x*x, w*y, w*x*y (lib/psy.c:3509-3541) — independent per bin.
 //   scan     the running sums themselves are order-bound float chains (the source adds bin after bin; no other
@@ -18,8 +18,8 @@
 //   solve    per bin, the window sums are differences (mirrored: sums) of two finished rows of the five arrays
 //            (:3543-3636): a thread takes bin i of every block of the workgroup, so the bark tables are read once.
 //   both passes of bark_noise_hybridmp run like this (offset 140 / window "-1", then offset 0 / noisewindowfixed).
-//   ntfix    aoTuV M7 (short and transition blocks): a serial walk over <= 256 bins per block, on LDS rows (the sum
-//            arrays are free by then).
+//   ntfix    aoTuV M7 (short and transition blocks): per bin and per 8-bin group, by all threads (ntfix_parallel.h);
+//            what a bin reads of its neighbours goes through LDS rows (the sum arrays are free by then).
 //   post     compander + M9 per bin, then M2 / M8 per normal-partition (a lane per partition: its sums are
 //            order-bound over the partition's bins; the rows are stored skewed by one word per partition, so the
 //            lanes hit different banks), then the rows go out.
@@ -38,6 +38,7 @@
 #include <stdlib.h>
 #include "batch.h"
 #include "kernels.h"
+#include "ntfix_parallel.h"
 
 #define VMIN(x, y) ((x) > (y) ? (y) : (x))
 #define VMAX(x, y) ((x) < (y) ? (y) : (x))
@@ -116,103 +117,6 @@ __device__ __forceinline__ void nm_scan(float *__restrict__ q, const int n)
     }
 }
 
-// aoTuV M7, lib/psy.c:3645-3768, on LDS rows: spectral = logmdct, noise = pass 2's logmdct - work; temp / inmod: 256 each
-__device__ void nm_ntfix(const vbm_psy *p, const int block_mode, const float *spectral, float *noise, float *temp, float *inmod,
-                         const int scratch)
-{
-    int i, j, k;
-    const int n = p->n;
-    int nx = p->tonefix_end;
-    const float limit = fabsf(p->noiseoffset[1][0]);
-    const float *__restrict__ ntfix_noiseoffset = p->ntfix_noiseoffset, *__restrict__ noiseoffset1 = p->noiseoffset[1];
-    if (!nx) return;
-    for (i = 0; i < scratch; i++) { temp[i] = 0.f; inmod[i] = 0.f; }     // the source clears 256; entries from n + 4 on are never read
-    if (block_mode <= 1) {
-        const int freq_upc = 3;
-        const int freq_unc = 4;
-        int nxplus = nx + freq_unc;
-        float tolerance = 9.f;
-        const float strength = .6f;
-        if (n == 256) tolerance = 15.f;
-        if (nxplus > n) {
-            nx = n;
-            nxplus = n - freq_unc;
-        }
-        for (i = 0; i < nxplus; i++) {
-            const float sp = spectral[i];
-            if (sp < -70) inmod[i] = (float)(-70 + (double)(sp + 70) * .1);
-            else inmod[i] = sp;
-        }
-        for (i = freq_unc; i < nx; i++) {
-            if ((spectral[i] > spectral[i - 1]) && (spectral[i] > spectral[i + 1])) {
-                int ps = i - 1;
-                int pe = i + 1;
-                const int upper = i - freq_upc;
-                const int under = i + freq_unc;
-                for (j = ps; j > upper; j--) {
-                    if (spectral[j + 1] < spectral[j]) break;
-                    ps = j;
-                }
-                for (j = pe; j < under; j++) {
-                    if (spectral[j - 1] < spectral[j]) break;
-                    pe = j;
-                }
-                {
-                    float ss = inmod[i] - inmod[ps];
-                    ss = VMAX(ss, inmod[i] - inmod[pe]);
-                    if (ss > tolerance) {
-                        if (spectral[i] > noise[i]) {
-                            ss -= tolerance;
-                            ss *= strength;
-                        }
-                        for (j = ps; j <= pe; j++) {
-                            temp[j] = VMAX(ss, temp[j]);
-                            if (temp[j] < 0) temp[j] = 0;
-                        }
-                    }
-                }
-                i = pe;
-            }
-        }
-        for (i = freq_unc - 1; i < nx; i++) {
-            const float test = VMIN(ntfix_noiseoffset[i], noiseoffset1[i] + limit);
-            if (temp[i] > test) temp[i] = test;
-            noise[i] -= temp[i];
-        }
-    } else if (block_mode == 2) {
-        for (i = 0, k = 0; i < nx; i += 8, k++) {
-            double na = 0;
-            for (j = 0; j < 8; j++) na += noise[i + j];
-            na /= 8;
-            temp[k] = (float)na;
-        }
-        nx /= 8;
-        for (i = 3; i < nx; i++) {
-            if ((temp[i] > temp[i - 1]) && (temp[i] > temp[i + 1])) {
-                int a = 0, bb = 0;
-                float thres = 0;
-                if (temp[i - 1] > temp[i - 2]) {
-                    thres = temp[i - 2];
-                    a = i - 3;
-                } else {
-                    thres = temp[i - 1];
-                    a = i - 2;
-                }
-                bb = i + 3;
-                thres = temp[i] - thres;
-                if ((double)thres > 2.) {
-                    const int eightimes = i * 8;
-                    const float test = VMIN(ntfix_noiseoffset[eightimes], noiseoffset1[eightimes] + limit);
-                    thres = VMIN(thres - 2, test);
-                    a *= 8;
-                    bb *= 8;
-                    for (j = a; j <= bb; j++) noise[j] -= thres;
-                }
-            }
-        }
-    }
-}
-
 template <int NB> struct rowseg;
 template <> struct rowseg<1> { static __device__ __forceinline__ void put(float *q, const float *v) { q[0] = v[0]; } };
 template <> struct rowseg<2> { static __device__ __forceinline__ void put(float *q, const float *v) { *reinterpret_cast<float2 *>(q) = make_float2(v[0], v[1]); } };
@@ -234,10 +138,17 @@ __device__ __forceinline__ void put_row(float *__restrict__ q, const float *v, c
         for (int u = 0; u < nb; u++) q[u] = v[u];
 }
 
-// ROWS = ceil(n / 256): thread t holds bins t, t + 256, ... of all NB blocks
-template <int NB, int ROWS>
+// The workgroup's 256 threads stand SPLIT groups side by side: a group of TPR = 256 / SPLIT threads takes PB = NB / SPLIT
+// of the workgroup's blocks, thread t of it the bins t, t + TPR, ... (ROWS = ceil(n / TPR) of them) of those PB blocks.
+// SPLIT = 2 is for n = 128, where one group of 256 would leave its upper half without bins.
+// M7: the batch holds short or transition blocks (block_mode <= 2).  Long blocks have no M7, and their instantiations do
+// not carry its code: inlined it costs k_noisemask<2,4> 24 VGPRs (100 -> 124), registers that the kernels running beside
+// the full-size batch then miss (per-block bench + 6.5 %, profiles/psy_small_forms).  With M7 the 2048-bin form has 197
+// VGPRs: two workgroups per CU where its LDS would allow three, for the transition batches of 4096-sample classes.
+template <int NB, int ROWS, int SPLIT, bool M7>
 __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
 {
+    constexpr int PB = NB / SPLIT, TPR = NM_THREADS / SPLIT;
     extern __shared__ __align__(16) float SU[];      // [NB][5][NS] addends, then running sums; later rows for M7 / M2 / M8
     __shared__ float s_ncl[NB], s_poste[NB];
     __shared__ int s_col[NB], s_need[NB];
@@ -254,37 +165,41 @@ __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
     if (lane0 >= ncb) return;
     const int nb = VMIN(NB, ncb - lane0);
     const int tid = (int)threadIdx.x;
+    // the thread's first bin; the first of its blocks; how many of its PB blocks exist
+    const int bin0 = (SPLIT == 1) ? tid : tid % TPR, b0 = (SPLIT == 1) ? 0 : (tid / TPR) * PB;
+    const int nbt = (SPLIT == 1) ? nb : VMAX(0, VMIN(PB, nb - b0));
     const int BS = 5 * NS;        // floats of LDS per block
 
     const int i1 = p->hy_i1, i2 = p->hy_i2;
     const int fixed = p->noisewindowfixed;
     const int f1 = (fixed > 0) ? p->hy_f1 : 0, f2 = (fixed > 0) ? p->hy_f2 : 0;
-    const size_t tile = (size_t)(lane0 >> 6) * b.slab_words + (lane0 & 63);
+    const size_t tile = (size_t)(lane0 >> 6) * b.slab_words + (lane0 & 63) + b0;
+    float *const SB = SU + (size_t)b0 * BS;        // the thread's blocks in LDS
 
-    float lm[ROWS][NB], wk[ROWS][NB], nz[ROWS][NB];
+    float lm[ROWS][PB], wk[ROWS][PB], nz[ROWS][PB];
     int wlo[ROWS], whi[ROWS];        // the variable window of the thread's bins (bins from i2 on: that of bin i2 - 1)
 
     // ---- logmdct (lib/mapping0.c:936-950)
     {
-        const float *__restrict__ src = b.mdct_bm + (size_t)lane0 * n;
+        const float *__restrict__ src = b.mdct_bm + (size_t)(lane0 + b0) * n;
         const int *__restrict__ bark_lo = p->bark_lo, *__restrict__ bark_hi = p->bark_hi;
 #pragma unroll
         for (int r = 0; r < ROWS; r++) {
-            const int i = tid + r * NM_THREADS;
+            const int i = bin0 + r * TPR;
             const int iw = (i < i2) ? i : i2 - 1;
             wlo[r] = 0; whi[r] = 0;
             if (i < n && iw >= 0) { wlo[r] = bark_lo[iw]; whi[r] = bark_hi[iw]; }
-            float mv[NB];
+            float mv[PB];
 #pragma unroll
-            for (int blk = 0; blk < NB; blk++) {
+            for (int blk = 0; blk < PB; blk++) {
                 float v = 0.f;
-                if (i < n && blk < nb) v = src[(size_t)blk * n + i];
+                if (i < n && blk < nbt) v = src[(size_t)blk * n + i];
                 mv[blk] = v;
                 lm[r][blk] = (float)((double)vbm_todB(v) + .345);
             }
             // the MDCT rows in the tiled layout for the lane-per-block kernels behind this one (k_mix, couple): this
             // kernel reads the block-major rows anyway, so no transpose pass of its own is needed
-            if (i < n) put_row<NB>(b.mdctT + tile + (size_t)i * 64, mv, nb);
+            if (i < n) put_row<PB>(b.mdctT + tile + (size_t)i * 64, mv, nbt);
         }
     }
 
@@ -314,11 +229,11 @@ __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
         if (any) {      // (uniform over the workgroup)
 #pragma unroll
             for (int r = 0; r < ROWS; r++) {
-                const int i = tid + r * NM_THREADS;
+                const int i = bin0 + r * TPR;
                 if (i < n)
 #pragma unroll
-                    for (int blk = 0; blk < NB; blk++)
-                        if (blk < nb) SU[(size_t)blk * BS + i] = lm[r][blk];
+                    for (int blk = 0; blk < PB; blk++)
+                        if (blk < nbt) SB[(size_t)blk * BS + i] = lm[r][blk];
             }
             __syncthreads();
             if (tid < nb && s_need[tid]) {
@@ -348,18 +263,18 @@ __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
         // addends of logmdct (pass 1) / work (pass 2)
 #pragma unroll
         for (int r = 0; r < ROWS; r++) {
-            const int i = tid + r * NM_THREADS;
+            const int i = bin0 + r * TPR;
             if (i < n)
 #pragma unroll
-                for (int blk = 0; blk < NB; blk++)
-                    if (blk < nb) nm_terms(pass == 1 ? lm[r][blk] : wk[r][blk], i, offset, SU + (size_t)blk * 5 * NS, NS);
+                for (int blk = 0; blk < PB; blk++)
+                    if (blk < nbt) nm_terms(pass == 1 ? lm[r][blk] : wk[r][blk], i, offset, SB + (size_t)blk * 5 * NS, NS);
         }
         __syncthreads();
         if (tid < nb * 5) nm_scan(SU + (size_t)tid * NS, n);
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < ROWS; r++) {
-            const int i = tid + r * NM_THREADS;
+            const int i = bin0 + r * TPR;
             if (i >= n) continue;
             const float x = (float)i;                      // the source's x += 1.f from 0 is exact below 2^24
             const bool have = i2 > 0;                      // (bins from i2 on keep A, B, D of the last bin solved, :3587-3591)
@@ -369,9 +284,9 @@ __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
             const int fw = (i < f2) ? i : f2 - 1;
             const int fhi = fw + fixed / 2, flo = fhi - fixed;
 #pragma unroll
-            for (int blk = 0; blk < NB; blk++) {
-                if (blk >= nb) continue;
-                const float *S = SU + (size_t)blk * 5 * NS;
+            for (int blk = 0; blk < PB; blk++) {
+                if (blk >= nbt) continue;
+                const float *S = SB + (size_t)blk * 5 * NS;
                 hy_abd v; v.A = 0.f; v.B = 0.f; v.D = 1.f;
                 if (have) v = nm_window(S, NS, wlo[r], whi[r], mirror);
                 float R = (v.A + x * v.B) / v.D;
@@ -395,33 +310,102 @@ __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
         __syncthreads();
     }
 
-    // ---- aoTuV M7 (short and transition blocks) on rows in LDS: logmdct at [0], work at [NS], scratch behind
-    if (b.block_mode <= 2) {
-        const int scratch = VMIN(256, NS);
+    // ---- aoTuV M7 (short and transition blocks, lib/psy.c:3645-3768; the per-bin and per-group bodies and why they
+    //      give the source's bits: ntfix_parallel.h), on four rows per block in LDS (the sum arrays are free by now)
+    if (M7 && p->tonefix_end) {
+        const float limit = fabsf(p->noiseoffset[1][0]);
+        const float *__restrict__ ntfix_noiseoffset = p->ntfix_noiseoffset, *__restrict__ noiseoffset1 = p->noiseoffset[1];
+        int nx = p->tonefix_end;
+        if (b.block_mode <= 1) {
+            // rows: spectral, inmod, the peaks' ss, their reach
+            int nxplus = nx + NTFIX_FREQ_UNC;
+            if (nxplus > n) { nx = n; nxplus = n - NTFIX_FREQ_UNC; }
+            const float tolerance = ntfix_short_tolerance(n);
 #pragma unroll
-        for (int r = 0; r < ROWS; r++) {
-            const int i = tid + r * NM_THREADS;
-            if (i < n)
+            for (int r = 0; r < ROWS; r++) {
+                const int i = bin0 + r * TPR;
+                if (i < n)
 #pragma unroll
-                for (int blk = 0; blk < NB; blk++)
-                    if (blk < nb) {
-                        SU[(size_t)blk * BS + i] = lm[r][blk];
-                        SU[(size_t)blk * BS + NS + i] = wk[r][blk];
-                    }
-        }
-        __syncthreads();
-        if (tid < nb) {
-            float *row = SU + (size_t)tid * BS;
-            nm_ntfix(p, b.block_mode, row, row + NS, row + 2 * NS, row + 2 * NS + scratch, scratch);
-        }
-        __syncthreads();
+                    for (int blk = 0; blk < PB; blk++)
+                        if (blk < nbt) {
+                            SB[(size_t)blk * BS + i] = lm[r][blk];
+                            SB[(size_t)blk * BS + NS + i] = ntfix_inmod(lm[r][blk], i, nxplus);
+                        }
+            }
+            __syncthreads();
 #pragma unroll
-        for (int r = 0; r < ROWS; r++) {
-            const int i = tid + r * NM_THREADS;
-            if (i < n)
+            for (int r = 0; r < ROWS; r++) {
+                const int i = bin0 + r * TPR;
+                if (i >= NTFIX_FREQ_UNC && i < nx)
 #pragma unroll
-                for (int blk = 0; blk < NB; blk++)
-                    if (blk < nb) wk[r][blk] = SU[(size_t)blk * BS + NS + i];
+                    for (int blk = 0; blk < PB; blk++)
+                        if (blk < nbt) {
+                            float *row = SB + (size_t)blk * BS;
+                            int down, up;
+                            row[2 * NS + i] = ntfix_short_peak(row, row + NS, wk[r][blk], i, tolerance, &down, &up);
+                            reinterpret_cast<int *>(row + 3 * NS)[i] = ntfix_reach_pack(down, up);
+                        }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < ROWS; r++) {
+                const int i = bin0 + r * TPR;
+                if (i >= NTFIX_FREQ_UNC - 1 && i < nx) {
+                    const float tone_off = ntfix_noiseoffset[i], noise_off = noiseoffset1[i];
+#pragma unroll
+                    for (int blk = 0; blk < PB; blk++)
+                        if (blk < nbt) {
+                            const float *row = SB + (size_t)blk * BS;
+                            const float temp = ntfix_short_temp(row + 2 * NS, reinterpret_cast<const int *>(row + 3 * NS), i, nx);
+                            wk[r][blk] = ntfix_short_apply(wk[r][blk], temp, tone_off, noise_off, limit);
+                        }
+                }
+            }
+        } else {
+            // rows: noise, the groups' means (0 behind the last one, as the source's cleared temp), thres, first group
+            const int ngr = (nx + 7) >> 3, nx8 = nx >> 3;
+#pragma unroll
+            for (int r = 0; r < ROWS; r++) {
+                const int i = bin0 + r * TPR;
+                if (i < n)
+#pragma unroll
+                    for (int blk = 0; blk < PB; blk++)
+                        if (blk < nbt) SB[(size_t)blk * BS + i] = wk[r][blk];
+            }
+            __syncthreads();
+            for (int t = tid; t < nb * (nx8 + 1); t += NM_THREADS) {
+                const int blk = t / (nx8 + 1), k = t - blk * (nx8 + 1);
+                float *row = SU + (size_t)blk * BS;
+                row[NS + k] = (k < ngr) ? ntfix_group_mean(row + 8 * k) : 0.f;
+            }
+            __syncthreads();
+            for (int t = tid; t < nb * nx8; t += NM_THREADS) {
+                const int blk = t / nx8, k = t - blk * nx8;
+                if (k < 3) continue;
+                float *row = SU + (size_t)blk * BS;
+                float thres;
+                const int a = ntfix_group_peak(row + NS, k, ntfix_noiseoffset[8 * k], noiseoffset1[8 * k], limit, &thres);
+                row[2 * NS + k] = thres;
+                reinterpret_cast<int *>(row + 3 * NS)[k] = a;
+            }
+            __syncthreads();
+            // (the pull on the LDS row, a bin at a time: unrolled over the thread's registers it costs the 2048-bin
+            //  form the registers of its third workgroup per CU)
+            for (int blk = 0; blk < nb; blk++) {
+                float *row = SU + (size_t)blk * BS;
+#pragma unroll 1
+                for (int i = tid; i < n; i += NM_THREADS)
+                    row[i] = ntfix_trans_pull(row[i], row + 2 * NS, reinterpret_cast<const int *>(row + 3 * NS), i, nx8);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < ROWS; r++) {
+                const int i = bin0 + r * TPR;
+                if (i < n)
+#pragma unroll
+                    for (int blk = 0; blk < PB; blk++)
+                        if (blk < nbt) wk[r][blk] = SB[(size_t)blk * BS + i];
+            }
         }
         __syncthreads();
     }
@@ -440,16 +424,16 @@ __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
         float *__restrict__ logmdctT = b.logmdctT + tile, *__restrict__ epeakT = b.epeakT + tile;
 #pragma unroll
         for (int r = 0; r < ROWS; r++) {
-            const int i = tid + r * NM_THREADS;
+            const int i = bin0 + r * TPR;
             if (i >= n) continue;
             const int sk = i + i / partition;
-            float epv[NB];
+            float epv[PB];
 #pragma unroll
-            for (int blk = 0; blk < NB; blk++) {
+            for (int blk = 0; blk < PB; blk++) {
                 epv[blk] = 0.f;
-                if (blk < nb) {
+                if (blk < nbt) {
                     const float lmk = nz[r][blk], wv = wk[r][blk], lmd = lm[r][blk];
-                    const float ncl = s_ncl[blk];
+                    const float ncl = s_ncl[b0 + blk];
                     const int thter = (ncl > 0) ? n33p : 0;
                     int dB = (int)((double)lmk + .5);
                     if (dB >= VBM_NOISE_COMPAND_LEVELS) dB = VBM_NOISE_COMPAND_LEVELS - 1;
@@ -462,19 +446,19 @@ __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
                     if (i < m9_end) {
                         const float temp = lmd - ep;
                         if (temp >= 12.f) {
-                            const int col = s_col[blk];
+                            const int col = s_col[b0 + blk];
                             const float lst = b.st.mblock[(size_t)(col >> 6) * b.st.slab_words + (col & 63) + (size_t)i * 64];
                             const float mi = lmd - lst;
                             if (mi >= 1) e = mi;
                         }
                     }
                     epv[blk] = e;
-                    SU[(size_t)blk * BS + sk] = lmd;
-                    SU[(size_t)blk * BS + SK + sk] = lk;
+                    SB[(size_t)blk * BS + sk] = lmd;
+                    SB[(size_t)blk * BS + SK + sk] = lk;
                 }
             }
-            put_row<NB>(logmdctT + (size_t)i * 64, lm[r], nb);
-            put_row<NB>(epeakT + (size_t)i * 64, epv, nb);
+            put_row<PB>(logmdctT + (size_t)i * 64, lm[r], nbt);
+            put_row<PB>(epeakT + (size_t)i * 64, epv, nbt);
         }
     }
     __syncthreads();
@@ -484,6 +468,7 @@ __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
         const int nparts = (n + partition - 1) / partition;
         const float *__restrict__ noiseoffset1 = p->noiseoffset[1];
         const int min_nn_lp = p->min_nn_lp;
+        const size_t tile0 = (size_t)(lane0 >> 6) * b.slab_words + (lane0 & 63);
         for (int t = tid; t < nb * nparts; t += NM_THREADS) {
             const int blk = t / nparts, k = t - blk * nparts;
             const int i = k * partition;
@@ -513,7 +498,7 @@ __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
                         if (me < nt) np = (VMIN(o, nt - me)) / nt;
                 }
             }
-            b.npeakT[tile + blk + (size_t)k * 64] = np;
+            b.npeakT[tile0 + blk + (size_t)k * 64] = np;
         }
     }
     __syncthreads();
@@ -523,28 +508,34 @@ __global__ __launch_bounds__(NM_THREADS) void k_noisemask(vbm_batch b)
         float *__restrict__ noiseT = b.noiseT + tile;
 #pragma unroll
         for (int r = 0; r < ROWS; r++) {
-            const int i = tid + r * NM_THREADS;
+            const int i = bin0 + r * TPR;
             if (i >= n) continue;
             const int sk = i + i / partition;
-            float v[NB];
+            float v[PB];
 #pragma unroll
-            for (int blk = 0; blk < NB; blk++) v[blk] = (blk < nb) ? SU[(size_t)blk * BS + SK + sk] : 0.f;
-            put_row<NB>(noiseT + (size_t)i * 64, v, nb);
+            for (int blk = 0; blk < PB; blk++) v[blk] = (blk < nbt) ? SB[(size_t)blk * BS + SK + sk] : 0.f;
+            put_row<PB>(noiseT + (size_t)i * 64, v, nbt);
         }
     }
 }
 
-template <int NB, int ROWS>
-int launch(const vbm_batch *b, hipStream_t st)
+template <int NB, int ROWS, int SPLIT, bool M7>
+int launch_form(const vbm_batch *b, hipStream_t st)
 {
     // (called from several host threads at once: one-time set-up through initialisers of function-local statics)
     const size_t lds = (size_t)5 * NB * (b->n + NM_PAD) * sizeof(float);
-    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_noisemask<NB, ROWS>),
+    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_noisemask<NB, ROWS, SPLIT, M7>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
     (void)attr;
     const unsigned wgs = (unsigned)((b->ncb + NB - 1) / NB);
-    hipLaunchKernelGGL((k_noisemask<NB, ROWS>), dim3((wgs + 7u) & ~7u), dim3(NM_THREADS), lds, st, *b);
+    hipLaunchKernelGGL((k_noisemask<NB, ROWS, SPLIT, M7>), dim3((wgs + 7u) & ~7u), dim3(NM_THREADS), lds, st, *b);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+template <int NB, int ROWS, int SPLIT>
+int launch(const vbm_batch *b, hipStream_t st)
+{
+    return b->block_mode <= 2 ? launch_form<NB, ROWS, SPLIT, true>(b, st) : launch_form<NB, ROWS, SPLIT, false>(b, st);
 }
 
 }  // namespace
@@ -555,8 +546,10 @@ extern "C" int vbm_launch_noisemask(const vbm_batch *b, hipStream_t st)
 {
     const int n = b->n;
     if ((n & 63) || n < 128 || n > 4096) return -2;     // (M7's scratch rows live in a block's five sum arrays)
-    if (n <= 256) return launch<8, 1>(b, st);
-    if (n <= 512) return launch<4, 2>(b, st);
+    // (n = 128: two groups of 128 threads with four blocks each, or half the workgroup has no bin)
+    if (n <= 128) return launch<8, 1, 2>(b, st);
+    if (n <= 256) return launch<8, 1, 1>(b, st);
+    if (n <= 512) return launch<4, 2, 1>(b, st);
     // (occupancy experiments, round 3, tools/gpu_noise_occ.sh / gpu_ab_env.sh — all removed again: the kernel's time alone goes
     //  with 1 / workgroups per CU: 0.73 ms at three, 0.96 at two, 1.74 at one.  A fourth workgroup per CU — sums without
     //  padding = exactly a quarter of the LDS, rows XOR-swizzled per sum so that the ten scan lanes still hit ten banks, the
@@ -564,6 +557,6 @@ extern "C" int vbm_launch_noisemask(const vbm_batch *b, hipStream_t st)
     //  against 4.59-4.62 (LDS the kernels beside this one no longer get); even the register scalars alone cost the padded
     //  form 1 %.  One block per workgroup (seven workgroups per CU, 4-byte row stores): 0.90 ms alone.  At most two
     //  workgroups per CU: from PCM 5.2 ms against 4.7.  Three it is.)
-    if (n <= 1024) return launch<2, 4>(b, st);
-    return launch<1, 16>(b, st);
+    if (n <= 1024) return launch<2, 4, 1>(b, st);
+    return launch<1, 16, 1>(b, st);
 }
