@@ -844,6 +844,29 @@ int  vbm_decoder_create(vbm_decoder **dec, const vbm_decode_setup *ds, int nstre
 int  vbm_decoder_create_halfrate(vbm_decoder **dec, const vbm_decode_setup *ds, int nstreams, int max_batch,
                                  int halfrate);
 int  vbm_decoder_halfrate(const vbm_decoder *dec);
+/* Mixed decoders: streams of different header classes in one call.  The decoder is made from caps, not
+ * from a setup: up to max_classes classes (vbm_decoder_add_class) of up to max_channels channels (1..8) and blocks of up
+ * to max_blocksize (a power of two in 256..4096); halfrate as in vbm_decoder_create_halfrate.  Every stream is bound to
+ * a class (vbm_decoder_bind_streams) before its first packet, and may be bound to another at any time.
+ * vbm_synthesis_batch, vbm_synthesis_runs and vbm_synthesis_runs_gaps then take streams of any mix of classes in one
+ * call, and each stream's d_samples, d_status, d_run_samples and PCM are bit for bit those of a decoder of its class
+ * alone.  The rows are those of the caps: d_pcm is [nsb][max_channels][max_blocksize/2] (/4 at half rate) for
+ * vbm_synthesis_batch and [nruns][max_channels][pcm_stride] for runs, of which a stream writes its class's channels and
+ * samples and nothing else; pcm_stride >= max over the runs of run_packets[r] * blocksizes[1]/2 (/4) of run r's class.
+ * A call that lists a stream not bound to a class is VBM_EINVAL and enqueues nothing.  vbm_decoder_reset,
+ * vbm_decoder_restart_streams and vbm_decoder_halfrate work as on any decoder (a reset keeps classes and bindings).
+ * Not built for mixed decoders, VBM_EINVAL with a message: vbm_synthesis_ranges, vbm_range_store_create,
+ * vbm_range_store_create_device, vbm_decode_index_device, vbm_decoder_fetch.
+ * vbm_decoder_add_class: copies the setup to the device, enqueued on `stream`, and returns its slot of the class table
+ *   in *class_id (0, 1, ...).  Slots are never rewritten or removed, so calls in flight stay valid; calls that use the
+ *   class must follow on `stream` or after it.  VBM_EINVAL: the class is over a cap, or the table is full.
+ * vbm_decoder_bind_streams: stream stream_ids[i] (distinct, n <= max_batch) is of class class_ids[i] from here on, and
+ *   restarts as by vbm_decoder_restart_streams: enqueued on `stream`, in order with the calls before and after it. */
+int  vbm_decoder_create_mixed(vbm_decoder **dec, int max_classes, int max_channels, int max_blocksize, int nstreams,
+                              int max_batch, int halfrate);
+int  vbm_decoder_add_class(vbm_decoder *dec, const vbm_decode_setup *ds, int *class_id, void *stream);
+int  vbm_decoder_bind_streams(vbm_decoder *dec, int n, const int *stream_ids /*host*/, const int *class_ids /*host*/,
+                              void *stream);
 void vbm_decoder_destroy(vbm_decoder *dec);
 /* every stream back to its initial state (device idle afterwards) */
 int  vbm_decoder_reset(vbm_decoder *dec);

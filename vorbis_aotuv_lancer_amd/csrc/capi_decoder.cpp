@@ -20,6 +20,13 @@
 // A half-rate decoder (vbm_decoder_create_halfrate) enqueues the same chains with the IMDCT of half each block size and
 // the half-rate instantiations of the overlap kernels; its windows and trig tables are those of the halved sizes, its
 // IMDCT rows, tails and PCM rows half as long.
+//
+// A mixed decoder (vbm_decoder_create_mixed) is the same object made from caps instead of a setup: its rows have
+// max_channels channels and max_blocksize / 2 bins, it has a block list, a window and a trig table per block size the
+// caps allow, and a table of classes (vbm_decoder_add_class) in place of the one setup.  vbm_synthesis_batch and
+// vbm_synthesis_runs enqueue the same chains with the <MX = true> kernels: the class of every row goes up behind the
+// ids or the run table in the same staging turn (from the host mirror of vbm_decoder_bind_streams' map), and there is
+// one IMDCT launch per block size.  The range store, the index and fetch are refused on it.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -43,14 +50,16 @@ constexpr int kStage = 4;
 #define CK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return fail(vbm_set_hip_error(e_, #x)); } while (0)
 
 struct vbm_decoder {
-    vbmd_setup hs;                   // host copy (block sizes, channels)
-    int S = 0, cap = 0, ch = 0;
+    vbmd_setup hs;                   // host copy (block sizes, channels); not set in a mixed decoder
+    int S = 0, cap = 0, ch = 0;      // ch: channels of a row of every row buffer (mixed: max_channels)
     int halfrate = 0;                // 1: vorbis_synthesis_halfrate
-    long half = 0, n1 = 0, ohalf = 0;   // blocksizes[1]/2, blocksizes[1] >> halfrate, blocksizes[1]/2 >> halfrate
-    int max_classes = 0;
+    long half = 0, n1 = 0, ohalf = 0;   // B/2, B >> halfrate, B/2 >> halfrate; B: blocksizes[1] (mixed: max_blocksize)
+    int max_classes = 0;             // bytes of partition-class scratch of a row
+    int nz = 2;                      // block lists and IMDCT launches per call: one per W (mixed: per block size)
+    int size[VBMD_SIZES] = {};       // the block size of list z
     uint8_t *d_setup = nullptr;      // vbmd_setup + blob
-    float *d_tables = nullptr;       // fromdB[256], win0, win1, trig0, trig1 (of blocksizes[w] >> halfrate)
-    const float *fromdB = nullptr, *win[2] = {}, *trig[2] = {};
+    float *d_tables = nullptr;       // fromdB[256], the windows, the trig tables (of size[z] >> halfrate)
+    const float *fromdB = nullptr, *win[VBMD_SIZES] = {}, *trig[VBMD_SIZES] = {};
     int *d_ids = nullptr, *d_info = nullptr, *d_fit = nullptr, *d_flags = nullptr, *d_status = nullptr;
     int *d_lists = nullptr, *d_counts = nullptr;
     int *d_runtab = nullptr, *d_plan = nullptr, *d_run_last = nullptr;   // runs: [2S+1], [cap][6], [S]
@@ -62,18 +71,44 @@ struct vbm_decoder {
     float *d_tail = nullptr;
     int *d_prevW = nullptr;
     long long *d_gp = nullptr, *d_sc = nullptr;
-    int *h_stage[kStage] = {};       // max(2S+1, 4 cap + 1) ints each
+    int *h_stage[kStage] = {};       // max(2S+1, 4 cap + 1) ints each; cap more in a mixed decoder (the rows' classes)
     hipEvent_t ev_stage[kStage] = {};
     int stage_turn = 0;
     std::vector<uint8_t> seen;
     std::vector<int> run_start;
     int last_nsb = 0;
+    // mixed decoders (vbm_decoder_create_mixed): the class table, and which class every stream is bound to.  d_ids and
+    // d_runtab have cap more ints, the class of every row behind the ids or the run table of the same staging turn.
+    struct klass {
+        int ch, bs[2];
+        std::vector<uint8_t> image;  // vbmd_setup + blob as they lie on the device: the source of the enqueued copy
+        uint8_t *d_image;
+    };
+    int mixed = 0, table_cap = 0;
+    std::vector<klass> classes;      // never shrinks, and never grows past table_cap (reserved: entries do not move)
+    std::vector<vbmd_class> table;   // host copy of d_table (reserved likewise)
+    std::vector<int> scls;           // [S] host mirror of d_scls, -1: not bound
+    vbmd_class *d_table = nullptr;
+    int *d_scls = nullptr;
 
-    vbmd_launch launch(int nsb) const
+    // rcls: in a mixed decoder the device array of the rows' classes; nblocks: rows x channels of the call
+    vbmd_launch launch(int nsb, const int *rcls = nullptr, long nblocks = 0) const
     {
         vbmd_launch L;
         L.s = (const vbmd_setup *)d_setup;
-        L.blob = d_setup + sizeof(vbmd_setup);
+        L.blob = d_setup ? d_setup + sizeof(vbmd_setup) : nullptr;
+        L.mx = mixed != 0;
+        L.M = vbmd_mixed();
+        if (mixed) {
+            L.M.table = d_table;
+            L.M.rcls = rcls;
+            L.M.scls = d_scls;
+            L.M.CH = ch;
+            L.M.cls_bytes = max_classes;
+            L.M.list_stride = (long)cap * ch;
+            for (int z = 0; z < nz; z++) L.M.win[z] = win[z];
+        }
+        L.nblocks = mixed ? nblocks : (long)nsb * ch;
         L.nsb = nsb;
         L.ch = ch;
         L.hs = halfrate;
@@ -108,9 +143,12 @@ void free_decoder(vbm_decoder *d)
     if (!d) return;
     void *bufs[] = {d->d_setup, d->d_tables, d->d_ids, d->d_info, d->d_fit, d->d_flags, d->d_status, d->d_lists,
                     d->d_counts, d->d_res, d->d_spec, d->d_imdct, d->d_cls, d->d_tail, d->d_prevW, d->d_gp, d->d_sc,
-                    d->d_runtab, d->d_plan, d->d_run_last, d->d_rtab, d->d_rows, d->d_zero, d->d_itab};
+                    d->d_runtab, d->d_plan, d->d_run_last, d->d_rtab, d->d_rows, d->d_zero, d->d_itab, d->d_table,
+                    d->d_scls};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
+    for (const vbm_decoder::klass &k : d->classes)
+        if (k.d_image) (void)hipFree(k.d_image);
     for (int i = 0; i < kStage; i++) {
         if (d->h_stage[i]) (void)hipHostFree(d->h_stage[i]);
         if (d->ev_stage[i]) (void)hipEventDestroy(d->ev_stage[i]);
@@ -151,18 +189,167 @@ int check_ids(vbm_decoder *d, int n, const int *ids)
     return VBM_OK;
 }
 
+// the streams of a decode call (check_ids), each of them bound to a class if the decoder is a mixed one
+int check_call_ids(vbm_decoder *d, int n, const int *ids)
+{
+    const int rc = check_ids(d, n, ids);
+    if (rc || !d->mixed) return rc;
+    for (int i = 0; i < n; i++)
+        if (d->scls[ids[i]] < 0) {
+            g_vbm_err = "stream " + std::to_string(ids[i]) + " is not bound to a class (vbm_decoder_bind_streams)";
+            return VBM_EINVAL;
+        }
+    return VBM_OK;
+}
+
+// an entry point that is not built for mixed decoders
+int refuse_mixed(const vbm_decoder *d, const char *what)
+{
+    if (!d || !d->mixed) return VBM_OK;
+    g_vbm_err = std::string(what) + " is not built for a mixed decoder: one header class per range store and index";
+    return VBM_EINVAL;
+}
+
 // The front of every decode call, over the L.nsb rows of L = d->launch(nsb): the two clears, unpack() (the entry
-// point's unpack launch), spectrum and one IMDCT launch per block size.  what: the error text of a failed clear.
+// point's unpack launch), spectrum and one IMDCT launch per block list.  what: the error text of a failed clear.
 template <class Unpack>
 int enqueue_front(const vbm_decoder *d, const vbmd_launch &L, hipStream_t q, const char *what, Unpack unpack)
 {
-    hipError_t e = hipMemsetAsync(d->d_counts, 0, 2 * sizeof(int), q);
+    hipError_t e = hipMemsetAsync(d->d_counts, 0, d->nz * sizeof(int), q);
     if (e == hipSuccess) e = hipMemsetAsync(d->d_res, 0, (size_t)L.nsb * d->ch * d->half * sizeof(float), q);
     if (e != hipSuccess) return vbm_set_hip_error(e, what);
     if (unpack()) return VBM_EHIP;
     if (vbmd_launch_spectrum(L, d->d_spec, nullptr, q)) return VBM_EHIP;
-    for (int W = 0; W < 2; W++)
-        if (vbmd_launch_imdct(L, W, d->hs.blocksizes[W] >> d->halfrate, d->trig[W], q)) return VBM_EHIP;
+    for (int z = 0; z < d->nz; z++)
+        if (vbmd_launch_imdct(L, z, d->size[z] >> d->halfrate, d->trig[z], q)) return VBM_EHIP;
+    return VBM_OK;
+}
+
+// A decoder of one setup (ds), or a mixed one (ds null) with a table of table_cap classes of up to max_channels
+// channels and blocks of up to max_blocksize
+int create(vbm_decoder **out, const vbm_decode_setup *ds, int table_cap, int max_channels, int max_blocksize,
+           int nstreams, int max_batch, int halfrate)
+{
+    if (!out || nstreams <= 0 || max_batch <= 0) return VBM_EINVAL;
+    if (halfrate != 0 && halfrate != 1) { g_vbm_err = "halfrate must be 0 or 1"; return VBM_EINVAL; }
+    *out = nullptr;
+    const int ndev = vbm_device_count();
+    if (ndev < 0) return ndev;
+    if (ndev == 0) {
+        g_vbm_err = "no HIP device: the MI355X decode path has no CPU fallback";
+        return VBM_ENODEV;
+    }
+    vbm_decoder *d = new vbm_decoder();
+    auto fail = [d](int rc) { free_decoder(d); return rc; };
+    d->S = nstreams;
+    d->cap = max_batch;
+    d->halfrate = halfrate;
+    d->mixed = ds ? 0 : 1;
+    if (ds) {
+        d->hs = ds->s;
+        d->size[0] = ds->s.blocksizes[0];
+        d->size[1] = ds->s.blocksizes[1];
+        d->max_classes = ds->s.max_classes;
+    } else {
+        d->hs = vbmd_setup();
+        d->nz = 0;
+        for (int bs = 256; bs <= max_blocksize; bs *= 2) d->size[d->nz++] = bs;
+        // vbmd_setup_parse's bound for the largest setup the caps allow: one class byte per partition, grouping >= 1
+        d->max_classes = max_channels * (max_blocksize / 2);
+        d->table_cap = table_cap;
+        d->classes.reserve((size_t)table_cap);
+        d->table.reserve((size_t)table_cap);
+        d->scls.assign((size_t)nstreams, -1);
+    }
+    d->ch = ds ? ds->s.channels : max_channels;
+    const int largest = d->size[d->nz - 1];
+    d->half = largest / 2;
+    d->n1 = largest >> halfrate;
+    d->ohalf = d->half >> halfrate;
+    const size_t cap = (size_t)max_batch, ch = (size_t)d->ch;
+    if (ds) {
+        const size_t setup_bytes = sizeof(vbmd_setup) + ds->blob.size();
+        CK(hipMalloc((void **)&d->d_setup, setup_bytes));
+        CK(hipMemcpy(d->d_setup, &ds->s, sizeof(vbmd_setup), hipMemcpyHostToDevice));
+        if (!ds->blob.empty())
+            CK(hipMemcpy(d->d_setup + sizeof(vbmd_setup), ds->blob.data(), ds->blob.size(), hipMemcpyHostToDevice));
+    }
+    // tables: FLOOR1_fromdB_LOOKUP, the windows, the MDCT trig tables (lib/mdct.c:67-76); at half rate the windows and
+    // transforms of half each block size (lib/block.c:208-209, _vorbis_window_get(b->window[W] - hs))
+    std::vector<float> tab, mixed_win[VBMD_SIZES];
+    if (ds) {
+        tab = ds->fromdB;
+    } else {
+        int sizes[VBMD_SIZES];
+        std::vector<float> *wins[VBMD_SIZES];
+        for (int z = 0; z < d->nz; z++) {
+            sizes[z] = d->size[z] >> halfrate;
+            wins[z] = &mixed_win[z];
+        }
+        const int rc = vbmd_common_tables(&tab, d->nz, sizes, wins);
+        if (rc) return fail(rc);
+    }
+    size_t off_win[VBMD_SIZES], off_trig[VBMD_SIZES];
+    for (int z = 0; z < d->nz; z++) {
+        const std::vector<float> &win = !ds ? mixed_win[z] : halfrate ? ds->hwin[z] : ds->win[z];
+        off_win[z] = tab.size();
+        tab.insert(tab.end(), win.begin(), win.end());
+    }
+    for (int z = 0; z < d->nz; z++) {
+        const int n = d->size[z] >> halfrate;
+        std::vector<float> t((size_t)n + n / 4);
+        vbm_host_mdct_trig(n, t.data());
+        while (tab.size() % 4) tab.push_back(0.f);
+        off_trig[z] = tab.size();
+        tab.insert(tab.end(), t.begin(), t.end());
+    }
+    CK(hipMalloc((void **)&d->d_tables, tab.size() * sizeof(float)));
+    CK(hipMemcpy(d->d_tables, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    d->fromdB = d->d_tables;
+    for (int z = 0; z < d->nz; z++) {
+        d->win[z] = d->d_tables + off_win[z];
+        d->trig[z] = d->d_tables + off_trig[z];
+    }
+    const size_t row_classes = d->mixed ? cap : 0;           // the rows' classes travel behind the ids / the run table
+    CK(hipMalloc((void **)&d->d_ids, (cap + row_classes) * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_info, cap * 4 * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_fit, cap * ch * VBMD_POSTS * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_flags, cap * ch * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_status, cap * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_lists, (d->mixed ? d->nz * cap * ch : 2 * cap) * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_counts, VBMD_SIZES * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_res, cap * ch * d->half * sizeof(float)));
+    CK(hipMalloc((void **)&d->d_spec, cap * ch * d->half * sizeof(float)));
+    CK(hipMalloc((void **)&d->d_imdct, cap * ch * d->n1 * sizeof(float)));
+    CK(hipMalloc((void **)&d->d_cls, cap * (size_t)d->max_classes));
+    CK(hipMalloc((void **)&d->d_tail, (size_t)nstreams * ch * d->ohalf * sizeof(float)));
+    CK(hipMalloc((void **)&d->d_prevW, (size_t)nstreams * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_gp, (size_t)nstreams * sizeof(long long)));
+    CK(hipMalloc((void **)&d->d_sc, (size_t)nstreams * sizeof(long long)));
+    // range piece tables: at most cap / 2 pieces (each has two rows or more) of 7 ints, and the row starts
+    const size_t runtab = 2 * (size_t)nstreams + 1 + row_classes, rtab = 4 * cap + 1, stage = rtab > runtab ? rtab : runtab;
+    CK(hipMalloc((void **)&d->d_runtab, runtab * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_plan, cap * 6 * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_run_last, (size_t)nstreams * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_rtab, rtab * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_rows, cap * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_zero, cap * sizeof(int)));
+    CK(hipMemset(d->d_zero, 0, cap * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_itab, stage * sizeof(int)));
+    d->stage_ints = stage;
+    if (d->mixed) {
+        CK(hipMalloc((void **)&d->d_table, (size_t)table_cap * sizeof(vbmd_class)));
+        CK(hipMemset(d->d_table, 0, (size_t)table_cap * sizeof(vbmd_class)));
+        CK(hipMalloc((void **)&d->d_scls, (size_t)nstreams * sizeof(int)));
+        CK(hipMemset(d->d_scls, 0xff, (size_t)nstreams * sizeof(int)));
+    }
+    for (int i = 0; i < kStage; i++) {
+        CK(hipHostMalloc((void **)&d->h_stage[i], stage * sizeof(int), hipHostMallocDefault));
+        CK(hipEventCreateWithFlags(&d->ev_stage[i], hipEventDisableTiming));
+    }
+    const int rc = vbm_decoder_reset(d);
+    if (rc) return fail(rc);
+    *out = d;
     return VBM_OK;
 }
 
@@ -178,89 +365,92 @@ extern "C" int vbm_decoder_halfrate(const vbm_decoder *d) { return d ? d->halfra
 extern "C" int vbm_decoder_create_halfrate(vbm_decoder **out, const vbm_decode_setup *ds, int nstreams, int max_batch,
                                            int halfrate)
 {
-    if (!out || !ds || nstreams <= 0 || max_batch <= 0) return VBM_EINVAL;
-    if (halfrate != 0 && halfrate != 1) { g_vbm_err = "halfrate must be 0 or 1"; return VBM_EINVAL; }
-    *out = nullptr;
-    const int ndev = vbm_device_count();
-    if (ndev < 0) return ndev;
-    if (ndev == 0) {
-        g_vbm_err = "no HIP device: the MI355X decode path has no CPU fallback";
-        return VBM_ENODEV;
+    if (!ds) return VBM_EINVAL;
+    return create(out, ds, 0, 0, 0, nstreams, max_batch, halfrate);
+}
+
+extern "C" int vbm_decoder_create_mixed(vbm_decoder **out, int max_classes, int max_channels, int max_blocksize,
+                                        int nstreams, int max_batch, int halfrate)
+{
+    if (max_classes <= 0) { g_vbm_err = "max_classes must be positive"; return VBM_EINVAL; }
+    if (max_channels < 1 || max_channels > VBMD_MAXCH) { g_vbm_err = "max_channels must be 1..8"; return VBM_EINVAL; }
+    if (max_blocksize < 256 || max_blocksize > 4096 || (max_blocksize & (max_blocksize - 1))) {
+        g_vbm_err = "max_blocksize must be a power of two in 256..4096";
+        return VBM_EINVAL;
     }
-    vbm_decoder *d = new vbm_decoder();
-    d->hs = ds->s;
-    d->S = nstreams;
-    d->cap = max_batch;
-    d->ch = ds->s.channels;
-    d->halfrate = halfrate;
-    d->half = ds->s.blocksizes[1] / 2;
-    d->n1 = ds->s.blocksizes[1] >> halfrate;
-    d->ohalf = d->half >> halfrate;
-    d->max_classes = ds->s.max_classes;
-    const size_t cap = (size_t)max_batch, ch = (size_t)d->ch;
-    auto fail = [d](int rc) { free_decoder(d); return rc; };
-    const size_t setup_bytes = sizeof(vbmd_setup) + ds->blob.size();
-    CK(hipMalloc((void **)&d->d_setup, setup_bytes));
-    CK(hipMemcpy(d->d_setup, &ds->s, sizeof(vbmd_setup), hipMemcpyHostToDevice));
-    if (!ds->blob.empty())
-        CK(hipMemcpy(d->d_setup + sizeof(vbmd_setup), ds->blob.data(), ds->blob.size(), hipMemcpyHostToDevice));
-    // tables: FLOOR1_fromdB_LOOKUP, the two windows, the two MDCT trig tables (lib/mdct.c:67-76); at half rate the
-    // windows and transforms of half each block size (lib/block.c:208-209, _vorbis_window_get(b->window[W] - hs))
-    std::vector<float> tab(ds->fromdB);
-    size_t off_win[2], off_trig[2];
-    for (int w = 0; w < 2; w++) {
-        const std::vector<float> &win = halfrate ? ds->hwin[w] : ds->win[w];
-        off_win[w] = tab.size();
-        tab.insert(tab.end(), win.begin(), win.end());
+    return create(out, nullptr, max_classes, max_channels, max_blocksize, nstreams, max_batch, halfrate);
+}
+
+extern "C" int vbm_decoder_add_class(vbm_decoder *d, const vbm_decode_setup *ds, int *class_id, void *stream)
+{
+    if (!d || !ds || !class_id) return VBM_EINVAL;
+    if (!d->mixed) { g_vbm_err = "vbm_decoder_add_class needs a decoder of vbm_decoder_create_mixed"; return VBM_EINVAL; }
+    if (ds->s.channels > d->ch) {
+        g_vbm_err = "the class has " + std::to_string(ds->s.channels) + " channels, the decoder's max_channels is " +
+                    std::to_string(d->ch);
+        return VBM_EINVAL;
     }
-    for (int w = 0; w < 2; w++) {
-        const int n = ds->s.blocksizes[w] >> halfrate;
-        std::vector<float> t((size_t)n + n / 4);
-        vbm_host_mdct_trig(n, t.data());
-        while (tab.size() % 4) tab.push_back(0.f);
-        off_trig[w] = tab.size();
-        tab.insert(tab.end(), t.begin(), t.end());
+    if (ds->s.blocksizes[1] > d->size[d->nz - 1]) {
+        g_vbm_err = "the class has blocks of " + std::to_string(ds->s.blocksizes[1]) +
+                    ", the decoder's max_blocksize is " + std::to_string(d->size[d->nz - 1]);
+        return VBM_EINVAL;
     }
-    CK(hipMalloc((void **)&d->d_tables, tab.size() * sizeof(float)));
-    CK(hipMemcpy(d->d_tables, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-    d->fromdB = d->d_tables;
-    for (int w = 0; w < 2; w++) {
-        d->win[w] = d->d_tables + off_win[w];
-        d->trig[w] = d->d_tables + off_trig[w];
+    if (ds->s.max_classes > d->max_classes) { g_vbm_err = "the class needs more partition scratch than the caps give"; return VBM_EINVAL; }
+    if ((int)d->classes.size() >= d->table_cap) {
+        g_vbm_err = "the class table is full (max_classes " + std::to_string(d->table_cap) + ")";
+        return VBM_EINVAL;
     }
-    CK(hipMalloc((void **)&d->d_ids, cap * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_info, cap * 4 * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_fit, cap * ch * VBMD_POSTS * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_flags, cap * ch * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_status, cap * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_lists, 2 * cap * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_counts, 2 * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_res, cap * ch * d->half * sizeof(float)));
-    CK(hipMalloc((void **)&d->d_spec, cap * ch * d->half * sizeof(float)));
-    CK(hipMalloc((void **)&d->d_imdct, cap * ch * d->n1 * sizeof(float)));
-    CK(hipMalloc((void **)&d->d_cls, cap * (size_t)d->max_classes));
-    CK(hipMalloc((void **)&d->d_tail, (size_t)nstreams * ch * d->ohalf * sizeof(float)));
-    CK(hipMalloc((void **)&d->d_prevW, (size_t)nstreams * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_gp, (size_t)nstreams * sizeof(long long)));
-    CK(hipMalloc((void **)&d->d_sc, (size_t)nstreams * sizeof(long long)));
-    // range piece tables: at most cap / 2 pieces (each has two rows or more) of 7 ints, and the row starts
-    const size_t runtab = 2 * (size_t)nstreams + 1, rtab = 4 * cap + 1, stage = rtab > runtab ? rtab : runtab;
-    CK(hipMalloc((void **)&d->d_runtab, runtab * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_plan, cap * 6 * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_run_last, (size_t)nstreams * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_rtab, rtab * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_rows, cap * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_zero, cap * sizeof(int)));
-    CK(hipMemset(d->d_zero, 0, cap * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_itab, stage * sizeof(int)));
-    d->stage_ints = stage;
-    for (int i = 0; i < kStage; i++) {
-        CK(hipHostMalloc((void **)&d->h_stage[i], stage * sizeof(int), hipHostMallocDefault));
-        CK(hipEventCreateWithFlags(&d->ev_stage[i], hipEventDisableTiming));
+    const int id = (int)d->classes.size();
+    vbm_decoder::klass k;
+    k.ch = ds->s.channels;
+    k.bs[0] = ds->s.blocksizes[0];
+    k.bs[1] = ds->s.blocksizes[1];
+    k.image.resize(sizeof(vbmd_setup) + ds->blob.size());
+    memcpy(k.image.data(), &ds->s, sizeof(vbmd_setup));
+    if (!ds->blob.empty()) memcpy(k.image.data() + sizeof(vbmd_setup), ds->blob.data(), ds->blob.size());
+    k.d_image = nullptr;
+    hipError_t e = hipMalloc((void **)&k.d_image, k.image.size());
+    if (e != hipSuccess) return vbm_set_hip_error(e, "hipMalloc(class)");
+    // slot `id` is new to the device: no call in flight reads it, and no slot below it is written.  The sources of the
+    // two copies live as long as the decoder and never move.  They are pageable, so the runtime may stage them before it
+    // returns: the copies are ordered on the stream, but the host may wait for the staging.
+    d->classes.push_back(std::move(k));
+    const vbm_decoder::klass &kk = d->classes.back();
+    d->table.push_back({(const vbmd_setup *)kk.d_image, kk.d_image + sizeof(vbmd_setup)});
+    hipStream_t q = (hipStream_t)stream;
+    e = hipMemcpyAsync(kk.d_image, kk.image.data(), kk.image.size(), hipMemcpyHostToDevice, q);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d->d_table + id, &d->table[id], sizeof(vbmd_class), hipMemcpyHostToDevice, q);
+    if (e != hipSuccess) {
+        // the host table must not name a class the device slot lacks: wait out whatever copy did start, then take the
+        // entry back, so that the next add gets this slot
+        (void)hipStreamSynchronize(q);
+        (void)hipFree(kk.d_image);
+        d->table.pop_back();
+        d->classes.pop_back();
+        return vbm_set_hip_error(e, "hipMemcpyAsync(class)");
     }
-    const int rc = vbm_decoder_reset(d);
-    if (rc) return fail(rc);
-    *out = d;
+    *class_id = id;
+    return VBM_OK;
+}
+
+extern "C" int vbm_decoder_bind_streams(vbm_decoder *d, int n, const int *stream_ids, const int *class_ids, void *stream)
+{
+    if (!d || n < 0 || n > d->cap || (n > 0 && (!stream_ids || !class_ids))) return VBM_EINVAL;
+    if (!d->mixed) { g_vbm_err = "vbm_decoder_bind_streams needs a decoder of vbm_decoder_create_mixed"; return VBM_EINVAL; }
+    if (n == 0) return VBM_OK;
+    int rc = check_ids(d, n, stream_ids);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)
+        if (class_ids[i] < 0 || class_ids[i] >= (int)d->classes.size()) { g_vbm_err = "class id out of range"; return VBM_EINVAL; }
+    hipStream_t q = (hipStream_t)stream;
+    rc = stage(d, d->d_ids, 2 * (size_t)n, q, [&](int *slot) {
+        memcpy(slot, stream_ids, (size_t)n * sizeof(int));
+        memcpy(slot + n, class_ids, (size_t)n * sizeof(int));
+    });
+    if (rc) return rc;
+    if (vbmd_launch_restart(d->d_ids, n, d->d_prevW, d->d_gp, d->d_sc, d->d_ids + n, d->d_scls, q)) return VBM_EHIP;
+    for (int i = 0; i < n; i++) d->scls[stream_ids[i]] = class_ids[i];
     return VBM_OK;
 }
 
@@ -293,7 +483,7 @@ extern "C" int vbm_decoder_restart_streams(vbm_decoder *d, int n, const int *str
     if (rc) return rc;
     hipStream_t q = (hipStream_t)stream;
     if ((rc = stage_ints(d, d->d_ids, stream_ids, (size_t)n, q))) return rc;
-    return vbmd_launch_restart(d->d_ids, n, d->d_prevW, d->d_gp, d->d_sc, q) ? VBM_EHIP : VBM_OK;
+    return vbmd_launch_restart(d->d_ids, n, d->d_prevW, d->d_gp, d->d_sc, nullptr, nullptr, q) ? VBM_EHIP : VBM_OK;
 }
 
 extern "C" int vbm_synthesis_batch(vbm_decoder *d, int nsb, const int *stream_ids, const uint8_t *d_packets,
@@ -303,11 +493,23 @@ extern "C" int vbm_synthesis_batch(vbm_decoder *d, int nsb, const int *stream_id
     if (!d || nsb <= 0 || nsb > d->cap || !stream_ids || !d_packets || packet_stride <= 0 || !d_packet_bytes ||
         !d_pcm || !d_samples || !d_status)
         return VBM_EINVAL;
-    int rc = check_ids(d, nsb, stream_ids);
+    int rc = check_call_ids(d, nsb, stream_ids);
     if (rc) return rc;
     hipStream_t q = (hipStream_t)stream;
-    if ((rc = stage_ints(d, d->d_ids, stream_ids, (size_t)nsb, q))) return rc;
-    const vbmd_launch L = d->launch(nsb);
+    long nblocks = 0;
+    if (d->mixed) {
+        rc = stage(d, d->d_ids, 2 * (size_t)nsb, q, [&](int *slot) {                // the ids, then the rows' classes
+            memcpy(slot, stream_ids, (size_t)nsb * sizeof(int));
+            for (int k = 0; k < nsb; k++) {
+                slot[nsb + k] = d->scls[stream_ids[k]];
+                nblocks += d->classes[slot[nsb + k]].ch;
+            }
+        });
+    } else {
+        rc = stage_ints(d, d->d_ids, stream_ids, (size_t)nsb, q);
+    }
+    if (rc) return rc;
+    const vbmd_launch L = d->launch(nsb, d->d_ids + nsb, nblocks);
     rc = enqueue_front(d, L, q, "hipMemsetAsync(decode)",
                        [&] { return vbmd_launch_unpack(L, d_packets, packet_stride, d_packet_bytes, d_status, q); });
     if (rc) return rc;
@@ -336,33 +538,44 @@ extern "C" int vbm_synthesis_runs_gaps(vbm_decoder *d, int nruns, const int *str
         return VBM_EINVAL;
     if (nruns == 0) return VBM_OK;
     if (nruns > d->S) { g_vbm_err = "more runs than streams"; return VBM_EINVAL; }
-    int rc = check_ids(d, nruns, stream_ids);
+    int rc = check_call_ids(d, nruns, stream_ids);
     if (rc) return rc;
     d->run_start.resize((size_t)nruns + 1);
     long long P = 0;
-    int most = 0;
+    long need = 0, nblocks = 0;                            // the longest run's samples; rows x channels (mixed)
     for (int r = 0; r < nruns; r++) {
         if (run_packets[r] < 0) { g_vbm_err = "negative packet count"; return VBM_EINVAL; }
         d->run_start[r] = (int)P;
         P += run_packets[r];
         if (P > d->cap) { g_vbm_err = "more packets than max_batch in one call"; return VBM_EINVAL; }
-        if (run_packets[r] > most) most = run_packets[r];
+        long row = d->ohalf;
+        if (d->mixed) {
+            const vbm_decoder::klass &k = d->classes[d->scls[stream_ids[r]]];
+            row = k.bs[1] >> (1 + d->halfrate);
+            nblocks += (long)run_packets[r] * k.ch;
+        }
+        need = std::max(need, run_packets[r] * row);
     }
     d->run_start[nruns] = (int)P;
     if (P > 0 && (!d_pcm || !d_samples || !d_status)) return VBM_EINVAL;
-    if (pcm_stride < (long)most * d->ohalf) {
+    if (pcm_stride < need) {
         g_vbm_err = d->halfrate ? "pcm_stride below max(run_packets) * blocksizes[1]/4"
                                 : "pcm_stride below max(run_packets) * blocksizes[1]/2";
         return VBM_EINVAL;
     }
     hipStream_t q = (hipStream_t)stream;
-    rc = stage(d, d->d_runtab, 2 * (size_t)nruns + 1, q, [&](int *slot) {      // the run table: ids, then run starts
+    const int nsb = (int)P;
+    const size_t tab = 2 * (size_t)nruns + 1;
+    // the run table: ids, then run starts; in a mixed decoder the rows' classes behind it
+    rc = stage(d, d->d_runtab, tab + (d->mixed ? (size_t)nsb : 0), q, [&](int *slot) {
         memcpy(slot, stream_ids, (size_t)nruns * sizeof(int));
         memcpy(slot + nruns, d->run_start.data(), ((size_t)nruns + 1) * sizeof(int));
+        if (d->mixed)
+            for (int r = 0; r < nruns; r++)
+                std::fill(slot + tab + d->run_start[r], slot + tab + d->run_start[r + 1], d->scls[stream_ids[r]]);
     });
     if (rc) return rc;
-    const int nsb = (int)P;
-    const vbmd_launch L = d->launch(nsb);
+    const vbmd_launch L = d->launch(nsb, d->d_runtab + tab, nblocks);
     rc = enqueue_front(d, L, q, "hipMemsetAsync(decode runs)",
                        [&] { return vbmd_launch_unpack_csr(L, d_data, d_offsets, data_bytes, d_status, q); });
     if (rc) return rc;
@@ -375,6 +588,7 @@ extern "C" int vbm_synthesis_runs_gaps(vbm_decoder *d, int nruns, const int *str
 
 extern "C" int vbm_decoder_fetch(vbm_decoder *d, const char *name, void *d_out, long *rows, char *kind, void *stream)
 {
+    if (refuse_mixed(d, "vbm_decoder_fetch")) return VBM_EINVAL;
     if (!d || !name || d->last_nsb <= 0) return VBM_EINVAL;
     hipStream_t q = (hipStream_t)stream;
     const int nsb = d->last_nsb;
@@ -430,6 +644,7 @@ int check_csr(const vbm_decoder *d, int nstreams, const long long *stream_packet
 {
     if (!d || nstreams <= 0 || !stream_packets || data_bytes < 0 || (data_bytes > 0 && !data) || !offsets)
         return VBM_EINVAL;
+    if (refuse_mixed(d, "a range store or device index")) return VBM_EINVAL;
     if (stream_packets[0] != 0) { g_vbm_err = "stream_packets[0] must be 0"; return VBM_EINVAL; }
     for (int i = 0; i < nstreams; i++)
         if (stream_packets[i + 1] < stream_packets[i]) { g_vbm_err = "stream_packets must not decrease"; return VBM_EINVAL; }
@@ -542,6 +757,7 @@ extern "C" int vbm_synthesis_ranges(vbm_decoder *d, const vbm_range_store *st, i
                                     const long long *starts, const int *lengths, float *d_pcm, long pcm_stride,
                                     int *got, void *stream)
 {
+    if (refuse_mixed(d, "vbm_synthesis_ranges")) return VBM_EINVAL;
     if (!d || !st || nranges < 0 || (nranges > 0 && (!stream_ids || !starts || !lengths || !got)))
         return VBM_EINVAL;
     if (st->dec != d) { g_vbm_err = "the range store belongs to another decoder"; return VBM_EINVAL; }

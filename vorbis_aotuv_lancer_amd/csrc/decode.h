@@ -379,7 +379,8 @@ VBMD_HD void vbmd_blockin(const int *blocksizes, int lW, int W, long long vgp, i
 //   flags        [channels] bit 0: the channel's floor is coded, bit 1: nonzero after the coupling propagation
 //   res          [channels][stride] residue before inverse coupling; must be zero on entry (bins < blocksize/2 used)
 //   cls          partition-class scratch, s.max_classes bytes
-// Copy: one instantiation per kernel that calls it (k_unpack the default, k_unpack_csr 1, k_unpack_rows 2), so that
+// Copy: one instantiation per kernel that calls it (k_unpack the default, k_unpack_csr 1, k_unpack_rows 2, the mixed
+// forms of the first two 3 and 4), so that
 // each has a single call site and is inlined as it was with one caller, instead of becoming a shared out-of-line
 // function.
 template <int Copy = 0>

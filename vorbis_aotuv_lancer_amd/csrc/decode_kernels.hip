@@ -29,6 +29,13 @@
 // spectrum are the same launches at the full block size; k_imdct<blocksizes[W] / 2> transforms the lower half of each
 // spectrum (128 .. 2048 points) and k_overlap<1>, k_run_plan<1>, k_overlap_runs<1> and k_run_commit<1> are the overlap
 // kernels with every size halved.  A full-rate decoder launches the <0> instantiations, in which every shift is by zero.
+//
+// Mixed decoders (vbm_decoder_create_mixed): the rows of one call may belong to different header classes.  Every kernel
+// that reads the setup is a template on MX: the <false> instantiation is the single-class kernel, with the decoder's one
+// setup and rows of `channels` channels; the <true> one takes its row's setup and blob from the class table
+// (vbmd_mixed: by the row's class, or in k_run_plan / k_run_commit by the stream's) and addresses rows of M.CH channels
+// and `half` = max_blocksize / 2 bins, of which a row uses its class's.  The block lists are then one per transform size
+// (size_index) and hold blocks row * CH + c, and the windows come from the per-size tables.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -42,8 +49,55 @@ using namespace vbm_mdct;
 
 constexpr int IM_WAVES = 4;
 
+// list of a block size in a mixed decoder: 256 -> 0 .. 4096 -> 4
+__device__ __forceinline__ int size_index(int blocksize) { return 23 - __clz(blocksize); }
+
+template <bool MX>
+__device__ __forceinline__ const vbmd_setup *setup_of(const vbmd_setup *s, const vbmd_mixed &M, int cls)
+{
+    return MX ? M.table[cls].s : s;
+}
+
+// Row k of every unpack kernel: vbmd_unpack of its bytes, its status, and its entry in the block lists.  Single class:
+// the row joins list W.  Mixed: its channels join the list of its transform size as blocks k * CH + c.  Out: the call
+// has a status_out of the caller's beside the decoder's own status.
+template <bool MX, int Copy, bool Out = true>
+__device__ __forceinline__ void unpack_row(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob,
+                                           const vbmd_mixed &M, int k, int nsb, const uint8_t *pkt, long nb,
+                                           int *__restrict__ info, int *__restrict__ fit, int *__restrict__ flags,
+                                           float *__restrict__ res, long half, uint8_t *__restrict__ cls,
+                                           int *__restrict__ status, int *__restrict__ status_out,
+                                           int *__restrict__ lists, int *__restrict__ counts)
+{
+    if (MX) {
+        const vbmd_class &c = M.table[M.rcls[k]];
+        s = c.s;
+        blob = c.blob;
+    }
+    const int ch = s->channels, CH = MX ? M.CH : ch;
+    const long cls_bytes = MX ? M.cls_bytes : s->max_classes;
+    // an instantiation of vbmd_unpack per kernel (decode.h): as a shared out-of-line function it costs each kernel
+    // 75 more VGPRs and half its occupancy
+    const int st = vbmd_unpack<MX ? 3 + Copy : Copy>(*s, blob, pkt, nb, info + 4 * k, fit + (long)k * CH * VBMD_POSTS,
+                                                     flags + (long)k * CH, res + (long)k * CH * half, half,
+                                                     cls + (long)k * cls_bytes);
+    status[k] = st;
+    if (Out) status_out[k] = st;
+    if (st != 0) return;
+    const int W = info[4 * k + 1];
+    if (MX) {
+        const int z = size_index(s->blocksizes[W]);
+        const int pos = atomicAdd(&counts[z], ch);
+        for (int c = 0; c < ch; c++) lists[z * M.list_stride + pos + c] = k * CH + c;
+    } else {
+        const int pos = atomicAdd(&counts[W], 1);
+        lists[(long)W * nsb + pos] = k;
+    }
+}
+
+template <bool MX>
 __global__ __launch_bounds__(64)
-void k_unpack(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob, int nsb,
+void k_unpack(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob, vbmd_mixed M, int nsb,
               const uint8_t *__restrict__ packets, long stride, const int *__restrict__ nbytes, int *__restrict__ info,
               int *__restrict__ fit, int *__restrict__ flags, float *__restrict__ res, long half,
               uint8_t *__restrict__ cls, int *__restrict__ status, int *__restrict__ status_out,
@@ -51,24 +105,17 @@ void k_unpack(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nsb) return;
-    const int ch = s->channels;
     long nb = nbytes[k];
     if (nb > stride) nb = stride;          // never past the row's storage either
     if (nb < 0) nb = 0;
-    const int st = vbmd_unpack(*s, blob, packets + (long)k * stride, nb, info + 4 * k, fit + (long)k * ch * VBMD_POSTS,
-                               flags + (long)k * ch, res + (long)k * ch * half, half, cls + (long)k * s->max_classes);
-    status[k] = st;
-    status_out[k] = st;
-    if (st == 0) {
-        const int W = info[4 * k + 1];
-        const int pos = atomicAdd(&counts[W], 1);
-        lists[(long)W * nsb + pos] = k;
-    }
+    unpack_row<MX, 0>(s, blob, M, k, nsb, packets + (long)k * stride, nb, info, fit, flags, res, half, cls, status,
+                      status_out, lists, counts);
 }
 
 // k_unpack over CSR rows: packet k is data[offsets[k] .. offsets[k+1]), clamped to [0, data_bytes)
+template <bool MX>
 __global__ __launch_bounds__(64)
-void k_unpack_csr(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob, int nsb,
+void k_unpack_csr(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob, vbmd_mixed M, int nsb,
                   const uint8_t *__restrict__ data, const long long *__restrict__ offsets, long long data_bytes,
                   int *__restrict__ info, int *__restrict__ fit, int *__restrict__ flags, float *__restrict__ res,
                   long half, uint8_t *__restrict__ cls, int *__restrict__ status, int *__restrict__ status_out,
@@ -76,19 +123,11 @@ void k_unpack_csr(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ 
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nsb) return;
-    const int ch = s->channels;
     long long b = offsets[k], e = offsets[k + 1];
     b = b < 0 ? 0 : b > data_bytes ? data_bytes : b;
     e = e < b ? b : e > data_bytes ? data_bytes : e;
-    const int st = vbmd_unpack<1>(*s, blob, data + b, (long)(e - b), info + 4 * k, fit + (long)k * ch * VBMD_POSTS,
-                                  flags + (long)k * ch, res + (long)k * ch * half, half, cls + (long)k * s->max_classes);
-    status[k] = st;
-    status_out[k] = st;
-    if (st == 0) {
-        const int W = info[4 * k + 1];
-        const int pos = atomicAdd(&counts[W], 1);
-        lists[(long)W * nsb + pos] = k;
-    }
+    unpack_row<MX, 1>(s, blob, M, k, nsb, data + b, (long)(e - b), info, fit, flags, res, half, cls, status, status_out,
+                      lists, counts);
 }
 
 // floor index at bin j of the used-post polyline (segx strictly ascending, segx[0] = 0): render_line's Bresenham
@@ -112,16 +151,19 @@ __device__ __forceinline__ int floor_at(const int *segx, const int *segy, int m,
     return y0 + kx * base + (dy < 0 ? -wraps : wraps);
 }
 
+template <bool MX>
 __global__ __launch_bounds__(256)
-void k_spectrum(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict__ status, const int *__restrict__ info,
+void k_spectrum(const vbmd_setup *__restrict__ s, vbmd_mixed M, int nsb, const int *__restrict__ status,
+                const int *__restrict__ info,
                 const int *__restrict__ fit, const int *__restrict__ flags, const float *__restrict__ res,
                 const float *__restrict__ fromdB, float *__restrict__ spec, int *__restrict__ findex, long half)
 {
     __shared__ int segx[VBMD_MAXCH][VBMD_POSTS + 1], segy[VBMD_MAXCH][VBMD_POSTS + 1], nseg[VBMD_MAXCH];
     __shared__ int s_flags[VBMD_MAXCH];
     const int row = blockIdx.x, tid = threadIdx.x;
-    const int ch = s->channels;
-    const long rbase = (long)row * ch * half;
+    if (MX) s = M.table[M.rcls[row]].s;
+    const int ch = s->channels, CH = MX ? M.CH : ch;
+    const long rbase = (long)row * CH * half;
     if (status[row] != 0) {
         for (long i = tid; i < ch * half; i += blockDim.x) {
             if (spec) spec[rbase + i] = 0.f;
@@ -134,12 +176,12 @@ void k_spectrum(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict
     const vbmd_mapping &m = s->map[s->mode_mapping[mode]];
     if (tid < ch) {
         const int c = tid;
-        const int fl = flags[(long)row * ch + c];
+        const int fl = flags[(long)row * CH + c];
         s_flags[c] = fl;
         int cnt = 0;
         if (fl & 1) {
             const vbmd_floor &f = s->floor[m.floorsub[m.mux[c]]];
-            const int *fv = fit + ((long)row * ch + c) * VBMD_POSTS;
+            const int *fv = fit + ((long)row * CH + c) * VBMD_POSTS;
             int ly = fv[0] * f.mult;
             ly = ly < 0 ? 0 : ly > 255 ? 255 : ly;
             segx[c][0] = 0;
@@ -224,10 +266,18 @@ __device__ __forceinline__ void store_rev4(float *o, const float *v)   // o[0..3
     *reinterpret_cast<float4 *>(o) = make_float4(v[3], v[2], v[1], v[0]);
 }
 
+// entry blk of a transform's list -> its block, row * channels + channel, of the spectrum and IMDCT buffers
+template <bool MX>
+__device__ __forceinline__ long block_of(const int *__restrict__ list, long blk, int ch)
+{
+    return MX ? (long)list[blk] : (long)list[blk / ch] * ch + blk % ch;
+}
+
 // one wavefront per 512-complex group (BPG blocks of N = 128 .. 2048; 128 only in a half-rate decoder, whose transform
 // of a 256-sample block it is); blocks b of the row list of this block size.  Reads in[0, N/2) of each block's `half`
-// bins and writes N floats of its n1-float output row.
-template <int N>
+// bins and writes N floats of its n1-float output row.  MX: the list holds the blocks themselves (row * CH + channel),
+// *count of them, so a group may hold blocks of rows of different classes; a size with no blocks ends at once.
+template <int N, bool MX>
 __global__ __launch_bounds__(64 * IM_WAVES)
 void k_imdct(const float *__restrict__ spec, float *__restrict__ out, const int *__restrict__ list,
              const int *__restrict__ count, int ch, long half, long n1, const float *__restrict__ trig_g)
@@ -237,9 +287,10 @@ void k_imdct(const float *__restrict__ spec, float *__restrict__ out, const int 
     __shared__ __attribute__((aligned(16))) float s_trig[NTRIG];
     __shared__ __attribute__((aligned(16))) float2 s_x[IM_WAVES][SLOTS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (MX && *count == 0) return;
     for (int i = tid; i < NTRIG; i += blockDim.x) s_trig[i] = trig_g[i];
     __syncthreads();
-    const long nblocks = (long)(*count) * ch;
+    const long nblocks = MX ? (long)(*count) : (long)(*count) * ch;
     const long ngroups = (nblocks + BPG - 1) / BPG;
     float2 *sx = s_x[wave];
     for (long group = (long)blockIdx.x * IM_WAVES + wave; group < ngroups; group += (long)gridDim.x * IM_WAVES) {
@@ -249,8 +300,7 @@ void k_imdct(const float *__restrict__ spec, float *__restrict__ out, const int 
             const int P = lane + 64 * k, b = P / C, p = P % C;
             const long blk = group * BPG + b;
             if (blk < nblocks) {
-                const long row = list[blk / ch];
-                const float *in = spec + (row * ch + blk % ch) * half;
+                const float *in = spec + block_of<MX>(list, blk, ch) * half;
                 c[k] = backward_rotate<N>(in, s_trig, p);
             } else {
                 c[k] = make_float2(0.f, 0.f);
@@ -275,8 +325,7 @@ void k_imdct(const float *__restrict__ spec, float *__restrict__ out, const int 
                 backward_post(wB, *reinterpret_cast<const float2 *>(s_trig + N / 2 + 2 * (C - 1 - u)), a1[r], b1[r]);
             }
             if (blk < nblocks) {
-                const long row = list[blk / ch];
-                float *o = out + (row * ch + blk % ch) * n1;
+                float *o = out + block_of<MX>(list, blk, ch) * n1;
                 float na0[4], na1[4];
 #pragma unroll
                 for (int r = 0; r < 4; r++) { na0[r] = -a0[r]; na1[r] = -a1[r]; }
@@ -295,6 +344,7 @@ void k_imdct(const float *__restrict__ spec, float *__restrict__ out, const int 
 }
 
 // 4096-point blocks: one wavefront per block, two 512-complex halves (as k_window_mdct_4096)
+template <bool MX>
 __global__ __launch_bounds__(64 * IM_WAVES)
 void k_imdct_4096(const float *__restrict__ spec, float *__restrict__ out, const int *__restrict__ list,
                   const int *__restrict__ count, int ch, long half, long n1, const float *__restrict__ trig_g)
@@ -303,14 +353,15 @@ void k_imdct_4096(const float *__restrict__ spec, float *__restrict__ out, const
     __shared__ __attribute__((aligned(16))) float s_trig[NTRIG];
     __shared__ __attribute__((aligned(16))) float2 s_x[IM_WAVES][2][SLOTS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (MX && *count == 0) return;
     for (int i = tid; i < NTRIG; i += blockDim.x) s_trig[i] = trig_g[i];
     __syncthreads();
-    const long nblocks = (long)(*count) * ch;
+    const long nblocks = MX ? (long)(*count) : (long)(*count) * ch;
     float2 *sx0 = s_x[wave][0], *sx1 = s_x[wave][1];
 #define SLOT(m) (((m) < 512 ? sx0 : sx1)[slot_addr((m) & 511)])
     for (long blk = (long)blockIdx.x * IM_WAVES + wave; blk < nblocks; blk += (long)gridDim.x * IM_WAVES) {
-        const long row = list[blk / ch];
-        const float *in = spec + (row * ch + blk % ch) * half;
+        const long block = block_of<MX>(list, blk, ch);
+        const float *in = spec + block * half;
         float2 c0[8], c1[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) {
@@ -324,7 +375,7 @@ void k_imdct_4096(const float *__restrict__ spec, float *__restrict__ out, const
         }
         radix_rounds<10>(c0, sx0, s_trig, lane);
         radix_rounds<10>(c1, sx1, s_trig, lane);
-        float *o = out + (row * ch + blk % ch) * n1;
+        float *o = out + block * n1;
 #pragma unroll
         for (int pass = 0; pass < 2; pass++) {
             const int u0 = 4 * lane + 256 * pass;
@@ -360,11 +411,12 @@ void k_imdct_4096(const float *__restrict__ spec, float *__restrict__ out, const
 
 // HS: 0, or 1 in a half-rate decoder (lib/block.c:897-1166 with hs = 1): every size is that of the halved block, n1 the
 // IMDCT row of blocksizes[1] >> HS floats, `half` the tail and PCM row of blocksizes[1] >> (1 + HS), win0 / win1 the
-// windows of the halved sizes.
-template <int HS>
+// windows of the halved sizes.  MX: `half` is the tail and PCM row of the decoder's largest block, of which the row's
+// class uses the front, and win0 / win1 are the class's own, from the per-size tables.
+template <int HS, bool MX>
 __global__ __launch_bounds__(256)
-void k_overlap(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict__ ids, const int *__restrict__ status,
-               const int *__restrict__ info, const float *__restrict__ imdct, long n1,
+void k_overlap(const vbmd_setup *__restrict__ s, vbmd_mixed M, int nsb, const int *__restrict__ ids,
+               const int *__restrict__ status, const int *__restrict__ info, const float *__restrict__ imdct, long n1,
                const float *__restrict__ win0, const float *__restrict__ win1,
                const long long *__restrict__ granulepos, const uint8_t *__restrict__ eos,
                float *__restrict__ tail, int *__restrict__ prevW, long long *__restrict__ st_gp,
@@ -375,10 +427,15 @@ void k_overlap(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict_
         if (tid == 0) samples[row] = 0;
         return;
     }
-    const int ch = s->channels, sid = ids[row];
+    if (MX) s = M.table[M.rcls[row]].s;
+    const int ch = s->channels, CH = MX ? M.CH : ch, sid = ids[row];
     const int W = info[4 * row + 1], lW = prevW[sid];
     const int bs0 = s->blocksizes[0], bs1 = s->blocksizes[1];
     const int n = s->blocksizes[W] >> (1 + HS), n0 = bs0 >> (1 + HS), nh1 = bs1 >> (1 + HS);
+    if (MX) {
+        win0 = M.win[size_index(bs0)];
+        win1 = M.win[size_index(bs1)];
+    }
     // vorbis_synthesis_blockin: what becomes final, and the granulepos bookkeeping
     long long sc = st_sc[sid], gp = st_gp[sid];
     const long long vgp = granulepos ? granulepos[row] : -1;
@@ -386,9 +443,9 @@ void k_overlap(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict_
     long begin, end;
     vbmd_blockin<HS>(s->blocksizes, lW, W, vgp, eof, sc, gp, begin, end);
     for (int c = 0; c < ch; c++) {
-        const float *p = imdct + ((long)row * ch + c) * n1;
-        float *t = tail + ((long)sid * ch + c) * half;
-        float *o = pcm + ((long)row * ch + c) * half;
+        const float *p = imdct + ((long)row * CH + c) * n1;
+        float *t = tail + ((long)sid * CH + c) * half;
+        float *o = pcm + ((long)row * CH + c) * half;
         for (long i = begin + tid; i < end; i += blockDim.x) {
             float v;
             if (lW == 1 && W == 1) {
@@ -422,9 +479,9 @@ void k_overlap(const vbmd_setup *__restrict__ s, int nsb, const int *__restrict_
 // plan[k] = {run, previous valid row of the run (-1: the stream's tail), lW, begin, end, output offset}, and samples[k].
 // The run's final prevW / granulepos / sample count go straight to the stream state: no kernel of this call reads
 // them after this one.  run_last[r]: the run's last valid row (-1: none), for k_run_commit.
-template <int HS>
+template <int HS, bool MX>
 __global__ __launch_bounds__(64)
-void k_run_plan(const vbmd_setup *__restrict__ s, int nruns, const int *__restrict__ runtab,
+void k_run_plan(const vbmd_setup *__restrict__ s, vbmd_mixed M, int nruns, const int *__restrict__ runtab,
                 const int *__restrict__ status, const int *__restrict__ info,
                 const long long *__restrict__ granulepos, const uint8_t *__restrict__ eos,
                 const uint8_t *__restrict__ gap, int *__restrict__ prevW,
@@ -434,6 +491,7 @@ void k_run_plan(const vbmd_setup *__restrict__ s, int nruns, const int *__restri
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nruns) return;
     const int sid = runtab[r], k0 = runtab[nruns + r], k1 = runtab[nruns + r + 1];
+    if (MX) s = M.table[M.scls[sid]].s;
     int lW = prevW[sid], prev = -1, off = 0;
     long long sc = st_sc[sid], gp = st_gp[sid];
     for (int k = k0; k < k1; k++) {
@@ -469,10 +527,11 @@ void k_run_plan(const vbmd_setup *__restrict__ s, int nruns, const int *__restri
 // One workgroup per row: k_overlap's overlap-add, term for term, with the tail read from the previous valid row's
 // IMDCT output (its second half, which is what k_overlap's tail copy would hold) or, for a run's first valid row,
 // from the stream's tail.  Output: the run's PCM [nruns][ch][pcm_stride] at the planned offset.
-template <int HS>
+template <int HS, bool MX>
 __global__ __launch_bounds__(256)
-void k_overlap_runs(const vbmd_setup *__restrict__ s, const int *__restrict__ runtab, const int *__restrict__ status,
-                    const int *__restrict__ info, const int *__restrict__ plan, const float *__restrict__ imdct, long n1,
+void k_overlap_runs(const vbmd_setup *__restrict__ s, vbmd_mixed M, const int *__restrict__ runtab,
+                    const int *__restrict__ status, const int *__restrict__ info, const int *__restrict__ plan,
+                    const float *__restrict__ imdct, long n1,
                     const float *__restrict__ win0, const float *__restrict__ win1, const float *__restrict__ tail,
                     float *__restrict__ pcm, long pcm_stride, long half)
 {
@@ -482,15 +541,20 @@ void k_overlap_runs(const vbmd_setup *__restrict__ s, const int *__restrict__ ru
     const int run = pl[0], prev = pl[1], lW = pl[2];
     const long begin = pl[3], end = pl[4], off = pl[5];
     if (end <= begin) return;                   // lW < 0 (end = 0) included
-    const int ch = s->channels, sid = runtab[run];
+    if (MX) s = M.table[M.rcls[row]].s;
+    const int ch = s->channels, CH = MX ? M.CH : ch, sid = runtab[run];
     const int W = info[4 * row + 1];
     const int bs0 = s->blocksizes[0], bs1 = s->blocksizes[1];
     const int n0 = bs0 >> (1 + HS), nh1 = bs1 >> (1 + HS);
+    if (MX) {
+        win0 = M.win[size_index(bs0)];
+        win1 = M.win[size_index(bs1)];
+    }
     for (int c = 0; c < ch; c++) {
-        const float *p = imdct + ((long)row * ch + c) * n1;
-        const float *t = prev >= 0 ? imdct + ((long)prev * ch + c) * n1 + (s->blocksizes[lW] >> (1 + HS))
-                                   : tail + ((long)sid * ch + c) * half;
-        float *o = pcm + ((long)run * ch + c) * pcm_stride + off;
+        const float *p = imdct + ((long)row * CH + c) * n1;
+        const float *t = prev >= 0 ? imdct + ((long)prev * CH + c) * n1 + (s->blocksizes[lW] >> (1 + HS))
+                                   : tail + ((long)sid * CH + c) * half;
+        float *o = pcm + ((long)run * CH + c) * pcm_stride + off;
         for (long i = begin + tid; i < end; i += blockDim.x) {
             float v;
             if (lW == 1 && W == 1) {
@@ -512,20 +576,21 @@ void k_overlap_runs(const vbmd_setup *__restrict__ s, const int *__restrict__ ru
 }
 
 // One workgroup per run: the second half of the run's last valid row -> the stream's tail (k_overlap's tail copy)
-template <int HS>
+template <int HS, bool MX>
 __global__ __launch_bounds__(256)
-void k_run_commit(const vbmd_setup *__restrict__ s, int nruns, const int *__restrict__ runtab,
+void k_run_commit(const vbmd_setup *__restrict__ s, vbmd_mixed M, int nruns, const int *__restrict__ runtab,
                   const int *__restrict__ run_last, const int *__restrict__ info, const float *__restrict__ imdct,
                   long n1, float *__restrict__ tail, long half)
 {
     const int r = blockIdx.x, tid = threadIdx.x;
     const int last = run_last[r];
     if (last < 0) return;
-    const int ch = s->channels, sid = runtab[r];
+    if (MX) s = M.table[M.scls[runtab[r]]].s;
+    const int ch = s->channels, CH = MX ? M.CH : ch, sid = runtab[r];
     const int n = s->blocksizes[info[4 * last + 1]] >> (1 + HS);
     for (int c = 0; c < ch; c++) {
-        const float *p = imdct + ((long)last * ch + c) * n1;
-        float *t = tail + ((long)sid * ch + c) * half;
+        const float *p = imdct + ((long)last * CH + c) * n1;
+        float *t = tail + ((long)sid * CH + c) * half;
         for (int i = tid; i < n; i += blockDim.x) t[i] = p[n + i];
     }
 }
@@ -555,19 +620,12 @@ void k_unpack_rows(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nsb) return;
-    const int ch = s->channels;
     const long j = rows[k];
     long long b = offsets[j], e = offsets[j + 1];
     b = b < 0 ? 0 : b > data_bytes ? data_bytes : b;
     e = e < b ? b : e > data_bytes ? data_bytes : e;
-    const int st = vbmd_unpack<2>(*s, blob, data + b, (long)(e - b), info + 4 * k, fit + (long)k * ch * VBMD_POSTS,
-                                  flags + (long)k * ch, res + (long)k * ch * half, half, cls + (long)k * s->max_classes);
-    status[k] = st;
-    if (st == 0) {
-        const int W = info[4 * k + 1];
-        const int pos = atomicAdd(&counts[W], 1);
-        lists[(long)W * nsb + pos] = k;
-    }
+    unpack_row<false, 2, false>(s, blob, vbmd_mixed(), k, nsb, data + b, (long)(e - b), info, fit, flags, res, half, cls,
+                         status, nullptr, lists, counts);
 }
 
 // One lane per piece: k_run_plan's plan entries, with begin / end / out_start from the store's index instead of the
@@ -609,11 +667,13 @@ void k_range_plan(int npieces, const int *__restrict__ rtab, const int *__restri
     }
 }
 
+// cls (vbm_decoder_bind_streams): the new class of each of the streams, written to the stream -> class map scls
 __global__ void k_restart(const int *__restrict__ ids, int n, int *__restrict__ prevW, long long *__restrict__ gp,
-                          long long *__restrict__ sc)
+                          long long *__restrict__ sc, const int *__restrict__ cls, int *__restrict__ scls)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
+    if (cls) scls[ids[k]] = cls[k];
     prevW[ids[k]] = -1;
     gp[ids[k]] = -1;
     sc[ids[k]] = -1;
@@ -629,11 +689,16 @@ inline int last_err() { return hipGetLastError() == hipSuccess ? 0 : -2; }
 
 }  // namespace
 
+// the instantiation of kernel K for the decoder of L: K<MX>, or K<HS, MX>
+#define PICK_MX(K) (L.mx ? K<true> : K<false>)
+#define PICK_HS_MX(K) (L.hs ? (L.mx ? K<1, true> : K<1, false>) : (L.mx ? K<0, true> : K<0, false>))
+
 int vbmd_launch_unpack(const vbmd_launch &L, const uint8_t *packets, long stride, const int *nbytes, int *status_out,
                        hipStream_t q)
 {
     if (L.nsb <= 0) return 0;
-    hipLaunchKernelGGL(k_unpack, dim3((L.nsb + 63) / 64), dim3(64), 0, q, L.s, L.blob, L.nsb, packets, stride, nbytes,
+    const auto kernel = PICK_MX(k_unpack);
+    hipLaunchKernelGGL(kernel, dim3((L.nsb + 63) / 64), dim3(64), 0, q, L.s, L.blob, L.M, L.nsb, packets, stride, nbytes,
                        L.info, L.fit, L.flags, L.res, L.half, L.cls, L.status, status_out, L.lists, L.counts);
     return last_err();
 }
@@ -641,7 +706,8 @@ int vbmd_launch_unpack(const vbmd_launch &L, const uint8_t *packets, long stride
 int vbmd_launch_spectrum(const vbmd_launch &L, float *spec, int *findex, hipStream_t q)
 {
     if (L.nsb <= 0) return 0;
-    hipLaunchKernelGGL(k_spectrum, dim3(L.nsb), dim3(256), 0, q, L.s, L.nsb, L.status, L.info, L.fit, L.flags, L.res,
+    const auto kernel = PICK_MX(k_spectrum);
+    hipLaunchKernelGGL(kernel, dim3(L.nsb), dim3(256), 0, q, L.s, L.M, L.nsb, L.status, L.info, L.fit, L.flags, L.res,
                        L.fromdB, spec, findex, L.half);
     return last_err();
 }
@@ -649,20 +715,25 @@ int vbmd_launch_spectrum(const vbmd_launch &L, float *spec, int *findex, hipStre
 int vbmd_launch_imdct(const vbmd_launch &L, int W, int N, const float *trig, hipStream_t q)
 {
     if (L.nsb <= 0) return 0;
-    const long nblocks = (long)L.nsb * L.ch;
-    const int *list = L.lists + (long)W * L.nsb, *count = L.counts + W;
+    const long nblocks = L.nblocks;
+    const int *list = L.lists + (L.mx ? W * L.M.list_stride : (long)W * L.nsb), *count = L.counts + W;
     if (N == 4096) {
         long wgs = (nblocks + IM_WAVES - 1) / IM_WAVES;
         if (wgs > 2048) wgs = 2048;
-        hipLaunchKernelGGL(k_imdct_4096, dim3((unsigned)wgs), dim3(64 * IM_WAVES), 0, q, L.spec, L.imdct, list, count,
-                           L.ch, L.half, L.n1, trig);
+        const auto kernel = PICK_MX(k_imdct_4096);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(64 * IM_WAVES), 0, q, L.spec, L.imdct, list, count, L.ch,
+                           L.half, L.n1, trig);
         return last_err();
     }
     const int bpg = 2048 / N;
     long wgs = ((nblocks + bpg - 1) / bpg + IM_WAVES - 1) / IM_WAVES;
     if (wgs > 2048) wgs = 2048;
     dim3 grid((unsigned)wgs), block(64 * IM_WAVES);
-#define LAUNCH(NN) hipLaunchKernelGGL(k_imdct<NN>, grid, block, 0, q, L.spec, L.imdct, list, count, L.ch, L.half, L.n1, trig)
+#define LAUNCH(NN) \
+    do { \
+        const auto kernel = L.mx ? k_imdct<NN, true> : k_imdct<NN, false>; \
+        hipLaunchKernelGGL(kernel, grid, block, 0, q, L.spec, L.imdct, list, count, L.ch, L.half, L.n1, trig); \
+    } while (0)
     if (N == 2048) LAUNCH(2048);
     else if (N == 1024) LAUNCH(1024);
     else if (N == 512) LAUNCH(512);
@@ -677,15 +748,17 @@ int vbmd_launch_overlap(const vbmd_launch &L, const int *ids, const long long *g
                         float *pcm, int *samples, hipStream_t q)
 {
     if (L.nsb <= 0) return 0;
-    hipLaunchKernelGGL(L.hs ? k_overlap<1> : k_overlap<0>, dim3(L.nsb), dim3(256), 0, q, L.s, L.nsb, ids, L.status, L.info,
-                       L.imdct, L.n1, L.win0, L.win1, granulepos, eos, L.tail, L.prevW, L.gp, L.sc, pcm, samples, L.ohalf);
+    const auto kernel = PICK_HS_MX(k_overlap);
+    hipLaunchKernelGGL(kernel, dim3(L.nsb), dim3(256), 0, q, L.s, L.M, L.nsb, ids, L.status, L.info, L.imdct, L.n1,
+                       L.win0, L.win1, granulepos, eos, L.tail, L.prevW, L.gp, L.sc, pcm, samples, L.ohalf);
     return last_err();
 }
 
-int vbmd_launch_restart(const int *ids, int n, int *prevW, long long *gp, long long *sc, hipStream_t q)
+int vbmd_launch_restart(const int *ids, int n, int *prevW, long long *gp, long long *sc, const int *cls, int *scls,
+                        hipStream_t q)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_restart, dim3((n + 255) / 256), dim3(256), 0, q, ids, n, prevW, gp, sc);
+    hipLaunchKernelGGL(k_restart, dim3((n + 255) / 256), dim3(256), 0, q, ids, n, prevW, gp, sc, cls, scls);
     return last_err();
 }
 
@@ -700,7 +773,8 @@ int vbmd_launch_unpack_csr(const vbmd_launch &L, const uint8_t *data, const long
                            int *status_out, hipStream_t q)
 {
     if (L.nsb <= 0) return 0;
-    hipLaunchKernelGGL(k_unpack_csr, dim3((L.nsb + 63) / 64), dim3(64), 0, q, L.s, L.blob, L.nsb, data, offsets,
+    const auto kernel = PICK_MX(k_unpack_csr);
+    hipLaunchKernelGGL(kernel, dim3((L.nsb + 63) / 64), dim3(64), 0, q, L.s, L.blob, L.M, L.nsb, data, offsets,
                        data_bytes, L.info, L.fit, L.flags, L.res, L.half, L.cls, L.status, status_out, L.lists,
                        L.counts);
     return last_err();
@@ -711,15 +785,18 @@ int vbmd_launch_runs(const vbmd_launch &L, int nruns, const int *runtab, const l
                      int *run_samples, int *samples, hipStream_t q)
 {
     if (nruns <= 0) return 0;
-    hipLaunchKernelGGL(L.hs ? k_run_plan<1> : k_run_plan<0>, dim3((nruns + 63) / 64), dim3(64), 0, q, L.s, nruns, runtab, L.status, L.info,
+    const auto plan_kernel = PICK_HS_MX(k_run_plan);
+    hipLaunchKernelGGL(plan_kernel, dim3((nruns + 63) / 64), dim3(64), 0, q, L.s, L.M, nruns, runtab, L.status, L.info,
                        granulepos, eos, gap, L.prevW, L.gp, L.sc, plan, samples, run_samples, run_last);
     if (last_err()) return -2;
     if (L.nsb > 0) {
-        hipLaunchKernelGGL(L.hs ? k_overlap_runs<1> : k_overlap_runs<0>, dim3(L.nsb), dim3(256), 0, q, L.s, runtab, L.status,
-                           L.info, plan, L.imdct, L.n1, L.win0, L.win1, L.tail, pcm, pcm_stride, L.ohalf);
+        const auto overlap_kernel = PICK_HS_MX(k_overlap_runs);
+        hipLaunchKernelGGL(overlap_kernel, dim3(L.nsb), dim3(256), 0, q, L.s, L.M, runtab, L.status, L.info, plan,
+                           L.imdct, L.n1, L.win0, L.win1, L.tail, pcm, pcm_stride, L.ohalf);
         if (last_err()) return -2;
-        hipLaunchKernelGGL(L.hs ? k_run_commit<1> : k_run_commit<0>, dim3(nruns), dim3(256), 0, q, L.s, nruns, runtab, run_last,
-                           L.info, L.imdct, L.n1, L.tail, L.ohalf);
+        const auto commit_kernel = PICK_HS_MX(k_run_commit);
+        hipLaunchKernelGGL(commit_kernel, dim3(nruns), dim3(256), 0, q, L.s, L.M, nruns, runtab, run_last, L.info,
+                           L.imdct, L.n1, L.tail, L.ohalf);
     }
     return last_err();
 }
@@ -743,7 +820,9 @@ int vbmd_launch_ranges(const vbmd_launch &L, int npieces, const int *rtab, const
     hipLaunchKernelGGL(k_range_plan, dim3((npieces + 63) / 64), dim3(64), 0, q, npieces, rtab, rows, L.status, L.info,
                        pk_begin, pk_end, out_start, plan);
     if (last_err()) return -2;
-    hipLaunchKernelGGL(L.hs ? k_overlap_runs<1> : k_overlap_runs<0>, dim3(L.nsb), dim3(256), 0, q, L.s, runtab, L.status,
-                       L.info, plan, L.imdct, L.n1, L.win0, L.win1, L.tail, pcm, pcm_stride, L.ohalf);
+    const auto kernel = L.hs ? k_overlap_runs<1, false> : k_overlap_runs<0, false>;     // no range calls on mixed decoders
+    hipLaunchKernelGGL(kernel, dim3(L.nsb), dim3(256), 0, q, L.s, L.M, runtab, L.status, L.info, plan, L.imdct, L.n1,
+                       L.win0, L.win1, L.tail, pcm, pcm_stride, L.ohalf);
     return last_err();
 }
+

@@ -551,23 +551,25 @@ int vbmd_setup_parse(vbm_decode_setup *ds, const uint8_t *headers, const long *l
     }
     s.max_classes = (int)((maxc + 15) & ~15L);
     // the tables the device path needs: windows of both block sizes and of half each, FLOOR1_fromdB_LOOKUP (common.vpk)
+    const int sizes[4] = {s.blocksizes[0], s.blocksizes[1], s.blocksizes[0] / 2, s.blocksizes[1] / 2};
+    std::vector<float> *win[4] = {&ds->win[0], &ds->win[1], &ds->hwin[0], &ds->hwin[1]};
+    return vbmd_common_tables(&ds->fromdB, 4, sizes, win);
+}
+
+int vbmd_common_tables(std::vector<float> *fromdB, int n, const int *sizes, std::vector<float> *const *win)
+{
     const std::string path = lib_data_dir() + "/common.vpk";
     vpk_file f;
     if (vpk_open(&f, path.c_str())) { g_vbm_err = "cannot open " + path; return VBM_EFAULT; }
     size_t cnt = 0;
     const float *db = (const float *)vpk_get(&f, "FLOOR1_fromdB_LOOKUP", VPK_F32, &cnt);
     bool ok = db && cnt == 256;
-    if (ok) ds->fromdB.assign(db, db + 256);
-    for (int w = 0; w < 2 && ok; w++) {
-        const std::string name = "window/" + std::to_string(s.blocksizes[w]);
-        const float *win = (const float *)vpk_get(&f, name.c_str(), VPK_F32, &cnt);
-        ok = win && (int)cnt == s.blocksizes[w] / 2;
-        if (ok) ds->win[w].assign(win, win + cnt);
-        if (!ok) break;
-        const std::string hname = "window/" + std::to_string(s.blocksizes[w] / 2);
-        win = (const float *)vpk_get(&f, hname.c_str(), VPK_F32, &cnt);
-        ok = win && (int)cnt == s.blocksizes[w] / 4;
-        if (ok) ds->hwin[w].assign(win, win + cnt);
+    if (ok) fromdB->assign(db, db + 256);
+    for (int i = 0; i < n && ok; i++) {
+        const std::string name = "window/" + std::to_string(sizes[i]);
+        const float *w = (const float *)vpk_get(&f, name.c_str(), VPK_F32, &cnt);
+        ok = w && (int)cnt == sizes[i] / 2;
+        if (ok) win[i]->assign(w, w + cnt);
     }
     vpk_close(&f);
     if (!ok) { g_vbm_err = "common.vpk lacks a decode table"; return VBM_EFAULT; }

@@ -12,6 +12,10 @@ struct vbm_decode_setup {
     std::vector<float> hwin[2];       // ... of blocksizes[0] / 2 and [1] / 2, for half-rate decoders
 };
 
+// FLOOR1_fromdB_LOOKUP and the rising half-windows of n block sizes (win[i]: sizes[i] / 2 floats), from the package's
+// common tables: what a setup carries for its own sizes, and a mixed decoder for every size its caps allow
+int vbmd_common_tables(std::vector<float> *fromdB, int n, const int *sizes, std::vector<float> *const *win);
+
 // The host index of one stream's n packets (CSR as vbm_synthesis_runs takes them, clamped to [0, data_bytes)), from a
 // fresh stream state: per packet the status (vbmd_head) and, for valid packets, vbmd_blockin's [begin, end) (0, 0 for
 // failed ones) and out_start, the exclusive prefix sum of end - begin; *total = the sum.  begin / end may be NULL.

@@ -192,7 +192,7 @@ class Decoder(_Handle):
         if offsets.numel() != P + 1:
             raise ValueError(f"offsets must have sum(counts) + 1 = {P + 1} entries, has {offsets.numel()}")
         if pcm_stride is None:
-            pcm_stride = max(1, int(cnt.max(initial=0)) * self.row)
+            pcm_stride = self._run_stride(ids, cnt)
         if out is None:
             pcm = torch.empty((nruns, self.channels, pcm_stride), dtype=torch.float32, device=dev)
             run_samples = torch.empty(nruns, dtype=torch.int32, device=dev)
@@ -270,6 +270,106 @@ class Decoder(_Handle):
     def _hold_index_inputs(self, *tensors):
         """decode_index_device's inputs stay alive until the work has run (apart from ._last, which fetch reads)"""
         self._last_index = tensors
+
+    def _run_stride(self, ids, counts):
+        """synthesis_runs' default pcm_stride: room for the longest run"""
+        return max(1, int(counts.max(initial=0)) * self.row)
+
+
+class MixedDecoder(Decoder):
+    """A Decoder for streams of different header classes (vbm_decoder_create_mixed): made from caps instead of a
+    setup, up to max_classes classes of up to max_channels channels and blocks of up to max_blocksize.
+        c = md.add_class(dsetup)            # or md.class_for(headers): adds, or finds by byte-equal headers
+        md.bind(stream_ids, class_ids)      # also restarts those streams
+    synthesis_batch and synthesis_runs then take streams of any mix of classes in one call and one launch chain, each
+    stream's result bit for bit that of a Decoder of its class.  Their PCM rows are the caps': pcm is [n, max_channels,
+    stride], and row r uses pcm[r, :channels_of([id])[0], :samples]; the rest is not written.  A call that lists an
+    unbound stream is a VbmError.  .channels is max_channels and .row the most samples a packet of the largest block
+    returns; rates and channel counts are per stream: rate_of(ids), channels_of(ids).  Range stores, synthesis_ranges,
+    the device index and fetch are not built for it (VbmError)."""
+
+    def __init__(self, nstreams, max_batch, max_classes=64, max_channels=8, max_blocksize=4096, halfrate=False):
+        self.dsetup, self.blocksizes, self.rate = None, None, None
+        self.channels, self.max_classes, self.max_blocksize = max_channels, max_classes, max_blocksize
+        self.nstreams, self.max_batch = nstreams, max_batch
+        self.halfrate = bool(halfrate)
+        self.row = max_blocksize // (4 if self.halfrate else 2)
+        self._h = C.c_void_p()
+        check(lib.vbm_decoder_create_mixed(C.byref(self._h), max_classes, max_channels, max_blocksize, nstreams,
+                                           max_batch, int(self.halfrate)), "vbm_decoder_create_mixed")
+        self._last = None
+        self.classes = []                                     # DecodeSetup of every class, by class id
+        self._by_headers = {}                                 # (identification, setup packet) -> class id
+        self._own = []                                        # the setups class_for made: closed with the decoder
+        self.stream_class = np.full(nstreams, -1, np.int32)   # the host mirror of the binding
+
+    def add_class(self, dsetup):
+        """-> the class id (0, 1, ...) of this DecodeSetup, copied to the device on the current stream.  The setup must
+        stay open as long as the decoder uses it for channels_of / rate_of."""
+        cid = C.c_int(-1)
+        check(lib.vbm_decoder_add_class(self._h, dsetup._h, C.byref(cid), self._stream()), "vbm_decoder_add_class")
+        assert cid.value == len(self.classes)
+        self.classes.append(dsetup)
+        return cid.value
+
+    def class_for(self, headers):
+        """-> the class id of these three header packets: the class with byte-equal identification and setup packets,
+        added if it is new"""
+        key = (bytes(headers[0]), bytes(headers[2]))
+        if key not in self._by_headers:
+            ds = DecodeSetup(headers)
+            try:
+                self._by_headers[key] = self.add_class(ds)
+            except VbmError:
+                ds.close()
+                raise
+            self._own.append(ds)
+        return self._by_headers[key]
+
+    def bind(self, stream_ids, class_ids):
+        """streams stream_ids (distinct) are of classes class_ids from here on, and restart (enqueued on the current
+        stream, in order with the calls around it)"""
+        ids, cls = _i32(stream_ids), _i32(class_ids)
+        if ids.shape != cls.shape or ids.ndim != 1:
+            raise ValueError("stream_ids and class_ids must be 1-D and of the same length")
+        check(lib.vbm_decoder_bind_streams(self._h, len(ids), ids.ctypes.data, cls.ctypes.data, self._stream()),
+              "vbm_decoder_bind_streams")
+        self.stream_class[ids] = cls
+
+    def _of(self, ids, what):
+        cls = self.stream_class[_i32(ids)]
+        if (cls < 0).any():
+            raise ValueError("a stream is not bound to a class")
+        return [what(self.classes[c]) for c in cls]
+
+    def channels_of(self, ids):
+        """the channel count of each of these streams' classes"""
+        return self._of(ids, lambda ds: ds.channels)
+
+    def rate_of(self, ids):
+        """the output rate of each of these streams (half the class's on a half-rate decoder)"""
+        return self._of(ids, lambda ds: output_rate(ds.rate, self.halfrate))
+
+    def row_of(self, ids):
+        """the most samples one packet of each of these streams returns"""
+        return self._of(ids, lambda ds: ds.blocksizes[1] // (4 if self.halfrate else 2))
+
+    def fetch(self, name):
+        """not built for a mixed decoder: the VbmError of vbm_decoder_fetch"""
+        check(lib.vbm_decoder_fetch(self._h, name.encode(), None, None, None, self._stream()), "vbm_decoder_fetch")
+
+    def _run_stride(self, ids, counts):
+        # a stream id out of range or unbound is left out here: the call itself refuses it with its VbmError
+        bound = (ids >= 0) & (ids < self.nstreams)
+        bound[bound] = self.stream_class[ids[bound]] >= 0
+        rows = np.asarray(self.row_of(ids[bound]), dtype=np.int64)
+        return max(1, int((counts[bound] * rows).max(initial=0)))
+
+    def close(self):
+        super().close()
+        for ds in self._own:
+            ds.close()
+        self._own = []
 
 
 def output_rate(rate, halfrate):
@@ -614,7 +714,8 @@ def _calls(src, max_packets):
         yield ids, counts, torch.cat(datas), np.concatenate(offs), torch.cat(gps), torch.cat(eoss)
 
 
-def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chained=False, multiplexed=False):
+def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chained=False, multiplexed=False,
+               one_decoder=False):
     """.ogg files (bytes or paths), one logical stream each -> [(pcm float32 [channels, n] contiguous on the current
     device, rate)], one per file.  Files whose identification and setup headers are byte-equal share one DecodeSetup
     and Decoder, one stream per file; their packets go through synthesis_runs in calls of at most max_packets rows.
@@ -630,7 +731,10 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
     multiplexed=True: the files may carry other streams beside the Vorbis one (Theora, Skeleton, Kate ...); the first
     Vorbis stream of a file, or with chained of each of its links, is decoded and the rest is ignored, as the
     reference's vorbisfile.c does (csrc/ogg_select.h; on the device with device_demux, stream.select_vorbis_stream on the
-    host without).  A file without a Vorbis stream raises VbmError saying so."""
+    host without).  A file without a Vorbis stream raises VbmError saying so.
+    one_decoder=True: the files and links of all header classes go through one MixedDecoder, its caps the largest
+    channel count and block size among them, in calls planned over all of them together instead of group by group;
+    the result is the same, tensor for tensor."""
     if max_packets <= 0:
         raise ValueError("max_packets must be positive")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -645,21 +749,42 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
                            f"{lib.vbm_last_error().decode()}")
     pieces = [[] for _ in demuxed]                        # per entry: (pcm [channels, stride] view, index into lens)
     lens, keep, rates, nlens = [], [], [0] * len(demuxed), 0
-    for members in groups.values():
-        ds = DecodeSetup(demuxed[members[0]][0])
-        dec = Decoder(ds, len(members), max_packets, halfrate=halfrate)
-        keep.append((ds, dec))
+    setups = []                                           # one DecodeSetup per group, in the groups' order
+
+    def jobs():
+        """(decoder, the entries that are its streams 0, 1, ...); without one_decoder each group's setup and decoder
+        are made when its turn comes"""
+        if one_decoder and groups:                        # one job: every entry a stream of one mixed decoder
+            setups.extend(DecodeSetup(demuxed[members[0]][0]) for members in groups.values())
+            md = MixedDecoder(len(demuxed), max_packets, max_classes=len(setups), halfrate=halfrate,
+                              max_channels=max(ds.channels for ds in setups),
+                              max_blocksize=max(ds.blocksizes[1] for ds in setups))
+            keep.append(md)
+            for ds, members in zip(setups, groups.values()):
+                c = md.add_class(ds)
+                for a in range(0, len(members), max_packets):         # one bind call takes max_batch streams
+                    md.bind(members[a:a + max_packets], [c] * len(members[a:a + max_packets]))
+            yield md, list(range(len(demuxed)))
+            return
+        for members in groups.values():                   # one job per header group
+            setups.append(DecodeSetup(demuxed[members[0]][0]))
+            keep.append(Decoder(setups[-1], len(members), max_packets, halfrate=halfrate))
+            yield keep[-1], members
+
+    for dec, members in jobs():
         up = lambda x: torch.as_tensor(x, device=dev)     # host-demuxed arrays go up here; demuxed on the device: as is
         src = [(up(demuxed[j][1]), demuxed[j][2], up(demuxed[j][3]), up(demuxed[j][4])) for j in members]
         for ids, counts, data, offsets, gp, eo in _calls(src, max_packets):
             pcm, run_samples, _, _ = dec.synthesis_runs(ids, counts, data, torch.from_numpy(offsets).to(dev),
-                                                        granulepos=gp, eos=eo, pcm_stride=max(counts) * dec.row)
+                                                        granulepos=gp, eos=eo)
+            chans = dec.channels_of(ids) if one_decoder else [dec.channels] * len(ids)
             for r, s in enumerate(ids):
-                pieces[members[s]].append((pcm[r], nlens + r))
+                pieces[members[s]].append((pcm[r, :chans[r]], nlens + r))
             lens.append(run_samples)
             nlens += len(ids)
+    for ds, members in zip(setups, groups.values()):
         for j in members:
-            rates[j] = dec.rate
+            rates[j] = output_rate(ds.rate, bool(halfrate))
             if not pieces[j]:
                 pieces[j].append((torch.zeros((ds.channels, 0), dtype=torch.float32, device=dev), None))
     n = torch.cat(lens).cpu().tolist() if lens else []   # the one wait for the device
@@ -667,9 +792,8 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
     for j in range(len(demuxed)):
         parts = [p if k is None else p[:, :n[k]] for p, k in pieces[j]]
         out.append((torch.cat(parts, dim=1).contiguous(), rates[j]))
-    for ds, dec in keep:
-        dec.close()
-        ds.close()
+    for x in keep + setups:
+        x.close()
     if chained:
         return [out[int(file_links[f]):int(file_links[f + 1])] for f in range(len(file_links) - 1)]
     return out
