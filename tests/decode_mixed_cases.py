@@ -50,6 +50,149 @@ def sequence(n):
     return (SEQ * (n // len(SEQ) + 1))[:n]
 
 
+# ---- the generated corpus (vm.CORPUS) as classes ----------------------------------------------------------------------
+SILENT = "pair_2048_2048_end_le_begin"      # the family whose residue range is empty: every spectrum is zero
+
+
+@functools.lru_cache(maxsize=None)
+def family(k):
+    """vm.CORPUS[k] as a Class, with .name, .setup (the dict), .packets (the bytes of vm.corpus_packets) and per packet
+    the model's .status and .info, and .loud: its model spectrum is nonzero"""
+    from tests.test_decoder_model_cpu import family as model_family
+    setup, _, headers, _, rows, _, _ = model_family(k)
+    c = Class(headers, setup["channels"], tuple(setup["blocksizes"]), vm.Model(setup, fromdB()))
+    c.name, c.setup = vm.CORPUS[k][0], setup
+    c.packets = [p for _, p, _ in rows]
+    c.status = [r["status"] for _, _, r in rows]
+    c.info = [r["info"] for _, _, r in rows]
+    c.loud = [bool(r["spectrum"].any()) for _, _, r in rows]
+    return c
+
+
+def family_named(name):
+    return family([n for n, _ in vm.CORPUS].index(name))
+
+
+@functools.lru_cache(maxsize=None)
+def whole(k, seed=0):
+    """(a, b): whole writer-made loud packets of family k, one of each block flag the family has, the short one first;
+    the same packet twice where the family has one flag"""
+    c = family(k)
+    pw = vm.PacketWriter(c.model, np.random.default_rng(7100 + 131 * seed + k))
+    modes = c.setup["modes"]
+    made = []
+    for f in sorted({md[0] for md in modes}):
+        mine = [i for i, md in enumerate(modes) if md[0] == f]
+        made.append(pw.packet(mine[seed % len(mine)], loud=True))
+    return made[0], made[-1]
+
+
+def family_stream(k, seed, seq=SEQ):
+    """a stream of family k that follows the block-size sequence with whole(k, seed)'s two packets"""
+    a, b = whole(k, seed)
+    return [(b if c == "L" else a, -1, 0) for c in seq]
+
+
+def corpus_pick(loud=None, failing=None):
+    """{family: [packet indices]}: all of them, or per family the first `loud` packets with a nonzero model spectrum
+    (in the silent family: that decode) and the first `failing` ones that fail"""
+    pick = {}
+    for k in range(len(vm.CORPUS)):
+        f = family(k)
+        if loud is None:
+            pick[k] = list(range(len(f.packets)))
+            continue
+        good = [i for i in range(len(f.packets)) if (f.status[i] == 0 if f.name == SILENT else f.loud[i])]
+        bad = [i for i in range(len(f.packets)) if f.status[i] != 0][:failing]
+        at = 1 + 5 * k % (loud - 1)         # the first failing one at a place of the family's own: good neighbours
+        pick[k] = good[:at] + bad[:1] + good[at:loud] + bad[1:]
+    return pick
+
+
+def corpus_script(pick):
+    """Every picked corpus packet p of every family as a stream of its own that plays [p, a, p, b], with (a, b) =
+    whole(family): a synthesis_batch of all p, one of all a, and one synthesis_runs of every [p, b].  The rows of the
+    first two calls go round-robin over the families, those of the third in the reverse of that order.
+    -> (classes, script, {(family, packet index): stream id}, the round-robin order [(family, packet index)])"""
+    fams = [family(k) for k in range(len(vm.CORPUS))]
+    sid = {}
+    for k in range(len(fams)):
+        for i in pick[k]:
+            sid[k, i] = len(sid)
+    order = [(k, pick[k][j]) for j in range(max(len(p) for p in pick.values())) for k in range(len(fams))
+             if j < len(pick[k])]
+    row = lambda p: (p, -1, 0)                                       # noqa: E731
+    script = [("add", k) for k in range(len(fams))]
+    script.append(("bind", [sid[x] for x in order], [k for k, _ in order]))
+    script.append(("batch", [(sid[k, i], row(fams[k].packets[i])) for k, i in order]))
+    script.append(("batch", [(sid[k, i], row(whole(k)[0])) for k, i in order]))
+    script.append(("runs", [(sid[k, i], [row(fams[k].packets[i]), row(whole(k)[1])]) for k, i in order[::-1]]))
+    return fams, script, sid, order
+
+
+def corpus_blocks(order):
+    """{transform size: {family: blocks}} of the first call over `order`, from the model's info as count_blocks does:
+    a row that decodes puts its channels on the list of its block size"""
+    sizes = {}
+    for k, i in order:
+        f = family(k)
+        if f.status[i] == 0:
+            of = sizes.setdefault(f.bs[f.info[i][1]], {})
+            of[k] = of.get(k, 0) + f.ch
+    return sizes
+
+
+def corpus_sandwiched(order):
+    """the rows of the first call that fail between two rows of other families that decode"""
+    ok = [family(k).status[i] == 0 for k, i in order]
+    return [r for r in range(1, len(order) - 1)
+            if not ok[r] and ok[r - 1] and ok[r + 1] and order[r - 1][0] != order[r][0] != order[r + 1][0]]
+
+
+def class_bytes(setup):
+    """the partition-class scratch one packet of this setup dict needs, before rounding (parse_setup's arithmetic: per
+    residue the partitions of the largest block, for every channel in types 0 and 1)"""
+    n, ch = setup["blocksizes"][1] // 2, setup["channels"]
+    need = 1
+    for r in setup["residues"]:
+        size = n * ch if r["type"] == 2 else n
+        length = min(r["end"], size) - r["begin"]
+        if length > 0:
+            need = max(need, length // r["grouping"] * (1 if r["type"] == 2 else ch))
+    return need
+
+
+# decoders whose caps a class meets exactly: (caps, corpus families, a synthetic class beside them or None)
+CAPS = [
+    (dict(max_channels=3, max_blocksize=256), ["pair_256_256_grouping1"], (1, (256, 256))),       # the class scratch
+    (dict(max_channels=8, max_blocksize=512), ["modes_5_submaps_16", "group_dim4_ragged", "pair_256_512_res0"],
+     (1, (256, 512))),                                                                            # channels, few bins
+    (dict(max_channels=2, max_blocksize=4096), ["pair_4096_4096_single_books", "pair_512_4096_long_codewords",
+                                                "pair_256_2048_maptype2", "modes_1"], None),      # bins, few channels
+]
+CAPS_ROWS = 9                               # more than one IMDCT group of 256-blocks at 3 channels, and no multiple
+
+
+def caps_script(n):
+    """CAPS[n] -> (classes, script, the class of every row): CAPS_ROWS streams of SEQ, the rows going round the classes
+    from the last one on, so in CAPS[0] every row of the corpus family lies between two rows of the synthetic class;
+    five steps of one packet per stream, then the rest in one runs call"""
+    _, names, synth = CAPS[n]
+    classes = [family_named(x) for x in names] + ([synthetic(*synth)] if synth else [])
+    of = [(r + len(classes) - 1) % len(classes) for r in range(CAPS_ROWS)]
+    index = [x for x, _ in vm.CORPUS]
+    streams = {}
+    for r, c in enumerate(of):
+        if c < len(names):
+            streams[r] = family_stream(index.index(names[c]), 1 + r // len(classes))
+        else:
+            streams[r] = list(stream(*synth, seed=r))
+    script = [("add", c) for c in range(len(classes))] + [("bind", list(range(CAPS_ROWS)), of)]
+    script += [("batch", [(s, pk[t]) for s, pk in streams.items()]) for t in range(5)]
+    script.append(("runs", [(s, pk[5:]) for s, pk in streams.items()]))
+    return classes, script, of
+
+
 def ogg_packets(blob):
     """an .ogg file -> (headers, [(packet, granulepos, eos)])"""
     import vorbis_aotuv_lancer_amd as v
@@ -114,11 +257,15 @@ class Player:
             else:
                 pending += self.call(ev[0], ev[1], inp)
         self.result = {}
-        for sid, ch, pcm, n, samples, status in pending:            # the one wait is the first .cpu() here
-            n = int(n)
-            full = pcm.cpu().numpy()
-            assert np.all(full[ch:] == FILL) and np.all(full[:ch, n:] == FILL), f"stream {sid}: written outside its PCM"
-            self.result.setdefault(sid, []).append((full[:ch, :n], samples.cpu().tolist(), status.cpu().tolist()))
+        for meta, at, pcm, n, samples, status in pending:           # the one wait is the first .cpu() here
+            pcm, n = pcm.cpu().numpy(), n.cpu().tolist()
+            samples, status = samples.cpu().tolist(), status.cpu().tolist()
+            for r, (sid, ch) in enumerate(meta):
+                full = pcm[r]
+                assert np.all(full[ch:] == FILL) and np.all(full[:ch, n[r]:] == FILL), \
+                    f"stream {sid}: written outside its PCM"
+                self.result.setdefault(sid, []).append((full[:ch, :n[r]], samples[at[r]:at[r + 1]],
+                                                        status[at[r]:at[r + 1]]))
         self.close()
         return self.result
 
@@ -129,20 +276,19 @@ class Player:
         return (pcm, *ints)
 
     def call_on(self, dec, kind, ids, rows, inp, chans, stride):
-        """one call of `dec` over rows [(stream id, packet or run)] under the stream ids `ids` -> pending entries"""
+        """one call of `dec` over rows [(stream id, packet or run)] under the stream ids `ids` -> one pending entry:
+        ([(stream id, channels) per row], the rows' first packets [rows + 1], pcm, samples per row, samples, status)"""
+        meta = [(sid, chans[r]) for r, (sid, _) in enumerate(rows)]
         if kind == "batch":
             pk, nb, gp, eo = inp
             pcm, samples, status = dec.synthesis_batch(ids, pk, nb, granulepos=gp, eos=eo,
                                                        out=self.out(len(ids), dec.channels, dec.row))
-            return [(sid, chans[r], pcm[r], samples[r], samples[r:r + 1], status[r:r + 1])
-                    for r, (sid, _) in enumerate(rows)]
+            return [(meta, list(range(len(rows) + 1)), pcm, samples, samples, status)]
         data, offs, gp, eo, gap = inp
         counts = [len(r) for _, r in rows]
         pcm, rs, samples, status = dec.synthesis_runs(ids, counts, data, offs, granulepos=gp, eos=eo, gap=gap,
                                                       out=self.out(len(ids), dec.channels, stride, sum(counts)))
-        at = np.cumsum([0] + counts)
-        return [(sid, chans[r], pcm[r], rs[r], samples[at[r]:at[r + 1]], status[at[r]:at[r + 1]])
-                for r, (sid, _) in enumerate(rows)]
+        return [(meta, np.cumsum([0] + counts).tolist(), pcm, rs, samples, status)]
 
     def row(self, c):
         return self.classes[c].bs[1] // (4 if self.halfrate else 2)
@@ -191,16 +337,38 @@ class Mixed(Player):
 class PerClass(Player):
     """the yardstick: one single-class Decoder per class, each taking its own streams' rows of every call"""
 
-    def __init__(self, *a, **kw):
+    def __init__(self, *a, compact=False, **kw):
         super().__init__(*a, **kw)
-        self.dec = {}
+        self.dec, self.compact = {}, compact
+
+    def play(self, script):
+        """compact: every Decoder is sized to the streams its class is ever bound to and to the most rows a call gives
+        it, and takes those streams under ids 0, 1, ... of its own (.local[class][stream id])"""
+        of, self.local, self.need = {}, {}, {}
+        for ev in script:
+            if ev[0] == "bind":
+                of.update(zip(ev[1], ev[2]))
+                for s, c in zip(ev[1], ev[2]):
+                    mine = self.local.setdefault(c, {})
+                    mine.setdefault(s, len(mine))
+            elif ev[0] in ("batch", "runs"):
+                rows = {}
+                for s, r in ev[1]:
+                    rows[of[s]] = rows.get(of[s], 0) + (1 if ev[0] == "batch" else len(r))
+                for c, n in rows.items():
+                    self.need[c] = max(self.need.get(c, 1), n)
+        return super().play(script)
+
+    def ids(self, c, streams):
+        return [self.local[c][s] for s in streams] if self.compact else list(streams)
 
     def add(self, c):
-        self.dec[c] = self.v.Decoder(self.classes[c].ds, self.S, self.cap, halfrate=self.halfrate)
+        S, cap = (len(self.local.get(c, [0])), self.need.get(c, 1)) if self.compact else (self.S, self.cap)
+        self.dec[c] = self.v.Decoder(self.classes[c].ds, S, cap, halfrate=self.halfrate)
 
     def bind(self, ids, cs):
         for c in sorted(set(cs)):
-            self.dec[c].restart_streams([s for s, k in zip(ids, cs) if k == c])
+            self.dec[c].restart_streams(self.ids(c, [s for s, k in zip(ids, cs) if k == c]))
 
     def call(self, kind, rows, inp):
         out = []
@@ -208,8 +376,8 @@ class PerClass(Player):
             mine = [(s, r) for s, r in rows if self.of[s] == c]
             sub = _batch_inputs(mine, self.dev) if kind == "batch" else _runs_inputs(mine, self.dev)
             stride = max([1] + [len(r) * self.row(c) for _, r in mine]) if kind == "runs" else None
-            out += self.call_on(self.dec[c], kind, [s for s, _ in mine], mine, sub, [self.classes[c].ch] * len(mine),
-                                stride)
+            out += self.call_on(self.dec[c], kind, self.ids(c, [s for s, _ in mine]), mine, sub,
+                                [self.classes[c].ch] * len(mine), stride)
         return out
 
     def close(self):
@@ -230,14 +398,15 @@ def same(got, want):
     return total
 
 
-def both(v, classes, script, S, cap, dev, halfrate=False, count=False, **caps):
-    """the script on a MixedDecoder and on the yardstick, compared -> the Mixed player (its .result, .blocks)"""
+def both(v, classes, script, S, cap, dev, halfrate=False, count=False, compact=False, **caps):
+    """the script on a MixedDecoder and on the yardstick, compared -> the Mixed player (its .result, .blocks).
+    compact: the yardstick's Decoders are sized to their own classes (PerClass.play)"""
     for k in classes:
         k.ds = v.DecodeSetup(k.headers)
     try:
         m = Mixed(v, classes, S, cap, dev, halfrate, count, **caps)
         got = m.play(script)
-        want = PerClass(v, classes, S, cap, dev, halfrate).play(script)
+        want = PerClass(v, classes, S, cap, dev, halfrate, compact=compact).play(script)
         m.samples = same(got, want)
         assert m.samples > 0
     finally:
