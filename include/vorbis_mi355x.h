@@ -642,9 +642,29 @@ int vbm_host_ogg_select(vbm_ogg_selector *sel, int nfiles, const uint8_t *data, 
  *   vbm_ogg_feed_fill_gaps   vbm_ogg_feed_fill plus d_gap [packet_cap] (uint8, device; NULL: no marks are written):
  *                            1 when something was lost between the slot's previous delivered packet and this one.
  *                            vbm_ogg_feed_fill on a resync feed drops the marks; on a strict feed fill_gaps writes zeros.
- *   vbm_host_ogg_feed_create2 / _scan_events / _fill_gaps   the host twin. */
+ *   vbm_host_ogg_feed_create2 / _scan_events / _fill_gaps   the host twin.
+ *
+ * Multiplexed mode (vbm_ogg_feed_create2 with VBM_OGG_FEED_MULTIPLEXED, alone or together with VBM_OGG_FEED_RESYNC) is for
+ * mounts that carry other logical streams beside the audio: Theora video, an Ogg Skeleton track, Kate or CMML text.  It
+ * applies the rule of vbm_ogg_select (above) as the bytes arrive, per slot, in front of the feed's own rules (stated once
+ * in csrc/ogg_feed.h): of every group of streams the first whose first packet is a Vorbis identification header is the
+ * slot's stream, and every page of another stream is foreign.  A foreign page is stepped over whole, once it is whole:
+ * nothing of it reaches a packet, a store or a status.  Until then it is carried like any page, so max_page_carry has to
+ * cover the largest foreign page too (above it: VBM_OGG_FEED_EBIG).  8 bytes more per slot; vbm_ogg_feed_reset_streams
+ * makes a slot fresh, with a new group and nothing chosen.  Every call, struct and status is as without the flag.
+ *   - strict: the feed does what a strict feed does on the bytes vbm_ogg_select keeps.  Foreign pages are not
+ *     CRC-checked.  A chain is still VBM_EOGG, at the second group's Vorbis head page and not before; that page, like
+ *     every head page that has to show the Vorbis mark, is judged once it is whole.  Bytes that are no page header (27
+ *     are present; capture pattern, version) are VBM_EOGG whether or not a stream has been chosen: unlike a file, a feed
+ *     has no end at which to drop them.  `end` with no Vorbis stream is VBM_EOGG (fewer than three packets).
+ *   - resync: rule 1 is unchanged, and only pages with a good CRC are told apart.  Rule 2 becomes: a link start is a
+ *     page with the beginning-of-stream flag that the rule above keeps.  A foreign page, beginning-of-stream or not,
+ *     is ignored and counted in ignored_pages; it closes no link, drops no open packet and sets no gap mark.  A mount
+ *     joined mid-way ignores what comes before the next group, whose Vorbis head page starts link 0.
+ * The value is 4: tests pin flags 2 and 3 as VBM_EINVAL, so bit 1 stays invalid, and so is every bit from 8 up. */
 #define VBM_OGG_FEED_EBIG (-1003)
 #define VBM_OGG_FEED_RESYNC 1u
+#define VBM_OGG_FEED_MULTIPLEXED 4u
 typedef struct {
     int status;                 /* 0, VBM_EOGG or VBM_OGG_FEED_EBIG */
     int headers_ready;

@@ -19,6 +19,13 @@ with probability 1/100, seeded; `--lose` sets the rate), where the first pass co
 gave back.  The whole-file
 comparisons are left out.
 
+`--multiplexed [--foreign-ratio K]` (with or without `--resync`) measures a feed made with multiplexed=True on the same
+mounts with a video-like foreign stream of K times their bytes between their pages (a foreign head page in front of the
+Vorbis one, then behind every audio page foreign pages of up to 4096 bytes, K times the page's bytes in all), cut into
+the same number of calls.  The first pass compares the packets of every slot with demux_ogg of the Vorbis-only mount;
+then the same timed passes.  Reported beside the unflagged feed of the same kind on the Vorbis-only mounts, and the
+flagged feed on the Vorbis-only mounts.  The whole-file comparisons are left out.
+
 Per-kernel times: run this under `rocprofv3 --kernel-trace --stats`."""
 import argparse
 import ctypes as C
@@ -100,6 +107,63 @@ def lose_pages(runs, rate, seed=1):
         lost += len(pages) - len(keep)
         out.append(b"".join(keep))
     return out, lost
+
+
+def multiplex(runs, ratio, seed=5):
+    """every run with a foreign stream of `ratio` times its bytes between its pages -> (runs, foreign pages per run)"""
+    from tests.ogg_select_cases import sized_page
+    rng, out, counts = np.random.default_rng(seed), [], []
+    for k, r in enumerate(runs):
+        serial, seq, at, parts, owed = 0x7e000000 + k, 1, 0, [sized_page(0x7e000000 + k, 0, 27 + 1 + 42, rng, flags=2)], 0.0
+        while at < len(r):
+            n = 27 + r[at + 26] + sum(r[at + 27:at + 27 + r[at + 26]])
+            parts.append(r[at:at + n])
+            at += n
+            owed += ratio * n
+            while at > n and owed >= 27:                            # behind the Vorbis head page
+                take = int(min(owed, 4096))
+                parts.append(sized_page(serial, seq, take, rng))
+                seq, owed = seq + 1, owed - take
+        out.append(b"".join(parts))
+        counts.append(seq)
+    return out, counts
+
+
+def multiplexed_run(v, lib, check, a, runs, ids, want):
+    """--multiplexed: a flagged feed on the multiplexed mounts (outputs against demux_ogg of the Vorbis-only mounts,
+    then the timed passes), and on the Vorbis-only mounts -> the JSON fields"""
+    S, K, T = a.streams, len(runs), a.writes
+    kw = dict(max_page_carry=a.max_page_carry, max_packet_bytes=a.max_packet_bytes, header_cap=a.header_cap,
+              resync=a.resync, multiplexed=True)
+    out = {}
+    muxed, nforeign = multiplex(runs, a.foreign_ratio)
+    for name, mounts in (("multiplexed_mounts", muxed), ("vorbis_only_mounts", runs)):
+        calls = cut_calls(mounts, S, T)
+        feed = v.OggFeed(S, max(int(c[1][-1]) for c in calls), **kw)
+        caps, packets, ignored = [], np.zeros(S, np.int64), 0
+        body = [[] for _ in range(min(K, S))]
+        for data, off, end in calls:
+            r = feed.push(ids, data, end=end, offsets=off)
+            assert not r.info["status"].any() and (r.left is None or not r.left.any())
+            caps.append((int(r.offsets.numel()) - 1, int(r.payload.numel())))
+            packets += r.counts
+            ignored += int(r.events["ignored_pages"].sum()) if a.resync else 0
+            offs, pay = r.offsets.cpu().numpy(), r.payload.cpu().numpy()
+            for s in range(len(body)):
+                p, n = int(r.info["packet_base"][s]), int(r.info["packets"][s])
+                body[s].append(pay[offs[p]:offs[p + n]].tobytes())
+        same = all(packets[s] == len(want[s % K][3]) for s in range(S)) and \
+            all(b"".join(body[s]) == want[s][1].tobytes() and feed.headers(s) == want[s][0] for s in range(len(body)))
+        if a.resync:
+            same = same and ignored == (sum(nforeign[s % K] for s in range(S)) if mounts is muxed else 0)
+        scan, fill = timed_passes(lib, check, feed, ids, calls, caps, a.reps, a.resync)
+        feed.close()
+        per_call = sum(int(c[1][-1]) for c in calls) / T
+        out[name] = {"same_packets_as_demux_ogg": bool(same), "bytes_per_call": per_call, "scan_ms": scan, "fill_ms": fill,
+                     "ms_per_push": scan + fill, "GB_per_s": per_call / ((scan + fill) / 1e3) / 1e9}
+    out["foreign_ratio"] = a.foreign_ratio
+    out["foreign_pages_per_call"] = sum(nforeign[s % K] for s in range(S)) / T
+    return out
 
 
 def timed_passes(lib, check, feed, ids, calls, caps, reps, resync):
@@ -192,6 +256,9 @@ def main():
     ap.add_argument("--header-cap", type=int, default=8192)
     ap.add_argument("--resync", action="store_true", help="measure a resync feed against the strict feed of the same run")
     ap.add_argument("--lose", type=float, default=0.01, help="--resync: the share of pages the second figure loses")
+    ap.add_argument("--multiplexed", action="store_true",
+                    help="measure a feed made with multiplexed=True (strict, or resync with --resync) on multiplexed mounts")
+    ap.add_argument("--foreign-ratio", type=float, default=4.0, help="--multiplexed: foreign bytes per byte of the mount")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_feed.py needs a GPU: there is nothing to measure without one")
@@ -236,6 +303,22 @@ def main():
     # the timed passes: raw calls, outputs of the sizes the first pass found, device events around every scan and fill
     ms_scan, ms_fill = timed_passes(lib, check, feed, ids, calls, caps, a.reps, False)
     per_call = total_bytes / T
+    if a.multiplexed:
+        unflagged = {"scan_ms": ms_scan, "fill_ms": ms_fill}
+        if a.resync:                                               # the unflagged feed of the same kind
+            plain = v.OggFeed(S, max(call_bytes), max_page_carry=a.max_page_carry, max_packet_bytes=a.max_packet_bytes,
+                              header_cap=a.header_cap, resync=True)
+            sc, fi = timed_passes(lib, check, plain, ids, calls, caps, a.reps, True)
+            plain.close()
+            unflagged = {"scan_ms": sc, "fill_ms": fi}
+        feed.close()
+        unflagged.update(ms_per_push=unflagged["scan_ms"] + unflagged["fill_ms"], bytes_per_call=per_call)
+        print(json.dumps({
+            "metric": "ogg_feed_multiplexed", "mode": "resync" if a.resync else "strict", "streams": S, "signals": K,
+            "quality": a.quality, "calls": T, "reps": a.reps, "packets_per_call": statistics.mean(packets_per_call),
+            "same_outputs": bool(same), "unflagged_on_vorbis_only_mounts": unflagged,
+            "flagged": multiplexed_run(v, lib, check, a, runs, ids, want)}), flush=True)
+        return
     if a.resync:
         res = resync_run(v, lib, check, a, runs, ids, calls, feed)
         feed.close()

@@ -27,10 +27,38 @@
 // that ends the skipped part counts as the end of the packet in front of the call's first (pkt_before one less), which
 // rewrites that packet's end offset, the call's first CSR entry, with the value it has.  Such a record is marked
 // (OggDmxPage::pad), because its numbers below S are not header bytes.  Per slot 16 B more (OggFeedLink).
+//
+// Multiplexed mode (VBM_OGG_FEED_MULTIPLEXED, alone or with the resync mode): the rule of ogg_select.h applied page by
+// page in front of either walk, with its predicates (oggsel_wants_mark, oggsel_choose, oggsel_is_mark) over the two words
+// a slot carries (OggFeedMux, 8 B more per slot; the chosen serial number is the one the slot tracks, OggDmxCounts::
+// serial).  For every WHOLE page the walk meets, in this order (oggfeed_mux_page):
+//     head = (flags & 2), or the page is the first the slot meets (as pos == begin in ogg_select.h);
+//     head && past_heads: a new group starts: past_heads = 0, chosen = 0;
+//     !head:              past_heads = 1;
+//     head && !chosen, the body has 7 bytes or more and begins 01 'v' 'o' 'r' 'b' 'i' 's' (read only now that the body
+//                         is known to lie in the run): chosen = 1, and the page is the stream's own;
+//     the page is KEPT if and only if chosen and its serial number is the chosen one (a head page that sets chosen is);
+//     otherwise it is foreign.
+// A foreign page is stepped over whole: no page record, no body byte to any store, no CRC check in strict mode; it is
+// counted (a resync feed reports the count in ignored_pages).  A kept page goes to the walk as if no other had been there.
+// The group state moves on only with a page the walk has passed: a page at which a call stops is judged again by the
+// next call, from the same state.
+//   strict  the feed does what the strict feed does on the bytes ogg_select.h keeps (oggfeed_mux_step), with two
+//           deviations that a live feed cannot avoid.  A position that does not parse as a page header (capture
+//           pattern, version) once 27 bytes are there is VBM_EOGG whether or not a stream is chosen: there is no end
+//           of file at which an unchosen tail could be dropped.  And a head page that has to show the mark is judged
+//           once it is whole, not once its header is: the VBM_EOGG of a chain comes in the call that completes the
+//           second group's Vorbis head page.  A page behind the heads with the chosen serial number is kept whatever
+//           its body holds, so the walk judges its header at once, as without the flag.
+//   resync  rule 1 is unchanged, and only a page with a good CRC reaches the group state.  Rule 2: a page is a link
+//           start when it carries the beginning-of-stream flag and is kept; a foreign page, head or not, is ignored
+//           and counted, and closes no link, drops no packet and sets no mark.  Rules 3 to 6 are untouched.
+// A foreign page that is not whole yet is carried like any page, within max_page_carry.  Page records stay
+// chunk / 27 + 1 per slot: foreign pages take none.
 #pragma once
 #include <limits.h>
 
-#include "ogg_demux.h"
+#include "ogg_select.h"
 
 struct OggFeedCaps {
     int max_page_carry, max_packet_bytes, header_cap;
@@ -72,7 +100,66 @@ struct OggFeedRsCall {           // one listed stream of a resync scan, beside i
 struct OggFeedHead {             // a whole page candidate
     int flags, nseg, body;       // header type, segments, body bytes (the sum of the lacing values)
     uint32_t serial, seq;
+    uint32_t lace;               // device: this lane's four bytes of the 256 behind the header (for `mark`)
 };
+
+struct OggFeedMux {              // multiplexed mode: a slot's group between calls; all zero = a fresh slot
+    int past_heads;              // bit 0: a page without the head flag has been met in the group (the inverse of
+                                 // ogg_select.h's in_heads); bit 1: the slot has met a page
+    int chosen;                  // the group has shown its Vorbis head page
+};
+
+static_assert(sizeof(OggFeedMux) == 8, "OggFeedMux is the slot's memory");
+
+// One whole page against the group state (the rule: the head of this file).  serial: the one the slot tracks;
+// sno, body: the page's; mark(): its first 7 body bytes are the mark, asked only when the rule wants them.  Moves mx on
+// -> the page is kept
+template <class Mark>
+VBMX_HD bool oggfeed_mux_page(OggFeedMux &mx, uint32_t serial, int flags, uint32_t sno, int body, const Mark &mark)
+{
+    OggSelWalk w;
+    w.in_heads = !(mx.past_heads & 1), w.chosen = mx.chosen != 0, w.serial = serial;
+    w.info = vbm_ogg_select_info{};
+    const bool head = (flags & 2) || !(mx.past_heads & 2);
+    const bool shown = oggsel_wants_mark(w, head, body) && mark();
+    const bool kept = oggsel_choose(w, head, sno, shown);
+    mx.past_heads = (w.in_heads ? 0 : 1) | 2;
+    mx.chosen = w.chosen;
+    return kept;
+}
+
+// A strict multiplexed feed's run at pos, in front of the walk's own step:
+//    1  a foreign page of len bytes, all here: to be stepped over (nm: the group state behind it)
+//    0  the walk's own step goes on from here: the run is used up, or the page is kept (nm: the state once it is taken)
+//   -1  no page header (27 bytes are here)
+//   -2  the header, the lacing table or the body is not all in front of run_end
+// No byte is read before it is known to lie in front of run_end.
+VBMX_HD int oggfeed_mux_step(const uint8_t *work, long long pos, long long run_end, uint32_t serial, const OggFeedMux &mx,
+                             OggFeedMux &nm, int &len)
+{
+    nm = mx;
+    const long long left = run_end - pos;
+    if (left <= 0) return 0;
+    if (left < 27) return -2;
+    const uint8_t *h = work + pos;
+    if (!oggchain_header_ok(oggdmx_rd32(h), h[4])) return -1;
+    const int flags = h[5], nseg = h[26];
+    const uint32_t sno = oggdmx_rd32(h + 14);
+    const auto none = [] { return false; };
+    const bool head = (flags & 2) || !(mx.past_heads & 2);
+    if (!head && oggfeed_mux_page(nm, serial, flags, sno, 0, none)) return 0;   // kept whatever its body holds
+    if (!oggchain_lacing_fits(left, nseg)) return -2;
+    int body = 0;
+    for (int i = 0; i < nseg; i++) body += h[27 + i];
+    if (!oggchain_body_fits(left, nseg, body)) return -2;
+    len = 27 + nseg + body;
+    if (!head) return 1;
+    const uint8_t *b = h + 27 + nseg;                              // 7 bytes are there when asked for; the eighth may not be
+    const auto mark = [b] {
+        return oggsel_is_mark(oggdmx_rd32(b), (uint32_t)b[4] | ((uint32_t)b[5] << 8) | ((uint32_t)b[6] << 16));
+    };
+    return oggfeed_mux_page(nm, serial, flags, sno, body, mark) ? 0 : 1;
+}
 
 VBMX_HD int oggfeed_tail_in(const OggFeedState &st, const OggFeedCaps &caps)
 {
@@ -95,10 +182,13 @@ VBMX_HD void oggfeed_call_begin(const OggFeedState &st, long long at, int slot, 
 // One stream, one call.  The run is work[at, run_end): whole pages are taken from it in order, at most `limit` of them,
 // and recorded in pages[0, room).  bad_at_limit: the page after the first `limit` failed its CRC (the second walk of a
 // stream, after the page-parallel CRC pass).  No byte is read before it is known to lie in front of run_end, and every
-// page taken moves on by at least 27 bytes.  Fills `c` but for its bases.
+// page taken moves on by at least 27 bytes.  Fills `c` but for its bases.  MUX: the multiplexed mode; mx is the slot's
+// group state and becomes the one behind the last page passed (`limit` counts recorded pages: foreign pages take no
+// record, and the second walk of a stream passes the same foreign pages between them as the first).
+template <bool MUX>
 VBMX_HD void oggfeed_walk(const uint8_t *work, long long at, long long run_end, const OggFeedState &st,
                           const OggFeedCaps &caps, int end_flag, int limit, bool bad_at_limit, OggDmxPage *pages,
-                          long long room, int slot, OggFeedCall &c)
+                          long long room, int slot, OggFeedCall &c, OggFeedMux &mx)
 {
     oggfeed_call_begin(st, at, slot, c);
     if (st.status || st.done) return;                              // bytes for a failed or ended stream are ignored
@@ -107,6 +197,20 @@ VBMX_HD void oggfeed_walk(const uint8_t *work, long long at, long long run_end, 
     w.cnt = st.cnt, w.partial = st.partial;
     int status = 0, n = 0;
     while (n < limit) {
+        OggFeedMux nm = {};
+        if (MUX) {
+            int len = 0;
+            const int f = oggfeed_mux_step(work, w.pos, run_end, w.cnt.serial, mx, nm, len);
+            if (f == 1) {                                          // foreign: stepped over whole
+                mx = nm;
+                w.pos += len;
+                continue;
+            }
+            if (f < 0) {
+                if (f == -1) status = VBM_EOGG;
+                break;
+            }
+        }
         const OggDmxWalk before = w;
         OggDmxPage pg;
         const int r = oggdmx_walk_step(work, w, pg);
@@ -125,6 +229,7 @@ VBMX_HD void oggfeed_walk(const uint8_t *work, long long at, long long run_end, 
             break;
         }
         pages[n++] = pg;
+        if (MUX) mx = nm;
     }
     if (bad_at_limit && n == limit) status = VBM_EOGG;
     long long tail = status ? 0 : run_end - w.pos;
@@ -210,12 +315,14 @@ VBMX_HD bool oggfeed_rs_capture(uint32_t w) { return w == 0x5367674fu; }   // "O
 //   head(h, left, hd)      the candidate at h with `left` bytes in front of the run's end: 1 whole (hd filled), 0 no
 //                          header (version), -2 the header, the lacing table or the body is not all here
 //   crc(h, len)            the page carries its own checksum
+//   mark(h, hd)            (multiplexed mode) the first 7 body bytes of the whole page hd at h are the mark of ogg_select.h
+// MUX: the multiplexed mode; mx is the slot's group state and becomes the one behind the last page passed.
 // No byte is read before it is known to lie in front of run_end; every turn of the loop moves pos on by one byte at least
 // or leaves it.  Fills `c` but for its bases, and `r`.
-template <class Ops>
+template <bool MUX, class Ops>
 VBMX_HD void oggfeed_rs_walk(const Ops &ops, const uint8_t *work, long long at, long long run_end, int tail_in,
                              const OggFeedState &st, const OggFeedLink &lk0, const OggFeedCaps &caps, int end_flag,
-                             OggDmxPage *pages, long long room, int slot, OggFeedCall &c, OggFeedRsCall &r)
+                             OggDmxPage *pages, long long room, int slot, OggFeedCall &c, OggFeedRsCall &r, OggFeedMux &mx)
 {
     oggfeed_call_begin(st, at, slot, c);
     r.next = lk0;
@@ -255,8 +362,20 @@ VBMX_HD void oggfeed_rs_walk(const Ops &ops, const uint8_t *work, long long at, 
             continue;
         }
         // 2 whose page
+        OggFeedMux nm = {};
+        if (MUX) {
+            nm = mx;
+            const auto mark = [&] { return ops.mark(h, hd); };
+            if (!oggfeed_mux_page(nm, cnt.serial, hd.flags, hd.serial, hd.body, mark)) {   // foreign, head or not
+                mx = nm;
+                ignored++;
+                pos += len;
+                continue;
+            }
+        }
         const bool start = (hd.flags & 2) != 0, cont = (hd.flags & 1) != 0;
         if (!start && (lk.links == 0 || lk.bad || lk.eos || hd.serial != cnt.serial)) {
+            if (MUX) mx = nm;
             ignored++;
             pos += len;
             continue;
@@ -279,6 +398,7 @@ VBMX_HD void oggfeed_rs_walk(const Ops &ops, const uint8_t *work, long long at, 
         if (disc) {                                                // 3 discontinuity
             if (pre.packets < 3) {                                 // headers open: the link is bad, the page is used up
                 nl.bad = 1;
+                if (MUX) mx = nm;
                 cnt = pre, lk = nl, partial = 0;
                 started = started || start;
                 if (start) base = pre;
@@ -320,6 +440,7 @@ VBMX_HD void oggfeed_rs_walk(const Ops &ops, const uint8_t *work, long long at, 
         partial = np;
         lk = nl;
         if (hd.flags & 4) lk.eos = 1;
+        if (MUX) mx = nm;
         took = true;
         pos += len;
     }
@@ -368,7 +489,7 @@ VBMX_HD void oggfeed_rs_walk(const Ops &ops, const uint8_t *work, long long at, 
     r.ev.left = left;
 }
 
-// the host's three: byte after byte
+// the host's four: byte after byte
 struct OggFeedSerialOps {
     const uint32_t *T;
     const OggMuxPow *pw;
@@ -393,6 +514,12 @@ struct OggFeedSerialOps {
     }
 
     bool crc(const uint8_t *h, int len) const { return oggdmx_page_crc_ok(T, *pw, h, len); }
+
+    bool mark(const uint8_t *h, const OggFeedHead &hd) const
+    {
+        const uint8_t *b = h + 27 + hd.nseg;                       // asked for only when the body has 7 bytes or more
+        return oggsel_is_mark(oggdmx_rd32(b), (uint32_t)b[4] | ((uint32_t)b[5] << 8) | ((uint32_t)b[6] << 16));
+    }
 };
 
 VBMX_HD void oggfeed_rs_info(const OggFeedCall &c, const OggFeedRsCall &r, vbm_ogg_feed_info &fi)

@@ -25,6 +25,10 @@
 //                             the body length, and the CRC is dmx_wave_page_crc at once, because it decides where the
 //                             walk goes next
 //          k_feed_events      one lane per listed stream: its event struct
+// A multiplexed feed (VBM_OGG_FEED_MULTIPLEXED) runs the <true> forms of k_feed_walk, k_feed_settle and
+// k_feed_resync_walk: the same walks with the group rule of ogg_feed.h in front of every page.  The strict walk reads a
+// head page's 7 mark bytes plainly; the wave walk takes them out of the dwords its `head` op has already loaded.  The
+// other feeds run the <false> forms, in which no statement of the rule is left.
 // Nothing of a slot changes before k_feed_commit, which runs only after a fill that wrote its outputs.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -55,6 +59,8 @@ struct FeedMem {                   // the feed's state and workspace
     int *bad, *status, *committed;
     OggFeedLink *link;             // resync feeds only (else null): [max_streams] the slots' links,
     OggFeedRsCall *rs;             // [max_streams] the listed streams of the scan beside `call`
+    OggFeedMux *mux, *mux_next;    // multiplexed feeds only (else null): [max_streams] the slots' groups, and those of
+                                   // the listed streams once the scan is committed
 };
 
 VBMX_HD long long feed_at(const long long *off, int i, const OggFeedCaps &caps)
@@ -65,6 +71,7 @@ VBMX_HD long long feed_at(const long long *off, int i, const OggFeedCaps &caps)
 VBMX_HD long long feed_first_rec(const long long *off, int i) { return (off[i] - off[0]) / 27 + i; }
 
 // stream i of the list, walked from its slot's state over its run in the work buffer
+template <bool MUX>
 VBMX_HD void feed_walk_one(const FeedArgs &a, const FeedMem &m, const OggFeedCaps &caps, int i, int limit, bool bad_at_limit,
                            OggFeedCall &c)
 {
@@ -72,8 +79,11 @@ VBMX_HD void feed_walk_one(const FeedArgs &a, const FeedMem &m, const OggFeedCap
     const OggFeedState st = m.state[slot];
     const long long at = feed_at(a.off, i, caps), rec = feed_first_rec(a.off, i);
     const long long run_end = at + oggfeed_tail_in(st, caps) + (a.off[i + 1] - a.off[i]);
-    oggfeed_walk(m.work, at, run_end, st, caps, a.end[i], limit, bad_at_limit, m.pages + rec,
-                 feed_first_rec(a.off, i + 1) - rec, slot, c);
+    OggFeedMux mx = {};
+    if (MUX) mx = m.mux[slot];
+    oggfeed_walk<MUX>(m.work, at, run_end, st, caps, a.end[i], limit, bad_at_limit, m.pages + rec,
+                      feed_first_rec(a.off, i + 1) - rec, slot, c, mx);
+    if (MUX) m.mux_next[i] = mx;
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------
@@ -97,19 +107,20 @@ __global__ void __launch_bounds__(256) k_feed_gather(int n, FeedArgs a, FeedMem 
     }
 }
 
+template <bool MUX>
 __global__ void __launch_bounds__(64) k_feed_walk(int n, FeedArgs a, FeedMem m, OggFeedCaps caps)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
     OggFeedCall c;
-    feed_walk_one(a, m, caps, i, INT_MAX, false, c);
+    feed_walk_one<MUX>(a, m, caps, i, INT_MAX, false, c);
     m.call[i] = c;
     m.npages[i] = c.npages;
     m.count[2 * i] = c.packets, m.count[2 * i + 1] = c.payload_bytes;
     m.bad[i] = INT_MAX;
 }
 
-// oggfeed_rs_walk's three by the 64 lanes of a wavefront; every result is the same in every lane
+// oggfeed_rs_walk's four by the 64 lanes of a wavefront; every result is the same in every lane
 struct FeedWaveOps {
     const uint32_t *T;             // the CRC table in LDS
     const OggMuxPow *pw;
@@ -142,7 +153,30 @@ struct FeedWaveOps {
         int body = (int)((v & 0xff) + ((v >> 8) & 0xff) + ((v >> 16) & 0xff) + (v >> 24));
         for (int m = 32; m >= 1; m >>= 1) body += __shfl_xor(body, m, 64);
         hd.body = __builtin_amdgcn_readfirstlane(body);
+        hd.lace = lw;
         return left - 27 - hd.nseg < hd.body ? -2 : 1;
+    }
+
+    // The page is whole and its body has 7 bytes or more.  They begin at byte nseg of the 256 that `head` loaded, four
+    // to a lane: with 244 segments or fewer, bytes nseg .. nseg + 7 lie in the dwords of lanes nseg / 4 .. nseg / 4 + 2
+    // (62 at most; the eighth byte, which may lie behind the run and then reads as 0, is masked by oggsel_is_mark).  A
+    // head page of more segments takes a second round trip: 7 byte reads at the same address in every lane.
+    __device__ bool mark(const uint8_t *h, const OggFeedHead &hd) const
+    {
+        uint32_t lo, hi;
+        if (hd.nseg <= 244) {
+            const int d = hd.nseg >> 2, sh = (hd.nseg & 3) * 8;
+            const uint64_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)hd.lace, d);
+            const uint64_t w1 = (uint32_t)__builtin_amdgcn_readlane((int)hd.lace, d + 1);
+            const uint64_t w2 = (uint32_t)__builtin_amdgcn_readlane((int)hd.lace, d + 2);
+            lo = (uint32_t)((w0 | (w1 << 32)) >> sh);
+            hi = (uint32_t)((w1 | (w2 << 32)) >> sh);
+        } else {
+            const uint8_t *b = h + 27 + hd.nseg;
+            lo = dmx_load4(b, 4);
+            hi = dmx_load4(b + 4, 3);
+        }
+        return oggsel_is_mark(lo, hi);
     }
 
     __device__ bool crc(const uint8_t *h, int len) const
@@ -158,19 +192,24 @@ struct FeedWaveOps {
     }
 };
 
-// stream i of the list by the rules of the resync mode
-template <class Ops>
+// stream i of the list by the rules of the resync mode; writer: this caller stores the group state (the device walk
+// holds it in every lane)
+template <bool MUX, class Ops>
 VBMX_HD void feed_rs_walk_one(const Ops &ops, const FeedArgs &a, const FeedMem &m, const OggFeedCaps &caps, int i,
-                              OggFeedCall &c, OggFeedRsCall &r)
+                              OggFeedCall &c, OggFeedRsCall &r, bool writer)
 {
     const int slot = a.ids[i];
     const OggFeedState st = m.state[slot];
     const long long at = feed_at(a.off, i, caps), rec = feed_first_rec(a.off, i);
     const int tail_in = oggfeed_tail_in(st, caps);
-    oggfeed_rs_walk(ops, m.work, at, at + tail_in + (a.off[i + 1] - a.off[i]), tail_in, st, m.link[slot], caps, a.end[i],
-                    m.pages + rec, feed_first_rec(a.off, i + 1) - rec, slot, c, r);
+    OggFeedMux mx = {};
+    if (MUX) mx = m.mux[slot];
+    oggfeed_rs_walk<MUX>(ops, m.work, at, at + tail_in + (a.off[i + 1] - a.off[i]), tail_in, st, m.link[slot], caps,
+                         a.end[i], m.pages + rec, feed_first_rec(a.off, i + 1) - rec, slot, c, r, mx);
+    if (MUX && writer) m.mux_next[i] = mx;
 }
 
+template <bool MUX>
 __global__ void __launch_bounds__(256) k_feed_resync_walk(int n, OggMuxPow pw, FeedArgs a, FeedMem m, OggFeedCaps caps)
 {
     __shared__ uint32_t T[256];
@@ -182,7 +221,7 @@ __global__ void __launch_bounds__(256) k_feed_resync_walk(int n, OggMuxPow pw, F
     for (int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < n; i += nwaves) {
         OggFeedCall c;
         OggFeedRsCall r;
-        feed_rs_walk_one(ops, a, m, caps, i, c, r);
+        feed_rs_walk_one<MUX>(ops, a, m, caps, i, c, r, lane == 0);
         if (lane == 0) {
             m.call[i] = c;
             m.rs[i] = r;
@@ -220,6 +259,7 @@ __global__ void __launch_bounds__(256) k_feed_crc(int n, OggMuxPow pw, FeedArgs 
     }
 }
 
+template <bool MUX>
 __global__ void __launch_bounds__(64) k_feed_settle(int n, FeedArgs a, FeedMem m, OggFeedCaps caps)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -227,7 +267,7 @@ __global__ void __launch_bounds__(64) k_feed_settle(int n, FeedArgs a, FeedMem m
     const int bad = m.bad[i];
     if (bad >= m.npages[i]) return;
     OggFeedCall c;                                  // pages from the bad one on are not taken
-    feed_walk_one(a, m, caps, i, bad, true, c);
+    feed_walk_one<MUX>(a, m, caps, i, bad, true, c);
     m.call[i] = c;
     m.count[2 * i] = c.packets, m.count[2 * i + 1] = c.payload_bytes;
 }
@@ -322,6 +362,7 @@ __global__ void __launch_bounds__(256) k_feed_commit(int n, FeedArgs a, FeedMem 
             dmx_wave_copy(m.tail + (long long)c.slot * caps.max_page_carry, m.work + c.pos_end, tail, lane);
         if (lane == 0) m.state[c.slot] = c.next;
         if (lane == 0 && m.rs) m.link[c.slot] = m.rs[i].next;
+        if (lane == 0 && m.mux) m.mux[c.slot] = m.mux_next[i];
     }
 }
 
@@ -330,12 +371,14 @@ __global__ void k_feed_mark(FeedMem m)
     if (*m.status == 0) *m.committed = 1;
 }
 
-__global__ void __launch_bounds__(256) k_feed_reset(int n, const int *ids, OggFeedState *state, OggFeedLink *link)
+__global__ void __launch_bounds__(256) k_feed_reset(int n, const int *ids, OggFeedState *state, OggFeedLink *link,
+                                                    OggFeedMux *mux)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     state[ids[i]] = OggFeedState{};
     if (link) link[ids[i]] = OggFeedLink{};
+    if (mux) mux[ids[i]] = OggFeedMux{};
 }
 
 }  // namespace
@@ -343,7 +386,7 @@ __global__ void __launch_bounds__(256) k_feed_reset(int n, const int *ids, OggFe
 // ---- host side (scaffold: twin_host.h) --------------------------------------------------------------------------
 
 struct vbm_ogg_feed {
-    bool host = false, resync = false;
+    bool host = false, resync = false, mux = false;
     int max_streams = 0;
     long long max_call_bytes = 0;
     OggFeedCaps caps = {};
@@ -377,10 +420,10 @@ int create(vbm_ogg_feed **out, int max_streams, long long max_call_bytes, int ma
            int header_cap, unsigned flags, bool host, const char *name)
 {
     if (!out || max_streams < 1 || max_call_bytes < 0 || max_page_carry < 1 || max_page_carry > 65307 ||
-        max_packet_bytes < 1 || header_cap < 1 || (flags & ~VBM_OGG_FEED_RESYNC))
+        max_packet_bytes < 1 || header_cap < 1 || (flags & ~(VBM_OGG_FEED_RESYNC | VBM_OGG_FEED_MULTIPLEXED)))
         return fail(VBM_EINVAL, std::string(name) + ": bad argument (max_streams >= 1, max_call_bytes >= 0, max_page_carry "
-                                                    "in 1..65307, max_packet_bytes >= 1, header_cap >= 1, flags 0 or "
-                                                    "VBM_OGG_FEED_RESYNC)");
+                                                    "in 1..65307, max_packet_bytes >= 1, header_cap >= 1, flags of "
+                                                    "VBM_OGG_FEED_RESYNC | VBM_OGG_FEED_MULTIPLEXED)");
     if (!host) {
         int n = 0;
         if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(VBM_ENODEV, "vbm_ogg_feed_create: no HIP device");
@@ -389,6 +432,7 @@ int create(vbm_ogg_feed **out, int max_streams, long long max_call_bytes, int ma
     if (!f) return fail(VBM_EFAULT, "vbm_ogg_feed_create: out of memory");
     f->host = f->mem.host = host;
     f->resync = (flags & VBM_OGG_FEED_RESYNC) != 0;
+    f->mux = (flags & VBM_OGG_FEED_MULTIPLEXED) != 0;
     f->max_streams = max_streams;
     f->max_call_bytes = max_call_bytes;
     f->caps = {max_page_carry, max_packet_bytes, header_cap};
@@ -419,6 +463,8 @@ int create(vbm_ogg_feed **out, int max_streams, long long max_call_bytes, int ma
     if (!rc) rc = f->mem.get(f->args, args_bytes(max_streams), who);
     if (!rc && f->resync) rc = f->mem.get(f->m.link, S, who);
     if (!rc && f->resync) rc = f->mem.get(f->m.rs, S, who);
+    if (!rc && f->mux) rc = f->mem.get(f->m.mux, S, who);
+    if (!rc && f->mux) rc = f->mem.get(f->m.mux_next, S, who);
     if (!rc && !host) rc = f->stage.create(args_bytes(max_streams), "vbm_ogg_feed_create: staging");
     if (rc) {
         vbm_ogg_feed_destroy(f);
@@ -568,13 +614,16 @@ extern "C" int vbm_ogg_feed_scan(vbm_ogg_feed *f, int n, const int *ids, const u
     const FeedArgs a = args_view(f->args, n);
     if (n > 0) {
         hipLaunchKernelGGL(k_feed_gather, wave_grid(n), dim3(256), 0, q, n, a, f->m, f->caps, d_data);
-        if (f->resync) hipLaunchKernelGGL(k_feed_resync_walk, wave_grid(n), dim3(256), 0, q, n, f->pow, a, f->m, f->caps);
-        else hipLaunchKernelGGL(k_feed_walk, dim3((n + 63) / 64), dim3(64), 0, q, n, a, f->m, f->caps);
+        const auto rs_walk = f->mux ? k_feed_resync_walk<true> : k_feed_resync_walk<false>;
+        const auto walk = f->mux ? k_feed_walk<true> : k_feed_walk<false>;
+        if (f->resync) hipLaunchKernelGGL(rs_walk, wave_grid(n), dim3(256), 0, q, n, f->pow, a, f->m, f->caps);
+        else hipLaunchKernelGGL(walk, dim3((n + 63) / 64), dim3(64), 0, q, n, a, f->m, f->caps);
     }
     hipLaunchKernelGGL(k_feed_scan_pages, dim3(1), dim3(256), 0, q, n, f->m.npages, f->m.page_base);
     if (n > 0 && !f->resync) {                      // a resync walk has judged every CRC itself
         hipLaunchKernelGGL(k_feed_crc, page_grid(f), dim3(256), 0, q, n, f->pow, a, f->m);
-        hipLaunchKernelGGL(k_feed_settle, dim3((n + 63) / 64), dim3(64), 0, q, n, a, f->m, f->caps);
+        const auto settle = f->mux ? k_feed_settle<true> : k_feed_settle<false>;
+        hipLaunchKernelGGL(settle, dim3((n + 63) / 64), dim3(64), 0, q, n, a, f->m, f->caps);
     }
     hipLaunchKernelGGL(k_feed_scan_counts, dim3(1), dim3(256), 0, q, n, f->m, d_totals);
     if (n > 0) hipLaunchKernelGGL(k_feed_info, dim3((n + 255) / 256), dim3(256), 0, q, n, f->m, d_info);
@@ -670,6 +719,7 @@ extern "C" int vbm_ogg_feed_reset_streams(vbm_ogg_feed *f, int n, const int *ids
         for (int i = 0; i < n; i++) {
             f->m.state[ids[i]] = OggFeedState{};
             if (f->resync) f->m.link[ids[i]] = OggFeedLink{};
+            if (f->mux) f->m.mux[ids[i]] = OggFeedMux{};
         }
         return VBM_OK;
     }
@@ -678,7 +728,7 @@ extern "C" int vbm_ogg_feed_reset_streams(vbm_ogg_feed *f, int n, const int *ids
     rc = upload_args(f, n, ids, nullptr, nullptr, q, "vbm_ogg_feed_reset_streams: upload of the ids");
     if (rc) return rc;
     hipLaunchKernelGGL(k_feed_reset, dim3((n + 255) / 256), dim3(256), 0, q, n, args_view(f->args, n).ids,
-                       f->m.state, f->m.link);
+                       f->m.state, f->m.link, f->m.mux);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? VBM_OK : vbm_set_hip_error(e, "vbm_ogg_feed_reset_streams: launch");
 }
@@ -708,14 +758,17 @@ extern "C" int vbm_host_ogg_feed_scan(vbm_ogg_feed *f, int n, const int *ids, co
             if (a.off[i + 1] > a.off[i]) memcpy(run + tail, data + a.off[i], (size_t)(a.off[i + 1] - a.off[i]));
         }
         OggFeedCall c;
+        const auto walk_one = f->mux ? feed_walk_one<true> : feed_walk_one<false>;
         if (f->resync) {
-            feed_rs_walk_one(OggFeedSerialOps{T, &f->pow}, a, m, f->caps, i, c, m.rs[i]);
+            const OggFeedSerialOps ops = {T, &f->pow};
+            if (f->mux) feed_rs_walk_one<true>(ops, a, m, f->caps, i, c, m.rs[i], true);
+            else feed_rs_walk_one<false>(ops, a, m, f->caps, i, c, m.rs[i], true);
         } else {
-            feed_walk_one(a, m, f->caps, i, INT_MAX, false, c);
+            walk_one(a, m, f->caps, i, INT_MAX, false, c);
             const OggDmxPage *pages = m.pages + feed_first_rec(a.off, i);
             for (int k = 0; k < c.npages; k++) {
                 if (oggdmx_page_crc_ok(T, f->pow, m.work + pages[k].at, pages[k].len)) continue;
-                feed_walk_one(a, m, f->caps, i, k, true, c);       // pages from the bad one on are not taken
+                walk_one(a, m, f->caps, i, k, true, c);            // pages from the bad one on are not taken
                 break;
             }
         }
@@ -791,6 +844,7 @@ static int fill_host(vbm_ogg_feed *f, uint8_t *payload, long long payload_cap, l
             memcpy(m.tail + (size_t)c.slot * (size_t)f->caps.max_page_carry, m.work + c.pos_end, (size_t)tail);
         m.state[c.slot] = c.next;
         if (f->resync) m.link[c.slot] = m.rs[i].next;
+        if (f->mux) m.mux[c.slot] = m.mux_next[i];
     }
     f->host_committed = true;
     return VBM_OK;

@@ -699,17 +699,24 @@ class OggFeed(_TwinHandle):
                 link_of[r.ids[i]] = r.link[i]     # (r.link_started marks the call its first page came in)
             live = np.flatnonzero(r.counts)
             dec.synthesis_runs(r.ids[live], r.counts[live], r.payload, r.offsets, granulepos=r.granulepos, eos=r.eos,
-                               gap=r.gap)"""
+                               gap=r.gap)
+
+    multiplexed=True (with or without resync) is for mounts that carry video, a Skeleton track or text beside the audio
+    (include/vorbis_mi355x.h, "Multiplexed mode"): per slot, the pages of every stream but the group's first Vorbis
+    stream are stepped over as they arrive, and push, push_all, headers and reset are used as before.  A resync feed
+    counts them in events["ignored_pages"].  max_page_carry has to cover the largest foreign page."""
 
     EOGG, EBIG = -1002, -1003
-    RESYNC = 1
+    RESYNC, MULTIPLEXED = 1, 4
 
     def __init__(self, max_streams, max_call_bytes, max_page_carry=65307, max_packet_bytes=65536, header_cap=16384,
-                 host=False, device=None, resync=False):
+                 host=False, device=None, resync=False, multiplexed=False):
         self.max_streams, self.max_call_bytes, self.resync = int(max_streams), int(max_call_bytes), bool(resync)
+        self.multiplexed = bool(multiplexed)
         args = (self.max_streams, self.max_call_bytes, int(max_page_carry), int(max_packet_bytes), int(header_cap))
-        if resync:
-            super().__init__("feed", host, device, *args, self.RESYNC, create="create2")
+        flags = (self.RESYNC if resync else 0) | (self.MULTIPLEXED if multiplexed else 0)
+        if flags:
+            super().__init__("feed", host, device, *args, flags, create="create2")
         else:
             super().__init__("feed", host, device, *args)
 
