@@ -1,7 +1,6 @@
 """Shared by test_ogg_chain_cpu.py and test_ogg_chain_gpu.py: chained corpora, the rule of csrc/ogg_chain.h as a page
 walker in Python (the first yardstick; the second is vbm_ogg_demux on each link's bytes, ogg_demux_batch.single), and
 the C calls of the split's host twin and device form over one interface."""
-import ctypes as C
 import functools
 import struct
 
@@ -9,28 +8,15 @@ import numpy as np
 
 from tests import ogg_demux_batch as B
 from tests.ogg_demux_batch import ECAP, EINVAL, EOGG  # noqa: F401
-from tests.test_ogg_demux_cpu import _corruptions, _pages, _recrc
+from tests.ogg_pages import corruptions, parse, random_bytes, recrc, split_pages
+from tests.ogg_twin import Result, Twin
 
 
 # ---- the rule ----------------------------------------------------------------------------------------------------------
 
 def walk(data, begin, end):
     """-> the link starts of the file data[begin:end]"""
-    starts, pos = [begin], begin
-    while end - pos >= 27:
-        h = data[pos:pos + 27]
-        if h[:4] != b"OggS" or h[4] != 0:
-            break
-        nseg = h[26]
-        if end - pos - 27 < nseg:
-            break
-        body = sum(data[pos + 27:pos + 27 + nseg])
-        if end - pos - 27 - nseg < body:
-            break
-        if h[5] & 2 and pos != begin:
-            starts.append(pos)
-        pos += 27 + nseg + body
-    return starts
+    return [begin] + [p.pos for p in parse(data, begin, end) if p.flags & 2 and p.pos != begin]
 
 
 def expected(blobs, first=0):
@@ -54,14 +40,10 @@ def links_of(blob):
 def reserial(blob, serialno):
     """the same pages under another serial number"""
     out = []
-    for p in _pages(blob):
+    for p in split_pages(blob):
         p[14:18] = struct.pack("<I", serialno)
-        out.append(bytes(_recrc(p)))
+        out.append(bytes(recrc(p)))
     return b"".join(out)
-
-
-def _rb(rng, n):
-    return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,7 +54,7 @@ def small_links(n):
     setup = v.Setup(1, 44100, 0.1)
     out = []
     for k in range(n):
-        pk = [_rb(rng, int(x)) for x in rng.integers(0, 400, 1 + k % 5)]
+        pk = [random_bytes(rng, int(x)) for x in rng.integers(0, 400, 1 + k % 5)]
         out.append(v.write_ogg(setup, pk, [(64 * (i + 1), i == len(pk) - 1) for i in range(len(pk))], serialno=1000 + k))
     return out
 
@@ -84,20 +66,20 @@ def class_links():
     rng = np.random.default_rng(41)
     out = []
     for k, (ch, rate, q) in enumerate([(1, 8000, 0.5), (2, 44100, 0.5), (6, 48000, 0.8)]):
-        pk = [_rb(rng, n) for n in (17, 255, 900, 0, 4100)]
+        pk = [random_bytes(rng, n) for n in (17, 255, 900, 0, 4100)]
         out.append(v.write_ogg(v.Setup(ch, rate, q), pk, [(256 * (i + 1), i == 4) for i in range(5)], serialno=2000 + k))
     return out
 
 
 def _with_empty_page(blob):
     """a 27-byte page (no segments) put in behind the first page, the later pages renumbered"""
-    pages = _pages(blob)
+    pages = split_pages(blob)
     empty = bytearray(pages[0][:27])
     empty[5], empty[26] = 0, 0
     pages.insert(1, empty)
     for k, p in enumerate(pages):
         p[18:22] = struct.pack("<I", k)
-        _recrc(p)
+        recrc(p)
     return b"".join(bytes(p) for p in pages)
 
 
@@ -110,15 +92,16 @@ def shaped_links():
            "255 segments": reserial(d["packet over three pages"], 3003),
            "zero segments": _with_empty_page(small_links(3)[2]),
            "70 KB comment": reserial(d["header packet spans pages"], 3005)}
-    assert any(p[26] == 255 for p in _pages(out["255 segments"])) and any(len(p) == 27 for p in _pages(out["zero segments"]))
+    assert any(p[26] == 255 for p in split_pages(out["255 segments"]))
+    assert any(len(p) == 27 for p in split_pages(out["zero segments"]))
     assert B.single(out["zero segments"]) is not None
     return out
 
 
 def _flag(blob, page, set_bits=0, clear_bits=0):
-    pages = _pages(blob)
+    pages = split_pages(blob)
     pages[page][5] = (pages[page][5] | set_bits) & ~clear_bits
-    _recrc(pages[page])
+    recrc(pages[page])
     return b"".join(bytes(p) for p in pages)
 
 
@@ -127,7 +110,7 @@ def chains():
     """name -> (file, the number of links the rule gives it, or None where only the walker says)"""
     a, b, c = small_links(3)
     sh = shaped_links()
-    pa, pb = _pages(a), _pages(b)
+    pa, pb = split_pages(a), split_pages(b)
     j = b"".join
     out = {"1 link": (a, 1), "2 links": (a + b, 2), "3 links": (a + b + c, 3), "65 links": (j(small_links(65)), 65),
            "three classes": (j(class_links()), 3),
@@ -143,7 +126,7 @@ def chains():
     return out
 
 
-# The middle link of three under every _corruptions variant: which links the rule finds, and which of them the demux then
+# The middle link of three under every corruptions variant: which links the rule finds, and which of them the demux then
 # accepts.  A page that no longer parses ends the walk, so everything behind it stays with the link it lies in; a page
 # that still parses (bad CRC, serial, sequence, continuation) costs its own link only.
 MIDDLE = {"capture pattern": [False],                        # the link's first page: it never starts, link 0 takes it all
@@ -166,10 +149,10 @@ def middle_corruptions():
     import vorbis_aotuv_lancer_amd as v
     rng = np.random.default_rng(43)
     # the middle link needs a page that continues a packet
-    pk = [_rb(rng, n) for n in (300, 70000, 20, 700)]
+    pk = [random_bytes(rng, n) for n in (300, 70000, 20, 700)]
     mid = v.write_ogg(v.Setup(1, 44100, 0.1), pk, [(128 * (i + 1), i == 3) for i in range(4)], serialno=4000)
     a, b, _ = small_links(3)
-    return {name: a + bad + b for name, bad in _corruptions(mid).items()}
+    return {name: a + bad + b for name, bad in corruptions(mid).items()}
 
 
 def alignment_batch():
@@ -197,65 +180,16 @@ def two_link_file():
     return blob, reserial(blob, 5001)
 
 
-# ---- one interface over the host twin and the device calls ------------------------------------------------------------
+# ---- the host twin and the device calls (ogg_twin.Twin) ------------------------------------------------------------------
 
-class Result:
-    pass
-
-
-class Chain:
-    """A splitter and its buffers.  impl 'host': numpy arrays and vbm_host_ogg_chain_split; 'device': torch tensors and
-    vbm_ogg_chain_split on the current stream."""
+class Chain(Twin):
+    """A splitter and its buffers"""
 
     def __init__(self, impl, max_files, max_bytes):
-        self.impl, self.lib = impl, B._lib()
-        self.h = C.c_void_p()
-        make = self.lib.vbm_host_ogg_chain_create if impl == "host" else self.lib.vbm_ogg_chain_create
-        rc = make(C.byref(self.h), max_files, max_bytes)
-        assert rc == 0, (rc, self.lib.vbm_last_error())
-        self.keep = None
-
-    def close(self):
-        if self.impl == "device":
-            import torch
-            torch.cuda.synchronize()
-        self.lib.vbm_ogg_chain_destroy(self.h)
-
-    def _new(self, n, fill):
-        if self.impl == "host":
-            return np.full(n, fill, np.int64)
-        import torch
-        return torch.full((n,), fill, dtype=torch.int64, device="cuda")
-
-    def _ptr(self, a):
-        return a.ctypes.data if self.impl == "host" else a.data_ptr()
-
-    def _back(self, a):
-        return a if self.impl == "host" else a.cpu().numpy()
-
-    def _q(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        super().__init__(impl, "chain", max_files, max_bytes)
 
     def split_raw(self, nfiles, data_ptr, off_ptr, file_links_ptr, link_offsets_ptr, link_cap):
-        if self.impl == "host":
-            return self.lib.vbm_host_ogg_chain_split(self.h, nfiles, data_ptr, off_ptr, file_links_ptr, link_offsets_ptr,
-                                                     link_cap)
-        return self.lib.vbm_ogg_chain_split(self.h, nfiles, data_ptr, off_ptr, file_links_ptr, link_offsets_ptr, link_cap,
-                                            self._q())
-
-    def status(self):
-        st = C.c_int(-7)
-        assert self.lib.vbm_ogg_chain_status(self.h, C.byref(st), None if self.impl == "host" else self._q()) == 0
-        return st.value
-
-    def upload(self, data):
-        """uint8 numpy -> the address the split takes (kept alive here)"""
-        if self.impl == "device":
-            import torch
-            data = torch.from_numpy(data.copy()).cuda()
-        self.keep = data
-        return self._ptr(data) if len(data) else None
+        return self.call("chain_split", nfiles, data_ptr, off_ptr, file_links_ptr, link_offsets_ptr, link_cap)
 
     def split(self, data, offsets, link_cap, canary=8):
         """data: uint8 numpy or an address -> Result: .file_links [n + 1], .link_offsets [link_cap + 1], .status,
@@ -263,17 +197,14 @@ class Chain:
         n = len(offsets) - 1
         if isinstance(data, np.ndarray):
             data = self.upload(data)
-        blank = -0x5A5A
-        fl, lo = self._new(n + 1 + canary, blank), self._new(link_cap + 1 + canary, blank)
+        fl, lo = self.guarded(n + 1, np.int64, canary), self.guarded(link_cap + 1, np.int64, canary)
         off = np.ascontiguousarray(offsets, np.int64)
-        rc = self.split_raw(n, data, off.ctypes.data, self._ptr(fl), self._ptr(lo), link_cap)
+        rc = self.split_raw(n, data, off.ctypes.data, self.ptr(fl), self.ptr(lo), link_cap)
         assert rc == 0, (rc, self.lib.vbm_last_error())
         r = Result()
         r.status = self.status()
-        fl, lo = self._back(fl), self._back(lo)
-        r.canaries_ok = bool((fl[n + 1:] == blank).all() and (lo[link_cap + 1:] == blank).all())
-        r.touched = bool((lo[:link_cap + 1] != blank).any())
-        r.file_links, r.link_offsets = fl[:n + 1], lo[:link_cap + 1]
+        (r.file_links, _, ok0), (r.link_offsets, r.touched, ok1) = self.unguard(fl, n + 1), self.unguard(lo, link_cap + 1)
+        r.canaries_ok = ok0 and ok1
         return r
 
 

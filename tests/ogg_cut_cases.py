@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 from tests.test_decode_index_cpu import G, split_dump, true_granules, with_bad_packets
-from tests.test_stream_wrapper import parse_pages as _parse_pages
+from tests.ogg_pages import parse_pages, random_bytes
 
 ECAP, ESHAPE, EINVAL = 1, 2, -131
 SERIAL = 77                                               # of the sources
@@ -118,7 +118,7 @@ def synthetic_source(sizes, seed=3, step=100):
     rng = np.random.default_rng(seed)
     src = Source.__new__(Source)
     src.name, src.headers = "synthetic", [b"\x01vorbis-id", b"\x03vorbis-comment", b"\x05vorbis-setup" * 40]
-    packets = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in sizes]
+    packets = [random_bytes(rng, n) for n in sizes]
     src.data = np.frombuffer(b"".join(packets), np.uint8).copy()
     src.offsets = np.cumsum([0] + list(sizes)).astype(np.int64)
     P = len(sizes)
@@ -196,22 +196,6 @@ def model(src, s, L, serial):
     finally:
         os_.close()
     return b"".join(out), s, got, 0, (pre, k, m)
-
-
-@functools.lru_cache(maxsize=4096)
-def _checked_page(page):
-    return _parse_pages(page)[0]
-
-
-def parse_pages(blob):
-    """test_stream_wrapper.parse_pages (bitwise CRC of every page), a page seen before taken from a cache"""
-    out, at = [], 0
-    while at < len(blob):
-        nseg = blob[at + 26]
-        size = 27 + nseg + sum(blob[at + 27:at + 27 + nseg])
-        out.append(_checked_page(bytes(blob[at:at + size])))
-        at += size
-    return out
 
 
 def check_cut(src, cut, length, pkm, serial):

@@ -5,14 +5,10 @@ import functools
 
 import numpy as np
 
-from tests.test_ogg_demux_cpu import _corruptions, _streams
+from tests.ogg_pages import corruptions, pack, random_bytes, split_pages
+from tests.ogg_twin import Result, Twin, lib as _lib
 
 EOGG, EINVAL, ECAP = -1002, -131, 1
-
-
-def _lib():
-    from vorbis_aotuv_lancer_amd._lib import lib
-    return lib
 
 
 def _info_dtype():
@@ -40,12 +36,30 @@ def _paged(v, packets, flush_after_headers, comments=(), setup=None):
     return b"".join(out)
 
 
+def streams(v):
+    """(name, .ogg bytes) of write_ogg output: several classes' headers, with packets that span pages, packets whose
+    lengths are multiples of 255 (0 included), and an eos packet"""
+    rng = np.random.default_rng(5)
+    out = []
+    for ch, rate, q in [(1, 44100, 0.1), (2, 44100, 0.5), (6, 48000, 0.8), (2, 96000, 0.5)]:
+        setup = v.Setup(ch, rate, q)
+        lens = [1, 254, 255, 256, 510, 0, 765, 4097, 70000, 255 * 255, 255 * 255 + 1, 3, 255 * 3, 2, 300] * 2
+        pk = [random_bytes(rng, n) for n in lens]
+        infos = [(-1 if k % 3 == 1 else 1024 * (k + 1), k == len(pk) - 1) for k in range(len(pk))]
+        out.append((f"{ch}ch_{rate}_q{q}", v.write_ogg(setup, pk, infos, serialno=0x1234 + ch)))
+    # many small packets: pages that close on the 4096-byte / 4-packet rule and on 255 segments
+    setup = v.Setup(2, 44100, 0.5)
+    pk = [random_bytes(rng, n) for n in rng.integers(0, 600, 700)]
+    out.append(("small_packets", v.write_ogg(setup, pk, [(k * 512, k == len(pk) - 1) for k in range(len(pk))])))
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def directed():
     """(name, blob): the shapes the issue lists, valid files, but for the last"""
     import vorbis_aotuv_lancer_amd as v
     rng = np.random.default_rng(21)
-    rb = lambda n: rng.integers(0, 256, n, dtype=np.uint8).tobytes()  # noqa: E731
+    rb = functools.partial(random_bytes, rng)
     out = [("zero length", b""),
            ("headers alone", v.write_ogg(v.Setup(2, 44100, 0.5), [], []))]
     # 240 one-byte packets then 70000 bytes: 15 + 255 + 5 segments of it on three pages, the middle one of 255 segments
@@ -56,18 +70,17 @@ def directed():
     # a comment header of 70 KB: a header packet over several pages, and then the setup header and audio on one page
     out.append(("header packet spans pages", _paged(v, [rb(n) for n in (40, 41, 600)], False, comments=["k=" + "x" * 70000])))
     # the same without its last two pages: the 70000-byte packet is open at the end of the data and is dropped
-    from tests.test_ogg_demux_cpu import _pages
-    out.append(("unterminated packet at the end", b"".join(bytes(p) for p in _pages(out[2][1])[:-2])))
+    out.append(("unterminated packet at the end", b"".join(split_pages(out[2][1], as_bytes=True)[:-2])))
     out.append(("truncated", out[3][1][:-200]))                                                   # VBM_EOGG
     return out
 
 
 @functools.lru_cache(maxsize=None)
 def mixed():
-    """the five _streams files and every _corruptions variant of the second, good and bad interleaved"""
+    """the five streams files and every corruptions variant of the second, good and bad interleaved"""
     import vorbis_aotuv_lancer_amd as v
-    good = _streams(v)
-    bad = list(_corruptions(good[1][1]).items())
+    good = streams(v)
+    bad = list(corruptions(good[1][1]).items())
     out = []
     for k in range(max(len(good), len(bad))):
         if k < len(bad):
@@ -81,12 +94,11 @@ def mixed():
 def six_packet_file():
     """the file of test_demux_never_reads_past_n and the ends of its pages"""
     import vorbis_aotuv_lancer_amd as v
-    from tests.test_ogg_demux_cpu import _pages
     rng = np.random.default_rng(9)
-    pk = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (300, 255, 1, 600, 0, 2000)]
+    pk = [random_bytes(rng, n) for n in (300, 255, 1, 600, 0, 2000)]
     blob = v.write_ogg(v.Setup(1, 44100, 0.1), pk, [(100 * k, k == len(pk) - 1) for k in range(len(pk))])
     bounds, pos = set(), 0
-    for p in _pages(blob):
+    for p in split_pages(blob):
         pos += len(p)
         bounds.add(pos)
     return blob, bounds
@@ -112,109 +124,53 @@ def single(blob):
     return list(sizes[:3]), hdr.tobytes(), body.tobytes(), offs, gp, eos
 
 
-# ---- one interface over the host twin and the device calls ------------------------------------------------------------
+# ---- the host twin and the device calls (ogg_twin.Twin) ------------------------------------------------------------------
 
-def pack(blobs, first=0):
-    """`first` bytes of 0xEE, then the files back to back -> (uint8 array, offsets int64 [n + 1])"""
-    offsets = np.zeros(len(blobs) + 1, np.int64)
-    np.cumsum([len(b) for b in blobs], out=offsets[1:])
-    return np.frombuffer(b"\xee" * first + b"".join(blobs), np.uint8), offsets + first
-
-
-class Result:
-    pass
-
-
-class Batch:
-    """A demuxer and its buffers.  impl 'host': numpy arrays and vbm_host_*; 'device': torch tensors and the device calls
-    on the current stream."""
+class Batch(Twin):
+    """A demuxer and its buffers"""
 
     def __init__(self, impl, max_files, max_bytes):
-        self.impl, self.lib = impl, _lib()
-        self.h = C.c_void_p()
-        make = self.lib.vbm_host_ogg_demuxer_create if impl == "host" else self.lib.vbm_ogg_demuxer_create
-        assert make(C.byref(self.h), max_files, max_bytes) == 0
-        self.keep = None
-
-    def close(self):
-        if self.impl == "device":
-            import torch
-            torch.cuda.synchronize()
-        self.lib.vbm_ogg_demuxer_destroy(self.h)
-
-    # buffers: numpy on the host, torch on the device; ptr / back convert
-    def _new(self, n, dtype, fill=None):
-        if self.impl == "host":
-            return np.zeros(n, dtype) if fill is None else np.full(n, fill, dtype)
-        import torch
-        t = {np.uint8: torch.uint8, np.int64: torch.int64}[dtype]
-        return torch.zeros(n, dtype=t, device="cuda") if fill is None else torch.full((n,), fill, dtype=t, device="cuda")
-
-    def _ptr(self, a):
-        return a.ctypes.data if self.impl == "host" else a.data_ptr()
-
-    def _back(self, a):
-        return a if self.impl == "host" else a.cpu().numpy()
-
-    def _q(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        super().__init__(impl, "demuxer", max_files, max_bytes, status_name="demux_status")
 
     def scan_raw(self, nfiles, data_ptr, off_ptr, info_ptr, totals_ptr):
-        if self.impl == "host":
-            return self.lib.vbm_host_ogg_demux_scan(self.h, nfiles, data_ptr, off_ptr, info_ptr, totals_ptr)
-        return self.lib.vbm_ogg_demux_scan(self.h, nfiles, data_ptr, off_ptr, info_ptr, totals_ptr, self._q())
+        return self.call("demux_scan", nfiles, data_ptr, off_ptr, info_ptr, totals_ptr)
 
     def fill_raw(self, hdr, hcap, pay, pcap, offs, gp, eos, kcap):
-        if self.impl == "host":
-            return self.lib.vbm_host_ogg_demux_fill(self.h, hdr, hcap, pay, pcap, offs, gp, eos, kcap)
-        return self.lib.vbm_ogg_demux_fill(self.h, hdr, hcap, pay, pcap, offs, gp, eos, kcap, self._q())
-
-    def status(self):
-        st = C.c_int(-7)
-        assert self.lib.vbm_ogg_demux_status(self.h, C.byref(st), None if self.impl == "host" else self._q()) == 0
-        return st.value
+        return self.call("demux_fill", hdr, hcap, pay, pcap, offs, gp, eos, kcap)
 
     def scan(self, data, offsets):
         """data: uint8 numpy (or an address), offsets: int64 numpy [n + 1] -> (info, totals) as numpy"""
         n = len(offsets) - 1
         if isinstance(data, np.ndarray):
-            if self.impl == "device":
-                import torch
-                data = torch.from_numpy(data.copy()).cuda()
-            self.keep = data
-            data = self._ptr(data) if len(data) else None
-        info = self._new(n * _info_dtype().itemsize, np.uint8)
-        totals = self._new(3, np.int64, -1)
+            data = self.upload(data)
+        info = self.new(n * _info_dtype().itemsize, np.uint8)
+        totals = self.new(3, np.int64, -1)
         off = np.ascontiguousarray(offsets, np.int64)
-        rc = self.scan_raw(n, data, off.ctypes.data, self._ptr(info), self._ptr(totals))
+        rc = self.scan_raw(n, data, off.ctypes.data, self.ptr(info), self.ptr(totals))
         assert rc == 0, (rc, self.lib.vbm_last_error())
-        return self._back(info).view(_info_dtype()), self._back(totals)
+        return self.back(info).view(_info_dtype()), self.back(totals)
 
     def fill(self, totals, short=None, canary=8):
         """buffers of exactly the totals' sizes (short: 'packets' / 'payload' / 'headers' tells fill one less), `canary`
-        elements of 0xA5 behind each -> Result of numpy arrays without the canaries, .status, .touched (any buffer
-        differs from its initial 0xA5 pattern), .canaries_ok"""
+        blank elements behind each -> Result of numpy arrays without the canaries, .status, .touched (any buffer
+        differs from its blank pattern), .canaries_ok"""
         P, B, H = (int(x) for x in totals)
-        bufs = {"headers": self._new(H + canary, np.uint8, 0xA5), "payload": self._new(B + canary, np.uint8, 0xA5),
-                "offsets": self._new(P + 1 + canary, np.int64, -0x5A5A), "granulepos": self._new(P + canary, np.int64, -0x5A5A),
-                "eos": self._new(P + canary, np.uint8, 0xA5)}
+        sizes = {"headers": (H, np.uint8), "payload": (B, np.uint8), "offsets": (P + 1, np.int64),
+                 "granulepos": (P, np.int64), "eos": (P, np.uint8)}
+        bufs = {name: self.guarded(n, dtype, canary) for name, (n, dtype) in sizes.items()}
         caps = {"packets": P, "payload": B, "headers": H}
         if short:
             caps[short] -= 1
-        rc = self.fill_raw(self._ptr(bufs["headers"]), caps["headers"], self._ptr(bufs["payload"]), caps["payload"],
-                           self._ptr(bufs["offsets"]), self._ptr(bufs["granulepos"]), self._ptr(bufs["eos"]), caps["packets"])
+        rc = self.fill_raw(self.ptr(bufs["headers"]), caps["headers"], self.ptr(bufs["payload"]), caps["payload"],
+                           self.ptr(bufs["offsets"]), self.ptr(bufs["granulepos"]), self.ptr(bufs["eos"]), caps["packets"])
         assert rc == 0, (rc, self.lib.vbm_last_error())
         r = Result()
         r.status = self.status()
         r.touched, r.canaries_ok = False, True
-        sizes = {"headers": H, "payload": B, "offsets": P + 1, "granulepos": P, "eos": P}
         for name, buf in bufs.items():
-            a = self._back(buf)
-            blank = 0xA5 if a.dtype == np.uint8 else -0x5A5A
-            r.canaries_ok = r.canaries_ok and bool((a[sizes[name]:] == blank).all())
-            r.touched = r.touched or bool((a[:sizes[name]] != blank).any())
-            setattr(r, name, a[:sizes[name]])
+            a, touched, ok = self.unguard(buf, sizes[name][0])
+            r.touched, r.canaries_ok = r.touched or touched, r.canaries_ok and ok
+            setattr(r, name, a)
         return r
 
 

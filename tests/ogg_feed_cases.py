@@ -8,15 +8,12 @@ import functools
 import numpy as np
 
 from tests.ogg_demux_batch import ECAP, EINVAL, EOGG, directed, mixed, same, single, six_packet_file
+from tests.ogg_pages import pack, split_pages
+from tests.ogg_twin import Result, Twin, lib as _lib  # noqa: F401
 
 EBIG = -1003
 BIG = 1 << 17                     # packet / header capacity that holds every packet of the corpora
 CHUNKS = (26, 27, 28, 255, 256, 4096)
-
-
-def _lib():
-    from vorbis_aotuv_lancer_amd._lib import lib
-    return lib
 
 
 def _info_dtype():
@@ -24,97 +21,46 @@ def _info_dtype():
     return FEED_INFO
 
 
-class Result:
-    pass
-
-
-class Feed:
-    """A feed and its buffers.  impl 'host': numpy arrays and vbm_host_*; 'device': torch tensors and the device calls on
-    the current stream.  Every call is appended to .log."""
+class Feed(Twin):
+    """A feed and its buffers.  Every call is appended to .log."""
 
     def __init__(self, impl, max_streams, max_call_bytes, carry=65307, packet=BIG, header=BIG):
-        self.impl, self.lib = impl, _lib()
-        self.h = C.c_void_p()
-        make = self.lib.vbm_host_ogg_feed_create if impl == "host" else self.lib.vbm_ogg_feed_create
-        rc = make(C.byref(self.h), max_streams, max_call_bytes, carry, packet, header)
-        assert rc == 0, (rc, self.lib.vbm_last_error())
-        self.keep = None
+        super().__init__(impl, "feed", max_streams, max_call_bytes, carry, packet, header)
         self.log = []
 
-    def close(self):
-        if self.impl == "device":
-            import torch
-            torch.cuda.synchronize()
-        self.lib.vbm_ogg_feed_destroy(self.h)
-
-    def _new(self, n, dtype, fill=None):
-        if self.impl == "host":
-            return np.zeros(n, dtype) if fill is None else np.full(n, fill, dtype)
-        import torch
-        t = {np.uint8: torch.uint8, np.int64: torch.int64}[dtype]
-        return torch.zeros(n, dtype=t, device="cuda") if fill is None else torch.full((n,), fill, dtype=t, device="cuda")
-
-    def _ptr(self, a):
-        return a.ctypes.data if self.impl == "host" else a.data_ptr()
-
-    def _back(self, a):
-        return a if self.impl == "host" else a.cpu().numpy()
-
-    def _q(self):
-        if self.impl == "host":
-            return None
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def scan_raw(self, n, ids_ptr, data_ptr, off_ptr, end_ptr, info_ptr, totals_ptr):
-        if self.impl == "host":
-            return self.lib.vbm_host_ogg_feed_scan(self.h, n, ids_ptr, data_ptr, off_ptr, end_ptr, info_ptr, totals_ptr)
-        return self.lib.vbm_ogg_feed_scan(self.h, n, ids_ptr, data_ptr, off_ptr, end_ptr, info_ptr, totals_ptr, self._q())
+        return self.call("feed_scan", n, ids_ptr, data_ptr, off_ptr, end_ptr, info_ptr, totals_ptr)
 
     def fill_raw(self, pay, pcap, offs, gp, eos, kcap):
-        if self.impl == "host":
-            return self.lib.vbm_host_ogg_feed_fill(self.h, pay, pcap, offs, gp, eos, kcap)
-        return self.lib.vbm_ogg_feed_fill(self.h, pay, pcap, offs, gp, eos, kcap, self._q())
-
-    def status(self):
-        st = C.c_int(-7)
-        assert self.lib.vbm_ogg_feed_status(self.h, C.byref(st), self._q()) == 0
-        return st.value
+        return self.call("feed_fill", pay, pcap, offs, gp, eos, kcap)
 
     def scan(self, ids, chunks, end=None, first=0):
         """chunks back to back behind `first` bytes of 0xEE -> (info, totals) as numpy"""
         n = len(ids)
         ids = np.ascontiguousarray(ids, np.int32)
-        off = np.zeros(n + 1, np.int64)
-        np.cumsum([len(c) for c in chunks], out=off[1:])
-        off += first
-        raw = np.frombuffer(b"\xee" * first + b"".join(chunks), np.uint8)
-        if self.impl == "device":
-            import torch
-            raw = torch.from_numpy(raw.copy()).cuda() if len(raw) else torch.zeros(0, dtype=torch.uint8, device="cuda")
-        self.keep = raw
+        raw, off = pack(chunks, first)
         flags = None if end is None else np.ascontiguousarray(np.broadcast_to(np.asarray(end, np.uint8), (n,)))
-        meta = self._new(16 + n * _info_dtype().itemsize, np.uint8)
-        rc = self.scan_raw(n, ids.ctypes.data, self._ptr(raw) if len(raw) else None, off.ctypes.data,
-                           None if flags is None else flags.ctypes.data, self._ptr(meta) + 16, self._ptr(meta))
+        meta = self.new(16 + n * _info_dtype().itemsize, np.uint8)
+        rc = self.scan_raw(n, ids.ctypes.data, self.upload(raw), off.ctypes.data,
+                           None if flags is None else flags.ctypes.data, self.ptr(meta) + 16, self.ptr(meta))
         assert rc == 0, (rc, self.lib.vbm_last_error())
-        meta = self._back(meta)
+        meta = self.back(meta)
         info, totals = meta[16:].view(_info_dtype()).copy(), meta[:16].view(np.int64).copy()
         self.log.append(("scan", info.tobytes(), totals.tolist()))
         return info, totals
 
     def fill(self, totals, short=None, canary=8):
         """buffers of exactly the totals' sizes (short: 'packets' / 'payload' tells fill one less), `canary` elements of
-        0xA5 behind each -> Result of numpy arrays without the canaries, .status, .touched, .canaries_ok"""
+        blank bytes behind each -> Result of numpy arrays without the canaries, .status, .touched, .canaries_ok"""
         P, B = (int(x) for x in totals)
-        # one buffer of 0xA5 bytes for all four outputs (one fill, one copy back): offsets, granulepos, payload, eos
+        # one buffer of blank bytes for all four outputs (one fill, one copy back): offsets, granulepos, payload, eos
         sizes = {"offsets": (P + 1, 8), "granulepos": (P, 8), "payload": (B, 1), "eos": (P, 1)}
         at, where = 0, {}
         for name, (n, w) in sizes.items():
             where[name] = at
             at += (n + canary) * w
-        buf = self._new(at, np.uint8, 0xA5)
-        ptr = {name: self._ptr(buf) + where[name] for name in sizes}
+        buf = self.guarded(at, np.uint8, 0)
+        ptr = {name: self.ptr(buf) + where[name] for name in sizes}
         caps = {"packets": P, "payload": B}
         if short:
             caps[short] -= 1
@@ -123,12 +69,11 @@ class Feed:
         r = Result()
         r.status = self.status()
         r.touched, r.canaries_ok = False, True
-        back = self._back(buf)
+        back = self.back(buf)
         for name, (n, w) in sizes.items():
-            a = back[where[name]:where[name] + (n + canary) * w]
-            r.canaries_ok = r.canaries_ok and bool((a[n * w:] == 0xA5).all())
-            r.touched = r.touched or bool((a[:n * w] != 0xA5).any())
-            setattr(r, name, a[:n * w].view(np.int64 if w == 8 else np.uint8).copy())
+            a, touched, ok = self.unguard(back[where[name]:where[name] + (n + canary) * w], n * w)
+            r.touched, r.canaries_ok = r.touched or touched, r.canaries_ok and ok
+            setattr(r, name, a.view(np.int64 if w == 8 else np.uint8).copy())
         self.log.append(("fill", r.status, r.touched, r.canaries_ok, r.payload.tobytes(), r.offsets.tolist(),
                          r.granulepos.tolist(), r.eos.tolist()))
         return r
@@ -143,18 +88,18 @@ class Feed:
     def headers(self, slot):
         """-> (sizes [3], bytes) or None while they are not ready"""
         sizes = (C.c_int * 3)()
-        if self.lib.vbm_ogg_feed_headers(self.h, slot, None, 0, sizes, self._q()) != 0:
+        if self.lib.vbm_ogg_feed_headers(self.h, slot, None, 0, sizes, self.q()) != 0:
             return None
         n = sum(sizes)
         buf = np.zeros(n + 8, np.uint8)
-        assert self.lib.vbm_ogg_feed_headers(self.h, slot, buf.ctypes.data, n, sizes, self._q()) == 0
+        assert self.lib.vbm_ogg_feed_headers(self.h, slot, buf.ctypes.data, n, sizes, self.q()) == 0
         assert not buf[n:].any()
         self.log.append(("headers", slot, list(sizes), buf[:n].tobytes()))
         return list(sizes), buf[:n].tobytes()
 
     def reset(self, ids):
         ids = np.ascontiguousarray(ids, np.int32)
-        assert self.lib.vbm_ogg_feed_reset_streams(self.h, len(ids), ids.ctypes.data, self._q()) == 0
+        assert self.lib.vbm_ogg_feed_reset_streams(self.h, len(ids), ids.ctypes.data, self.q()) == 0
 
 
 def check_csr(info, totals, res):
@@ -382,8 +327,7 @@ def scenario_too_big(impl, which):
         bad, caps, cs = d["header packet spans pages"], dict(header=65536), 4096
     else:                                                       # a page of 255 segments cut in its middle
         bad, caps = d["packet over three pages"], dict(carry=4096)
-        from tests.test_ogg_demux_cpu import _pages
-        pages = _pages(bad)
+        pages = split_pages(bad)
         big = next(i for i, p in enumerate(pages) if p[26] == 255)
         cs = sum(len(p) for p in pages[:big]) + len(pages[big]) // 2
     feed = Feed(impl, 3, 3 * max(cs, len(good)), **caps)
@@ -479,14 +423,14 @@ def check_einval(impl):
     try:
         i32 = lambda *a: np.array(a, np.int32)                  # noqa: E731
         i64 = lambda *a: np.array(a, np.int64)                  # noqa: E731
-        data = feed._new(2000, np.uint8)
-        meta = feed._new(16 + 4 * _info_dtype().itemsize, np.uint8)
-        d, info, totals = feed._ptr(data), feed._ptr(meta) + 16, feed._ptr(meta)
+        data = feed.new(2000, np.uint8)
+        meta = feed.new(16 + 4 * _info_dtype().itemsize, np.uint8)
+        d, info, totals = feed.ptr(data), feed.ptr(meta) + 16, feed.ptr(meta)
 
         def scan(ids, off, data=d, info=info, totals=totals, n=None):
             return feed.scan_raw(len(ids) if n is None else n, ids.ctypes.data, data, off.ctypes.data, None, info, totals)
 
-        assert feed.fill_raw(None, 0, feed._ptr(feed._new(1, np.int64)), None, None, 0) == EINVAL   # fill without a scan
+        assert feed.fill_raw(None, 0, feed.ptr(feed.new(1, np.int64)), None, None, 0) == EINVAL   # fill without a scan
         assert scan(i32(1, 1), i64(0, 10, 20)) == EINVAL        # listed twice
         assert scan(i32(0, 4), i64(0, 10, 20)) == EINVAL        # out of range
         assert scan(i32(0, -1), i64(0, 10, 20)) == EINVAL
@@ -500,22 +444,22 @@ def check_einval(impl):
         assert scan(i32(0, 1), i64(0, 10, 20), totals=None) == EINVAL
         assert feed.scan_raw(2, None, d, i64(0, 10, 20).ctypes.data, None, info, totals) == EINVAL
         assert feed.scan_raw(2, i32(0, 1).ctypes.data, d, None, None, info, totals) == EINVAL
-        assert feed.lib.vbm_ogg_feed_reset_streams(feed.h, 2, i32(2, 2).ctypes.data, feed._q()) == EINVAL
-        assert feed.lib.vbm_ogg_feed_reset_streams(feed.h, 1, i32(9).ctypes.data, feed._q()) == EINVAL
+        assert feed.lib.vbm_ogg_feed_reset_streams(feed.h, 2, i32(2, 2).ctypes.data, feed.q()) == EINVAL
+        assert feed.lib.vbm_ogg_feed_reset_streams(feed.h, 1, i32(9).ctypes.data, feed.q()) == EINVAL
         sizes = (C.c_int * 3)()
-        assert feed.lib.vbm_ogg_feed_headers(feed.h, 0, None, 0, sizes, feed._q()) == EINVAL        # not ready
-        assert feed.lib.vbm_ogg_feed_headers(feed.h, 4, None, 0, sizes, feed._q()) == EINVAL
+        assert feed.lib.vbm_ogg_feed_headers(feed.h, 0, None, 0, sizes, feed.q()) == EINVAL        # not ready
+        assert feed.lib.vbm_ogg_feed_headers(feed.h, 4, None, 0, sizes, feed.q()) == EINVAL
         # the other kind of feed
         wrong = feed.lib.vbm_ogg_feed_scan if impl == "host" else feed.lib.vbm_host_ogg_feed_scan
         args = (feed.h, 1, i32(0).ctypes.data, d, i64(0, 10).ctypes.data, None, info, totals)
         assert wrong(*args, None) == EINVAL if impl == "host" else wrong(*args) == EINVAL
         # nothing was enqueued or changed: the feed works, and the ids of a refused call are not remembered
         info_, totals_ = feed.scan([1, 0], [blob[:500], blob[:400]])
-        out = feed._new(8, np.int64)
-        assert feed.fill_raw(None, -1, feed._ptr(out), None, None, 0) == EINVAL
+        out = feed.new(8, np.int64)
+        assert feed.fill_raw(None, -1, feed.ptr(out), None, None, 0) == EINVAL
         assert feed.fill_raw(None, 0, None, None, None, 0) == EINVAL
-        assert feed.fill_raw(None, 1, feed._ptr(out), None, None, 0) == EINVAL
-        assert feed.fill_raw(None, 0, feed._ptr(out), None, None, 1) == EINVAL
+        assert feed.fill_raw(None, 1, feed.ptr(out), None, None, 0) == EINVAL
+        assert feed.fill_raw(None, 0, feed.ptr(out), None, None, 1) == EINVAL
         res = feed.fill(totals_)
         assert res.status == 0
         st = Streams()
@@ -525,10 +469,9 @@ def check_einval(impl):
         assert same(st.view(feed, 0), single(blob)) and same(st.view(feed, 1), single(blob))
         sz, _ = feed.headers(0)
         assert feed.lib.vbm_ogg_feed_headers(feed.h, 0, np.zeros(sum(sz), np.uint8).ctypes.data, sum(sz) - 1, sizes,
-                                             feed._q()) == EINVAL
+                                             feed.q()) == EINVAL
     finally:
         feed.close()
     for bad in ((0, 10, 1, 1, 1), (1, -1, 1, 1, 1), (1, 10, 0, 1, 1), (1, 10, 65308, 1, 1), (1, 10, 1, 0, 1), (1, 10, 1, 1, 0)):
         h = C.c_void_p()
-        make = feed.lib.vbm_host_ogg_feed_create if impl == "host" else feed.lib.vbm_ogg_feed_create
-        assert make(C.byref(h), *bad) == EINVAL, bad
+        assert feed.fn("feed_create")(C.byref(h), *bad) == EINVAL, bad

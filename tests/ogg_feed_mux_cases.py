@@ -18,9 +18,10 @@ import numpy as np
 
 from tests import ogg_chain_cases as CH
 from tests import ogg_feed_resync_cases as RS
+from tests import ogg_pages as PG
 from tests import ogg_resync_model as M
 from tests import ogg_select_cases as SEL
-from tests.test_ogg_demux_cpu import _corruptions, _pages, _recrc  # noqa: F401
+from tests.ogg_pages import corruptions, random_bytes
 
 EOGG, EBIG, EINVAL = -1002, -1003, -131
 MUX, RESYNC = 4, 1
@@ -30,32 +31,19 @@ BIG = RS.BIG
 # ---- pages of a multiplexed file by the rule, and the cut mapping -----------------------------------------------------
 
 def walk(data):
-    """-> [(pos, len, kept, head)] of every page of the undamaged file `data`, by the rule of csrc/ogg_select.h; checked
-    against ogg_select_cases.model"""
+    """-> [(pos, len, kept, head)] of every page of the undamaged file `data`, by the rule of csrc/ogg_select.h"""
     return list(_walk(bytes(data)))
 
 
 @functools.lru_cache(maxsize=None)
 def _walk(data):
-    out, pos, in_heads, chosen, serial = [], 0, True, False, 0
-    while len(data) - pos >= 27 and data[pos:pos + 4] == b"OggS":
-        nseg = data[pos + 26]
-        body = sum(data[pos + 27:pos + 27 + nseg])
-        n = 27 + nseg + body
-        if len(data) - pos < n:
-            break
-        s = struct.unpack_from("<I", data, pos + 14)[0]
-        head = bool(data[pos + 5] & 2) or pos == 0
-        if head and not in_heads:
-            in_heads, chosen = True, False
-        if not head:
-            in_heads = False
-        if head and not chosen and data[pos + 27 + nseg:pos + 27 + nseg + 7] == SEL.MARK:
-            chosen, serial = True, s
-        out.append((pos, n, chosen and s == serial, head))
-        pos += n
+    out, pos, state = [], 0, PG.GROUP_START
+    for p in PG.parse(data, 0, len(data)):
+        head = bool(p.flags & 2) or p.pos == 0
+        state, _ = PG.group_step(state, head, p.serial, PG.body7(data, p))
+        out.append((p.pos, p.size, state[1] and p.serial == state[2], head))
+        pos = p.pos + p.size
     assert pos == len(data), "the equivalence corpus holds whole pages only"
-    assert b"".join(data[p:p + n] for p, n, k, _ in out if k) == SEL.model(data)[0]
     return tuple(out)
 
 
@@ -94,19 +82,16 @@ def random_cuts(data, seed, k=6):
 
 # ---- corpus -------------------------------------------------------------------------------------------------------------
 
-def _rb(rng, n):
-    return rng.integers(0, 256, int(n), dtype=np.uint8).tobytes()
-
-
 @functools.lru_cache(maxsize=None)
 def tiny():
     """-> (M, V): a Vorbis-like stream of a few hundred bytes (a head page with the mark, two more header packets, audio
     packets of tens of bytes, one continued over a page) between the pages of two foreign streams, Skeleton-like first"""
     rng = np.random.default_rng(41)
-    pk = [SEL.MARK + _rb(rng, 23), _rb(rng, 11), _rb(rng, 14)] + [_rb(rng, n) for n in (20, 0, 31, 255, 9, 300, 17)]
-    v = SEL.lay(pk, 500, max_segs=2)
-    sk = SEL.lay([b"fishead\0" + _rb(rng, 20), _rb(rng, 12), _rb(rng, 40)], 600, max_segs=1)
-    th = SEL.lay([b"\x80theora" + _rb(rng, 9), _rb(rng, 260), b""], 601, max_segs=1)
+    rb = functools.partial(random_bytes, rng)
+    pk = [PG.MARK + rb(23), rb(11), rb(14)] + [rb(n) for n in (20, 0, 31, 255, 9, 300, 17)]
+    v = PG.lay(pk, 500, max_segs=2)
+    sk = PG.lay([b"fishead\0" + rb(20), rb(12), rb(40)], 600, max_segs=1)
+    th = PG.lay([b"\x80theora" + rb(9), rb(260), b""], 601, max_segs=1)
     other = [p for pair in zip(sk[1:], th[1:]) for p in pair]   # behind the heads: a Vorbis page, a foreign one, and so on
     assert len(other) == 4 and len(v) >= 7
     rest = [p for pair in zip(v[1:], other) for p in pair] + v[1 + len(other):]
@@ -123,10 +108,10 @@ def many_segments():
     v = SEL.vorbis_pages(4)
     h = v[0]
     body = h[27 + h[26]:]
-    assert h[26] == 1 and body[:7] == SEL.MARK
-    head = SEL.page(struct.unpack_from("<I", h, 14)[0], 0, [0] * 250 + [len(body)], body, flags=2)
+    assert h[26] == 1 and body[:7] == PG.MARK
+    head = PG.page(struct.unpack_from("<I", h, 14)[0], 0, [0] * 250 + [len(body)], body, flags=2)
     sk = SEL.foreign("skeleton", 93, 51, sizes=(30, 200))
-    return SEL._cat([sk[0], head] + SEL.interleave([sk[1:], v[1:]], 52))
+    return SEL._cat([sk[0], head] + PG.interleave([sk[1:], v[1:]], 52))
 
 
 @functools.lru_cache(maxsize=None)
@@ -162,126 +147,33 @@ def mid_join():
 # ---- the resync model with the group rule --------------------------------------------------------------------------------
 
 class MuxSlot(M.Slot):
-    """ogg_resync_model.Slot with the group rule between its rules 1 and 2: the loop of Slot.call, and at `# mux` the
-    statements this mode adds.  tracked: the serial number the product's slot tracks (none, 0, for a link that went bad
-    at its first page)."""
+    """ogg_resync_model.Slot with the group rule between its rules 1 and 2.  The rule runs on a copy of its state, which
+    is committed once the page goes by: a page the call stops at is judged again by the next.  tracked: the serial
+    number the product's slot tracks (none, 0, for a link that went bad at its first page)."""
 
     def __init__(self):
         super().__init__()
-        self.past_heads = self.chosen = self.met = False
+        self.in_heads, self.chosen, self.tracked = PG.GROUP_START
+        self.met = False              # a page has gone by: until then any page is a head page
+        self.judged = None            # (in_heads, chosen) behind the page in hand
+
+    def foreign(self, page, nseg, bos, serial):
+        state, _ = PG.group_step((self.in_heads, self.chosen, self.tracked), bos or not self.met, serial,
+                                 page[27 + nseg:27 + nseg + 7])
+        self.judged = state[:2]
+        if state[1] and serial == state[2]:
+            return False                                   # the page is kept: rule 2 judges it
+        self.passed()
+        return True
+
+    def passed(self):
+        (self.in_heads, self.chosen), self.met = self.judged, True
+
+    def link_started(self):
         self.tracked = 0
 
-    def call(self, chunk, end=False):
-        out, skipped, ignored, left = [], 0, 0, 0
-        started = stopped = took = False
-        taken = 0
-        if not self.done:
-            run, carried, pos = self.tail + bytes(chunk), len(self.tail), 0
-            while len(run) - pos >= 4:
-                p = run.find(b"OggS", pos)
-                if p < 0:
-                    skipped += len(run) - 3 - pos
-                    pos = len(run) - 3
-                    break
-                skipped += p - pos
-                pos = p
-                have = len(run) - pos
-                if have >= 5 and run[pos + 4] != 0:
-                    skipped, pos = skipped + 1, pos + 1
-                    continue
-                if have < 27 or have < 27 + run[pos + 26]:
-                    break
-                nseg = run[pos + 26]
-                lacing = list(run[pos + 27:pos + 27 + nseg])
-                size = 27 + nseg + sum(lacing)
-                if have < size:
-                    break
-                page = run[pos:pos + size]
-                flags, granule, serial, seq, crc = struct.unpack_from("<BqIII", page, 5)
-                if M.page_crc(page) != crc:
-                    skipped, pos = skipped + 1, pos + 1
-                    continue
-                bos, cont = bool(flags & 2), bool(flags & 1)
-                # mux: the group rule, on a copy of its state: a page the call stops at is judged again by the next
-                past, chosen, tracked = self.past_heads, self.chosen, self.tracked
-                head = bos or not self.met
-                if head and past:
-                    past, chosen = False, False
-                if not head:
-                    past = True
-                if head and not chosen and page[27 + nseg:27 + nseg + 7] == SEL.MARK:
-                    chosen, tracked = True, serial
-                if not (chosen and serial == tracked):
-                    self.past_heads, self.chosen, self.met = past, chosen, True
-                    ignored, pos = ignored + 1, pos + size
-                    continue
-                # (end of the group rule: the page is kept)
-                if not bos and (not self.links or self.bad or self.eos or serial != self.serial):
-                    self.past_heads, self.chosen, self.met = past, chosen, True            # mux
-                    ignored, pos = ignored + 1, pos + size
-                    continue
-                disc = cont if bos else (seq != self.seq or cont != (self.open is not None))
-                if (bos or disc) and took or taken == len(chunk) // 27 + 1:
-                    stopped = True
-                    break
-                took, pos = True, pos + size
-                self.past_heads, self.chosen, self.met = past, chosen, True                # mux
-                if bos:
-                    self.links.append(M.Link())
-                    self.serial, self.open, self.npk = serial, None, 0
-                    self.bad = self.eos = False
-                    self.gap = len(self.links) > 1
-                    started = True
-                    self.tracked = 0                                                       # mux
-                if disc:
-                    if self.npk < 3:
-                        self.bad = True
-                        continue
-                    self.open, self.gap = None, True
-                self.tracked = serial                                                      # mux
-                body = page[27 + nseg:]
-                if disc and cont:
-                    while lacing:
-                        lv = lacing.pop(0)
-                        body = body[lv:]
-                        if lv < 255:
-                            break
-                self.seq = (seq + 1) & 0xffffffff
-                taken += 1
-                completed = []
-                for lv in lacing:
-                    if self.open is None:
-                        self.open = bytearray()
-                    self.open += body[:lv]
-                    body = body[lv:]
-                    if lv < 255:
-                        completed.append(bytes(self.open))
-                        self.open = None
-                link = self.links[-1]
-                for k, pk in enumerate(completed):
-                    last = k == len(completed) - 1
-                    if self.npk < 3:
-                        link.headers.append(pk)
-                    else:
-                        rec = (pk, granule if last else -1, int(bool(flags & 4) and last), int(self.gap))
-                        self.gap = False
-                        out.append(rec)
-                        link.packets.append(rec[0]), link.granulepos.append(rec[1])
-                        link.eos.append(rec[2]), link.gap.append(rec[3])
-                    self.npk += 1
-                if flags & 4:
-                    self.eos = True
-            if stopped:
-                self.tail = run[pos:carried] if pos < carried else b""
-                left = len(run) - max(pos, carried)
-            else:
-                self.tail = run[pos:]
-            if end and not stopped:
-                skipped += len(self.tail)
-                self.tail, self.open, self.done = b"", None, True
-        return {"packets": out, "link": max(len(self.links) - 1, 0), "link_started": int(started), "link_bad": int(self.bad),
-                "gaps": sum(r[3] for r in out), "skipped": skipped, "ignored": ignored, "left": left,
-                "headers_ready": int(bool(self.links) and self.npk >= 3 and not self.bad)}
+    def page_taken(self, serial):
+        self.tracked = serial
 
 
 def model_run(data, cuts=(), end=True):
@@ -299,16 +191,7 @@ def resync_run(impl, blobs, cuts, multiplexed=True, end=True, **kw):
 
 def check_resync_model(run, blobs, cuts, end=True):
     """every call of every slot equals MuxSlot's, and so do the headers of every link"""
-    for s, (b, c) in enumerate(zip(blobs, cuts)):
-        slot, calls = model_run(b, c, end)
-        assert len(run.calls[s]) == len(calls), (s, len(run.calls[s]), len(calls))
-        for k, (got, want) in enumerate(zip(run.calls[s], calls)):
-            assert got == want, (s, k, {x: (got[x], want[x]) for x in got if got[x] != want[x] and x != "packets"},
-                                 len(got["packets"]), len(want["packets"]))
-        want_h = {k: l.headers[:3] for k, l in enumerate(slot.links) if len(l.headers) >= 3}
-        assert run.headers[s] == want_h, (s, sorted(run.headers[s]), sorted(want_h))
-        assert run.status[s] == 0
-    return run
+    return RS.check_against_model(run, blobs, cuts, end, model=MuxSlot)
 
 
 def check_resync_equivalence(impl, blobs, cuts, **kw):
@@ -396,10 +279,10 @@ def check_strict_equivalence(impl, blobs, cuts, **kw):
 
 
 def damaged_files():
-    """the _corruptions variants of three small multiplexed files"""
+    """the corruptions variants of three small multiplexed files"""
     out = {}
     for src in ("skeleton first", "three groups", "two vorbis streams behind a foreign one"):
-        for name, bad in _corruptions(corpus()[src]).items():
+        for name, bad in corruptions(corpus()[src]).items():
             out[f"{src}: {name}"] = bad
     return out
 

@@ -8,7 +8,7 @@ import numpy as np
 
 from tests import ogg_resync_model as M
 from tests.ogg_demux_batch import directed, mixed, single
-from tests.test_ogg_demux_cpu import _pages
+from tests.ogg_pages import pack, random_bytes, split_pages
 
 BIG = 1 << 17
 CHUNKS = (26, 27, 28, 255, 256, 4096)
@@ -16,7 +16,7 @@ EBIG, EINVAL, ECAP = -1003, -131, 1
 
 
 def pages(blob):
-    return [bytes(p) for p in _pages(blob)]
+    return split_pages(blob, as_bytes=True)
 
 
 def join(ps):
@@ -32,7 +32,7 @@ def cuts_every(n, step):
 def assert_no_stray_capture(blob):
     """no page body of the input holds "OggS" away from a page start: damage tests rely on it"""
     at, starts = 0, set()
-    for p in _pages(blob):
+    for p in split_pages(blob):
         starts.add(at)
         at += len(p)
     k = blob.find(b"OggS")
@@ -68,7 +68,7 @@ def _mux(packets, serialno, flush):
 def paged_six():
     """the six packets of six_packet_file, one per page: six audio pages"""
     rng = np.random.default_rng(9)
-    pk = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (300, 255, 1, 600, 0, 2000)]
+    pk = [random_bytes(rng, n) for n in (300, 255, 1, 600, 0, 2000)]
     blob = _mux(pk, 31, lambda k: True)
     assert len(audio_pages(blob)) == 6
     assert_no_stray_capture(blob)
@@ -82,7 +82,7 @@ def long_file():
     rng = np.random.default_rng(5)
     sizes = [int(x) for x in rng.integers(1, 700, 60)]
     sizes[7], sizes[8], sizes[20], sizes[21] = 70000, 70000, 255 * 3, 0
-    pk = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in sizes]
+    pk = [random_bytes(rng, n) for n in sizes]
     blob = _mux(pk, 4242, lambda k: k % 3 == 2 and k not in (7, 8))
     assert 20 <= len(pages(blob)) <= 60
     assert_no_stray_capture(blob)
@@ -92,7 +92,7 @@ def long_file():
 def audio_pages(blob):
     """the numbers of the pages on which no header packet lies"""
     done, out = 0, []
-    for k, p in enumerate(_pages(blob)):
+    for k, p in enumerate(split_pages(blob)):
         if done >= 3:
             out.append(k)
         done += sum(1 for lv in p[27:27 + p[26]] if lv < 255)
@@ -102,7 +102,7 @@ def audio_pages(blob):
 def packets_by_page(blob):
     """-> [(first page, last page, bytes, granulepos, eos)] of every audio packet, by a lacing walk of its own"""
     out, open_, first, done = [], None, 0, 0
-    for k, p in enumerate(_pages(blob)):
+    for k, p in enumerate(split_pages(blob)):
         nseg = p[26]
         body, ends = bytes(p[27 + nseg:]), [i for i in range(nseg) if p[27 + i] < 255]
         for i in range(nseg):
@@ -153,8 +153,8 @@ def false_capture_file():
     import vorbis_aotuv_lancer_amd as v
     rng = np.random.default_rng(77)
     fake = b"OggS\0\0" + bytes(20) + b"\x02\x10\x08" + bytes(24)              # claims 27 + 2 + 24 bytes
-    pk = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (200, 300)] + [b"ab" + fake + b"cd"] + \
-         [rng.integers(0, 256, 150, dtype=np.uint8).tobytes()]
+    pk = [random_bytes(rng, n) for n in (200, 300)] + [b"ab" + fake + b"cd"] + \
+         [random_bytes(rng, 150)]
     os_, out = v.OggStream(99), []
     for h in v.header_packets(v.Setup(1, 44100, 0.1)):
         os_.packetin(h, 0)
@@ -177,7 +177,7 @@ def overclaim_file():
     CRC fails and the walk meets more whole pages in the tail than a small chunk has page records for.
     -> (the damaged bytes, the packets that must come out)"""
     rng = np.random.default_rng(12)
-    blob = _mux([rng.integers(0, 256, 50, dtype=np.uint8).tobytes() for _ in range(45)], 808, lambda k: True)
+    blob = _mux([random_bytes(rng, 50) for _ in range(45)], 808, lambda k: True)
     ps, ap = pages(blob), audio_pages(blob)
     assert len(ap) == 45 and all(len(ps[k]) == 78 for k in ap)
     assert_no_stray_capture(blob)
@@ -248,8 +248,7 @@ class Run:
             self.feed.close()
 
     def push(self, who, parts, flags, first=0):
-        raw = np.frombuffer(b"\xee" * first + b"".join(parts), np.uint8)
-        off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64) + first
+        raw, off = pack(parts, first)
         if not self.feed.host:
             import torch
             raw = torch.from_numpy(raw.copy()).cuda()
@@ -279,10 +278,10 @@ class Run:
                     self.headers[s][rec["link"]] = self.feed.headers(int(sid))
 
 
-def check_against_model(run, blobs, cuts, end=True):
+def check_against_model(run, blobs, cuts, end=True, model=M.Slot):
     """every call of every slot equals the model's, and so do the headers of every link that completed them"""
     for s, (b, c) in enumerate(zip(blobs, cuts)):
-        slot, calls = M.run(b, c, end)
+        slot, calls = M.run(b, c, end, slot=model())
         assert len(run.calls[s]) == len(calls), (s, len(run.calls[s]), len(calls))
         for k, (got, want) in enumerate(zip(run.calls[s], calls)):
             assert got == want, (s, k, {x: (got[x], want[x]) for x in got if got[x] != want[x] and x != "packets"},

@@ -1,33 +1,10 @@
 """The six rules of the resync feed (include/vorbis_mi355x.h, "Resync mode") restated byte-serially in Python: a slot
-keeps bytes, Python lists and bytearrays, not the product's counts and page records, and the CRC is a plain table loop.
-Nothing here is shared with the product.  Slot.call() is one push of one slot; run() drives a whole byte string through
-a list of cut points and pushes what a call left again, as OggFeed.push_all does."""
-import functools
+keeps bytes, Python lists and bytearrays, not the product's counts and page records, and the CRC is a plain table loop
+(ogg_pages.page_crc).  Nothing here is shared with the product.  Slot.call() is one push of one slot; run() drives a
+whole byte string through a list of cut points and pushes what a call left again, as OggFeed.push_all does."""
 import struct
 
-
-def _table():
-    t = []
-    for i in range(256):
-        r = i << 24
-        for _ in range(8):
-            r = ((r << 1) ^ 0x04c11db7) & 0xffffffff if r & 0x80000000 else (r << 1) & 0xffffffff
-        t.append(r)
-    return t
-
-
-_T = _table()
-
-
-@functools.lru_cache(maxsize=4096)
-def page_crc(page):
-    """the checksum of a page, its own field counted as zero"""
-    r = 0
-    for i, b in enumerate(page):
-        if 22 <= i < 26:
-            b = 0
-        r = ((r << 8) & 0xffffffff) ^ _T[(r >> 24) ^ b]
-    return r
+from tests.ogg_pages import page_crc
 
 
 class Link:
@@ -43,6 +20,22 @@ class Slot:
         self.open = None              # the bytes of the open packet; None: no packet is open
         self.npk = 0                  # packets the current link has completed
         self.bad = self.eos = self.gap = self.done = False
+
+    # What a mode with a rule of its own between rule 1 (a whole page with a good CRC) and rule 2 (whose page) overrides;
+    # ogg_feed_mux_cases.MuxSlot does.  A page the call stops at reaches none of the last three: the next call judges
+    # it again.
+    def foreign(self, page, nseg, bos, serial):
+        """-> the page is not for rule 2 to judge: it is ignored"""
+        return False
+
+    def passed(self):
+        """the page went by, ignored by rule 2 or taken"""
+
+    def link_started(self):
+        """the page taken starts a link"""
+
+    def page_taken(self, serial):
+        """the page taken goes on to its packets"""
 
     def call(self, chunk, end=False):
         """-> {packets: [(bytes, granulepos, eos, gap)], link, link_started, link_bad, gaps, skipped, ignored, left,
@@ -77,7 +70,11 @@ class Slot:
                     skipped, pos = skipped + 1, pos + 1
                     continue
                 bos, cont = bool(flags & 2), bool(flags & 1)
+                if self.foreign(page, nseg, bos, serial):
+                    ignored, pos = ignored + 1, pos + size
+                    continue
                 if not bos and (not self.links or self.bad or self.eos or serial != self.serial):
+                    self.passed()
                     ignored, pos = ignored + 1, pos + size
                     continue
                 disc = cont if bos else (seq != self.seq or cont != (self.open is not None))
@@ -85,17 +82,20 @@ class Slot:
                     stopped = True
                     break
                 took, pos = True, pos + size
+                self.passed()
                 if bos:
                     self.links.append(Link())
                     self.serial, self.open, self.npk = serial, None, 0
                     self.bad = self.eos = False
                     self.gap = len(self.links) > 1
                     started = True
+                    self.link_started()
                 if disc:
                     if self.npk < 3:
                         self.bad = True
                         continue
                     self.open, self.gap = None, True
+                self.page_taken(serial)
                 body = page[27 + nseg:]
                 if disc and cont:                    # the leading segments belong to no packet
                     while lacing:

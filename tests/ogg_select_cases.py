@@ -2,7 +2,6 @@
 byte-serial page walker in Python (the first yardstick; the second is vbm_ogg_demux on the Vorbis-only file a
 multiplexed one was built from, ogg_demux_batch.single), and the C calls of the selection's host twin and device form
 over one interface."""
-import ctypes as C
 import functools
 import struct
 
@@ -10,10 +9,11 @@ import numpy as np
 
 from tests import ogg_chain_cases as CH
 from tests import ogg_demux_batch as B
+from tests import ogg_pages as PG
 from tests.ogg_demux_batch import ECAP, EINVAL, EOGG  # noqa: F401
-from tests.test_ogg_demux_cpu import _corruptions, _pages, _recrc
+from tests.ogg_pages import MARK, corruptions, head_page, interleave, lay, random_bytes, recrc, sized_page
+from tests.ogg_twin import Result, Twin
 
-MARK = b"\x01vorbis"
 INFO_FIELDS = ("kept_bytes", "kept_pages", "foreign_pages", "streams", "foreign_streams", "first_serial")
 
 
@@ -32,38 +32,26 @@ def model(data):
 @functools.lru_cache(maxsize=None)
 def _model(data):
     end, pos = len(data), 0
-    in_heads, chosen, serial = True, False, 0
+    state = PG.GROUP_START
     info = dict.fromkeys(INFO_FIELDS, 0)
     kept = []                                             # (pos, len) of every kept piece, in order
-    while end - pos >= 27:
-        h = data[pos:pos + 27]
-        if h[:4] != b"OggS" or h[4] != 0:
-            break
-        nseg = h[26]
-        if end - pos - 27 < nseg:
-            break
-        body = sum(data[pos + 27:pos + 27 + nseg])
-        if end - pos - 27 - nseg < body:
-            break
-        s = struct.unpack_from("<I", h, 14)[0]
-        head = bool(h[5] & 2) or pos == 0
-        if head and not in_heads:
-            in_heads, chosen = True, False
-        if not head:
-            in_heads = False
-        if head and not chosen and body >= 7 and data[pos + 27 + nseg:pos + 27 + nseg + 7] == MARK:
-            chosen, serial = True, s
+    for p in PG.parse(data, 0, end):
+        s = p.serial
+        head = bool(p.flags & 2) or pos == 0
+        state, picked = PG.group_step(state, head, s, PG.body7(data, p))
+        if picked:
             if info["streams"] == 0:
                 info["first_serial"] = s
             info["streams"] += 1
-        n = 27 + nseg + body
-        if chosen and s == serial:
+        n = p.size
+        if state[1] and s == state[2]:
             kept.append((pos, n))
             info["kept_pages"] += 1
         else:
             info["foreign_pages"] += 1
             info["foreign_streams"] += head
         pos += n
+    chosen = state[1]
     if chosen and end > pos:
         kept.append((pos, end - pos))
     runs, dst = [], 0
@@ -89,69 +77,21 @@ def expected(blobs):
     return b"".join(outs), off, infos
 
 
-# ---- pages -------------------------------------------------------------------------------------------------------------
-
-def page(serial, seq, lacing, body, flags=0, granule=0):
-    assert len(lacing) <= 255 and sum(lacing) == len(body)
-    p = bytearray(b"OggS\0" + bytes([flags]) + struct.pack("<qIII", granule, serial, seq, 0) + bytes([len(lacing)])
-                  + bytes(lacing) + body)
-    return bytes(_recrc(p))
-
-
-def lay(packets, serial, max_segs=255, bos=True, eos=True, first_alone=True):
-    """packets -> the pages of one logical stream: at most max_segs segments per page, the first packet on a page of
-    its own, continuation flags where a page begins inside a packet"""
-    segs = []                                             # (the segment's bytes, it ends its packet, the packet)
-    for k, pk in enumerate(packets):
-        n = len(pk) // 255 + 1
-        for i in range(n):
-            segs.append((pk[255 * i:255 * i + 255], i == n - 1, k))
-    pages, at, seq, open_packet, done = [], 0, 0, False, 0
-    while at < len(segs):
-        take = max_segs
-        if first_alone and seq == 0:
-            take = min(take, len(packets[0]) // 255 + 1)
-        part = segs[at:at + take]
-        at += len(part)
-        flags = (1 if open_packet else 0) | (2 if bos and seq == 0 else 0) | (4 if eos and at == len(segs) else 0)
-        ends = sum(1 for s in part if s[1])
-        done += ends
-        pages.append(page(serial, seq, [len(s[0]) for s in part], b"".join(s[0] for s in part), flags,
-                          64 * done if ends else -1))
-        open_packet = not part[-1][1]
-        seq += 1
-    return pages
-
-
-def interleave(streams, seed):
-    """page lists of one group -> one page list: every stream's first page first, in the order given, then the rest
-    merged in a seeded order that keeps each stream's own"""
-    rng = np.random.default_rng(seed)
-    out = [s[0] for s in streams]
-    rest = [list(s[1:]) for s in streams]
-    while any(rest):
-        k = int(rng.choice([i for i, r in enumerate(rest) if r]))
-        out.append(rest[k].pop(0))
-    return out
-
-
-def _rb(rng, n):
-    return rng.integers(0, 256, int(n), dtype=np.uint8).tobytes()
-
+# ---- streams of pages --------------------------------------------------------------------------------------------------
 
 def foreign(kind, serial, seed, sizes=(40, 300, 9, 700), max_segs=3):
     """a stream that is not Vorbis: random packets behind a plausible first one"""
     rng = np.random.default_rng(seed)
-    first = {"skeleton": b"fishead\0" + _rb(rng, 56), "theora": b"\x80theora" + _rb(rng, 35),
-             "opus": b"OpusHead" + _rb(rng, 11)}[kind]
-    rest = [(b"fisbone\0" if kind == "skeleton" else b"") + _rb(rng, n) for n in sizes]
+    first = {"skeleton": b"fishead\0" + random_bytes(rng, 56), "theora": b"\x80theora" + random_bytes(rng, 35),
+             "opus": b"OpusHead" + random_bytes(rng, 11)}[kind]
+    rest = [(b"fisbone\0" if kind == "skeleton" else b"") + random_bytes(rng, n) for n in sizes]
     return lay([first] + rest, serial, max_segs)
 
 
 def vorbis_pages(k, serial=None):
     """small link k of ogg_chain_cases as pages, under its own serial number or another"""
     blob = CH.small_links(8)[k]
-    return [bytes(p) for p in _pages(blob if serial is None else CH.reserial(blob, serial))]
+    return PG.split_pages(blob if serial is None else CH.reserial(blob, serial), as_bytes=True)
 
 
 def _cat(pages):
@@ -231,11 +171,6 @@ def case7():
     return out
 
 
-def _head(serial, body, flags=2, nseg=None):
-    lacing = [len(body)] if nseg is None else [0] * nseg
-    return page(serial, 0, lacing, body, flags)
-
-
 @functools.lru_cache(maxsize=None)
 def case8():
     """edges (zero files is a batch of its own)"""
@@ -244,15 +179,15 @@ def case8():
     plain = _cat(v)
     noflag = bytearray(v[0])
     noflag[5] &= ~2
-    noflag = bytes(_recrc(noflag))
+    noflag = bytes(recrc(noflag))
     other = bytearray(noflag)
     other[27 + other[26]] = 3                               # the packet type byte: no mark
-    other = bytes(_recrc(other))
+    other = bytes(recrc(other))
     return {"empty": b"", "1 byte": plain[:1], "26 bytes": plain[:26], "27 bytes": plain[:27],
-            "head page of no segments": _cat([_head(90, b"", nseg=0)] + v),
-            "head page with a body of 6": _cat([_head(91, MARK[:6])] + tail),
-            "head page with a body of exactly 7": _cat([_head(struct.unpack_from("<I", v[0], 14)[0], MARK)] + tail),
-            "body of 7, one byte wrong": _cat([_head(92, b"\x01vorbit")] + tail),
+            "head page of no segments": _cat([head_page(90, b"", nseg=0)] + v),
+            "head page with a body of 6": _cat([head_page(91, MARK[:6])] + tail),
+            "head page with a body of exactly 7": _cat([head_page(struct.unpack_from("<I", v[0], 14)[0], MARK)] + tail),
+            "body of 7, one byte wrong": _cat([head_page(92, b"\x01vorbit")] + tail),
             "first page without the flag, with the mark": _cat([noflag] + tail),
             "first page without the flag or the mark": _cat([other] + tail)}
 
@@ -266,10 +201,10 @@ def singles():
 
 @functools.lru_cache(maxsize=None)
 def damage():
-    """every _corruptions variant of cases 1, 2 and 5"""
+    """every corruptions variant of cases 1, 2 and 5"""
     out = {}
     for src in (case1()["skeleton first"][0], case2()["video-like"][0], case5()["three groups"][0]):
-        for name, bad in _corruptions(src).items():
+        for name, bad in corruptions(src).items():
             out[f"{len(out)} {name}"] = bad
     return out
 
@@ -280,18 +215,6 @@ def cuts():
     blob = _cat(interleave([vorbis_pages(0), foreign("theora", 88, 28, sizes=(40, 60))], 29))
     assert 3000 < len(blob) < 4500, len(blob)               # the setup header alone is 3 KB
     return [blob[:n] for n in range(len(blob) + 1)]
-
-
-def sized_page(serial, seq, total, rng, flags=0, mark=False):
-    """a page of exactly `total` bytes (27 at least)"""
-    nseg = 0 if total == 27 else min(255, max(1, -(-(total - 27) // 256)))
-    body = total - 27 - nseg
-    lacing = [body // nseg + (1 if i < body % nseg else 0) for i in range(nseg)] if nseg else []
-    data = bytearray(_rb(rng, body))
-    if mark:
-        assert body >= 7
-        data[:7] = MARK
-    return page(serial, seq, lacing, bytes(data), flags)
 
 
 @functools.lru_cache(maxsize=None)
@@ -365,70 +288,23 @@ def group(name):
             "alignment": alignment_files}[name]()
 
 
-# ---- one interface over the host twin and the device calls ------------------------------------------------------------
+# ---- the host twin and the device calls (ogg_twin.Twin) ------------------------------------------------------------------
 
 def info_dtype():
     from vorbis_aotuv_lancer_amd.stream import SELECT_INFO
     return SELECT_INFO
 
 
-class Result:
-    pass
-
-
-class Select:
-    """A selector and its buffers.  impl 'host': numpy arrays and vbm_host_ogg_select; 'device': torch tensors and
-    vbm_ogg_select on the current stream."""
+class Select(Twin):
+    """A selector and its buffers"""
 
     GUARD = 64
 
     def __init__(self, impl, max_files, max_bytes):
-        self.impl, self.lib = impl, B._lib()
-        self.h = C.c_void_p()
-        make = self.lib.vbm_host_ogg_select_create if impl == "host" else self.lib.vbm_ogg_select_create
-        rc = make(C.byref(self.h), max_files, max_bytes)
-        assert rc == 0, (rc, self.lib.vbm_last_error())
-        self.keep = None
-
-    def close(self):
-        if self.impl == "device":
-            import torch
-            torch.cuda.synchronize()
-        self.lib.vbm_ogg_select_destroy(self.h)
-
-    def _new(self, n, fill):
-        if self.impl == "host":
-            return np.full(n, fill, np.uint8)
-        import torch
-        return torch.full((n,), fill, dtype=torch.uint8, device="cuda")
-
-    def _ptr(self, a):
-        return a.ctypes.data if self.impl == "host" else a.data_ptr()
-
-    def _back(self, a):
-        return a if self.impl == "host" else a.cpu().numpy()
-
-    def _q(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        super().__init__(impl, "select", max_files, max_bytes)
 
     def select_raw(self, nfiles, data_ptr, off_ptr, out_ptr, out_cap, out_off_ptr, info_ptr):
-        if self.impl == "host":
-            return self.lib.vbm_host_ogg_select(self.h, nfiles, data_ptr, off_ptr, out_ptr, out_cap, out_off_ptr, info_ptr)
-        return self.lib.vbm_ogg_select(self.h, nfiles, data_ptr, off_ptr, out_ptr, out_cap, out_off_ptr, info_ptr, self._q())
-
-    def status(self):
-        st = C.c_int(-7)
-        assert self.lib.vbm_ogg_select_status(self.h, C.byref(st), None if self.impl == "host" else self._q()) == 0
-        return st.value
-
-    def upload(self, data):
-        """uint8 numpy -> the address the call takes (kept alive here)"""
-        if self.impl == "device":
-            import torch
-            data = torch.from_numpy(data.copy()).cuda()
-        self.keep = data
-        return self._ptr(data) if len(data) else None
+        return self.call("select", nfiles, data_ptr, off_ptr, out_ptr, out_cap, out_off_ptr, info_ptr)
 
     def select(self, data, offsets, out_cap):
         """data: uint8 numpy or an address -> Result: .out [out_cap], .out_offsets [n + 1], .info [n], .status, .touched
@@ -437,17 +313,16 @@ class Select:
         if isinstance(data, np.ndarray):
             data = self.upload(data)
         isz, g = info_dtype().itemsize, self.GUARD
-        out, oo, info = self._new(out_cap + g, 0xA5), self._new(8 * (n + 1) + g, 0xA5), self._new(n * isz + g, 0xA5)
+        out, oo, info = (self.guarded(k, np.uint8, g) for k in (out_cap, 8 * (n + 1), n * isz))
         off = np.ascontiguousarray(offsets, np.int64)
-        rc = self.select_raw(n, data, off.ctypes.data, self._ptr(out), out_cap, self._ptr(oo), self._ptr(info))
+        rc = self.select_raw(n, data, off.ctypes.data, self.ptr(out), out_cap, self.ptr(oo), self.ptr(info))
         assert rc == 0, (rc, self.lib.vbm_last_error())
         r = Result()
         r.status = self.status()
-        out, oo, info = self._back(out), self._back(oo), self._back(info)
-        r.guard_ok = bool((out[out_cap:] == 0xA5).all() and (oo[8 * (n + 1):] == 0xA5).all() and (info[n * isz:] == 0xA5).all())
-        r.touched = bool((out[:out_cap] != 0xA5).any())
-        r.out, r.out_offsets = out[:out_cap], oo[:8 * (n + 1)].copy().view(np.int64)
-        r.info = info[:n * isz].copy().view(info_dtype())
+        (r.out, r.touched, ok0), (oo, _, ok1), (info, _, ok2) = (self.unguard(a, k) for a, k in
+                                                                 ((out, out_cap), (oo, 8 * (n + 1)), (info, n * isz)))
+        r.guard_ok = ok0 and ok1 and ok2
+        r.out_offsets, r.info = oo.copy().view(np.int64), info.copy().view(info_dtype())
         return r
 
 

@@ -4,14 +4,11 @@ packet, pages(flush=True) where the call flushes."""
 import numpy as np
 
 import vorbis_aotuv_lancer_amd as v
+from tests.ogg_pages import random_bytes as payload
 
 INFO = np.dtype({"names": ["stream", "block_mode", "lW", "W", "nW", "eos", "granulepos", "packetno"],
                  "formats": ["<i4"] * 6 + ["<i8", "<i8"]})
 assert INFO.itemsize == 40
-
-
-def payload(rng, size):
-    return rng.integers(0, 256, size, dtype=np.uint8).tobytes()
 
 
 # ---- per-stream schedules: a list of steps, each a list of (size, eos) packets, or "restart" ------------------------

@@ -14,7 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_c_example_writes_the_oracles_packets(oracle, cuda, tmp_path):
-    from tests.test_stream_wrapper import parse_pages, packets_of, unpack_headers
+    from tests.ogg_pages import parse_pages, packets_of
+    from tests.test_stream_wrapper import unpack_headers
     exe = os.path.join(ROOT, "examples", "encode_raw")
     if not os.path.exists(exe):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "examples")])

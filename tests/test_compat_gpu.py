@@ -44,7 +44,8 @@ def test_example_program_reproduces_reference_dump(oracle, cuda, tmp_path):
     assert hashlib.md5(got).hexdigest() == "0b15c75f94cb66bb39a5adaefcf26fbd"
     assert got == ref
     # and the .ogg it wrote is a stream: headers first, its audio packets are the dump's
-    from tests.test_stream_wrapper import parse_pages, packets_of, unpack_headers
+    from tests.ogg_pages import parse_pages, packets_of
+    from tests.test_stream_wrapper import unpack_headers
     from tests.test_frontend_gpu import split_dump
     pk = packets_of(parse_pages(open(ogg, "rb").read()))
     unpack_headers(*pk[:3])

@@ -263,7 +263,8 @@ def test_complete_ogg_stream(oracle, cuda):
     the three headers plus exactly the packets the oracle produces, granule positions end at the sample
     count, e_o_s sits on the last page."""
     import vorbis_aotuv_lancer_amd as v
-    from tests.test_stream_wrapper import parse_pages, packets_of, unpack_headers
+    from tests.ogg_pages import parse_pages, packets_of
+    from tests.test_stream_wrapper import unpack_headers
     ch, rate, q = 2, 44100, 0.5
     nsamp = 50 * 1024
     sig = synth_signal(ch, rate, nsamp, seed=77)

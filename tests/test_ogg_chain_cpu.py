@@ -10,7 +10,7 @@ import pytest
 from tests import ogg_chain_cases as K
 from tests import ogg_demux_batch as B
 from tests.ogg_chain_cases import ECAP, EINVAL
-from tests.test_ogg_demux_cpu import _guarded
+from tests.ogg_pages import guarded_mapping
 
 
 @pytest.mark.parametrize("name", ["1 link", "2 links", "3 links", "65 links", "three classes", "headers alone in the middle",
@@ -42,7 +42,7 @@ def test_multiplexed_start():
     mixes two serial numbers"""
     blob, _ = K.chains()["multiplexed start"]
     links = K.links_of(blob)
-    assert len(links) == 2 and len(K._pages(links[0])) == 1
+    assert len(links) == 2 and len(K.split_pages(links[0])) == 1
     assert K.check_demux("host", [blob]) == [False, False]
 
 
@@ -67,7 +67,7 @@ def test_every_prefix_of_a_two_link_file_as_one_batch():
     fl, lo = K.run("host", blobs)
     want_fl, want_lo = K.expected(blobs)
     assert np.array_equal(fl, want_fl) and np.array_equal(lo, want_lo)
-    p0 = len(K._pages(l1)[0])                                # link 1 starts once its first page is all there
+    p0 = len(K.split_pages(l1)[0])                                # link 1 starts once its first page is all there
     assert np.array_equal(np.diff(fl), [1 if k < len(l0) + p0 else 2 for k in range(len(blob) + 1)])
     # the links of the prefixes that reach into link 1, demuxed as one batch
     first = len(l0) + 1
@@ -178,12 +178,12 @@ def test_split_never_reads_past_the_last_file():
     libc = C.CDLL(None, use_errno=True)
     libc.mprotect.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
     a, b, c = K.small_links(3)
-    pages = K._pages(c)
+    pages = K.split_pages(c)
     cuts = [len(c) - 1, len(c) - len(pages[-1]) + 26, len(c) - len(pages[-1]) + 27, len(c) - len(pages[-1]) + 28, 0, 5]
     for cut in cuts:
         blobs = [a + b, c[:cut]] if cut else [a + b, b""]
         data, offsets = B.pack(blobs)
-        m, base, cap = _guarded(libc, len(data))
+        m, base, cap = guarded_mapping(libc, len(data))
         ch = K.Chain("host", 2, len(data))
         try:
             at = base + cap - len(data)

@@ -47,7 +47,7 @@ def test_every_prefix_of_a_two_link_file_as_one_batch(cuda):
     hfl, hlo = K.run("host", blobs)
     fl, lo = K.run("device", blobs)
     assert np.array_equal(fl, hfl) and np.array_equal(lo, hlo)
-    assert fl[-1] == 2 * len(blobs) - len(l0) - len(K._pages(l1)[0])
+    assert fl[-1] == 2 * len(blobs) - len(l0) - len(K.split_pages(l1)[0])
     # the links of the prefixes that reach into link 1, demuxed on the device and on the host twin
     j0, data = int(fl[len(l0) + 1]), np.frombuffer(b"".join(blobs), np.uint8)
     sub = lo[j0:]

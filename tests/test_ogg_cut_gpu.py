@@ -10,7 +10,7 @@ from tests import ogg_cut_cases as K
 from tests import ogg_select_cases as S
 from tests.ogg_cut_cases import ECAP, EINVAL, ESHAPE
 from tests.signals import synth_signal
-from tests.test_ogg_demux_cpu import _pages
+from tests.ogg_pages import split_pages
 
 pytestmark = pytest.mark.gpu
 
@@ -119,7 +119,7 @@ def test_padded_packets_start_at_every_residue(world):
     dst = set()
     for o, base in zip(outs, off):
         at = int(base)
-        for p in _pages(o):
+        for p in split_pages(o):
             dst.add((at + 27 + p[26]) % 16)
             at += len(p)
     assert dst == set(range(16))
@@ -178,7 +178,7 @@ def test_multiplexed_index_gives_the_same_cuts(cuda, world):
     import vorbis_aotuv_lancer_amd as v
     w = world["2ch"]
     src = w["srcs"][0]
-    pages = [bytes(p) for p in _pages(src.blob)]
+    pages = [bytes(p) for p in split_pages(src.blob)]
     muxed = S._cat(S.interleave([S.foreign("theora", 72, 2, sizes=(150000, 30, 66000), max_segs=255), pages], 3))
     assert S.model(muxed)[0] == src.blob and muxed != src.blob
     wins = K.windows(src, 6, seed=31)

@@ -44,12 +44,12 @@ def test_mixed_batch_equals_single_file_demux():
 
 def test_info_fields():
     import vorbis_aotuv_lancer_amd as v
-    from tests.test_ogg_demux_cpu import _pages
+    from tests.ogg_pages import split_pages
     names, blobs = zip(*B.mixed())
     info, _, _ = B.run("host", blobs)
     for f, blob in enumerate(blobs):
         if info[f]["status"] == 0:
-            assert info[f]["pages"] == len(_pages(blob)), names[f]
+            assert info[f]["pages"] == len(split_pages(blob)), names[f]
             assert info[f]["serialno"] == int.from_bytes(blob[14:18], "little"), names[f]
             assert [len(h) for h in v.demux_ogg(blob)[0]] == info[f]["header_bytes"].tolist()
 
@@ -57,7 +57,7 @@ def test_info_fields():
 def test_directed_shapes():
     """zero length, headers alone, 255 segments on a page, a packet over three pages, multiples of 255, a setup header
     that shares its page with audio, a header packet over pages, an unterminated last packet"""
-    from tests.test_ogg_demux_cpu import _pages
+    from tests.ogg_pages import split_pages
     d = dict(B.directed())
     blobs = list(d.values())
     info, totals, res = B.run("host", blobs)
@@ -68,11 +68,11 @@ def test_directed_shapes():
     pk = dict(zip(d, info["packets"].tolist()))
     assert pk["headers alone"] == 0 and pk["packet over three pages"] == 242 and pk["unterminated packet at the end"] == 240
     # the fixtures are what they are named
-    three = _pages(d["packet over three pages"])
+    three = split_pages(d["packet over three pages"])
     assert [p[26] for p in three[-3:]] == [255, 255, 6] and three[-2][5] & 1 and three[-1][5] & 1
-    shared = _pages(d["setup header shares its page"])
+    shared = split_pages(d["setup header shares its page"])
     assert sum(x < 255 for x in shared[1][27:27 + shared[1][26]]) >= 3        # comment, setup, audio
-    spans = _pages(d["header packet spans pages"])
+    spans = split_pages(d["header packet spans pages"])
     assert len(spans) >= 3 and spans[1][26] == 255 and spans[2][5] & 1
     # headers alone, and no file at all
     for blobs in ([d["headers alone"]], [d["zero length"]], []):

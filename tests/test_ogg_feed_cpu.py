@@ -9,7 +9,7 @@ import pytest
 
 from tests import ogg_feed_cases as F
 from tests.ogg_demux_batch import EOGG, single, six_packet_file
-from tests.test_ogg_demux_cpu import _guarded
+from tests.ogg_pages import guarded_mapping
 
 
 @pytest.fixture(scope="module")
@@ -98,7 +98,7 @@ def test_feed_never_reads_past_a_chunk():
     lib = F._lib()
     libc = C.CDLL(None, use_errno=True)
     libc.mprotect.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
-    m, base, cap = _guarded(libc, len(blob))
+    m, base, cap = guarded_mapping(libc, len(blob))
     feed = F.Feed("host", 1, len(blob), carry=8192)
     info = np.zeros(1, F._info_dtype())
     totals = np.zeros(2, np.int64)

@@ -13,7 +13,7 @@ from tests import ogg_feed_resync_cases as RS
 from tests import ogg_select_cases as SEL
 from tests.ogg_feed_mux_cases import EBIG, EINVAL, EOGG
 from tests.signals import synth_signal
-from tests.test_ogg_demux_cpu import _pages
+from tests.ogg_pages import split_pages
 
 pytestmark = pytest.mark.gpu
 
@@ -200,7 +200,7 @@ def test_the_default_did_not_move(cuda):
 # ---- end to end: encoded audio between foreign pages ----------------------------------------------------------------------
 
 def _p(blob):
-    return [bytes(p) for p in _pages(blob)]
+    return [bytes(p) for p in split_pages(blob)]
 
 
 @pytest.fixture(scope="module")

@@ -10,7 +10,7 @@ from tests import ogg_demux_batch as B
 from tests import ogg_select_cases as S
 from tests.ogg_select_cases import ECAP, EINVAL, EOGG
 from tests.signals import synth_signal
-from tests.test_ogg_demux_cpu import _pages
+from tests.ogg_pages import split_pages
 
 pytestmark = pytest.mark.gpu
 
@@ -122,7 +122,7 @@ def test_defaults_are_unchanged(cuda):
 # ---- decoding: real audio between the foreign pages ---------------------------------------------------------------------
 
 def _p(blob):
-    return [bytes(p) for p in _pages(blob)]
+    return [bytes(p) for p in split_pages(blob)]
 
 
 @pytest.fixture(scope="module")

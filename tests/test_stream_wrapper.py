@@ -8,14 +8,16 @@ and compares every field with the mode pack.  No reference header bytes exist to
 (parity with the reference unpinned); pack and unpack are different code in the reference, so the round
 trip is an independent check.
 
-Ogg pages: parsed back per the reference's doc/framing.html with an independent CRC (bitwise, no table)."""
+Ogg pages: parsed back per the reference's doc/framing.html with an independent CRC (bitwise, no table), both in
+tests/ogg_pages.py."""
 import glob
 import os
-import struct
 import sys
 
 import numpy as np
 import pytest
+
+from tests.ogg_pages import crc_bitwise, packets_of, page_crc, parse_pages, split_pages
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -251,50 +253,6 @@ def test_header_packets_read_back_to_the_mode_pack(pack):
     setup.close()
 
 
-def crc_bitwise(data):
-    """doc/framing.html:363-366: direct CRC-32, polynomial 0x04c11db7, initial value and final XOR 0"""
-    r = 0
-    for byte in data:
-        r ^= byte << 24
-        for _ in range(8):
-            r = ((r << 1) ^ 0x04c11db7) & 0xffffffff if r & 0x80000000 else (r << 1) & 0xffffffff
-    return r
-
-
-def parse_pages(blob):
-    pages, at = [], 0
-    while at < len(blob):
-        assert blob[at:at + 4] == b"OggS" and blob[at + 4] == 0
-        flags = blob[at + 5]
-        granule, serial, seq, crc = struct.unpack_from("<qIII", blob, at + 6)
-        nseg = blob[at + 26]
-        lacing = list(blob[at + 27:at + 27 + nseg])
-        size = 27 + nseg + sum(lacing)
-        page = bytearray(blob[at:at + size])
-        page[22:26] = b"\0\0\0\0"
-        assert crc_bitwise(page) == crc, "page CRC"
-        pages.append({"flags": flags, "granule": granule, "serial": serial, "seq": seq, "lacing": lacing,
-                      "body": blob[at + 27 + nseg:at + size]})
-        at += size
-    return pages
-
-
-def packets_of(pages):
-    out, cur, open_ = [], b"", False
-    for pg in pages:
-        assert bool(pg["flags"] & 1) == open_, "continued-packet flag"
-        at = 0
-        for lv in pg["lacing"]:
-            cur += pg["body"][at:at + lv]
-            at += lv
-            if lv < 255:
-                out.append(cur)
-                cur = b""
-        open_ = bool(pg["lacing"]) and pg["lacing"][-1] == 255
-    assert not open_
-    return out
-
-
 def test_ogg_pages_round_trip():
     import vorbis_aotuv_lancer_amd as v
     rng = np.random.default_rng(5)
@@ -330,6 +288,20 @@ def test_ogg_pages_round_trip():
         done += ends
         assert pg["granule"] == (gps[done - 1] if ends else -1)
     os_.close()
+
+
+def test_page_checksums_agree():
+    """the tests' two checksums (table and bitwise, tests/ogg_pages.py) and the product's, which the corpora no longer
+    borrow: on no bytes, on one byte, and on every page of a file with its checksum field zeroed"""
+    from vorbis_aotuv_lancer_amd.stream import _page_crc
+    from tests.ogg_demux_batch import six_packet_file
+    pages = split_pages(six_packet_file()[0])
+    assert len(pages) >= 3
+    for p in pages:
+        p[22:26] = b"\0\0\0\0"
+    for data in [b"", b"\x5a"] + [bytes(p) for p in pages]:
+        assert page_crc(data) == crc_bitwise(data) == _page_crc(data), len(data)
+    assert page_crc(b"\x5a") != 0
 
 
 def test_header_bytes_equal_the_oracles(oracle):
