@@ -992,6 +992,36 @@ int  vbm_range_store_create_device(vbm_range_store **st, vbm_decoder *dec, int n
                                    const long long *stream_packets /*host*/, const uint8_t *d_data,
                                    const long long *d_offsets, long long data_bytes, const long long *d_granulepos,
                                    const uint8_t *d_eos, void *stream);
+/* The same four for a mixed decoder (vbm_decoder_create_mixed): stream_classes [nstreams] (host) is the class of each
+ * stream, an id vbm_decoder_add_class has returned for this decoder; any other id is VBM_EINVAL with a message, before
+ * anything is allocated or enqueued.  A store's classes are its own: they are not taken from vbm_decoder_bind_streams,
+ * and a class added after one store was made may be used by the next.  The index of every stream is the one its
+ * class's setup gives for it alone, bit for bit.  The index kernels are the same two launches whatever the number of
+ * classes: a packet finds its stream, hence its class, by a search in the staged table of first packets, and a
+ * wavefront takes its stream's block sizes from the class table (per launch at most 2 * max_batch or nstreams of the
+ * decoder streams).  vbm_host_decode_index_scan_mixed: the CPU twin over setups[nclasses], with the same lookup;
+ * VBM_EINVAL for a class id outside [0, nclasses).  stream_classes NULL: the call without _mixed.
+ * The plain four refuse a mixed decoder, and these refuse a decoder of one setup (VBM_EINVAL). */
+int  vbm_range_store_create_mixed(vbm_range_store **st, vbm_decoder *dec, int nstreams, const long long *stream_packets,
+                                  const int *stream_classes /*host [nstreams]*/, const uint8_t *data,
+                                  const long long *offsets, long long data_bytes, const long long *granulepos,
+                                  const uint8_t *eos);
+int  vbm_range_store_create_device_mixed(vbm_range_store **st, vbm_decoder *dec, int nstreams,
+                                         const long long *stream_packets /*host*/,
+                                         const int *stream_classes /*host [nstreams]*/, const uint8_t *d_data,
+                                         const long long *d_offsets, long long data_bytes,
+                                         const long long *d_granulepos, const uint8_t *d_eos, void *stream);
+int  vbm_decode_index_device_mixed(vbm_decoder *dec, int nstreams, const long long *stream_packets /*host [nstreams+1]*/,
+                                   const int *stream_classes /*host [nstreams]*/, const uint8_t *d_data,
+                                   const long long *d_offsets /*[P+1]*/, long long data_bytes,
+                                   const long long *d_granulepos /*[P] or NULL*/, const uint8_t *d_eos /*[P] or NULL*/,
+                                   int *d_status, int *d_begin, int *d_end, long long *d_out_start, long long *d_totals,
+                                   void *stream);
+int  vbm_host_decode_index_scan_mixed(int nclasses, const vbm_decode_setup *const *setups, int halfrate, int nstreams,
+                                      const long long *stream_packets, const int *stream_classes, const uint8_t *data,
+                                      const long long *offsets, long long data_bytes, const long long *granulepos,
+                                      const uint8_t *eos, int *status, int *begin, int *end, long long *out_start,
+                                      long long *totals);
 /* Sample windows of the store's streams.  Range r is stream stream_ids[r], start starts[r] >= 0, length lengths[r]
  * >= 0 (host arrays; ranges may repeat and overlap).  got[r] (host) = clamp(total - start, 0, length), and
  *   d_pcm[r][c][0 .. got[r]) == linear decode of the stream [c][start .. start + got[r])   bit for bit;
@@ -1000,7 +1030,11 @@ int  vbm_range_store_create_device(vbm_range_store **st, vbm_decoder *dec, int n
  * plus one pre-roll packet; a range of more than max_batch packets is cut into pieces, and pieces are packed into
  * sub-calls of at most max_batch rows, all enqueued on `stream` (the piece table of each goes through the staging
  * ring).  VBM_EINVAL, with nothing enqueued: a store of another decoder, a stream id out of range, a negative start
- * or length, pcm_stride < max(lengths), max_batch < 2. */
+ * or length, pcm_stride < max(lengths), max_batch < 2.
+ * A mixed decoder takes the stores its _mixed creators made for it: d_pcm is [nranges][max_channels][pcm_stride], the
+ * layout of vbm_synthesis_runs on such a decoder, and range r writes channels 0 .. channels(class of its stream) - 1,
+ * samples 0 .. got[r] - 1 and nothing else.  The sub-calls are the same whatever the number of classes, one launch
+ * chain each; no stream state is read or written, and the bindings of vbm_decoder_bind_streams play no part. */
 int  vbm_synthesis_ranges(vbm_decoder *dec, const vbm_range_store *st, int nranges, const int *stream_ids,
                           const long long *starts, const int *lengths, float *d_pcm, long pcm_stride, int *got,
                           void *stream);

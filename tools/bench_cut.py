@@ -14,7 +14,12 @@ windows of `--window` seconds, every one its own output file:
                median of --host-reps): what a user can do today without a re-encode
     host_prep  the wall time of making the files' header pages with the host writer (one OggStream per file; the cut
                writes each output's serial number into them), which OggIndex.cut_ranges spends once; not part of `cut`
-The device's outputs are compared with the twin's byte for byte."""
+The device's outputs are compared with the twin's byte for byte.
+
+--classes K: the files are dealt evenly over K header classes (tools/bench_index.py's class_files) and one call of
+OggIndex(one_decoder=True).cut_ranges(out=) over all windows is timed against K single-class indexes, each given its
+own files' windows (sorted by class beforehand, outside the timing): cut_ms of both, and the clips must be equal.
+--arms per_class times the single-class indexes alone: that runs on a build without mixed range stores too."""
 import argparse
 import json
 import os
@@ -42,6 +47,58 @@ def events_ms(torch, fn, reps):
     return ms
 
 
+def classes_report(v, torch, a):
+    from tools.bench_decode_mixed import CLASSES
+    from tools.bench_index import class_files
+    K = a.classes
+    files, of = class_files(v, K, a.files, a.seconds, a.signals)
+    arms = ["mixed", "per_class"] if a.arms == "both" else [a.arms]
+    mine = [[i for i, c in enumerate(of) if c == k] for k in range(K)]
+    mixed = v.OggIndex(files, device_demux=True, one_decoder=True) if "mixed" in arms else None
+    single = [v.OggIndex([files[i] for i in m], device_demux=True) for m in mine]
+    totals = [int(single[c].total_samples[i // K]) for i, c in enumerate(of)]
+    rng = np.random.default_rng(a.seed)
+    ids = rng.integers(0, a.files, a.ranges)
+    L = np.array([int(a.window * CLASSES[of[i]][0]) for i in ids], np.int64)
+    starts = np.array([rng.integers(0, max(1, totals[i] - n)) for i, n in zip(ids, L)], np.int64)
+    serials = np.arange(a.ranges)
+    rows = [np.flatnonzero(np.asarray(of)[ids] == k) for k in range(K)]
+    local = [np.array([mine[k].index(int(i)) for i in ids[r]], np.int64) for k, r in enumerate(rows)]
+    clips = [None] * a.ranges                                          # the list form: the sizes, and the reference
+    for k, r in enumerate(rows):
+        for i, c in zip(r, single[k].cut_ranges(local[k], starts[r], L[r], serials[r])[0]):
+            clips[i] = c
+    size = np.array([len(c) for c in clips])
+    out = torch.zeros(int(size.sum()), dtype=torch.uint8, device="cuda")
+    outs = [torch.zeros(int(size[r].sum()), dtype=torch.uint8, device="cuda") for r in rows]
+    res = {}
+
+    def one():
+        res["m"] = mixed.cut_ranges(ids, starts, L, serials, out=out)
+
+    def per_class():
+        res["s"] = [single[k].cut_ranges(local[k], starts[r], L[r], serials[r], out=outs[k])
+                    for k, r in enumerate(rows) if len(r)]
+
+    fns, times = {"mixed": one, "per_class": per_class}, {arm: [] for arm in arms}
+    for _ in range(a.runs):                                            # the arms alternate, run by run
+        for arm in arms:
+            times[arm].append(statistics.median(events_ms(torch, fns[arm], a.reps)))
+    same = mixed is None or out.cpu().numpy().tobytes() == b"".join(clips)
+    for k, r in enumerate(rows):
+        same &= outs[k].cpu().numpy().tobytes() == b"".join(clips[i] for i in r)
+    res = {"metric": "ogg_cut_classes_ms", "classes": K, "files": a.files, "seconds": a.seconds, "ranges": a.ranges,
+           "window_seconds": a.window, "out_bytes": int(size.sum()), "reps": a.reps, "runs": a.runs,
+           "same_outputs": bool(same)}
+    for arm in arms:
+        res[arm + "_ms"], res[arm + "_ms_runs"] = statistics.median(times[arm]), times[arm]
+    if len(arms) == 2:
+        res["per_class_over_mixed"] = res["per_class_ms"] / res["mixed_ms"]
+    print(json.dumps(res), flush=True)
+    for x in single + ([mixed] if mixed else []):
+        x.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=256)
@@ -52,12 +109,18 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=2026)
+    ap.add_argument("--classes", type=int, default=0, help="K > 0: one mixed index against K single-class ones")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--arms", choices=["both", "per_class"], default="both")
     a = ap.parse_args()
 
     import torch
     import vorbis_aotuv_lancer_amd as v
     from tests.signals import burst_signal
 
+    if a.classes:
+        classes_report(v, torch, a)
+        return
     rate, n = 44100, int(a.seconds * 44100)
     base = v.encode_ogg([burst_signal(2, rate, n, seed=900 + k, period=20000, level=1.0 if k % 4 else 0.05)
                          for k in range(a.signals)], rate, quality=0.5)

@@ -1,6 +1,6 @@
 """vorbis_aotuv_lancer_amd — MI355X-native batched Vorbis (aoTuV) encode path, plus a batched
 device decoder (DecodeSetup, Decoder: Vorbis packets -> PCM; decode_ogg: .ogg files -> PCM; DeviceDemuxer: the Ogg demux of many files per call on the device; ChainSplitter, split_ogg_chain: the links of chained files; StreamSelector, select_vorbis_stream: the Vorbis stream of multiplexed files; OggFeed: the same for live streams, the next bytes of every stream per call; OggIndex: random sample
-windows of many .ogg files, as PCM or cut into new .ogg files without a re-encode (OggCutter); halfrate=True on any of them decodes at half the sample rate) and its mirror for whole
+windows of many .ogg files, as PCM or cut into new .ogg files without a re-encode (OggCutter), of any mix of header classes with one_decoder=True (one MixedDecoder and one RangeStore with a class per stream); halfrate=True on any of them decodes at half the sample rate) and its mirror for whole
 files (encode_ogg: PCM arrays of any lengths -> one .ogg each; plan_files: the schedule it follows).
 
 Host-side mirror (Python) of the reference's per-block encode interface over the C ABI in

@@ -26,7 +26,15 @@
 // caps allow, and a table of classes (vbm_decoder_add_class) in place of the one setup.  vbm_synthesis_batch and
 // vbm_synthesis_runs enqueue the same chains with the <MX = true> kernels: the class of every row goes up behind the
 // ids or the run table in the same staging turn (from the host mirror of vbm_decoder_bind_streams' map), and there is
-// one IMDCT launch per block size.  The range store, the index and fetch are refused on it.
+// one IMDCT launch per block size.  Fetch is refused on it.
+//
+// Range stores and the index of a mixed decoder (the _mixed creators, vbm_decode_index_device_mixed): the store keeps a
+// host class column, one class per stream, which is its own and independent of vbm_decoder_bind_streams.
+// vbm_synthesis_ranges sends the class of every piece (its stream's) behind the piece table in the same staging turn;
+// k_range_rows spreads it over the piece's rows into the row-class column behind d_rows, and the rest of the chain is
+// the <MX = true> one of vbm_synthesis_runs, its IMDCT grids sized by sum(rows x channels of the piece's class).  The
+// index stages the streams' classes behind their first packets; k_index_head finds a packet's stream, hence class, by
+// a search in that table, and k_index_scan takes stream i's block sizes from its class.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -64,6 +72,7 @@ struct vbm_decoder {
     int *d_lists = nullptr, *d_counts = nullptr;
     int *d_runtab = nullptr, *d_plan = nullptr, *d_run_last = nullptr;   // runs: [2S+1], [cap][6], [S]
     int *d_rtab = nullptr, *d_rows = nullptr, *d_zero = nullptr;         // ranges: [4 cap + 1], [cap], [cap] zeros
+                                     // (mixed: d_rows [2 cap], the class of every row behind the rows)
     int *d_itab = nullptr;           // device index: [stage_ints] first packets of the streams of one scan launch
     size_t stage_ints = 0;           // ints in a staging slot
     float *d_res = nullptr, *d_spec = nullptr, *d_imdct = nullptr;
@@ -202,11 +211,12 @@ int check_call_ids(vbm_decoder *d, int n, const int *ids)
     return VBM_OK;
 }
 
-// an entry point that is not built for mixed decoders
-int refuse_mixed(const vbm_decoder *d, const char *what)
+// an entry point that is not built for mixed decoders, or that has a _mixed form which takes the streams' classes
+int refuse_mixed(const vbm_decoder *d, const char *what, const char *instead = nullptr)
 {
     if (!d || !d->mixed) return VBM_OK;
-    g_vbm_err = std::string(what) + " is not built for a mixed decoder: one header class per range store and index";
+    g_vbm_err = instead ? std::string(what) + " of a mixed decoder needs a class per stream: " + instead
+                        : std::string(what) + " is not built for a mixed decoder";
     return VBM_EINVAL;
 }
 
@@ -326,13 +336,14 @@ int create(vbm_decoder **out, const vbm_decode_setup *ds, int table_cap, int max
     CK(hipMalloc((void **)&d->d_prevW, (size_t)nstreams * sizeof(int)));
     CK(hipMalloc((void **)&d->d_gp, (size_t)nstreams * sizeof(long long)));
     CK(hipMalloc((void **)&d->d_sc, (size_t)nstreams * sizeof(long long)));
-    // range piece tables: at most cap / 2 pieces (each has two rows or more) of 7 ints, and the row starts
+    // range piece tables: at most cap / 2 pieces (each has two rows or more) of 7 ints, and the row starts; in a mixed
+    // decoder an eighth int per piece, its class, which 4 cap + 1 holds as well
     const size_t runtab = 2 * (size_t)nstreams + 1 + row_classes, rtab = 4 * cap + 1, stage = rtab > runtab ? rtab : runtab;
     CK(hipMalloc((void **)&d->d_runtab, runtab * sizeof(int)));
     CK(hipMalloc((void **)&d->d_plan, cap * 6 * sizeof(int)));
     CK(hipMalloc((void **)&d->d_run_last, (size_t)nstreams * sizeof(int)));
     CK(hipMalloc((void **)&d->d_rtab, rtab * sizeof(int)));
-    CK(hipMalloc((void **)&d->d_rows, cap * sizeof(int)));
+    CK(hipMalloc((void **)&d->d_rows, (cap + row_classes) * sizeof(int)));
     CK(hipMalloc((void **)&d->d_zero, cap * sizeof(int)));
     CK(hipMemset(d->d_zero, 0, cap * sizeof(int)));
     CK(hipMalloc((void **)&d->d_itab, stage * sizeof(int)));
@@ -625,6 +636,7 @@ struct vbm_range_store {
     uint8_t *d_data = nullptr;
     long long *d_offsets = nullptr, *d_out_start = nullptr;   // [P + 1], [P]
     int *d_begin = nullptr, *d_end = nullptr;                 // [P]
+    std::vector<int> cls;                // [S] the class of each stream, in a store of a mixed decoder (else empty)
 };
 
 namespace {
@@ -639,12 +651,25 @@ void free_store(vbm_range_store *st)
 }
 
 // The argument rules of a range store's CSR, for host arrays (vbm_range_store_create) and device arrays alike
-int check_csr(const vbm_decoder *d, int nstreams, const long long *stream_packets, const uint8_t *data,
-              const long long *offsets, long long data_bytes)
+// classes: null (a decoder of one setup), or the class of each stream (a mixed decoder), all of them in its table
+int check_csr(const vbm_decoder *d, int nstreams, const long long *stream_packets, const int *classes,
+              const uint8_t *data, const long long *offsets, long long data_bytes)
 {
     if (!d || nstreams <= 0 || !stream_packets || data_bytes < 0 || (data_bytes > 0 && !data) || !offsets)
         return VBM_EINVAL;
-    if (refuse_mixed(d, "a range store or device index")) return VBM_EINVAL;
+    if (!classes && refuse_mixed(d, "a range store or device index",
+                                 "vbm_range_store_create_mixed, _create_device_mixed, vbm_decode_index_device_mixed"))
+        return VBM_EINVAL;
+    if (classes && !d->mixed) {
+        g_vbm_err = "stream classes need a decoder of vbm_decoder_create_mixed";
+        return VBM_EINVAL;
+    }
+    for (int i = 0; classes && i < nstreams; i++)
+        if (classes[i] < 0 || classes[i] >= (int)d->classes.size()) {
+            g_vbm_err = "stream " + std::to_string(i) + ": class id " + std::to_string(classes[i]) +
+                        " is not in the decoder's table (vbm_decoder_add_class)";
+            return VBM_EINVAL;
+        }
     if (stream_packets[0] != 0) { g_vbm_err = "stream_packets[0] must be 0"; return VBM_EINVAL; }
     for (int i = 0; i < nstreams; i++)
         if (stream_packets[i + 1] < stream_packets[i]) { g_vbm_err = "stream_packets must not decrease"; return VBM_EINVAL; }
@@ -653,12 +678,12 @@ int check_csr(const vbm_decoder *d, int nstreams, const long long *stream_packet
 }
 
 // *out: a store of d for a CSR that check_csr passes, the host index sized, the device arrays allocated, none filled
-int new_store(vbm_range_store **out, vbm_decoder *d, int nstreams, const long long *stream_packets, const uint8_t *data,
-              const long long *offsets, long long data_bytes)
+int new_store(vbm_range_store **out, vbm_decoder *d, int nstreams, const long long *stream_packets, const int *classes,
+              const uint8_t *data, const long long *offsets, long long data_bytes)
 {
     if (!out) return VBM_EINVAL;
     *out = nullptr;
-    const int bad = check_csr(d, nstreams, stream_packets, data, offsets, data_bytes);
+    const int bad = check_csr(d, nstreams, stream_packets, classes, data, offsets, data_bytes);
     if (bad) return bad;
     const size_t np = (size_t)stream_packets[nstreams];
     vbm_range_store *st = new vbm_range_store();
@@ -666,6 +691,7 @@ int new_store(vbm_range_store **out, vbm_decoder *d, int nstreams, const long lo
     st->dec = d;
     st->S = nstreams;
     st->first.assign(stream_packets, stream_packets + nstreams + 1);
+    if (classes) st->cls.assign(classes, classes + nstreams);
     st->status.resize(np);
     st->out_end.resize(np);
     st->totals.resize((size_t)nstreams);
@@ -680,24 +706,33 @@ int new_store(vbm_range_store **out, vbm_decoder *d, int nstreams, const long lo
 }
 
 // k_index_head over all packets, then k_index_scan over the streams, as many per launch as one staging slot holds
-// first packets for (they go up through the ring into d_itab; launches on one stream follow each other)
-int enqueue_index(vbm_decoder *d, int nstreams, const long long *stream_packets, const uint8_t *d_data,
-                  const long long *d_offsets, long long data_bytes, const long long *d_granulepos, const uint8_t *d_eos,
-                  int *d_status, int *d_begin, int *d_end, long long *d_out_start, long long *d_out_end,
-                  long long *d_totals, hipStream_t q)
+// first packets for (they go up through the ring into d_itab; launches on one stream follow each other).
+// classes (a mixed decoder): the streams' classes go up behind their first packets, half as many streams per slot, and
+// k_index_head runs behind each upload, over the packets of its streams: one launch over all packets of all classes
+// whenever one slot holds the streams, as it does up to 2 * max_batch of them.
+int enqueue_index(vbm_decoder *d, int nstreams, const long long *stream_packets, const int *classes,
+                  const uint8_t *d_data, const long long *d_offsets, long long data_bytes,
+                  const long long *d_granulepos, const uint8_t *d_eos, int *d_status, int *d_begin, int *d_end,
+                  long long *d_out_start, long long *d_out_end, long long *d_totals, hipStream_t q)
 {
     const vbmd_setup *s = (const vbmd_setup *)d->d_setup;
-    if (vbmd_launch_index_head(s, stream_packets[nstreams], d_data, d_offsets, data_bytes, d_status, d_begin, q))
+    if (!classes &&
+        vbmd_launch_index_head(s, stream_packets[nstreams], d_data, d_offsets, data_bytes, d_status, d_begin, q))
         return VBM_EHIP;
-    const int room = (int)std::min<size_t>(d->stage_ints - 1, (size_t)INT_MAX - 1);
+    const size_t ints = classes ? (d->stage_ints - 1) / 2 : d->stage_ints - 1;
+    const int room = (int)std::min<size_t>(ints, (size_t)INT_MAX - 1);
     for (int s0 = 0; s0 < nstreams; s0 += room) {
         const int n = std::min(room, nstreams - s0);
-        const int rc = stage(d, d->d_itab, (size_t)n + 1, q, [&](int *slot) {
+        const int rc = stage(d, d->d_itab, (size_t)n + 1 + (classes ? n : 0), q, [&](int *slot) {
             for (int i = 0; i <= n; i++) slot[i] = (int)stream_packets[s0 + i];
+            if (classes) memcpy(slot + n + 1, classes + s0, (size_t)n * sizeof(int));
         });
         if (rc) return rc;
-        if (vbmd_launch_index_scan(s, d->halfrate, n, d->d_itab, d_status, d_granulepos, d_eos, d_begin, d_end,
-                                   d_out_start, d_out_end, d_totals + s0, q))
+        if (classes && vbmd_launch_index_head_mixed(d->d_table, n, d->d_itab, stream_packets[s0], stream_packets[s0 + n],
+                                                    d_data, d_offsets, data_bytes, d_status, d_begin, q))
+            return VBM_EHIP;
+        if (vbmd_launch_index_scan(s, classes ? d->d_table : nullptr, d->halfrate, n, d->d_itab, d_status, d_granulepos,
+                                   d_eos, d_begin, d_end, d_out_start, d_out_end, d_totals + s0, q))
             return VBM_EHIP;
     }
     return VBM_OK;
@@ -705,11 +740,14 @@ int enqueue_index(vbm_decoder *d, int nstreams, const long long *stream_packets,
 
 }  // namespace
 
-extern "C" int vbm_range_store_create(vbm_range_store **out, vbm_decoder *d, int nstreams,
-                                      const long long *stream_packets, const uint8_t *data, const long long *offsets,
-                                      long long data_bytes, const long long *granulepos, const uint8_t *eos)
+namespace {
+
+// vbm_range_store_create (classes null) and vbm_range_store_create_mixed
+int create_store(vbm_range_store **out, vbm_decoder *d, int nstreams, const long long *stream_packets,
+                 const int *classes, const uint8_t *data, const long long *offsets, long long data_bytes,
+                 const long long *granulepos, const uint8_t *eos)
 {
-    const int bad = new_store(out, d, nstreams, stream_packets, data, offsets, data_bytes);
+    const int bad = new_store(out, d, nstreams, stream_packets, classes, data, offsets, data_bytes);
     if (bad) return bad;
     vbm_range_store *st = *out;
     auto fail = [=](int rc) { free_store(st); *out = nullptr; return rc; };
@@ -718,7 +756,9 @@ extern "C" int vbm_range_store_create(vbm_range_store **out, vbm_decoder *d, int
     std::vector<long long> out_start(np);
     for (int i = 0; i < nstreams; i++) {
         const long long a = stream_packets[i];
-        vbmd_index_stream(d->hs, d->halfrate, stream_packets[i + 1] - a, data, offsets + a, data_bytes,
+        // a class's setup is the head of the host image its device copy was made from
+        const vbmd_setup &hs = classes ? *(const vbmd_setup *)d->classes[classes[i]].image.data() : d->hs;
+        vbmd_index_stream(hs, d->halfrate, stream_packets[i + 1] - a, data, offsets + a, data_bytes,
                           granulepos ? granulepos + a : nullptr, eos ? eos + a : nullptr, st->status.data() + a,
                           begin.data() + a, end.data() + a, out_start.data() + a, &st->totals[i]);
     }
@@ -731,6 +771,23 @@ extern "C" int vbm_range_store_create(vbm_range_store **out, vbm_decoder *d, int
         CK(hipMemcpy(st->d_end, end.data(), np * sizeof(int), hipMemcpyHostToDevice));
     }
     return VBM_OK;
+}
+
+}  // namespace
+
+extern "C" int vbm_range_store_create(vbm_range_store **out, vbm_decoder *d, int nstreams,
+                                      const long long *stream_packets, const uint8_t *data, const long long *offsets,
+                                      long long data_bytes, const long long *granulepos, const uint8_t *eos)
+{
+    return create_store(out, d, nstreams, stream_packets, nullptr, data, offsets, data_bytes, granulepos, eos);
+}
+
+extern "C" int vbm_range_store_create_mixed(vbm_range_store **out, vbm_decoder *d, int nstreams,
+                                            const long long *stream_packets, const int *stream_classes,
+                                            const uint8_t *data, const long long *offsets, long long data_bytes,
+                                            const long long *granulepos, const uint8_t *eos)
+{
+    return create_store(out, d, nstreams, stream_packets, stream_classes, data, offsets, data_bytes, granulepos, eos);
 }
 
 extern "C" void vbm_range_store_destroy(vbm_range_store *st)
@@ -757,10 +814,13 @@ extern "C" int vbm_synthesis_ranges(vbm_decoder *d, const vbm_range_store *st, i
                                     const long long *starts, const int *lengths, float *d_pcm, long pcm_stride,
                                     int *got, void *stream)
 {
-    if (refuse_mixed(d, "vbm_synthesis_ranges")) return VBM_EINVAL;
     if (!d || !st || nranges < 0 || (nranges > 0 && (!stream_ids || !starts || !lengths || !got)))
         return VBM_EINVAL;
-    if (st->dec != d) { g_vbm_err = "the range store belongs to another decoder"; return VBM_EINVAL; }
+    if (st->dec != d) {
+        g_vbm_err = d->mixed ? "the range store was not made for this mixed decoder (vbm_range_store_create_mixed)"
+                             : "the range store belongs to another decoder";
+        return VBM_EINVAL;
+    }
     if (d->cap < 2) { g_vbm_err = "range calls need max_batch >= 2"; return VBM_EINVAL; }
     long most = 0;
     bool any = false;
@@ -791,11 +851,19 @@ extern "C" int vbm_synthesis_ranges(vbm_decoder *d, const vbm_range_store *st, i
             tab.insert(tab.end(), {pc.r, pc.pre, pc.first, (int)(unsigned)(s & 0xffffffffu), (int)(unsigned)(s >> 32),
                                    got[r0 + pc.r]});
         }
+        long nblocks = 0;                                   // mixed: the pieces' classes, and rows x channels
+        for (int p = p0; d->mixed && p < p0 + np; p++) {
+            const vbm_range_piece &pc = plan.pieces[p];
+            tab.push_back(st->cls[stream_ids[r0 + pc.r]]);
+            nblocks += (long)(pc.count + 1) * d->classes[tab.back()].ch;
+        }
         int rc = stage_ints(d, d->d_rtab, tab.data(), tab.size(), q);
         if (rc) return rc;
-        const vbmd_launch L = d->launch(nsb);
+        int *rcls = d->mixed ? d->d_rows + d->cap : nullptr;
+        const vbmd_launch L = d->launch(nsb, rcls, nblocks);
         rc = enqueue_front(d, L, q, "hipMemsetAsync(decode ranges)", [&] {
-            return vbmd_launch_unpack_rows(L, np, d->d_rtab, d->d_rows, st->d_data, st->d_offsets, st->data_bytes, q);
+            return vbmd_launch_unpack_rows(L, np, d->d_rtab, d->d_rows, rcls, st->d_data, st->d_offsets, st->data_bytes,
+                                           q);
         });
         if (rc) return rc;
         if (vbmd_launch_ranges(L, np, d->d_rtab, d->d_rows, st->d_begin, st->d_end, st->d_out_start, d->d_zero,
@@ -812,12 +880,24 @@ extern "C" int vbm_decode_index_device(vbm_decoder *d, int nstreams, const long 
                                        const long long *d_granulepos, const uint8_t *d_eos, int *d_status, int *d_begin,
                                        int *d_end, long long *d_out_start, long long *d_totals, void *stream)
 {
-    const int rc = check_csr(d, nstreams, stream_packets, d_data, d_offsets, data_bytes);
+    return vbm_decode_index_device_mixed(d, nstreams, stream_packets, nullptr, d_data, d_offsets, data_bytes,
+                                         d_granulepos, d_eos, d_status, d_begin, d_end, d_out_start, d_totals, stream);
+}
+
+// stream_classes null: vbm_decode_index_device's body, which refuses a mixed decoder
+extern "C" int vbm_decode_index_device_mixed(vbm_decoder *d, int nstreams, const long long *stream_packets,
+                                             const int *stream_classes, const uint8_t *d_data,
+                                             const long long *d_offsets, long long data_bytes,
+                                             const long long *d_granulepos, const uint8_t *d_eos, int *d_status,
+                                             int *d_begin, int *d_end, long long *d_out_start, long long *d_totals,
+                                             void *stream)
+{
+    const int rc = check_csr(d, nstreams, stream_packets, stream_classes, d_data, d_offsets, data_bytes);
     if (rc) return rc;
     if (!d_totals || (stream_packets[nstreams] > 0 && (!d_status || !d_begin || !d_end || !d_out_start)))
         return VBM_EINVAL;
-    return enqueue_index(d, nstreams, stream_packets, d_data, d_offsets, data_bytes, d_granulepos, d_eos, d_status,
-                         d_begin, d_end, d_out_start, nullptr, d_totals, (hipStream_t)stream);
+    return enqueue_index(d, nstreams, stream_packets, stream_classes, d_data, d_offsets, data_bytes, d_granulepos, d_eos,
+                         d_status, d_begin, d_end, d_out_start, nullptr, d_totals, (hipStream_t)stream);
 }
 
 extern "C" int vbm_range_store_create_device(vbm_range_store **out, vbm_decoder *d, int nstreams,
@@ -825,7 +905,18 @@ extern "C" int vbm_range_store_create_device(vbm_range_store **out, vbm_decoder 
                                              const long long *d_offsets, long long data_bytes,
                                              const long long *d_granulepos, const uint8_t *d_eos, void *stream)
 {
-    int rc = new_store(out, d, nstreams, stream_packets, d_data, d_offsets, data_bytes);
+    return vbm_range_store_create_device_mixed(out, d, nstreams, stream_packets, nullptr, d_data, d_offsets, data_bytes,
+                                               d_granulepos, d_eos, stream);
+}
+
+// stream_classes null: vbm_range_store_create_device's body, which refuses a mixed decoder
+extern "C" int vbm_range_store_create_device_mixed(vbm_range_store **out, vbm_decoder *d, int nstreams,
+                                                   const long long *stream_packets, const int *stream_classes,
+                                                   const uint8_t *d_data, const long long *d_offsets,
+                                                   long long data_bytes, const long long *d_granulepos,
+                                                   const uint8_t *d_eos, void *stream)
+{
+    int rc = new_store(out, d, nstreams, stream_packets, stream_classes, d_data, d_offsets, data_bytes);
     if (rc) return rc;
     vbm_range_store *st = *out;
     const size_t np = (size_t)stream_packets[nstreams], ns = (size_t)nstreams;
@@ -845,8 +936,8 @@ extern "C" int vbm_range_store_create_device(vbm_range_store **out, vbm_decoder 
     CK(hipMemcpyAsync(st->d_offsets, d_offsets, (np + 1) * sizeof(long long), hipMemcpyDeviceToDevice, q));
     long long *d_out_end = (long long *)d_back, *d_totals = d_out_end + np;
     int *d_status = (int *)(d_totals + ns);
-    rc = enqueue_index(d, nstreams, stream_packets, st->d_data, st->d_offsets, data_bytes, d_granulepos, d_eos,
-                       d_status, st->d_begin, st->d_end, st->d_out_start, d_out_end, d_totals, q);
+    rc = enqueue_index(d, nstreams, stream_packets, stream_classes, st->d_data, st->d_offsets, data_bytes, d_granulepos,
+                       d_eos, d_status, st->d_begin, st->d_end, st->d_out_start, d_out_end, d_totals, q);
     if (rc) return fail(rc);
     std::vector<uint8_t> back(back_bytes);
     CK(hipMemcpyAsync(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost, q));

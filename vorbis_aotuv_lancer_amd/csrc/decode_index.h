@@ -48,6 +48,20 @@ VBMD_HD int vbmi_head(const vbmd_setup &s, const uint8_t *data, const long long 
     return status;
 }
 
+// The stream of packet k among streams [0, n): the largest i with first[i] <= k.  first [n + 1] does not decrease and
+// first[0] <= k < first[n], so that stream is not empty and holds k.  This is how k_index_head<true> and the host twin
+// (vbm_host_decode_index_scan_mixed) find the class of a packet: class[stream].
+VBMD_HD int vbmi_stream_of(const int *first, int n, long long k)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (first[mid] <= k) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // One stream, packet after packet from a fresh state, as vbmd_index_stream does it.  status [n] is given; begin [n]
 // holds W on entry.
 template <int HS>
@@ -145,11 +159,18 @@ VBMD_HD void vbmi_chunk(const int *bs, long long left, const int *status, const 
 
 // ---- launches (decode_index.hip) -------------------------------------------------------------------------------------
 #if defined(__HIPCC__) || defined(__HIP__)
+struct vbmd_class;                   // decode_kernels.h
 // status and W (into begin) of packets [0, P) of the CSR
 int vbmd_launch_index_head(const vbmd_setup *d_setup, long long P, const uint8_t *d_data, const long long *d_offsets,
                            long long data_bytes, int *d_status, int *d_begin, hipStream_t q);
+// the same for packets [d_first[0], d_first[nstreams]) of streams of a mixed decoder's classes: d_first [nstreams + 1],
+// then the class of every stream [nstreams]; a packet takes the setup of its stream's class (vbmi_stream_of)
+int vbmd_launch_index_head_mixed(const vbmd_class *table, int nstreams, const int *d_first, long long k0, long long k1,
+                                 const uint8_t *d_data, const long long *d_offsets, long long data_bytes, int *d_status,
+                                 int *d_begin, hipStream_t q);
 // streams [0, nstreams): stream i is packets d_first[i] .. d_first[i + 1] of the arrays, whose begin [] holds W
-int vbmd_launch_index_scan(const vbmd_setup *d_setup, int halfrate, int nstreams, const int *d_first,
-                           const int *d_status, const long long *d_granulepos, const uint8_t *d_eos, int *d_begin,
+// table: null, or the class table of a mixed decoder: stream i is then of class d_first[nstreams + 1 + i]
+int vbmd_launch_index_scan(const vbmd_setup *d_setup, const vbmd_class *table, int halfrate, int nstreams,
+                           const int *d_first, const int *d_status, const long long *d_granulepos, const uint8_t *d_eos, int *d_begin,
                            int *d_end, long long *d_out_start, long long *d_out_end, long long *d_totals, hipStream_t q);
 #endif

@@ -7,8 +7,11 @@
 // No LDS, no scratch, no block-wide barrier: the four wavefronts of a block work on four streams on their own.
 #include <hip/hip_runtime.h>
 #include <climits>
+#include <string>
+#include <vector>
 
 #include "decode_index.h"
+#include "decode_kernels.h"
 #include "decode_setup.h"
 #include "vbm_internal.h"
 #include "vorbis_mi355x.h"
@@ -82,28 +85,37 @@ struct vbmi_host_lanes {               // the same on the CPU: 64 values per qua
     static vbmi_state last(const vbmi_state (&a)[64]) { return a[63]; }
 };
 
-__global__ void __launch_bounds__(256) k_index_head(const vbmd_setup *s, long long P, const uint8_t *data,
+// MX: packets [k0, P) are those of the n streams of first [n + 1], whose classes [n] lie behind it; a lane finds its
+// packet's stream by a search in first (vbmi_stream_of), hence its class's setup in the table
+template <bool MX>
+__global__ void __launch_bounds__(256) k_index_head(const vbmd_setup *s, const vbmd_class *table, const int *first,
+                                                    int n, long long k0, long long P, const uint8_t *data,
                                                     const long long *offsets, long long data_bytes, int *status,
                                                     int *begin)
 {
     const long long stride = (long long)gridDim.x * 256;
-    for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < P; k += stride) {
+    for (long long k = k0 + (long long)blockIdx.x * 256 + threadIdx.x; k < P; k += stride) {
         int W;
+        if (MX) s = table[first[n + 1 + vbmi_stream_of(first, n, k)]].s;
         status[k] = vbmi_head(*s, data, offsets, data_bytes, k, W);
         begin[k] = W;
     }
 }
 
-template <int HS>
-__global__ void __launch_bounds__(256) k_index_scan(const vbmd_setup *s, int nstreams, const int *first,
-                                                    const int *status, const long long *granulepos, const uint8_t *eos,
-                                                    int *begin, int *end, long long *out_start, long long *out_end,
+// MX: stream i takes its block sizes from the class first[nstreams + 1 + i] of the table, so the four wavefronts of a
+// block may scan four streams of four classes
+template <int HS, bool MX>
+__global__ void __launch_bounds__(256) k_index_scan(const vbmd_setup *s, const vbmd_class *table, int nstreams,
+                                                    const int *first, const int *status,
+                                                    const long long *granulepos, const uint8_t *eos, int *begin,
+                                                    int *end, long long *out_start, long long *out_end,
                                                     long long *totals)
 {
     const int lane = threadIdx.x & 63;
-    const int *bs = s->blocksizes;
+    const int *bs = MX ? nullptr : s->blocksizes;
     const int nwaves = gridDim.x * 4;
     for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < nstreams; i += nwaves) {      // uniform over the wavefront
+        if (MX) bs = table[first[nstreams + 1 + i]].s->blocksizes;
         const long long a = first[i], n = first[i + 1] - a;
         const long long *gp = granulepos ? granulepos + a : nullptr;
         const uint8_t *eo = eos ? eos + a : nullptr;
@@ -147,25 +159,75 @@ int vbmd_launch_index_head(const vbmd_setup *d_setup, long long P, const uint8_t
 {
     if (P <= 0) return 0;
     const long long blocks = (P + 255) / 256;
-    hipLaunchKernelGGL(k_index_head, dim3((unsigned)(blocks < kHeadBlocks ? blocks : kHeadBlocks)), dim3(256), 0, q,
-                       d_setup, P, d_data, d_offsets, data_bytes, d_status, d_begin);
+    hipLaunchKernelGGL(k_index_head<false>, dim3((unsigned)(blocks < kHeadBlocks ? blocks : kHeadBlocks)), dim3(256), 0,
+                       q, d_setup, nullptr, nullptr, 0, 0, P, d_data, d_offsets, data_bytes, d_status, d_begin);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int vbmd_launch_index_scan(const vbmd_setup *d_setup, int halfrate, int nstreams, const int *d_first,
-                           const int *d_status, const long long *d_granulepos, const uint8_t *d_eos, int *d_begin,
+int vbmd_launch_index_head_mixed(const vbmd_class *table, int nstreams, const int *d_first, long long k0, long long k1,
+                                 const uint8_t *d_data, const long long *d_offsets, long long data_bytes, int *d_status,
+                                 int *d_begin, hipStream_t q)
+{
+    if (k1 <= k0 || nstreams <= 0) return 0;
+    const long long blocks = (k1 - k0 + 255) / 256;
+    hipLaunchKernelGGL(k_index_head<true>, dim3((unsigned)(blocks < kHeadBlocks ? blocks : kHeadBlocks)), dim3(256), 0,
+                       q, nullptr, table, d_first, nstreams, k0, k1, d_data, d_offsets, data_bytes, d_status, d_begin);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int vbmd_launch_index_scan(const vbmd_setup *d_setup, const vbmd_class *table, int halfrate, int nstreams,
+                           const int *d_first, const int *d_status, const long long *d_granulepos, const uint8_t *d_eos, int *d_begin,
                            int *d_end, long long *d_out_start, long long *d_out_end, long long *d_totals, hipStream_t q)
 {
     if (nstreams <= 0) return 0;
     const int blocks = (nstreams + 3) / 4;
     const dim3 grid((unsigned)(blocks < kScanBlocks ? blocks : kScanBlocks));
-    if (halfrate)
-        hipLaunchKernelGGL(k_index_scan<1>, grid, dim3(256), 0, q, d_setup, nstreams, d_first, d_status, d_granulepos,
-                           d_eos, d_begin, d_end, d_out_start, d_out_end, d_totals);
-    else
-        hipLaunchKernelGGL(k_index_scan<0>, grid, dim3(256), 0, q, d_setup, nstreams, d_first, d_status, d_granulepos,
-                           d_eos, d_begin, d_end, d_out_start, d_out_end, d_totals);
+    const auto kernel = halfrate ? (table ? k_index_scan<1, true> : k_index_scan<1, false>)
+                                 : (table ? k_index_scan<0, true> : k_index_scan<0, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, q, d_setup, table, nstreams, d_first, d_status, d_granulepos, d_eos,
+                       d_begin, d_end, d_out_start, d_out_end, d_totals);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// the host twin over the streams of nclasses setups; classes null: every stream is of setups[0]
+static int host_index_scan(int nclasses, const vbm_decode_setup *const *setups, int halfrate, int nstreams,
+                           const long long *stream_packets, const int *classes, const uint8_t *data,
+                           const long long *offsets, long long data_bytes, const long long *granulepos,
+                           const uint8_t *eos, int *status, int *begin, int *end, long long *out_start,
+                           long long *totals)
+{
+    if (halfrate != 0 && halfrate != 1) { g_vbm_err = "halfrate must be 0 or 1"; return VBM_EINVAL; }
+    if (nclasses <= 0 || !setups || nstreams <= 0 || !stream_packets || data_bytes < 0 || (data_bytes > 0 && !data) ||
+        !offsets || !totals)
+        return VBM_EINVAL;
+    if (stream_packets[0] != 0) { g_vbm_err = "stream_packets[0] must be 0"; return VBM_EINVAL; }
+    for (int i = 0; i < nstreams; i++)
+        if (stream_packets[i + 1] < stream_packets[i]) { g_vbm_err = "stream_packets must not decrease"; return VBM_EINVAL; }
+    const long long P = stream_packets[nstreams];
+    if (P >= INT_MAX) { g_vbm_err = "more than 2^31 - 2 packets in one index"; return VBM_EINVAL; }
+    if (P > 0 && (!status || !begin || !end || !out_start)) return VBM_EINVAL;
+    for (int c = 0; c < nclasses; c++)
+        if (!setups[c]) return VBM_EINVAL;
+    for (int i = 0; classes && i < nstreams; i++)
+        if (classes[i] < 0 || classes[i] >= nclasses) {
+            g_vbm_err = "stream " + std::to_string(i) + ": class id " + std::to_string(classes[i]) + " is not in the table";
+            return VBM_EINVAL;
+        }
+    // the kernels' lookup: a packet's stream by vbmi_stream_of in the int table of first packets, then its class
+    std::vector<int> first(stream_packets, stream_packets + nstreams + 1);
+    for (long long k = 0; k < P; k++) {
+        const vbm_decode_setup *ds = setups[classes ? classes[vbmi_stream_of(first.data(), nstreams, k)] : 0];
+        status[k] = vbmi_head(ds->s, data, offsets, data_bytes, k, begin[k]);
+    }
+    for (int i = 0; i < nstreams; i++) {
+        const long long a = stream_packets[i], n = stream_packets[i + 1] - a;
+        const long long *gp = granulepos ? granulepos + a : nullptr;
+        const uint8_t *eo = eos ? eos + a : nullptr;
+        const int *bs = setups[classes ? classes[i] : 0]->s.blocksizes;
+        if (halfrate) host_scan_stream<1>(bs, n, status + a, gp, eo, begin + a, end + a, out_start + a, totals + i);
+        else host_scan_stream<0>(bs, n, status + a, gp, eo, begin + a, end + a, out_start + a, totals + i);
+    }
+    return VBM_OK;
 }
 
 extern "C" int vbm_host_decode_index_scan(const vbm_decode_setup *ds, int halfrate, int nstreams,
@@ -174,22 +236,23 @@ extern "C" int vbm_host_decode_index_scan(const vbm_decode_setup *ds, int halfra
                                           const uint8_t *eos, int *status, int *begin, int *end, long long *out_start,
                                           long long *totals)
 {
-    if (halfrate != 0 && halfrate != 1) { g_vbm_err = "halfrate must be 0 or 1"; return VBM_EINVAL; }
-    if (!ds || nstreams <= 0 || !stream_packets || data_bytes < 0 || (data_bytes > 0 && !data) || !offsets || !totals)
+    if (!ds) {
+        if (halfrate != 0 && halfrate != 1) g_vbm_err = "halfrate must be 0 or 1";
         return VBM_EINVAL;
-    if (stream_packets[0] != 0) { g_vbm_err = "stream_packets[0] must be 0"; return VBM_EINVAL; }
-    for (int i = 0; i < nstreams; i++)
-        if (stream_packets[i + 1] < stream_packets[i]) { g_vbm_err = "stream_packets must not decrease"; return VBM_EINVAL; }
-    const long long P = stream_packets[nstreams];
-    if (P >= INT_MAX) { g_vbm_err = "more than 2^31 - 2 packets in one index"; return VBM_EINVAL; }
-    if (P > 0 && (!status || !begin || !end || !out_start)) return VBM_EINVAL;
-    for (long long k = 0; k < P; k++) status[k] = vbmi_head(ds->s, data, offsets, data_bytes, k, begin[k]);
-    for (int i = 0; i < nstreams; i++) {
-        const long long a = stream_packets[i], n = stream_packets[i + 1] - a;
-        const long long *gp = granulepos ? granulepos + a : nullptr;
-        const uint8_t *eo = eos ? eos + a : nullptr;
-        if (halfrate) host_scan_stream<1>(ds->s.blocksizes, n, status + a, gp, eo, begin + a, end + a, out_start + a, totals + i);
-        else host_scan_stream<0>(ds->s.blocksizes, n, status + a, gp, eo, begin + a, end + a, out_start + a, totals + i);
     }
-    return VBM_OK;
+    return host_index_scan(1, &ds, halfrate, nstreams, stream_packets, nullptr, data, offsets, data_bytes, granulepos,
+                           eos, status, begin, end, out_start, totals);
+}
+
+extern "C" int vbm_host_decode_index_scan_mixed(int nclasses, const vbm_decode_setup *const *setups, int halfrate,
+                                                int nstreams, const long long *stream_packets,
+                                                const int *stream_classes, const uint8_t *data,
+                                                const long long *offsets, long long data_bytes,
+                                                const long long *granulepos, const uint8_t *eos, int *status,
+                                                int *begin, int *end, long long *out_start, long long *totals)
+{
+    if (halfrate != 0 && halfrate != 1) { g_vbm_err = "halfrate must be 0 or 1"; return VBM_EINVAL; }
+    if (!stream_classes) return VBM_EINVAL;
+    return host_index_scan(nclasses, setups, halfrate, nstreams, stream_packets, stream_classes, data, offsets,
+                           data_bytes, granulepos, eos, status, begin, end, out_start, totals);
 }

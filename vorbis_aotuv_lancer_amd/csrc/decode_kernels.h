@@ -60,8 +60,9 @@ int vbmd_launch_runs(const vbmd_launch &L, int nruns, const int *runtab, const l
                      int *run_samples, int *samples, hipStream_t q);
 // ranges (vbm_synthesis_ranges): rtab is the piece table (k_range_rows in decode_kernels.hip); rows: [nsb] store
 // packet of each row; pk_begin / pk_end / out_start: the store's index; runtab: one readable int per output row
-int vbmd_launch_unpack_rows(const vbmd_launch &L, int npieces, const int *rtab, int *rows, const uint8_t *data,
-                            const long long *offsets, long long data_bytes, hipStream_t q);
+// mixed: the pieces' classes [npieces] lie behind rtab, and rcls (L.M.rcls) gets the class of every row
+int vbmd_launch_unpack_rows(const vbmd_launch &L, int npieces, const int *rtab, int *rows, int *rcls,
+                            const uint8_t *data, const long long *offsets, long long data_bytes, hipStream_t q);
 int vbmd_launch_ranges(const vbmd_launch &L, int npieces, const int *rtab, const int *rows, const int *pk_begin,
                        const int *pk_end, const long long *out_start, const int *runtab, int *plan, float *pcm,
                        long pcm_stride, hipStream_t q);

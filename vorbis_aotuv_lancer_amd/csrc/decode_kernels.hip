@@ -23,7 +23,8 @@
 // Ranges (vbm_synthesis_ranges): rows are pieces of a range store's streams, each a pre-roll packet and the packets
 // after it.  k_range_rows maps rows to store packets, k_unpack_rows unpacks them from the store, k_spectrum and
 // k_imdct* are the same launches, k_range_plan writes k_run_plan's entries from the store's index and k_overlap_runs
-// runs unchanged.  No stream state is read or written.
+// runs unchanged.  No stream state is read or written.  On a mixed decoder k_range_rows<true> also writes each row's
+// class (its piece's, from the piece table) into the rcls column, and the rest of the chain is the <MX = true> one.
 //
 // Half rate (vbm_decoder_create_halfrate; the reference's vorbis_synthesis_halfrate, lib/synthesis.c:166-179): unpack and
 // spectrum are the same launches at the full block size; k_imdct<blocksizes[W] / 2> transforms the lower half of each
@@ -598,8 +599,11 @@ void k_run_commit(const vbmd_setup *__restrict__ s, vbmd_mixed M, int nruns, con
 // Ranges (vbm_synthesis_ranges).  A piece is a pre-roll packet of the store followed by `count` consecutive packets;
 // its rows are contiguous in the call.  rtab: row starts [npieces + 1], then per piece {output row, pre-roll packet,
 // first packet, window start (low, high 32 bits), window length}.  One lane per piece: row -> store packet.
+// MX: the pieces' classes [npieces] (the class of each piece's stream, from the store's class column) lie behind the
+// table, and every row of a piece gets its piece's class in rcls, the column the row kernels read.
+template <bool MX>
 __global__ __launch_bounds__(64)
-void k_range_rows(int npieces, const int *__restrict__ rtab, int *__restrict__ rows)
+void k_range_rows(int npieces, const int *__restrict__ rtab, int *__restrict__ rows, int *__restrict__ rcls)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npieces) return;
@@ -607,11 +611,16 @@ void k_range_rows(int npieces, const int *__restrict__ rtab, int *__restrict__ r
     const int *pc = rtab + npieces + 1 + 6 * (long)p;
     rows[k0] = pc[1];
     for (int k = k0 + 1; k < k1; k++) rows[k] = pc[2] + (k - k0 - 1);
+    if (MX) {
+        const int c = rtab[7 * (long)npieces + 1 + p];
+        for (int k = k0; k < k1; k++) rcls[k] = c;
+    }
 }
 
 // k_unpack_csr with the bytes of row k taken from the store's packet rows[k]
+template <bool MX>
 __global__ __launch_bounds__(64)
-void k_unpack_rows(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob, int nsb,
+void k_unpack_rows(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__ blob, vbmd_mixed M, int nsb,
                    const int *__restrict__ rows, const uint8_t *__restrict__ data,
                    const long long *__restrict__ offsets, long long data_bytes, int *__restrict__ info,
                    int *__restrict__ fit, int *__restrict__ flags, float *__restrict__ res, long half,
@@ -624,14 +633,15 @@ void k_unpack_rows(const vbmd_setup *__restrict__ s, const uint8_t *__restrict__
     long long b = offsets[j], e = offsets[j + 1];
     b = b < 0 ? 0 : b > data_bytes ? data_bytes : b;
     e = e < b ? b : e > data_bytes ? data_bytes : e;
-    unpack_row<false, 2, false>(s, blob, vbmd_mixed(), k, nsb, data + b, (long)(e - b), info, fit, flags, res, half, cls,
-                         status, nullptr, lists, counts);
+    unpack_row<MX, 2, false>(s, blob, M, k, nsb, data + b, (long)(e - b), info, fit, flags, res, half, cls, status,
+                             nullptr, lists, counts);
 }
 
 // One lane per piece: k_run_plan's plan entries, with begin / end / out_start from the store's index instead of the
 // carried granulepos state.  The pre-roll row writes nothing (end = 0); every later valid row writes the part of
 // [out_start, out_start + end - begin) that lies in the piece's window, at its offset in the range's output row.
-// Its previous valid row is always inside the piece, so k_overlap_runs never reads a stream's tail.
+// Its previous valid row is always inside the piece, so k_overlap_runs never reads a stream's tail, and of the piece's
+// class, so the plan needs no class.
 __global__ __launch_bounds__(64)
 void k_range_plan(int npieces, const int *__restrict__ rtab, const int *__restrict__ rows,
                   const int *__restrict__ status, const int *__restrict__ info, const int *__restrict__ pk_begin,
@@ -801,13 +811,15 @@ int vbmd_launch_runs(const vbmd_launch &L, int nruns, const int *runtab, const l
     return last_err();
 }
 
-int vbmd_launch_unpack_rows(const vbmd_launch &L, int npieces, const int *rtab, int *rows, const uint8_t *data,
-                            const long long *offsets, long long data_bytes, hipStream_t q)
+int vbmd_launch_unpack_rows(const vbmd_launch &L, int npieces, const int *rtab, int *rows, int *rcls,
+                            const uint8_t *data, const long long *offsets, long long data_bytes, hipStream_t q)
 {
     if (L.nsb <= 0) return 0;
-    hipLaunchKernelGGL(k_range_rows, dim3((npieces + 63) / 64), dim3(64), 0, q, npieces, rtab, rows);
+    const auto rows_kernel = PICK_MX(k_range_rows);
+    hipLaunchKernelGGL(rows_kernel, dim3((npieces + 63) / 64), dim3(64), 0, q, npieces, rtab, rows, rcls);
     if (last_err()) return -2;
-    hipLaunchKernelGGL(k_unpack_rows, dim3((L.nsb + 63) / 64), dim3(64), 0, q, L.s, L.blob, L.nsb, rows, data, offsets,
+    const auto kernel = PICK_MX(k_unpack_rows);
+    hipLaunchKernelGGL(kernel, dim3((L.nsb + 63) / 64), dim3(64), 0, q, L.s, L.blob, L.M, L.nsb, rows, data, offsets,
                        data_bytes, L.info, L.fit, L.flags, L.res, L.half, L.cls, L.status, L.lists, L.counts);
     return last_err();
 }
@@ -820,7 +832,7 @@ int vbmd_launch_ranges(const vbmd_launch &L, int npieces, const int *rtab, const
     hipLaunchKernelGGL(k_range_plan, dim3((npieces + 63) / 64), dim3(64), 0, q, npieces, rtab, rows, L.status, L.info,
                        pk_begin, pk_end, out_start, plan);
     if (last_err()) return -2;
-    const auto kernel = L.hs ? k_overlap_runs<1, false> : k_overlap_runs<0, false>;     // no range calls on mixed decoders
+    const auto kernel = PICK_HS_MX(k_overlap_runs);
     hipLaunchKernelGGL(kernel, dim3(L.nsb), dim3(256), 0, q, L.s, L.M, runtab, L.status, L.info, plan, L.imdct, L.n1,
                        L.win0, L.win1, L.tail, pcm, pcm_stride, L.ohalf);
     return last_err();

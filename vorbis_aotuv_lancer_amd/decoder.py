@@ -285,8 +285,12 @@ class MixedDecoder(Decoder):
     stream's result bit for bit that of a Decoder of its class.  Their PCM rows are the caps': pcm is [n, max_channels,
     stride], and row r uses pcm[r, :channels_of([id])[0], :samples]; the rest is not written.  A call that lists an
     unbound stream is a VbmError.  .channels is max_channels and .row the most samples a packet of the largest block
-    returns; rates and channel counts are per stream: rate_of(ids), channels_of(ids).  Range stores, synthesis_ranges,
-    the device index and fetch are not built for it (VbmError)."""
+    returns; rates and channel counts are per stream: rate_of(ids), channels_of(ids).
+    Random access: RangeStore(md, streams, classes=[class id per stream]) (and RangeStore.from_device,
+    decode_index_device with classes=) keeps streams of any mix of classes; the store's classes are its own, not bind's.
+    synthesis_ranges(store, ids, starts, lengths) then returns pcm [n, max_channels, stride], of which range r uses
+    the channels of its stream's class and got[r] samples; the rest is not written.  One launch chain per sub-call,
+    whatever the classes.  fetch is not built for it (VbmError)."""
 
     def __init__(self, nstreams, max_batch, max_classes=64, max_channels=8, max_blocksize=4096, halfrate=False):
         self.dsetup, self.blocksizes, self.rate = None, None, None
@@ -402,34 +406,60 @@ def _stream_packets(stream_packets, P):
     return np.ascontiguousarray(first)
 
 
-def decode_index_device(decoder, data, offsets, granulepos=None, eos=None, stream_packets=None):
+def _stream_classes(classes, nstreams):
+    """None, or one class id per stream -> int32 [nstreams], contiguous"""
+    if classes is None:
+        return None
+    cls = _i32(classes)
+    if cls.ndim != 1 or len(cls) != nstreams:
+        raise ValueError(f"classes needs one class id per stream: {nstreams}, has {cls.size}")
+    return cls
+
+
+def decode_index_device(decoder, data, offsets, granulepos=None, eos=None, stream_packets=None, classes=None):
     """The index of demuxed streams, built on the device (vbm_decode_index_device) at the decoder's rate: data uint8
     [bytes], offsets int64 [P+1], granulepos int64 [P] / eos uint8 [P] or None, CUDA tensors holding one CSR over the
     packets of all streams (a DemuxBatch's payload, offsets, granulepos and eos); stream_packets: host ints [S+1], the
     first packet of every stream and P (None: one stream).
     -> (status int32 [P], begin int32 [P], end int32 [P], out_start int64 [P], totals int64 [S]), device tensors;
     end - begin, out_start and totals are decode_index's samples, out_start and total of each stream alone.  Only
-    enqueues work on the current stream."""
+    enqueues work on the current stream.  classes: with a MixedDecoder, the class id of every stream (required;
+    vbm_decode_index_device_mixed): each stream's index is that of its own class.  With a Decoder it is an error."""
     offsets, P, first, gp, eo = _csr_t(data, offsets, granulepos, eos, stream_packets)
+    cls = _stream_classes(classes, len(first) - 1)
     dev = offsets.device
     status, begin, end = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
     out_start = torch.empty(P, dtype=torch.int64, device=dev)
     totals = torch.empty(len(first) - 1, dtype=torch.int64, device=dev)
-    check(lib.vbm_decode_index_device(decoder._h, len(first) - 1, first.ctypes.data, _ptr(data, data.numel()),
-                                      offsets.data_ptr(), data.numel(), _ptr(gp, P), _ptr(eo, P), status.data_ptr(),
-                                      begin.data_ptr(), end.data_ptr(), out_start.data_ptr(), totals.data_ptr(),
-                                      decoder._stream()), "vbm_decode_index_device")
+    name, extra = ("vbm_decode_index_device", ()) if cls is None else ("vbm_decode_index_device_mixed", (cls.ctypes.data,))
+    check(getattr(lib, name)(decoder._h, len(first) - 1, first.ctypes.data, *extra, _ptr(data, data.numel()),
+                             offsets.data_ptr(), data.numel(), _ptr(gp, P), _ptr(eo, P), status.data_ptr(),
+                             begin.data_ptr(), end.data_ptr(), out_start.data_ptr(), totals.data_ptr(),
+                             decoder._stream()), name)
     decoder._hold_index_inputs(data, offsets, gp, eo)
     return status, begin, end, out_start, totals
 
 
-def decode_index_scan_host(dsetup, data, offsets, granulepos=None, eos=None, stream_packets=None, halfrate=False):
+def decode_index_scan_host(dsetup, data, offsets, granulepos=None, eos=None, stream_packets=None, halfrate=False,
+                           classes=None):
     """The CPU twin of decode_index_device (vbm_host_decode_index_scan; no device needed), on numpy arrays.
+    classes: dsetup is then a list of DecodeSetups and classes the index into it of every stream
+    (vbm_host_decode_index_scan_mixed, the twin of the index on a MixedDecoder).
     -> (status int32 [P], begin int32 [P], end int32 [P], out_start int64 [P], totals int64 [S])"""
     data, offsets, P, gp, eo = _csr_np(data, offsets, granulepos, eos)
     first = _stream_packets(stream_packets, P)
     status, begin, end = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
     out_start, totals = np.zeros(P, np.int64), np.zeros(len(first) - 1, np.int64)
+    if classes is not None:
+        cls = _stream_classes(classes, len(first) - 1)
+        setups = (C.c_void_p * max(len(dsetup), 1))(*[ds._h.value for ds in dsetup])
+        check(lib.vbm_host_decode_index_scan_mixed(len(dsetup), setups, int(bool(halfrate)), len(first) - 1,
+                                                   first.ctypes.data, cls.ctypes.data, _ptr(data, len(data)),
+                                                   offsets.ctypes.data, len(data), _ptr(gp), _ptr(eo),
+                                                   status.ctypes.data, begin.ctypes.data, end.ctypes.data,
+                                                   out_start.ctypes.data, totals.ctypes.data),
+              "vbm_host_decode_index_scan_mixed")
+        return status, begin, end, out_start, totals
     check(lib.vbm_host_decode_index_scan(dsetup._h, int(bool(halfrate)), len(first) - 1, first.ctypes.data,
                                          _ptr(data, len(data)), offsets.ctypes.data, len(data), _ptr(gp), _ptr(eo),
                                          status.ctypes.data, begin.ctypes.data, end.ctypes.data, out_start.ctypes.data,
@@ -441,13 +471,15 @@ class RangeStore(_Handle):
     """The packets of many streams of one Decoder's headers in device memory, with their index, for
     Decoder.synthesis_ranges.  streams: (data, offsets, granulepos, eos) tuples as demux_ogg returns them (granulepos
     / eos may be None).  .totals: int64 [nstreams], each stream's linear decode length (ov_pcm_total), at the
-    decoder's rate: .halfrate is the decoder's."""
+    decoder's rate: .halfrate is the decoder's.  classes: with a MixedDecoder, the class id of every stream (required;
+    the streams may then be of any mix of the decoder's classes, and .classes keeps them); with a Decoder an error."""
     _destroy = "vbm_range_store_destroy"
 
-    def __init__(self, decoder, streams):
+    def __init__(self, decoder, streams, classes=None):
         streams = list(streams)
         if not streams:
             raise ValueError("a range store needs at least one stream")
+        cls = _stream_classes(classes, len(streams))
         datas, offs, gps, eoss, first, base = [], [np.zeros(1, np.int64)], [], [], [0], 0
         for data, o, gp, eo in streams:
             data = np.asarray(data, dtype=np.uint8).ravel()
@@ -463,26 +495,29 @@ class RangeStore(_Handle):
         offsets = np.ascontiguousarray(np.concatenate(offs))
         gp = np.ascontiguousarray(np.concatenate(gps))
         eo = np.ascontiguousarray(np.concatenate(eoss))
-        self._create(decoder, np.ascontiguousarray(np.asarray(first, np.int64)), "vbm_range_store_create",
+        self._create(decoder, np.ascontiguousarray(np.asarray(first, np.int64)), cls, "vbm_range_store_create",
                      _ptr(data, len(data)), offsets.ctypes.data, len(data), gp.ctypes.data, eo.ctypes.data)
 
-    def _create(self, decoder, first, create, *csr):
-        """the tail of both constructors: the fields, the C store from create(..., stream_packets, *csr), its totals"""
+    def _create(self, decoder, first, cls, create, *csr):
+        """the tail of both constructors: the fields, the C store from create(..., stream_packets, *csr), or with the
+        streams' classes from create_mixed(..., stream_packets, classes, *csr); its totals"""
         self.decoder, self.nstreams, self.halfrate = decoder, len(first) - 1, decoder.halfrate
-        self.packets = first
+        self.packets, self.classes = first, cls
         self._h = C.c_void_p()
+        if cls is not None:
+            create, csr = create + "_mixed", (cls.ctypes.data,) + csr
         check(getattr(lib, create)(C.byref(self._h), decoder._h, self.nstreams, first.ctypes.data, *csr), create)
         self.totals = np.zeros(self.nstreams, np.int64)
         check(lib.vbm_range_store_totals(self._h, self.totals.ctypes.data), "vbm_range_store_totals")
 
     @classmethod
-    def from_device(cls, decoder, payload, offsets=None, granulepos=None, eos=None, stream_packets=None):
+    def from_device(cls, decoder, payload, offsets=None, granulepos=None, eos=None, stream_packets=None, classes=None):
         """The same store from a CSR that is already on the device (vbm_range_store_create_device): payload uint8
         [bytes], offsets int64 [P+1], granulepos int64 [P] / eos uint8 [P] or None as CUDA tensors, stream_packets host
         ints [S+1] (the first packet of every stream, and P).  A stream.DemuxBatch may be given in place of payload,
         alone: every file of it is a stream (a failed file an empty one).  The index is built by device kernels and
         no packet byte crosses to the host; the store keeps its own copies, so the tensors are free when this
-        returns.  Waits for the device once."""
+        returns.  Waits for the device once.  classes: as the constructor's."""
         if offsets is None:
             b = payload
             payload, offsets, granulepos, eos = b.payload, b.offsets, b.granulepos, b.eos
@@ -491,7 +526,8 @@ class RangeStore(_Handle):
             raise ValueError("offsets needs at least one entry, and stream_packets must be given")
         offsets, P, first, gp, eo = _csr_t(payload, offsets, granulepos, eos, stream_packets)
         self = cls.__new__(cls)
-        self._create(decoder, first, "vbm_range_store_create_device", _ptr(payload, payload.numel()),
+        self._create(decoder, first, _stream_classes(classes, len(first) - 1), "vbm_range_store_create_device",
+                     _ptr(payload, payload.numel()),
                      offsets.data_ptr(), payload.numel(), _ptr(gp, P), _ptr(eo, P), decoder._stream())
         return self
 
@@ -529,6 +565,25 @@ def _raise_failed(batch, names):
                            "(vbm_ogg_demux on the file alone names the page)")
 
 
+def header_classes(headers):
+    """Per-file header triples -> (class id of every file, the first file of every class, max channels, max block
+    size): files are of one class when their identification and setup packets are byte-equal, and classes are numbered
+    in order of first appearance.  The caps are read from the identification packets (channels: byte 11, the two block
+    size exponents: byte 28).  Pure host code: no library call, no device."""
+    ids, firsts, by = [], [], {}
+    for i, h in enumerate(headers):
+        key = (bytes(h[0]), bytes(h[2]))
+        if key not in by:
+            by[key] = len(firsts)
+            firsts.append(i)
+        ids.append(by[key])
+    idents = [bytes(headers[i][0]) for i in firsts]
+    for i, ident in zip(firsts, idents):
+        if len(ident) < 30 or ident[:7] != b"\x01vorbis":
+            raise ValueError(f"file {i}: not a Vorbis identification header")
+    return ids, firsts, max(x[11] for x in idents), max(1 << (x[28] >> 4) for x in idents)
+
+
 class OggIndex:
     """Random sample windows of many .ogg files (bytes or paths, one logical stream each, one set of headers: files
     whose identification or setup headers differ are a ValueError).  The files' packets and index stay in device
@@ -542,9 +597,17 @@ class OggIndex:
     (RangeStore.from_device) instead of file by file on the host; the index and every range are the same bit for
     bit.  multiplexed=True: the files may carry other streams beside the Vorbis one (stream.StreamSelector on the
     device with device_demux, stream.select_vorbis_stream on the host without); a file without a Vorbis stream is a
-    VbmError that says so."""
+    VbmError that says so.
+    one_decoder=True (as decode_ogg's): the files may be of any mix of header classes.  They are grouped by byte-equal
+    identification and setup headers (header_classes) and indexed in one store of one MixedDecoder, its caps the
+    largest channel count and block size among them; decode_ranges returns [n, max channels, L], range r in the
+    channels of its file and zeros elsewhere, and every clip of cut_ranges opens with its own file's header pages.
+    .file_channels and .file_rates: one entry per file (on every index).  With one_decoder, .channels is the largest
+    channel count, .rate the common output rate or None when the files' rates differ, and .setup is None (.setups:
+    one per class, .file_class: the class of every file)."""
 
-    def __init__(self, files, max_batch=4096, halfrate=False, device_demux=False, multiplexed=False):
+    def __init__(self, files, max_batch=4096, halfrate=False, device_demux=False, multiplexed=False,
+                 one_decoder=False):
         from .stream import _read_files, demux_ogg_device
         if max_batch < 2:
             raise ValueError("max_batch must be at least 2")
@@ -557,10 +620,36 @@ class OggIndex:
         else:
             demuxed = [_demux_host(name, _select_host(name, blob) if multiplexed else blob)
                        for name, blob in zip(names, blobs)]
-        self._open(b.headers if device_demux else [d[0] for d in demuxed], max_batch, halfrate)
-        self.store = (RangeStore.from_device(self.decoder, b) if device_demux
-                      else RangeStore(self.decoder, [d[1:] for d in demuxed]))
+        headers = b.headers if device_demux else [d[0] for d in demuxed]
+        classes = self._open_mixed(names, headers, max_batch, halfrate) if one_decoder else None
+        if not one_decoder:
+            self._open(headers, max_batch, halfrate)
+        self.store = (RangeStore.from_device(self.decoder, b, classes=classes) if device_demux
+                      else RangeStore(self.decoder, [d[1:] for d in demuxed], classes=classes))
         self.total_samples = self.store.totals
+
+    def _open_mixed(self, names, headers, max_batch, halfrate):
+        """any header classes -> .setups, .decoder (a MixedDecoder of their caps), the class of every file"""
+        cls, firsts, max_ch, max_bs = header_classes(headers)
+        for i in firsts:                                      # every setup is checked before any work is enqueued
+            rc = DecodeSetup.status(headers[i])
+            if rc:
+                raise VbmError(f"{names[i]}: unsupported or invalid Vorbis headers (code {rc}): "
+                               f"{lib.vbm_last_error().decode()}")
+        self.setup, self.setups = None, [DecodeSetup(headers[i]) for i in firsts]
+        self.decoder = MixedDecoder(1, max_batch, max_classes=len(firsts), max_channels=max_ch, max_blocksize=max_bs,
+                                    halfrate=halfrate)
+        for ds in self.setups:
+            self.decoder.add_class(ds)
+        self.halfrate = self.decoder.halfrate
+        self.file_class = np.asarray(cls, dtype=np.int32)
+        self.file_channels = np.asarray([self.setups[c].channels for c in cls], dtype=np.int64)
+        self.file_rates = np.asarray([output_rate(self.setups[c].rate, self.halfrate) for c in cls])
+        self.channels = int(self.file_channels.max())
+        self.rate = self.file_rates[0].item() if (self.file_rates == self.file_rates[0]).all() else None
+        self.headers = [[bytes(p) for p in h] for h in headers]
+        self._hdr_pages, self._cutter = {}, None
+        return cls
 
     def _open(self, headers, max_batch, halfrate):
         """one header class -> .setup, .decoder"""
@@ -572,6 +661,9 @@ class OggIndex:
         self.setup = DecodeSetup(h0)
         self.decoder = Decoder(self.setup, 1, max_batch, halfrate=halfrate)
         self.channels, self.rate, self.halfrate = self.setup.channels, self.decoder.rate, self.decoder.halfrate
+        self.setups, self.file_class = [self.setup], np.zeros(len(headers), np.int32)
+        self.file_channels = np.full(len(headers), self.channels, dtype=np.int64)
+        self.file_rates = np.full(len(headers), self.rate)
         self.headers = [[bytes(p) for p in h] for h in headers]     # per file; the comment packets are the files' own
         self._hdr_pages, self._cutter = {}, None
 
@@ -655,7 +747,8 @@ class OggIndex:
             self._cutter = None
         self.store.close()
         self.decoder.close()
-        self.setup.close()
+        for ds in self.setups:
+            ds.close()
 
 
 def _demux_files(files, device_demux, chained, multiplexed=False):
