@@ -8,9 +8,10 @@ import numpy as np
 import torch
 
 from tests import vorbis_model as vm
-from tests.test_decoder_model_cpu import fromdB
+from tests.decode_calls import FILL_PLAYER, batch_inputs, runs_inputs
+from tests.decode_packets import family as model_family
+from tests.decode_packets import fromdB
 
-FILL = -77.25            # what the output buffers hold before a call: not a sample value of any corpus stream
 SEQ = vm.SEQUENCES[0]    # short->short, short->long, long->short and long->long
 
 
@@ -58,7 +59,6 @@ SILENT = "pair_2048_2048_end_le_begin"      # the family whose residue range is 
 def family(k):
     """vm.CORPUS[k] as a Class, with .name, .setup (the dict), .packets (the bytes of vm.corpus_packets) and per packet
     the model's .status and .info, and .loud: its model spectrum is nonzero"""
-    from tests.test_decoder_model_cpu import family as model_family
     setup, _, headers, _, rows, _, _ = model_family(k)
     c = Class(headers, setup["channels"], tuple(setup["blocksizes"]), vm.Model(setup, fromdB()))
     c.name, c.setup = vm.CORPUS[k][0], setup
@@ -193,40 +193,12 @@ def caps_script(n):
     return classes, script, of
 
 
-def ogg_packets(blob):
-    """an .ogg file -> (headers, [(packet, granulepos, eos)])"""
-    import vorbis_aotuv_lancer_amd as v
-    headers, data, offsets, gp, eos = v.demux_ogg(blob)
-    data = np.asarray(data, np.uint8).tobytes()
-    return headers, [(data[int(a):int(b)], int(g), int(e)) for a, b, g, e in zip(offsets[:-1], offsets[1:], gp, eos)]
-
-
 # ---- scripts --------------------------------------------------------------------------------------------------------
 # A script is a list of events:
 #   ("add", c)                        class c of the test's class list joins the mixed decoder's table
 #   ("bind", [stream ids], [c ...])   the streams are of these classes from here on, and restart
 #   ("batch", [(stream id, (packet, granulepos, eos)) ...])                 one synthesis_batch call
 #   ("runs", [(stream id, [(packet, granulepos, eos[, gap]) ...]) ...])     one synthesis_runs call
-def _batch_inputs(rows, dev):
-    from tests.test_decoder_gpu import rows_tensor
-    pk, nb = rows_tensor([p[0] for _, p in rows], dev)
-    gp = torch.tensor([p[1] for _, p in rows], dtype=torch.int64, device=dev)
-    eo = torch.tensor([p[2] for _, p in rows], dtype=torch.uint8, device=dev)
-    return pk, nb, gp, eo
-
-
-def _runs_inputs(runs, dev):
-    flat = [p for _, r in runs for p in r]
-    data = np.frombuffer(b"".join(p[0] for p in flat), np.uint8).copy()
-    offs = np.zeros(len(flat) + 1, np.int64)
-    offs[1:] = np.cumsum([len(p[0]) for p in flat])
-    gap = np.array([p[3] if len(p) > 3 else 0 for p in flat], np.uint8)
-    up = lambda a: torch.from_numpy(a).to(dev)                       # noqa: E731
-    return (up(data) if len(data) else torch.zeros(0, dtype=torch.uint8, device=dev), up(offs),
-            up(np.array([p[1] for p in flat], np.int64)), up(np.array([p[2] for p in flat], np.uint8)),
-            up(gap) if gap.any() else None)
-
-
 class Player:
     """Runs a script.  Every input tensor is made before the first call and every output is read after the last one,
     so the calls follow each other with no host wait in between.  .result[stream id] is the list, one entry per call
@@ -241,9 +213,9 @@ class Player:
         prepared = []
         for ev in script:
             if ev[0] == "batch":
-                prepared.append(_batch_inputs(ev[1], self.dev))
+                prepared.append(batch_inputs([p for _, p in ev[1]], self.dev))
             elif ev[0] == "runs":
-                prepared.append(_runs_inputs(ev[1], self.dev))
+                prepared.append(runs_inputs([r for _, r in ev[1]], self.dev))
             else:
                 prepared.append(None)
         torch.cuda.synchronize()
@@ -262,7 +234,7 @@ class Player:
             samples, status = samples.cpu().tolist(), status.cpu().tolist()
             for r, (sid, ch) in enumerate(meta):
                 full = pcm[r]
-                assert np.all(full[ch:] == FILL) and np.all(full[:ch, n[r]:] == FILL), \
+                assert np.all(full[ch:] == FILL_PLAYER) and np.all(full[:ch, n[r]:] == FILL_PLAYER), \
                     f"stream {sid}: written outside its PCM"
                 self.result.setdefault(sid, []).append((full[:ch, :n[r]], samples[at[r]:at[r + 1]],
                                                         status[at[r]:at[r + 1]]))
@@ -271,7 +243,7 @@ class Player:
 
     def out(self, n, channels, stride, P=None):
         dev = self.dev
-        pcm = torch.full((n, channels, stride), FILL, dtype=torch.float32, device=dev)
+        pcm = torch.full((n, channels, stride), FILL_PLAYER, dtype=torch.float32, device=dev)
         ints = [torch.empty(k, dtype=torch.int32, device=dev) for k in ([n, n] if P is None else [n, P, P])]
         return (pcm, *ints)
 
@@ -374,7 +346,7 @@ class PerClass(Player):
         out = []
         for c in sorted({self.of[s] for s, _ in rows}):
             mine = [(s, r) for s, r in rows if self.of[s] == c]
-            sub = _batch_inputs(mine, self.dev) if kind == "batch" else _runs_inputs(mine, self.dev)
+            sub = (batch_inputs if kind == "batch" else runs_inputs)([r for _, r in mine], self.dev)
             stride = max([1] + [len(r) * self.row(c) for _, r in mine]) if kind == "runs" else None
             out += self.call_on(self.dec[c], kind, self.ids(c, [s for s, _ in mine]), mine, sub,
                                 [self.classes[c].ch] * len(mine), stride)

@@ -5,6 +5,7 @@ synthesis_ranges per class over the same windows of the same streams.  Every com
 import numpy as np
 
 from tests import decode_mixed_cases as M
+from tests.decode_packets import as_stream, join
 
 # classes that collide on transform sizes: 512 is the long block of one, both blocks of another and the short block of
 # a third; 4096 is both blocks of the widest class
@@ -12,22 +13,9 @@ COLLIDING = [(1, (256, 512)), (2, (512, 512)), (3, (512, 4096)), (7, (4096, 4096
 NPACKETS = 12
 
 
-def tuple_of(packets):
-    """[(packet, granulepos, eos)] -> (data, offsets, granulepos, eos) as demux_ogg returns a stream"""
-    data = np.frombuffer(b"".join(p[0] for p in packets), np.uint8).copy()
-    offs = np.zeros(len(packets) + 1, np.int64)
-    offs[1:] = np.cumsum([len(p[0]) for p in packets])
-    return (data, offs, np.array([p[1] for p in packets], np.int64).reshape(-1),
-            np.array([p[2] for p in packets], np.uint8).reshape(-1))
-
-
 def csr(streams):
     """[(class, packets)] -> (data, offsets, granulepos, eos, stream_packets) of all of them back to back"""
-    flat = [p for _, pk in streams for p in pk]
-    data, offs, gp, eo = tuple_of(flat)
-    first = np.zeros(len(streams) + 1, np.int64)
-    first[1:] = np.cumsum([len(pk) for _, pk in streams])
-    return data, offs, gp, eo, first
+    return join([as_stream(pk) for _, pk in streams])
 
 
 def range_streams():
@@ -62,7 +50,7 @@ def host_index(v, classes_ds, streams, halfrate):
     """per stream decode_index_scan_host with its class's setup -> [(status, begin, end, out_start, total)]"""
     out = []
     for c, pk in streams:
-        data, offs, gp, eo = tuple_of(pk)
+        data, offs, gp, eo = as_stream(pk)
         st, b, e, o, t = v.decode_index_scan_host(classes_ds[c], data, offs, gp, eo, halfrate=halfrate)
         out.append((st, b, e, o, int(t[0])))
     return out
@@ -112,9 +100,9 @@ def plan_calls(first, status, out_end, totals, cap, windows):
 
 
 def mixed_ranges(v, md, store, windows, dev, stride):
-    """one synthesis_ranges call of the mixed decoder into a FILL buffer -> (pcm tensor, got); nothing is awaited"""
+    """one synthesis_ranges call of the mixed decoder into a FILL_PLAYER buffer -> (pcm tensor, got); nothing is awaited"""
     import torch
-    pcm = torch.full((len(windows), md.channels, stride), M.FILL, dtype=torch.float32, device=dev)
+    pcm = torch.full((len(windows), md.channels, stride), M.FILL_PLAYER, dtype=torch.float32, device=dev)
     _, got = md.synthesis_ranges(store, [w[0] for w in windows], [w[1] for w in windows], [w[2] for w in windows],
                                  out=pcm)
     return pcm, got
@@ -130,7 +118,7 @@ class Yardstick:
             mine = [s for s, k in enumerate(self.of) if k == c]
             self.local.update({s: j for j, s in enumerate(mine)})
             self.dec[c] = v.Decoder(classes_ds[c], 1, cap, halfrate=halfrate)
-            self.store[c] = v.RangeStore(self.dec[c], [tuple_of(streams[s][1]) for s in mine])
+            self.store[c] = v.RangeStore(self.dec[c], [as_stream(streams[s][1]) for s in mine])
 
     def ranges(self, windows, dev, stride):
         """-> per window (pcm [channels, stride] numpy, got), each class's windows in one call of its own"""
@@ -140,7 +128,7 @@ class Yardstick:
             rows = [r for r, w in enumerate(windows) if self.of[w[0]] == c]
             if not rows:
                 continue
-            pcm = torch.full((len(rows), dec.channels, stride), M.FILL, dtype=torch.float32, device=dev)
+            pcm = torch.full((len(rows), dec.channels, stride), M.FILL_PLAYER, dtype=torch.float32, device=dev)
             _, got = dec.synthesis_ranges(self.store[c], [self.local[windows[r][0]] for r in rows],
                                           [windows[r][1] for r in rows], [windows[r][2] for r in rows], out=pcm)
             pending.append((rows, pcm, got))
@@ -157,14 +145,14 @@ class Yardstick:
 
 def same_ranges(pcm, got, want, channels):
     """the mixed call's (pcm [n, max channels, stride] numpy, got) against Yardstick.ranges' rows: got equal, the
-    class's channels equal over the full stride (so FILL is intact past got), the other channels all FILL"""
+    class's channels equal over the full stride (so the fill is intact past got), the other channels all fill"""
     written = 0
     for r, (wp, wg) in enumerate(want):
         ch = channels[r]
         assert int(got[r]) == wg, f"window {r}: got"
         assert wp.shape == (ch, pcm.shape[2])
         assert np.array_equal(pcm[r, :ch], wp), f"window {r}: PCM"
-        assert np.all(pcm[r, ch:] == M.FILL), f"window {r}: written past its channels"
-        assert np.all(wp[:, wg:] == M.FILL)
+        assert np.all(pcm[r, ch:] == M.FILL_PLAYER), f"window {r}: written past its channels"
+        assert np.all(wp[:, wg:] == M.FILL_PLAYER)
         written += wg
     return written

@@ -2,14 +2,13 @@
 (decode_index_scan_host's arrays) and OggStream, the host writer that test_stream_wrapper.py pins; the sources the
 cuts are taken from; the windows; and the C calls of the host twin."""
 import functools
-import os
 
 import numpy as np
 
-from tests.test_decode_index_cpu import G, split_dump, true_granules, with_bad_packets
+from tests.decode_packets import dump_packets, true_granules, with_bad_packets
 from tests.ogg_pages import parse_pages, random_bytes
 
-ECAP, ESHAPE, EINVAL = 1, 2, -131
+ECAP, ESHAPE = 1, 2
 SERIAL = 77                                               # of the sources
 DUMPS = {"2ch": (2, 44100, 0.5, "ref_scalar_2ch_44100_q05_20s.pkt", 150),
          "6ch": (6, 48000, 0.8, "ref_scalar_6ch_48000_q08_10s.pkt", 60)}
@@ -99,7 +98,7 @@ def dump_source(name):
     parts = name.split("-")
     ch, rate, q, golden, n = DUMPS[parts[0]]
     headers = v.header_packets(v.Setup(ch, rate, q))
-    packets = split_dump(open(os.path.join(G, golden), "rb").read())[:n]
+    packets = dump_packets(golden)[:n]
     variant = "plain"
     for p in parts[1:]:
         if p == "bad":

@@ -1,48 +1,24 @@
 """Gap marks in the decoder (vbm_synthesis_runs_gaps, Decoder.synthesis_runs(gap=...)) on the MI355X: a mark makes the
 stream lose count as vorbis_synthesis_blockin does when packets are out of sequence (lib/block.c:911-915), and nothing
-else.  Sample counts are checked against a numpy restatement of lib/block.c:1076-1140, PCM bit for bit against today's
-path on the same packet list without marks, and the live loop (resync OggFeed.push_all -> synthesis_runs) link by
-link."""
+else.  Sample counts are checked against the tests' one restatement of lib/block.c:907-915 and 1050-1161 (blockin in
+tests/decode_packets.py), PCM bit for bit against today's path on the same packet list without marks, and the live
+loop (resync OggFeed.push_all -> synthesis_runs) link by link."""
 import numpy as np
 import pytest
-import torch
 
 from tests import ogg_feed_resync_cases as R
+from tests.decode_calls import runs_inputs
+from tests.decode_packets import blockin
 from tests.signals import burst_signal
-from tests.test_decode_runs_gpu import csr
 
 pytestmark = pytest.mark.gpu
 
 
 def blockin_counts(bs, W, gp_in, eos, gap):
-    """lib/block.c:907-915 and 1076-1140 for a list of valid packets from a fresh stream -> samples returned per packet.
-    W: block flag per packet; gp_in / eos: the packets' granule positions and end flags; gap: out of sequence here."""
-    out, lW, count, pos = [], -1, -1, -1
-    for k in range(len(W)):
-        if gap[k]:
-            count = pos = -1
-        n = 0 if lW < 0 else bs[lW] // 4 + bs[W[k]] // 4
-        step = (0 if lW < 0 else bs[lW] // 4) + bs[W[k]] // 4
-        begin, end = 0, n
-        count = 0 if count == -1 else count + step
-        if pos == -1:
-            if gp_in[k] != -1:
-                pos = gp_in[k]
-                if count > pos:
-                    extra = max(count - gp_in[k], 0)
-                    if eos[k]:
-                        end -= min(extra, end - begin)
-                    else:
-                        begin = min(begin + extra, end)
-        else:
-            pos += step
-            if gp_in[k] != -1 and pos != gp_in[k]:
-                if pos > gp_in[k] and eos[k]:
-                    end -= max(min(pos - gp_in[k], end - begin), 0)
-                pos = gp_in[k]
-        out.append(end - begin)
-        lW = W[k]
-    return out
+    """tests/decode_packets.py's blockin for a list of valid packets from a fresh stream at full rate -> samples
+    returned per packet.  W: block flag per packet; gp_in / eos: the packets' granule positions and end flags; gap: out
+    of sequence here."""
+    return blockin(bs, 0, [0] * len(W), W, gp_in, eos, gap)[0]
 
 
 @pytest.fixture(scope="module")
@@ -71,12 +47,12 @@ def material(cuda):
 
 
 def decode(dec, ids, runs, gaps=None, marks=True):
-    data, offs, gp, eo = csr(runs, "cuda")
-    kw = {}
-    if marks:
-        g = np.concatenate([np.zeros(len(r), np.uint8) if gaps is None else np.asarray(gaps[i], np.uint8)
-                            for i, r in enumerate(runs)])
-        kw["gap"] = None if gaps is None else torch.from_numpy(g).cuda()
+    """one synthesis_runs call.  gaps: per run the marks of its rows, which go to the call as a tensor even when all
+    are zero; marks=False: the call is made without the gap argument"""
+    if gaps is not None:
+        runs = [[p + (g,) for p, g in zip(r, gs)] for r, gs in zip(runs, gaps)]
+    data, offs, gp, eo, gap = runs_inputs(runs, "cuda", marks=gaps is not None)
+    kw = {"gap": gap} if marks else {}
     return dec.synthesis_runs(ids, [len(r) for r in runs], data, offs, granulepos=gp, eos=eo, **kw)
 
 

@@ -4,87 +4,29 @@ size over the lower half of the float32 spectrum, the Vorbis window of half the 
 for bit against the oracle's scalar inverse MDCT of that size + float32 overlap-add (check_pcm_exact), batches
 that do not fill the 128-point transform's groups, runs and ranges bit for bit against the stepwise half-rate decode,
 and a full-rate and a half-rate decoder side by side."""
-import functools
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from tests import vorbis_model as vm
-from tests.test_decode_ranges_gpu import as_stream, check, ranges
-from tests.test_decode_runs_gpu import runs_call
-from tests.test_decoder_gpu import check_pcm_exact, rows_tensor, split_dump
-from tests.test_decoder_model_cpu import fromdB
-from tests.test_decoder_synthetic_gpu import RUNS, with_failed_packets
+from tests.decode_calls import (batch_inputs, check, check_pcm_bound, check_pcm_exact, ranges, rows_tensor, runs_call,
+                                step_rows, stepwise)
+from tests.decode_packets import RUNS, as_stream, dump_packets, fromdB, with_failed_packets
 
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 PAIR_IDS = [f"{a}_{b}" for a, b in vm.PAIRS]
 
 
-# ---- the float64 reference -------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _basis(N):
-    k, t = np.arange(N // 2), np.arange(N)
-    return np.cos(2 * np.pi / N * np.outer(t + 0.5 + N / 4, k + 0.5))
+def as_info(W_steps):
+    """the step lists' block flags as the info rows check_pcm_bound and check_pcm_exact read"""
+    return [[(0, int(W)) for W in row] for row in W_steps]
 
 
-def half_imdct64(spec, n):
-    """mdct_backward of size n / 2 over bins [0, n/4) of a block of n samples (lib/block.c:208-209: the transform is
-    made for blocksizes[W] >> hs) -> n / 2 samples, float64"""
-    return _basis(n // 2) @ spec[:n // 4].astype(np.float64)
-
-
-def half_overlap64(tail, lW, p, W, bs):
-    """vorbis_synthesis_blockin's overlap-add (lib/block.c:897-1045) with n, n0, n1 shifted by hs + 1 = 2 and the
-    windows of half each block size -> (what becomes final, the new tail)"""
-    n, n0, n1 = bs[W] // 4, bs[0] // 4, bs[1] // 4
-    w0, w1 = vm.vorbis_window64(n0), vm.vorbis_window64(n1)
-    if lW < 0:
-        return np.zeros(0), p[n:2 * n].copy()
-    if lW == 1 and W == 1:
-        out = tail[:n1] * w1[::-1] + p[:n1] * w1
-    elif lW == 1:
-        off = n1 // 2 - n0 // 2
-        out = np.concatenate([tail[:off], tail[off:off + n0] * w0[::-1] + p[:n0] * w0])
-    elif W == 1:
-        off = n1 // 2 - n0 // 2
-        out = np.concatenate([tail[:n0] * w0[::-1] + p[off:off + n0] * w0, p[off + n0:off + n0 + off]])
-    else:
-        out = tail[:n0] * w0[::-1] + p[:n0] * w0
-    return out, p[n:2 * n].copy()
-
-
-def check_halfrate_bound(bs, channels, nsteps, spec_steps, W_steps, pcm_steps, samples_steps, peaks):
-    """per stream s: the device PCM of every step against the float64 reference built from spec_steps[t][s]
-    ([ch][bs1/2] float32, full rate).  Bound: 1e-5 of the step's float64 peak.  A step may return fewer samples than
-    the overlap gives only where its granule position trims its end (the stream's last) -> worst error / peak"""
-    worst = 0.0
-    for s in range(len(nsteps)):
-        tail, lW = None, -1
-        for t in range(nsteps[s]):
-            W = int(W_steps[t][s])
-            outs, tails = [], []
-            for c in range(channels):
-                p = half_imdct64(spec_steps[t][s][c], bs[W])
-                o, tl = half_overlap64(tail[c] if tail is not None else None, lW, p, W, bs)
-                outs.append(o)
-                tails.append(tl)
-            if lW >= 0:
-                assert len(outs[0]) == (bs[lW] // 4 + bs[W] // 4) >> 1
-            tail, lW = tails, W
-            want = np.stack(outs)
-            ns = int(samples_steps[t][s])
-            assert ns == want.shape[1] or (t == nsteps[s] - 1 and ns < want.shape[1]), (s, t, ns, want.shape[1])
-            if ns:
-                want = want[:, :ns]
-                got = pcm_steps[t][s][:, :ns].astype(np.float64)
-                peak = float(np.abs(want).max())
-                peaks.append(peak)
-                err = float(np.abs(got - want).max())
-                worst = max(worst, err / max(peak, 1e-3))
-                assert err <= 1e-5 * max(peak, 1e-3), f"stream {s} step {t}: max error {err} at peak {peak}"
-    return worst
+def check_halfrate_bound(ds, streams, spec_steps, W_steps, pcm_steps, samples_steps, peaks):
+    """check_pcm_bound at half rate, the reference's spectra those of spec_steps[t][s] ([ch][bs1/2] float32, full rate)
+    and its windows the Vorbis window of half each block size in float64 -> worst error / peak"""
+    win = [vm.vorbis_window64(ds.blocksizes[0] // 4), vm.vorbis_window64(ds.blocksizes[1] // 4)]
+    return check_pcm_bound(ds, streams, pcm_steps, spec_steps, as_info(W_steps), samples_steps, win=win, peaks=peaks,
+                           halfrate=True)
 
 
 def model_steps(v, ds, model, streams, cuda):
@@ -95,9 +37,7 @@ def model_steps(v, ds, model, streams, cuda):
     assert dec.halfrate and dec.row == ds.blocksizes[1] // 4
     spec_steps, W_steps, pcm_steps, samples_steps = [], [], [], []
     for t in range(T):
-        pk, nb = rows_tensor([streams[s][t][0] for s in range(S)], cuda)
-        gp = torch.tensor([streams[s][t][1] for s in range(S)], dtype=torch.int64, device=cuda)
-        eo = torch.tensor([streams[s][t][2] for s in range(S)], dtype=torch.uint8, device=cuda)
+        pk, nb, gp, eo = batch_inputs([streams[s][t] for s in range(S)], cuda)
         pcm, samples, status = dec.synthesis_batch(list(range(S)), pk, nb, granulepos=gp, eos=eo)
         assert tuple(pcm.shape) == (S, ds.channels, ds.blocksizes[1] // 4)
         assert not status.cpu().numpy().any()
@@ -115,8 +55,7 @@ def model_steps(v, ds, model, streams, cuda):
 
 def exact_halfrate(oracle, ds, streams, spec_steps, W_steps, pcm_steps, samples_steps):
     """check_pcm_exact at half rate on the step lists of this file -> steps x streams compared"""
-    info_steps = [[(0, int(W)) for W in row] for row in W_steps]
-    return check_pcm_exact(oracle, ds, streams, pcm_steps, spec_steps, info_steps, samples_steps, halfrate=True)
+    return check_pcm_exact(oracle, ds, streams, pcm_steps, spec_steps, as_info(W_steps), samples_steps, halfrate=True)
 
 
 def assert_samples_equal_the_index(v, ds, streams, samples_steps):
@@ -149,8 +88,7 @@ def test_halfrate_pcm_of_every_block_size_pair_is_within_the_bound(oracle, cuda,
     totals = assert_samples_equal_the_index(v, ds, streams, samples_steps)
     assert totals == [(pk[-1][1] + 37) // 2 - 18 for pk in streams]        # tests/test_decode_halfrate_cpu.py
     peaks = []
-    worst = check_halfrate_bound(ds.blocksizes, ds.channels, [len(pk) for pk in streams], spec_steps, W_steps,
-                                 pcm_steps, samples_steps, peaks)
+    worst = check_halfrate_bound(ds, streams, spec_steps, W_steps, pcm_steps, samples_steps, peaks)
     assert min(peaks) >= 1e-3, min(peaks)
     print(f"\nhalf rate, block sizes {PAIR_IDS[k]}, {ds.channels} ch: max |pcm - float64 reference| / peak = "
           f"{worst:.3g} (peaks {min(peaks):.3g} .. {max(peaks):.3g})")
@@ -177,37 +115,13 @@ def test_halfrate_batches_that_do_not_fill_the_imdct_groups(oracle, cuda, bs, ns
         assert sorted(int(w) for w in W_steps[0]) == [0] * nshort + [1] * nlong
     assert_samples_equal_the_index(v, ds, streams, samples_steps)
     peaks = []
-    worst = check_halfrate_bound(bs, 7, [len(pk) for pk in streams], spec_steps, W_steps, pcm_steps, samples_steps,
-                                 peaks)
+    worst = check_halfrate_bound(ds, streams, spec_steps, W_steps, pcm_steps, samples_steps, peaks)
     assert min(peaks) >= 1e-3
     print(f"\nhalf rate, 7 ch {bs}, {nshort} short + {nlong} long rows: max |pcm - float64 reference| / peak = "
           f"{worst:.3g}")
     exact = exact_halfrate(oracle, ds, streams, spec_steps, W_steps, pcm_steps, samples_steps)
     print(f"half rate, 7 ch {bs}: {exact} steps x streams equal the scalar inverse MDCT bit for bit")
     ds.close()
-
-
-def stepwise_half(v, ds, streams, dev, restart_at=None):
-    """tests/test_decode_runs_gpu.py's stepwise on a half-rate decoder -> per stream (pcm [ch, n], samples, status)"""
-    S = len(streams)
-    dec = v.Decoder(ds, S, S, halfrate=True)
-    pcm, samp, stat = [[] for _ in range(S)], [[] for _ in range(S)], [[] for _ in range(S)]
-    for t in range(max(len(s) for s in streams)):
-        ids = [s for s in range(S) if t < len(streams[s])]
-        rs = [s for s in ids if restart_at and restart_at.get(s) == t]
-        if rs:
-            dec.restart_streams(rs)
-        pk, nb = rows_tensor([streams[s][t][0] for s in ids], dev)
-        gp = torch.tensor([streams[s][t][1] for s in ids], dtype=torch.int64, device=dev)
-        eo = torch.tensor([streams[s][t][2] for s in ids], dtype=torch.uint8, device=dev)
-        p, n, st = dec.synthesis_batch(ids, pk, nb, granulepos=gp, eos=eo)
-        p, n, st = p.cpu().numpy(), n.cpu().numpy(), st.cpu().numpy()
-        for r, s in enumerate(ids):
-            pcm[s].append(p[r, :, :n[r]])
-            samp[s].append(int(n[r]))
-            stat[s].append(int(st[r]))
-    dec.close()
-    return [(np.concatenate(pcm[s], axis=1), samp[s], stat[s]) for s in range(S)]
 
 
 def decode_in_runs(dec, streams, cuts, dev, single=()):
@@ -221,15 +135,7 @@ def decode_in_runs(dec, streams, cuts, dev, single=()):
         if j in single:
             for t in range(a, b):
                 ids = [s for s in range(S) if t < len(streams[s])]
-                pk, nb = rows_tensor([streams[s][t][0] for s in ids], dev)
-                gp = torch.tensor([streams[s][t][1] for s in ids], dtype=torch.int64, device=dev)
-                eo = torch.tensor([streams[s][t][2] for s in ids], dtype=torch.uint8, device=dev)
-                p, n, st = dec.synthesis_batch(ids, pk, nb, granulepos=gp, eos=eo)
-                p, n, st = p.cpu().numpy(), n.cpu().numpy(), st.cpu().numpy()
-                for r, s in enumerate(ids):
-                    pcm[s].append(p[r, :, :n[r]])
-                    samp[s].append(int(n[r]))
-                    stat[s].append(int(st[r]))
+                step_rows(dec, ids, [streams[s][t] for s in ids], dev, pcm, samp, stat)
             continue
         ids = [s for s in range(S) if a < len(streams[s])]
         runs = [streams[s][a:b] for s in ids]
@@ -255,7 +161,7 @@ def test_halfrate_runs_and_ranges_equal_the_stepwise_decode(cuda, name, k):
     ds = v.DecodeSetup(h)
     model = vm.Model(setup, fromdB())
     streams = with_failed_packets(vm.pcm_streams(model, 8000 + k), h, len(setup["modes"]), model.modebits)
-    want = stepwise_half(v, ds, streams, cuda)
+    want = stepwise(v, ds, streams, cuda, halfrate=True)
     assert all(any(st) for _, _, st in want)                   # the failed packets are inside
     for pk, (pcm, samples, status) in zip(streams, want):
         st, sm, out_start, total = v.decode_index(ds, *as_stream(pk), halfrate=True)
@@ -311,7 +217,7 @@ def test_halfrate_of_a_real_stream(oracle, cuda):
     reference is built from the spectrum a full-rate decoder fetches for the same packets"""
     import vorbis_aotuv_lancer_amd as v
     ds = v.DecodeSetup(v.header_packets(v.Setup(2, 44100, 0.5)))
-    packets = split_dump(open(os.path.join(G, "ref_scalar_2ch_44100_q05_20s.pkt"), "rb").read())[:200]
+    packets = dump_packets("ref_scalar_2ch_44100_q05_20s.pkt")[:200]
     S, T = 4, 50
     streams = [[(p, -1, 0) for p in packets[s * T:(s + 1) * T]] for s in range(S)]
     full = v.Decoder(ds, S, S)
@@ -334,13 +240,12 @@ def test_halfrate_of_a_real_stream(oracle, cuda):
     assert all(np.array_equal(2 * samples_steps[t], full_samples[t]) for t in range(T))
     assert_samples_equal_the_index(v, ds, streams, samples_steps)
     peaks = []
-    worst = check_halfrate_bound(ds.blocksizes, 2, [T] * S, spec_steps, W_steps, pcm_steps, samples_steps, peaks)
+    worst = check_halfrate_bound(ds, streams, spec_steps, W_steps, pcm_steps, samples_steps, peaks)
     print(f"\nhalf rate, 2ch 44100 q0.5 reference stream: max |pcm - float64 reference| / peak = {worst:.3g} "
           f"(peaks {min(peaks):.3g} .. {max(peaks):.3g})")
     exact = exact_halfrate(oracle, ds, streams, spec_steps, W_steps, pcm_steps, samples_steps)
     # the full-rate decoder beside it, on the same packets and spectra
-    info_steps = [[(0, int(W)) for W in row] for row in W_steps]
-    exact_full = check_pcm_exact(oracle, ds, streams, full_pcm, spec_steps, info_steps, full_samples)
+    exact_full = check_pcm_exact(oracle, ds, streams, full_pcm, spec_steps, as_info(W_steps), full_samples)
     print(f"reference stream: {exact} steps x streams at half rate and {exact_full} at full rate equal the scalar inverse "
           f"MDCT bit for bit")
     full.close()
@@ -360,9 +265,7 @@ def test_full_rate_and_half_rate_decoders_side_by_side(cuda):
     S, T = len(streams), len(streams[0])
 
     def step(dec, t):
-        pk, nb = rows_tensor([streams[s][t][0] for s in range(S)], cuda)
-        gp = torch.tensor([streams[s][t][1] for s in range(S)], dtype=torch.int64, device=cuda)
-        eo = torch.tensor([streams[s][t][2] for s in range(S)], dtype=torch.uint8, device=cuda)
+        pk, nb, gp, eo = batch_inputs([streams[s][t] for s in range(S)], cuda)
         pcm, n, st = dec.synthesis_batch(list(range(S)), pk, nb, granulepos=gp, eos=eo)
         assert not st.cpu().numpy().any()
         n = n.cpu().numpy()
@@ -371,7 +274,7 @@ def test_full_rate_and_half_rate_decoders_side_by_side(cuda):
     alone = v.Decoder(ds, S, S)
     want_full = [step(alone, t) for t in range(T)]
     alone.close()
-    want_half = stepwise_half(v, ds, streams, cuda)
+    want_half = stepwise(v, ds, streams, cuda, halfrate=True)
     full, half = v.Decoder(ds, S, S), v.Decoder(ds, S, S, halfrate=True)
     assert not full.halfrate and half.halfrate
     got_half = [[] for _ in range(S)]

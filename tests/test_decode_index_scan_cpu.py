@@ -4,28 +4,13 @@ array, at both rates: on the corpora of test_decode_index_cpu.py, on seeded stre
 adversarial granule positions and eos flags (the granulepos values below -1 included, which send a stream down the
 serial fallback), and on CSRs with empty streams and offsets that are negative, past the data or decreasing."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-from tests.test_decode_index_cpu import G, csr, granule_variants, split_dump, with_bad_packets
-from tests.test_decoder_cpu import oracle_packets, pack_setup
-
-EINVAL = -131
-LENGTHS = [0, 1, 2, 3, 63, 64, 65, 127, 128, 129, 200, 4097]
-BS = (256, 2048)                     # Setup(2, 44100, 0.5): modebits 1, mode 0 short, mode 1 long
-GP_KINDS = ["none", "jitter", "jitter0", "zero", "big", "minus2", "minus129", "land"]
-
-
-def serial_index(v, ds, data, offsets, gp, eos, first, halfrate):
-    """vbm_decode_index_halfrate of every stream alone -> (status, samples, out_start, totals) over the whole CSR"""
-    st, sm, os_, tot = [], [], [], []
-    for a, b in zip(first[:-1], first[1:]):
-        r = v.decode_index(ds, data, offsets[a:b + 1], None if gp is None else gp[a:b],
-                           None if eos is None else eos[a:b], halfrate=halfrate)
-        st.append(r[0]), sm.append(r[1]), os_.append(r[2]), tot.append(r[3])
-    return (np.concatenate(st), np.concatenate(sm), np.concatenate(os_), np.asarray(tot, np.int64))
+from tests.decode_packets import (BS, DUMPS, EINVAL, GP_KINDS, INDEX_PACKS, csr, dump_packets, join, one_byte_corpus,
+                                  one_byte_stream, oracle_packets, pack_setup, page_granule_variants, serial_index,
+                                  with_bad_packets)
 
 
 def assert_scan_equals_serial(v, ds, data, offsets, gp, eos, first):
@@ -44,75 +29,6 @@ def assert_scan_equals_serial(v, ds, data, offsets, gp, eos, first):
         assert np.all(begin >= 0) and np.all(begin[status != 0] == 0) and np.all(end[status != 0] == 0)
         full = full or (status, begin, end, out_start, totals)
     return full
-
-
-def join(streams):
-    """[(data, offsets, gp, eos)] -> one CSR (data, offsets, gp, eos, first)"""
-    datas, offs, gps, eoss, first, base = [], [np.zeros(1, np.int64)], [], [], [0], 0
-    for data, o, gp, eo in streams:
-        datas.append(np.asarray(data, np.uint8))
-        offs.append(np.asarray(o[1:], np.int64) + base)
-        gps.append(np.asarray(gp, np.int64))
-        eoss.append(np.asarray(eo, np.uint8))
-        first.append(first[-1] + len(o) - 1)
-        base += len(data)
-    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)
-    return cat(datas, np.uint8), cat(offs, np.int64), cat(gps, np.int64), cat(eoss, np.uint8), np.asarray(first, np.int64)
-
-
-# ---- seeded streams of one-byte packets --------------------------------------------------------------------------
-def one_byte_stream(rng, n, invalid, kind, last_eos, first_valid=0):
-    """n packets of one byte: bit 0 the packet type (1: not audio), bit 1 the mode, bits 2 and 3 lW and nW
-    -> (data, offsets, granulepos, eos)"""
-    bad = rng.random(n) < invalid
-    bad[:first_valid] = True
-    mode = rng.integers(0, 2, n)
-    data = (bad.astype(np.uint8) | (mode << 1) | (rng.integers(0, 4, n) << 2)).astype(np.uint8)
-    # the count an encoder would write (sum of the steps), and the step of every valid packet
-    count, step, lW, g = np.zeros(n, np.int64), np.zeros(n, np.int64), -1, 0
-    for k in range(n):
-        if not bad[k]:
-            step[k] = (BS[lW] // 4 if lW >= 0 else 0) + BS[mode[k]] // 4
-            if lW >= 0:
-                g += step[k]
-            lW = mode[k]
-        count[k] = g
-    gp = np.full(n, -1, np.int64)
-    some = rng.random(n) < 0.2
-    if kind in ("jitter", "jitter0"):
-        gp[some] = (count + rng.integers(-3000, 3001, n))[some]
-        if kind == "jitter0":
-            gp[some] = np.maximum(gp[some], 0)
-    elif kind == "zero":
-        gp[some] = np.where(rng.random(n) < 0.5, 0, count)[some]
-    elif kind == "big":
-        gp[some] = np.where(rng.random(n) < 0.5, 2 ** 40, count)[some]
-    elif kind in ("minus2", "minus129"):
-        gp[some] = np.where(rng.random(n) < 0.5, -2 if kind == "minus2" else -129, count)[some]
-    elif kind == "land":
-        # -1 - (the next valid packet's step): the running position lands on -1 there and is "none yet" again
-        nxt = np.full(n, 128, np.int64)
-        valid = np.flatnonzero(~bad)
-        for a, b in zip(valid[:-1], valid[1:]):
-            nxt[a] = BS[mode[a]] // 4 + BS[mode[b]] // 4
-        gp[some] = np.where(rng.random(n) < 0.5, -1 - nxt, count)[some]
-    eos = (rng.random(n) < 0.1).astype(np.uint8)
-    if n:
-        eos[-1] = last_eos
-    return data, np.arange(n + 1, dtype=np.int64), gp, eos
-
-
-def one_byte_corpus(seed=1, lengths=LENGTHS, kinds=GP_KINDS, shares=(0.0, 0.1, 0.9)):
-    rng = np.random.default_rng(seed)
-    streams = []
-    for n in lengths:
-        for invalid in shares:
-            for kind in kinds:
-                streams.append(one_byte_stream(rng, n, invalid, kind, int(rng.integers(0, 2))))
-    for kind in kinds:
-        streams.append(one_byte_stream(rng, 150, 1.0, kind, 1))                    # no valid packet at all
-        streams.append(one_byte_stream(rng, 150, 0.1, kind, 1, first_valid=64))    # the first valid packet is 64
-    return streams
 
 
 @pytest.fixture(scope="module")
@@ -157,7 +73,7 @@ def real_streams(ds, packets, headers, seed):
     out = []
     for pk in (packets, with_bad_packets(packets, headers, seed)):
         data, offs = csr(pk)
-        for gps, eoss in granule_variants(ds, pk):
+        for gps, eoss in page_granule_variants(ds, pk):
             out.append((data, offs, np.asarray(gps, np.int64), np.asarray(eoss, np.uint8)))
     return out
 
@@ -169,21 +85,17 @@ def check_real(v, ds, streams):
     assert_scan_equals_serial(v, ds, *join(streams))
 
 
-@pytest.mark.parametrize("ch,rate,q,golden", [
-    (2, 44100, 0.5, "ref_scalar_2ch_44100_q05_20s.pkt"),
-    (6, 48000, 0.8, "ref_scalar_6ch_48000_q08_10s.pkt"),
-])
+@pytest.mark.parametrize("ch,rate,q,golden", DUMPS)
 def test_reference_dumps(ch, rate, q, golden):
     import vorbis_aotuv_lancer_amd as v
     h = v.header_packets(v.Setup(ch, rate, q))
     ds = v.DecodeSetup(h)
-    packets = split_dump(open(os.path.join(G, golden), "rb").read())
+    packets = dump_packets(golden)
     check_real(v, ds, real_streams(ds, packets, h, 5))
     ds.close()
 
 
-@pytest.mark.parametrize("pack", ["mode_1ch_44100_q0.5.vpk", "mode_2ch_44100_q0.1.vpk", "mode_2ch_96000_q0.5.vpk",
-                                  "mode_1ch_8000_q0.5.vpk", "mode_6ch_48000_q0.5.vpk", "mode_2ch_44100_q-0.1.vpk"])
+@pytest.mark.parametrize("pack", INDEX_PACKS)
 def test_shipped_packs(oracle, pack):
     import vorbis_aotuv_lancer_amd as v
     setup, d = pack_setup(v, pack)
@@ -216,7 +128,7 @@ def test_offsets_negative_past_the_data_and_decreasing():
     import vorbis_aotuv_lancer_amd as v
     h = v.header_packets(v.Setup(2, 44100, 0.5))
     ds = v.DecodeSetup(h)
-    packets = split_dump(open(os.path.join(G, "ref_scalar_2ch_44100_q05_20s.pkt"), "rb").read())[:150]
+    packets = dump_packets("ref_scalar_2ch_44100_q05_20s.pkt")[:150]
     data, offs = csr(packets)
     first = [0, 40, 40, 110, 150]
     rng = np.random.default_rng(2)

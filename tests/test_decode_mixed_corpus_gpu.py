@@ -11,6 +11,7 @@ import torch
 
 from tests import decode_mixed_cases as M
 from tests import ogg_feed_resync_cases as R
+from tests.decode_calls import runs_inputs
 from tests.signals import synth_signal
 
 pytestmark = pytest.mark.gpu
@@ -170,7 +171,7 @@ def test_live_loop_of_the_readme(cuda, mounts):
             P = int(r.counts[live].sum())
             assert P <= cap
             stride = max(int(k) * w for k, w in zip(r.counts[live], md.row_of(r.ids[live])))
-            out = (torch.full((int(live.sum()), md.channels, stride), M.FILL, dtype=torch.float32, device=cuda),
+            out = (torch.full((int(live.sum()), md.channels, stride), M.FILL_PLAYER, dtype=torch.float32, device=cuda),
                    *(torch.empty(k, dtype=torch.int32, device=cuda) for k in (int(live.sum()), P, P)))
             md.synthesis_runs(r.ids[live], r.counts[live], r.payload, r.offsets, granulepos=r.granulepos, eos=r.eos,
                               gap=r.gap, out=out)
@@ -199,7 +200,7 @@ def test_live_loop_of_the_readme(cuda, mounts):
         at, call = 0, []
         for row, (slot, cnt) in enumerate(zip(r.ids[live].tolist(), r.counts[live].tolist())):
             ch = chans[row]
-            assert np.all(pcm[row, ch:] == M.FILL) and np.all(pcm[row, :ch, rs[row]:] == M.FILL), slot
+            assert np.all(pcm[row, ch:] == M.FILL_PLAYER) and np.all(pcm[row, :ch, rs[row]:] == M.FILL_PLAYER), slot
             got[slot][-1].append((pcm[row, :ch, :rs[row]], sm[at:at + cnt], st[at:at + cnt]))
             call.append((slot, [(data[offs[k]:offs[k + 1]], gp[k], eo[k], gap[k]) for k in range(at, at + cnt)]))
             for k in range(at, at + cnt):
@@ -241,10 +242,10 @@ def test_live_loop_of_the_readme(cuda, mounts):
         call = next(it)
         for c in sorted({cls[s] for s, _ in call}):
             mine = [(s, run) for s, run in call if cls[s] == c]
-            data, offs, gp, eo, gap = M._runs_inputs(mine, cuda)
+            data, offs, gp, eo, gap = runs_inputs([r for _, r in mine], cuda)
             counts = [len(run) for _, run in mine]
             stride = max(counts) * dec[c].row
-            out = (torch.full((len(mine), dec[c].channels, stride), M.FILL, dtype=torch.float32, device=cuda),
+            out = (torch.full((len(mine), dec[c].channels, stride), M.FILL_PLAYER, dtype=torch.float32, device=cuda),
                    *(torch.empty(k, dtype=torch.int32, device=cuda) for k in (len(mine), sum(counts), sum(counts))))
             dec[c].synthesis_runs([s for s, _ in mine], counts, data, offs, granulepos=gp, eos=eo, gap=gap, out=out)
             pending.append((mine, counts, out))
@@ -253,7 +254,7 @@ def test_live_loop_of_the_readme(cuda, mounts):
         pcm, rs, sm, st = pcm.cpu().numpy(), rs.cpu().tolist(), sm.cpu().tolist(), st.cpu().tolist()
         at = 0
         for row, ((s, _), cnt) in enumerate(zip(mine, counts)):
-            assert np.all(pcm[row, :, rs[row]:] == M.FILL)
+            assert np.all(pcm[row, :, rs[row]:] == M.FILL_PLAYER)
             twin[s].append((pcm[row, :, :rs[row]], sm[at:at + cnt], st[at:at + cnt]))
             at += cnt
     for d in dec.values():

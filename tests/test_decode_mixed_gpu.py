@@ -7,6 +7,8 @@ import pytest
 import torch
 
 from tests import decode_mixed_cases as M
+from tests.decode_calls import rows_tensor
+from tests.decode_packets import ogg_packets
 from tests.signals import synth_signal
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +17,7 @@ RATES = [False, True]
 RATE_IDS = ["full", "half"]
 
 
-def stepwise(streams):
+def step_script(streams):
     """streams {stream id: [packets]} -> batch events, one packet per stream per call while it lasts"""
     T = max(len(pk) for pk in streams.values())
     return [("batch", [(s, pk[t]) for s, pk in streams.items() if t < len(pk)]) for t in range(T)]
@@ -40,13 +42,13 @@ def test_one_class_equals_the_decoder(cuda, encoded):
     k = M.synthetic(2, (256, 2048))
     streams = {0: M.stream(2, (256, 2048)), 1: M.stream(2, (256, 2048), contrary=True), 2: M.stream(2, (256, 2048), seed=5)}
     start = [("add", 0), ("bind", [0, 1, 2], [0, 0, 0])]
-    M.both(v, [k], start + stepwise(streams), 3, 8, cuda)
+    M.both(v, [k], start + step_script(streams), 3, 8, cuda)
     runs = [("runs", [(s, list(pk[:4])) for s, pk in streams.items()]),
             ("runs", [(s, list(pk[4:])) for s, pk in streams.items()])]
     m = M.both(v, [k], start + runs, 3, 32, cuda)
     assert [sum(len(sm) for _, sm, _ in m.result[s]) for s in range(3)] == [10, 10, 10]
     assert m.result[0][-1][1][-1] < 1024 + 128                 # the trimmed last packet
-    headers, pk = M.ogg_packets(encoded[0][3])                 # 4099 stereo samples
+    headers, pk = ogg_packets(encoded[0][3])                 # 4099 stereo samples
     assert 3 <= len(pk) <= 40 and pk[-1][2] == 1 and pk[-1][1] == 4099
     real = M.Class(headers, 2, (256, 2048))
     m = M.both(v, [real], [("add", 0), ("bind", [0], [0]), ("runs", [(0, pk)])], 1, 64, cuda, max_channels=2,
@@ -65,7 +67,7 @@ def test_channel_mix_at_equal_sizes(cuda, halfrate):
     classes = [M.synthetic(ch, bs) for ch in (1, 2, 6)]
     streams = {s: M.stream(k.ch, bs, seed=s) for s, k in enumerate(classes)}
     script = [("add", 0), ("add", 1), ("add", 2), ("bind", [2, 0, 1], [2, 0, 1])]
-    script += stepwise(streams)[:5] + [("runs", [(s, list(pk[5:])) for s, pk in streams.items()])]
+    script += step_script(streams)[:5] + [("runs", [(s, list(pk[5:])) for s, pk in streams.items()])]
     m = M.both(v, classes, script, 3, 16, cuda, halfrate=halfrate, count=True)
     group = 512 // ((256 >> halfrate) // 4)                      # blocks of 256 in a 512-complex group: 8, or 16
     small = [sum(ch for _, _, ch in call.get(256, [])) for call in m.blocks]
@@ -87,7 +89,7 @@ def test_size_collisions(cuda, halfrate):
     streams = {s: M.stream(k.ch, k.bs, seed=s) for s, k in enumerate(classes)}
     ids = list(streams)
     script = [("add", c) for c in ids] + [("bind", ids, ids)]
-    script += [("runs", [(s, list(pk[:6])) for s, pk in streams.items()])] + stepwise({s: pk[6:] for s, pk in streams.items()})
+    script += [("runs", [(s, list(pk[:6])) for s, pk in streams.items()])] + step_script({s: pk[6:] for s, pk in streams.items()})
     m = M.both(v, classes, script, len(ids), 40, cuda, halfrate=halfrate, count=True)
     assert all(st == [0] * len(st) for r in m.result.values() for _, _, st in r)
     first = m.blocks[0]                                          # the runs call: six packets of every stream
@@ -140,7 +142,7 @@ def test_rebind_to_a_smaller_class_after_calls_have_run(cuda):
     script = [("add", 0), ("bind", [0, 1], [0, 0]),
               ("runs", [(0, list(big[:3])), (1, list(other[:5]))]), ("runs", [(0, list(big[3:])), (1, list(other[5:7]))]),
               ("add", 1), ("bind", [0], [1]),
-              ("runs", [(0, list(small[:4])), (1, list(other[7:]))])] + stepwise({0: small[4:]})
+              ("runs", [(0, list(small[:4])), (1, list(other[7:]))])] + step_script({0: small[4:]})
     m = M.both(v, classes, script, 2, 16, cuda)
     assert sum(p.shape[1] for p, _, _ in m.result[0][:2]) == 5 * 2048 - 37          # the last packet is trimmed
     assert m.result[0][2][1][0] == 0 and m.result[0][2][0].shape[0] == 1     # the first packet after the bind
@@ -186,9 +188,8 @@ def test_arguments(cuda, encoded):
     md.bind([0, 1], [0, 1])
     assert md.channels_of([1, 0]) == [1, 2] and md.rate_of([0]) == [ds[small].rate]
     pk = M.stream(2, (256, 512))
-    from tests.test_decoder_gpu import rows_tensor
     rows, nb = rows_tensor([pk[0][0], pk[1][0]], cuda)
-    pcm = torch.full((2, 2, 512), M.FILL, dtype=torch.float32, device=cuda)
+    pcm = torch.full((2, 2, 512), M.FILL_PLAYER, dtype=torch.float32, device=cuda)
     ints = torch.full((4,), -5, dtype=torch.int32, device=cuda)
     with pytest.raises(v.VbmError, match="not bound"):         # stream 2 was never bound: nothing is enqueued
         md.synthesis_batch([0, 2], rows, nb, out=(pcm, ints[:2], ints[2:]))
@@ -196,7 +197,7 @@ def test_arguments(cuda, encoded):
     with pytest.raises(v.VbmError, match="not bound"):
         md.synthesis_runs([3], [1], data, torch.tensor([0, 16], device=cuda))
     torch.cuda.synchronize()
-    assert (pcm == M.FILL).all() and (ints == -5).all()
+    assert (pcm == M.FILL_PLAYER).all() and (ints == -5).all()
     _, samples, status = md.synthesis_batch([0], rows[:1], nb[:1])        # the decoder still works
     assert status.cpu().tolist() == [0] and samples.cpu().tolist() == [0]
     with pytest.raises(v.VbmError, match="mixed"):

@@ -5,8 +5,7 @@ import numpy as np
 import pytest
 
 from tests import decode_mixed_range_cases as R
-
-EINVAL = -131            # VBM_EINVAL
+from tests.decode_packets import EINVAL
 
 
 @pytest.fixture(scope="module")

@@ -8,6 +8,8 @@ import torch
 
 from tests import decode_mixed_cases as M
 from tests import decode_mixed_range_cases as R
+from tests.decode_calls import runs_call
+from tests.decode_packets import as_stream
 from tests.signals import synth_signal
 
 pytestmark = pytest.mark.gpu
@@ -49,7 +51,7 @@ def corpus(cuda):
 def open_mixed(v, classes, ds, streams, cap, halfrate=False, nstreams=1):
     md = v.MixedDecoder(nstreams, cap, halfrate=halfrate, **caps(classes))
     cid = [md.add_class(d) for d in ds]
-    store = v.RangeStore(md, [R.tuple_of(pk) for _, pk in streams], classes=[cid[c] for c, _ in streams])
+    store = v.RangeStore(md, [as_stream(pk) for _, pk in streams], classes=[cid[c] for c, _ in streams])
     return md, store
 
 
@@ -112,7 +114,7 @@ def test_index_of_several_classes(cuda, halfrate):
         a, z = int(first[i]), int(first[i + 1])
         assert np.array_equal(status[a:z], st) and np.array_equal(begin[a:z], b) and np.array_equal(end[a:z], e), i
         assert np.array_equal(out_start[a:z], o) and totals[i] == total, i
-    host = v.RangeStore(md, [R.tuple_of(pk) for _, pk in streams], classes=[cid[c] for c in of])
+    host = v.RangeStore(md, [as_stream(pk) for _, pk in streams], classes=[cid[c] for c in of])
     dev = v.RangeStore.from_device(md, *t, stream_packets=first, classes=[cid[c] for c in of])
     assert np.array_equal(host.totals, totals) and np.array_equal(dev.totals, totals)
     windows = []
@@ -127,8 +129,7 @@ def test_index_of_several_classes(cuda, halfrate):
 
 
 def runs(md, parts, dev):
-    data, offs, gp, eo, gap = M._runs_inputs(parts, dev)
-    return md.synthesis_runs([s for s, _ in parts], [len(p) for _, p in parts], data, offs, granulepos=gp, eos=eo)[:2]
+    return runs_call(md, [s for s, _ in parts], [r for _, r in parts], dev)[:2]
 
 
 def test_range_calls_leave_bound_streams_alone(cuda, corpus):
@@ -160,9 +161,9 @@ def test_class_added_after_the_first_store(cuda, corpus):
     md = v.MixedDecoder(1, 4096, **caps(classes))
     cid = [md.add_class(ds[0]), md.add_class(ds[1])]
     early = [s for s, (c, _) in enumerate(streams) if c < 2]
-    store1 = v.RangeStore(md, [R.tuple_of(streams[s][1]) for s in early], classes=[cid[streams[s][0]] for s in early])
+    store1 = v.RangeStore(md, [as_stream(streams[s][1]) for s in early], classes=[cid[streams[s][0]] for s in early])
     cid += [md.add_class(d) for d in ds[2:]]
-    store2 = v.RangeStore(md, [R.tuple_of(pk) for _, pk in streams], classes=[cid[c] for c, _ in streams])
+    store2 = v.RangeStore(md, [as_stream(pk) for _, pk in streams], classes=[cid[c] for c, _ in streams])
     rows1 = [r for r, w in enumerate(windows) if w[0] in early]
     w1 = [(early.index(windows[r][0]),) + windows[r][1:] for r in rows1]
     chans = [classes[streams[w[0]][0]].ch for w in windows]
@@ -254,7 +255,7 @@ def test_cut_ranges_over_two_classes(cuda, encoded):
 def test_refusals(cuda, corpus, encoded):
     """nothing is enqueued: the output keeps its fill"""
     v, classes, ds, streams, at = corpus
-    tuples = [R.tuple_of(pk) for _, pk in streams[:2]]
+    tuples = [as_stream(pk) for _, pk in streams[:2]]
     md, store = open_mixed(v, classes, ds, streams[:2], 64)
     with pytest.raises(ValueError, match="one class id per stream"):
         v.RangeStore(md, tuples, classes=[0])
@@ -274,16 +275,16 @@ def test_refusals(cuda, corpus, encoded):
         v.decode_index_device(one, *t, stream_packets=first, classes=[0, 0])
     single = v.RangeStore(one, tuples[:1])
     other, other_store = open_mixed(v, classes, ds, streams[:2], 64)
-    pcm = torch.full((1, md.channels, 64), M.FILL, dtype=torch.float32, device=cuda)
+    pcm = torch.full((1, md.channels, 64), M.FILL_PLAYER, dtype=torch.float32, device=cuda)
     for dec, st in ((md, other_store), (other, store), (md, single)):
         with pytest.raises(v.VbmError, match="mixed"):
             dec.synthesis_ranges(st, [0], [0], [64], out=pcm)
     with pytest.raises(v.VbmError, match="another decoder"):
         one.synthesis_ranges(store, [0], [0], [64], out=pcm[:, :1])
     torch.cuda.synchronize()
-    assert (pcm == M.FILL).all()
+    assert (pcm == M.FILL_PLAYER).all()
     _, got = md.synthesis_ranges(store, [0], [0], [64], out=pcm)        # the decoder and its store still work
-    assert got.tolist() == [64] and (pcm[0, 0] != M.FILL).all() and (pcm[0, 1:] == M.FILL).all()
+    assert got.tolist() == [64] and (pcm[0, 0] != M.FILL_PLAYER).all() and (pcm[0, 1:] == M.FILL_PLAYER).all()
     for x in (single, one, other_store, other, store, md):
         x.close()
     ix = v.OggIndex(encoded[:2], one_decoder=True, halfrate=True)

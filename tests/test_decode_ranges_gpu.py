@@ -7,47 +7,10 @@ import numpy as np
 import pytest
 import torch
 
-from tests.signals import burst_signal, synth_signal
-from tests.test_decode_runs_gpu import encode_chunked, encoded, runs_call, stepwise
-from tests.test_decoder_cpu import pack_setup
-from tests.test_decoder_gpu import device_encode, rows_tensor
-from tests.test_reference_input_gpu import gen_windowed_sine
-
-EINVAL, ENOTAUDIO = -131, -135
-FILL = 7.5                                                 # what no range call writes
-
-
-def as_stream(pk):
-    """[(packet, granulepos, eos)] -> (data, offsets, granulepos, eos) numpy, as demux_ogg returns them"""
-    data = np.frombuffer(b"".join(p[0] for p in pk), np.uint8).copy()
-    offs = np.cumsum([0] + [len(p[0]) for p in pk]).astype(np.int64)
-    return data, offs, np.array([p[1] for p in pk], np.int64), np.array([p[2] for p in pk], np.uint8)
-
-
-def linear(v, ds, pk, cuda):
-    """the whole stream in one synthesis_runs call -> pcm [ch, total] (equal to the stepwise decode:
-    tests/test_decode_runs_gpu.py)"""
-    dec = v.Decoder(ds, 1, max(1, len(pk)))
-    pcm, rs, _, _ = runs_call(dec, [0], [pk], cuda)
-    out = pcm[0, :, :int(rs[0])].cpu().numpy()
-    dec.close()
-    return out
-
-
-def ranges(dec, store, ids, starts, lengths, stride=None):
-    """one call into a buffer filled with FILL -> (pcm numpy, got)"""
-    L = max(1, max(lengths, default=0)) if stride is None else stride
-    out = torch.full((len(ids), dec.channels, L), FILL, dtype=torch.float32, device="cuda")
-    pcm, got = dec.synthesis_ranges(store, ids, starts, lengths, out=out)
-    return pcm.cpu().numpy(), got
-
-
-def check(lin, ids, starts, lengths, pcm, got, what=""):
-    for r, (i, s, L) in enumerate(zip(ids, starts, lengths)):
-        n = max(0, min(lin[i].shape[1] - s, L))
-        assert got[r] == n, f"{what} range {r}: got"
-        assert np.array_equal(pcm[r, :, :n], lin[i][:, s:s + n]), f"{what} range {r} (stream {i}, start {s}, len {L})"
-        assert np.all(pcm[r, :, n:] == FILL), f"{what} range {r}: written past got"
+from tests.decode_calls import (FILL_RANGES, check, device_encode, encode_chunked, encoded, linear, ranges,
+                                rows_tensor, runs_call, stepwise)
+from tests.decode_packets import EINVAL, ENOTAUDIO, as_stream, pack_setup
+from tests.signals import burst_signal, gen_windowed_sine, synth_signal
 
 
 CLASSES = ["mode_1ch_44100_q0.5.vpk", "mode_2ch_44100_q0.5.vpk", "mode_6ch_48000_q0.5.vpk", "mode_1ch_8000_q0.5.vpk",
@@ -253,7 +216,7 @@ def test_argument_errors_enqueue_nothing(cuda):
     dec = v.Decoder(ds, 1, 16)
     other = v.Decoder(ds, 1, 16)
     store = v.RangeStore(dec, [as_stream(pk)])
-    out = torch.full((2, 2, 100), FILL, device=cuda)
+    out = torch.full((2, 2, 100), FILL_RANGES, device=cuda)
     for args in ([5], [0], [100]), ([0], [-1], [100]), ([0], [0], [-1]):
         with pytest.raises(v.VbmError, match=str(EINVAL)):
             dec.synthesis_ranges(store, *args)
@@ -265,7 +228,7 @@ def test_argument_errors_enqueue_nothing(cuda):
     with pytest.raises(v.VbmError, match=str(EINVAL)):
         one.synthesis_ranges(v.RangeStore(one, [as_stream(pk)]), [0], [0], [10])   # max_batch < 2
     torch.cuda.synchronize()
-    assert torch.all(out == FILL)
+    assert torch.all(out == FILL_RANGES)
     ids, st, ln = np.array([0], np.int32), np.array([0], np.int64), np.array([10], np.int32)
     got = np.zeros(1, np.int32)
     assert lib.vbm_synthesis_ranges(dec._h, None, 1, ids.ctypes.data, st.ctypes.data, ln.ctypes.data,
@@ -300,7 +263,7 @@ def test_full_size_ranges_unsynchronised(cuda):
     for c in range(4):
         ids = [int(i) for i in rng.integers(0, S, 2048)]
         starts = [int(rng.integers(0, store.totals[i])) for i in ids]
-        out = torch.full((2048, 2, 44100), FILL, dtype=torch.float32, device=cuda)
+        out = torch.full((2048, 2, 44100), FILL_RANGES, dtype=torch.float32, device=cuda)
         pcm, got = dec.synthesis_ranges(store, ids, starts, [44100] * 2048, out=out)
         calls.append((ids, starts, pcm, got))
     torch.cuda.synchronize()

@@ -5,130 +5,10 @@ import numpy as np
 import pytest
 import torch
 
-from tests.signals import burst_signal, synth_signal
-from tests.test_decoder_cpu import pack_setup
-from tests.test_decoder_gpu import device_encode, rows_tensor
-from tests.test_reference_input_gpu import gen_windowed_sine
-
-EINVAL, ENOTAUDIO = -131, -135
-
-
-def stepwise(v, ds, streams, dev, restart_at=None):
-    """streams: per stream [(packet, granulepos, eos)], fed one packet per stream per call (synthesis_batch).
-    restart_at: {stream: packet index} restarts the stream before that packet.
-    -> per stream (pcm [ch, n], samples [P], status [P])"""
-    S = len(streams)
-    dec = v.Decoder(ds, S, S)
-    pcm = [[] for _ in range(S)]
-    samp = [[] for _ in range(S)]
-    stat = [[] for _ in range(S)]
-    for t in range(max(len(s) for s in streams)):
-        ids = [s for s in range(S) if t < len(streams[s])]
-        rs = [s for s in ids if restart_at and restart_at.get(s) == t]
-        if rs:
-            dec.restart_streams(rs)
-        pk, nb = rows_tensor([streams[s][t][0] for s in ids], dev)
-        gp = torch.tensor([streams[s][t][1] for s in ids], dtype=torch.int64, device=dev)
-        eo = torch.tensor([streams[s][t][2] for s in ids], dtype=torch.uint8, device=dev)
-        p, n, st = dec.synthesis_batch(ids, pk, nb, granulepos=gp, eos=eo)
-        p, n, st = p.cpu().numpy(), n.cpu().numpy(), st.cpu().numpy()
-        for r, s in enumerate(ids):
-            pcm[s].append(p[r, :, :n[r]])
-            samp[s].append(int(n[r]))
-            stat[s].append(int(st[r]))
-    dec.close()
-    return [(np.concatenate(pcm[s], axis=1), samp[s], stat[s]) for s in range(S)]
-
-
-def csr(runs, dev):
-    """runs: per run [(packet, granulepos, eos)] -> data, offsets, granulepos, eos device tensors (rows concatenated)"""
-    flat = [p for r in runs for p in r]
-    data = b"".join(p[0] for p in flat)
-    offs = np.zeros(len(flat) + 1, np.int64)
-    offs[1:] = np.cumsum([len(p[0]) for p in flat])
-    return (torch.from_numpy(np.frombuffer(data or b"\0", np.uint8).copy()).to(dev), torch.from_numpy(offs).to(dev),
-            torch.tensor([p[1] for p in flat], dtype=torch.int64, device=dev),
-            torch.tensor([p[2] for p in flat], dtype=torch.uint8, device=dev))
-
-
-def runs_call(dec, ids, runs, dev):
-    """one synthesis_runs call -> device tensors (pcm, run_samples, samples, status)"""
-    data, offs, gp, eo = csr(runs, dev)
-    return dec.synthesis_runs(ids, [len(r) for r in runs], data, offs, granulepos=gp, eos=eo)
-
-
-class Collect:
-    """per stream: the device outputs of calls, concatenated on the host at the end (one wait)"""
-
-    def __init__(self, S):
-        self.parts = [[] for _ in range(S)]
-
-    def add(self, sid, pcm, nsamp, samples, status):
-        self.parts[sid].append((pcm, nsamp, samples, status))
-
-    def result(self, sid):
-        pcm, samp, stat = [], [], []
-        for p, n, sm, st in self.parts[sid]:
-            n = int(n)
-            pcm.append(p[:, :n].cpu().numpy())
-            samp += sm.cpu().tolist()
-            stat += st.cpu().tolist()
-        return np.concatenate(pcm, axis=1), samp, stat
-
-    def add_runs(self, ids, runs, out):
-        pcm, rs, sm, st = out
-        at = 0
-        for r, sid in enumerate(ids):
-            c = len(runs[r])
-            self.add(sid, pcm[r], rs[r], sm[at:at + c], st[at:at + c])
-            at += c
-
-    def add_steps(self, ids, out):
-        pcm, sm, st = out
-        for r, sid in enumerate(ids):
-            self.add(sid, pcm[r], sm[r], sm[r:r + 1], st[r:r + 1])
-
-
-def assert_same(got, want, what=""):
-    assert got[2] == want[2], f"{what}: status"
-    assert got[1] == want[1], f"{what}: samples"
-    assert got[0].dtype == np.float32 and np.array_equal(got[0], want[0]), f"{what}: pcm"
-
-
-def encode_chunked(v, setup, sig, cuda):
-    """device front end, 1024 samples per write with the rounds drained in between, end of stream declared
-    -> [(packet, granulepos, eos)] of the one stream"""
-    enc = v.Encoder(setup, 1)
-    fe = v.FrontEnd(enc)
-    got = []
-
-    def drain():
-        while True:
-            info, packets, nbytes = fe.encode_round()
-            if len(info) == 0:
-                return
-            packets, nbytes = packets.cpu().numpy(), nbytes.cpu().numpy()
-            for k, pi in enumerate(info):
-                got.append((int(pi["packetno"]), bytes(packets[k, :nbytes[k]]), int(pi["granulepos"]), int(pi["eos"])))
-
-    dsig = torch.from_numpy(np.ascontiguousarray(sig[None])).to(cuda)
-    for c in range(0, sig.shape[1], 1024):
-        fe.write(dsig[:, :, c:c + 1024].contiguous())
-        drain()
-    fe.finish()
-    drain()
-    fe.close()
-    enc.close()
-    got.sort()
-    assert [g[0] for g in got] == list(range(3, 3 + len(got))) and got[-1][3] == 1
-    return [g[1:] for g in got]
-
-
-def encoded(v, setup, seconds, seed, cuda, burst=False):
-    ch, rate = setup.channels, setup.rate
-    n = int(seconds * rate) // 1024 * 1024
-    sig = (burst_signal if burst else synth_signal)(ch, rate, n, seed=seed)
-    return encode_chunked(v, setup, sig, cuda)
+from tests.decode_calls import (Collect, assert_same, device_encode, encode_chunked, encoded, rows_tensor, runs_call,
+                                runs_inputs, stepwise)
+from tests.decode_packets import EINVAL, ENOTAUDIO, pack_setup
+from tests.signals import burst_signal, gen_windowed_sine
 
 
 CLASSES = ["mode_1ch_44100_q0.5.vpk", "mode_2ch_44100_q0.1.vpk", "mode_2ch_44100_q0.5.vpk", "mode_6ch_48000_q0.5.vpk",
@@ -332,10 +212,10 @@ def test_argument_errors(cuda):
     pk = encoded(v, setup, 1.0, 45, cuda)
     ds = v.DecodeSetup(v.header_packets(setup))
     dec = v.Decoder(ds, 4, 8)
-    data, offs, gp, eo = csr([pk[:4], pk[4:8]], cuda)
+    data, offs, gp, eo, _ = runs_inputs([pk[:4], pk[4:8]], cuda)
     with pytest.raises(v.VbmError, match=str(EINVAL)):
         dec.synthesis_runs([1, 1], [4, 4], data, offs)                         # duplicate ids
-    data9, offs9, _, _ = csr([pk[:5], pk[5:9]], cuda)
+    data9, offs9, _, _, _ = runs_inputs([pk[:5], pk[5:9]], cuda)
     with pytest.raises(v.VbmError, match=str(EINVAL)):
         dec.synthesis_runs([0, 1], [5, 4], data9, offs9)                       # P = 9 > max_batch = 8
     with pytest.raises(v.VbmError, match=str(EINVAL)):

@@ -1,55 +1,18 @@
 """Decoder, host side (no GPU): header parse against the shipped packs and an independent Python unpacker, the
 reference's error codes for malformed headers, exact parity of the packet unpack with the oracle's encode-side
 captures, truncated packets, and Ogg read-back."""
-import glob
 import os
 
 import numpy as np
 import pytest
 
 from tests import orc
-from tests.signals import burst_signal
-from tests.test_stream_wrapper import unpack_headers
-import vpk  # noqa: E402  (tools/, on the path once test_stream_wrapper is imported)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DATA = os.path.join(ROOT, "vorbis_aotuv_lancer_amd", "data")
-
-ENOTVORBIS, EBADHEADER, EVERSION, ENOTAUDIO, EBADPACKET, EIMPL, ENODEV = -132, -133, -134, -135, -136, -130, -1000
-
-# (channels, rate, quality): the classes of the unpack parity test
-PARITY = [(2, 44100, 0.5), (2, 44100, 0.1), (6, 48000, 0.8), (1, 44100, 0.5), (8, 44100, 0.5), (2, 96000, 0.5)]
+from tests.decode_packets import (DATA, EBADHEADER, EIMPL, ENODEV, ENOTAUDIO, ENOTVORBIS, EVERSION, PACKS, PARITY,
+                                  ROOT, BitReader, floor_expected, headers_of, oracle_packets, pack_setup,
+                                  residue_coded, unpack_book, unpack_headers, vpk)
 
 
-def pack_setup(v, pack):
-    d = vpk.read_vpk(os.path.join(DATA, pack))
-    ch, rate, q = int(d["info/channels"][0]), int(d["info/rate"][0]), float(d["info/quality"][0])
-    if int(d["info/managed"][0]):
-        av, mn, mx, _ = [int(x) for x in d["bi/rates"]]
-        return v.Setup(ch, rate, bitrate=(mx, av, mn)), d
-    return v.Setup(ch, rate, q), d
-
-
-def headers_of(ch, rate, q):
-    import vorbis_aotuv_lancer_amd as v
-    return v.header_packets(v.Setup(ch, rate, q))
-
-
-def oracle_packets(oracle, ch, rate, q, seconds=3.0, seed=3):
-    """oracle encode with capture of a burst signal (all four block types) -> list of block dicts"""
-    st = orc.Stream(orc.Setup(oracle, ch, rate, q))
-    sig = burst_signal(ch, rate, int(seconds * rate), seed=seed)
-    blocks = []
-    for i in range(0, sig.shape[1], 1024):
-        st.write(sig[:, i:i + 1024])
-        blocks.extend(st.blocks())
-    st.finish()
-    blocks.extend(st.blocks())
-    st.close()
-    return blocks
-
-
-@pytest.mark.parametrize("pack", sorted(os.path.basename(p) for p in glob.glob(os.path.join(DATA, "mode_*.vpk"))))
+@pytest.mark.parametrize("pack", PACKS)
 def test_header_parse_matches_the_pack_and_the_python_unpacker(pack):
     import vorbis_aotuv_lancer_amd as v
     setup, d = pack_setup(v, pack)
@@ -62,20 +25,6 @@ def test_header_parse_matches_the_pack_and_the_python_unpacker(pack):
     ds.close()
 
 
-class _Bits:
-    """bit positions of the fields the malformed-header tests edit (LSb-first packing)"""
-
-    def __init__(self, data):
-        self.d, self.pos = bytes(data), 0
-
-    def read(self, n):
-        v = 0
-        for i in range(n):
-            v |= ((self.d[(self.pos + i) >> 3] >> ((self.pos + i) & 7)) & 1) << i
-        self.pos += n
-        return v
-
-
 def set_bits(data, pos, n, value):
     b = bytearray(data)
     for i in range(n):
@@ -86,7 +35,6 @@ def set_bits(data, pos, n, value):
 
 def floor_type_bit(h2):
     """bit position of the first floor type field of a setup header (after the books and time placeholders)"""
-    from tests.test_stream_wrapper import BitReader, unpack_book
     r = BitReader(h2)
     for _ in range(7):
         r.read(8)
@@ -114,80 +62,10 @@ def test_malformed_headers_return_the_reference_codes():
     assert S([h0[:28] + bytes([(h0[28] & 0x0F) | (13 << 4)]) + h0[29:], h1, h2]) == EIMPL   # 8192
     # floor type 0
     pos = floor_type_bit(h2)
-    assert _Bits(h2[pos >> 3:]).read(8 + (pos & 7)) >> (pos & 7) == 1
+    assert BitReader(h2[pos >> 3:]).read(8 + (pos & 7)) >> (pos & 7) == 1
     assert S([h0, h1, set_bits(h2, pos, 16, 0)]) == EIMPL
     # a setup header cut short
     assert S([h0, h1, h2[:len(h2) // 2]]) == EBADHEADER
-
-
-def render_line(x0, x1, y0, y1, n):
-    """floor1_inverse2's render_line (lib/floor1.c:368) as indices, bins [x0, min(n, x1))"""
-    out = {}
-    dy, adx = y1 - y0, x1 - x0
-    base = int(dy / adx)
-    sy = base - 1 if dy < 0 else base + 1
-    ady = abs(dy) - abs(base) * adx
-    x, y, err = x0, y0, 0
-    if x < min(n, x1):
-        out[x] = y
-    x += 1
-    while x < min(n, x1):
-        err += ady
-        if err >= adx:
-            err -= adx
-            y += sy
-        else:
-            y += base
-        out[x] = y
-        x += 1
-    return out
-
-
-def floor_expected(ref, enc_x1, mode, ilogmask, n):
-    """The floor line a decoder renders, from the encoder's ilogmask capture.  Equal to the capture, except on a floor
-    whose last post the encoder keeps at an x the header cannot express: floor1_pack writes rangebits = ilog(x1) and
-    every decoder takes postlist[1] = 1 << rangebits (lib/floor1.c:119-182), so the 5.1 packs' LFE floor (posts
-    {0, 12}, no interior post) is encoded over [0, 12) and decoded over [0, 16).  There the expected line is rendered
-    from the capture's two end values over the header's range."""
-    want = np.array(ilogmask, copy=True)
-    m = ref["maps"][ref["modes"][mode][3]]
-    for c in range(want.shape[0]):
-        f = ref["floors"][m["floorsubmap"][m["chmuxlist"][c]]]
-        hx = f["postlist"][1]
-        ex = enc_x1[m["floorsubmap"][m["chmuxlist"][c]]]
-        if hx == ex or not want[c].any():
-            continue
-        assert len(f["postlist"]) == 2, "only a floor without interior posts can be restated from its end values"
-        y0, y1 = int(want[c, 0]), int(want[c, n - 1])
-        for x, y in render_line(0, hx, y0, y1, n).items():
-            want[c, x] = y
-        want[c, min(hx, n):] = y1
-    return want
-
-
-def residue_coded(ref, mode, ch, n, nonzero):
-    """mask [ch][n] of the bins the mode's residue setup codes (lib/res0.c:_01inverse / res2_inverse)"""
-    m = ref["maps"][ref["modes"][mode][3]]
-    mask = np.zeros((ch, n), bool)
-    for sm in range(m["submaps"]):
-        r = ref["residues"][m["residuesubmap"][sm]]
-        chans = [c for c in range(ch) if m["chmuxlist"][c] == sm]
-        if r["type"] == 2:
-            if not any(nonzero[c] for c in chans):
-                continue
-            nb = len(chans)
-            end = min(r["end"], n * nb)
-            coded = (end - r["begin"]) // r["grouping"] * r["grouping"]
-            for i, c in enumerate(chans):
-                k = np.arange(n) * nb + i
-                mask[c] = (k >= r["begin"]) & (k < r["begin"] + coded)
-        else:
-            end = min(r["end"], n)
-            coded = (end - r["begin"]) // r["grouping"] * r["grouping"]
-            for c in chans:
-                if nonzero[c]:
-                    mask[c, r["begin"]:r["begin"] + max(coded, 0)] = True
-    return mask
 
 
 @pytest.mark.parametrize("ch,rate,q", PARITY)

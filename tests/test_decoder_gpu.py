@@ -2,8 +2,6 @@
 oracle's captures, PCM within a bound of a float64 IMDCT + window + overlap-add and bit for bit against the oracle's
 scalar inverse MDCT + float32 window + overlap-add, the reference's own round-trip test (test/test.c), a full-size
 batch, and the API edges."""
-import functools
-import glob
 import os
 
 import numpy as np
@@ -11,34 +9,10 @@ import pytest
 import torch
 
 from tests import orc
-from tests.signals import burst_signal, synth_signal
-from tests.test_decoder_cpu import (DATA, ENOTAUDIO, PARITY, floor_expected, oracle_packets, pack_setup,
-                                    residue_coded)
-from tests.test_reference_input_gpu import classes, gen_windowed_sine
-from tests.test_stream_wrapper import unpack_headers
-import vpk  # noqa: E402  (tools/, on the path once test_stream_wrapper is imported)
-
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-PACKS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(DATA, "mode_*.vpk")))
-EINVAL = -131
-
-
-def rows_tensor(packets, dev, stride=None):
-    stride = stride or max(1, max(len(p) for p in packets))
-    a = np.zeros((len(packets), stride), np.uint8)
-    for i, p in enumerate(packets):
-        a[i, :len(p)] = np.frombuffer(p, np.uint8)
-    nb = np.array([len(p) for p in packets], np.int32)
-    return torch.from_numpy(a).to(dev), torch.from_numpy(nb).to(dev)
-
-
-def split_dump(d):
-    out, at = [], 0
-    while at < len(d):
-        n = int.from_bytes(d[at:at + 4], "little")
-        out.append(d[at + 4:at + 4 + n])
-        at += 4 + n
-    return out
+from tests.decode_calls import check_pcm_bound, check_pcm_exact, decode_one, device_encode, rows_tensor
+from tests.decode_packets import (DATA, DUMPS, EINVAL, ENOTAUDIO, PACKS, PARITY, dump_packets, floor_expected,
+                                  matrix_classes, oracle_packets, pack_setup, residue_coded, unpack_headers, vpk)
+from tests.signals import gen_windowed_sine, synth_signal
 
 
 def pack_oracle_packets(oracle, pack, seconds=2.0):
@@ -48,17 +22,7 @@ def pack_oracle_packets(oracle, pack, seconds=2.0):
     if int(d["info/managed"][0]):
         av, mn, mx, _ = [int(x) for x in d["bi/rates"]]
         bitrate = (mx, av, mn)
-    st = orc.Stream(orc.Setup(oracle, ch, rate, None if bitrate else q, bitrate=bitrate))
-    oracle.lib.orc_stream_set_capture(st.v, 0)
-    sig = burst_signal(ch, rate, int(seconds * rate), seed=11)
-    out = []
-    for i in range(0, sig.shape[1], 1024):
-        st.write(sig[:, i:i + 1024])
-        out += [b["packet"] for b in st.blocks()]
-    st.finish()
-    out += [b["packet"] for b in st.blocks()]
-    st.close()
-    return out
+    return [b["packet"] for b in oracle_packets(oracle, ch, rate, q, seconds, seed=11, bitrate=bitrate, capture=False)]
 
 
 def device_vs_host(ds, dec, packets, dev):
@@ -100,14 +64,11 @@ def test_device_unpack_equals_host_unpack(oracle, cuda, pack):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("ch,rate,q,golden", [
-    (2, 44100, 0.5, "ref_scalar_2ch_44100_q05_20s.pkt"),
-    (6, 48000, 0.8, "ref_scalar_6ch_48000_q08_10s.pkt"),
-])
+@pytest.mark.parametrize("ch,rate,q,golden", DUMPS)
 def test_device_unpack_of_the_reference_dumps(oracle, cuda, ch, rate, q, golden):
     import vorbis_aotuv_lancer_amd as v
     ds = v.DecodeSetup(v.header_packets(v.Setup(ch, rate, q)))
-    packets = split_dump(open(os.path.join(G, golden), "rb").read())
+    packets = dump_packets(golden)
     dec = v.Decoder(ds, len(packets), len(packets))
     device_vs_host(ds, dec, packets, cuda)
     dec.close()
@@ -151,149 +112,6 @@ def restated_spectrum(ref, fromdB, enc_x1, b, mode, n):
     return out.astype(np.float32)
 
 
-@functools.lru_cache(maxsize=None)
-def _cosines(N):
-    k, t = np.arange(N // 2), np.arange(N)
-    return np.cos(2 * np.pi / N * np.outer(t + 0.5 + N / 4, k + 0.5))
-
-
-def imdct64(X):
-    """float64 mdct_backward: C^T X with C[k, n] = cos(2 pi / N (n + 1/2 + N/4)(k + 1/2)) (the reference's forward is
-    4/N C x; window, forward, backward, window and overlap-add return the input)"""
-    return _cosines(2 * len(X)) @ X.astype(np.float64)
-
-
-def overlap64(tail, lW, p, W, bs, win):
-    """vorbis_synthesis_blockin's overlap-add in float64: what becomes final, and the new tail"""
-    n0, n1 = bs[0] // 2, bs[1] // 2
-    w0, w1 = win[0].astype(np.float64), win[1].astype(np.float64)
-    n = bs[W] // 2
-    if lW < 0:
-        return np.zeros(0), p[n:2 * n].copy()
-    if lW == 1 and W == 1:
-        out = tail[:n1] * w1[::-1] + p[:n1] * w1
-    elif lW == 1:
-        off = n1 // 2 - n0 // 2
-        out = np.concatenate([tail[:off], tail[off:off + n0] * w0[::-1] + p[:n0] * w0])
-    elif W == 1:
-        off = n1 // 2 - n0 // 2
-        out = np.concatenate([tail[:n0] * w0[::-1] + p[off:off + n0] * w0, p[off + n0:off + n0 + off]])
-    else:
-        out = tail[:n0] * w0[::-1] + p[:n0] * w0
-    return out, p[n:2 * n].copy()
-
-
-def check_pcm_bound(ds, streams_pk, pcm_steps, spec_steps, info_steps, samples_steps, win=None, peaks=None):
-    """per stream: the device PCM of every step against float64 IMDCT + window + OLA of the fetched spectrum.
-    win: the two windows' rising halves (default: the product's own table); peaks: a list that receives every step's
-    float64 peak"""
-    import vorbis_aotuv_lancer_amd as v
-    bs = ds.blocksizes
-    if win is None:
-        win = [v.window_table(bs[0]), v.window_table(bs[1])]
-    worst = 0.0
-    for s in range(len(streams_pk)):
-        tail, lW = None, -1
-        for t in range(len(streams_pk[s])):
-            W = int(info_steps[t][s][1])
-            n = bs[W] // 2
-            p = np.stack([imdct64(spec_steps[t][s][c][:n]) for c in range(ds.channels)])
-            outs, tails = [], []
-            for c in range(ds.channels):
-                o, tl = overlap64(tail[c] if tail is not None else None, lW, p[c], W, bs, win)
-                outs.append(o)
-                tails.append(tl)
-            tail, lW = tails, W
-            want = np.stack(outs)
-            ns = int(samples_steps[t][s])
-            # the end-of-stream packet is trimmed to its granule position (lib/block.c:1084-1161): the first ns stay
-            last = t == len(streams_pk[s]) - 1
-            assert ns == want.shape[1] or (last and ns < want.shape[1]), (s, t, ns, want.shape[1])
-            want = want[:, :ns]
-            got = pcm_steps[t][s][:, :ns].astype(np.float64)
-            if ns:
-                if peaks is not None:
-                    peaks.append(float(np.abs(want).max()))
-                peak = max(np.abs(want).max(), 1e-3)
-                err = np.abs(got - want).max()
-                worst = max(worst, err / peak)
-                assert err <= 1e-5 * peak, f"stream {s} step {t}: max error {err} at peak {peak}"
-    return worst
-
-
-def overlap32(tail, lW, p, W, n0, n1, w0, w1):
-    """overlap64 in float32: numpy rounds each product and the sum separately, as vorbis_synthesis_blockin's scalar
-    pcm[i]*w[n-i-1] + p[i]*w[i] does with contraction off.  n0 / n1: half the two block sizes (a quarter at half
-    rate), w0 / w1 the rising half windows of those lengths"""
-    n = n1 if W else n0
-    if lW < 0:
-        return np.zeros(0, np.float32), p[n:2 * n].copy()
-    if lW == 1 and W == 1:
-        out = tail[:n1] * w1[::-1] + p[:n1] * w1
-    elif lW == 1:
-        off = n1 // 2 - n0 // 2
-        out = np.concatenate([tail[:off], tail[off:off + n0] * w0[::-1] + p[:n0] * w0])
-    elif W == 1:
-        off = n1 // 2 - n0 // 2
-        out = np.concatenate([tail[:n0] * w0[::-1] + p[off:off + n0] * w0, p[off + n0:off + n0 + off]])
-    else:
-        out = tail[:n0] * w0[::-1] + p[:n0] * w0
-    assert out.dtype == np.float32
-    return out, p[n:2 * n].copy()
-
-
-def ulps_apart(a, b):
-    """distance of two float32 values in representable values (-0.0 and 0.0 are 0 apart)"""
-    def key(x):
-        i = int(np.array(x, np.float32).view(np.int32))
-        return i if i >= 0 else -(i & 0x7fffffff)
-    return abs(key(a) - key(b))
-
-
-def check_pcm_exact(oracle, ds, streams_pk, pcm_steps, spec_steps, info_steps, samples_steps, halfrate=False):
-    """check_pcm_bound's walk with a float32 yardstick and no tolerance: the device PCM of every step, stream and
-    channel equals (np.array_equal) the oracle's scalar inverse MDCT (oracle/orc_mdct.c: orc_mdct_backward, itself
-    checked against the float64 definition in tests/test_oracle_mdct.py) of the float32 spectrum, overlap-added in
-    float32 with the product's own window tables, the tail carried in float32.  At half rate the transform has half the
-    block's points over the lower half of the bins, and the windows are those of half the size.
-    -> the number of (step, stream) pairs compared"""
-    import vorbis_aotuv_lancer_amd as v
-    bs = ds.blocksizes
-    hs = 1 if halfrate else 0
-    n0, n1 = bs[0] >> (1 + hs), bs[1] >> (1 + hs)
-    w0, w1 = v.window_table(bs[0] >> hs), v.window_table(bs[1] >> hs)
-    assert w0.dtype == np.float32 and w1.dtype == np.float32 and (len(w0), len(w1)) == (n0, n1)
-    compared = 0
-    for s in range(len(streams_pk)):
-        tail, lW = None, -1
-        for t in range(len(streams_pk[s])):
-            W = int(info_steps[t][s][1])
-            N = bs[W] >> hs                                            # points of the transform
-            spec = np.stack([np.asarray(spec_steps[t][s][c][:N // 2], np.float32) for c in range(ds.channels)])
-            p = oracle.mdct_backward(spec)
-            outs, tails = [], []
-            for c in range(ds.channels):
-                o, tl = overlap32(tail[c] if tail is not None else None, lW, p[c], W, n0, n1, w0, w1)
-                outs.append(o)
-                tails.append(tl)
-            tail, lW = tails, W
-            want = np.stack(outs)
-            ns = int(samples_steps[t][s])
-            last = t == len(streams_pk[s]) - 1
-            assert ns == want.shape[1] or (last and ns < want.shape[1]), (s, t, ns, want.shape[1])
-            want = want[:, :ns]
-            got = pcm_steps[t][s][:, :ns]
-            assert got.dtype == np.float32 and want.dtype == np.float32
-            if not np.array_equal(got, want):
-                c, i = (int(x[0]) for x in np.nonzero(got != want))
-                raise AssertionError(
-                    f"stream {s} step {t} channel {c} sample {i} (block of {bs[W]}, after {'none' if lW < 0 else bs[lW]}"
-                    f"{', half rate' if hs else ''}): device {float(got[c, i]):.9g}, scalar inverse MDCT {float(want[c, i]):.9g}, "
-                    f"{ulps_apart(got[c, i], want[c, i])} ulps apart; {int((got != want).sum())} of {got.size} differ")
-            compared += 1 if ns else 0
-    return compared
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("ch,rate,q", PARITY)
 def test_spectrum_exact_and_pcm_bounded(oracle, cuda, ch, rate, q):
@@ -333,42 +151,8 @@ def test_spectrum_exact_and_pcm_bounded(oracle, cuda, ch, rate, q):
     ds.close()
 
 
-def device_encode(v, setup, sig, cuda, S=1):
-    """device front end, end of stream declared: -> per stream [(packet, granulepos, eos)]"""
-    enc = v.Encoder(setup, S)
-    fe = v.FrontEnd(enc)
-    fe.write(torch.from_numpy(np.repeat(sig[None], S, axis=0)).to(cuda))
-    fe.finish()
-    got = [[] for _ in range(S)]
-    while True:
-        info, packets, nbytes = fe.encode_round()
-        if len(info) == 0:
-            break
-        packets, nbytes = packets.cpu().numpy(), nbytes.cpu().numpy()
-        for k, pi in enumerate(info):
-            got[int(pi["stream"])].append((bytes(packets[k, :nbytes[k]]), int(pi["granulepos"]), int(pi["eos"])))
-    fe.close()
-    enc.close()
-    return got
-
-
-def decode_one(v, ds, packets, cuda):
-    """one stream, one packet per call, with granulepos and eos -> decoded PCM [ch, n]"""
-    dec = v.Decoder(ds, 1, 1)
-    out = []
-    for p, gp, eos in packets:
-        pk, nb = rows_tensor([p], cuda)
-        pcm, samples, status = dec.synthesis_batch(
-            [0], pk, nb, granulepos=torch.tensor([gp], dtype=torch.int64, device=cuda),
-            eos=torch.tensor([eos], dtype=torch.uint8, device=cuda))
-        assert int(status[0]) == 0
-        out.append(pcm[0, :, :int(samples[0])].cpu().numpy())
-    dec.close()
-    return np.concatenate(out, axis=1)
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("ch,rate,q,bitrate", [c + (None,) for c in classes()] + [(2, 44100, None, 128000),
+@pytest.mark.parametrize("ch,rate,q,bitrate", [c + (None,) for c in matrix_classes()] + [(2, 44100, None, 128000),
                                                                                    (6, 48000, 0.8, None)])
 def test_reference_round_trip(cuda, ch, rate, q, bitrate):
     """test/test.c: the windowed sine of test/util.c, encoded with end of stream, decodes to exactly its 2048 samples

@@ -9,9 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_decode_ranges_gpu import FILL, as_stream
-from tests.test_decode_runs_gpu import csr, encoded
-from tests.test_decoder_gpu import rows_tensor
+from tests.decode_calls import FILL_RANGES, batch_inputs, encoded, runs_inputs
+from tests.decode_packets import as_stream
 
 MAX_BATCH = 8                                              # one staging slot: 4 * 8 + 1 ints, 32 streams' first packets
 INDEX_STREAMS = 40                                         # more than that: two k_index_scan launches, two slots
@@ -34,26 +33,24 @@ def run_sequence(v, headers, pk, cuda, halfrate, sync):
     dec = v.Decoder(ds, 2, MAX_BATCH, halfrate=halfrate)
     failed = (headers[0], -1, 0)                           # a header where audio belongs: ENOTAUDIO, no samples
     store = v.RangeStore(dec, [as_stream(pk), as_stream(pk[:30]), as_stream(pk[:12] + [failed] + pk[12:25])])
-    one_packet = csr([[p] for p in pk[:INDEX_STREAMS]], cuda)
+    one_packet = runs_inputs([[p] for p in pk[:INDEX_STREAMS]], cuda)[:4]
     first = np.arange(INDEX_STREAMS + 1, dtype=np.int64)
     # every input and output buffer of every call is made here, before the first call, and held to the end: an upload
     # waits for the stream, so the loop below holds decoder calls only
     plan = []
     for c in range(CYCLES):
         a = 5 * c
-        rows = rows_tensor([pk[a][0], pk[a + 1][0]], cuda)
-        gp = torch.tensor([pk[a][1], pk[a + 1][1]], dtype=torch.int64, device=cuda)
-        eo = torch.tensor([pk[a][2], pk[a + 1][2]], dtype=torch.uint8, device=cuda)
+        *rows, gp, eo = batch_inputs(pk[a:a + 2], cuda)
         runs = [pk[a + 2:a + 4] + [failed] + pk[a + 4:a + 6], pk[a + 1:a + 4]]      # 5 + 3 rows
         windows = ([0, 1, 2, 0], [100 * c, 3000, 4000 + c, 7000], [9000, 9000, 5000, 2000 + c])
-        buf = torch.full((4, dec.channels, 9000), FILL, dtype=torch.float32, device=cuda)
+        buf = torch.full((4, dec.channels, 9000), FILL_RANGES, dtype=torch.float32, device=cuda)
         row = dec.row
         outs = dict(batch=(torch.zeros((2, dec.channels, row), dtype=torch.float32, device=cuda),
                            torch.zeros(2, dtype=torch.int32, device=cuda), torch.zeros(2, dtype=torch.int32, device=cuda)),
                     runs=(torch.zeros((2, dec.channels, 5 * row), dtype=torch.float32, device=cuda),
                           torch.zeros(2, dtype=torch.int32, device=cuda), torch.zeros(8, dtype=torch.int32, device=cuda),
                           torch.zeros(8, dtype=torch.int32, device=cuda)))
-        plan.append((rows, gp, eo, [len(r) for r in runs], csr(runs, cuda), windows, buf, outs))
+        plan.append((rows, gp, eo, [len(r) for r in runs], runs_inputs(runs, cuda), windows, buf, outs))
     # decode_index_device makes its own outputs: blocks of their sizes are left with torch's allocator, so that it has
     # nothing to ask the device for inside the loop
     spare = [torch.empty(INDEX_STREAMS, dtype=dt, device=cuda) for _ in range(CYCLES)
@@ -105,6 +102,6 @@ def test_back_to_back_calls_equal_synchronised_calls(cuda, material):
         # the sequence crossed what it is meant to: a failed packet among the runs, ranges of several sub-calls, PCM
         by = {name: out for name, out in want}
         assert (by["runs"][3] != 0).sum() == 1 and by["runs"][1].min() > 0
-        assert by["ranges"][1][0] == 9000 and by["ranges"][1].sum() > 15000 and np.any(by["ranges"][0] != FILL)
+        assert by["ranges"][1][0] == 9000 and by["ranges"][1].sum() > 15000 and np.any(by["ranges"][0] != FILL_RANGES)
         assert by["index"][4].shape == (INDEX_STREAMS,) and np.all(by["index"][0] == 0)
         assert by["batch"][1].max() > 0 and np.abs(by["batch"][0]).max() > 0

@@ -6,8 +6,6 @@ reference's packet dumps it must equal the host unpack, and its dequantiser must
 vectors.  Then header round trips, the generated corpus (host unpack = model, bit for bit, on every packet), a
 coverage assertion that names what a later change of the generator dropped, and setups the decoder must reject."""
 import copy
-import functools
-import glob
 import os
 
 import numpy as np
@@ -15,36 +13,9 @@ import pytest
 
 from tests import orc
 from tests import vorbis_model as vm
-from tests.test_decoder_cpu import (DATA, EBADHEADER, EIMPL, PARITY, floor_expected, headers_of, oracle_packets,
-                                    pack_setup, residue_coded)
-from tests.test_sharedbook_vectors import Q_DELTA, Q_MIN, QUANTLIST, TEST4, TEST5
-from tests.test_stream_wrapper import unpack_headers
-import vpk  # noqa: E402  (tools/, on the path once test_stream_wrapper is imported)
-
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-PACKS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(DATA, "mode_*.vpk")))
-NAMES = [name for name, _ in vm.CORPUS]
-
-
-def fromdB():
-    import vorbis_aotuv_lancer_amd as v
-    return v.tables.pack("common.vpk")["FLOOR1_fromdB_LOOKUP"]
-
-
-def same(got, want):
-    """host unpack (status, info, floor index, residue, used) against a model result -> what differs, or None"""
-    rc, info, findex, res, used = got
-    if rc != want["status"]:
-        return f"status {rc}, model {want['status']}"
-    if list(info) != want["info"]:
-        return f"info {list(info)}, model {want['info']}"
-    if not np.array_equal(used, want["used"]):
-        return f"floor used {used}, model {want['used']}"
-    if not np.array_equal(findex, want["floor_index"]):
-        return f"floor index at {np.argwhere(findex != want['floor_index'])[:4].tolist()}"
-    if res.tobytes() != want["residue"].tobytes():
-        return f"residue at {np.argwhere(res != want['residue'])[:4].tolist()}"
-    return None
+from tests.decode_packets import (DATA, DUMPS, EBADHEADER, EIMPL, NAMES, PACKS, PARITY, QUANTLIST, Q_DELTA, Q_MIN,
+                                  TEST4, TEST5, dump_packets, family, floor_expected, fromdB, headers_of,
+                                  oracle_packets, pack_setup, residue_coded, unpack_differs, unpack_headers, vpk)
 
 
 # ---- the model is checked first ------------------------------------------------------------------------------------
@@ -76,28 +47,16 @@ def test_model_matches_the_oracle_captures_exactly(oracle, ch, rate, q):
         assert {(0, 0, 0), (0, 1, 1), (1, 1, 0), (1, 1, 1)} <= kinds, kinds
 
 
-def split_dump(d):
-    out, at = [], 0
-    while at < len(d):
-        n = int.from_bytes(d[at:at + 4], "little")
-        out.append(d[at + 4:at + 4 + n])
-        at += 4 + n
-    return out
-
-
-@pytest.mark.parametrize("ch,rate,q,golden", [
-    (2, 44100, 0.5, "ref_scalar_2ch_44100_q05_20s.pkt"),
-    (6, 48000, 0.8, "ref_scalar_6ch_48000_q08_10s.pkt"),
-])
+@pytest.mark.parametrize("ch,rate,q,golden", DUMPS)
 def test_model_equals_host_unpack_on_the_reference_dumps(ch, rate, q, golden):
     import vorbis_aotuv_lancer_amd as v
     h = headers_of(ch, rate, q)
     ds = v.DecodeSetup(h)
     model = vm.Model(unpack_headers(*h), fromdB())
-    packets = split_dump(open(os.path.join(G, golden), "rb").read())
+    packets = dump_packets(golden)
     assert len(packets) > 400
     for k in range(len(packets)):
-        diff = same(ds.unpack(packets[k]), model.decode(packets[k]))
+        diff = unpack_differs(ds.unpack(packets[k]), model.decode(packets[k]))
         assert diff is None, f"packet {k}: {diff}"
     ds.close()
 
@@ -130,28 +89,6 @@ def test_pack_headers_rewrites_every_shipped_setup_header_byte_for_byte(pack):
     h = v.header_packets(setup, ["TITLE=round trip"])
     assert vm.pack_headers(unpack_headers(*h)) == tuple(h)
     setup.close()
-
-
-@functools.lru_cache(maxsize=None)
-def family(k):
-    """-> (setup dict, header coding, headers, model counters, [(label, packet, model result)], ds facts, mismatches)"""
-    import vorbis_aotuv_lancer_amd as v
-    setup, coding = vm.build_corpus_setup(k)
-    h = vm.pack_headers(setup, coding)
-    assert v.DecodeSetup.status(h) == 0, v.lib.vbm_last_error()
-    ds = v.DecodeSetup(h)
-    facts = (ds.counts(), list(ds.blocksizes), ds.modes, ds.channels)
-    model = vm.Model(setup, fromdB())
-    rows, bad = [], []
-    for label, p in vm.corpus_packets(model, h, 5000 + k):
-        r = model.decode(p)
-        vm.check_scales(r)
-        diff = same(ds.unpack(p), r)
-        if diff:
-            bad.append(f"{label}: {diff}")
-        rows.append((label, p, r))
-    ds.close()
-    return setup, coding, h, dict(model.C), rows, facts, bad
 
 
 @pytest.mark.parametrize("k", range(len(vm.CORPUS)), ids=NAMES)

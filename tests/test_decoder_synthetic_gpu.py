@@ -3,34 +3,16 @@ independent model (tests/vorbis_model.py) on the generated corpus, PCM of every 
 bound of a float64 IMDCT + float64 Vorbis window + overlap-add, the runs and ranges paths against the stepwise one on
 synthetic setups, and batches whose row x channel counts do not fill the IMDCT kernels' groups.  The PCM of the
 block-size pairs, of those batches and of one mono stream alone is also compared bit for bit with the oracle's scalar
-inverse MDCT (tests/test_decoder_gpu.py: check_pcm_exact)."""
+inverse MDCT (tests/decode_calls.py: check_pcm_exact)."""
 import numpy as np
 import pytest
-import torch
 
 from tests import vorbis_model as vm
-from tests.test_decode_ranges_gpu import as_stream, check, ranges
-from tests.test_decode_runs_gpu import runs_call, stepwise
-from tests.test_decoder_gpu import check_pcm_bound, check_pcm_exact, rows_tensor
-from tests.test_decoder_model_cpu import NAMES, family, fromdB
+from tests.decode_calls import (against_model, batch_inputs, check, check_pcm_bound, check_pcm_exact, ranges,
+                                rows_tensor, runs_call, stepwise)
+from tests.decode_packets import NAMES, RUNS, as_stream, family, fromdB, with_failed_packets
 
 PAIR_IDS = [f"{a}_{b}" for a, b in vm.PAIRS]
-
-
-def against_model(dec, results, status, samples, what):
-    """the intermediates of the last call against the model's results, row by row"""
-    got = {n: dec.fetch(n).cpu().numpy() for n in ("info", "floor_used", "floor_index", "residue", "spectrum")}
-    for k, r in enumerate(results):
-        assert status[k] == r["status"], f"{what} row {k}: status"
-        if r["status"]:
-            assert samples[k] == 0 and not got["spectrum"][k].any(), f"{what} row {k}: a failed row gives nothing"
-            continue
-        assert list(got["info"][k]) == r["info"], f"{what} row {k}: info"
-        assert np.array_equal(got["floor_used"][k], r["used"]), f"{what} row {k}: floor used"
-        assert np.array_equal(got["floor_index"][k], r["floor_index"]), f"{what} row {k}: floor index"
-        assert got["residue"][k].tobytes() == r["residue"].tobytes(), f"{what} row {k}: residue"
-        assert got["spectrum"][k].tobytes() == r["spectrum"].tobytes(), f"{what} row {k}: spectrum"
-    return got
 
 
 @pytest.mark.gpu
@@ -58,9 +40,7 @@ def decode_steps(v, ds, model, streams, cuda, what):
     dec = v.Decoder(ds, S, S)
     pcm_steps, spec_steps, info_steps, samples_steps = [], [], [], []
     for t in range(T):
-        pk, nb = rows_tensor([streams[s][t][0] for s in range(S)], cuda)
-        gp = torch.tensor([streams[s][t][1] for s in range(S)], dtype=torch.int64, device=cuda)
-        eo = torch.tensor([streams[s][t][2] for s in range(S)], dtype=torch.uint8, device=cuda)
+        pk, nb, gp, eo = batch_inputs([streams[s][t] for s in range(S)], cuda)
         pcm, samples, status = dec.synthesis_batch(list(range(S)), pk, nb, granulepos=gp, eos=eo)
         samples, status = samples.cpu().numpy(), status.cpu().numpy()
         got = against_model(dec, [model.decode(streams[s][t][0]) for s in range(S)], status, samples, f"{what} step {t}")
@@ -106,27 +86,6 @@ def test_pcm_of_every_block_size_pair_is_within_the_bound(oracle, cuda, k):
     exact = check_pcm_exact(oracle, ds, streams, *steps)
     print(f"block sizes {PAIR_IDS[k]}: {exact} steps x streams equal the scalar inverse MDCT bit for bit")
     ds.close()
-
-
-def with_failed_packets(streams, headers, modes, modebits):
-    """the streams with packets that fail inside them: a header packet, the empty packet, a mode past the last"""
-    out = []
-    for s, pk in enumerate(streams):
-        pk = list(pk)
-        pk.insert(3, (headers[2], -1, 0))
-        pk.insert(6, (b"", -1, 0))
-        if modes < (1 << modebits):
-            w = vm.BitWriter()
-            w.write(0, 1)
-            w.write(modes, modebits)
-            w.write(0xABCDE, 20)
-            pk.insert(2 + s, (w.tobytes(), -1, 0))
-        out.append(pk)
-    return out
-
-
-# one setup per residue type (the 256/256 one has bs0 = bs1), and a pair of equal large blocks
-RUNS = [("pair_256_256_grouping1", 0), ("res0", 2), ("res2", 1), ("res1_3modes", 3), ("pair_1024_1024", 9)]
 
 
 @pytest.mark.gpu
@@ -223,11 +182,9 @@ def test_one_mono_stream_alone_equals_the_scalar_inverse_mdct(oracle, cuda, bs, 
     dec = v.Decoder(ds, S, S, halfrate=halfrate)
     pcm_steps, spec_steps, info_steps, samples_steps = [], [], [], []
     for t in range(T):
-        p, gp, eo = streams[0][t]
-        pk, nb = rows_tensor([p], cuda)
-        pcm, samples, status = dec.synthesis_batch([0], pk, nb,
-                                                   granulepos=torch.tensor([gp], dtype=torch.int64, device=cuda),
-                                                   eos=torch.tensor([eo], dtype=torch.uint8, device=cuda))
+        p = streams[0][t][0]
+        pk, nb, gp, eo = batch_inputs([streams[0][t]], cuda)
+        pcm, samples, status = dec.synthesis_batch([0], pk, nb, granulepos=gp, eos=eo)
         assert not status.cpu().numpy().any()
         r = model.decode(p)
         spec = dec.fetch("spectrum").cpu().numpy()

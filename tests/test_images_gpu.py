@@ -92,8 +92,7 @@ def test_decoder_on_copies_and_negatives(oracle, cuda, c):
     inverse MDCT, the window and the overlap-add are sums and products, which round alike for x and -x.  (Inverted at
     q0.5 decodes to a mix of negated and copied bins, so its PCM has no such property; its spectrum is compared.)"""
     import vorbis_aotuv_lancer_amd as v
-    from tests.test_decode_runs_gpu import runs_call
-    from tests.test_decoder_synthetic_gpu import against_model
+    from tests.decode_calls import against_model, runs_call
     streams = [(image, kind) for c2, image, kind in DECODED if c2 == c]
     decoded = [model_spectra(oracle, c, image) for image, _ in streams]
     runs = [[(b["packet"], b["granulepos"], b["eos"]) for b in blks] for _, blks, _ in decoded]

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 
 from tests import ogg_cut_cases as K
-from tests.ogg_cut_cases import ECAP, EINVAL, ESHAPE
+from tests.decode_packets import EINVAL
+from tests.ogg_cut_cases import ECAP, ESHAPE
 
 
 def agree(store, ranges, decodable=True):

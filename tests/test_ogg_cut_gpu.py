@@ -8,7 +8,8 @@ import torch
 
 from tests import ogg_cut_cases as K
 from tests import ogg_select_cases as S
-from tests.ogg_cut_cases import ECAP, EINVAL, ESHAPE
+from tests.decode_packets import EINVAL
+from tests.ogg_cut_cases import ECAP, ESHAPE
 from tests.signals import synth_signal
 from tests.ogg_pages import split_pages
 

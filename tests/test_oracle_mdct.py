@@ -59,7 +59,7 @@ def test_oracle_window_regions(oracle):
 
 # ---- the scalar inverse (orc_mdct_backward): the yardstick of the device decoder's PCM ---------------------------------
 def imdct_basis(n):
-    """float64 mdct_backward as tests/test_decoder_gpu.py's imdct64 defines it: out = B X with
+    """float64 mdct_backward as tests/decode_calls.py's imdct64 defines it: out = B X with
     B[t, k] = cos(2 pi / n (t + 1/2 + n/4)(k + 1/2)); the forward above is 4/n B^T x"""
     t = np.arange(n)[:, None]
     k = np.arange(n // 2)[None, :]

@@ -8,19 +8,11 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_decode_index_scan_cpu import BS, join, one_byte_corpus, serial_index
-from tests.test_decode_ranges_gpu import FILL, as_stream, ranges
-from tests.test_decode_runs_gpu import encoded, runs_call
-from tests.test_decoder_cpu import pack_setup
-from tests.test_decoder_gpu import rows_tensor
+from tests.decode_calls import encoded, ranges, rows_tensor, runs_call, to_dev
+from tests.decode_packets import BS, EINVAL, as_stream, join, one_byte_corpus, pack_setup, serial_index
 
-EINVAL = -131
 GUARD = 64                                                 # canary elements on either side of every output
 CANARY = {torch.int32: 0x5a5a5a5a, torch.int64: 0x5a5a5a5a5a5a5a5a}
-
-
-def to_dev(x, cuda):
-    return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(cuda)
 
 
 def device_index(dec, data, offsets, gp, eos, first, cuda):

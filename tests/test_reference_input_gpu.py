@@ -6,30 +6,16 @@ reference's matrix (test/test.c:38-57: 1..8 channels x {44100, 48000, 32000, 220
 shipped mode pack, at the pack's quality: block sequence and packets against the oracle, through the batched front
 end and through the reference's own entry points (include/vorbis_compat.h)."""
 import ctypes as C
-import glob
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from tests import compat, orc
+from tests.decode_packets import matrix_classes
 from tests.signals import gen_windowed_sine
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def classes():
-    """(channels, rate, quality) of the shipped VBR packs that lie in the reference's test matrix"""
-    out = []
-    for f in sorted(glob.glob(os.path.join(ROOT, "vorbis_aotuv_lancer_amd", "data", "mode_*ch_*_q*.vpk"))):
-        m = re.match(r"mode_(\d+)ch_(\d+)_q(-?[\d.]+)\.vpk", os.path.basename(f))
-        ch, rate, q = int(m.group(1)), int(m.group(2)), float(m.group(3))
-        if 1 <= ch <= 8 and rate in (44100, 48000, 32000, 22050, 16000, 96000):
-            out.append((ch, rate, q))
-    return out
 
 
 def oracle_blocks(oracle, ch, rate, q, pcm):
@@ -43,11 +29,11 @@ def oracle_blocks(oracle, ch, rate, q, pcm):
 
 
 def test_matrix_is_not_empty():
-    cl = classes()
+    cl = matrix_classes()
     assert len(cl) >= 20 and {c[0] for c in cl} == {1, 2, 3, 4, 5, 6, 7, 8} and 96000 in {c[1] for c in cl}
 
 
-@pytest.mark.parametrize("ch,rate,q", classes())
+@pytest.mark.parametrize("ch,rate,q", matrix_classes())
 def test_windowed_sine_then_eos(oracle, cuda, ch, rate, q):
     import vorbis_aotuv_lancer_amd as v
     sine = gen_windowed_sine()

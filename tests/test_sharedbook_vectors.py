@@ -7,18 +7,7 @@ oracle (oracle/orc_book.c) and for the product's host code (csrc/setup_host.cpp)
 reference's expected arrays imply."""
 import ctypes as C
 
-import numpy as np
-
-Q_MIN, Q_DELTA = -533200896, 1611661312          # lib/sharedbook.c:513, :524, :535, :554
-QUANTLIST = [0, 7, 2]                            # partial_quantlist1, :492
-# test4_result (:539-547): entry e, component k -> quantlist[(e / 3^k) % 3] * delta + min, non-sequential
-TEST4 = [-3, -3, -3, 4, -3, -3, -1, -3, -3, -3, 4, -3, 4, 4, -3, -1, 4, -3, -3, -1, -3, 4, -1, -3, -1, -1, -3,
-         -3, -3, 4, 4, -3, 4, -1, -3, 4, -3, 4, 4, 4, 4, 4, -1, 4, 4, -3, -1, 4, 4, -1, 4, -1, -1, 4,
-         -3, -3, -1, 4, -3, -1, -1, -3, -1, -3, 4, -1, 4, 4, -1, -1, 4, -1, -3, -1, -1, 4, -1, -1, -1, -1, -1]
-# test5_result (:558-566): the same book with q_sequencep = 1 (running sums along the dimension)
-TEST5 = [-3, -6, -9, 4, 1, -2, -1, -4, -7, -3, 1, -2, 4, 8, 5, -1, 3, 0, -3, -4, -7, 4, 3, 0, -1, -2, -5,
-         -3, -6, -2, 4, 1, 5, -1, -4, 0, -3, 1, 5, 4, 8, 12, -1, 3, 7, -3, -4, 0, 4, 3, 7, -1, -2, 2,
-         -3, -6, -7, 4, 1, 0, -1, -4, -5, -3, 1, 0, 4, 8, 7, -1, 3, 2, -3, -4, -5, 4, 3, 2, -1, -2, -3]
+from tests.decode_packets import Q_DELTA, Q_MIN, QUANTLIST, TEST4, TEST5      # the reference's vectors
 
 
 def dequant(quantvals, minval, delta, sequence):

@@ -1,207 +1,29 @@
 """Stream wrapper (host only — runs without a GPU).
 
 Header packets: the product packs them like the reference's ENCODE side (vorbis_analysis_headerout).  The
-check reads them back with a restatement of the reference's DECODE side — _vorbis_unpack_info/_comment/_books
-(lib/info.c:203-430), vorbis_staticbook_unpack (lib/codebook.c:277-395), floor1_unpack (lib/floor1.c:119-180),
-res0_unpack (lib/res0.c:191-249), mapping0_unpack (lib/mapping0.c:95-160), including their validity checks —
-and compares every field with the mode pack.  No reference header bytes exist to compare with
+check reads them back with a restatement of the reference's DECODE side (unpack_headers in tests/decode_packets.py)
+— _vorbis_unpack_info/_comment/_books (lib/info.c:203-430), vorbis_staticbook_unpack (lib/codebook.c:277-395),
+floor1_unpack (lib/floor1.c:119-180), res0_unpack (lib/res0.c:191-249), mapping0_unpack (lib/mapping0.c:95-160),
+including their validity checks — and compares every field with the mode pack.  No reference header bytes exist to compare with
 (parity with the reference unpinned); pack and unpack are different code in the reference, so the round
 trip is an independent check.
 
 Ogg pages: parsed back per the reference's doc/framing.html with an independent CRC (bitwise, no table), both in
 tests/ogg_pages.py."""
-import glob
 import os
-import sys
 
 import numpy as np
 import pytest
 
+from tests.decode_packets import PACKS, ilog, pack_setup, unpack_headers
 from tests.ogg_pages import crc_bitwise, packets_of, page_crc, parse_pages, split_pages
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import vpk  # noqa: E402
 
-DATA = os.path.join(ROOT, "vorbis_aotuv_lancer_amd", "data")
-
-
-class BitReader:
-    """oggpack_read: LSb first"""
-
-    def __init__(self, data):
-        self.d, self.pos = data, 0
-
-    def read(self, bits):
-        v = 0
-        for i in range(bits):
-            byte = self.pos >> 3
-            if byte >= len(self.d):
-                raise EOFError
-            v |= ((self.d[byte] >> (self.pos & 7)) & 1) << i
-            self.pos += 1
-        return v
-
-    def bytes_left(self):
-        return len(self.d) - ((self.pos + 7) >> 3)
-
-
-def ilog(v):
-    return int(v).bit_length()
-
-
-def maptype1_quantvals(entries, dim):
-    vals = max(int(np.floor(np.float32(entries) ** (np.float32(1.) / np.float32(dim)))), 1)
-    while True:
-        acc, acc1, ok = 1, 1, True
-        for _ in range(dim):
-            if entries // vals < acc:
-                ok = False
-                break
-            acc *= vals
-            acc1 *= vals + 1
-        if ok and acc <= entries and acc1 > entries:
-            return vals
-        vals += -1 if (not ok or acc > entries) else 1
-
-
-def unpack_book(r):
-    assert r.read(24) == 0x564342
-    dim, entries = r.read(16), r.read(24)
-    assert ilog(dim) + ilog(entries) <= 24
-    if r.read(1) == 0:
-        unused = r.read(1)
-        lengths = []
-        for _ in range(entries):
-            if unused:
-                lengths.append(r.read(5) + 1 if r.read(1) else 0)
-            else:
-                lengths.append(r.read(5) + 1)
-    else:
-        length = r.read(5) + 1
-        lengths = []
-        while len(lengths) < entries:
-            num = r.read(ilog(entries - len(lengths)))
-            assert length <= 32 and num <= entries - len(lengths)
-            lengths += [length] * num
-            length += 1
-    book = {"dim": dim, "entries": entries, "lengthlist": lengths, "maptype": r.read(4)}
-    if book["maptype"] in (1, 2):
-        book["q_min"], book["q_delta"] = r.read(32), r.read(32)
-        book["q_quant"], book["q_sequencep"] = r.read(4) + 1, r.read(1)
-        qv = maptype1_quantvals(entries, dim) if book["maptype"] == 1 else entries * dim
-        book["quantlist"] = [r.read(book["q_quant"]) for _ in range(qv)]
-    else:
-        assert book["maptype"] == 0
-    return book
-
-
-def unpack_headers(h0, h1, h2):
-    out = {}
-    r = BitReader(h0)
-    assert r.read(8) == 1 and bytes(r.read(8) for _ in range(6)) == b"vorbis"
-    assert r.read(32) == 0
-    out["channels"], out["rate"] = r.read(8), r.read(32)
-    out["bitrates"] = [r.read(32), r.read(32), r.read(32)]
-    out["blocksizes"] = [1 << r.read(4), 1 << r.read(4)]
-    assert r.read(1) == 1 and out["rate"] >= 1 and out["channels"] >= 1 and 64 <= out["blocksizes"][0] <= out["blocksizes"][1] <= 8192
-    assert len(h0) == 30
-
-    r = BitReader(h1)
-    assert r.read(8) == 3 and bytes(r.read(8) for _ in range(6)) == b"vorbis"
-    out["vendor"] = bytes(r.read(8) for _ in range(r.read(32)))
-    out["comments"] = [bytes(r.read(8) for _ in range(r.read(32))) for _ in range(r.read(32))]
-    assert r.read(1) == 1
-
-    r = BitReader(h2)
-    assert r.read(8) == 5 and bytes(r.read(8) for _ in range(6)) == b"vorbis"
-    out["books"] = [unpack_book(r) for _ in range(r.read(8) + 1)]
-    nb = len(out["books"])
-    for _ in range(r.read(6) + 1):          # time backend placeholders
-        assert r.read(16) == 0
-    floors = []
-    for _ in range(r.read(6) + 1):
-        assert r.read(16) == 1             # floor type 1
-        f = {"partitions": r.read(5)}
-        f["partitionclass"] = [r.read(4) for _ in range(f["partitions"])]
-        maxclass = max(f["partitionclass"], default=-1)
-        f["class_dim"], f["class_subs"], f["class_book"], f["class_subbook"] = [], [], [], []
-        for _ in range(maxclass + 1):
-            f["class_dim"].append(r.read(3) + 1)
-            f["class_subs"].append(r.read(2))
-            f["class_book"].append(r.read(8) if f["class_subs"][-1] else None)
-            assert f["class_book"][-1] is None or f["class_book"][-1] < nb
-            f["class_subbook"].append([r.read(8) - 1 for _ in range(1 << f["class_subs"][-1])])
-            assert all(-1 <= x < nb for x in f["class_subbook"][-1])
-        f["mult"] = r.read(2) + 1
-        rangebits = r.read(4)
-        count = sum(f["class_dim"][c] for c in f["partitionclass"])
-        assert count <= 63
-        f["postlist"] = [0, 1 << rangebits] + [r.read(rangebits) for _ in range(count)]
-        assert len(set(f["postlist"])) == len(f["postlist"])   # no repeated posts (zero-length segments)
-        floors.append(f)
-    out["floors"] = floors
-    residues = []
-    for _ in range(r.read(6) + 1):
-        res = {"type": r.read(16)}
-        assert res["type"] in (0, 1, 2)
-        res["begin"], res["end"], res["grouping"] = r.read(24), r.read(24), r.read(24) + 1
-        res["partitions"], res["groupbook"] = r.read(6) + 1, r.read(8)
-        res["secondstages"] = []
-        for _ in range(res["partitions"]):
-            cascade = r.read(3)
-            if r.read(1):
-                cascade |= r.read(5) << 3
-            res["secondstages"].append(cascade)
-        res["booklist"] = [r.read(8) for _ in range(sum(bin(c).count("1") for c in res["secondstages"]))]
-        assert res["groupbook"] < nb and all(b < nb and out["books"][b]["maptype"] != 0 for b in res["booklist"])
-        gb = out["books"][res["groupbook"]]
-        assert gb["dim"] >= 1 and res["partitions"] ** gb["dim"] <= gb["entries"]
-        residues.append(res)
-    out["residues"] = residues
-    maps = []
-    ch = out["channels"]
-    for _ in range(r.read(6) + 1):
-        assert r.read(16) == 0
-        m = {"submaps": r.read(4) + 1 if r.read(1) else 1}
-        m["coupling"] = []
-        if r.read(1):
-            for _ in range(r.read(8) + 1):
-                mag, ang = r.read(ilog(ch - 1)), r.read(ilog(ch - 1))
-                assert mag != ang and mag < ch and ang < ch
-                m["coupling"].append((mag, ang))
-        assert r.read(2) == 0
-        m["chmuxlist"] = [r.read(4) for _ in range(ch)] if m["submaps"] > 1 else [0] * ch
-        assert all(x < m["submaps"] for x in m["chmuxlist"])
-        m["floorsubmap"], m["residuesubmap"] = [], []
-        for _ in range(m["submaps"]):
-            r.read(8)
-            m["floorsubmap"].append(r.read(8))
-            m["residuesubmap"].append(r.read(8))
-            assert m["floorsubmap"][-1] < len(floors) and m["residuesubmap"][-1] < len(residues)
-        maps.append(m)
-    out["maps"] = maps
-    modes = []
-    for _ in range(r.read(6) + 1):
-        md = (r.read(1), r.read(16), r.read(16), r.read(8))
-        assert md[1] == 0 and md[2] == 0 and md[3] < len(maps)
-        modes.append(md)
-    out["modes"] = modes
-    assert r.read(1) == 1                      # framing bit
-    assert r.bytes_left() == 0                 # nothing but padding bits after it
-    return out
-
-
-@pytest.mark.parametrize("pack", sorted(os.path.basename(p) for p in glob.glob(os.path.join(DATA, "mode_*.vpk"))))
+@pytest.mark.parametrize("pack", PACKS)
 def test_header_packets_read_back_to_the_mode_pack(pack):
     import vorbis_aotuv_lancer_amd as v
-    d = vpk.read_vpk(os.path.join(DATA, pack))
-    ch, rate, q = int(d["info/channels"][0]), int(d["info/rate"][0]), float(d["info/quality"][0])
-    if int(d["info/managed"][0]):
-        av, mn, mx, _ = [int(x) for x in d["bi/rates"]]
-        setup = v.Setup(ch, rate, bitrate=(mx, av, mn))
-    else:
-        setup = v.Setup(ch, rate, q)
+    setup, d = pack_setup(v, pack)
+    ch, rate = int(d["info/channels"][0]), int(d["info/rate"][0])
     comments = ["TITLE=parity", "ARTIST=" + "x" * 300]
     hdr = v.header_packets(setup, comments)
     u = unpack_headers(*hdr)

@@ -1,5 +1,6 @@
 """An independent Vorbis I audio-packet decoder, a header writer, a packet writer and a seeded generator of valid but
-unusual setups, for the decoder tests (test_decoder_model_cpu.py, test_decoder_synthetic_gpu.py).
+unusual setups, for the decoder tests (test_decoder_model_cpu.py, test_decoder_synthetic_gpu.py; the corpus rows both
+share are decode_packets.family).
 
 The decoder is written from the specification in the reference tree (doc/Vorbis_I_spec.tex with 03-codebook.tex,
 07-floor1.tex, 08-residue.tex), one bit at a time and one spec step at a time.  It shares no table layout with the
@@ -201,7 +202,7 @@ class Book:
         return node
 
 
-# ---- header writer: inverse of tests/test_stream_wrapper.unpack_headers ----------------------------------------------
+# ---- header writer: inverse of tests/decode_packets.unpack_headers ----------------------------------------------
 def pack_book(w, b, coding="auto"):
     """coding: "ordered" (length runs), "dense" (5 bits per entry), "sparse" (flag + 5 bits), or "auto": what the
     reference's writer picks (ordered if the lengths never decrease and none is 0, else sparse if any is 0)"""
