@@ -10,8 +10,8 @@ import sys
 
 import numpy as np
 
-from tests import orc
 from tests import vorbis_model as vm
+from tests.encode_oracle import walk
 from tests.signals import burst_signal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -254,18 +254,8 @@ def matrix_classes():
 def oracle_packets(oracle, ch, rate, q, seconds=3.0, seed=3, bitrate=None, capture=True):
     """oracle encode of a burst signal (all four block types) -> list of block dicts, with the encode-side captures
     unless capture is off (then "packet" and the packet's own fields alone)"""
-    st = orc.Stream(orc.Setup(oracle, ch, rate, None if bitrate else q, bitrate=bitrate))
-    if not capture:
-        oracle.lib.orc_stream_set_capture(st.v, 0)
-    sig = burst_signal(ch, rate, int(seconds * rate), seed=seed)
-    blocks = []
-    for i in range(0, sig.shape[1], 1024):
-        st.write(sig[:, i:i + 1024])
-        blocks.extend(st.blocks())
-    st.finish()
-    blocks.extend(st.blocks())
-    st.close()
-    return blocks
+    return walk(oracle, ch, rate, None if bitrate else q, bitrate, burst_signal(ch, rate, int(seconds * rate), seed=seed),
+                capture=capture)
 
 
 def render_line(x0, x1, y0, y1, n):

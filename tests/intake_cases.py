@@ -18,6 +18,7 @@ import ctypes as C
 import numpy as np
 
 from tests import orc
+from tests.encode_oracle import RECORD_KEEP, record
 from tests.signals import burst_signal
 
 # (channels, rate, quality): 256/2048, 512/1024, one size (512), 512/4096, coupled 5.1 256/2048
@@ -166,7 +167,8 @@ def edge_signals(ch, rate, lengths):
 
 
 def _blocks(st, seq):
-    """hand out every ready block of orc.Stream st: ((lW, W, nW, block_mode, eos, granulepos, packetno), bytes)"""
+    """hand out every ready block of orc.Stream st as its record (tests/encode_oracle.py), reading the block's own
+    fields and the packet alone: these schedules have thousands of drains"""
     lib = st.lib
     info, i64, nb = (C.c_int * 8)(), (C.c_int64 * 2)(), C.c_long()
     while lib.orc_analysis_blockout(st.v, st.vb) == 1:
@@ -174,7 +176,8 @@ def _blocks(st, seq):
         lib.orc_block_info(st.vb, info)
         lib.orc_block_info64(st.vb, i64)
         pk = lib.orc_block_packet(st.vb, C.byref(nb))
-        seq.append(((info[0], info[1], info[2], info[5], info[6], int(i64[0]), int(i64[1])), C.string_at(pk, nb.value)))
+        seq.append(record(dict(zip(RECORD_KEEP, (info[0], info[1], info[2], info[5], info[6], i64[0], i64[1],
+                                                 C.string_at(pk, nb.value))))))
 
 
 def oracle_run(oracle, setup, signals, schedule):

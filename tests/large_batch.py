@@ -32,6 +32,7 @@ import functools
 import numpy as np
 
 from tests import orc
+from tests.encode_oracle import compare_blobs, lockstep, walk
 from tests.image_signals import (all_same, alt_sign, delay1, dual_mono, front_same_rest_independent, hard_left,
                                  hard_left_dither, head, inverted, one_live, swap_mid_stream)
 from tests.reach_signals import (click_trains, decaying_hits, edge_tones, faint_noise, gated_bands, nsamples,
@@ -43,7 +44,6 @@ STAGES_I = ["post_valid", "nonzero"]
 MANAGED_F = ["poste", "mdct_raw", "logfft", "logmdct", "noise", "tone", "mdct"]
 MINMAX = (144000, 128000, 112000)
 SECONDS = 2.0
-_cache = {}
 
 
 def synth(seed):
@@ -106,20 +106,11 @@ def streams_of(oracle, c):
     """the oracle's blocks of every signal of the case (1024 samples per write, end of stream declared): computed once"""
     out = []
     for name, make in c["signals"]:
-        key = (name, c["ch"], c["rate"], c["q"], c["bitrate"], c["seconds"])
-        if key not in _cache:
-            pcm = head(make, c["seconds"])(c["ch"], c["rate"])
-            assert pcm.dtype == np.float32 and pcm.shape[0] == c["ch"] and pcm.shape[1] % 1024 == 0 and pcm.shape[1] <= 2 * c["rate"]
-            st = orc.Stream(orc.Setup(oracle, c["ch"], c["rate"], c["q"], bitrate=c["bitrate"]))
-            blks = []
-            for at in range(0, pcm.shape[1], 1024):
-                st.write(pcm[:, at:at + 1024])
-                blks.extend(st.blocks())
-            st.finish()
-            blks.extend(st.blocks())
-            st.close()
-            _cache[key] = blks
-        out.append(_cache[key])
+        def pcm(make=make):
+            x = head(make, c["seconds"])(c["ch"], c["rate"])
+            assert x.shape[1] % 1024 == 0 and x.shape[1] <= 2 * c["rate"]
+            return x
+        out.append(walk(oracle, c["ch"], c["rate"], c["q"], c["bitrate"], pcm, key=("large_batch", name, c["seconds"])))
     assert 1 <= len(out) <= 4
     return out
 
@@ -180,21 +171,8 @@ def R_of(c):
 
 
 def replicated_schedule(streams, R):
-    """Lock step over S = K * R streams, stream s carrying signal s % K: the k-th block of every stream that has one, one
-    call per block type present, in ascending type.  -> [(k, block_mode, signals present (ascending), stream ids
-    (ascending))]: row r of a call holds signal present[r % len(present)], so the first len(present) rows are the
-    first copies, and every call holds all R copies of each signal present."""
-    K = len(streams)
-    out = []
-    for k in range(max(len(b) for b in streams)):
-        by_mode = {}
-        for m, blocks in enumerate(streams):
-            if k < len(blocks):
-                by_mode.setdefault(blocks[k]["block_mode"], []).append(m)
-        for mode, present in sorted(by_mode.items()):
-            ids = (np.arange(R, dtype=np.int32)[:, None] * K + np.asarray(present, np.int32)[None, :]).reshape(-1)
-            out.append((k, mode, present, ids))
-    return out
+    """lockstep(streams, R) of tests/encode_oracle.py without the blocks: [(k, block_mode, signals present, stream ids)]"""
+    return [call[:4] for call in lockstep(streams, R)]
 
 
 def schedule_masks(c, streams, R):
@@ -244,139 +222,49 @@ def encoded_posts(post, floor):
     return np.array(p, np.int32)
 
 
-# ---- the runner -----------------------------------------------------------------------------------------------------------
-def _diagnose(label, name, x, ok, group, rows_per_sb):
-    """x: int32 [rows, width] of one stage, ok: bool mask of the same shape or None, group: rows per replica"""
-    import torch
-    ne = x.view(-1, group, x.shape[1]) != x[:group]
-    if ok is not None:
-        ne &= ok.view(-1, group, x.shape[1])
-    ne = ne.view(x.shape)
-    bad = torch.nonzero(ne.any(dim=1)).flatten()
-    r = int(bad[0])
-    at = int(torch.nonzero(ne[r]).flatten()[0])
-    sb = r // rows_per_sb
-    return (f"{label}: identical input, different {name}: {bad.numel()} of {x.shape[0]} rows differ from their signal's first "
-            f"row; first: row {r} (lane {r % 64} of tile {r // 64}, stream-block row {sb}, channel {r % rows_per_sb}) against "
-            f"row {r % group}, first differing 32-bit word {at} of {x.shape[1]}: {int(x[r, at])} / {int(x[r % group, at])}, "
-            f"{int(ne[r].sum())} words of the row differ; rows affected: {bad[:12].tolist()}")
-
-
 def run_case(oracle, cuda, c):
     """-> dict(blocks = lead blocks compared with the oracle, calls, masks = {block type: set of masks}, rows = rows held
-    to their twins, R)"""
+    to their twins, R): run_lockstep of tests/encode_calls.py with R replicas; `post`, and in managed classes the
+    packetblobs, the choice and `nonzero` (twins only: the device's is the last packetblob's), are added per call here"""
     import torch
     import vorbis_aotuv_lancer_amd as v
+    from tests.encode_calls import packet_words, run_lockstep
     ch, managed = c["ch"], c["bitrate"] is not None
     streams = streams_of(oracle, c)
-    K, R = len(streams), R_of(c)
-    S = K * R
+    R = R_of(c)
     setup = v.Setup(ch, c["rate"], bitrate=c["bitrate"]) if managed else v.Setup(ch, c["rate"], c["q"])
-    enc = v.Encoder(setup, S)
+    enc = v.Encoder(setup, len(streams) * R)
     if c["sub_batches"] > 1:
         enc.set_sub_batches(c["sub_batches"])
     floors = [floors_of(c, W) for W in (0, 1)]
-    keep_res = torch.tensor([x not in c["res1_channels"] for x in range(ch)], device=cuda)
-    stat = dict(blocks=0, calls=0, masks={}, rows=0, R=R)
-    for k, mode, present, ids in replicated_schedule(streams, R):
-        Km, nsb = len(present), len(ids)
-        blks = [streams[m][k] for m in present]
-        N = blks[0]["N"]
-        label = f"{c['name']} block {k} type {mode} signals {present} ({nsb} stream-blocks)"
-        stat["masks"].setdefault(mode, set()).add(call_mask(mode, N // 2, ch, nsb, c["sub_batches"]))
-        # upload the distinct blocks, expand on the device
-        distinct = torch.from_numpy(np.stack([b["pcm"] for b in blks])).to(cuda)                    # [Km, ch, N]
-        pcm = distinct.index_select(0, torch.arange(nsb, device=cuda) % Km).contiguous()             # [nsb, ch, N]
-        wflags = np.tile(np.array([b["lW"] | (b["nW"] << 1) for b in blks], np.uint8), R)
-        packets, nbytes = enc.analysis_batch(mode, ids, wflags, pcm)
+    masks = {}
 
-        # ---- collect: (name, int32 [rows, width], mask or None, rows per stream-block)
-        held = []
-
-        def hold(name, t, rows_per_sb, ok=None):
-            t = t.contiguous()
-            held.append((name, t.view(torch.int32).view(t.shape[0], -1), ok, rows_per_sb))
-
-        def by_length(p, n):
-            words = torch.arange(p.shape[1] // 4, device=cuda)[None, :] * 4
-            return words < n[:, None]          # every 32-bit word that holds a byte of the packet
-
-        hold("packet lengths", nbytes, 1)
-        hold("packets", packets, 1, by_length(packets, nbytes))
-        got = {}
-        for name in (MANAGED_F if managed else STAGES_F) + STAGES_I:
-            got[name] = enc.fetch(name)
-            hold(name, got[name], ch)
-        valid = got["post_valid"] != 0
-        got["post"] = enc.fetch("post")
+    def more(call):
+        Km, nsb, mode = len(call.present), len(call.ids), call.mode
+        masks.setdefault(mode, set()).add(call_mask(mode, call.blks[0]["N"] // 2, ch, nsb, c["sub_batches"]))
+        post = enc.fetch("post")
         posts = torch.tensor([floors[mode >> 1][x][0] for x in range(ch)], device=cuda).repeat(nsb)
-        ok_post = valid[:, None] & (torch.arange(got["post"].shape[1], device=cuda)[None, :] < posts[:, None])
-        hold("post", got["post"], ch, ok_post)
-        if managed:
-            got["choice"] = enc.fetch("choice")
-            hold("choice", got["choice"], 1)
-            blobs = [enc.fetch_blob(kb) for kb in range(15)]
-            for kb, (bp, bn) in enumerate(blobs):
-                hold(f"blob {kb} lengths", bn, 1)
-                hold(f"blob {kb}", bp, 1, by_length(bp, bn))
-        else:
-            got["residue"] = enc.fetch("residue")
-            hold("residue", got["residue"], ch,
-                 keep_res.repeat(nsb)[:, None].expand(-1, got["residue"].shape[1]).contiguous() if c["res1_channels"] else None)
-
-        # ---- twins: one reduction, one sync
-        flags = []
-        for name, x, ok, rps in held:
-            group = Km * rps
-            assert x.shape[0] == R * group, (label, name, x.shape)
-            ne = x.view(R, group, -1) != x[:group]
-            if ok is not None:
-                ne &= ok.view(R, group, -1)
-            flags.append(ne.any())
-            stat["rows"] += x.shape[0] - group
-        bad = torch.stack(flags).cpu().numpy()
-        if bad.any():
-            name, x, ok, rps = held[int(np.flatnonzero(bad)[0])]
-            raise AssertionError(_diagnose(label, name, x, ok, Km * rps, rps))
-
-        # ---- the oracle: the first copies only
-        lead = {name: t[:Km * (1 if name == "choice" else ch)].cpu().numpy() for name, t in got.items()}
-        for name in (MANAGED_F if managed else STAGES_F):
-            want = np.concatenate([np.atleast_1d(b[name]) for b in blks])
-            assert lead[name].shape == want.shape, (label, name, lead[name].shape, want.shape)
-            diff = lead[name].view(np.uint32) != want.view(np.uint32)
-            assert not diff.any(), (label, name, tuple(np.argwhere(diff)[0]))
-        for name in STAGES_I:
-            if managed and name == "nonzero":
-                continue            # (the device's is the last packetblob's)
-            assert np.array_equal(lead[name], np.concatenate([b[name] for b in blks])), (label, name)
-        for i, b in enumerate(blks):
+        ok = (call.got["post_valid"] != 0)[:, None] & (torch.arange(post.shape[1], device=cuda)[None, :] < posts[:, None])
+        call.held.append(("post", post, ok, ch))
+        lead = post[:Km * ch].cpu().numpy()
+        for i, b in enumerate(call.blks):
             for x in range(ch):
                 if b["post_valid"][x]:
                     fl = floors[mode >> 1][x]
                     want = encoded_posts(b["post"][x], fl)
-                    assert np.array_equal(lead["post"][i * ch + x, :fl[0]], want), (label, "post", i, x, lead["post"][i * ch + x, :fl[0]], want)
+                    assert np.array_equal(lead[i * ch + x, :fl[0]], want), (call.label, "post", i, x, lead[i * ch + x, :fl[0]], want)
         if managed:
+            choice = enc.fetch("choice")
+            blobs = [enc.fetch_blob(kb) for kb in range(15)]
+            call.held += [("nonzero", enc.fetch("nonzero"), None, ch), ("choice", choice, None, 1)]
             for kb, (bp, bn) in enumerate(blobs):
-                bp, bn = bp[:Km].cpu().numpy(), bn[:Km].cpu().numpy()
-                for i, b in enumerate(blks):
-                    assert bn[i] == b["blob_bytes"][kb], (label, "blob size", kb, i, int(bn[i]), b["blob_bytes"][kb])
-                    have, want = bytes(bp[i, :bn[i]]), b["blobs"][kb]
-                    if kb == b["choice"] and len(want) < bn[i]:
-                        have = have[:len(want)]      # the oracle cuts the chosen blob in place, the device the packet it hands out
-                    assert have == want, (label, "blob bytes", kb, i)
-            for i, b in enumerate(blks):
-                assert lead["choice"][i] == b["choice"], (label, "choice", i, int(lead["choice"][i]), b["choice"])
-        else:
-            want = np.concatenate([b["residue"] for b in blks])
-            keep = np.array([x not in c["res1_channels"] for x in range(ch)] * Km)
-            diff = lead["residue"][keep] != want[keep]
-            assert not diff.any(), (label, "residue", tuple(np.argwhere(diff)[0]))
-        pk, nb = packets[:Km].cpu().numpy(), nbytes[:Km].cpu().numpy()
-        for i, b in enumerate(blks):
-            assert nb[i] == len(b["packet"]) and bytes(pk[i, :nb[i]]) == b["packet"], (label, "packet", i)
-        stat["blocks"] += Km
-        stat["calls"] += 1
+                call.held += [(f"blob {kb} lengths", bn, None, 1), (f"blob {kb}", bp, packet_words(bp, bn), 1)]
+            compare_blobs([(bp[:Km].cpu().numpy(), bn[:Km].cpu().numpy()) for bp, bn in blobs], choice[:Km].cpu().numpy(),
+                          call.blks, call.label, cut=True)
+
+    stat = run_lockstep(enc, cuda, streams, ch, MANAGED_F if managed else STAGES_F,
+                        STAGES_I[:1] if managed else STAGES_I + ["residue"], c["res1_channels"], R=R, on_call=more, label=c["name"])
     enc.close()
     setup.close()
-    return stat
+    return dict(stat, masks=masks, R=R)
+

@@ -80,6 +80,18 @@ def random_cuts(data, seed, k=6):
     return sorted(int(x) for x in rng.integers(0, len(data) + 1, k))
 
 
+def foreign_page_cuts(m):
+    """inside a foreign page's header, its lacing table and its body, and at its two ends; the page has a body"""
+    p, n = next((p, n) for p, n, kept, head in walk(m) if not kept and not head and m[p + 26] >= 1 and n > 40)
+    nseg = m[p + 26]
+    return [p, p + 1, p + 26, p + 27, p + 27 + nseg - 1, p + 27 + nseg, p + 27 + nseg + 1, p + n - 1, p + n]
+
+
+def mark_cuts(m):
+    p, nseg = next((p, m[p + 26]) for p, n, kept, head in walk(m) if kept and head)
+    return [p + 27 + nseg + k for k in range(1, 7)]
+
+
 # ---- corpus -------------------------------------------------------------------------------------------------------------
 
 @functools.lru_cache(maxsize=None)

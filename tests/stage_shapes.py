@@ -1,6 +1,6 @@
-"""Shared by the shape tests of single kernels (tests/test_tonemask_shapes_gpu.py, tests/test_couple_consts_gpu.py):
-oracle block sequences of a few distinct signals, and a schedule that hands them to vbm_analysis_batch in batches of
-an exact size per block type.
+"""Shared by the shape tests of single kernels (tests/test_tonemask_shapes_gpu.py, tests/test_couple_consts_gpu.py,
+tests/test_psy_small_forms_gpu.py): a schedule that hands the oracle block sequences of a few distinct signals
+(tests/encode_oracle.py, streams_for) to vbm_analysis_batch in batches of an exact size per block type.
 
 A batch's size is what selects a kernel's tail workgroup, its second tile and so on, so the tests want batches of
 exactly B stream-blocks of one type.  B streams are run side by side.  Every call takes the streams whose NEXT block
@@ -8,23 +8,6 @@ has the highest block type any stream is waiting with (long before transition be
 streams that are ahead wait at the type boundary round a burst until the others arrive: with signals whose bursts
 start at the same sample the whole set goes through every type together at least once.  `schedule()` is plain Python
 over the oracle's block lists; the tests assert the coverage they rely on."""
-import numpy as np
-
-from tests import orc
-
-KEEP = ("lW", "nW", "block_mode", "pcm", "packet", "tone", "residue")
-
-
-def oracle_stream_blocks(oracle, ch, rate, q, sig, bitrate=None, keep=KEEP):
-    """all blocks of one signal (writes of 1024 samples, then end of stream), reduced to the fields in `keep`"""
-    setup = orc.Setup(oracle, ch, rate, q, bitrate=bitrate)
-    st = orc.Stream(setup)
-    out = []
-    for i in range(0, sig.shape[1], 1024):
-        st.write(sig[:, i:i + 1024])
-        out.extend({k: b[k] for k in keep if k in b} for b in st.blocks())
-    st.close()
-    return out
 
 
 def schedule(streams):
@@ -50,26 +33,10 @@ def full_batches(calls, nstreams):
     return {mode for mode, ids, _ in calls if len(ids) == nstreams}
 
 
-def run_schedule(enc, cuda, streams, calls, stages, on_batch=None):
-    """Runs the calls; compares the named float / int stages and the packets with the oracle's, bit for bit.
-    Returns the list of mismatches (call index, block type, batch size, what, where)."""
-    import torch
-    bad = []
-    for k, (mode, ids, idx) in enumerate(calls):
-        blks = [streams[s][i] for s, i in zip(ids, idx)]
-        pcm = torch.from_numpy(np.stack([b["pcm"] for b in blks])).to(cuda)
-        packets, nbytes = enc.analysis_batch(mode, ids, [b["lW"] | (b["nW"] << 1) for b in blks], pcm)
-        for name in stages:
-            got = enc.fetch(name).cpu().numpy().view(np.uint32)
-            ref = np.concatenate([b[name] for b in blks]).view(np.uint32)
-            if not np.array_equal(got, ref):
-                bad.append((k, mode, len(ids), name, tuple(np.argwhere(got != ref)[0])))
-        if on_batch is not None:
-            on_batch(k, mode, ids, blks, bad)
-        packets, nbytes = packets.cpu().numpy(), nbytes.cpu().numpy()
-        for i, b in enumerate(blks):
-            if nbytes[i] != len(b["packet"]) or bytes(packets[i, :max(nbytes[i], 0)]) != b["packet"]:
-                bad.append((k, mode, len(ids), "packet", (ids[i], int(nbytes[i]), len(b["packet"]))))
-        if bad:
-            break
-    return bad
+def run_schedule(enc, cuda, streams, calls, stages, ch, on_call=None):
+    """Runs the calls; the named stages and the packets are the oracle's, bit for bit (tests/encode_calls.py,
+    run_lockstep: `k` of a failure's label is the call's index)"""
+    from tests.encode_calls import run_lockstep
+    steps = ((k, mode, ids, ids, [streams[s][i] for s, i in zip(ids, idx)]) for k, (mode, ids, idx) in enumerate(calls))
+    run_lockstep(enc, cuda, streams, ch, [s for s in stages if s != "residue"], [s for s in stages if s == "residue"],
+                 schedule=steps, on_call=on_call)

@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests import orc
-from tests.test_frontend_gpu import drain
+from tests.encode_calls import collect_device, drain
+from tests.encode_oracle import records, walk
 
 pytestmark = pytest.mark.gpu
 VBM_EINVAL = -131
@@ -79,23 +79,9 @@ def test_device_guard_refuses_oversized_writes(oracle, cuda):
     without the refused samples."""
     import vorbis_aotuv_lancer_amd as v
     from tests.signals import synth_signal
-    from tests.test_frontend_gpu import collect_device
     S, ch, n, before = 3, 2, 14 * 1024, 4
     sigs = [synth_signal(ch, 44100, n, seed=880 + s) for s in range(S)]
-    osetup = orc.Setup(oracle, ch, 44100, 0.5)
-    want = []
-    for sig in sigs:
-        st = orc.Stream(osetup)
-        oracle.lib.orc_stream_set_capture(st.v, 0)
-        seq = []
-        for at in range(0, n, 1024):
-            st.write(sig[:, at:at + 1024])
-            seq.extend(st.blocks())
-        st.finish()
-        seq.extend(st.blocks())
-        st.close()
-        want.append([((b["lW"], b["W"], b["nW"], b["block_mode"], b["eos"], b["granulepos"], b["sequence"]), b["packet"])
-                     for b in seq])
+    want = [records(walk(oracle, ch, 44100, 0.5, pcm=sig, capture=False)) for sig in sigs]
     setup = v.Setup(ch, 44100, 0.5)
     enc = v.Encoder(setup, S, max_batch=v.lib.vbm_device_round_lanes(setup._h, S))
     fe = v.FrontEnd(enc)
@@ -144,20 +130,7 @@ def test_digital_silence_and_near_silence(oracle, cuda, ch, rate, q):
     sigs = [np.zeros((ch, n), np.float32), (1e-6 * rng.standard_normal((ch, n))).astype(np.float32),
             np.zeros((ch, n), np.float32)]
     sigs[2][:, 20000:20003] = 0.9
-    osetup = orc.Setup(oracle, ch, rate, q)
-    want = []
-    for sig in sigs:
-        st = orc.Stream(osetup)
-        oracle.lib.orc_stream_set_capture(st.v, 0)
-        seq = []
-        for at in range(0, n, 1024):
-            st.write(sig[:, at:at + 1024])
-            seq.extend(st.blocks())
-        st.finish()
-        seq.extend(st.blocks())
-        st.close()
-        want.append([((b["lW"], b["W"], b["nW"], b["block_mode"], b["eos"], b["granulepos"], b["sequence"]), b["packet"])
-                     for b in seq])
+    want = [records(walk(oracle, ch, rate, q, pcm=sig, capture=False)) for sig in sigs]
     enc = v.Encoder(v.Setup(ch, rate, q), 3)
     fe = v.FrontEnd(enc)
     got = [[] for _ in range(3)]

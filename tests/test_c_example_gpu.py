@@ -6,7 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import orc
+from tests.encode_oracle import walk
 from tests.signals import synth_signal
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_c_example_writes_the_oracles_packets(oracle, cuda, tmp_path):
     from tests.ogg_pages import parse_pages, packets_of
-    from tests.test_stream_wrapper import unpack_headers
+    from tests.decode_packets import unpack_headers
     exe = os.path.join(ROOT, "examples", "encode_raw")
     if not os.path.exists(exe):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "examples")])
@@ -31,13 +31,4 @@ def test_c_example_writes_the_oracles_packets(oracle, cuda, tmp_path):
     unpack_headers(*pk[:3])
     assert pages[0]["flags"] & 2 and pages[-1]["flags"] & 4 and pages[-1]["granule"] == nsamp
 
-    st = orc.Stream(orc.Setup(oracle, ch, rate, q))
-    oracle.lib.orc_stream_set_capture(st.v, 0)
-    want = []
-    for at in range(0, nsamp, 1024):
-        st.write(sig[:, at:at + 1024])
-        want.extend(b["packet"] for b in st.blocks())
-    st.finish()
-    want.extend(b["packet"] for b in st.blocks())
-    st.close()
-    assert pk[3:] == want
+    assert pk[3:] == [b["packet"] for b in walk(oracle, ch, rate, q, pcm=sig, capture=False)]

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import compat, orc
+from tests.encode_oracle import records, walk
 from tests.signals import synth_signal
 
 pytestmark = pytest.mark.gpu
@@ -45,28 +46,17 @@ def test_example_program_reproduces_reference_dump(oracle, cuda, tmp_path):
     assert got == ref
     # and the .ogg it wrote is a stream: headers first, its audio packets are the dump's
     from tests.ogg_pages import parse_pages, packets_of
-    from tests.test_stream_wrapper import unpack_headers
-    from tests.test_frontend_gpu import split_dump
+    from tests.decode_packets import unpack_headers
+    from tests.encode_calls import split_dump
     pk = packets_of(parse_pages(open(ogg, "rb").read()))
     unpack_headers(*pk[:3])
     assert pk[3:] == split_dump(ref)
 
 
 def oracle_streams(oracle, ch, rate, q, sigs, bitrate=None, chunk=1024):
-    setup = orc.Setup(oracle, ch, rate, q, bitrate=bitrate)
-    want = []
-    for sig in sigs:
-        st = orc.Stream(setup)
-        oracle.lib.orc_stream_set_capture(st.v, 0)
-        seq = []
-        for at in range(0, sig.shape[1], chunk):
-            st.write(sig[:, at:at + chunk])
-            seq.extend(st.blocks())
-        st.finish()
-        seq.extend(st.blocks())
-        st.close()
-        want.append([((b["lW"], b["W"], b["nW"], b["eos"], b["granulepos"], b["sequence"]), b["packet"]) for b in seq])
-    return want
+    """per signal what compat.Stream.drain returns: the records of tests/encode_oracle.py without the block type"""
+    return [[(m[:3] + m[4:], p) for m, p in records(walk(oracle, ch, rate, q, bitrate, sig, chunk=chunk, capture=False))]
+            for sig in sigs]
 
 
 @pytest.fixture()

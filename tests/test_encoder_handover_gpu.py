@@ -3,16 +3,16 @@
 profile_switch: device-built rounds go from graphs to plain launches (stage timing on) and back, with work of the other
 form still in flight.  reset_in_flight: reset() with rounds pending, then the same objects encode from packet 0.
 batch_after_rounds: vbm_analysis_batch2 entered while deferred rounds are pending on the internal streams.
-Sizes, signals and the delay points are those of tests/test_ordering_gpu.py."""
+Sizes, signals and the delay points are those of tests/test_ordering_gpu.py (tests/encode_calls.py)."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
+from tests.encode_calls import (CH, K, Q, RATE, S, check_oracle, delay, drain_host, make_setup,  # noqa: F401
+                                signals)
 from tests.gpuutil import TwinLedger
-from tests.test_ordering_gpu import (CH, K, Q, RATE, S, check_oracle, delay, drain_host, make_setup,  # noqa: F401
-                                     signals)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +31,7 @@ def device_encoder(v, monkeypatch):
 
 
 def device_schedule(cuda, enc, fe, base, before=None, after=None):
-    """the 18 writes of test_ordering_gpu.run_device_rounds (lazy=2, a consumer stream); before / after: {write: call}"""
+    """the 18 writes of run_device_rounds (tests/encode_calls.py) (lazy=2, a consumer stream); before / after: {write: call}"""
     led = TwinLedger(S, K, cuda)
     consumer = torch.cuda.Stream(device=cuda)
     for c in range(NCHUNKS):

@@ -17,10 +17,9 @@ chain's value at those two points.
             spectrum values it is compared with lie in the same range."""
 import numpy as np
 import pytest
-import torch
 
-from tests import orc
-from tests.test_frontend_gpu import drain
+from tests.encode_calls import write_and_drain
+from tests.encode_oracle import RECORD_KEEP, compare_records, records, walk
 
 NSAMP, BURST = 13 * 1024, 7300
 LEVELS = (1e-4, 1e-3, 1e-2, 0.1, 1.0)
@@ -46,28 +45,10 @@ def case_signals(S, ch, W):
     return [low_tone(ch, 44100, LEVELS[(s + rot) % 5], FREQS[(s + 2 * rot) % 5], seed=900 + 7 * rot + s) for s in range(S)]
 
 
-_want = {}
-
-
 def oracle_streams(oracle, S, ch, W):
-    """the oracle fed the same writes (W samples, drained after every write, then end of stream)"""
-    if (S, ch, W) not in _want:
-        osetup = orc.Setup(oracle, ch, 44100, 0.5)
-        want = []
-        for sig in case_signals(S, ch, W):
-            st = orc.Stream(osetup)
-            oracle.lib.orc_stream_set_capture(st.v, 0)
-            seq = []
-            for at in range(0, NSAMP, W):
-                st.write(sig[:, at:at + W])
-                seq.extend(st.blocks())
-            st.finish()
-            seq.extend(st.blocks())
-            st.close()
-            want.append([((b["lW"], b["W"], b["nW"], b["block_mode"], b["eos"], b["granulepos"], b["sequence"]), b["packet"])
-                         for b in seq])
-        _want[(S, ch, W)] = want
-    return _want[(S, ch, W)]
+    """the oracle fed the same writes (W samples, drained after every write, then end of stream): computed once"""
+    return [records(walk(oracle, ch, 44100, 0.5, pcm=sig, chunk=W, capture=False, keep=RECORD_KEEP, key=("envelope", S, W, s)))
+            for s, sig in enumerate(case_signals(S, ch, W))]
 
 
 def test_every_level_is_used_by_a_one_stream_case():
@@ -93,16 +74,9 @@ def test_block_sequence_and_packets(oracle, cuda, S, ch, W):
     fe = v.FrontEnd(enc)
     try:
         got = [[] for _ in range(S)]
-        allp = torch.from_numpy(np.stack(case_signals(S, ch, W))).to(cuda)
-        for at in range(0, NSAMP, W):
-            fe.write(allp[:, :, at:at + W].contiguous())
-            drain(fe, got)
-        fe.finish()
-        drain(fe, got)
+        write_and_drain(fe, cuda, case_signals(S, ch, W), got, chunk=W)
         for s in range(S):
-            assert [m for m, _ in got[s]] == [m for m, _ in want[s]], f"stream {s}: block sequence differs"
-            bad = [i for i in range(len(want[s])) if got[s][i][1] != want[s][i][1]]
-            assert not bad, f"stream {s}: packet {bad[0]} differs"
+            compare_records(got[s], want[s], f"stream {s}")
     finally:
         fe.close()
         enc.close()

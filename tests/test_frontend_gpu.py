@@ -5,85 +5,18 @@
     the dumps end without the end-of-stream flush, which is therefore pinned by the oracle only, and
   * the oracle, stream by stream, for many concurrent streams with different block sequences:
     (lW, W, nW, block type, granulepos, packetno, e_o_s) and packet bytes of every block."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from tests import orc
+from tests.encode_calls import collect_device, drain, flush_held, frontend_vs_oracle, probe_pcm, split_dump
+from tests.encode_oracle import records, walk
 from tests.signals import synth_signal
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def split_dump(d):
-    out, at = [], 0
-    while at < len(d):
-        n = int.from_bytes(d[at:at + 4], "little")
-        out.append(d[at + 4:at + 4 + n])
-        at += 4 + n
-    return out
-
-
-def collect(sink, info, packets, nbytes):
-    packets = packets.cpu().numpy()
-    nbytes = nbytes.cpu().numpy()
-    for k, pi in enumerate(info):
-        assert nbytes[k] >= 0, "packet buffer overflow"
-        sink[int(pi["stream"])].append(((int(pi["lW"]), int(pi["W"]), int(pi["nW"]), int(pi["block_mode"]),
-                                         int(pi["eos"]), int(pi["granulepos"]), int(pi["packetno"])),
-                                        bytes(packets[k, :nbytes[k]])))
-
-
-def drain(fe, sink, max_rounds=None, multi=False):
-    """rounds until no stream has a block (or, with max_rounds, until that many rounds ran and no buffer
-    is more than half full); sink[stream] collects (info fields, packet bytes).  multi: through
-    vbm_frontend_encode_rounds (several rounds per call, joined at the end)"""
-    if multi == "lazy":
-        # lazy joins: the outputs of a call are complete once the next call has been enqueued (or after join)
-        held = getattr(fe, "_held", None)
-        while True:
-            out = fe.encode_rounds(min_rounds=max_rounds or 64, max_rounds=4 if max_rounds is None else 16, lazy=True)
-            if held is not None:
-                collect(sink, held[0].copy(), held[1], held[2])
-            held = (out[0], out[1], out[2])
-            if not out[3] or max_rounds is not None:
-                break
-        fe._held = held
-        return
-    if multi:
-        while True:
-            info, packets, nbytes, counts = fe.encode_rounds(min_rounds=max_rounds or 64, max_rounds=4 if max_rounds is None else 16)
-            collect(sink, info, packets, nbytes)
-            if not counts or max_rounds is not None:
-                return
-    rounds = 0
-    while True:
-        if max_rounds is not None and rounds >= max_rounds and fe.max_buffered + 1024 <= fe.capacity // 2:
-            return
-        rounds += 1
-        info, packets, nbytes = fe.encode_round()
-        if len(info) == 0:
-            return
-        packets = packets.cpu().numpy()
-        nbytes = nbytes.cpu().numpy()
-        for k, pi in enumerate(info):
-            assert nbytes[k] >= 0, "packet buffer overflow"
-            sink[int(pi["stream"])].append(((int(pi["lW"]), int(pi["W"]), int(pi["nW"]), int(pi["block_mode"]),
-                                             int(pi["eos"]), int(pi["granulepos"]), int(pi["packetno"])),
-                                            bytes(packets[k, :nbytes[k]])))
-
-
-def probe_pcm(oracle, ch, rate, secs):
-    total = rate * secs
-    n = ((total + 1023) // 1024) * 1024          # the probe driver writes whole 1024-sample chunks
-    out = np.empty((ch, n), np.float32)
-    oracle.lib.orc_probe_signal.argtypes = [C.c_int, C.c_long, C.c_long, C.c_void_p]
-    oracle.lib.orc_probe_signal(ch, rate, n, out.ctypes.data)
-    return out
 
 
 @pytest.mark.parametrize("ch,rate,q,secs,golden", [
@@ -115,54 +48,6 @@ def test_frontend_reproduces_reference_packet_dump(oracle, cuda, ch, rate, q, se
     assert got[0][-1][0][4] == 1 and all(m[4] == 0 for m, _ in got[0][:-1])      # e_o_s on the last packet only
 
 
-def frontend_vs_oracle(oracle, cuda, ch, rate, q, NS, seconds, need_modes=(0, 1, 2, 3), max_rounds=None, bitrate=None,
-                       sigs=None, multi=False):
-    import vorbis_aotuv_lancer_amd as v
-    nsamp = int(seconds * rate) // 1024 * 1024
-    if sigs is None:
-        sigs = [synth_signal(ch, rate, nsamp, seed=500 + s, level=1.0 if s % 3 else 0.05) for s in range(NS)]
-    # oracle: same write pattern (1024 at a time, drain after every write, then end of stream)
-    osetup = orc.Setup(oracle, ch, rate, q, bitrate=bitrate)
-    want = []
-    for s in range(NS):
-        st = orc.Stream(osetup)
-        oracle.lib.orc_stream_set_capture(st.v, 0)
-        seq = []
-        for at in range(0, nsamp, 1024):
-            st.write(sigs[s][:, at:at + 1024])
-            seq.extend(st.blocks())
-        st.finish()
-        seq.extend(st.blocks())
-        st.close()
-        want.append([((b["lW"], b["W"], b["nW"], b["block_mode"], b["eos"], b["granulepos"], b["sequence"]), b["packet"])
-                     for b in seq])
-    enc = v.Encoder(v.Setup(ch, rate, q, bitrate=bitrate), NS)
-    fe = v.FrontEnd(enc)
-    got = [[] for _ in range(NS)]
-    allp = torch.from_numpy(np.stack(sigs)).to(cuda)
-    for at in range(0, nsamp, 1024):
-        fe.write(allp[:, :, at:at + 1024].contiguous())
-        drain(fe, got, max_rounds, multi)
-    def flush_held():
-        if getattr(fe, "_held", None) is not None:
-            fe.join()
-            collect(got, fe._held[0].copy(), fe._held[1], fe._held[2])
-            fe._held = None
-    # vorbis_analysis_wrote(vd, 0) fits its end-of-stream LPC to what the buffer holds at that moment
-    # (lib/block.c:531-541), so, like the reference application loop, drain before finishing
-    flush_held()
-    drain(fe, got)
-    fe.finish()
-    drain(fe, got)
-    modes = set()
-    for s in range(NS):
-        assert [m for m, _ in got[s]] == [m for m, _ in want[s]], f"stream {s}: block sequence differs"
-        bad = [i for i in range(len(want[s])) if got[s][i][1] != want[s][i][1]]
-        assert not bad, f"stream {s}: packet {bad[0]} differs"
-        modes |= {m[3] for m, _ in got[s]}
-    assert modes >= set(need_modes), modes
-
-
 def test_frontend_many_streams_match_oracle(oracle, cuda):
     frontend_vs_oracle(oracle, cuda, 2, 44100, 0.5, NS=70, seconds=1.6)
 
@@ -187,17 +72,8 @@ def test_frontend_lazy_joins_at_scale(oracle, cuda, monkeypatch, bitrate):
     nsamp = (30 if bitrate is None else 22) * 1024
     base = [synth_signal(ch, rate, nsamp, seed=640 + k, level=1.0 if k % 2 else 0.05) for k in range(K)]
     sigs = [base[s % K] for s in range(S)]
-    osetup = orc.Setup(oracle, ch, rate, q, bitrate=bitrate)
-    want = []
-    for k in range(K):
-        st = orc.Stream(osetup)
-        oracle.lib.orc_stream_set_capture(st.v, 0)
-        seq = []
-        for at in range(0, nsamp, 1024):
-            st.write(base[k][:, at:at + 1024])
-            seq.extend(b["packet"] for b in st.blocks())
-        st.close()
-        want.append(seq)
+    # (the end of the streams is not declared)
+    want = [[b["packet"] for b in walk(oracle, ch, rate, q, bitrate, base[k], finish=False, capture=False)] for k in range(K)]
     enc = v.Encoder(v.Setup(ch, rate, q, bitrate=bitrate), S)
     fe = v.FrontEnd(enc)
     got = [[] for _ in range(S)]
@@ -205,9 +81,7 @@ def test_frontend_lazy_joins_at_scale(oracle, cuda, monkeypatch, bitrate):
     for at in range(0, nsamp, 1024):
         fe.write(allp[:, :, at:at + 1024].contiguous())
         drain(fe, got, 2, "lazy")
-    fe.join()
-    collect(got, fe._held[0].copy(), fe._held[1], fe._held[2])
-    fe._held = None
+    flush_held(fe, got)
     drain(fe, got)
     for s in range(S):
         assert [p for _, p in got[s]] == want[s % K], f"stream {s}"
@@ -264,7 +138,7 @@ def test_complete_ogg_stream(oracle, cuda):
     count, e_o_s sits on the last page."""
     import vorbis_aotuv_lancer_amd as v
     from tests.ogg_pages import parse_pages, packets_of
-    from tests.test_stream_wrapper import unpack_headers
+    from tests.decode_packets import unpack_headers
     ch, rate, q = 2, 44100, 0.5
     nsamp = 50 * 1024
     sig = synth_signal(ch, rate, nsamp, seed=77)
@@ -290,16 +164,7 @@ def test_complete_ogg_stream(oracle, cuda):
     header_pages = [pg for pg in pages if pg["granule"] == 0]
     assert sum(1 for pg in header_pages for lv in pg["lacing"] if lv < 255) == 3
     # and they are the oracle's
-    st = orc.Stream(orc.Setup(oracle, ch, rate, q))
-    oracle.lib.orc_stream_set_capture(st.v, 0)
-    want = []
-    for at in range(0, nsamp, 1024):
-        st.write(sig[:, at:at + 1024])
-        want.extend(b["packet"] for b in st.blocks())
-    st.finish()
-    want.extend(b["packet"] for b in st.blocks())
-    st.close()
-    assert pk[3:] == want
+    assert pk[3:] == [b["packet"] for b in walk(oracle, ch, rate, q, pcm=sig, capture=False)]
 
 
 def test_frontend_reproduces_reference_120s_len_crc(oracle, cuda):
@@ -331,19 +196,9 @@ def test_streams_out_of_lock_step(oracle, cuda, layout):
     hands out)."""
     import vorbis_aotuv_lancer_amd as v
     ch, rate, q = 2, 44100, 0.5
-    osetup = orc.Setup(oracle, ch, rate, q)
 
     def oracle_stream(sig):
-        st = orc.Stream(osetup)
-        oracle.lib.orc_stream_set_capture(st.v, 0)
-        seq = []
-        for at in range(0, sig.shape[1], 1024):
-            st.write(sig[:, at:at + 1024])
-            seq.extend(st.blocks())
-        st.finish()
-        seq.extend(st.blocks())
-        st.close()
-        return [((b["lW"], b["W"], b["nW"], b["block_mode"], b["eos"], b["granulepos"], b["sequence"]), b["packet"]) for b in seq]
+        return records(walk(oracle, ch, rate, q, pcm=sig, capture=False))
 
     sig = {name: synth_signal(ch, rate, n * 1024, seed=seed) for name, n, seed in
            [("a0", 30, 11), ("a1", 45, 12), ("b2", 25, 13), ("b3", 25, 14), ("c0", 12, 15)]}
@@ -396,28 +251,6 @@ def test_streams_out_of_lock_step(oracle, cuda, layout):
 
 
 # ---- rounds built on the device (vbm_frontend_encode_rounds_device): no host in the loop ------------------------
-def collect_device(sink, fe, out):
-    """outputs of one encode_rounds_device call (device tensors) -> sink[stream]"""
-    import vorbis_aotuv_lancer_amd as v
-    info, packets, nbytes, counts = out
-    nb = nbytes.cpu().numpy()
-    live = np.flatnonzero(nb != -2)
-    if len(live) == 0:
-        return 0
-    rec = info.cpu().numpy().view(np.dtype(v.PacketInfo))[:, 0]
-    pk = packets[torch.from_numpy(live).to(packets.device)].cpu().numpy()
-    for j, k in enumerate(live):
-        pi = rec[k]
-        assert nb[k] >= 0, "packet buffer overflow"
-        assert pi["stream"] >= 0
-        sink[int(pi["stream"])].append(((int(pi["lW"]), int(pi["W"]), int(pi["nW"]), int(pi["block_mode"]), int(pi["eos"]),
-                                         int(pi["granulepos"]), int(pi["packetno"])), bytes(pk[j, :nb[k]])))
-    # the counts are the live lanes per block type, and every region is filled from its start
-    c = counts.cpu().numpy()
-    assert int(c.sum()) == len(live)
-    return len(live)
-
-
 @pytest.mark.parametrize("ch,rate,q,NS,lazy", [(2, 44100, 0.5, 70, False), (2, 44100, 0.5, 70, True), (2, 44100, 0.5, 1100, False),
                                                (2, 44100, 0.5, 1100, True), (6, 48000, 0.8, 9, False),
                                                (1, 8000, 0.5, 6, False), (2, 44100, -0.1, 5, False),
@@ -449,20 +282,7 @@ def run_device_built_rounds(oracle, cuda, monkeypatch, ch, rate, q, NS, lazy, K)
         for at in (6000, 13500, 20500):
             x[:, at:at + 200] += (0.6 * rng.standard_normal((ch, 200))).astype(np.float32)
         base = [x]
-    osetup = orc.Setup(oracle, ch, rate, q)
-    want = []
-    for k in range(K):
-        st = orc.Stream(osetup)
-        oracle.lib.orc_stream_set_capture(st.v, 0)
-        seq = []
-        for at in range(0, nsamp, 1024):
-            st.write(base[k][:, at:at + 1024])
-            seq.extend(st.blocks())
-        st.finish()
-        seq.extend(st.blocks())
-        st.close()
-        want.append([((b["lW"], b["W"], b["nW"], b["block_mode"], b["eos"], b["granulepos"], b["sequence"]), b["packet"])
-                     for b in seq])
+    want = [records(walk(oracle, ch, rate, q, pcm=base[k], capture=False)) for k in range(K)]
     setup = v.Setup(ch, rate, q)
     lanes = v.lib.vbm_device_round_lanes(setup._h, NS)
     enc = v.Encoder(setup, NS, max_batch=lanes)

@@ -7,25 +7,16 @@ import numpy as np
 import pytest
 import torch
 
-from tests import orc
+from tests.encode_oracle import walk
 from tests.gpuutil import TwinLedger
 from tests.signals import burst_signal, synth_signal
 
 pytestmark = pytest.mark.gpu
 
 
-def oracle_packets(oracle, osetup, sig, nchunks, finish=False):
-    st = orc.Stream(osetup)
-    oracle.lib.orc_stream_set_capture(st.v, 0)
-    want = []
-    for c in range(nchunks):
-        st.write(sig[:, c * 1024:(c + 1) * 1024])
-        want.extend(b["packet"] for b in st.blocks())
-    if finish:
-        st.finish()
-        want.extend(b["packet"] for b in st.blocks())
-    st.close()
-    return want
+def oracle_packets(oracle, ch, rate, q, sig, nchunks, finish=False, bitrate=None):
+    assert sig.shape[1] == nchunks * 1024
+    return [b["packet"] for b in walk(oracle, ch, rate, q, bitrate, sig, finish=finish, capture=False, keep=("packet",))]
 
 
 @pytest.mark.parametrize("S,K,ch,rate,q,nchunks,multi", [
@@ -66,9 +57,8 @@ def test_full_size_from_pcm(oracle, cuda, S, K, ch, rate, q, nchunks, multi):
     assert led.nblocks >= S * (nchunks - 3)
     if ch == 6:
         assert led.nblocks > S * nchunks            # short blocks occurred
-    osetup = orc.Setup(oracle, ch, rate, q)
     for k in range(K):
-        assert led.lead_packets(k) == oracle_packets(oracle, osetup, sigs[k], nchunks), f"signal {k}: packets differ from the oracle"
+        assert led.lead_packets(k) == oracle_packets(oracle, ch, rate, q, sigs[k], nchunks), f"signal {k}: packets differ from the oracle"
     fe.close()
     enc.close()
 
@@ -122,9 +112,8 @@ def test_full_size_benchmarked_path(oracle, cuda, monkeypatch, bitrate):
             break
         led.add_host_round(info, packets, nbytes, "end of stream")
     led.finish("benchmarked path")
-    osetup = orc.Setup(oracle, ch, rate, q, bitrate=bitrate)
     for k in range(K):
-        assert led.lead_packets(k) == oracle_packets(oracle, osetup, sigs[k], nchunks, finish=True), \
+        assert led.lead_packets(k) == oracle_packets(oracle, ch, rate, q, sigs[k], nchunks, finish=True, bitrate=bitrate), \
             f"signal {k}: packets differ from the oracle"
     fe.close()
     enc.close()

@@ -4,7 +4,7 @@ coupling, a = -b in the point-coupling hypot, an M6 residue_def of 0, equal nepe
 0 and of -2 |magnitude|).  tests/test_images_cpu.py shows on the oracle alone that the corpus gets there.  Everything
 here is bit for bit, with no tolerance anywhere.
 
-  * Stage by stage (run_stages of tests/test_reach_gpu.py: vbm_analysis_batch on oracle-carved blocks), image streams
+  * Stage by stage (run_stages of tests/encode_calls.py: vbm_analysis_batch on oracle-carved blocks), image streams
     and synth_signal streams in one batch, so partitions on a tie share a 64-lane tile with partitions that are not.
   * From PCM through the stream front end, every class of the corpus, the managed ones included.
   * Managed, blob by blob: all fifteen packetblobs, the choice and the delivered packet of every block.
@@ -18,18 +18,17 @@ channel 0 serves in three steps, takes k_couple_quantize as one serial chunk in 
 the blob loop on top of each."""
 import pytest
 
+from tests.encode_calls import frontend_vs_oracle, managed_blobs, run_stages
+from tests.image_cases import DECODED, check_relation, cid, model_spectra, twins
 from tests.image_signals import MINMAX, SECONDS, classes, images_of, seconds_of
 from tests.reach_signals import nsamples
 from tests.signals import synth_signal
-from tests.test_frontend_gpu import frontend_vs_oracle
-from tests.test_images_cpu import DECODED, check_relation, cid, model_spectra, twins
-from tests.test_reach_gpu import managed_blobs, run_stages
 
 pytestmark = pytest.mark.gpu
 
 
 def makers_of(ch, rate, q=None, bitrate=None, only=None, nsynth=2, seed=840):
-    """(name, make) of the class's images with `nsynth` synth_signal streams among them, for blocks_of's cache"""
+    """(name, make) of the class's images with `nsynth` synth_signal streams among them; the name is the key of the oracle walk's cache"""
     out, secs = [], seconds_of(ch, rate, q, bitrate)
     for e in images_of(ch, rate, q, bitrate):
         if only is None or any(e["name"].startswith(x + "_%dch" % ch) for x in only):

@@ -3,8 +3,8 @@
 bench.py's from-PCM leg enqueues write after write (resident PCM, rounds built on the device, lazy = 2, a consumer stream
 joins after every call) and never waits: at any moment several calls are in flight across the workspaces and the output
 ring.  Every other parity test of FrontEnd.encode_rounds_device blocks the host once per write (the twin ledger reads
-back), so the deepest overlap they check is one call.  Here the window of tests/test_ordering_gpu.py's size (2048 stereo
-q5 streams, 8 twin signals) runs with nothing between the first write and the last that waits for the device: a
+back), so the deepest overlap they check is one call.  Here the window of tests/test_ordering_gpu.py's size (tests/encode_calls.py:
+2048 stereo q5 streams, 8 twin signals) runs with nothing between the first write and the last that waits for the device: a
 DeviceLog (tests/gpuutil.py) copies each call's outputs on the consumer's stream, the consumer releases the ring sets
 (FrontEnd.release), and the ledger sees the log only after the window.  Right after the last call is enqueued the test
 counts the calls whose consumer event has not completed: that is the depth the case reached, printed, and where a spin
@@ -17,15 +17,16 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_ordering_gpu as og
+from tests import encode_calls as og
+from tests.encode_calls import delay  # noqa: F401  (fixture)
 from tests.gpuutil import DeviceLog, TwinLedger
-from tests.test_transforms_ahead_gpu import POINTS, delay  # noqa: F401  (the fixture with the two transform points)
 
 pytestmark = pytest.mark.gpu
 
 S, K, CH = og.S, og.K, og.CH
 RING = 3                        # sets per round count (FrontEnd.encode_rounds_device)
 CONSUMER_BUSY_MS = 3.0
+_cache = {}
 
 
 def bench_rounds(nchunks):
@@ -35,7 +36,7 @@ def bench_rounds(nchunks):
 
 def spin_cycles(device, ms):
     """torch.cuda._sleep counts ticks of the device's clock: its rate, measured once before any window"""
-    if "rate" not in og._cache:
+    if "rate" not in _cache:
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda._sleep(100000)                       # (first use: module load)
         torch.cuda.synchronize(device)
@@ -44,8 +45,8 @@ def spin_cycles(device, ms):
         torch.cuda._sleep(ticks)
         b.record()
         torch.cuda.synchronize(device)
-        og._cache["rate"] = ticks / max(a.elapsed_time(b), 1e-3)          # ticks per millisecond
-    return int(og._cache["rate"] * ms)
+        _cache["rate"] = ticks / max(a.elapsed_time(b), 1e-3)          # ticks per millisecond
+    return int(_cache["rate"] * ms)
 
 
 def run_window(cuda, monkeypatch, oracle, nchunks, period, rounds, bitrate=None, workspaces="4", compact=False,

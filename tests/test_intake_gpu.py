@@ -5,13 +5,11 @@ against the oracle driven through the identical writes, drains and ends.  Per st
 What the delivery changes in the reference, and so here: the start-of-stream LPC is fitted at the write that first
 takes a stream past one long block (lib/block.c:547-550), the end-of-stream LPC to what is buffered at the end
 (:516-537), and a short block's type to the envelope marks known when it is carved (lib/envelope.c:683-707)."""
-import numpy as np
 import pytest
 import torch
 
 from tests import intake_cases as ic
-from tests import orc
-from tests.test_frontend_gpu import collect_device, drain
+from tests.encode_calls import DeviceRun, compare_slots, need_types, osetup, wanted
 
 pytestmark = pytest.mark.gpu
 
@@ -21,134 +19,6 @@ STEREO_Q5, STEREO_22, MONO_8, STEREO_QNEG, SURROUND = ic.CLASSES
 
 def class_id(cls):
     return IDS[cls]
-
-
-_osetups, _wanted = {}, {}
-
-
-def osetup(oracle, cls):
-    if cls not in _osetups:
-        _osetups[cls] = orc.Setup(oracle, *cls)
-    return _osetups[cls]
-
-
-def wanted(oracle, cls, key, signals, schedule):
-    """the oracle's sequences for a (class, case): computed once, shared by the tests that replay the case"""
-    if (cls, key) not in _wanted:
-        _wanted[(cls, key)] = ic.oracle_run(oracle, osetup(oracle, cls), signals, schedule)
-    return _wanted[(cls, key)]
-
-
-class DeviceRun:
-    """One FrontEnd driven through a schedule.  how: "write" (FrontEnd.write: every stream, one size), "streams"
-    (write_streams, one call per distinct size of a step) or "strided" (write_streams_strided from a device arena:
-    by slot, channel stride larger than any write, base one float off 16-byte alignment).
-    rounds: None = host-built rounds until nothing is left; n = every drain runs n device-built rounds first, and where
-    an end, a restart or nothing follows, host-built rounds then carve what is left (the end-of-stream fit wants the
-    buffer drained).  device_count[s] / device_eos[s]: blocks / e_o_s blocks of slot s that device-built rounds carved."""
-    ARENA = 4100
-
-    def __init__(self, cuda, cls, nstreams, how, rounds=None):
-        import vorbis_aotuv_lancer_amd as v
-        self.v, self.cuda, self.how, self.rounds = v, cuda, how, rounds
-        self.setup = v.Setup(*cls)
-        self.S, self.ch = nstreams, cls[0]
-        lanes = v.lib.vbm_device_round_lanes(self.setup._h, nstreams) if rounds else None
-        self.enc = v.Encoder(self.setup, nstreams, max_batch=lanes)
-        self.fe = v.FrontEnd(self.enc)
-        self.got = [[] for _ in range(nstreams)]
-        self.done = {s: [] for s in range(nstreams)}     # finished logical streams of a slot
-        self.at = [0] * nstreams
-        self.gen = [0] * nstreams
-        self.device_blocks = 0
-        self.device_count = [0] * nstreams
-        self.device_eos = [0] * nstreams
-        if how == "strided":
-            self.flat = torch.zeros(1 + nstreams * self.ch * self.ARENA, dtype=torch.float32, device=cuda)
-            self.arena = self.flat[1:].view(nstreams, self.ch, self.ARENA)
-            assert self.arena.data_ptr() % 16 == 4
-
-    def signal(self, signals, s):
-        sig = signals[s]
-        return sig[self.gen[s]] if isinstance(sig, (list, tuple)) else sig
-
-    def write(self, signals, sizes):
-        pcs = {}
-        for s, n in sizes.items():
-            sig = self.signal(signals, s)
-            assert n > 0 and self.at[s] + n <= sig.shape[1]
-            pcs[s] = sig[:, self.at[s]:self.at[s] + n]
-            self.at[s] += n
-        if self.how == "write":
-            n = next(iter(sizes.values()))
-            assert sorted(sizes) == list(range(self.S)) and all(m == n for m in sizes.values())
-            self.fe.write(torch.from_numpy(np.stack([pcs[s] for s in range(self.S)])).to(self.cuda).contiguous())
-            return
-        for n in sorted(set(sizes.values())):
-            ids = [s for s in sorted(sizes) if sizes[s] == n]
-            if self.how == "streams":
-                self.fe.write_streams(ids, torch.from_numpy(np.stack([pcs[s] for s in ids])).to(self.cuda).contiguous())
-            else:
-                assert n < self.ARENA
-                for s in ids:
-                    self.arena[s, :, :n] = torch.from_numpy(np.ascontiguousarray(pcs[s])).to(self.cuda)
-                torch.cuda.synchronize()
-                self.fe.write_streams_strided(ids, self.arena, n, self.ch * self.ARENA, self.ARENA, by_slot=True)
-
-    def run(self, signals, schedule):
-        for k, step in enumerate(schedule):
-            if step[0] == "write":
-                self.write(signals, step[1])
-            elif step[0] == "drain":
-                ahead = schedule[k + 1][0] if k + 1 < len(schedule) else "finish"
-                if self.rounds:
-                    before = [len(g) for g in self.got]
-                    out = self.fe.encode_rounds_device(nrounds=self.rounds)
-                    self.device_blocks += collect_device(self.got, self.fe, out)
-                    for s in range(self.S):
-                        self.device_count[s] += len(self.got[s]) - before[s]
-                        self.device_eos[s] += sum(m[4] for m, _ in self.got[s][before[s]:])
-                if not self.rounds or ahead != "write":
-                    drain(self.fe, self.got)
-            elif step[0] == "finish":
-                self.fe.finish(step[1])
-            elif step[0] == "restart":
-                for s in step[1]:
-                    self.done[s].append(self.got[s])
-                    self.got[s] = []
-                    self.at[s] = 0
-                    self.gen[s] += 1
-                self.fe.restart_streams(step[1])
-        if self.rounds:
-            self.fe.device_stats()
-            assert self.fe.refused_writes == 0
-        return {s: self.done[s] + [self.got[s]] for s in range(self.S)}
-
-    def close(self):
-        self.fe.close()
-        self.enc.close()
-
-
-def compare(got, want, label=""):
-    for s in sorted(want):
-        assert len(got[s]) == len(want[s]), (label, s)
-        for g, (a, b) in enumerate(zip(got[s], want[s])):
-            assert [m for m, _ in a] == [m for m, _ in b], f"{label} stream {s}.{g}: block sequence differs from the oracle"
-            bad = [i for i in range(len(b)) if a[i][1] != b[i][1]]
-            assert not bad, f"{label} stream {s}.{g}: packet {bad[0]} of {len(b)} differs from the oracle"
-
-
-def block_types(want):
-    return {m[3] for seqs in want.values() for seq in seqs for m, _ in seq}
-
-
-def need_types(cls, want):
-    # two block sizes: long and short blocks both occur; one size: types 0 and 1
-    types = block_types(want)
-    if cls == MONO_8:
-        assert types >= {0, 1}, types
-    else:
-        assert types & {0, 1} and 3 in types, types
 
 
 # ---- a. write sizes through FrontEnd.write -------------------------------------------------------------------------
@@ -174,7 +44,7 @@ def test_write_sizes(oracle, cuda, cls, name):
         with pytest.raises(run.v.VbmError):
             run.fe.write(torch.zeros((2, cls[0], run.fe.capacity), device=cuda))
         assert run.fe.max_buffered == bs1 // 2                       # nothing was taken
-    compare(run.run(signals, schedule), want, name)
+    compare_slots(run.run(signals, schedule), want, name)
     run.close()
 
 
@@ -186,7 +56,7 @@ def test_one_sample_writes(oracle, cuda, cls):
     assert bs1 <= 2048
     signals, schedule, want = write_case(oracle, cls, "1", drain_every=64, total=bs1 + 300)
     run = DeviceRun(cuda, cls, 2, "write")
-    compare(run.run(signals, schedule), want)
+    compare_slots(run.run(signals, schedule), want)
     run.close()
 
 
@@ -220,7 +90,7 @@ def test_different_sizes_in_one_step(oracle, cuda, cls, how):
     signals, schedule, want = mixed_step_case(oracle, cls)
     need_types(cls, want)
     run = DeviceRun(cuda, cls, len(PER_STREAM), how)
-    compare(run.run(signals, schedule), want, how)
+    compare_slots(run.run(signals, schedule), want, how)
     run.close()
 
 
@@ -246,7 +116,7 @@ def test_stream_lengths(oracle, cuda, cls, drain_as_you_go):
     for s in range(len(lengths)):
         assert len(want[s][0]) >= 1 and want[s][0][-1][0][4] == 1
     run = DeviceRun(cuda, cls, len(lengths), "streams")
-    compare(run.run(signals, schedule), want)
+    compare_slots(run.run(signals, schedule), want)
     run.close()
 
 
@@ -278,7 +148,7 @@ def test_fill_then_drain(oracle, cuda, cls):
     got = run.run(signals, tail)
     want = ic.oracle_run(oracle, osetup(oracle, cls), signals, schedule + tail)
     need_types(cls, want)
-    compare(got, want)
+    compare_slots(got, want)
     run.close()
 
 
@@ -297,7 +167,7 @@ def test_write_sizes_with_device_built_rounds(oracle, cuda, monkeypatch, name):
     vals = max(ic.MIXED) if name == "mixed" else int(name)
     run = DeviceRun(cuda, cls, 2, "write", rounds=1)
     run.rounds = device_rounds_per_write(run.setup, vals)
-    compare(run.run(signals, schedule), want, name)
+    compare_slots(run.run(signals, schedule), want, name)
     assert run.device_blocks > len(want[0][0])                      # most blocks came out of device-built rounds
     run.close()
 
@@ -318,7 +188,7 @@ def test_stream_lengths_with_device_built_rounds(oracle, cuda, monkeypatch):
         if L <= 100:
             assert len(want[s][0]) <= 2 and run.device_eos[s] == 1 and run.device_count[s] == len(want[s][0]), L
     assert sum(run.device_eos) >= 8
-    compare(run.run(signals, schedule[cut:]), want)
+    compare_slots(run.run(signals, schedule[cut:]), want)
     run.close()
 
 
@@ -339,7 +209,7 @@ def test_onset_offsets(oracle, cuda):
     schedule, want = onset_case(oracle, cls, "offsets", signals)
     assert len({tuple(m[:4] for m, _ in want[s][0]) for s in want}) >= 2
     run = DeviceRun(cuda, cls, len(signals), "write")
-    compare(run.run(signals, schedule), want)
+    compare_slots(run.run(signals, schedule), want)
     run.close()
 
 
@@ -350,5 +220,5 @@ def test_onset_amplitudes(oracle, cuda, cls):
     schedule, want = onset_case(oracle, cls, "amplitudes", signals)
     assert len({short_blocks(want[s][0]) for s in want}) >= 2
     run = DeviceRun(cuda, cls, len(signals), "write")
-    compare(run.run(signals, schedule), want)
+    compare_slots(run.run(signals, schedule), want)
     run.close()

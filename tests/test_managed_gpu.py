@@ -4,28 +4,21 @@ from raw PCM through the stream front end.
 
 PARITY UNPINNED by the reference (its dumps are VBR only): the oracle's managed mode is checked by the
 properties in tests/test_managed_oracle.py, and this file holds the device path to the oracle bit for bit."""
-import numpy as np
 import pytest
-import torch
 
-from tests import orc
+from tests.encode_calls import fetch_blobs, frontend_vs_oracle, run_lockstep
+from tests.encode_oracle import compare_blobs, walk
 from tests.signals import synth_signal
-from tests.test_frontend_gpu import frontend_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
 
 def oracle_blocks(oracle, bitrate, seconds, seed, silence=None):
-    st = orc.Stream(orc.Setup(oracle, 2, 44100, bitrate=bitrate))
+    """1024 samples per write, the end of the stream not declared"""
     sig = synth_signal(2, 44100, int(seconds * 44100), seed=seed, level=1.0 if seed % 3 else 0.05)
     if silence:
         sig[:, silence[0]:silence[1]] = 0
-    out = []
-    for i in range(0, sig.shape[1], 1024):
-        st.write(sig[:, i:i + 1024])
-        out.extend(st.blocks())
-    st.close()
-    return out
+    return walk(oracle, 2, 44100, bitrate=bitrate, pcm=sig, finish=False)
 
 
 @pytest.mark.parametrize("bitrate,silence", [(128000, None), ((144000, 128000, 112000), (44100, 3 * 44100))])
@@ -33,40 +26,22 @@ def test_blobs_choice_and_packets_block_by_block(oracle, cuda, bitrate, silence)
     import vorbis_aotuv_lancer_amd as v
     NS = 6
     streams = [oracle_blocks(oracle, bitrate, 3.5, 300 + s, silence if s % 2 else None) for s in range(NS)]
-    nsteps = min(len(b) for b in streams)
     setup = v.Setup(2, 44100, bitrate=bitrate)
     enc = v.Encoder(setup, NS)
-    modes, padded, choices = set(), 0, set()
-    for k in range(nsteps):
-        by_mode = {}
-        for s in range(NS):
-            by_mode.setdefault(streams[s][k]["block_mode"], []).append(s)
-        for mode, ids in sorted(by_mode.items()):
-            modes.add(mode)
-            blks = [streams[s][k] for s in ids]
-            pcm = torch.from_numpy(np.stack([b["pcm"] for b in blks])).to(cuda)
-            wflags = [b["lW"] | (b["nW"] << 1) for b in blks]
-            packets, nbytes = enc.analysis_batch(mode, ids, wflags, pcm)
-            packets, nbytes = packets.cpu().numpy(), nbytes.cpu().numpy()
-            choice = enc.fetch("choice").cpu().numpy()
-            got = enc.fetch("mdct").cpu().numpy().view(np.uint32)          # after M1 (offset_select 1 only)
-            ref = np.concatenate([b["mdct"] for b in blks]).view(np.uint32)
-            assert np.array_equal(got, ref), (k, mode, "mdct")
-            for kb in range(15):
-                bp, bn = enc.fetch_blob(kb)
-                bp, bn = bp.cpu().numpy(), bn.cpu().numpy()
-                for i, b in enumerate(blks):
-                    assert bn[i] == b["blob_bytes"][kb], (k, mode, ids[i], "blob size", kb, int(bn[i]), b["blob_bytes"][kb])
-                    assert bytes(bp[i, :bn[i]]) == b["blobs"][kb], (k, mode, ids[i], "blob bytes", kb)
-            for i, b in enumerate(blks):
-                assert choice[i] == b["choice"], (k, mode, ids[i], "choice", int(choice[i]), b["choice"])
-                assert nbytes[i] == len(b["packet"]) and bytes(packets[i, :nbytes[i]]) == b["packet"], (k, mode, ids[i])
-                padded += len(b["packet"]) > b["blob_bytes"][b["choice"]]
-                choices.add(b["choice"])
-    assert modes == {0, 1, 2, 3}
+    padded, choices = [0], set()
+
+    def blobs(call):
+        compare_blobs(fetch_blobs(enc), enc.fetch("choice").cpu().numpy(), call.blks, call.label)
+        for b in call.blks:
+            padded[0] += len(b["packet"]) > b["blob_bytes"][b["choice"]]
+            choices.add(b["choice"])
+
+    # `mdct`: after M1 (offset_select 1 only)
+    stat = run_lockstep(enc, cuda, streams, 2, ("mdct",), stop="shortest", on_call=blobs)
+    assert stat["modes"] == {0, 1, 2, 3}
     assert len(choices) >= 3
     if silence:
-        assert padded > 0            # the floor was hit: zero bytes appended (lib/bitrate.c:179-188)
+        assert padded[0] > 0            # the floor was hit: zero bytes appended (lib/bitrate.c:179-188)
     enc.close()
     setup.close()
 

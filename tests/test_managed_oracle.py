@@ -11,25 +11,23 @@ import os
 import numpy as np
 import pytest
 
-from tests import orc
+from tests.encode_oracle import walk
 from tests.signals import synth_signal
 
 
 def run(oracle, bitrate, sig):
-    st = orc.Stream(orc.Setup(oracle, 2, 44100, bitrate=bitrate))
-    oracle.lib.orc_stream_set_capture(st.v, 0)
+    """[(block, average reservoir, min / max reservoir, avgfloat)]: the bitrate state as every block leaves it (zeros for
+    the blocks that come after the end was declared)"""
     oracle.lib.orc_stream_bitrate_state.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     res, af = (C.c_int64 * 2)(), C.c_double()
     out = []
-    for at in range(0, sig.shape[1], 1024):
-        st.write(sig[:, at:at + 1024])
-        for b in st.blocks():
+
+    def state(st, b, ended):
+        if not ended:
             oracle.lib.orc_stream_bitrate_state(st.v, res, C.byref(af))
-            out.append((b, int(res[0]), int(res[1]), af.value))
-    st.finish()
-    for b in st.blocks():
-        out.append((b, 0, 0, 0.))
-    st.close()
+        out.append((b, 0, 0, 0.) if ended else (b, int(res[0]), int(res[1]), af.value))
+
+    walk(oracle, 2, 44100, bitrate=bitrate, pcm=sig, capture=False, on_block=state)
     return out
 
 

@@ -123,24 +123,12 @@ def test_one_byte_per_call(resync):
     (X.check_resync_equivalence if resync else X.check_strict_equivalence)("host", [m], cuts)
 
 
-def _foreign_page_cuts(m):
-    """inside a foreign page's header, its lacing table and its body, and at its two ends; the page has a body"""
-    p, n = next((p, n) for p, n, kept, head in X.walk(m) if not kept and not head and m[p + 26] >= 1 and n > 40)
-    nseg = m[p + 26]
-    return [p, p + 1, p + 26, p + 27, p + 27 + nseg - 1, p + 27 + nseg, p + 27 + nseg + 1, p + n - 1, p + n]
-
-
-def _mark_cuts(m):
-    p, nseg = next((p, m[p + 26]) for p, n, kept, head in X.walk(m) if kept and head)
-    return [p + 27 + nseg + k for k in range(1, 7)]
-
-
 @pytest.mark.parametrize("resync", [False, True])
 @pytest.mark.parametrize("name", ["tiny", "three groups", "more than 244 segments in front of the mark"])
 def test_cuts_in_foreign_pages_and_in_the_mark(resync, name):
     m = X.corpus()[name]
-    cuts = [[c] for c in _foreign_page_cuts(m) + _mark_cuts(m)]
-    cuts += [sorted(set(_foreign_page_cuts(m))), _mark_cuts(m)]        # ... and all of them one after the other
+    cuts = [[c] for c in X.foreign_page_cuts(m) + X.mark_cuts(m)]
+    cuts += [sorted(set(X.foreign_page_cuts(m))), X.mark_cuts(m)]        # ... and all of them one after the other
     if not resync:
         assert cuts == [X.strict_cuts(m, c) for c in cuts]
     (X.check_resync_equivalence if resync else X.check_strict_equivalence)("host", [m] * len(cuts), cuts)

@@ -91,11 +91,10 @@ def test_one_byte_per_call(cuda, resync):
 @pytest.mark.parametrize("resync", [False, True])
 def test_cuts_in_foreign_pages_and_in_the_mark(cuda, resync):
     """... the head page of more than 244 segments among them: the wave walk's second round trip"""
-    from tests.test_ogg_feed_mux_cpu import _foreign_page_cuts, _mark_cuts
     blobs, cuts = [], []
     for name in ("tiny", "three groups", "more than 244 segments in front of the mark"):
         m = X.corpus()[name]
-        cs = [[c] for c in _foreign_page_cuts(m) + _mark_cuts(m)] + [sorted(set(_foreign_page_cuts(m))), _mark_cuts(m)]
+        cs = [[c] for c in X.foreign_page_cuts(m) + X.mark_cuts(m)] + [sorted(set(X.foreign_page_cuts(m))), X.mark_cuts(m)]
         blobs += [m] * len(cs)
         cuts += cs
     if resync:

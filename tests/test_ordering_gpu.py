@@ -7,149 +7,16 @@ spins for milliseconds in front of the work behind it (vbm_debug_set_delay): wha
 delayed work runs ahead of it, deterministically.  Packets may not change: every stream against its twin and the
 distinct signals against the oracle, for the host-built rounds, the device-built (graph) rounds and the two-stream
 per-block form.  A second family of cases fills every scratch buffer with 0xFF between calls
-(vbm_debug_poison_*): nothing a batch reads may be left over from the batch that used the workspace before."""
+(vbm_debug_poison_*): nothing a batch reads may be left over from the batch that used the workspace before.
+The sizes, signals, rounds runners and the `delay` fixture are those of tests/encode_calls.py."""
 import numpy as np
 import pytest
 import torch
 
-from tests import orc
-from tests.gpuutil import TwinLedger
-from tests.signals import burst_signal
+from tests.encode_calls import (CH, MANAGED, Q, RATE, S, check_oracle, delay, run_device_rounds,  # noqa: F401 (delay: fixture)
+                                run_host_rounds)
 
 pytestmark = pytest.mark.gpu
-
-CH, RATE, Q = 2, 44100, 0.5
-S, K = 2048, 8                  # 256 twins per signal: batches of 256 .. 2048 blocks (small and "big" ones, >= 1024)
-DELAY_US = 3000                 # longer than any kernel of a batch of this size
-
-POINTS = {"job_big": 0, "job_small": 1, "job_state": 2, "job_back": 3, "job_out": 4, "fe_fork": 5, "fe_shift": 6,
-          "dev_big_front": 7, "dev_big_back": 8, "dev_small_front": 9, "dev_small_back": 10, "dev_plan": 11,
-          "batch_front": 12, "batch_back": 13, "fe_write": 14, "dev_out": 15}
-
-
-@pytest.fixture
-def delay():
-    import vorbis_aotuv_lancer_amd as v
-
-    def set_points(*names):
-        mask = 0
-        for n in names:
-            mask |= 1 << POINTS[n]
-        assert v.lib.vbm_debug_set_delay(mask, DELAY_US if mask else 0) == 0
-    yield set_points
-    v.lib.vbm_debug_set_delay(0, 0)
-
-
-_cache = {}
-
-
-def signals(nchunks, period):
-    key = (nchunks, period)
-    if key not in _cache:
-        _cache[key] = [burst_signal(CH, RATE, nchunks * 1024, seed=70 + k, period=period, level=1.0 if k % 3 else 0.05)
-                       for k in range(K)]
-    return _cache[key]
-
-
-MANAGED = (144000, 128000, 112000)     # vorbis_encode_init(max, nominal, min): the bitrate manager's reservoirs are carried state
-
-
-def make_setup(v, bitrate):
-    return v.Setup(CH, RATE, bitrate=bitrate) if bitrate else v.Setup(CH, RATE, Q)
-
-
-def oracle_want(oracle, nchunks, period, bitrate=None):
-    key = ("want", nchunks, period, bitrate)
-    if key not in _cache:
-        osetup = orc.Setup(oracle, CH, RATE, None if bitrate else Q, bitrate=bitrate)
-        want = []
-        for sig in signals(nchunks, period):
-            st = orc.Stream(osetup)
-            oracle.lib.orc_stream_set_capture(st.v, 0)
-            seq = []
-            for c in range(nchunks):
-                st.write(sig[:, c * 1024:(c + 1) * 1024])
-                seq.extend(b["packet"] for b in st.blocks())
-            st.finish()
-            seq.extend(b["packet"] for b in st.blocks())
-            st.close()
-            want.append(seq)
-        _cache[key] = want
-    return _cache[key]
-
-
-def drain_host(fe, led, label):
-    while True:
-        info, packets, nbytes = fe.encode_round()
-        if len(info) == 0:
-            return
-        led.add_host_round(info, packets, nbytes, label)
-
-
-def run_host_rounds(cuda, nchunks, period, poison=False, multi=False, bitrate=None):
-    import vorbis_aotuv_lancer_amd as v
-    base = torch.from_numpy(np.stack(signals(nchunks, period))).to(cuda)
-    enc = v.Encoder(make_setup(v, bitrate), S)
-    fe = v.FrontEnd(enc)
-    led = TwinLedger(S, K, cuda)
-    for c in range(nchunks):
-        if poison:
-            enc.debug_poison(-1, 0xFF)
-            fe.debug_poison(0xFF)
-        fe.write(base[:, :, c * 1024:(c + 1) * 1024].repeat(S // K, 1, 1).contiguous())
-        if multi:
-            while True:
-                info, packets, nbytes, counts = fe.encode_rounds(min_rounds=64, max_rounds=4)
-                if not counts:
-                    break
-                led.add_host_round(info.copy(), packets, nbytes, f"write {c}")
-        else:
-            drain_host(fe, led, f"write {c}")
-    fe.finish()
-    drain_host(fe, led, "end of stream")
-    led.finish("host-built rounds")
-    fe.close()
-    enc.close()
-    return led
-
-
-def run_device_rounds(cuda, monkeypatch, nchunks, period, poison=False, lazy=2, bitrate=None):
-    import vorbis_aotuv_lancer_amd as v
-    monkeypatch.setenv("VBM_WORKSPACES", "4")
-    base = torch.from_numpy(np.stack(signals(nchunks, period))).to(cuda)
-    setup = make_setup(v, bitrate)
-    enc = v.Encoder(setup, S, max_batch=v.lib.vbm_device_round_lanes(setup._h, S))
-    fe = v.FrontEnd(enc)
-    led = TwinLedger(S, K, cuda)
-    consumer = torch.cuda.Stream(device=cuda)
-    for c in range(nchunks):
-        if poison:
-            fe.join()
-            enc.debug_poison(-1, 0xFF)
-            fe.debug_poison(0xFF)
-        fe.write(base[:, :, c * 1024:(c + 1) * 1024].repeat(S // K, 1, 1).contiguous())
-        info, packets, nbytes, counts = fe.encode_rounds_device(nrounds=2, lazy=lazy)
-        fe.join(consumer)
-        with torch.cuda.stream(consumer):
-            led.add_device_rounds(info, packets, nbytes, f"write {c}")
-        consumer.synchronize()
-    fe.device_stats()
-    assert fe.refused_writes == 0
-    torch.cuda.synchronize()
-    drain_host(fe, led, "drain")
-    fe.finish()
-    drain_host(fe, led, "end of stream")
-    led.finish("device-built rounds")
-    fe.close()
-    enc.close()
-    return led
-
-
-def check_oracle(led, oracle, nchunks, period, bitrate=None):
-    want = oracle_want(oracle, nchunks, period, bitrate)
-    for k in range(K):
-        assert led.lead_packets(k) == want[k], f"signal {k}: packets differ from the oracle"
-    assert led.modes[0] + led.modes[1] > 0 and led.modes[2] > 0 and led.modes[3] > 0, led.modes   # all block types ran
 
 
 @pytest.mark.parametrize("point", ["none", "job_big", "job_small", "job_state", "job_back", "job_out", "fe_fork", "fe_shift",

@@ -18,31 +18,20 @@ import numpy as np
 import pytest
 import torch
 
+from tests import encode_calls as ec
 from tests import orc
-from tests.large_batch import replicated_schedule
+from tests.encode_oracle import compare_packets, walk
 from tests.signals import burst_signal, synth_signal
 
 pytestmark = pytest.mark.gpu
 
 FILL, POISON = 0xA5, 0xFF
-_cache = {}
 
 
 def oracle_blocks(oracle, ch, rate, q, name, pcm):
     """the oracle's blocks of one signal (1024 samples per write, end of stream declared): computed once"""
-    key = (ch, rate, q, name)
-    if key not in _cache:
-        assert pcm.dtype == np.float32 and pcm.shape[0] == ch and pcm.shape[1] % 1024 == 0
-        st = orc.Stream(orc.Setup(oracle, ch, rate, q))
-        blks = []
-        for at in range(0, pcm.shape[1], 1024):
-            st.write(pcm[:, at:at + 1024])
-            blks.extend(st.blocks())
-        st.finish()
-        blks.extend(st.blocks())
-        st.close()
-        _cache[key] = [{k: b[k] for k in ("pcm", "lW", "nW", "N", "block_mode", "packet")} for b in blks]
-    return _cache[key]
+    assert pcm.shape[1] % 1024 == 0
+    return walk(oracle, ch, rate, q, pcm=pcm, keep=("pcm", "lW", "nW", "N", "block_mode", "packet"), key=("packet_words", name))
 
 
 def silence(ch, n):
@@ -57,55 +46,10 @@ def filled(shape, dtype, value, dev):
     return torch.full(shape, value, dtype=dtype, device=dev)
 
 
-def check_rows(packets, nbytes, want, label):
-    """rows of `packets` against the packets in `want` (bytes), whole: the packet, then zeros"""
-    pk, nb = packets.cpu().numpy(), nbytes.cpu().numpy()
-    assert len(want) == pk.shape[0] == nb.shape[0], (label, len(want), pk.shape)
-    for i, w in enumerate(want):
-        assert nb[i] == len(w), (label, "length", i, int(nb[i]), len(w))
-        if bytes(pk[i, :nb[i]]) != w:
-            at = next(k for k in range(len(w)) if pk[i, k] != w[k])
-            raise AssertionError((label, "packet bytes", i, "first differing byte", at, "of", len(w)))
-        tail = np.flatnonzero(pk[i, nb[i]:])
-        assert tail.size == 0, (label, "row not zero past the packet", i, "length", int(nb[i]), "first byte",
-                                int(nb[i] + tail[0]), "value", int(pk[i, nb[i] + tail[0]]), "count", int(tail.size))
-
-
-def check_replicas(packets, nbytes, K, label):
-    """row r equals row r % K, all max_packet_bytes of it, and so do the lengths (one sync)"""
-    n = packets.shape[0]
-    first = torch.arange(n, device=packets.device) % K
-    ne = (packets != packets[first]).any(dim=1) | (nbytes != nbytes[first])
-    bad = torch.nonzero(ne).flatten()
-    if bad.numel():
-        r = int(bad[0])
-        at = int(torch.nonzero(packets[r] != packets[r % K]).flatten()[0]) if bool((packets[r] != packets[r % K]).any()) else -1
-        raise AssertionError(f"{label}: {bad.numel()} of {n} rows differ from their signal's first row; first: row {r} (lane "
-                             f"{r % 64} of tile {r // 64}), lengths {int(nbytes[r])} / {int(nbytes[r % K])}, first differing byte {at}")
-
-
-def run_lockstep(cuda, v, enc, streams, R, label, poison=True):
-    """K oracle streams replicated R times through Encoder.analysis_batch, a call per block index and block type
-    (tests/large_batch.py, replicated_schedule); -> block types seen"""
-    K = len(streams)
-    seen = set()
-    for k, mode, present, ids in replicated_schedule(streams, R):
-        Km, nsb = len(present), len(ids)
-        blks = [streams[m][k] for m in present]
-        if poison:
-            torch.cuda.synchronize()
-            enc.debug_poison(-1, POISON)
-        distinct = torch.from_numpy(np.stack([b["pcm"] for b in blks])).to(cuda)
-        pcm = distinct.index_select(0, torch.arange(nsb, device=cuda) % Km).contiguous()
-        wflags = np.tile(np.array([b["lW"] | (b["nW"] << 1) for b in blks], np.uint8), R)
-        out = (filled((nsb, enc.max_packet_bytes), torch.uint8, FILL, cuda), filled((nsb,), torch.int32, -7, cuda))
-        packets, nbytes = enc.analysis_batch(mode, ids, wflags, pcm, out=out)
-        where = f"{label} block {k} type {mode} signals {present} ({nsb} stream-blocks)"
-        if R > 1:
-            check_replicas(packets, nbytes, Km, where)
-        check_rows(packets[:Km], nbytes[:Km], [b["packet"] for b in blks], where)
-        seen.add(mode)
-    return seen
+def run_lockstep(cuda, enc, streams, R, label):
+    """K oracle streams replicated R times through Encoder.analysis_batch (tests/encode_calls.py, run_lockstep): the
+    destination pre-filled, every workspace poisoned before every call, whole rows compared; -> block types seen"""
+    return ec.run_lockstep(enc, cuda, streams, R=R, out_fill=FILL, poison=POISON, label=label)["modes"]
 
 
 # ---- per-block path: two lane tiles, short packets over long ones ---------------------------------------------------------
@@ -157,7 +101,7 @@ def test_per_block_two_tiles_short_packets_over_long_ones(oracle, cuda, monkeypa
         wflags = np.array([b["lW"] | (b["nW"] << 1) for b in blks], np.uint8)
         out = (filled((len(ids), enc.max_packet_bytes), torch.uint8, FILL, cuda), filled((len(ids),), torch.int32, -7, cuda))
         packets, nbytes = enc.analysis_batch(mode, np.asarray(ids, np.int32), wflags, pcm, out=out)
-        check_rows(packets, nbytes, [b["packet"] for b in blks], label)
+        compare_packets(packets.cpu().numpy(), nbytes.cpu().numpy(), [b["packet"] for b in blks], label, zero_tail=True)
 
     enc.debug_poison(-1, POISON)
     for m in range(3):                                               # the opening blocks, a signal's streams per call
@@ -179,15 +123,14 @@ def test_per_block_two_tiles_short_packets_over_long_ones(oracle, cuda, monkeypa
 
 # ---- device-built rounds: counts far below the launch bounds -------------------------------------------------------------
 def test_device_built_rounds_eight_streams(oracle, cuda, monkeypatch):
-    """8 streams with bursts (the signals and oracle packets of tests/test_ordering_gpu.py), rounds built on the device:
+    """8 streams with bursts (the signals and oracle packets of the rounds runners, tests/encode_calls.py), rounds built on the device:
     every block type's region is launched for its bound (thousands of lanes) and holds a handful of blocks"""
     import vorbis_aotuv_lancer_amd as v
-    from tests import test_ordering_gpu as og
-    nchunks, period, S = 18, 12000, og.K
+    nchunks, period, S = 18, 12000, ec.K
     monkeypatch.setenv("VBM_WORKSPACES", "4")
-    want = og.oracle_want(oracle, nchunks, period)
-    base = torch.from_numpy(np.stack(og.signals(nchunks, period))).to(cuda)
-    setup = v.Setup(og.CH, og.RATE, og.Q)
+    want = ec.oracle_want(oracle, nchunks, period)
+    base = torch.from_numpy(np.stack(ec.signals(nchunks, period))).to(cuda)
+    setup = v.Setup(ec.CH, ec.RATE, ec.Q)
     lanes = v.lib.vbm_device_round_lanes(setup._h, S)
     enc = v.Encoder(setup, S, max_batch=lanes)
     fe = v.FrontEnd(enc)
@@ -293,7 +236,7 @@ def test_submap_and_vector_shapes(oracle, cuda, name, ch, rate, q):
     setup = v.Setup(ch, rate, q)
     R = 3
     enc = v.Encoder(setup, len(streams) * R)
-    seen = run_lockstep(cuda, v, enc, streams, R, name)
+    seen = run_lockstep(cuda, enc, streams, R, name)
     assert seen & {0, 1} and 3 in seen, seen          # short and long blocks
     enc.close()
     setup.close()
@@ -349,7 +292,7 @@ def test_both_slice_forms_cut_a_phrase_pair(oracle, cuda, form):
             assert any(b % 2 for b in bounds), (form, partvals, bounds)
     setup = v.Setup(ch, rate, q)
     enc = v.Encoder(setup, K * R)
-    seen = run_lockstep(cuda, v, enc, streams, R, f"{form} slices")
+    seen = run_lockstep(cuda, enc, streams, R, f"{form} slices")
     assert seen & {0, 1} and 3 in seen, seen
     enc.close()
     setup.close()

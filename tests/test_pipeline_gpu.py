@@ -4,28 +4,23 @@ NS independent streams are encoded by the oracle on the CPU (block sequence, raw
 every captured stage vector, packets).  The same blocks are then pushed through
 vbm_analysis_batch in lock-step (k-th block of every stream per step, grouped by block type),
 and every intermediate the C ABI exposes is compared bit-for-bit."""
-import numpy as np
 import pytest
 import torch
 
-from tests import orc
+from tests.encode_calls import run_lockstep
+from tests.encode_oracle import walk
 from tests.signals import synth_signal
 
 pytestmark = pytest.mark.gpu
 
 STAGES_F = ["mdct_raw", "logfft", "logmdct", "noise", "tone", "logmask", "mdct"]
+STAGES_I = ["post_valid", "residue", "nonzero"]
 
 
 def oracle_blocks(oracle, ch, rate, q, seconds, seed):
-    setup = orc.Setup(oracle, ch, rate, q)
-    st = orc.Stream(setup)
+    """1024 samples per write, the end of the stream not declared"""
     sig = synth_signal(ch, rate, int(seconds * rate), seed=seed, level=1.0 if seed % 3 else 0.05)
-    out = []
-    for i in range(0, sig.shape[1], 1024):
-        st.write(sig[:, i:i + 1024])
-        out.extend(st.blocks())
-    st.close()
-    return out
+    return walk(oracle, ch, rate, q, pcm=sig, finish=False)
 
 
 def run_case(oracle, cuda, ch, rate, q, nstreams, seconds, check_stages=True, res1_channels=(), sub_batches=1,
@@ -38,69 +33,12 @@ def run_case(oracle, cuda, ch, rate, q, nstreams, seconds, check_stages=True, re
     enc = v.Encoder(setup, nstreams)
     enc.set_sub_batches(sub_batches)
     assert enc.sub_batches == sub_batches
-    seen_modes = set()
-    mismatches = []
-    pending = []
-    back = torch.cuda.Stream(device=cuda) if two_streams else None
-    for k in range(nsteps):
-        by_mode = {}
-        for s in range(nstreams):
-            by_mode.setdefault(streams[s][k]["block_mode"], []).append(s)
-        for mode, ids in sorted(by_mode.items()):
-            seen_modes.add(mode)
-            blks = [streams[s][k] for s in ids]
-            pcm = torch.from_numpy(np.stack([b["pcm"] for b in blks])).to(cuda)
-            wflags = [b["lW"] | (b["nW"] << 1) for b in blks]
-            if two_streams:   # vbm_analysis_batch2: back half on its own stream; no host sync between the calls
-                outs = (torch.empty((len(ids), enc.max_packet_bytes), dtype=torch.uint8, device=cuda),
-                        torch.empty((len(ids),), dtype=torch.int32, device=cuda))
-                pending.append((k, mode, blks, outs))
-                enc.analysis_batch(mode, ids, wflags, pcm, back_stream=back, out=outs)
-                continue
-            packets, nbytes = enc.analysis_batch(mode, ids, wflags, pcm)
-            nbytes = nbytes.cpu().numpy()
-            packets = packets.cpu().numpy()
-            if check_stages:
-                for name in STAGES_F:
-                    got = enc.fetch(name).cpu().numpy().view(np.uint32)
-                    ref = np.concatenate([b[name] for b in blks]).view(np.uint32)
-                    if not np.array_equal(got, ref):
-                        bad = np.argwhere(got != ref)[0]
-                        mismatches.append((k, mode, name, tuple(bad)))
-                got = enc.fetch("post_valid").cpu().numpy()
-                ref = np.concatenate([b["post_valid"] for b in blks])
-                if not np.array_equal(got, ref):
-                    mismatches.append((k, mode, "post_valid", ()))
-                got = enc.fetch("residue").cpu().numpy()
-                ref = np.concatenate([b["residue"] for b in blks])
-                if res1_channels:
-                    # res-1 encodes in place (lib/res0.c:372-375 on in[j] itself): after the packet
-                    # kernel those channels hold the VQ remainder, not the quantised residue
-                    keep = np.array([c not in res1_channels for c in range(ch)] * len(blks))
-                    got, ref = got[keep], ref[keep]
-                if not np.array_equal(got, ref):
-                    mismatches.append((k, mode, "residue", tuple(np.argwhere(got != ref)[0])))
-                got = enc.fetch("nonzero").cpu().numpy()
-                ref = np.concatenate([b["nonzero"] for b in blks])
-                if not np.array_equal(got, ref):
-                    mismatches.append((k, mode, "nonzero", ()))
-            for i, b in enumerate(blks):
-                pk = bytes(packets[i, :max(nbytes[i], 0)])
-                if nbytes[i] != len(b["packet"]) or pk != b["packet"]:
-                    mismatches.append((k, mode, "packet", (ids[i], int(nbytes[i]), len(b["packet"]))))
-            assert not mismatches, mismatches[:8]
-    if two_streams:
-        torch.cuda.synchronize()
-        for k, mode, blks, (packets, nbytes) in pending:
-            packets, nbytes = packets.cpu().numpy(), nbytes.cpu().numpy()
-            for i, b in enumerate(blks):
-                pk = bytes(packets[i, :max(nbytes[i], 0)])
-                if nbytes[i] != len(b["packet"]) or pk != b["packet"]:
-                    mismatches.append((k, mode, "packet", (i, int(nbytes[i]), len(b["packet"]))))
-        assert not mismatches, mismatches[:8]
+    # two_streams: vbm_analysis_batch2, back half on its own stream; no host sync between the calls
+    stat = run_lockstep(enc, cuda, streams, ch, STAGES_F if check_stages else (), STAGES_I if check_stages else (),
+                        res1_channels, stop="shortest", back_stream=torch.cuda.Stream(device=cuda) if two_streams else None)
     enc.close()
     setup.close()
-    return seen_modes, nsteps
+    return stat["modes"], nsteps
 
 
 def test_stereo_q5_stage_and_packet_parity(oracle, cuda):

@@ -15,34 +15,25 @@ import numpy as np
 import pytest
 
 from tests import orc
+from tests.encode_oracle import walk
 from tests.reach_signals import REACH
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import oracle_reach  # noqa: E402
 
-_cache = {}
-
-
 def entry(name):
     return next(e for e in REACH if e["name"] == name)
 
 
 def blocks(oracle, name):
-    if name not in _cache:
-        e = entry(name)
-        st = orc.Stream(orc.Setup(oracle, e["ch"], e["rate"], e["q"], bitrate=e["bitrate"]))
-        pcm = e["make"](e["ch"], e["rate"])
-        assert pcm.dtype == np.float32 and pcm.shape[0] == e["ch"] and pcm.shape[1] <= 2 * e["rate"] and pcm.shape[1] % 1024 == 0
-        out = []
-        for at in range(0, pcm.shape[1], 1024):
-            st.write(pcm[:, at:at + 1024])
-            out.extend(st.blocks())
-        st.finish()
-        out.extend(st.blocks())
-        st.close()
-        _cache[name] = out
-    return _cache[name]
+    e = entry(name)
+
+    def pcm():
+        x = e["make"](e["ch"], e["rate"])
+        assert x.shape[1] <= 2 * e["rate"] and x.shape[1] % 1024 == 0
+        return x
+    return walk(oracle, e["ch"], e["rate"], e["q"], e["bitrate"], pcm, key=("reach", name))
 
 
 def detector(pcm, mode, last_mode):
@@ -221,18 +212,8 @@ def _suite_slice(args):
     o = orc.Oracle(so)
     hits = []
     for e in oracle_reach.suite_corpus()[index::count]:
-        st = orc.Stream(orc.Setup(o, e["ch"], e["rate"], e["q"], bitrate=e["bitrate"]))
-        o.lib.orc_stream_set_capture(st.v, 0)
-        pcm = e["make"]()
-        step = pcm.shape[1] if e.get("one_write") else 1024
-        seq = []
-        for at in range(0, pcm.shape[1], step):
-            st.write(pcm[:, at:at + step])
-            seq.extend(st.blocks())
-        if e.get("eos", True):
-            st.finish()
-            seq.extend(st.blocks())
-        st.close()
+        seq = walk(o, e["ch"], e["rate"], e["q"], e["bitrate"], e["make"](), chunk=None if e.get("one_write") else 1024,
+                   finish=e.get("eos", True), capture=False)
         last = 0
         for b in seq:
             for c in range(e["ch"]):

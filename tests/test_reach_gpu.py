@@ -3,7 +3,8 @@ synth_signal / burst_signal family never takes ("Oracle branches:
 all aoTuV's M2 post-echo reduction: k_prologue's detector, the `s_poste` arm of k_noisemask and the npeak = -1 it
 hands to offset-and-mix and to couple/quantise.
 
-Stage by stage (vbm_analysis_batch on oracle-carved blocks, like tests/test_pipeline_gpu.py): every stage that file
+Stage by stage (run_stages / managed_blobs of tests/encode_calls.py: vbm_analysis_batch on oracle-carved blocks, like
+tests/test_pipeline_gpu.py, shared with tests/test_images_gpu.py): every stage that file
 compares, and for every block three it does not: `poste`, `epeak` and `npeak`, bit for bit.
 
   * `npeak` is compared as couple/quantise leaves it, which is where the oracle captures it: both sides rewrite the
@@ -16,94 +17,19 @@ compares, and for every block three it does not: `poste`, `epeak` and `npeak`, b
 From PCM (the stream front end, like tests/test_vq_edges_gpu.py): block headers and packets, byte for byte, in batches
 that put reach streams and synth_signal streams side by side in one 64-lane tile, so that blocks with poste > 0 sit next
 to blocks without."""
-import numpy as np
 import pytest
-import torch
 
-from tests import orc
+from tests.encode_calls import frontend_vs_oracle, managed_blobs, run_stages
 from tests.reach_signals import REACH, click_trains, decaying_hits, faint_noise, gated_bands, nsamples, overdriven_noise
 from tests.signals import synth_signal
-from tests.test_frontend_gpu import frontend_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
-STAGES_F = ["mdct_raw", "logfft", "logmdct", "noise", "tone", "logmask", "mdct", "epeak"]
 SECONDS = 2.0
-_cache = {}
-
-
-def blocks_of(oracle, key, make, ch, rate, q=None, bitrate=None):
-    """the oracle's blocks of one stream, 1024 samples per write and the end of the stream declared: computed once"""
-    if key not in _cache:
-        st = orc.Stream(orc.Setup(oracle, ch, rate, q, bitrate=bitrate))
-        pcm = make()
-        out = []
-        for at in range(0, pcm.shape[1], 1024):
-            st.write(pcm[:, at:at + 1024])
-            out.extend(st.blocks())
-        st.finish()
-        out.extend(st.blocks())
-        st.close()
-        _cache[key] = out
-    return _cache[key]
 
 
 def synth(ch, rate, seed):
     return synth_signal(ch, rate, nsamples(rate, SECONDS), seed=seed)
-
-
-def steps(streams):
-    """lock step: the k-th block of every stream that has one, grouped by block mode"""
-    for k in range(max(len(b) for b in streams)):
-        by_mode = {}
-        for s, blocks in enumerate(streams):
-            if k < len(blocks):
-                by_mode.setdefault(blocks[k]["block_mode"], []).append(s)
-        for mode, ids in sorted(by_mode.items()):
-            yield k, mode, ids, [streams[s][k] for s in ids]
-
-
-def run_stages(oracle, cuda, ch, rate, q, makers, res1_channels=()):
-    import vorbis_aotuv_lancer_amd as v
-    streams = [blocks_of(oracle, (name, ch, rate, q), make, ch, rate, q) for name, make in makers]
-    setup = v.Setup(ch, rate, q)
-    enc = v.Encoder(setup, len(streams))
-    count = dict(blocks=0, poste=0, minus1=0, mixed=0)
-    for k, mode, ids, blks in steps(streams):
-        pcm = torch.from_numpy(np.stack([b["pcm"] for b in blks])).to(cuda)
-        packets, nbytes = enc.analysis_batch(mode, ids, [b["lW"] | (b["nW"] << 1) for b in blks], pcm)
-        packets, nbytes = packets.cpu().numpy(), nbytes.cpu().numpy()
-        where = (k, mode, ids)
-        ref = np.concatenate([b["poste"] for b in blks])
-        got = enc.fetch("poste").cpu().numpy()
-        assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (where, "poste", got, ref)
-        for name in STAGES_F:
-            got = enc.fetch(name).cpu().numpy().view(np.uint32)
-            want = np.concatenate([b[name] for b in blks]).view(np.uint32)
-            assert np.array_equal(got, want), (where, name, tuple(np.argwhere(got != want)[0]))
-        got = enc.fetch("npeak").cpu().numpy()
-        want = np.concatenate([b["npeak"] for b in blks])
-        assert got.shape == want.shape, (where, "npeak rows", got.shape, want.shape)
-        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (where, "npeak", tuple(np.argwhere(got != want)[0]))
-        for name in ("post_valid", "nonzero"):
-            assert np.array_equal(enc.fetch(name).cpu().numpy(), np.concatenate([b[name] for b in blks])), (where, name)
-        got = enc.fetch("residue").cpu().numpy()
-        want = np.concatenate([b["residue"] for b in blks])
-        if res1_channels:      # a type-1 residue encodes in place: those rows hold the VQ remainder after the packet kernel
-            keep = np.array([c not in res1_channels for c in range(ch)] * len(blks))
-            got, want = got[keep], want[keep]
-        assert np.array_equal(got, want), (where, "residue", tuple(np.argwhere(got != want)[0]))
-        for i, b in enumerate(blks):
-            assert nbytes[i] == len(b["packet"]) and bytes(packets[i, :nbytes[i]]) == b["packet"], (where, "packet", ids[i])
-        count["blocks"] += len(blks)
-        count["poste"] += sum(bool((b["poste"] > 0).any()) for b in blks)
-        count["minus1"] += sum(int((b["npeak"][c] == -1).sum()) for b in blks for c in range(ch) if b["poste"][c] > 0)
-        count["mixed"] += 0 < int((ref > 0).sum()) < len(ref)      # channel-blocks with and without, side by side in a tile
-    enc.close()
-    setup.close()
-    print(f"{ch}ch {rate} q{q:g}: {count['blocks']} blocks compared, {count['poste']} with poste > 0, "
-          f"{count['minus1']} npeak entries of -1 in their channels with poste > 0, {count['mixed']} batches with both kinds of channel-block")
-    return count
 
 
 def test_stages_stereo_q5(oracle, cuda):
@@ -198,46 +124,6 @@ BLOB_CASES = [
     ((144000, 128000, 112000), [("overdriven_noise", lambda: overdriven_noise(2, 44100)), ("synth", lambda: synth(2, 44100, 808))], 0),
 ]
 
-
-def managed_blobs(oracle, cuda, bitrate, makers):
-    """2ch 44100 managed, the streams of `makers` in one encoder: all fifteen packetblobs, the bitrate manager's choice
-    and the delivered packet of every block -> (blocks compared, blocks with poste > 0, packets cut)"""
-    import vorbis_aotuv_lancer_amd as v
-    ch, rate = 2, 44100
-    streams = [blocks_of(oracle, (name, ch, rate, bitrate), make, ch, rate, bitrate=bitrate) for name, make in makers]
-    setup = v.Setup(ch, rate, bitrate=bitrate)
-    enc = v.Encoder(setup, len(streams))
-    nblocks = nposte = ncut = 0
-    for k, mode, ids, blks in steps(streams):
-        pcm = torch.from_numpy(np.stack([b["pcm"] for b in blks])).to(cuda)
-        packets, nbytes = enc.analysis_batch(mode, ids, [b["lW"] | (b["nW"] << 1) for b in blks], pcm)
-        packets, nbytes = packets.cpu().numpy(), nbytes.cpu().numpy()
-        choice = enc.fetch("choice").cpu().numpy()
-        got = enc.fetch("poste").cpu().numpy()
-        ref = np.concatenate([b["poste"] for b in blks])
-        assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (k, mode, ids, "poste")
-        for kb in range(15):
-            bp, bn = enc.fetch_blob(kb)
-            bp, bn = bp.cpu().numpy(), bn.cpu().numpy()
-            for i, b in enumerate(blks):
-                assert bn[i] == b["blob_bytes"][kb], (k, mode, ids[i], "blob size", kb, int(bn[i]), b["blob_bytes"][kb])
-                have, want = bytes(bp[i, :bn[i]]), b["blobs"][kb]
-                if kb == b["choice"] and len(want) < bn[i]:
-                    # oggpack_writetrunc: the oracle cuts the chosen blob in place (to whole bytes) after its size was
-                    # recorded, the device cuts the packet it hands out; the blob is compared up to the cut, the
-                    # packet below in full
-                    have = have[:len(want)]
-                    ncut += 1
-                assert have == want, (k, mode, ids[i], "blob bytes", kb)
-        for i, b in enumerate(blks):
-            assert choice[i] == b["choice"], (k, mode, ids[i], "choice", int(choice[i]), b["choice"])
-            assert nbytes[i] == len(b["packet"]) and bytes(packets[i, :nbytes[i]]) == b["packet"], (k, mode, ids[i])
-        nblocks += len(blks)
-        nposte += sum(bool((b["poste"] > 0).any()) for b in blks)
-    enc.close()
-    setup.close()
-    print(f"2ch 44100 b{bitrate}: {nblocks} blocks compared with all blobs, {nposte} with poste > 0, {ncut} packets cut")
-    return nblocks, nposte, ncut
 
 
 @pytest.mark.parametrize("bitrate,makers,min_poste", BLOB_CASES, ids=["b128000_hits", "b256000_faint", "b128000_minmax_overdriven"])

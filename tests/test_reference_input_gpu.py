@@ -11,21 +11,13 @@ import numpy as np
 import pytest
 import torch
 
-from tests import compat, orc
+from tests import compat
 from tests.decode_packets import matrix_classes
+from tests.encode_calls import drain
+from tests.encode_oracle import compare_records, records, walk
 from tests.signals import gen_windowed_sine
 
 pytestmark = pytest.mark.gpu
-
-
-def oracle_blocks(oracle, ch, rate, q, pcm):
-    st = orc.Stream(orc.Setup(oracle, ch, rate, q))
-    oracle.lib.orc_stream_set_capture(st.v, 0)
-    st.write(pcm)
-    st.finish()
-    want = [((b["lW"], b["W"], b["nW"], b["eos"], b["granulepos"], b["sequence"]), b["packet"]) for b in st.blocks()]
-    st.close()
-    return want
 
 
 def test_matrix_is_not_empty():
@@ -38,8 +30,8 @@ def test_windowed_sine_then_eos(oracle, cuda, ch, rate, q):
     import vorbis_aotuv_lancer_amd as v
     sine = gen_windowed_sine()
     pcm = np.repeat(sine[None, :], ch, axis=0)                # the same data on every channel (write_read.c:88-92)
-    want = oracle_blocks(oracle, ch, rate, q, pcm)
-    assert want and want[-1][0][3] == 1 and want[-1][0][4] == 2048      # e_o_s, last granule = samples written
+    want = records(walk(oracle, ch, rate, q, pcm=pcm, chunk=None, capture=False))
+    assert want and want[-1][0][4] == 1 and want[-1][0][5] == 2048      # e_o_s, last granule = samples written
 
     # batched front end: S = 3 streams with the same input, end declared before the first round
     S = 3
@@ -48,22 +40,15 @@ def test_windowed_sine_then_eos(oracle, cuda, ch, rate, q):
     fe.write(torch.from_numpy(np.repeat(pcm[None], S, axis=0)).to(cuda))
     fe.finish()
     got = [[] for _ in range(S)]
-    while True:
-        info, packets, nbytes = fe.encode_round()
-        if len(info) == 0:
-            break
-        packets, nbytes = packets.cpu().numpy(), nbytes.cpu().numpy()
-        for k, pi in enumerate(info):
-            got[int(pi["stream"])].append(((int(pi["lW"]), int(pi["W"]), int(pi["nW"]), int(pi["eos"]), int(pi["granulepos"]),
-                                            int(pi["packetno"])), bytes(packets[k, :nbytes[k]])))
+    drain(fe, got)
     for s in range(S):
-        assert got[s] == want, f"stream {s}"
+        compare_records(got[s], want, f"stream {s}")
     fe.close()
 
-    # the reference's own call sequence (test/write_read.c:85-115)
+    # the reference's own call sequence (test/write_read.c:85-115); its packets carry no block type
     dll = compat.bind(C.CDLL(v.COMPAT_LIB_PATH))
     st = compat.Stream(dll, ch, rate, q)
     assert st.write(pcm) == 0
     assert st.finish() == 0
-    assert st.drain() == want
+    assert st.drain() == [(m[:3] + m[4:], p) for m, p in want]
     st.close()

@@ -17,25 +17,12 @@ tests/test_vq_search_cpu.py on the host instead.
 """
 import numpy as np
 import pytest
-import torch
 
-from tests import orc
+from tests.encode_calls import write_and_drain
+from tests.encode_oracle import compare_records, records, walk
 from tests.vq_edge_cases import CASES, N
 
 pytestmark = pytest.mark.gpu
-
-def oracle_packets(oracle, ch, rate, q, pcm):
-    st = orc.Stream(orc.Setup(oracle, ch, rate, q))
-    oracle.lib.orc_stream_set_capture(st.v, 0)
-    want = []
-    for at in list(range(0, pcm.shape[1], 1024)) + [None]:
-        if at is None:
-            st.finish()
-        else:
-            st.write(pcm[:, at:at + 1024])
-        want += [((b["lW"], b["W"], b["nW"], b["eos"], b["granulepos"], b["sequence"]), b["packet"]) for b in st.blocks()]
-    st.close()
-    return want
 
 
 @pytest.mark.parametrize("name,ch,rate,q,make", CASES, ids=[c[0] for c in CASES])
@@ -43,7 +30,7 @@ def test_edge_signal_matches_oracle(oracle, cuda, name, ch, rate, q, make):
     import vorbis_aotuv_lancer_amd as v
     pcm = make(ch, rate)
     assert pcm.shape == (ch, N) and pcm.dtype == np.float32
-    want = oracle_packets(oracle, ch, rate, q, pcm)
+    want = records(walk(oracle, ch, rate, q, pcm=pcm, capture=False))
     assert len(want) > 40 and {w[0][1] for w in want} == {0, 1}, "the signal must produce long and short blocks"
 
     # two streams with the same input (lanes 0 and 1 of a tile), written 1024 samples at a time
@@ -51,26 +38,7 @@ def test_edge_signal_matches_oracle(oracle, cuda, name, ch, rate, q, make):
     enc = v.Encoder(v.Setup(ch, rate, q), S)
     fe = v.FrontEnd(enc)
     got = [[] for _ in range(S)]
-
-    def drain():
-        while True:
-            info, packets, nbytes = fe.encode_round()
-            if len(info) == 0:
-                return
-            packets, nbytes = packets.cpu().numpy(), nbytes.cpu().numpy()
-            for k, pi in enumerate(info):
-                got[int(pi["stream"])].append(((int(pi["lW"]), int(pi["W"]), int(pi["nW"]), int(pi["eos"]),
-                                                int(pi["granulepos"]), int(pi["packetno"])), bytes(packets[k, :nbytes[k]])))
-
-    allp = torch.from_numpy(np.repeat(pcm[None], S, axis=0)).to(cuda)
-    for at in range(0, N, 1024):
-        fe.write(allp[:, :, at:at + 1024].contiguous())
-        drain()
-    fe.finish()
-    drain()
+    write_and_drain(fe, cuda, [pcm] * S, got)
     fe.close()
     for s in range(S):
-        assert len(got[s]) == len(want), f"stream {s}: {len(got[s])} packets, the oracle has {len(want)}"
-        for k, (g, w) in enumerate(zip(got[s], want)):
-            assert g[0] == w[0], f"stream {s} packet {k}: block {g[0]} against the oracle's {w[0]}"
-            assert g[1] == w[1], f"stream {s} packet {k} (W={w[0][1]}): {len(g[1])} bytes differ from the oracle's {len(w[1])}"
+        compare_records(got[s], want, f"stream {s}")

@@ -6,8 +6,8 @@ import pytest
 import torch
 
 from tests import intake_cases as ic
+from tests.encode_calls import DeviceRun, compare_slots, need_types, osetup, wanted
 from tests.signals import burst_signal
-from tests.test_intake_gpu import DeviceRun, compare, need_types, osetup, wanted
 
 pytestmark = pytest.mark.gpu
 
@@ -118,7 +118,7 @@ def test_mixed_sizes_in_one_step(oracle, cuda, cls):
     assert run.wide >= 3 and run.narrow >= 3, (run.wide, run.narrow)     # both copy paths ran
     run.fe.device_stats()
     assert run.fe.refused_writes == 0
-    compare(got, want, "ragged")
+    compare_slots(got, want, "ragged")
     run.close()
 
 
@@ -171,7 +171,7 @@ def test_refused_calls_change_no_stream(oracle, cuda):
         fe.write_ragged([0], store, [0], [64])
     assert int(v.lib.vbm_frontend_write_ragged(fe._h, None, 0, None, None, None, None, None)) == 0   # nothing listed
     same_packets(got, plain.run(signals, schedule))
-    compare(got, want, "after refused calls")
+    compare_slots(got, want, "after refused calls")
     run.fe.device_stats()
     assert run.fe.refused_writes == 0
     run.close()

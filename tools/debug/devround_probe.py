@@ -5,6 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 os.environ.setdefault("VBM_WORKSPACES", "4")
 import vorbis_aotuv_lancer_amd as v
 from tests import orc
+from tests.encode_oracle import walk
 from tests.signals import synth_signal
 import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,15 +14,7 @@ oracle = orc.Oracle(so)
 ch, rate, q, NS, K = 2, 44100, 0.5, int(os.environ.get("NS", "1100")), 7
 nsamp = 26 * 1024
 base = [synth_signal(ch, rate, nsamp, seed=730 + k, level=1.0 if k % 3 else 0.05) for k in range(K)]
-osetup = orc.Setup(oracle, ch, rate, q)
-want = []
-for k in range(K):
-    st = orc.Stream(osetup); oracle.lib.orc_stream_set_capture(st.v, 0)
-    seq = []
-    for at in range(0, nsamp, 1024):
-        st.write(base[k][:, at:at + 1024]); seq.extend(st.blocks())
-    st.close()
-    want.append([b["packet"] for b in seq])
+want = [[b["packet"] for b in walk(oracle, ch, rate, q, pcm=base[k], finish=False, capture=False)] for k in range(K)]
 setup = v.Setup(ch, rate, q)
 lanes = v.lib.vbm_device_round_lanes(setup._h, NS)
 enc = v.Encoder(setup, NS, max_batch=lanes)

@@ -2,7 +2,7 @@
 import sys, os, numpy as np, torch, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from tests import orc
-from tests.test_frontend_gpu import probe_pcm, drain
+from tests.encode_calls import probe_pcm, drain
 import vorbis_aotuv_lancer_amd as v
 o = orc.Oracle("oracle/build/liboracle.so")
 ch, rate, q, secs = 2, 44100, 0.5, int(sys.argv[1]) if len(sys.argv) > 1 else 20

@@ -2,7 +2,7 @@
 import sys, os, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from tests.signals import synth_signal
-from tests.test_frontend_gpu import drain
+from tests.encode_calls import drain
 import vorbis_aotuv_lancer_amd as v
 ch, rate, q, NS, seconds = 2, 44100, 0.5, 40, 2.2
 nsamp = int(seconds * rate) // 1024 * 1024
