@@ -810,7 +810,8 @@ int vbm_window_mdct_time(const vbm_mdct_plan *plan, const float *d_pcm, float *d
  * vorbis_synthesis + vorbis_synthesis_blockin + vorbis_synthesis_pcmout + vorbis_synthesis_read
  * (reference lib/synthesis.c:25-91, lib/block.c:897-1190; examples/decoder_example.c).
  * Not supported (VBM_EIMPL at setup): floor type 0, block sizes outside 256..4096, more than 8 channels.  No chained
- * streams; seeking is by sample windows of a range store (vbm_synthesis_ranges), not of a live stream.  Half-rate
+ * streams; seeking is by sample windows of a range store (vbm_synthesis_ranges); a live stream gets them through a
+ * live range store, which keeps its last packets (vbm_live_store_*, "live range store" below).  Half-rate
  * decoding (vorbis_synthesis_halfrate) is a property of the decoder: vbm_decoder_create_halfrate below.  The
  * reference's own vorbis_synthesis* names are not exported. */
 #define VBM_ENOTVORBIS (-132) /* OV_ENOTVORBIS, include/vorbis/codec.h:229-233 */
@@ -1104,6 +1105,71 @@ int  vbm_host_ogg_cut_ranges(vbm_ogg_cutter *cut, int nstreams, const long long 
                              const uint8_t *header_pages, const long long *header_offsets, const int *header_ids,
                              uint8_t *out, long long out_cap,
                              long long *out_offsets, int *out_status, long long *got_starts, long long *got_lengths);
+
+/* ---- live range store: an appendable range store for live feeds (csrc/live_store.h) ------------------------------------
+ * A vbm_range_store with a fixed region per stream: max_packets packet slots and max_bytes payload bytes in device
+ * memory.  It takes appended runs of packets, in the arguments of vbm_synthesis_runs_gaps, and drops the oldest packets
+ * when a region is full.  vbm_synthesis_ranges, vbm_ogg_cut_ranges, vbm_range_store_totals and vbm_range_store_destroy
+ * take it as they take any store.
+ *   Positions are output samples since the slot's last restart, at the decoder's rate: the concatenation of what
+ *   vbm_synthesis_runs_gaps returns for the same packets, granule positions, e_o_s flags and gap marks in the same order.
+ *   totals[i] is its end; first_sample[i] is out_end of the first retained valid packet, which serves only as pre-roll
+ *   (no valid packet retained: totals[i]; a fresh slot: 0).  A window that starts at or behind first_sample[i] is bit for
+ *   bit the slice of the linear decode; one that starts in front of it gets got = 0 (a cut: an empty output, length 0).
+ *   vbm_live_store_create   for a decoder of one setup; _create_mixed for one of vbm_decoder_create_mixed, whose slots
+ *                           have no class until vbm_live_store_restart gives them one.  Memory: about nstreams *
+ *                           (max_bytes + 32 * max_packets) bytes.  max_bytes < 2^31 - 64, nstreams * (max_packets + 1)
+ *                           < 2^31 - 1.
+ *   vbm_live_store_append   entry e: run_packets[e] >= 0 consecutive packets for slot stream_ids[e] (host arrays, ids
+ *                           distinct, n <= nstreams), the entries' packets concatenated in one CSR on the device (d_data,
+ *                           d_offsets [P + 1], d_granulepos / d_eos / d_gap [P] or NULL).  The index goes on from the
+ *                           slot's carried state, so how a stream is split over appends does not show.  Per entry
+ *                           (host, any may be NULL): status[e] 0, VBM_LIVE_EBIG (a run of more than max_packets packets or
+ *                           max_bytes bytes: the slot is left as it was, the other entries are appended) or VBM_EINVAL
+ *                           (its offsets are no CSR inside d_data: likewise); dropped[e], the packets that left;
+ *                           retained[e], the packets the slot holds now.  A run that does not fit makes the slot drop,
+ *                           from the front, the fewest packets such that what remains is at most half of each capacity
+ *                           and leaves room for the run; the rest moves to the front of the region.  Enqueues on
+ *                           `stream` and waits for it once: 40 B per entry and 12 B per new packet come back for the
+ *                           host planner, and the caller's arrays are free when it returns.  VBM_EINVAL, with nothing
+ *                           changed: an id out of range or listed twice, a negative count, a slot without a class.
+ *   vbm_live_store_restart  the listed slots (distinct) are empty and fresh; classes [n] (host) for a store of a mixed
+ *                           decoder, which sets each slot's class until its next restart, and NULL for any other.
+ *                           Only enqueues.
+ *   vbm_live_store_state    first_sample, totals, packets, bytes [nstreams] and trims [2] (trims the packet cap made,
+ *                           trims the byte cap made), from the host's mirror; any may be NULL.
+ *   vbm_live_store_snapshot the retained packets of all streams as a compact index and CSR in host arrays, the form
+ *                           vbm_host_ogg_cut_ranges takes: first [nstreams + 1]; status, begin, out_end [P]; totals
+ *                           [nstreams]; data, offsets [P + 1], with P and the bytes summed from vbm_live_store_state.
+ *                           Waits for `stream`.
+ * Calls on one store (append, restart, ranges, cut, snapshot) are ordered by the caller on one stream.
+ * vbm_host_live_store_*: the CPU twin over host memory, from the same source (csrc/live_store.h): no device and no
+ * decoder, only the setup and the rate.  Its append refuses offsets that are no CSR with VBM_EINVAL for the whole call.
+ * A host store in a device call, or the reverse, is VBM_EINVAL. */
+#define VBM_LIVE_EBIG (-1004)
+int  vbm_live_store_create(vbm_range_store **st, vbm_decoder *dec, int nstreams, int max_packets, long long max_bytes);
+int  vbm_live_store_create_mixed(vbm_range_store **st, vbm_decoder *dec, int nstreams, int max_packets,
+                                 long long max_bytes);
+int  vbm_live_store_append(vbm_range_store *st, int n, const int *stream_ids, const int *run_packets,
+                           const uint8_t *d_data, const long long *d_offsets, long long data_bytes,
+                           const long long *d_granulepos, const uint8_t *d_eos, const uint8_t *d_gap, int *status,
+                           int *dropped, int *retained, void *stream);
+int  vbm_live_store_restart(vbm_range_store *st, int n, const int *stream_ids, const int *classes, void *stream);
+int  vbm_live_store_state(const vbm_range_store *st, long long *first_sample, long long *totals, long long *packets,
+                          long long *bytes, long long *trims);
+int  vbm_live_store_snapshot(const vbm_range_store *st, long long *first, int *status, int *begin, long long *out_end,
+                             long long *totals, uint8_t *data, long long *offsets, void *stream);
+int  vbm_host_live_store_create(vbm_range_store **st, const vbm_decode_setup *ds, int halfrate, int nstreams,
+                                int max_packets, long long max_bytes);
+int  vbm_host_live_store_append(vbm_range_store *st, int n, const int *stream_ids, const int *run_packets,
+                                const uint8_t *data, const long long *offsets, long long data_bytes,
+                                const long long *granulepos, const uint8_t *eos, const uint8_t *gap, int *status,
+                                int *dropped, int *retained);
+int  vbm_host_live_store_restart(vbm_range_store *st, int n, const int *stream_ids);
+int  vbm_host_live_store_state(const vbm_range_store *st, long long *first_sample, long long *totals,
+                               long long *packets, long long *bytes, long long *trims);
+int  vbm_host_live_store_snapshot(const vbm_range_store *st, long long *first, int *status, int *begin,
+                                  long long *out_end, long long *totals, uint8_t *data, long long *offsets);
 
 /* ---- test instrumentation --------------------------------------------------------------------------------
  * The path is spread over several internal HIP streams; events order them.  These calls make a missing edge show

@@ -16,8 +16,8 @@ from .mdct import MdctLookup, mdct_forward, window_mdct, window_fft_log  # noqa:
 from .encoder import Setup, Encoder, FrontEnd, PacketInfo, batch_variants  # noqa: F401,E402
 from .stream import header_packets, OggStream, OggMux, write_ogg, read_ogg, demux_ogg, DeviceDemuxer, DemuxBatch, demux_ogg_device, ChainSplitter, split_ogg_chain, StreamSelector, select_vorbis_stream, OggFeed, FeedResult, OggCutter, header_pages  # noqa: F401,E402
 from .decoder import (DecodeSetup, Decoder, MixedDecoder, decode_ogg, decode_index, decode_index_device,  # noqa: F401,E402
-                      decode_index_scan_host, RangeStore, OggIndex)  # noqa: F401,E402
+                      decode_index_scan_host, RangeStore, LiveRangeStore, LiveAppend, OggIndex)  # noqa: F401,E402
 from .files import encode_ogg, plan_files  # noqa: F401,E402
 
-__all__ = ["Setup", "Encoder", "FrontEnd", "PacketInfo", "batch_variants", "header_packets", "OggStream", "OggMux", "write_ogg", "read_ogg", "demux_ogg", "DeviceDemuxer", "DemuxBatch", "demux_ogg_device", "ChainSplitter", "split_ogg_chain", "StreamSelector", "select_vorbis_stream", "OggFeed", "FeedResult", "OggCutter", "header_pages", "DecodeSetup", "Decoder", "MixedDecoder", "decode_ogg", "encode_ogg", "plan_files", "decode_index", "decode_index_device", "decode_index_scan_host", "RangeStore", "OggIndex", "lib", "LIB_PATH", "COMPAT_LIB_PATH", "VbmError", "check", "window_table",
+__all__ = ["Setup", "Encoder", "FrontEnd", "PacketInfo", "batch_variants", "header_packets", "OggStream", "OggMux", "write_ogg", "read_ogg", "demux_ogg", "DeviceDemuxer", "DemuxBatch", "demux_ogg_device", "ChainSplitter", "split_ogg_chain", "StreamSelector", "select_vorbis_stream", "OggFeed", "FeedResult", "OggCutter", "header_pages", "DecodeSetup", "Decoder", "MixedDecoder", "decode_ogg", "encode_ogg", "plan_files", "decode_index", "decode_index_device", "decode_index_scan_host", "RangeStore", "LiveRangeStore", "LiveAppend", "OggIndex", "lib", "LIB_PATH", "COMPAT_LIB_PATH", "VbmError", "check", "window_table",
            "MdctLookup", "mdct_forward", "window_mdct", "window_fft_log"]

@@ -35,6 +35,13 @@
 // the <MX = true> one of vbm_synthesis_runs, its IMDCT grids sized by sum(rows x channels of the piece's class).  The
 // index stages the streams' classes behind their first packets; k_index_head finds a packet's stream, hence class, by
 // a search in that table, and k_index_scan takes stream i's block sizes from its class.
+//
+// Live range stores (vbm_live_store_*; rules, layout and kernels: live_store.h, live_store.hip): a range store with a
+// fixed region per stream that takes appended runs (the arguments of vbm_synthesis_runs_gaps) and drops the oldest
+// packets when a region is full.  An append enqueues k_index_head over the caller's CSR and the four live kernels, reads
+// 40 B per entry and 12 B per new packet back and waits once; vbm_synthesis_ranges and vbm_ogg_cut_ranges read it
+// through the view, which says where each stream's packets end and which sample is the first it still has.  The host
+// twin (vbm_host_live_store_*) is the same object over host memory, with no decoder.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -44,6 +51,7 @@
 #include "decode_index.h"
 #include "decode_kernels.h"
 #include "decode_setup.h"
+#include "live_store.h"
 #include "range_plan.h"
 #include "vbm_internal.h"
 #include "vorbis_mi355x.h"
@@ -637,13 +645,68 @@ struct vbm_range_store {
     long long *d_offsets = nullptr, *d_out_start = nullptr;   // [P + 1], [P]
     int *d_begin = nullptr, *d_end = nullptr;                 // [P]
     std::vector<int> cls;                // [S] the class of each stream, in a store of a mixed decoder (else empty)
+    int halfrate = 0;                    // the decoder's (a host twin's store has no decoder)
+    struct vbm_live *live = nullptr;     // a live store's regions, state mirror and workspace (below), else null
 };
+
+// A live store (live_store.h) is a vbm_range_store whose streams lie in fixed regions: first[i] = i * (MP + 1), the host
+// index (status, out_end) is sized for every slot, and d_data .. d_end are the regions' arrays.  The device form's
+// workspace: one pinned table (the entries of an append or restart go up in it; its event says when the copy out of it is
+// done), the head's verdicts on the appended packets, the plans, the trimmed list, and the block that comes back in one
+// copy: the entries' records, then out_end and status of every new packet (12 B each).
+struct vbm_live {
+    bool host = false;
+    vbml_arrays A = {};                  // device memory, or host memory in the twin
+    vbmd_setup hs;                       // twin: the setup
+    std::vector<long long> last, lo, bytes;      // [S] mirror: end of the stream's packets, first_sample, retained bytes
+    long long trims[2] = {0, 0};         // trims made by the packet cap, by the byte cap
+    int *h_tab = nullptr, *d_tab = nullptr, *d_trimmed = nullptr;      // [3 S + 1], [3 S + 1], [S + 1]
+    hipEvent_t ev_tab = nullptr;
+    vbml_plan *d_plans = nullptr;        // [S]
+    size_t pk_cap = 0;                   // packets one append may bring before the next three grow
+    int *d_head = nullptr;               // [2 pk_cap] status, W
+    uint8_t *d_back = nullptr, *h_back = nullptr;          // [S records + 12 pk_cap]
+    std::vector<int> seen;
+    std::vector<uint8_t> twin_mem;       // twin: d_head's and d_back's stand-ins
+};
+
+namespace {
+
+void free_live(vbm_range_store *st)
+{
+    vbm_live *lv = st->live;
+    void *arrays[] = {lv->A.slots, lv->A.data, lv->A.offsets, lv->A.out_start, lv->A.status, lv->A.begin, lv->A.end};
+    for (void *p : arrays)
+        if (p) lv->host ? free(p) : (void)hipFree(p);
+    void *work[] = {lv->d_tab, lv->d_trimmed, lv->d_plans, lv->d_head, lv->d_back};
+    for (void *p : work)
+        if (p) (void)hipFree(p);
+    if (lv->h_tab) (void)hipHostFree(lv->h_tab);
+    if (lv->h_back) (void)hipHostFree(lv->h_back);
+    if (lv->ev_tab) (void)hipEventDestroy(lv->ev_tab);
+    delete lv;
+    st->live = nullptr;
+}
+
+void live_view(const vbm_range_store *st, vbm_range_store_view *v)
+{
+    v->last = st->live->last.data();
+    v->lo = st->live->lo.data();
+    v->host = st->live->host;
+}
+
+}  // namespace
 
 namespace {
 
 void free_store(vbm_range_store *st)
 {
     if (!st) return;
+    if (st->live) {                      // a live store's arrays are its regions'
+        free_live(st);
+        delete st;
+        return;
+    }
     void *bufs[] = {st->d_data, st->d_offsets, st->d_out_start, st->d_begin, st->d_end};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
@@ -689,6 +752,7 @@ int new_store(vbm_range_store **out, vbm_decoder *d, int nstreams, const long lo
     vbm_range_store *st = new vbm_range_store();
     auto fail = [st](int rc) { free_store(st); return rc; };
     st->dec = d;
+    st->halfrate = d->halfrate;
     st->S = nstreams;
     st->first.assign(stream_packets, stream_packets + nstreams + 1);
     if (classes) st->cls.assign(classes, classes + nstreams);
@@ -793,14 +857,16 @@ extern "C" int vbm_range_store_create_mixed(vbm_range_store **out, vbm_decoder *
 extern "C" void vbm_range_store_destroy(vbm_range_store *st)
 {
     if (!st) return;
-    (void)hipDeviceSynchronize();
+    if (!st->live || !st->live->host) (void)hipDeviceSynchronize();
     free_store(st);
 }
 
 void vbm_range_store_get_view(const vbm_range_store *st, vbm_range_store_view *v)
 {
-    *v = {st->S, st->dec->halfrate, (long long)st->status.size(), st->data_bytes, st->first.data(), st->out_end.data(),
-          st->totals.data(), st->status.data(), st->d_data, st->d_offsets, st->d_out_start, st->d_begin, st->d_end};
+    *v = {st->S, st->halfrate, (long long)st->status.size(), st->data_bytes, st->first.data(), st->out_end.data(),
+          st->totals.data(), st->first.data() + 1, nullptr, 0, st->status.data(), st->d_data, st->d_offsets,
+          st->d_out_start, st->d_begin, st->d_end};
+    if (st->live) live_view(st, v);
 }
 
 extern "C" int vbm_range_store_totals(const vbm_range_store *st, long long *totals)
@@ -817,7 +883,7 @@ extern "C" int vbm_synthesis_ranges(vbm_decoder *d, const vbm_range_store *st, i
     if (!d || !st || nranges < 0 || (nranges > 0 && (!stream_ids || !starts || !lengths || !got)))
         return VBM_EINVAL;
     if (st->dec != d) {
-        g_vbm_err = d->mixed ? "the range store was not made for this mixed decoder (vbm_range_store_create_mixed)"
+        g_vbm_err = st->live && st->live->host ? "a host store (vbm_host_live_store_create) in a device call" : d->mixed ? "the range store was not made for this mixed decoder (vbm_range_store_create_mixed)"
                              : "the range store belongs to another decoder";
         return VBM_EINVAL;
     }
@@ -833,8 +899,10 @@ extern "C" int vbm_synthesis_ranges(vbm_decoder *d, const vbm_range_store *st, i
     if (pcm_stride < most) { g_vbm_err = "pcm_stride below max(lengths)"; return VBM_EINVAL; }
     if (any && !d_pcm) return VBM_EINVAL;
     vbm_range_plan plan;
-    const char *err = vbm_plan_ranges(st->first.data(), st->status.data(), st->out_end.data(), st->totals.data(), d->cap,
-                                      nranges, stream_ids, starts, lengths, got, &plan);
+    vbm_range_store_view v;
+    vbm_range_store_get_view(st, &v);
+    const char *err = vbm_plan_ranges(v.first, v.last, v.lo, v.status, v.out_end, v.totals, d->cap, nranges, stream_ids,
+                                      starts, lengths, got, &plan);
     if (err) { g_vbm_err = err; return VBM_EINVAL; }
     hipStream_t q = (hipStream_t)stream;
     std::vector<int> tab;
@@ -947,4 +1015,465 @@ extern "C" int vbm_range_store_create_device_mixed(vbm_range_store **out, vbm_de
     if (np) memcpy(st->status.data(), back.data() + (np + ns) * sizeof(long long), np * sizeof(int));
     (void)hipFree(d_back);
     return VBM_OK;
+}
+
+// ---- live range stores (live_store.h, live_store.hip) ------------------------------------------------------------------
+namespace {
+
+int live_fail(vbm_range_store *st, int rc)
+{
+    free_store(st);
+    return rc;
+}
+
+// n zeroed elements in the store's kind of memory
+template <class T> int live_get(vbm_live *lv, T *&p, size_t n)
+{
+    const size_t bytes = (n ? n : 1) * sizeof(T);
+    void *v = nullptr;
+    if (lv->host) {
+        v = calloc(bytes, 1);
+        if (!v) { g_vbm_err = "live store: out of host memory"; return VBM_EFAULT; }
+    } else {
+        hipError_t e = hipMalloc(&v, bytes);
+        if (e == hipSuccess) e = hipMemset(v, 0, bytes);
+        if (e != hipSuccess) {
+            if (v) (void)hipFree(v);
+            return vbm_set_hip_error(e, "live store: hipMalloc");
+        }
+    }
+    p = (T *)v;
+    return VBM_OK;
+}
+
+// room for an append of P packets: the head's arrays and the block that comes back
+int live_room(vbm_live *lv, int S, size_t P)
+{
+    if (P <= lv->pk_cap && (lv->host ? !lv->twin_mem.empty() : lv->d_back != nullptr)) return VBM_OK;
+    const size_t cap = std::max(P, std::max<size_t>(2 * lv->pk_cap, 1024));
+    const size_t back_bytes = (size_t)S * sizeof(vbml_back) + cap * 12;
+    if (lv->host) {
+        lv->twin_mem.assign(back_bytes + cap * 2 * sizeof(int), 0);
+        lv->pk_cap = cap;
+        return VBM_OK;
+    }
+    if (lv->d_head) (void)hipFree(lv->d_head);
+    if (lv->d_back) (void)hipFree(lv->d_back);
+    if (lv->h_back) (void)hipHostFree(lv->h_back);
+    lv->d_head = nullptr, lv->d_back = lv->h_back = nullptr, lv->pk_cap = 0;
+    hipError_t e = hipMalloc((void **)&lv->d_head, cap * 2 * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void **)&lv->d_back, back_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&lv->h_back, back_bytes, hipHostMallocDefault);
+    if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_live_store_append: workspace");
+    lv->pk_cap = cap;
+    return VBM_OK;
+}
+
+// ds: the twin's setup (then d is null); classes: a store of a mixed decoder
+int live_create(vbm_range_store **out, vbm_decoder *d, const vbm_decode_setup *ds, int halfrate, bool mixed,
+                int nstreams, int max_packets, long long max_bytes)
+{
+    if (!out) return VBM_EINVAL;
+    *out = nullptr;
+    if (halfrate != 0 && halfrate != 1) { g_vbm_err = "halfrate must be 0 or 1"; return VBM_EINVAL; }
+    if ((!d && !ds) || nstreams <= 0 || max_packets <= 0 || max_bytes <= 0) {
+        g_vbm_err = "a live store needs a decoder or setup, nstreams, max_packets and max_bytes above 0";
+        return VBM_EINVAL;
+    }
+    if (d && mixed != (d->mixed != 0)) {
+        g_vbm_err = mixed ? "vbm_live_store_create_mixed needs a decoder of vbm_decoder_create_mixed"
+                          : "a live store of a mixed decoder is made by vbm_live_store_create_mixed";
+        return VBM_EINVAL;
+    }
+    if (max_bytes > INT_MAX - 64 || (long long)nstreams * ((long long)max_packets + 1) >= INT_MAX) {
+        g_vbm_err = "a live store holds at most 2^31 - 65 bytes per stream and 2^31 - 2 packet slots in all";
+        return VBM_EINVAL;
+    }
+    vbm_range_store *st = new vbm_range_store();
+    vbm_live *lv = st->live = new vbm_live();
+    lv->host = d == nullptr;
+    if (ds) lv->hs = ds->s;
+    st->dec = d;
+    st->halfrate = d ? d->halfrate : halfrate;
+    st->S = nstreams;
+    const size_t S = (size_t)nstreams, slots = S * ((size_t)max_packets + 1);
+    vbml_arrays &A = lv->A;
+    A.MP = max_packets;
+    A.MB = max_bytes;
+    A.stride = (max_bytes + 15) & ~15LL;
+    st->first.resize(S + 1);
+    for (size_t i = 0; i <= S; i++) st->first[i] = (long long)(i * ((size_t)max_packets + 1));
+    st->status.assign(slots, 0);
+    st->out_end.assign(slots, 0);
+    st->totals.assign(S, 0);
+    if (mixed) st->cls.assign(S, -1);
+    lv->last.assign(st->first.begin(), st->first.begin() + S);
+    lv->lo.assign(S, 0);
+    lv->bytes.assign(S, 0);
+    lv->seen.assign(S, 0);
+    st->data_bytes = (long long)S * A.stride;
+    int rc = live_get(lv, A.slots, S);
+    if (!rc) rc = live_get(lv, A.data, (size_t)st->data_bytes + 16);
+    if (!rc) rc = live_get(lv, A.offsets, slots + 1);
+    if (!rc) rc = live_get(lv, A.out_start, slots);
+    if (!rc) rc = live_get(lv, A.status, slots);
+    if (!rc) rc = live_get(lv, A.begin, slots);
+    if (!rc) rc = live_get(lv, A.end, slots);
+    if (rc) return live_fail(st, rc);
+    st->d_data = A.data, st->d_offsets = A.offsets, st->d_out_start = A.out_start, st->d_begin = A.begin, st->d_end = A.end;
+    // every slot fresh (class -1 in a mixed store: vbm_live_store_restart gives it one), every region's first offset
+    std::vector<vbml_slot> fresh(S, vbml_fresh(mixed ? -1 : 0));
+    std::vector<long long> offs(slots + 1, 0);
+    for (size_t i = 0; i < S; i++) offs[i * ((size_t)max_packets + 1)] = (long long)i * A.stride;
+    if (lv->host) {
+        memcpy(A.slots, fresh.data(), S * sizeof(vbml_slot));
+        memcpy(A.offsets, offs.data(), offs.size() * sizeof(long long));
+        if ((rc = live_room(lv, nstreams, 0))) return live_fail(st, rc);
+        *out = st;
+        return VBM_OK;
+    }
+    auto fail = [st](int rc) { return live_fail(st, rc); };
+    CK(hipMemcpy(A.slots, fresh.data(), S * sizeof(vbml_slot), hipMemcpyHostToDevice));
+    CK(hipMemcpy(A.offsets, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice));
+    CK(hipHostMalloc((void **)&lv->h_tab, (3 * S + 1) * sizeof(int), hipHostMallocDefault));
+    CK(hipEventCreateWithFlags(&lv->ev_tab, hipEventDisableTiming));
+    CK(hipMalloc((void **)&lv->d_tab, (3 * S + 1) * sizeof(int)));
+    CK(hipMalloc((void **)&lv->d_trimmed, (S + 1) * sizeof(int)));
+    CK(hipMalloc((void **)&lv->d_plans, S * sizeof(vbml_plan)));
+    if ((rc = live_room(lv, nstreams, 0))) return fail(rc);
+    *out = st;
+    return VBM_OK;
+}
+
+// the store's kind, and every id in range and listed once
+int live_check(vbm_range_store *st, bool host, int n, const int *ids, const char *who)
+{
+    if (!st || !st->live) { g_vbm_err = std::string(who) + ": needs a live store"; return VBM_EINVAL; }
+    if (st->live->host != host) {
+        g_vbm_err = std::string(who) + (host ? ": a device store in a host call" : ": a host store in a device call");
+        return VBM_EINVAL;
+    }
+    if (n < 0 || n > st->S || (n > 0 && !ids)) { g_vbm_err = std::string(who) + ": bad entry count or null ids"; return VBM_EINVAL; }
+    std::vector<int> &seen = st->live->seen;
+    std::fill(seen.begin(), seen.end(), 0);
+    for (int e = 0; e < n; e++) {
+        if (ids[e] < 0 || ids[e] >= st->S) { g_vbm_err = std::string(who) + ": stream id out of range"; return VBM_EINVAL; }
+        if (seen[ids[e]]) { g_vbm_err = std::string(who) + ": stream id appears twice in one call"; return VBM_EINVAL; }
+        seen[ids[e]] = 1;
+    }
+    return VBM_OK;
+}
+
+// the entries of the pinned table: first packets [n + 1], classes [n] (a mixed store), slots [n]
+void live_table(const vbm_range_store *st, int n, const int *ids, const int *counts, int *tab)
+{
+    int P = 0;
+    for (int e = 0; e < n; e++) {
+        tab[e] = P;
+        P += counts[e];
+    }
+    tab[n] = P;
+    const int ids_at = st->cls.empty() ? n + 1 : 2 * n + 1;
+    for (int e = 0; e < n; e++) {
+        if (!st->cls.empty()) tab[n + 1 + e] = st->cls[ids[e]];
+        tab[ids_at + e] = ids[e];
+    }
+}
+
+// the host's part of an append: the records that came back -> the mirror, and the caller's per-entry arrays
+void live_commit(vbm_range_store *st, int n, const int *ids, const int *tab, const vbml_back *back,
+                 const long long *pk_out_end, const int *pk_status, int *status, int *dropped, int *retained)
+{
+    vbm_live *lv = st->live;
+    for (int e = 0; e < n; e++) {
+        const vbml_back &b = back[e];
+        const int sid = ids[e];
+        if (status) status[e] = b.status;
+        if (dropped) dropped[e] = b.dropped;
+        if (retained) retained[e] = b.retained;
+        if (b.status) continue;
+        const long long P0 = st->first[sid];
+        const long long keep = lv->last[sid] - P0 - b.dropped;
+        if (b.dropped && keep > 0) {
+            memmove(&st->status[P0], &st->status[P0 + b.dropped], (size_t)keep * sizeof(int));
+            memmove(&st->out_end[P0], &st->out_end[P0 + b.dropped], (size_t)keep * sizeof(long long));
+        }
+        const int np = tab[e + 1] - tab[e];
+        if (np > 0) {
+            memcpy(&st->status[P0 + keep], pk_status + tab[e], (size_t)np * sizeof(int));
+            memcpy(&st->out_end[P0 + keep], pk_out_end + tab[e], (size_t)np * sizeof(long long));
+        }
+        lv->last[sid] = P0 + b.retained;
+        lv->lo[sid] = b.first_sample;
+        lv->bytes[sid] = b.bytes;
+        st->totals[sid] = b.total;
+        lv->trims[0] += b.by & 1;
+        lv->trims[1] += (b.by >> 1) & 1;
+    }
+}
+
+// what both appends check of the host arguments; *P: the packets of the call
+int live_append_args(vbm_range_store *st, bool host, int n, const int *ids, const int *counts, const uint8_t *data,
+                     const long long *offsets, long long data_bytes, long long *P, const char *who)
+{
+    int rc = live_check(st, host, n, ids, who);
+    if (rc) return rc;
+    if (data_bytes < 0 || (data_bytes > 0 && !data) || !offsets || (n > 0 && !counts)) {
+        g_vbm_err = std::string(who) + ": null pointer or negative data_bytes";
+        return VBM_EINVAL;
+    }
+    *P = 0;
+    for (int e = 0; e < n; e++) {
+        if (counts[e] < 0) { g_vbm_err = std::string(who) + ": negative packet count"; return VBM_EINVAL; }
+        *P += counts[e];
+        if (!st->cls.empty() && st->cls[ids[e]] < 0) {
+            g_vbm_err = std::string(who) + ": slot " + std::to_string(ids[e]) + " has no class (vbm_live_store_restart)";
+            return VBM_EINVAL;
+        }
+    }
+    if (*P >= INT_MAX) { g_vbm_err = std::string(who) + ": more than 2^31 - 2 packets in one call"; return VBM_EINVAL; }
+    return VBM_OK;
+}
+
+}  // namespace
+
+extern "C" int vbm_live_store_create(vbm_range_store **st, vbm_decoder *dec, int nstreams, int max_packets,
+                                     long long max_bytes)
+{
+    if (!dec) return VBM_EINVAL;
+    return live_create(st, dec, nullptr, 0, false, nstreams, max_packets, max_bytes);
+}
+
+extern "C" int vbm_live_store_create_mixed(vbm_range_store **st, vbm_decoder *dec, int nstreams, int max_packets,
+                                           long long max_bytes)
+{
+    if (!dec) return VBM_EINVAL;
+    return live_create(st, dec, nullptr, 0, true, nstreams, max_packets, max_bytes);
+}
+
+extern "C" int vbm_host_live_store_create(vbm_range_store **st, const vbm_decode_setup *ds, int halfrate, int nstreams,
+                                          int max_packets, long long max_bytes)
+{
+    if (!ds) {
+        if (halfrate != 0 && halfrate != 1) g_vbm_err = "halfrate must be 0 or 1";
+        return VBM_EINVAL;
+    }
+    return live_create(st, nullptr, ds, halfrate, false, nstreams, max_packets, max_bytes);
+}
+
+extern "C" int vbm_live_store_append(vbm_range_store *st, int n, const int *stream_ids, const int *run_packets,
+                                     const uint8_t *d_data, const long long *d_offsets, long long data_bytes,
+                                     const long long *d_granulepos, const uint8_t *d_eos, const uint8_t *d_gap,
+                                     int *status, int *dropped, int *retained, void *stream)
+{
+    const char *who = "vbm_live_store_append";
+    long long P = 0;
+    int rc = live_append_args(st, false, n, stream_ids, run_packets, d_data, d_offsets, data_bytes, &P, who);
+    if (rc || n == 0) return rc;
+    vbm_live *lv = st->live;
+    vbm_decoder *d = st->dec;
+    hipStream_t q = (hipStream_t)stream;
+    if ((rc = live_room(lv, st->S, (size_t)P))) return rc;
+    hipError_t e = hipEventSynchronize(lv->ev_tab);         // the last copy out of the table is done
+    if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_live_store_append: hipEventSynchronize");
+    live_table(st, n, stream_ids, run_packets, lv->h_tab);
+    const bool mixed = !st->cls.empty();
+    const int ids_at = mixed ? 2 * n + 1 : n + 1;
+    e = hipMemcpyAsync(lv->d_tab, lv->h_tab, (size_t)(ids_at + n) * sizeof(int), hipMemcpyHostToDevice, q);
+    if (e == hipSuccess) e = hipEventRecord(lv->ev_tab, q);
+    if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_live_store_append: upload");
+    int *d_head_status = lv->d_head, *d_head_W = lv->d_head + lv->pk_cap;
+    vbml_back *d_back = (vbml_back *)lv->d_back;
+    long long *d_pk_out_end = (long long *)(d_back + n);
+    int *d_pk_status = (int *)(d_pk_out_end + P);
+    const vbmd_setup *s = (const vbmd_setup *)d->d_setup;
+    if (mixed ? vbmd_launch_index_head_mixed(d->d_table, n, lv->d_tab, 0, P, d_data, d_offsets, data_bytes, d_head_status,
+                                             d_head_W, q)
+              : vbmd_launch_index_head(s, P, d_data, d_offsets, data_bytes, d_head_status, d_head_W, q))
+        return VBM_EHIP;
+    if (vbml_launch_append(lv->A, st->halfrate, s, mixed ? d->d_table : nullptr, n, lv->d_tab, ids_at, d_data, d_offsets,
+                           data_bytes, d_head_status, d_head_W, d_granulepos, d_eos, d_gap, lv->d_plans, lv->d_trimmed,
+                           d_pk_status, d_pk_out_end, d_back, q))
+        return VBM_EHIP;
+    const size_t back_bytes = (size_t)n * sizeof(vbml_back) + (size_t)P * 12;
+    e = hipMemcpyAsync(lv->h_back, lv->d_back, back_bytes, hipMemcpyDeviceToHost, q);
+    if (e == hipSuccess) e = hipStreamSynchronize(q);       // the one wait: the caller's arrays are free after it
+    if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_live_store_append: read-back");
+    const vbml_back *back = (const vbml_back *)lv->h_back;
+    const long long *pk_out_end = (const long long *)(back + n);
+    live_commit(st, n, stream_ids, lv->h_tab, back, pk_out_end, (const int *)(pk_out_end + P), status, dropped, retained);
+    return VBM_OK;
+}
+
+extern "C" int vbm_host_live_store_append(vbm_range_store *st, int n, const int *stream_ids, const int *run_packets,
+                                          const uint8_t *data, const long long *offsets, long long data_bytes,
+                                          const long long *granulepos, const uint8_t *eos, const uint8_t *gap,
+                                          int *status, int *dropped, int *retained)
+{
+    const char *who = "vbm_host_live_store_append";
+    long long P = 0;
+    int rc = live_append_args(st, true, n, stream_ids, run_packets, data, offsets, data_bytes, &P, who);
+    if (rc) return rc;
+    bool csr = offsets[0] >= 0 && offsets[P] <= data_bytes;             // the host can see the offsets: all, at once
+    for (long long k = 0; k < P && csr; k++) csr = offsets[k + 1] >= offsets[k];
+    if (!csr) { g_vbm_err = std::string(who) + ": the offsets are no CSR inside data"; return VBM_EINVAL; }
+    if (n == 0) return VBM_OK;
+    vbm_live *lv = st->live;
+    if ((rc = live_room(lv, st->S, (size_t)P))) return rc;
+    std::vector<int> tab(3 * (size_t)n + 1);
+    live_table(st, n, stream_ids, run_packets, tab.data());
+    vbml_back *back = (vbml_back *)lv->twin_mem.data();
+    long long *pk_out_end = (long long *)(back + n);
+    int *pk_status = (int *)(pk_out_end + P);
+    int *head_status = (int *)(lv->twin_mem.data() + (size_t)st->S * sizeof(vbml_back) + lv->pk_cap * 12);
+    int *head_W = head_status + lv->pk_cap;
+    for (long long k = 0; k < P; k++) head_status[k] = vbmi_head(lv->hs, data, offsets, data_bytes, k, head_W[k]);
+    for (int e = 0; e < n; e++) {
+        const auto entry = st->halfrate ? vbml_host_append_entry<1> : vbml_host_append_entry<0>;
+        entry(lv->A, lv->hs.blocksizes, stream_ids[e], tab[e], tab[e + 1], data, offsets, data_bytes, head_status, head_W,
+              granulepos, eos, gap, pk_status, pk_out_end, back[e]);
+    }
+    live_commit(st, n, stream_ids, tab.data(), back, pk_out_end, pk_status, status, dropped, retained);
+    return VBM_OK;
+}
+
+namespace {
+
+// both restarts: the slots fresh, in a mixed store of the classes given
+int live_restart(vbm_range_store *st, bool host, int n, const int *ids, const int *classes, hipStream_t q, const char *who)
+{
+    int rc = live_check(st, host, n, ids, who);
+    if (rc) return rc;
+    vbm_live *lv = st->live;
+    const bool mixed = !st->cls.empty();
+    if (mixed != (classes != nullptr) && n > 0) {
+        g_vbm_err = std::string(who) + (mixed ? ": a store of a mixed decoder needs the slots' classes"
+                                              : ": classes need a store of a mixed decoder");
+        return VBM_EINVAL;
+    }
+    for (int e = 0; mixed && e < n; e++)
+        if (classes[e] < 0 || classes[e] >= (int)st->dec->classes.size()) {
+            g_vbm_err = std::string(who) + ": class id " + std::to_string(classes[e]) + " is not in the decoder's table";
+            return VBM_EINVAL;
+        }
+    if (n == 0) return VBM_OK;
+    if (host) {
+        for (int e = 0; e < n; e++) lv->A.slots[ids[e]] = vbml_fresh(0);
+    } else {
+        hipError_t e = hipEventSynchronize(lv->ev_tab);
+        if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_live_store_restart: hipEventSynchronize");
+        memcpy(lv->h_tab, ids, (size_t)n * sizeof(int));
+        if (mixed) memcpy(lv->h_tab + n, classes, (size_t)n * sizeof(int));
+        e = hipMemcpyAsync(lv->d_tab, lv->h_tab, (size_t)(mixed ? 2 : 1) * n * sizeof(int), hipMemcpyHostToDevice, q);
+        if (e == hipSuccess) e = hipEventRecord(lv->ev_tab, q);
+        if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_live_store_restart: upload");
+        if (vbml_launch_restart(lv->A, n, lv->d_tab, mixed ? lv->d_tab + n : nullptr, q)) return VBM_EHIP;
+    }
+    for (int e = 0; e < n; e++) {
+        const int sid = ids[e];
+        lv->last[sid] = st->first[sid];
+        lv->lo[sid] = lv->bytes[sid] = st->totals[sid] = 0;
+        if (mixed) st->cls[sid] = classes[e];
+    }
+    return VBM_OK;
+}
+
+}  // namespace
+
+extern "C" int vbm_live_store_restart(vbm_range_store *st, int n, const int *stream_ids, const int *classes, void *stream)
+{
+    return live_restart(st, false, n, stream_ids, classes, (hipStream_t)stream, "vbm_live_store_restart");
+}
+
+extern "C" int vbm_host_live_store_restart(vbm_range_store *st, int n, const int *stream_ids)
+{
+    return live_restart(st, true, n, stream_ids, nullptr, nullptr, "vbm_host_live_store_restart");
+}
+
+extern "C" int vbm_live_store_state(const vbm_range_store *st, long long *first_sample, long long *totals,
+                                    long long *packets, long long *bytes, long long *trims)
+{
+    if (!st || !st->live) { g_vbm_err = "vbm_live_store_state: needs a live store"; return VBM_EINVAL; }
+    const vbm_live *lv = st->live;
+    for (int i = 0; i < st->S; i++) {
+        if (first_sample) first_sample[i] = lv->lo[i];
+        if (totals) totals[i] = st->totals[i];
+        if (packets) packets[i] = lv->last[i] - st->first[i];
+        if (bytes) bytes[i] = lv->bytes[i];
+    }
+    if (trims) trims[0] = lv->trims[0], trims[1] = lv->trims[1];
+    return VBM_OK;
+}
+
+extern "C" int vbm_host_live_store_state(const vbm_range_store *st, long long *first_sample, long long *totals,
+                                         long long *packets, long long *bytes, long long *trims)
+{
+    return vbm_live_store_state(st, first_sample, totals, packets, bytes, trims);
+}
+
+namespace {
+
+// Both snapshots.  The index of the retained packets is the host mirror's; begin, the offsets and the bytes come out of
+// the regions, stream after stream (device form: behind a wait for `q`, one blocking copy per array and stream).
+int live_snapshot(const vbm_range_store *st, bool host, long long *first, int *status, int *begin, long long *out_end,
+                  long long *totals, uint8_t *data, long long *offsets, hipStream_t q, const char *who)
+{
+    if (!st || !st->live || st->live->host != host) {
+        g_vbm_err = std::string(who) + (host ? ": needs a store of vbm_host_live_store_create"
+                                             : ": needs a store of vbm_live_store_create");
+        return VBM_EINVAL;
+    }
+    if (!first || !totals || !offsets) return VBM_EINVAL;
+    const vbm_live *lv = st->live;
+    const vbml_arrays &A = lv->A;
+    if (!host) {
+        const hipError_t e = hipStreamSynchronize(q);
+        if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_live_store_snapshot: hipStreamSynchronize");
+    }
+    auto fetch = [&](void *dst, const void *src, size_t bytes) {
+        if (!bytes) return hipSuccess;
+        if (host) { memcpy(dst, src, bytes); return hipSuccess; }
+        return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+    };
+    long long at = 0, byte = 0;
+    std::vector<long long> off;
+    first[0] = 0;
+    offsets[0] = 0;
+    for (int i = 0; i < st->S; i++) {
+        const long long P0 = st->first[i], n = lv->last[i] - P0, nb = lv->bytes[i];
+        if (n > 0 && (!status || !begin || !out_end)) return VBM_EINVAL;
+        if (nb > 0 && !data) return VBM_EINVAL;
+        off.resize((size_t)n + 1);
+        hipError_t e = fetch(off.data(), A.offsets + P0, ((size_t)n + 1) * sizeof(long long));
+        if (e == hipSuccess) e = fetch(begin + at, A.begin + P0, (size_t)n * sizeof(int));
+        if (e == hipSuccess) e = fetch(data + byte, A.data + (long long)i * A.stride, (size_t)nb);
+        if (e != hipSuccess) return vbm_set_hip_error(e, "vbm_live_store_snapshot: copy");
+        for (long long k = 0; k < n; k++) {
+            status[at + k] = st->status[P0 + k];
+            out_end[at + k] = st->out_end[P0 + k];
+            offsets[at + k + 1] = byte + (off[k + 1] - off[0]);
+        }
+        totals[i] = st->totals[i];
+        at += n;
+        byte += nb;
+        first[i + 1] = at;
+    }
+    return VBM_OK;
+}
+
+}  // namespace
+
+extern "C" int vbm_live_store_snapshot(const vbm_range_store *st, long long *first, int *status, int *begin,
+                                       long long *out_end, long long *totals, uint8_t *data, long long *offsets,
+                                       void *stream)
+{
+    return live_snapshot(st, false, first, status, begin, out_end, totals, data, offsets, (hipStream_t)stream,
+                         "vbm_live_store_snapshot");
+}
+
+extern "C" int vbm_host_live_store_snapshot(const vbm_range_store *st, long long *first, int *status, int *begin,
+                                            long long *out_end, long long *totals, uint8_t *data, long long *offsets)
+{
+    return live_snapshot(st, true, first, status, begin, out_end, totals, data, offsets, nullptr,
+                         "vbm_host_live_store_snapshot");
 }

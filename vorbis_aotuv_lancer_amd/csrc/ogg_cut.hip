@@ -205,6 +205,7 @@ struct CutIndex {                        // what the search reads, of a store or
     const long long *first;
     const int *status;
     const long long *out_end, *totals;
+    const long long *last, *lo;          // a live store's ends of streams and first retained samples, else null
 };
 
 int create(vbm_ogg_cutter **out, int max_ranges, long long max_out_bytes, long long max_header_bytes, bool host)
@@ -285,10 +286,11 @@ int prepare(const vbm_ogg_cutter *m, bool host, const CutIndex &ix, int nranges,
         rg.s = starts[r];
         const long long left = ix.totals[i] - rg.s;
         rg.got = left < 0 ? 0 : left < lengths[r] ? left : lengths[r];
+        if (ix.lo && rg.s < ix.lo[i]) rg.got = 0;           // a live store has dropped the window's start
         rg.serialno = serialnos ? serialnos[r] : r;
         if (rg.got > 0) {
             const long long a = ix.first[i];
-            if (!vbm_range_find(a, ix.first[i + 1], ix.status, ix.out_end, rg.s, rg.got, rg.k, rg.m, rg.pre))
+            if (!vbm_range_find(a, ix.last ? ix.last[i] : ix.first[i + 1], ix.status, ix.out_end, rg.s, rg.got, rg.k, rg.m, rg.pre))
                 return fail(VBM_EINVAL, who + ": range store index: no pre-roll packet");
             if (rg.k == rg.m) {                             // the start cannot be trimmed as well as the end
                 const long long s0 = rg.k > a ? ix.out_end[rg.k - 1] : 0;
@@ -338,6 +340,7 @@ extern "C" int vbm_ogg_cut_ranges(vbm_ogg_cutter *m, const vbm_range_store *stor
     if (!m || !store) return fail(VBM_EINVAL, "vbm_ogg_cut_ranges: null cutter or store");
     vbm_range_store_view v;
     vbm_range_store_get_view(store, &v);
+    if (v.host) return fail(VBM_EINVAL, "vbm_ogg_cut_ranges: a host store (vbm_host_live_store_create) in a device call");
     if (v.halfrate) return fail(VBM_EINVAL, "vbm_ogg_cut_ranges: a half-rate store's positions are not packet granule positions");
     if (out_cap > 0 && d_out && v.data_bytes > 0 && (uintptr_t)d_out < (uintptr_t)(v.d_data + v.data_bytes) &&
         (uintptr_t)v.d_data < (uintptr_t)(d_out + out_cap))
@@ -350,7 +353,7 @@ extern "C" int vbm_ogg_cut_ranges(vbm_ogg_cutter *m, const vbm_range_store *stor
         if (rc) return rc;
     }
     OggCutRange *recs = (OggCutRange *)slot;
-    const CutIndex ix = {v.S, v.first, v.status, v.out_end, v.totals};
+    const CutIndex ix = {v.S, v.first, v.status, v.out_end, v.totals, v.last, v.lo};
     int rc = prepare(m, false, ix, nranges, stream_ids, starts, lengths, serialnos, nheaders, header_pages, header_offsets,
                      header_ids, d_out, out_cap,
                      d_out_offsets, d_status, got_starts, got_lengths, recs, who);
@@ -399,7 +402,7 @@ extern "C" int vbm_host_ogg_cut_ranges(vbm_ogg_cutter *m, int nstreams, const lo
         (uintptr_t)data < (uintptr_t)(out + out_cap))
         return fail(VBM_EINVAL, "vbm_host_ogg_cut_ranges: the output overlaps the store");
     m->recs.resize((size_t)(nranges > 0 && nranges <= m->max_ranges ? nranges : 0));
-    const CutIndex ix = {nstreams, first, status, out_end, totals};
+    const CutIndex ix = {nstreams, first, status, out_end, totals, nullptr, nullptr};
     int rc = prepare(m, true, ix, nranges, stream_ids, starts, lengths, serialnos, nheaders, header_pages, header_offsets,
                      header_ids, out, out_cap,
                      out_offsets, out_status, got_starts, got_lengths, m->recs.data(), who);

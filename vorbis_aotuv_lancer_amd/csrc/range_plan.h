@@ -33,9 +33,12 @@ inline bool vbm_range_find(long long a, long long b, const int *status, const lo
 // with output past s) .. m (holds s + got - 1) after the pre-roll p (the last valid packet before k), cut into pieces
 // of at most cap rows (cap >= 2); pieces packed into sub-calls of at most cap rows and cap output rows.
 // -> nullptr, or the error of an index that no decode gives, with an empty plan
-inline const char *vbm_plan_ranges(const long long *first, const int *status, const long long *out_end,
-                                   const long long *totals, int cap, int nranges, const int *stream_ids,
-                                   const long long *starts, const int *lengths, int *got, vbm_range_plan *plan)
+// last, lo (a live store's; live_store.h): stream i's packets end at last[i] instead of first[i + 1], and a range that
+// starts before lo[i], the stream's first retained sample, gets nothing.
+inline const char *vbm_plan_ranges(const long long *first, const long long *last, const long long *lo, const int *status,
+                                   const long long *out_end, const long long *totals, int cap, int nranges,
+                                   const int *stream_ids, const long long *starts, const int *lengths, int *got,
+                                   vbm_range_plan *plan)
 {
     *plan = {{}, {0}, {}};
     std::vector<vbm_range_piece> &pieces = plan->pieces;
@@ -45,9 +48,10 @@ inline const char *vbm_plan_ranges(const long long *first, const int *status, co
         const int i = stream_ids[r];
         const long long total = totals[i], s = starts[r];
         got[r] = (int)std::max(0LL, std::min(total - s, (long long)lengths[r]));
+        if (lo && s < lo[i]) got[r] = 0;
         if (got[r] == 0) continue;
         int k, m, pre;
-        if (!vbm_range_find(first[i], first[i + 1], status, out_end, s, got[r], k, m, pre)) {   // lW >= 0 at k
+        if (!vbm_range_find(first[i], last[i], status, out_end, s, got[r], k, m, pre)) {   // lW >= 0 at k
             *plan = {};
             return "range store index: no pre-roll packet";
         }
@@ -67,5 +71,14 @@ inline const char *vbm_plan_ranges(const long long *first, const int *status, co
     }
     call_first.push_back((int)pieces.size());
     return nullptr;
+}
+
+// the plan over a plain store, whose streams lie back to back
+inline const char *vbm_plan_ranges(const long long *first, const int *status, const long long *out_end,
+                                   const long long *totals, int cap, int nranges, const int *stream_ids,
+                                   const long long *starts, const int *lengths, int *got, vbm_range_plan *plan)
+{
+    return vbm_plan_ranges(first, first + 1, nullptr, status, out_end, totals, cap, nranges, stream_ids, starts, lengths,
+                           got, plan);
 }
 }  // namespace

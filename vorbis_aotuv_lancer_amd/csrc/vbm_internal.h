@@ -25,6 +25,10 @@ struct vbm_range_store_view {          // a range store's index and device array
     int S, halfrate;
     long long packets, data_bytes;
     const long long *first, *out_end, *totals;   // host: [S + 1], [P], [S]
+    const long long *last;                       // host: [S] the end of each stream's packets: first + 1, or a live
+                                                 // store's, whose streams do not end where the next begins
+    const long long *lo;                         // host: [S] a live store's first retained samples, else null
+    int host;                                    // a host twin's store (vbm_host_live_store_create): no device array
     const int *status;                           // host: [P]
     const uint8_t *d_data;
     const long long *d_offsets, *d_out_start;    // device: [P + 1], [P]

@@ -532,6 +532,130 @@ class RangeStore(_Handle):
         return self
 
 
+LIVE_EBIG = -1004
+
+
+class LiveAppend:
+    """What LiveRangeStore.append did, per entry: status (0, LIVE_EBIG: the run is larger than a capacity and the slot
+    was left as it was, or VBM_EINVAL -131: its offsets are no CSR), dropped (packets that left the slot's front) and
+    retained (packets the slot holds now), int32 numpy arrays"""
+
+    def __init__(self, status, dropped, retained):
+        self.status, self.dropped, self.retained = status, dropped, retained
+
+
+class LiveRangeStore(RangeStore):
+    """A time-shift buffer (vbm_live_store_*; csrc/live_store.h): a RangeStore with a fixed region per stream, max_packets
+    packet slots and max_bytes payload bytes in device memory, that takes appended runs of packets and drops the oldest
+    when a region is full.  Decoder.synthesis_ranges, MixedDecoder.synthesis_ranges and OggCutter.cut take it as they
+    take a RangeStore.  Positions are output samples since the slot's last restart at the decoder's rate: the
+    concatenation of what synthesis_runs returns for the same packets, granulepos, eos and gap in the same order.
+    .totals [nstreams] is its end and .first_sample [nstreams] the first sample a window may start at (out_end of the
+    first retained valid packet, which is only pre-roll); a window that starts earlier gets got = 0, a cut an empty file.
+    decoder_or_setup: a Decoder or MixedDecoder; or, with host=True, a DecodeSetup: the CPU twin over numpy arrays, which
+    needs no device (halfrate is then the twin's own; a device store has its decoder's).  A store of a MixedDecoder gives
+    every slot its class with restart(ids, classes).  Calls on one store are ordered by the caller on one stream."""
+
+    def __init__(self, decoder_or_setup, nstreams, max_packets, max_bytes, host=False, halfrate=False):
+        self.host = bool(host)
+        self.nstreams, self.max_packets, self.max_bytes = int(nstreams), int(max_packets), int(max_bytes)
+        self._h = C.c_void_p()
+        if self.host:
+            self.decoder, self.halfrate, self.classes = None, bool(halfrate), None
+            check(lib.vbm_host_live_store_create(C.byref(self._h), decoder_or_setup._h, int(self.halfrate), self.nstreams,
+                                                 self.max_packets, self.max_bytes), "vbm_host_live_store_create")
+        else:
+            self.decoder, self.halfrate = decoder_or_setup, decoder_or_setup.halfrate
+            mixed = isinstance(decoder_or_setup, MixedDecoder)
+            self.classes = np.full(self.nstreams, -1, np.int32) if mixed else None
+            create = "vbm_live_store_create_mixed" if mixed else "vbm_live_store_create"
+            check(getattr(lib, create)(C.byref(self._h), decoder_or_setup._h, self.nstreams, self.max_packets,
+                                       self.max_bytes), create)
+        self._pre = "vbm_host_live_store_" if self.host else "vbm_live_store_"
+        self._refresh()
+
+    def _q(self):
+        return () if self.host else (self.decoder._stream(),)
+
+    def _refresh(self):
+        """.first_sample, .totals, .packets, .bytes, .stats from the store's host mirror"""
+        S = self.nstreams
+        self.first_sample, self.totals = np.zeros(S, np.int64), np.zeros(S, np.int64)
+        self.packets, self.bytes = np.zeros(S, np.int64), np.zeros(S, np.int64)
+        trims = np.zeros(2, np.int64)
+        check(getattr(lib, self._pre + "state")(self._h, self.first_sample.ctypes.data, self.totals.ctypes.data,
+                                                self.packets.ctypes.data, self.bytes.ctypes.data, trims.ctypes.data),
+              self._pre + "state")
+        self.stats = {"trims_by_packets": int(trims[0]), "trims_by_bytes": int(trims[1])}
+
+    def append(self, ids, counts, data, offsets, granulepos=None, eos=None, gap=None):
+        """synthesis_runs' arguments: entry e is counts[e] consecutive packets for slot ids[e] (host ints, ids distinct,
+        zero counts allowed), data uint8 [bytes] and offsets int64 [P + 1] one CSR over the packets of all entries in list
+        order, granulepos int64 [P] / eos uint8 [P] / gap uint8 [P] or None: CUDA tensors (numpy arrays with host=True).
+        The index goes on from each slot's carried state, so how a stream is split over appends does not show.  A run
+        that does not fit makes its slot drop, from the front, the fewest packets such that what remains is at most half
+        of each capacity and leaves room for the run.  Waits for the device once; the tensors are free when it returns.
+        -> LiveAppend"""
+        ids, cnt = _i32(ids), _i32(counts)
+        if ids.shape != cnt.shape or ids.ndim != 1:
+            raise ValueError("ids and counts must be 1-D and of the same length")
+        n, P = len(ids), int(cnt.clip(min=0).sum())
+        if self.host:
+            data, offsets, _, gp, eo = _csr_np(data, offsets, granulepos, eos)
+            gap = None if gap is None else np.ascontiguousarray(np.asarray(gap, dtype=np.uint8))
+            nbytes = len(data)
+        else:
+            assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
+            offsets = offsets.to(torch.int64).contiguous()
+            gp, eo = _per_packet(granulepos, eos)
+            gap = None if gap is None else gap.to(torch.uint8).contiguous()
+            nbytes = data.numel()
+        size = (lambda a: a.numel()) if not self.host else len
+        if size(offsets) != P + 1:
+            raise ValueError(f"offsets must have sum(counts) + 1 = {P + 1} entries, has {size(offsets)}")
+        for a in (gp, eo, gap):
+            if a is not None and size(a) != P:
+                raise ValueError("granulepos, eos and gap need one entry per packet")
+        status, dropped, retained = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        check(getattr(lib, self._pre + "append")(self._h, n, ids.ctypes.data, cnt.ctypes.data, _ptr(data, nbytes),
+                                                 _ptr(offsets), nbytes, _ptr(gp), _ptr(eo), _ptr(gap),
+                                                 status.ctypes.data, dropped.ctypes.data, retained.ctypes.data,
+                                                 *self._q()), self._pre + "append")
+        self._refresh()
+        return LiveAppend(status, dropped, retained)
+
+    def restart(self, ids, classes=None):
+        """The slots ids (distinct) are empty and fresh: positions start over at 0.  classes: with a store of a
+        MixedDecoder, the class of each from here to its next restart (required); else an error.  Only enqueues."""
+        ids = _i32(ids)
+        if self.host:
+            if classes is not None:
+                raise ValueError("the host twin has one setup: no classes")
+            check(lib.vbm_host_live_store_restart(self._h, len(ids), ids.ctypes.data), "vbm_host_live_store_restart")
+        else:
+            cls = None if classes is None else _i32(classes)
+            if cls is not None and cls.shape != ids.shape:
+                raise ValueError("classes needs one class id per slot")
+            check(lib.vbm_live_store_restart(self._h, len(ids), ids.ctypes.data, _ptr(cls), *self._q()),
+                  "vbm_live_store_restart")
+            if cls is not None and self.classes is not None:
+                self.classes[ids] = cls
+        self._refresh()
+
+    def snapshot(self):
+        """The retained packets of all streams as a compact index and CSR in numpy arrays, the tuple
+        OggCutter(host=True).cut takes: (first int64 [S + 1], status int32 [P], begin int32 [P], out_end int64 [P],
+        totals int64 [S], data uint8, offsets int64 [P + 1]); positions stay absolute.  Waits for the device."""
+        S, P, B = self.nstreams, int(self.packets.sum()), int(self.bytes.sum())
+        first, totals, offsets = np.zeros(S + 1, np.int64), np.zeros(S, np.int64), np.zeros(P + 1, np.int64)
+        status, begin, out_end = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int64)
+        data = np.zeros(B, np.uint8)
+        check(getattr(lib, self._pre + "snapshot")(self._h, first.ctypes.data, _ptr(status, P), _ptr(begin, P),
+                                                   _ptr(out_end, P), totals.ctypes.data, _ptr(data, B),
+                                                   offsets.ctypes.data, *self._q()), self._pre + "snapshot")
+        return first, status, begin, out_end, totals, data, offsets
+
+
 def _demux_host(name, blob):
     """demux_ogg of one file or link, its errors under the entry's name"""
     from .stream import demux_ogg
