@@ -491,6 +491,60 @@ int vbm_ogg_chain_status(vbm_ogg_chain *ch, int *status, void *stream);
 int vbm_host_ogg_chain_split(vbm_ogg_chain *ch, int nfiles, const uint8_t *data, const long long *file_offsets,
                              long long *file_links, long long *link_offsets, long long link_cap);
 
+/* ---- Tolerant Ogg demux: many whole files that may be damaged, chained or both, on the device ------------------------
+ * Every call above is strict: one violated page rule gives the file or link VBM_EOGG.  A resync demux delivers what
+ * rules 1 to 4 and 6 of the resync feed ("Resync mode" below) deliver from each file pushed whole with `end`; rule 5 (stops)
+ * and the slot capacities do not exist here.  Per file, from its first byte: the walk goes to the next "OggS" (a version
+ * byte other than 0 moves it on one byte); a candidate whose 27 header bytes, lacing table or body do not all lie in
+ * the file ends the file there; a whole candidate with a bad CRC moves the walk on one byte, one with a good CRC by its
+ * size, so a capture pattern inside a good page is never looked at.  Rules 2 to 4 (whose page, discontinuity, link
+ * start) apply to the good pages unchanged.  The ENTRIES of the batch are the links whose three header packets
+ * completed, in order: file f has entries d_file_links[f] .. d_file_links[f+1] - 1, possibly none, and an entry's status
+ * is always 0.  A gap mark (1) is on the first audio packet of every link but the file's first and on the first packet
+ * completed behind every discontinuity.
+ *   vbm_ogg_resync_create   workspace on the current device for calls of up to max_files files that span up to
+ *                           max_bytes bytes and hold up to max_candidates capture patterns: about 248 * max_candidates
+ *                           + max_bytes / 1024 + 56 * max_files bytes (csrc/ogg_resync.h).  Patterns cannot overlap, so
+ *                           max_bytes / 4 always suffices; real files have about one per 4 KB.
+ *                           vbm_host_ogg_resync_create: the same in host memory, touches no device.
+ *   vbm_ogg_resync_scan     d_events [nfiles]: per file, beginning-of-stream pages taken, those whose link is no entry,
+ *                           gap marks set, bytes skipped, good pages ignored, pages taken.  d_file_links [nfiles + 1].
+ *                           d_info, of capacity entry_cap: per entry a vbm_ogg_file_info as vbm_ogg_demux_scan gives it.
+ *                           d_totals [6]: entries, audio packets, payload bytes, header bytes, candidates found, and
+ *                           the scan's status: 0, or VBM_OGG_DEMUX_ECAP when the candidates exceed max_candidates (then
+ *                           only d_totals[4] and [5] are written) or the entries exceed entry_cap (then d_info is not
+ *                           written; everything else is).  The counts are exact: a second try with them succeeds.  All
+ *                           four are device memory; file_offsets is host memory and is free on return.
+ *   vbm_ogg_resync_fill     as vbm_ogg_demux_fill over the entries, with one more output d_gap [packet_cap].  After a
+ *                           scan that ended in VBM_OGG_DEMUX_ECAP, or with a capacity below the batch's total, NOTHING
+ *                           is written and the status word becomes VBM_OGG_DEMUX_ECAP.
+ *   vbm_ogg_resync_status   the status word of the last scan or fill -> *status (host memory); waits for `stream`.
+ * scan and fill allocate nothing and only enqueue on `stream`; VBM_EINVAL, with nothing enqueued, as for
+ * vbm_ogg_demux_scan / _fill, and for a negative entry_cap or max_candidates.  A crafted file of nested false headers
+ * makes the CRC work quadratic in its size, as it does for the reference's sequential page seek.
+ *   vbm_host_ogg_resync_scan / _fill   the same source on the CPU with host pointers and a host object. */
+typedef struct {
+    int links_started, links_bad;
+    long long gaps, skipped_bytes, ignored_pages, pages;
+} vbm_ogg_resync_events;
+typedef struct vbm_ogg_resync vbm_ogg_resync;
+int vbm_ogg_resync_create(vbm_ogg_resync **rs, int max_files, long long max_bytes, long long max_candidates);
+int vbm_host_ogg_resync_create(vbm_ogg_resync **rs, int max_files, long long max_bytes, long long max_candidates);
+void vbm_ogg_resync_destroy(vbm_ogg_resync *rs);
+int vbm_ogg_resync_scan(vbm_ogg_resync *rs, int nfiles, const uint8_t *d_data, const long long *file_offsets,
+                        vbm_ogg_resync_events *d_events, long long *d_file_links, vbm_ogg_file_info *d_info,
+                        long long entry_cap, long long *d_totals, void *stream);
+int vbm_ogg_resync_fill(vbm_ogg_resync *rs, uint8_t *d_headers, long long header_cap, uint8_t *d_payload,
+                        long long payload_cap, long long *d_offsets, long long *d_granulepos, uint8_t *d_eos,
+                        uint8_t *d_gap, long long packet_cap, void *stream);
+int vbm_ogg_resync_status(vbm_ogg_resync *rs, int *status, void *stream);
+int vbm_host_ogg_resync_scan(vbm_ogg_resync *rs, int nfiles, const uint8_t *data, const long long *file_offsets,
+                             vbm_ogg_resync_events *events, long long *file_links, vbm_ogg_file_info *info,
+                             long long entry_cap, long long *totals);
+int vbm_host_ogg_resync_fill(vbm_ogg_resync *rs, uint8_t *headers, long long header_cap, uint8_t *payload,
+                             long long payload_cap, long long *offsets, long long *granulepos, uint8_t *eos, uint8_t *gap,
+                             long long packet_cap);
+
 /* ---- Ogg stream selection: the Vorbis stream of multiplexed files, for many files per call, on the device -------------
  * A multiplexed file carries the pages of several logical streams interleaved (.ogv: Theora beside Vorbis; Skeleton,
  * Kate or CMML tracks beside the audio), and the calls above take one stream per file.  A selection copies, for each of

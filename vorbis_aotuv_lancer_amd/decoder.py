@@ -875,35 +875,42 @@ class OggIndex:
             ds.close()
 
 
-def _demux_files(files, device_demux, chained, multiplexed=False):
-    """decode_ogg's demux -> (names, entries, file_links): entry i, a file or with chained a link, is (headers, data,
-    offsets, granulepos, eos) as demux_ogg's, offsets a numpy array and the rest where the demux left them (CUDA tensors
-    or numpy arrays); file f is entries file_links[f] .. file_links[f + 1] - 1"""
-    from .stream import _read_files, demux_ogg_device, split_ogg_chain
+def _demux_files(files, device_demux, chained, multiplexed=False, resync=False):
+    """decode_ogg's demux -> (names, entries, file_links): entry i, a file or with chained or resync a link, is (headers,
+    data, offsets, granulepos, eos, gap) as demux_ogg's, offsets a numpy array and the rest where the demux left them
+    (CUDA tensors or numpy arrays), gap None without resync; file f is entries file_links[f] .. file_links[f + 1] - 1"""
+    from .stream import _read_files, demux_ogg_device, demux_ogg_resync, split_ogg_chain
     if device_demux:
-        b = demux_ogg_device(files, chained=chained, multiplexed=multiplexed)
+        b = demux_ogg_device(files, chained=chained, multiplexed=multiplexed, resync=resync)
         _raise_failed(b, b.names)
         offsets, entries = b.offsets.cpu().numpy(), []
         for i in range(len(b)):
             a, n, at = int(b.packet_base[i]), int(b.packets[i]), int(b.payload_base[i])
             entries.append((b.headers[i], b.payload[at:at + int(b.payload_bytes[i])], offsets[a:a + n + 1] - at,
-                            b.granulepos[a:a + n], b.eos[a:a + n]))
+                            b.granulepos[a:a + n], b.eos[a:a + n], b.gaps(i) if resync else None))
         return b.names, entries, b.file_links
     names, entries, file_links = [], [], [0]
+    if resync:
+        for name, blob in zip(*_read_files(files)):
+            for k, link in enumerate(demux_ogg_resync(blob)[0]):
+                names.append(f"{name} link {k}")
+                entries.append(link)
+            file_links.append(len(entries))
+        return names, entries, file_links
     for name, blob in zip(*_read_files(files)):
         if multiplexed:
             blob = _select_host(name, blob)
         links = [(f"{name} link {k}", link) for k, link in enumerate(split_ogg_chain(blob))] if chained else [(name, blob)]
         for entry, link in links:
             names.append(entry)
-            entries.append(_demux_host(entry, link))
+            entries.append(_demux_host(entry, link) + (None,))
         file_links.append(len(entries))
     return names, entries, file_links
 
 
 def _calls(src, max_packets):
-    """The synthesis_runs calls over one group's streams src[s] = (data, offsets, granulepos, eos), each yielded as
-    (ids, counts, data, offsets, granulepos, eos): its runs and their CSR"""
+    """The synthesis_runs calls over one group's streams src[s] = (data, offsets, granulepos, eos, gap), each yielded as
+    (ids, counts, data, offsets, granulepos, eos, gap): its runs and their CSR; gap is None when the streams have none"""
     pos = [0] * len(src)
     while True:
         live = [s for s in range(len(src)) if pos[s] < len(src[s][1]) - 1]
@@ -918,9 +925,11 @@ def _calls(src, max_packets):
             ids.append(s)
             counts.append(c)
             budget -= c
-        datas, offs, gps, eoss, base = [], [np.zeros(1, np.int64)], [], [], 0
+        datas, offs, gps, eoss, gaps, base = [], [np.zeros(1, np.int64)], [], [], [], 0
         for s, c in zip(ids, counts):
-            data, o, gp, eo = src[s]
+            data, o, gp, eo, ga = src[s]
+            if ga is not None:
+                gaps.append(ga[pos[s]:pos[s] + c])
             a, b = int(o[pos[s]]), int(o[pos[s] + c])
             datas.append(data[a:b])
             offs.append(o[pos[s] + 1:pos[s] + c + 1] - a + base)
@@ -928,11 +937,12 @@ def _calls(src, max_packets):
             eoss.append(eo[pos[s]:pos[s] + c])
             base += b - a
             pos[s] += c
-        yield ids, counts, torch.cat(datas), np.concatenate(offs), torch.cat(gps), torch.cat(eoss)
+        yield ids, counts, torch.cat(datas), np.concatenate(offs), torch.cat(gps), torch.cat(eoss), \
+            torch.cat(gaps) if gaps else None
 
 
 def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chained=False, multiplexed=False,
-               one_decoder=False):
+               one_decoder=False, resync=False):
     """.ogg files (bytes or paths), one logical stream each -> [(pcm float32 [channels, n] contiguous on the current
     device, rate)], one per file.  Files whose identification and setup headers are byte-equal share one DecodeSetup
     and Decoder, one stream per file; their packets go through synthesis_runs in calls of at most max_packets rows.
@@ -951,11 +961,19 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
     host without).  A file without a Vorbis stream raises VbmError saying so.
     one_decoder=True: the files and links of all header classes go through one MixedDecoder, its caps the largest
     channel count and block size among them, in calls planned over all of them together instead of group by group;
-    the result is the same, tensor for tensor."""
+    the result is the same, tensor for tensor.
+    resync=True: the files may be damaged, chained or both (stream.ResyncDemuxer with device_demux, demux_ogg_resync on
+    the host without; csrc/ogg_resync.h).  The result is one list per file of (pcm, rate), one per link that completed
+    its three headers, empty for a file that has none; nothing is VBM_EOGG.  The packets go through synthesis_runs with
+    the demux's gap marks, so behind a hole the decoder loses count as the reference's does ("out of sequence").  Whole
+    header packets that no DecodeSetup takes raise VbmError naming file and link, as without the flag.  Not built
+    together with multiplexed=True (ValueError)."""
     if max_packets <= 0:
         raise ValueError("max_packets must be positive")
+    if resync and multiplexed:
+        raise ValueError("decode_ogg: resync=True with multiplexed=True is not built")
     dev = torch.device("cuda", torch.cuda.current_device())
-    names, demuxed, file_links = _demux_files(files, device_demux, chained, multiplexed)
+    names, demuxed, file_links = _demux_files(files, device_demux, chained, multiplexed, resync)
     groups = {}
     for i, d in enumerate(demuxed):
         groups.setdefault((d[0][0], d[0][2]), []).append(i)
@@ -990,10 +1008,11 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
 
     for dec, members in jobs():
         up = lambda x: torch.as_tensor(x, device=dev)     # host-demuxed arrays go up here; demuxed on the device: as is
-        src = [(up(demuxed[j][1]), demuxed[j][2], up(demuxed[j][3]), up(demuxed[j][4])) for j in members]
-        for ids, counts, data, offsets, gp, eo in _calls(src, max_packets):
+        src = [(up(demuxed[j][1]), demuxed[j][2], up(demuxed[j][3]), up(demuxed[j][4]),
+                None if demuxed[j][5] is None else up(demuxed[j][5])) for j in members]
+        for ids, counts, data, offsets, gp, eo, ga in _calls(src, max_packets):
             pcm, run_samples, _, _ = dec.synthesis_runs(ids, counts, data, torch.from_numpy(offsets).to(dev),
-                                                        granulepos=gp, eos=eo)
+                                                        granulepos=gp, eos=eo, gap=ga)
             chans = dec.channels_of(ids) if one_decoder else [dec.channels] * len(ids)
             for r, s in enumerate(ids):
                 pieces[members[s]].append((pcm[r, :chans[r]], nlens + r))
@@ -1011,6 +1030,6 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
         out.append((torch.cat(parts, dim=1).contiguous(), rates[j]))
     for x in keep + setups:
         x.close()
-    if chained:
+    if chained or resync:
         return [out[int(file_links[f]):int(file_links[f + 1])] for f in range(len(file_links) - 1)]
     return out

@@ -388,11 +388,14 @@ class DemuxBatch:
     above) are the links of the files given, named "<file> link k": file_links int64 [given files + 1] counts them, and
     links(f) is the range of entries of given file f.  Otherwise every file is its own one entry.  From
     demux_ogg_device(multiplexed=True) select_info holds one SELECT_INFO record per given file (vbm_ogg_select_info);
-    None otherwise."""
+    None otherwise.  From a ResyncDemuxer (demux_ogg_device(resync=True)) the entries are the links that completed their
+    headers, a given file may have none, gap uint8 [P] lies beside eos (1: something was lost in front of that packet;
+    gaps(f) is entry f's slice) and events holds one RESYNC_EVENTS record per given file; both None otherwise."""
 
-    def __init__(self, names, info, headers, payload, offsets, granulepos, eos, file_links=None):
+    def __init__(self, names, info, headers, payload, offsets, granulepos, eos, file_links=None, gap=None, events=None):
         self.names, self.info, self.headers = names, info, headers
         self.select_info = None
+        self.gap, self.events = gap, events
         self.file_links = np.arange(len(names) + 1, dtype=np.int64) if file_links is None else file_links
         self.payload, self.offsets, self.granulepos, self.eos = payload, offsets, granulepos, eos
         self.status = info["status"].tolist()
@@ -410,6 +413,12 @@ class DemuxBatch:
     def links(self, f):
         """-> the entries that are the links of given file f"""
         return range(int(self.file_links[f]), int(self.file_links[f + 1]))
+
+    def gaps(self, f):
+        """-> entry f's slice of gap, beside runs(f): the marks Decoder.synthesis_runs(gap=...) takes (a ResyncDemuxer's
+        batch only)"""
+        a, n = int(self.packet_base[f]), int(self.packets[f])
+        return self.gap[a:a + n]
 
 
 class DeviceDemuxer(_TwinHandle):
@@ -536,6 +545,124 @@ def split_ogg_chain(data):
     return [raw[int(a):int(b)] for a, b in zip(lo[:-1], lo[1:])]
 
 
+RESYNC_EVENTS = np.dtype([("links_started", "<i4"), ("links_bad", "<i4"), ("gaps", "<i8"), ("skipped_bytes", "<i8"),
+                          ("ignored_pages", "<i8"), ("pages", "<i8")])       # vbm_ogg_resync_events
+
+
+class ResyncDemuxer(_TwinHandle):
+    """The tolerant demux of many whole .ogg files per call, damaged, chained or both, on the device
+    (vbm_ogg_resync_scan / _fill; the rule: csrc/ogg_resync.h): what the resync feed delivers from each file pushed whole.
+
+        rd = ResyncDemuxer(len(files), sum(map(len, files)))
+        b = rd.demux(files)                       # entries: the links that completed their headers; b.links(f) of file f
+        pcm, n, _, _ = dec.synthesis_runs([0], [b.packets[e]], b.payload, *b.runs(e), gap=b.gaps(e))
+
+    host=True runs the CPU twin on numpy arrays (no GPU needed).  max_candidates: the capture patterns the workspace has
+    room for (default max_bytes // 27 + 2 * max_files + 64); a batch with more makes the object anew with the exact
+    count and tries again, as does one with more entries than the first try had room for (2 n + 62)."""
+
+    ECAP = 1
+    # the capture search of the device form (csrc/ogg_resync.hip), in bytes from the dword that holds the buffer's first
+    # byte: a lane's windows, a wavefront's, a row of 256 lanes, a tile of four rows, and the tiles of a full grid
+    LANE, WAVE, ROW, TILE, GRID = 16, 1024, 4096, 16384, 1024 * 16384
+
+    def __init__(self, max_files, max_bytes, host=False, device=None, max_candidates=None):
+        self.max_files, self.max_bytes = int(max_files), int(max_bytes)
+        self.max_candidates = self.max_bytes // 27 + 2 * self.max_files + 64 if max_candidates is None else int(max_candidates)
+        super().__init__("resync", host, device, self.max_files, self.max_bytes, self.max_candidates)
+
+    def demux(self, files):
+        names, blobs = _read_files(files)
+        return self.demux_joined(names, *_join(blobs, self.device))
+
+    def _scan(self, n, raw, off, cap):
+        """one scan with room for cap entries -> (totals [6], file_links [n + 1], events [n], info [cap]) on the host"""
+        nl, ne = 8 * (n + 1), n * RESYNC_EVENTS.itemsize
+        size = 48 + nl + ne + cap * FILE_INFO.itemsize
+        if self.host:
+            meta = np.zeros(size, np.uint8)
+            p = meta.ctypes.data
+            check(lib.vbm_host_ogg_resync_scan(self._h, n, raw.ctypes.data if len(raw) else None, off.ctypes.data,
+                                               p + 48 + nl if n else None, p + 48, p + 48 + nl + ne if cap else None, cap,
+                                               p), "vbm_host_ogg_resync_scan")
+        else:
+            import torch
+            d_meta = torch.zeros(size, dtype=torch.uint8, device=self.device)      # info, events, links and totals: one D2H
+            p = d_meta.data_ptr()
+            check(lib.vbm_ogg_resync_scan(self._h, n, raw.data_ptr() if len(raw) else None, off.ctypes.data,
+                                          p + 48 + nl if n else None, p + 48, p + 48 + nl + ne if cap else None, cap, p,
+                                          self._q()), "vbm_ogg_resync_scan")
+            meta = d_meta.cpu().numpy()
+        return (meta[:48].view(np.int64), meta[48:48 + nl].view(np.int64).copy(),
+                meta[48 + nl:48 + nl + ne].view(RESYNC_EVENTS).copy(), meta[48 + nl + ne:].view(FILE_INFO))
+
+    def demux_joined(self, names, raw, off, entry_cap=None):
+        """demux() of files that already lie in one buffer: raw uint8 (a tensor on the device; a numpy array with
+        host=True), file i in raw[off[i]:off[i + 1]], off int64 numpy [n + 1].  entry_cap: the entries the first try has
+        room for."""
+        off = np.ascontiguousarray(off, np.int64)
+        n = len(off) - 1
+        cap = 2 * n + 62 if entry_cap is None else int(entry_cap)
+        for attempt in range(3):
+            totals, file_links, events, info = self._scan(n, raw, off, cap)
+            if int(totals[5]) == 0:
+                break
+            if int(totals[5]) != self.ECAP or attempt == 2:
+                raise VbmError(f"vbm_ogg_resync_scan: status {int(totals[5])} with room for the counts it returned")
+            if int(totals[4]) > self.max_candidates:             # the workspace is sized at create: a new object
+                self.close()
+                self.__init__(self.max_files, self.max_bytes, self.host, self.device, int(totals[4]))
+            else:
+                cap = int(totals[0])
+        E, P, B, H = (int(x) for x in totals[:4])
+        info = info[:E].copy()
+        st = C.c_int(-1)
+        if self.host:
+            hdr, gap = np.zeros(H, np.uint8), np.zeros(P, np.uint8)
+            payload, offsets, gp, eos = _csr_buffers(P, B)
+            check(lib.vbm_host_ogg_resync_fill(self._h, hdr.ctypes.data if H else None, H, payload.ctypes.data if B else None,
+                                               B, offsets.ctypes.data, gp.ctypes.data if P else None,
+                                               eos.ctypes.data if P else None, gap.ctypes.data if P else None, P),
+                  "vbm_host_ogg_resync_fill")
+            check(lib.vbm_ogg_resync_status(self._h, C.byref(st), None), "vbm_ogg_resync_status")
+            h = hdr.tobytes()
+        else:
+            import torch
+            dev, q = self.device, self._q()
+            d_hdr = torch.empty(H, dtype=torch.uint8, device=dev)
+            gap = torch.empty(P, dtype=torch.uint8, device=dev)
+            payload, offsets, gp, eos = _csr_buffers(P, B, dev)
+            check(lib.vbm_ogg_resync_fill(self._h, d_hdr.data_ptr() if H else None, H, payload.data_ptr() if B else None, B,
+                                          offsets.data_ptr(), gp.data_ptr() if P else None, eos.data_ptr() if P else None,
+                                          gap.data_ptr() if P else None, P, q), "vbm_ogg_resync_fill")
+            h = d_hdr.cpu().numpy().tobytes()              # waits for the fill: raw is free after it
+            check(lib.vbm_ogg_resync_status(self._h, C.byref(st), q), "vbm_ogg_resync_status")
+        if st.value:
+            raise VbmError(f"vbm_ogg_resync_fill: status {st.value} with buffers of the sizes the scan returned")
+        entry_names = [f"{names[f]} link {k}" for f in range(n) for k in range(int(file_links[f + 1] - file_links[f]))]
+        headers = [_split3(h, fi["header_bytes"], int(fi["header_base"])) for fi in info]
+        return DemuxBatch(entry_names, info, headers, payload, offsets, gp, eos, file_links, gap, events)
+
+
+def demux_ogg_resync(data):
+    """.ogg bytes of one file, damaged, chained or both -> (links, events), on the host (needs no GPU): every link that
+    completed its three headers as (headers [3 packets], data uint8 [bytes], offsets int64 [P + 1], granulepos int64 [P],
+    eos uint8 [P], gap uint8 [P]), audio packet k of the link in data[offsets[k]:offsets[k + 1]], and the file's
+    RESYNC_EVENTS record.  Never fails: a file with nothing to deliver gives no link."""
+    raw = bytes(data)
+    rd = ResyncDemuxer(1, len(raw), host=True)
+    try:
+        b = rd.demux([raw])
+    finally:
+        rd.close()
+    links = []
+    for e in b.links(0):
+        offs, gp, eos = b.runs(e)
+        a, z = int(offs[0]), int(offs[-1])
+        links.append((b.headers[e], b.payload[a:z].copy(), offs - a, gp.copy(), eos.copy(), b.gaps(e).copy()))
+    return links, b.events[0]
+
+
 SELECT_INFO = np.dtype([("kept_bytes", "<i8"), ("kept_pages", "<i8"), ("foreign_pages", "<i8"), ("streams", "<i4"),
                         ("foreign_streams", "<i4"), ("first_serial", "<u4"), ("reserved", "<i4")])   # vbm_ogg_select_info
 
@@ -593,7 +720,7 @@ def select_vorbis_stream(data):
     return out.tobytes()
 
 
-def demux_ogg_device(files, host=False, chained=False, multiplexed=False):
+def demux_ogg_device(files, host=False, chained=False, multiplexed=False, resync=False):
     """.ogg files (bytes or paths) -> DemuxBatch, through a DeviceDemuxer made for them (host=True: its CPU twin).
     chained=True: the files may be chained.  After the one upload a ChainSplitter finds their links, one small D2H brings
     the link offsets back, and the demuxer runs over the same buffer with the links as its files: the batch's entries
@@ -601,9 +728,20 @@ def demux_ogg_device(files, host=False, chained=False, multiplexed=False):
     multiplexed=True: the files may carry other streams beside the Vorbis one.  After the upload a StreamSelector copies
     the Vorbis pages of every file to a second device buffer, one small D2H brings the new file offsets and the records
     b.select_info (SELECT_INFO, one per given file) back, and the split and the demux run over that buffer.  A file
-    without a Vorbis stream is an empty entry, which fails as one (VBM_EOGG)."""
+    without a Vorbis stream is an empty entry, which fails as one (VBM_EOGG).
+    resync=True: the files may be damaged, chained or both, and come out through a ResyncDemuxer made for them: the
+    entries are the links that completed their headers (chained is implied), none of them fails, and the batch has gap
+    marks and events.  Not built together with multiplexed=True (ValueError)."""
+    if resync and multiplexed:
+        raise ValueError("demux_ogg_device: resync=True with multiplexed=True is not built")
     names, blobs = _read_files(files)
     nbytes = sum(len(b) for b in blobs)
+    if resync:
+        rd = ResyncDemuxer(max(1, len(blobs)), nbytes, host=host)
+        try:
+            return rd.demux_joined(names, *_join(blobs, rd.device))
+        finally:
+            rd.close()
     if not chained and not multiplexed:
         dm = DeviceDemuxer(max(1, len(blobs)), nbytes, host=host)
         try:
