@@ -58,16 +58,16 @@ class Strict:
 class Resync:
     def __init__(self, v, data, off):
         from vorbis_aotuv_lancer_amd._lib import lib, check
-        from vorbis_aotuv_lancer_amd.stream import FILE_INFO, RESYNC_EVENTS
+        from vorbis_aotuv_lancer_amd.stream import resync_meta
         self.lib, self.check, self.data, self.off, n = lib, check, data, off, len(off) - 1
         self.rd = v.ResyncDemuxer(n, int(off[-1]))
         self.cap = 2 * n + 62
-        nl, ne = 8 * (n + 1), n * RESYNC_EVENTS.itemsize
-        self.meta = torch.zeros(48 + nl + ne + self.cap * FILE_INFO.itemsize, dtype=torch.uint8, device="cuda")
-        self.at = (48 + nl, 48, 48 + nl + ne)
+        layout = resync_meta(n, self.cap)
+        self.meta = torch.zeros(layout.size, dtype=torch.uint8, device="cuda")
+        self.at = layout.ptrs(self.meta)
         self.q = self.rd._q()
         self.scan()
-        self.totals = self.meta[:48].cpu().numpy().view(np.int64).copy()
+        self.totals = layout.views(self.meta.cpu().numpy())["totals"].copy()
         assert self.totals[5] == 0
         E, P, B, H = (int(x) for x in self.totals[:4])
         self.sizes = (P, B, H)
@@ -76,9 +76,9 @@ class Resync:
                                  (P, torch.uint8))]
 
     def scan(self):
-        p = self.meta.data_ptr()
+        at = self.at
         self.check(self.lib.vbm_ogg_resync_scan(self.rd._h, len(self.off) - 1, self.data.data_ptr(), self.off.ctypes.data,
-                                                p + self.at[0], p + self.at[1], p + self.at[2], self.cap, p, self.q), "scan")
+                                                at["events"], at["links"], at["info"], self.cap, at["totals"], self.q), "scan")
 
     def fill(self):
         P, B, H = self.sizes

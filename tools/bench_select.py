@@ -70,7 +70,7 @@ def events_ms(torch, fn, reps):
 
 def plain_report(v, torch, files, plain_mb, reps):
     from vorbis_aotuv_lancer_amd._lib import lib, check
-    from vorbis_aotuv_lancer_amd.stream import SELECT_INFO
+    from vorbis_aotuv_lancer_amd.stream import select_meta
     per = sum(len(f) for f in files)
     blobs = files * max(1, int(plain_mb * 1e6 / per))
     n = len(blobs)
@@ -79,15 +79,17 @@ def plain_report(v, torch, files, plain_mb, reps):
     nbytes = int(off[-1])
     data = torch.from_numpy(np.frombuffer(b"".join(blobs), np.uint8).copy()).cuda()
     out, ref = torch.zeros_like(data), torch.zeros_like(data)
-    meta = torch.zeros(8 * (n + 1) + n * SELECT_INFO.itemsize, dtype=torch.uint8, device="cuda")
+    layout = select_meta(n)
+    meta = torch.zeros(layout.size, dtype=torch.uint8, device="cuda")
+    at = layout.ptrs(meta)
     sel = v.StreamSelector(n, nbytes)
 
     def call(cap):
-        check(lib.vbm_ogg_select(sel._h, n, data.data_ptr(), off.ctypes.data, out.data_ptr(), cap, meta.data_ptr(),
-                                 meta.data_ptr() + 8 * (n + 1), sel._q()), "vbm_ogg_select")
+        check(lib.vbm_ogg_select(sel._h, n, data.data_ptr(), off.ctypes.data, out.data_ptr(), cap, at["out_off"], at["info"],
+                                 sel._q()), "vbm_ogg_select")
 
     whole = events_ms(torch, lambda: call(nbytes), reps)
-    same = bool(torch.equal(out, data)) and np.array_equal(meta[:8 * (n + 1)].cpu().numpy().view(np.int64), off)
+    same = bool(torch.equal(out, data)) and np.array_equal(layout.views(meta.cpu().numpy())["out_off"], off)
     walk = events_ms(torch, lambda: call(0), reps)
     copy = events_ms(torch, lambda: ref.copy_(data), reps)
     sel.close()
@@ -108,13 +110,13 @@ def wall(torch, fn):
 
 
 def muxed_report(v, torch, files, muxed, reps, baseline_only):
-    from vorbis_aotuv_lancer_amd.stream import _join
-    dev = torch.device("cuda", torch.cuda.current_device())
+    from vorbis_aotuv_lancer_amd._twin import Mem
+    mem = Mem(torch.device("cuda", torch.cuda.current_device()))
     ways = {"vorbis_only": lambda: v.demux_ogg_device(files)}
     if not baseline_only:
         ways["multiplexed"] = lambda: v.demux_ogg_device(muxed, multiplexed=True)
         ways["host_select_then_upload"] = lambda: v.demux_ogg_device([v.select_vorbis_stream(m) for m in muxed])
-        ways["upload_alone"] = lambda: _join(muxed, dev)       # what multiplexed=True spends before its first kernel
+        ways["upload_alone"] = lambda: mem.join(muxed)       # what multiplexed=True spends before its first kernel
     times, outs = {w: [] for w in ways}, {}
     for rep in range(reps + 1):                            # the first round warms up
         for w, fn in ways.items():

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, check, VbmError
+from ._twin import _Handle, _TwinHandle, ptr, size
 
 ENOTVORBIS, EBADHEADER, EVERSION, ENOTAUDIO, EBADPACKET = -132, -133, -134, -135, -136
 
@@ -49,29 +50,6 @@ def _csr_t(data, offsets, granulepos, eos, stream_packets):
     if P < 0:
         raise ValueError("offsets needs at least one entry")
     return (offsets, P, _stream_packets(stream_packets, P)) + _per_packet(granulepos, eos, P)
-
-
-def _ptr(a, when=True):
-    """The address of an optional tensor or numpy array for a C call: None for None, and when `when` is false"""
-    if a is None or not when:
-        return None
-    return a.data_ptr() if torch.is_tensor(a) else a.ctypes.data
-
-
-class _Handle:
-    """Owner of the C object ._h: close() destroys it, once, and so does collection"""
-    _destroy = None                  # the name of the entry point that destroys it
-
-    def close(self):
-        if self._h:
-            getattr(lib, self._destroy)(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DecodeSetup(_Handle):
@@ -166,7 +144,7 @@ class Decoder(_Handle):
             pcm, samples, status = out
         gp, eo = _per_packet(granulepos, eos)
         check(lib.vbm_synthesis_batch(self._h, nsb, ids.ctypes.data, packets.data_ptr(), packets.stride(0),
-                                      nbytes.data_ptr(), _ptr(gp), _ptr(eo), pcm.data_ptr(), samples.data_ptr(),
+                                      nbytes.data_ptr(), ptr(gp), ptr(eo), pcm.data_ptr(), samples.data_ptr(),
                                       status.data_ptr(), self._stream()), "vbm_synthesis_batch")
         self._last = (nsb, dev, packets, nbytes, gp, eo)     # inputs stay alive until the work has run
         return pcm, samples, status
@@ -207,7 +185,7 @@ class Decoder(_Handle):
             if gap.numel() != P:
                 raise ValueError(f"gap must have sum(counts) = {P} entries, has {gap.numel()}")
         check(lib.vbm_synthesis_runs_gaps(self._h, nruns, ids.ctypes.data, cnt.ctypes.data, data.data_ptr(),
-                                          offsets.data_ptr(), data.numel(), _ptr(gp), _ptr(eo), _ptr(gap), pcm.data_ptr(),
+                                          offsets.data_ptr(), data.numel(), ptr(gp), ptr(eo), ptr(gap), pcm.data_ptr(),
                                           pcm_stride, run_samples.data_ptr(), samples.data_ptr(), status.data_ptr(),
                                           self._stream()), "vbm_synthesis_runs_gaps")
         if P:
@@ -392,8 +370,8 @@ def decode_index(dsetup, data, offsets, granulepos=None, eos=None, halfrate=Fals
     status, samples = np.zeros(P, np.int32), np.zeros(P, np.int32)
     out_start = np.zeros(P, np.int64)
     total = C.c_longlong()
-    check(lib.vbm_decode_index_halfrate(dsetup._h, int(bool(halfrate)), P, _ptr(data, len(data)), offsets.ctypes.data,
-                                        len(data), _ptr(gp), _ptr(eo), status.ctypes.data, samples.ctypes.data,
+    check(lib.vbm_decode_index_halfrate(dsetup._h, int(bool(halfrate)), P, ptr(data, len(data)), offsets.ctypes.data,
+                                        len(data), ptr(gp), ptr(eo), status.ctypes.data, samples.ctypes.data,
                                         out_start.ctypes.data, C.byref(total)), "vbm_decode_index_halfrate")
     return status, samples, out_start, total.value
 
@@ -432,8 +410,8 @@ def decode_index_device(decoder, data, offsets, granulepos=None, eos=None, strea
     out_start = torch.empty(P, dtype=torch.int64, device=dev)
     totals = torch.empty(len(first) - 1, dtype=torch.int64, device=dev)
     name, extra = ("vbm_decode_index_device", ()) if cls is None else ("vbm_decode_index_device_mixed", (cls.ctypes.data,))
-    check(getattr(lib, name)(decoder._h, len(first) - 1, first.ctypes.data, *extra, _ptr(data, data.numel()),
-                             offsets.data_ptr(), data.numel(), _ptr(gp, P), _ptr(eo, P), status.data_ptr(),
+    check(getattr(lib, name)(decoder._h, len(first) - 1, first.ctypes.data, *extra, ptr(data, data.numel()),
+                             offsets.data_ptr(), data.numel(), ptr(gp, P), ptr(eo, P), status.data_ptr(),
                              begin.data_ptr(), end.data_ptr(), out_start.data_ptr(), totals.data_ptr(),
                              decoder._stream()), name)
     decoder._hold_index_inputs(data, offsets, gp, eo)
@@ -454,14 +432,14 @@ def decode_index_scan_host(dsetup, data, offsets, granulepos=None, eos=None, str
         cls = _stream_classes(classes, len(first) - 1)
         setups = (C.c_void_p * max(len(dsetup), 1))(*[ds._h.value for ds in dsetup])
         check(lib.vbm_host_decode_index_scan_mixed(len(dsetup), setups, int(bool(halfrate)), len(first) - 1,
-                                                   first.ctypes.data, cls.ctypes.data, _ptr(data, len(data)),
-                                                   offsets.ctypes.data, len(data), _ptr(gp), _ptr(eo),
+                                                   first.ctypes.data, cls.ctypes.data, ptr(data, len(data)),
+                                                   offsets.ctypes.data, len(data), ptr(gp), ptr(eo),
                                                    status.ctypes.data, begin.ctypes.data, end.ctypes.data,
                                                    out_start.ctypes.data, totals.ctypes.data),
               "vbm_host_decode_index_scan_mixed")
         return status, begin, end, out_start, totals
     check(lib.vbm_host_decode_index_scan(dsetup._h, int(bool(halfrate)), len(first) - 1, first.ctypes.data,
-                                         _ptr(data, len(data)), offsets.ctypes.data, len(data), _ptr(gp), _ptr(eo),
+                                         ptr(data, len(data)), offsets.ctypes.data, len(data), ptr(gp), ptr(eo),
                                          status.ctypes.data, begin.ctypes.data, end.ctypes.data, out_start.ctypes.data,
                                          totals.ctypes.data), "vbm_host_decode_index_scan")
     return status, begin, end, out_start, totals
@@ -496,7 +474,7 @@ class RangeStore(_Handle):
         gp = np.ascontiguousarray(np.concatenate(gps))
         eo = np.ascontiguousarray(np.concatenate(eoss))
         self._create(decoder, np.ascontiguousarray(np.asarray(first, np.int64)), cls, "vbm_range_store_create",
-                     _ptr(data, len(data)), offsets.ctypes.data, len(data), gp.ctypes.data, eo.ctypes.data)
+                     ptr(data, len(data)), offsets.ctypes.data, len(data), gp.ctypes.data, eo.ctypes.data)
 
     def _create(self, decoder, first, cls, create, *csr):
         """the tail of both constructors: the fields, the C store from create(..., stream_packets, *csr), or with the
@@ -527,8 +505,8 @@ class RangeStore(_Handle):
         offsets, P, first, gp, eo = _csr_t(payload, offsets, granulepos, eos, stream_packets)
         self = cls.__new__(cls)
         self._create(decoder, first, _stream_classes(classes, len(first) - 1), "vbm_range_store_create_device",
-                     _ptr(payload, payload.numel()),
-                     offsets.data_ptr(), payload.numel(), _ptr(gp, P), _ptr(eo, P), decoder._stream())
+                     ptr(payload, payload.numel()),
+                     offsets.data_ptr(), payload.numel(), ptr(gp, P), ptr(eo, P), decoder._stream())
         return self
 
 
@@ -544,7 +522,7 @@ class LiveAppend:
         self.status, self.dropped, self.retained = status, dropped, retained
 
 
-class LiveRangeStore(RangeStore):
+class LiveRangeStore(RangeStore, _TwinHandle):
     """A time-shift buffer (vbm_live_store_*; csrc/live_store.h): a RangeStore with a fixed region per stream, max_packets
     packet slots and max_bytes payload bytes in device memory, that takes appended runs of packets and drops the oldest
     when a region is full.  Decoder.synthesis_ranges, MixedDecoder.synthesis_ranges and OggCutter.cut take it as they
@@ -560,6 +538,8 @@ class LiveRangeStore(RangeStore):
         self.host = bool(host)
         self.nstreams, self.max_packets, self.max_bytes = int(nstreams), int(max_packets), int(max_bytes)
         self._h = C.c_void_p()
+        # the two forms are made from different things: the host twin from a setup and its own rate, the device form
+        # from a decoder, plain or mixed
         if self.host:
             self.decoder, self.halfrate, self.classes = None, bool(halfrate), None
             check(lib.vbm_host_live_store_create(C.byref(self._h), decoder_or_setup._h, int(self.halfrate), self.nstreams,
@@ -571,11 +551,11 @@ class LiveRangeStore(RangeStore):
             create = "vbm_live_store_create_mixed" if mixed else "vbm_live_store_create"
             check(getattr(lib, create)(C.byref(self._h), decoder_or_setup._h, self.nstreams, self.max_packets,
                                        self.max_bytes), create)
-        self._pre = "vbm_host_live_store_" if self.host else "vbm_live_store_"
         self._refresh()
 
     def _q(self):
-        return () if self.host else (self.decoder._stream(),)
+        """the decoder's stream; None for the host twin"""
+        return None if self.host else self.decoder._stream()
 
     def _refresh(self):
         """.first_sample, .totals, .packets, .bytes, .stats from the store's host mirror"""
@@ -583,9 +563,8 @@ class LiveRangeStore(RangeStore):
         self.first_sample, self.totals = np.zeros(S, np.int64), np.zeros(S, np.int64)
         self.packets, self.bytes = np.zeros(S, np.int64), np.zeros(S, np.int64)
         trims = np.zeros(2, np.int64)
-        check(getattr(lib, self._pre + "state")(self._h, self.first_sample.ctypes.data, self.totals.ctypes.data,
-                                                self.packets.ctypes.data, self.bytes.ctypes.data, trims.ctypes.data),
-              self._pre + "state")
+        self._call("live_store_state", self.first_sample.ctypes.data, self.totals.ctypes.data, self.packets.ctypes.data,
+                   self.bytes.ctypes.data, trims.ctypes.data)
         self.stats = {"trims_by_packets": int(trims[0]), "trims_by_bytes": int(trims[1])}
 
     def append(self, ids, counts, data, offsets, granulepos=None, eos=None, gap=None):
@@ -603,24 +582,19 @@ class LiveRangeStore(RangeStore):
         if self.host:
             data, offsets, _, gp, eo = _csr_np(data, offsets, granulepos, eos)
             gap = None if gap is None else np.ascontiguousarray(np.asarray(gap, dtype=np.uint8))
-            nbytes = len(data)
         else:
             assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
             offsets = offsets.to(torch.int64).contiguous()
             gp, eo = _per_packet(granulepos, eos)
             gap = None if gap is None else gap.to(torch.uint8).contiguous()
-            nbytes = data.numel()
-        size = (lambda a: a.numel()) if not self.host else len
         if size(offsets) != P + 1:
             raise ValueError(f"offsets must have sum(counts) + 1 = {P + 1} entries, has {size(offsets)}")
         for a in (gp, eo, gap):
             if a is not None and size(a) != P:
                 raise ValueError("granulepos, eos and gap need one entry per packet")
         status, dropped, retained = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
-        check(getattr(lib, self._pre + "append")(self._h, n, ids.ctypes.data, cnt.ctypes.data, _ptr(data, nbytes),
-                                                 _ptr(offsets), nbytes, _ptr(gp), _ptr(eo), _ptr(gap),
-                                                 status.ctypes.data, dropped.ctypes.data, retained.ctypes.data,
-                                                 *self._q()), self._pre + "append")
+        self._call("live_store_append", n, ids.ctypes.data, cnt.ctypes.data, ptr(data, size(data)), ptr(offsets), size(data),
+                   ptr(gp), ptr(eo), ptr(gap), status.ctypes.data, dropped.ctypes.data, retained.ctypes.data)
         self._refresh()
         return LiveAppend(status, dropped, retained)
 
@@ -628,16 +602,17 @@ class LiveRangeStore(RangeStore):
         """The slots ids (distinct) are empty and fresh: positions start over at 0.  classes: with a store of a
         MixedDecoder, the class of each from here to its next restart (required); else an error.  Only enqueues."""
         ids = _i32(ids)
+        # the two forms differ in more than the stream here: only the device form takes classes (and behind them its
+        # stream, which _call adds only behind a twin's own arguments)
         if self.host:
             if classes is not None:
                 raise ValueError("the host twin has one setup: no classes")
-            check(lib.vbm_host_live_store_restart(self._h, len(ids), ids.ctypes.data), "vbm_host_live_store_restart")
+            self._call("live_store_restart", len(ids), ids.ctypes.data)
         else:
             cls = None if classes is None else _i32(classes)
             if cls is not None and cls.shape != ids.shape:
                 raise ValueError("classes needs one class id per slot")
-            check(lib.vbm_live_store_restart(self._h, len(ids), ids.ctypes.data, _ptr(cls), *self._q()),
-                  "vbm_live_store_restart")
+            self._call("live_store_restart", len(ids), ids.ctypes.data, ptr(cls), self._q())
             if cls is not None and self.classes is not None:
                 self.classes[ids] = cls
         self._refresh()
@@ -650,17 +625,16 @@ class LiveRangeStore(RangeStore):
         first, totals, offsets = np.zeros(S + 1, np.int64), np.zeros(S, np.int64), np.zeros(P + 1, np.int64)
         status, begin, out_end = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int64)
         data = np.zeros(B, np.uint8)
-        check(getattr(lib, self._pre + "snapshot")(self._h, first.ctypes.data, _ptr(status, P), _ptr(begin, P),
-                                                   _ptr(out_end, P), totals.ctypes.data, _ptr(data, B),
-                                                   offsets.ctypes.data, *self._q()), self._pre + "snapshot")
+        self._call("live_store_snapshot", first.ctypes.data, ptr(status, P), ptr(begin, P), ptr(out_end, P),
+                   totals.ctypes.data, ptr(data, B), offsets.ctypes.data)
         return first, status, begin, out_end, totals, data, offsets
 
 
 def _demux_host(name, blob):
-    """demux_ogg of one file or link, its errors under the entry's name"""
-    from .stream import demux_ogg
+    """demux_ogg of one file or link as an Entry (no gap marks), its errors under the entry's name"""
+    from .stream import Entry, demux_ogg
     try:
-        return demux_ogg(blob)
+        return Entry(*demux_ogg(blob), None)
     except VbmError as e:
         raise VbmError(f"{name}: {e}") from None
 
@@ -744,12 +718,12 @@ class OggIndex:
         else:
             demuxed = [_demux_host(name, _select_host(name, blob) if multiplexed else blob)
                        for name, blob in zip(names, blobs)]
-        headers = b.headers if device_demux else [d[0] for d in demuxed]
+        headers = b.headers if device_demux else [d.headers for d in demuxed]
         classes = self._open_mixed(names, headers, max_batch, halfrate) if one_decoder else None
         if not one_decoder:
             self._open(headers, max_batch, halfrate)
         self.store = (RangeStore.from_device(self.decoder, b, classes=classes) if device_demux
-                      else RangeStore(self.decoder, [d[1:] for d in demuxed], classes=classes))
+                      else RangeStore(self.decoder, [(d.data, d.offsets, d.granulepos, d.eos) for d in demuxed], classes=classes))
         self.total_samples = self.store.totals
 
     def _open_mixed(self, names, headers, max_batch, halfrate):
@@ -876,18 +850,18 @@ class OggIndex:
 
 
 def _demux_files(files, device_demux, chained, multiplexed=False, resync=False):
-    """decode_ogg's demux -> (names, entries, file_links): entry i, a file or with chained or resync a link, is (headers,
-    data, offsets, granulepos, eos, gap) as demux_ogg's, offsets a numpy array and the rest where the demux left them
+    """decode_ogg's demux -> (names, entries, file_links): entry i, a file or with chained or resync a link, is a
+    stream.Entry (headers, data, offsets, granulepos, eos, gap) as demux_ogg's, offsets a numpy array and the rest where the demux left them
     (CUDA tensors or numpy arrays), gap None without resync; file f is entries file_links[f] .. file_links[f + 1] - 1"""
-    from .stream import _read_files, demux_ogg_device, demux_ogg_resync, split_ogg_chain
+    from .stream import Entry, _read_files, demux_ogg_device, demux_ogg_resync, split_ogg_chain
     if device_demux:
         b = demux_ogg_device(files, chained=chained, multiplexed=multiplexed, resync=resync)
         _raise_failed(b, b.names)
         offsets, entries = b.offsets.cpu().numpy(), []
         for i in range(len(b)):
             a, n, at = int(b.packet_base[i]), int(b.packets[i]), int(b.payload_base[i])
-            entries.append((b.headers[i], b.payload[at:at + int(b.payload_bytes[i])], offsets[a:a + n + 1] - at,
-                            b.granulepos[a:a + n], b.eos[a:a + n], b.gaps(i) if resync else None))
+            entries.append(Entry(b.headers[i], b.payload[at:at + int(b.payload_bytes[i])], offsets[a:a + n + 1] - at,
+                                 b.granulepos[a:a + n], b.eos[a:a + n], b.gaps(i) if resync else None))
         return b.names, entries, b.file_links
     names, entries, file_links = [], [], [0]
     if resync:
@@ -903,23 +877,24 @@ def _demux_files(files, device_demux, chained, multiplexed=False, resync=False):
         links = [(f"{name} link {k}", link) for k, link in enumerate(split_ogg_chain(blob))] if chained else [(name, blob)]
         for entry, link in links:
             names.append(entry)
-            entries.append(_demux_host(entry, link) + (None,))
+            entries.append(_demux_host(entry, link))
         file_links.append(len(entries))
     return names, entries, file_links
 
 
 def _calls(src, max_packets):
-    """The synthesis_runs calls over one group's streams src[s] = (data, offsets, granulepos, eos, gap), each yielded as
-    (ids, counts, data, offsets, granulepos, eos, gap): its runs and their CSR; gap is None when the streams have none"""
+    """The synthesis_runs calls over one group's streams, src[s] an entry of _demux_files (offsets on the host, the rest
+    on the device), each yielded as (ids, counts, data, offsets, granulepos, eos, gap): its runs and their CSR; gap is
+    None when the streams have none"""
     pos = [0] * len(src)
     while True:
-        live = [s for s in range(len(src)) if pos[s] < len(src[s][1]) - 1]
+        live = [s for s in range(len(src)) if pos[s] < len(src[s].offsets) - 1]
         if not live:
             return
         share, budget = max(1, max_packets // len(live)), max_packets
         ids, counts = [], []
         for s in live:                                    # the row budget in equal shares over the unfinished streams
-            c = min(len(src[s][1]) - 1 - pos[s], share, budget)
+            c = min(len(src[s].offsets) - 1 - pos[s], share, budget)
             if c <= 0:
                 break
             ids.append(s)
@@ -927,14 +902,14 @@ def _calls(src, max_packets):
             budget -= c
         datas, offs, gps, eoss, gaps, base = [], [np.zeros(1, np.int64)], [], [], [], 0
         for s, c in zip(ids, counts):
-            data, o, gp, eo, ga = src[s]
-            if ga is not None:
-                gaps.append(ga[pos[s]:pos[s] + c])
+            e, o = src[s], src[s].offsets
+            if e.gap is not None:
+                gaps.append(e.gap[pos[s]:pos[s] + c])
             a, b = int(o[pos[s]]), int(o[pos[s] + c])
-            datas.append(data[a:b])
+            datas.append(e.data[a:b])
             offs.append(o[pos[s] + 1:pos[s] + c + 1] - a + base)
-            gps.append(gp[pos[s]:pos[s] + c])
-            eoss.append(eo[pos[s]:pos[s] + c])
+            gps.append(e.granulepos[pos[s]:pos[s] + c])
+            eoss.append(e.eos[pos[s]:pos[s] + c])
             base += b - a
             pos[s] += c
         yield ids, counts, torch.cat(datas), np.concatenate(offs), torch.cat(gps), torch.cat(eoss), \
@@ -976,9 +951,9 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
     names, demuxed, file_links = _demux_files(files, device_demux, chained, multiplexed, resync)
     groups = {}
     for i, d in enumerate(demuxed):
-        groups.setdefault((d[0][0], d[0][2]), []).append(i)
+        groups.setdefault((d.headers[0], d.headers[2]), []).append(i)
     for members in groups.values():                       # every setup is checked before any work is enqueued
-        rc = DecodeSetup.status(demuxed[members[0]][0])
+        rc = DecodeSetup.status(demuxed[members[0]].headers)
         if rc:
             raise VbmError(f"{names[members[0]]}: unsupported or invalid Vorbis headers (code {rc}): "
                            f"{lib.vbm_last_error().decode()}")
@@ -990,7 +965,7 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
         """(decoder, the entries that are its streams 0, 1, ...); without one_decoder each group's setup and decoder
         are made when its turn comes"""
         if one_decoder and groups:                        # one job: every entry a stream of one mixed decoder
-            setups.extend(DecodeSetup(demuxed[members[0]][0]) for members in groups.values())
+            setups.extend(DecodeSetup(demuxed[members[0]].headers) for members in groups.values())
             md = MixedDecoder(len(demuxed), max_packets, max_classes=len(setups), halfrate=halfrate,
                               max_channels=max(ds.channels for ds in setups),
                               max_blocksize=max(ds.blocksizes[1] for ds in setups))
@@ -1002,14 +977,14 @@ def decode_ogg(files, max_packets=4096, halfrate=False, device_demux=False, chai
             yield md, list(range(len(demuxed)))
             return
         for members in groups.values():                   # one job per header group
-            setups.append(DecodeSetup(demuxed[members[0]][0]))
+            setups.append(DecodeSetup(demuxed[members[0]].headers))
             keep.append(Decoder(setups[-1], len(members), max_packets, halfrate=halfrate))
             yield keep[-1], members
 
     for dec, members in jobs():
         up = lambda x: torch.as_tensor(x, device=dev)     # host-demuxed arrays go up here; demuxed on the device: as is
-        src = [(up(demuxed[j][1]), demuxed[j][2], up(demuxed[j][3]), up(demuxed[j][4]),
-                None if demuxed[j][5] is None else up(demuxed[j][5])) for j in members]
+        src = [d._replace(data=up(d.data), granulepos=up(d.granulepos), eos=up(d.eos),
+                          gap=None if d.gap is None else up(d.gap)) for d in (demuxed[j] for j in members)]
         for ids, counts, data, offsets, gp, eo, ga in _calls(src, max_packets):
             pcm, run_samples, _, _ = dec.synthesis_runs(ids, counts, data, torch.from_numpy(offsets).to(dev),
                                                         granulepos=gp, eos=eo, gap=ga)

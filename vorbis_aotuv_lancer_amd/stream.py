@@ -3,10 +3,12 @@ vorbis_analysis_headerout (reference lib/info.c:636-717) and libogg's ogg_stream
 (page format: reference doc/framing.html) over the C ABI of include/vorbis_mi355x.h.  OggStream / write_ogg page one
 stream on the host; OggMux pages every stream of an encoder at once on the device (vbm_ogg_mux_*)."""
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
 from ._lib import lib, check, VbmError
+from ._twin import HOST, Layout, _TwinHandle, ptr, size
 
 
 def header_packets(setup, comments=(), vendor=None):
@@ -164,8 +166,8 @@ class OggMux:
         out, offsets, status = self._ring[self._ring_at]
         self._ring_at = (self._ring_at + 1) % 3
         stride = int(packets.stride(0)) if n and packets.dim() == 2 else self.max_packet_bytes
-        check(lib.vbm_ogg_mux_packets(self._h, packets.data_ptr() if n else None, stride, nbytes.data_ptr() if n else None,
-                                      dinfo.data_ptr() if n else None, n, 1 if flush else 0, out.data_ptr(), out.numel(),
+        check(lib.vbm_ogg_mux_packets(self._h, ptr(packets, n), stride, ptr(nbytes, n), ptr(dinfo, n), n,
+                                      1 if flush else 0, out.data_ptr(), out.numel(),
                                       offsets.data_ptr(), status.data_ptr(), C.c_void_p(self._stream())),
               "vbm_ogg_mux_packets")
         self._keep = (dinfo, packets, nbytes)
@@ -183,10 +185,9 @@ class OggMux:
         out = np.empty(self.out_bound(n), np.uint8)
         offsets = np.zeros(self.nstreams + 1, np.int64)
         status = np.zeros(self.nstreams + 1, np.int32)
-        check(lib.vbm_host_ogg_mux_packets(self._hh, pk.ctypes.data if n else None, pk.shape[1] if n else self.max_packet_bytes,
-                                           nb.ctypes.data if n else None, rec.ctypes.data if n else None, n,
-                                           1 if flush else 0, out.ctypes.data, len(out), offsets.ctypes.data,
-                                           status.ctypes.data), "vbm_host_ogg_mux_packets")
+        check(lib.vbm_host_ogg_mux_packets(self._hh, ptr(pk, n), pk.shape[1] if n else self.max_packet_bytes, ptr(nb, n),
+                                           ptr(rec, n), n, 1 if flush else 0, out.ctypes.data, len(out),
+                                           offsets.ctypes.data, status.ctypes.data), "vbm_host_ogg_mux_packets")
         return out[:offsets[-1]], offsets, status
 
     def close(self):
@@ -284,64 +285,43 @@ def _split3(h, sizes, at=0):
     return [h[at:at + a], h[at + a:at + a + b], h[at + a + b:at + a + b + c]]
 
 
-def _join(blobs, device=None):
-    """[bytes] -> (raw uint8 [all of them end to end], offsets int64 [n + 1]); raw goes to `device` in one copy if one is
-    given, and is a numpy array otherwise"""
-    off = np.zeros(len(blobs) + 1, np.int64)
-    np.cumsum([len(b) for b in blobs], out=off[1:])
-    raw = np.frombuffer(b"".join(blobs), np.uint8)
-    if device is not None:
-        import torch
-        raw = torch.from_numpy(raw.copy()).to(device) if len(raw) else torch.empty(0, dtype=torch.uint8, device=device)
-    return raw, off
+# one demuxed file or link, as demux_ogg returns it, with the gap marks of a resync demux (None from any other) behind
+Entry = namedtuple("Entry", "headers data offsets granulepos eos gap")
 
 
-def _csr_buffers(P, B, device=None):
-    """-> (payload uint8 [B], offsets int64 [P + 1], granulepos int64 [P], eos uint8 [P]) for a fill: torch tensors on
-    `device`, or numpy arrays without one"""
-    if device is None:
-        return np.zeros(B, np.uint8), np.zeros(P + 1, np.int64), np.zeros(P, np.int64), np.zeros(P, np.uint8)
-    import torch
-    return (torch.empty(B, dtype=torch.uint8, device=device), torch.empty(P + 1, dtype=torch.int64, device=device),
-            torch.empty(P, dtype=torch.int64, device=device), torch.empty(P, dtype=torch.uint8, device=device))
-
-
-class _TwinHandle:
-    """The handle of a C object that comes as a device form (made under its device, destroyed after a synchronize) and a
-    host twin: vbm_[host_]ogg_<kind>_create(&h, *args) and vbm_ogg_<kind>_destroy(h)."""
+class _OggTwin(_TwinHandle):
+    """A vbm_[host_]ogg_<kind> object, and the two halves of a demux call that the batch demuxers and the feed share"""
 
     def __init__(self, kind, host, device, *args, create="create"):
-        self.host, self.device, self._h = bool(host), None, C.c_void_p()
-        self._destroy = getattr(lib, f"vbm_ogg_{kind}_destroy")
-        name = f"vbm_host_ogg_{kind}_{create}" if host else f"vbm_ogg_{kind}_{create}"
-        if host:
-            check(getattr(lib, name)(C.byref(self._h), *args), name)
-        else:
-            import torch
-            self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-            with torch.cuda.device(self.device):
-                check(getattr(lib, name)(C.byref(self._h), *args), name)
+        self._destroy = f"vbm_ogg_{kind}_destroy"
+        self._create(f"ogg_{kind}_{create}", host, device, *args)
 
-    def _q(self):
-        """the current stream of the device; None for the host twin"""
-        if self.host:
-            return None
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _scan_meta(self, layout, *calls, zero=False):
+        """The scan half: one block of that layout where the object's buffers live, then every call (stem, args), args
+        being made from the addresses of the block's arrays ({name: address, None for an empty array}), then the block
+        brought back in one small copy -> {name: that array on the host}"""
+        block = self.mem.new(layout.size, np.uint8, zero)
+        at = layout.ptrs(block)
+        for stem, args in calls:
+            self._call(stem, *args(at))
+        return layout.views(self.mem.host(block))
 
-    def close(self):
-        if self._h:
-            if not self.host:
-                import torch
-                torch.cuda.synchronize(self.device)
-            self._destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _fill_csr(self, stem, P, B, H=None, gap=False, status=None):
+        """The fill half, with buffers of the sizes the scan returned: vbm_[host_]<stem>([headers, H,] payload, B, offsets,
+        granulepos, eos, [gap,] P) -> (the header bytes, payload, offsets, granulepos, eos, gap); the first is None
+        without H and the last without gap.  With H the header bytes come back in one copy, which waits for the fill, and
+        then the status word vbm_<status> is read: it is 0 with buffers of these sizes."""
+        hdr = None if H is None else self.mem.new(H, np.uint8)
+        payload, offsets, gp, eos = self.mem.csr(P, B)
+        marks = self.mem.new(P, np.uint8) if gap else None
+        self._call(stem, *((ptr(hdr, H), H) if H is not None else ()), ptr(payload, B), B, ptr(offsets), ptr(gp, P),
+                   ptr(eos, P), *((ptr(marks, P),) if gap else ()), P)
+        if H is not None:
+            hdr = self.mem.host(hdr).tobytes()            # waits for the fill: the input is free after it
+            st = self._status(status)
+            if st:
+                raise VbmError(f"vbm_{stem}: status {st} with buffers of the sizes the scan returned")
+        return hdr, payload, offsets, gp, eos, marks
 
 
 def demux_ogg(data):
@@ -354,8 +334,8 @@ def demux_ogg(data):
     sizes = (C.c_long * 5)()
     check(lib.vbm_ogg_demux(buf, len(raw), sizes, None, None, None, None, None), "vbm_ogg_demux")
     hdr = np.zeros(max(1, sizes[0] + sizes[1] + sizes[2]), np.uint8)
-    body, offsets, gp, eos = _csr_buffers(sizes[3], sizes[4])
-    check(lib.vbm_ogg_demux(buf, len(raw), sizes, hdr.ctypes.data, body.ctypes.data if len(body) else None,
+    body, offsets, gp, eos = HOST.csr(sizes[3], sizes[4])
+    check(lib.vbm_ogg_demux(buf, len(raw), sizes, hdr.ctypes.data, ptr(body, len(body)),
                             offsets.ctypes.data, gp.ctypes.data, eos.ctypes.data), "vbm_ogg_demux")
     return _split3(hdr.tobytes(), sizes), body, offsets, gp, eos
 
@@ -363,6 +343,11 @@ def demux_ogg(data):
 FILE_INFO = np.dtype([("status", "<i4"), ("pages", "<i4"), ("serialno", "<u4"), ("header_bytes", "<i4", (3,)),
                       ("packets", "<i8"), ("payload_bytes", "<i8"), ("packet_base", "<i8"), ("payload_base", "<i8"),
                       ("header_base", "<i8")])       # vbm_ogg_file_info
+
+
+def demux_meta(n):
+    """what vbm_ogg_demux_scan returns for n files, in one block"""
+    return Layout(totals=(np.int64, 3), info=(FILE_INFO, n))
 
 
 def _read_files(files):
@@ -421,7 +406,7 @@ class DemuxBatch:
         return self.gap[a:a + n]
 
 
-class DeviceDemuxer(_TwinHandle):
+class DeviceDemuxer(_OggTwin):
     """vbm_ogg_demux for many whole .ogg files per call, on the device (vbm_ogg_demux_scan / _fill): up to max_files
     files of up to max_bytes bytes together per demux() call.
 
@@ -440,52 +425,23 @@ class DeviceDemuxer(_TwinHandle):
 
     def demux(self, files):
         names, blobs = _read_files(files)
-        return self.demux_joined(names, *_join(blobs, self.device))
+        return self.demux_joined(names, *self.mem.join(blobs))
 
     def demux_joined(self, names, raw, off):
         """demux() of files that already lie in one buffer: raw uint8 (a tensor on the device; a numpy array with
         host=True), entry i in raw[off[i]:off[i + 1]], off int64 numpy [n + 1]"""
         off = np.ascontiguousarray(off, np.int64)
         n = len(off) - 1
-        if self.host:
-            info, totals = np.zeros(n, FILE_INFO), np.zeros(3, np.int64)
-            check(lib.vbm_host_ogg_demux_scan(self._h, n, raw.ctypes.data if len(raw) else None, off.ctypes.data,
-                                              info.ctypes.data if n else None, totals.ctypes.data),
-                  "vbm_host_ogg_demux_scan")
-            P, B, H = (int(x) for x in totals)
-            hdr = np.zeros(H, np.uint8)
-            payload, offsets, gp, eos = _csr_buffers(P, B)
-            check(lib.vbm_host_ogg_demux_fill(self._h, hdr.ctypes.data if H else None, H, payload.ctypes.data if B else None,
-                                              B, offsets.ctypes.data, gp.ctypes.data if P else None,
-                                              eos.ctypes.data if P else None, P), "vbm_host_ogg_demux_fill")
-            st = C.c_int(-1)
-            check(lib.vbm_ogg_demux_status(self._h, C.byref(st), None), "vbm_ogg_demux_status")
-            h = hdr.tobytes()
-        else:
-            import torch
-            dev, q = self.device, self._q()
-            # info and totals in one buffer: one small D2H
-            d_meta = torch.empty(n * FILE_INFO.itemsize + 24, dtype=torch.uint8, device=dev)
-            check(lib.vbm_ogg_demux_scan(self._h, n, raw.data_ptr() if len(raw) else None, off.ctypes.data,
-                                         d_meta.data_ptr() + 24 if n else None, d_meta.data_ptr(), q), "vbm_ogg_demux_scan")
-            meta = d_meta.cpu().numpy()
-            totals, info = meta[:24].view(np.int64), meta[24:].view(FILE_INFO)
-            P, B, H = (int(x) for x in totals)
-            d_hdr = torch.empty(H, dtype=torch.uint8, device=dev)
-            payload, offsets, gp, eos = _csr_buffers(P, B, dev)
-            check(lib.vbm_ogg_demux_fill(self._h, d_hdr.data_ptr() if H else None, H, payload.data_ptr() if B else None, B,
-                                         offsets.data_ptr(), gp.data_ptr() if P else None, eos.data_ptr() if P else None, P,
-                                         q), "vbm_ogg_demux_fill")
-            h = d_hdr.cpu().numpy().tobytes()              # waits for the fill: raw is free after it
-            st = C.c_int(-1)
-            check(lib.vbm_ogg_demux_status(self._h, C.byref(st), q), "vbm_ogg_demux_status")
-        if st.value:
-            raise VbmError(f"vbm_ogg_demux_fill: status {st.value} with buffers of the sizes the scan returned")
+        meta = self._scan_meta(demux_meta(n), ("ogg_demux_scan", lambda at: (
+            n, ptr(raw, len(raw)), off.ctypes.data, at["info"], at["totals"])))
+        P, B, H = (int(x) for x in meta["totals"])
+        h, payload, offsets, gp, eos, _ = self._fill_csr("ogg_demux_fill", P, B, H, status="ogg_demux_status")
+        info = meta["info"]
         headers = [None if fi["status"] else _split3(h, fi["header_bytes"], int(fi["header_base"])) for fi in info]
         return DemuxBatch(names, info, headers, payload, offsets, gp, eos)
 
 
-class ChainSplitter(_TwinHandle):
+class ChainSplitter(_OggTwin):
     """Where the links of chained .ogg files start, for up to max_files files of up to max_bytes bytes together per
     split() call, on the device (vbm_ogg_chain_split; the rule: csrc/ogg_chain.h).  host=True runs the CPU twin on numpy
     arrays (no GPU needed).  The split never fails: what does not parse stays with the last link found, for the demux
@@ -507,29 +463,18 @@ class ChainSplitter(_TwinHandle):
         n = len(off) - 1
         cap = 2 * n + 62 if link_cap is None else int(link_cap)
         for attempt in range(2):
-            st = C.c_int(-1)
-            if self.host:
-                out = np.zeros(n + cap + 2, np.int64)
-                check(lib.vbm_host_ogg_chain_split(self._h, n, raw.ctypes.data if len(raw) else None, off.ctypes.data,
-                                                   out.ctypes.data, out.ctypes.data + 8 * (n + 1), cap),
-                      "vbm_host_ogg_chain_split")
-                check(lib.vbm_ogg_chain_status(self._h, C.byref(st), None), "vbm_ogg_chain_status")
-            else:
-                import torch
-                q = self._q()
-                # file_links and link_offsets in one buffer: one small D2H
-                d_out = torch.empty(n + cap + 2, dtype=torch.int64, device=self.device)
-                check(lib.vbm_ogg_chain_split(self._h, n, raw.data_ptr() if len(raw) else None, off.ctypes.data,
-                                              d_out.data_ptr(), d_out.data_ptr() + 8 * (n + 1), cap, q), "vbm_ogg_chain_split")
-                out = d_out.cpu().numpy()
-                check(lib.vbm_ogg_chain_status(self._h, C.byref(st), q), "vbm_ogg_chain_status")
+            # file_links and link_offsets in one buffer: one small D2H
+            out = self.mem.new(n + cap + 2, np.int64)
+            self._call("ogg_chain_split", n, ptr(raw, len(raw)), off.ctypes.data, ptr(out), ptr(out) + 8 * (n + 1), cap)
+            out = self.mem.host(out)
+            st = self._status("ogg_chain_status")
             total = int(out[n])
-            if st.value == 0:
+            if st == 0:
                 return out[:n + 1].copy(), out[n + 1:n + total + 2].copy()
-            if st.value != self.ECAP or attempt:
+            if st != self.ECAP or attempt:
                 break
             cap = total
-        raise VbmError(f"vbm_ogg_chain_split: status {st.value} with room for the {total} links it counted")
+        raise VbmError(f"vbm_ogg_chain_split: status {st} with room for the {total} links it counted")
 
 
 def split_ogg_chain(data):
@@ -537,11 +482,8 @@ def split_ogg_chain(data):
     not the file's first starts a link, and a file without one is its own one link.  On the host; needs no GPU.  The
     split never fails: each link is judged when it is demuxed (demux_ogg)."""
     raw = bytes(data)
-    sp = ChainSplitter(1, len(raw), host=True)
-    try:
+    with ChainSplitter(1, len(raw), host=True) as sp:
         _, lo = sp.split(np.frombuffer(raw, np.uint8), np.array([0, len(raw)], np.int64))
-    finally:
-        sp.close()
     return [raw[int(a):int(b)] for a, b in zip(lo[:-1], lo[1:])]
 
 
@@ -549,7 +491,12 @@ RESYNC_EVENTS = np.dtype([("links_started", "<i4"), ("links_bad", "<i4"), ("gaps
                           ("ignored_pages", "<i8"), ("pages", "<i8")])       # vbm_ogg_resync_events
 
 
-class ResyncDemuxer(_TwinHandle):
+def resync_meta(n, cap):
+    """what vbm_ogg_resync_scan returns for n files with room for cap entries, in one block"""
+    return Layout(totals=(np.int64, 6), links=(np.int64, n + 1), events=(RESYNC_EVENTS, n), info=(FILE_INFO, cap))
+
+
+class ResyncDemuxer(_OggTwin):
     """The tolerant demux of many whole .ogg files per call, damaged, chained or both, on the device
     (vbm_ogg_resync_scan / _fill; the rule: csrc/ogg_resync.h): what the resync feed delivers from each file pushed whole.
 
@@ -573,28 +520,13 @@ class ResyncDemuxer(_TwinHandle):
 
     def demux(self, files):
         names, blobs = _read_files(files)
-        return self.demux_joined(names, *_join(blobs, self.device))
+        return self.demux_joined(names, *self.mem.join(blobs))
 
     def _scan(self, n, raw, off, cap):
         """one scan with room for cap entries -> (totals [6], file_links [n + 1], events [n], info [cap]) on the host"""
-        nl, ne = 8 * (n + 1), n * RESYNC_EVENTS.itemsize
-        size = 48 + nl + ne + cap * FILE_INFO.itemsize
-        if self.host:
-            meta = np.zeros(size, np.uint8)
-            p = meta.ctypes.data
-            check(lib.vbm_host_ogg_resync_scan(self._h, n, raw.ctypes.data if len(raw) else None, off.ctypes.data,
-                                               p + 48 + nl if n else None, p + 48, p + 48 + nl + ne if cap else None, cap,
-                                               p), "vbm_host_ogg_resync_scan")
-        else:
-            import torch
-            d_meta = torch.zeros(size, dtype=torch.uint8, device=self.device)      # info, events, links and totals: one D2H
-            p = d_meta.data_ptr()
-            check(lib.vbm_ogg_resync_scan(self._h, n, raw.data_ptr() if len(raw) else None, off.ctypes.data,
-                                          p + 48 + nl if n else None, p + 48, p + 48 + nl + ne if cap else None, cap, p,
-                                          self._q()), "vbm_ogg_resync_scan")
-            meta = d_meta.cpu().numpy()
-        return (meta[:48].view(np.int64), meta[48:48 + nl].view(np.int64).copy(),
-                meta[48 + nl:48 + nl + ne].view(RESYNC_EVENTS).copy(), meta[48 + nl + ne:].view(FILE_INFO))
+        meta = self._scan_meta(resync_meta(n, cap), ("ogg_resync_scan", lambda at: (
+            n, ptr(raw, len(raw)), off.ctypes.data, at["events"], at["links"], at["info"], cap, at["totals"])), zero=True)
+        return meta["totals"], meta["links"].copy(), meta["events"].copy(), meta["info"]
 
     def demux_joined(self, names, raw, off, entry_cap=None):
         """demux() of files that already lie in one buffer: raw uint8 (a tensor on the device; a numpy array with
@@ -616,29 +548,7 @@ class ResyncDemuxer(_TwinHandle):
                 cap = int(totals[0])
         E, P, B, H = (int(x) for x in totals[:4])
         info = info[:E].copy()
-        st = C.c_int(-1)
-        if self.host:
-            hdr, gap = np.zeros(H, np.uint8), np.zeros(P, np.uint8)
-            payload, offsets, gp, eos = _csr_buffers(P, B)
-            check(lib.vbm_host_ogg_resync_fill(self._h, hdr.ctypes.data if H else None, H, payload.ctypes.data if B else None,
-                                               B, offsets.ctypes.data, gp.ctypes.data if P else None,
-                                               eos.ctypes.data if P else None, gap.ctypes.data if P else None, P),
-                  "vbm_host_ogg_resync_fill")
-            check(lib.vbm_ogg_resync_status(self._h, C.byref(st), None), "vbm_ogg_resync_status")
-            h = hdr.tobytes()
-        else:
-            import torch
-            dev, q = self.device, self._q()
-            d_hdr = torch.empty(H, dtype=torch.uint8, device=dev)
-            gap = torch.empty(P, dtype=torch.uint8, device=dev)
-            payload, offsets, gp, eos = _csr_buffers(P, B, dev)
-            check(lib.vbm_ogg_resync_fill(self._h, d_hdr.data_ptr() if H else None, H, payload.data_ptr() if B else None, B,
-                                          offsets.data_ptr(), gp.data_ptr() if P else None, eos.data_ptr() if P else None,
-                                          gap.data_ptr() if P else None, P, q), "vbm_ogg_resync_fill")
-            h = d_hdr.cpu().numpy().tobytes()              # waits for the fill: raw is free after it
-            check(lib.vbm_ogg_resync_status(self._h, C.byref(st), q), "vbm_ogg_resync_status")
-        if st.value:
-            raise VbmError(f"vbm_ogg_resync_fill: status {st.value} with buffers of the sizes the scan returned")
+        h, payload, offsets, gp, eos, gap = self._fill_csr("ogg_resync_fill", P, B, H, gap=True, status="ogg_resync_status")
         entry_names = [f"{names[f]} link {k}" for f in range(n) for k in range(int(file_links[f + 1] - file_links[f]))]
         headers = [_split3(h, fi["header_bytes"], int(fi["header_base"])) for fi in info]
         return DemuxBatch(entry_names, info, headers, payload, offsets, gp, eos, file_links, gap, events)
@@ -650,16 +560,13 @@ def demux_ogg_resync(data):
     eos uint8 [P], gap uint8 [P]), audio packet k of the link in data[offsets[k]:offsets[k + 1]], and the file's
     RESYNC_EVENTS record.  Never fails: a file with nothing to deliver gives no link."""
     raw = bytes(data)
-    rd = ResyncDemuxer(1, len(raw), host=True)
-    try:
+    with ResyncDemuxer(1, len(raw), host=True) as rd:
         b = rd.demux([raw])
-    finally:
-        rd.close()
     links = []
     for e in b.links(0):
         offs, gp, eos = b.runs(e)
         a, z = int(offs[0]), int(offs[-1])
-        links.append((b.headers[e], b.payload[a:z].copy(), offs - a, gp.copy(), eos.copy(), b.gaps(e).copy()))
+        links.append(Entry(b.headers[e], b.payload[a:z].copy(), offs - a, gp.copy(), eos.copy(), b.gaps(e).copy()))
     return links, b.events[0]
 
 
@@ -667,7 +574,12 @@ SELECT_INFO = np.dtype([("kept_bytes", "<i8"), ("kept_pages", "<i8"), ("foreign_
                         ("foreign_streams", "<i4"), ("first_serial", "<u4"), ("reserved", "<i4")])   # vbm_ogg_select_info
 
 
-class StreamSelector(_TwinHandle):
+def select_meta(n):
+    """what vbm_ogg_select returns for n files beside the bytes it keeps, in one block"""
+    return Layout(out_off=(np.int64, n + 1), info=(SELECT_INFO, n))
+
+
+class StreamSelector(_OggTwin):
     """The Vorbis stream of multiplexed .ogg files (Theora, Skeleton, Kate ... pages between the audio's), for up to
     max_files files of up to max_bytes bytes together per select() call, on the device (vbm_ogg_select; the rule:
     csrc/ogg_select.h): the pages of the first Vorbis stream of every group are copied, whole and in order, to a second
@@ -689,22 +601,11 @@ class StreamSelector(_TwinHandle):
         off = np.ascontiguousarray(off, np.int64)
         n = len(off) - 1
         cap = int(off[n] - off[0])                       # the input's size always suffices: the status stays 0
-        nb = 8 * (n + 1)
-        if self.host:
-            out, meta = np.zeros(cap, np.uint8), np.zeros(nb + n * SELECT_INFO.itemsize, np.uint8)
-            check(lib.vbm_host_ogg_select(self._h, n, raw.ctypes.data if len(raw) else None, off.ctypes.data,
-                                          out.ctypes.data if cap else None, cap, meta.ctypes.data,
-                                          meta.ctypes.data + nb if n else None), "vbm_host_ogg_select")
-        else:
-            import torch
-            out = torch.empty(cap, dtype=torch.uint8, device=self.device)
-            d_meta = torch.empty(nb + n * SELECT_INFO.itemsize, dtype=torch.uint8, device=self.device)
-            check(lib.vbm_ogg_select(self._h, n, raw.data_ptr() if len(raw) else None, off.ctypes.data,
-                                     out.data_ptr() if cap else None, cap, d_meta.data_ptr(),
-                                     d_meta.data_ptr() + nb if n else None, self._q()), "vbm_ogg_select")
-            meta = d_meta.cpu().numpy()
-        out_off, info = meta[:nb].view(np.int64).copy(), meta[nb:].view(SELECT_INFO).copy()
-        return out[:int(out_off[n])], out_off, info
+        out = self.mem.new(cap, np.uint8)
+        meta = self._scan_meta(select_meta(n), ("ogg_select", lambda at: (
+            n, ptr(raw, len(raw)), off.ctypes.data, ptr(out, cap), cap, at["out_off"], at["info"])))
+        out_off = meta["out_off"].copy()
+        return out[:int(out_off[n])], out_off, meta["info"].copy()
 
 
 def select_vorbis_stream(data):
@@ -712,11 +613,8 @@ def select_vorbis_stream(data):
     group of a chained file; a plain Vorbis file comes back as it is, and a file without a Vorbis stream as b"".  On the
     host; needs no GPU.  The selection never fails: what it returns is judged when it is demuxed (demux_ogg)."""
     raw = bytes(data)
-    sel = StreamSelector(1, len(raw), host=True)
-    try:
+    with StreamSelector(1, len(raw), host=True) as sel:
         out, _, _ = sel.select(np.frombuffer(raw, np.uint8), np.array([0, len(raw)], np.int64))
-    finally:
-        sel.close()
     return out.tobytes()
 
 
@@ -735,45 +633,30 @@ def demux_ogg_device(files, host=False, chained=False, multiplexed=False, resync
     if resync and multiplexed:
         raise ValueError("demux_ogg_device: resync=True with multiplexed=True is not built")
     names, blobs = _read_files(files)
-    nbytes = sum(len(b) for b in blobs)
+    nfiles, nbytes = max(1, len(blobs)), sum(len(b) for b in blobs)
     if resync:
-        rd = ResyncDemuxer(max(1, len(blobs)), nbytes, host=host)
-        try:
-            return rd.demux_joined(names, *_join(blobs, rd.device))
-        finally:
-            rd.close()
+        with ResyncDemuxer(nfiles, nbytes, host=host) as rd:
+            return rd.demux_joined(names, *rd.mem.join(blobs))
     if not chained and not multiplexed:
-        dm = DeviceDemuxer(max(1, len(blobs)), nbytes, host=host)
-        try:
+        with DeviceDemuxer(nfiles, nbytes, host=host) as dm:
             return dm.demux(blobs)
-        finally:
-            dm.close()
     device, select_info, file_links = None, None, None
     raw = None
     if multiplexed:
-        sel = StreamSelector(max(1, len(blobs)), nbytes, host=host)
-        try:
+        with StreamSelector(nfiles, nbytes, host=host) as sel:
             device = sel.device
-            raw, off = _join(blobs, device)
+            raw, off = sel.mem.join(blobs)
             raw, off, select_info = sel.select(raw, off)     # the D2H waits for the copy: the upload is free after it
-        finally:
-            sel.close()
     entry_names, entry_off = names, None if raw is None else off
     if chained:
-        sp = ChainSplitter(max(1, len(blobs)), nbytes, host=host, device=device)
-        try:
+        with ChainSplitter(nfiles, nbytes, host=host, device=device) as sp:
             device = sp.device
             if raw is None:
-                raw, off = _join(blobs, device)
+                raw, off = sp.mem.join(blobs)
             file_links, entry_off = sp.split(raw, off)
-        finally:
-            sp.close()
         entry_names = [f"{names[f]} link {k}" for f in range(len(blobs)) for k in range(int(file_links[f + 1] - file_links[f]))]
-    dm = DeviceDemuxer(max(1, len(entry_names)), nbytes, host=host, device=device)
-    try:
+    with DeviceDemuxer(max(1, len(entry_names)), nbytes, host=host, device=device) as dm:
         b = dm.demux_joined(entry_names, raw, entry_off)
-    finally:
-        dm.close()
     if chained:
         b.file_links = file_links
     b.select_info = select_info
@@ -787,6 +670,11 @@ FEED_INFO = np.dtype([("status", "<i4"), ("headers_ready", "<i4"), ("header_byte
 
 FEED_EVENTS = np.dtype([("link", "<i4"), ("link_started", "<i4"), ("link_bad", "<i4"), ("gaps", "<i4"),
                         ("skipped_bytes", "<i8"), ("ignored_pages", "<i8"), ("left", "<i8")])    # vbm_ogg_feed_events
+
+
+def feed_meta(n, resync):
+    """what vbm_ogg_feed_scan, and from a resync feed vbm_ogg_feed_scan_events, return for n slots, in one block"""
+    return Layout(totals=(np.int64, 2), info=(FEED_INFO, n), events=(FEED_EVENTS, n if resync else 0))
 
 
 class FeedResult:
@@ -813,7 +701,7 @@ class FeedResult:
         return len(self.ids)
 
 
-class OggFeed(_TwinHandle):
+class OggFeed(_OggTwin):
     """The Ogg demux for live streams (vbm_ogg_feed_scan / _fill): max_streams slots, each fed the next bytes of its
     stream, cut anywhere, up to max_call_bytes bytes per push() over all slots.
 
@@ -868,58 +756,26 @@ class OggFeed(_TwinHandle):
             blobs = [bytes(c) for c in chunks]
             if len(blobs) != n:
                 raise ValueError("one chunk per id")
-            raw, off = _join(blobs, self.device)
+            raw, off = self.mem.join(blobs)
         else:
             raw, off = chunks, np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
             if len(off) != n + 1:
                 raise ValueError("offsets must have len(ids) + 1 entries")
         flags = np.ascontiguousarray(np.broadcast_to(np.asarray(end, dtype=np.uint8), (n,)))
-        if self.host:
-            info, totals = np.zeros(n, FEED_INFO), np.zeros(2, np.int64)
-            check(lib.vbm_host_ogg_feed_scan(self._h, n, ids.ctypes.data, raw.ctypes.data if len(raw) else None,
-                                             off.ctypes.data, flags.ctypes.data, info.ctypes.data if n else None,
-                                             totals.ctypes.data), "vbm_host_ogg_feed_scan")
-            P, B = int(totals[0]), int(totals[1])
-            payload, offs, gp, eos = _csr_buffers(P, B)
-            if not self.resync:
-                check(lib.vbm_host_ogg_feed_fill(self._h, payload.ctypes.data if B else None, B, offs.ctypes.data,
-                                                 gp.ctypes.data if P else None, eos.ctypes.data if P else None, P),
-                      "vbm_host_ogg_feed_fill")
-                return FeedResult(ids, info, payload, offs, gp, eos)
-            events, gap = np.zeros(n, FEED_EVENTS), np.zeros(P, np.uint8)
-            check(lib.vbm_host_ogg_feed_scan_events(self._h, events.ctypes.data if n else None),
-                  "vbm_host_ogg_feed_scan_events")
-            check(lib.vbm_host_ogg_feed_fill_gaps(self._h, payload.ctypes.data if B else None, B, offs.ctypes.data,
-                                                  gp.ctypes.data if P else None, eos.ctypes.data if P else None,
-                                                  gap.ctypes.data if P else None, P), "vbm_host_ogg_feed_fill_gaps")
-            return FeedResult(ids, info, payload, offs, gp, eos, gap, events)
-        import torch
-        dev, q = self.device, self._q()
-        with torch.cuda.device(dev):
-            # totals, infos and (resync) events in one buffer: one small D2H
-            ni, ne = n * FEED_INFO.itemsize, n * FEED_EVENTS.itemsize if self.resync else 0
-            d_meta = torch.empty(16 + ni + ne, dtype=torch.uint8, device=dev)
-            check(lib.vbm_ogg_feed_scan(self._h, n, ids.ctypes.data, raw.data_ptr() if raw.numel() else None, off.ctypes.data,
-                                        flags.ctypes.data, d_meta.data_ptr() + 16 if n else None, d_meta.data_ptr(), q),
-                  "vbm_ogg_feed_scan")
-            if self.resync:
-                check(lib.vbm_ogg_feed_scan_events(self._h, d_meta.data_ptr() + 16 + ni if n else None, q),
-                      "vbm_ogg_feed_scan_events")
-            meta = d_meta.cpu().numpy()
-            totals, info = meta[:16].view(np.int64), meta[16:16 + ni].view(FEED_INFO)
-            P, B = int(totals[0]), int(totals[1])
-            payload, offs, gp, eos = _csr_buffers(P, B, dev)
+        scans = [("ogg_feed_scan", lambda at: (n, ids.ctypes.data, ptr(raw, size(raw)), off.ctypes.data, flags.ctypes.data,
+                                               at["info"], at["totals"]))]
+        if self.resync:
+            scans.append(("ogg_feed_scan_events", lambda at: (at["events"],)))
+        with self.mem.scope():
+            meta = self._scan_meta(feed_meta(n, self.resync), *scans)
+            P, B = int(meta["totals"][0]), int(meta["totals"][1])
             # the buffers have the sizes the scan returned: this fill cannot fall short, so its status word is not waited for
-            if not self.resync:
-                check(lib.vbm_ogg_feed_fill(self._h, payload.data_ptr() if B else None, B, offs.data_ptr(),
-                                            gp.data_ptr() if P else None, eos.data_ptr() if P else None, P, q),
-                      "vbm_ogg_feed_fill")
-                return FeedResult(ids, info.copy(), payload, offs, gp, eos)
-            gap = torch.empty(P, dtype=torch.uint8, device=dev)
-            check(lib.vbm_ogg_feed_fill_gaps(self._h, payload.data_ptr() if B else None, B, offs.data_ptr(),
-                                             gp.data_ptr() if P else None, eos.data_ptr() if P else None,
-                                             gap.data_ptr() if P else None, P, q), "vbm_ogg_feed_fill_gaps")
-        return FeedResult(ids, info.copy(), payload, offs, gp, eos, gap, meta[16 + ni:].view(FEED_EVENTS).copy())
+            _, payload, offs, gp, eos, gap = self._fill_csr("ogg_feed_fill_gaps" if self.resync else "ogg_feed_fill", P, B,
+                                                            gap=self.resync)
+        return FeedResult(ids, meta["info"], payload, offs, gp, eos, gap, meta["events"] if self.resync else None)
+
+
+
 
     @staticmethod
     def _again(r, flags):
@@ -958,11 +814,7 @@ class OggFeed(_TwinHandle):
             a, b = off[1:][keep] - r.left[keep], off[1:][keep]
             noff = np.concatenate([[0], np.cumsum(b - a)]).astype(np.int64)
             idx = np.concatenate([np.arange(x, y) for x, y in zip(a, b)])
-            if self.host:
-                chunks = np.ascontiguousarray(chunks[idx])
-            else:
-                import torch
-                chunks = chunks[torch.from_numpy(idx).to(chunks.device)]
+            chunks = chunks[self.mem.upload(idx)]           # indexing with an array gathers, on the host as on the device
             ids, flags, off = ids[keep], flags[keep], noff
 
     def headers(self, id):
@@ -995,7 +847,7 @@ def header_pages(headers, serialno):
         os_.close()
 
 
-class OggCutter(_TwinHandle):
+class OggCutter(_OggTwin):
     """Sample windows of indexed streams as new Ogg Vorbis files with the packets left as they are (vbm_ogg_cut_*; the
     rule and the refusals: csrc/ogg_cut.h), for up to max_ranges windows, max_out_bytes output bytes and
     max_header_bytes of header pages per cut() call.  The device form cuts from a decoder.RangeStore and only enqueues
@@ -1026,28 +878,21 @@ class OggCutter(_TwinHandle):
         sets, hid = {}, np.zeros(n, np.int32)
         for r, p in enumerate(header_pages):              # the distinct sets, in the order they first appear
             hid[r] = sets.setdefault(p, len(sets))
-        hdr, hoff = _join(list(sets))
+        hdr, hoff = HOST.join(list(sets))
         got_s, got_l = np.zeros(n, np.int64), np.zeros(n, np.int64)
-        cap = 0 if out is None else int(out.numel() if not self.host else out.size)
-        tail = (n, ids.ctypes.data, st.ctypes.data, ln.ctypes.data, None if sn is None else sn.ctypes.data, len(sets),
-                hdr.ctypes.data if len(hdr) else None, hoff.ctypes.data, hid.ctypes.data)
+        cap = 0 if out is None else int(size(out))
+        off, stat = self.mem.new(n + 1, np.int64), self.mem.new(n + 1, np.int32)
+        tail = (n, ids.ctypes.data, st.ctypes.data, ln.ctypes.data, ptr(sn), len(sets), ptr(hdr, len(hdr)), hoff.ctypes.data,
+                hid.ctypes.data, ptr(out, cap), cap, ptr(off), ptr(stat), got_s.ctypes.data, got_l.ctypes.data)
+        # the two forms differ in more than the stream here: the host twin takes the index as arrays, the device form a
+        # store's handle (and its stream, which _call adds only behind a twin's own arguments)
         if self.host:
             first, status, begin, out_end, totals, data, offsets = src
             first, out_end, totals, offsets = (np.ascontiguousarray(a, np.int64) for a in (first, out_end, totals, offsets))
             status, begin = np.ascontiguousarray(status, np.int32), np.ascontiguousarray(begin, np.int32)
             data = np.ascontiguousarray(data, np.uint8)
-            off, stat = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int32)
-            check(lib.vbm_host_ogg_cut_ranges(self._h, len(first) - 1, first.ctypes.data, status.ctypes.data,
-                                              begin.ctypes.data, out_end.ctypes.data, totals.ctypes.data,
-                                              data.ctypes.data if len(data) else None, offsets.ctypes.data, len(data),
-                                              *tail, out.ctypes.data if cap else None, cap, off.ctypes.data,
-                                              stat.ctypes.data, got_s.ctypes.data, got_l.ctypes.data),
-                  "vbm_host_ogg_cut_ranges")
+            self._call("ogg_cut_ranges", len(first) - 1, first.ctypes.data, status.ctypes.data, begin.ctypes.data,
+                       out_end.ctypes.data, totals.ctypes.data, ptr(data, len(data)), offsets.ctypes.data, len(data), *tail)
         else:
-            import torch
-            off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-            stat = torch.empty(n + 1, dtype=torch.int32, device=self.device)
-            check(lib.vbm_ogg_cut_ranges(self._h, src._h, *tail, out.data_ptr() if cap else None, cap, off.data_ptr(),
-                                         stat.data_ptr(), got_s.ctypes.data, got_l.ctypes.data, self._q()),
-                  "vbm_ogg_cut_ranges")
+            self._call("ogg_cut_ranges", src._h, *tail, self._q())
         return off, stat, got_s, got_l
