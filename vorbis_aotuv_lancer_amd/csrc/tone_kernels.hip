@@ -10,14 +10,17 @@
 //            `seed[j] <= seed[j-d]` (d = 1..6): both only between lines less than eighth_octave_lines (8) apart,
 //            because the walk pops an entry only while it lies within that distance of the current line
 //            (lib/psy.c:864-868).  One thread per line evaluates them once — 13 float compares — into two bytes.
-//   chase    seed_chase's stack walk (lib/psy.c:851-881) on those bytes.  An entry further than 7 lines back can
-//            never be popped again, so the walk's whole state is a 7-bit mask "line i-k is still on the stack"
-//            (the stack itself is the set of surviving lines; an entry's amplitude is its seed).  One lane walks
-//            16 lines of run-in with the state "nothing poppable" assumed at the start (state updates only), then
-//            its 64 own lines; a lane's state at its first own line is then checked against what its left
-//            neighbour arrived at, and a lane that guessed wrong re-runs from the true state until all agree
-//            (lane 0 starts from the true empty stack, so the fixed point is the serial walk's result; re-runs are
-//            rare).  A line's fate is final when it leaves the 7-line window: for the last seven lines of a chunk
+//   chase    seed_chase's stack walk (lib/psy.c:851-881) on those bytes (tone_chase.h).  An entry further than 7
+//            lines back can never be popped again, so the walk's whole state is two 7-bit masks: m, "line i-k is
+//            still on the stack" (the stack itself is the set of surviving lines; an entry's amplitude is its seed),
+//            and L, "that entry is not above the entry below it", which is fixed when the entry is pushed because the
+//            stack is LIFO.  A line's pops are then one prefix operation on the masks: no loop, no branch, the same
+//            straight-line step in every lane.  One lane walks 16 lines of run-in from the state (0, 0), "nothing
+//            poppable" (state updates only), then its 64 own lines; a lane's state at its first own line (m and the L
+//            bits of the entries in m) is then checked against what its left neighbour arrived at, and a lane that
+//            guessed wrong re-runs from the true state until all agree (lane 0 starts from the true empty stack, so
+//            the fixed point is the serial walk's result; re-runs are rare but for rows of equal seeds, where they
+//            cascade).  A line's fate is final when it leaves the 7-line window: for the last seven lines of a chunk
 //            that happens in the right neighbour's first seven steps, which hands the seven bits left with one
 //            shuffle (no lane walks past its chunk).  Integer operations on registers only.
 //   fill     the tail of seed_chase (lib/psy.c:1012-1026): one wavefront per block, one lane per line: a surviving
@@ -39,6 +42,7 @@
 #include <mutex>
 #include "batch.h"
 #include "kernels.h"
+#include "tone_chase.h"
 
 #define NEGINF -9999.f
 #define VMIN(x, y) ((x) > (y) ? (y) : (x))
@@ -53,98 +57,6 @@ __device__ __forceinline__ int seed_key(float f)
     return v ^ ((v >> 31) & 0x7fffffff);   // monotone float -> int (involution)
 }
 __device__ __forceinline__ float seed_val(int k) { return __int_as_float(k ^ ((k >> 31) & 0x7fffffff)); }
-
-// One line of seed_chase's walk (lib/psy.c:851-881) on the mask machine: pop while the new seed is not below the top
-// (ge) and the top is not above the entry below it (le, from H: byte b = LE of line i-1-b), both within reach (inside
-// the 7-bit window).  Returns the mask before the line itself is pushed: its bit 6 is the final fate of line i-7.
-__device__ __forceinline__ unsigned chase_pop(unsigned m, const unsigned long long H, const unsigned ge)
-{
-    for (;;) {
-        const unsigned m2 = m & (m - 1);
-        if (!m2) break;
-        const int k0 = __ffs((int)m) - 1, k1 = __ffs((int)m2) - 1;
-        const unsigned c1 = (ge >> k0) & 1u;
-        const unsigned c2 = (unsigned)(H >> (8 * k0 + (k1 - k0 - 1))) & 1u;
-        if (!(c1 & c2)) break;
-        m = m2;
-    }
-    return m;
-}
-
-// One chase lane: run-in lines [i, own), then its own lines [own, oend], starting with window mask m (bit b: line
-// i-1-b is on the stack).  gl[j] = GE | LE << 8 of line j.  i and own are multiples of 4 (four lines per LDS read).
-//   m_own / m_next  the mask at the start of lines own and oend + 1
-//   alive           final fate of the own lines the walk itself sees leave the window: own .. oend - 7, and for the
-//                   last chunk of a row (`last`) also the lines it ended on top of
-//   left7           bit t: final fate of line own - 7 + t, the left neighbour's last seven lines.  They sit in this
-//                   walk's mask at its first line and leave the window in its first seven steps, so once m_own has been
-//                   checked against the neighbour's m_next they are the truth and the neighbour need not walk on
-//                   past its chunk to learn them.
-// The run-in loop only carries the state; the own loop collects bit 6 of every step into F (bit t: line own + t - 7),
-// a nibble per LDS read: alive = F >> 7, left7 = F & 0x7f.
-__device__ __forceinline__ void chase_run(const unsigned short *__restrict__ gl, int i, unsigned m, const int own, const int oend,
-                                          const bool last, unsigned long long &alive, unsigned &left7, unsigned &m_own,
-                                          unsigned &m_next)
-{
-    unsigned long long H = 0;               // byte b: LE of line i-1-b
-#pragma unroll
-    for (int b = 0; b < 7; b++) {
-        const int q = i - 1 - b;
-        if (q >= 0) H |= (unsigned long long)(gl[q] >> 8) << (8 * b);
-    }
-    for (; i < own; i += 4) {
-        const unsigned long long g4 = *(const unsigned long long *)(gl + i);
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const unsigned g = (unsigned)(g4 >> (16 * u)) & 0xffffu;
-            m = chase_pop(m, H, g & 0xffu);
-            m = ((m << 1) | 1u) & 0x7fu;
-            H = (H << 8) | (g >> 8);
-        }
-    }
-    m_own = m;
-    unsigned long long F = 0;
-    for (; i + 3 <= oend; i += 4) {
-        const unsigned long long g4 = *(const unsigned long long *)(gl + i);
-        unsigned nb = 0;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const unsigned g = (unsigned)(g4 >> (16 * u)) & 0xffffu;
-            m = chase_pop(m, H, g & 0xffu);
-            nb |= ((m >> 6) & 1u) << u;
-            m = ((m << 1) | 1u) & 0x7fu;
-            H = (H << 8) | (g >> 8);
-        }
-        F |= (unsigned long long)nb << (i - own);
-    }
-    if (i <= oend) {                        // the last chunk's one to three lines past a multiple of four
-        const unsigned long long g4 = *(const unsigned long long *)(gl + i);
-        unsigned nb = 0;
-#pragma unroll
-        for (int u = 0; u < 3; u++) {
-            if (i + u <= oend) {
-                const unsigned g = (unsigned)(g4 >> (16 * u)) & 0xffffu;
-                m = chase_pop(m, H, g & 0xffu);
-                nb |= ((m >> 6) & 1u) << u;
-                m = ((m << 1) | 1u) & 0x7fu;
-                H = (H << 8) | (g >> 8);
-            }
-        }
-        F |= (unsigned long long)nb << (i - own);
-    }
-    m_next = m;
-    alive = F >> 7;
-    left7 = (unsigned)F & 0x7fu;
-    if (last) {
-#pragma unroll
-        for (int b = 0; b < 7; b++) {       // lines the walk ended on top of (a chunk of fewer than seven lines: the
-            const int q = oend - b - own;   // left neighbour's too)
-            const unsigned bit = (m >> b) & 1u;
-            if (q >= 0) alive |= (unsigned long long)bit << q;
-            else left7 |= bit << (q + 7);
-        }
-    }
-}
 
 // TM_NB channel-blocks per workgroup, 32 threads per block
 template <int TM_NB>
@@ -277,21 +189,22 @@ __global__ __launch_bounds__(TM_NB * 32) void k_tonemask(vbm_batch b, const int 
         const bool active = blk < nblk && own < tn;
         const unsigned short *gl = glS + blk * glp;
         unsigned long long alive = 0;
-        unsigned m_own = 0, m_next = 0, used = 0, left7 = 0;
+        unsigned m_own = 0, L_own = 0, m_next = 0, L_next = 0, used = 0, left7 = 0;
         const int oend = own + 63 < tn - 1 ? own + 63 : tn - 1;
         const bool last = own + 64 >= tn;                      // the last chunk of the row: no right neighbour
         if (active) {
             const int i0 = own >= runin ? own - runin : 0;     // runin: multiple of 4
-            chase_run(gl, i0, 0u, own, oend, last, alive, left7, m_own, m_next);
-            used = m_own;
+            chase_run(gl, i0, 0u, 0u, own, oend, last, alive, left7, m_own, L_own, m_next, L_next);
+            used = m_own | ((L_own & m_own) << 8);
         }
-        // a lane whose assumed state differs from what its left neighbour arrived at runs again from the true one
+        // a lane whose assumed state differs from what its left neighbour arrived at runs again from the true one.  The
+        // state is m and the L bits of the entries on the stack (an L bit beside a clear m bit means nothing), one word
         for (;;) {
-            const unsigned truth = __shfl_up(m_next, 1);
+            const unsigned truth = __shfl_up(m_next | ((L_next & m_next) << 8), 1);
             const bool redo = active && c > 0 && truth != used;
             if (!__any(redo)) break;
             if (redo) {
-                chase_run(gl, own, truth, own, oend, last, alive, left7, m_own, m_next);
+                chase_run(gl, own, truth & 0x7fu, truth >> 8, own, oend, last, alive, left7, m_own, L_own, m_next, L_next);
                 used = truth;
             }
         }
