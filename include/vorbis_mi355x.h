@@ -1233,6 +1233,10 @@ int  vbm_host_live_store_snapshot(const vbm_range_store *st, long long *first, i
  *                            enum vbm_delay_point); process-wide; usec = 0 switches it off
  *   vbm_debug_poison_workspace  fills the scratch arrays of encoder workspace w (-1: all) with `byte`, device idle
  *   vbm_debug_poison_frontend   the same for the front end's block buffers, search spectra and round lists
+ *   vbm_debug_frontend_buffers  where every stream's samples lie, once the front end's stream has drained: base, parity,
+ *                            pcm_current [S]; shift [2 + S]: the compaction list's count (0 between rounds), the count of
+ *                            the newest round that shifted, that round's list; live (may be NULL) [S][ch][live_stride]:
+ *                            the pcm_current samples of every channel buffer from the stream's origin on
  * Some launchers take another kernel, or another slicing of the same kernel, once a batch is large (csrc/batch.h,
  * "kernel variants chosen by batch size").  vbm_debug_batch_variants says which forms a batch of `nsb` stream-blocks of
  * `ch` channels takes, from the launchers' own predicates; block_mode 0..3, n = blocksize / 2, few: the batch is a
@@ -1247,6 +1251,8 @@ int vbm_debug_set_delay(unsigned mask, int usec);
 unsigned vbm_debug_batch_variants(int block_mode, int n, int ch, int nsb, int few);
 int vbm_debug_poison_workspace(vbm_encoder *enc, int w, int byte);
 int vbm_debug_poison_frontend(vbm_frontend *fe, int byte);
+int vbm_debug_frontend_buffers(vbm_frontend *fe, int *base, int *parity, int *pcm_current, int *shift, float *live,
+                               long long live_stride);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,9 @@ struct vbm_batch {
     const uint8_t *wflags;          // [nsb] bit0 = lW, bit1 = nW (vb->lW, vb->nW)
     // block-major transform interface
     const float *pcm;               // [ncb][N] un-windowed block PCM
+    const long long *pcm_off;       // NULL, or (big batch of a device-built round) the transforms read the blocks where they
+    long pcm_cap;                   //   lie: [nsb] float offsets, block (sb, c) at pcm_at + pcm_off[sb] + c * pcm_cap
+    const float *pcm_at;            //   (mdct_kernel.h: vbm_block_src); `pcm` is then read by nobody (no type-2 blocks)
     float *mdct_bm;                 // [ncb][n]
     float *logfft_bm;               // [ncb][n]
     uint16_t *qf_bm;                // [ncb][n]  floor fit input: dBquant(logmask) | (logmdct+twofitatten >= logmask) << 15

@@ -41,6 +41,7 @@ struct vbm_encoder {
                              // the short rounds of the front end run on while a big batch still holds its workspace)
     vbm_batch bw[kMaxWS];
     int *d_stream_id[kMaxWS];
+    long long *d_src_ws = nullptr;            // [kMaxWS][Ls] block origins in the front end's buffers (device-built rounds)
     uint8_t *d_wflags[kMaxWS];
     int cur = 0;             // workspace of the last call (vbm_encoder_fetch)
     int next = 0;            // workspace of the next call
@@ -552,6 +553,7 @@ static void configure(vbm_encoder *e, vbm_batch &b, int block_mode, int nsb, con
     b.L = e->L;      // fixed leading dimensions: buffers were sized for `cap`
     b.Ls = e->Ls;
     b.pcm = d_pcm;
+    b.pcm_off = nullptr; b.pcm_cap = 0; b.pcm_at = nullptr;
     b.blobno = VBM_PACKETBLOBS / 2;
     b.fit_max_posts = 2;
     for (int c = 0; c < e->ch; c++) {
@@ -698,15 +700,17 @@ static int launch_transforms(vbm_encoder *e, const vbm_batch &v, hipStream_t q, 
     const vbm_setup *d = vbm_setup_device_ptrs(e->H);
     const int W = v.W, short_n = e->hs->blocksizes[0];
     const uint8_t *wf = W ? v.wflags_cb : nullptr;
+    const vbm_block_src lying = {v.pcm_off, v.pcm_at, v.pcm_cap, e->ch};
+    const vbm_block_src *direct = v.pcm_off ? &lying : nullptr;
     RUN(vbm_launch_spread_flags(&v, q));
     {
         stage_scope t(e, timed, 0, q);
         RUN(vbm_launch_window_mdct(v.pcm, v.mdct_bm, wf, d->mdct_trig[W], d->window[W], d->window[0], v.N, short_n, 1, v.ncb,
-                                   0, v.d_nsb, e->ch, q));
+                                   0, v.d_nsb, e->ch, direct, q));
     }
     stage_scope t(e, timed, 1, q);
     RUN(vbm_launch_window_fft_log(v.pcm, v.logfft_bm, v.local_ampmax, wf, d->fft_wa[W], d->window[W], d->window[0], v.N,
-                                  short_n, v.ncb, v.d_nsb, e->ch, q));
+                                  short_n, v.ncb, v.d_nsb, e->ch, direct, q));
     return VBM_OK;
 }
 
@@ -871,6 +875,7 @@ struct type_job {
     int lane0, bound;            // first stream-block lane of the type's region; blocks in it (d_nsb set: the most it may hold)
     const int *d_nsb;            // device-resident count (rounds built on the device) or NULL
     const float *pcm;            // the region's block PCM [bound][ch][N]
+    vbm_block_src direct = {};   // off set: the transforms read the blocks in the front end's buffers instead (off: lane 0's)
     uint8_t *d_packets;          // outputs of this type, already offset (may be NULL)
     int *d_packet_bytes;
     bool big = false, timed = false;
@@ -899,6 +904,7 @@ static vbm_batch job_batch(vbm_encoder *e, const type_job &j)
     configure(e, full, j.m, j.bound, j.pcm, j.w);
     vbm_batch v = slice_of(full, j.lane0, j.bound);
     v.pcm = j.pcm;
+    if (j.direct.off) { v.pcm_off = j.direct.off + j.lane0; v.pcm_at = j.direct.pcm; v.pcm_cap = j.direct.cap; }
     v.d_nsb = j.d_nsb;
     v.few = j.few;
     return v;
@@ -1108,8 +1114,8 @@ static int analysis_round_impl(vbm_encoder *e, const int *counts, const int *str
 // [lane0[m], lane0[m] + cap[m]) of workspace w, its kernels are launched for cap[m] blocks and read the count from
 // d_count[m].  Order of a stream's blocks: every batch begun earlier may hold the block before one of this round's
 // and is waited for (its state event; a finished batch costs nothing) wherever the block types allow the succession.
-int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, int **d_stream_id, uint8_t **d_wflags, int *lanes,
-                                  int **d_counts)
+int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, int **d_stream_id, uint8_t **d_wflags,
+                                  long long **d_src, int *lanes, int **d_counts)
 {
     int rc = vbm_encoder_set_sub_batches(e, e->nsplit);
     if (rc) return rc;
@@ -1152,6 +1158,14 @@ int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, 
         // (null-stream fill: the front end's non-blocking stream would not wait for it)
         if (hipMemset(e->d_counts_ws, 0, kMaxWS * 4 * sizeof(int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return VBM_EHIP;
     }
+    if (!e->d_src_ws) {     // where the blocks of every lane lie in the front end's buffers: one list per workspace
+        const size_t bytes = (size_t)kMaxWS * e->Ls * sizeof(long long);
+        if (hipMalloc((void **)&e->d_src_ws, bytes) != hipSuccess) return VBM_EHIP;
+        e->allocs.push_back(e->d_src_ws);
+        e->alloc_bytes.push_back(bytes);
+        if (hipMemset(e->d_src_ws, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return VBM_EHIP;
+    }
+    *d_src = e->d_src_ws + (size_t)w * e->Ls;
     *w_out = w;
     *d_stream_id = e->d_stream_id[w];
     *d_wflags = e->d_wflags[w];
@@ -1212,8 +1226,21 @@ static int run_piece(vbm_encoder *e, vbm_encoder::round_graph &g, hipStream_t q,
 // take from bw[w]: every one an allocation of workspace w alone, none of the carried stream state (vbm_batch::st).
 // Workspace w is free by then: vbm_encoder_device_round_open has made `fork` wait for the done events of every batch
 // that ran in it, before the round was planned, and ev_fork comes after that on the same stream.
+//
+// The big batch's transforms have no gathered copy (big_direct): they read their blocks in the front end's channel
+// buffers, at the offsets k_fe_round_commit left in the workspace's list (parity and origin as the decision saw them;
+// the transforms read neither parity[] nor base[]).  They run on `fork`, the front end's own stream, and everything
+// that could change a sample of those blocks is enqueued on that stream behind them: the round's shift and flip, the
+// next write's append, the next round.  And none of it would, even beside them: an append writes past pcm_current,
+// which lies behind every block carved so far; the shift writes the stream's other buffer, so the start of the buffer
+// a block lies in is rewritten two compactions later at the earliest; extrapolation, finish and restart enter through
+// fe_enter and stream order like everything else.  Only this form qualifies: a small batch's transforms and the long
+// blocks of a call's later rounds run on other streams beside the shift, a transition block's PCM is read again
+// behind the state waits (k_prologue), and the plain-launch form runs the big batch's transforms on sub[4]; all of
+// those keep the gather (vbm_encoder_device_round_direct tells the front end which form the next round takes).
 static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, const int *cap, const float *d_blocks,
-                                   uint8_t *d_packets, int *d_packet_bytes, bool first_round, hipStream_t fork)
+                                   const vbm_block_src *big_direct, uint8_t *d_packets, int *d_packet_bytes,
+                                   bool first_round, hipStream_t fork)
 {
     hipError_t err;
     const int *d_count = e->d_counts_ws + 4 * w;
@@ -1244,7 +1271,8 @@ static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, cons
         // half of the batch before.  (On sub[3], which carries no job in a first round, they measured no gain:
         // profiles/transforms_ahead.)
         hipStream_t qT = fork, qF = e->sub[4], qB = e->sub[5];
-        const type_job j = job_of(3);
+        type_job j = job_of(3);
+        if (big_direct) j.direct = *big_direct;
         vbm_debug_delay_point(VBM_DP_DEV_BIG_TRANSFORMS, qT);
         if ((rc = run_piece(e, e->gJ[w][4][kTransforms], qT, j, kTransforms))) return rc;
         if ((err = hipEventRecord(e->ev_tf_big[w], qT)) != hipSuccess ||
@@ -1296,9 +1324,22 @@ static int device_round_run_graphs(vbm_encoder *e, int w, const int *lane0, cons
     return VBM_OK;
 }
 
+// replayed graphs or plain launches (stage timing needs the plain launches: events between the kernels; a
+// managed-bitrate back half writes the chosen packets straight to the caller's buffers, which change from call to call)
+static int device_round_mode(const vbm_encoder *e) { return (!e->profiling && !e->hs->managed) ? 1 : 2; }
+
+// The big batch's transforms read the front end's buffers only where they run on the front end's own stream, ahead of
+// its shift: the replayed form.  The plain form runs them on sub[4], beside the shift, and keeps the gathered copy; so
+// do setups whose long blocks are not 2048 samples (4096 at q < 0: the one size the kernels have the direct form for
+// is the one where a wavefront owns a block in both of them).
+bool vbm_encoder_device_round_direct(const vbm_encoder *e)
+{
+    return device_round_mode(e) == 1 && e->hs->blocksizes[1] == 2048;
+}
+
 int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const int *cap, const int *d_count,
-                                 const float *d_blocks, uint8_t *d_packets, int *d_packet_bytes, bool first_round,
-                                 hipStream_t fork)
+                                 const float *d_blocks, const vbm_block_src *big_direct, uint8_t *d_packets,
+                                 int *d_packet_bytes, bool first_round, hipStream_t fork)
 {
     const vbm_setup *s = e->hs;
     hipError_t err;
@@ -1306,9 +1347,8 @@ int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const 
     for (int m = 0; m < 4; m++)
         if (cap[m] < 0 || (lane0[m] & 63) || lane0[m] + cap[m] > e->Ls || (cap[m] && s->modes < 2 && (m >> 1))) return VBM_EINVAL;
     if (d_count != e->d_counts_ws + 4 * w) return VBM_EINVAL;
-    // Stage timing needs the plain launches (events between the kernels); a managed-bitrate back half writes the
-    // chosen packets straight to the caller's buffers, which change from call to call: plain launches as well.
-    const int mode = (!e->profiling && !s->managed) ? 1 : 2;
+    const int mode = device_round_mode(e);
+    if (big_direct && (!vbm_encoder_device_round_direct(e) || !first_round || !big_direct->off)) return VBM_EINVAL;
     if (e->device_mode && e->device_mode != mode) {
         // The two ways use different internal streams: everything in flight is waited for at the switch.  The flags
         // stay: a set flag only costs a later wait for an event that has fired by then, and the plain form's depmask
@@ -1316,7 +1356,7 @@ int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const 
         if ((rc = wait_slots(e, fork, e->reuse_pending, any_slot, false))) return rc;
     }
     e->device_mode = mode;
-    if (mode == 1) return device_round_run_graphs(e, w, lane0, cap, d_blocks, d_packets, d_packet_bytes, first_round, fork);
+    if (mode == 1) return device_round_run_graphs(e, w, lane0, cap, d_blocks, big_direct, d_packets, d_packet_bytes, first_round, fork);
     if ((err = hipEventRecord(e->ev_fork, fork)) != hipSuccess) return vbm_set_hip_error(err, "hipEventRecord");
     e->last_nsb = 0;
     // every slot that may still be running, except this round's own

@@ -135,6 +135,7 @@ extern "C" int vbm_frontend_create(vbm_frontend **out, vbm_encoder *enc)
     A(f.parity, int, S);
     A(f.base, int, S);
     A(f.overflow, int, 1);
+    A(f.shift_list, int, S); A(f.shift_n, int, 2);
     A(f.pcm_current, int, S); A(f.centerW, int, S); A(f.lW, int, S); A(f.W, int, S); A(f.nW, int, S);
     A(f.eofflag, int, S); A(f.preextrapolate, int, S);
     A(f.granulepos, long long, S); A(f.sequence, long long, S);
@@ -198,6 +199,7 @@ extern "C" int vbm_frontend_reset(vbm_frontend *fe)
     zero(f.parity, S * sizeof(int));
     zero(f.base, S * sizeof(int));
     zero(f.overflow, sizeof(int));
+    zero(f.shift_n, 2 * sizeof(int));
     zero(f.lW, S * sizeof(int)); zero(f.W, S * sizeof(int)); zero(f.nW, S * sizeof(int));
     zero(f.eofflag, S * sizeof(int)); zero(f.preextrapolate, S * sizeof(int));
     zero(f.granulepos, S * sizeof(long long));
@@ -772,7 +774,8 @@ extern "C" int vbm_frontend_encode_rounds_device(vbm_frontend *fe, int nrounds, 
         int w, ws_lanes;
         int *d_sid, *counts_ws;
         uint8_t *d_wf;
-        rc = vbm_encoder_device_round_open(fe->enc, q, &w, &d_sid, &d_wf, &ws_lanes, &counts_ws);
+        long long *d_src;
+        rc = vbm_encoder_device_round_open(fe->enc, q, &w, &d_sid, &d_wf, &d_src, &ws_lanes, &counts_ws);
         if (rc) return rc;
         if (ws_lanes < fe->lanes) {
             g_vbm_err = "encoder workspace too small for rounds built on the device: create it with max_batch >= vbm_device_round_lanes()";
@@ -798,21 +801,28 @@ extern "C" int vbm_frontend_encode_rounds_device(vbm_frontend *fe, int nrounds, 
         R.stream_id = d_sid;
         R.wflags = d_wf;
         R.begin = fe->d_begin_lane;
+        R.src = d_src;
         R.info = d_info + (size_t)r * fe->lanes;
         R.stats = fe->d_stats;
         vbm_debug_delay_point(VBM_DP_DEV_PLAN, q);
         if (vbm_fe_launch_round_plan(&fe->f, ds, &R, fe->d_type, fe->d_dec, bytes_r, fe->lanes, q)) return VBM_EHIP;
         if ((err = hipMemcpyAsync(counts_r, counts_ws, 4 * sizeof(int), hipMemcpyDeviceToDevice, q)) != hipSuccess)
             return vbm_set_hip_error(err, "hipMemcpyAsync(counts)");
+        // The long blocks of a call's first round (its big batch) are not copied: their transforms run on this very
+        // stream, ahead of the shift, and read the blocks where they lie (R.src).  Every other job keeps its gather:
+        // its transforms run on another stream beside the shift, and a transition block's PCM is read again behind
+        // the state waits (k_prologue).
+        const vbm_block_src direct = {d_src, fe->f.pcm, fe->f.cap, ch};
+        const bool big_direct = r == 0 && caps[3] > 0 && vbm_encoder_device_round_direct(fe->enc);
         for (int m = 0; m < 4; m++) {
-            if (!caps[m]) continue;
+            if (!caps[m] || (m == 3 && big_direct)) continue;
             const int N = (m >> 1) ? bs1 : bs0;
             if (vbm_fe_launch_gather(&fe->f, d_sid + fe->lane0[m], fe->d_begin_lane + fe->lane0[m], caps[m], N,
                                      blocks + (size_t)fe->lane0[m] * ch * bs1, counts_ws + m, q))
                 return VBM_EHIP;
         }
         vbm_debug_stamp(q, 2 + (r ? 1 : 0));
-        rc = vbm_encoder_device_round_run(fe->enc, w, fe->lane0, caps, counts_ws, blocks,
+        rc = vbm_encoder_device_round_run(fe->enc, w, fe->lane0, caps, counts_ws, blocks, big_direct ? &direct : nullptr,
                                           d_packets ? d_packets + (size_t)r * fe->lanes * maxb : nullptr, bytes_r, r == 0, q);
         if (rc) return rc;
         vbm_debug_delay_point(VBM_DP_FE_SHIFT, q);
@@ -867,6 +877,38 @@ extern "C" int vbm_debug_poison_frontend(vbm_frontend *fe, int byte)
         return vbm_set_hip_error(err, "hipMemset(poison)");
     err = hipDeviceSynchronize();
     return err == hipSuccess ? VBM_OK : vbm_set_hip_error(err, "hipDeviceSynchronize");
+}
+
+// Test instrumentation: where every stream's samples lie, once the front end's stream has drained.  base, parity,
+// pcm_current: [S]; shift: [2 + S] the compaction list's count (0 between rounds), the count of the newest round that
+// shifted, and that round's list; live (may be NULL): [S][ch][live_stride] the pcm_current samples of every channel
+// buffer from the stream's origin on.
+extern "C" int vbm_debug_frontend_buffers(vbm_frontend *fe, int *base, int *parity, int *pcm_current, int *shift,
+                                          float *live, long long live_stride)
+{
+    if (!fe || !base || !parity || !pcm_current || !shift) return VBM_EINVAL;
+    const vbm_fe_state &f = fe->f;
+    const int S = fe->S;
+    hipError_t err;
+    if ((err = hipStreamSynchronize(fe->q)) != hipSuccess ||
+        (err = hipMemcpy(base, f.base, S * sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess ||
+        (err = hipMemcpy(parity, f.parity, S * sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess ||
+        (err = hipMemcpy(pcm_current, f.pcm_current, S * sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess ||
+        (err = hipMemcpy(shift, f.shift_n, 2 * sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess ||
+        (err = hipMemcpy(shift + 2, f.shift_list, S * sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess)
+        return vbm_set_hip_error(err, "hipMemcpy(front end buffers)");
+    if (!live) return VBM_OK;
+    for (int s = 0; s < S; s++) {
+        if (pcm_current[s] < 0 || pcm_current[s] > live_stride || base[s] + (long)pcm_current[s] > f.cap) return VBM_EINVAL;
+        for (int c = 0; c < fe->ch; c++) {
+            const long sc = (long)s * fe->ch + c;
+            if (pcm_current[s] &&
+                (err = hipMemcpy(live + sc * live_stride, f.pcm + (long)parity[s] * f.plane + sc * f.cap + base[s],
+                                 pcm_current[s] * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess)
+                return vbm_set_hip_error(err, "hipMemcpy(front end samples)");
+        }
+    }
+    return VBM_OK;
 }
 
 extern "C" int vbm_frontend_join(vbm_frontend *fe, void *stream)

@@ -464,13 +464,15 @@ template <int N> struct fft_run<N, false> {
     }
 };
 
-template <int N>
+// DIRECT: block blk lies in the front end's channel buffers (mdct_kernel.h: vbm_block_src; pcm is unused).  A wavefront
+// owns a block, so its address is wave-uniform: scalar division, scalar load of the table entry.
+template <int N, bool DIRECT = false>
 __global__ __launch_bounds__(64 * fft_waves<N>::value) __attribute__((amdgpu_waves_per_eu(N == 4096 ? 1 : 3)))
 void k_window_fft_log(const float *__restrict__ pcm, float *__restrict__ logfft,
                       float *__restrict__ local_ampmax, const uint8_t *__restrict__ wflags,
                       const float *__restrict__ wa_g,      // FFTPACK twiddles, N floats (trigcache + N)
                       const float *__restrict__ win_self, const float *__restrict__ win_short,
-                      int short_n, long nblocks, const int *__restrict__ d_live, int live_mult)
+                      int short_n, long nblocks, const int *__restrict__ d_live, int live_mult, vbm_block_src direct)
 {
     if (d_live) {
         const long live = (long)*d_live * live_mult;
@@ -506,7 +508,13 @@ void k_window_fft_log(const float *__restrict__ pcm, float *__restrict__ logfft,
             if (!(f & 1)) { ln = short_n; wl = s_wshort; }
             if (!(f & 2)) { rn = short_n; wr = s_wshort; }
         }
-        const float4 *src = reinterpret_cast<const float4 *>(pcm + blk * N);
+        const float *first = pcm + blk * N;
+        if (DIRECT) {
+            const int b = __builtin_amdgcn_readfirstlane((int)blk);      // (fewer than 2^31 blocks per launch)
+            const int sb = b / direct.ch;
+            first = direct.pcm + direct.off[sb] + (long)(b - sb * direct.ch) * direct.cap;
+        }
+        const float4 *src = reinterpret_cast<const float4 *>(first);
 #pragma unroll
         for (int g = 0; g < N / 256; g++) {
             int q = lane + 64 * g;
@@ -566,9 +574,12 @@ void k_window_fft_log(const float *__restrict__ pcm, float *__restrict__ logfft,
 extern "C" int vbm_launch_window_fft_log(const float *d_pcm, float *d_logfft, float *d_local_ampmax,
                                          const uint8_t *d_wflags, const float *d_wa, const float *d_win_self,
                                          const float *d_win_short, int n, int short_n, long nblocks,
-                                         const int *d_live, int live_mult, hipStream_t stream)
+                                         const int *d_live, int live_mult, const vbm_block_src *direct,
+                                         hipStream_t stream)
 {
     if (nblocks <= 0) return 0;
+    if (direct && (n != 2048 || !direct->off || !direct->pcm || direct->ch <= 0 || (direct->cap & 3) ||
+                   ((uintptr_t)direct->pcm & 15))) return -1;
     if (n != 4096 && n != 2048 && n != 1024 && n != 512 && n != 256) return -1;
     const int nw = (n == 4096) ? 2 : WAVES_PER_WG;
     long wgs = (nblocks + nw - 1) / nw;
@@ -577,8 +588,11 @@ extern "C" int vbm_launch_window_fft_log(const float *d_pcm, float *d_logfft, fl
     dim3 grid((unsigned)wgs), block(64 * nw);
 #define LAUNCH_FFT(NN)                                                                                              \
     hipLaunchKernelGGL(k_window_fft_log<NN>, grid, block, 0, stream, d_pcm, d_logfft, d_local_ampmax, d_wflags, d_wa, \
-                       d_win_self, d_win_short, short_n, nblocks, d_live, live_mult)
-    if (n == 4096) LAUNCH_FFT(4096);
+                       d_win_self, d_win_short, short_n, nblocks, d_live, live_mult, vbm_block_src{})
+    if (direct)
+        hipLaunchKernelGGL((k_window_fft_log<2048, true>), grid, block, 0, stream, direct->pcm, d_logfft, d_local_ampmax,
+                           d_wflags, d_wa, d_win_self, d_win_short, short_n, nblocks, d_live, live_mult, *direct);
+    else if (n == 4096) LAUNCH_FFT(4096);
     else if (n == 2048) LAUNCH_FFT(2048);
     else if (n == 1024) LAUNCH_FFT(1024);
     else if (n == 512) LAUNCH_FFT(512);

@@ -25,6 +25,8 @@ struct vbm_fe_state {
     int *base;                   // [S] where the stream's sample 0 sits in its channel buffers (see k_fe_shift)
     int base_max;                // the buffers are compacted once base would pass this
     int *overflow;               // [1] writes refused because a stream's buffer was full (device-built rounds: no host check)
+    int *shift_list;             // [S] the streams whose origin passes base_max with this round's decision, in any order
+    int *shift_n;                // [2] entries of shift_list (the decision counts, k_fe_flip resets); the round before's
     // vorbis_dsp_state (lib/block.c:173-344 initial values)
     int *pcm_current, *centerW, *lW, *W, *nW, *eofflag, *preextrapolate;   // [S]
     long long *granulepos, *sequence;                                      // [S]
@@ -69,6 +71,9 @@ struct vbm_fe_round {
     int *stream_id;              // [lanes]  (the encoder workspace's own list)
     uint8_t *wflags;             // [lanes]
     int *begin;                  // [lanes] first sample of the block in its stream's buffer
+    long long *src;              // [lanes] the same as a float offset into vbm_fe_state::pcm, channel 0 (channel c: + c * cap),
+                                 //         parity and origin as the decision saw them: what a transform needs to read
+                                 //         the block where it lies (mdct_kernel.h: vbm_block_src)
     vbm_packet_info *info;       // [lanes] description of every lane's block (stream = -1: none)
     unsigned long long *stats;   // [5] running totals: blocks of type 0..3, samples the streams advanced by
 };

@@ -675,6 +675,12 @@ __device__ __forceinline__ void fe_decide_one(const vbm_fe_state &f, const vbm_s
             pcm_current -= movementW;
             f.pcm_current[s] = pcm_current;
             d.movement = movementW;
+            // the origin passes base_max with this block: k_fe_shift compacts the stream (it walks this list)
+            // (a stream is listed once per round and k_fe_flip empties the list behind every round: k < S)
+            if (f.base[s] + movementW > f.base_max) {
+                const int k = atomicAdd(f.shift_n, 1);
+                if (k < S) f.shift_list[k] = s;
+            }
 
             f.lW[s] = W;
             f.W[s] = nW;
@@ -789,6 +795,8 @@ __global__ void k_fe_round_commit(vbm_fe_state f, const vbm_setup *__restrict__ 
         r.stream_id[slot] = s;
         r.wflags[slot] = (uint8_t)(d.lW | (d.nW << 1));
         r.begin[slot] = d.beginW;
+        // (parity and origin change in k_fe_flip only, behind this round's transforms and gathers)
+        r.src[slot] = (long long)f.parity[s] * f.plane + (long long)s * f.ch * f.cap + f.base[s] + d.beginW;
         vbm_packet_info pi;
         pi.stream = s; pi.block_mode = d.block_mode; pi.lW = d.lW; pi.W = d.W; pi.nW = d.nW; pi.eos = d.eos;
         pi.granulepos = d.granulepos; pi.packetno = d.sequence;
@@ -832,25 +840,36 @@ __global__ void k_fe_gather(vbm_fe_state f, const int *__restrict__ ids, const i
 
 // every stream whose decision of this round moved its window on: the origin moves up by the same amount; once it
 // has passed base_max, the surviving samples are copied to the start of the other buffer (k_fe_flip then switches
-// the parity and resets the origin)
-__global__ void k_fe_shift(vbm_fe_state f, const vbm_fe_decision *__restrict__ dec)
+// the parity and resets the origin).  A stream compacts once per base_max samples: the decision lists those that do
+// (fe_decide_one, f.shift_list), and a grid of fixed size strides over list x channels x quarters of the copy,
+// 16 bytes per thread and step.
+constexpr int FE_SHIFT_SLICES = 4;
+constexpr unsigned FE_SHIFT_GRID = 2048;
+__global__ __launch_bounds__(256) void k_fe_shift(vbm_fe_state f, const vbm_fe_decision *__restrict__ dec)
 {
-    const int c = blockIdx.x;
-    const int s = c / f.ch;
-    const int mv = dec[s].movement;
-    if (mv <= 0) return;
-    const int nb = f.base[s] + mv;
-    if (nb <= f.base_max) return;
-    const int n = f.pcm_current[s];                 // already reduced by the decision
-    const int par = f.parity[s];
-    const float4 *src = reinterpret_cast<const float4 *>(f.pcm + (long)par * f.plane + (long)c * f.cap + nb);
-    float4 *dst = reinterpret_cast<float4 *>(f.pcm + (long)(par ^ 1) * f.plane + (long)c * f.cap);
-    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < (n + 3) / 4; i += gridDim.y * blockDim.x) dst[i] = src[i];
+    const int listed = f.shift_n[0] < f.S ? f.shift_n[0] : f.S;
+    const long items = (long)listed * f.ch * FE_SHIFT_SLICES;
+    for (long item = blockIdx.x; item < items; item += gridDim.x) {
+        const int y = (int)(item % FE_SHIFT_SLICES);
+        const long kc = item / FE_SHIFT_SLICES;
+        const int s = f.shift_list[kc / f.ch];
+        const long c = (long)s * f.ch + kc % f.ch;
+        const int nb = f.base[s] + dec[s].movement;     // > base_max: that is what put the stream on the list
+        const int n = f.pcm_current[s];                 // already reduced by the decision
+        const int par = f.parity[s];
+        const float4 *src = reinterpret_cast<const float4 *>(f.pcm + (long)par * f.plane + c * f.cap + nb);
+        float4 *dst = reinterpret_cast<float4 *>(f.pcm + (long)(par ^ 1) * f.plane + c * f.cap);
+        for (int i = y * blockDim.x + threadIdx.x; i < (n + 3) / 4; i += FE_SHIFT_SLICES * blockDim.x) dst[i] = src[i];
+    }
 }
 
 __global__ void k_fe_flip(vbm_fe_state f, const vbm_fe_decision *__restrict__ dec)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s == 0) {                                       // the list has been walked: empty for the next round
+        f.shift_n[1] = f.shift_n[0];
+        f.shift_n[0] = 0;
+    }
     if (s >= f.S) return;
     const int mv = dec[s].movement;
     if (mv <= 0) return;
@@ -958,7 +977,8 @@ extern "C" int vbm_fe_launch_round_plan(const vbm_fe_state *f, const vbm_setup *
 
 extern "C" int vbm_fe_launch_shift(const vbm_fe_state *f, const vbm_fe_decision *d_dec, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_fe_shift, dim3((unsigned)(f->S * f->ch), 4), dim3(256), 0, st, *f, d_dec);
+    const unsigned most = (unsigned)(f->S * f->ch * FE_SHIFT_SLICES);
+    hipLaunchKernelGGL(k_fe_shift, dim3(most < FE_SHIFT_GRID ? most : FE_SHIFT_GRID), dim3(256), 0, st, *f, d_dec);
     hipLaunchKernelGGL(k_fe_flip, dim3((unsigned)((f->S + 255) / 256)), dim3(256), 0, st, *f, d_dec);
     return CHECK_LAUNCH();
 }

@@ -81,14 +81,27 @@ __device__ __forceinline__ const float *block_src(const float *__restrict__ pcm,
     return pcm + (long)g.parity[s] * g.plane + (long)c * g.cap + g.base[s] + (long)j * 64;
 }
 
+// first sample of block `blk` in the front end's channel buffers (mdct_kernel.h: vbm_block_src).  A wavefront owns
+// one block: the address is wave-uniform (scalar division, scalar load of the table entry)
+__device__ __forceinline__ const float *direct_src(const vbm_block_src &d, long blk)
+{
+    const int b = __builtin_amdgcn_readfirstlane((int)blk);      // (fewer than 2^31 blocks per launch)
+    const int sb = b / d.ch;
+    return d.pcm + d.off[sb] + (long)(b - sb * d.ch) * d.cap;
+}
+
 // group of eight 16-B loads -> registers
 // returns whether any block of the group exists (wave-uniform): a group without one is skipped
-template <int N, bool GATHER>
+template <int N, bool GATHER, bool DIRECT>
 __device__ __forceinline__ bool issue_loads(float4 (&v)[8], const float *__restrict__ pcm,
-                                            long group, long nblocks, int lane, const vbm_ve_gather &g)
+                                            long group, long nblocks, int lane, const vbm_ve_gather &g,
+                                            const vbm_block_src &direct)
 {
     using G = Geo<N>;
+    static_assert(!DIRECT || (G::BPG == 1 && !GATHER), "direct blocks: one block per wavefront");
     bool any = false;
+    const float *whole = nullptr;       // DIRECT: the group is one block
+    if (DIRECT && group < nblocks) whole = direct_src(direct, group);
     // Gathered blocks (the envelope's search MDCTs: 16 blocks of 128 samples per group): where a block starts takes
     // two integer divisions and four loads of per-stream state; lane b resolves block b once and the eight loads of
     // a lane pick their block's address up by shuffle (each lane resolving the block of each of its loads spent
@@ -113,6 +126,8 @@ __device__ __forceinline__ bool issue_loads(float4 (&v)[8], const float *__restr
         if (GATHER) {
             const unsigned lo = (unsigned)__shfl((int)alo, b), hi = (unsigned)__shfl((int)ahi, b);
             src = reinterpret_cast<const float *>((uintptr_t)(((unsigned long long)hi << 32) | lo));
+        } else if (DIRECT) {
+            src = whole;
         } else {
             src = (blk < nblocks) ? block_src<GATHER>(pcm, blk, N, g) : nullptr;
         }
@@ -125,7 +140,7 @@ __device__ __forceinline__ bool issue_loads(float4 (&v)[8], const float *__restr
     return __any(any);
 }
 
-template <int N, bool GATHER = false>
+template <int N, bool GATHER = false, bool DIRECT = false>
 __global__ __launch_bounds__(64 * WAVES_PER_WG)
 void k_window_mdct(const float *__restrict__ pcm, float *__restrict__ out,
                    const uint8_t *__restrict__ wflags,  // per block: bit0 = lW, bit1 = nW (N == 2048 only; may be null = all long)
@@ -134,7 +149,8 @@ void k_window_mdct(const float *__restrict__ pcm, float *__restrict__ out,
                    const float *__restrict__ win_short, // rising half-window of the short size (short_n/2 floats), N == 2048 only
                    int short_n, int apply_window,       // 0 none, 1 Vorbis window (lW/nW shapes), 2 = win_self is a full N-sample table
                    long nblocks, vbm_ve_gather gather,
-                   const int *__restrict__ d_live, int live_mult)   // device-resident count: only *d_live * live_mult blocks exist
+                   const int *__restrict__ d_live, int live_mult,   // device-resident count: only *d_live * live_mult blocks exist
+                   vbm_block_src direct)                            // DIRECT: where the blocks lie (pcm is unused)
 {
     if (d_live) {
         const long live = (long)*d_live * live_mult;
@@ -170,14 +186,14 @@ void k_window_mdct(const float *__restrict__ pcm, float *__restrict__ out,
 
     float4 v[8];
     bool have = false;
-    if (group < ngroups) have = issue_loads<N, GATHER>(v, pcm, group, nblocks, lane, gather);
+    if (group < ngroups) have = issue_loads<N, GATHER, DIRECT>(v, pcm, group, nblocks, lane, gather, direct);
 
     for (; group < ngroups; group += gstride) {
         if (!have) {
             // none of the group's blocks exists (the envelope search covers 32 steps per channel and launch, a
             // 1024-sample write brings 16): nothing to transform, nothing to store
             const long nx = group + gstride;
-            have = (nx < ngroups) ? issue_loads<N, GATHER>(v, pcm, nx, nblocks, lane, gather) : false;
+            have = (nx < ngroups) ? issue_loads<N, GATHER, DIRECT>(v, pcm, nx, nblocks, lane, gather, direct) : false;
             continue;
         }
         // ---------------- window + odd-sample exchange -----------------------------
@@ -227,7 +243,7 @@ void k_window_mdct(const float *__restrict__ pcm, float *__restrict__ out,
             c[k].x = r1 * T.y + r0 * T.x;
             c[k].y = r1 * T.x - r0 * T.y;
         }
-        have = (next < ngroups) ? issue_loads<N, GATHER>(v, pcm, next, nblocks, lane, gather) : false;
+        have = (next < ngroups) ? issue_loads<N, GATHER, DIRECT>(v, pcm, next, nblocks, lane, gather, direct) : false;
         wave_lds_sync();  // exchange slots are reused below
 
         radix_rounds<G::LOG2C>(c, sx, s_trig, lane);
@@ -388,9 +404,12 @@ extern "C" int vbm_launch_window_mdct(const float *d_pcm, float *d_out, const ui
                                       const float *d_trig, const float *d_win_self,
                                       const float *d_win_short, int n, int short_n,
                                       int apply_window, long nblocks, int max_workgroups,
-                                      const int *d_live, int live_mult, hipStream_t stream)
+                                      const int *d_live, int live_mult, const vbm_block_src *direct,
+                                      hipStream_t stream)
 {
     if (nblocks <= 0) return 0;
+    if (direct && (n != 2048 || !direct->off || !direct->pcm || direct->ch <= 0 || (direct->cap & 3) ||
+                   ((uintptr_t)direct->pcm & 15))) return -1;
     if (n == 4096) {
         long wgs4 = (nblocks + WAVES_PER_WG - 1) / WAVES_PER_WG;
         if (max_workgroups <= 0) max_workgroups = 256 * 4;
@@ -401,6 +420,7 @@ extern "C" int vbm_launch_window_mdct(const float *d_pcm, float *d_out, const ui
     }
     if (n != 2048 && n != 1024 && n != 512 && n != 256) return -1;
     const vbm_ve_gather none = {};
+    const vbm_block_src rows = {};
     const int bpg = 2048 / n;
     long ngroups = (nblocks + bpg - 1) / bpg;
     long wgs = (ngroups + WAVES_PER_WG - 1) / WAVES_PER_WG;
@@ -409,8 +429,11 @@ extern "C" int vbm_launch_window_mdct(const float *d_pcm, float *d_out, const ui
     dim3 grid((unsigned)wgs), block(64 * WAVES_PER_WG);
 #define LAUNCH_MDCT(NN)                                                                                        \
     hipLaunchKernelGGL(k_window_mdct<NN>, grid, block, 0, stream, d_pcm, d_out, d_wflags, d_trig, d_win_self, \
-                       d_win_short, short_n, apply_window, nblocks, none, d_live, live_mult)
-    if (n == 2048) LAUNCH_MDCT(2048);
+                       d_win_short, short_n, apply_window, nblocks, none, d_live, live_mult, rows)
+    if (direct)
+        hipLaunchKernelGGL((k_window_mdct<2048, false, true>), grid, block, 0, stream, direct->pcm, d_out, d_wflags, d_trig,
+                           d_win_self, d_win_short, short_n, apply_window, nblocks, none, d_live, live_mult, *direct);
+    else if (n == 2048) LAUNCH_MDCT(2048);
     else if (n == 1024) LAUNCH_MDCT(1024);
     else if (n == 512) LAUNCH_MDCT(512);
     else LAUNCH_MDCT(256);
@@ -428,6 +451,6 @@ extern "C" int vbm_launch_ve_mdct(const vbm_ve_gather *g, float *d_out, const fl
     long wgs = (ngroups + WAVES_PER_WG - 1) / WAVES_PER_WG;
     if (wgs > 256 * 8) wgs = 256 * 8;
     hipLaunchKernelGGL((k_window_mdct<128, true>), dim3((unsigned)wgs), dim3(64 * WAVES_PER_WG), 0, stream, g->pcm, d_out,
-                       (const uint8_t *)nullptr, d_trig, d_win, (const float *)nullptr, 0, 2, nblocks, *g, (const int *)nullptr, 0);
+                       (const uint8_t *)nullptr, d_trig, d_win, (const float *)nullptr, 0, 2, nblocks, *g, (const int *)nullptr, 0, vbm_block_src{});
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

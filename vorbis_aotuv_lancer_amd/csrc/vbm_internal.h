@@ -15,11 +15,13 @@ vbm_setup_host *vbm_encoder_setup_host(vbm_encoder *e);            // capi_encod
 int vbm_encoder_streams(const vbm_encoder *e);
 int vbm_encoder_workspaces(const vbm_encoder *e);
 int vbm_encoder_reset_streams_dev(vbm_encoder *e, const int *d_ids, int n, hipStream_t q);
-int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, int **d_stream_id, uint8_t **d_wflags, int *lanes,
-                                  int **d_counts);
+struct vbm_block_src;                                              // mdct_kernel.h
+int vbm_encoder_device_round_open(vbm_encoder *e, hipStream_t fork, int *w_out, int **d_stream_id, uint8_t **d_wflags,
+                                  long long **d_src, int *lanes, int **d_counts);
+bool vbm_encoder_device_round_direct(const vbm_encoder *e);        // the next first round's long blocks need no gather
 int vbm_encoder_device_round_run(vbm_encoder *e, int w, const int *lane0, const int *cap, const int *d_count,
-                                 const float *d_blocks, uint8_t *d_packets, int *d_packet_bytes, bool first_round,
-                                 hipStream_t fork);
+                                 const float *d_blocks, const vbm_block_src *big_direct, uint8_t *d_packets,
+                                 int *d_packet_bytes, bool first_round, hipStream_t fork);
 struct vbm_range_store;
 struct vbm_range_store_view {          // a range store's index and device arrays, for ogg_cut.hip
     int S, halfrate;
